@@ -99,6 +99,24 @@ def synthetic_frame(seed: int) -> np.ndarray:
     return np.clip(img, 0, 255).astype(np.uint8)
 
 
+DUMP_BYTES = 48 << 20                # --dump-outputs: at most this many bytes of float32 samples
+
+
+def dump_outputs(d: str, out: np.ndarray) -> None:
+    """--dump-outputs: the upscaled frame of the last timed step as d/frame.npy, float32 sample values (0..255).  [rows, cols, 3] when it fits in
+    DUMP_BYTES; otherwise [n, 3], the pixels at n flat indices (row * cols + col) drawn without replacement by np.random.default_rng(0) and sorted -
+    the same pixels for the same frame size, so two builds' files compare element for element."""
+    os.makedirs(d, exist_ok=True)
+    px = out.reshape(-1, 3)
+    n = DUMP_BYTES // (3 * 4)
+    if px.shape[0] <= n:
+        sample = out.astype(np.float32)
+    else:
+        idx = np.sort(np.random.default_rng(0).choice(px.shape[0], n, replace=False))
+        sample = px[idx].astype(np.float32)
+    np.save(os.path.join(d, "frame.npy"), sample)
+
+
 def cpu_baseline(work: str, tile_out: int) -> dict:
     """The oracle (CPU port of the path: fp32 ONNX executor on torch-CPU kernels + numpy tile pipeline) timed on this box's host cores on a
     bounded sample of the same workload: tiles of the same graph (exported at batch 1) through the network plus their pre / post work, extrapolated
@@ -391,7 +409,8 @@ def main():
     ap.add_argument("--gpus", type=int, default=1)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
-    ap.add_argument("--repeats", type=int, default=7, help="the K-step timed region is run this many times back to back; the median region is quoted, all are listed")
+    ap.add_argument("--repeats", type=int, default=1, help="the K-step timed region is run this many times back to back; the median region is quoted, all are listed "
+                                                           "(default 1: --steps K times exactly K steps)")
     ap.add_argument("--mode", choices=["frames", "strips", "shards", "shards1p"], default="frames",
                     help="frames: every rank renders K whole frames (weak scaling, the headline); strips: rank r renders strip r of N of the same frame K times (strong scaling); "
                          "shards: one frame in N tile ranges with every tile computed once, one process per GPU, the seam bands copied out of the neighbours' slabs through IPC handles "
@@ -407,7 +426,12 @@ def main():
     ap.add_argument("--host-rehearsal", action="store_true",
                     help="the rank protocol only (spawn or launcher environment, gloo rendezvous, barriers, max-reduction, placement records, the one JSON line) with every engine "
                          "call replaced by a sleep: runs without a GPU, prints value = null and n_gpus = 0.  What tests/test_shard_gloo.py runs at 2 and 8 ranks")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the frame the last timed step computed (rank 0's) to DIR/frame.npy as float32: the whole frame when it fits in "
+                         f"{DUMP_BYTES >> 20} MB, else a fixed seeded sample of its pixels (dump_outputs)")
     a = ap.parse_args()
+    if a.dump_outputs and (a.mode != "frames" or a.host_rehearsal):
+        ap.error("--dump-outputs needs --mode frames and a GPU run")
     select_config(a.config)
 
     if a.mode == "shards1p":
@@ -511,6 +535,11 @@ def main():
         region_walls.append(shard.max_over_ranks(wall_r, dist)); region_ms.append(ms_r); region_ranks.append(shard.gather_objects(wall_r, dist))
     mid = sorted(range(len(region_walls)), key=lambda k: region_walls[k])[len(region_walls) // 2]     # the median region (upper median for even R)
     wall_max, ms, walls = region_walls[mid], region_ms[mid], region_ranks[mid]
+    last_out = None
+    if a.dump_outputs and rank == 0:         # the frame the last timed step left on the device, read back before anything else renders
+        last_out = np.empty_like(out)
+        if not eng.resident_output(last_out):
+            raise SystemExit("reading the resident output failed: " + eng.last_error())
 
     # ---- the same K frames through the whole render() contract (host buffer in, host buffer out), copies overlapped on side
     # streams (renderSequence over page-locked buffers, a ring of 3 output frames); every rank, same barriers, max over ranks
@@ -675,6 +704,8 @@ def main():
         }
         if not a.no_cpu_baseline and world == 1 and (a.config == 3 or a.cpu_baseline):
             line["cpu_baseline"] = cpu_baseline(a.work, eng.output_tile_size)
+        if last_out is not None:
+            dump_outputs(a.dump_outputs, last_out)
         print(json.dumps(line), file=json_out, flush=True)
     json_out.close()
     eng.close()

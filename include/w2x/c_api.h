@@ -97,6 +97,8 @@ double w2x_plan_flops(w2x_engine* e);   /* algorithmic FLOP of one network pass 
 int w2x_pass_tiles(w2x_engine* e);      /* tiles per network pass (batchSize x super-batch factor) */
 float w2x_last_render_ms(w2x_engine* e);
 float w2x_bench_resident(w2x_engine* e, int iters);
+/* the output frame the last w2x_bench_resident step left in device memory -> dst (bytes = rows*s * cols*s * 3 samples) */
+int w2x_resident_output(w2x_engine* e, void* dst, size_t bytes);
 /* out[5*k+{0,1,2}] = {ms, launches, algorithmic FLOP} for k = 0 gemm, 1 attention, 2 se/scale, 3 gather, 4 compose, 5 fused mlp;
    out[30] = frame ms; cap >= 31 */
 int w2x_profile_frame(w2x_engine* e, double* out, int cap);

@@ -80,6 +80,8 @@ public:
     // Re-run the device part of the last render() (gather, network, compose; no H2D/D2H) `iters` times and return the
     // average milliseconds per frame - inputs already resident in HBM (bench.py's timed region).
     float benchResident(int iters);
+    // Copy the output frame the last benchResident() step left in HBM to dst (`bytes` = the scaled frame's size).
+    bool residentOutput(void* dst, size_t bytes);
     // Per-kernel-family HIP-event timing of one resident frame (layout documented at the definition).
     bool profileFrame(double* out, int cap);
     int opTimes(double* out, int cap) const;   // ms per plan op of the last profileFrame(); returns the op count

@@ -348,7 +348,8 @@ def test_rolling_sequence_of_frames_matches_render(pkg, onnx_model, monkeypatch,
     first stream goes on with the next frame's first group while the second stream composes the frame behind its own group, the tile slab alternating
     between two buffers.  Seven different frames (the fourth sighting of each buffer pair replays captured graphs), one pass per frame, two passes per
     frame (108 tiles of 64) and TTA (8 slots per tile): every frame is the bytes of render(), with output buffers reused as a ring, and W2X_NO_ROLLING=1
-    gives the same; the engine is left usable and a resident replay leaves the last frame's output in place."""
+    gives the same; a resident replay computes the bytes of render() (read back with resident_output), the engine is left usable and
+    the replay leaves the last frame's output in place."""
     path = onnx_model("swin_unet/art", 4, 2, 64)
     frames = [smooth_frame(shape[0], shape[1], 60 + k) for k in range(7)]
     outs = {}
@@ -369,6 +370,9 @@ def test_rolling_sequence_of_frames_matches_render(pkg, onnx_model, monkeypatch,
             assert np.array_equal(ring[6 % 3], want[6]) and np.array_equal(ring[5 % 3], want[5]) and np.array_equal(ring[4 % 3], want[4])
         assert np.array_equal(eng.render(frames[2]), want[2])
         assert eng.bench_resident(5) > 0 and eng.bench_resident(4) > 0          # resident replays of the last frame roll too (odd and even counts)
+        res = np.empty_like(want[2])
+        assert eng.resident_output(res) and np.array_equal(res, want[2]), f"rolling={rolling}"   # the frame the last resident step computed, read back
+        assert not eng.resident_output(np.empty((8, 8, 3), np.uint8))         # a buffer of another size is refused
         assert np.array_equal(eng.render(frames[3]), want[3])
         outs[rolling] = want
         eng.close()

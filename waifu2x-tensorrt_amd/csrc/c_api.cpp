@@ -152,6 +152,7 @@ float w2x_last_render_ms(w2x_engine* e) { return e ? e->engine.lastRenderMs() : 
 int w2x_profile_frame(w2x_engine* e, double* out, int cap) { return e && e->engine.profileFrame(out, cap) ? 1 : 0; }
 int w2x_op_times(w2x_engine* e, double* out, int cap) { return e ? e->engine.opTimes(out, cap) : 0; }
 float w2x_bench_resident(w2x_engine* e, int iters) { return e ? e->engine.benchResident(iters) : -1.f; }
+int w2x_resident_output(w2x_engine* e, void* dst, size_t bytes) { return e && e->engine.residentOutput(dst, bytes) ? 1 : 0; }
 
 int w2x_calculate_tiles(int in_w, int in_h, int out_w, int out_h, int tile_in, int tile_out, int scaling,
                         double overlap_x, double overlap_y, int* in_rects, int* out_rects, int cap) {

@@ -1874,6 +1874,20 @@ float Img2Img::benchResident(int iters) try {
     return -1.f;
 }
 
+// The output frame the last benchResident() step (or render()) left in device memory: rows * s x cols * s x 3 samples, packed; `bytes` must be that size.
+bool Img2Img::residentOutput(void* dst, size_t bytes) try {
+    if (!impl->loaded || impl->last_rows == 0 || !dst) return false;
+    const size_t s = (size_t)impl->cfg.scaling, bps = impl->deep ? 2 : 1;
+    if (bytes != (size_t)impl->last_rows * s * impl->last_cols * s * 3 * bps) return false;
+    DeviceGuard guard(impl->device);
+    hipAssert(hipMemcpyAsync(dst, impl->d_out, bytes, hipMemcpyDeviceToHost, impl->stream));
+    hipAssert(hipStreamSynchronize(impl->stream));
+    return true;
+} catch (const std::exception& e) {
+    W2X_LOG(error, "Reading the resident output failed unexpectedly: " + std::string(e.what()) + ".");
+    return false;
+}
+
 // Per-kernel-family device time of one resident frame, measured with HIP events on the compute stream.
 // out[5*k + {0,1,2}] = {milliseconds, launches, algorithmic FLOP} for k = 0 gemm, 1 attention, 2 se/scale, 3 gather,
 // 4 compose, 5 fused mlp; out[30] = wall ms of the whole frame (first launch start to last launch end).

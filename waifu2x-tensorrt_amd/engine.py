@@ -126,6 +126,7 @@ def lib():
     L.w2x_plan_flops.argtypes = [vp]; L.w2x_plan_flops.restype = C.c_double
     L.w2x_last_render_ms.argtypes = [vp]; L.w2x_last_render_ms.restype = C.c_float
     L.w2x_bench_resident.argtypes = [vp, C.c_int]; L.w2x_bench_resident.restype = C.c_float
+    L.w2x_resident_output.argtypes = [vp, vp, C.c_size_t]; L.w2x_resident_output.restype = C.c_int
     L.w2x_profile_frame.argtypes = [vp, vp, C.c_int]; L.w2x_profile_frame.restype = C.c_int
     L.w2x_op_times.argtypes = [vp, vp, C.c_int]; L.w2x_op_times.restype = C.c_int
     L.w2x_calculate_tiles.argtypes = [C.c_int] * 7 + [C.c_double, C.c_double, vp, vp, C.c_int]; L.w2x_calculate_tiles.restype = C.c_int
@@ -144,7 +145,7 @@ def lib():
 
 EXPORTED_SYMBOLS = [
     "w2x_create", "w2x_destroy", "w2x_set_message_callback", "w2x_set_progress_callback", "w2x_build", "w2x_load",
-    "w2x_render", "w2x_render16", "w2x_infer", "w2x_output_tile_size", "w2x_plan_flops", "w2x_pass_tiles", "w2x_last_render_ms", "w2x_bench_resident", "w2x_profile_frame", "w2x_op_times",
+    "w2x_render", "w2x_render16", "w2x_infer", "w2x_output_tile_size", "w2x_plan_flops", "w2x_pass_tiles", "w2x_last_render_ms", "w2x_bench_resident", "w2x_resident_output", "w2x_profile_frame", "w2x_op_times",
     "w2x_render_strip", "w2x_strip_plan", "w2x_render_sharded", "w2x_shard_plan", "w2x_shard_compute", "w2x_shard_slab", "w2x_shard_finish", "w2x_ipc_export", "w2x_ipc_open", "w2x_ipc_close", "w2x_render_sequence", "w2x_alloc_host", "w2x_free_host", "w2x_pin_host", "w2x_unpin_host", "w2x_calculate_tiles", "w2x_tile_weights", "w2x_describe_plan", "w2x_describe_plan_precision", "w2x_write_engine_file", "w2x_validate_engine_file", "w2x_device_pci_bus_id", "w2x_sha256_hex", "w2x_version", "w2x_debug_set"]
 
 
@@ -353,6 +354,12 @@ class Img2Img:
 
     def bench_resident(self, iters: int) -> float:
         return self._L.w2x_bench_resident(self._h, iters)
+
+    def resident_output(self, dst: np.ndarray) -> bool:
+        """Copy the output frame the last bench_resident() step left on the device into dst (packed [rows * s, cols * s, 3] of the frame's sample type)."""
+        if not dst.flags.c_contiguous:
+            raise ValueError("dst must be a packed array")
+        return bool(self._L.w2x_resident_output(self._h, dst.ctypes.data, dst.nbytes))
 
     def profile_frame(self) -> dict:
         """HIP-event time per kernel family for one resident frame: {family: (ms, launches, flop)}, plus 'frame_ms'."""
