@@ -28,6 +28,8 @@ typedef struct w2x_engine w2x_engine;
 
 enum { W2X_PRECISION_TF32 = 0, W2X_PRECISION_FP16 = 1, W2X_PRECISION_FP32 = 2 };  /* config.h:7-10; CLI map main.cpp:76-84; FP32: an addition (include/w2x/config.h) */
 
+enum { W2X_RESIZE_BICUBIC = 0, W2X_RESIZE_BILINEAR = 1 };   /* extension: the filter of the resized renders (include/w2x/config.h ResizeFilter) */
+
 typedef struct w2x_build_config {   /* trt::BuildConfig, config.h:12-31 */
     int deviceId, precision;
     int minBatchSize, optBatchSize, maxBatchSize;
@@ -57,6 +59,11 @@ int w2x_render(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src
 /* The same on 16-bit samples (extension; the reference reads and writes 8-bit frames only, capture.cpp:96-99, and lists deeper images as a
  * TODO, README.md:88): interleaved BGR uint16, steps in BYTES; x = u16 * float(1/65535) into the network, sat(rint(x * 65535)) out. */
 int w2x_render16(w2x_engine* e, const uint16_t* src, int rows, int cols, size_t src_step, uint16_t* dst, size_t dst_step);
+/* Extension (Img2Img::renderResized): the frame w2x_render gives, resized on the device to dst_rows x dst_cols with an antialiased filter
+ * (W2X_RESIZE_BICUBIC / _BILINEAR: torch.nn.functional.interpolate(antialias=True) on the fp32 canvas, then quantised).  Each target dimension must lie
+ * in [input dim, input dim * scaling]; other sizes return 0 through the message callback.  At the scaled size the bytes are w2x_render's. */
+int w2x_render_resized(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, int dst_rows, int dst_cols, size_t dst_step, int filter);
+int w2x_render16_resized(w2x_engine* e, const uint16_t* src, int rows, int cols, size_t src_step, uint16_t* dst, int dst_rows, int dst_cols, size_t dst_step, int filter);
 /* Multi-GPU split of ONE frame (no reference counterpart: main.cpp:70-74 is single-device): strip `part` of
  * `parts` = a contiguous range of the reference's column-major tile order (img2img_render.cpp:43-44) plus the output columns
  * it alone composes.  w2x_strip_plan is pure host logic: out[0..3] = first_tile, tile_count, x0, x1 (x in output pixels). */
@@ -85,6 +92,9 @@ void w2x_ipc_close(void* p);
  * frame buffers from w2x_alloc_host (engine-owned, w2x_free_host or w2x_destroy releases them).  w2x_pin_host page-locks caller
  * memory in place and accepts whole pages only (data and bytes multiples of 4096). */
 int w2x_render_sequence(w2x_engine* e, const uint8_t* const* srcs, int rows, int cols, size_t src_step, uint8_t* const* dsts, size_t dst_step, int count);
+/* w2x_render_sequence with every frame resized like w2x_render_resized (one target size for the sequence, 8-bit frames) */
+int w2x_render_sequence_resized(w2x_engine* e, const uint8_t* const* srcs, int rows, int cols, size_t src_step, uint8_t* const* dsts, int dst_rows, int dst_cols, size_t dst_step,
+                                int count, int filter);
 void* w2x_alloc_host(w2x_engine* e, size_t bytes);
 void w2x_free_host(w2x_engine* e, void* data);
 int w2x_pin_host(w2x_engine* e, void* data, size_t bytes);
@@ -111,6 +121,10 @@ int w2x_calculate_tiles(int in_w, int in_h, int out_w, int out_h, int tile_in, i
                         double overlap_x, double overlap_y, int* in_rects, int* out_rects, int cap);
 /* which: 0 top, 1 right, 2 bottom, 3 left (weights[] index, img2img_load.cpp:30-51); out: size*size floats. */
 int w2x_tile_weights(int which, int overlap_x, int overlap_y, int size, float* out);
+/* Tap tables of the resized renders along one axis, `in` -> `out` samples: first[i] = first input index of output i, weights[i * taps + k] its weights
+ * (normalised, zero past the taps it has).  Returns taps per output; 0 for invalid arguments; with first / weights NULL only the count; -taps (nothing
+ * written) when cap < out * taps. */
+int w2x_resize_weights(int in, int out, int filter, int* first, float* weights, int cap);
 /* Lower an ONNX file at [batch,3,tile,tile] and write a textual description of the plan (ops, FLOPs) into buf. */
 int w2x_describe_plan(const char* onnx_path, int batch, int tile, char* buf, size_t cap);
 /* the same for any precision (W2X_PRECISION_FP16 / _TF32 / _FP32: the plan build() would write for that BuildConfig::precision; TF32 and FP32 share one) */

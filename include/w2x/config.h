@@ -20,6 +20,9 @@ enum class Precision { TF32, FP16, FP32 };
 // min <= opt <= max, writes the plan for the opt shape and keys the plan cache on all of them, like the reference's JSON side
 // file; load() takes the first optimized engine, else the first compatible one (img2img_load.cpp:100-107) and re-specialises
 // the plan from the same ONNX file for a shape inside the range that is not the opt shape.
+// Extension: the filter of Img2Img::renderResized (an antialiased downsample of the network's output): bicubic (a = -0.5) or bilinear (triangle)
+enum class ResizeFilter { Bicubic, Bilinear };
+
 struct BuildConfig {
     int deviceId = 0;                                             // HIP device ordinal
     Precision precision = Precision::FP16;

@@ -38,6 +38,10 @@ public:
     bool load(const std::string& path, const RenderConfig& config);
     // img2img.h:20 - dst must be rows*scaling x cols*scaling (caller pre-sizes it, main.cpp:234-235)
     bool render(const Image& src, Image& dst);
+    // Extension: render() to any output size between the input and the scaled frame - dst.rows x dst.cols, each in [src dim, src dim * scaling] - through
+    // an antialiased resize on the device (PIL's convolution resampler, as torch.nn.functional.interpolate(antialias=True) computes it) of the fp32 canvas
+    // render() would quantise; 8- or 16-bit frames.  At dst = rows*scaling x cols*scaling the bytes are render()'s.  Other sizes: false (message callback).
+    bool renderResized(const Image& src, Image& dst, ResizeFilter filter = ResizeFilter::Bicubic);
     // One device's share of a single frame spread over `parts` devices (tile-column strips): composes and writes only
     // the output columns of strip `part` (w2x_strip_plan); identical bytes to render() there.  render() == renderStrip(.., 0, 1).
     bool renderStrip(const Image& src, Image& dst, int part, int parts);
@@ -58,6 +62,8 @@ public:
     // three HIP streams; outputs are the bytes render() gives.  The copies only overlap for page-locked host memory: take the frame
     // buffers from allocHost() (owned by the engine, released by freeHost(), release at destruction at the latest).
     bool renderSequence(const Image* srcs, Image* dsts, int count);
+    // renderSequence() with every frame resized like renderResized() to dsts[i].rows x dsts[i].cols (one size for the sequence; 8-bit frames)
+    bool renderSequenceResized(const Image* srcs, Image* dsts, int count, ResizeFilter filter = ResizeFilter::Bicubic);
     void* allocHost(size_t bytes);
     void freeHost(void* data);
     // Page-locks caller-owned memory in place.  Only whole pages are accepted (data and bytes multiples of 4096): a registration
@@ -88,7 +94,8 @@ public:
 
     struct Impl;
 private:
-    bool renderPart(const Image& src, Image& dst, int part, int parts, const char* who);
+    bool renderPart(const Image& src, Image& dst, int part, int parts, const char* who, int resizeFilter = -1);   // resizeFilter >= 0: renderResized
+    bool runSequence(const Image* srcs, Image* dsts, int count, int resizeFilter, const char* who);
     std::unique_ptr<Impl> impl;
 };
 

@@ -75,6 +75,29 @@ int w2x_render16(w2x_engine* e, const uint16_t* src, int rows, int cols, size_t 
     return e->engine.render(s, d) ? 1 : 0;
 }
 
+// the resized renders: the target size is explicit; an unknown filter is refused here, through the engine's message callback
+static bool resize_filter(w2x_engine* e, int filter, const char* who, w2x::ResizeFilter& f) {
+    if (filter == W2X_RESIZE_BICUBIC || filter == W2X_RESIZE_BILINEAR) { f = filter == W2X_RESIZE_BILINEAR ? w2x::ResizeFilter::Bilinear : w2x::ResizeFilter::Bicubic; return true; }
+    if (e->msg) e->msg((int)w2x::Severity::error, (std::string("[") + who + "@0] Unknown resize filter " + std::to_string(filter) + ".").c_str(), e->msg_user);
+    return false;
+}
+
+int w2x_render_resized(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, int dst_rows, int dst_cols, size_t dst_step, int filter) {
+    w2x::ResizeFilter f;
+    if (!e || !resize_filter(e, filter, "w2x_render_resized", f)) return 0;
+    w2x::Image s; s.data = const_cast<uint8_t*>(src); s.rows = rows; s.cols = cols; s.step = src_step;
+    w2x::Image d; d.data = dst; d.rows = dst_rows; d.cols = dst_cols; d.step = dst_step;
+    return e->engine.renderResized(s, d, f) ? 1 : 0;
+}
+
+int w2x_render16_resized(w2x_engine* e, const uint16_t* src, int rows, int cols, size_t src_step, uint16_t* dst, int dst_rows, int dst_cols, size_t dst_step, int filter) {
+    w2x::ResizeFilter f;
+    if (!e || !resize_filter(e, filter, "w2x_render16_resized", f)) return 0;
+    w2x::Image s; s.data = reinterpret_cast<uint8_t*>(const_cast<uint16_t*>(src)); s.rows = rows; s.cols = cols; s.step = src_step; s.depth = 16;
+    w2x::Image d; d.data = reinterpret_cast<uint8_t*>(dst); d.rows = dst_rows; d.cols = dst_cols; d.step = dst_step; d.depth = 16;
+    return e->engine.renderResized(s, d, f) ? 1 : 0;
+}
+
 int w2x_render_strip(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, size_t dst_step, int part, int parts) {
     if (!e) return 0;
     w2x::Image s; s.data = const_cast<uint8_t*>(src); s.rows = rows; s.cols = cols; s.step = src_step;
@@ -120,6 +143,17 @@ int w2x_render_sequence(w2x_engine* e, const uint8_t* const* srcs, int rows, int
     }
     return e->engine.renderSequence(s.data(), d.data(), count) ? 1 : 0;
 }
+int w2x_render_sequence_resized(w2x_engine* e, const uint8_t* const* srcs, int rows, int cols, size_t src_step, uint8_t* const* dsts, int dst_rows, int dst_cols, size_t dst_step,
+                                int count, int filter) {
+    w2x::ResizeFilter f;
+    if (!e || count < 0 || (count > 0 && (!srcs || !dsts)) || !resize_filter(e, filter, "w2x_render_sequence_resized", f)) return 0;
+    std::vector<w2x::Image> s(count), d(count);
+    for (int i = 0; i < count; ++i) {
+        s[i].data = const_cast<uint8_t*>(srcs[i]); s[i].rows = rows; s[i].cols = cols; s[i].step = src_step;
+        d[i].data = dsts[i]; d[i].rows = dst_rows; d[i].cols = dst_cols; d[i].step = dst_step;
+    }
+    return e->engine.renderSequenceResized(s.data(), d.data(), count, f) ? 1 : 0;
+}
 void* w2x_alloc_host(w2x_engine* e, size_t bytes) { return e ? e->engine.allocHost(bytes) : nullptr; }
 void w2x_free_host(w2x_engine* e, void* data) { if (e) e->engine.freeHost(data); }
 int w2x_pin_host(w2x_engine* e, void* data, size_t bytes) { return e && e->engine.pinHost(data, bytes) ? 1 : 0; }
@@ -163,6 +197,16 @@ int w2x_calculate_tiles(int in_w, int in_h, int out_w, int out_h, int tile_in, i
         if (out_rects) { out_rects[4 * i] = g.out[i].x; out_rects[4 * i + 1] = g.out[i].y; out_rects[4 * i + 2] = g.out[i].w; out_rects[4 * i + 3] = g.out[i].h; }
     }
     return g.count;
+}
+
+int w2x_resize_weights(int in, int out, int filter, int* first, float* weights, int cap) {
+    if (in <= 0 || out <= 0 || (filter != W2X_RESIZE_BICUBIC && filter != W2X_RESIZE_BILINEAR)) return 0;
+    const w2x::ResizeTaps t = w2x::resize_taps(in, out, filter);
+    if (!first || !weights) return t.taps;
+    if ((long)cap < (long)out * t.taps) return -t.taps;
+    memcpy(first, t.first.data(), t.first.size() * sizeof(int));
+    memcpy(weights, t.w.data(), t.w.size() * sizeof(float));
+    return t.taps;
 }
 
 int w2x_tile_weights(int which, int overlap_x, int overlap_y, int size, float* out) {

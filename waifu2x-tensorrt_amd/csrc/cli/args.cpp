@@ -1,7 +1,9 @@
 #include "args.h"
+#include "imageio.h"
 
 #include <algorithm>
 #include <cmath>
+#include <cstdio>
 #include <cstdlib>
 #include <filesystem>
 #include <sstream>
@@ -63,6 +65,8 @@ std::string usage() {
            "  render                      Render image(s)/video(s)\n"
            "      -i,--input PATH ... REQUIRED   --recursive   -o,--output DIR   --nosuffix\n"
            "      --blend FLOAT [1/16] {1/8,1/16,1/32,0}   --tta   --codec TEXT [libx264]   --pix_fmt TEXT [yuv420p]   --crf INT [23] 0..51\n"
+           "      --outscale FLOAT        (extension) output size = input size x FLOAT, 1 <= FLOAT <= --scale: the network output resized on the GPU\n"
+           "      --resize-filter TEXT [bicubic]  (extension) {bicubic,bilinear}: the antialiasing filter of --outscale\n"
            "      --tta-mode TEXT [mean]  (extension) {mean,reference}: with --tta, `mean` averages the 8 augmentations; `reference`\n"
            "                              reproduces the bytes of the reference's accumulation (img2img_render.cpp:313-316); --tta-compat = reference\n"
            "  build                       Build model\n"
@@ -72,7 +76,7 @@ std::string usage() {
 Options parse(int argc, const char* const* argv) {
     Options o;
     std::vector<std::string> a(argv + 1, argv + argc);
-    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false;
+    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_filter = false;
     auto value = [&](size_t& i) -> std::string {
         const std::string name = a[i];
         auto eq = name.find('=');
@@ -114,6 +118,8 @@ Options parse(int argc, const char* const* argv) {
         else if (k == "--codec") o.codec = value(i);
         else if (k == "--pix_fmt") o.pixFmt = value(i);
         else if (k == "--crf") o.crf = to_int(k, value(i));
+        else if (k == "--outscale") { o.outscale = to_double(k, value(i)); seen_outscale = true; }
+        else if (k == "--resize-filter") { o.resizeFilter = value(i); std::transform(o.resizeFilter.begin(), o.resizeFilter.end(), o.resizeFilter.begin(), ::tolower); seen_filter = true; }
         else throw std::runtime_error("The following argument was not expected: " + a[i]);
     }
     if (o.command.empty()) throw std::runtime_error("A subcommand is required");
@@ -144,7 +150,17 @@ Options parse(int argc, const char* const* argv) {
         if (o.crf < 0 || o.crf > 51) throw std::runtime_error("--crf: Value not in range 0 to 51");
         member<std::string>("--tta-mode", o.ttaMode, {"mean", "reference"});
         if (o.ttaMode == "reference" && !o.tta) throw std::runtime_error("--tta-mode reference: needs --tta");
-    }
+        if (seen_outscale) {
+            if (!(o.outscale >= 1.0 && o.outscale <= o.scale)) {
+                std::ostringstream os; os << "--outscale: " << o.outscale << " not in [1, " << o.scale << "] (the output is a downsample of the --scale network's)";
+                throw std::runtime_error(os.str());
+            }
+            member<std::string>("--resize-filter", o.resizeFilter, {"bicubic", "bilinear"});
+            if (o.devices > 1)
+                for (const auto& p : o.inputs)
+                    if (!std::filesystem::is_directory(p) && is_builtin_still(p)) throw std::runtime_error("--outscale: a still over --devices " + std::to_string(o.devices) + " is not supported: " + p);
+        } else if (seen_filter) throw std::runtime_error("--resize-filter: needs --outscale");
+    } else if (seen_outscale || seen_filter) throw std::runtime_error(std::string(seen_outscale ? "--outscale" : "--resize-filter") + ": only with render");
     // cross-checks, main.cpp:142-145
     if (o.model == "cunet/art" && o.scale == 4) throw std::runtime_error("cunet/art does not support scale factor 4.");
     if (o.noise == -1 && o.scale == 1) throw std::runtime_error("Noise level -1 does not support scale factor 1.");
@@ -156,12 +172,20 @@ std::string model_path(const Options& o) {
            (o.scale == 1 ? "" : "scale" + std::to_string(o.scale) + "x") + ".onnx";
 }
 
+static std::string outscale_tag(const Options& o) {
+    if (o.outscale <= 0) return "";
+    char buf[64]; std::snprintf(buf, sizeof buf, "(outscale%g)", o.outscale);
+    return buf;
+}
+
 std::string output_suffix(const Options& o) {
     std::string m = o.model;
     std::replace(m.begin(), m.end(), '/', '_');
     return "(" + m + ")" + (o.noise == -1 ? "" : "(noise" + std::to_string(o.noise) + ")") +
-           (o.scale == 1 ? "" : "(scale" + std::to_string(o.scale) + ")") + (o.tta ? "(tta)" : "");
+           (o.scale == 1 ? "" : "(scale" + std::to_string(o.scale) + ")") + outscale_tag(o) + (o.tta ? "(tta)" : "");
 }
+
+int out_dim(const Options& o, int dim) { return o.outscale > 0 ? (int)std::lround(dim * o.outscale) : dim * o.scale; }
 
 std::string output_path(const Options& o, const std::string& input, bool single_frame) {
     namespace fs = std::filesystem;
@@ -179,6 +203,7 @@ std::string to_json(const Options& o) {
        << ", \"batchSize\": " << o.batchSize << ", \"tileSize\": " << o.tileSize << ", \"device\": " << o.device << ", \"devices\": " << o.devices << ", \"split\": " << q(o.split)
        << ", \"precision\": " << q(o.precision) << ", \"recursive\": " << (o.recursive ? "true" : "false") << ", \"output\": " << q(o.output)
        << ", \"nosuffix\": " << (o.nosuffix ? "true" : "false") << ", \"blend\": " << o.blend << ", \"tta\": " << (o.tta ? "true" : "false") << ", \"tta_mode\": " << q(o.ttaMode)
+       << ", \"outscale\": " << (o.outscale > 0 ? std::to_string(o.outscale) : std::string("null")) << ", \"resize_filter\": " << q(o.resizeFilter)
        << ", \"codec\": " << q(o.codec) << ", \"pix_fmt\": " << q(o.pixFmt) << ", \"crf\": " << o.crf << ", \"inputs\": [";
     for (size_t i = 0; i < o.inputs.size(); ++i) os << (i ? ", " : "") << q(o.inputs[i]);
     os << "], \"model_path\": " << q(o.command == "convert" ? "" : model_path(o)) << ", \"suffix\": " << q(o.command == "convert" ? "" : output_suffix(o)) << ", \"outputs\": [";

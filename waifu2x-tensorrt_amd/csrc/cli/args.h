@@ -32,6 +32,9 @@ struct Options {
     std::string ttaMode = "mean";         // --tta-mode {mean,reference}: mean = the true average of the 8 augmentations; reference = the bytes the
                                           // reference's accumulation produces (img2img_render.cpp:313-316) -> RenderConfig::ttaBugCompat
     bool deep = false;                    // --deep: 16-bit PNGs keep 16 bits per sample (read, rendered and written as CV_16UC3; default: cut to 8 like cv::imread)
+    double outscale = 0;                  // --outscale F: output lround(W * F) x lround(H * F), F in [1, --scale]: the network's output resized on the device
+                                          // (Img2Img::renderResized / renderSequenceResized); 0 = the network's own size, the reference's behaviour
+    std::string resizeFilter = "bicubic"; // --resize-filter {bicubic,bilinear}: the antialiasing filter of --outscale
     bool printConfig = false;             // --print-config: dump the parsed options and derived names as JSON and exit (tests)
     bool help = false;
 };
@@ -42,10 +45,12 @@ std::string usage();
 
 // models/<model>/[noiseN_][scaleSx].onnx  (main.cpp:201-204)
 std::string model_path(const Options& o);
-// "(model_with_underscores)(noiseN)(scaleS)(tta)"  (main.cpp:205-209)
+// "(model_with_underscores)(noiseN)(scaleS)(tta)"  (main.cpp:205-209); with --outscale F "(outscale<F as %g>)" after (scaleS)
 std::string output_suffix(const Options& o);
 // output file name for one input (main.cpp:240-257): directory override, suffix, .png for stills / .mp4 for videos
 std::string output_path(const Options& o, const std::string& input, bool single_frame);
 std::string to_json(const Options& o);
+// the output size of a `rows` x `cols` frame: x scale, or lround(x * outscale) with --outscale
+int out_dim(const Options& o, int dim);
 
 }  // namespace w2x::cli

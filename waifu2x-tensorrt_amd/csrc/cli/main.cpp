@@ -93,10 +93,11 @@ struct AviSink : FrameSink {
 // fills slots in stream order, one persistent worker per engine renders its chunks with renderSequence (upload / compute / download of
 // consecutive frames overlapped), one writer thread drains the slots in stream order - decoding, N renders and encoding all overlap,
 // and frames leave in the order they came (the reference serialises read -> render -> write per frame).
-bool run_frame_pipeline(std::vector<std::unique_ptr<Img2Img>>& engines, FrameSource& src, FrameSink& dst, int width, int height, int scale,
-                        const std::function<void(int)>& on_frames) {
+// Output frames are outW x outH: the network's size, or with `resize` (--outscale) that size through renderSequenceResized.
+bool run_frame_pipeline(std::vector<std::unique_ptr<Img2Img>>& engines, FrameSource& src, FrameSink& dst, int width, int height, int outW, int outH,
+                        const ResizeFilter* resize, const std::function<void(int)>& on_frames) {
     const int N = (int)engines.size(), CH = 4, SLOTS = 2;
-    const size_t inBytes = (size_t)width * height * 3, outBytes = inBytes * scale * scale;
+    const size_t inBytes = (size_t)width * height * 3, outBytes = (size_t)outW * outH * 3;
     struct Slot { std::vector<uint8_t*> in, out; int frames = 0; int state = 0; };   // 0 free, 1 read, 2 rendered
     std::vector<std::vector<Slot>> slots(N, std::vector<Slot>(SLOTS));
     auto release = [&] { for (int e = 0; e < N; ++e) for (Slot& sl : slots[e]) { for (uint8_t* p : sl.in) engines[e]->freeHost(p); for (uint8_t* p : sl.out) engines[e]->freeHost(p); sl.in.clear(); sl.out.clear(); } };
@@ -130,9 +131,9 @@ bool run_frame_pipeline(std::vector<std::unique_ptr<Img2Img>>& engines, FrameSou
             std::vector<Image> si(got), di(got);
             for (int k = 0; k < got; ++k) {
                 si[k] = Image{sl.in[k], height, width, (size_t)width * 3};
-                di[k] = Image{sl.out[k], height * scale, width * scale, (size_t)width * scale * 3};
+                di[k] = Image{sl.out[k], outH, outW, (size_t)outW * 3};
             }
-            const bool ok = engines[e]->renderSequence(si.data(), di.data(), got);
+            const bool ok = resize ? engines[e]->renderSequenceResized(si.data(), di.data(), got, *resize) : engines[e]->renderSequence(si.data(), di.data(), got);
             { std::lock_guard<std::mutex> lk(mu); if (!ok) failed = true; sl.state = 2; }
             cv.notify_all();
             if (!ok) return;
@@ -205,13 +206,17 @@ int main(int argc, char** argv) {
             c.overlapX = c.overlapY = o.blend; c.tta = o.tta; c.ttaBugCompat = o.ttaMode == "reference";
             if (!engines.back()->load(modelPath, c)) return -1;
         }
+        // --outscale (extension): every output lround(W * F) x lround(H * F), the network's output resized on the device
+        const ResizeFilter filter = o.resizeFilter == "bilinear" ? ResizeFilter::Bilinear : ResizeFilter::Bicubic;
+        const bool resize = o.outscale > 0;
         const std::vector<std::string> files = find_inputs(o);
         fileCount = files.size();
         for (const std::string& file : files) {
             if (cli::is_builtin_still(file)) {
                 frameIndex = 0; frameCount = 1;
                 cli::Bitmap in = cli::read_image(file, o.deep), out;
-                out.rows = in.rows * o.scale; out.cols = in.cols * o.scale;
+                out.rows = cli::out_dim(o, in.rows); out.cols = cli::out_dim(o, in.cols);
+                if (resize && o.devices > 1) throw std::runtime_error(file + ": --outscale renders a still on one device (--devices 1)");
                 const bool deep = !in.bgr16.empty();                   // --deep on a 16-bit PNG: CV_16UC3 through the engine (extension)
                 Image src, dst;
                 if (deep) {
@@ -222,6 +227,7 @@ int main(int argc, char** argv) {
                     src = Image{in.bgr.data(), in.rows, in.cols, (size_t)in.cols * 3}; dst = Image{out.bgr.data(), out.rows, out.cols, (size_t)out.cols * 3};
                 }
                 auto render_still = [&](const Image& s0, Image& d0) {
+                    if (resize) return engines[0]->renderResized(s0, d0, filter);
                     if (o.devices == 1) return engines[0]->render(s0, d0);
                     // every tile once: engine k takes the k-th contiguous range of the tile order, the seam bands travel device to device, each
                     // engine composes and downloads its own cells of the output (Img2Img::renderSharded).  16-bit frames and --split strips keep the
@@ -275,9 +281,10 @@ int main(int argc, char** argv) {
                 frameIndex = 0; frameCount = frames;
                 const bool single = frames == 1;
                 std::string outFile = cli::output_path(o, file, single);
-                const size_t outBytes = (size_t)width * height * 3 * o.scale * o.scale;
+                const int outW = cli::out_dim(o, width), outH = cli::out_dim(o, height);
+                const size_t outBytes = (size_t)outW * outH * 3;
                 if (have_ffmpeg) {
-                    std::string wcmd = "ffmpeg -v error -y -f rawvideo -pix_fmt bgr24 -s " + std::to_string(width * o.scale) + "x" + std::to_string(height * o.scale) +
+                    std::string wcmd = "ffmpeg -v error -y -f rawvideo -pix_fmt bgr24 -s " + std::to_string(outW) + "x" + std::to_string(outH) +
                                        " -r " + std::to_string(single ? 1.0 : fps) + " -i - ";
                     if (!single) wcmd += "-c:v " + o.codec + " -pix_fmt " + o.pixFmt + " -crf " + std::to_string(o.crf) + " ";
                     sink.reset(new PipeSink(wcmd + shell_quote(outFile), outBytes));
@@ -285,10 +292,10 @@ int main(int argc, char** argv) {
                     outFile = fs::path(outFile).replace_extension(".avi").string();
                     on_message(Severity::info, "ffmpeg is not on PATH: writing uncompressed video to " + outFile);
                     auto as = std::make_unique<AviSink>();
-                    as->wr.open(outFile, width * o.scale, height * o.scale, fps);
+                    as->wr.open(outFile, outW, outH, fps);
                     sink = std::move(as);
                 }
-                const bool ok = run_frame_pipeline(engines, *source, *sink, width, height, o.scale, [&](int n) { frameIndex += n; if (n) on_progress(1, 1, 0.0); });
+                const bool ok = run_frame_pipeline(engines, *source, *sink, width, height, outW, outH, resize ? &filter : nullptr, [&](int n) { frameIndex += n; if (n) on_progress(1, 1, 0.0); });
                 const bool closed = sink->close();
                 if (!ok || !closed) return -1;
             }

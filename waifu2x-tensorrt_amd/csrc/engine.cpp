@@ -11,6 +11,7 @@
 #include <cstdio>
 #include <cstdlib>
 #include <cstring>
+#include <deque>
 #include <filesystem>
 #include <fstream>
 #include <map>
@@ -265,6 +266,17 @@ struct Img2Img::Impl {
     uint8_t* d_out2 = nullptr; size_t out2_cap = 0;
     hipStream_t s_up = nullptr, s_dn = nullptr;
     hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_dn[2] = {nullptr, nullptr};
+    // renderResized() / renderSequenceResized(): the fp32 RGB canvas compose_canvas_kernel writes and resample_kernel reads (allocated on the first
+    // resized frame, so render() callers pay nothing; not a captured address: growing it keeps the pass graphs) and the device tap tables, uploaded
+    // once per (canvas size, target size, filter).  `rs` is the table of the frame being rendered (null outside a resized call).
+    float* d_canvas = nullptr; size_t canvas_cap = 0;
+    struct ResizeTables {
+        int inW = 0, inH = 0, outW = 0, outH = 0, filter = 0;
+        int *fx = nullptr, *fy = nullptr; float *wx = nullptr, *wy = nullptr;
+        int kx = 0, ky = 0, rows_max = 0;
+    };
+    std::deque<ResizeTables> rs_tables;
+    const ResizeTables* rs = nullptr;
     std::vector<void*> pinned;
     std::vector<void*> host_allocs;     // allocHost(): page-locked buffers handed to the caller
     std::vector<TileSlot> h_slots;
@@ -364,6 +376,10 @@ struct Img2Img::Impl {
         if (s_up) { (void)hipStreamDestroy(s_up); s_up = nullptr; }
         if (s_dn) { (void)hipStreamDestroy(s_dn); s_dn = nullptr; }
         frame2_cap = out2_cap = 0;
+        for (ResizeTables& t : rs_tables) for (void* q : {(void*)t.fx, (void*)t.fy, (void*)t.wx, (void*)t.wy}) if (q) (void)hipFree(q);
+        rs_tables.clear(); rs = nullptr;
+        if (d_canvas) { (void)hipFree(d_canvas); d_canvas = nullptr; }
+        canvas_cap = 0;
         for (void** p : {(void**)&d_frame, (void**)&d_out, (void**)&d_frame2, (void**)&d_out2, &d_slab, &d_slab2, (void**)&d_slots, (void**)&d_rampx, (void**)&d_rampy, (void**)&d_blob_in, (void**)&d_blob_out})
             if (*p) { (void)hipFree(*p); *p = nullptr; }
         frame_cap = out_cap = slab_cap = slab2_cap = slots_cap = 0;
@@ -878,6 +894,7 @@ struct Img2Img::Impl {
     // device part of one frame: gather -> network per batch -> compose.  Frame must already be in d_frame.
     void run_frame(int rows, int cols, const TileGrid& grid, bool report, const StripPlan& sp) {
         run_passes(rows, cols, sp.tile_count, 0, report, 0, true);
+        if (rs) { compose_canvas(rows, cols, grid, stream); resample(stream); return; }   // a resized frame (renderResized)
         compose_rect(rows, cols, grid, sp.x0, sp.x1, 0, 0, sp.first_tile);
     }
 
@@ -907,6 +924,13 @@ struct Img2Img::Impl {
         hipAssert(hipEventRecord(ev_g0[which], stream));
         hipStream_t s2 = gstream[0];
         hipAssert(hipStreamWaitEvent(s2, ev_g0[which], 0));
+        if (rs) {   // a resized frame: the canvas compose is the slab's last reader, the resample the writer of d_out; in order on s2, they share one canvas
+            compose_canvas(rows, cols, grid, s2);
+            hipAssert(hipEventRecord(ev_cmp[which], s2));
+            if (out_free) hipAssert(hipStreamWaitEvent(s2, out_free, 0));
+            resample(s2);
+            return;
+        }
         if (out_free) hipAssert(hipStreamWaitEvent(s2, out_free, 0));     // the frame that last left through this output buffer has been downloaded
         compose_rect(rows, cols, grid, sp.x0, sp.x1, 0, 0, sp.first_tile, s2);
         hipAssert(hipEventRecord(ev_cmp[which], s2));
@@ -1060,6 +1084,65 @@ struct Img2Img::Impl {
         stamp_begin(4, 0);
         hipAssert(launch_compose(cp, on ? on : stream));
         stamp_end();
+    }
+
+    // resized frames (rs set): the whole canvas of the frame's tiles (one part, slot 0 = tile 0) as fp32 planes into d_canvas, then the resize of
+    // d_canvas into d_out (rs->outW x rs->outH, packed)
+    void compose_canvas(int rows, int cols, const TileGrid& grid, hipStream_t on) {
+        const int To = plan.Tout;
+        ComposeParams cp;
+        cp.tiles = d_slab; cp.fp32 = plan.elt == 4;
+        cp.outW = cols * cfg.scaling; cp.outH = rows * cfg.scaling; cp.To = To;
+        cp.nx = grid.nx; cp.ny = grid.ny; cp.stride_x = To - grid.outOvX; cp.stride_y = To - grid.outOvY;
+        const bool overlapping = cfg.overlapX != 0 || cfg.overlapY != 0;
+        cp.ovx = overlapping ? ovx : 0; cp.ovy = overlapping ? ovy : 0;
+        cp.ramp_x = d_rampx; cp.ramp_y = d_rampy; cp.tta = cfg.tta ? 1 : 0; cp.tta_bug_compat = cfg.ttaBugCompat ? 1 : 0;
+        hipAssert(launch_compose_canvas(cp, d_canvas, on));
+    }
+    void resample(hipStream_t on) {
+        ResampleParams rp;
+        rp.canvas = d_canvas; rp.inW = rs->inW; rp.inH = rs->inH;
+        rp.dst = d_out; rp.dst_step = (size_t)rs->outW * 3 * (deep ? 2 : 1); rp.deep = deep ? 1 : 0;
+        rp.outW = rs->outW; rp.outH = rs->outH;
+        rp.fx = rs->fx; rp.wx = rs->wx; rp.kx = rs->kx; rp.fy = rs->fy; rp.wy = rs->wy; rp.ky = rs->ky; rp.rows_max = rs->rows_max;
+        hipAssert(launch_resample(rp, on));
+    }
+    // the device tap tables of one (canvas, target, filter) and a canvas that holds the frame; the caller sets rs to the result for the frame
+    const ResizeTables* resize_tables(int inW, int inH, int outW, int outH, int filter) {
+        for (const ResizeTables& t : rs_tables) if (t.inW == inW && t.inH == inH && t.outW == outW && t.outH == outH && t.filter == filter) return &t;
+        if (rs_tables.size() >= 16) {                                        // sizes that keep changing: start over rather than grow without bound
+            for (ResizeTables& t : rs_tables) for (void* q : {(void*)t.fx, (void*)t.fy, (void*)t.wx, (void*)t.wy}) if (q) hipAssert(hipFree(q));
+            rs_tables.clear();
+        }
+        const ResizeTaps tx = resize_taps(inW, outW, filter), ty = resize_taps(inH, outH, filter);
+        if (tx.taps <= 0 || ty.taps <= 0) throw std::runtime_error("invalid resize");
+        ResizeTables t;
+        t.inW = inW; t.inH = inH; t.outW = outW; t.outH = outH; t.filter = filter; t.kx = tx.taps; t.ky = ty.taps;
+        t.rows_max = resample_rows_max(ty.first.data(), outH, inH, ty.taps);
+        auto upload = [&](auto*& d, const auto& v) {
+            hipAssert(hipMalloc((void**)&d, v.size() * sizeof(v[0])));
+            hipAssert(hipMemcpy(d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
+        };
+        try { upload(t.fx, tx.first); upload(t.wx, tx.w); upload(t.fy, ty.first); upload(t.wy, ty.w); }
+        catch (...) { for (void* q : {(void*)t.fx, (void*)t.fy, (void*)t.wx, (void*)t.wy}) if (q) (void)hipFree(q); throw; }   // (no half-made entry is cached)
+        rs_tables.push_back(t);
+        return &rs_tables.back();
+    }
+    void ensure_canvas(size_t bytes) {
+        if (bytes <= canvas_cap) return;
+        if (d_canvas) hipAssert(hipFree(d_canvas));
+        d_canvas = nullptr; canvas_cap = 0;
+        hipAssert(hipMalloc((void**)&d_canvas, bytes));
+        canvas_cap = bytes;
+    }
+    // renderResized() / renderSequenceResized(): the target size of a frame must be a downsample of the network output by a factor of 1 to s per axis
+    std::string resize_problem(const Image& src, const Image& dst, int filter) const {
+        const int s = cfg.scaling;
+        if (filter != 0 && filter != 1) return "Unknown resize filter.";
+        if (dst.rows < src.rows || dst.rows > src.rows * s || dst.cols < src.cols || dst.cols > src.cols * s || dst.rows <= 0 || dst.cols <= 0)
+            return "Output image has invalid size for a resize: " + std::to_string(dst.cols) + "x" + std::to_string(dst.rows) + " is not between " + std::to_string(src.cols) + "x" +
+                   std::to_string(src.rows) + " and " + std::to_string(src.cols * s) + "x" + std::to_string(src.rows * s) + ".";
+        return "";
     }
 };
 
@@ -1270,11 +1353,17 @@ bool Img2Img::load(const std::string& modelPath, const RenderConfig& config) try
 
 bool Img2Img::render(const Image& src, Image& dst) { return renderPart(src, dst, 0, 1, "render"); }
 
+// render() followed by an antialiased resize of the canvas to dst.rows x dst.cols (between the input size and s times it), on the device: the frame's
+// tiles, compose_canvas_kernel (fp32 canvas), resample_kernel (k_resample.hip), the download of the target size.  At the scaled size it is render().
+bool Img2Img::renderResized(const Image& src, Image& dst, ResizeFilter filter) {
+    return renderPart(src, dst, 0, 1, "renderResized", filter == ResizeFilter::Bilinear ? 1 : 0);
+}
+
 // One GPU's share of a frame when a single image is spread over several devices: renders and writes only the
 // output columns strip_plan() assigns to `part`; the other columns of dst are left untouched.  part 0 of 1 = render().
 bool Img2Img::renderStrip(const Image& src, Image& dst, int part, int parts) { return renderPart(src, dst, part, parts, "renderStrip"); }
 
-bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, const char* who) try {
+bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, const char* who, int resizeFilter) try {
     if (!impl->loaded) { W2X_LOG_AS(who, error, "Render called before a successful load."); return false; }
     DeviceGuard guard(impl->device);
     if (parts <= 0 || part < 0 || part >= parts) { W2X_LOG_AS(who, error, "Invalid strip index."); return false; }
@@ -1284,14 +1373,25 @@ bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, cons
     if ((src.depth != 8 && src.depth != 16) || dst.depth != src.depth) { W2X_LOG_AS(who, error, "Input and output images must both be 8-bit or both 16-bit."); return false; }
     const size_t bps = src.depth / 8;                          // bytes per sample
     if (!src.data || rows <= 0 || cols <= 0 || src.step < (size_t)cols * 3 * bps) { W2X_LOG_AS(who, error, "Input image is empty or has an invalid step."); return false; }
-    if (!dst.data || dst.rows != rows * s || dst.cols != cols * s || dst.step < (size_t)dst.cols * 3 * bps) {
+    // a resized frame (renderResized): dst is the target size; at the scaled size it is a plain render()
+    const bool resized = resizeFilter >= 0 && !(dst.rows == rows * s && dst.cols == cols * s);
+    if (resized) {
+        const std::string why = impl->resize_problem(src, dst, resizeFilter);
+        if (!why.empty()) { W2X_LOG_AS(who, error, why); return false; }
+        if (!dst.data || dst.step < (size_t)dst.cols * 3 * bps) { W2X_LOG_AS(who, error, "Output image is empty or has an invalid step."); return false; }
+    } else if (!dst.data || dst.rows != rows * s || dst.cols != cols * s || dst.step < (size_t)dst.cols * 3 * bps) {
         W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(cols * s) + "x" + std::to_string(rows * s) + ".");
         return false;
     }
     hipStream_t stream = impl->stream;
     // img2img_render.cpp:226 upload
     impl->ensure(impl->d_frame, impl->frame_cap, (size_t)rows * cols * 3 * bps);
-    impl->ensure(impl->d_out, impl->out_cap, (size_t)rows * s * cols * s * 3 * bps);
+    impl->ensure(impl->d_out, impl->out_cap, (size_t)dst.rows * dst.cols * 3 * bps);
+    struct ResizeScope { Img2Img::Impl* e; ~ResizeScope() { e->rs = nullptr; } } resize_scope{impl.get()};
+    if (resized) {
+        impl->rs = impl->resize_tables(cols * s, rows * s, dst.cols, dst.rows, resizeFilter);
+        impl->ensure_canvas((size_t)rows * s * cols * s * 3 * sizeof(float));
+    }
     impl->deep = bps == 2;
     // img2img_render.cpp:226 upload: below, once the parts are known (a frame that runs in parts uploads the first part's columns first)
     // :232-240
@@ -1311,7 +1411,7 @@ bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, cons
     constexpr int kMaxParts = Impl::kMaxRenderParts;
     int npart = 1;
     int first_of[kMaxParts + 1] = {0, sp.tile_count, 0, 0, 0};   // part k = tiles [first_of[k], first_of[k + 1]) of the strip
-    if (parts == 1 && impl->pipeline_parts > 1 && sp.tile_count >= 16 && grid.outOvX < plan.Tout - grid.outOvX && grid.outOvY < plan.Tout - grid.outOvY) {
+    if (parts == 1 && !resized && impl->pipeline_parts > 1 && sp.tile_count >= 16 && grid.outOvX < plan.Tout - grid.outOvX && grid.outOvY < plan.Tout - grid.outOvY) {
         int q = 1; while ((q * steps) % plan.userB) ++q;        // part boundaries: whole reference batches
         const int want = std::min({impl->pipeline_parts, kMaxParts, sp.tile_count / 8});
         // the LAST part is the small one - its cells are the only ones that travel after the last kernel (a fifth of the tiles, at least 8: smaller passes no longer
@@ -1366,7 +1466,8 @@ bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, cons
         impl->run_frame(rows, cols, grid, true, sp);
         hipAssert(hipEventRecord(impl->ev1, stream));
         // :344 download ; the reference leaves the sync commented out (:345, quirk Q10) - we wait before handing dst back
-        hipAssert(hipMemcpy2DAsync(dst.data + (size_t)sp.x0 * 3 * bps, dst.step, impl->d_out + (size_t)sp.x0 * 3 * bps, (size_t)dst.cols * 3 * bps, (size_t)(sp.x1 - sp.x0) * 3 * bps, dst.rows, hipMemcpyDeviceToHost, stream));
+        const int dx0 = resized ? 0 : sp.x0, dx1 = resized ? dst.cols : sp.x1;
+        hipAssert(hipMemcpy2DAsync(dst.data + (size_t)dx0 * 3 * bps, dst.step, impl->d_out + (size_t)dx0 * 3 * bps, (size_t)dst.cols * 3 * bps, (size_t)(dx1 - dx0) * 3 * bps, dst.rows, hipMemcpyDeviceToHost, stream));
         hipAssert(hipStreamSynchronize(stream));
     } else {
         impl->ensure_copy_streams();
@@ -1433,6 +1534,7 @@ bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, cons
     hipAssert(hipEventElapsedTime(&impl->last_ms, impl->ev0, impl->ev1));
     impl->last_rows = rows; impl->last_cols = cols; impl->last_grid = grid; impl->last_strip = sp;
     impl->one_part_stale = npart > 1;     // (benchResident / profileFrame replay the frame as ONE part and rebuild the slot table when they are called: one_part_slots)
+    if (resized) impl->last_rows = impl->last_cols = 0;   // (a resized frame is not replayed: benchResident / residentOutput / profileFrame serve render() frames)
     // the second slab of a rolling sequence now (an allocation drops the captured passes: better here, on the frame size's first sight, than inside benchResident / renderSequence)
     if (parts == 1 && impl->slab2_cap < impl->slab_cap && impl->can_roll(sp.tile_count)) impl->ensure(impl->d_slab2, impl->slab2_cap, impl->slab_cap);
     return true;
@@ -1695,27 +1797,42 @@ void ipc_close(void* p) { if (p && hipIpcCloseMemHandle(p) != hipSuccess) (void)
 // buffers, events between the three streams).  Each frame is the same gather -> network -> compose as render(), so outputs are
 // bit-identical; the progress callback is not raised per batch here.  Copies only overlap when the host buffers are page-locked
 // (pinHost); with pageable memory the call is still correct, the runtime just serialises the copies.
-bool Img2Img::renderSequence(const Image* srcs, Image* dsts, int count) try {
-    if (!impl->loaded) { W2X_LOG(error, "Render called before a successful load."); return false; }
+bool Img2Img::renderSequence(const Image* srcs, Image* dsts, int count) { return runSequence(srcs, dsts, count, -1, "renderSequence"); }
+
+// renderResized() over a sequence: every frame resized to dsts[i].rows x dsts[i].cols (one target size), the canvas compose and the resample on the
+// compute side of the rolling pipeline (run_rolling_frame), the copy streams overlapped as in renderSequence().  At the scaled size it is renderSequence().
+bool Img2Img::renderSequenceResized(const Image* srcs, Image* dsts, int count, ResizeFilter filter) {
+    return runSequence(srcs, dsts, count, filter == ResizeFilter::Bilinear ? 1 : 0, "renderSequenceResized");
+}
+
+bool Img2Img::runSequence(const Image* srcs, Image* dsts, int count, int resizeFilter, const char* who) try {
+    if (!impl->loaded) { W2X_LOG_AS(who, error, "Render called before a successful load."); return false; }
     if (count <= 0) return true;
     DeviceGuard guard(impl->device);
     const RenderConfig& cfg = impl->cfg;
     const Plan& plan = impl->plan;
     const int rows = srcs[0].rows, cols = srcs[0].cols, s = cfg.scaling;
-    for (int i = 0; i < count; ++i) if (srcs[i].depth != 8 || dsts[i].depth != 8) { W2X_LOG(error, "renderSequence takes 8-bit frames (16-bit images go through render())."); return false; }
+    for (int i = 0; i < count; ++i) if (srcs[i].depth != 8 || dsts[i].depth != 8) { W2X_LOG_AS(who, error, std::string(who) + " takes 8-bit frames (16-bit images go through render())."); return false; }
+    // a resized sequence (renderSequenceResized): every dst is the target size of dsts[0]; at the scaled size it is a plain sequence
+    const int out_rows = resizeFilter >= 0 ? dsts[0].rows : rows * s, out_cols = resizeFilter >= 0 ? dsts[0].cols : cols * s;
+    const bool resized = resizeFilter >= 0 && !(out_rows == rows * s && out_cols == cols * s);
+    if (resized) {
+        const std::string why = impl->resize_problem(srcs[0], dsts[0], resizeFilter);
+        if (!why.empty()) { W2X_LOG_AS(who, error, why); return false; }
+    }
     impl->deep = false;
     for (int i = 0; i < count; ++i) {
-        if (!srcs[i].data || srcs[i].rows != rows || srcs[i].cols != cols || srcs[i].step < (size_t)cols * 3 || rows <= 0 || cols <= 0) { W2X_LOG(error, "Input images must be non-empty and of one size."); return false; }
-        if (!dsts[i].data || dsts[i].rows != rows * s || dsts[i].cols != cols * s || dsts[i].step < (size_t)cols * s * 3) { W2X_LOG(error, "Output image has invalid size: expected " + std::to_string(cols * s) + "x" + std::to_string(rows * s) + "."); return false; }
+        if (!srcs[i].data || srcs[i].rows != rows || srcs[i].cols != cols || srcs[i].step < (size_t)cols * 3 || rows <= 0 || cols <= 0) { W2X_LOG_AS(who, error, "Input images must be non-empty and of one size."); return false; }
+        if (!dsts[i].data || dsts[i].rows != out_rows || dsts[i].cols != out_cols || dsts[i].step < (size_t)out_cols * 3) { W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(out_cols) + "x" + std::to_string(out_rows) + "."); return false; }
     }
     hipStream_t stream = impl->stream;
     impl->ensure_copy_streams();
-    const size_t in_bytes = (size_t)rows * cols * 3, out_bytes = in_bytes * s * s;
+    const size_t in_bytes = (size_t)rows * cols * 3, out_bytes = (size_t)out_rows * out_cols * 3;
     impl->ensure(impl->d_frame, impl->frame_cap, in_bytes);   impl->ensure(impl->d_frame2, impl->frame2_cap, in_bytes);
     impl->ensure(impl->d_out, impl->out_cap, out_bytes);      impl->ensure(impl->d_out2, impl->out2_cap, out_bytes);
     TileGrid grid = calculate_tiles(cols, rows, cols * s, rows * s, plan.T, plan.T, plan.Tout, plan.Tout, s, cfg.overlapX, cfg.overlapY);
-    if (grid.count <= 0) { W2X_LOG(error, "Tile grid is empty."); return false; }
-    for (const Rect& r : grid.out) if (r.w <= 0 || r.h <= 0) { W2X_LOG(error, "Tile grid does not fit the output (scaling does not match the model)."); return false; }
+    if (grid.count <= 0) { W2X_LOG_AS(who, error, "Tile grid is empty."); return false; }
+    for (const Rect& r : grid.out) if (r.w <= 0 || r.h <= 0) { W2X_LOG_AS(who, error, "Tile grid does not fit the output (scaling does not match the model)."); return false; }
     const StripPlan sp = strip_plan(grid, cols * s, plan.Tout, 0, 1);
     const int steps = cfg.tta ? 8 : 1, B = plan.B, S = plan.B / plan.userB;
     const int batchCount = (int)std::lround(std::ceil((double)(sp.tile_count * steps) / plan.userB));
@@ -1738,6 +1855,11 @@ bool Img2Img::renderSequence(const Image* srcs, Image* dsts, int count) try {
     // frame f is composed on the second group's stream while frame f + 1's first group already runs (run_rolling_frame) when every pass of a frame splits
     const bool roll = count > 1 && impl->can_roll(sp.tile_count);
     if (roll) impl->ensure(impl->d_slab2, impl->slab2_cap, impl->slab_cap);
+    struct ResizeScope { Img2Img::Impl* e; ~ResizeScope() { e->rs = nullptr; } } resize_scope{impl.get()};
+    if (resized) {
+        impl->rs = impl->resize_tables(cols * s, rows * s, out_cols, out_rows, resizeFilter);
+        impl->ensure_canvas((size_t)rows * s * cols * s * 3 * sizeof(float));
+    }
     hipAssert(hipStreamSynchronize(stream));
     hipAssert(hipEventRecord(impl->ev0, stream));
     for (int i = 0; i < count; ++i) {
@@ -1756,7 +1878,7 @@ bool Img2Img::renderSequence(const Image* srcs, Image* dsts, int count) try {
             hipAssert(hipEventRecord(impl->ev_comp[b], stream));
         }
         hipAssert(hipStreamWaitEvent(impl->s_dn, impl->ev_comp[b], 0));
-        hipAssert(hipMemcpy2DAsync(dsts[i].data, dsts[i].step, outs[b], (size_t)cols * s * 3, (size_t)cols * s * 3, rows * s, hipMemcpyDeviceToHost, impl->s_dn));
+        hipAssert(hipMemcpy2DAsync(dsts[i].data, dsts[i].step, outs[b], (size_t)out_cols * 3, (size_t)out_cols * 3, out_rows, hipMemcpyDeviceToHost, impl->s_dn));
         hipAssert(hipEventRecord(impl->ev_dn[b], impl->s_dn));
     }
     if (roll) impl->end_rolling();
@@ -1768,12 +1890,13 @@ bool Img2Img::renderSequence(const Image* srcs, Image* dsts, int count) try {
     hipAssert(hipEventElapsedTime(&total_ms, impl->ev0, impl->ev1));
     impl->last_ms = total_ms / count;        // lastRenderMs(): compute-stream time per frame of the sequence
     impl->last_rows = rows; impl->last_cols = cols; impl->last_grid = grid; impl->last_strip = sp;
+    if (resized) impl->last_rows = impl->last_cols = 0;   // (not replayed by benchResident: renderPart)
     return true;
 } catch (const std::exception& e) {
     // copies on the side streams may still be reading or writing the caller's buffers, and a rolling sequence composes on the second group's stream
     // (end_rolling() has not run when an exception fires): let all four drain before the caller gets its buffers back
     impl->drain_after_error();
-    W2X_LOG(error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
+    W2X_LOG_AS(who, error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
     return false;
 }
 

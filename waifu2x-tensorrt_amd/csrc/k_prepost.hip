@@ -236,6 +236,22 @@ __global__ __launch_bounds__(kComposeThreads) void compose_kernel(const ComposeP
     }
 }
 
+// The canvas of a resized frame (renderResized): compose_pixel_sums for every pixel of the rect, unquantised, as three fp32 planes.  A thread
+// per pixel along a row (the plane stores of a wave are 256 contiguous bytes each), a workgroup row per canvas row.
+template <typename P>
+__global__ __launch_bounds__(256) void compose_canvas_kernel(const ComposeParams p, float* canvas) {
+    const int x1 = p.x1 > 0 ? p.x1 : p.outW, y1 = p.y1 > 0 ? p.y1 : p.outH;
+    const int X = p.x0 + blockIdx.x * 256 + threadIdx.x;
+    if (X >= x1) return;
+    const size_t plane = (size_t)p.outW * p.outH;
+    for (int Y = p.y0 + blockIdx.y; Y < y1; Y += gridDim.y) {
+        float r, g, b;
+        compose_pixel_sums<P>(p, (const P*)p.tiles, X, Y, r, g, b);
+        const size_t i = (size_t)Y * p.outW + X;
+        canvas[i] = r; canvas[plane + i] = g; canvas[2 * plane + i] = b;
+    }
+}
+
 __global__ void se_kernel(const SeParams p) {
     // one block per batch item; tiny (C <= 256)
     extern __shared__ float sm[];
@@ -346,6 +362,14 @@ hipError_t launch_compose(const ComposeParams& p, hipStream_t s) {
     const dim3 grid((unsigned)((gw + kComposeThreads - 1) / kComposeThreads), (unsigned)((nrows + kComposeRows - 1) / kComposeRows));
     if (p.fp32) hipLaunchKernelGGL(compose_kernel<float4v>, grid, dim3(kComposeThreads), 0, s, p);
     else hipLaunchKernelGGL(compose_kernel<half4>, grid, dim3(kComposeThreads), 0, s, p);
+    return hipGetLastError();
+}
+hipError_t launch_compose_canvas(const ComposeParams& p, float* canvas, hipStream_t s) {
+    const int w = (p.x1 > 0 ? p.x1 : p.outW) - p.x0, h = (p.y1 > 0 ? p.y1 : p.outH) - p.y0;
+    if (w <= 0 || h <= 0) return hipSuccess;
+    const dim3 grid((unsigned)((w + 255) / 256), (unsigned)(h < 65535 ? h : 65535));
+    if (p.fp32) hipLaunchKernelGGL(compose_canvas_kernel<float4v>, grid, dim3(256), 0, s, p, canvas);
+    else hipLaunchKernelGGL(compose_canvas_kernel<half4>, grid, dim3(256), 0, s, p, canvas);
     return hipGetLastError();
 }
 hipError_t launch_se(const SeParams& p, hipStream_t s) {

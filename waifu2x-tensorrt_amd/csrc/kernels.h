@@ -224,6 +224,23 @@ hipError_t launch_se(const SeParams& p, hipStream_t s);
 hipError_t launch_scale(void* x, const float* scale, int B, int HW, int Cs, bool fp32, hipStream_t s);
 hipError_t launch_gather(const GatherParams& p, hipStream_t s);
 hipError_t launch_compose(const ComposeParams& p, hipStream_t s);
+// k_prepost.hip compose_canvas_kernel: compose_kernel's per-pixel sums for the same rect of p (x0..x1, y0..y1; p.dst / p.deep unused) left
+// unquantised as fp32 RGB planes: canvas[c][Y][X], plane stride outW * outH (the input of the resize, renderResized)
+hipError_t launch_compose_canvas(const ComposeParams& p, float* canvas, hipStream_t s);
+// k_resample.hip resample_kernel: an antialiased separable resize of the fp32 RGB canvas (three planes of inH x inW) to outH x outW, quantised like
+// compose (sat(rint(x * 255)), 16-bit: 65535) and stored as BGR.  The tap tables (tiles.h resize_taps) live on the device: fx / wx per output column,
+// fy / wy per output row; rows_max = the input rows an output tile of kResampleRows rows reads at most (resample_rows_max)
+struct ResampleParams {
+    const float* canvas = nullptr; int inW = 0, inH = 0;
+    uint8_t* dst = nullptr; size_t dst_step = 0; int deep = 0;
+    int outW = 0, outH = 0;
+    const int* fx = nullptr; const float* wx = nullptr; int kx = 0;
+    const int* fy = nullptr; const float* wy = nullptr; int ky = 0;
+    int rows_max = 0;
+};
+constexpr int kResampleRows = 16, kResampleCols = 64;
+int resample_rows_max(const int* fy, int outH, int inH, int ky);   // host: the largest input row span of an output row tile
+hipError_t launch_resample(const ResampleParams& p, hipStream_t s);
 // debug/test helpers used by w2x_infer (mirrors blobFromImages / imagesFromBlob, img2img_infer.cpp:5-39)
 hipError_t launch_blob_to_nhwc(const float* nchw, void* out_nhwc4, int B, int T, bool fp32, hipStream_t s);
 hipError_t launch_nhwc_to_blob(const void* in_nhwc4, float* nchw, int B, int T, bool fp32, hipStream_t s);

@@ -1,5 +1,6 @@
 #include "tiles.h"
 
+#include <algorithm>
 #include <cmath>
 
 namespace w2x {
@@ -119,6 +120,36 @@ ShardPlan shard_plan(const TileGrid& g, int outW, int outH, int tileOutW, int ti
         if (r1 != 0) add(c1, c1 + 1, 0, r1);                           // the head of the last column
     }
     return sp;
+}
+
+ResizeTaps resize_taps(int in, int out, int filter) {
+    ResizeTaps t;
+    if (in <= 0 || out <= 0 || (filter != 0 && filter != 1)) return t;
+    const double scale = (double)in / out;
+    const double half = filter == 0 ? 2.0 : 1.0;                       // interp_size / 2: bicubic 4 taps, bilinear 2 at scale 1
+    const double support = scale >= 1.0 ? half * scale : half;
+    const double inv = scale >= 1.0 ? 1.0 / scale : 1.0;
+    t.taps = (int)std::ceil(support) * 2 + 1;
+    t.first.assign(out, 0); t.w.assign((size_t)out * t.taps, 0.f);
+    auto f = [&](double x) {
+        x = std::fabs(x);
+        if (filter == 1) return x < 1.0 ? 1.0 - x : 0.0;
+        const double a = -0.5;
+        if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0;
+        if (x < 2.0) return ((a * x - 5.0 * a) * x + 8.0 * a) * x - 4.0 * a;
+        return 0.0;
+    };
+    std::vector<double> w(t.taps);
+    for (int i = 0; i < out; ++i) {
+        const double center = scale * (i + 0.5);
+        const long x0 = std::max<long>((long)(center - support + 0.5), 0);
+        const long n = std::min<long>(std::min<long>((long)(center + support + 0.5), in) - x0, t.taps);
+        double total = 0.0;
+        for (long k = 0; k < n; ++k) { w[k] = f((k + x0 - center + 0.5) * inv); total += w[k]; }
+        t.first[i] = (int)x0;
+        for (long k = 0; k < n; ++k) t.w[(size_t)i * t.taps + k] = (float)(total != 0.0 ? w[k] / total : w[k]);
+    }
+    return t;
 }
 
 }  // namespace w2x

@@ -47,4 +47,12 @@ std::vector<float> blend_ramp(int ov);
 // full mask like the reference builds it; which: 0 top, 1 right, 2 bottom, 3 left
 std::vector<float> tile_weight_mask(int which, int ovx, int ovy, int size);
 
+// Tap tables of an antialiased separable resize of one axis, `in` -> `out` samples: PIL's convolution resampler as
+// torch.nn.functional.interpolate(mode=bilinear / bicubic, antialias=True, align_corners=False) computes it.  Output i is centred on
+// (i + 0.5) * scale (scale = in / out); the filter support grows by `scale` when scale > 1; the taps are clipped at the border and
+// normalised to sum 1; bicubic uses a = -0.5.  Computed in double, stored as float: first[i] = the first input index, w[i * taps + k]
+// its k-th weight (zero past the taps output i has).  filter: 0 bicubic, 1 bilinear.  taps = 0 for invalid arguments.
+struct ResizeTaps { int taps = 0; std::vector<int> first; std::vector<float> w; };
+ResizeTaps resize_taps(int in, int out, int filter);
+
 }  // namespace w2x

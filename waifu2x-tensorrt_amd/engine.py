@@ -24,6 +24,15 @@ class Precision(enum.IntEnum):      # config.h:7-10
     FP32 = 2                        # not in the reference: the same engine with exact fp32 products
 
 
+RESIZE_FILTERS = {"bicubic": 0, "bilinear": 1}   # W2X_RESIZE_BICUBIC / W2X_RESIZE_BILINEAR (include/w2x/c_api.h)
+
+
+def _filter_id(name) -> int:
+    if name not in RESIZE_FILTERS:
+        raise ValueError(f"filter must be one of {sorted(RESIZE_FILTERS)}, got {name!r}")
+    return RESIZE_FILTERS[name]
+
+
 class Severity(enum.IntEnum):       # logger.h:11-18
     critical = 0
     error = 1
@@ -105,6 +114,10 @@ def lib():
     L.w2x_load.argtypes = [vp, C.c_char_p, C.POINTER(_RenderConfig)]; L.w2x_load.restype = C.c_int
     L.w2x_render.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t]; L.w2x_render.restype = C.c_int
     L.w2x_render16.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t]; L.w2x_render16.restype = C.c_int
+    L.w2x_render_resized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, C.c_int, C.c_size_t, C.c_int]; L.w2x_render_resized.restype = C.c_int
+    L.w2x_render16_resized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, C.c_int, C.c_size_t, C.c_int]; L.w2x_render16_resized.restype = C.c_int
+    L.w2x_render_sequence_resized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int]; L.w2x_render_sequence_resized.restype = C.c_int
+    L.w2x_resize_weights.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]; L.w2x_resize_weights.restype = C.c_int
     L.w2x_render_strip.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]; L.w2x_render_strip.restype = C.c_int
     L.w2x_render_sequence.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int]; L.w2x_render_sequence.restype = C.c_int
     L.w2x_alloc_host.argtypes = [vp, C.c_size_t]; L.w2x_alloc_host.restype = vp
@@ -146,6 +159,7 @@ def lib():
 EXPORTED_SYMBOLS = [
     "w2x_create", "w2x_destroy", "w2x_set_message_callback", "w2x_set_progress_callback", "w2x_build", "w2x_load",
     "w2x_render", "w2x_render16", "w2x_infer", "w2x_output_tile_size", "w2x_plan_flops", "w2x_pass_tiles", "w2x_last_render_ms", "w2x_bench_resident", "w2x_resident_output", "w2x_profile_frame", "w2x_op_times",
+    "w2x_render_resized", "w2x_render16_resized", "w2x_render_sequence_resized", "w2x_resize_weights",
     "w2x_render_strip", "w2x_strip_plan", "w2x_render_sharded", "w2x_shard_plan", "w2x_shard_compute", "w2x_shard_slab", "w2x_shard_finish", "w2x_ipc_export", "w2x_ipc_open", "w2x_ipc_close", "w2x_render_sequence", "w2x_alloc_host", "w2x_free_host", "w2x_pin_host", "w2x_unpin_host", "w2x_calculate_tiles", "w2x_tile_weights", "w2x_describe_plan", "w2x_describe_plan_precision", "w2x_write_engine_file", "w2x_validate_engine_file", "w2x_device_pci_bus_id", "w2x_sha256_hex", "w2x_version", "w2x_debug_set"]
 
 
@@ -230,6 +244,69 @@ class Img2Img:
                 raise W2xError(self.last_error() or "render failed")
             return dst
         return ok
+
+    def render_resized(self, src: np.ndarray, size, filter: str = "bicubic", dst: np.ndarray | None = None):
+        """render() followed by an antialiased resize on the device to size = (rows, cols), each in [input dim, input dim * scaling]
+        (w2x_render_resized / w2x_render16_resized; uint8 or uint16 frames).  With dst=None returns the array or raises; with dst returns a bool."""
+        bps = src.dtype.itemsize
+        if src.dtype not in (np.uint8, np.uint16) or src.ndim != 3 or src.shape[2] != 3 or src.strides[2] != bps or src.strides[1] != 3 * bps:
+            raise ValueError("src must be a uint8 (or uint16) [rows, cols, 3] BGR array with packed pixels")
+        rows, cols = int(size[0]), int(size[1])
+        fid = _filter_id(filter)
+        ret_array = dst is None
+        if dst is None:
+            dst = np.empty((max(rows, 0), max(cols, 0), 3), src.dtype)
+        if dst.dtype != src.dtype or dst.shape != (rows, cols, 3) or (dst.size and (dst.strides[2] != bps or dst.strides[1] != 3 * bps)):
+            raise ValueError("dst must be a packed [rows, cols, 3] array of the target size and the frame's sample type")   # (an empty target: refused by the library)
+        fn = self._L.w2x_render_resized if bps == 1 else self._L.w2x_render16_resized
+        ok = bool(fn(self._h, src.ctypes.data, src.shape[0], src.shape[1], src.strides[0], dst.ctypes.data if dst.size else None, rows, cols,
+                     dst.strides[0], fid))
+        if ret_array:
+            if not ok:
+                raise W2xError(self.last_error() or "render_resized failed")
+            return dst
+        return ok
+
+    def render_sequence_resized(self, frames, size, outs=None, pinned: bool = False, filter: str = "bicubic"):
+        """render_sequence() with every frame resized to size = (rows, cols) like render_resized() (w2x_render_sequence_resized; uint8 frames).
+        outs / pinned as in render_sequence()."""
+        n = len(frames)
+        if n == 0:
+            return []
+        rows, cols = int(size[0]), int(size[1])
+        fid = _filter_id(filter)
+        r, c = frames[0].shape[:2]
+        for f in frames:
+            if f.dtype != np.uint8 or f.shape != (r, c, 3) or f.strides != (c * 3, 3, 1):
+                raise ValueError("frames must be packed uint8 [rows, cols, 3] arrays of one size")
+        own = []
+        if outs is None:
+            if pinned:
+                own = [self.alloc_host((rows, cols, 3)) for _ in range(min(n, 3))]
+            else:
+                outs = [np.empty((rows, cols, 3), np.uint8) for _ in range(n)]
+        for o in (own or outs):
+            if o.dtype != np.uint8 or o.shape != (rows, cols, 3) or o.strides != (cols * 3, 3, 1):
+                raise ValueError("outs must be packed uint8 arrays of the target size")
+
+        def run(fs, os_):
+            m = len(fs)
+            if not self._L.w2x_render_sequence_resized(self._h, (C.c_void_p * m)(*[f.ctypes.data for f in fs]), r, c, c * 3,
+                                                       (C.c_void_p * m)(*[o.ctypes.data for o in os_]), rows, cols, cols * 3, m, fid):
+                raise W2xError(self.last_error() or "render_sequence_resized failed")
+        if own:          # a ring of engine-owned buffers: the sequence in pieces, each result copied out
+            res = []
+            try:
+                for k0 in range(0, n, len(own)):
+                    m = min(len(own), n - k0)
+                    run(frames[k0:k0 + m], own[:m])
+                    res += [o.copy() for o in own[:m]]
+            finally:
+                for o in own:
+                    self.free_host(o)
+            return res
+        run(frames, outs)
+        return outs
 
     def render_strip(self, src: np.ndarray, dst: np.ndarray, part: int, parts: int) -> bool:
         """One device's share of a frame split into tile-column strips (w2x_render_strip): writes only its columns of dst."""
@@ -462,6 +539,20 @@ def tile_weights(which, ovx, ovy, size):
     if not L.w2x_tile_weights(which, ovx, ovy, size, out.ctypes.data):
         raise W2xError("bad arguments")
     return out
+
+
+def resize_weights(in_size: int, out_size: int, filter: str = "bicubic"):
+    """Tap tables of the resized renders along one axis (w2x_resize_weights) -> (first[out] int32, weights[out, taps] float32)."""
+    L = lib()
+    fid = _filter_id(filter)
+    taps = L.w2x_resize_weights(int(in_size), int(out_size), fid, None, None, 0)
+    if taps <= 0:
+        raise W2xError(f"invalid resize {in_size} -> {out_size}")
+    first = np.zeros(out_size, np.int32)
+    w = np.zeros((out_size, taps), np.float32)
+    if L.w2x_resize_weights(int(in_size), int(out_size), fid, first.ctypes.data, w.ctypes.data, w.size) != taps:
+        raise W2xError("w2x_resize_weights failed")
+    return first, w
 
 
 def describe_plan(onnx_path, batch, tile, precision=None) -> str:
