@@ -1,0 +1,188 @@
+"""Float64 references of the fused fp16 transformer kernels (k_swinattn96.hip, k_swinattn192u.hip, k_mlp96q.hip, mlp2_kernel<192,2,4> of
+k_mlp2.hip), for tests/test_gpu_transformer_kernels.py.
+
+Every operation comes in two forms:
+  * exact (`f16_model=False`): float64 throughout, no intermediate rounding - the function the kernel approximates;
+  * ideal fp16 kernel (`f16_model=True`): float64 arithmetic, rounded to fp16 at the storage points the kernels document - the LayerNorm output,
+    q / k / v, the probabilities, the head outputs, the projection / second-layer output, the GELU output and y.
+A kernel is held to "no worse than the ideal fp16 kernel, against the exact one" (the pattern of parity_util.assert_as_accurate_as_ideal_fp16).
+
+The LayerNorm gamma / beta are folded into the first matrix and bias, as lower.cpp does: LN here is the bare normalisation.  GELU is the exact
+erf form, so the kernels' degree-4 fit (W2X_GELU_DEG) is measured, not assumed.  Inputs (rows, weights, the logical bias table) are fp16 values;
+the q scale and the fp32 biases are taken as they are handed to the kernel."""
+import numpy as np
+from scipy.special import erf
+
+NTOK, WS, HEADS = 36, 6, 6
+LOG2E = 1.4426950408889634
+
+
+def f16(a):
+    return np.asarray(a, dtype=np.float64).astype(np.float16).astype(np.float64)
+
+
+def layer_norm(x, eps):
+    m = x.mean(axis=-1, keepdims=True)
+    v = ((x - m) ** 2).mean(axis=-1, keepdims=True)
+    return (x - m) / np.sqrt(v + eps)
+
+
+def gelu(h):
+    return 0.5 * h * (1.0 + erf(h / np.sqrt(2.0)))
+
+
+def row_stats(y, eps):
+    """LayerNorm statistics of rows (mean, rstd) as the kernels' stats_out holds them."""
+    y = np.asarray(y, dtype=np.float64)
+    m = y.mean(axis=-1)
+    return np.stack([m, 1.0 / np.sqrt(((y - m[..., None]) ** 2).mean(axis=-1) + eps)], axis=-1)
+
+
+# ---- windows
+def window_table(H, W, ry, rx):
+    """int32 [H*W]: window-order row (window wl = wy * W/6 + wx, token t = ty * 6 + tx) -> pixel ((wy*6+ty+ry) % H) * W + (wx*6+tx+rx) % W -
+    the closed form k_swinattn*.hip evaluate for ry >= 0, and what lower.cpp stores as the explicit table."""
+    nwy, nwx = H // WS, W // WS
+    wy, wx, ty, tx = np.meshgrid(np.arange(nwy), np.arange(nwx), np.arange(WS), np.arange(WS), indexing="ij")
+    return ((((wy * WS + ty + ry) % H) * W + (wx * WS + tx + rx) % W).reshape(-1)).astype(np.int32)
+
+
+def swin_shift_masks(H, W, shift=3):
+    """The Swin shift mask (-100 between tokens of different regions of the rolled map) as mask classes: (masks [nmask][36][36], maskid [nwin])."""
+    def region(n):
+        r = np.zeros(n, dtype=np.int64)
+        r[n - WS:n - shift] = 1
+        r[n - shift:] = 2
+        return r
+    lab = region(H)[:, None] * 3 + region(W)[None, :]
+    nwy, nwx = H // WS, W // WS
+    win = lab.reshape(nwy, WS, nwx, WS).transpose(0, 2, 1, 3).reshape(nwy * nwx, NTOK)
+    masks = np.where(win[:, :, None] != win[:, None, :], -100.0, 0.0)
+    uniq, maskid = np.unique(masks.reshape(len(masks), -1), axis=0, return_inverse=True)
+    return uniq.reshape(-1, NTOK, NTOK), maskid.reshape(-1).astype(np.int32)
+
+
+def pack_bias32(bias):
+    """numpy restatement of fragorder.h swin_bias32: logical [nmh][36][36] (fp16 values) -> fp32 * log2(e) in the kernels' load order
+    [nmh][query tile 3][key tile 0: 64 lanes x 4 | key tile 1: 64 lanes x 4 | keys 32..35: 64 lanes]."""
+    b = np.asarray(bias, dtype=np.float32).reshape(-1, NTOK, NTOK) * np.float32(LOG2E)
+    nmh = b.shape[0]
+    lane = np.arange(64)
+    fr, g = lane & 15, lane >> 4
+    out = np.zeros((nmh, 3, 576), dtype=np.float32)
+    for qt in range(3):
+        q = np.minimum(qt * 16 + fr, NTOK - 1)
+        for kt in range(2):
+            keys = kt * 16 + g[:, None] * 4 + np.arange(4)[None, :]
+            out[:, qt, kt * 256:(kt + 1) * 256] = b[:, q[:, None], keys].reshape(nmh, 256)
+        out[:, qt, 512:576] = b[:, q, 32 + g]
+    return out.reshape(-1)
+
+
+def attention(x, wqkv, bqkv, wproj, bproj, bias, maskid, table, scale, eps, f16_model=False):
+    """y = x + proj(W-MSA(LN(x))) on token maps x [B][H][W][C] (window-order row -> pixel: table), per-head rel-pos bias + mask
+    bias [nmask][heads][36][36] selected per window by maskid [nwin]."""
+    B, H, W, C = x.shape
+    nwin = H * W // NTOK
+    X = np.asarray(x, dtype=np.float64).reshape(B, H * W, C)[:, table].reshape(B * nwin, NTOK, C)
+    bw = np.broadcast_to(np.asarray(bias, dtype=np.float64)[np.asarray(maskid)][None], (B, nwin, HEADS, NTOK, NTOK)).reshape(B * nwin, HEADS, NTOK, NTOK)
+    yt = attention_windows(X, wqkv, bqkv, wproj, bproj, bw, scale, eps, f16_model).reshape(B, H * W, C)
+    y = np.empty_like(yt)
+    y[:, table] = yt
+    return y.reshape(B, H, W, C)
+
+
+def attention_windows(X, wqkv, bqkv, wproj, bproj, bw, scale, eps, f16_model=False):
+    """The same on windows: X [n][36][C] tokens in window order, bw [n][heads][36][36] the bias of each window's class -> y tokens."""
+    r = f16 if f16_model else (lambda a: a)
+    n, _, C = X.shape
+    hd = C // HEADS
+    xn = r(layer_norm(X, eps))
+    wq, wk, wv = (np.asarray(wqkv, dtype=np.float64)[i * C:(i + 1) * C] for i in range(3))
+    bq, bk, bv = (np.asarray(bqkv, dtype=np.float64)[i * C:(i + 1) * C] for i in range(3))
+    heads = lambda a: a.reshape(n, NTOK, HEADS, hd).transpose(0, 2, 1, 3)     # [n][heads][36][hd]
+    if f16_model:
+        # the kernels: q rounded after the scale, k without its bias (it adds the same q.bk to every key of a query: the softmax drops it),
+        # v without its bias (added to the normalised output: the weighted mean commutes with it)
+        q, k, v = heads(r((xn @ wq.T + bq) * scale)), heads(r(xn @ wk.T)), heads(r(xn @ wv.T))
+    else:
+        q, k, v = heads((xn @ wq.T + bq) * scale), heads(xn @ wk.T + bk), heads(xn @ wv.T + bv)
+    s = q @ k.transpose(0, 1, 3, 2) + bw
+    e = np.exp(s - s.max(axis=-1, keepdims=True))
+    if f16_model:
+        e = r(e)
+        o = r(e @ v / e.sum(axis=-1, keepdims=True) + bv.reshape(HEADS, 1, hd))
+    else:
+        o = e @ v / e.sum(axis=-1, keepdims=True)
+    o = o.transpose(0, 2, 1, 3).reshape(n, NTOK, C)
+    pr = r(o @ np.asarray(wproj, dtype=np.float64).T + bproj)
+    return r(X + pr)
+
+
+def mlp(x, w1, b1, w2, b2, eps, f16_model=False):
+    """y = x + W2 gelu(W1 LN(x) + b1) + b2 on rows x [M][C] (exact erf GELU)."""
+    r = f16 if f16_model else (lambda a: a)
+    x = np.asarray(x, dtype=np.float64)
+    h = r(layer_norm(x, eps)) @ np.asarray(w1, dtype=np.float64).T + b1
+    o = r(r(gelu(h)) @ np.asarray(w2, dtype=np.float64).T + b2)
+    return r(x + o)
+
+
+def image_head(y, tiw, tib, B, Mrows, aW, clip=None, f16_model=False):
+    """The image head folded into the C = 96 MLP: Linear 96 -> 64 per row, optional Clip, DepthToSpace(4): out[b][4 oy + dy][4 ox + dx][ch]
+    = head[row b * Mrows + oy * aW + ox][16 dy + 4 dx + ch]."""
+    r = f16 if f16_model else (lambda a: a)
+    h = r(np.asarray(y, dtype=np.float64) @ np.asarray(tiw, dtype=np.float64).T + tib)
+    if clip is not None:
+        h = np.clip(h, clip[0], clip[1])
+    Hr = Mrows // aW
+    return h.reshape(B, Hr, aW, 4, 4, 4).transpose(0, 1, 3, 2, 4, 5).reshape(B, 4 * Hr, 4 * aW, 4)
+
+
+# ---- the large-input formula (tools/kernel_check/transformer_check.cpp gen_x16)
+_M64 = (1 << 64) - 1
+
+
+def gen_rows(rows, C, seed):
+    """fp16 rows of the run-splitting cases at global row indices `rows`: k / 256 - 2, channels 0..2 the row index in 10-bit digits, the
+    others a splitmix64 hash of (row, channel, seed) - identical to transformer_check.cpp gen_x16."""
+    rows = np.asarray(rows, dtype=np.uint64)
+    k = np.empty((len(rows), C), dtype=np.uint64)
+    for c in range(3):
+        k[:, c] = (rows >> np.uint64(10 * c)) & np.uint64(1023)
+    with np.errstate(over="ignore"):
+        z = rows[:, None] * np.uint64(C) + np.arange(3, C, dtype=np.uint64)[None, :] + np.uint64((seed * 0x9E3779B97F4A7C15) & _M64)
+        z = (z ^ (z >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+        z = (z ^ (z >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+        z ^= z >> np.uint64(31)
+    k[:, 3:] = z >> np.uint64(54)
+    return (k.astype(np.float64) / 256.0 - 2.0).astype(np.float16)
+
+
+# ---- metrics
+def ulp16(a):
+    """ULP of fp16 at |a| (normal range; subnormal spacing below 2^-14)."""
+    return np.exp2(np.floor(np.log2(np.maximum(np.abs(a), 2.0 ** -14))) - 10)
+
+
+def error_metrics(got, exact):
+    """Error of `got` against the exact reference in units of ulp16(|exact|): max, rms, fraction within 1 ULP16, mean signed error.  |exact| is
+    floored at a quarter of the tensor's rms: the outputs are sums (x + branch) whose rounding does not shrink where the sum cancels."""
+    exact = np.asarray(exact, dtype=np.float64)
+    floor = 0.25 * np.sqrt(np.mean(exact * exact))
+    d = (np.asarray(got, dtype=np.float64) - exact) / ulp16(np.maximum(np.abs(exact), floor))
+    if not np.isfinite(d).all():
+        return {"max_ulp": float("inf"), "rms_ulp": float("inf"), "frac_1ulp": 0.0, "mean_ulp": float("nan"), "n": int(d.size)}
+    return {"max_ulp": float(np.abs(d).max()), "rms_ulp": float(np.sqrt(np.mean(d * d))), "frac_1ulp": float((np.abs(d) <= 1.0).mean()),
+            "mean_ulp": float(d.mean()), "n": int(d.size)}
+
+
+# ---- the harness (tools/kernel_check/transformer_check.cpp): host code only, built like the w2x command line
+def build_harness(exe):
+    import os
+    import subprocess
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    subprocess.run(["g++", "-std=c++17", "-O2", "-fopenmp", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
+                    "-I" + os.path.join(root, "waifu2x-tensorrt_amd", "csrc"), os.path.join(root, "tools", "kernel_check", "transformer_check.cpp"),
+                    "-o", str(exe), "-L/opt/rocm/lib", "-lamdhip64", "-ldl", "-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=300)
+    return str(exe)

@@ -10,6 +10,8 @@ import subprocess
 import pytest
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+# waifu2x-tensorrt_amd/Makefile: KFLAGS of k_mlp2.o / k_mlp96q.o
+MAKEFILE_MLP_FLAGS = ["-mllvm", "-amdgpu-sched-strategy=max-ilp", "-fno-honor-nans"]
 
 
 @pytest.mark.gpu
@@ -17,8 +19,14 @@ def test_fused_mlp_kernels_agree_and_are_deterministic(tmp_path):
     hipcc = shutil.which("hipcc") or "/opt/rocm/bin/hipcc"
     csrc = os.path.join(ROOT, "waifu2x-tensorrt_amd", "csrc")
     exe = str(tmp_path / "mlp_ab")
-    subprocess.run([hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", csrc, os.path.join(ROOT, "tools", "ab", "mlp_ab.hip"),
-                    os.path.join(ROOT, "tools", "ab", "k_mlp_staged.hip"), os.path.join(csrc, "k_mlp2.hip"), os.path.join(csrc, "k_mlp96q.hip"), "-o", exe], check=True, timeout=900)
+    # the shipped kernel files with the Makefile's per-file flags (the library's objects), the harness and the retired kernel with plain -O3
+    base = [hipcc, "--offload-arch=gfx950", "-O3", "-std=c++17", "-I", csrc]
+    objs = []
+    for src, flags in ((os.path.join(csrc, "k_mlp2.hip"), MAKEFILE_MLP_FLAGS), (os.path.join(csrc, "k_mlp96q.hip"), MAKEFILE_MLP_FLAGS),
+                       (os.path.join(ROOT, "tools", "ab", "mlp_ab.hip"), []), (os.path.join(ROOT, "tools", "ab", "k_mlp_staged.hip"), [])):
+        objs.append(str(tmp_path / (os.path.basename(src) + ".o")))
+        subprocess.run(base + flags + ["-c", src, "-o", objs[-1]], check=True, timeout=900)
+    subprocess.run([hipcc, "--offload-arch=gfx950"] + objs + ["-o", exe], check=True, timeout=900)
     out = subprocess.run([exe], check=True, capture_output=True, text=True, timeout=600).stdout
     cases = re.findall(r"C=(\d+) M=(\d+) stats=(\d): max\|dy\|=([0-9.]+) .*max rel stats diff=([0-9.e+-]+)", out)
     assert len(cases) >= 18, out

@@ -1,0 +1,126 @@
+"""CPU checks of the float64 references in tests/kernel_ref.py and of the host side of tools/kernel_check/transformer_check.cpp: the references
+against an independent torch formulation, the packed attention bias table (fragorder.h swin_bias32, the one function lower.cpp and the harness
+share) against the logical table, and the large-input formula of the C++ harness against its Python twin."""
+import json
+import os
+
+import numpy as np
+import torch
+import torch.nn.functional as F
+
+import kernel_ref as kr
+
+
+def _weights(rng, n, k, s=None):
+    return kr.f16(rng.normal(0, s if s is not None else 1 / np.sqrt(k), (n, k)))
+
+
+def test_attention_reference_matches_torch_float64():
+    rng = np.random.default_rng(1)
+    for C, H, W, ry in ((96, 12, 18, 3), (192, 6, 12, 0)):
+        B, hd = 2, C // 6
+        x = kr.f16(rng.normal(0, 1, (B, H, W, C)))
+        wqkv, wproj = _weights(rng, 3 * C, C), _weights(rng, C, C)
+        bqkv, bproj = rng.normal(0, 0.1, 3 * C), rng.normal(0, 0.1, C)
+        masks, maskid = kr.swin_shift_masks(H, W) if ry else (np.zeros((1, 36, 36)), np.zeros(H * W // 36, np.int32))
+        bias = kr.f16(rng.normal(0, 1, (len(masks), 6, 36, 36)) + masks[:, None])
+        table = kr.window_table(H, W, ry, ry)
+        scale = hd ** -0.5
+        got = kr.attention(x, wqkv, bqkv, wproj, bproj, bias, maskid, table, scale, 1e-5)
+        # torch: roll + window partition as the ONNX graph spells it, per-window loops over heads
+        t = torch.from_numpy(x).roll((-ry, -ry), dims=(1, 2))
+        win = t.reshape(B, H // 6, 6, W // 6, 6, C).permute(0, 1, 3, 2, 4, 5).reshape(B, -1, 36, C)
+        xn = F.layer_norm(win, (C,), eps=1e-5)
+        qkv = xn @ torch.from_numpy(wqkv).T + torch.from_numpy(bqkv)
+        q, k, v = (qkv[..., i * C:(i + 1) * C].reshape(B, -1, 36, 6, hd).transpose(2, 3) for i in range(3))
+        a = torch.softmax(q @ k.transpose(-1, -2) * scale + torch.from_numpy(bias)[torch.from_numpy(maskid).long()], dim=-1)
+        o = (a @ v).transpose(2, 3).reshape(B, -1, 36, C) @ torch.from_numpy(wproj).T + torch.from_numpy(bproj) + win
+        o = o.reshape(B, H // 6, W // 6, 6, 6, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, C).roll((ry, ry), dims=(1, 2))
+        assert np.abs(got - o.numpy()).max() <= 1e-12
+        # the ideal fp16 kernel is an fp16 evaluation of the same function: within a few fp16 ULP
+        ideal = kr.attention(x, wqkv, bqkv, wproj, bproj, bias, maskid, table, scale, 1e-5, f16_model=True)
+        assert kr.error_metrics(ideal, got)["max_ulp"] < 8
+
+
+def test_mlp_and_head_reference_match_torch_float64():
+    rng = np.random.default_rng(2)
+    for C in (96, 192):
+        x = kr.f16(rng.normal(0, 1, (300, C)))
+        w1, w2 = _weights(rng, 2 * C, C, 3.0 / np.sqrt(C)), _weights(rng, C, 2 * C)
+        b1, b2 = rng.normal(0, 0.1, 2 * C), rng.normal(0, 0.1, C)
+        got = kr.mlp(x, w1, b1, w2, b2, 1e-5)
+        t = torch.from_numpy(x)
+        h = F.linear(F.layer_norm(t, (C,), eps=1e-5), torch.from_numpy(w1), torch.from_numpy(b1))
+        ref = t + F.linear(F.gelu(h, approximate="none"), torch.from_numpy(w2), torch.from_numpy(b2))
+        assert np.abs(got - ref.numpy()).max() <= 1e-12
+        assert np.abs(h.numpy()).max() > 6.5      # the GELU clamp region is reached
+    tiw, tib = _weights(rng, 64, 96), rng.normal(0, 0.1, 64)
+    y = kr.f16(rng.normal(0, 1, (2 * 64 * 8, 96)))
+    got = kr.image_head(y, tiw, tib, 2, 64 * 8, 64, clip=(0.0, 1.0))
+    # DepthToSpace(4), DCR order: output column 16 dy + 4 dx + ch of row (oy, ox) -> pixel (4 oy + dy, 4 ox + dx), channel ch
+    h = torch.clamp(F.linear(torch.from_numpy(y), torch.from_numpy(tiw), torch.from_numpy(tib)), 0, 1).reshape(2, 8, 64, 4, 4, 4)
+    ref = h.permute(0, 1, 3, 2, 4, 5).reshape(2, 32, 256, 4)
+    assert np.abs(got - ref.numpy()).max() <= 1e-12
+
+
+def test_stats_reference():
+    rng = np.random.default_rng(3)
+    y = kr.f16(rng.normal(5, 2, (50, 96)))
+    s = kr.row_stats(y, 1e-5)
+    t = torch.from_numpy(y)
+    assert np.abs(s[:, 0] - t.mean(-1).numpy()).max() <= 1e-12
+    assert np.abs(s[:, 1] - torch.rsqrt(t.var(-1, unbiased=False) + 1e-5).numpy()).max() <= 1e-12
+
+
+def test_window_table_and_shift_masks():
+    t = kr.window_table(12, 18, 3, 3)
+    assert sorted(t.tolist()) == list(range(12 * 18))
+    masks, maskid = kr.swin_shift_masks(12, 18)
+    # 2 x 3 windows: interior (unmasked) | last column | last row | corner
+    m = maskid.tolist()
+    assert len(masks) == 4 and m[0] == m[1] and m[3] == m[4] and len({m[0], m[2], m[3], m[5]}) == 4
+    assert (masks[m[0]] == 0).all() and (masks[m[5]] == -100).sum() == 36 * 36 - 4 * 9 * 9   # the corner: four regions of 3 x 3 tokens
+
+
+def test_packed_bias_table_round_trips(tmp_path):
+    """fragorder.h swin_bias32 (built into the harness; lower.cpp calls the same function) against the logical table: every packed entry is
+    logical * log2(e) at the (query, key) its lane order names, and the numpy restatement gives the same bits."""
+    exe = kr.build_harness(tmp_path / "transformer_check")
+    rng = np.random.default_rng(4)
+    nmh = 4 * 6
+    bias = rng.normal(0, 2, (nmh, 36, 36)).astype(np.float16)
+    bias.tofile(tmp_path / "bias.bin")
+    import subprocess
+    subprocess.run([exe, "--pack-bias", str(tmp_path), str(nmh)], check=True, timeout=60)
+    packed = np.fromfile(tmp_path / "bias32.bin", dtype=np.float32)
+    assert packed.tobytes() == kr.pack_bias32(bias).tobytes()
+    p = packed.reshape(nmh, 3, 576)
+    lane = np.arange(64)
+    fr, g = lane & 15, lane >> 4
+    logical = np.full((nmh, 36, 36), np.nan, dtype=np.float32)
+    for qt in range(3):
+        for kt in range(2):
+            for j in range(4):
+                q, k = qt * 16 + fr, kt * 16 + 4 * g + j
+                ok = q < 36
+                logical[:, q[ok], k[ok]] = p[:, qt, kt * 256 + lane[ok] * 4 + j]
+        q = qt * 16 + fr
+        ok = q < 36
+        logical[:, q[ok], 32 + g[ok]] = p[:, qt, 512 + lane[ok]]
+    assert not np.isnan(logical).any()
+    assert np.array_equal(logical, bias.astype(np.float32) * np.float32(kr.LOG2E))
+
+
+def test_large_input_formula_matches_the_harness(tmp_path):
+    exe = kr.build_harness(tmp_path / "transformer_check")
+    rng = np.random.default_rng(5)
+    for C in (96, 192):
+        rows = np.concatenate([np.arange(8), rng.integers(0, 1 << 31, 500), [(1 << 30) - 1, 11_184_810, 22_369_619]]).astype(np.int64)
+        rows.tofile(tmp_path / "gen.rows")
+        (tmp_path / "gen.json").write_text(json.dumps({"C": C, "seed": 77, "nrows": len(rows)}))
+        import subprocess
+        subprocess.run([exe, "--gen-only", str(tmp_path)], check=True, timeout=60, env=dict(os.environ, HIP_VISIBLE_DEVICES=""))
+        got = np.fromfile(tmp_path / "gen.bin", dtype=np.float16).reshape(-1, C)
+        want = kr.gen_rows(rows, C, 77)
+        assert got.tobytes() == want.tobytes()
+        assert len({r.tobytes() for r in want}) == len(set(rows.tolist()))     # distinct rows stay distinct

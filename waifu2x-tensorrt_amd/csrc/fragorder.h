@@ -7,6 +7,8 @@
 #include <stdexcept>
 #include <vector>
 
+#include "common.h"
+
 namespace w2x {
 
 // W [N][K] row-major -> [N/16 row tiles][K/32 k-steps][64 lanes][8]: lane = (row & 15) + 16 * g holds columns ks*32 + 8g .. +7
@@ -87,6 +89,27 @@ inline std::vector<uint16_t> frag32_w2(const uint16_t* w, int C) {
                         f[((((size_t)ch * NT + nt) * 2 + s) * 64 + lane) * 8 + e] = w[(size_t)(nt * 32 + (lane & 31)) * H2 + hid];
                     }
     return f;
+}
+
+// Rel-pos bias (+ shift mask) of the fused attention (k_swinattn96.hip, k_swinattn192u.hip).  Logical table: fp16 bits [nmh = nmask * heads][ntok][ntok]
+// (query, key) -> fp32 * log2(e) in the kernels' load order, so that every wave load is one contiguous 1 KB (or 256 B) block:
+// [nmh][query tile 3][ A: key tile 0 [64 lanes][4] | B: key tile 1 [64 lanes][4] | C: keys 32..35 [64 lanes][1] ],
+// lane = 16*g + fr <-> query 16*qt + fr, keys 16*kt + 4*g + j.  Queries past ntok repeat the last one (their scores are never stored).
+inline std::vector<float> swin_bias32(const uint16_t* src, int nmh, int ntok) {
+    if (ntok != 36) throw std::runtime_error("swin_bias32: window");
+    const int per_qt = 64 * 4 * 2 + 64, per_unit = 3 * per_qt;
+    std::vector<float> t((size_t)nmh * per_unit, 0.f);
+    auto at = [&](int m2, int qq, int kk) -> float {
+        if (qq >= ntok) qq = ntok - 1;
+        return f16_to_f32(src[((size_t)m2 * ntok + qq) * ntok + kk]) * 1.44269504088896341f;
+    };
+    for (int m2 = 0; m2 < nmh; ++m2) for (int qt = 0; qt < 3; ++qt) for (int lane = 0; lane < 64; ++lane) {
+        const int fr = lane & 15, gg = lane >> 4, qq = qt * 16 + fr;
+        float* base = &t[(size_t)m2 * per_unit + (size_t)qt * per_qt];
+        for (int kt = 0; kt < 2; ++kt) for (int j = 0; j < 4; ++j) base[kt * 256 + lane * 4 + j] = at(m2, qq, kt * 16 + gg * 4 + j);
+        base[512 + lane] = at(m2, qq, 32 + gg);
+    }
+    return t;
 }
 
 }  // namespace w2x

@@ -477,8 +477,10 @@ hipError_t launch_mlp96q(const MlpParams& p, hipStream_t s) {
         if (hipError_t e = hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev); e != hipSuccess) return e;
         __atomic_store_n(&cus[dev & 31], ncu, __ATOMIC_RELAXED);
     }
-    // the kernel addresses x / y with 32-bit byte offsets (and prefetches one tile stride past its last tile): longer passes run in pieces
-    const long max_rows = (long)((kMaxBufBytes / (C * 2)) / RW) * RW;
+    // the kernel addresses x / y with 32-bit byte offsets and prefetches one tile stride (NWV tiles per workgroup) past its last tile: longer passes
+    // run in pieces that leave room for that stride (a pass of kMaxBufBytes alone would not: tests/test_gpu_transformer_kernels.py split_mlp96_head)
+    const long max_tiles = std::min<long>((long)(kMaxBufBytes / (RW * C * 2)), 0xFFFFFFFFl / (RW * C * 2) - (long)ncu * NWV);
+    const long max_rows = max_tiles * RW;
     for (long r0 = 0; r0 < p.M; r0 += max_rows) {
         MlpParams q = p;
         q.M = std::min(max_rows, p.M - r0);
@@ -486,7 +488,7 @@ hipError_t launch_mlp96q(const MlpParams& p, hipStream_t s) {
         if (p.stats_out) q.stats_out = p.stats_out + 2 * r0;
         const long ntiles = (q.M + RW - 1) / RW;
         const int grid = (int)std::min<long>((ntiles + NWV - 1) / NWV, ncu);
-        if ((ntiles + (long)grid * NWV) * (long)(RW * C * 2) > 0xFFFFFFFFl) return hipErrorInvalidValue;   // (cannot happen below kMaxBufBytes with <= 1024 CUs)
+        if ((ntiles + (long)grid * NWV) * (long)(RW * C * 2) > 0xFFFFFFFFl) return hipErrorInvalidValue;   // (cannot happen: max_tiles)
         if (p.ti_w) {
             q.ti_row0 = r0;
             hipLaunchKernelGGL(mlp96q_kernel<true>, dim3(grid), dim3(NTHR), SMEM96Q, s, q, (int)ntiles);
