@@ -233,20 +233,24 @@ struct Img2Img::Impl {
     std::vector<int> pool_blocks;        // per tensor id: pooling partials per image written by the last producer (0: plan default)
     void* arena_base = nullptr; size_t arena_bytes = 0;
     std::vector<GemmParams> gemm;      // per op (kind == OP_GEMM)
-    std::vector<int> pool_tensors;
     int final_op = -1;
-    std::vector<int> tensor_last;      // last op that touches each tensor (upload_plan)
-    std::vector<char> fuse_up;         // op i is a pixel-shuffle projection (cunet's ConvTranspose) whose map only feeds the 64 -> 64 3x3 convolution that follows: op i + 1's launch computes it in its halo stage (k_conv3.hip conv3_kernel UP), op i is skipped
-    std::vector<char> fuse_stem;       // op i is a stem convolution whose 48- / 32-channel map only feeds the 3x3 convolution that follows: op i + 1's launch computes it in its halo stage (k_conv48.hip; k_conv3.hip for cunet), op i is skipped
-    std::vector<char> fuse_head;       // op i is a C = 96 MLP whose rows only feed the image head that follows: one launch (k_mlp96q.hip), op i + 1 is skipped
-    // fp32 plans: op i (LayerNorm + fc1 + GELU) and op i + 1 (fc2 + residual) are one mlp32_kernel launch when the engine runs Precision::TF32 (k_f32.hip); the hidden
-    // map between them is neither written nor read.  mlp32_w[i] = the bf16 hi / lo planes of both matrices in fragment-major order (device memory, freed by release())
-    std::vector<char> fuse_mlp32;
-    std::vector<std::array<void*, 4>> mlp32_w;
-    // ... and op i (LayerNorm + window gather + qkv), op i + 1 (attention core), op i + 2 (proj + window scatter + residual) are one swinattn32_kernel launch;
-    // attn32_w[i] = the planes of Wqkv and Wproj
-    std::vector<char> fuse_attn32;
-    std::vector<std::array<void*, 4>> attn32_w;
+    // The launches of one network pass, decided once per load() (upload_plan) and walked by run_network().  A fold computes several neighbouring plan ops
+    // in one launch; the map between them is neither stored nor read:
+    //  head   - a C = 96 MLP and the image head behind it (k_mlp96q.hip)
+    //  stem   - a stem convolution and the 3x3 convolution behind it, which computes the 48- / 32-channel map in its halo stage (k_conv48.hip; k_conv3.hip for cunet)
+    //  up     - cunet's pixel-shuffle projection (ConvTranspose) and the 64 -> 64 3x3 convolution behind it, which computes it in its halo stage (k_conv3.hip UP)
+    //  mlp32  - fp32 plans at Precision::TF32: LayerNorm + fc1 + GELU and fc2 + residual (k_f32.hip mlp32_kernel)
+    //  attn32 - the same: LayerNorm + window gather + qkv, attention core, proj + window scatter + residual (k_f32.hip swinattn32_kernel)
+    enum LaunchKind { L_OP, L_HEAD, L_STEM, L_UP, L_MLP32, L_ATTN32 };
+    struct Launch {
+        LaunchKind kind = L_OP;
+        int first = 0, last = 0;      // the plan ops it computes
+        int timed = 0;                // the op whose op_ms slot receives its time (profileFrame / opTimes)
+        double flops = 0;
+        int family = 0;               // profileFrame's kernel family (stamp_begin)
+        std::array<void*, 4> planes{{nullptr, nullptr, nullptr, nullptr}};   // mlp32 / attn32: bf16 hi / lo planes of both matrices, fragment-major (freed by release())
+    };
+    std::vector<Launch> launches;
 
     // frame-level buffers (grown on demand, reused across frames like the reference's input/output GpuMats, img2img.h:37-38)
     bool deep = false;                   // the frame in d_frame / d_out has 16-bit samples (Image::depth == 16)
@@ -285,11 +289,10 @@ struct Img2Img::Impl {
     bool profiling = false;
     struct Stamp { int kind; hipEvent_t a, b; double flops; int op; };
     std::vector<double> op_ms;   // per plan op, summed over the batches of the profiled frame
-    int cur_op = -1;
     std::vector<Stamp> stamps;
-    void stamp_begin(int kind, double flops) {
+    void stamp_begin(int kind, double flops, int op = -1) {
         if (!profiling) return;
-        Stamp st{kind, nullptr, nullptr, flops, cur_op};
+        Stamp st{kind, nullptr, nullptr, flops, op};
         hipAssert(hipEventCreate(&st.a)); hipAssert(hipEventCreate(&st.b));
         hipAssert(hipEventRecord(st.a, stream));
         stamps.push_back(st);
@@ -364,11 +367,9 @@ struct Img2Img::Impl {
         frag_blobs.clear();
         for (void* p : perm_blobs) if (p) (void)hipFree(p);
         perm_blobs.clear();
-        for (auto& w : mlp32_w) for (void* p : w) if (p) (void)hipFree(p);
-        mlp32_w.clear(); fuse_mlp32.clear();
-        for (auto& w : attn32_w) for (void* p : w) if (p) (void)hipFree(p);
-        attn32_w.clear(); fuse_attn32.clear();
-        tensors.clear(); blobs.clear(); gemm.clear(); pool_tensors.clear();
+        for (const Launch& L : launches) for (void* p : L.planes) if (p) (void)hipFree(p);
+        launches.clear();
+        tensors.clear(); blobs.clear(); gemm.clear();
         for (void* h : pinned) if (hipHostUnregister(h) != hipSuccess) (void)hipGetLastError();
         pinned.clear();
         // (allocHost() buffers belong to the caller's frames and outlive a re-load: they go in the destructor)
@@ -406,18 +407,54 @@ struct Img2Img::Impl {
         return t;
     }
 
+    // The tensors an op reads and writes: the one table behind the arena's lifetimes and the fold tests
+    struct TensorUse { std::array<int, 6> rd; std::array<int, 3> wr; };
+    static TensorUse tensor_use(const Op& op) {
+        TensorUse u; u.rd.fill(-1); u.wr.fill(-1);
+        switch (op.kind) {
+            case OP_GEMM: u.rd = {{op.g.a.t, op.g.res.t, op.g.res2.t, op.g.stats_in, op.g.se_scale, op.g.res_scale}}; u.wr = {{op.g.out.t, op.g.stats_out, op.g.pool_out}}; break;
+            case OP_ATTN: u.rd[0] = op.at.qkv; u.wr[0] = op.at.out; break;
+            case OP_SE: u.rd[0] = op.se.pool; u.wr[0] = op.se.scale; break;
+            case OP_SCALE_ADD: u.rd = {{op.se.pool, op.se.scale, -1, -1, -1, -1}}; u.wr[0] = op.se.pool; break;      // (in place)
+            case OP_MLP: u.rd[0] = op.m.x; u.wr = {{op.m.y, op.m.stats_out, -1}}; break;
+            case OP_SWINATTN: u.rd[0] = op.sa.x; u.wr = {{op.sa.y, op.sa.stats_out, -1}}; break;
+            default: break;
+        }
+        return u;
+    }
+    // Every tensor's lifetime [first op, last op] when the pass runs as the launches `ls`: everything a launch touches is live across the whole launch (a fold
+    // writes its last op's outputs while other workgroups still read its first op's inputs).  The input is written before op 0 (gather), the output read after the last op.
+    struct Lifetimes { std::vector<int> first, last; };
+    Lifetimes lifetimes(const std::vector<Launch>& ls) const {
+        const int nops = (int)plan.ops.size();
+        Lifetimes lt{std::vector<int>(plan.tensors.size(), nops), std::vector<int>(plan.tensors.size(), -1)};
+        for (const Launch& L : ls)
+            for (int i = L.first; i <= L.last; ++i) {
+                const TensorUse u = tensor_use(plan.ops[i]);
+                auto touch = [&](int t) { if (t >= 0) { lt.first[t] = std::min(lt.first[t], L.first); lt.last[t] = std::max(lt.last[t], L.last); } };
+                for (int t : u.rd) touch(t);
+                for (int t : u.wr) touch(t);
+            }
+        lt.first[plan.in_tensor] = -1;
+        lt.last[plan.out_tensor] = nops;
+        return lt;
+    }
+    // t is op i's output and only op i + 1 reads it (over the plan's own lifetimes: no other op touches it, and it is not the pass's output)
+    static bool passes_on(const Lifetimes& lt, int t, int i) { return t >= 0 && lt.first[t] == i && lt.last[t] == i + 1; }
+    Launch launch(LaunchKind kind, int first, int last) const {
+        static constexpr int kFamily[] = {0, 1, 2, 2, 5, 1};   // per OpKind: gemm, attention, se / scale, fused mlp (profileFrame's out[5 * k])
+        Launch L; L.kind = kind; L.first = first; L.last = last;
+        L.timed = kind == L_STEM || kind == L_UP ? first + 1 : first;     // (the convolution's launch computes the op in front of it)
+        const int k = plan.ops[first].kind;
+        L.family = kind == L_ATTN32 ? 1 : k >= 0 && k < 6 ? kFamily[k] : 0;
+        if (L.family != 2) for (int i = first; i <= last; ++i) L.flops += plan.ops[i].flops;   // (squeeze-excite launches are not priced)
+        return L;
+    }
+
     // fp32 plans, Precision::TF32: which runs of un-fused ops one fused launch of k_f32.hip serves.  Facts of the plan alone (lower.cpp's fuse_mlp() / fuse_attn() state
     // the same patterns for the fp16 plan); the plan itself stays un-fused - one lowering serves TF32 and FP32, and Precision::FP32 runs every launch.
     bool whole_view(const View& v) const { if (v.t < 0) return false; const TensorDesc& t = plan.tensors[v.t]; return v.y0 == 0 && v.x0 == 0 && v.H == t.H && v.W == t.W; }
-    int readers_of(int t) const {
-        int n = 0;
-        for (const Op& o : plan.ops) {
-            if (o.kind == OP_GEMM && (o.g.a.t == t || o.g.res.t == t || o.g.res2.t == t)) ++n;
-            if (o.kind == OP_ATTN && o.at.qkv == t) ++n;
-        }
-        return n;
-    }
-    bool mlp32_pair(size_t i) const {
+    bool mlp32_pair(size_t i, const Lifetimes& lt) const {
         if (plan.elt != 4 || switches().no_fuse || i + 1 >= plan.ops.size() || plan.ops[i].kind != OP_GEMM || plan.ops[i + 1].kind != OP_GEMM) return false;
         const GemmOp& g1 = plan.ops[i].g; const GemmOp& g2 = plan.ops[i + 1].g;
         const int Cm = g1.K;
@@ -426,10 +463,10 @@ struct Img2Img::Impl {
                g1.Mrows == plan.tensors[g1.a.t].H * plan.tensors[g1.a.t].W &&
                g2.amode == A_ROWS && !g2.ln && g2.act == ACT_NONE && g2.omode == O_ROWS && g2.a.t == g1.out.t && g2.K == 2 * Cm && g2.N == Cm && g2.res.t == g1.a.t && g2.res2.t < 0 &&
                !g2.has_clip && g2.pool_out < 0 && g2.se_scale < 0 && g2.res_scale < 0 && whole_view(g2.a) && whole_view(g2.res) && whole_view(g2.out) && plan.tensors[g2.out.t].C == Cm && g2.Mrows == g1.Mrows &&
-               g1.out.t != plan.out_tensor && readers_of(g1.out.t) == 1 &&
+               passes_on(lt, g1.out.t, (int)i) &&
                plan.blobs[g1.w].data.size() == (size_t)2 * Cm * Cm * 4 && plan.blobs[g2.w].data.size() == (size_t)2 * Cm * Cm * 4;      // fp32 [2C][C] and [C][2C], rows unpadded
     }
-    bool attn32_triple(size_t i) const {
+    bool attn32_triple(size_t i, const Lifetimes& lt) const {
         if (plan.elt != 4 || switches().no_fuse || switches().no_fuse_attn || i + 2 >= plan.ops.size() || plan.ops[i].kind != OP_GEMM || plan.ops[i + 1].kind != OP_ATTN || plan.ops[i + 2].kind != OP_GEMM) return false;
         const GemmOp& g1 = plan.ops[i].g; const AttnOp& a = plan.ops[i + 1].at; const GemmOp& g2 = plan.ops[i + 2].g;
         const int Cm = g1.K;
@@ -441,8 +478,46 @@ struct Img2Img::Impl {
                g2.amode == A_ROWS && g2.a.t == a.out && !g2.ln && g2.act == ACT_NONE && g2.omode == O_WIN && g2.win_table >= 0 && g2.K == Cm && g2.N == Cm && g2.res.t == g1.a.t && g2.res2.t < 0 &&
                !g2.has_clip && g2.pool_out < 0 && g2.se_scale < 0 && g2.res_scale < 0 && whole_view(g2.a) && whole_view(g2.res) && whole_view(g2.out) && plan.tensors[g2.out.t].C == Cm &&
                plan.tensors[g2.out.t].H * plan.tensors[g2.out.t].W == g1.Mrows && g2.Mrows == g1.Mrows &&
-               g1.out.t != plan.out_tensor && a.out != plan.out_tensor && readers_of(g1.out.t) == 1 && readers_of(a.out) == 1 &&
+               passes_on(lt, g1.out.t, (int)i) && passes_on(lt, a.out, (int)i + 1) &&
                plan.blobs[g1.w].data.size() == (size_t)3 * Cm * Cm * 4 && plan.blobs[g2.w].data.size() == (size_t)Cm * Cm * 4;
+    }
+    // The candidate launches of a pass: the folds that plan facts, the load's switches and its precision allow.  upload_plan() lays the arena out for them and then
+    // confirms or splits each with the prepared launch parameters.  No op but a launch's last may write the pass's output (out_override replaces the last op's).
+    std::vector<Launch> candidate_launches(Precision prec) const {
+        const int nops = (int)plan.ops.size();
+        std::vector<Launch> ls;
+        for (int i = 0; i < nops; ++i) ls.push_back(launch(L_OP, i, i));
+        const Lifetimes lt = lifetimes(ls);
+        ls.clear();
+        const bool fp16 = plan.elt == 2 && !check_general, tf32 = plan.elt == 4 && prec == Precision::TF32;   // (W2X_CHECK_GENERAL compares every shape-specialised launch alone)
+        // the image head (Linear 96 -> 4x4 sub-pixels x 4 channels) behind a C = 96 MLP: it rides on k_mlp96q.hip's launch only
+        auto head = [&](const Op& a, const Op& b, int i) {
+            return !switches().no_fuse_head && mlp_frag32(96) && a.kind == OP_MLP && b.kind == OP_GEMM && a.m.C == 96 && a.m.stats_out < 0 && b.g.a.t == a.m.y && passes_on(lt, a.m.y, i) &&
+                   b.g.amode == A_ROWS && b.g.K == 96 && b.g.N == 64 && b.g.r == 4 && b.g.omode == O_PIXSHUF && b.g.res.t < 0 && b.g.res2.t < 0 && b.g.act == ACT_NONE && !b.g.ln &&
+                   b.g.se_scale < 0 && b.g.res_scale < 0 && b.g.stats_out < 0 && b.g.pool_out < 0;
+        };
+        // the stem (3x3, 4 -> 48 / 32 channels) in front of the 3x3 convolution that alone reads it
+        auto stem = [&](const Op& a, const Op& b, int i) {
+            return a.kind == OP_GEMM && b.kind == OP_GEMM && a.g.a.t >= 0 && plan.tensors[a.g.a.t].C == 4 && ((a.g.N == 48 && b.g.K == 9 * 48) || (a.g.N == 32 && b.g.K == 9 * 32 && b.g.N == 64 && b.g.pool_out < 0)) &&
+                   b.g.a.t == a.g.out.t && passes_on(lt, a.g.out.t, i) && a.g.stats_out < 0 && a.g.pool_out < 0;
+        };
+        // cunet's ConvTranspose 2x2 stride 2 (a pixel-shuffle projection with a skip add) in front of the 64 -> 64 3x3 convolution that alone reads it
+        auto up = [&](const Op& a, const Op& b, int i) {
+            return a.kind == OP_GEMM && b.kind == OP_GEMM && a.g.omode == O_PIXSHUF && a.g.r == 2 && a.g.K == 64 && a.g.N == 256 && a.g.res.t >= 0 && a.g.res2.t < 0 && a.g.res_scale < 0 && !a.g.ln &&
+                   a.g.stats_out < 0 && a.g.pool_out < 0 && b.g.amode == A_CONV && b.g.kh == 3 && b.g.kw == 3 && b.g.stride == 1 && b.g.K == 9 * 64 && b.g.N == 64 && b.g.pool_out < 0 &&
+                   b.g.a.t == a.g.out.t && passes_on(lt, a.g.out.t, i);
+        };
+        auto writes_output = [&](int j) { const auto wr = tensor_use(plan.ops[j]).wr; return std::find(wr.begin(), wr.end(), plan.out_tensor) != wr.end(); };
+        for (int i = 0; i < nops;) {
+            const Op& a = plan.ops[i]; const Op& b = plan.ops[std::min(i + 1, nops - 1)];
+            LaunchKind k = tf32 && attn32_triple(i, lt) ? L_ATTN32 : tf32 && mlp32_pair(i, lt) ? L_MLP32 : i + 1 == nops || !fp16 ? L_OP :
+                           head(a, b, i) ? L_HEAD : stem(a, b, i) ? L_STEM : up(a, b, i) ? L_UP : L_OP;
+            int last = i + (k == L_OP ? 0 : k == L_ATTN32 ? 2 : 1);
+            for (int j = i; j < last; ++j) if (writes_output(j)) { k = L_OP; last = i; }
+            ls.push_back(launch(k, i, last));
+            i = last + 1;
+        }
+        return ls;
     }
     // the bf16 hi / lo planes of an fp32 matrix [N][K] in fragment-major order (split4 of k_f32.hip on the host: hi = bf16(x), lo = bf16(x - hi), round to nearest even)
     void upload_planes(const std::vector<uint8_t>& w, int N, int K, void*& dh, void*& dl) {
@@ -462,79 +537,15 @@ struct Img2Img::Impl {
         }
     }
 
-    void upload_plan() {
+    void upload_plan(Precision prec) {
         // Activation arena: tensors whose lifetimes (first writer .. last reader, in op order) do not overlap share
         // memory.  An op's outputs are placed before its inputs are released, so no op reads and writes one address.
+        // The lifetimes are those of the candidate launches: a candidate split back into its ops below keeps a layout that covers what they need.
+        const std::vector<Launch> candidates = candidate_launches(prec);
         {
             const int nt = (int)plan.tensors.size(), nops = (int)plan.ops.size();
-            std::vector<int> first(nt, nops), last(nt, -1);
-            auto touch = [&](int t, int op) { if (t < 0) return; first[t] = std::min(first[t], op); last[t] = std::max(last[t], op); };
-            for (int i = 0; i < nops; ++i) {
-                const Op& op = plan.ops[i];
-                switch (op.kind) {
-                    case OP_GEMM: touch(op.g.a.t, i); touch(op.g.res.t, i); touch(op.g.res2.t, i); touch(op.g.stats_in, i); touch(op.g.se_scale, i); touch(op.g.res_scale, i);
-                                  touch(op.g.out.t, i); touch(op.g.stats_out, i); touch(op.g.pool_out, i); break;
-                    case OP_ATTN: touch(op.at.qkv, i); touch(op.at.out, i); break;
-                    case OP_SE: touch(op.se.pool, i); touch(op.se.scale, i); break;
-                    case OP_SCALE_ADD: touch(op.se.pool, i); touch(op.se.scale, i); break;
-                    case OP_MLP: touch(op.m.x, i); touch(op.m.y, i); touch(op.m.stats_out, i); break;
-                    case OP_SWINATTN: touch(op.sa.x, i); touch(op.sa.y, i); touch(op.sa.stats_out, i); break;
-                    default: break;
-                }
-            }
-            first[plan.in_tensor] = -1;                       // written by the gather kernel before op 0
-            last[plan.out_tensor] = nops;                     // read after the last op (infer) / replaced by the frame slab
-            // An image head that rides on the MLP launch in front of it (fuse_head, decided below) writes its output WHILE that MLP still reads its input:
-            // the output must be alive from the MLP on, or it would be given the memory of the MLP's input, which dies at the MLP in the un-fused order.
-            // fp32 plans: a fused launch (mlp32_kernel / swinattn32_kernel) writes the LAST op's outputs while it still reads the first op's inputs - the row statistics among
-            // them, which die at the first op in the un-fused order: the outputs are alive from the first op on
-            fuse_mlp32.assign(nops, 0); fuse_attn32.assign(nops, 0);
-            for (int i = 0; i < nops; ++i) {
-                const int span = attn32_triple((size_t)i) ? 2 : mlp32_pair((size_t)i) ? 1 : 0;
-                if (!span) continue;
-                (span == 2 ? fuse_attn32 : fuse_mlp32)[i] = 1;
-                const GemmOp& gl = plan.ops[i + span].g;
-                first[gl.out.t] = std::min(first[gl.out.t], i);
-                if (gl.stats_out >= 0) first[gl.stats_out] = std::min(first[gl.stats_out], i);
-                i += span;
-            }
-            fuse_head.assign(nops, 0);
-            if (plan.elt == 2 && !switches().no_fuse_head && mlp_frag32(96))      // (the head rides on k_mlp96q.hip's launch only)
-                for (int i = 0; i + 1 < nops; ++i) {
-                    const Op& a = plan.ops[i]; const Op& b = plan.ops[i + 1];
-                    if (a.kind == OP_MLP && b.kind == OP_GEMM && a.m.C == 96 && a.m.stats_out < 0 && b.g.a.t == a.m.y && last[a.m.y] == i + 1 && b.g.amode == A_ROWS && b.g.K == 96 && b.g.N == 64 &&
-                        b.g.r == 4 && b.g.omode == O_PIXSHUF && b.g.res.t < 0 && b.g.res2.t < 0 && b.g.act == ACT_NONE && !b.g.ln && b.g.se_scale < 0 && b.g.res_scale < 0 && b.g.stats_out < 0 && b.g.pool_out < 0) {
-                        fuse_head[i] = 1;
-                        first[b.g.out.t] = std::min(first[b.g.out.t], i);
-                    }
-                }
-            // The stem folded into the patch convolution behind it (fuse_stem, confirmed below with the prepared parameters): that launch reads the stem's INPUT,
-            // which must therefore outlive the stem by one op (its memory would otherwise go to the convolution's output).
-            fuse_stem.assign(nops, 0);
-            if (plan.elt == 2)
-                for (int i = 0; i + 1 < nops; ++i) {
-                    const Op& a = plan.ops[i]; const Op& b = plan.ops[i + 1];
-                    if (a.kind == OP_GEMM && b.kind == OP_GEMM && a.g.a.t >= 0 && plan.tensors[a.g.a.t].C == 4 && ((a.g.N == 48 && b.g.K == 9 * 48) || (a.g.N == 32 && b.g.K == 9 * 32 && b.g.N == 64 && b.g.pool_out < 0)) && b.g.a.t == a.g.out.t && first[a.g.out.t] == i && last[a.g.out.t] == i + 1 &&
-                        a.g.out.t != plan.out_tensor && a.g.stats_out < 0 && a.g.pool_out < 0) {
-                        fuse_stem[i] = 1;
-                        last[a.g.a.t] = std::max(last[a.g.a.t], i + 1);
-                    }
-                }
-            // cunet's transposed convolution folded into the 3x3 convolution behind it (fuse_up, confirmed below with the prepared parameters): that launch reads the
-            // projection's rows, its skip map and its gate, which must therefore outlive the projection by one op.
-            fuse_up.assign(nops, 0);
-            if (plan.elt == 2)
-                for (int i = 0; i + 1 < nops; ++i) {
-                    const Op& a = plan.ops[i]; const Op& b = plan.ops[i + 1];
-                    if (a.kind == OP_GEMM && b.kind == OP_GEMM && a.g.omode == O_PIXSHUF && a.g.r == 2 && a.g.K == 64 && a.g.N == 256 && a.g.res.t >= 0 && a.g.res2.t < 0 && a.g.res_scale < 0 && !a.g.ln &&
-                        a.g.stats_out < 0 && a.g.pool_out < 0 && b.g.amode == A_CONV && b.g.kh == 3 && b.g.kw == 3 && b.g.stride == 1 && b.g.K == 9 * 64 && b.g.N == 64 && b.g.pool_out < 0 && b.g.a.t == a.g.out.t &&
-                        first[a.g.out.t] == i && last[a.g.out.t] == i + 1 && a.g.out.t != plan.out_tensor) {
-                        fuse_up[i] = 1;
-                        for (int t : {a.g.a.t, a.g.res.t, a.g.se_scale})
-                            if (t >= 0) last[t] = std::max(last[t], i + 1);
-                    }
-                }
-            tensor_last = last;
+            const Lifetimes lt = lifetimes(candidates);
+            const std::vector<int>& first = lt.first; const std::vector<int>& last = lt.last;
             struct Block { size_t off, size; };
             std::vector<Block> free_list;
             std::vector<size_t> off(nt, 0);
@@ -569,7 +580,7 @@ struct Img2Img::Impl {
             hipAssert(hipMemsetAsync(arena_base, 0, arena + 1024, stream));
             arena_bytes = arena;
             pool_blocks.assign(nt, 0);
-        tensors.assign(nt, nullptr);
+            tensors.assign(nt, nullptr);
             for (int t = 0; t < nt; ++t) tensors[t] = placed[t] ? (uint8_t*)arena_base + off[t] : nullptr;
         }
         blobs.assign(plan.blobs.size(), nullptr);
@@ -635,7 +646,7 @@ struct Img2Img::Impl {
             }
         for (const Op& op : plan.ops)
             if (plan.elt == 2 && op.kind == OP_SWINATTN) { frag_major_blob(op.sa.wqkv, 3 * op.sa.C, op.sa.C); frag_major_blob(op.sa.wproj, op.sa.C, op.sa.C); }
-        gemm.assign(plan.ops.size(), GemmParams{});
+        gemm.assign(plan.ops.size(), GemmParams{}); final_op = -1;
         for (size_t i = 0; i < plan.ops.size(); ++i) {
             const Op& op = plan.ops[i];
             if (op.kind != OP_GEMM) continue;
@@ -656,7 +667,6 @@ struct Img2Img::Impl {
             p.a_scale = g.se_scale >= 0 ? (const float*)tensors[g.se_scale] : nullptr;
             p.res_scale = g.res_scale >= 0 ? (const float*)tensors[g.res_scale] : nullptr;
             if ((p.a_scale || p.res_scale) && plan.elt != 2) throw std::runtime_error("plan: folded gates in an fp32 plan");
-            if (g.pool_out >= 0) pool_tensors.push_back(g.pool_out);
             if (g.out.t == plan.out_tensor) final_op = (int)i;
             // shape checks the kernels rely on (a wrong shape would fault on the device)
             if (p.ln && (!p.stats_in || !p.csum)) throw std::runtime_error("plan: LayerNorm op without statistics");
@@ -668,38 +678,27 @@ struct Img2Img::Impl {
             if (p.a.Cs != 4 && (p.a.Cs % 8)) throw std::runtime_error("plan: unaligned input channels");
         }
         if (final_op < 0) throw std::runtime_error("plan: the output tensor is not produced by a fused op");
-        // fp32 plans: the weights of the fused launches decided above (used only while cfg.precision == TF32)
-        mlp32_w.assign(plan.ops.size(), std::array<void*, 4>{{nullptr, nullptr, nullptr, nullptr}});
-        attn32_w.assign(plan.ops.size(), std::array<void*, 4>{{nullptr, nullptr, nullptr, nullptr}});
-        for (size_t i = 0; i < plan.ops.size(); ++i) {
-            if (fuse_mlp32[i]) {
-                const GemmOp& g1 = plan.ops[i].g; const GemmOp& g2 = plan.ops[i + 1].g;
-                upload_planes(plan.blobs[g1.w].data, 2 * g1.K, g1.K, mlp32_w[i][0], mlp32_w[i][1]);
-                upload_planes(plan.blobs[g2.w].data, g1.K, 2 * g1.K, mlp32_w[i][2], mlp32_w[i][3]);
-            }
-            if (fuse_attn32[i]) {
-                const GemmOp& g1 = plan.ops[i].g; const GemmOp& g2 = plan.ops[i + 2].g;
-                upload_planes(plan.blobs[g1.w].data, 3 * g1.K, g1.K, attn32_w[i][0], attn32_w[i][1]);
-                upload_planes(plan.blobs[g2.w].data, g1.K, g1.K, attn32_w[i][2], attn32_w[i][3]);
-            }
+        // Each fold confirmed with the prepared launch parameters, or split back into its ops.  The image head: k_mlp96q.hip takes a 32-row tile inside one image, at most
+        // two token rows, and clip bounds that fp16 holds exactly.  The stem and the transposed convolution: k_conv48.hip conv48_kernel<true> / k_conv3.hip conv3_kernel
+        // (switches.h no_fuse_head / no_fuse_stem / no_fuse_up keep the launches apart).
+        auto head_supported = [&](const GemmParams& g) {
+            return g.wt_frag && g.out.Cs == 4 && g.a.y0 == 0 && g.a.x0 == 0 && g.a.Ws == g.aW && (long)g.a.Hs * g.a.Ws == g.Mrows && g.Mrows % 32 == 0 && g.aW >= 32 && pixgemm_supported(g) &&
+                   (!g.has_clip || (f16_to_f32(f32_to_f16(g.clip_lo)) == g.clip_lo && f16_to_f32(f32_to_f16(g.clip_hi)) == g.clip_hi));
+        };
+        launches.clear();
+        for (const Launch& L : candidates) {
+            const GemmParams& p = gemm[L.last]; const GemmParams& q = gemm[L.first];
+            const bool ok = L.kind == L_HEAD ? head_supported(p) : L.kind == L_STEM ? conv48_stem_supported(p, q) || conv3_stem_supported(p, q) : L.kind == L_UP ? conv3_up_supported(p, q) : true;
+            if (ok) launches.push_back(L);
+            else for (int i = L.first; i <= L.last; ++i) launches.push_back(launch(L_OP, i, i));
         }
-        // The image head (Linear 96 -> 4x4 sub-pixels x 4 channels, Clip) behind the last MLP: its input rows have no other reader, so the MLP launch
-        // runs the head on every tile it produces and neither stores nor re-reads the 96-channel map (switches.h no_fuse_head keeps the two launches).
-        for (size_t i = 0; i + 1 < plan.ops.size(); ++i)       // the candidates of the arena pass above, now with the prepared launch parameters
-            if (fuse_head[i]) {
-                const GemmParams& g = gemm[i + 1];
-                if (!(g.wt_frag && g.out.Cs == 4 && g.a.y0 == 0 && g.a.x0 == 0 && g.a.Ws == g.aW && (long)g.a.Hs * g.a.Ws == g.Mrows && g.Mrows % 32 == 0 && g.aW >= 32 && pixgemm_supported(g) &&
-                      (!g.has_clip || (f16_to_f32(f32_to_f16(g.clip_lo)) == g.clip_lo && f16_to_f32(f32_to_f16(g.clip_hi)) == g.clip_hi)))) fuse_head[i] = 0;   // (k_mlp96q.hip: a 32-row tile inside one image, at most two token rows; clip bounds that fp16 holds exactly)
+        // fp32 plans at Precision::TF32: the weights of the fused launches as bf16 hi / lo planes
+        for (Launch& L : launches)
+            if (L.kind == L_MLP32 || L.kind == L_ATTN32) {
+                const GemmOp& g1 = plan.ops[L.first].g; const GemmOp& g2 = plan.ops[L.last].g;
+                upload_planes(plan.blobs[g1.w].data, g1.N, g1.K, L.planes[0], L.planes[1]);
+                upload_planes(plan.blobs[g2.w].data, g2.N, g2.K, L.planes[2], L.planes[3]);
             }
-        // The stem (3x3, 4 -> 48 channels) in front of the patch convolution (3x3, 48 -> 96): its output has no other reader, so the convolution computes the halo tile
-        // it needs from the input tile and the 48-channel map is neither stored nor read (k_conv48.hip conv48_kernel<true>; switches.h no_fuse_stem keeps the two launches).
-        // Round 6: the same for cunet's two U-Nets, whose stems (4 -> 32) feed a 32 -> 64 convolution each (k_conv3.hip conv3_kernel<false, true>).
-        for (size_t i = 0; i + 1 < plan.ops.size(); ++i)
-            if (fuse_stem[i] && !conv48_stem_supported(gemm[i + 1], gemm[i]) && !conv3_stem_supported(gemm[i + 1], gemm[i])) fuse_stem[i] = 0;
-        // Round 6: cunet's ConvTranspose 2x2 stride 2 (a pixel-shuffle projection with LeakyReLU, a gate on its rows and a skip add) in front of a 64 -> 64 convolution
-        // that alone reads it: the convolution assembles its halo tile from the skip map and the projection's input rows (k_conv3.hip conv3_kernel UP; switches.h no_fuse_up).
-        for (size_t i = 0; i + 1 < plan.ops.size(); ++i)
-            if (fuse_up[i] && !conv3_up_supported(gemm[i + 1], gemm[i])) fuse_up[i] = 0;
         hipAssert(hipStreamSynchronize(stream));
     }
 
@@ -721,165 +720,149 @@ struct Img2Img::Impl {
         const int cap = grp < 0 ? plan.B : plan.B / ng_now;
         if (live < 0 || live > cap) live = cap;
         auto tp = [&](int t) -> uint8_t* { return t < 0 ? nullptr : grp < 0 ? (uint8_t*)tensors[t] : group_ptr(tensors[t], grp); };
-        auto shift = [&](const void* ptr, int) -> void* { return group_ptr(ptr, grp); };
-        const int b0 = grp < 0 ? 0 : 1;   // (non-zero: re-address the prepared parameters)
-        bool skip_next = false;           // the op was folded into the previous launch (fuse_head, mlp32)
-        int skip_attn32 = 0;              // ops still to skip behind a swinattn32 launch
-        GemmParams stem_p; bool stem_held = false, held_up = false; double stem_flops = 0;   // the op is folded into the NEXT launch (fuse_stem): its re-addressed parameters wait here
-        for (size_t i = 0; i < plan.ops.size(); ++i) try {
-            const Op& op = plan.ops[i];
-            cur_op = (int)i;
-            struct Range { Impl* e; bool on; ~Range() { if (on) e->roctx_pop(); } } range{this, roctx_push != nullptr};   // W2X_ROCTX=1: a roctx range per plan op (rocprofv3 --marker-trace)
-            if (range.on) roctx_push((std::to_string(i) + " " + op.name).c_str());
-            switch (op.kind) {
-                case OP_GEMM: {
-                    if (skip_next) { skip_next = false; break; }
-                    if (skip_attn32) { --skip_attn32; break; }
-                    GemmParams p = gemm[i];
-                    p.B = live;
-                    if (b0) {
-                        const GemmOp& g = op.g;
-                        p.a.p = shift(p.a.p, g.a.t); p.res.p = shift(p.res.p, g.res.t); p.res2.p = shift(p.res2.p, g.res2.t); p.out.p = shift(p.out.p, g.out.t);
-                        p.stats_in = (const float*)shift(p.stats_in, g.stats_in); p.stats_out = (float*)shift(p.stats_out, g.stats_out); p.pool_out = (float*)shift(p.pool_out, g.pool_out);
-                        p.a_scale = (const float*)shift(p.a_scale, g.se_scale); p.res_scale = (const float*)shift(p.res_scale, g.res_scale);
-                    }
-                    if ((int)i == final_op && out_override) p.out.p = out_override;
-                    if (fuse_attn32[i] && cfg.precision == Precision::TF32) {     // LayerNorm + window gather + qkv, attention core, proj + scatter + residual in one launch
-                        const AttnOp& a = plan.ops[i + 1].at;
-                        GemmParams q = gemm[i + 2];
-                        if (b0) { const GemmOp& g2 = plan.ops[i + 2].g; q.out.p = shift(q.out.p, g2.out.t); q.res.p = shift(q.res.p, g2.res.t); q.stats_out = (float*)shift(q.stats_out, g2.stats_out); }
-                        SwinAttn32Params m;
-                        m.x = (const float*)p.a.p; m.y = (float*)q.out.p; m.res = (const float*)q.res.p; m.B = live; m.nwin = a.nwin; m.C = p.K; m.pix_per_item = p.Mrows;
-                        m.table_in = p.win_table; m.table_out = q.win_table; m.stats_in = p.stats_in;
-                        m.wqkv_h = attn32_w[i][0]; m.wqkv_l = attn32_w[i][1]; m.wproj_h = attn32_w[i][2]; m.wproj_l = attn32_w[i][3];
-                        m.bqkv = p.bias; m.bproj = q.bias; m.scale = a.scale; m.bias = (const float*)blobs[a.bias]; m.maskid = (const int*)blobs[a.maskid];
-                        m.stats_out = q.stats_out; m.eps_out = q.ln_eps;
-                        stamp_begin(1, op.flops + plan.ops[i + 1].flops + plan.ops[i + 2].flops);
-                        hipAssert(launch_swinattn32(m, s));
-                        stamp_end();
-                        skip_attn32 = 1;          // (the attention op skips itself below, then the proj op here)
+        // op i's prepared parameters for this pass: `live` tiles, the group's part of the arena, the pass's output where op i writes it
+        auto gp = [&](int i) {
+            GemmParams p = gemm[i];
+            p.B = live;
+            if (grp >= 0) {
+                auto shift = [&](auto*& ptr) { ptr = (std::remove_reference_t<decltype(ptr)>)group_ptr(ptr, grp); };
+                shift(p.a.p); shift(p.res.p); shift(p.res2.p); shift(p.out.p); shift(p.stats_in); shift(p.stats_out); shift(p.pool_out); shift(p.a_scale); shift(p.res_scale);
+            }
+            if (i == final_op && out_override) p.out.p = out_override;
+            return p;
+        };
+        for (const Launch& L : launches) try {
+            const Op& op = plan.ops[L.first];
+            struct Range { Impl* e; bool on; ~Range() { if (on) e->roctx_pop(); } } range{this, roctx_push != nullptr};   // W2X_ROCTX=1: a roctx range per launch (rocprofv3 --marker-trace)
+            if (range.on) roctx_push(launch_label(L).c_str());
+            auto issue = [&](auto&& f) { stamp_begin(L.family, L.flops, L.timed); hipAssert(f()); stamp_end(); };   // (profileFrame: events around the launch alone)
+            switch (L.kind) {
+                case L_HEAD: {      // the image head rides on the MLP launch
+                    const GemmParams g = gp(L.last);
+                    MlpParams p = mlp_params(op, live, tp);
+                    p.ti_w = g.wt_frag; p.ti_b = g.bias; p.ti_out = g.out.p; p.ti_Hs = g.out.Hs; p.ti_Ws = g.out.Ws; p.ti_Mrows = g.Mrows; p.ti_aW = g.aW;
+                    p.ti_clip = g.has_clip; p.ti_lo = g.clip_lo; p.ti_hi = g.clip_hi;
+                    issue([&] { return launch_mlp(p, s); });
+                    break;
+                }
+                case L_STEM: case L_UP: {      // the convolution computes the op in front of it in its halo stage (the stem: k_conv48.hip onto 48 channels, k_conv3.hip onto 32)
+                    const GemmParams p = gp(L.last), q = gp(L.first);
+                    issue([&] { return L.kind == L_UP ? launch_conv3_up(p, q, s) : q.N == 48 ? launch_conv48_stem(p, q, s) : launch_conv3_stem(p, q, s); });
+                    break;
+                }
+                case L_MLP32: {      // fc1 + GELU + fc2 + residual on fp32 rows
+                    const GemmParams p = gp(L.first), q = gp(L.last);
+                    Mlp32Params m;
+                    m.x = (const float*)p.a.p; m.y = (float*)q.out.p; m.M = (long)live * p.Mrows; m.C = p.K; m.stats_in = p.stats_in;
+                    m.w1h = L.planes[0]; m.w1l = L.planes[1]; m.w2h = L.planes[2]; m.w2l = L.planes[3];
+                    m.b1 = p.bias; m.b2 = q.bias; m.stats_out = q.stats_out; m.eps_out = q.ln_eps;
+                    issue([&] { return launch_mlp32(m, s); });
+                    break;
+                }
+                case L_ATTN32: {     // LayerNorm + window gather + qkv, attention core, proj + scatter + residual
+                    const GemmParams p = gp(L.first), q = gp(L.last);
+                    const AttnOp& a = plan.ops[L.first + 1].at;
+                    SwinAttn32Params m;
+                    m.x = (const float*)p.a.p; m.y = (float*)q.out.p; m.res = (const float*)q.res.p; m.B = live; m.nwin = a.nwin; m.C = p.K; m.pix_per_item = p.Mrows;
+                    m.table_in = p.win_table; m.table_out = q.win_table; m.stats_in = p.stats_in;
+                    m.wqkv_h = L.planes[0]; m.wqkv_l = L.planes[1]; m.wproj_h = L.planes[2]; m.wproj_l = L.planes[3];
+                    m.bqkv = p.bias; m.bproj = q.bias; m.scale = a.scale; m.bias = (const float*)blobs[a.bias]; m.maskid = (const int*)blobs[a.maskid];
+                    m.stats_out = q.stats_out; m.eps_out = q.ln_eps;
+                    issue([&] { return launch_swinattn32(m, s); });
+                    break;
+                }
+                case L_OP: switch (op.kind) {
+                    case OP_GEMM: {
+                        const GemmParams p = gp(L.first);
+                        if (op.g.pool_out >= 0) pool_blocks[op.g.pool_out] = plan.elt == 2 && conv3_supported(p) ? conv3_tiles(p) : 0;   // partial sums per image written by this launch (0: plan default)
+                        issue([&] { return plan.elt == 4 ? launch_gemm_f32(p, s, cfg.precision == Precision::FP32) : pixgemm_supported(p) ? launch_pixgemm(p, s) : conv3_supported(p) ? launch_conv3(p, s) : conv3h_supported(p) ? launch_conv3h(p, s) : conv48_supported(p) ? launch_conv48(p, s) : stem_supported(p) ? launch_stem(p, s) : launch_gemm(p, s); });
+                        if (check_general && plan.elt == 2 && (pixgemm_supported(p) || conv3_supported(p) || conv3h_supported(p) || conv48_supported(p) || stem_supported(p))) check_against_general(p, L.first, live);
                         break;
                     }
-                    if (fuse_mlp32[i] && cfg.precision == Precision::TF32) {      // fc1 + GELU + fc2 + residual on fp32 rows in one launch; op i + 1 is skipped
-                        GemmParams q = gemm[i + 1];
-                        if (b0) { const GemmOp& g2 = plan.ops[i + 1].g; q.out.p = shift(q.out.p, g2.out.t); q.stats_out = (float*)shift(q.stats_out, g2.stats_out); }
-                        Mlp32Params m;
-                        m.x = (const float*)p.a.p; m.y = (float*)q.out.p; m.M = (long)live * p.Mrows; m.C = p.K; m.stats_in = p.stats_in;
-                        m.w1h = mlp32_w[i][0]; m.w1l = mlp32_w[i][1]; m.w2h = mlp32_w[i][2]; m.w2l = mlp32_w[i][3];
-                        m.b1 = p.bias; m.b2 = q.bias; m.stats_out = q.stats_out; m.eps_out = q.ln_eps;
-                        stamp_begin(0, op.flops + plan.ops[i + 1].flops);
-                        hipAssert(launch_mlp32(m, s));
-                        stamp_end();
-                        skip_next = true;
+                    case OP_ATTN: {
+                        const AttnOp& a = op.at;
+                        AttnParams p;
+                        p.qkv = tp(a.qkv); p.out = tp(a.out); p.B = live; p.nwin = a.nwin; p.heads = a.heads; p.hd = a.hd;
+                        p.ntok = a.ws * a.ws; p.scale = a.scale; p.bias = blobs[a.bias]; p.maskid = (const int*)blobs[a.maskid];
+                        issue([&] { return plan.elt == 4 ? launch_attn_f32(p, s) : launch_attn(p, s); });
                         break;
                     }
-                    if ((fuse_stem[i] || fuse_up[i]) && !check_general) { stem_p = p; stem_held = true; held_up = fuse_up[i] != 0; stem_flops = op.flops; break; }    // computed by the next op's launch
-                    if (stem_held) {
-                        stem_held = false;
-                        stamp_begin(0, op.flops + stem_flops);
-                        hipAssert(held_up ? launch_conv3_up(p, stem_p, s) : conv48_stem_supported(p, stem_p) ? launch_conv48_stem(p, stem_p, s) : launch_conv3_stem(p, stem_p, s));
-                        stamp_end();
+                    case OP_SWINATTN: {
+                        const SwinAttnOp& a = op.sa;
+                        const TensorDesc& d = plan.tensors[a.x];
+                        SwinAttnParams p;
+                        p.x = tp(a.x); p.y = tp(a.y); p.table = (const int*)blobs[a.table]; p.H = a.H; p.W = a.W; p.ry = a.ry; p.rx = a.rx; p.B = live; p.nwin = a.nwin; p.C = a.C; p.hd = a.hd;
+                        p.wqkv = blobs[a.wqkv]; p.bqkv = (const float*)blobs[a.bqkv]; p.scale = a.scale; p.bias32 = (const float*)blobs[a.bias]; p.maskid = (const int*)blobs[a.maskid];
+                        p.wproj = blobs[a.wproj]; p.bproj = (const float*)blobs[a.bproj]; p.eps = a.eps;
+                        p.wqkv_frag = frag_blobs[a.wqkv]; p.wproj_frag = frag_blobs[a.wproj];
+                        p.stats_out = (float*)tp(a.stats_out); p.eps_out = a.eps_out;
+                        if (d.C != a.C || plan.tensors[a.y].C != a.C || d.H * d.W != a.nwin * a.ws * a.ws) throw std::runtime_error("plan: attention geometry mismatch");
+                        issue([&] { return launch_swin_attn(p, s); });
                         break;
                     }
-                    stamp_begin(0, op.flops);
-                    if (op.g.pool_out >= 0) pool_blocks[op.g.pool_out] = plan.elt == 2 && conv3_supported(p) ? conv3_tiles(p) : 0;   // partial sums per image written by this launch (0: plan default)
-                    hipAssert(plan.elt == 4 ? launch_gemm_f32(p, s, cfg.precision == Precision::FP32) : pixgemm_supported(p) ? launch_pixgemm(p, s) : conv3_supported(p) ? launch_conv3(p, s) : conv3h_supported(p) ? launch_conv3h(p, s) : conv48_supported(p) ? launch_conv48(p, s) : stem_supported(p) ? launch_stem(p, s) : launch_gemm(p, s));
-                    stamp_end();
-                    if (check_general && plan.elt == 2 && (pixgemm_supported(p) || conv3_supported(p) || conv3h_supported(p) || conv48_supported(p) || stem_supported(p))) {   // diagnostic: the general kernel must agree
-                        const TensorDesc& od = plan.tensors[op.g.out.t];
-                        const size_t n = (size_t)live * od.H * od.W * od.C;
-                        std::vector<uint16_t> a(n), b(n);
-                        void* tmp = nullptr;
-                        hipAssert(hipMalloc(&tmp, n * 2));
-                        hipAssert(hipStreamSynchronize(stream));
-                        hipAssert(hipMemcpy(a.data(), p.out.p, n * 2, hipMemcpyDeviceToHost));
-                        hipAssert(hipMemcpy(tmp, p.out.p, n * 2, hipMemcpyDeviceToDevice));   // pixels neither kernel writes compare equal
-                        GemmParams q = p; q.out.p = tmp; q.pool_out = nullptr;   // the pooling partials of the real launch stay
-                        hipAssert(launch_gemm(q, stream));
-                        hipAssert(hipStreamSynchronize(stream));
-                        hipAssert(hipMemcpy(b.data(), tmp, n * 2, hipMemcpyDeviceToHost));
-                        hipAssert(hipFree(tmp));
-                        double md = 0; size_t at = 0, bad = 0;
-                        for (size_t k = 0; k < n; ++k) { const double d = std::fabs(f16_to_f32(a[k]) - f16_to_f32(b[k])); if (d > 0.01) ++bad; if (d > md) { md = d; at = k; } }
-                        log(Severity::warn, "pixgemm check op " + std::to_string(i) + " [" + op.name + "]: max|d|=" + std::to_string(md) + " at pixel " + std::to_string(at / od.C) +
-                            " ch " + std::to_string(at % od.C) + " (x=" + std::to_string(at / od.C % od.W) + ", y=" + std::to_string(at / od.C / od.W % od.H) + "), " + std::to_string(bad) + " of " + std::to_string(n) + " off by > 0.01");
+                    case OP_MLP: {
+                        const MlpParams p = mlp_params(op, live, tp);
+                        issue([&] { return launch_mlp(p, s); });
+                        break;
                     }
-                    break;
-                }
-                case OP_ATTN: {
-                    if (i > 0 && fuse_attn32[i - 1] && cfg.precision == Precision::TF32) break;      // computed by the launch of the op in front
-                    const AttnOp& a = op.at;
-                    AttnParams p;
-                    p.qkv = tp(a.qkv); p.out = tp(a.out); p.B = live; p.nwin = a.nwin; p.heads = a.heads; p.hd = a.hd;
-                    p.ntok = a.ws * a.ws; p.scale = a.scale; p.bias = blobs[a.bias]; p.maskid = (const int*)blobs[a.maskid];
-                    stamp_begin(1, op.flops);
-                    hipAssert(plan.elt == 4 ? launch_attn_f32(p, s) : launch_attn(p, s));
-                    stamp_end();
-                    break;
-                }
-                case OP_SWINATTN: {
-                    const SwinAttnOp& a = op.sa;
-                    const TensorDesc& d = plan.tensors[a.x];
-                    SwinAttnParams p;
-                    p.x = tp(a.x); p.y = tp(a.y); p.table = (const int*)blobs[a.table]; p.H = a.H; p.W = a.W; p.ry = a.ry; p.rx = a.rx; p.B = live; p.nwin = a.nwin; p.C = a.C; p.hd = a.hd;
-                    p.wqkv = blobs[a.wqkv]; p.bqkv = (const float*)blobs[a.bqkv]; p.scale = a.scale; p.bias32 = (const float*)blobs[a.bias]; p.maskid = (const int*)blobs[a.maskid];
-                    p.wproj = blobs[a.wproj]; p.bproj = (const float*)blobs[a.bproj]; p.eps = a.eps;
-                    p.wqkv_frag = frag_blobs[a.wqkv]; p.wproj_frag = frag_blobs[a.wproj];
-                    p.stats_out = (float*)tp(a.stats_out); p.eps_out = a.eps_out;
-                    if (d.C != a.C || plan.tensors[a.y].C != a.C || d.H * d.W != a.nwin * a.ws * a.ws) throw std::runtime_error("plan: attention geometry mismatch");
-                    stamp_begin(1, op.flops);
-                    hipAssert(launch_swin_attn(p, s));
-                    stamp_end();
-                    break;
-                }
-                case OP_MLP: {
-                    const MlpOp& m = op.m;
-                    const TensorDesc& d = plan.tensors[m.x];
-                    MlpParams p;
-                    p.x = tp(m.x); p.y = tp(m.y); p.M = (long)live * d.H * d.W; p.C = m.C;
-                    p.w1 = blobs[m.w1]; p.b1 = (const float*)blobs[m.b1]; p.w2 = blobs[m.w2]; p.b2 = (const float*)blobs[m.b2];
-                    p.w1_frag = frag_blobs[m.w1]; p.w2_frag = frag_blobs[m.w2]; p.frag32 = mlp_frag32(m.C);
-                    p.eps = m.eps; p.stats_out = (float*)tp(m.stats_out); p.eps_out = m.eps_out;
-                    if (d.C != m.C || plan.tensors[m.y].C != m.C) throw std::runtime_error("plan: MLP width mismatch");
-                    double flops = op.flops;
-                    if (fuse_head[i] && !check_general) {      // the image head rides on this launch
-                        const GemmParams& g = gemm[i + 1];
-                        void* out = b0 ? shift(g.out.p, plan.ops[i + 1].g.out.t) : g.out.p;
-                        if ((int)i + 1 == final_op && out_override) out = out_override;
-                        p.ti_w = g.wt_frag; p.ti_b = g.bias; p.ti_out = out; p.ti_Hs = g.out.Hs; p.ti_Ws = g.out.Ws; p.ti_Mrows = g.Mrows; p.ti_aW = g.aW;
-                        p.ti_clip = g.has_clip; p.ti_lo = g.clip_lo; p.ti_hi = g.clip_hi;
-                        flops += plan.ops[i + 1].flops;
-                        skip_next = true;
+                    case OP_SE: {
+                        const SeOp& se = op.se;
+                        SeParams p;
+                        p.pool = (const float*)tp(se.pool); p.scale = (float*)tp(se.scale); p.B = live; p.C = se.C;
+                        p.Cs = plan.tensors[se.pool].C; p.Cmid = se.Cmid; p.inv_count = se.inv_count; p.nblocks = pool_blocks[se.pool] > 0 ? pool_blocks[se.pool] : se.nblocks; p.Mrows = se.Mrows;
+                        p.w1 = (const float*)blobs[se.w1]; p.b1 = (const float*)blobs[se.b1]; p.w2 = (const float*)blobs[se.w2]; p.b2 = (const float*)blobs[se.b2];
+                        issue([&] { return launch_se(p, s); });
+                        break;
                     }
-                    stamp_begin(5, flops);
-                    hipAssert(launch_mlp(p, s));
-                    stamp_end();
-                    break;
+                    case OP_SCALE_ADD: {
+                        const TensorDesc& d = plan.tensors[op.se.pool];
+                        issue([&] { return launch_scale(tp(op.se.pool), (const float*)tp(op.se.scale), live, d.H * d.W, d.C, plan.elt == 4, s); });
+                        break;
+                    }
+                    default: throw std::runtime_error("plan: unknown op kind");
                 }
-                case OP_SE: {
-                    const SeOp& se = op.se;
-                    SeParams p;
-                    p.pool = (const float*)tp(se.pool); p.scale = (float*)tp(se.scale); p.B = live; p.C = se.C;
-                    p.Cs = plan.tensors[se.pool].C; p.Cmid = se.Cmid; p.inv_count = se.inv_count; p.nblocks = pool_blocks[se.pool] > 0 ? pool_blocks[se.pool] : se.nblocks; p.Mrows = se.Mrows;
-                    p.w1 = (const float*)blobs[se.w1]; p.b1 = (const float*)blobs[se.b1]; p.w2 = (const float*)blobs[se.w2]; p.b2 = (const float*)blobs[se.b2];
-                    stamp_begin(2, 0);
-                    hipAssert(launch_se(p, s));
-                    stamp_end();
-                    break;
-                }
-                case OP_SCALE_ADD: {
-                    const TensorDesc& d = plan.tensors[op.se.pool];
-                    stamp_begin(2, 0);
-                    hipAssert(launch_scale(tp(op.se.pool), (const float*)tp(op.se.scale), live, d.H * d.W, d.C, plan.elt == 4, s));
-                    stamp_end();
-                    break;
-                }
-                default: throw std::runtime_error("plan: unknown op kind");
             }
         } catch (const std::exception& e) {     // name the op: "invalid argument" alone says nothing about a 60-op plan
-            throw std::runtime_error("op " + std::to_string(i) + " [" + plan.ops[i].name + "]: " + e.what());
+            throw std::runtime_error("op " + launch_label(L) + ": " + e.what());
         }
-        cur_op = -1;
+    }
+    // "12 [name]", or "12-13 [name + name]" for a fold: the roctx range and the error messages of a launch
+    std::string launch_label(const Launch& L) const {
+        std::string m = std::to_string(L.first) + (L.last > L.first ? "-" + std::to_string(L.last) : "") + " [";
+        for (int i = L.first; i <= L.last; ++i) m += (i > L.first ? " + " : "") + plan.ops[i].name;
+        return m + "]";
+    }
+    template <class TP> MlpParams mlp_params(const Op& op, int live, const TP& tp) const {
+        const MlpOp& m = op.m;
+        const TensorDesc& d = plan.tensors[m.x];
+        MlpParams p;
+        p.x = tp(m.x); p.y = tp(m.y); p.M = (long)live * d.H * d.W; p.C = m.C;
+        p.w1 = blobs[m.w1]; p.b1 = (const float*)blobs[m.b1]; p.w2 = blobs[m.w2]; p.b2 = (const float*)blobs[m.b2];
+        p.w1_frag = frag_blobs[m.w1]; p.w2_frag = frag_blobs[m.w2]; p.frag32 = mlp_frag32(m.C);
+        p.eps = m.eps; p.stats_out = (float*)tp(m.stats_out); p.eps_out = m.eps_out;
+        if (d.C != m.C || plan.tensors[m.y].C != m.C) throw std::runtime_error("plan: MLP width mismatch");
+        return p;
+    }
+    // W2X_CHECK_GENERAL (diagnostic): the general kernel must agree with the shape-specialised launch of op i that just wrote p.out
+    void check_against_general(const GemmParams& p, int i, int live) {
+        const Op& op = plan.ops[i];
+        const TensorDesc& od = plan.tensors[op.g.out.t];
+        const size_t n = (size_t)live * od.H * od.W * od.C;
+        std::vector<uint16_t> a(n), b(n);
+        void* tmp = nullptr;
+        hipAssert(hipMalloc(&tmp, n * 2));
+        hipAssert(hipStreamSynchronize(stream));
+        hipAssert(hipMemcpy(a.data(), p.out.p, n * 2, hipMemcpyDeviceToHost));
+        hipAssert(hipMemcpy(tmp, p.out.p, n * 2, hipMemcpyDeviceToDevice));   // pixels neither kernel writes compare equal
+        GemmParams q = p; q.out.p = tmp; q.pool_out = nullptr;   // the pooling partials of the real launch stay
+        hipAssert(launch_gemm(q, stream));
+        hipAssert(hipStreamSynchronize(stream));
+        hipAssert(hipMemcpy(b.data(), tmp, n * 2, hipMemcpyDeviceToHost));
+        hipAssert(hipFree(tmp));
+        double md = 0; size_t at = 0, bad = 0;
+        for (size_t k = 0; k < n; ++k) { const double d = std::fabs(f16_to_f32(a[k]) - f16_to_f32(b[k])); if (d > 0.01) ++bad; if (d > md) { md = d; at = k; } }
+        log(Severity::warn, "pixgemm check op " + std::to_string(i) + " [" + op.name + "]: max|d|=" + std::to_string(md) + " at pixel " + std::to_string(at / od.C) +
+            " ch " + std::to_string(at % od.C) + " (x=" + std::to_string(at / od.C % od.W) + ", y=" + std::to_string(at / od.C / od.W % od.H) + "), " + std::to_string(bad) + " of " + std::to_string(n) + " off by > 0.01");
     }
 
     template <class T> void ensure(T*& p, size_t& cap, size_t bytes) {
@@ -1318,21 +1301,21 @@ bool Img2Img::load(const std::string& modelPath, const RenderConfig& config) try
     impl->ensure_copy_streams();
     if (impl->groups > 1) { hipAssert(hipStreamCreateWithFlags(&impl->gstream[0], hipStreamNonBlocking)); hipAssert(hipEventCreateWithFlags(&impl->ev_join[0], hipEventDisableTiming)); }
     try {
-        impl->upload_plan();                                                      // :225-248
+        impl->upload_plan(config.precision);                                      // :225-248
     } catch (const std::exception& e) {
         W2X_LOG(error, "Failed to allocate resources: " + std::string(e.what()) + ".");
         impl->release();
         return false;
     }
     impl->cfg = config;
+    int folds[Impl::L_ATTN32 + 1] = {};
+    for (const Impl::Launch& L : impl->launches) ++folds[L.kind];
     W2X_LOG(info, "Loaded \"" + enginePath + "\": " + std::to_string(plan.ops.size()) + " ops, " + std::to_string(plan.B) + " tiles per pass, activation arena " +
                       std::to_string(impl->arena_bytes >> 20) + " MiB" +
-                      (std::count(impl->fuse_stem.begin(), impl->fuse_stem.end(), (char)1) ? ", " + std::to_string(std::count(impl->fuse_stem.begin(), impl->fuse_stem.end(), (char)1)) + " stem folded into the launch of the convolution behind it" : "") +
-                      (std::count(impl->fuse_up.begin(), impl->fuse_up.end(), (char)1) ? ", " + std::to_string(std::count(impl->fuse_up.begin(), impl->fuse_up.end(), (char)1)) + " transposed convolution folded into the launch of the convolution behind it" : "") +
-                      (std::count(impl->fuse_head.begin(), impl->fuse_head.end(), (char)1) ? ", image head folded into the last MLP launch" : "") +
-                      (config.precision == Precision::TF32 && std::count(impl->fuse_attn32.begin(), impl->fuse_attn32.end(), (char)1) + std::count(impl->fuse_mlp32.begin(), impl->fuse_mlp32.end(), (char)1) > 0
-                           ? ", " + std::to_string(std::count(impl->fuse_attn32.begin(), impl->fuse_attn32.end(), (char)1)) + " attention and " +
-                                 std::to_string(std::count(impl->fuse_mlp32.begin(), impl->fuse_mlp32.end(), (char)1)) + " MLP branches as fused fp32-row launches." : "."));
+                      (folds[Impl::L_STEM] ? ", " + std::to_string(folds[Impl::L_STEM]) + " stem folded into the launch of the convolution behind it" : "") +
+                      (folds[Impl::L_UP] ? ", " + std::to_string(folds[Impl::L_UP]) + " transposed convolution folded into the launch of the convolution behind it" : "") +
+                      (folds[Impl::L_HEAD] ? ", image head folded into the last MLP launch" : "") +
+                      (folds[Impl::L_ATTN32] + folds[Impl::L_MLP32] ? ", " + std::to_string(folds[Impl::L_ATTN32]) + " attention and " + std::to_string(folds[Impl::L_MLP32]) + " MLP branches as fused fp32-row launches." : "."));
     // :262-269 blend ramps
     impl->ovx = (int)std::lround(plan.T * config.scaling * config.overlapX);
     impl->ovy = (int)std::lround(plan.T * config.scaling * config.overlapY);
