@@ -29,6 +29,9 @@ typedef struct w2x_engine w2x_engine;
 enum { W2X_PRECISION_TF32 = 0, W2X_PRECISION_FP16 = 1, W2X_PRECISION_FP32 = 2 };  /* config.h:7-10; CLI map main.cpp:76-84; FP32: an addition (include/w2x/config.h) */
 
 enum { W2X_RESIZE_BICUBIC = 0, W2X_RESIZE_BILINEAR = 1 };   /* extension: the filter of the resized renders (include/w2x/config.h ResizeFilter) */
+/* extension: the matrix and range of the YUV renders (include/w2x/img2img.h YuvMatrix / YuvRange) */
+enum { W2X_YUV_BT601 = 0, W2X_YUV_BT709 = 1, W2X_YUV_BT2020 = 2 };
+enum { W2X_YUV_LIMITED = 0, W2X_YUV_FULL = 1 };
 
 typedef struct w2x_build_config {   /* trt::BuildConfig, config.h:12-31 */
     int deviceId, precision;
@@ -95,6 +98,17 @@ int w2x_render_sequence(w2x_engine* e, const uint8_t* const* srcs, int rows, int
 /* w2x_render_sequence with every frame resized like w2x_render_resized (one target size for the sequence, 8-bit frames) */
 int w2x_render_sequence_resized(w2x_engine* e, const uint8_t* const* srcs, int rows, int cols, size_t src_step, uint8_t* const* dsts, int dst_rows, int dst_cols, size_t dst_step,
                                 int count, int filter);
+/* Extension (Img2Img::renderYuv): render on planar YUV 4:2:0 frames (ffmpeg yuv420p / yuv420p10le; an AVFrame's data[0..2] and linesize[0..2]).
+ * planes[0..2] = Y, U (Cb), V (Cr); steps[0..2] in BYTES; Y is rows x cols, U and V (rows + 1) / 2 x (cols + 1) / 2.  bits 8 (uint8 samples) or 10
+ * (little-endian uint16, low 10 bits), chosen independently for src and dst.  matrix W2X_YUV_BT601 / _BT709 / _BT2020 (non-constant luminance), range
+ * W2X_YUV_LIMITED ("tv") / _FULL ("pc"), one pair for both directions; chroma sited MPEG-2 "left".  dst_rows x dst_cols must be the scaled size.
+ * Invalid depths, matrices, ranges, missing planes, short steps and other sizes return 0 through the message callback. */
+int w2x_render_yuv(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                   void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int matrix, int range);
+/* w2x_render_sequence over YUV frames: src_planes / dst_planes hold 3 * count pointers (frame i at [3i .. 3i + 2]); one set of steps, one size and one
+ * pair of depths for the sequence */
+int w2x_render_sequence_yuv(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                            void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int count, int matrix, int range);
 void* w2x_alloc_host(w2x_engine* e, size_t bytes);
 void w2x_free_host(w2x_engine* e, void* data);
 int w2x_pin_host(w2x_engine* e, void* data, size_t bytes);
@@ -125,6 +139,9 @@ int w2x_tile_weights(int which, int overlap_x, int overlap_y, int size, float* o
  * (normalised, zero past the taps it has).  Returns taps per output; 0 for invalid arguments; with first / weights NULL only the count; -taps (nothing
  * written) when cap < out * taps. */
 int w2x_resize_weights(int in, int out, int filter, int* first, float* weights, int cap);
+/* The planes of a packed YUV 4:2:0 frame of rows x cols at `bits` (8 or 10): plane_rows[k], plane_cols[k] (samples) and plane_bytes[k] = rows * cols *
+ * bytes per sample, k = Y, U, V.  Returns 1; 0 (nothing written) for an empty frame or other depths.  Any output pointer may be NULL. */
+int w2x_yuv_plane_sizes(int rows, int cols, int bits, int* plane_rows, int* plane_cols, size_t* plane_bytes);
 /* Lower an ONNX file at [batch,3,tile,tile] and write a textual description of the plan (ops, FLOPs) into buf. */
 int w2x_describe_plan(const char* onnx_path, int batch, int tile, char* buf, size_t cap);
 /* the same for any precision (W2X_PRECISION_FP16 / _TF32 / _FP32: the plan build() would write for that BuildConfig::precision; TF32 and FP32 share one) */

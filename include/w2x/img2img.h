@@ -28,6 +28,22 @@ struct Image {          // stand-in for cv::Mat of type CV_8UC3
     int depth = 8;
 };
 
+// Extension: planar YUV 4:2:0 frames as ffmpeg's yuv420p / yuv420p10le lay them out (an AVFrame's data[0..2] / linesize[0..2]): a Y plane of
+// rows x cols samples, U (Cb) and V (Cr) planes of ceil(rows/2) x ceil(cols/2); bits 8 (uint8 samples) or 10 (little-endian uint16 holding the low
+// 10 bits); each plane has its own pointer and step in bytes.  Chroma siting MPEG-2 "left" (chroma (i, j) at luma x = 2j, y = 2i + 1/2).
+struct YuvImage {
+    uint8_t* planes[3] = {nullptr, nullptr, nullptr};
+    size_t steps[3] = {0, 0, 0};
+    int rows = 0, cols = 0;
+    int bits = 8;
+};
+enum class YuvMatrix { BT601 = 0, BT709 = 1, BT2020 = 2 };   // (Kr, Kb) = (0.299, 0.114), (0.2126, 0.0722), (0.2627, 0.0593); BT.2020 non-constant luminance
+enum class YuvRange { Limited = 0, Full = 1 };               // "tv": Y 16..235, C 16..240 (times 2^(bits-8)); "pc": 0 .. 2^bits - 1
+struct YuvFormat {
+    YuvMatrix matrix = YuvMatrix::BT709;
+    YuvRange range = YuvRange::Limited;
+};
+
 class Img2Img {
 public:
     Img2Img();
@@ -64,6 +80,13 @@ public:
     bool renderSequence(const Image* srcs, Image* dsts, int count);
     // renderSequence() with every frame resized like renderResized() to dsts[i].rows x dsts[i].cols (one size for the sequence; 8-bit frames)
     bool renderSequenceResized(const Image* srcs, Image* dsts, int count, ResizeFilter filter = ResizeFilter::Bicubic);
+    // Extension: render() on YUV 4:2:0 frames.  The frame is converted to RGB on the device as it is read into tiles (chroma upsampled
+    // to the luma grid, the matrix inverted, R, G, B clamped to [0, 1]: these values take the place of u8 * float(1/255)) and the canvas render()
+    // would quantise is written back as YUV 4:2:0 at dst.bits (clamped to [0, 1], Y per pixel, chroma of the RGB filtered onto each chroma site).
+    // src.bits and dst.bits are chosen independently (8 or 10); dst must be rows*scaling x cols*scaling.  Other arguments: false (message callback).
+    bool renderYuv(const YuvImage& src, YuvImage& dst, YuvFormat format);
+    // renderYuv() over a sequence of equally sized frames through the pipeline of renderSequence() (three plane copies per frame each way)
+    bool renderSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format);
     void* allocHost(size_t bytes);
     void freeHost(void* data);
     // Page-locks caller-owned memory in place.  Only whole pages are accepted (data and bytes multiples of 4096): a registration
@@ -96,6 +119,7 @@ public:
 private:
     bool renderPart(const Image& src, Image& dst, int part, int parts, const char* who, int resizeFilter = -1);   // resizeFilter >= 0: renderResized
     bool runSequence(const Image* srcs, Image* dsts, int count, int resizeFilter, const char* who);
+    bool runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, const char* who);
     std::unique_ptr<Impl> impl;
 };
 

@@ -67,6 +67,9 @@ std::string usage() {
            "      --blend FLOAT [1/16] {1/8,1/16,1/32,0}   --tta   --codec TEXT [libx264]   --pix_fmt TEXT [yuv420p]   --crf INT [23] 0..51\n"
            "      --outscale FLOAT        (extension) output size = input size x FLOAT, 1 <= FLOAT <= --scale: the network output resized on the GPU\n"
            "      --resize-filter TEXT [bicubic]  (extension) {bicubic,bilinear}: the antialiasing filter of --outscale\n"
+           "      --colorspace TEXT       (extension) {bt601,bt709,bt2020}: videos read through ffmpeg stay YUV 4:2:0 at --pix_fmt\n"
+           "                              (yuv420p or yuv420p10le) and are converted on the GPU; the output carries the colour tags\n"
+           "      --color_range TEXT [tv] (extension) {tv,pc}: the range of the --colorspace frames\n"
            "      --tta-mode TEXT [mean]  (extension) {mean,reference}: with --tta, `mean` averages the 8 augmentations; `reference`\n"
            "                              reproduces the bytes of the reference's accumulation (img2img_render.cpp:313-316); --tta-compat = reference\n"
            "  build                       Build model\n"
@@ -76,7 +79,7 @@ std::string usage() {
 Options parse(int argc, const char* const* argv) {
     Options o;
     std::vector<std::string> a(argv + 1, argv + argc);
-    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_filter = false;
+    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_filter = false, seen_colorspace = false, seen_range = false;
     auto value = [&](size_t& i) -> std::string {
         const std::string name = a[i];
         auto eq = name.find('=');
@@ -120,6 +123,8 @@ Options parse(int argc, const char* const* argv) {
         else if (k == "--crf") o.crf = to_int(k, value(i));
         else if (k == "--outscale") { o.outscale = to_double(k, value(i)); seen_outscale = true; }
         else if (k == "--resize-filter") { o.resizeFilter = value(i); std::transform(o.resizeFilter.begin(), o.resizeFilter.end(), o.resizeFilter.begin(), ::tolower); seen_filter = true; }
+        else if (k == "--colorspace") { o.colorspace = value(i); std::transform(o.colorspace.begin(), o.colorspace.end(), o.colorspace.begin(), ::tolower); seen_colorspace = true; }
+        else if (k == "--color_range") { o.colorRange = value(i); std::transform(o.colorRange.begin(), o.colorRange.end(), o.colorRange.begin(), ::tolower); seen_range = true; }
         else throw std::runtime_error("The following argument was not expected: " + a[i]);
     }
     if (o.command.empty()) throw std::runtime_error("A subcommand is required");
@@ -160,7 +165,14 @@ Options parse(int argc, const char* const* argv) {
                 for (const auto& p : o.inputs)
                     if (!std::filesystem::is_directory(p) && is_builtin_still(p)) throw std::runtime_error("--outscale: a still over --devices " + std::to_string(o.devices) + " is not supported: " + p);
         } else if (seen_filter) throw std::runtime_error("--resize-filter: needs --outscale");
-    } else if (seen_outscale || seen_filter) throw std::runtime_error(std::string(seen_outscale ? "--outscale" : "--resize-filter") + ": only with render");
+        if (seen_colorspace) {
+            member<std::string>("--colorspace", o.colorspace, {"bt601", "bt709", "bt2020"});
+            member<std::string>("--color_range", o.colorRange, {"tv", "pc"});
+            if (o.pixFmt != "yuv420p" && o.pixFmt != "yuv420p10le") throw std::runtime_error("--pix_fmt: with --colorspace one of {yuv420p,yuv420p10le}, got " + o.pixFmt);
+            if (seen_outscale) throw std::runtime_error("--colorspace: not together with --outscale (YUV frames are rendered at the network's size)");
+        } else if (seen_range) throw std::runtime_error("--color_range: needs --colorspace");
+    } else if (seen_outscale || seen_filter || seen_colorspace || seen_range)
+        throw std::runtime_error(std::string(seen_outscale ? "--outscale" : seen_filter ? "--resize-filter" : seen_colorspace ? "--colorspace" : "--color_range") + ": only with render");
     // cross-checks, main.cpp:142-145
     if (o.model == "cunet/art" && o.scale == 4) throw std::runtime_error("cunet/art does not support scale factor 4.");
     if (o.noise == -1 && o.scale == 1) throw std::runtime_error("Noise level -1 does not support scale factor 1.");
@@ -204,6 +216,7 @@ std::string to_json(const Options& o) {
        << ", \"precision\": " << q(o.precision) << ", \"recursive\": " << (o.recursive ? "true" : "false") << ", \"output\": " << q(o.output)
        << ", \"nosuffix\": " << (o.nosuffix ? "true" : "false") << ", \"blend\": " << o.blend << ", \"tta\": " << (o.tta ? "true" : "false") << ", \"tta_mode\": " << q(o.ttaMode)
        << ", \"outscale\": " << (o.outscale > 0 ? std::to_string(o.outscale) : std::string("null")) << ", \"resize_filter\": " << q(o.resizeFilter)
+       << ", \"colorspace\": " << (o.colorspace.empty() ? std::string("null") : q(o.colorspace)) << ", \"color_range\": " << q(o.colorRange)
        << ", \"codec\": " << q(o.codec) << ", \"pix_fmt\": " << q(o.pixFmt) << ", \"crf\": " << o.crf << ", \"inputs\": [";
     for (size_t i = 0; i < o.inputs.size(); ++i) os << (i ? ", " : "") << q(o.inputs[i]);
     os << "], \"model_path\": " << q(o.command == "convert" ? "" : model_path(o)) << ", \"suffix\": " << q(o.command == "convert" ? "" : output_suffix(o)) << ", \"outputs\": [";

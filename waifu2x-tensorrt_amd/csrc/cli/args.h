@@ -35,6 +35,9 @@ struct Options {
     double outscale = 0;                  // --outscale F: output lround(W * F) x lround(H * F), F in [1, --scale]: the network's output resized on the device
                                           // (Img2Img::renderResized / renderSequenceResized); 0 = the network's own size, the reference's behaviour
     std::string resizeFilter = "bicubic"; // --resize-filter {bicubic,bilinear}: the antialiasing filter of --outscale
+    std::string colorspace;               // --colorspace {bt601,bt709,bt2020}: videos read through ffmpeg travel as raw --pix_fmt (yuv420p / yuv420p10le)
+                                          // frames, converted on the GPU (Img2Img::renderSequenceYuv); "" = bgr24 frames, the reference's path
+    std::string colorRange = "tv";        // --color_range {tv,pc}: the range of those frames (with --colorspace only)
     bool printConfig = false;             // --print-config: dump the parsed options and derived names as JSON and exit (tests)
     bool help = false;
 };

@@ -61,7 +61,28 @@ std::vector<std::string> find_inputs(const cli::Options& o) {
     return files;
 }
 
-// ---- frame streams: raw bgr24 frames from / to an ffmpeg pipe or a built-in uncompressed AVI
+// ---- YUV 4:2:0 frames as ffmpeg's rawvideo yuv420p / yuv420p10le carries them: the Y, U and V planes back to back, rows unpadded
+size_t yuv_frame_bytes(int rows, int cols, const std::string& pixFmt) {
+    const size_t bps = pixFmt == "yuv420p10le" ? 2 : 1;
+    return ((size_t)rows * cols + 2 * (size_t)((rows + 1) / 2) * ((cols + 1) / 2)) * bps;
+}
+YuvImage packed_yuv(uint8_t* p, int rows, int cols, int bits) {
+    const size_t bps = bits > 8 ? 2 : 1, cw = (size_t)(cols + 1) / 2, ch = (size_t)(rows + 1) / 2;
+    YuvImage f;
+    f.planes[0] = p; f.planes[1] = p + (size_t)rows * cols * bps; f.planes[2] = f.planes[1] + ch * cw * bps;
+    f.steps[0] = (size_t)cols * bps; f.steps[1] = f.steps[2] = cw * bps;
+    f.rows = rows; f.cols = cols; f.bits = bits;
+    return f;
+}
+// the writer's colour tags for --colorspace / --color_range
+std::string colour_tags(const cli::Options& o) {
+    const char* m = o.colorspace == "bt601" ? "smpte170m" : o.colorspace == "bt2020" ? "bt2020nc" : "bt709";
+    const char* pr = o.colorspace == "bt601" ? "smpte170m" : o.colorspace == "bt2020" ? "bt2020" : "bt709";
+    const char* trc = o.colorspace == "bt601" ? "smpte170m" : o.colorspace == "bt2020" ? "bt2020-10" : "bt709";
+    return std::string("-colorspace ") + m + " -color_primaries " + pr + " -color_trc " + trc + " -color_range " + o.colorRange + " ";
+}
+
+// ---- frame streams: raw bgr24 (or --colorspace: YUV 4:2:0) frames from / to an ffmpeg pipe or a built-in uncompressed AVI
 struct FrameSource { virtual ~FrameSource() {} virtual bool read(uint8_t* bgr) = 0; };
 struct FrameSink { virtual ~FrameSink() {} virtual bool write(const uint8_t* bgr) = 0; virtual bool close() = 0; };
 
@@ -93,11 +114,12 @@ struct AviSink : FrameSink {
 // fills slots in stream order, one persistent worker per engine renders its chunks with renderSequence (upload / compute / download of
 // consecutive frames overlapped), one writer thread drains the slots in stream order - decoding, N renders and encoding all overlap,
 // and frames leave in the order they came (the reference serialises read -> render -> write per frame).
-// Output frames are outW x outH: the network's size, or with `resize` (--outscale) that size through renderSequenceResized.
-bool run_frame_pipeline(std::vector<std::unique_ptr<Img2Img>>& engines, FrameSource& src, FrameSink& dst, int width, int height, int outW, int outH,
-                        const ResizeFilter* resize, const std::function<void(int)>& on_frames) {
+// A frame is inBytes in and outBytes out; `render` turns `count` of them into outputs on one engine (renderSequence, renderSequenceResized for
+// --outscale, renderSequenceYuv for --colorspace).
+using RenderFrames = std::function<bool(Img2Img&, uint8_t* const* in, uint8_t* const* out, int count)>;
+bool run_frame_pipeline(std::vector<std::unique_ptr<Img2Img>>& engines, FrameSource& src, FrameSink& dst, size_t inBytes, size_t outBytes,
+                        const RenderFrames& render, const std::function<void(int)>& on_frames) {
     const int N = (int)engines.size(), CH = 4, SLOTS = 2;
-    const size_t inBytes = (size_t)width * height * 3, outBytes = (size_t)outW * outH * 3;
     struct Slot { std::vector<uint8_t*> in, out; int frames = 0; int state = 0; };   // 0 free, 1 read, 2 rendered
     std::vector<std::vector<Slot>> slots(N, std::vector<Slot>(SLOTS));
     auto release = [&] { for (int e = 0; e < N; ++e) for (Slot& sl : slots[e]) { for (uint8_t* p : sl.in) engines[e]->freeHost(p); for (uint8_t* p : sl.out) engines[e]->freeHost(p); sl.in.clear(); sl.out.clear(); } };
@@ -127,13 +149,7 @@ bool run_frame_pipeline(std::vector<std::unique_ptr<Img2Img>>& engines, FrameSou
         for (long c = e;; c += N) {
             Slot& sl = slot_of(c);
             { std::unique_lock<std::mutex> lk(mu); cv.wait(lk, [&] { return sl.state == 1 || failed || (total_chunks >= 0 && c >= total_chunks); }); if (failed || sl.state != 1) return; }
-            const int got = sl.frames;
-            std::vector<Image> si(got), di(got);
-            for (int k = 0; k < got; ++k) {
-                si[k] = Image{sl.in[k], height, width, (size_t)width * 3};
-                di[k] = Image{sl.out[k], outH, outW, (size_t)outW * 3};
-            }
-            const bool ok = resize ? engines[e]->renderSequenceResized(si.data(), di.data(), got, *resize) : engines[e]->renderSequence(si.data(), di.data(), got);
+            const bool ok = render(*engines[e], sl.in.data(), sl.out.data(), sl.frames);
             { std::lock_guard<std::mutex> lk(mu); if (!ok) failed = true; sl.state = 2; }
             cv.notify_all();
             if (!ok) return;
@@ -269,24 +285,30 @@ int main(int argc, char** argv) {
                 std::string why;
                 auto avi = std::make_unique<AviSource>();
                 const bool is_avi = fs::path(file).extension() == ".avi" || fs::path(file).extension() == ".AVI";
+                bool yuv = false;                                      // --colorspace on a multi-frame input read through ffmpeg: YUV 4:2:0 frames
                 if (is_avi && avi->rd.open(file, &why)) {
                     width = avi->rd.info().width; height = avi->rd.info().height; frames = avi->rd.info().frames; fps = avi->rd.info().fps;
                     source = std::move(avi);
                 } else {
-                    if (!have_ffmpeg) throw std::runtime_error(file + ": needs ffmpeg and ffprobe on PATH (built in: .png, .ppm, .bmp, uncompressed 24-bit .avi" + (why.empty() ? "" : "; " + why) + ")");
+                    if (!have_ffmpeg) throw std::runtime_error(file + ": needs ffmpeg and ffprobe on PATH (built in: .png, .ppm, .bmp, uncompressed 24-bit .avi" + (why.empty() ? "" : "; " + why) +
+                                                               (o.colorspace.empty() ? "" : "; --colorspace reads and writes YUV frames through ffmpeg only") + ")");
                     const Probe pr = ffprobe(file);
                     width = pr.width; height = pr.height; frames = pr.frames; fps = pr.fps;
-                    source.reset(new PipeSource("ffmpeg -v error -i " + shell_quote(file) + " -f rawvideo -pix_fmt bgr24 -", (size_t)width * height * 3));
+                    yuv = !o.colorspace.empty() && frames != 1;
+                    const size_t inBytes = yuv ? yuv_frame_bytes(height, width, o.pixFmt) : (size_t)width * height * 3;
+                    source.reset(new PipeSource("ffmpeg -v error -i " + shell_quote(file) + " -f rawvideo -pix_fmt " + (yuv ? o.pixFmt : std::string("bgr24")) + " -", inBytes));
                 }
                 frameIndex = 0; frameCount = frames;
                 const bool single = frames == 1;
                 std::string outFile = cli::output_path(o, file, single);
                 const int outW = cli::out_dim(o, width), outH = cli::out_dim(o, height);
-                const size_t outBytes = (size_t)outW * outH * 3;
+                const size_t inBytes = yuv ? yuv_frame_bytes(height, width, o.pixFmt) : (size_t)width * height * 3;
+                const size_t outBytes = yuv ? yuv_frame_bytes(outH, outW, o.pixFmt) : (size_t)outW * outH * 3;
                 if (have_ffmpeg) {
-                    std::string wcmd = "ffmpeg -v error -y -f rawvideo -pix_fmt bgr24 -s " + std::to_string(outW) + "x" + std::to_string(outH) +
+                    std::string wcmd = "ffmpeg -v error -y -f rawvideo -pix_fmt " + (yuv ? o.pixFmt : std::string("bgr24")) + " -s " + std::to_string(outW) + "x" + std::to_string(outH) +
                                        " -r " + std::to_string(single ? 1.0 : fps) + " -i - ";
                     if (!single) wcmd += "-c:v " + o.codec + " -pix_fmt " + o.pixFmt + " -crf " + std::to_string(o.crf) + " ";
+                    if (yuv) wcmd += colour_tags(o);
                     sink.reset(new PipeSink(wcmd + shell_quote(outFile), outBytes));
                 } else {   // no encoder here: the upscaled stream as an uncompressed AVI
                     outFile = fs::path(outFile).replace_extension(".avi").string();
@@ -295,7 +317,23 @@ int main(int argc, char** argv) {
                     as->wr.open(outFile, outW, outH, fps);
                     sink = std::move(as);
                 }
-                const bool ok = run_frame_pipeline(engines, *source, *sink, width, height, outW, outH, resize ? &filter : nullptr, [&](int n) { frameIndex += n; if (n) on_progress(1, 1, 0.0); });
+                RenderFrames render = [&](Img2Img& e, uint8_t* const* in, uint8_t* const* out, int n) {
+                    std::vector<Image> si(n), di(n);
+                    for (int k = 0; k < n; ++k) { si[k] = Image{in[k], height, width, (size_t)width * 3}; di[k] = Image{out[k], outH, outW, (size_t)outW * 3}; }
+                    return resize ? e.renderSequenceResized(si.data(), di.data(), n, filter) : e.renderSequence(si.data(), di.data(), n);
+                };
+                if (yuv) {
+                    YuvFormat f;
+                    f.matrix = o.colorspace == "bt601" ? YuvMatrix::BT601 : o.colorspace == "bt2020" ? YuvMatrix::BT2020 : YuvMatrix::BT709;
+                    f.range = o.colorRange == "pc" ? YuvRange::Full : YuvRange::Limited;
+                    const int bits = o.pixFmt == "yuv420p10le" ? 10 : 8;
+                    render = [=](Img2Img& e, uint8_t* const* in, uint8_t* const* out, int n) {
+                        std::vector<YuvImage> si(n), di(n);
+                        for (int k = 0; k < n; ++k) { si[k] = packed_yuv(in[k], height, width, bits); di[k] = packed_yuv(out[k], outH, outW, bits); }
+                        return e.renderSequenceYuv(si.data(), di.data(), n, f);
+                    };
+                }
+                const bool ok = run_frame_pipeline(engines, *source, *sink, inBytes, outBytes, render, [&](int n) { frameIndex += n; if (n) on_progress(1, 1, 0.0); });
                 const bool closed = sink->close();
                 if (!ok || !closed) return -1;
             }

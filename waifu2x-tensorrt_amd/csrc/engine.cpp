@@ -281,6 +281,10 @@ struct Img2Img::Impl {
     };
     std::deque<ResizeTables> rs_tables;
     const ResizeTables* rs = nullptr;
+    // renderYuv() / renderSequenceYuv(): the frame being rendered is YUV 4:2:0 (null outside such a call).  d_frame / d_out then hold the three planes
+    // (yuv_layout) and the gather / compose launches are gather_yuv_kernel / compose_yuv_kernel; `key` tells the captured passes of each input format apart.
+    struct YuvJob { YuvCoefs in, out; int in_bits = 8, out_bits = 8, key = 0; };
+    const YuvJob* yuv = nullptr;
     std::vector<void*> pinned;
     std::vector<void*> host_allocs;     // allocHost(): page-locked buffers handed to the caller
     std::vector<TileSlot> h_slots;
@@ -337,7 +341,7 @@ struct Img2Img::Impl {
     // enqueueV3 (img2img_infer.cpp:80); here a pass is ~40 launches, which the host cannot issue fast enough for small tiles.
     // A pass is captured the second time it is met (the first run stays eager so that one-time attribute calls are out of the
     // way) and replayed from then on.  The key holds everything the captured launches bake in.
-    using GraphKey = std::tuple<const void*, const void*, const void*, const void*, int, int, int, int>;   // frame, slots, slab out, arena, rows, cols, live, 16-bit samples
+    using GraphKey = std::tuple<const void*, const void*, const void*, const void*, int, int, int, int>;   // frame, slots, slab out, arena, rows, cols, live, sample format (1: 16-bit, >= 2: YuvJob::key)
     // A pass that runs as NG tile groups is NG graphs, one per group, each a straight line of launches replayed on that group's OWN stream (fork / join
     // events between the streams are issued around the replays): a single captured graph with NG branches runs its side branches on streams the runtime
     // creates at instantiation, which land on whichever hardware queue has the fewest users at that moment - sometimes the copy streams' queue, where the
@@ -878,6 +882,7 @@ struct Img2Img::Impl {
     void run_frame(int rows, int cols, const TileGrid& grid, bool report, const StripPlan& sp) {
         run_passes(rows, cols, sp.tile_count, 0, report, 0, true);
         if (rs) { compose_canvas(rows, cols, grid, stream); resample(stream); return; }   // a resized frame (renderResized)
+        if (yuv) { compose_yuv(rows, cols, grid, stream); return; }                       // a YUV frame (renderYuv)
         compose_rect(rows, cols, grid, sp.x0, sp.x1, 0, 0, sp.first_tile);
     }
 
@@ -915,7 +920,8 @@ struct Img2Img::Impl {
             return;
         }
         if (out_free) hipAssert(hipStreamWaitEvent(s2, out_free, 0));     // the frame that last left through this output buffer has been downloaded
-        compose_rect(rows, cols, grid, sp.x0, sp.x1, 0, 0, sp.first_tile, s2);
+        if (yuv) compose_yuv(rows, cols, grid, s2);
+        else compose_rect(rows, cols, grid, sp.x0, sp.x1, 0, 0, sp.first_tile, s2);
         hipAssert(hipEventRecord(ev_cmp[which], s2));
     }
     // after the last frame of a rolling sequence: the first stream waits for the second, so that whatever follows on it sees the sequence done
@@ -967,10 +973,17 @@ struct Img2Img::Impl {
                 }
             }
             auto group_stream = [&](int grp) { return grp ? gstream[grp - 1] : stream; };
+            auto gather = [&](const GatherParams& gp, hipStream_t gs) {
+                if (!yuv) { hipAssert(launch_gather(gp, gs)); return; }
+                GatherYuvParams yp;                                   // a YUV frame (renderYuv): the same tiles from its planes
+                yp.src = yuv_layout(d_frame, rows, cols, yuv->in_bits); yp.k = yuv->in;
+                yp.out = gp.out; yp.fp32 = gp.fp32; yp.slots = gp.slots; yp.B = gp.B; yp.T = gp.T;
+                hipAssert(launch_gather_yuv(yp, gs));
+            };
             auto gather_group = [&](int grp, hipStream_t gs) {       // the group's tiles at the start of its part of the arena
                 GatherParams gp = gp0;
                 gp.out = group_ptr(tensors[plan.in_tensor], grp); gp.slots = gp0.slots + (size_t)first[grp]; gp.B = first[grp + 1] - first[grp];
-                hipAssert(launch_gather(gp, gs));
+                gather(gp, gs);
             };
             auto network_group = [&](int grp, hipStream_t gs) { run_network((uint8_t*)slab_out + (size_t)first[grp] * slot_bytes, first[grp + 1] - first[grp], grp, gs); };
             auto fork = [&] { hipAssert(hipEventRecord(ev_fork, stream)); for (int grp = 1; grp < NG; ++grp) hipAssert(hipStreamWaitEvent(gstream[grp - 1], ev_fork, 0)); };
@@ -979,7 +992,7 @@ struct Img2Img::Impl {
             auto run_pass = [&] {
                 if (!split) {
                     stamp_begin(3, 0);
-                    hipAssert(launch_gather(gp0, stream));
+                    gather(gp0, stream);
                     stamp_end();
                     run_network(slab_out, live);
                     return;
@@ -999,7 +1012,7 @@ struct Img2Img::Impl {
             auto run_eager = [&] { if (per_group) { fork(); for (int grp = 0; grp < NG; ++grp) run_group(grp); if (!no_join) join(); } else { if (rolling && gstream[0]) { join(); } run_pass(); } };
             if (!graphable) run_eager();
             else {
-                const GraphKey key{d_frame, d_slots + slots_off + (size_t)bi * B, slab_out, arena_base, rows, cols, live, deep ? 1 : 0};
+                const GraphKey key{d_frame, d_slots + slots_off + (size_t)bi * B, slab_out, arena_base, rows, cols, live, yuv ? yuv->key : deep ? 1 : 0};
                 auto replay = [&](const PassGraphs& pg) {
                     if (pg.n == 1) { if (rolling && gstream[0]) join(); hipAssert(hipGraphLaunch(pg.g[0], stream)); return; }   // (a whole-arena pass inside a rolling sequence: the other stream's group first)
                     fork();
@@ -1082,6 +1095,91 @@ struct Img2Img::Impl {
         cp.ramp_x = d_rampx; cp.ramp_y = d_rampy; cp.tta = cfg.tta ? 1 : 0; cp.tta_bug_compat = cfg.ttaBugCompat ? 1 : 0;
         hipAssert(launch_compose_canvas(cp, d_canvas, on));
     }
+    // YUV frames (yuv set): the whole canvas of the frame's tiles (one part, slot 0 = tile 0) written as YUV 4:2:0 planes into d_out
+    void compose_yuv(int rows, int cols, const TileGrid& grid, hipStream_t on) {
+        const int To = plan.Tout;
+        ComposeYuvParams yp;
+        ComposeParams& cp = yp.c;
+        cp.tiles = d_slab; cp.fp32 = plan.elt == 4;
+        cp.outW = cols * cfg.scaling; cp.outH = rows * cfg.scaling; cp.To = To;
+        cp.nx = grid.nx; cp.ny = grid.ny; cp.stride_x = To - grid.outOvX; cp.stride_y = To - grid.outOvY;
+        const bool overlapping = cfg.overlapX != 0 || cfg.overlapY != 0;
+        cp.ovx = overlapping ? ovx : 0; cp.ovy = overlapping ? ovy : 0;
+        cp.ramp_x = d_rampx; cp.ramp_y = d_rampy; cp.tta = cfg.tta ? 1 : 0; cp.tta_bug_compat = cfg.ttaBugCompat ? 1 : 0;
+        yp.dst = yuv_layout(d_out, cp.outH, cp.outW, yuv->out_bits); yp.k = yuv->out;
+        stamp_begin(4, 0);
+        hipAssert(launch_compose_yuv(yp, on));
+        stamp_end();
+    }
+    // the slot table and the slab of a sequence's frames (renderSequence / renderSequenceYuv): every tile of the frame, in one part
+    void sequence_slots(const TileGrid& grid, const StripPlan& sp) {
+        const int steps = cfg.tta ? 8 : 1, B = plan.B, S = plan.B / plan.userB;
+        const int batchCount = (int)std::lround(std::ceil((double)(sp.tile_count * steps) / plan.userB));
+        const int stepCount = ((batchCount + S - 1) / S) * B;
+        h_slots.resize(stepCount);
+        for (int st = 0; st < stepCount; ++st) {
+            int ti = st / steps, aug = st % steps;
+            TileSlot sl{0, 0, aug, 0};
+            if (ti < sp.tile_count) { sl.x = grid.in[ti].x; sl.y = grid.in[ti].y; sl.valid = 1; }
+            h_slots[st] = sl;
+        }
+        ensure(d_slots, slots_cap, (size_t)stepCount * sizeof(TileSlot));
+        hipAssert(hipMemcpyAsync(d_slots, h_slots.data(), (size_t)stepCount * sizeof(TileSlot), hipMemcpyHostToDevice, stream));
+        ensure(d_slab, slab_cap, (size_t)stepCount * plan.Tout * plan.Tout * 4 * plan.elt);
+        hipAssert(hipStreamSynchronize(stream));
+    }
+    // The frame loop of renderSequence() / renderSequenceYuv(): frame i is uploaded by up(i, device buffer, s_up) into one of two frame buffers, rendered
+    // (rolling when every pass of a frame splits: run_rolling_frame) into one of two output buffers, and downloaded by down(i, device buffer, s_dn); events
+    // order the three streams where a buffer comes round again.  Returns the compute stream's milliseconds for the whole sequence.
+    template <class Up, class Down>
+    float run_sequence(int count, int rows, int cols, const TileGrid& grid, const StripPlan& sp, const Up& up, const Down& down) {
+        uint8_t* const frames[2] = {d_frame, d_frame2};
+        uint8_t* const outs[2] = {d_out, d_out2};
+        struct Restore { Impl* im; uint8_t* f; uint8_t* o; ~Restore() { im->d_frame = f; im->d_out = o; } } restore{this, frames[0], outs[0]};   // also on exceptions
+        // frame f is composed on the second group's stream while frame f + 1's first group already runs (run_rolling_frame) when every pass of a frame splits
+        const bool roll = count > 1 && can_roll(sp.tile_count);
+        if (roll) ensure(d_slab2, slab2_cap, slab_cap);
+        hipAssert(hipStreamSynchronize(stream));
+        hipAssert(hipEventRecord(ev0, stream));
+        for (int i = 0; i < count; ++i) {
+            const int b = i & 1;
+            if (i >= 2) hipAssert(hipStreamWaitEvent(s_up, ev_comp[b], 0));       // frame i-2 has been gathered out of this buffer
+            up(i, frames[b], s_up);
+            hipAssert(hipEventRecord(ev_up[b], s_up));
+            hipAssert(hipStreamWaitEvent(stream, ev_up[b], 0));
+            d_frame = frames[b]; d_out = outs[b];
+            if (roll) {
+                run_rolling_frame(rows, cols, grid, sp, b, i >= 2 ? ev_dn[b] : nullptr);
+                hipAssert(hipEventRecord(ev_comp[b], gstream[0]));              // (behind the compose launch: both groups have gathered, the output is whole)
+            } else {
+                if (i >= 2) hipAssert(hipStreamWaitEvent(stream, ev_dn[b], 0));         // frame i-2 has left this output buffer
+                run_frame(rows, cols, grid, false, sp);
+                hipAssert(hipEventRecord(ev_comp[b], stream));
+            }
+            hipAssert(hipStreamWaitEvent(s_dn, ev_comp[b], 0));
+            down(i, outs[b], s_dn);
+            hipAssert(hipEventRecord(ev_dn[b], s_dn));
+        }
+        if (roll) end_rolling();
+        hipAssert(hipEventRecord(ev1, stream));
+        hipAssert(hipStreamSynchronize(s_dn));
+        hipAssert(hipStreamSynchronize(stream));
+        hipAssert(hipStreamSynchronize(s_up));
+        float total_ms = 0.f;
+        hipAssert(hipEventElapsedTime(&total_ms, ev0, ev1));
+        return total_ms;
+    }
+    // the device layout of a YUV frame in d_frame / d_out: Y, U, V one after the other, rows padded to 16 bytes (the stores of compose_yuv_kernel)
+    static YuvPlanes yuv_layout(uint8_t* base, int rows, int cols, int bits) {
+        const size_t bps = bits > 8 ? 2 : 1;
+        const int cw = (cols + 1) / 2, ch = (rows + 1) / 2;
+        YuvPlanes f;
+        f.rows = rows; f.cols = cols; f.bits = bits;
+        f.step[0] = ((size_t)cols * bps + 15) / 16 * 16; f.step[1] = f.step[2] = ((size_t)cw * bps + 15) / 16 * 16;
+        f.p[0] = base; f.p[1] = base + f.step[0] * rows; f.p[2] = f.p[1] + f.step[1] * ch;
+        return f;
+    }
+    static size_t yuv_bytes(int rows, int cols, int bits) { const YuvPlanes f = yuv_layout(nullptr, rows, cols, bits); return f.step[0] * rows + 2 * f.step[1] * ((rows + 1) / 2); }
     void resample(hipStream_t on) {
         ResampleParams rp;
         rp.canvas = d_canvas; rp.inW = rs->inW; rp.inH = rs->inH;
@@ -1817,60 +1915,16 @@ bool Img2Img::runSequence(const Image* srcs, Image* dsts, int count, int resizeF
     if (grid.count <= 0) { W2X_LOG_AS(who, error, "Tile grid is empty."); return false; }
     for (const Rect& r : grid.out) if (r.w <= 0 || r.h <= 0) { W2X_LOG_AS(who, error, "Tile grid does not fit the output (scaling does not match the model)."); return false; }
     const StripPlan sp = strip_plan(grid, cols * s, plan.Tout, 0, 1);
-    const int steps = cfg.tta ? 8 : 1, B = plan.B, S = plan.B / plan.userB;
-    const int batchCount = (int)std::lround(std::ceil((double)(sp.tile_count * steps) / plan.userB));
-    const int stepCount = ((batchCount + S - 1) / S) * B;
-    impl->h_slots.resize(stepCount);
-    for (int st = 0; st < stepCount; ++st) {
-        int ti = st / steps, aug = st % steps;
-        TileSlot sl{0, 0, aug, 0};
-        if (ti < sp.tile_count) { sl.x = grid.in[ti].x; sl.y = grid.in[ti].y; sl.valid = 1; }
-        impl->h_slots[st] = sl;
-    }
-    impl->ensure(impl->d_slots, impl->slots_cap, (size_t)stepCount * sizeof(TileSlot));
-    hipAssert(hipMemcpyAsync(impl->d_slots, impl->h_slots.data(), (size_t)stepCount * sizeof(TileSlot), hipMemcpyHostToDevice, stream));
-    impl->ensure(impl->d_slab, impl->slab_cap, (size_t)stepCount * plan.Tout * plan.Tout * 4 * plan.elt);
-    hipAssert(hipStreamSynchronize(stream));
+    impl->sequence_slots(grid, sp);
 
-    uint8_t* const frames[2] = {impl->d_frame, impl->d_frame2};
-    uint8_t* const outs[2] = {impl->d_out, impl->d_out2};
-    struct Restore { Impl* im; uint8_t* f; uint8_t* o; ~Restore() { im->d_frame = f; im->d_out = o; } } restore{impl.get(), frames[0], outs[0]};   // also on exceptions
-    // frame f is composed on the second group's stream while frame f + 1's first group already runs (run_rolling_frame) when every pass of a frame splits
-    const bool roll = count > 1 && impl->can_roll(sp.tile_count);
-    if (roll) impl->ensure(impl->d_slab2, impl->slab2_cap, impl->slab_cap);
     struct ResizeScope { Img2Img::Impl* e; ~ResizeScope() { e->rs = nullptr; } } resize_scope{impl.get()};
     if (resized) {
         impl->rs = impl->resize_tables(cols * s, rows * s, out_cols, out_rows, resizeFilter);
         impl->ensure_canvas((size_t)rows * s * cols * s * 3 * sizeof(float));
     }
-    hipAssert(hipStreamSynchronize(stream));
-    hipAssert(hipEventRecord(impl->ev0, stream));
-    for (int i = 0; i < count; ++i) {
-        const int b = i & 1;
-        if (i >= 2) hipAssert(hipStreamWaitEvent(impl->s_up, impl->ev_comp[b], 0));       // frame i-2 has been gathered out of this buffer
-        hipAssert(hipMemcpy2DAsync(frames[b], (size_t)cols * 3, srcs[i].data, srcs[i].step, (size_t)cols * 3, rows, hipMemcpyHostToDevice, impl->s_up));
-        hipAssert(hipEventRecord(impl->ev_up[b], impl->s_up));
-        hipAssert(hipStreamWaitEvent(stream, impl->ev_up[b], 0));
-        impl->d_frame = frames[b]; impl->d_out = outs[b];
-        if (roll) {
-            impl->run_rolling_frame(rows, cols, grid, sp, b, i >= 2 ? impl->ev_dn[b] : nullptr);
-            hipAssert(hipEventRecord(impl->ev_comp[b], impl->gstream[0]));              // (behind the compose launch: both groups have gathered, the output is whole)
-        } else {
-            if (i >= 2) hipAssert(hipStreamWaitEvent(stream, impl->ev_dn[b], 0));         // frame i-2 has left this output buffer
-            impl->run_frame(rows, cols, grid, false, sp);
-            hipAssert(hipEventRecord(impl->ev_comp[b], stream));
-        }
-        hipAssert(hipStreamWaitEvent(impl->s_dn, impl->ev_comp[b], 0));
-        hipAssert(hipMemcpy2DAsync(dsts[i].data, dsts[i].step, outs[b], (size_t)out_cols * 3, (size_t)out_cols * 3, out_rows, hipMemcpyDeviceToHost, impl->s_dn));
-        hipAssert(hipEventRecord(impl->ev_dn[b], impl->s_dn));
-    }
-    if (roll) impl->end_rolling();
-    hipAssert(hipEventRecord(impl->ev1, stream));
-    hipAssert(hipStreamSynchronize(impl->s_dn));
-    hipAssert(hipStreamSynchronize(stream));
-    hipAssert(hipStreamSynchronize(impl->s_up));
-    float total_ms = 0.f;
-    hipAssert(hipEventElapsedTime(&total_ms, impl->ev0, impl->ev1));
+    const float total_ms = impl->run_sequence(count, rows, cols, grid, sp,
+        [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dev, (size_t)cols * 3, srcs[i].data, srcs[i].step, (size_t)cols * 3, rows, hipMemcpyHostToDevice, on)); },
+        [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dsts[i].data, dsts[i].step, dev, (size_t)out_cols * 3, (size_t)out_cols * 3, out_rows, hipMemcpyDeviceToHost, on)); });
     impl->last_ms = total_ms / count;        // lastRenderMs(): compute-stream time per frame of the sequence
     impl->last_rows = rows; impl->last_cols = cols; impl->last_grid = grid; impl->last_strip = sp;
     if (resized) impl->last_rows = impl->last_cols = 0;   // (not replayed by benchResident: renderPart)
@@ -1878,6 +1932,80 @@ bool Img2Img::runSequence(const Image* srcs, Image* dsts, int count, int resizeF
 } catch (const std::exception& e) {
     // copies on the side streams may still be reading or writing the caller's buffers, and a rolling sequence composes on the second group's stream
     // (end_rolling() has not run when an exception fires): let all four drain before the caller gets its buffers back
+    impl->drain_after_error();
+    W2X_LOG_AS(who, error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
+    return false;
+}
+
+// renderYuv(): the sequence of one frame (run_frame: no rolling)
+bool Img2Img::renderYuv(const YuvImage& src, YuvImage& dst, YuvFormat format) { return runSequenceYuv(&src, &dst, 1, format, "renderYuv"); }
+
+bool Img2Img::renderSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format) {
+    return runSequenceYuv(srcs, dsts, count, format, "renderSequenceYuv");
+}
+
+// YUV 4:2:0 frames through renderSequence()'s pipeline: per frame three plane copies up on s_up, the passes with gather_yuv_kernel, compose_yuv_kernel
+// (on the second group's stream when the sequence rolls), three plane copies down on s_dn.  One size and one pair of depths for the sequence.
+bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, const char* who) try {
+    if (!impl->loaded) { W2X_LOG_AS(who, error, "Render called before a successful load."); return false; }
+    if (count <= 0) return true;
+    if (!srcs || !dsts) { W2X_LOG_AS(who, error, "No frames given."); return false; }
+    DeviceGuard guard(impl->device);
+    const RenderConfig& cfg = impl->cfg;
+    const Plan& plan = impl->plan;
+    const int matrix = (int)format.matrix, range = (int)format.range;
+    if (matrix < 0 || matrix > 2) { W2X_LOG_AS(who, error, "Unknown YUV matrix " + std::to_string(matrix) + "."); return false; }
+    if (range < 0 || range > 1) { W2X_LOG_AS(who, error, "Unknown YUV range " + std::to_string(range) + "."); return false; }
+    const int rows = srcs[0].rows, cols = srcs[0].cols, s = cfg.scaling, in_bits = srcs[0].bits, out_bits = dsts[0].bits;
+    if ((in_bits != 8 && in_bits != 10) || (out_bits != 8 && out_bits != 10)) { W2X_LOG_AS(who, error, "YUV frames must have 8 or 10 bits."); return false; }
+    if (rows <= 0 || cols <= 0) { W2X_LOG_AS(who, error, "Input image is empty."); return false; }
+    // every plane present, with a step that holds its row
+    auto planes_ok = [](const YuvImage& f) {
+        const size_t bps = f.bits > 8 ? 2 : 1;
+        for (int k = 0; k < 3; ++k) if (!f.planes[k] || f.steps[k] < (size_t)(k ? (f.cols + 1) / 2 : f.cols) * bps) return false;
+        return true;
+    };
+    for (int i = 0; i < count; ++i) {
+        if (srcs[i].rows != rows || srcs[i].cols != cols || srcs[i].bits != in_bits) { W2X_LOG_AS(who, error, "Input images must be of one size and depth."); return false; }
+        if (!planes_ok(srcs[i])) { W2X_LOG_AS(who, error, "Input image has a missing plane or an invalid step."); return false; }
+        if (dsts[i].rows != rows * s || dsts[i].cols != cols * s) { W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(cols * s) + "x" + std::to_string(rows * s) + "."); return false; }
+        if (dsts[i].bits != out_bits) { W2X_LOG_AS(who, error, "Output images must be of one depth."); return false; }
+        if (!planes_ok(dsts[i])) { W2X_LOG_AS(who, error, "Output image has a missing plane or an invalid step."); return false; }
+    }
+    hipStream_t stream = impl->stream;
+    impl->ensure_copy_streams();
+    const size_t in_bytes = Impl::yuv_bytes(rows, cols, in_bits), out_bytes = Impl::yuv_bytes(rows * s, cols * s, out_bits);
+    impl->ensure(impl->d_frame, impl->frame_cap, in_bytes);   impl->ensure(impl->d_frame2, impl->frame2_cap, in_bytes);
+    impl->ensure(impl->d_out, impl->out_cap, out_bytes);      impl->ensure(impl->d_out2, impl->out2_cap, out_bytes);
+    TileGrid grid = calculate_tiles(cols, rows, cols * s, rows * s, plan.T, plan.T, plan.Tout, plan.Tout, s, cfg.overlapX, cfg.overlapY);
+    if (grid.count <= 0) { W2X_LOG_AS(who, error, "Tile grid is empty."); return false; }
+    for (const Rect& r : grid.out) if (r.w <= 0 || r.h <= 0) { W2X_LOG_AS(who, error, "Tile grid does not fit the output (scaling does not match the model)."); return false; }
+    const StripPlan sp = strip_plan(grid, cols * s, plan.Tout, 0, 1);
+    impl->sequence_slots(grid, sp);
+
+    struct YuvScope { Impl* im; ~YuvScope() { im->yuv = nullptr; } } yuv_scope{impl.get()};   // also on exceptions
+    Impl::YuvJob job;
+    job.in = yuv_coefs(matrix, range, in_bits); job.out = yuv_coefs(matrix, range, out_bits);
+    job.in_bits = in_bits; job.out_bits = out_bits; job.key = 2 + (in_bits == 10 ? 1 : 0) + 2 * range + 4 * matrix;
+    impl->yuv = &job;
+    impl->deep = false;
+    // the three planes of a frame between the caller's layout and the device's (yuv_layout), on copy stream `on`
+    auto copy_planes = [&](const YuvImage& host, uint8_t* dev, int r, int c, bool up, hipStream_t on) {
+        const YuvPlanes d = Impl::yuv_layout(dev, r, c, host.bits);
+        const size_t bps = host.bits > 8 ? 2 : 1;
+        for (int k = 0; k < 3; ++k) {
+            const size_t width = (size_t)(k ? (c + 1) / 2 : c) * bps; const int h = k ? (r + 1) / 2 : r;
+            if (up) hipAssert(hipMemcpy2DAsync(d.p[k], d.step[k], host.planes[k], host.steps[k], width, h, hipMemcpyHostToDevice, on));
+            else hipAssert(hipMemcpy2DAsync(host.planes[k], host.steps[k], d.p[k], d.step[k], width, h, hipMemcpyDeviceToHost, on));
+        }
+    };
+    const float total_ms = impl->run_sequence(count, rows, cols, grid, sp,
+        [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(srcs[i], dev, rows, cols, true, on); },
+        [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(dsts[i], dev, rows * s, cols * s, false, on); });
+    impl->last_ms = total_ms / count;
+    impl->last_rows = impl->last_cols = 0;   // (d_frame / d_out hold planes: not replayed by benchResident / residentOutput / profileFrame)
+    return true;
+} catch (const std::exception& e) {
     impl->drain_after_error();
     W2X_LOG_AS(who, error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
     return false;

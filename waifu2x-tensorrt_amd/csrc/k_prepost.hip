@@ -8,6 +8,8 @@
 //             in the order left, top, right, bottom, fp32 overlap-add, *255 -> rint -> saturate -> BGR.  Replaces
 //             imagesFromBlob (img2img_infer.cpp:23-39), reverseAugmentation/TTA accumulate (:179-222,:305-318),
 //             applyWeights (:107-121), the canvas add (:329-330) and the final convertTo/cvtColor (:342-343).
+//   gather_yuv / compose_yuv: the same two steps on YUV 4:2:0 frames (renderYuv): colour conversion and chroma resampling
+//             folded into the tile reads and the canvas writes.
 //   se/scale: cunet squeeze-excite gate and channel scaling.
 #include "kernels.h"
 
@@ -252,6 +254,146 @@ __global__ __launch_bounds__(256) void compose_canvas_kernel(const ComposeParams
     }
 }
 
+// YUV 4:2:0 frames (renderYuv).  One sample of plane `pl` (8-bit: uint8, 10-bit: uint16).
+__device__ __forceinline__ float yuv_sample(const YuvPlanes& f, int pl, int y, int x) {
+    const uint8_t* row = f.p[pl] + (size_t)y * f.step[pl];
+    return f.bits > 8 ? (float)((const uint16_t*)row)[x] : (float)row[x];
+}
+
+// gather_kernel on a YUV frame: the same tile layout, slots and source index (clamped, through aug_src); per tile pixel Y and the 2 x 2 chroma
+// neighbours of its source position, chroma upsampled to the luma grid (columns: even x C[x/2], odd x the mean of C[(x-1)/2] and C[(x+1)/2]; rows:
+// 2k takes 1/4 C[k-1] + 3/4 C[k], 2k+1 takes 3/4 C[k] + 1/4 C[k+1]; indices clamped), the matrix inverted in fp32, R, G, B clamped to [0, 1].
+// (The upsampled codes are exact in fp32: integers below 2^10 times quarters.)
+template <typename P>
+__global__ __launch_bounds__(256) void gather_yuv_kernel(const GatherYuvParams p) {
+    const int T = p.T;
+    const long total = (long)p.B * T * T;
+    const int rows = p.src.rows, cols = p.src.cols, ch = (rows + 1) >> 1, cw = (cols + 1) >> 1;
+    const YuvCoefs& k = p.k;
+    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
+        int b = (int)(i / ((long)T * T));
+        int rem = (int)(i - (long)b * T * T);
+        int y = rem / T, x = rem - y * T;
+        TileSlot sl = p.slots[b];
+        P v = make_px<P>(0.f, 0.f, 0.f);
+        if (sl.valid) {
+            int sy, sx;
+            aug_src(sl.aug, T - 1, y, x, sy, sx);
+            const int fy = min(max(sl.y + sy, 0), rows - 1), fx = min(max(sl.x + sx, 0), cols - 1);
+            const int ck = fy >> 1, cj = fx >> 1;
+            const bool odd_y = fy & 1;
+            const int r0 = odd_y ? ck : max(ck - 1, 0), r1 = odd_y ? min(ck + 1, ch - 1) : ck;
+            const float w0 = odd_y ? 0.75f : 0.25f, w1 = odd_y ? 0.25f : 0.75f;
+            const int c1 = (fx & 1) ? min(cj + 1, cw - 1) : cj;
+            const float u = w0 * (0.5f * (yuv_sample(p.src, 1, r0, cj) + yuv_sample(p.src, 1, r0, c1))) + w1 * (0.5f * (yuv_sample(p.src, 1, r1, cj) + yuv_sample(p.src, 1, r1, c1)));
+            const float w = w0 * (0.5f * (yuv_sample(p.src, 2, r0, cj) + yuv_sample(p.src, 2, r0, c1))) + w1 * (0.5f * (yuv_sample(p.src, 2, r1, cj) + yuv_sample(p.src, 2, r1, c1)));
+            const float Y = (yuv_sample(p.src, 0, fy, fx) - k.y_off) * k.y_mul, cb = (u - k.c_off) * k.c_mul, cr = (w - k.c_off) * k.c_mul;
+            const float R = Y + k.r_cr * cr, G = Y + k.g_cb * cb + k.g_cr * cr, B = Y + k.b_cb * cb;
+            v = make_px<P>(fminf(fmaxf(R, 0.f), 1.f), fminf(fmaxf(G, 0.f), 1.f), fminf(fmaxf(B, 0.f), 1.f));
+        }
+        *((P*)p.out + i) = v;
+    }
+}
+
+__device__ __forceinline__ unsigned yuv_code(float off, float scale, float v, int maxcode) { return (unsigned)min(max(__float2int_rn(off + scale * v), 0), maxcode); }
+
+// compose_kernel for a YUV 4:2:0 output.  A thread owns kYuvSites consecutive chroma sites of one chroma row: the 2 x 8 luma pixels under them
+// (rows 2i, 2i + 1, columns 8t .. 8t + 7).  Each pixel's sums come from compose_pixel_sums (the blend and TTA order of the u8 path), clamped to [0, 1];
+// Y is coded per pixel.  Chroma site j filters the two rows (1/2, 1/2) and columns 2j - 1, 2j, 2j + 1 (1/4, 1/2, 1/4), coordinates clamped to the
+// frame.  Column 8t - 1 belongs to the lane on the left: it arrives by a cross-lane move (ds_bpermute), and only lane 0 of the wave, whose left
+// neighbour lies in another workgroup, computes it again.  A full run stores Y as 8 (10-bit: 16) bytes per row and U, V as 4 (8) bytes; the ragged
+// right end stores sample by sample.  Workgroup = one wave along a chroma row; no canvas goes through HBM.
+template <typename P>
+__global__ __launch_bounds__(kYuvThreads) void compose_yuv_kernel(const ComposeYuvParams p) {
+    static_assert(kYuvSites == 4, "the packed stores below are written for four sites per thread");
+    constexpr int kCols = 2 * kYuvSites;
+    const ComposeParams& c = p.c;
+    const P* tiles = (const P*)c.tiles;
+    const YuvCoefs& k = p.k;
+    const int W = c.outW, H = c.outH, cw = (W + 1) >> 1, ch = (H + 1) >> 1;
+    const int runs = (cw + kYuvSites - 1) / kYuvSites;
+    const int t = blockIdx.x * kYuvThreads + threadIdx.x;
+    const bool active = t < runs;
+    const int j0 = t * kYuvSites, X0 = 2 * j0;
+    const int ncols = active ? min(kCols, W - X0) : 0;         // luma columns of the run inside the frame (>= 1 for an active lane)
+    const bool wide = p.dst.bits > 8;
+    auto pixel = [&](int X, int Y, float* o) {
+        float r, g, b;
+        compose_pixel_sums<P>(c, tiles, X, Y, r, g, b);
+        o[0] = fminf(fmaxf(r, 0.f), 1.f); o[1] = fminf(fmaxf(g, 0.f), 1.f); o[2] = fminf(fmaxf(b, 0.f), 1.f);
+    };
+    for (int ci = blockIdx.y; ci < ch; ci += gridDim.y) {
+        const int Ya = 2 * ci, Yb = min(2 * ci + 1, H - 1);
+        float v[kCols][3];                                      // the run's columns, the two rows averaged
+        float left[3] = {0.f, 0.f, 0.f};
+        for (int r = 0; r < 2; ++r) {
+            const int Y = r ? Yb : Ya;
+            const bool store_y = r == 0 || Yb != Ya;
+            unsigned yc[kCols];
+#pragma unroll
+            for (int q = 0; q < kCols; ++q) {
+                float o[3] = {0.f, 0.f, 0.f};
+                if (q < ncols) pixel(X0 + q, Y, o);
+                yc[q] = yuv_code(k.y_off, k.y_scale, k.kr * o[0] + k.kg * o[1] + k.kb * o[2], k.maxcode);
+#pragma unroll
+                for (int e = 0; e < 3; ++e) v[q][e] = r ? 0.5f * (v[q][e] + o[e]) : o[e];
+            }
+            if (threadIdx.x == 0 && active && X0 > 0) {              // the wave's first lane: column X0 - 1 from the tiles
+                float o[3];
+                pixel(X0 - 1, Y, o);
+#pragma unroll
+                for (int e = 0; e < 3; ++e) left[e] = r ? 0.5f * (left[e] + o[e]) : o[e];
+            }
+            if (!active || !store_y) continue;
+            uint8_t* row = p.dst.p[0] + (size_t)Y * p.dst.step[0];
+            if (!wide) {
+                uint8_t* d = row + X0;
+                if (ncols == kCols && (((size_t)d) & 7) == 0)
+                    *(uint2*)d = make_uint2(yc[0] | yc[1] << 8 | yc[2] << 16 | yc[3] << 24, yc[4] | yc[5] << 8 | yc[6] << 16 | yc[7] << 24);
+                else for (int q = 0; q < ncols; ++q) d[q] = (uint8_t)yc[q];
+            } else {
+                uint16_t* d = (uint16_t*)row + X0;
+                if (ncols == kCols && (((size_t)d) & 15) == 0)
+                    *(uint4*)d = make_uint4(yc[0] | yc[1] << 16, yc[2] | yc[3] << 16, yc[4] | yc[5] << 16, yc[6] | yc[7] << 16);
+                else for (int q = 0; q < ncols; ++q) d[q] = (uint16_t)yc[q];
+            }
+        }
+        // column X0 - 1: the left lane's last column (every lane takes part in the move; lane 0 keeps its own)
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            const float from_left = __shfl_up(v[kCols - 1][e], 1);
+            if (threadIdx.x != 0) left[e] = from_left;
+            if (X0 == 0) left[e] = v[0][e];                          // column -1 clamps to column 0
+        }
+        if (!active) continue;
+        const int nsites = min(kYuvSites, cw - j0);
+        unsigned uc[kYuvSites], vc[kYuvSites];
+#pragma unroll
+        for (int s = 0; s < kYuvSites; ++s) {
+            const int qc = 2 * s, qr = min(2 * s + 1, ncols - 1);   // column 2j + 1 clamped to the frame (odd W)
+            float f[3];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) f[e] = 0.25f * (s ? v[qc - 1][e] : left[e]) + 0.5f * v[qc][e] + 0.25f * v[qr][e];
+            const float Y = k.kr * f[0] + k.kg * f[1] + k.kb * f[2];
+            uc[s] = yuv_code(k.c_off, k.c_scale, (f[2] - Y) * k.cb_div, k.maxcode);
+            vc[s] = yuv_code(k.c_off, k.c_scale, (f[0] - Y) * k.cr_div, k.maxcode);
+        }
+        for (int pl = 1; pl < 3; ++pl) {
+            const unsigned* cc = pl == 1 ? uc : vc;
+            uint8_t* row = p.dst.p[pl] + (size_t)ci * p.dst.step[pl];
+            if (!wide) {
+                uint8_t* d = row + j0;
+                if (nsites == kYuvSites && (((size_t)d) & 3) == 0) *(unsigned*)d = cc[0] | cc[1] << 8 | cc[2] << 16 | cc[3] << 24;
+                else for (int s = 0; s < nsites; ++s) d[s] = (uint8_t)cc[s];
+            } else {
+                uint16_t* d = (uint16_t*)row + j0;
+                if (nsites == kYuvSites && (((size_t)d) & 7) == 0) *(uint2*)d = make_uint2(cc[0] | cc[1] << 16, cc[2] | cc[3] << 16);
+                else for (int s = 0; s < nsites; ++s) d[s] = (uint16_t)cc[s];
+            }
+        }
+    }
+}
+
 __global__ void se_kernel(const SeParams p) {
     // one block per batch item; tiny (C <= 256)
     extern __shared__ float sm[];
@@ -370,6 +512,21 @@ hipError_t launch_compose_canvas(const ComposeParams& p, float* canvas, hipStrea
     const dim3 grid((unsigned)((w + 255) / 256), (unsigned)(h < 65535 ? h : 65535));
     if (p.fp32) hipLaunchKernelGGL(compose_canvas_kernel<float4v>, grid, dim3(256), 0, s, p, canvas);
     else hipLaunchKernelGGL(compose_canvas_kernel<half4>, grid, dim3(256), 0, s, p, canvas);
+    return hipGetLastError();
+}
+hipError_t launch_gather_yuv(const GatherYuvParams& p, hipStream_t s) {
+    const dim3 grid(grid_for((long)p.B * p.T * p.T));
+    if (p.fp32) hipLaunchKernelGGL(gather_yuv_kernel<float4v>, grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL(gather_yuv_kernel<half4>, grid, dim3(256), 0, s, p);
+    return hipGetLastError();
+}
+hipError_t launch_compose_yuv(const ComposeYuvParams& p, hipStream_t s) {
+    const int cw = (p.c.outW + 1) / 2, ch = (p.c.outH + 1) / 2;
+    if (cw <= 0 || ch <= 0) return hipSuccess;
+    const int runs = (cw + kYuvSites - 1) / kYuvSites;
+    const dim3 grid((unsigned)((runs + kYuvThreads - 1) / kYuvThreads), (unsigned)(ch < 65535 ? ch : 65535));
+    if (p.c.fp32) hipLaunchKernelGGL(compose_yuv_kernel<float4v>, grid, dim3(kYuvThreads), 0, s, p);
+    else hipLaunchKernelGGL(compose_yuv_kernel<half4>, grid, dim3(kYuvThreads), 0, s, p);
     return hipGetLastError();
 }
 hipError_t launch_se(const SeParams& p, hipStream_t s) {

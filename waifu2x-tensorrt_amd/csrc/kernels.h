@@ -241,6 +241,55 @@ struct ResampleParams {
 constexpr int kResampleRows = 16, kResampleCols = 64;
 int resample_rows_max(const int* fy, int outH, int inH, int ky);   // host: the largest input row span of an output row tile
 hipError_t launch_resample(const ResampleParams& p, hipStream_t s);
+// YUV 4:2:0 frames (Img2Img::renderYuv): three planes - Y of rows x cols, U and V of ceil(rows/2) x ceil(cols/2) - with 8-bit (uint8) or 10-bit
+// (uint16, low 10 bits) samples; steps in bytes.  Chroma siting MPEG-2 "left": chroma (i, j) sits at luma (x = 2j, y = 2i + 1/2).
+struct YuvPlanes {
+    uint8_t* p[3] = {nullptr, nullptr, nullptr}; size_t step[3] = {0, 0, 0};
+    int rows = 0, cols = 0, bits = 8;
+};
+// The code <-> normalised value maps of one (matrix, range, bits) (yuv_coefs): Y' = (Y - y_off) * y_mul, C' = (C - c_off) * c_mul on input,
+// Y = y_off + Y' / y_mul, C = c_off + C' / c_mul on output; kr, kb, kg the matrix
+struct YuvCoefs {
+    float y_off = 0.f, y_mul = 0.f, c_off = 0.f, c_mul = 0.f;   // input: code -> normalised
+    float y_scale = 0.f, c_scale = 0.f;                         // output: normalised -> code (before y_off / c_off are added)
+    float kr = 0.f, kg = 0.f, kb = 0.f;
+    float r_cr = 0.f, g_cb = 0.f, g_cr = 0.f, b_cb = 0.f;       // R = Y' + r_cr Cr', G = Y' + g_cb Cb' + g_cr Cr', B = Y' + b_cb Cb'
+    float cb_div = 0.f, cr_div = 0.f;                           // Cb' = (B - Y') * cb_div, Cr' = (R - Y') * cr_div
+    int maxcode = 255;
+};
+// matrix 0 BT.601, 1 BT.709, 2 BT.2020 non-constant; full_range 0 limited ("tv"), 1 full ("pc"); bits 8 or 10 (host, in double, rounded once to float)
+inline YuvCoefs yuv_coefs(int matrix, int full_range, int bits) {
+    const double kr = matrix == 0 ? 0.299 : matrix == 1 ? 0.2126 : 0.2627, kb = matrix == 0 ? 0.114 : matrix == 1 ? 0.0722 : 0.0593, kg = 1.0 - kr - kb;
+    const double q = (double)(1 << (bits - 8)), top = (double)((1 << bits) - 1);
+    const double y_off = full_range ? 0.0 : 16.0 * q, y_scale = full_range ? top : 219.0 * q;
+    const double c_off = full_range ? (double)(1 << (bits - 1)) : 128.0 * q, c_scale = full_range ? top : 224.0 * q;
+    YuvCoefs k;
+    k.y_off = (float)y_off; k.y_mul = (float)(1.0 / y_scale); k.c_off = (float)c_off; k.c_mul = (float)(1.0 / c_scale);
+    k.y_scale = (float)y_scale; k.c_scale = (float)c_scale;
+    k.kr = (float)kr; k.kg = (float)kg; k.kb = (float)kb;
+    k.r_cr = (float)(2.0 * (1.0 - kr)); k.b_cb = (float)(2.0 * (1.0 - kb));
+    k.g_cb = (float)(-2.0 * (1.0 - kb) * kb / kg); k.g_cr = (float)(-2.0 * (1.0 - kr) * kr / kg);
+    k.cb_div = (float)(1.0 / (2.0 * (1.0 - kb))); k.cr_div = (float)(1.0 / (2.0 * (1.0 - kr)));
+    k.maxcode = (1 << bits) - 1;
+    return k;
+}
+// k_prepost.hip gather_yuv_kernel: gather_kernel's tiles (same slots, replicate padding, TTA source index) from a YUV frame - Y and the 2 x 2
+// chroma neighbours of the source pixel, chroma upsampled to the luma grid, the matrix inverted in fp32, R, G, B clamped to [0, 1]
+struct GatherYuvParams {
+    YuvPlanes src; YuvCoefs k;
+    void* out = nullptr; int fp32 = 0;
+    const TileSlot* slots = nullptr;
+    int B = 0, T = 0;
+};
+hipError_t launch_gather_yuv(const GatherYuvParams& p, hipStream_t s);
+// k_prepost.hip compose_yuv_kernel: compose_pixel_sums over the whole canvas (p.c: p.c.dst / deep / x0..y1 unused), R, G, B clamped to [0, 1],
+// written as YUV 4:2:0 planes of p.c.outH x p.c.outW: Y per pixel, Cb / Cr of the RGB filtered (1/4, 1/2, 1/4) x (1/2, 1/2) onto each chroma site
+struct ComposeYuvParams {
+    ComposeParams c;
+    YuvPlanes dst; YuvCoefs k;
+};
+constexpr int kYuvSites = 4, kYuvThreads = 64;   // chroma sites (8 luma columns, 2 rows) per thread, threads per workgroup (one wave)
+hipError_t launch_compose_yuv(const ComposeYuvParams& p, hipStream_t s);
 // debug/test helpers used by w2x_infer (mirrors blobFromImages / imagesFromBlob, img2img_infer.cpp:5-39)
 hipError_t launch_blob_to_nhwc(const float* nchw, void* out_nhwc4, int B, int T, bool fp32, hipStream_t s);
 hipError_t launch_nhwc_to_blob(const void* in_nhwc4, float* nchw, int B, int T, bool fp32, hipStream_t s);

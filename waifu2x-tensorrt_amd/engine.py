@@ -27,6 +27,31 @@ class Precision(enum.IntEnum):      # config.h:7-10
 RESIZE_FILTERS = {"bicubic": 0, "bilinear": 1}   # W2X_RESIZE_BICUBIC / W2X_RESIZE_BILINEAR (include/w2x/c_api.h)
 
 
+YUV_MATRICES = {"bt601": 0, "bt709": 1, "bt2020": 2}   # W2X_YUV_BT601 / _BT709 / _BT2020 (include/w2x/c_api.h)
+
+
+def _matrix_id(name) -> int:
+    if name not in YUV_MATRICES:
+        raise ValueError(f"matrix must be one of {sorted(YUV_MATRICES)}, got {name!r}")
+    return YUV_MATRICES[name]
+
+
+def yuv_plane_shapes(rows: int, cols: int):
+    """[(rows, cols)] of the Y, U and V planes of a 4:2:0 frame"""
+    return [(rows, cols), ((rows + 1) // 2, (cols + 1) // 2), ((rows + 1) // 2, (cols + 1) // 2)]
+
+
+def _yuv_bits(planes) -> int:
+    """8 for uint8 planes, 10 for uint16 ones; checks the 4:2:0 shapes and packed samples"""
+    y = planes[0]
+    if y.ndim != 2 or y.dtype not in (np.uint8, np.uint16):
+        raise ValueError("YUV planes must be 2-D uint8 (8-bit) or uint16 (10-bit) arrays")
+    for p, shape in zip(planes, yuv_plane_shapes(*y.shape)):
+        if p.dtype != y.dtype or p.shape != shape or p.strides[1] != p.itemsize or p.strides[0] <= 0:
+            raise ValueError(f"YUV 4:2:0 planes of one sample type with packed rows expected: {[q.shape for q in planes]} for {y.shape}")
+    return 8 if y.dtype == np.uint8 else 10
+
+
 def _filter_id(name) -> int:
     if name not in RESIZE_FILTERS:
         raise ValueError(f"filter must be one of {sorted(RESIZE_FILTERS)}, got {name!r}")
@@ -118,6 +143,10 @@ def lib():
     L.w2x_render16_resized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, C.c_int, C.c_size_t, C.c_int]; L.w2x_render16_resized.restype = C.c_int
     L.w2x_render_sequence_resized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int]; L.w2x_render_sequence_resized.restype = C.c_int
     L.w2x_resize_weights.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]; L.w2x_resize_weights.restype = C.c_int
+    L.w2x_render_yuv.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]; L.w2x_render_yuv.restype = C.c_int
+    L.w2x_render_sequence_yuv.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.w2x_render_sequence_yuv.restype = C.c_int
+    L.w2x_yuv_plane_sizes.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp]; L.w2x_yuv_plane_sizes.restype = C.c_int
     L.w2x_render_strip.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]; L.w2x_render_strip.restype = C.c_int
     L.w2x_render_sequence.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int]; L.w2x_render_sequence.restype = C.c_int
     L.w2x_alloc_host.argtypes = [vp, C.c_size_t]; L.w2x_alloc_host.restype = vp
@@ -160,6 +189,7 @@ EXPORTED_SYMBOLS = [
     "w2x_create", "w2x_destroy", "w2x_set_message_callback", "w2x_set_progress_callback", "w2x_build", "w2x_load",
     "w2x_render", "w2x_render16", "w2x_infer", "w2x_output_tile_size", "w2x_plan_flops", "w2x_pass_tiles", "w2x_last_render_ms", "w2x_bench_resident", "w2x_resident_output", "w2x_profile_frame", "w2x_op_times",
     "w2x_render_resized", "w2x_render16_resized", "w2x_render_sequence_resized", "w2x_resize_weights",
+    "w2x_render_yuv", "w2x_render_sequence_yuv", "w2x_yuv_plane_sizes",
     "w2x_render_strip", "w2x_strip_plan", "w2x_render_sharded", "w2x_shard_plan", "w2x_shard_compute", "w2x_shard_slab", "w2x_shard_finish", "w2x_ipc_export", "w2x_ipc_open", "w2x_ipc_close", "w2x_render_sequence", "w2x_alloc_host", "w2x_free_host", "w2x_pin_host", "w2x_unpin_host", "w2x_calculate_tiles", "w2x_tile_weights", "w2x_describe_plan", "w2x_describe_plan_precision", "w2x_write_engine_file", "w2x_validate_engine_file", "w2x_device_pci_bus_id", "w2x_sha256_hex", "w2x_version", "w2x_debug_set"]
 
 
@@ -339,6 +369,85 @@ class Img2Img:
         arr = (C.c_void_p * parts)(*[C.c_void_p(int(p) or None) for p in slabs])
         dev = (C.c_int * parts)(*[int(d) for d in devices]) if devices is not None else None
         return bool(self._L.w2x_shard_finish(self._h, dst.ctypes.data, dst.shape[0], dst.shape[1], dst.strides[0], int(part), int(parts), arr, dev))
+
+    def _yuv_out(self, rows, cols, bits):
+        s = getattr(self, "_scaling", 0)
+        dt = np.uint8 if bits == 8 else np.uint16
+        return tuple(np.empty(shape, dt) for shape in yuv_plane_shapes(rows * s, cols * s))
+
+    def render_yuv(self, y: np.ndarray, u: np.ndarray, v: np.ndarray, *, matrix: str = "bt709", full_range: bool = False, out_bits: int | None = None,
+                   out=None):
+        """render() on a YUV 4:2:0 frame (w2x_render_yuv): uint8 planes are 8-bit, uint16 planes 10-bit; out_bits (8 or 10, default the input's)
+        sets the output depth.  Returns (Y, U, V) at the scaled size, or raises.  out: pre-allocated planes (then a bool is returned)."""
+        bits = _yuv_bits((y, u, v))
+        ob = bits if out_bits is None else int(out_bits)
+        ret_array = out is None
+        dst = self._yuv_out(*y.shape, ob if ob in (8, 10) else 8) if out is None else tuple(out)
+        if out is not None:
+            # the C ABI sees pointers and steps only: the plane shapes and the sample type of out_bits are checked here
+            s = getattr(self, "_scaling", 0)
+            dt = np.uint16 if ob == 10 else np.uint8
+            if len(dst) != 3 or any(not isinstance(p, np.ndarray) or p.dtype != dt or p.ndim != 2 or p.shape != shape or p.strides[1] != p.itemsize
+                                    for p, shape in zip(dst, yuv_plane_shapes(y.shape[0] * s, y.shape[1] * s))):
+                raise ValueError("out must be three 2-D planes of the scaled 4:2:0 shapes, uint8 for 8-bit and uint16 for 10-bit output, with packed rows")
+        dp = (C.c_void_p * 3)(*[p.ctypes.data for p in dst])
+        ok = bool(self._L.w2x_render_yuv(self._h, (C.c_void_p * 3)(*[p.ctypes.data for p in (y, u, v)]), (C.c_size_t * 3)(*[p.strides[0] for p in (y, u, v)]),
+                                         y.shape[0], y.shape[1], bits, dp, (C.c_size_t * 3)(*[p.strides[0] for p in dst]), dst[0].shape[0], dst[0].shape[1], ob,
+                                         _matrix_id(matrix), 1 if full_range else 0))
+        if ret_array:
+            if not ok:
+                raise W2xError(self.last_error() or "render_yuv failed")
+            return dst
+        return ok
+
+    def render_sequence_yuv(self, frames, *, matrix: str = "bt709", full_range: bool = False, out_bits: int | None = None, pinned: bool = False):
+        """render_yuv() over equally sized frames [(y, u, v), ...] through the pipeline of render_sequence() (w2x_render_sequence_yuv).
+        pinned=True takes the output planes from alloc_host() (a ring of three frames; copies of the results are returned)."""
+        n = len(frames)
+        if n == 0:
+            return []
+        bits = _yuv_bits(frames[0])
+        ob = bits if out_bits is None else int(out_bits)
+        rows, cols = frames[0][0].shape
+        steps = [p.strides[0] for p in frames[0]]
+        for f in frames:
+            if _yuv_bits(f) != bits or f[0].shape != (rows, cols) or [p.strides[0] for p in f] != steps:
+                raise ValueError("frames must be YUV planes of one size, depth and layout")
+        s = getattr(self, "_scaling", 0)
+        shapes = yuv_plane_shapes(rows * s, cols * s)
+        dt = np.uint8 if ob != 10 else np.uint16
+        own = []
+        if pinned:
+            for _ in range(min(n, 3)):
+                sizes = [r * c * np.dtype(dt).itemsize for r, c in shapes]
+                buf = self.alloc_host((sum(sizes),))
+                planes, o = [], 0
+                for (r, c), nb in zip(shapes, sizes):
+                    planes.append(buf[o:o + nb].view(dt).reshape(r, c)); o += nb
+                own.append((buf, tuple(planes)))
+        outs = [own[k % len(own)][1] for k in range(n)] if own else [self._yuv_out(rows, cols, 8 if ob != 10 else 10) for _ in range(n)]
+        dsteps = (C.c_size_t * 3)(*[p.strides[0] for p in outs[0]])
+
+        def run(fs, os_):
+            m = len(fs)
+            sp = (C.c_void_p * (3 * m))(*[p.ctypes.data for f in fs for p in f])
+            dp = (C.c_void_p * (3 * m))(*[p.ctypes.data for o in os_ for p in o])
+            if not self._L.w2x_render_sequence_yuv(self._h, sp, (C.c_size_t * 3)(*steps), rows, cols, bits, dp, dsteps, rows * s, cols * s, ob, m,
+                                                   _matrix_id(matrix), 1 if full_range else 0):
+                raise W2xError(self.last_error() or "render_sequence_yuv failed")
+        if own:
+            res = []
+            try:
+                for k0 in range(0, n, len(own)):
+                    m = min(len(own), n - k0)
+                    run(frames[k0:k0 + m], outs[k0:k0 + m])
+                    res += [tuple(p.copy() for p in o) for o in outs[k0:k0 + m]]
+            finally:
+                for buf, _ in own:
+                    self.free_host(buf)
+            return res
+        run(frames, outs)
+        return outs
 
     def alloc_host(self, shape) -> np.ndarray:
         """A uint8 array over page-locked memory owned by the engine (w2x_alloc_host): frame buffers whose PCIe copies
@@ -553,6 +662,14 @@ def resize_weights(in_size: int, out_size: int, filter: str = "bicubic"):
     if L.w2x_resize_weights(int(in_size), int(out_size), fid, first.ctypes.data, w.ctypes.data, w.size) != taps:
         raise W2xError("w2x_resize_weights failed")
     return first, w
+
+
+def yuv_plane_sizes(rows: int, cols: int, bits: int):
+    """(plane_rows[3], plane_cols[3], plane_bytes[3]) of a packed YUV 4:2:0 frame (w2x_yuv_plane_sizes); raises for invalid arguments"""
+    pr, pc, pb = (C.c_int * 3)(), (C.c_int * 3)(), (C.c_size_t * 3)()
+    if not lib().w2x_yuv_plane_sizes(int(rows), int(cols), int(bits), pr, pc, pb):
+        raise W2xError(f"invalid YUV frame {rows}x{cols} at {bits} bits")
+    return list(pr), list(pc), list(pb)
 
 
 def describe_plan(onnx_path, batch, tile, precision=None) -> str:
