@@ -9,12 +9,18 @@ A step = one pass of the hot path (gather -> network on every tile batch -> blen
 1920x1080 frame that is already resident in HBM; frames are independent, so ranks shard frames with no data-path
 collective (weak scaling: every rank renders K frames).  Rank 0 prints ONE JSON line.
 
-`value` is the resident figure (inputs in HBM when the timed region starts: the measurement contract of this build).  The same K
-frames are then rendered by every rank through the reference's whole render() contract - host frame in, host frame out
-(img2img_render.cpp:226,344; caller loop main.cpp:263-269) - as a renderSequence over page-locked buffers with the copies on
-side streams; that PCIe-inclusive figure is the top-level `host_to_host` object of the same line (max over ranks, same barriers,
-per-rank spread), never `value`.  At N > 1 it is the number that can fail to scale (N x 100 MB per frame into host memory);
-the resident one touches no shared resource.
+`value` is the resident figure (inputs in HBM when the timed region starts: the measurement contract of this build).  A plain run does
+only what that figure needs: it exports the synthetic-weight graph, builds and loads the engine, puts the frame on the device through render()
+(which captures the frame's hipGraphs), warms up, times the K steps, writes --dump-outputs and prints the line.  Everything else is measured with --full:
+  - the same K frames through the reference's whole render() contract - host frame in, host frame out (img2img_render.cpp:226,344;
+    caller loop main.cpp:263-269) - as a renderSequence over page-locked buffers with the copies on side streams, checked against
+    render()'s bytes; that PCIe-inclusive figure is the top-level `host_to_host` object (max over ranks, same barriers, per-rank
+    spread), never `value`.  At N > 1 it is the number that can fail to scale (N x 100 MB per frame into host memory); the resident
+    one touches no shared resource;
+  - `roofline`: HIP-event time per plan op and per kernel family of one frame (the engine's profiling pass), the dominant kernel priced
+    against the MFMA and HBM peaks (--op-times prints the per-op times);
+  - `cpu_baseline`: the CPU oracle timed on a sample of the same workload (config 3, or --cpu-baseline; tens of seconds).
+Every run exports its model and builds its engine file in a fresh directory, removed at exit: no run reads what an earlier one wrote.
 
 Every line says where it ran: `placement` holds, per rank, the PCI bus id of the GPU the rank's HIP runtime rendered on, the
 number of DISTINCT GPUs behind the ranks and W2X_DEVICE_MAP.  `n_gpus` is that distinct count: ranks sharing a card (a
@@ -30,9 +36,12 @@ and no launcher environment the script starts the N ranks itself (child processe
 from __future__ import annotations
 
 import argparse
+import atexit
 import json
 import os
+import shutil
 import sys
+import tempfile
 import time
 
 import numpy as np
@@ -87,6 +96,16 @@ def kernel_source_sha(symbol: str):
     return h.hexdigest()[:12]
 
 
+def fresh_work(root, tag: str) -> str:
+    """A new directory for this run's model and engine files - under --work, else in the system's temporary directory - removed when the
+    process exits."""
+    if root:
+        os.makedirs(root, exist_ok=True)
+    d = tempfile.mkdtemp(prefix=f"w2x_bench_{tag}_", dir=root or None)
+    atexit.register(shutil.rmtree, d, ignore_errors=True)
+    return d
+
+
 def synthetic_frame(seed: int) -> np.ndarray:
     """u8 BGR 1080p frame: seeded low-frequency sinusoids + +-4 LSB noise."""
     rng = np.random.default_rng(seed)
@@ -128,8 +147,7 @@ def cpu_baseline(work: str, tile_out: int) -> dict:
     import synth_models as sm
     from oracle import onnx_exec, pipeline
     path = sm.model_path(os.path.join(work, "cpu_b1"), MODEL, SCALE, NOISE)
-    if not os.path.exists(path):
-        sm.export_onnx(sm.make_model(MODEL, SCALE, seed=1234 + NOISE), path, 1, TILE, dynamic=True)
+    sm.export_onnx(sm.make_model(MODEL, SCALE, seed=1234 + NOISE), path, 1, TILE, dynamic=True)
     ex = onnx_exec.Executor(path)
     frame = synthetic_frame(0)
     n, ins, outs = pipeline.calculate_tiles(FRAME_W, FRAME_H, FRAME_W * SCALE, FRAME_H * SCALE, (TILE, TILE), (tile_out, tile_out), SCALE, (BLEND, BLEND))
@@ -241,10 +259,9 @@ def bench_shards_one_process(a) -> int:
     if have < a.gpus and not os.environ.get("W2X_DEVICE_MAP"):
         raise SystemExit(f"--gpus {a.gpus} but this node shows {have} GPU(s); refusing to report n_gpus != requested")
     pkg = g.package()
-    work = os.path.join(a.work, "shards")
+    work = fresh_work(a.work, "shards")
     path = sm.model_path(work, MODEL, SCALE, NOISE)
-    if not os.path.exists(path):
-        sm.export_onnx(sm.make_model(MODEL, SCALE, seed=1234 + NOISE), path, BATCH, TILE, dynamic=True)
+    sm.export_onnx(sm.make_model(MODEL, SCALE, seed=1234 + NOISE), path, BATCH, TILE, dynamic=True)
     engs = []
     for d in range(a.gpus):
         e = pkg.Img2Img()
@@ -404,6 +421,89 @@ def spawn_ranks(a) -> int:
     return rc
 
 
+def roofline(desc, op_ms, folded, folded_fwd, n_tiles: float, live: float) -> dict:
+    """--full: the `roofline` object from one frame's HIP-event time per plan op (w2x_op_times) and the plan's algorithmic FLOPs and bytes."""
+    import re
+    # dominant kernel of the frame: plan ops grouped by the kernel that serves them, by summed HIP-event time
+    # (measured on the compute stream by w2x_profile_frame / w2x_op_times)
+    symbols = {("swinattn", 96): "swin_attn96_kernel", ("swinattn", 192): "swin_attn192u_kernel",
+               ("mlp", 96): "mlp96q_kernel", ("mlp", 192): "mlp2_kernel<192,2>"}     # (names as tools/pmc_traffic.py keys them)
+    groups = {}
+    for line, t in zip(desc, op_ms):
+        m = re.match(r"\s*\d+ (\w+) (.*?)flops=(\d+)", line)
+        if not m: continue
+        kind, rest, flops = m.group(1), m.group(2), int(m.group(3)) * live
+        cm = re.search(r"\bC=(\d+)", rest)
+        key = (kind, int(cm.group(1))) if kind in ("swinattn", "mlp") and cm else (kind, 0)
+        am = re.search(r"\ba=(\w+) M=(\d+) K=(\d+) N=(\d+)", rest)
+        nbytes = 0.0
+        if kind == "gemm" and am and CONFIG_NAME != "configs[2]":
+            # other configs (cunet's convolutions): one group per operand shape, so that the dominant KERNEL is named - 3x3 convolutions over
+            # 32-channel chunks run on conv3_kernel; algorithmic bytes = read the input map once + write the output map once
+            mode, M, K, N = am.group(1), int(am.group(2)), int(am.group(3)), int(am.group(4))
+            taps = 9 if "3x3" in mode else 4 if "2x2" in mode else 1
+            key = (kind, f"{mode} {K // taps}->{N}")
+            nbytes = float(M) * live * (K // taps + N) * 2
+        if key[0] == "swinattn":    # read x + write y: tiles * windows * 36 tokens * C * 2 B, each way
+            nbytes = 2.0 * n_tiles * int(re.search(r"nwin=(\d+)", rest).group(1)) * 36 * key[1] * 2
+        elif key[0] == "mlp":
+            nbytes = 2.0 * int(re.search(r"M=(\d+)", rest).group(1)) * live * key[1] * 2
+        g = groups.setdefault(key, [0.0, 0, 0.0, 0.0]); g[0] += t; g[1] += 1; g[2] += flops; g[3] += nbytes
+    def kernel_roof(key):                    # the roofline figures of one kernel group
+        k_ms, k_n, k_flop, k_bytes = groups[key]
+        tflops = k_flop / (k_ms * 1e-3) / 1e12
+        gbs = k_bytes / (k_ms * 1e-3) / 1e9
+        t_mfma, t_hbm = k_flop / (MFMA_F16_PEAK_TFLOPS * 1e12), k_bytes / (HBM_PEAK_GBS * 1e9)
+        hbm_bound = t_hbm > t_mfma           # the roofline that binds this kernel = the larger of the two floor times
+        return {"bound": "hbm" if hbm_bound else "mfma",
+                "achieved": round(gbs if hbm_bound else tflops, 2), "peak": HBM_PEAK_GBS if hbm_bound else MFMA_F16_PEAK_TFLOPS,
+                "unit": "GB/s" if hbm_bound else "TFLOP/s",
+                "frac": round((gbs / HBM_PEAK_GBS) if hbm_bound else (tflops / MFMA_F16_PEAK_TFLOPS), 5), "traffic": None,
+                "kernel": symbols.get(key, ("conv3_kernel" if isinstance(key[1], str) and key[1].startswith("conv3x3s1") and int(key[1].split()[1].split("->")[0]) % 32 == 0 else
+                                            "gemm_kernel / pixgemm kernels") if key[0] == "gemm" else key[0]),
+                "plan_ops": key[1] if isinstance(key[1], str) else None,
+                "launches_per_frame": k_n, "avg_launch_us": round(k_ms * 1e3 / k_n, 2),
+                "algorithmic_gflop_per_launch": round(k_flop / k_n / 1e9, 3),
+                "algorithmic_mbyte_per_launch": round(k_bytes / k_n / 1e6, 3),
+                "other_roof": {"unit": "TFLOP/s" if hbm_bound else "GB/s", "achieved": round(tflops if hbm_bound else gbs, 2),
+                               "frac": round((tflops / MFMA_F16_PEAK_TFLOPS) if hbm_bound else (gbs / HBM_PEAK_GBS), 5)}}
+    ranked = sorted(groups, key=lambda k: -groups[k][0])
+    dom = ranked[0]
+    roof = kernel_roof(dom)
+    roof["launch_note"] = ("HIP events around each launch with every pass in one piece on one stream (the engine's profiling pass, = W2X_GROUPS=1: a launch covers all live tiles); "
+                           "the timed region of `value` runs each pass as two tile groups on two streams")
+    roof["kernels_ms_per_frame"] = {symbols.get(k, k[0] if not isinstance(k[1], str) else k[0] + " " + k[1]): round(v[0], 3) for k, v in sorted(groups.items(), key=lambda kv: -kv[1][0])}
+    # config 3's two attention kernels take 2.0 ms per frame each and swap places from box to box: a kernel within a tenth of the dominant one is shown beside it
+    if len(ranked) > 1 and groups[ranked[1]][0] >= 0.9 * groups[dom][0]:
+        roof["runner_up"] = kernel_roof(ranked[1])
+    notes = []
+    if folded:
+        notes.append("mlp96q_kernel's figure includes the image head (Linear 96 -> 64, Clip, DepthToSpace), which the engine folds into the last C = 96 MLP launch; that plan op has no launch and reports 0 ms")
+    if folded_fwd:
+        names = [re.sub(r"^.*\[(.*)\]\s*$", r"\1", desc[i]) for i in folded_fwd]
+        notes.append("computed inside the NEXT op's launch and counted with it (the plan op has no launch and reports 0 ms; the launch's roofline figures price its own op only): " + ", ".join(names) +
+                     " - a stem convolution in the halo stage of the convolution behind it (conv48_kernel<true> / conv3_kernel<false, 1>), cunet's transposed convolutions in the halo stage of "
+                     "the 64 -> 64 convolutions behind them (conv3_kernel<false, 2>)")
+    if notes:
+        roof["kernels_note"] = "; ".join(notes)
+    tr = os.path.join(ROOT, "profiles", "pmc_traffic.json")      # HBM bytes per launch from separate rocprofv3 --pmc passes (tools/profile_round.sh)
+    if os.path.exists(tr) and CONFIG_NAME == "configs[2]":
+        try:
+            table = json.load(open(tr))
+            for r in [roof] + ([roof["runner_up"]] if "runner_up" in roof else []):
+                t = table.get(r["kernel"])
+                now = kernel_source_sha(r["kernel"])
+                if t and t.get("source_sha") and t["source_sha"] == now:
+                    r["traffic"] = t["bytes_per_launch"]; r["traffic_source"] = t["source"]; r["traffic_kernel_source_sha"] = now
+                    for k_ in ("issue", "mfma_busy", "coexec"):      # SQ counters of the same round's passes (tools/pmc_traffic.py), same source-hash rule
+                        if k_ in t: r[k_] = t[k_]
+                elif t:          # the counters were taken on another revision of this kernel: not quoted
+                    r["traffic_note"] = f"profiles/pmc_traffic.json holds {t['bytes_per_launch']} bytes per launch measured on kernel source {t.get('source_sha', 'unrecorded')}; the kernel now built is {now}: not quoted"
+        except Exception:
+            pass
+    return roof
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -417,12 +517,17 @@ def main():
                          "(strong scaling); shards1p: the same with one process driving N engines")
     ap.add_argument("--config", type=int, choices=sorted(CONFIGS), default=3,
                     help="BASELINE.json configuration (1-based; 3 = configs[2], the one the metric is quoted on); the others emit the same JSON record for their workload; 0 = a test-sized frame")
-    ap.add_argument("--cpu-baseline", action="store_true", help="time the CPU oracle for --config other than 3 as well (minutes for the 400 / 640 tiles)")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline figure does not need (--mode frames / strips): the host-to-host renderSequence figure and its byte check "
+                         "against render(), the per-op / per-kernel profile and roofline, the CPU baseline")
+    ap.add_argument("--cpu-baseline", action="store_true", help="with --full: time the CPU oracle for --config other than 3 as well (minutes for the 400 / 640 tiles)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: leave the CPU baseline out")
     ap.add_argument("--frame", choices=["synthetic", "flat", "noise"], default="synthetic",
                     help="diagnostic: frame content (flat = one grey level, noise = uniform random bytes); `value` is quoted on synthetic")
-    ap.add_argument("--op-times", action="store_true", help="print HIP-event time per plan op (one frame) to stderr")
-    ap.add_argument("--work", default=os.environ.get("W2X_BENCH_WORK", "/tmp/w2x_bench"))
+    ap.add_argument("--op-times", action="store_true", help="with --full: print HIP-event time per plan op (one frame) to stderr")
+    ap.add_argument("--work", default=os.environ.get("W2X_BENCH_WORK"),
+                    help="each run exports its model and builds its engine file in a fresh directory under this one (default: the system's "
+                         "temporary directory), removed at exit")
     ap.add_argument("--host-rehearsal", action="store_true",
                     help="the rank protocol only (spawn or launcher environment, gloo rendezvous, barriers, max-reduction, placement records, the one JSON line) with every engine "
                          "call replaced by a sleep: runs without a GPU, prints value = null and n_gpus = 0.  What tests/test_shard_gloo.py runs at 2 and 8 ranks")
@@ -432,6 +537,8 @@ def main():
     a = ap.parse_args()
     if a.dump_outputs and (a.mode != "frames" or a.host_rehearsal):
         ap.error("--dump-outputs needs --mode frames and a GPU run")
+    if (a.op_times or a.cpu_baseline) and not a.full:
+        ap.error("--op-times and --cpu-baseline are parts of a --full run")
     select_config(a.config)
 
     if a.mode == "shards1p":
@@ -481,10 +588,9 @@ def main():
     if a.host_rehearsal:
         raise SystemExit(host_rehearsal(a, dist, rank, world, json_out, placement))
 
-    work = os.path.join(a.work, f"rank{rank}")
+    work = fresh_work(a.work, f"rank{rank}")
     path = sm.model_path(work, MODEL, SCALE, NOISE)
-    if not os.path.exists(path):
-        sm.export_onnx(sm.make_model(MODEL, SCALE, seed=1234 + NOISE), path, BATCH, TILE, dynamic=True)
+    sm.export_onnx(sm.make_model(MODEL, SCALE, seed=1234 + NOISE), path, BATCH, TILE, dynamic=True)
     eng = pkg.Img2Img()
     bc = pkg.BuildConfig.fixed(BATCH, TILE, device=local_rank)
     if not eng.build(path, bc):
@@ -541,10 +647,10 @@ def main():
         if not eng.resident_output(last_out):
             raise SystemExit("reading the resident output failed: " + eng.last_error())
 
-    # ---- the same K frames through the whole render() contract (host buffer in, host buffer out), copies overlapped on side
+    # ---- --full: the same K frames through the whole render() contract (host buffer in, host buffer out), copies overlapped on side
     # streams (renderSequence over page-locked buffers, a ring of 3 output frames); every rank, same barriers, max over ranks
     full_wall_max, full_wall, full_regions = None, None, []
-    if not strips:
+    if a.full and not strips:
         try:
             pf = eng.alloc_host(frame.shape); pf[...] = frame                    # page-locked frame buffers owned by the engine
             ring = [eng.alloc_host(out.shape) for _ in range(3)]
@@ -568,22 +674,23 @@ def main():
                 raise
             print(f"[w2x] full-path measurement skipped: {e}", file=sys.stderr)
         render_once()                        # restore the single-frame state profile_frame() works on
-    full_walls = shard.gather_objects(full_wall, dist)
 
-    prof = eng.profile_frame()
-    desc = pkg.describe_plan(path, eng.pass_tiles, TILE).splitlines()[2:]
-    op_ms = eng.op_times()
-    # an op the engine folded into a neighbour's launch has no launch of its own and reports 0 ms: the image head riding on the last C = 96 MLP
-    # (engine.cpp fuse_head; its time is inside the previous op's) and the stems / transposed convolutions computed by the convolution behind them (fuse_stem, fuse_up; inside the next op's)
-    folded = [i for i, (line, t) in enumerate(zip(desc, op_ms)) if t == 0.0 and i > 0 and " gemm " in f" {line} " and " mlp " in f" {desc[i - 1]} "]
-    folded_fwd = [i for i, (line, t) in enumerate(zip(desc, op_ms)) if t == 0.0 and i + 1 < len(desc) and " gemm " in f" {line} " and " gemm " in f" {desc[i + 1]} " and i not in folded]
-    if a.op_times and rank == 0:
-        for i, (line, t) in enumerate(zip(desc, op_ms)):
-            note = "  (no launch of its own: folded into the previous op's launch, whose time includes it)" if i in folded else \
-                   "  (no launch of its own: computed inside the next op's launch, whose time includes it)" if i in folded_fwd else ""
-            print(f"{t:8.3f} ms  {line[:150]}{note}", file=sys.stderr)
+    # ---- --full: the engine's profiling pass over one frame - HIP-event time per kernel family and per plan op
+    if a.full:
+        full_walls = shard.gather_objects(full_wall, dist)
+        prof = eng.profile_frame()
+        desc = pkg.describe_plan(path, eng.pass_tiles, TILE).splitlines()[2:]
+        op_ms = eng.op_times()
+        # an op the engine folded into a neighbour's launch has no launch of its own and reports 0 ms: the image head riding on the last C = 96 MLP
+        # (engine.cpp fuse_head; its time is inside the previous op's) and the stems / transposed convolutions computed by the convolution behind them (fuse_stem, fuse_up; inside the next op's)
+        folded = [i for i, (line, t) in enumerate(zip(desc, op_ms)) if t == 0.0 and i > 0 and " gemm " in f" {line} " and " mlp " in f" {desc[i - 1]} "]
+        folded_fwd = [i for i, (line, t) in enumerate(zip(desc, op_ms)) if t == 0.0 and i + 1 < len(desc) and " gemm " in f" {line} " and " gemm " in f" {desc[i + 1]} " and i not in folded]
+        if a.op_times and rank == 0:
+            for i, (line, t) in enumerate(zip(desc, op_ms)):
+                note = "  (no launch of its own: folded into the previous op's launch, whose time includes it)" if i in folded else \
+                       "  (no launch of its own: computed inside the next op's launch, whose time includes it)" if i in folded_fwd else ""
+                print(f"{t:8.3f} ms  {line[:150]}{note}", file=sys.stderr)
     if rank == 0:
-        import re
         fps = a.steps * (1 if strips else world) / wall_max       # strips: the N ranks together produce each frame
         n_tiles = pkg.calculate_tiles(FRAME_W, FRAME_H, FRAME_W * SCALE, FRAME_H * SCALE, TILE, eng.output_tile_size, SCALE, (BLEND, BLEND))[0]
         frame_tiles = n_tiles
@@ -591,83 +698,6 @@ def main():
             n_tiles = pkg.strip_plan(FRAME_W, FRAME_H, FRAME_W * SCALE, FRAME_H * SCALE, TILE, eng.output_tile_size, SCALE, (BLEND, BLEND), 0, world)[1]
         n_tiles *= 8 if TTA else 1               # network steps: a tile goes through the network once per augmentation
         live = n_tiles / eng.pass_tiles          # the zero-pad slots of the last batch are not computed (plan FLOPs are per pass of pass_tiles)
-        # dominant kernel of the frame: plan ops grouped by the kernel that serves them, by summed HIP-event time
-        # (measured on the compute stream by w2x_profile_frame / w2x_op_times)
-        symbols = {("swinattn", 96): "swin_attn96_kernel", ("swinattn", 192): "swin_attn192u_kernel",
-                   ("mlp", 96): "mlp96q_kernel", ("mlp", 192): "mlp2_kernel<192,2>"}     # (names as tools/pmc_traffic.py keys them)
-        groups = {}
-        for line, t in zip(desc, op_ms):
-            m = re.match(r"\s*\d+ (\w+) (.*?)flops=(\d+)", line)
-            if not m: continue
-            kind, rest, flops = m.group(1), m.group(2), int(m.group(3)) * live
-            cm = re.search(r"\bC=(\d+)", rest)
-            key = (kind, int(cm.group(1))) if kind in ("swinattn", "mlp") and cm else (kind, 0)
-            am = re.search(r"\ba=(\w+) M=(\d+) K=(\d+) N=(\d+)", rest)
-            nbytes = 0.0
-            if kind == "gemm" and am and CONFIG_NAME != "configs[2]":
-                # other configs (cunet's convolutions): one group per operand shape, so that the dominant KERNEL is named - 3x3 convolutions over
-                # 32-channel chunks run on conv3_kernel; algorithmic bytes = read the input map once + write the output map once
-                mode, M, K, N = am.group(1), int(am.group(2)), int(am.group(3)), int(am.group(4))
-                taps = 9 if "3x3" in mode else 4 if "2x2" in mode else 1
-                key = (kind, f"{mode} {K // taps}->{N}")
-                nbytes = float(M) * live * (K // taps + N) * 2
-            if key[0] == "swinattn":    # read x + write y: tiles * windows * 36 tokens * C * 2 B, each way
-                nbytes = 2.0 * n_tiles * int(re.search(r"nwin=(\d+)", rest).group(1)) * 36 * key[1] * 2
-            elif key[0] == "mlp":
-                nbytes = 2.0 * int(re.search(r"M=(\d+)", rest).group(1)) * live * key[1] * 2
-            g = groups.setdefault(key, [0.0, 0, 0.0, 0.0]); g[0] += t; g[1] += 1; g[2] += flops; g[3] += nbytes
-        def kernel_roof(key):                    # the roofline figures of one kernel group
-            k_ms, k_n, k_flop, k_bytes = groups[key]
-            tflops = k_flop / (k_ms * 1e-3) / 1e12
-            gbs = k_bytes / (k_ms * 1e-3) / 1e9
-            t_mfma, t_hbm = k_flop / (MFMA_F16_PEAK_TFLOPS * 1e12), k_bytes / (HBM_PEAK_GBS * 1e9)
-            hbm_bound = t_hbm > t_mfma           # the roofline that binds this kernel = the larger of the two floor times
-            return {"bound": "hbm" if hbm_bound else "mfma",
-                    "achieved": round(gbs if hbm_bound else tflops, 2), "peak": HBM_PEAK_GBS if hbm_bound else MFMA_F16_PEAK_TFLOPS,
-                    "unit": "GB/s" if hbm_bound else "TFLOP/s",
-                    "frac": round((gbs / HBM_PEAK_GBS) if hbm_bound else (tflops / MFMA_F16_PEAK_TFLOPS), 5), "traffic": None,
-                    "kernel": symbols.get(key, ("conv3_kernel" if isinstance(key[1], str) and key[1].startswith("conv3x3s1") and int(key[1].split()[1].split("->")[0]) % 32 == 0 else
-                                                "gemm_kernel / pixgemm kernels") if key[0] == "gemm" else key[0]),
-                    "plan_ops": key[1] if isinstance(key[1], str) else None,
-                    "launches_per_frame": k_n, "avg_launch_us": round(k_ms * 1e3 / k_n, 2),
-                    "algorithmic_gflop_per_launch": round(k_flop / k_n / 1e9, 3),
-                    "algorithmic_mbyte_per_launch": round(k_bytes / k_n / 1e6, 3),
-                    "other_roof": {"unit": "TFLOP/s" if hbm_bound else "GB/s", "achieved": round(tflops if hbm_bound else gbs, 2),
-                                   "frac": round((tflops / MFMA_F16_PEAK_TFLOPS) if hbm_bound else (gbs / HBM_PEAK_GBS), 5)}}
-        ranked = sorted(groups, key=lambda k: -groups[k][0])
-        dom = ranked[0]
-        roof = kernel_roof(dom)
-        roof["launch_note"] = ("HIP events around each launch with every pass in one piece on one stream (the engine's profiling pass, = W2X_GROUPS=1: a launch covers all live tiles); "
-                               "the timed region of `value` runs each pass as two tile groups on two streams")
-        roof["kernels_ms_per_frame"] = {symbols.get(k, k[0] if not isinstance(k[1], str) else k[0] + " " + k[1]): round(v[0], 3) for k, v in sorted(groups.items(), key=lambda kv: -kv[1][0])}
-        # config 3's two attention kernels take 2.0 ms per frame each and swap places from box to box: a kernel within a tenth of the dominant one is shown beside it
-        if len(ranked) > 1 and groups[ranked[1]][0] >= 0.9 * groups[dom][0]:
-            roof["runner_up"] = kernel_roof(ranked[1])
-        notes = []
-        if folded:
-            notes.append("mlp96q_kernel's figure includes the image head (Linear 96 -> 64, Clip, DepthToSpace), which the engine folds into the last C = 96 MLP launch; that plan op has no launch and reports 0 ms")
-        if folded_fwd:
-            names = [re.sub(r"^.*\[(.*)\]\s*$", r"\1", desc[i]) for i in folded_fwd]
-            notes.append("computed inside the NEXT op's launch and counted with it (the plan op has no launch and reports 0 ms; the launch's roofline figures price its own op only): " + ", ".join(names) +
-                         " - a stem convolution in the halo stage of the convolution behind it (conv48_kernel<true> / conv3_kernel<false, 1>), cunet's transposed convolutions in the halo stage of "
-                         "the 64 -> 64 convolutions behind them (conv3_kernel<false, 2>)")
-        if notes:
-            roof["kernels_note"] = "; ".join(notes)
-        tr = os.path.join(ROOT, "profiles", "pmc_traffic.json")      # HBM bytes per launch from separate rocprofv3 --pmc passes (tools/profile_round.sh)
-        if os.path.exists(tr) and CONFIG_NAME == "configs[2]":
-            try:
-                table = json.load(open(tr))
-                for r in [roof] + ([roof["runner_up"]] if "runner_up" in roof else []):
-                    t = table.get(r["kernel"])
-                    now = kernel_source_sha(r["kernel"])
-                    if t and t.get("source_sha") and t["source_sha"] == now:
-                        r["traffic"] = t["bytes_per_launch"]; r["traffic_source"] = t["source"]; r["traffic_kernel_source_sha"] = now
-                        for k_ in ("issue", "mfma_busy", "coexec"):      # SQ counters of the same round's passes (tools/pmc_traffic.py), same source-hash rule
-                            if k_ in t: r[k_] = t[k_]
-                    elif t:          # the counters were taken on another revision of this kernel: not quoted
-                        r["traffic_note"] = f"profiles/pmc_traffic.json holds {t['bytes_per_launch']} bytes per launch measured on kernel source {t.get('source_sha', 'unrecorded')}; the kernel now built is {now}: not quoted"
-            except Exception:
-                pass
         line = {
             "metric": rehearsal_prefix(placement) + ("upscaled MPix/s, 1080p->4K swin_unet/art fp16" if CONFIG_NAME == "configs[2]" else f"upscaled MPix/s, {FRAME_W}x{FRAME_H} x{SCALE} {MODEL} fp16{' +TTA' if TTA else ''}"),
             "value": round(fps * OUT_MPIX, 2), "unit": "MPix/s", "n_gpus": placement["distinct_gpus"], "n_ranks": world, "steps": a.steps, "warmup": a.warmup,
@@ -682,28 +712,30 @@ def main():
                        "mode": a.mode, "rank0_cpus": len(pinned) or None,
                        "per_rank_resident_ms_per_step": shard.spread([w * 1e3 / a.steps for w in walls]),
                        "render_call_ms_pageable": round(pcie_ms_one, 2),
-                       "full_path_ms_per_frame": None if full_wall_max is None else round(full_wall_max * 1e3 / a.steps, 3),
-                       "full_path_frames_per_s": None if full_wall_max is None else round(a.steps * world / full_wall_max, 3),
-                       "full_path_mpix_per_s": None if full_wall_max is None else round(a.steps * world / full_wall_max * OUT_MPIX, 2),
-                       "full_path_note": "host frame in -> host frame out for all K frames on every rank (renderSequence over engine-allocated page-locked buffers, H2D/D2H on side streams); max over ranks",
                        "tiles_per_network_pass": eng.pass_tiles,
                        "tile_groups_per_pass": int(os.environ.get("W2X_GROUPS", "2")),
-                       "algorithmic_tflop_per_frame": round(eng.plan_flops * live / 1e12, 4),
-                       "families_ms_per_frame": {k: round(v[0], 3) for k, v in prof.items() if k != "frame_ms"}},
-            "roofline": roof,
+                       "algorithmic_tflop_per_frame": round(eng.plan_flops * live / 1e12, 4)},
             "placement": placement,
+        }
+        if a.full:
+            line["config"].update({
+                "full_path_ms_per_frame": None if full_wall_max is None else round(full_wall_max * 1e3 / a.steps, 3),
+                "full_path_frames_per_s": None if full_wall_max is None else round(a.steps * world / full_wall_max, 3),
+                "full_path_mpix_per_s": None if full_wall_max is None else round(a.steps * world / full_wall_max * OUT_MPIX, 2),
+                "full_path_note": "host frame in -> host frame out for all K frames on every rank (renderSequence over engine-allocated page-locked buffers, H2D/D2H on side streams); max over ranks",
+                "families_ms_per_frame": {k: round(v[0], 3) for k, v in prof.items() if k != "frame_ms"}})
+            line["roofline"] = roofline(desc, op_ms, folded, folded_fwd, n_tiles, live)
             # the path the reference's render() is (img2img_render.cpp:226,344): host frame in -> host frame out, PCIe included.  Not `value` (docstring).
-            "host_to_host": None if full_wall_max is None else {
+            line["host_to_host"] = None if full_wall_max is None else {
                 "ms_per_frame": round(full_wall_max * 1e3 / a.steps, 3), "frames_per_s": round(a.steps * world / full_wall_max, 3),
                 "mpix_per_s": round(a.steps * world / full_wall_max * OUT_MPIX, 2), "unit": "MPix/s",
                 "per_rank_ms_per_frame": shard.spread([None if w is None else w * 1e3 / a.steps for w in full_walls]),
                 "ms_per_frame_samples": [round(w * 1e3 / a.steps, 3) for w in full_regions],
                 "vs_resident": round(wall_max / full_wall_max, 4),
                 "one_synchronous_render_call_ms": round(pcie_ms_one, 2),
-                "how": "all K frames of every rank through renderSequence over engine-allocated page-locked buffers, H2D / D2H on side streams; same barriers, max over ranks"},
-        }
-        if not a.no_cpu_baseline and world == 1 and (a.config == 3 or a.cpu_baseline):
-            line["cpu_baseline"] = cpu_baseline(a.work, eng.output_tile_size)
+                "how": "all K frames of every rank through renderSequence over engine-allocated page-locked buffers, H2D / D2H on side streams; same barriers, max over ranks"}
+            if not a.no_cpu_baseline and world == 1 and (a.config == 3 or a.cpu_baseline):
+                line["cpu_baseline"] = cpu_baseline(work, eng.output_tile_size)
         if last_out is not None:
             dump_outputs(a.dump_outputs, last_out)
         print(json.dumps(line), file=json_out, flush=True)

@@ -273,6 +273,31 @@ def test_one_frame_over_two_processes_through_ipc_handles(pkg, tmp_path):
 
 
 @pytest.mark.gpu
+def test_plain_bench_run_measures_the_headline_only(tmp_path):
+    """bench.py without --full: the resident timed steps and nothing else - one JSON line with the headline fields and no host-to-host,
+    roofline or CPU baseline object, the last timed frame written by --dump-outputs, and the run's model and engine files gone from
+    --work when it exits (the next run exports its own)."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    work, dump = tmp_path / "w", tmp_path / "dump"
+    env = dict(os.environ, W2X_BENCH_WORK=str(work))
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "3", "--warmup", "1", "--config", "0", "--dump-outputs", str(dump)],
+                       capture_output=True, text=True, timeout=600, env=env)
+    assert r.returncode == 0, r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    d = json.loads(lines[0])
+    assert d["value"] > 0 and d["unit"] == "MPix/s" and d["higher_is_better"] is True and d["dtype"] == "f16" and d["steps"] == 3 and d["warmup"] == 1
+    assert abs(d["value"] - 380 * 4 * 290 * 4 / 1e6 / (d["ms_per_step"] * 1e-3)) <= 0.01 * d["value"]
+    assert not {"roofline", "host_to_host", "cpu_baseline"} & set(d) and "full_path_ms_per_frame" not in d["config"]
+    f = np.load(dump / "frame.npy")
+    assert f.shape == (290 * 4, 380 * 4, 3) and f.dtype == np.float32 and f.min() >= 0 and f.max() <= 255 and np.array_equal(f, np.rint(f))
+    assert os.listdir(work) == []
+
+
+@pytest.mark.gpu
 def test_frame_sharded_bench_line_certifies_where_it_ran(tmp_path):
     """bench.py's headline mode (frames round-robin over ranks) with two ranks on the box's ONE GPU (W2X_DEVICE_MAP=0,0) on the test-sized frame: the line carries
     `placement` (both ranks' pids, the one PCI bus id), n_ranks = 2 but n_gpus = 1 and a metric that starts with REHEARSAL - it cannot be read as a two-GPU
@@ -282,7 +307,7 @@ def test_frame_sharded_bench_line_certifies_where_it_ran(tmp_path):
     import sys
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     env = dict(os.environ, W2X_DEVICE_MAP="0,0", W2X_BENCH_WORK=str(tmp_path / "w"))
-    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "0", "--no-cpu-baseline"],
+    r = subprocess.run([sys.executable, os.path.join(root, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--config", "0", "--full", "--no-cpu-baseline"],
                        capture_output=True, text=True, timeout=600, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]
@@ -313,8 +338,7 @@ def test_five_engines_in_five_processes_on_one_card(tmp_path, mode):
     n = 5
     env = dict(os.environ, W2X_DEVICE_MAP=",".join(["0"] * n), W2X_BENCH_WORK=str(tmp_path / "w"))
     args = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(n), "--steps", "2", "--warmup", "1", "--repeats", "1", "--config", "0", "--no-cpu-baseline"]
-    if mode == "shards":
-        args += ["--mode", "shards"]
+    args += ["--mode", "shards"] if mode == "shards" else ["--full"]      # frames: --full carries the host-to-host figure and its byte check against render()
     r = subprocess.run(args, capture_output=True, text=True, timeout=900, env=env)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.strip()]

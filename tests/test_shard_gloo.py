@@ -102,6 +102,15 @@ def test_bench_refuses_a_rank_count_that_differs_from_gpus():
     assert r.returncode != 0 and "refusing to report n_gpus" in (r.stderr + r.stdout)
 
 
+def test_bench_op_times_and_cpu_baseline_are_parts_of_a_full_run():
+    """A plain bench.py run measures the headline figure only: asking it for per-op times or the CPU baseline without --full is an
+    argument error, raised before anything is built or touched."""
+    import subprocess, sys
+    for extra in (["--op-times"], ["--cpu-baseline"]):
+        r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "1"] + extra, capture_output=True, text=True, timeout=300)
+        assert r.returncode == 2 and "--full" in r.stderr, r.stderr
+
+
 def _one_json_line(stdout: str) -> dict:
     import json
     lines = [l for l in stdout.splitlines() if l.strip()]

@@ -5,7 +5,7 @@ cd "$(dirname "$0")/../.." || exit 1
 rounds=$1; shift
 for r in $(seq 1 "$rounds"); do
   for setting in "$@"; do
-    env $setting python bench.py --steps ${STEPS:-20} --warmup 3 --no-cpu-baseline 2>/dev/null | python -c "
+    env $setting python bench.py --steps ${STEPS:-20} --warmup 3 --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.readlines()[-1]); print('[$setting]', 'resident', d['ms_per_step'], d.get('ms_per_step_samples'), '| sequence', d['config']['full_path_ms_per_frame'], '| render()', d['config']['render_call_ms_pageable'])"
   done

@@ -15,7 +15,7 @@ extra() { case "$1" in k_mlp2.hip) echo "-mllvm -amdgpu-sched-strategy=max-ilp -
 # (a host file of the library - "engine.cpp:-DW2X_EXP_..." - is compiled the way the Makefile does it: -x hip, object build/<stem>.o)
 build() { local obj="build/${1%.*}.o" lang=""; case "$1" in *.cpp) lang="-x hip";; esac
           $CXX $(extra "$1") $2 -I csrc $lang -c "${3:-csrc/$1}" -o "$obj" 2>/dev/null && /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o libw2x.so build/*.o; }
-run() { (cd "$ROOT"; python bench.py --no-cpu-baseline --steps ${STEPS:-20} ${BENCH_ARGS:-} 2>/dev/null | python -c "
+run() { (cd "$ROOT"; python bench.py --full --no-cpu-baseline --steps ${STEPS:-20} ${BENCH_ARGS:-} 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read())
 print('$1', '| ms/frame', d['ms_per_step'], d.get('ms_per_step_samples'), '| full path', d['config']['full_path_ms_per_frame'], '|', d['roofline']['kernels_ms_per_frame'], '| compose', d['config']['families_ms_per_frame']['compose'])"); }

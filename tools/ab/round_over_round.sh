@@ -9,7 +9,7 @@ CFG=${1:-3}; ROUNDS=${2:-2}
 cp waifu2x-tensorrt_amd/libw2x.so /tmp/libw2x_now.so
 one() {   # <label> <library>
   cp "$2" waifu2x-tensorrt_amd/libw2x.so
-  python bench.py --config "$CFG" --no-cpu-baseline --work "/tmp/w2x_bench_$1" 2>/dev/null | python -c "
+  python bench.py --config "$CFG" --full --no-cpu-baseline 2>/dev/null | python -c "
 import json,sys
 d=json.loads(sys.stdin.read()); print('$1', 'ms/frame', d['ms_per_step'], d['ms_per_step_samples'], 'host to host', d['host_to_host']['ms_per_frame'])"
   python tools/power_trace.py -- python bench.py --config "$CFG" --steps 300 --repeats 1 --no-cpu-baseline --work "/tmp/w2x_bench_$1" 2>/dev/null | python -c "

@@ -29,7 +29,7 @@ def main():
         k = argv.index("--")
         argv, extra = argv[:k], argv[k + 1:]
     rounds, settings = int(argv[0]), argv[1:]
-    args = ["--steps", os.environ.get("STEPS", "20"), "--warmup", "3", "--no-cpu-baseline"] + extra
+    args = ["--steps", os.environ.get("STEPS", "20"), "--warmup", "3", "--full", "--no-cpu-baseline"] + extra
     for _ in range(rounds):
         for s in settings:
             code = CHILD.format(root=ROOT, setting=s, args=args, bench=os.path.join(ROOT, "bench.py"))

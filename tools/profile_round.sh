@@ -9,8 +9,8 @@ OUT=$ROOT/gpurun_out/$TAG
 mkdir -p "$OUT"
 export TMPDIR=/tmp
 cd "$ROOT"
-python3 bench.py --steps 20 --warmup 3 > "$OUT/bench.json" 2> "$OUT/bench.err"
-python3 bench.py --steps 10 --warmup 2 --no-cpu-baseline --op-times > "$OUT/op_times.txt" 2>&1
+python3 bench.py --steps 20 --warmup 3 --full > "$OUT/bench.json" 2> "$OUT/bench.err"
+python3 bench.py --steps 10 --warmup 2 --full --no-cpu-baseline --op-times > "$OUT/op_times.txt" 2>&1
 # Per-kernel evidence is collected with every pass in one piece on one stream (W2X_GROUPS=1): a launch is then the 45-tile launch
 # that bench.py's roofline block prices (its HIP-event durations come from the engine's profiling mode, which does not split either);
 # the timed region of bench.json above runs each pass as two tile groups on two streams, whose half-size launches overlap.
