@@ -109,6 +109,15 @@ int w2x_render_yuv(w2x_engine* e, const void* const* src_planes, const size_t* s
  * pair of depths for the sequence */
 int w2x_render_sequence_yuv(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
                             void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int count, int matrix, int range);
+/* Extension (Img2Img::renderYuvResized): w2x_render_yuv with the canvas resized on the device to dst_rows x dst_cols before it is encoded (the filter and
+ * the size rule of w2x_render_resized: each target dimension in [input dim, input dim * scaling], the two independent, odd sizes allowed; the resized RGB
+ * is clamped and coded as w2x_render_yuv codes the canvas).  At the scaled size the bytes are w2x_render_yuv's.  What w2x_render_yuv refuses, other
+ * sizes and unknown filters return 0 through the message callback. */
+int w2x_render_yuv_resized(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                           void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int matrix, int range, int filter);
+/* w2x_render_sequence_yuv with every frame resized like w2x_render_yuv_resized (one target size for the sequence) */
+int w2x_render_sequence_yuv_resized(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                                    void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int count, int matrix, int range, int filter);
 void* w2x_alloc_host(w2x_engine* e, size_t bytes);
 void w2x_free_host(w2x_engine* e, void* data);
 int w2x_pin_host(w2x_engine* e, void* data, size_t bytes);

@@ -87,6 +87,13 @@ public:
     bool renderYuv(const YuvImage& src, YuvImage& dst, YuvFormat format);
     // renderYuv() over a sequence of equally sized frames through the pipeline of renderSequence() (three plane copies per frame each way)
     bool renderSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format);
+    // Extension: renderYuv() to any output size between the input and the scaled frame - dst.rows x dst.cols, each in [src dim, src dim * scaling],
+    // the two independent, odd sizes allowed.  The frame is read as renderYuv() reads it, the fp32 canvas is formed and resized as renderResized() does it
+    // (not clamped before the resize: the filter's overshoot is part of the result), and the resized RGB is encoded as renderYuv() encodes the canvas, at
+    // dst.bits.  At dst = rows*scaling x cols*scaling the bytes are renderYuv()'s.  Other sizes and whatever renderYuv() refuses: false (message callback).
+    bool renderYuvResized(const YuvImage& src, YuvImage& dst, YuvFormat format, ResizeFilter filter = ResizeFilter::Bicubic);
+    // renderSequenceYuv() with every frame resized like renderYuvResized() to dsts[i].rows x dsts[i].cols (one size and one pair of depths for the sequence)
+    bool renderSequenceYuvResized(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, ResizeFilter filter = ResizeFilter::Bicubic);
     void* allocHost(size_t bytes);
     void freeHost(void* data);
     // Page-locks caller-owned memory in place.  Only whole pages are accepted (data and bytes multiples of 4096): a registration
@@ -119,7 +126,7 @@ public:
 private:
     bool renderPart(const Image& src, Image& dst, int part, int parts, const char* who, int resizeFilter = -1);   // resizeFilter >= 0: renderResized
     bool runSequence(const Image* srcs, Image* dsts, int count, int resizeFilter, const char* who);
-    bool runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, const char* who);
+    bool runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, int resizeFilter, const char* who);   // resizeFilter >= 0: renderYuvResized
     std::unique_ptr<Impl> impl;
 };
 

@@ -2,6 +2,9 @@
 renderSequence (bgr24, 1920x1080 -> 7680x4320) and through renderSequenceYuv at 8/8 and 10/10 bits (BT.709 limited), all with engine-owned
 page-locked buffers.  Median ms per frame over --regions timed regions of --steps frames each, after warm-up; one JSON line on stdout.
 
+--outsize WxH renders every mode to that raster instead of the x4 one (renderSequenceResized for bgr24, renderSequenceYuvResized for the YUV modes,
+bicubic): 3840x2160 is the 1080p -> 2160p case of DESIGN 9c.
+
 The device time of gather_yuv_kernel / compose_yuv_kernel comes from a separate run of this script under `rocprofv3 --kernel-trace --stats`;
 --bytes prints the bytes each path moves across PCIe per frame.  Not part of bench.py."""
 from __future__ import annotations
@@ -22,13 +25,13 @@ sys.path.insert(0, os.path.join(ROOT, "tests"))
 W, H, S, MODEL, NOISE, BATCH, TILE, BLEND = 1920, 1080, 4, "swin_unet/art", 3, 4, 256, 0.0625
 
 
-def frame_bytes(mode: str) -> dict:
+def frame_bytes(mode: str, ow: int = W * S, oh: int = H * S) -> dict:
     """bytes per frame uploaded and downloaded: bgr24 3 samples per pixel, 4:2:0 1.5, 10-bit samples take 2 bytes"""
     if mode == "bgr24":
-        return {"up": W * H * 3, "down": W * S * H * S * 3}
+        return {"up": W * H * 3, "down": ow * oh * 3}
     bps = 2 if mode == "10/10" else 1
     yuv = lambda w, h: (w * h + 2 * ((w + 1) // 2) * ((h + 1) // 2)) * bps
-    return {"up": yuv(W, H), "down": yuv(W * S, H * S)}
+    return {"up": yuv(W, H), "down": yuv(ow, oh)}
 
 
 def main() -> int:
@@ -38,10 +41,13 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=4)
     ap.add_argument("--work", default=os.path.join(tempfile.gettempdir(), "w2x_yuv_bench"), help="where the synthetic model and its engine file go")
     ap.add_argument("--modes", default="bgr24,8/8,10/10")
+    ap.add_argument("--outsize", default="", help="WxH: render to this raster (between 1920x1080 and 7680x4320) instead of the x4 one")
     ap.add_argument("--bytes", action="store_true", help="print the bytes per frame of each mode and exit (no GPU)")
     a = ap.parse_args()
+    OW, OH = (int(v) for v in a.outsize.split("x")) if a.outsize else (W * S, H * S)
+    resized = (OW, OH) != (W * S, H * S)
     if a.bytes:
-        print(json.dumps({m: frame_bytes(m) for m in a.modes.split(",")}))
+        print(json.dumps({m: frame_bytes(m, OW, OH) for m in a.modes.split(",")}))
         return 0
     import ctypes as C
     import numpy as np
@@ -77,10 +83,13 @@ def main() -> int:
         bufs = []
         if mode == "bgr24":
             pf = eng.alloc_host(frame.shape); pf[...] = frame; bufs.append(pf)
-            ring = [eng.alloc_host((H * S, W * S, 3)) for _ in range(3)]; bufs += ring
+            ring = [eng.alloc_host((OH, OW, 3)) for _ in range(3)]; bufs += ring
 
             def region():
-                eng.render_sequence([pf] * n, outs=[ring[k % 3] for k in range(n)])
+                if resized:
+                    eng.render_sequence_resized([pf] * n, (OH, OW), outs=[ring[k % 3] for k in range(n)])
+                else:
+                    eng.render_sequence([pf] * n, outs=[ring[k % 3] for k in range(n)])
         else:
             bits = 10 if mode == "10/10" else 8
             import yuv_ref   # (tests/yuv_ref.py: the frame's planes)
@@ -90,14 +99,15 @@ def main() -> int:
                 p[...] = q
             outs = []
             for _ in range(3):
-                b, o = pinned_planes(H * S, W * S, bits); bufs.append(b); outs.append(o)
+                b, o = pinned_planes(OH, OW, bits); bufs.append(b); outs.append(o)
             sp = (C.c_void_p * (3 * n))(*[p.ctypes.data for _ in range(n) for p in planes])
             dp = (C.c_void_p * (3 * n))(*[p.ctypes.data for k in range(n) for p in outs[k % 3]])
             ss = (C.c_size_t * 3)(*[p.strides[0] for p in planes])
             ds = (C.c_size_t * 3)(*[p.strides[0] for p in outs[0]])
 
             def region():
-                if not eng._L.w2x_render_sequence_yuv(eng._h, sp, ss, H, W, bits, dp, ds, H * S, W * S, bits, n, 1, 0):
+                args = (eng._h, sp, ss, H, W, bits, dp, ds, OH, OW, bits, n, 1, 0)
+                if not (eng._L.w2x_render_sequence_yuv_resized(*args, 0) if resized else eng._L.w2x_render_sequence_yuv(*args)):
                     raise SystemExit("render_sequence_yuv failed: " + eng.last_error())
         for _ in range(a.warmup):
             region()
@@ -106,12 +116,12 @@ def main() -> int:
             t0 = time.perf_counter()
             region()
             times.append((time.perf_counter() - t0) * 1e3 / n)
-        res[mode] = {"ms_per_frame_median": round(statistics.median(times), 4), "ms_per_frame": [round(t, 4) for t in times], "bytes": frame_bytes(mode)}
+        res[mode] = {"ms_per_frame_median": round(statistics.median(times), 4), "ms_per_frame": [round(t, 4) for t in times], "bytes": frame_bytes(mode, OW, OH)}
         for b in bufs:
             eng.free_host(b)
     eng.close()
-    print(json.dumps({"tool": "yuv_bench", "workload": f"{MODEL} x{S} noise{NOISE} batch{BATCH} tile{TILE} fp16, {W}x{H} -> {W * S}x{H * S} frames, blend 1/16, "
-                      f"renderSequence (bgr24) / renderSequenceYuv (BT.709 limited, in/out bits) host to host, page-locked buffers, "
+    print(json.dumps({"tool": "yuv_bench", "workload": f"{MODEL} x{S} noise{NOISE} batch{BATCH} tile{TILE} fp16, {W}x{H} -> {OW}x{OH} frames, blend 1/16, "
+                      f"{'renderSequenceResized (bgr24) / renderSequenceYuvResized' if resized else 'renderSequence (bgr24) / renderSequenceYuv'} (BT.709 limited, in/out bits) host to host, page-locked buffers, "
                       f"{a.regions} regions x {n} frames after {a.warmup} warm-up regions", "results": res}))
     return 0
 

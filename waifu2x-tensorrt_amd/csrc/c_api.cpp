@@ -180,6 +180,25 @@ int w2x_render_sequence_yuv(w2x_engine* e, const void* const* src_planes, const 
     }
     return e->engine.renderSequenceYuv(s.data(), d.data(), count, yuv_format(matrix, range)) ? 1 : 0;
 }
+int w2x_render_yuv_resized(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                           void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int matrix, int range, int filter) {
+    w2x::ResizeFilter f;
+    if (!e || !resize_filter(e, filter, "w2x_render_yuv_resized", f)) return 0;
+    const w2x::YuvImage s = yuv_image(src_planes, src_steps, rows, cols, src_bits);
+    w2x::YuvImage d = yuv_image(dst_planes, dst_steps, dst_rows, dst_cols, dst_bits);
+    return e->engine.renderYuvResized(s, d, yuv_format(matrix, range), f) ? 1 : 0;
+}
+int w2x_render_sequence_yuv_resized(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                                    void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int count, int matrix, int range, int filter) {
+    w2x::ResizeFilter f;
+    if (!e || count < 0 || (count > 0 && (!src_planes || !dst_planes)) || !resize_filter(e, filter, "w2x_render_sequence_yuv_resized", f)) return 0;
+    std::vector<w2x::YuvImage> s(count), d(count);
+    for (int i = 0; i < count; ++i) {
+        s[i] = yuv_image(src_planes + 3 * i, src_steps, rows, cols, src_bits);
+        d[i] = yuv_image(dst_planes + 3 * i, dst_steps, dst_rows, dst_cols, dst_bits);
+    }
+    return e->engine.renderSequenceYuvResized(s.data(), d.data(), count, yuv_format(matrix, range), f) ? 1 : 0;
+}
 void* w2x_alloc_host(w2x_engine* e, size_t bytes) { return e ? e->engine.allocHost(bytes) : nullptr; }
 void w2x_free_host(w2x_engine* e, void* data) { if (e) e->engine.freeHost(data); }
 int w2x_pin_host(w2x_engine* e, void* data, size_t bytes) { return e && e->engine.pinHost(data, bytes) ? 1 : 0; }

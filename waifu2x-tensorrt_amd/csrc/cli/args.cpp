@@ -66,7 +66,9 @@ std::string usage() {
            "      -i,--input PATH ... REQUIRED   --recursive   -o,--output DIR   --nosuffix\n"
            "      --blend FLOAT [1/16] {1/8,1/16,1/32,0}   --tta   --codec TEXT [libx264]   --pix_fmt TEXT [yuv420p]   --crf INT [23] 0..51\n"
            "      --outscale FLOAT        (extension) output size = input size x FLOAT, 1 <= FLOAT <= --scale: the network output resized on the GPU\n"
-           "      --resize-filter TEXT [bicubic]  (extension) {bicubic,bilinear}: the antialiasing filter of --outscale\n"
+           "      --outsize WxH           (extension) every output exactly W x H; each input w x h needs w <= W <= w x --scale, h <= H <= h x --scale\n"
+           "                              (the two factors independent); works with --colorspace: YUV frames are resized on the GPU before they are encoded\n"
+           "      --resize-filter TEXT [bicubic]  (extension) {bicubic,bilinear}: the antialiasing filter of --outscale / --outsize\n"
            "      --colorspace TEXT       (extension) {bt601,bt709,bt2020}: videos read through ffmpeg stay YUV 4:2:0 at --pix_fmt\n"
            "                              (yuv420p or yuv420p10le) and are converted on the GPU; the output carries the colour tags\n"
            "      --color_range TEXT [tv] (extension) {tv,pc}: the range of the --colorspace frames\n"
@@ -79,7 +81,7 @@ std::string usage() {
 Options parse(int argc, const char* const* argv) {
     Options o;
     std::vector<std::string> a(argv + 1, argv + argc);
-    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_filter = false, seen_colorspace = false, seen_range = false;
+    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_outsize = false, seen_filter = false, seen_colorspace = false, seen_range = false;
     auto value = [&](size_t& i) -> std::string {
         const std::string name = a[i];
         auto eq = name.find('=');
@@ -122,6 +124,14 @@ Options parse(int argc, const char* const* argv) {
         else if (k == "--pix_fmt") o.pixFmt = value(i);
         else if (k == "--crf") o.crf = to_int(k, value(i));
         else if (k == "--outscale") { o.outscale = to_double(k, value(i)); seen_outscale = true; }
+        else if (k == "--outsize") {
+            const std::string v = value(i);
+            int n = 0;
+            if (std::sscanf(v.c_str(), "%dx%d%n", &o.outsizeW, &o.outsizeH, &n) != 2 || (size_t)n != v.size() || v.find_first_not_of("0123456789x") != std::string::npos)
+                throw std::runtime_error("--outsize: '" + v + "' is not WxH (two positive integers)");
+            if (o.outsizeW <= 0 || o.outsizeH <= 0) throw std::runtime_error("--outsize: " + v + ": width and height must be positive");
+            seen_outsize = true;
+        }
         else if (k == "--resize-filter") { o.resizeFilter = value(i); std::transform(o.resizeFilter.begin(), o.resizeFilter.end(), o.resizeFilter.begin(), ::tolower); seen_filter = true; }
         else if (k == "--colorspace") { o.colorspace = value(i); std::transform(o.colorspace.begin(), o.colorspace.end(), o.colorspace.begin(), ::tolower); seen_colorspace = true; }
         else if (k == "--color_range") { o.colorRange = value(i); std::transform(o.colorRange.begin(), o.colorRange.end(), o.colorRange.begin(), ::tolower); seen_range = true; }
@@ -164,15 +174,21 @@ Options parse(int argc, const char* const* argv) {
             if (o.devices > 1)
                 for (const auto& p : o.inputs)
                     if (!std::filesystem::is_directory(p) && is_builtin_still(p)) throw std::runtime_error("--outscale: a still over --devices " + std::to_string(o.devices) + " is not supported: " + p);
-        } else if (seen_filter) throw std::runtime_error("--resize-filter: needs --outscale");
+        } else if (seen_outsize) {
+            member<std::string>("--resize-filter", o.resizeFilter, {"bicubic", "bilinear"});
+            if (o.devices > 1)
+                for (const auto& p : o.inputs)
+                    if (!std::filesystem::is_directory(p) && is_builtin_still(p)) throw std::runtime_error("--outsize: a still over --devices " + std::to_string(o.devices) + " is not supported: " + p);
+        } else if (seen_filter) throw std::runtime_error("--resize-filter: needs --outscale or --outsize");
+        if (seen_outscale && seen_outsize) throw std::runtime_error("--outsize: not together with --outscale (one of a factor and a size)");
         if (seen_colorspace) {
             member<std::string>("--colorspace", o.colorspace, {"bt601", "bt709", "bt2020"});
             member<std::string>("--color_range", o.colorRange, {"tv", "pc"});
             if (o.pixFmt != "yuv420p" && o.pixFmt != "yuv420p10le") throw std::runtime_error("--pix_fmt: with --colorspace one of {yuv420p,yuv420p10le}, got " + o.pixFmt);
-            if (seen_outscale) throw std::runtime_error("--colorspace: not together with --outscale (YUV frames are rendered at the network's size)");
+            if (seen_outscale) throw std::runtime_error("--colorspace: not together with --outscale (a factor rarely gives the even sizes video wants: use --outsize WxH)");
         } else if (seen_range) throw std::runtime_error("--color_range: needs --colorspace");
-    } else if (seen_outscale || seen_filter || seen_colorspace || seen_range)
-        throw std::runtime_error(std::string(seen_outscale ? "--outscale" : seen_filter ? "--resize-filter" : seen_colorspace ? "--colorspace" : "--color_range") + ": only with render");
+    } else if (seen_outscale || seen_outsize || seen_filter || seen_colorspace || seen_range)
+        throw std::runtime_error(std::string(seen_outscale ? "--outscale" : seen_outsize ? "--outsize" : seen_filter ? "--resize-filter" : seen_colorspace ? "--colorspace" : "--color_range") + ": only with render");
     // cross-checks, main.cpp:142-145
     if (o.model == "cunet/art" && o.scale == 4) throw std::runtime_error("cunet/art does not support scale factor 4.");
     if (o.noise == -1 && o.scale == 1) throw std::runtime_error("Noise level -1 does not support scale factor 1.");
@@ -185,6 +201,7 @@ std::string model_path(const Options& o) {
 }
 
 static std::string outscale_tag(const Options& o) {
+    if (o.outsizeW > 0) return "(" + std::to_string(o.outsizeW) + "x" + std::to_string(o.outsizeH) + ")";
     if (o.outscale <= 0) return "";
     char buf[64]; std::snprintf(buf, sizeof buf, "(outscale%g)", o.outscale);
     return buf;
@@ -197,7 +214,10 @@ std::string output_suffix(const Options& o) {
            (o.scale == 1 ? "" : "(scale" + std::to_string(o.scale) + ")") + outscale_tag(o) + (o.tta ? "(tta)" : "");
 }
 
-int out_dim(const Options& o, int dim) { return o.outscale > 0 ? (int)std::lround(dim * o.outscale) : dim * o.scale; }
+int out_dim(const Options& o, int dim, bool width) {
+    if (o.outsizeW > 0) return width ? o.outsizeW : o.outsizeH;
+    return o.outscale > 0 ? (int)std::lround(dim * o.outscale) : dim * o.scale;
+}
 
 std::string output_path(const Options& o, const std::string& input, bool single_frame) {
     namespace fs = std::filesystem;
@@ -215,7 +235,8 @@ std::string to_json(const Options& o) {
        << ", \"batchSize\": " << o.batchSize << ", \"tileSize\": " << o.tileSize << ", \"device\": " << o.device << ", \"devices\": " << o.devices << ", \"split\": " << q(o.split)
        << ", \"precision\": " << q(o.precision) << ", \"recursive\": " << (o.recursive ? "true" : "false") << ", \"output\": " << q(o.output)
        << ", \"nosuffix\": " << (o.nosuffix ? "true" : "false") << ", \"blend\": " << o.blend << ", \"tta\": " << (o.tta ? "true" : "false") << ", \"tta_mode\": " << q(o.ttaMode)
-       << ", \"outscale\": " << (o.outscale > 0 ? std::to_string(o.outscale) : std::string("null")) << ", \"resize_filter\": " << q(o.resizeFilter)
+       << ", \"outscale\": " << (o.outscale > 0 ? std::to_string(o.outscale) : std::string("null")) << ", \"outsize\": " << (o.outsizeW > 0 ? "[" + std::to_string(o.outsizeW) + ", " + std::to_string(o.outsizeH) + "]" : std::string("null"))
+       << ", \"resize_filter\": " << q(o.resizeFilter)
        << ", \"colorspace\": " << (o.colorspace.empty() ? std::string("null") : q(o.colorspace)) << ", \"color_range\": " << q(o.colorRange)
        << ", \"codec\": " << q(o.codec) << ", \"pix_fmt\": " << q(o.pixFmt) << ", \"crf\": " << o.crf << ", \"inputs\": [";
     for (size_t i = 0; i < o.inputs.size(); ++i) os << (i ? ", " : "") << q(o.inputs[i]);

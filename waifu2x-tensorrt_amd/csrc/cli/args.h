@@ -34,7 +34,9 @@ struct Options {
     bool deep = false;                    // --deep: 16-bit PNGs keep 16 bits per sample (read, rendered and written as CV_16UC3; default: cut to 8 like cv::imread)
     double outscale = 0;                  // --outscale F: output lround(W * F) x lround(H * F), F in [1, --scale]: the network's output resized on the device
                                           // (Img2Img::renderResized / renderSequenceResized); 0 = the network's own size, the reference's behaviour
-    std::string resizeFilter = "bicubic"; // --resize-filter {bicubic,bilinear}: the antialiasing filter of --outscale
+    int outsizeW = 0, outsizeH = 0;       // --outsize WxH: every output exactly W x H, each input w x h with w <= W <= w * scale, h <= H <= h * scale (the two factors
+                                          // independent): resized on the device like --outscale; with --colorspace through Img2Img::renderSequenceYuvResized; 0 = not given
+    std::string resizeFilter = "bicubic"; // --resize-filter {bicubic,bilinear}: the antialiasing filter of --outscale / --outsize
     std::string colorspace;               // --colorspace {bt601,bt709,bt2020}: videos read through ffmpeg travel as raw --pix_fmt (yuv420p / yuv420p10le)
                                           // frames, converted on the GPU (Img2Img::renderSequenceYuv); "" = bgr24 frames, the reference's path
     std::string colorRange = "tv";        // --color_range {tv,pc}: the range of those frames (with --colorspace only)
@@ -48,12 +50,12 @@ std::string usage();
 
 // models/<model>/[noiseN_][scaleSx].onnx  (main.cpp:201-204)
 std::string model_path(const Options& o);
-// "(model_with_underscores)(noiseN)(scaleS)(tta)"  (main.cpp:205-209); with --outscale F "(outscale<F as %g>)" after (scaleS)
+// "(model_with_underscores)(noiseN)(scaleS)(tta)"  (main.cpp:205-209); with --outscale F "(outscale<F as %g>)", with --outsize WxH "(WxH)" after (scaleS)
 std::string output_suffix(const Options& o);
 // output file name for one input (main.cpp:240-257): directory override, suffix, .png for stills / .mp4 for videos
 std::string output_path(const Options& o, const std::string& input, bool single_frame);
 std::string to_json(const Options& o);
-// the output size of a `rows` x `cols` frame: x scale, or lround(x * outscale) with --outscale
-int out_dim(const Options& o, int dim);
+// the output size of a `rows` x `cols` frame, one axis at a time (width: the columns): x scale, lround(x * outscale) with --outscale, W or H with --outsize
+int out_dim(const Options& o, int dim, bool width);
 
 }  // namespace w2x::cli

@@ -115,7 +115,7 @@ struct AviSink : FrameSink {
 // consecutive frames overlapped), one writer thread drains the slots in stream order - decoding, N renders and encoding all overlap,
 // and frames leave in the order they came (the reference serialises read -> render -> write per frame).
 // A frame is inBytes in and outBytes out; `render` turns `count` of them into outputs on one engine (renderSequence, renderSequenceResized for
-// --outscale, renderSequenceYuv for --colorspace).
+// --outscale / --outsize, renderSequenceYuv for --colorspace, renderSequenceYuvResized for --colorspace with --outsize).
 using RenderFrames = std::function<bool(Img2Img&, uint8_t* const* in, uint8_t* const* out, int count)>;
 bool run_frame_pipeline(std::vector<std::unique_ptr<Img2Img>>& engines, FrameSource& src, FrameSink& dst, size_t inBytes, size_t outBytes,
                         const RenderFrames& render, const std::function<void(int)>& on_frames) {
@@ -222,17 +222,25 @@ int main(int argc, char** argv) {
             c.overlapX = c.overlapY = o.blend; c.tta = o.tta; c.ttaBugCompat = o.ttaMode == "reference";
             if (!engines.back()->load(modelPath, c)) return -1;
         }
-        // --outscale (extension): every output lround(W * F) x lround(H * F), the network's output resized on the device
+        // --outscale (extension): every output lround(W * F) x lround(H * F), the network's output resized on the device; --outsize: every output W x H
         const ResizeFilter filter = o.resizeFilter == "bilinear" ? ResizeFilter::Bilinear : ResizeFilter::Bicubic;
-        const bool resize = o.outscale > 0;
+        const bool resize = o.outscale > 0 || o.outsizeW > 0;
+        // --outsize: an input the size cannot be reached from stops the run
+        auto check_outsize = [&](const std::string& file, int w, int h) {
+            if (o.outsizeW <= 0 || (o.outsizeW >= w && o.outsizeW <= w * o.scale && o.outsizeH >= h && o.outsizeH <= h * o.scale)) return;
+            throw std::runtime_error(file + ": --outsize " + std::to_string(o.outsizeW) + "x" + std::to_string(o.outsizeH) + " cannot be reached from this " + std::to_string(w) + "x" +
+                                     std::to_string(h) + " input: the output must lie between " + std::to_string(w) + "x" + std::to_string(h) + " and " + std::to_string(w * o.scale) + "x" +
+                                     std::to_string(h * o.scale) + " (--scale " + std::to_string(o.scale) + ")");
+        };
         const std::vector<std::string> files = find_inputs(o);
         fileCount = files.size();
         for (const std::string& file : files) {
             if (cli::is_builtin_still(file)) {
                 frameIndex = 0; frameCount = 1;
                 cli::Bitmap in = cli::read_image(file, o.deep), out;
-                out.rows = cli::out_dim(o, in.rows); out.cols = cli::out_dim(o, in.cols);
-                if (resize && o.devices > 1) throw std::runtime_error(file + ": --outscale renders a still on one device (--devices 1)");
+                check_outsize(file, in.cols, in.rows);
+                out.rows = cli::out_dim(o, in.rows, false); out.cols = cli::out_dim(o, in.cols, true);
+                if (resize && o.devices > 1) throw std::runtime_error(file + ": --outscale / --outsize render a still on one device (--devices 1)");
                 const bool deep = !in.bgr16.empty();                   // --deep on a 16-bit PNG: CV_16UC3 through the engine (extension)
                 Image src, dst;
                 if (deep) {
@@ -301,7 +309,8 @@ int main(int argc, char** argv) {
                 frameIndex = 0; frameCount = frames;
                 const bool single = frames == 1;
                 std::string outFile = cli::output_path(o, file, single);
-                const int outW = cli::out_dim(o, width), outH = cli::out_dim(o, height);
+                check_outsize(file, width, height);
+                const int outW = cli::out_dim(o, width, true), outH = cli::out_dim(o, height, false);
                 const size_t inBytes = yuv ? yuv_frame_bytes(height, width, o.pixFmt) : (size_t)width * height * 3;
                 const size_t outBytes = yuv ? yuv_frame_bytes(outH, outW, o.pixFmt) : (size_t)outW * outH * 3;
                 if (have_ffmpeg) {
@@ -330,7 +339,7 @@ int main(int argc, char** argv) {
                     render = [=](Img2Img& e, uint8_t* const* in, uint8_t* const* out, int n) {
                         std::vector<YuvImage> si(n), di(n);
                         for (int k = 0; k < n; ++k) { si[k] = packed_yuv(in[k], height, width, bits); di[k] = packed_yuv(out[k], outH, outW, bits); }
-                        return e.renderSequenceYuv(si.data(), di.data(), n, f);
+                        return resize ? e.renderSequenceYuvResized(si.data(), di.data(), n, f, filter) : e.renderSequenceYuv(si.data(), di.data(), n, f);
                     };
                 }
                 const bool ok = run_frame_pipeline(engines, *source, *sink, inBytes, outBytes, render, [&](int n) { frameIndex += n; if (n) on_progress(1, 1, 0.0); });

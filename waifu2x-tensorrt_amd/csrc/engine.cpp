@@ -283,6 +283,7 @@ struct Img2Img::Impl {
     const ResizeTables* rs = nullptr;
     // renderYuv() / renderSequenceYuv(): the frame being rendered is YUV 4:2:0 (null outside such a call).  d_frame / d_out then hold the three planes
     // (yuv_layout) and the gather / compose launches are gather_yuv_kernel / compose_yuv_kernel; `key` tells the captured passes of each input format apart.
+    // With `rs` set as well (renderYuvResized) the frame ends with compose_canvas_kernel and resample_yuv_kernel, and d_out holds planes of the target size.
     struct YuvJob { YuvCoefs in, out; int in_bits = 8, out_bits = 8, key = 0; };
     const YuvJob* yuv = nullptr;
     std::vector<void*> pinned;
@@ -881,7 +882,7 @@ struct Img2Img::Impl {
     // device part of one frame: gather -> network per batch -> compose.  Frame must already be in d_frame.
     void run_frame(int rows, int cols, const TileGrid& grid, bool report, const StripPlan& sp) {
         run_passes(rows, cols, sp.tile_count, 0, report, 0, true);
-        if (rs) { compose_canvas(rows, cols, grid, stream); resample(stream); return; }   // a resized frame (renderResized)
+        if (rs) { compose_canvas(rows, cols, grid, stream); if (yuv) resample_yuv(stream); else resample(stream); return; }   // a resized frame (renderResized / renderYuvResized)
         if (yuv) { compose_yuv(rows, cols, grid, stream); return; }                       // a YUV frame (renderYuv)
         compose_rect(rows, cols, grid, sp.x0, sp.x1, 0, 0, sp.first_tile);
     }
@@ -916,7 +917,7 @@ struct Img2Img::Impl {
             compose_canvas(rows, cols, grid, s2);
             hipAssert(hipEventRecord(ev_cmp[which], s2));
             if (out_free) hipAssert(hipStreamWaitEvent(s2, out_free, 0));
-            resample(s2);
+            if (yuv) resample_yuv(s2); else resample(s2);
             return;
         }
         if (out_free) hipAssert(hipStreamWaitEvent(s2, out_free, 0));     // the frame that last left through this output buffer has been downloaded
@@ -1188,6 +1189,15 @@ struct Img2Img::Impl {
         rp.fx = rs->fx; rp.wx = rs->wx; rp.kx = rs->kx; rp.fy = rs->fy; rp.wy = rs->wy; rp.ky = rs->ky; rp.rows_max = rs->rows_max;
         hipAssert(launch_resample(rp, on));
     }
+    // a resized YUV frame (rs and yuv set, renderYuvResized): the resize of d_canvas written as the planes of d_out (yuv_layout of the target size)
+    void resample_yuv(hipStream_t on) {
+        ResampleYuvParams rp;
+        rp.canvas = d_canvas; rp.inW = rs->inW; rp.inH = rs->inH;
+        rp.outW = rs->outW; rp.outH = rs->outH;
+        rp.fx = rs->fx; rp.wx = rs->wx; rp.kx = rs->kx; rp.fy = rs->fy; rp.wy = rs->wy; rp.ky = rs->ky; rp.rows_max = rs->rows_max;
+        rp.dst = yuv_layout(d_out, rs->outH, rs->outW, yuv->out_bits); rp.k = yuv->out;
+        hipAssert(launch_resample_yuv(rp, on));
+    }
     // the device tap tables of one (canvas, target, filter) and a canvas that holds the frame; the caller sets rs to the result for the frame
     const ResizeTables* resize_tables(int inW, int inH, int outW, int outH, int filter) {
         for (const ResizeTables& t : rs_tables) if (t.inW == inW && t.inH == inH && t.outW == outW && t.outH == outH && t.filter == filter) return &t;
@@ -1217,12 +1227,13 @@ struct Img2Img::Impl {
         canvas_cap = bytes;
     }
     // renderResized() / renderSequenceResized(): the target size of a frame must be a downsample of the network output by a factor of 1 to s per axis
-    std::string resize_problem(const Image& src, const Image& dst, int filter) const {
+    std::string resize_problem(const Image& src, const Image& dst, int filter) const { return resize_problem(src.rows, src.cols, dst.rows, dst.cols, filter); }
+    std::string resize_problem(int rows, int cols, int out_rows, int out_cols, int filter) const {
         const int s = cfg.scaling;
         if (filter != 0 && filter != 1) return "Unknown resize filter.";
-        if (dst.rows < src.rows || dst.rows > src.rows * s || dst.cols < src.cols || dst.cols > src.cols * s || dst.rows <= 0 || dst.cols <= 0)
-            return "Output image has invalid size for a resize: " + std::to_string(dst.cols) + "x" + std::to_string(dst.rows) + " is not between " + std::to_string(src.cols) + "x" +
-                   std::to_string(src.rows) + " and " + std::to_string(src.cols * s) + "x" + std::to_string(src.rows * s) + ".";
+        if (out_rows < rows || out_rows > rows * s || out_cols < cols || out_cols > cols * s || out_rows <= 0 || out_cols <= 0)
+            return "Output image has invalid size for a resize: " + std::to_string(out_cols) + "x" + std::to_string(out_rows) + " is not between " + std::to_string(cols) + "x" +
+                   std::to_string(rows) + " and " + std::to_string(cols * s) + "x" + std::to_string(rows * s) + ".";
         return "";
     }
 };
@@ -1938,15 +1949,28 @@ bool Img2Img::runSequence(const Image* srcs, Image* dsts, int count, int resizeF
 }
 
 // renderYuv(): the sequence of one frame (run_frame: no rolling)
-bool Img2Img::renderYuv(const YuvImage& src, YuvImage& dst, YuvFormat format) { return runSequenceYuv(&src, &dst, 1, format, "renderYuv"); }
+bool Img2Img::renderYuv(const YuvImage& src, YuvImage& dst, YuvFormat format) { return runSequenceYuv(&src, &dst, 1, format, -1, "renderYuv"); }
 
 bool Img2Img::renderSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format) {
-    return runSequenceYuv(srcs, dsts, count, format, "renderSequenceYuv");
+    return runSequenceYuv(srcs, dsts, count, format, -1, "renderSequenceYuv");
+}
+
+// renderYuv() with the canvas resized to dst.rows x dst.cols before it is encoded: the frame's tiles from its planes (gather_yuv_kernel),
+// compose_canvas_kernel (fp32 canvas, not clamped), resample_yuv_kernel (k_resample.hip: the resize of renderResized, then clamp, Y per pixel, chroma of
+// the filtered RGB), the download of the target's planes.  At the scaled size it is renderYuv().
+bool Img2Img::renderYuvResized(const YuvImage& src, YuvImage& dst, YuvFormat format, ResizeFilter filter) {
+    return runSequenceYuv(&src, &dst, 1, format, filter == ResizeFilter::Bilinear ? 1 : filter == ResizeFilter::Bicubic ? 0 : 2, "renderYuvResized");
+}
+
+bool Img2Img::renderSequenceYuvResized(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, ResizeFilter filter) {
+    return runSequenceYuv(srcs, dsts, count, format, filter == ResizeFilter::Bilinear ? 1 : filter == ResizeFilter::Bicubic ? 0 : 2, "renderSequenceYuvResized");
 }
 
 // YUV 4:2:0 frames through renderSequence()'s pipeline: per frame three plane copies up on s_up, the passes with gather_yuv_kernel, compose_yuv_kernel
 // (on the second group's stream when the sequence rolls), three plane copies down on s_dn.  One size and one pair of depths for the sequence.
-bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, const char* who) try {
+// resizeFilter >= 0 (renderYuvResized / renderSequenceYuvResized): every dst is the target size of dsts[0], the frame step ends with the canvas compose
+// and resample_yuv_kernel; at the scaled size it is the plain sequence.
+bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, int resizeFilter, const char* who) try {
     if (!impl->loaded) { W2X_LOG_AS(who, error, "Render called before a successful load."); return false; }
     if (count <= 0) return true;
     if (!srcs || !dsts) { W2X_LOG_AS(who, error, "No frames given."); return false; }
@@ -1959,6 +1983,12 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
     const int rows = srcs[0].rows, cols = srcs[0].cols, s = cfg.scaling, in_bits = srcs[0].bits, out_bits = dsts[0].bits;
     if ((in_bits != 8 && in_bits != 10) || (out_bits != 8 && out_bits != 10)) { W2X_LOG_AS(who, error, "YUV frames must have 8 or 10 bits."); return false; }
     if (rows <= 0 || cols <= 0) { W2X_LOG_AS(who, error, "Input image is empty."); return false; }
+    const int out_rows = resizeFilter >= 0 ? dsts[0].rows : rows * s, out_cols = resizeFilter >= 0 ? dsts[0].cols : cols * s;
+    const bool resized = resizeFilter >= 0 && !(out_rows == rows * s && out_cols == cols * s);
+    if (resizeFilter >= 0) {
+        const std::string why = impl->resize_problem(rows, cols, out_rows, out_cols, resizeFilter);
+        if (!why.empty()) { W2X_LOG_AS(who, error, why); return false; }
+    }
     // every plane present, with a step that holds its row
     auto planes_ok = [](const YuvImage& f) {
         const size_t bps = f.bits > 8 ? 2 : 1;
@@ -1968,13 +1998,13 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
     for (int i = 0; i < count; ++i) {
         if (srcs[i].rows != rows || srcs[i].cols != cols || srcs[i].bits != in_bits) { W2X_LOG_AS(who, error, "Input images must be of one size and depth."); return false; }
         if (!planes_ok(srcs[i])) { W2X_LOG_AS(who, error, "Input image has a missing plane or an invalid step."); return false; }
-        if (dsts[i].rows != rows * s || dsts[i].cols != cols * s) { W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(cols * s) + "x" + std::to_string(rows * s) + "."); return false; }
+        if (dsts[i].rows != out_rows || dsts[i].cols != out_cols) { W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(out_cols) + "x" + std::to_string(out_rows) + "."); return false; }
         if (dsts[i].bits != out_bits) { W2X_LOG_AS(who, error, "Output images must be of one depth."); return false; }
         if (!planes_ok(dsts[i])) { W2X_LOG_AS(who, error, "Output image has a missing plane or an invalid step."); return false; }
     }
     hipStream_t stream = impl->stream;
     impl->ensure_copy_streams();
-    const size_t in_bytes = Impl::yuv_bytes(rows, cols, in_bits), out_bytes = Impl::yuv_bytes(rows * s, cols * s, out_bits);
+    const size_t in_bytes = Impl::yuv_bytes(rows, cols, in_bits), out_bytes = Impl::yuv_bytes(out_rows, out_cols, out_bits);
     impl->ensure(impl->d_frame, impl->frame_cap, in_bytes);   impl->ensure(impl->d_frame2, impl->frame2_cap, in_bytes);
     impl->ensure(impl->d_out, impl->out_cap, out_bytes);      impl->ensure(impl->d_out2, impl->out2_cap, out_bytes);
     TileGrid grid = calculate_tiles(cols, rows, cols * s, rows * s, plan.T, plan.T, plan.Tout, plan.Tout, s, cfg.overlapX, cfg.overlapY);
@@ -1989,6 +2019,11 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
     job.in_bits = in_bits; job.out_bits = out_bits; job.key = 2 + (in_bits == 10 ? 1 : 0) + 2 * range + 4 * matrix;
     impl->yuv = &job;
     impl->deep = false;
+    struct ResizeScope { Impl* im; ~ResizeScope() { im->rs = nullptr; } } resize_scope{impl.get()};
+    if (resized) {
+        impl->rs = impl->resize_tables(cols * s, rows * s, out_cols, out_rows, resizeFilter);
+        impl->ensure_canvas((size_t)rows * s * cols * s * 3 * sizeof(float));
+    }
     // the three planes of a frame between the caller's layout and the device's (yuv_layout), on copy stream `on`
     auto copy_planes = [&](const YuvImage& host, uint8_t* dev, int r, int c, bool up, hipStream_t on) {
         const YuvPlanes d = Impl::yuv_layout(dev, r, c, host.bits);
@@ -2001,7 +2036,7 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
     };
     const float total_ms = impl->run_sequence(count, rows, cols, grid, sp,
         [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(srcs[i], dev, rows, cols, true, on); },
-        [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(dsts[i], dev, rows * s, cols * s, false, on); });
+        [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(dsts[i], dev, out_rows, out_cols, false, on); });
     impl->last_ms = total_ms / count;
     impl->last_rows = impl->last_cols = 0;   // (d_frame / d_out hold planes: not replayed by benchResident / residentOutput / profileFrame)
     return true;

@@ -290,6 +290,18 @@ struct ComposeYuvParams {
 };
 constexpr int kYuvSites = 4, kYuvThreads = 64;   // chroma sites (8 luma columns, 2 rows) per thread, threads per workgroup (one wave)
 hipError_t launch_compose_yuv(const ComposeYuvParams& p, hipStream_t s);
+// k_resample.hip resample_yuv_kernel: resample_kernel's resize of the fp32 RGB canvas (same tap tables, same rows_max) with compose_yuv_kernel's
+// encoding behind it instead of the BGR quantisation: the resized R, G, B clamped to [0, 1] and written as YUV 4:2:0 planes of outH x outW
+// (dst.rows x dst.cols), Y per pixel, Cb / Cr of the RGB filtered (1/4, 1/2, 1/4) x (1/2, 1/2) onto each chroma site (renderYuvResized)
+struct ResampleYuvParams {
+    const float* canvas = nullptr; int inW = 0, inH = 0;
+    int outW = 0, outH = 0;
+    const int* fx = nullptr; const float* wx = nullptr; int kx = 0;
+    const int* fy = nullptr; const float* wy = nullptr; int ky = 0;
+    int rows_max = 0;
+    YuvPlanes dst; YuvCoefs k;
+};
+hipError_t launch_resample_yuv(const ResampleYuvParams& p, hipStream_t s);
 // debug/test helpers used by w2x_infer (mirrors blobFromImages / imagesFromBlob, img2img_infer.cpp:5-39)
 hipError_t launch_blob_to_nhwc(const float* nchw, void* out_nhwc4, int B, int T, bool fp32, hipStream_t s);
 hipError_t launch_nhwc_to_blob(const void* in_nhwc4, float* nchw, int B, int T, bool fp32, hipStream_t s);

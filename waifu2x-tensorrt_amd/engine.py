@@ -146,6 +146,8 @@ def lib():
     L.w2x_render_yuv.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]; L.w2x_render_yuv.restype = C.c_int
     L.w2x_render_sequence_yuv.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
     L.w2x_render_sequence_yuv.restype = C.c_int
+    L.w2x_render_yuv_resized.argtypes = L.w2x_render_yuv.argtypes + [C.c_int]; L.w2x_render_yuv_resized.restype = C.c_int
+    L.w2x_render_sequence_yuv_resized.argtypes = L.w2x_render_sequence_yuv.argtypes + [C.c_int]; L.w2x_render_sequence_yuv_resized.restype = C.c_int
     L.w2x_yuv_plane_sizes.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp]; L.w2x_yuv_plane_sizes.restype = C.c_int
     L.w2x_render_strip.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]; L.w2x_render_strip.restype = C.c_int
     L.w2x_render_sequence.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int]; L.w2x_render_sequence.restype = C.c_int
@@ -189,7 +191,7 @@ EXPORTED_SYMBOLS = [
     "w2x_create", "w2x_destroy", "w2x_set_message_callback", "w2x_set_progress_callback", "w2x_build", "w2x_load",
     "w2x_render", "w2x_render16", "w2x_infer", "w2x_output_tile_size", "w2x_plan_flops", "w2x_pass_tiles", "w2x_last_render_ms", "w2x_bench_resident", "w2x_resident_output", "w2x_profile_frame", "w2x_op_times",
     "w2x_render_resized", "w2x_render16_resized", "w2x_render_sequence_resized", "w2x_resize_weights",
-    "w2x_render_yuv", "w2x_render_sequence_yuv", "w2x_yuv_plane_sizes",
+    "w2x_render_yuv", "w2x_render_sequence_yuv", "w2x_yuv_plane_sizes", "w2x_render_yuv_resized", "w2x_render_sequence_yuv_resized",
     "w2x_render_strip", "w2x_strip_plan", "w2x_render_sharded", "w2x_shard_plan", "w2x_shard_compute", "w2x_shard_slab", "w2x_shard_finish", "w2x_ipc_export", "w2x_ipc_open", "w2x_ipc_close", "w2x_render_sequence", "w2x_alloc_host", "w2x_free_host", "w2x_pin_host", "w2x_unpin_host", "w2x_calculate_tiles", "w2x_tile_weights", "w2x_describe_plan", "w2x_describe_plan_precision", "w2x_write_engine_file", "w2x_validate_engine_file", "w2x_device_pci_bus_id", "w2x_sha256_hex", "w2x_version", "w2x_debug_set"]
 
 
@@ -400,9 +402,42 @@ class Img2Img:
             return dst
         return ok
 
+    def render_yuv_resized(self, y: np.ndarray, u: np.ndarray, v: np.ndarray, size, *, matrix: str = "bt709", full_range: bool = False,
+                           out_bits: int | None = None, filter: str = "bicubic", dst=None):
+        """render_yuv() with the canvas resized on the device to size = (rows, cols), each in [input dim, input dim * scaling], before it is encoded
+        (w2x_render_yuv_resized).  Returns (Y, U, V) at the target size, or raises.  dst: pre-allocated planes (then a bool is returned)."""
+        bits = _yuv_bits((y, u, v))
+        ob = bits if out_bits is None else int(out_bits)
+        rows, cols = int(size[0]), int(size[1])
+        fid = _filter_id(filter)
+        dt = np.uint16 if ob == 10 else np.uint8
+        shapes = yuv_plane_shapes(max(rows, 0), max(cols, 0))
+        ret_array = dst is None
+        out = tuple(np.empty(shape, dt) for shape in shapes) if dst is None else tuple(dst)
+        if len(out) != 3 or any(not isinstance(p, np.ndarray) or p.dtype != dt or p.shape != shape or (p.size and p.strides[1] != p.itemsize) for p, shape in zip(out, shapes)):
+            raise ValueError("dst must be three 2-D planes of the target's 4:2:0 shapes, uint8 for 8-bit and uint16 for 10-bit output, with packed rows")
+        dp = (C.c_void_p * 3)(*[p.ctypes.data if p.size else None for p in out])   # (an empty target: refused by the library)
+        ok = bool(self._L.w2x_render_yuv_resized(self._h, (C.c_void_p * 3)(*[p.ctypes.data for p in (y, u, v)]), (C.c_size_t * 3)(*[p.strides[0] for p in (y, u, v)]),
+                                                 y.shape[0], y.shape[1], bits, dp, (C.c_size_t * 3)(*[p.strides[0] for p in out]), rows, cols, ob,
+                                                 _matrix_id(matrix), 1 if full_range else 0, fid))
+        if ret_array:
+            if not ok:
+                raise W2xError(self.last_error() or "render_yuv_resized failed")
+            return out
+        return ok
+
+    def render_sequence_yuv_resized(self, frames, size, *, matrix: str = "bt709", full_range: bool = False, out_bits: int | None = None, pinned: bool = False,
+                                    filter: str = "bicubic"):
+        """render_sequence_yuv() with every frame resized to size = (rows, cols) like render_yuv_resized() (w2x_render_sequence_yuv_resized)"""
+        return self._sequence_yuv(frames, (int(size[0]), int(size[1])), _filter_id(filter), matrix, full_range, out_bits, pinned)
+
     def render_sequence_yuv(self, frames, *, matrix: str = "bt709", full_range: bool = False, out_bits: int | None = None, pinned: bool = False):
         """render_yuv() over equally sized frames [(y, u, v), ...] through the pipeline of render_sequence() (w2x_render_sequence_yuv).
         pinned=True takes the output planes from alloc_host() (a ring of three frames; copies of the results are returned)."""
+        return self._sequence_yuv(frames, None, None, matrix, full_range, out_bits, pinned)
+
+    def _sequence_yuv(self, frames, size, fid, matrix, full_range, out_bits, pinned):
+        """the two YUV sequence calls: size = None the scaled size (w2x_render_sequence_yuv), else the target of w2x_render_sequence_yuv_resized with filter fid"""
         n = len(frames)
         if n == 0:
             return []
@@ -414,7 +449,8 @@ class Img2Img:
             if _yuv_bits(f) != bits or f[0].shape != (rows, cols) or [p.strides[0] for p in f] != steps:
                 raise ValueError("frames must be YUV planes of one size, depth and layout")
         s = getattr(self, "_scaling", 0)
-        shapes = yuv_plane_shapes(rows * s, cols * s)
+        orows, ocols = (rows * s, cols * s) if size is None else size
+        shapes = yuv_plane_shapes(max(orows, 1), max(ocols, 1))                # (an empty target: refused by the library)
         dt = np.uint8 if ob != 10 else np.uint16
         own = []
         if pinned:
@@ -425,16 +461,16 @@ class Img2Img:
                 for (r, c), nb in zip(shapes, sizes):
                     planes.append(buf[o:o + nb].view(dt).reshape(r, c)); o += nb
                 own.append((buf, tuple(planes)))
-        outs = [own[k % len(own)][1] for k in range(n)] if own else [self._yuv_out(rows, cols, 8 if ob != 10 else 10) for _ in range(n)]
+        outs = [own[k % len(own)][1] for k in range(n)] if own else [tuple(np.empty(shape, dt) for shape in shapes) for _ in range(n)]
         dsteps = (C.c_size_t * 3)(*[p.strides[0] for p in outs[0]])
 
         def run(fs, os_):
             m = len(fs)
             sp = (C.c_void_p * (3 * m))(*[p.ctypes.data for f in fs for p in f])
             dp = (C.c_void_p * (3 * m))(*[p.ctypes.data for o in os_ for p in o])
-            if not self._L.w2x_render_sequence_yuv(self._h, sp, (C.c_size_t * 3)(*steps), rows, cols, bits, dp, dsteps, rows * s, cols * s, ob, m,
-                                                   _matrix_id(matrix), 1 if full_range else 0):
-                raise W2xError(self.last_error() or "render_sequence_yuv failed")
+            args = (self._h, sp, (C.c_size_t * 3)(*steps), rows, cols, bits, dp, dsteps, orows, ocols, ob, m, _matrix_id(matrix), 1 if full_range else 0)
+            if not (self._L.w2x_render_sequence_yuv(*args) if size is None else self._L.w2x_render_sequence_yuv_resized(*args, fid)):
+                raise W2xError(self.last_error() or ("render_sequence_yuv failed" if size is None else "render_sequence_yuv_resized failed"))
         if own:
             res = []
             try:
