@@ -118,6 +118,14 @@ int w2x_render_yuv_resized(w2x_engine* e, const void* const* src_planes, const s
 /* w2x_render_sequence_yuv with every frame resized like w2x_render_yuv_resized (one target size for the sequence) */
 int w2x_render_sequence_yuv_resized(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
                                     void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int count, int matrix, int range, int filter);
+/* Extension (Img2Img::renderRgba): w2x_render on interleaved 8-bit BGRA frames (CV_8UC4; steps in bytes, >= cols * 4; dst rows*scaling x cols*scaling) in one
+ * call: one upload, the colour bleed on the device (bleed = radius 0..16: the colours of the pixels with alpha > 0 spread that far under alpha == 0, see
+ * w2x_alpha_bleed), colour and alpha tiles in one schedule, one download.  Colour bytes: w2x_render of w2x_alpha_bleed(BGR, A, bleed); alpha bytes: the green
+ * channel of w2x_render of the gray image B = G = R = A.  skip_uniform_alpha != 0: a frame whose alpha plane is one value v runs no alpha tiles and gets
+ * alpha v everywhere.  A bleed outside [0, 16], empty images and short steps return 0 through the message callback. */
+int w2x_render_rgba(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, size_t dst_step, int bleed, int skip_uniform_alpha);
+/* Test hook (Img2Img::alphaBleed): the device bleed alone - BGRA frame in, the BGR frame the tiles would be read from out (rows x cols, bgr_step >= cols * 3) */
+int w2x_alpha_bleed_device(w2x_engine* e, const uint8_t* bgra, int rows, int cols, size_t bgra_step, uint8_t* bgr, size_t bgr_step, int radius);
 void* w2x_alloc_host(w2x_engine* e, size_t bytes);
 void w2x_free_host(w2x_engine* e, void* data);
 int w2x_pin_host(w2x_engine* e, void* data, size_t bytes);
@@ -151,6 +159,11 @@ int w2x_resize_weights(int in, int out, int filter, int* first, float* weights, 
 /* The planes of a packed YUV 4:2:0 frame of rows x cols at `bits` (8 or 10): plane_rows[k], plane_cols[k] (samples) and plane_bytes[k] = rows * cols *
  * bytes per sample, k = Y, U, V.  Returns 1; 0 (nothing written) for an empty frame or other depths.  Any output pointer may be NULL. */
 int w2x_yuv_plane_sizes(int rows, int cols, int bits, int* plane_rows, int* plane_cols, size_t* plane_bytes);
+/* The colour bleed on the host (tiles.h alpha_bleed): bgr rows x cols interleaved 8-bit BGR, alpha rows x cols bytes, radius in [0, 16]; out (not aliasing bgr)
+ * receives the frame with the colours of the pixels of alpha > 0 spread `radius` pixels outward under the pixels of alpha == 0: `radius` Jacobi iterations in
+ * which an unknown pixel with n > 0 known neighbours among its eight takes (their sum + (n >> 1)) / n per channel and becomes known.  1 on success, 0 (nothing
+ * written) for invalid arguments. */
+int w2x_alpha_bleed(const uint8_t* bgr, size_t bgr_step, const uint8_t* alpha, size_t alpha_step, int rows, int cols, int radius, uint8_t* out, size_t out_step);
 /* Lower an ONNX file at [batch,3,tile,tile] and write a textual description of the plan (ops, FLOPs) into buf. */
 int w2x_describe_plan(const char* onnx_path, int batch, int tile, char* buf, size_t cap);
 /* the same for any precision (W2X_PRECISION_FP16 / _TF32 / _FP32: the plan build() would write for that BuildConfig::precision; TF32 and FP32 share one) */

@@ -44,6 +44,10 @@ struct YuvFormat {
     YuvRange range = YuvRange::Limited;
 };
 
+// Extension: RGBA frames (renderRgba).  bleed: radius (0..16 pixels) over which the colours of the visible pixels (alpha > 0) are spread under
+// the transparent ones before the network sees the frame; skipUniformAlpha: a frame whose alpha plane is one value keeps it and runs no alpha tiles.
+struct RgbaOptions { int bleed = 0; bool skipUniformAlpha = false; };
+
 class Img2Img {
 public:
     Img2Img();
@@ -94,6 +98,13 @@ public:
     bool renderYuvResized(const YuvImage& src, YuvImage& dst, YuvFormat format, ResizeFilter filter = ResizeFilter::Bicubic);
     // renderSequenceYuv() with every frame resized like renderYuvResized() to dsts[i].rows x dsts[i].cols (one size and one pair of depths for the sequence)
     bool renderSequenceYuvResized(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, ResizeFilter filter = ResizeFilter::Bicubic);
+    // Extension: render() on 8-bit interleaved BGRA frames (CV_8UC4, what cv::imread(IMREAD_UNCHANGED) hands out; step >= cols * 4; dst rows*scaling x
+    // cols*scaling) in one call: one upload of 4 bytes per pixel, the colour bleed on the device, the frame's N colour tiles and N alpha tiles (the alpha plane
+    // as the gray image B = G = R = A) as ONE schedule of 2N tiles - colour first, cut into batches and passes like render()'s N, so the progress callback
+    // counts ceil(2N * steps / batchSize) batches -, one compose, one download of 4 bytes per output pixel.  Colour bytes: render() of alpha_bleed(BGR, A, bleed);
+    // alpha bytes: the green channel of render() of the gray image.  skipUniformAlpha and min(A) == max(A) == v: no alpha tiles, every output alpha is v, the
+    // progress total is the colour tiles' alone.  Other depths, empty images, short steps, other sizes, bleed outside [0, 16]: false (message callback).
+    bool renderRgba(const Image& src, Image& dst, const RgbaOptions& opt = {});
     void* allocHost(size_t bytes);
     void freeHost(void* data);
     // Page-locks caller-owned memory in place.  Only whole pages are accepted (data and bytes multiples of 4096): a registration
@@ -107,6 +118,8 @@ public:
     // Test hook mirroring the private trt::Img2Img::infer (img2img.h:25, img2img_infer.cpp:41-93):
     // host NCHW f32 blob [B,3,T,T] in [0,1] -> [B,3,T',T'] f32.
     bool infer(const float* input, float* output);
+    // Test hook: alpha_bleed_kernel alone - the BGRA frame up, the bleed at `radius`, the BGR frame gather would read down (bgr: rows x cols, step >= cols * 3)
+    bool alphaBleed(const Image& bgra, Image& bgr, int radius);
     int outputTileSize() const;
     int scaling() const;   // RenderConfig::scaling of the loaded configuration (0 before load)
     double planFlops() const;

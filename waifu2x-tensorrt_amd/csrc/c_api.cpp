@@ -199,6 +199,21 @@ int w2x_render_sequence_yuv_resized(w2x_engine* e, const void* const* src_planes
     }
     return e->engine.renderSequenceYuvResized(s.data(), d.data(), count, yuv_format(matrix, range), f) ? 1 : 0;
 }
+int w2x_render_rgba(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, size_t dst_step, int bleed, int skip_uniform_alpha) {
+    if (!e) return 0;
+    w2x::Image s; s.data = const_cast<uint8_t*>(src); s.rows = rows; s.cols = cols; s.step = src_step;
+    w2x::Image d; d.data = dst; d.step = dst_step;
+    const int sc = e->engine.scaling();
+    d.rows = rows * sc; d.cols = cols * sc;
+    w2x::RgbaOptions o; o.bleed = bleed; o.skipUniformAlpha = skip_uniform_alpha != 0;
+    return e->engine.renderRgba(s, d, o) ? 1 : 0;
+}
+int w2x_alpha_bleed_device(w2x_engine* e, const uint8_t* bgra, int rows, int cols, size_t bgra_step, uint8_t* bgr, size_t bgr_step, int radius) {
+    if (!e) return 0;
+    w2x::Image s; s.data = const_cast<uint8_t*>(bgra); s.rows = rows; s.cols = cols; s.step = bgra_step;
+    w2x::Image d; d.data = bgr; d.rows = rows; d.cols = cols; d.step = bgr_step;
+    return e->engine.alphaBleed(s, d, radius) ? 1 : 0;
+}
 void* w2x_alloc_host(w2x_engine* e, size_t bytes) { return e ? e->engine.allocHost(bytes) : nullptr; }
 void w2x_free_host(w2x_engine* e, void* data) { if (e) e->engine.freeHost(data); }
 int w2x_pin_host(w2x_engine* e, void* data, size_t bytes) { return e && e->engine.pinHost(data, bytes) ? 1 : 0; }
@@ -253,6 +268,10 @@ int w2x_yuv_plane_sizes(int rows, int cols, int bits, int* plane_rows, int* plan
         if (plane_bytes) plane_bytes[k] = (size_t)r * c * (bits > 8 ? 2 : 1);
     }
     return 1;
+}
+
+int w2x_alpha_bleed(const uint8_t* bgr, size_t bgr_step, const uint8_t* alpha, size_t alpha_step, int rows, int cols, int radius, uint8_t* out, size_t out_step) {
+    try { return w2x::alpha_bleed(bgr, bgr_step, alpha, alpha_step, rows, cols, radius, out, out_step) ? 1 : 0; } catch (...) { return 0; }
 }
 
 int w2x_resize_weights(int in, int out, int filter, int* first, float* weights, int cap) {

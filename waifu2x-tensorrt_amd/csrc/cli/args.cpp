@@ -72,6 +72,9 @@ std::string usage() {
            "      --colorspace TEXT       (extension) {bt601,bt709,bt2020}: videos read through ffmpeg stay YUV 4:2:0 at --pix_fmt\n"
            "                              (yuv420p or yuv420p10le) and are converted on the GPU; the output carries the colour tags\n"
            "      --color_range TEXT [tv] (extension) {tv,pc}: the range of the --colorspace frames\n"
+           "      --alpha-bleed INT [0]   (extension) 0..16: stills with an alpha channel: spread the colours of the visible pixels that many pixels under the\n"
+           "                              transparent ones before upscaling (no dark fringe on cut-outs); not with --deep\n"
+           "      --alpha-skip-uniform    (extension) a still whose alpha channel is one value (an opaque export) keeps it without running it through the network\n"
            "      --tta-mode TEXT [mean]  (extension) {mean,reference}: with --tta, `mean` averages the 8 augmentations; `reference`\n"
            "                              reproduces the bytes of the reference's accumulation (img2img_render.cpp:313-316); --tta-compat = reference\n"
            "  build                       Build model\n"
@@ -81,7 +84,7 @@ std::string usage() {
 Options parse(int argc, const char* const* argv) {
     Options o;
     std::vector<std::string> a(argv + 1, argv + argc);
-    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_outsize = false, seen_filter = false, seen_colorspace = false, seen_range = false;
+    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_outsize = false, seen_filter = false, seen_colorspace = false, seen_range = false, seen_bleed = false, seen_skip = false;
     auto value = [&](size_t& i) -> std::string {
         const std::string name = a[i];
         auto eq = name.find('=');
@@ -132,6 +135,8 @@ Options parse(int argc, const char* const* argv) {
             if (o.outsizeW <= 0 || o.outsizeH <= 0) throw std::runtime_error("--outsize: " + v + ": width and height must be positive");
             seen_outsize = true;
         }
+        else if (k == "--alpha-bleed") { o.alphaBleed = to_int(k, value(i)); seen_bleed = true; }
+        else if (k == "--alpha-skip-uniform") { o.alphaSkipUniform = true; seen_skip = true; }
         else if (k == "--resize-filter") { o.resizeFilter = value(i); std::transform(o.resizeFilter.begin(), o.resizeFilter.end(), o.resizeFilter.begin(), ::tolower); seen_filter = true; }
         else if (k == "--colorspace") { o.colorspace = value(i); std::transform(o.colorspace.begin(), o.colorspace.end(), o.colorspace.begin(), ::tolower); seen_colorspace = true; }
         else if (k == "--color_range") { o.colorRange = value(i); std::transform(o.colorRange.begin(), o.colorRange.end(), o.colorRange.begin(), ::tolower); seen_range = true; }
@@ -187,8 +192,13 @@ Options parse(int argc, const char* const* argv) {
             if (o.pixFmt != "yuv420p" && o.pixFmt != "yuv420p10le") throw std::runtime_error("--pix_fmt: with --colorspace one of {yuv420p,yuv420p10le}, got " + o.pixFmt);
             if (seen_outscale) throw std::runtime_error("--colorspace: not together with --outscale (a factor rarely gives the even sizes video wants: use --outsize WxH)");
         } else if (seen_range) throw std::runtime_error("--color_range: needs --colorspace");
-    } else if (seen_outscale || seen_outsize || seen_filter || seen_colorspace || seen_range)
-        throw std::runtime_error(std::string(seen_outscale ? "--outscale" : seen_outsize ? "--outsize" : seen_filter ? "--resize-filter" : seen_colorspace ? "--colorspace" : "--color_range") + ": only with render");
+        if (seen_bleed) {
+            if (!(o.alphaBleed >= 0 && o.alphaBleed <= 16)) throw std::runtime_error("--alpha-bleed: " + std::to_string(o.alphaBleed) + " not in [0, 16] (the radius in pixels)");
+            if (o.alphaBleed > 0 && o.deep) throw std::runtime_error("--alpha-bleed: not together with --deep (the bleed works on 8-bit colour; 16-bit stills keep the colours as stored)");
+        }
+    } else if (seen_outscale || seen_outsize || seen_filter || seen_colorspace || seen_range || seen_bleed || seen_skip)
+        throw std::runtime_error(std::string(seen_outscale ? "--outscale" : seen_outsize ? "--outsize" : seen_filter ? "--resize-filter" : seen_colorspace ? "--colorspace" : seen_range ? "--color_range" :
+                                             seen_bleed ? "--alpha-bleed" : "--alpha-skip-uniform") + ": only with render");
     // cross-checks, main.cpp:142-145
     if (o.model == "cunet/art" && o.scale == 4) throw std::runtime_error("cunet/art does not support scale factor 4.");
     if (o.noise == -1 && o.scale == 1) throw std::runtime_error("Noise level -1 does not support scale factor 1.");
@@ -238,6 +248,7 @@ std::string to_json(const Options& o) {
        << ", \"outscale\": " << (o.outscale > 0 ? std::to_string(o.outscale) : std::string("null")) << ", \"outsize\": " << (o.outsizeW > 0 ? "[" + std::to_string(o.outsizeW) + ", " + std::to_string(o.outsizeH) + "]" : std::string("null"))
        << ", \"resize_filter\": " << q(o.resizeFilter)
        << ", \"colorspace\": " << (o.colorspace.empty() ? std::string("null") : q(o.colorspace)) << ", \"color_range\": " << q(o.colorRange)
+       << ", \"alpha_bleed\": " << o.alphaBleed << ", \"alpha_skip_uniform\": " << (o.alphaSkipUniform ? "true" : "false")
        << ", \"codec\": " << q(o.codec) << ", \"pix_fmt\": " << q(o.pixFmt) << ", \"crf\": " << o.crf << ", \"inputs\": [";
     for (size_t i = 0; i < o.inputs.size(); ++i) os << (i ? ", " : "") << q(o.inputs[i]);
     os << "], \"model_path\": " << q(o.command == "convert" ? "" : model_path(o)) << ", \"suffix\": " << q(o.command == "convert" ? "" : output_suffix(o)) << ", \"outputs\": [";

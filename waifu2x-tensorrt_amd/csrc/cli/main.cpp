@@ -3,7 +3,8 @@
 //   w2x --model swin_unet/art --scale 4 --noise 3 --batchSize 4 --tileSize 256 render -i in.png -o outdir [--tta] [--blend 1/16]
 // Stills (.png / .ppm / .bmp) and uncompressed .avi files are read and written by the built-in codecs (imageio.h); other formats and
 // videos are piped through ffmpeg as raw bgr24 when ffmpeg/ffprobe are on PATH (videoio/capture.cpp:96-99, writer.cpp:24-33 do the same).
-// A PNG / BMP with an alpha channel keeps it: the alpha plane goes through the same engine as a gray image (upstream TODO, README.md:88).
+// A PNG / BMP with an alpha channel keeps it (upstream TODO, README.md:88): an 8-bit still on one device at the network's size goes through Img2Img::renderRgba
+// (colour and alpha in one call, --alpha-bleed / --alpha-skip-uniform); on the other routes the alpha plane goes through the same engine as a gray image.
 // Extension: --devices N drives N engines - a single image is split into tile-column strips (Img2Img::renderStrip), every engine
 // writing its own columns of the shared output buffer; a video is cut into chunks of frames that go round-robin to one persistent
 // worker thread per engine (renderSequence over that engine's page-locked buffers), with one reader and one in-order writer thread.
@@ -20,6 +21,7 @@
 #include <thread>
 
 #include "../../../include/w2x/img2img.h"
+#include "../tiles.h"
 #include "args.h"
 #include "imageio.h"
 
@@ -268,9 +270,28 @@ int main(int argc, char** argv) {
                     for (char k : oks) all = all && k;
                     return all;
                 };
-                const bool ok = render_still(src, dst);
-                if (!ok) return -1;
-                if (!in.alpha.empty()) {   // the alpha plane as a gray image through the same engine; its green channel is the new alpha
+                // an 8-bit still with alpha on one device at the network's size: colour and alpha in one renderRgba() call
+                const bool one_call = !in.alpha.empty() && !deep && o.devices == 1 && !resize;
+                if (one_call) {
+                    std::vector<uint8_t> bgra((size_t)in.rows * in.cols * 4), obgra((size_t)out.rows * out.cols * 4);
+                    for (size_t i = 0; i < in.alpha.size(); ++i) { bgra[4 * i] = in.bgr[3 * i]; bgra[4 * i + 1] = in.bgr[3 * i + 1]; bgra[4 * i + 2] = in.bgr[3 * i + 2]; bgra[4 * i + 3] = in.alpha[i]; }
+                    Image s4{bgra.data(), in.rows, in.cols, (size_t)in.cols * 4}, d4{obgra.data(), out.rows, out.cols, (size_t)out.cols * 4};
+                    RgbaOptions ro; ro.bleed = o.alphaBleed; ro.skipUniformAlpha = o.alphaSkipUniform;
+                    if (!engines[0]->renderRgba(s4, d4, ro)) return -1;
+                    out.alpha.resize((size_t)out.rows * out.cols);
+                    for (size_t i = 0; i < out.alpha.size(); ++i) { out.bgr[3 * i] = obgra[4 * i]; out.bgr[3 * i + 1] = obgra[4 * i + 1]; out.bgr[3 * i + 2] = obgra[4 * i + 2]; out.alpha[i] = obgra[4 * i + 3]; }
+                } else {
+                    // the two-call routes: --alpha-bleed spreads the visible colours on the host first (8-bit colour; the parser refuses it with --deep)
+                    std::vector<uint8_t> bled;
+                    if (!in.alpha.empty() && !deep && o.alphaBleed > 0) {
+                        bled.resize(in.bgr.size());
+                        if (!alpha_bleed(in.bgr.data(), (size_t)in.cols * 3, in.alpha.data(), (size_t)in.cols, in.rows, in.cols, o.alphaBleed, bled.data(), (size_t)in.cols * 3))
+                            throw std::runtime_error(file + ": --alpha-bleed " + std::to_string(o.alphaBleed) + " could not be applied");
+                        src.data = bled.data();
+                    }
+                    if (!render_still(src, dst)) return -1;
+                }
+                if (!in.alpha.empty() && !one_call) {   // the alpha plane as a gray image through the same engine; its green channel is the new alpha
                     cli::Bitmap ga, go;
                     // sized from the geometry: with --deep the colour planes live in bgr16 and in.bgr / out.bgr are empty
                     ga.rows = in.rows; ga.cols = in.cols; ga.bgr.resize((size_t)in.rows * in.cols * 3);

@@ -9,8 +9,10 @@
 //   w2x_parse_check avi   FILE                      AviReader::open + every frame
 //   w2x_parse_check args  ARGS...                   cli::parse
 //   w2x_parse_check tiles W H T S TOUT OVX OVY      calculate_tiles
+//   w2x_parse_check bleed FILE RADIUS               read_image, then alpha_bleed of its colour under its alpha plane (an opaque plane without one), padded rows
 // Exit code: 0 = accepted, 2 = rejected with a message on stderr (the clean `false` of the product path); anything else is a crash
 // or a sanitizer report.
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -27,7 +29,7 @@
 using namespace w2x;
 
 static int run(int argc, char** argv) {
-    if (argc < 3) throw std::runtime_error("usage: w2x_parse_check {onnx|plan|image|avi|args|tiles} ...");
+    if (argc < 3) throw std::runtime_error("usage: w2x_parse_check {onnx|plan|image|avi|args|tiles|bleed} ...");
     const std::string mode = argv[1];
     if (mode == "onnx") {
         if (argc < 5) throw std::runtime_error("onnx FILE BATCH TILE [fp32]");
@@ -66,6 +68,25 @@ static int run(int argc, char** argv) {
         const TileGrid g = calculate_tiles(W, H, W * S, H * S, T, T, TO, TO, S, atof(argv[7]), atof(argv[8]));
         for (int parts = 1; parts <= 8 && parts <= g.nx; ++parts) for (int p = 0; p < parts; ++p) (void)strip_plan(g, W * S, TO, p, parts);
         printf("ok: %d tiles (%d x %d)\n", g.count, g.nx, g.ny);
+    } else if (mode == "bleed") {
+        if (argc < 4) throw std::runtime_error("bleed FILE RADIUS");
+        const cli::Bitmap b = cli::read_image(argv[2]);
+        const int radius = atoi(argv[3]);
+        if (b.bgr.size() != (size_t)b.rows * b.cols * 3) throw std::runtime_error("not an 8-bit image");
+        // exact-size heap blocks with padded steps: a read or write past a row or the frame is a sanitizer report
+        const size_t cs = (size_t)b.cols * 3 + 5, as = (size_t)b.cols + 3;
+        std::vector<uint8_t> c(cs * b.rows), a(as * b.rows, 255), out(cs * b.rows, 0xEE);
+        for (int y = 0; y < b.rows; ++y) {
+            std::copy(b.bgr.begin() + (size_t)y * b.cols * 3, b.bgr.begin() + (size_t)(y + 1) * b.cols * 3, c.begin() + y * cs);
+            if (!b.alpha.empty()) std::copy(b.alpha.begin() + (size_t)y * b.cols, b.alpha.begin() + (size_t)(y + 1) * b.cols, a.begin() + y * as);
+        }
+        if (!alpha_bleed(c.data(), cs, a.data(), as, b.rows, b.cols, radius, out.data(), cs)) throw std::runtime_error("alpha_bleed refused " + std::to_string(b.cols) + "x" + std::to_string(b.rows) + " at radius " + std::to_string(radius));
+        size_t changed = 0;
+        for (int y = 0; y < b.rows; ++y) {
+            for (size_t x = 0; x < (size_t)b.cols * 3; ++x) changed += out[y * cs + x] != c[y * cs + x];
+            for (size_t x = (size_t)b.cols * 3; x < cs; ++x) if (out[y * cs + x] != 0xEE) throw std::runtime_error("alpha_bleed wrote into the row padding");
+        }
+        printf("ok: %d x %d at radius %d, %zu bytes changed\n", b.cols, b.rows, radius, changed);
     } else throw std::runtime_error("unknown mode " + mode);
     return 0;
 }

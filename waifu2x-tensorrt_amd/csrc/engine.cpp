@@ -286,6 +286,13 @@ struct Img2Img::Impl {
     // With `rs` set as well (renderYuvResized) the frame ends with compose_canvas_kernel and resample_yuv_kernel, and d_out holds planes of the target size.
     struct YuvJob { YuvCoefs in, out; int in_bits = 8, out_bits = 8, key = 0; };
     const YuvJob* yuv = nullptr;
+    // renderRgba(): d_frame holds the uploaded BGRA frame, alpha_bleed_kernel writes the BGR frame and the alpha plane the passes gather from (gather_rgba_kernel,
+    // `rgba` set for the duration of the call), d_minmax receives max(A) and max(255 - A), read back into the page-locked h_minmax behind the kernel
+    uint8_t* d_bgr = nullptr; size_t bgr_cap = 0;
+    uint8_t* d_alpha = nullptr; size_t alpha_cap = 0;
+    unsigned* d_minmax = nullptr; unsigned* h_minmax = nullptr;
+    hipEvent_t ev_minmax = nullptr;
+    bool rgba = false;
     std::vector<void*> pinned;
     std::vector<void*> host_allocs;     // allocHost(): page-locked buffers handed to the caller
     std::vector<TileSlot> h_slots;
@@ -342,6 +349,7 @@ struct Img2Img::Impl {
     // enqueueV3 (img2img_infer.cpp:80); here a pass is ~40 launches, which the host cannot issue fast enough for small tiles.
     // A pass is captured the second time it is met (the first run stays eager so that one-time attribute calls are out of the
     // way) and replayed from then on.  The key holds everything the captured launches bake in.
+    static constexpr int kRgbaKey = 64;   // (YuvJob::key stays below 32)
     using GraphKey = std::tuple<const void*, const void*, const void*, const void*, int, int, int, int>;   // frame, slots, slab out, arena, rows, cols, live, sample format (1: 16-bit, >= 2: YuvJob::key)
     // A pass that runs as NG tile groups is NG graphs, one per group, each a straight line of launches replayed on that group's OWN stream (fork / join
     // events between the streams are issued around the replays): a single captured graph with NG branches runs its side branches on streams the runtime
@@ -386,6 +394,10 @@ struct Img2Img::Impl {
         rs_tables.clear(); rs = nullptr;
         if (d_canvas) { (void)hipFree(d_canvas); d_canvas = nullptr; }
         canvas_cap = 0;
+        for (void** q : {(void**)&d_bgr, (void**)&d_alpha, (void**)&d_minmax}) if (*q) { (void)hipFree(*q); *q = nullptr; }
+        bgr_cap = alpha_cap = 0; rgba = false;
+        if (h_minmax) { if (hipHostFree(h_minmax) != hipSuccess) (void)hipGetLastError(); h_minmax = nullptr; }
+        if (ev_minmax) { (void)hipEventDestroy(ev_minmax); ev_minmax = nullptr; }
         for (void** p : {(void**)&d_frame, (void**)&d_out, (void**)&d_frame2, (void**)&d_out2, &d_slab, &d_slab2, (void**)&d_slots, (void**)&d_rampx, (void**)&d_rampy, (void**)&d_blob_in, (void**)&d_blob_out})
             if (*p) { (void)hipFree(*p); *p = nullptr; }
         frame_cap = out_cap = slab_cap = slab2_cap = slots_cap = 0;
@@ -936,7 +948,8 @@ struct Img2Img::Impl {
 
     // the network passes of `tile_count` tiles (slots d_slots[slots_off ..]); their outputs go to slab slots slab_slot0, slab_slot0 + 1, ...
     // fresh: the first passes of a frame (W2X_POISON wipes the arena and the slab here, not between the parts of a pipelined frame)
-    void run_passes(int rows, int cols, int tile_count, size_t slab_slot0, bool report, size_t slots_off, bool fresh, int batch0 = 0, int batch_total = 0) {
+    // pass0 / pass1: only the passes [pass0, pass1) of that schedule (pass1 < 0: to its end)
+    void run_passes(int rows, int cols, int tile_count, size_t slab_slot0, bool report, size_t slots_off, bool fresh, int batch0 = 0, int batch_total = 0, int pass0 = 0, int pass1 = -1) {
         const int B = plan.B, T = plan.T, To = plan.Tout;
         const int steps = cfg.tta ? 8 : 1;
         const int userB = plan.userB, S = B / userB;
@@ -949,7 +962,7 @@ struct Img2Img::Impl {
         }
         // (W2X_POISON fills the whole arena before the frame and so runs the default path: tile groups in their arena parts, replayed graphs)
         const bool graphable = use_graphs && !profiling && !check_general;
-        for (int bi = 0; bi < passCount; ++bi) {
+        for (int bi = pass0; bi < (pass1 < 0 ? passCount : std::min(pass1, passCount)); ++bi) {
             const auto t0 = std::chrono::steady_clock::now();
             const int live = std::max(0, std::min(B, tile_count * steps - bi * B));
             void* const slab_out = (uint8_t*)d_slab + (slab_slot0 + (size_t)bi * B) * slot_bytes;
@@ -975,6 +988,13 @@ struct Img2Img::Impl {
             }
             auto group_stream = [&](int grp) { return grp ? gstream[grp - 1] : stream; };
             auto gather = [&](const GatherParams& gp, hipStream_t gs) {
+                if (rgba) {                                           // an RGBA frame (renderRgba): the same tiles from the bled BGR frame or the alpha plane
+                    GatherRgbaParams rp;
+                    rp.bgr = d_bgr; rp.bgr_step = (size_t)cols * 3; rp.alpha = d_alpha; rp.alpha_step = (size_t)cols; rp.rows = rows; rp.cols = cols;
+                    rp.out = gp.out; rp.fp32 = gp.fp32; rp.slots = gp.slots; rp.B = gp.B; rp.T = gp.T;
+                    hipAssert(launch_gather_rgba(rp, gs));
+                    return;
+                }
                 if (!yuv) { hipAssert(launch_gather(gp, gs)); return; }
                 GatherYuvParams yp;                                   // a YUV frame (renderYuv): the same tiles from its planes
                 yp.src = yuv_layout(d_frame, rows, cols, yuv->in_bits); yp.k = yuv->in;
@@ -1013,7 +1033,7 @@ struct Img2Img::Impl {
             auto run_eager = [&] { if (per_group) { fork(); for (int grp = 0; grp < NG; ++grp) run_group(grp); if (!no_join) join(); } else { if (rolling && gstream[0]) { join(); } run_pass(); } };
             if (!graphable) run_eager();
             else {
-                const GraphKey key{d_frame, d_slots + slots_off + (size_t)bi * B, slab_out, arena_base, rows, cols, live, yuv ? yuv->key : deep ? 1 : 0};
+                const GraphKey key{d_frame, d_slots + slots_off + (size_t)bi * B, slab_out, arena_base, rows, cols, live, rgba ? kRgbaKey : yuv ? yuv->key : deep ? 1 : 0};
                 auto replay = [&](const PassGraphs& pg) {
                     if (pg.n == 1) { if (rolling && gstream[0]) join(); hipAssert(hipGraphLaunch(pg.g[0], stream)); return; }   // (a whole-arena pass inside a rolling sequence: the other stream's group first)
                     fork();
@@ -1111,6 +1131,35 @@ struct Img2Img::Impl {
         stamp_begin(4, 0);
         hipAssert(launch_compose_yuv(yp, on));
         stamp_end();
+    }
+    // RGBA frames (renderRgba / alphaBleed): the BGRA frame into d_frame, the two words zeroed, alpha_bleed_kernel -> d_bgr, d_alpha, d_minmax; all on `stream`
+    void upload_and_bleed(const Image& src, int radius) {
+        const int rows = src.rows, cols = src.cols;
+        ensure(d_frame, frame_cap, (size_t)rows * cols * 4);
+        ensure(d_bgr, bgr_cap, (size_t)rows * cols * 3);
+        ensure(d_alpha, alpha_cap, (size_t)rows * cols);
+        if (!d_minmax) hipAssert(hipMalloc((void**)&d_minmax, 2 * sizeof(unsigned)));
+        hipAssert(hipMemcpy2DAsync(d_frame, (size_t)cols * 4, src.data, src.step, (size_t)cols * 4, rows, hipMemcpyHostToDevice, stream));
+        hipAssert(hipMemsetAsync(d_minmax, 0, 2 * sizeof(unsigned), stream));
+        AlphaBleedParams bp;
+        bp.bgra = d_frame; bp.step = (size_t)cols * 4; bp.rows = rows; bp.cols = cols; bp.radius = radius;
+        bp.bgr = d_bgr; bp.bgr_step = (size_t)cols * 3; bp.alpha = d_alpha; bp.alpha_step = (size_t)cols; bp.minmax = d_minmax;
+        hipAssert(launch_alpha_bleed(bp, stream));
+    }
+    // the whole canvas of an RGBA frame as BGRA dwords into d_out: colour tiles from slab slot 0, alpha tiles from slot alpha_slot0 (uniform: none, A = value)
+    void compose_rgba(int rows, int cols, const TileGrid& grid, size_t alpha_slot0, bool uniform, unsigned value) {
+        const int To = plan.Tout;
+        ComposeRgbaParams rp;
+        ComposeParams& cp = rp.c;
+        cp.tiles = d_slab; cp.fp32 = plan.elt == 4; cp.dst = d_out; cp.dst_step = (size_t)cols * cfg.scaling * 4;
+        cp.outW = cols * cfg.scaling; cp.outH = rows * cfg.scaling; cp.To = To;
+        cp.nx = grid.nx; cp.ny = grid.ny; cp.stride_x = To - grid.outOvX; cp.stride_y = To - grid.outOvY;
+        const bool overlapping = cfg.overlapX != 0 || cfg.overlapY != 0;
+        cp.ovx = overlapping ? ovx : 0; cp.ovy = overlapping ? ovy : 0;
+        cp.ramp_x = d_rampx; cp.ramp_y = d_rampy; cp.tta = cfg.tta ? 1 : 0; cp.tta_bug_compat = cfg.ttaBugCompat ? 1 : 0;
+        rp.alpha_tiles = uniform ? nullptr : (const uint8_t*)d_slab + alpha_slot0 * (size_t)To * To * 4 * plan.elt;
+        rp.alpha_value = value;
+        hipAssert(launch_compose_rgba(rp, stream));
     }
     // the slot table and the slab of a sequence's frames (renderSequence / renderSequenceYuv): every tile of the frame, in one part
     void sequence_slots(const TileGrid& grid, const StripPlan& sp) {
@@ -2043,6 +2092,103 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
 } catch (const std::exception& e) {
     impl->drain_after_error();
     W2X_LOG_AS(who, error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
+    return false;
+}
+
+// RGBA frames.  One upload (4 bytes per pixel), alpha_bleed_kernel (the BGR frame with the visible colours spread under alpha == 0, the alpha plane, the
+// plane's range), ONE schedule of the frame's N colour tiles followed by its N alpha tiles - cut into reference batches and network passes as run_passes() cuts any
+// tile count, so a pass at the boundary holds tiles of both kinds -, compose_rgba_kernel, one download (4 bytes per output pixel).  A single part on the compute
+// stream: the multi-part overlap of render() is not used here.  skipUniformAlpha: the two words come back behind the bleed kernel while the passes that hold colour
+// tiles only - the same in the 2N and the N schedule - are issued; their progress is reported once the total is known.
+bool Img2Img::renderRgba(const Image& src, Image& dst, const RgbaOptions& opt) try {
+    const char* who = "renderRgba";
+    if (!impl->loaded) { W2X_LOG_AS(who, error, "Render called before a successful load."); return false; }
+    DeviceGuard guard(impl->device);
+    const RenderConfig& cfg = impl->cfg;
+    const Plan& plan = impl->plan;
+    const int rows = src.rows, cols = src.cols, s = cfg.scaling;
+    if (src.depth != 8 || dst.depth != 8) { W2X_LOG_AS(who, error, "RGBA input and output images must be 8-bit."); return false; }
+    if (!src.data || rows <= 0 || cols <= 0 || src.step < (size_t)cols * 4) { W2X_LOG_AS(who, error, "Input image is empty or has an invalid step."); return false; }
+    if (!dst.data || dst.rows != rows * s || dst.cols != cols * s || dst.step < (size_t)dst.cols * 4) {
+        W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(cols * s) + "x" + std::to_string(rows * s) + ".");
+        return false;
+    }
+    if (opt.bleed < 0 || opt.bleed > kBleedMaxRadius) { W2X_LOG_AS(who, error, "Alpha bleed radius " + std::to_string(opt.bleed) + " is not in [0, " + std::to_string(kBleedMaxRadius) + "]."); return false; }
+    hipStream_t stream = impl->stream;
+    TileGrid grid = calculate_tiles(cols, rows, cols * s, rows * s, plan.T, plan.T, plan.Tout, plan.Tout, s, cfg.overlapX, cfg.overlapY);
+    if (grid.count <= 0) { W2X_LOG_AS(who, error, "Tile grid is empty."); return false; }
+    for (const Rect& r : grid.out) if (r.w <= 0 || r.h <= 0) { W2X_LOG_AS(who, error, "Tile grid does not fit the output (scaling does not match the model)."); return false; }
+    const int steps = cfg.tta ? 8 : 1, B = plan.B, S = plan.B / plan.userB, N = grid.count;
+    auto batches_of = [&](int tiles) { return (int)std::lround(std::ceil((double)(tiles * steps) / plan.userB)); };   // img2img_render.cpp:249
+    const size_t stepTotal = (size_t)((batches_of(2 * N) + S - 1) / S) * B;
+    struct RgbaScope { Impl* im; ~RgbaScope() { im->rgba = false; } } rgba_scope{impl.get()};   // also on exceptions
+    impl->deep = false;
+    impl->last_rows = impl->last_cols = 0;   // (d_frame / d_out hold BGRA from here on: not replayed by benchResident / residentOutput / profileFrame)
+    impl->ensure(impl->d_out, impl->out_cap, (size_t)dst.rows * dst.cols * 4);
+    impl->upload_and_bleed(src, opt.bleed);
+    if (opt.skipUniformAlpha) {
+        if (!impl->h_minmax) hipAssert(hipHostMalloc((void**)&impl->h_minmax, 2 * sizeof(unsigned), hipHostMallocDefault));
+        if (!impl->ev_minmax) hipAssert(hipEventCreateWithFlags(&impl->ev_minmax, hipEventDisableTiming));
+        hipAssert(hipMemcpyAsync(impl->h_minmax, impl->d_minmax, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+        hipAssert(hipEventRecord(impl->ev_minmax, stream));
+    }
+    // the schedule: slot = step index, tile = step / stepsPerTile over the 2N tiles (colour 0 .. N - 1, alpha N .. 2N - 1), zero pad slots at the end
+    impl->h_slots.resize(stepTotal);
+    for (size_t st = 0; st < stepTotal; ++st) {
+        const int ti = (int)(st / steps), aug = (int)(st % steps);
+        TileSlot sl{0, 0, aug, 0};
+        if (ti < 2 * N) { sl.x = grid.in[ti % N].x; sl.y = grid.in[ti % N].y; sl.valid = ti < N ? kSlotColour : kSlotAlpha; }
+        impl->h_slots[st] = sl;
+    }
+    impl->ensure(impl->d_slots, impl->slots_cap, stepTotal * sizeof(TileSlot));
+    hipAssert(hipMemcpyAsync(impl->d_slots, impl->h_slots.data(), stepTotal * sizeof(TileSlot), hipMemcpyHostToDevice, stream));
+    impl->ensure(impl->d_slab, impl->slab_cap, stepTotal * plan.Tout * plan.Tout * 4 * plan.elt);
+    impl->one_part_stale = false;
+    hipAssert(hipEventRecord(impl->ev0, stream));
+    impl->rgba = true;
+    bool uniform = false; unsigned value = 255;
+    if (!opt.skipUniformAlpha) impl->run_passes(rows, cols, 2 * N, 0, true, 0, true);
+    else {
+        const int F = N * steps / B;                 // passes of colour tiles only: the same launches whether the alpha tiles follow or not
+        const auto t0 = std::chrono::steady_clock::now();
+        impl->run_passes(rows, cols, 2 * N, 0, false, 0, true, 0, 0, 0, F);
+        hipAssert(hipEventSynchronize(impl->ev_minmax));
+        uniform = impl->h_minmax[0] + impl->h_minmax[1] == 255u;      // max(A) + max(255 - A) == 255  <=>  min(A) == max(A)
+        value = impl->h_minmax[0];
+        const int tiles = uniform ? N : 2 * N, batchCount = batches_of(tiles);
+        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+        for (int k = 0; k < std::min(F * S, batchCount); ++k) impl->log(k + 1, batchCount, 1000.0 * F * S / std::max(ms, 1e-6));
+        impl->run_passes(rows, cols, tiles, 0, true, 0, false, 0, 0, F, -1);
+    }
+    impl->compose_rgba(rows, cols, grid, (size_t)N * steps, uniform, value);
+    hipAssert(hipEventRecord(impl->ev1, stream));
+    hipAssert(hipMemcpy2DAsync(dst.data, dst.step, impl->d_out, (size_t)dst.cols * 4, (size_t)dst.cols * 4, dst.rows, hipMemcpyDeviceToHost, stream));
+    hipAssert(hipStreamSynchronize(stream));
+    hipAssert(hipEventElapsedTime(&impl->last_ms, impl->ev0, impl->ev1));
+    return true;
+} catch (const std::exception& e) {
+    impl->drain_after_error();
+    W2X_LOG_AS("renderRgba", error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
+    return false;
+}
+
+bool Img2Img::alphaBleed(const Image& bgra, Image& bgr, int radius) try {
+    const char* who = "alphaBleed";
+    if (!impl->loaded) { W2X_LOG_AS(who, error, "Alpha bleed called before a successful load."); return false; }
+    DeviceGuard guard(impl->device);
+    const int rows = bgra.rows, cols = bgra.cols;
+    if (bgra.depth != 8 || bgr.depth != 8) { W2X_LOG_AS(who, error, "RGBA input and output images must be 8-bit."); return false; }
+    if (!bgra.data || rows <= 0 || cols <= 0 || bgra.step < (size_t)cols * 4) { W2X_LOG_AS(who, error, "Input image is empty or has an invalid step."); return false; }
+    if (!bgr.data || bgr.rows != rows || bgr.cols != cols || bgr.step < (size_t)cols * 3) { W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(cols) + "x" + std::to_string(rows) + "."); return false; }
+    if (radius < 0 || radius > kBleedMaxRadius) { W2X_LOG_AS(who, error, "Alpha bleed radius " + std::to_string(radius) + " is not in [0, " + std::to_string(kBleedMaxRadius) + "]."); return false; }
+    impl->last_rows = impl->last_cols = 0;   // (d_frame is overwritten: the last render() frame is no longer there to replay)
+    impl->upload_and_bleed(bgra, radius);
+    hipAssert(hipMemcpy2DAsync(bgr.data, bgr.step, impl->d_bgr, (size_t)cols * 3, (size_t)cols * 3, rows, hipMemcpyDeviceToHost, impl->stream));
+    hipAssert(hipStreamSynchronize(impl->stream));
+    return true;
+} catch (const std::exception& e) {
+    impl->drain_after_error();
+    W2X_LOG_AS("alphaBleed", error, "Alpha bleed failed unexpectedly: " + std::string(e.what()) + ".");
     return false;
 }
 

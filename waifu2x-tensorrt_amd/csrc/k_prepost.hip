@@ -12,44 +12,10 @@
 //             folded into the tile reads and the canvas writes.
 //   se/scale: cunet squeeze-excite gate and channel scaling.
 #include "kernels.h"
+#include "prepost_device.h"
 
 namespace w2x {
 namespace {
-
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-// a tile pixel is four stored channels (r, g, b, 0) in the plan's precision: half4 (fp16 engines) or float4v (fp32 engines)
-template <typename P> __device__ __forceinline__ P make_px(float r, float g, float b);
-template <> __device__ __forceinline__ half4 make_px<half4>(float r, float g, float b) { return (half4){(_Float16)r, (_Float16)g, (_Float16)b, (_Float16)0.f}; }
-template <> __device__ __forceinline__ float4v make_px<float4v>(float r, float g, float b) { return (float4v){r, g, b, 0.f}; }
-
-// source coordinate inside the un-augmented tile for pixel (y,x) of the augmented tile (applyAugmentation)
-__device__ __forceinline__ void aug_src(int k, int n, int y, int x, int& sy, int& sx) {
-    switch (k) {
-        default: sy = y; sx = x; break;
-        case 1: sy = n - y; sx = x; break;          // flip code 0
-        case 2: sy = y; sx = n - x; break;          // flip code 1
-        case 3: sy = x; sx = n - y; break;          // rot90
-        case 4: sy = n - y; sx = n - x; break;      // rot180
-        case 5: sy = n - x; sx = y; break;          // rot270
-        case 6: sy = n - x; sx = n - y; break;      // flip0 then rot90
-        case 7: sy = x; sx = y; break;              // flip1 then rot90
-    }
-}
-// source coordinate inside the network output for pixel (y,x) of the de-augmented tile (reverseAugmentation)
-__device__ __forceinline__ void deaug_src(int k, int n, int y, int x, int& sy, int& sx) {
-    switch (k) {
-        default: sy = y; sx = x; break;
-        case 1: sy = n - y; sx = x; break;
-        case 2: sy = y; sx = n - x; break;
-        case 3: sy = n - x; sx = y; break;          // rot270
-        case 4: sy = n - y; sx = n - x; break;
-        case 5: sy = x; sx = n - y; break;          // rot90
-        case 6: sy = n - x; sx = n - y; break;      // rot270 then flip0
-        case 7: sy = x; sx = y; break;              // rot270 then flip1
-    }
-}
 
 template <typename P>
 __global__ __launch_bounds__(256) void gather_kernel(const GatherParams p) {
@@ -79,59 +45,6 @@ __global__ __launch_bounds__(256) void gather_kernel(const GatherParams p) {
     }
 }
 
-// One output pixel: the covering tiles in ascending tile index (img2img_render.cpp:329-330), ramp weights L, T, R, B in that order on
-// the clipped rect (:110-120), fp32 sums, then rint(x * 255) saturated (:342), RGB -> BGR (:343).  Returns b | g << 8 | r << 16.
-__device__ __forceinline__ unsigned quantize_bgr(float r, float g, float b) {
-    const unsigned B = (unsigned)min(max(__float2int_rn(b * 255.f), 0), 255), G = (unsigned)min(max(__float2int_rn(g * 255.f), 0), 255),
-                   R = (unsigned)min(max(__float2int_rn(r * 255.f), 0), 255);
-    return B | G << 8 | R << 16;
-}
-template <typename P>
-__device__ __forceinline__ void compose_pixel_sums(const ComposeParams& p, const P* tiles, int X, int Y, float& r0, float& r1, float& r2) {
-    const int To = p.To, n = To - 1;
-    const int steps = p.tta ? 8 : 1;
-    // candidate tile columns/rows: origin = idx*stride, extent To (clipped to the canvas)
-    int i0 = X - To + 1; i0 = i0 <= 0 ? 0 : (i0 + p.stride_x - 1) / p.stride_x;
-    int i1 = min(p.nx - 1, X / p.stride_x);
-    int j0 = Y - To + 1; j0 = j0 <= 0 ? 0 : (j0 + p.stride_y - 1) / p.stride_y;
-    int j1 = min(p.ny - 1, Y / p.stride_y);
-    float acc0 = 0.f, acc1 = 0.f, acc2 = 0.f;
-    for (int ti = i0; ti <= i1; ++ti) {
-        const int ox = ti * p.stride_x, lx = X - ox;
-        const int rw = ox + To > p.outW ? p.outW - ox : To;
-        for (int tj = j0; tj <= j1; ++tj) {
-            const int oy = tj * p.stride_y, ly = Y - oy;
-            const int rh = oy + To > p.outH ? p.outH - oy : To;
-            const long tile = (long)ti * p.ny + tj - p.first_tile;
-            const P* tp = tiles + tile * steps * (long)To * To;
-            float v0, v1, v2;
-            if (!p.tta) {
-                const P h = tp[(long)ly * To + lx];
-                v0 = (float)h[0]; v1 = (float)h[1]; v2 = (float)h[2];
-            } else {
-                float s0 = 0.f, s1 = 0.f, s2 = 0.f;
-                P h;
-#pragma unroll
-                for (int k = 0; k < 8; ++k) {
-                    int sy, sx;
-                    deaug_src(k, n, ly, lx, sy, sx);
-                    h = tp[(long)k * To * To + (long)sy * To + sx];
-                    s0 += (float)h[0]; s1 += (float)h[1]; s2 += (float)h[2];
-                }
-                if (p.tta_bug_compat) { v0 = (float)h[0]; v1 = (float)h[1]; v2 = (float)h[2]; }
-                else { v0 = s0 * 0.125f; v1 = s1 * 0.125f; v2 = s2 * 0.125f; }
-            }
-            if (p.ovx || p.ovy) {
-                if (ox > 0 && lx < p.ovx) { float w = p.ramp_x[lx]; v0 *= w; v1 *= w; v2 *= w; }
-                if (oy > 0 && ly < p.ovy) { float w = p.ramp_y[ly]; v0 *= w; v1 *= w; v2 *= w; }
-                if (ox + rw < p.outW && n - lx < p.ovx) { float w = p.ramp_x[n - lx]; v0 *= w; v1 *= w; v2 *= w; }
-                if (oy + rh < p.outH && n - ly < p.ovy) { float w = p.ramp_y[n - ly]; v0 *= w; v1 *= w; v2 *= w; }
-            }
-            acc0 += v0; acc1 += v1; acc2 += v2;
-        }
-    }
-    r0 = acc0; r1 = acc1; r2 = acc2;
-}
 template <typename P>
 __device__ __forceinline__ unsigned compose_pixel(const ComposeParams& p, const P* tiles, int X, int Y) {
     float a0, a1, a2;

@@ -290,6 +290,40 @@ struct ComposeYuvParams {
 };
 constexpr int kYuvSites = 4, kYuvThreads = 64;   // chroma sites (8 luma columns, 2 rows) per thread, threads per workgroup (one wave)
 hipError_t launch_compose_yuv(const ComposeYuvParams& p, hipStream_t s);
+// RGBA frames (renderRgba; k_rgba.hip).
+// alpha_bleed_kernel: the uploaded BGRA frame split into the BGR frame gather reads and the alpha plane, with the colour of every pixel of alpha > 0
+// spread `radius` pixels (0..16) outward under the pixels of alpha == 0 (tiles.h alpha_bleed states the arithmetic), all iterations in one launch.
+// minmax: two device words the launch reduces max(A) and max(255 - A) into with vector atomics (the caller zeroes them first).
+struct AlphaBleedParams {
+    const uint8_t* bgra = nullptr; size_t step = 0; int rows = 0, cols = 0;   // u8 BGRA interleaved, rows 4-byte aligned
+    int radius = 0;
+    uint8_t* bgr = nullptr; size_t bgr_step = 0;                              // out: u8 BGR interleaved
+    uint8_t* alpha = nullptr; size_t alpha_step = 0;                          // out: u8 plane
+    unsigned* minmax = nullptr;
+};
+constexpr int kBleedTileW = 64, kBleedTileH = 32, kBleedMaxRadius = 16;
+hipError_t launch_alpha_bleed(const AlphaBleedParams& p, hipStream_t s);
+// gather_rgba_kernel: gather_kernel on the two planes of an RGBA frame.  A slot of this table says which plane it reads in `valid`: 1 the BGR frame
+// (exactly gather_kernel), 2 the alpha plane as the gray pixel (a, a, a, 0), a = u8 * fl32(1/255); 0 stays the zero-pad slot.
+struct GatherRgbaParams {
+    const uint8_t* bgr = nullptr; size_t bgr_step = 0;
+    const uint8_t* alpha = nullptr; size_t alpha_step = 0;
+    int rows = 0, cols = 0;
+    void* out = nullptr; int fp32 = 0;
+    const TileSlot* slots = nullptr;
+    int B = 0, T = 0;
+};
+constexpr int kSlotColour = 1, kSlotAlpha = 2;
+hipError_t launch_gather_rgba(const GatherRgbaParams& p, hipStream_t s);
+// compose_rgba_kernel: compose_pixel_sums over the colour tiles (c.tiles) quantised to B, G, R, and over the alpha tiles (alpha_tiles, the same grid, slot 0 =
+// tile 0) whose green sum quantised the same way is A; one dword B | G << 8 | R << 16 | A << 24 per pixel into c.dst (c.dst_step bytes per row, 4-byte
+// aligned).  alpha_tiles == nullptr: A = alpha_value everywhere (a uniform plane whose tiles were not run).
+struct ComposeRgbaParams {
+    ComposeParams c;
+    const void* alpha_tiles = nullptr;
+    unsigned alpha_value = 255;
+};
+hipError_t launch_compose_rgba(const ComposeRgbaParams& p, hipStream_t s);
 // k_resample.hip resample_yuv_kernel: resample_kernel's resize of the fp32 RGB canvas (same tap tables, same rows_max) with compose_yuv_kernel's
 // encoding behind it instead of the BGR quantisation: the resized R, G, B clamped to [0, 1] and written as YUV 4:2:0 planes of outH x outW
 // (dst.rows x dst.cols), Y per pixel, Cb / Cr of the RGB filtered (1/4, 1/2, 1/4) x (1/2, 1/2) onto each chroma site (renderYuvResized)

@@ -2,6 +2,7 @@
 
 #include <algorithm>
 #include <cmath>
+#include <cstring>
 
 namespace w2x {
 
@@ -150,6 +151,43 @@ ResizeTaps resize_taps(int in, int out, int filter) {
         for (long k = 0; k < n; ++k) t.w[(size_t)i * t.taps + k] = (float)(total != 0.0 ? w[k] / total : w[k]);
     }
     return t;
+}
+
+bool alpha_bleed(const uint8_t* bgr, size_t bgr_step, const uint8_t* alpha, size_t alpha_step, int rows, int cols, int radius, uint8_t* out, size_t out_step) {
+    if (!bgr || !alpha || !out || rows <= 0 || cols <= 0 || radius < 0 || radius > 16) return false;
+    if (bgr_step < (size_t)cols * 3 || out_step < (size_t)cols * 3 || alpha_step < (size_t)cols) return false;
+    const size_t n_px = (size_t)rows * cols;
+    std::vector<uint8_t> col(n_px * 3), col2, known(n_px), known2;
+    for (int y = 0; y < rows; ++y) {
+        memcpy(&col[(size_t)y * cols * 3], bgr + (size_t)y * bgr_step, (size_t)cols * 3);
+        for (int x = 0; x < cols; ++x) known[(size_t)y * cols + x] = alpha[(size_t)y * alpha_step + x] > 0;
+    }
+    for (int it = 1; it <= radius; ++it) {
+        col2 = col; known2 = known;                    // state it starts as state it - 1; only pixels that become known change
+        bool changed = false;
+        for (int y = 0; y < rows; ++y)
+            for (int x = 0; x < cols; ++x) {
+                const size_t i = (size_t)y * cols + x;
+                if (known[i]) continue;
+                unsigned n = 0, sum[3] = {0, 0, 0};
+                for (int dy = -1; dy <= 1; ++dy)
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        const int yy = y + dy, xx = x + dx;
+                        if ((dy == 0 && dx == 0) || yy < 0 || yy >= rows || xx < 0 || xx >= cols) continue;
+                        const size_t q = (size_t)yy * cols + xx;
+                        if (!known[q]) continue;
+                        ++n;
+                        for (int ch = 0; ch < 3; ++ch) sum[ch] += col[q * 3 + ch];
+                    }
+                if (!n) continue;
+                for (int ch = 0; ch < 3; ++ch) col2[i * 3 + ch] = (uint8_t)((sum[ch] + (n >> 1)) / n);
+                known2[i] = 1; changed = true;
+            }
+        if (!changed) break;                           // nothing left to reach: the later states are this one
+        col.swap(col2); known.swap(known2);
+    }
+    for (int y = 0; y < rows; ++y) memcpy(out + (size_t)y * out_step, &col[(size_t)y * cols * 3], (size_t)cols * 3);
+    return true;
 }
 
 }  // namespace w2x

@@ -1,6 +1,8 @@
 // Host-side tile geometry: bit-exact restatement of calculateTiles / createTileWeights
 // (/root/reference/src/tensorrt/img2img_render.cpp:7-66, img2img_load.cpp:29-52, 262-265).
 #pragma once
+#include <cstddef>
+#include <cstdint>
 #include <vector>
 
 namespace w2x {
@@ -54,5 +56,12 @@ std::vector<float> tile_weight_mask(int which, int ovx, int ovy, int size);
 // its k-th weight (zero past the taps output i has).  filter: 0 bicubic, 1 bilinear.  taps = 0 for invalid arguments.
 struct ResizeTaps { int taps = 0; std::vector<int> first; std::vector<float> w; };
 ResizeTaps resize_taps(int in, int out, int filter);
+
+// Colour bleed under transparent pixels (RGBA frames), integer and exact.  bgr: rows x cols interleaved 8-bit BGR, alpha: rows x cols
+// bytes, radius R in [0, 16].  known_0(p) = alpha(p) > 0, col_0 = bgr.  Iteration it = 1..R reads state it - 1 and writes state it (Jacobi): a pixel unknown in
+// state it - 1 with n > 0 neighbours among its eight that lie inside the frame and are known in state it - 1 takes, per channel, (their sum + (n >> 1)) / n
+// and becomes known; every other pixel keeps colour and flag.  out = col_R (a pixel still unknown keeps its colour; R = 0, an all-zero and an all-non-zero
+// plane leave the frame unchanged; a known pixel never changes).  out may not alias bgr.  false (nothing written) for invalid arguments.
+bool alpha_bleed(const uint8_t* bgr, size_t bgr_step, const uint8_t* alpha, size_t alpha_step, int rows, int cols, int radius, uint8_t* out, size_t out_step);
 
 }  // namespace w2x

@@ -148,6 +148,9 @@ def lib():
     L.w2x_render_sequence_yuv.restype = C.c_int
     L.w2x_render_yuv_resized.argtypes = L.w2x_render_yuv.argtypes + [C.c_int]; L.w2x_render_yuv_resized.restype = C.c_int
     L.w2x_render_sequence_yuv_resized.argtypes = L.w2x_render_sequence_yuv.argtypes + [C.c_int]; L.w2x_render_sequence_yuv_resized.restype = C.c_int
+    L.w2x_render_rgba.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]; L.w2x_render_rgba.restype = C.c_int
+    L.w2x_alpha_bleed_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int]; L.w2x_alpha_bleed_device.restype = C.c_int
+    L.w2x_alpha_bleed.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t]; L.w2x_alpha_bleed.restype = C.c_int
     L.w2x_yuv_plane_sizes.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp]; L.w2x_yuv_plane_sizes.restype = C.c_int
     L.w2x_render_strip.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]; L.w2x_render_strip.restype = C.c_int
     L.w2x_render_sequence.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int]; L.w2x_render_sequence.restype = C.c_int
@@ -192,6 +195,7 @@ EXPORTED_SYMBOLS = [
     "w2x_render", "w2x_render16", "w2x_infer", "w2x_output_tile_size", "w2x_plan_flops", "w2x_pass_tiles", "w2x_last_render_ms", "w2x_bench_resident", "w2x_resident_output", "w2x_profile_frame", "w2x_op_times",
     "w2x_render_resized", "w2x_render16_resized", "w2x_render_sequence_resized", "w2x_resize_weights",
     "w2x_render_yuv", "w2x_render_sequence_yuv", "w2x_yuv_plane_sizes", "w2x_render_yuv_resized", "w2x_render_sequence_yuv_resized",
+    "w2x_render_rgba", "w2x_alpha_bleed_device", "w2x_alpha_bleed",
     "w2x_render_strip", "w2x_strip_plan", "w2x_render_sharded", "w2x_shard_plan", "w2x_shard_compute", "w2x_shard_slab", "w2x_shard_finish", "w2x_ipc_export", "w2x_ipc_open", "w2x_ipc_close", "w2x_render_sequence", "w2x_alloc_host", "w2x_free_host", "w2x_pin_host", "w2x_unpin_host", "w2x_calculate_tiles", "w2x_tile_weights", "w2x_describe_plan", "w2x_describe_plan_precision", "w2x_write_engine_file", "w2x_validate_engine_file", "w2x_device_pci_bus_id", "w2x_sha256_hex", "w2x_version", "w2x_debug_set"]
 
 
@@ -276,6 +280,46 @@ class Img2Img:
                 raise W2xError(self.last_error() or "render failed")
             return dst
         return ok
+
+    def render_rgba(self, bgra: np.ndarray, *, bleed: int = 0, skip_uniform_alpha: bool = False, dst: np.ndarray | None = None):
+        """render() on a uint8 [rows, cols, 4] BGRA frame in one call (w2x_render_rgba): the colours of the pixels with alpha > 0 are spread `bleed` pixels
+        (0..16) under the transparent ones, colour and alpha tiles share one schedule; skip_uniform_alpha: a frame whose alpha plane is one value keeps it
+        and runs no alpha tiles.  Rows may be padded (strides[0] >= cols * 4).  With dst=None returns the [rows * s, cols * s, 4] array or raises; with dst
+        returns a bool."""
+        ret_array = dst is None
+        s = getattr(self, "_scaling", 0)
+        ok = isinstance(bgra, np.ndarray) and bgra.ndim == 3 and bgra.shape[2] == 4
+        if ok and bgra.dtype != np.uint8:
+            # the C ABI carries no sample depth: deeper frames are refused here, with the engine's message
+            self._on_msg(int(Severity.error), b"[renderRgba@0] RGBA input and output images must be 8-bit.", None)
+            if ret_array:
+                raise W2xError(self.last_error())
+            return False
+        if not ok or bgra.strides[2] != 1 or bgra.strides[1] != 4:
+            raise ValueError("bgra must be a uint8 [rows, cols, 4] BGRA array with packed pixels")
+        if dst is None:
+            dst = np.empty((bgra.shape[0] * s, bgra.shape[1] * s, 4), np.uint8)
+        if s and (dst.dtype != np.uint8 or dst.shape != (bgra.shape[0] * s, bgra.shape[1] * s, 4) or dst.strides[2] != 1 or dst.strides[1] != 4):
+            # the C ABI only sees pointers and steps, so the cv::Mat-style size check lives here
+            self._on_msg(int(Severity.error), f"[renderRgba@0] Output image has invalid size: expected {bgra.shape[1] * s}x{bgra.shape[0] * s}.".encode(), None)
+            return False
+        ok = bool(self._L.w2x_render_rgba(self._h, bgra.ctypes.data if bgra.size else None, bgra.shape[0], bgra.shape[1], bgra.strides[0],
+                                          dst.ctypes.data if dst.size else None, dst.strides[0], int(bleed), 1 if skip_uniform_alpha else 0))
+        if ret_array:
+            if not ok:
+                raise W2xError(self.last_error() or "render_rgba failed")
+            return dst
+        return ok
+
+    def alpha_bleed_device(self, bgra: np.ndarray, radius: int) -> np.ndarray:
+        """Test hook (w2x_alpha_bleed_device): the device bleed alone on a uint8 [rows, cols, 4] BGRA frame -> the [rows, cols, 3] BGR frame the tiles are read from"""
+        if bgra.dtype != np.uint8 or bgra.ndim != 3 or bgra.shape[2] != 4 or bgra.strides[2] != 1 or bgra.strides[1] != 4:
+            raise ValueError("bgra must be a uint8 [rows, cols, 4] BGRA array with packed pixels")
+        out = np.empty((bgra.shape[0], bgra.shape[1], 3), np.uint8)
+        if not self._L.w2x_alpha_bleed_device(self._h, bgra.ctypes.data if bgra.size else None, bgra.shape[0], bgra.shape[1], bgra.strides[0],
+                                              out.ctypes.data if out.size else None, out.strides[0], int(radius)):
+            raise W2xError(self.last_error() or "alpha_bleed_device failed")
+        return out
 
     def render_resized(self, src: np.ndarray, size, filter: str = "bicubic", dst: np.ndarray | None = None):
         """render() followed by an antialiased resize on the device to size = (rows, cols), each in [input dim, input dim * scaling]
@@ -698,6 +742,20 @@ def resize_weights(in_size: int, out_size: int, filter: str = "bicubic"):
     if L.w2x_resize_weights(int(in_size), int(out_size), fid, first.ctypes.data, w.ctypes.data, w.size) != taps:
         raise W2xError("w2x_resize_weights failed")
     return first, w
+
+
+def alpha_bleed(bgr: np.ndarray, alpha: np.ndarray, radius: int) -> np.ndarray:
+    """The colour bleed of the RGBA renders on the host (w2x_alpha_bleed): bgr uint8 [rows, cols, 3], alpha uint8 [rows, cols], radius 0..16 -> the frame with
+    the colours of the pixels of alpha > 0 spread `radius` pixels outward under the pixels of alpha == 0; raises for invalid arguments"""
+    if bgr.dtype != np.uint8 or bgr.ndim != 3 or bgr.shape[2] != 3 or (bgr.size and (bgr.strides[2] != 1 or bgr.strides[1] != 3)):
+        raise ValueError("bgr must be a uint8 [rows, cols, 3] array with packed pixels")
+    if alpha.dtype != np.uint8 or alpha.shape != bgr.shape[:2] or (alpha.size and alpha.strides[1] != 1):
+        raise ValueError("alpha must be a uint8 [rows, cols] array of the frame's size with packed rows")
+    out = np.empty(bgr.shape, np.uint8)
+    if not lib().w2x_alpha_bleed(bgr.ctypes.data if bgr.size else None, bgr.strides[0], alpha.ctypes.data if alpha.size else None, alpha.strides[0],
+                                 bgr.shape[0], bgr.shape[1], int(radius), out.ctypes.data if out.size else None, out.strides[0]):
+        raise W2xError(f"invalid alpha bleed: a {bgr.shape[1]}x{bgr.shape[0]} frame at radius {radius}")
+    return out
 
 
 def yuv_plane_sizes(rows: int, cols: int, bits: int):
