@@ -173,6 +173,17 @@ int w2x_describe_plan_precision(const char* onnx_path, int batch, int tile, int 
  * engine"), writing "ok" or the reason into buf. */
 int w2x_write_engine_file(const char* onnx_path, int batch, int tile, const char* out_path);
 int w2x_validate_engine_file(const char* path, char* buf, size_t cap);
+/* Dead-skip extents (csrc/liveness.h), host only: lower the ONNX file at [batch,3,tile,tile] (fp16) and report, for tile `tile_index` (column-major,
+ * w2x_calculate_tiles order) of an in_w x in_h frame, the part of every plan op's row map that some kept output pixel of that tile depends on.  A launch that
+ * computes several plan ops (the stem, the image head) takes its LAST op's entry.  tile_index < 0 (w2x_infer: tile outputs consumed whole) and tta != 0: "all".
+ * Per op W2X_EXTENT_INTS ints: 0 op kind (0 gemm, 4 mlp, 5 window attention), 1-2 row map W, H, 3-6 cx, wx, cy, wy - the live columns are [0, cx) U [W - wx, W),
+ * the live rows [0, cy) U [H - wy, H), all: cx = W, wx = 0, cy = H, wy = 0 - 7-9 attention roll rx, ry and window size (else -1, -1, 0), 10-12 the tensors the
+ * op reads, writes and adds as a residual (-1: none), 13-15 convolution kh, kw, stride (else 1), 16-17 origin x0, y0 of the input view in its tensor, 18 the
+ * pixel-shuffle factor r (the row map is the INPUT token map; else 1), 19-22 W, H of the read and the written tensor, 23-24 live and total units of the launch
+ * (windows for attention, rows otherwise).  Returns the op count; -count when cap < count * W2X_EXTENT_INTS (nothing written); 0 on error. */
+enum { W2X_EXTENT_INTS = 25 };
+int w2x_dead_skip_extents(const char* onnx_path, int batch, int tile, int in_w, int in_h, int scaling, double overlap_x, double overlap_y, int tile_index, int tta,
+                          int* out, int cap);
 /* PCI bus id ("0000:c1:00.0") of HIP device `device` of this process (after W2X_DEVICE_MAP), for callers that place their host threads and
  * page-locked buffers on the GPU's NUMA node (/sys/bus/pci/devices/<id>/local_cpulist); 1 on success. */
 int w2x_device_pci_bus_id(int device, char* buf, size_t cap);
@@ -181,7 +192,8 @@ void w2x_sha256_hex(const void* data, size_t len, char* out);
 const char* w2x_version(void);
 /* Test hook, process-wide: the reference paths the A/B tests compare the shipped kernels and plans with - un-fused lowering ("no_fuse", "no_fuse_attn",
  * "no_se_fold"; read by build), separate launches ("no_fuse_head", "no_fuse_stem", "no_fuse_up"; read by load), the general kernel instead of a shape-specialised one
- * ("no_pixgemm", "no_conv3", "no_conv3h", "no_conv3h_walk", "no_conv48", "no_stem", "attn_valu"; read per launch).  Which ops share a launch is fixed at load:
+ * ("no_pixgemm", "no_conv3", "no_conv3h", "no_conv3h_walk", "no_conv48", "no_stem", "attn_valu"; read per launch), every tile slot's dead-skip extents "all"
+ * ("no_dead_skip"; read per frame set-up, where the slot table of a render call is written - and by w2x_dead_skip_extents).  Which ops share a launch is fixed at load:
  * a switch set after load() changes the kernel of a launch of its own, never a folded launch (the stem, the transposed convolution, the image head).  They have no environment names.  The operational
  * switches (W2X_GROUPS, W2X_NO_GRAPH, ... - csrc/switches.h) can be set here too, by field name, but are re-read from the environment by
  * every build / load.  1 = set, 0 = no such switch. */

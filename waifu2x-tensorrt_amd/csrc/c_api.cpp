@@ -1,5 +1,6 @@
 // Flat C ABI over w2x::Img2Img (declared in include/w2x/c_api.h, which cites the reference interfaces).
 #include "../../include/w2x/c_api.h"
+#include <mutex>
 
 #include <cstring>
 #include <fstream>
@@ -7,6 +8,7 @@
 #include <string>
 
 #include "../../include/w2x/img2img.h"
+#include "liveness.h"
 #include "lower.h"
 #include "sha256.h"
 #include "tiles.h"
@@ -339,6 +341,45 @@ void w2x_sha256_hex(const void* data, size_t len, char* out) {
 }
 
 const char* w2x_version(void) { return "w2x-hip 0.1 (gfx950)"; }
+
+int w2x_dead_skip_extents(const char* onnx_path, int batch, int tile, int in_w, int in_h, int scaling, double overlap_x, double overlap_y, int tile_index, int tta,
+                          int* out, int cap) {
+    try {
+        // (the lowered plan of the last (file, batch, tile) is kept: a test asks for many frames and tiles of one plan)
+        static std::mutex mu;
+        static std::string key;
+        static w2x::Plan plan;
+        std::lock_guard<std::mutex> lock(mu);
+        const std::string k = std::string(onnx_path ? onnx_path : "") + "|" + std::to_string(batch) + "|" + std::to_string(tile);
+        if (k != key) { plan = w2x::build_plan(onnx_path, batch, 3, tile, tile, false); plan.userB = batch; key = k; }
+        const int nops = (int)plan.ops.size();
+        if (!out || cap < nops * W2X_EXTENT_INTS) return -nops;
+        int kept_w = plan.Tout, kept_h = plan.Tout;
+        bool all = tta != 0 || tile_index < 0 || w2x::switches().no_dead_skip;
+        if (tile_index >= 0) {
+            const w2x::TileGrid g = w2x::calculate_tiles(in_w, in_h, in_w * scaling, in_h * scaling, tile, tile, plan.Tout, plan.Tout, scaling, overlap_x, overlap_y);
+            if (tile_index >= g.count) return 0;
+            kept_w = g.out[tile_index].w; kept_h = g.out[tile_index].h;
+        }
+        const std::vector<w2x::OpExtent> ext = w2x::dead_skip_extents(plan, kept_w, kept_h, all);
+        for (int i = 0; i < nops; ++i) {
+            const w2x::Op& op = plan.ops[i]; const w2x::OpExtent& e = ext[i];
+            int* o = out + (size_t)i * W2X_EXTENT_INTS;
+            int in_t = -1, out_t = -1, res_t = -1, kh = 1, kw = 1, stride = 1, x0 = 0, y0 = 0, r = 1;
+            if (op.kind == w2x::OP_GEMM) {
+                in_t = op.g.a.t; out_t = op.g.out.t; res_t = op.g.res.t; x0 = op.g.a.x0; y0 = op.g.a.y0;
+                if (op.g.amode == w2x::A_CONV) { kh = op.g.kh; kw = op.g.kw; stride = op.g.stride; }
+                if (op.g.omode == w2x::O_PIXSHUF) r = op.g.r;
+            } else if (op.kind == w2x::OP_MLP) { in_t = op.m.x; out_t = op.m.y; }
+            else if (op.kind == w2x::OP_SWINATTN) { in_t = op.sa.x; out_t = op.sa.y; }
+            auto dim = [&](int t, bool w) { return t >= 0 && t < (int)plan.tensors.size() ? (w ? plan.tensors[t].W : plan.tensors[t].H) : 0; };
+            const int v[W2X_EXTENT_INTS] = {op.kind, e.x.n, e.y.n, e.x.c, e.x.w, e.y.c, e.y.w, e.rx, e.ry, e.ws, in_t, out_t, res_t, kh, kw, stride, x0, y0, r,
+                                            dim(in_t, true), dim(in_t, false), dim(out_t, true), dim(out_t, false), (int)e.live_units(), (int)e.total_units()};
+            for (int k = 0; k < W2X_EXTENT_INTS; ++k) o[k] = v[k];
+        }
+        return nops;
+    } catch (const std::exception&) { return 0; }
+}
 
 int w2x_debug_set(const char* name, int value) { return w2x::set_switch(name, value) ? 1 : 0; }
 

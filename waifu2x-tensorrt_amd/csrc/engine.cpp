@@ -22,6 +22,7 @@
 #include "common.h"
 #include "fragorder.h"
 #include "kernels.h"
+#include "liveness.h"
 #include "lower.h"
 #include "plan.h"
 #include "sha256.h"
@@ -262,6 +263,45 @@ struct Img2Img::Impl {
     bool rolling = false;                               // inside run_rolling_frame: split passes do not join their streams
     bool rolling_ok = true;                             // W2X_NO_ROLLING switches the frame-to-frame pipeline of benchResident / renderSequence off
     TileSlot* d_slots = nullptr; size_t slots_cap = 0;
+    // Dead-skip extents (liveness.h, kernels.h LiveExt): d_live[op * live_stride + slot] for the slots of d_slots, rewritten by upload_live() wherever a slot
+    // table is uploaded (a frame's set-up: render / renderStrip parts, shardCompute, sequences, RGBA schedules, one_part_slots).  Captured passes hold addresses
+    // into it: it only moves through ensure(), which drops them.  The no_dead_skip switch (read here, per frame set-up), W2X_CHECK_GENERAL (whole maps are compared)
+    // and TTA slots (the kept rect would have to go through the slot's dihedral map) get "all"; the profiling pass honours the table like any pass.
+    LiveExt* d_live = nullptr; size_t live_cap = 0, live_stride = 0;
+    std::vector<LiveExt> h_live;
+    std::map<std::pair<int, int>, std::vector<OpExtent>> live_cache;     // per kept rect (w, h) of this load's plan
+    void upload_live(const TileGrid& grid, size_t count, hipStream_t on) {
+        const size_t nops = plan.ops.size();
+        if (!count || !nops) return;
+        if (count > live_stride) {
+            ensure(d_live, live_cap, (nops * count + 8) * sizeof(LiveExt));      // (slack: a kernel may read the entry behind a run's last image)
+            live_stride = count;
+        }
+        const bool all = switches().no_dead_skip || check_general || cfg.tta;
+        std::map<std::pair<int, int>, int> tile_at;                              // tile origins are distinct
+        if (!all) for (int t = 0; t < grid.count; ++t) tile_at[{grid.in[t].x, grid.in[t].y}] = t;
+        auto extents = [&](int w, int h) -> const std::vector<OpExtent>& {
+            auto it = live_cache.find({w, h});
+            if (it == live_cache.end()) it = live_cache.emplace(std::make_pair(w, h), dead_skip_extents(plan, w, h, false)).first;
+            return it->second;
+        };
+        const std::vector<OpExtent>& whole = extents(plan.Tout, plan.Tout);
+        h_live.resize(nops * count);
+        for (size_t st = 0; st < count; ++st) {
+            const TileSlot& sl = h_slots[st];
+            const std::vector<OpExtent>* e = &whole;
+            if (!all && sl.valid && sl.aug == 0) {
+                const auto it = tile_at.find({sl.x, sl.y});
+                if (it != tile_at.end()) e = &extents(grid.out[it->second].w, grid.out[it->second].h);
+            }
+            for (size_t i = 0; i < nops; ++i) {
+                const OpExtent& x = (*e)[i];
+                auto u16 = [](int v) { return (uint16_t)std::min(std::max(v, 0), 65535); };
+                h_live[i * count + st] = x.all() ? LiveExt{65535, 0, 65535, 0} : LiveExt{u16(x.x.c), u16(x.x.w), u16(x.y.c), u16(x.y.w)};
+            }
+        }
+        hipAssert(hipMemcpy2DAsync(d_live, live_stride * sizeof(LiveExt), h_live.data(), count * sizeof(LiveExt), count * sizeof(LiveExt), nops, hipMemcpyHostToDevice, on));
+    }
     float *d_rampx = nullptr, *d_rampy = nullptr;
     int ovx = 0, ovy = 0;
     float* d_blob_in = nullptr; float* d_blob_out = nullptr;
@@ -337,6 +377,8 @@ struct Img2Img::Impl {
         }
         ensure(d_slots, slots_cap, stepCount * sizeof(TileSlot));
         hipAssert(hipMemcpy(d_slots, h_slots.data(), stepCount * sizeof(TileSlot), hipMemcpyHostToDevice));
+        upload_live(last_grid, stepCount, stream);
+        hipAssert(hipStreamSynchronize(stream));
         ensure(d_slab, slab_cap, stepCount * plan.Tout * plan.Tout * 4 * plan.elt);      // (already that large: renderPart sizes the slab for both layouts)
         one_part_stale = false;
     }
@@ -398,9 +440,10 @@ struct Img2Img::Impl {
         bgr_cap = alpha_cap = 0; rgba = false;
         if (h_minmax) { if (hipHostFree(h_minmax) != hipSuccess) (void)hipGetLastError(); h_minmax = nullptr; }
         if (ev_minmax) { (void)hipEventDestroy(ev_minmax); ev_minmax = nullptr; }
-        for (void** p : {(void**)&d_frame, (void**)&d_out, (void**)&d_frame2, (void**)&d_out2, &d_slab, &d_slab2, (void**)&d_slots, (void**)&d_rampx, (void**)&d_rampy, (void**)&d_blob_in, (void**)&d_blob_out})
+        for (void** p : {(void**)&d_frame, (void**)&d_out, (void**)&d_frame2, (void**)&d_out2, &d_slab, &d_slab2, (void**)&d_slots, (void**)&d_live, (void**)&d_rampx, (void**)&d_rampy, (void**)&d_blob_in, (void**)&d_blob_out})
             if (*p) { (void)hipFree(*p); *p = nullptr; }
         frame_cap = out_cap = slab_cap = slab2_cap = slots_cap = 0;
+        live_cap = live_stride = 0; live_cache.clear();
         shard_rows = shard_cols = 0; shard_halo_slots = 0; rolling = false; one_part_stale = false;
         last_rows = last_cols = last_batches = 0;      // (benchResident / profileFrame replay the last frame of THIS load)
         if (ev0) { (void)hipEventDestroy(ev0); ev0 = nullptr; }
@@ -732,11 +775,13 @@ struct Img2Img::Impl {
     uint8_t* group_ptr(const void* full, int grp) const {
         return full ? (uint8_t*)arena_base + (size_t)grp * arena_part() + (size_t)((const uint8_t*)full - (const uint8_t*)arena_base) / ng_now : nullptr;
     }
-    void run_network(void* out_override, int live = -1, int grp = -1, hipStream_t s = nullptr) {
+    void run_network(void* out_override, int live = -1, int grp = -1, hipStream_t s = nullptr, const LiveExt* ext = nullptr) {
         if (!s) s = stream;
         const int cap = grp < 0 ? plan.B : plan.B / ng_now;
         if (live < 0 || live > cap) live = cap;
         auto tp = [&](int t) -> uint8_t* { return t < 0 ? nullptr : grp < 0 ? (uint8_t*)tensors[t] : group_ptr(tensors[t], grp); };
+        // `ext`: the dead-skip entry of this pass's (group's) first slot in op 0's table, or null ("all": w2x_infer); op i's table lies i * live_stride entries on
+        auto lv = [&](int i) -> const LiveExt* { return ext ? ext + (size_t)i * live_stride : nullptr; };
         // op i's prepared parameters for this pass: `live` tiles, the group's part of the arena, the pass's output where op i writes it
         auto gp = [&](int i) {
             GemmParams p = gemm[i];
@@ -757,6 +802,7 @@ struct Img2Img::Impl {
                 case L_HEAD: {      // the image head rides on the MLP launch
                     const GemmParams g = gp(L.last);
                     MlpParams p = mlp_params(op, live, tp);
+                    p.live = lv(L.last);      // (the head is per token: its rows are the MLP's)
                     p.ti_w = g.wt_frag; p.ti_b = g.bias; p.ti_out = g.out.p; p.ti_Hs = g.out.Hs; p.ti_Ws = g.out.Ws; p.ti_Mrows = g.Mrows; p.ti_aW = g.aW;
                     p.ti_clip = g.has_clip; p.ti_lo = g.clip_lo; p.ti_hi = g.clip_hi;
                     issue([&] { return launch_mlp(p, s); });
@@ -813,12 +859,14 @@ struct Img2Img::Impl {
                         p.wproj = blobs[a.wproj]; p.bproj = (const float*)blobs[a.bproj]; p.eps = a.eps;
                         p.wqkv_frag = frag_blobs[a.wqkv]; p.wproj_frag = frag_blobs[a.wproj];
                         p.stats_out = (float*)tp(a.stats_out); p.eps_out = a.eps_out;
+                        p.live = lv(L.first);
                         if (d.C != a.C || plan.tensors[a.y].C != a.C || d.H * d.W != a.nwin * a.ws * a.ws) throw std::runtime_error("plan: attention geometry mismatch");
                         issue([&] { return launch_swin_attn(p, s); });
                         break;
                     }
                     case OP_MLP: {
-                        const MlpParams p = mlp_params(op, live, tp);
+                        MlpParams p = mlp_params(op, live, tp);
+                        p.live = lv(L.first);
                         issue([&] { return launch_mlp(p, s); });
                         break;
                     }
@@ -857,6 +905,7 @@ struct Img2Img::Impl {
         p.w1 = blobs[m.w1]; p.b1 = (const float*)blobs[m.b1]; p.w2 = blobs[m.w2]; p.b2 = (const float*)blobs[m.b2];
         p.w1_frag = frag_blobs[m.w1]; p.w2_frag = frag_blobs[m.w2]; p.frag32 = mlp_frag32(m.C);
         p.eps = m.eps; p.stats_out = (float*)tp(m.stats_out); p.eps_out = m.eps_out;
+        p.live_W = d.W; p.live_H = d.H;
         if (d.C != m.C || plan.tensors[m.y].C != m.C) throw std::runtime_error("plan: MLP width mismatch");
         return p;
     }
@@ -1006,7 +1055,8 @@ struct Img2Img::Impl {
                 gp.out = group_ptr(tensors[plan.in_tensor], grp); gp.slots = gp0.slots + (size_t)first[grp]; gp.B = first[grp + 1] - first[grp];
                 gather(gp, gs);
             };
-            auto network_group = [&](int grp, hipStream_t gs) { run_network((uint8_t*)slab_out + (size_t)first[grp] * slot_bytes, first[grp + 1] - first[grp], grp, gs); };
+            const LiveExt* const ext0 = d_live && slots_off + (size_t)(bi + 1) * B <= live_stride ? d_live + slots_off + (size_t)bi * B : nullptr;   // this pass's slots in op 0's table
+            auto network_group = [&](int grp, hipStream_t gs) { run_network((uint8_t*)slab_out + (size_t)first[grp] * slot_bytes, first[grp + 1] - first[grp], grp, gs, ext0 ? ext0 + first[grp] : nullptr); };
             auto fork = [&] { hipAssert(hipEventRecord(ev_fork, stream)); for (int grp = 1; grp < NG; ++grp) hipAssert(hipStreamWaitEvent(gstream[grp - 1], ev_fork, 0)); };
             auto join = [&] { for (int grp = 1; grp < NG; ++grp) { hipAssert(hipEventRecord(ev_join[grp - 1], gstream[grp - 1])); hipAssert(hipStreamWaitEvent(stream, ev_join[grp - 1], 0)); } };
             // the whole pass as launches issued from `stream` (the groups forked off it by events: capturable as ONE graph with NG branches)
@@ -1015,7 +1065,7 @@ struct Img2Img::Impl {
                     stamp_begin(3, 0);
                     gather(gp0, stream);
                     stamp_end();
-                    run_network(slab_out, live);
+                    run_network(slab_out, live, -1, nullptr, ext0);
                     return;
                 }
                 ng_now = NG;
@@ -1175,6 +1225,7 @@ struct Img2Img::Impl {
         }
         ensure(d_slots, slots_cap, (size_t)stepCount * sizeof(TileSlot));
         hipAssert(hipMemcpyAsync(d_slots, h_slots.data(), (size_t)stepCount * sizeof(TileSlot), hipMemcpyHostToDevice, stream));
+        upload_live(grid, (size_t)stepCount, stream);
         ensure(d_slab, slab_cap, (size_t)stepCount * plan.Tout * plan.Tout * 4 * plan.elt);
         hipAssert(hipStreamSynchronize(stream));
     }
@@ -1597,6 +1648,7 @@ bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, cons
     }
     impl->ensure(impl->d_slots, impl->slots_cap, stepTotal * sizeof(TileSlot));
     hipAssert(hipMemcpyAsync(impl->d_slots, impl->h_slots.data(), stepTotal * sizeof(TileSlot), hipMemcpyHostToDevice, stream));
+    impl->upload_live(grid, stepTotal, stream);
     // the slab holds the frame's tiles in tile order: the last part's passes end at most a pass beyond them (and the frame as ONE part - what
     // benchResident / profileFrame replay - ends at most a pass beyond its tiles: sized for both now, an allocation later would drop the captured passes)
     const size_t one_part_steps = (size_t)(((int)std::lround(std::ceil((double)(sp.tile_count * steps) / plan.userB)) + S - 1) / S) * B;
@@ -1719,6 +1771,7 @@ static void shard_phase1(Img2Img::Impl& e, const Image& src, const TileGrid& gri
     }
     e.ensure(e.d_slots, e.slots_cap, (size_t)stepCount * sizeof(TileSlot));
     hipAssert(hipMemcpyAsync(e.d_slots, e.h_slots.data(), (size_t)stepCount * sizeof(TileSlot), hipMemcpyHostToDevice, e.stream));
+    e.upload_live(grid, (size_t)stepCount, e.stream);
     e.shard_halo_slots = (size_t)(sp.first_tile - sp.halo_first) * steps;
     e.ensure(e.d_slab, e.slab_cap, (e.shard_halo_slots + (size_t)stepCount) * slot_bytes);
     hipAssert(hipEventRecord(e.ev0, e.stream));
@@ -2142,6 +2195,7 @@ bool Img2Img::renderRgba(const Image& src, Image& dst, const RgbaOptions& opt) t
     }
     impl->ensure(impl->d_slots, impl->slots_cap, stepTotal * sizeof(TileSlot));
     hipAssert(hipMemcpyAsync(impl->d_slots, impl->h_slots.data(), stepTotal * sizeof(TileSlot), hipMemcpyHostToDevice, stream));
+    impl->upload_live(grid, stepTotal, stream);
     impl->ensure(impl->d_slab, impl->slab_cap, stepTotal * plan.Tout * plan.Tout * 4 * plan.elt);
     impl->one_part_stale = false;
     hipAssert(hipEventRecord(impl->ev0, stream));

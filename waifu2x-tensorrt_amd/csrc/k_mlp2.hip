@@ -186,6 +186,12 @@ __global__ __launch_bounds__(NW * 64, (C == 96 ? 3 : W2X_MLP192_WPS) * NW / 4) v
     _Float16* Xw = (_Float16*)(smem + wv * K::SLAB);          // [RW][LDX]
     unsigned char* const WBb = smem + (K::KEEP ? K::NWV * K::SLAB : 0);   // two weight buffers of NF fragments [64 lanes][8]
 
+    // dead-skip (kernels.h LiveExt): a workgroup none of whose rows a kept output pixel depends on ends here - its waves share the staged weights and the
+    // barriers, so the row group is the workgroup's BM rows.  Scalar table reads, uniform over the workgroup.
+    if (p.live) {
+        const long g0 = (long)blockIdx.x * K::BM, left = p.M - g0;
+        if (!live_rows(p.live, p.live_row0 + g0, left < K::BM ? (int)left : K::BM, p.live_W, p.live_H)) return;
+    }
     const long row0 = ((long)blockIdx.x * K::NWV + wv) * RW;       // first row of this wave
     const long nrows = p.M - row0 < RW ? p.M - row0 : RW;     // may be <= 0: the wave then only runs dead arithmetic
     // rows through buffer resources (32-bit byte offsets, bounds-checked: pieces past the last row read zeros, their stores are dropped;
@@ -705,6 +711,7 @@ hipError_t launch_mlp2_c(const MlpParams& p, hipStream_t s) {
         q.M = p.M - r0 < max_rows ? p.M - r0 : max_rows;
         q.x = (const char*)p.x + (size_t)r0 * C * 2; q.y = (char*)p.y + (size_t)r0 * C * 2;
         if (p.stats_out) q.stats_out = p.stats_out + 2 * r0;
+        q.live_row0 = p.live_row0 + r0;
         dim3 grid((unsigned)((q.M + K::BM - 1) / K::BM));
         hipLaunchKernelGGL((mlp2_kernel<C, TT, NW>), grid, dim3(K::NWV * 64), K::SMEM, s, q);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;

@@ -219,15 +219,29 @@ __global__ __launch_bounds__(NTHR, 3) void mlp96q_kernel(const MlpParams p, int 
     // last tiles run beside empty slots (10.0 of 12 waves resident on average, profiles/r5_final/pmc_sq.summary.txt).  Which wave computes a tile does not
     // change a bit of it.
     constexpr bool DYN = W2X_MLP96_DYN && !TOIMG;
+    // dead-skip (kernels.h LiveExt): the walk takes live tiles only - a tile none of whose RW rows a kept output pixel depends on is passed over where the
+    // next tile is chosen (scalar table reads, wave-uniform), so it costs neither loads nor products nor stores; a live tile runs as it always did
+    auto tile_live = [&](int tl) -> bool {
+        if (!p.live || tl >= ntiles) return true;
+        const long r0 = (long)tl * RW, left = p.M - r0;
+        return live_rows(p.live, p.live_row0 + r0, left < RW ? (int)left : RW, p.live_W, p.live_H);
+    };
     auto grab = [&]() -> int {
-        int t = 0;
-        if (lane == 0) t = atomicAdd((int*)(smem + CTR_OFF), 1);
-        t = __builtin_amdgcn_readfirstlane(t);
-        const int tl = (blockIdx.x + (t / NWV) * (int)gridDim.x) * NWV + t % NWV;
+        int tl;
+        do {
+            int t = 0;
+            if (lane == 0) t = atomicAdd((int*)(smem + CTR_OFF), 1);
+            t = __builtin_amdgcn_readfirstlane(t);
+            tl = (blockIdx.x + (t / NWV) * (int)gridDim.x) * NWV + t % NWV;
+        } while (!tile_live(tl));
         return tl < ntiles ? tl : ntiles;            // (ntiles: one tile past the end - its rows read zeros, its stores are dropped, the loop ends)
     };
+    auto stride_from = [&](int tl) -> int {          // (fixed stride: the first live tile at or behind tl)
+        while (!tile_live(tl)) tl += nw;
+        return tl < ntiles ? tl : ntiles;
+    };
     int tile = gw, next_tile = ntiles;
-    if constexpr (DYN) tile = grab();
+    if constexpr (DYN) tile = grab(); else tile = stride_from(gw);
     if (tile < ntiles) W2X_FETCH(tile)
 #if W2X_MLP_PREFETCH
     // NP stores that the hardware drops (offset past the end), so that the first pass through the loop sees the same queue as every
@@ -237,7 +251,7 @@ __global__ __launch_bounds__(NTHR, 3) void mlp96q_kernel(const MlpParams p, int 
     for (int k = 0; k < NP; ++k) __builtin_amdgcn_raw_buffer_store_b128(uint4v{}, YB, 0xFFFFF000u + k * 16u, 0, 0);   // (distinct offsets: identical stores would be merged)
 #endif
 #pragma unroll 1
-    for (; tile < ntiles; tile = DYN ? next_tile : tile + nw) {
+    for (; tile < ntiles; tile = (DYN || W2X_MLP_PREFETCH) ? next_tile : stride_from(tile + nw)) {
         const long row0 = (long)((W2X_MLP_EXP & 1) ? (tile & 63) : tile) * RW;
         const long nrows = p.M - row0 < RW ? p.M - row0 : RW;
         // ---- x rows: flat coalesced pieces -> slab (the raw rows stay there for the residual add)
@@ -304,7 +318,8 @@ __global__ __launch_bounds__(NTHR, 3) void mlp96q_kernel(const MlpParams p, int 
             }
 #if W2X_MLP_PREFETCH
             if (ch == W2X_MLP_PFCH) {                                           // the next tile's rows (past the last tile: zeros)
-                if constexpr (DYN) { next_tile = grab(); W2X_FETCH(next_tile) } else { W2X_FETCH(tile + nw) }
+                if constexpr (DYN) next_tile = grab(); else next_tile = stride_from(tile + nw);
+                W2X_FETCH(next_tile)
                 W2X_RING_FENCE();
             }
 #endif
@@ -486,6 +501,7 @@ hipError_t launch_mlp96q(const MlpParams& p, hipStream_t s) {
         q.M = std::min(max_rows, p.M - r0);
         q.x = (const char*)p.x + (size_t)r0 * C * 2; q.y = (char*)p.y + (size_t)r0 * C * 2;
         if (p.stats_out) q.stats_out = p.stats_out + 2 * r0;
+        q.live_row0 = p.live_row0 + r0;
         const long ntiles = (q.M + RW - 1) / RW;
         const int grid = (int)std::min<long>((ntiles + NWV - 1) / NWV, ncu);
         if ((ntiles + (long)grid * NWV) * (long)(RW * C * 2) > 0xFFFFFFFFl) return hipErrorInvalidValue;   // (cannot happen: max_tiles)

@@ -136,13 +136,22 @@ __global__ __launch_bounds__(256, W2X_A192U_WPC) void swin_attn192u_kernel(const
     const int fr = lane & 15, g = lane >> 4;
 
     const int iw0 = blockIdx.x * G, iw1 = iw0 + 1, itotal = p.B * p.nwin;
-    const bool wok0 = iw0 < itotal, wok1 = iw1 < itotal;
+    bool wok0 = iw0 < itotal, wok1 = iw1 < itotal;
     const int HW = p.nwin * NTOK;
     const int wb0 = iw0 / p.nwin, wb1 = iw1 / p.nwin;
     const int pixbase0 = wb0 * HW, pixbase1 = wb1 * HW;
     const int wl0 = iw0 - wb0 * p.nwin, wl1 = iw1 - wb1 * p.nwin;
     const int nwx = p.W / 6;
     const int wy0 = wl0 / nwx, wx0 = wl0 - wy0 * nwx, wy1 = wl1 / nwx, wx1 = wl1 - wy1 * nwx;
+    // dead-skip (kernels.h LiveExt; k_swinattn96.hip): a window no kept output pixel depends on is treated like one past the end (rows read zeros, stores are
+    // dropped), a workgroup without a live window ends here.  One scalar table read per window.
+    if (p.live && p.ry >= 0) {
+        int y0 = wy0 * 6 + p.ry, x0 = wx0 * 6 + p.rx, y1 = wy1 * 6 + p.ry, x1 = wx1 * 6 + p.rx;
+        y0 -= y0 >= p.H ? p.H : 0; x0 -= x0 >= p.W ? p.W : 0; y1 -= y1 >= p.H ? p.H : 0; x1 -= x1 >= p.W ? p.W : 0;
+        wok0 = wok0 && live_token(live_ext_load(p.live, wb0), x0, y0, p.W, p.H);
+        wok1 = wok1 && live_token(live_ext_load(p.live, wb1), x1, y1, p.W, p.H);
+        if (!wok0 && !wok1) return;
+    }
     const unsigned xbytes = (unsigned)p.B * (unsigned)HW * (C * 2);
     const __amdgpu_buffer_rsrc_t X = make_rsrc(p.x, xbytes), Y = make_rsrc(p.y, xbytes);
     const _Float16* __restrict__ Wqkv = (const _Float16*)p.wqkv_frag;    // [36 row tiles][6 k-steps][64 lanes][8]
@@ -514,6 +523,7 @@ hipError_t launch_swin_attn192u(const SwinAttnParams& p, hipStream_t s) {
         q.x = (const char*)p.x + (size_t)b0 * img_bytes;
         q.y = (char*)p.y + (size_t)b0 * img_bytes;
         if (p.stats_out) q.stats_out = p.stats_out + (size_t)b0 * p.nwin * NTOK * 2;
+        if (p.live) q.live = p.live + b0;
         const long total_win = (long)q.B * q.nwin;
         hipLaunchKernelGGL(kern, dim3((unsigned)((total_win + G - 1) / G)), dim3(256), SMEM192U, s, q);
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;

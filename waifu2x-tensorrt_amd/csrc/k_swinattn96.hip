@@ -211,6 +211,20 @@ __global__ __launch_bounds__(NTHR, 4) void swin_attn96_kernel(const SwinAttnPara
 
     const int wl0 = blockIdx.x * G;              // the workgroup's windows: wl0 and wl0 + 1 of image blockIdx.y (a pair never straddles two images: no division by the window count)
     const int HW = p.nwin * NTOK;
+    // dead-skip (kernels.h LiveExt): one scalar table read per workgroup.  A window none of whose tokens a kept output pixel depends on is treated like a window
+    // that does not exist (its rows read zeros, its stores are dropped - the live window of the pair runs the same instructions on the same data); a workgroup
+    // without a live window ends here.  (The sets are whole windows: a window's first token decides.)
+    bool lv0 = true, lv1 = wl0 + 1 < p.nwin;
+    if (p.live && p.ry >= 0) {
+        const LiveExt e = live_ext_load(p.live, (int)blockIdx.y);
+        const int nwx = p.W / 6, wy = wl0 / nwx, wx = wl0 - wy * nwx;
+        const int wy1 = wx + 1 == nwx ? wy + 1 : wy, wx1 = wx + 1 == nwx ? 0 : wx + 1;
+        int y0 = wy * 6 + p.ry, x0 = wx * 6 + p.rx, y1 = wy1 * 6 + p.ry, x1 = wx1 * 6 + p.rx;
+        y0 -= y0 >= p.H ? p.H : 0; x0 -= x0 >= p.W ? p.W : 0; y1 -= y1 >= p.H ? p.H : 0; x1 -= x1 >= p.W ? p.W : 0;
+        lv0 = live_token(e, x0, y0, p.W, p.H);
+        lv1 = lv1 && live_token(e, x1, y1, p.W, p.H);
+        if (!lv0 && !lv1) return;
+    }
     const unsigned xbytes = (unsigned)p.B * (unsigned)HW * (C * 2);
     const __amdgpu_buffer_rsrc_t X = make_rsrc(p.x, xbytes), Y = make_rsrc(p.y, xbytes);
     const _Float16* __restrict__ Wqkv = (const _Float16*)p.wqkv_frag;    // [18 row tiles][3 k-steps][64 lanes][8] (engine.cpp frag_major)
@@ -249,7 +263,7 @@ __global__ __launch_bounds__(NTHR, 4) void swin_attn96_kernel(const SwinAttnPara
             const int w = tid >= NTOK ? 1 : 0, t = tid - w * NTOK;
             const int wl = wl0 + w;
             srow = (w * SLAB + slab_row(t)) * LDX * 2;
-            if (wl < p.nwin) {
+            if (w ? lv1 : lv0) {
                 if (p.ry >= 0) {
                     // window -> (wy, wx) through a reciprocal instead of an integer division (two of which were a third of this block's instructions):
                     // (wl + 0.5) / nwx is at least 0.5 / nwx away from an integer, far more than the rounding of the product for any token map a pass holds
@@ -517,6 +531,7 @@ hipError_t launch_swin_attn96(const SwinAttnParams& p, hipStream_t s) {
         q.x = (const char*)p.x + (size_t)b0 * img_bytes;
         q.y = (char*)p.y + (size_t)b0 * img_bytes;
         if (p.stats_out) q.stats_out = p.stats_out + (size_t)b0 * p.nwin * NTOK * 2;
+        if (p.live) q.live = p.live + b0;
         hipLaunchKernelGGL(swin_attn96_kernel, dim3((unsigned)((q.nwin + G - 1) / G), (unsigned)q.B), dim3(NTHR), SMEM96, s, q);      // x: window pairs of an image, y: images
         if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
     }

@@ -44,6 +44,35 @@ template <class T> __device__ __forceinline__ void w2x_store_out(T* p, const T v
 }
 #endif
 
+// Dead-skip extents (liveness.h): per (plan op, pass slot) the part of the op's row map (W x H tokens) that some kept output pixel of the slot's tile
+// depends on - columns [0, cx) U [W - wx, W), rows [0, cy) U [H - wy, H); cx >= W and cy >= H: everything.  The engine keeps one table per op in device memory and
+// rewrites it with the slot table of every frame; a kernel reads its slot's entry once per workgroup / tile through the scalar data cache (a uniform load from
+// the constant address space) and skips units whose rows are all dead.  A null table means "all" (w2x_infer, the tools).
+struct LiveExt { uint16_t cx, wx, cy, wy; };
+#ifdef __HIPCC__
+__device__ __forceinline__ LiveExt live_ext_load(const LiveExt* t, int slot) {
+    typedef const unsigned long long __attribute__((address_space(4)))* cptr;
+    const unsigned long long v = ((cptr)(unsigned long long)t)[slot];
+    return LiveExt{(uint16_t)v, (uint16_t)(v >> 16), (uint16_t)(v >> 32), (uint16_t)(v >> 48)};
+}
+__device__ __forceinline__ bool live_token(const LiveExt e, int x, int y, int W, int H) { return (x < e.cx || x >= W - e.wx) && (y < e.cy || y >= H - e.wy); }
+// rows [r0, r0 + n) of a pass of row-major W x H token maps (n <= W H, wave-uniform arguments): false when none of them is live
+__device__ __forceinline__ bool live_rows(const LiveExt* t, long r0, int n, int W, int H) {
+    const int HW = W * H;
+    if (n > HW) return true;
+    const int img = (int)(r0 / HW);
+    int r = (int)(r0 - (long)img * HW);
+    LiveExt e = live_ext_load(t, img);
+    for (int left = n; left > 0;) {
+        if (r >= HW) { r -= HW; e = live_ext_load(t, img + 1); }      // (the run crosses into the next image; past the last image nothing is stored: harmless)
+        const int y = r / W, x0 = r - y * W, x1 = x0 + left < W ? x0 + left : W;      // the piece [x0, x1) of token row y
+        if ((y < e.cy || y >= H - e.wy) && (x0 < e.cx || x1 > W - e.wx)) return true;
+        left -= x1 - x0; r += x1 - x0;
+    }
+    return false;
+}
+#endif
+
 struct TView {           // device view of a channel-last tensor
     void* p = nullptr;
     int Hs = 0, Ws = 0, Cs = 0;  // stored dims
@@ -104,6 +133,9 @@ struct MlpParams {               // y = x + W2 gelu(W1 LN(x) + b1) + b2 on conti
     void* ti_out = nullptr; int ti_Hs = 0, ti_Ws = 0, ti_Mrows = 0, ti_aW = 0;   // output map [B][Hs][Ws][4], rows per image, row width of the token map
     int ti_clip = 0; float ti_lo = 0.f, ti_hi = 0.f;
     long ti_row0 = 0;              // (set by the launcher when it cuts a pass into runs: global index of this run's first row)
+    // dead-skip (LiveExt above): the op's table entry of the pass's first image, the token map of an image; null: every row runs
+    const LiveExt* live = nullptr; int live_W = 0, live_H = 0;
+    long live_row0 = 0;            // (set by the launcher like ti_row0)
 };
 
 struct SwinAttnParams {          // y = x + proj(W-MSA(LN(x))) on token maps [B][H][W][C], window 6x6
@@ -123,6 +155,7 @@ struct SwinAttnParams {          // y = x + proj(W-MSA(LN(x))) on token maps [B]
     // the same two matrices in MFMA-fragment order (engine.cpp frag_major): [16-row tile][32-column k-step][lane][8], so a
     // wave's fragment load is one contiguous KiB.  Required by k_swinattn96.hip / k_swinattn192u.hip.
     const void* wqkv_frag = nullptr; const void* wproj_frag = nullptr;
+    const LiveExt* live = nullptr; // dead-skip (LiveExt above): the op's table entry of the pass's first image; null: every window runs
 };
 
 struct SeParams {

@@ -47,6 +47,7 @@ const Field kFields[] = {
     {"no_conv48", nullptr, &Switches::no_conv48, nullptr, 0, 1},
     {"no_stem", nullptr, &Switches::no_stem, nullptr, 0, 1},
     {"attn_valu", nullptr, &Switches::attn_valu, nullptr, 0, 1},
+    {"no_dead_skip", nullptr, &Switches::no_dead_skip, nullptr, 0, 1},
 };
 void assign(Switches& s, const Field& f, long v) {
     v = std::min<long>(f.hi, std::max<long>(f.lo, v));

@@ -31,6 +31,7 @@ struct Switches {
     bool no_conv3h_walk = false; // k_conv3h.hip: the tile kernel instead of the column walk for the 64-channel image heads
     bool no_pixgemm = false, no_conv3 = false, no_conv3h = false, no_conv48 = false, no_stem = false;   // launchers: the general kernel instead
     bool attn_valu = false;      // launchers: the lane-per-query attention core instead of the matrix-pipe one
+    bool no_dead_skip = false;   // engine: every slot's dead-skip extents are "all" (liveness.h) - read where a frame's slot table is set up, not per launch
 };
 
 Switches& switches();                            // process-wide; (W2X_DEVICE_MAP, a test hook of its own, is read where devices are resolved)

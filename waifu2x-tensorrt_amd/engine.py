@@ -186,6 +186,7 @@ def lib():
     L.w2x_sha256_hex.argtypes = [vp, C.c_size_t, C.c_char_p]
     L.w2x_version.restype = C.c_char_p
     L.w2x_debug_set.argtypes = [C.c_char_p, C.c_int]; L.w2x_debug_set.restype = C.c_int
+    L.w2x_dead_skip_extents.argtypes = [C.c_char_p] + [C.c_int] * 5 + [C.c_double, C.c_double, C.c_int, C.c_int, vp, C.c_int]; L.w2x_dead_skip_extents.restype = C.c_int
     _lib = L
     return L
 
@@ -195,7 +196,7 @@ EXPORTED_SYMBOLS = [
     "w2x_render", "w2x_render16", "w2x_infer", "w2x_output_tile_size", "w2x_plan_flops", "w2x_pass_tiles", "w2x_last_render_ms", "w2x_bench_resident", "w2x_resident_output", "w2x_profile_frame", "w2x_op_times",
     "w2x_render_resized", "w2x_render16_resized", "w2x_render_sequence_resized", "w2x_resize_weights",
     "w2x_render_yuv", "w2x_render_sequence_yuv", "w2x_yuv_plane_sizes", "w2x_render_yuv_resized", "w2x_render_sequence_yuv_resized",
-    "w2x_render_rgba", "w2x_alpha_bleed_device", "w2x_alpha_bleed",
+    "w2x_render_rgba", "w2x_alpha_bleed_device", "w2x_alpha_bleed", "w2x_dead_skip_extents",
     "w2x_render_strip", "w2x_strip_plan", "w2x_render_sharded", "w2x_shard_plan", "w2x_shard_compute", "w2x_shard_slab", "w2x_shard_finish", "w2x_ipc_export", "w2x_ipc_open", "w2x_ipc_close", "w2x_render_sequence", "w2x_alloc_host", "w2x_free_host", "w2x_pin_host", "w2x_unpin_host", "w2x_calculate_tiles", "w2x_tile_weights", "w2x_describe_plan", "w2x_describe_plan_precision", "w2x_write_engine_file", "w2x_validate_engine_file", "w2x_device_pci_bus_id", "w2x_sha256_hex", "w2x_version", "w2x_debug_set"]
 
 
@@ -774,6 +775,22 @@ def describe_plan(onnx_path, batch, tile, precision=None) -> str:
     if not ok:
         raise W2xError(s)
     return s
+
+
+EXTENT_FIELDS = ("kind", "W", "H", "cx", "wx", "cy", "wy", "rx", "ry", "ws", "t_in", "t_out", "t_res", "kh", "kw", "stride", "x0", "y0", "r",
+                 "in_W", "in_H", "out_W", "out_H", "live_units", "total_units")
+
+
+def dead_skip_extents(onnx_path, batch, tile, in_w, in_h, scaling, overlap, tile_index, tta=False) -> list[dict]:
+    """w2x_dead_skip_extents: per plan op the live part of its row map for tile `tile_index` of an in_w x in_h frame (tile_index < 0: w2x_infer, "all").  Host only."""
+    L = lib()
+    n = -L.w2x_dead_skip_extents(os.fsencode(onnx_path), batch, tile, in_w, in_h, scaling, float(overlap[0]), float(overlap[1]), int(tile_index), int(bool(tta)), None, 0)
+    if n <= 0:
+        raise W2xError("w2x_dead_skip_extents failed")
+    out = np.zeros((n, len(EXTENT_FIELDS)), np.int32)
+    if L.w2x_dead_skip_extents(os.fsencode(onnx_path), batch, tile, in_w, in_h, scaling, float(overlap[0]), float(overlap[1]), int(tile_index), int(bool(tta)), out.ctypes.data, out.size) != n:
+        raise W2xError("w2x_dead_skip_extents failed")
+    return [dict(zip(EXTENT_FIELDS, (int(v) for v in row))) for row in out]
 
 
 def write_engine_file(onnx_path, batch, tile, out_path) -> bool:
