@@ -124,6 +124,18 @@ int w2x_render_sequence_yuv_resized(w2x_engine* e, const void* const* src_planes
  * channel of w2x_render of the gray image B = G = R = A.  skip_uniform_alpha != 0: a frame whose alpha plane is one value v runs no alpha tiles and gets
  * alpha v everywhere.  A bleed outside [0, 16], empty images and short steps return 0 through the message callback. */
 int w2x_render_rgba(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, size_t dst_step, int bleed, int skip_uniform_alpha);
+/* Extension (Img2Img::renderRgbaResized): w2x_render_rgba with the output resized on the device to dst_rows x dst_cols - the targets and filters of
+ * w2x_render_resized (each dimension in [src dim, src dim * scaling]; filter 0 bicubic, 1 bilinear).  Colour bytes: w2x_render_resized of the bled colour frame;
+ * alpha bytes: the green channel of w2x_render_resized of the gray image B = G = R = A.  At the scaled size it is w2x_render_rgba. */
+int w2x_render_rgba_resized(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, int dst_rows, int dst_cols, size_t dst_step, int bleed,
+                            int skip_uniform_alpha, int filter);
+/* Extension (Img2Img::renderSequenceRgba): count BGRA frames of one size with one set of options, upload / compute / download overlapped as in
+ * w2x_render_sequence (page-locked buffers: w2x_alloc_host); output i is the bytes of w2x_render_rgba on frame i. */
+int w2x_render_sequence_rgba(w2x_engine* e, const uint8_t* const* srcs, int rows, int cols, size_t src_step, uint8_t* const* dsts, size_t dst_step, int count, int bleed,
+                             int skip_uniform_alpha);
+/* w2x_render_sequence_rgba with every frame resized like w2x_render_rgba_resized (one target size for the sequence) */
+int w2x_render_sequence_rgba_resized(w2x_engine* e, const uint8_t* const* srcs, int rows, int cols, size_t src_step, uint8_t* const* dsts, int dst_rows, int dst_cols,
+                                     size_t dst_step, int count, int bleed, int skip_uniform_alpha, int filter);
 /* Test hook (Img2Img::alphaBleed): the device bleed alone - BGRA frame in, the BGR frame the tiles would be read from out (rows x cols, bgr_step >= cols * 3) */
 int w2x_alpha_bleed_device(w2x_engine* e, const uint8_t* bgra, int rows, int cols, size_t bgra_step, uint8_t* bgr, size_t bgr_step, int radius);
 void* w2x_alloc_host(w2x_engine* e, size_t bytes);

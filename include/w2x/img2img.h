@@ -105,6 +105,14 @@ public:
     // alpha bytes: the green channel of render() of the gray image.  skipUniformAlpha and min(A) == max(A) == v: no alpha tiles, every output alpha is v, the
     // progress total is the colour tiles' alone.  Other depths, empty images, short steps, other sizes, bleed outside [0, 16]: false (message callback).
     bool renderRgba(const Image& src, Image& dst, const RgbaOptions& opt = {});
+    // renderRgba() with the output resized on the device to dst.rows x dst.cols, the targets and filters of renderResized() for 8-bit frames: each
+    // dimension in [src dim, src dim * scaling], independently.  Colour bytes: renderResized() of alpha_bleed(BGR, A, bleed); alpha bytes: the green channel of
+    // renderResized() of the gray image - resized separately and straight, not premultiplied.  At the scaled size it is renderRgba().
+    bool renderRgbaResized(const Image& src, Image& dst, const RgbaOptions& opt = {}, ResizeFilter filter = ResizeFilter::Bicubic);
+    // A sequence of equally sized BGRA frames with one set of options, upload / compute / download overlapped as in renderSequence() (page-locked buffers:
+    // allocHost()); output i is the bytes of renderRgba() / renderRgbaResized() on frame i.  skipUniformAlpha is decided per frame.  No progress is reported.
+    bool renderSequenceRgba(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt = {});
+    bool renderSequenceRgbaResized(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt = {}, ResizeFilter filter = ResizeFilter::Bicubic);
     void* allocHost(size_t bytes);
     void freeHost(void* data);
     // Page-locks caller-owned memory in place.  Only whole pages are accepted (data and bytes multiples of 4096): a registration
@@ -139,6 +147,8 @@ public:
 private:
     bool renderPart(const Image& src, Image& dst, int part, int parts, const char* who, int resizeFilter = -1);   // resizeFilter >= 0: renderResized
     bool runSequence(const Image* srcs, Image* dsts, int count, int resizeFilter, const char* who);
+    bool renderRgbaFrame(const Image& src, Image& dst, const RgbaOptions& opt, int resizeFilter, const char* who);   // resizeFilter >= 0: renderRgbaResized
+    bool runSequenceRgba(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt, int resizeFilter, const char* who);
     bool runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, int resizeFilter, const char* who);   // resizeFilter >= 0: renderYuvResized
     std::unique_ptr<Impl> impl;
 };

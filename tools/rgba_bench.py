@@ -9,6 +9,14 @@ on a 1920 x 1080 cut-out frame, and two_calls / rgba on a 200 x 200 sprite (one 
 Every call ends in the engine's stream synchronise, so a host clock around it is the call's time.  The modes are timed in turns (one call of each per
 round, --calls rounds after --warmup rounds) and the median per mode is reported; one JSON line on stdout.
 
+--group resize times, on the same 1080p frame at the x2 and the x3 target (3840 x 2160, 5760 x 3240),
+  two_resized  the route renderRgbaResized replaces: render_resized(bgr), np.repeat of the alpha plane, render_resized(gray), the green channel extracted and stacked
+  rgba_resized render_rgba_resized(bleed=0)
+--group sequence times, per frame, 16 different 1080p frames in page-locked buffers (alloc_host; the outputs go to a ring of four page-locked buffers)
+  rgba_loop     a loop of render_rgba() calls, frame by frame
+  rgba_sequence one render_sequence_rgba() call on the same buffers
+with the same method (modes in turns, median).
+
 --only MODE runs that mode alone (for `rocprofv3 --kernel-trace --stats -- python tools/rgba_bench.py --only rgba_bleed8`, which gives the device time of
 alpha_bleed_kernel / gather_rgba_kernel / compose_rgba_kernel).  --bytes prints the bytes each route moves across PCIe and exits (no GPU).  Not part of
 bench.py."""
@@ -54,14 +62,16 @@ def main() -> int:
     ap.add_argument("--calls", type=int, default=9, help="timed calls per mode (at least 7)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--only", default="", help="one of " + ",".join(MODES) + ": run that mode alone on the 1080p frame")
+    ap.add_argument("--group", default="frames", choices=["frames", "resize", "sequence"], help="frames: the modes above; resize / sequence: the modes of DESIGN 9e")
     ap.add_argument("--work", default=os.path.join(tempfile.gettempdir(), "w2x_rgba_bench"), help="where the synthetic model and its engine file go")
     ap.add_argument("--bytes", action="store_true", help="print the bytes per frame of each route and exit (no GPU)")
     a = ap.parse_args()
     if a.bytes:
         print(json.dumps({"1920x1080": route_bytes(W, H), f"{SPRITE}x{SPRITE}": route_bytes(SPRITE, SPRITE)}))
         return 0
-    if a.only and a.only not in MODES:
-        raise SystemExit(f"--only: {a.only} not in {MODES}")
+    group_modes = {"frames": MODES, "resize": ["two_resized", "rgba_resized"], "sequence": ["rgba_loop", "rgba_sequence"]}[a.group]
+    if a.only and a.only not in group_modes:
+        raise SystemExit(f"--only: {a.only} not in {group_modes}")
     calls = max(a.calls, 7)
     import numpy as np
     import synth_models as sm
@@ -129,15 +139,81 @@ def main() -> int:
         return {m: {"ms_per_call_median": round(statistics.median(times[m]), 3), "ms_min": round(min(times[m]), 3), "ms_max": round(max(times[m]), 3),
                     "batches_reported": batches[m]} for m in modes}
 
+    def timed(r, modes, check=None):
+        """the method of measure() on a dict of calls: an equality check first, warm-up rounds, then the modes in turns"""
+        if check:
+            x = r[check[0]]().copy()
+            assert np.array_equal(x, r[check[1]]()), f"{check[1]} differs from {check[0]}"
+        for _ in range(a.warmup):
+            for m in modes:
+                r[m]()
+        times = {m: [] for m in modes}
+        for _ in range(calls):
+            for m in modes:
+                t0 = time.perf_counter()
+                r[m]()
+                times[m].append((time.perf_counter() - t0) * 1e3)
+        return times
+
+    def measure_resized(bgra, factor, modes):
+        rows, cols = bgra.shape[:2]
+        size = (rows * factor, cols * factor)
+        out4 = np.empty(size + (4,), np.uint8)
+        out3 = np.empty(size + (3,), np.uint8)
+        gray_out = np.empty(size + (3,), np.uint8)
+
+        def two_resized():
+            assert eng.render_resized(np.ascontiguousarray(bgra[..., :3]), size, dst=out3)
+            gray = np.repeat(bgra[..., 3:4], 3, axis=2)
+            assert eng.render_resized(gray, size, dst=gray_out)
+            out4[..., :3] = out3
+            out4[..., 3] = gray_out[..., 1]
+            return out4
+
+        def rgba_resized():
+            assert eng.render_rgba_resized(bgra, size, dst=out4), eng.last_error()
+            return out4
+        r = {"two_resized": two_resized, "rgba_resized": rgba_resized}
+        times = timed(r, modes, ("two_resized", "rgba_resized") if len(modes) == 2 else None)
+        return {m: {"ms_per_call_median": round(statistics.median(times[m]), 3), "ms_min": round(min(times[m]), 3), "ms_max": round(max(times[m]), 3)} for m in modes}
+
+    def measure_sequence(modes, count=16, ring=4):
+        frames = [eng.alloc_host((H, W, 4)) for _ in range(count)]
+        outs = [eng.alloc_host((H * S, W * S, 4)) for _ in range(ring)]
+        for k, f in enumerate(frames):
+            f[...] = cutout(np, H, W, 10 + k)
+        dsts = [outs[k % ring] for k in range(count)]
+
+        def rgba_loop():
+            for k in range(count):
+                assert eng.render_rgba(frames[k], dst=dsts[k]), eng.last_error()
+            return dsts[count - 1]
+
+        def rgba_sequence():
+            eng.render_sequence_rgba(frames, outs=dsts)
+            return dsts[count - 1]
+        r = {"rgba_loop": rgba_loop, "rgba_sequence": rgba_sequence}
+        times = timed(r, modes, ("rgba_loop", "rgba_sequence") if len(modes) == 2 else None)
+        for buf in frames + outs:
+            eng.free_host(buf)
+        return {m: {"ms_per_frame_median": round(statistics.median(times[m]) / count, 3), "ms_per_frame_min": round(min(times[m]) / count, 3),
+                    "ms_per_frame_max": round(max(times[m]) / count, 3), "frames": count} for m in modes}
+
     res = {}
     frame = cutout(np, H, W, 3)
-    if a.only:
+    if a.group == "resize":
+        modes = [a.only] if a.only else ["two_resized", "rgba_resized"]
+        for factor in (2, 3):
+            res[f"{W}x{H} -> {W * factor}x{H * factor}"] = measure_resized(frame, factor, modes)
+    elif a.group == "sequence":
+        res[f"{W}x{H} x16 pinned"] = measure_sequence([a.only] if a.only else ["rgba_loop", "rgba_sequence"])
+    elif a.only:
         res[f"{W}x{H}"] = measure("frame", frame, [a.only])
     else:
         res[f"{W}x{H}"] = measure("frame", frame, MODES)
         res[f"{SPRITE}x{SPRITE}"] = measure("sprite", cutout(np, SPRITE, SPRITE, 4), ["two_calls", "rgba"])
     eng.close()
-    print(json.dumps({"tool": "rgba_bench", "workload": f"{MODEL} x{S} noise{NOISE} batch{BATCH} tile{TILE} fp16, blend 1/16, BGRA frames host to host (pageable numpy arrays), "
+    print(json.dumps({"tool": "rgba_bench", "workload": f"{MODEL} x{S} noise{NOISE} batch{BATCH} tile{TILE} fp16, blend 1/16, BGRA frames host to host ({'page-locked buffers' if a.group == 'sequence' else 'pageable numpy arrays'}), group {a.group}, "
                       f"median of {calls} calls per mode after {a.warmup} warm-up rounds, modes timed in turns", "bytes": {"1920x1080": route_bytes(W, H)}, "results": res}))
     return 0
 

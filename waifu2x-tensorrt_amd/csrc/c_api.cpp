@@ -210,6 +210,39 @@ int w2x_render_rgba(w2x_engine* e, const uint8_t* src, int rows, int cols, size_
     w2x::RgbaOptions o; o.bleed = bleed; o.skipUniformAlpha = skip_uniform_alpha != 0;
     return e->engine.renderRgba(s, d, o) ? 1 : 0;
 }
+int w2x_render_rgba_resized(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, int dst_rows, int dst_cols, size_t dst_step, int bleed,
+                            int skip_uniform_alpha, int filter) {
+    w2x::ResizeFilter f;
+    if (!e || !resize_filter(e, filter, "w2x_render_rgba_resized", f)) return 0;
+    w2x::Image s; s.data = const_cast<uint8_t*>(src); s.rows = rows; s.cols = cols; s.step = src_step;
+    w2x::Image d; d.data = dst; d.rows = dst_rows; d.cols = dst_cols; d.step = dst_step;
+    w2x::RgbaOptions o; o.bleed = bleed; o.skipUniformAlpha = skip_uniform_alpha != 0;
+    return e->engine.renderRgbaResized(s, d, o, f) ? 1 : 0;
+}
+int w2x_render_sequence_rgba(w2x_engine* e, const uint8_t* const* srcs, int rows, int cols, size_t src_step, uint8_t* const* dsts, size_t dst_step, int count, int bleed,
+                             int skip_uniform_alpha) {
+    if (!e || count < 0 || (count > 0 && (!srcs || !dsts))) return 0;
+    const int sc = e->engine.scaling();
+    std::vector<w2x::Image> s(count), d(count);
+    for (int i = 0; i < count; ++i) {
+        s[i].data = const_cast<uint8_t*>(srcs[i]); s[i].rows = rows; s[i].cols = cols; s[i].step = src_step;
+        d[i].data = dsts[i]; d[i].rows = rows * sc; d[i].cols = cols * sc; d[i].step = dst_step;
+    }
+    w2x::RgbaOptions o; o.bleed = bleed; o.skipUniformAlpha = skip_uniform_alpha != 0;
+    return e->engine.renderSequenceRgba(s.data(), d.data(), count, o) ? 1 : 0;
+}
+int w2x_render_sequence_rgba_resized(w2x_engine* e, const uint8_t* const* srcs, int rows, int cols, size_t src_step, uint8_t* const* dsts, int dst_rows, int dst_cols,
+                                     size_t dst_step, int count, int bleed, int skip_uniform_alpha, int filter) {
+    w2x::ResizeFilter f;
+    if (!e || count < 0 || (count > 0 && (!srcs || !dsts)) || !resize_filter(e, filter, "w2x_render_sequence_rgba_resized", f)) return 0;
+    std::vector<w2x::Image> s(count), d(count);
+    for (int i = 0; i < count; ++i) {
+        s[i].data = const_cast<uint8_t*>(srcs[i]); s[i].rows = rows; s[i].cols = cols; s[i].step = src_step;
+        d[i].data = dsts[i]; d[i].rows = dst_rows; d[i].cols = dst_cols; d[i].step = dst_step;
+    }
+    w2x::RgbaOptions o; o.bleed = bleed; o.skipUniformAlpha = skip_uniform_alpha != 0;
+    return e->engine.renderSequenceRgbaResized(s.data(), d.data(), count, o, f) ? 1 : 0;
+}
 int w2x_alpha_bleed_device(w2x_engine* e, const uint8_t* bgra, int rows, int cols, size_t bgra_step, uint8_t* bgr, size_t bgr_step, int radius) {
     if (!e) return 0;
     w2x::Image s; s.data = const_cast<uint8_t*>(bgra); s.rows = rows; s.cols = cols; s.step = bgra_step;

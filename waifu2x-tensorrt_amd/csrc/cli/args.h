@@ -41,8 +41,8 @@ struct Options {
                                           // frames, converted on the GPU (Img2Img::renderSequenceYuv); "" = bgr24 frames, the reference's path
     std::string colorRange = "tv";        // --color_range {tv,pc}: the range of those frames (with --colorspace only)
     int alphaBleed = 0;                   // --alpha-bleed N (0..16): stills with an alpha channel: the colours of the visible pixels are spread N pixels under the
-                                          // transparent ones before the network sees them (Img2Img::renderRgba; on the routes that render colour and alpha in two
-                                          // calls - --devices > 1, --outscale / --outsize - the host alpha_bleed); 0 = the colours as stored
+                                          // transparent ones before the network sees them (Img2Img::renderRgba, with --outscale / --outsize Img2Img::renderRgbaResized; on
+                                          // the routes that render colour and alpha in two calls - --devices > 1 - the host alpha_bleed); 0 = the colours as stored
     bool alphaSkipUniform = false;        // --alpha-skip-uniform: a still whose alpha plane is one value keeps it without running the plane through the network
     bool printConfig = false;             // --print-config: dump the parsed options and derived names as JSON and exit (tests)
     bool help = false;

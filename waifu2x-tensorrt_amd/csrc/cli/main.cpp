@@ -3,8 +3,9 @@
 //   w2x --model swin_unet/art --scale 4 --noise 3 --batchSize 4 --tileSize 256 render -i in.png -o outdir [--tta] [--blend 1/16]
 // Stills (.png / .ppm / .bmp) and uncompressed .avi files are read and written by the built-in codecs (imageio.h); other formats and
 // videos are piped through ffmpeg as raw bgr24 when ffmpeg/ffprobe are on PATH (videoio/capture.cpp:96-99, writer.cpp:24-33 do the same).
-// A PNG / BMP with an alpha channel keeps it (upstream TODO, README.md:88): an 8-bit still on one device at the network's size goes through Img2Img::renderRgba
-// (colour and alpha in one call, --alpha-bleed / --alpha-skip-uniform); on the other routes the alpha plane goes through the same engine as a gray image.
+// A PNG / BMP with an alpha channel keeps it (upstream TODO, README.md:88): an 8-bit still on one device goes through Img2Img::renderRgba, or with --outscale /
+// --outsize through Img2Img::renderRgbaResized (colour and alpha in one call, --alpha-bleed / --alpha-skip-uniform on the GPU); on the other routes
+// (--devices > 1, --deep) the alpha plane goes through the same engine as a gray image.
 // Extension: --devices N drives N engines - a single image is split into tile-column strips (Img2Img::renderStrip), every engine
 // writing its own columns of the shared output buffer; a video is cut into chunks of frames that go round-robin to one persistent
 // worker thread per engine (renderSequence over that engine's page-locked buffers), with one reader and one in-order writer thread.
@@ -270,14 +271,14 @@ int main(int argc, char** argv) {
                     for (char k : oks) all = all && k;
                     return all;
                 };
-                // an 8-bit still with alpha on one device at the network's size: colour and alpha in one renderRgba() call
-                const bool one_call = !in.alpha.empty() && !deep && o.devices == 1 && !resize;
+                // an 8-bit still with alpha on one device: colour and alpha in one renderRgba() call, or one renderRgbaResized() call with --outscale / --outsize
+                const bool one_call = !in.alpha.empty() && !deep && o.devices == 1;
                 if (one_call) {
                     std::vector<uint8_t> bgra((size_t)in.rows * in.cols * 4), obgra((size_t)out.rows * out.cols * 4);
                     for (size_t i = 0; i < in.alpha.size(); ++i) { bgra[4 * i] = in.bgr[3 * i]; bgra[4 * i + 1] = in.bgr[3 * i + 1]; bgra[4 * i + 2] = in.bgr[3 * i + 2]; bgra[4 * i + 3] = in.alpha[i]; }
                     Image s4{bgra.data(), in.rows, in.cols, (size_t)in.cols * 4}, d4{obgra.data(), out.rows, out.cols, (size_t)out.cols * 4};
                     RgbaOptions ro; ro.bleed = o.alphaBleed; ro.skipUniformAlpha = o.alphaSkipUniform;
-                    if (!engines[0]->renderRgba(s4, d4, ro)) return -1;
+                    if (!(resize ? engines[0]->renderRgbaResized(s4, d4, ro, filter) : engines[0]->renderRgba(s4, d4, ro))) return -1;
                     out.alpha.resize((size_t)out.rows * out.cols);
                     for (size_t i = 0; i < out.alpha.size(); ++i) { out.bgr[3 * i] = obgra[4 * i]; out.bgr[3 * i + 1] = obgra[4 * i + 1]; out.bgr[3 * i + 2] = obgra[4 * i + 2]; out.alpha[i] = obgra[4 * i + 3]; }
                 } else {

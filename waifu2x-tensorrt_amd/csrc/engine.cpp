@@ -333,6 +333,10 @@ struct Img2Img::Impl {
     unsigned* d_minmax = nullptr; unsigned* h_minmax = nullptr;
     hipEvent_t ev_minmax = nullptr;
     bool rgba = false;
+    // The RGBA entry points (renderRgba, renderRgbaResized, renderSequenceRgba*): the options of the frames being rendered (null outside such a call).  With it set
+    // run_frame() is rgba_frame(); with `rs` set as well the frame ends with compose_canvas_rgba_kernel and resample_rgba_kernel.
+    struct RgbaJob { int bleed = 0; bool skip = false; };
+    const RgbaJob* rgba_job = nullptr;
     std::vector<void*> pinned;
     std::vector<void*> host_allocs;     // allocHost(): page-locked buffers handed to the caller
     std::vector<TileSlot> h_slots;
@@ -437,7 +441,7 @@ struct Img2Img::Impl {
         if (d_canvas) { (void)hipFree(d_canvas); d_canvas = nullptr; }
         canvas_cap = 0;
         for (void** q : {(void**)&d_bgr, (void**)&d_alpha, (void**)&d_minmax}) if (*q) { (void)hipFree(*q); *q = nullptr; }
-        bgr_cap = alpha_cap = 0; rgba = false;
+        bgr_cap = alpha_cap = 0; rgba = false; rgba_job = nullptr;
         if (h_minmax) { if (hipHostFree(h_minmax) != hipSuccess) (void)hipGetLastError(); h_minmax = nullptr; }
         if (ev_minmax) { (void)hipEventDestroy(ev_minmax); ev_minmax = nullptr; }
         for (void** p : {(void**)&d_frame, (void**)&d_out, (void**)&d_frame2, (void**)&d_out2, &d_slab, &d_slab2, (void**)&d_slots, (void**)&d_live, (void**)&d_rampx, (void**)&d_rampy, (void**)&d_blob_in, (void**)&d_blob_out})
@@ -942,6 +946,7 @@ struct Img2Img::Impl {
 
     // device part of one frame: gather -> network per batch -> compose.  Frame must already be in d_frame.
     void run_frame(int rows, int cols, const TileGrid& grid, bool report, const StripPlan& sp) {
+        if (rgba_job) { rgba_frame(rows, cols, grid, report, nullptr); return; }                               // an RGBA frame of a sequence (renderSequenceRgba)
         run_passes(rows, cols, sp.tile_count, 0, report, 0, true);
         if (rs) { compose_canvas(rows, cols, grid, stream); if (yuv) resample_yuv(stream); else resample(stream); return; }   // a resized frame (renderResized / renderYuvResized)
         if (yuv) { compose_yuv(rows, cols, grid, stream); return; }                       // a YUV frame (renderYuv)
@@ -1083,7 +1088,8 @@ struct Img2Img::Impl {
             auto run_eager = [&] { if (per_group) { fork(); for (int grp = 0; grp < NG; ++grp) run_group(grp); if (!no_join) join(); } else { if (rolling && gstream[0]) { join(); } run_pass(); } };
             if (!graphable) run_eager();
             else {
-                const GraphKey key{d_frame, d_slots + slots_off + (size_t)bi * B, slab_out, arena_base, rows, cols, live, rgba ? kRgbaKey : yuv ? yuv->key : deep ? 1 : 0};
+                // (an RGBA pass reads d_bgr / d_alpha, never d_frame: its graphs do not depend on which frame buffer of a sequence is current)
+                const GraphKey key{rgba ? (const void*)d_bgr : (const void*)d_frame, d_slots + slots_off + (size_t)bi * B, slab_out, arena_base, rows, cols, live, rgba ? kRgbaKey : yuv ? yuv->key : deep ? 1 : 0};
                 auto replay = [&](const PassGraphs& pg) {
                     if (pg.n == 1) { if (rolling && gstream[0]) join(); hipAssert(hipGraphLaunch(pg.g[0], stream)); return; }   // (a whole-arena pass inside a rolling sequence: the other stream's group first)
                     fork();
@@ -1186,10 +1192,17 @@ struct Img2Img::Impl {
     void upload_and_bleed(const Image& src, int radius) {
         const int rows = src.rows, cols = src.cols;
         ensure(d_frame, frame_cap, (size_t)rows * cols * 4);
+        ensure_bleed_planes(rows, cols);
+        hipAssert(hipMemcpy2DAsync(d_frame, (size_t)cols * 4, src.data, src.step, (size_t)cols * 4, rows, hipMemcpyHostToDevice, stream));
+        bleed_frame(rows, cols, radius);
+    }
+    void ensure_bleed_planes(int rows, int cols) {
         ensure(d_bgr, bgr_cap, (size_t)rows * cols * 3);
         ensure(d_alpha, alpha_cap, (size_t)rows * cols);
         if (!d_minmax) hipAssert(hipMalloc((void**)&d_minmax, 2 * sizeof(unsigned)));
-        hipAssert(hipMemcpy2DAsync(d_frame, (size_t)cols * 4, src.data, src.step, (size_t)cols * 4, rows, hipMemcpyHostToDevice, stream));
+    }
+    // the BGRA frame in d_frame (packed) -> d_bgr, d_alpha, d_minmax, on `stream`
+    void bleed_frame(int rows, int cols, int radius) {
         hipAssert(hipMemsetAsync(d_minmax, 0, 2 * sizeof(unsigned), stream));
         AlphaBleedParams bp;
         bp.bgra = d_frame; bp.step = (size_t)cols * 4; bp.rows = rows; bp.cols = cols; bp.radius = radius;
@@ -1210,6 +1223,129 @@ struct Img2Img::Impl {
         rp.alpha_tiles = uniform ? nullptr : (const uint8_t*)d_slab + alpha_slot0 * (size_t)To * To * 4 * plan.elt;
         rp.alpha_value = value;
         hipAssert(launch_compose_rgba(rp, stream));
+    }
+    // a resized RGBA frame (rs set): the whole canvas as four fp32 planes R, G, B, A (uniform: three) into d_canvas, then its resize as BGRA dwords into d_out
+    void compose_canvas_rgba(int rows, int cols, const TileGrid& grid, size_t alpha_slot0, bool uniform) {
+        const int To = plan.Tout;
+        ComposeCanvasRgbaParams rp;
+        ComposeParams& cp = rp.c;
+        cp.tiles = d_slab; cp.fp32 = plan.elt == 4;
+        cp.outW = cols * cfg.scaling; cp.outH = rows * cfg.scaling; cp.To = To;
+        cp.nx = grid.nx; cp.ny = grid.ny; cp.stride_x = To - grid.outOvX; cp.stride_y = To - grid.outOvY;
+        const bool overlapping = cfg.overlapX != 0 || cfg.overlapY != 0;
+        cp.ovx = overlapping ? ovx : 0; cp.ovy = overlapping ? ovy : 0;
+        cp.ramp_x = d_rampx; cp.ramp_y = d_rampy; cp.tta = cfg.tta ? 1 : 0; cp.tta_bug_compat = cfg.ttaBugCompat ? 1 : 0;
+        rp.alpha_tiles = uniform ? nullptr : (const uint8_t*)d_slab + alpha_slot0 * (size_t)To * To * 4 * plan.elt;
+        rp.canvas = d_canvas;
+        hipAssert(launch_compose_canvas_rgba(rp, stream));
+    }
+    void resample_rgba(bool uniform, unsigned value) {
+        ResampleRgbaParams rp;
+        rp.canvas = d_canvas; rp.inW = rs->inW; rp.inH = rs->inH;
+        rp.dst = d_out; rp.dst_step = (size_t)rs->outW * 4;
+        rp.outW = rs->outW; rp.outH = rs->outH;
+        rp.fx = rs->fx; rp.wx = rs->wx; rp.kx = rs->kx; rp.fy = rs->fy; rp.wy = rs->wy; rp.ky = rs->ky; rp.rows_max = rs->rows_max;
+        rp.uniform = uniform ? 1 : 0; rp.alpha_value = value;
+        hipAssert(launch_resample_rgba(rp, stream));
+    }
+    // The refusals and the set-up the RGBA entry points share (renderRgba, renderRgbaResized, renderSequenceRgba*).  rgba_check(): `count` frames of one size,
+    // one target (resizeFilter >= 0: dsts[0]'s size, else the scaled size) and one set of options; returns the message of the first refusal, or "" with `c` filled.
+    // The order is deliberate and the same for one frame and for a sequence: depth, the first frame's size, the target (resize_problem), then per frame its size, its
+    // pointers and steps, then the bleed radius, then the grid - so a null dst with an out-of-range target reports the target.
+    struct RgbaCall { int rows = 0, cols = 0, out_rows = 0, out_cols = 0; bool resized = false; TileGrid grid; };
+    std::string rgba_check(const Image* srcs, const Image* dsts, int count, const RgbaOptions& opt, int resizeFilter, RgbaCall& c) const {
+        const int rows = srcs[0].rows, cols = srcs[0].cols, s = cfg.scaling;
+        for (int i = 0; i < count; ++i) if (srcs[i].depth != 8 || dsts[i].depth != 8) return "RGBA input and output images must be 8-bit.";
+        if (rows <= 0 || cols <= 0) return "Input image is empty or has an invalid step.";
+        const int out_rows = resizeFilter >= 0 ? dsts[0].rows : rows * s, out_cols = resizeFilter >= 0 ? dsts[0].cols : cols * s;
+        if (resizeFilter >= 0) {
+            const std::string why = resize_problem(rows, cols, out_rows, out_cols, resizeFilter);
+            if (!why.empty()) return why;
+        }
+        for (int i = 0; i < count; ++i) {
+            if (srcs[i].rows != rows || srcs[i].cols != cols) return "Input images must be of one size.";
+            if (!srcs[i].data || srcs[i].step < (size_t)cols * 4) return "Input image is empty or has an invalid step.";
+            if (!dsts[i].data || dsts[i].rows != out_rows || dsts[i].cols != out_cols || dsts[i].step < (size_t)out_cols * 4)
+                return "Output image has invalid size: expected " + std::to_string(out_cols) + "x" + std::to_string(out_rows) + ".";
+        }
+        if (opt.bleed < 0 || opt.bleed > kBleedMaxRadius) return "Alpha bleed radius " + std::to_string(opt.bleed) + " is not in [0, " + std::to_string(kBleedMaxRadius) + "].";
+        c.rows = rows; c.cols = cols; c.out_rows = out_rows; c.out_cols = out_cols;
+        c.resized = resizeFilter >= 0 && !(out_rows == rows * s && out_cols == cols * s);   // at the scaled size the call is the plain one
+        c.grid = calculate_tiles(cols, rows, cols * s, rows * s, plan.T, plan.T, plan.Tout, plan.Tout, s, cfg.overlapX, cfg.overlapY);
+        if (c.grid.count <= 0) return "Tile grid is empty.";
+        for (const Rect& r : c.grid.out) if (r.w <= 0 || r.h <= 0) return "Tile grid does not fit the output (scaling does not match the model).";
+        return "";
+    }
+    // resets what rgba_begin() sets, on every exit of an RGBA entry point (also on exceptions)
+    struct RgbaScope { Impl* im; ~RgbaScope() { im->rgba = false; im->rgba_job = nullptr; im->rs = nullptr; } };
+    // after the frame and output buffers are sized: the frame is marked not replayable, the shared tables are made, `rs` and the four-plane canvas of a resized call
+    void rgba_begin(const RgbaCall& c, const RgbaJob& job, int resizeFilter) {
+        deep = false;
+        last_rows = last_cols = 0;   // (d_frame / d_out hold BGRA from here on: not replayed by benchResident / residentOutput / profileFrame)
+        rgba_setup(c.rows, c.cols, c.grid, job.skip);
+        if (c.resized) {
+            const int s = cfg.scaling;
+            rs = resize_tables(c.cols * s, c.rows * s, c.out_cols, c.out_rows, resizeFilter);
+            ensure_canvas((size_t)c.rows * s * c.cols * s * 4 * sizeof(float));
+        }
+        rgba_job = &job;
+    }
+    // What the frames of an RGBA call share, made once per call (the RGBA counterpart of sequence_slots): the planes the bleed writes, the two words' host side,
+    // and the slot table, liveness table and slab of the 2N schedule - slot = step index, tile = step / stepsPerTile over the 2N tiles (colour 0 .. N - 1,
+    // alpha N .. 2N - 1), zero pad slots at the end.  A frame whose alpha tiles are skipped runs a prefix of the same table.
+    void rgba_setup(int rows, int cols, const TileGrid& grid, bool skip) {
+        const int steps = cfg.tta ? 8 : 1, B = plan.B, S = plan.B / plan.userB, N = grid.count;
+        const int batches = (int)std::lround(std::ceil((double)(2 * N * steps) / plan.userB));   // img2img_render.cpp:249
+        const size_t stepTotal = (size_t)((batches + S - 1) / S) * B;
+        ensure_bleed_planes(rows, cols);
+        if (skip) {
+            if (!h_minmax) hipAssert(hipHostMalloc((void**)&h_minmax, 2 * sizeof(unsigned), hipHostMallocDefault));
+            if (!ev_minmax) hipAssert(hipEventCreateWithFlags(&ev_minmax, hipEventDisableTiming));
+        }
+        h_slots.resize(stepTotal);
+        for (size_t st = 0; st < stepTotal; ++st) {
+            const int ti = (int)(st / steps), aug = (int)(st % steps);
+            TileSlot sl{0, 0, aug, 0};
+            if (ti < 2 * N) { sl.x = grid.in[ti % N].x; sl.y = grid.in[ti % N].y; sl.valid = ti < N ? kSlotColour : kSlotAlpha; }
+            h_slots[st] = sl;
+        }
+        ensure(d_slots, slots_cap, stepTotal * sizeof(TileSlot));
+        hipAssert(hipMemcpyAsync(d_slots, h_slots.data(), stepTotal * sizeof(TileSlot), hipMemcpyHostToDevice, stream));
+        upload_live(grid, stepTotal, stream);
+        ensure(d_slab, slab_cap, stepTotal * plan.Tout * plan.Tout * 4 * plan.elt);
+        one_part_stale = false;
+    }
+    // The device part of one RGBA frame, on `stream`, with the BGRA frame in d_frame and rgba_setup() done: alpha_bleed_kernel, ONE schedule of the frame's N
+    // colour tiles followed by its N alpha tiles, then compose_rgba_kernel - or, with rs set, compose_canvas_rgba_kernel and resample_rgba_kernel - into d_out.
+    // skip (skipUniformAlpha): the two words come back behind the bleed kernel while the passes that hold colour tiles only - the same in the 2N and the N
+    // schedule - are issued; the host waits for them, then issues the rest of whichever schedule the frame takes.  `started`: recorded behind the bleed.
+    void rgba_frame(int rows, int cols, const TileGrid& grid, bool report, hipEvent_t started) {
+        const RgbaJob job = *rgba_job;
+        const int steps = cfg.tta ? 8 : 1, B = plan.B, S = plan.B / plan.userB, N = grid.count;
+        auto batches_of = [&](int tiles) { return (int)std::lround(std::ceil((double)(tiles * steps) / plan.userB)); };
+        bleed_frame(rows, cols, job.bleed);
+        if (job.skip) {
+            hipAssert(hipMemcpyAsync(h_minmax, d_minmax, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
+            hipAssert(hipEventRecord(ev_minmax, stream));
+        }
+        if (started) hipAssert(hipEventRecord(started, stream));
+        rgba = true;
+        bool uniform = false; unsigned value = 255;
+        if (!job.skip) run_passes(rows, cols, 2 * N, 0, report, 0, true);
+        else {
+            const int F = N * steps / B;                 // passes of colour tiles only: the same launches whether the alpha tiles follow or not
+            const auto t0 = std::chrono::steady_clock::now();
+            run_passes(rows, cols, 2 * N, 0, false, 0, true, 0, 0, 0, F);
+            hipAssert(hipEventSynchronize(ev_minmax));
+            uniform = h_minmax[0] + h_minmax[1] == 255u;      // max(A) + max(255 - A) == 255  <=>  min(A) == max(A)
+            value = h_minmax[0];
+            const int tiles = uniform ? N : 2 * N, batchCount = batches_of(tiles);
+            const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
+            if (report) for (int k = 0; k < std::min(F * S, batchCount); ++k) log(k + 1, batchCount, 1000.0 * F * S / std::max(ms, 1e-6));
+            run_passes(rows, cols, tiles, 0, report, 0, false, 0, 0, F, -1);
+        }
+        if (rs) { compose_canvas_rgba(rows, cols, grid, (size_t)N * steps, uniform); resample_rgba(uniform, value); }
+        else compose_rgba(rows, cols, grid, (size_t)N * steps, uniform, value);
     }
     // the slot table and the slab of a sequence's frames (renderSequence / renderSequenceYuv): every tile of the frame, in one part
     void sequence_slots(const TileGrid& grid, const StripPlan& sp) {
@@ -1238,7 +1374,10 @@ struct Img2Img::Impl {
         uint8_t* const outs[2] = {d_out, d_out2};
         struct Restore { Impl* im; uint8_t* f; uint8_t* o; ~Restore() { im->d_frame = f; im->d_out = o; } } restore{this, frames[0], outs[0]};   // also on exceptions
         // frame f is composed on the second group's stream while frame f + 1's first group already runs (run_rolling_frame) when every pass of a frame splits
-        const bool roll = count > 1 && can_roll(sp.tile_count);
+        // RGBA frames do not roll: d_bgr, d_alpha and d_minmax are single buffers the bleed writes on the compute stream, and in a rolling sequence the second
+        // tile group of frame f would still gather from them while frame f + 1 bleeds into them.  Through run_frame() every pass joins its groups before the
+        // next launch on `stream`, so stream order alone keeps the single buffers (and the one slab and canvas) safe.
+        const bool roll = count > 1 && !rgba_job && can_roll(sp.tile_count);
         if (roll) ensure(d_slab2, slab2_cap, slab_cap);
         hipAssert(hipStreamSynchronize(stream));
         hipAssert(hipEventRecord(ev0, stream));
@@ -2152,77 +2291,73 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
 // plane's range), ONE schedule of the frame's N colour tiles followed by its N alpha tiles - cut into reference batches and network passes as run_passes() cuts any
 // tile count, so a pass at the boundary holds tiles of both kinds -, compose_rgba_kernel, one download (4 bytes per output pixel).  A single part on the compute
 // stream: the multi-part overlap of render() is not used here.  skipUniformAlpha: the two words come back behind the bleed kernel while the passes that hold colour
-// tiles only - the same in the 2N and the N schedule - are issued; their progress is reported once the total is known.
-bool Img2Img::renderRgba(const Image& src, Image& dst, const RgbaOptions& opt) try {
-    const char* who = "renderRgba";
+// tiles only - the same in the 2N and the N schedule - are issued; their progress is reported once the total is known.  (The frame step is Impl::rgba_frame.)
+bool Img2Img::renderRgba(const Image& src, Image& dst, const RgbaOptions& opt) { return renderRgbaFrame(src, dst, opt, -1, "renderRgba"); }
+
+// renderRgba() with the canvas resized to dst.rows x dst.cols: the same upload, bleed and schedule, then compose_canvas_rgba_kernel (four fp32 planes,
+// not quantised) and resample_rgba_kernel (the resize of renderResized over the four planes, BGRA dwords), the download of the target.  Colour and alpha are resized
+// separately and straight.  At the scaled size it is renderRgba().
+bool Img2Img::renderRgbaResized(const Image& src, Image& dst, const RgbaOptions& opt, ResizeFilter filter) {
+    return renderRgbaFrame(src, dst, opt, filter == ResizeFilter::Bilinear ? 1 : filter == ResizeFilter::Bicubic ? 0 : 2, "renderRgbaResized");
+}
+
+bool Img2Img::renderRgbaFrame(const Image& src, Image& dst, const RgbaOptions& opt, int resizeFilter, const char* who) try {
     if (!impl->loaded) { W2X_LOG_AS(who, error, "Render called before a successful load."); return false; }
     DeviceGuard guard(impl->device);
-    const RenderConfig& cfg = impl->cfg;
-    const Plan& plan = impl->plan;
-    const int rows = src.rows, cols = src.cols, s = cfg.scaling;
-    if (src.depth != 8 || dst.depth != 8) { W2X_LOG_AS(who, error, "RGBA input and output images must be 8-bit."); return false; }
-    if (!src.data || rows <= 0 || cols <= 0 || src.step < (size_t)cols * 4) { W2X_LOG_AS(who, error, "Input image is empty or has an invalid step."); return false; }
-    if (!dst.data || dst.rows != rows * s || dst.cols != cols * s || dst.step < (size_t)dst.cols * 4) {
-        W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(cols * s) + "x" + std::to_string(rows * s) + ".");
-        return false;
-    }
-    if (opt.bleed < 0 || opt.bleed > kBleedMaxRadius) { W2X_LOG_AS(who, error, "Alpha bleed radius " + std::to_string(opt.bleed) + " is not in [0, " + std::to_string(kBleedMaxRadius) + "]."); return false; }
+    Impl::RgbaCall c;
+    if (const std::string why = impl->rgba_check(&src, &dst, 1, opt, resizeFilter, c); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
     hipStream_t stream = impl->stream;
-    TileGrid grid = calculate_tiles(cols, rows, cols * s, rows * s, plan.T, plan.T, plan.Tout, plan.Tout, s, cfg.overlapX, cfg.overlapY);
-    if (grid.count <= 0) { W2X_LOG_AS(who, error, "Tile grid is empty."); return false; }
-    for (const Rect& r : grid.out) if (r.w <= 0 || r.h <= 0) { W2X_LOG_AS(who, error, "Tile grid does not fit the output (scaling does not match the model)."); return false; }
-    const int steps = cfg.tta ? 8 : 1, B = plan.B, S = plan.B / plan.userB, N = grid.count;
-    auto batches_of = [&](int tiles) { return (int)std::lround(std::ceil((double)(tiles * steps) / plan.userB)); };   // img2img_render.cpp:249
-    const size_t stepTotal = (size_t)((batches_of(2 * N) + S - 1) / S) * B;
-    struct RgbaScope { Impl* im; ~RgbaScope() { im->rgba = false; } } rgba_scope{impl.get()};   // also on exceptions
-    impl->deep = false;
-    impl->last_rows = impl->last_cols = 0;   // (d_frame / d_out hold BGRA from here on: not replayed by benchResident / residentOutput / profileFrame)
-    impl->ensure(impl->d_out, impl->out_cap, (size_t)dst.rows * dst.cols * 4);
-    impl->upload_and_bleed(src, opt.bleed);
-    if (opt.skipUniformAlpha) {
-        if (!impl->h_minmax) hipAssert(hipHostMalloc((void**)&impl->h_minmax, 2 * sizeof(unsigned), hipHostMallocDefault));
-        if (!impl->ev_minmax) hipAssert(hipEventCreateWithFlags(&impl->ev_minmax, hipEventDisableTiming));
-        hipAssert(hipMemcpyAsync(impl->h_minmax, impl->d_minmax, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
-        hipAssert(hipEventRecord(impl->ev_minmax, stream));
-    }
-    // the schedule: slot = step index, tile = step / stepsPerTile over the 2N tiles (colour 0 .. N - 1, alpha N .. 2N - 1), zero pad slots at the end
-    impl->h_slots.resize(stepTotal);
-    for (size_t st = 0; st < stepTotal; ++st) {
-        const int ti = (int)(st / steps), aug = (int)(st % steps);
-        TileSlot sl{0, 0, aug, 0};
-        if (ti < 2 * N) { sl.x = grid.in[ti % N].x; sl.y = grid.in[ti % N].y; sl.valid = ti < N ? kSlotColour : kSlotAlpha; }
-        impl->h_slots[st] = sl;
-    }
-    impl->ensure(impl->d_slots, impl->slots_cap, stepTotal * sizeof(TileSlot));
-    hipAssert(hipMemcpyAsync(impl->d_slots, impl->h_slots.data(), stepTotal * sizeof(TileSlot), hipMemcpyHostToDevice, stream));
-    impl->upload_live(grid, stepTotal, stream);
-    impl->ensure(impl->d_slab, impl->slab_cap, stepTotal * plan.Tout * plan.Tout * 4 * plan.elt);
-    impl->one_part_stale = false;
-    hipAssert(hipEventRecord(impl->ev0, stream));
-    impl->rgba = true;
-    bool uniform = false; unsigned value = 255;
-    if (!opt.skipUniformAlpha) impl->run_passes(rows, cols, 2 * N, 0, true, 0, true);
-    else {
-        const int F = N * steps / B;                 // passes of colour tiles only: the same launches whether the alpha tiles follow or not
-        const auto t0 = std::chrono::steady_clock::now();
-        impl->run_passes(rows, cols, 2 * N, 0, false, 0, true, 0, 0, 0, F);
-        hipAssert(hipEventSynchronize(impl->ev_minmax));
-        uniform = impl->h_minmax[0] + impl->h_minmax[1] == 255u;      // max(A) + max(255 - A) == 255  <=>  min(A) == max(A)
-        value = impl->h_minmax[0];
-        const int tiles = uniform ? N : 2 * N, batchCount = batches_of(tiles);
-        const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
-        for (int k = 0; k < std::min(F * S, batchCount); ++k) impl->log(k + 1, batchCount, 1000.0 * F * S / std::max(ms, 1e-6));
-        impl->run_passes(rows, cols, tiles, 0, true, 0, false, 0, 0, F, -1);
-    }
-    impl->compose_rgba(rows, cols, grid, (size_t)N * steps, uniform, value);
+    Impl::RgbaScope rgba_scope{impl.get()};
+    impl->ensure(impl->d_frame, impl->frame_cap, (size_t)c.rows * c.cols * 4);
+    impl->ensure(impl->d_out, impl->out_cap, (size_t)c.out_rows * c.out_cols * 4);
+    const Impl::RgbaJob job{opt.bleed, opt.skipUniformAlpha};
+    impl->rgba_begin(c, job, resizeFilter);
+    hipAssert(hipMemcpy2DAsync(impl->d_frame, (size_t)c.cols * 4, src.data, src.step, (size_t)c.cols * 4, c.rows, hipMemcpyHostToDevice, stream));
+    impl->rgba_frame(c.rows, c.cols, c.grid, true, impl->ev0);
     hipAssert(hipEventRecord(impl->ev1, stream));
-    hipAssert(hipMemcpy2DAsync(dst.data, dst.step, impl->d_out, (size_t)dst.cols * 4, (size_t)dst.cols * 4, dst.rows, hipMemcpyDeviceToHost, stream));
+    hipAssert(hipMemcpy2DAsync(dst.data, dst.step, impl->d_out, (size_t)c.out_cols * 4, (size_t)c.out_cols * 4, c.out_rows, hipMemcpyDeviceToHost, stream));
     hipAssert(hipStreamSynchronize(stream));
     hipAssert(hipEventElapsedTime(&impl->last_ms, impl->ev0, impl->ev1));
     return true;
 } catch (const std::exception& e) {
     impl->drain_after_error();
-    W2X_LOG_AS("renderRgba", error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
+    W2X_LOG_AS(who, error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
+    return false;
+}
+
+// RGBA frames through renderSequence()'s pipeline: frame i is uploaded at 4 bytes per pixel on s_up into one of two frame buffers, its frame step
+// (Impl::rgba_frame) runs on the compute stream into one of two output buffers, and the output leaves at 4 bytes per pixel on s_dn while frame i + 1 runs.
+// One size, one target and one set of options for the sequence; output i is the bytes of the single-frame call on frame i.  No progress is reported.
+bool Img2Img::renderSequenceRgba(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt) { return runSequenceRgba(srcs, dsts, count, opt, -1, "renderSequenceRgba"); }
+
+bool Img2Img::renderSequenceRgbaResized(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt, ResizeFilter filter) {
+    return runSequenceRgba(srcs, dsts, count, opt, filter == ResizeFilter::Bilinear ? 1 : filter == ResizeFilter::Bicubic ? 0 : 2, "renderSequenceRgbaResized");
+}
+
+bool Img2Img::runSequenceRgba(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt, int resizeFilter, const char* who) try {
+    if (!impl->loaded) { W2X_LOG_AS(who, error, "Render called before a successful load."); return false; }
+    if (count <= 0) return true;
+    if (!srcs || !dsts) { W2X_LOG_AS(who, error, "No frames given."); return false; }
+    DeviceGuard guard(impl->device);
+    Impl::RgbaCall c;
+    if (const std::string why = impl->rgba_check(srcs, dsts, count, opt, resizeFilter, c); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
+    const int rows = c.rows, cols = c.cols, out_rows = c.out_rows, out_cols = c.out_cols;
+    const StripPlan sp = strip_plan(c.grid, cols * impl->cfg.scaling, impl->plan.Tout, 0, 1);
+    Impl::RgbaScope rgba_scope{impl.get()};
+    impl->ensure_copy_streams();
+    const size_t in_bytes = (size_t)rows * cols * 4, out_bytes = (size_t)out_rows * out_cols * 4;
+    impl->ensure(impl->d_frame, impl->frame_cap, in_bytes);   impl->ensure(impl->d_frame2, impl->frame2_cap, in_bytes);
+    impl->ensure(impl->d_out, impl->out_cap, out_bytes);      impl->ensure(impl->d_out2, impl->out2_cap, out_bytes);
+    const Impl::RgbaJob job{opt.bleed, opt.skipUniformAlpha};
+    impl->rgba_begin(c, job, resizeFilter);
+    const float total_ms = impl->run_sequence(count, rows, cols, c.grid, sp,
+        [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dev, (size_t)cols * 4, srcs[i].data, srcs[i].step, (size_t)cols * 4, rows, hipMemcpyHostToDevice, on)); },
+        [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dsts[i].data, dsts[i].step, dev, (size_t)out_cols * 4, (size_t)out_cols * 4, out_rows, hipMemcpyDeviceToHost, on)); });
+    impl->last_ms = total_ms / count;
+    return true;
+} catch (const std::exception& e) {
+    impl->drain_after_error();
+    W2X_LOG_AS(who, error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
     return false;
 }
 

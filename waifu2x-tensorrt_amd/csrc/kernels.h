@@ -357,6 +357,29 @@ struct ComposeRgbaParams {
     unsigned alpha_value = 255;
 };
 hipError_t launch_compose_rgba(const ComposeRgbaParams& p, hipStream_t s);
+// Resized RGBA frames (renderRgbaResized; k_rgba.hip).
+// compose_canvas_rgba_kernel: compose_canvas_kernel over both tile sets of an RGBA frame - the colour tiles' sums as the fp32 planes R, G, B (what
+// compose_canvas_kernel writes for the colour frame) and the green sum of the alpha tiles as a fourth plane A (what it writes into plane 1 for the gray
+// image): canvas[c][Y][X], plane stride outW * outH, whole canvas (c.x0..y1, c.dst, c.deep unused).  alpha_tiles == nullptr: three planes.
+struct ComposeCanvasRgbaParams {
+    ComposeParams c;
+    const void* alpha_tiles = nullptr;
+    float* canvas = nullptr;
+};
+hipError_t launch_compose_canvas_rgba(const ComposeCanvasRgbaParams& p, hipStream_t s);
+// resample_rgba_kernel: resample_kernel's resize (same tap tables, same rows_max, same accumulation per plane) over the four planes of that canvas, each
+// quantised sat(rint(x * 255)) and stored as one dword B | G << 8 | R << 16 | A << 24 per pixel into dst (dst_step bytes per row, a multiple of 4).
+// uniform != 0: the canvas has three planes, none is filtered for alpha and A = alpha_value everywhere.
+struct ResampleRgbaParams {
+    const float* canvas = nullptr; int inW = 0, inH = 0;
+    uint8_t* dst = nullptr; size_t dst_step = 0;
+    int outW = 0, outH = 0;
+    const int* fx = nullptr; const float* wx = nullptr; int kx = 0;
+    const int* fy = nullptr; const float* wy = nullptr; int ky = 0;
+    int rows_max = 0;
+    int uniform = 0; unsigned alpha_value = 255;
+};
+hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s);
 // k_resample.hip resample_yuv_kernel: resample_kernel's resize of the fp32 RGB canvas (same tap tables, same rows_max) with compose_yuv_kernel's
 // encoding behind it instead of the BGR quantisation: the resized R, G, B clamped to [0, 1] and written as YUV 4:2:0 planes of outH x outW
 // (dst.rows x dst.cols), Y per pixel, Cb / Cr of the RGB filtered (1/4, 1/2, 1/4) x (1/2, 1/2) onto each chroma site (renderYuvResized)

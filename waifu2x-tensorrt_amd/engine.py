@@ -149,6 +149,10 @@ def lib():
     L.w2x_render_yuv_resized.argtypes = L.w2x_render_yuv.argtypes + [C.c_int]; L.w2x_render_yuv_resized.restype = C.c_int
     L.w2x_render_sequence_yuv_resized.argtypes = L.w2x_render_sequence_yuv.argtypes + [C.c_int]; L.w2x_render_sequence_yuv_resized.restype = C.c_int
     L.w2x_render_rgba.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]; L.w2x_render_rgba.restype = C.c_int
+    L.w2x_render_rgba_resized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int]; L.w2x_render_rgba_resized.restype = C.c_int
+    L.w2x_render_sequence_rgba.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, C.c_int]; L.w2x_render_sequence_rgba.restype = C.c_int
+    L.w2x_render_sequence_rgba_resized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.w2x_render_sequence_rgba_resized.restype = C.c_int
     L.w2x_alpha_bleed_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int]; L.w2x_alpha_bleed_device.restype = C.c_int
     L.w2x_alpha_bleed.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t]; L.w2x_alpha_bleed.restype = C.c_int
     L.w2x_yuv_plane_sizes.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp]; L.w2x_yuv_plane_sizes.restype = C.c_int
@@ -196,7 +200,7 @@ EXPORTED_SYMBOLS = [
     "w2x_render", "w2x_render16", "w2x_infer", "w2x_output_tile_size", "w2x_plan_flops", "w2x_pass_tiles", "w2x_last_render_ms", "w2x_bench_resident", "w2x_resident_output", "w2x_profile_frame", "w2x_op_times",
     "w2x_render_resized", "w2x_render16_resized", "w2x_render_sequence_resized", "w2x_resize_weights",
     "w2x_render_yuv", "w2x_render_sequence_yuv", "w2x_yuv_plane_sizes", "w2x_render_yuv_resized", "w2x_render_sequence_yuv_resized",
-    "w2x_render_rgba", "w2x_alpha_bleed_device", "w2x_alpha_bleed", "w2x_dead_skip_extents",
+    "w2x_render_rgba", "w2x_render_rgba_resized", "w2x_render_sequence_rgba", "w2x_render_sequence_rgba_resized", "w2x_alpha_bleed_device", "w2x_alpha_bleed", "w2x_dead_skip_extents",
     "w2x_render_strip", "w2x_strip_plan", "w2x_render_sharded", "w2x_shard_plan", "w2x_shard_compute", "w2x_shard_slab", "w2x_shard_finish", "w2x_ipc_export", "w2x_ipc_open", "w2x_ipc_close", "w2x_render_sequence", "w2x_alloc_host", "w2x_free_host", "w2x_pin_host", "w2x_unpin_host", "w2x_calculate_tiles", "w2x_tile_weights", "w2x_describe_plan", "w2x_describe_plan_precision", "w2x_write_engine_file", "w2x_validate_engine_file", "w2x_device_pci_bus_id", "w2x_sha256_hex", "w2x_version", "w2x_debug_set"]
 
 
@@ -311,6 +315,86 @@ class Img2Img:
                 raise W2xError(self.last_error() or "render_rgba failed")
             return dst
         return ok
+
+    def render_rgba_resized(self, bgra: np.ndarray, size, *, bleed: int = 0, skip_uniform_alpha: bool = False, filter: str = "bicubic", dst: np.ndarray | None = None):
+        """render_rgba() with the output resized on the device to size = (rows, cols), each in [input dim, input dim * scaling] (w2x_render_rgba_resized):
+        colour and alpha are resized separately and straight, with the filters of render_resized().  With dst=None returns the [rows, cols, 4] array or
+        raises; with dst returns a bool."""
+        ret_array = dst is None
+        ok = isinstance(bgra, np.ndarray) and bgra.ndim == 3 and bgra.shape[2] == 4
+        if ok and bgra.dtype != np.uint8:
+            # the C ABI carries no sample depth: deeper frames are refused here, with the engine's message
+            self._on_msg(int(Severity.error), b"[renderRgbaResized@0] RGBA input and output images must be 8-bit.", None)
+            if ret_array:
+                raise W2xError(self.last_error())
+            return False
+        if not ok or bgra.strides[2] != 1 or bgra.strides[1] != 4:
+            raise ValueError("bgra must be a uint8 [rows, cols, 4] BGRA array with packed pixels")
+        rows, cols = int(size[0]), int(size[1])
+        fid = _filter_id(filter)
+        if dst is None:
+            dst = np.empty((max(rows, 0), max(cols, 0), 4), np.uint8)
+        if dst.dtype != np.uint8 or dst.shape != (rows, cols, 4) or (dst.size and (dst.strides[2] != 1 or dst.strides[1] != 4)):
+            raise ValueError("dst must be a uint8 [rows, cols, 4] array of the target size with packed pixels")   # (an empty target: refused by the library)
+        ok = bool(self._L.w2x_render_rgba_resized(self._h, bgra.ctypes.data if bgra.size else None, bgra.shape[0], bgra.shape[1], bgra.strides[0],
+                                                  dst.ctypes.data if dst.size else None, rows, cols, dst.strides[0], int(bleed), 1 if skip_uniform_alpha else 0, fid))
+        if ret_array:
+            if not ok:
+                raise W2xError(self.last_error() or "render_rgba_resized failed")
+            return dst
+        return ok
+
+    def render_sequence_rgba(self, frames, *, size=None, bleed: int = 0, skip_uniform_alpha: bool = False, filter: str = "bicubic", outs=None, pinned: bool = False):
+        """Equally sized uint8 [rows, cols, 4] BGRA frames with upload / compute / download overlapped (w2x_render_sequence_rgba); with size = (rows, cols) every
+        frame is resized like render_rgba_resized() (w2x_render_sequence_rgba_resized).  Output i is the bytes of the single-frame call on frame i.
+        outs / pinned as in render_sequence()."""
+        s = getattr(self, "_scaling", 0)
+        n = len(frames)
+        if n == 0:
+            return []
+        r, c = frames[0].shape[:2]
+        for f in frames:
+            if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 4 or f.strides != (f.shape[1] * 4, 4, 1):
+                raise ValueError("frames must be packed uint8 [rows, cols, 4] arrays")
+            if f.shape != (r, c, 4):
+                # the C ABI carries one size for the sequence: frames that differ are refused here, with the engine's message
+                self._on_msg(int(Severity.error), b"[renderSequenceRgba@0] Input images must be of one size.", None)
+                raise W2xError(self.last_error())
+        rows, cols = (r * s, c * s) if size is None else (int(size[0]), int(size[1]))
+        fid = _filter_id(filter)
+        own = []
+        if outs is None:
+            if pinned:
+                own = [self.alloc_host((rows, cols, 4)) for _ in range(min(n, 3))]
+            else:
+                outs = [np.empty((rows, cols, 4), np.uint8) for _ in range(n)]
+        for o in (own or outs):
+            if o.dtype != np.uint8 or o.shape != (rows, cols, 4) or o.strides != (cols * 4, 4, 1):
+                raise ValueError("outs must be packed uint8 [rows, cols, 4] arrays of the output size")
+        flags = (int(bleed), 1 if skip_uniform_alpha else 0)
+
+        def run(fs, os_):
+            m = len(fs)
+            sp = (C.c_void_p * m)(*[f.ctypes.data for f in fs]); dp = (C.c_void_p * m)(*[o.ctypes.data for o in os_])
+            if size is None:
+                ok = self._L.w2x_render_sequence_rgba(self._h, sp, r, c, c * 4, dp, cols * 4, m, *flags)
+            else:
+                ok = self._L.w2x_render_sequence_rgba_resized(self._h, sp, r, c, c * 4, dp, rows, cols, cols * 4, m, *flags, fid)
+            if not ok:
+                raise W2xError(self.last_error() or "render_sequence_rgba failed")
+        if own:          # a ring of engine-owned buffers: the sequence in pieces, each result copied out
+            res = []
+            try:
+                for k0 in range(0, n, len(own)):
+                    m = min(len(own), n - k0)
+                    run(frames[k0:k0 + m], own[:m])
+                    res += [o.copy() for o in own[:m]]
+            finally:
+                for o in own:
+                    self.free_host(o)
+            return res
+        run(frames, outs)
+        return outs
 
     def alpha_bleed_device(self, bgra: np.ndarray, radius: int) -> np.ndarray:
         """Test hook (w2x_alpha_bleed_device): the device bleed alone on a uint8 [rows, cols, 4] BGRA frame -> the [rows, cols, 3] BGR frame the tiles are read from"""
