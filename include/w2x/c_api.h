@@ -32,6 +32,8 @@ enum { W2X_RESIZE_BICUBIC = 0, W2X_RESIZE_BILINEAR = 1 };   /* extension: the fi
 /* extension: the matrix and range of the YUV renders (include/w2x/img2img.h YuvMatrix / YuvRange) */
 enum { W2X_YUV_BT601 = 0, W2X_YUV_BT709 = 1, W2X_YUV_BT2020 = 2 };
 enum { W2X_YUV_LIMITED = 0, W2X_YUV_FULL = 1 };
+/* extension: the plane layouts of the YUV renders (include/w2x/img2img.h YuvLayout): yuv420p, yuv422p, yuv444p (10 bits: ...p10le) and nv12 (10 bits: p010le) */
+enum { W2X_YUV_I420 = 0, W2X_YUV_I422 = 1, W2X_YUV_I444 = 2, W2X_YUV_NV12 = 3 };
 
 typedef struct w2x_build_config {   /* trt::BuildConfig, config.h:12-31 */
     int deviceId, precision;
@@ -109,6 +111,16 @@ int w2x_render_yuv(w2x_engine* e, const void* const* src_planes, const size_t* s
  * pair of depths for the sequence */
 int w2x_render_sequence_yuv(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
                             void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int count, int matrix, int range);
+/* Extension (YuvImage::layout): w2x_render_yuv / w2x_render_sequence_yuv on frames of any W2X_YUV_I420 .. _NV12 layout, chosen independently for
+ * src and dst like the depths (nv12 in, yuv444p10le out).  Plane arrays stay three pointers and three steps per frame.  I422: U and V are rows x (cols + 1) / 2;
+ * I444: rows x cols; NV12: planes[1] holds (rows + 1) / 2 rows of 2 * ((cols + 1) / 2) samples U, V, U, V, ... and planes[2] / steps[2] are ignored (may be NULL /
+ * 0); NV12 at 10 bits is P010: each uint16 of Y and UV carries its code in the HIGH 10 bits (read v >> 6, written code << 6; the planar layouts keep the low 10).
+ * With both layouts W2X_YUV_I420 the bytes are w2x_render_yuv's.  Unknown layouts, a missing plane or a step shorter than the layout's row return 0 through
+ * the message callback, with whatever w2x_render_yuv refuses.  (The resized calls below take I420 only.) */
+int w2x_render_yuv_layout(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits, int src_layout,
+                          void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int dst_layout, int matrix, int range);
+int w2x_render_sequence_yuv_layout(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits, int src_layout,
+                                   void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int dst_layout, int count, int matrix, int range);
 /* Extension (Img2Img::renderYuvResized): w2x_render_yuv with the canvas resized on the device to dst_rows x dst_cols before it is encoded (the filter and
  * the size rule of w2x_render_resized: each target dimension in [input dim, input dim * scaling], the two independent, odd sizes allowed; the resized RGB
  * is clamped and coded as w2x_render_yuv codes the canvas).  At the scaled size the bytes are w2x_render_yuv's.  What w2x_render_yuv refuses, other
@@ -171,6 +183,10 @@ int w2x_resize_weights(int in, int out, int filter, int* first, float* weights, 
 /* The planes of a packed YUV 4:2:0 frame of rows x cols at `bits` (8 or 10): plane_rows[k], plane_cols[k] (samples) and plane_bytes[k] = rows * cols *
  * bytes per sample, k = Y, U, V.  Returns 1; 0 (nothing written) for an empty frame or other depths.  Any output pointer may be NULL. */
 int w2x_yuv_plane_sizes(int rows, int cols, int bits, int* plane_rows, int* plane_cols, size_t* plane_bytes);
+/* The same for a frame of `layout` (W2X_YUV_I420 .. _NV12): *nplanes = 3, or 2 for NV12 (Y, UV); plane_cols[k] counts the SAMPLES of a row (NV12's UV plane:
+ * 2 * ((cols + 1) / 2)); the three-entry arrays get 0 in the entries past *nplanes.  Returns 1; 0 (nothing written) for an empty frame, other depths or an
+ * unknown layout.  Any output pointer may be NULL. */
+int w2x_yuv_layout_plane_sizes(int rows, int cols, int bits, int layout, int* nplanes, int* plane_rows, int* plane_cols, size_t* plane_bytes);
 /* The colour bleed on the host (tiles.h alpha_bleed): bgr rows x cols interleaved 8-bit BGR, alpha rows x cols bytes, radius in [0, 16]; out (not aliasing bgr)
  * receives the frame with the colours of the pixels of alpha > 0 spread `radius` pixels outward under the pixels of alpha == 0: `radius` Jacobi iterations in
  * which an unknown pixel with n > 0 known neighbours among its eight takes (their sum + (n >> 1)) / n per channel and becomes known.  1 on success, 0 (nothing

@@ -31,11 +31,17 @@ struct Image {          // stand-in for cv::Mat of type CV_8UC3
 // Extension: planar YUV 4:2:0 frames as ffmpeg's yuv420p / yuv420p10le lay them out (an AVFrame's data[0..2] / linesize[0..2]): a Y plane of
 // rows x cols samples, U (Cb) and V (Cr) planes of ceil(rows/2) x ceil(cols/2); bits 8 (uint8 samples) or 10 (little-endian uint16 holding the low
 // 10 bits); each plane has its own pointer and step in bytes.  Chroma siting MPEG-2 "left" (chroma (i, j) at luma x = 2j, y = 2i + 1/2).
+// `layout` picks one of four arrangements of the same samples: I420 is the above; I422 (yuv422p / yuv422p10le) has U and V of
+// rows x ceil(cols/2), chroma row y co-sited with luma row y; I444 (yuv444p / yuv444p10le) has U and V of rows x cols; NV12 (nv12 / p010le) is I420
+// with the chroma in ONE plane, planes[1], of ceil(rows/2) rows of 2 * ceil(cols/2) samples U, V, U, V, ... (planes[2] is ignored and may be null) - and
+// at 10 bits it is P010: the code sits in the HIGH 10 bits of each uint16 (read v >> 6, written code << 6), in Y and in UV.
+enum class YuvLayout { I420 = 0, I422 = 1, I444 = 2, NV12 = 3 };
 struct YuvImage {
     uint8_t* planes[3] = {nullptr, nullptr, nullptr};
     size_t steps[3] = {0, 0, 0};
     int rows = 0, cols = 0;
     int bits = 8;
+    YuvLayout layout = YuvLayout::I420;
 };
 enum class YuvMatrix { BT601 = 0, BT709 = 1, BT2020 = 2 };   // (Kr, Kb) = (0.299, 0.114), (0.2126, 0.0722), (0.2627, 0.0593); BT.2020 non-constant luminance
 enum class YuvRange { Limited = 0, Full = 1 };               // "tv": Y 16..235, C 16..240 (times 2^(bits-8)); "pc": 0 .. 2^bits - 1
@@ -88,6 +94,8 @@ public:
     // to the luma grid, the matrix inverted, R, G, B clamped to [0, 1]: these values take the place of u8 * float(1/255)) and the canvas render()
     // would quantise is written back as YUV 4:2:0 at dst.bits (clamped to [0, 1], Y per pixel, chroma of the RGB filtered onto each chroma site).
     // src.bits and dst.bits are chosen independently (8 or 10); dst must be rows*scaling x cols*scaling.  Other arguments: false (message callback).
+    // src.layout and dst.layout are independent too (nv12 in, yuv444p10le out): I444 chroma is read at the pixel and written per pixel without a
+    // filter, I422 filters columns only (1/4, 1/2, 1/4), NV12 is I420's arithmetic on interleaved samples.  One layout per side for a sequence.
     bool renderYuv(const YuvImage& src, YuvImage& dst, YuvFormat format);
     // renderYuv() over a sequence of equally sized frames through the pipeline of renderSequence() (three plane copies per frame each way)
     bool renderSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format);
@@ -95,6 +103,7 @@ public:
     // the two independent, odd sizes allowed.  The frame is read as renderYuv() reads it, the fp32 canvas is formed and resized as renderResized() does it
     // (not clamped before the resize: the filter's overshoot is part of the result), and the resized RGB is encoded as renderYuv() encodes the canvas, at
     // dst.bits.  At dst = rows*scaling x cols*scaling the bytes are renderYuv()'s.  Other sizes and whatever renderYuv() refuses: false (message callback).
+    // I420 frames only, both sides (resample_yuv_kernel encodes 4:2:0): any other layout: false.
     bool renderYuvResized(const YuvImage& src, YuvImage& dst, YuvFormat format, ResizeFilter filter = ResizeFilter::Bicubic);
     // renderSequenceYuv() with every frame resized like renderYuvResized() to dsts[i].rows x dsts[i].cols (one size and one pair of depths for the sequence)
     bool renderSequenceYuvResized(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, ResizeFilter filter = ResizeFilter::Bicubic);

@@ -157,10 +157,10 @@ int w2x_render_sequence_resized(w2x_engine* e, const uint8_t* const* srcs, int r
     return e->engine.renderSequenceResized(s.data(), d.data(), count, f) ? 1 : 0;
 }
 // the YUV renders: matrix and range go to the engine as given (it refuses unknown values through the message callback)
-static w2x::YuvImage yuv_image(const void* const* planes, const size_t* steps, int rows, int cols, int bits) {
+static w2x::YuvImage yuv_image(const void* const* planes, const size_t* steps, int rows, int cols, int bits, int layout = W2X_YUV_I420) {
     w2x::YuvImage f;
     for (int k = 0; k < 3; ++k) { f.planes[k] = planes ? (uint8_t*)const_cast<void*>(planes[k]) : nullptr; f.steps[k] = steps ? steps[k] : 0; }
-    f.rows = rows; f.cols = cols; f.bits = bits;
+    f.rows = rows; f.cols = cols; f.bits = bits; f.layout = (w2x::YuvLayout)layout;   // (the engine refuses unknown layouts like unknown matrices)
     return f;
 }
 static w2x::YuvFormat yuv_format(int matrix, int range) { w2x::YuvFormat f; f.matrix = (w2x::YuvMatrix)matrix; f.range = (w2x::YuvRange)range; return f; }
@@ -179,6 +179,23 @@ int w2x_render_sequence_yuv(w2x_engine* e, const void* const* src_planes, const 
     for (int i = 0; i < count; ++i) {
         s[i] = yuv_image(src_planes + 3 * i, src_steps, rows, cols, src_bits);
         d[i] = yuv_image(dst_planes + 3 * i, dst_steps, dst_rows, dst_cols, dst_bits);
+    }
+    return e->engine.renderSequenceYuv(s.data(), d.data(), count, yuv_format(matrix, range)) ? 1 : 0;
+}
+int w2x_render_yuv_layout(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits, int src_layout,
+                          void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int dst_layout, int matrix, int range) {
+    if (!e) return 0;
+    const w2x::YuvImage s = yuv_image(src_planes, src_steps, rows, cols, src_bits, src_layout);
+    w2x::YuvImage d = yuv_image(dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, dst_layout);
+    return e->engine.renderYuv(s, d, yuv_format(matrix, range)) ? 1 : 0;
+}
+int w2x_render_sequence_yuv_layout(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits, int src_layout,
+                                   void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int dst_layout, int count, int matrix, int range) {
+    if (!e || count < 0 || (count > 0 && (!src_planes || !dst_planes))) return 0;
+    std::vector<w2x::YuvImage> s(count), d(count);
+    for (int i = 0; i < count; ++i) {
+        s[i] = yuv_image(src_planes + 3 * i, src_steps, rows, cols, src_bits, src_layout);
+        d[i] = yuv_image(dst_planes + 3 * i, dst_steps, dst_rows, dst_cols, dst_bits, dst_layout);
     }
     return e->engine.renderSequenceYuv(s.data(), d.data(), count, yuv_format(matrix, range)) ? 1 : 0;
 }
@@ -298,6 +315,21 @@ int w2x_yuv_plane_sizes(int rows, int cols, int bits, int* plane_rows, int* plan
     if (rows <= 0 || cols <= 0 || (bits != 8 && bits != 10)) return 0;
     for (int k = 0; k < 3; ++k) {
         const int r = k ? (rows + 1) / 2 : rows, c = k ? (cols + 1) / 2 : cols;
+        if (plane_rows) plane_rows[k] = r;
+        if (plane_cols) plane_cols[k] = c;
+        if (plane_bytes) plane_bytes[k] = (size_t)r * c * (bits > 8 ? 2 : 1);
+    }
+    return 1;
+}
+
+int w2x_yuv_layout_plane_sizes(int rows, int cols, int bits, int layout, int* nplanes, int* plane_rows, int* plane_cols, size_t* plane_bytes) {
+    if (rows <= 0 || cols <= 0 || (bits != 8 && bits != 10) || layout < W2X_YUV_I420 || layout > W2X_YUV_NV12) return 0;
+    const int n = layout == W2X_YUV_NV12 ? 2 : 3;
+    const int cr = layout == W2X_YUV_I420 || layout == W2X_YUV_NV12 ? (rows + 1) / 2 : rows;
+    const int cc = layout == W2X_YUV_I444 ? cols : layout == W2X_YUV_NV12 ? 2 * ((cols + 1) / 2) : (cols + 1) / 2;
+    if (nplanes) *nplanes = n;
+    for (int k = 0; k < 3; ++k) {
+        const int r = k >= n ? 0 : k ? cr : rows, c = k >= n ? 0 : k ? cc : cols;
         if (plane_rows) plane_rows[k] = r;
         if (plane_cols) plane_cols[k] = c;
         if (plane_bytes) plane_bytes[k] = (size_t)r * c * (bits > 8 ? 2 : 1);

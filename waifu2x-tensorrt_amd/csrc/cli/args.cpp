@@ -72,6 +72,10 @@ std::string usage() {
            "      --colorspace TEXT       (extension) {bt601,bt709,bt2020}: videos read through ffmpeg stay YUV 4:2:0 at --pix_fmt\n"
            "                              (yuv420p or yuv420p10le) and are converted on the GPU; the output carries the colour tags\n"
            "      --color_range TEXT [tv] (extension) {tv,pc}: the range of the --colorspace frames\n"
+           "      --yuv-in FMT            (extension) with --colorspace: the raw format asked of the ffmpeg reader [--pix_fmt], one of\n"
+           "                              {yuv420p,yuv420p10le,yuv422p,yuv422p10le,yuv444p,yuv444p10le,nv12,p010le}; converted on the GPU\n"
+           "      --yuv-out FMT           (extension) with --colorspace: the raw format handed to the writer [--pix_fmt], same choices; --pix_fmt is then\n"
+           "                              the encoder's format only (any, default FMT); neither option works with --outsize\n"
            "      --alpha-bleed INT [0]   (extension) 0..16: stills with an alpha channel: spread the colours of the visible pixels that many pixels under the\n"
            "                              transparent ones before upscaling (no dark fringe on cut-outs); not with --deep\n"
            "      --alpha-skip-uniform    (extension) a still whose alpha channel is one value (an opaque export) keeps it without running it through the network\n"
@@ -81,10 +85,12 @@ std::string usage() {
            "  convert -i IN -o OUT        (extension) re-encode one still image (png/ppm), no GPU\n";
 }
 
+const char* const kYuvFormats[8] = {"yuv420p", "yuv420p10le", "yuv422p", "yuv422p10le", "yuv444p", "yuv444p10le", "nv12", "p010le"};
+
 Options parse(int argc, const char* const* argv) {
     Options o;
     std::vector<std::string> a(argv + 1, argv + argc);
-    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_outsize = false, seen_filter = false, seen_colorspace = false, seen_range = false, seen_bleed = false, seen_skip = false;
+    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_outsize = false, seen_filter = false, seen_colorspace = false, seen_range = false, seen_bleed = false, seen_skip = false, seen_pixfmt = false;
     auto value = [&](size_t& i) -> std::string {
         const std::string name = a[i];
         auto eq = name.find('=');
@@ -124,7 +130,7 @@ Options parse(int argc, const char* const* argv) {
         else if (k == "--tta-mode") { o.ttaMode = value(i); std::transform(o.ttaMode.begin(), o.ttaMode.end(), o.ttaMode.begin(), ::tolower); }
         else if (k == "--tta-compat") o.ttaMode = "reference";
         else if (k == "--codec") o.codec = value(i);
-        else if (k == "--pix_fmt") o.pixFmt = value(i);
+        else if (k == "--pix_fmt") { o.pixFmt = value(i); seen_pixfmt = true; }
         else if (k == "--crf") o.crf = to_int(k, value(i));
         else if (k == "--outscale") { o.outscale = to_double(k, value(i)); seen_outscale = true; }
         else if (k == "--outsize") {
@@ -140,6 +146,8 @@ Options parse(int argc, const char* const* argv) {
         else if (k == "--resize-filter") { o.resizeFilter = value(i); std::transform(o.resizeFilter.begin(), o.resizeFilter.end(), o.resizeFilter.begin(), ::tolower); seen_filter = true; }
         else if (k == "--colorspace") { o.colorspace = value(i); std::transform(o.colorspace.begin(), o.colorspace.end(), o.colorspace.begin(), ::tolower); seen_colorspace = true; }
         else if (k == "--color_range") { o.colorRange = value(i); std::transform(o.colorRange.begin(), o.colorRange.end(), o.colorRange.begin(), ::tolower); seen_range = true; }
+        else if (k == "--yuv-in") o.yuvIn = value(i);
+        else if (k == "--yuv-out") o.yuvOut = value(i);
         else throw std::runtime_error("The following argument was not expected: " + a[i]);
     }
     if (o.command.empty()) throw std::runtime_error("A subcommand is required");
@@ -161,6 +169,7 @@ Options parse(int argc, const char* const* argv) {
     if (o.devices < 1) throw std::runtime_error("--devices: number must be positive");
     member<std::string>("--split", o.split, {"shards", "strips"});
     member<std::string>("--precision", o.precision, {"fp16", "tf32", "fp32"});   // fp32: an addition (include/w2x/config.h)
+    const bool seen_yuv_in = !o.yuvIn.empty(), seen_yuv_out = !o.yuvOut.empty();
     if (o.command == "render") {
         if (o.inputs.empty()) throw std::runtime_error("--input is required");
         for (const auto& p : o.inputs) if (!std::filesystem::exists(p)) throw std::runtime_error("--input: Path does not exist: " + p);
@@ -189,16 +198,24 @@ Options parse(int argc, const char* const* argv) {
         if (seen_colorspace) {
             member<std::string>("--colorspace", o.colorspace, {"bt601", "bt709", "bt2020"});
             member<std::string>("--color_range", o.colorRange, {"tv", "pc"});
-            if (o.pixFmt != "yuv420p" && o.pixFmt != "yuv420p10le") throw std::runtime_error("--pix_fmt: with --colorspace one of {yuv420p,yuv420p10le}, got " + o.pixFmt);
+            for (const char* opt : {"--yuv-in", "--yuv-out"}) {
+                const std::string& v = opt[6] == 'i' ? o.yuvIn : o.yuvOut;
+                if (v.empty()) continue;
+                member<std::string>(opt, v, {kYuvFormats[0], kYuvFormats[1], kYuvFormats[2], kYuvFormats[3], kYuvFormats[4], kYuvFormats[5], kYuvFormats[6], kYuvFormats[7]});
+                if (seen_outsize) throw std::runtime_error(std::string(opt) + ": not together with --outsize (resized YUV output is yuv420p / yuv420p10le at --pix_fmt)");
+            }
+            if (seen_yuv_out) { if (!seen_pixfmt) o.pixFmt = o.yuvOut; }   // --pix_fmt is the encoder's format only
+            else if (o.pixFmt != "yuv420p" && o.pixFmt != "yuv420p10le") throw std::runtime_error("--pix_fmt: with --colorspace one of {yuv420p,yuv420p10le}, got " + o.pixFmt);
             if (seen_outscale) throw std::runtime_error("--colorspace: not together with --outscale (a factor rarely gives the even sizes video wants: use --outsize WxH)");
         } else if (seen_range) throw std::runtime_error("--color_range: needs --colorspace");
+        else if (seen_yuv_in || seen_yuv_out) throw std::runtime_error(std::string(seen_yuv_in ? "--yuv-in" : "--yuv-out") + ": needs --colorspace");
         if (seen_bleed) {
             if (!(o.alphaBleed >= 0 && o.alphaBleed <= 16)) throw std::runtime_error("--alpha-bleed: " + std::to_string(o.alphaBleed) + " not in [0, 16] (the radius in pixels)");
             if (o.alphaBleed > 0 && o.deep) throw std::runtime_error("--alpha-bleed: not together with --deep (the bleed works on 8-bit colour; 16-bit stills keep the colours as stored)");
         }
-    } else if (seen_outscale || seen_outsize || seen_filter || seen_colorspace || seen_range || seen_bleed || seen_skip)
-        throw std::runtime_error(std::string(seen_outscale ? "--outscale" : seen_outsize ? "--outsize" : seen_filter ? "--resize-filter" : seen_colorspace ? "--colorspace" : seen_range ? "--color_range" :
-                                             seen_bleed ? "--alpha-bleed" : "--alpha-skip-uniform") + ": only with render");
+    } else if (seen_outscale || seen_outsize || seen_filter || seen_colorspace || seen_range || seen_bleed || seen_skip || seen_yuv_in || seen_yuv_out)
+        throw std::runtime_error(std::string(seen_yuv_in ? "--yuv-in" : seen_yuv_out ? "--yuv-out" : seen_outscale ? "--outscale" : seen_outsize ? "--outsize" : seen_filter ? "--resize-filter" : seen_colorspace ? "--colorspace" :
+                                             seen_range ? "--color_range" : seen_bleed ? "--alpha-bleed" : "--alpha-skip-uniform") + ": only with render");
     // cross-checks, main.cpp:142-145
     if (o.model == "cunet/art" && o.scale == 4) throw std::runtime_error("cunet/art does not support scale factor 4.");
     if (o.noise == -1 && o.scale == 1) throw std::runtime_error("Noise level -1 does not support scale factor 1.");
@@ -248,6 +265,7 @@ std::string to_json(const Options& o) {
        << ", \"outscale\": " << (o.outscale > 0 ? std::to_string(o.outscale) : std::string("null")) << ", \"outsize\": " << (o.outsizeW > 0 ? "[" + std::to_string(o.outsizeW) + ", " + std::to_string(o.outsizeH) + "]" : std::string("null"))
        << ", \"resize_filter\": " << q(o.resizeFilter)
        << ", \"colorspace\": " << (o.colorspace.empty() ? std::string("null") : q(o.colorspace)) << ", \"color_range\": " << q(o.colorRange)
+       << ", \"yuv_in\": " << (o.yuvIn.empty() ? std::string("null") : q(o.yuvIn)) << ", \"yuv_out\": " << (o.yuvOut.empty() ? std::string("null") : q(o.yuvOut))
        << ", \"alpha_bleed\": " << o.alphaBleed << ", \"alpha_skip_uniform\": " << (o.alphaSkipUniform ? "true" : "false")
        << ", \"codec\": " << q(o.codec) << ", \"pix_fmt\": " << q(o.pixFmt) << ", \"crf\": " << o.crf << ", \"inputs\": [";
     for (size_t i = 0; i < o.inputs.size(); ++i) os << (i ? ", " : "") << q(o.inputs[i]);

@@ -40,6 +40,9 @@ struct Options {
     std::string colorspace;               // --colorspace {bt601,bt709,bt2020}: videos read through ffmpeg travel as raw --pix_fmt (yuv420p / yuv420p10le)
                                           // frames, converted on the GPU (Img2Img::renderSequenceYuv); "" = bgr24 frames, the reference's path
     std::string colorRange = "tv";        // --color_range {tv,pc}: the range of those frames (with --colorspace only)
+    std::string yuvIn, yuvOut;            // --yuv-in / --yuv-out FMT (with --colorspace only; kYuvFormats): the raw format asked of the ffmpeg reader / handed to the
+                                          // writer, converted on the GPU in either direction (YuvImage::layout); "" = --pix_fmt, which with --yuv-out given is the
+                                          // encoder's format alone (unrestricted, default the --yuv-out format)
     int alphaBleed = 0;                   // --alpha-bleed N (0..16): stills with an alpha channel: the colours of the visible pixels are spread N pixels under the
                                           // transparent ones before the network sees them (Img2Img::renderRgba, with --outscale / --outsize Img2Img::renderRgbaResized; on
                                           // the routes that render colour and alpha in two calls - --devices > 1 - the host alpha_bleed); 0 = the colours as stored
@@ -48,6 +51,8 @@ struct Options {
     bool help = false;
 };
 
+// the raw frame formats of --yuv-in / --yuv-out (ffmpeg's names): planar 4:2:0, 4:2:2, 4:4:4 at 8 / 10 bits, semi-planar 4:2:0 (nv12, 10 bits: p010le)
+extern const char* const kYuvFormats[8];
 // throws std::runtime_error with the message to print (exit code -1 like main.cpp:147-150) on invalid input
 Options parse(int argc, const char* const* argv);
 std::string usage();

@@ -64,18 +64,28 @@ std::vector<std::string> find_inputs(const cli::Options& o) {
     return files;
 }
 
-// ---- YUV 4:2:0 frames as ffmpeg's rawvideo yuv420p / yuv420p10le carries them: the Y, U and V planes back to back, rows unpadded
-size_t yuv_frame_bytes(int rows, int cols, const std::string& pixFmt) {
-    const size_t bps = pixFmt == "yuv420p10le" ? 2 : 1;
-    return ((size_t)rows * cols + 2 * (size_t)((rows + 1) / 2) * ((cols + 1) / 2)) * bps;
+// ---- YUV frames as ffmpeg's rawvideo carries them (cli::kYuvFormats): the planes back to back - Y, U, V, or Y, UV for nv12 / p010le -, rows unpadded
+struct RawYuv { YuvLayout layout; int bits; };
+RawYuv raw_yuv(const std::string& fmt) {
+    const bool ten = fmt.size() > 4 && fmt.compare(fmt.size() - 4, 4, "10le") == 0;
+    if (fmt == "nv12" || fmt == "p010le") return {YuvLayout::NV12, ten ? 10 : 8};
+    return {fmt.rfind("yuv422p", 0) == 0 ? YuvLayout::I422 : fmt.rfind("yuv444p", 0) == 0 ? YuvLayout::I444 : YuvLayout::I420, ten ? 10 : 8};
 }
-YuvImage packed_yuv(uint8_t* p, int rows, int cols, int bits) {
-    const size_t bps = bits > 8 ? 2 : 1, cw = (size_t)(cols + 1) / 2, ch = (size_t)(rows + 1) / 2;
+// a packed frame over p: chroma of ch rows x cw samples (nv12: both components in one plane)
+YuvImage packed_yuv(uint8_t* p, int rows, int cols, const RawYuv& fmt) {
+    const bool sub_y = fmt.layout == YuvLayout::I420 || fmt.layout == YuvLayout::NV12;
+    const size_t bps = fmt.bits > 8 ? 2 : 1, ch = sub_y ? (size_t)(rows + 1) / 2 : (size_t)rows;
+    const size_t cw = fmt.layout == YuvLayout::I444 ? (size_t)cols : (size_t)((cols + 1) / 2) * (fmt.layout == YuvLayout::NV12 ? 2 : 1);
     YuvImage f;
-    f.planes[0] = p; f.planes[1] = p + (size_t)rows * cols * bps; f.planes[2] = f.planes[1] + ch * cw * bps;
-    f.steps[0] = (size_t)cols * bps; f.steps[1] = f.steps[2] = cw * bps;
-    f.rows = rows; f.cols = cols; f.bits = bits;
+    f.planes[0] = p; f.planes[1] = p + (size_t)rows * cols * bps; f.planes[2] = fmt.layout == YuvLayout::NV12 ? nullptr : f.planes[1] + ch * cw * bps;
+    f.steps[0] = (size_t)cols * bps; f.steps[1] = cw * bps; f.steps[2] = fmt.layout == YuvLayout::NV12 ? 0 : cw * bps;
+    f.rows = rows; f.cols = cols; f.bits = fmt.bits; f.layout = fmt.layout;
     return f;
+}
+size_t yuv_frame_bytes(int rows, int cols, const RawYuv& fmt) {
+    const YuvImage f = packed_yuv(nullptr, rows, cols, fmt);
+    const size_t ch = fmt.layout == YuvLayout::I420 || fmt.layout == YuvLayout::NV12 ? (size_t)(rows + 1) / 2 : (size_t)rows;
+    return f.steps[0] * rows + (f.steps[1] + f.steps[2]) * ch;
 }
 // the writer's colour tags for --colorspace / --color_range
 std::string colour_tags(const cli::Options& o) {
@@ -315,7 +325,9 @@ int main(int argc, char** argv) {
                 std::string why;
                 auto avi = std::make_unique<AviSource>();
                 const bool is_avi = fs::path(file).extension() == ".avi" || fs::path(file).extension() == ".AVI";
-                bool yuv = false;                                      // --colorspace on a multi-frame input read through ffmpeg: YUV 4:2:0 frames
+                bool yuv = false;                                      // --colorspace on a multi-frame input read through ffmpeg: YUV frames
+                const std::string& rawIn = o.yuvIn.empty() ? o.pixFmt : o.yuvIn, & rawOut = o.yuvOut.empty() ? o.pixFmt : o.yuvOut;   // --yuv-in / --yuv-out
+                const RawYuv fmtIn = raw_yuv(rawIn), fmtOut = raw_yuv(rawOut);
                 if (is_avi && avi->rd.open(file, &why)) {
                     width = avi->rd.info().width; height = avi->rd.info().height; frames = avi->rd.info().frames; fps = avi->rd.info().fps;
                     source = std::move(avi);
@@ -325,18 +337,18 @@ int main(int argc, char** argv) {
                     const Probe pr = ffprobe(file);
                     width = pr.width; height = pr.height; frames = pr.frames; fps = pr.fps;
                     yuv = !o.colorspace.empty() && frames != 1;
-                    const size_t inBytes = yuv ? yuv_frame_bytes(height, width, o.pixFmt) : (size_t)width * height * 3;
-                    source.reset(new PipeSource("ffmpeg -v error -i " + shell_quote(file) + " -f rawvideo -pix_fmt " + (yuv ? o.pixFmt : std::string("bgr24")) + " -", inBytes));
+                    const size_t inBytes = yuv ? yuv_frame_bytes(height, width, fmtIn) : (size_t)width * height * 3;
+                    source.reset(new PipeSource("ffmpeg -v error -i " + shell_quote(file) + " -f rawvideo -pix_fmt " + (yuv ? rawIn : std::string("bgr24")) + " -", inBytes));
                 }
                 frameIndex = 0; frameCount = frames;
                 const bool single = frames == 1;
                 std::string outFile = cli::output_path(o, file, single);
                 check_outsize(file, width, height);
                 const int outW = cli::out_dim(o, width, true), outH = cli::out_dim(o, height, false);
-                const size_t inBytes = yuv ? yuv_frame_bytes(height, width, o.pixFmt) : (size_t)width * height * 3;
-                const size_t outBytes = yuv ? yuv_frame_bytes(outH, outW, o.pixFmt) : (size_t)outW * outH * 3;
+                const size_t inBytes = yuv ? yuv_frame_bytes(height, width, fmtIn) : (size_t)width * height * 3;
+                const size_t outBytes = yuv ? yuv_frame_bytes(outH, outW, fmtOut) : (size_t)outW * outH * 3;
                 if (have_ffmpeg) {
-                    std::string wcmd = "ffmpeg -v error -y -f rawvideo -pix_fmt " + (yuv ? o.pixFmt : std::string("bgr24")) + " -s " + std::to_string(outW) + "x" + std::to_string(outH) +
+                    std::string wcmd = "ffmpeg -v error -y -f rawvideo -pix_fmt " + (yuv ? rawOut : std::string("bgr24")) + " -s " + std::to_string(outW) + "x" + std::to_string(outH) +
                                        " -r " + std::to_string(single ? 1.0 : fps) + " -i - ";
                     if (!single) wcmd += "-c:v " + o.codec + " -pix_fmt " + o.pixFmt + " -crf " + std::to_string(o.crf) + " ";
                     if (yuv) wcmd += colour_tags(o);
@@ -357,10 +369,9 @@ int main(int argc, char** argv) {
                     YuvFormat f;
                     f.matrix = o.colorspace == "bt601" ? YuvMatrix::BT601 : o.colorspace == "bt2020" ? YuvMatrix::BT2020 : YuvMatrix::BT709;
                     f.range = o.colorRange == "pc" ? YuvRange::Full : YuvRange::Limited;
-                    const int bits = o.pixFmt == "yuv420p10le" ? 10 : 8;
                     render = [=](Img2Img& e, uint8_t* const* in, uint8_t* const* out, int n) {
                         std::vector<YuvImage> si(n), di(n);
-                        for (int k = 0; k < n; ++k) { si[k] = packed_yuv(in[k], height, width, bits); di[k] = packed_yuv(out[k], outH, outW, bits); }
+                        for (int k = 0; k < n; ++k) { si[k] = packed_yuv(in[k], height, width, fmtIn); di[k] = packed_yuv(out[k], outH, outW, fmtOut); }
                         return resize ? e.renderSequenceYuvResized(si.data(), di.data(), n, f, filter) : e.renderSequenceYuv(si.data(), di.data(), n, f);
                     };
                 }

@@ -321,10 +321,11 @@ struct Img2Img::Impl {
     };
     std::deque<ResizeTables> rs_tables;
     const ResizeTables* rs = nullptr;
-    // renderYuv() / renderSequenceYuv(): the frame being rendered is YUV 4:2:0 (null outside such a call).  d_frame / d_out then hold the three planes
-    // (yuv_layout) and the gather / compose launches are gather_yuv_kernel / compose_yuv_kernel; `key` tells the captured passes of each input format apart.
+    // renderYuv() / renderSequenceYuv(): the frame being rendered is YUV (null outside such a call).  d_frame / d_out then hold the planes of in_layout /
+    // out_layout (yuv_layout; kernels.h kYuvI420 ..) and the gather / compose launches are gather_yuv_kernel / compose_yuv_kernel (4:4:4 output:
+    // compose_yuv444_kernel); `key` tells the captured passes of each input format - depth, range, matrix, layout - apart.
     // With `rs` set as well (renderYuvResized) the frame ends with compose_canvas_kernel and resample_yuv_kernel, and d_out holds planes of the target size.
-    struct YuvJob { YuvCoefs in, out; int in_bits = 8, out_bits = 8, key = 0; };
+    struct YuvJob { YuvCoefs in, out; int in_bits = 8, out_bits = 8, key = 0, in_layout = kYuvI420, out_layout = kYuvI420; };
     const YuvJob* yuv = nullptr;
     // renderRgba(): d_frame holds the uploaded BGRA frame, alpha_bleed_kernel writes the BGR frame and the alpha plane the passes gather from (gather_rgba_kernel,
     // `rgba` set for the duration of the call), d_minmax receives max(A) and max(255 - A), read back into the page-locked h_minmax behind the kernel
@@ -395,7 +396,7 @@ struct Img2Img::Impl {
     // enqueueV3 (img2img_infer.cpp:80); here a pass is ~40 launches, which the host cannot issue fast enough for small tiles.
     // A pass is captured the second time it is met (the first run stays eager so that one-time attribute calls are out of the
     // way) and replayed from then on.  The key holds everything the captured launches bake in.
-    static constexpr int kRgbaKey = 64;   // (YuvJob::key stays below 32)
+    static constexpr int kRgbaKey = 64;   // (YuvJob::key stays below 50)
     using GraphKey = std::tuple<const void*, const void*, const void*, const void*, int, int, int, int>;   // frame, slots, slab out, arena, rows, cols, live, sample format (1: 16-bit, >= 2: YuvJob::key)
     // A pass that runs as NG tile groups is NG graphs, one per group, each a straight line of launches replayed on that group's OWN stream (fork / join
     // events between the streams are issued around the replays): a single captured graph with NG branches runs its side branches on streams the runtime
@@ -1051,7 +1052,7 @@ struct Img2Img::Impl {
                 }
                 if (!yuv) { hipAssert(launch_gather(gp, gs)); return; }
                 GatherYuvParams yp;                                   // a YUV frame (renderYuv): the same tiles from its planes
-                yp.src = yuv_layout(d_frame, rows, cols, yuv->in_bits); yp.k = yuv->in;
+                yp.src = yuv_layout(d_frame, rows, cols, yuv->in_bits, yuv->in_layout); yp.k = yuv->in;
                 yp.out = gp.out; yp.fp32 = gp.fp32; yp.slots = gp.slots; yp.B = gp.B; yp.T = gp.T;
                 hipAssert(launch_gather_yuv(yp, gs));
             };
@@ -1172,7 +1173,7 @@ struct Img2Img::Impl {
         cp.ramp_x = d_rampx; cp.ramp_y = d_rampy; cp.tta = cfg.tta ? 1 : 0; cp.tta_bug_compat = cfg.ttaBugCompat ? 1 : 0;
         hipAssert(launch_compose_canvas(cp, d_canvas, on));
     }
-    // YUV frames (yuv set): the whole canvas of the frame's tiles (one part, slot 0 = tile 0) written as YUV 4:2:0 planes into d_out
+    // YUV frames (yuv set): the whole canvas of the frame's tiles (one part, slot 0 = tile 0) written as the planes of yuv->out_layout into d_out
     void compose_yuv(int rows, int cols, const TileGrid& grid, hipStream_t on) {
         const int To = plan.Tout;
         ComposeYuvParams yp;
@@ -1183,7 +1184,7 @@ struct Img2Img::Impl {
         const bool overlapping = cfg.overlapX != 0 || cfg.overlapY != 0;
         cp.ovx = overlapping ? ovx : 0; cp.ovy = overlapping ? ovy : 0;
         cp.ramp_x = d_rampx; cp.ramp_y = d_rampy; cp.tta = cfg.tta ? 1 : 0; cp.tta_bug_compat = cfg.ttaBugCompat ? 1 : 0;
-        yp.dst = yuv_layout(d_out, cp.outH, cp.outW, yuv->out_bits); yp.k = yuv->out;
+        yp.dst = yuv_layout(d_out, cp.outH, cp.outW, yuv->out_bits, yuv->out_layout); yp.k = yuv->out;
         stamp_begin(4, 0);
         hipAssert(launch_compose_yuv(yp, on));
         stamp_end();
@@ -1409,17 +1410,21 @@ struct Img2Img::Impl {
         hipAssert(hipEventElapsedTime(&total_ms, ev0, ev1));
         return total_ms;
     }
-    // the device layout of a YUV frame in d_frame / d_out: Y, U, V one after the other, rows padded to 16 bytes (the stores of compose_yuv_kernel)
-    static YuvPlanes yuv_layout(uint8_t* base, int rows, int cols, int bits) {
+    // the device layout of a YUV frame in d_frame / d_out: Y, U, V (NV12: Y, UV) one after the other, rows padded to 16 bytes (the stores of the compose kernels)
+    static YuvPlanes yuv_layout(uint8_t* base, int rows, int cols, int bits, int layout) {
         const size_t bps = bits > 8 ? 2 : 1;
-        const int cw = (cols + 1) / 2, ch = (rows + 1) / 2;
+        const int cw = yuv_chroma_samples(cols, layout), ch = yuv_chroma_rows(rows, layout);
         YuvPlanes f;
-        f.rows = rows; f.cols = cols; f.bits = bits;
+        f.rows = rows; f.cols = cols; f.bits = bits; f.layout = layout;
         f.step[0] = ((size_t)cols * bps + 15) / 16 * 16; f.step[1] = f.step[2] = ((size_t)cw * bps + 15) / 16 * 16;
-        f.p[0] = base; f.p[1] = base + f.step[0] * rows; f.p[2] = f.p[1] + f.step[1] * ch;
+        f.p[0] = base; f.p[1] = base + f.step[0] * rows; f.p[2] = layout == kYuvNV12 ? nullptr : f.p[1] + f.step[1] * ch;
         return f;
     }
-    static size_t yuv_bytes(int rows, int cols, int bits) { const YuvPlanes f = yuv_layout(nullptr, rows, cols, bits); return f.step[0] * rows + 2 * f.step[1] * ((rows + 1) / 2); }
+    static int yuv_planes(int layout) { return layout == kYuvNV12 ? 2 : 3; }
+    static size_t yuv_bytes(int rows, int cols, int bits, int layout) {
+        const YuvPlanes f = yuv_layout(nullptr, rows, cols, bits, layout);
+        return f.step[0] * rows + (yuv_planes(layout) - 1) * f.step[1] * yuv_chroma_rows(rows, layout);
+    }
     void resample(hipStream_t on) {
         ResampleParams rp;
         rp.canvas = d_canvas; rp.inW = rs->inW; rp.inH = rs->inH;
@@ -1434,7 +1439,7 @@ struct Img2Img::Impl {
         rp.canvas = d_canvas; rp.inW = rs->inW; rp.inH = rs->inH;
         rp.outW = rs->outW; rp.outH = rs->outH;
         rp.fx = rs->fx; rp.wx = rs->wx; rp.kx = rs->kx; rp.fy = rs->fy; rp.wy = rs->wy; rp.ky = rs->ky; rp.rows_max = rs->rows_max;
-        rp.dst = yuv_layout(d_out, rs->outH, rs->outW, yuv->out_bits); rp.k = yuv->out;
+        rp.dst = yuv_layout(d_out, rs->outH, rs->outW, yuv->out_bits, kYuvI420); rp.k = yuv->out;
         hipAssert(launch_resample_yuv(rp, on));
     }
     // the device tap tables of one (canvas, target, filter) and a canvas that holds the frame; the caller sets rs to the result for the frame
@@ -2207,8 +2212,9 @@ bool Img2Img::renderSequenceYuvResized(const YuvImage* srcs, YuvImage* dsts, int
     return runSequenceYuv(srcs, dsts, count, format, filter == ResizeFilter::Bilinear ? 1 : filter == ResizeFilter::Bicubic ? 0 : 2, "renderSequenceYuvResized");
 }
 
-// YUV 4:2:0 frames through renderSequence()'s pipeline: per frame three plane copies up on s_up, the passes with gather_yuv_kernel, compose_yuv_kernel
-// (on the second group's stream when the sequence rolls), three plane copies down on s_dn.  One size and one pair of depths for the sequence.
+// YUV frames through renderSequence()'s pipeline: per frame one copy per plane up on s_up (three, NV12 two), the passes with gather_yuv_kernel, the compose
+// kernel of the output layout (on the second group's stream when the sequence rolls), one copy per plane down on s_dn.  One size, one pair of depths and one
+// pair of layouts (srcs[0].layout, dsts[0].layout: DESIGN 9f) for the sequence; nothing is repacked or converted on the host.
 // resizeFilter >= 0 (renderYuvResized / renderSequenceYuvResized): every dst is the target size of dsts[0], the frame step ends with the canvas compose
 // and resample_yuv_kernel; at the scaled size it is the plain sequence.
 bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, int resizeFilter, const char* who) try {
@@ -2224,19 +2230,26 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
     const int rows = srcs[0].rows, cols = srcs[0].cols, s = cfg.scaling, in_bits = srcs[0].bits, out_bits = dsts[0].bits;
     if ((in_bits != 8 && in_bits != 10) || (out_bits != 8 && out_bits != 10)) { W2X_LOG_AS(who, error, "YUV frames must have 8 or 10 bits."); return false; }
     if (rows <= 0 || cols <= 0) { W2X_LOG_AS(who, error, "Input image is empty."); return false; }
+    const int in_layout = (int)srcs[0].layout, out_layout = (int)dsts[0].layout;
+    if (in_layout < kYuvI420 || in_layout > kYuvNV12 || out_layout < kYuvI420 || out_layout > kYuvNV12) {
+        W2X_LOG_AS(who, error, "Unknown YUV layout " + std::to_string(in_layout < kYuvI420 || in_layout > kYuvNV12 ? in_layout : out_layout) + ".");
+        return false;
+    }
+    if (resizeFilter >= 0 && (in_layout != kYuvI420 || out_layout != kYuvI420)) { W2X_LOG_AS(who, error, "Resized YUV frames must be I420 (yuv420p / yuv420p10le) on both sides."); return false; }
     const int out_rows = resizeFilter >= 0 ? dsts[0].rows : rows * s, out_cols = resizeFilter >= 0 ? dsts[0].cols : cols * s;
     const bool resized = resizeFilter >= 0 && !(out_rows == rows * s && out_cols == cols * s);
     if (resizeFilter >= 0) {
         const std::string why = impl->resize_problem(rows, cols, out_rows, out_cols, resizeFilter);
         if (!why.empty()) { W2X_LOG_AS(who, error, why); return false; }
     }
-    // every plane present, with a step that holds its row
+    // every plane of the layout present (NV12: Y and UV), with a step that holds its row
     auto planes_ok = [](const YuvImage& f) {
         const size_t bps = f.bits > 8 ? 2 : 1;
-        for (int k = 0; k < 3; ++k) if (!f.planes[k] || f.steps[k] < (size_t)(k ? (f.cols + 1) / 2 : f.cols) * bps) return false;
+        for (int k = 0; k < Impl::yuv_planes((int)f.layout); ++k) if (!f.planes[k] || f.steps[k] < (size_t)(k ? yuv_chroma_samples(f.cols, (int)f.layout) : f.cols) * bps) return false;
         return true;
     };
     for (int i = 0; i < count; ++i) {
+        if ((int)srcs[i].layout != in_layout || (int)dsts[i].layout != out_layout) { W2X_LOG_AS(who, error, "The frames of a sequence must be of one layout (one for the inputs, one for the outputs)."); return false; }
         if (srcs[i].rows != rows || srcs[i].cols != cols || srcs[i].bits != in_bits) { W2X_LOG_AS(who, error, "Input images must be of one size and depth."); return false; }
         if (!planes_ok(srcs[i])) { W2X_LOG_AS(who, error, "Input image has a missing plane or an invalid step."); return false; }
         if (dsts[i].rows != out_rows || dsts[i].cols != out_cols) { W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(out_cols) + "x" + std::to_string(out_rows) + "."); return false; }
@@ -2245,7 +2258,7 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
     }
     hipStream_t stream = impl->stream;
     impl->ensure_copy_streams();
-    const size_t in_bytes = Impl::yuv_bytes(rows, cols, in_bits), out_bytes = Impl::yuv_bytes(out_rows, out_cols, out_bits);
+    const size_t in_bytes = Impl::yuv_bytes(rows, cols, in_bits, in_layout), out_bytes = Impl::yuv_bytes(out_rows, out_cols, out_bits, out_layout);
     impl->ensure(impl->d_frame, impl->frame_cap, in_bytes);   impl->ensure(impl->d_frame2, impl->frame2_cap, in_bytes);
     impl->ensure(impl->d_out, impl->out_cap, out_bytes);      impl->ensure(impl->d_out2, impl->out2_cap, out_bytes);
     TileGrid grid = calculate_tiles(cols, rows, cols * s, rows * s, plan.T, plan.T, plan.Tout, plan.Tout, s, cfg.overlapX, cfg.overlapY);
@@ -2257,7 +2270,8 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
     struct YuvScope { Impl* im; ~YuvScope() { im->yuv = nullptr; } } yuv_scope{impl.get()};   // also on exceptions
     Impl::YuvJob job;
     job.in = yuv_coefs(matrix, range, in_bits); job.out = yuv_coefs(matrix, range, out_bits);
-    job.in_bits = in_bits; job.out_bits = out_bits; job.key = 2 + (in_bits == 10 ? 1 : 0) + 2 * range + 4 * matrix;
+    job.in_bits = in_bits; job.out_bits = out_bits; job.in_layout = in_layout; job.out_layout = out_layout;
+    job.key = 2 + (in_bits == 10 ? 1 : 0) + 2 * range + 4 * matrix + 12 * in_layout;   // 2 .. 13 per layout: 2 .. 49, below kRgbaKey
     impl->yuv = &job;
     impl->deep = false;
     struct ResizeScope { Impl* im; ~ResizeScope() { im->rs = nullptr; } } resize_scope{impl.get()};
@@ -2265,12 +2279,13 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
         impl->rs = impl->resize_tables(cols * s, rows * s, out_cols, out_rows, resizeFilter);
         impl->ensure_canvas((size_t)rows * s * cols * s * 3 * sizeof(float));
     }
-    // the three planes of a frame between the caller's layout and the device's (yuv_layout), on copy stream `on`
+    // the planes of a frame (NV12 two, else three) between the caller's layout and the device's (yuv_layout), on copy stream `on`
     auto copy_planes = [&](const YuvImage& host, uint8_t* dev, int r, int c, bool up, hipStream_t on) {
-        const YuvPlanes d = Impl::yuv_layout(dev, r, c, host.bits);
+        const int layout = (int)host.layout;
+        const YuvPlanes d = Impl::yuv_layout(dev, r, c, host.bits, layout);
         const size_t bps = host.bits > 8 ? 2 : 1;
-        for (int k = 0; k < 3; ++k) {
-            const size_t width = (size_t)(k ? (c + 1) / 2 : c) * bps; const int h = k ? (r + 1) / 2 : r;
+        for (int k = 0; k < Impl::yuv_planes(layout); ++k) {
+            const size_t width = (size_t)(k ? yuv_chroma_samples(c, layout) : c) * bps; const int h = k ? yuv_chroma_rows(r, layout) : r;
             if (up) hipAssert(hipMemcpy2DAsync(d.p[k], d.step[k], host.planes[k], host.steps[k], width, h, hipMemcpyHostToDevice, on));
             else hipAssert(hipMemcpy2DAsync(host.planes[k], host.steps[k], d.p[k], d.step[k], width, h, hipMemcpyDeviceToHost, on));
         }

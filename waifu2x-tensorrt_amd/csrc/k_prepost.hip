@@ -9,7 +9,8 @@
 //             imagesFromBlob (img2img_infer.cpp:23-39), reverseAugmentation/TTA accumulate (:179-222,:305-318),
 //             applyWeights (:107-121), the canvas add (:329-330) and the final convertTo/cvtColor (:342-343).
 //   gather_yuv / compose_yuv: the same two steps on YUV 4:2:0 frames (renderYuv): colour conversion and chroma resampling
-//             folded into the tile reads and the canvas writes.
+//             folded into the tile reads and the canvas writes.  Both are instantiated per layout (I420, I422, I444, NV12 / P010: DESIGN 9f);
+//             compose_yuv444_kernel is the 4:4:4 output in compose_kernel's shape.
 //   se/scale: cunet squeeze-excite gate and channel scaling.
 #include "kernels.h"
 #include "prepost_device.h"
@@ -173,11 +174,28 @@ __device__ __forceinline__ float yuv_sample(const YuvPlanes& f, int pl, int y, i
     return f.bits > 8 ? (float)((const uint16_t*)row)[x] : (float)row[x];
 }
 
+// The same for a frame of layout L: Y of P010 (NV12 at 10 bits) carries its code in the high 10 bits; chroma component pl (1: U, 2: V) at (y, x) of
+// the chroma grid comes from plane pl, or for NV12 from sample 2x + pl - 1 of plane 1.
+template <int L>
+__device__ __forceinline__ float yuv_luma(const YuvPlanes& f, int y, int x) {
+    if constexpr (L != kYuvNV12) return yuv_sample(f, 0, y, x);
+    const uint8_t* row = f.p[0] + (size_t)y * f.step[0];
+    return f.bits > 8 ? (float)(((const uint16_t*)row)[x] >> 6) : (float)row[x];
+}
+template <int L>
+__device__ __forceinline__ float yuv_chroma(const YuvPlanes& f, int pl, int y, int x) {
+    if constexpr (L != kYuvNV12) return yuv_sample(f, pl, y, x);
+    const uint8_t* row = f.p[1] + (size_t)y * f.step[1];
+    const int i = 2 * x + pl - 1;
+    return f.bits > 8 ? (float)(((const uint16_t*)row)[i] >> 6) : (float)row[i];
+}
+
 // gather_kernel on a YUV frame: the same tile layout, slots and source index (clamped, through aug_src); per tile pixel Y and the 2 x 2 chroma
 // neighbours of its source position, chroma upsampled to the luma grid (columns: even x C[x/2], odd x the mean of C[(x-1)/2] and C[(x+1)/2]; rows:
 // 2k takes 1/4 C[k-1] + 3/4 C[k], 2k+1 takes 3/4 C[k] + 1/4 C[k+1]; indices clamped), the matrix inverted in fp32, R, G, B clamped to [0, 1].
-// (The upsampled codes are exact in fp32: integers below 2^10 times quarters.)
-template <typename P>
+// (The upsampled codes are exact in fp32: integers below 2^10 times quarters.)  That is I420, and NV12 through yuv_luma / yuv_chroma; I422 keeps the
+// column rule and takes chroma row fy itself; I444 takes the chroma of the pixel.
+template <typename P, int L>
 __global__ __launch_bounds__(256) void gather_yuv_kernel(const GatherYuvParams p) {
     const int T = p.T;
     const long total = (long)p.B * T * T;
@@ -193,14 +211,23 @@ __global__ __launch_bounds__(256) void gather_yuv_kernel(const GatherYuvParams p
             int sy, sx;
             aug_src(sl.aug, T - 1, y, x, sy, sx);
             const int fy = min(max(sl.y + sy, 0), rows - 1), fx = min(max(sl.x + sx, 0), cols - 1);
-            const int ck = fy >> 1, cj = fx >> 1;
-            const bool odd_y = fy & 1;
-            const int r0 = odd_y ? ck : max(ck - 1, 0), r1 = odd_y ? min(ck + 1, ch - 1) : ck;
-            const float w0 = odd_y ? 0.75f : 0.25f, w1 = odd_y ? 0.25f : 0.75f;
-            const int c1 = (fx & 1) ? min(cj + 1, cw - 1) : cj;
-            const float u = w0 * (0.5f * (yuv_sample(p.src, 1, r0, cj) + yuv_sample(p.src, 1, r0, c1))) + w1 * (0.5f * (yuv_sample(p.src, 1, r1, cj) + yuv_sample(p.src, 1, r1, c1)));
-            const float w = w0 * (0.5f * (yuv_sample(p.src, 2, r0, cj) + yuv_sample(p.src, 2, r0, c1))) + w1 * (0.5f * (yuv_sample(p.src, 2, r1, cj) + yuv_sample(p.src, 2, r1, c1)));
-            const float Y = (yuv_sample(p.src, 0, fy, fx) - k.y_off) * k.y_mul, cb = (u - k.c_off) * k.c_mul, cr = (w - k.c_off) * k.c_mul;
+            float u, w;
+            if constexpr (L == kYuvI444) {
+                u = yuv_chroma<L>(p.src, 1, fy, fx); w = yuv_chroma<L>(p.src, 2, fy, fx);
+            } else if constexpr (L == kYuvI422) {
+                const int cj = fx >> 1, c1 = (fx & 1) ? min(cj + 1, cw - 1) : cj;
+                u = 0.5f * (yuv_chroma<L>(p.src, 1, fy, cj) + yuv_chroma<L>(p.src, 1, fy, c1));
+                w = 0.5f * (yuv_chroma<L>(p.src, 2, fy, cj) + yuv_chroma<L>(p.src, 2, fy, c1));
+            } else {
+                const int ck = fy >> 1, cj = fx >> 1;
+                const bool odd_y = fy & 1;
+                const int r0 = odd_y ? ck : max(ck - 1, 0), r1 = odd_y ? min(ck + 1, ch - 1) : ck;
+                const float w0 = odd_y ? 0.75f : 0.25f, w1 = odd_y ? 0.25f : 0.75f;
+                const int c1 = (fx & 1) ? min(cj + 1, cw - 1) : cj;
+                u = w0 * (0.5f * (yuv_chroma<L>(p.src, 1, r0, cj) + yuv_chroma<L>(p.src, 1, r0, c1))) + w1 * (0.5f * (yuv_chroma<L>(p.src, 1, r1, cj) + yuv_chroma<L>(p.src, 1, r1, c1)));
+                w = w0 * (0.5f * (yuv_chroma<L>(p.src, 2, r0, cj) + yuv_chroma<L>(p.src, 2, r0, c1))) + w1 * (0.5f * (yuv_chroma<L>(p.src, 2, r1, cj) + yuv_chroma<L>(p.src, 2, r1, c1)));
+            }
+            const float Y = (yuv_luma<L>(p.src, fy, fx) - k.y_off) * k.y_mul, cb = (u - k.c_off) * k.c_mul, cr = (w - k.c_off) * k.c_mul;
             const float R = Y + k.r_cr * cr, G = Y + k.g_cb * cb + k.g_cr * cr, B = Y + k.b_cb * cb;
             v = make_px<P>(fminf(fmaxf(R, 0.f), 1.f), fminf(fmaxf(G, 0.f), 1.f), fminf(fmaxf(B, 0.f), 1.f));
         }
@@ -216,30 +243,36 @@ __device__ __forceinline__ unsigned yuv_code(float off, float scale, float v, in
 // frame.  Column 8t - 1 belongs to the lane on the left: it arrives by a cross-lane move (ds_bpermute), and only lane 0 of the wave, whose left
 // neighbour lies in another workgroup, computes it again.  A full run stores Y as 8 (10-bit: 16) bytes per row and U, V as 4 (8) bytes; the ragged
 // right end stores sample by sample.  Workgroup = one wave along a chroma row; no canvas goes through HBM.
-template <typename P>
+// L: kYuvI420 is the above.  kYuvNV12 is the same arithmetic with U and V stored interleaved in plane 1 (8 bytes per full run, 10-bit: 16)
+// and, at 10 bits, every code shifted into the high bits (P010).  kYuvI422 has one luma row per chroma row: no vertical pair, a thread owns four
+// sites (8 luma columns) of row i and filters the columns of that row alone.
+template <typename P, int L>
 __global__ __launch_bounds__(kYuvThreads) void compose_yuv_kernel(const ComposeYuvParams p) {
     static_assert(kYuvSites == 4, "the packed stores below are written for four sites per thread");
+    static_assert(L == kYuvI420 || L == kYuvI422 || L == kYuvNV12, "4:4:4 output is compose_yuv444_kernel");
     constexpr int kCols = 2 * kYuvSites;
+    constexpr bool kPair = L != kYuvI422, kSemi = L == kYuvNV12;
     const ComposeParams& c = p.c;
     const P* tiles = (const P*)c.tiles;
     const YuvCoefs& k = p.k;
-    const int W = c.outW, H = c.outH, cw = (W + 1) >> 1, ch = (H + 1) >> 1;
+    const int W = c.outW, H = c.outH, cw = (W + 1) >> 1, ch = kPair ? (H + 1) >> 1 : H;
     const int runs = (cw + kYuvSites - 1) / kYuvSites;
     const int t = blockIdx.x * kYuvThreads + threadIdx.x;
     const bool active = t < runs;
     const int j0 = t * kYuvSites, X0 = 2 * j0;
     const int ncols = active ? min(kCols, W - X0) : 0;         // luma columns of the run inside the frame (>= 1 for an active lane)
     const bool wide = p.dst.bits > 8;
+    const int sh = kSemi && wide ? 6 : 0;                       // P010
     auto pixel = [&](int X, int Y, float* o) {
         float r, g, b;
         compose_pixel_sums<P>(c, tiles, X, Y, r, g, b);
         o[0] = fminf(fmaxf(r, 0.f), 1.f); o[1] = fminf(fmaxf(g, 0.f), 1.f); o[2] = fminf(fmaxf(b, 0.f), 1.f);
     };
     for (int ci = blockIdx.y; ci < ch; ci += gridDim.y) {
-        const int Ya = 2 * ci, Yb = min(2 * ci + 1, H - 1);
+        const int Ya = kPair ? 2 * ci : ci, Yb = kPair ? min(2 * ci + 1, H - 1) : ci;
         float v[kCols][3];                                      // the run's columns, the two rows averaged
         float left[3] = {0.f, 0.f, 0.f};
-        for (int r = 0; r < 2; ++r) {
+        for (int r = 0; r < (kPair ? 2 : 1); ++r) {
             const int Y = r ? Yb : Ya;
             const bool store_y = r == 0 || Yb != Ya;
             unsigned yc[kCols];
@@ -247,7 +280,7 @@ __global__ __launch_bounds__(kYuvThreads) void compose_yuv_kernel(const ComposeY
             for (int q = 0; q < kCols; ++q) {
                 float o[3] = {0.f, 0.f, 0.f};
                 if (q < ncols) pixel(X0 + q, Y, o);
-                yc[q] = yuv_code(k.y_off, k.y_scale, k.kr * o[0] + k.kg * o[1] + k.kb * o[2], k.maxcode);
+                yc[q] = yuv_code(k.y_off, k.y_scale, k.kr * o[0] + k.kg * o[1] + k.kb * o[2], k.maxcode) << sh;
 #pragma unroll
                 for (int e = 0; e < 3; ++e) v[q][e] = r ? 0.5f * (v[q][e] + o[e]) : o[e];
             }
@@ -291,6 +324,21 @@ __global__ __launch_bounds__(kYuvThreads) void compose_yuv_kernel(const ComposeY
             uc[s] = yuv_code(k.c_off, k.c_scale, (f[2] - Y) * k.cb_div, k.maxcode);
             vc[s] = yuv_code(k.c_off, k.c_scale, (f[0] - Y) * k.cr_div, k.maxcode);
         }
+        if constexpr (kSemi) {                                      // NV12 / P010: U, V, U, V, ... in plane 1
+            uint8_t* row = p.dst.p[1] + (size_t)ci * p.dst.step[1];
+            if (!wide) {
+                uint8_t* d = row + 2 * j0;
+                if (nsites == kYuvSites && (((size_t)d) & 7) == 0)
+                    *(uint2*)d = make_uint2(uc[0] | vc[0] << 8 | uc[1] << 16 | vc[1] << 24, uc[2] | vc[2] << 8 | uc[3] << 16 | vc[3] << 24);
+                else for (int s = 0; s < nsites; ++s) { d[2 * s] = (uint8_t)uc[s]; d[2 * s + 1] = (uint8_t)vc[s]; }
+            } else {
+                uint16_t* d = (uint16_t*)row + 2 * j0;
+                if (nsites == kYuvSites && (((size_t)d) & 15) == 0)
+                    *(uint4*)d = make_uint4((uc[0] | vc[0] << 16) << 6, (uc[1] | vc[1] << 16) << 6, (uc[2] | vc[2] << 16) << 6, (uc[3] | vc[3] << 16) << 6);
+                else for (int s = 0; s < nsites; ++s) { d[2 * s] = (uint16_t)(uc[s] << 6); d[2 * s + 1] = (uint16_t)(vc[s] << 6); }
+            }
+            continue;
+        }
         for (int pl = 1; pl < 3; ++pl) {
             const unsigned* cc = pl == 1 ? uc : vc;
             uint8_t* row = p.dst.p[pl] + (size_t)ci * p.dst.step[pl];
@@ -302,6 +350,93 @@ __global__ __launch_bounds__(kYuvThreads) void compose_yuv_kernel(const ComposeY
                 uint16_t* d = (uint16_t*)row + j0;
                 if (nsites == kYuvSites && (((size_t)d) & 7) == 0) *(uint2*)d = make_uint2(cc[0] | cc[1] << 16, cc[2] | cc[3] << 16);
                 else for (int s = 0; s < nsites; ++s) d[s] = (uint16_t)cc[s];
+            }
+        }
+    }
+}
+
+// compose_kernel for a YUV 4:4:4 output: compose_kernel's launch shape and its four-pixel fast path - a thread owns four consecutive pixels
+// of a row and walks a band of kComposeRows rows; where the four share their covering tiles and no TTA is involved, a tile contributes them as two
+// 16-byte loads, elsewhere each pixel goes through compose_pixel_sums; the sums and their order are compose_pixel_sums' either way.  Each pixel's R, G, B
+// are clamped to [0, 1] and coded on the spot: Y by compose_yuv_kernel's expression (the same bytes on the same canvas), Cb and Cr from the pixel's own
+// colour - no filter, no neighbour.  A full group stores 4 bytes per plane (10-bit: 8); the ragged right end stores sample by sample.
+template <typename P>
+__global__ __launch_bounds__(kComposeThreads) void compose_yuv444_kernel(const ComposeYuvParams p) {
+    constexpr bool kHalf = sizeof(P) == 8;
+    const ComposeParams& c = p.c;
+    const YuvCoefs& k = p.k;
+    const int W = c.outW, H = c.outH;
+    const int gw = (W + 3) >> 2;
+    const int xg = blockIdx.x * kComposeThreads + threadIdx.x;
+    if (xg >= gw) return;
+    const P* tiles = (const P*)c.tiles;
+    const int To = c.To, n = To - 1;
+    const int X = 4 * xg;
+    const int np = min(4, W - X);
+    int a0 = X - To + 1; a0 = a0 <= 0 ? 0 : (a0 + c.stride_x - 1) / c.stride_x;
+    int b0 = X + 3 - To + 1; b0 = b0 <= 0 ? 0 : (b0 + c.stride_x - 1) / c.stride_x;
+    const int a1 = min(c.nx - 1, X / c.stride_x), b1 = min(c.nx - 1, (X + 3) / c.stride_x);
+    const bool fast = kHalf && np == 4 && !c.tta && a0 == b0 && a1 == b1;
+    const bool wide = p.dst.bits > 8;
+    const int Y0 = blockIdx.y * kComposeRows, Y1 = min(H, Y0 + kComposeRows);
+    for (int Y = Y0; Y < Y1; ++Y) {
+        float acc[4][3] = {};
+        if (fast) {
+            int j0 = Y - To + 1; j0 = j0 <= 0 ? 0 : (j0 + c.stride_y - 1) / c.stride_y;
+            const int j1 = min(c.ny - 1, Y / c.stride_y);
+            for (int ti = a0; ti <= a1; ++ti) {
+                const int ox = ti * c.stride_x, lx = X - ox;
+                const int rw = ox + To > W ? W - ox : To;
+                for (int tj = j0; tj <= j1; ++tj) {
+                    const int oy = tj * c.stride_y, ly = Y - oy;
+                    const int rh = oy + To > H ? H - oy : To;
+                    const long tile = (long)ti * c.ny + tj - c.first_tile;
+                    const half4* tp = (const half4*)c.tiles + tile * (long)To * To + (long)ly * To + lx;
+                    half4 h[4];
+                    if ((((size_t)tp) & 15) == 0) { const half8 u0 = *(const half8*)tp, u1 = *(const half8*)(tp + 2);
+                        h[0] = (half4){u0[0], u0[1], u0[2], u0[3]}; h[1] = (half4){u0[4], u0[5], u0[6], u0[7]}; h[2] = (half4){u1[0], u1[1], u1[2], u1[3]}; h[3] = (half4){u1[4], u1[5], u1[6], u1[7]}; }
+                    else { h[0] = tp[0]; h[1] = tp[1]; h[2] = tp[2]; h[3] = tp[3]; }
+                    const bool wl = ox > 0, wt = oy > 0 && ly < c.ovy, wr = ox + rw < W, wb = oy + rh < H && n - ly < c.ovy;
+                    const float fy_t = wt ? c.ramp_y[ly] : 1.f, fy_b = wb ? c.ramp_y[n - ly] : 1.f;
+#pragma unroll
+                    for (int q = 0; q < 4; ++q) {
+                        float v0 = (float)h[q][0], v1 = (float)h[q][1], v2 = (float)h[q][2];
+                        if (c.ovx || c.ovy) {
+                            const int lk = lx + q;
+                            if (wl && lk < c.ovx) { float w = c.ramp_x[lk]; v0 *= w; v1 *= w; v2 *= w; }
+                            if (wt) { v0 *= fy_t; v1 *= fy_t; v2 *= fy_t; }
+                            if (wr && n - lk < c.ovx) { float w = c.ramp_x[n - lk]; v0 *= w; v1 *= w; v2 *= w; }
+                            if (wb) { v0 *= fy_b; v1 *= fy_b; v2 *= fy_b; }
+                        }
+                        acc[q][0] += v0; acc[q][1] += v1; acc[q][2] += v2;
+                    }
+                }
+            }
+        } else {
+            for (int q = 0; q < np; ++q) compose_pixel_sums<P>(c, tiles, X + q, Y, acc[q][0], acc[q][1], acc[q][2]);
+        }
+        unsigned yc[4], uc[4], vc[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            float o[3];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) o[e] = fminf(fmaxf(acc[q][e], 0.f), 1.f);
+            const float Yn = k.kr * o[0] + k.kg * o[1] + k.kb * o[2];
+            yc[q] = yuv_code(k.y_off, k.y_scale, Yn, k.maxcode);
+            uc[q] = yuv_code(k.c_off, k.c_scale, (o[2] - Yn) * k.cb_div, k.maxcode);
+            vc[q] = yuv_code(k.c_off, k.c_scale, (o[0] - Yn) * k.cr_div, k.maxcode);
+        }
+        for (int pl = 0; pl < 3; ++pl) {
+            const unsigned* cc = pl == 0 ? yc : pl == 1 ? uc : vc;
+            uint8_t* row = p.dst.p[pl] + (size_t)Y * p.dst.step[pl];
+            if (!wide) {
+                uint8_t* d = row + X;
+                if (np == 4 && (((size_t)d) & 3) == 0) *(unsigned*)d = cc[0] | cc[1] << 8 | cc[2] << 16 | cc[3] << 24;
+                else for (int q = 0; q < np; ++q) d[q] = (uint8_t)cc[q];
+            } else {
+                uint16_t* d = (uint16_t*)row + X;
+                if (np == 4 && (((size_t)d) & 7) == 0) *(uint2*)d = make_uint2(cc[0] | cc[1] << 16, cc[2] | cc[3] << 16);
+                else for (int q = 0; q < np; ++q) d[q] = (uint16_t)cc[q];
             }
         }
     }
@@ -427,19 +562,45 @@ hipError_t launch_compose_canvas(const ComposeParams& p, float* canvas, hipStrea
     else hipLaunchKernelGGL(compose_canvas_kernel<half4>, grid, dim3(256), 0, s, p, canvas);
     return hipGetLastError();
 }
+template <int L>
+static void launch_gather_yuv_as(const GatherYuvParams& p, dim3 grid, hipStream_t s) {
+    if (p.fp32) hipLaunchKernelGGL((gather_yuv_kernel<float4v, L>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((gather_yuv_kernel<half4, L>), grid, dim3(256), 0, s, p);
+}
 hipError_t launch_gather_yuv(const GatherYuvParams& p, hipStream_t s) {
     const dim3 grid(grid_for((long)p.B * p.T * p.T));
-    if (p.fp32) hipLaunchKernelGGL(gather_yuv_kernel<float4v>, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(gather_yuv_kernel<half4>, grid, dim3(256), 0, s, p);
+    switch (p.src.layout) {
+        case kYuvI420: launch_gather_yuv_as<kYuvI420>(p, grid, s); break;
+        case kYuvI422: launch_gather_yuv_as<kYuvI422>(p, grid, s); break;
+        case kYuvI444: launch_gather_yuv_as<kYuvI444>(p, grid, s); break;
+        case kYuvNV12: launch_gather_yuv_as<kYuvNV12>(p, grid, s); break;
+        default: return hipErrorInvalidValue;                       // no kernel for it: an error, never another layout's kernel
+    }
     return hipGetLastError();
 }
+template <int L>
+static void launch_compose_yuv_as(const ComposeYuvParams& p, dim3 grid, hipStream_t s) {
+    if (p.c.fp32) hipLaunchKernelGGL((compose_yuv_kernel<float4v, L>), grid, dim3(kYuvThreads), 0, s, p);
+    else hipLaunchKernelGGL((compose_yuv_kernel<half4, L>), grid, dim3(kYuvThreads), 0, s, p);
+}
 hipError_t launch_compose_yuv(const ComposeYuvParams& p, hipStream_t s) {
-    const int cw = (p.c.outW + 1) / 2, ch = (p.c.outH + 1) / 2;
-    if (cw <= 0 || ch <= 0) return hipSuccess;
+    if (p.c.outW <= 0 || p.c.outH <= 0) return hipSuccess;
+    if (p.dst.layout == kYuvI444) {
+        const int gw = (p.c.outW + 3) / 4;
+        const dim3 grid((unsigned)((gw + kComposeThreads - 1) / kComposeThreads), (unsigned)((p.c.outH + kComposeRows - 1) / kComposeRows));
+        if (p.c.fp32) hipLaunchKernelGGL(compose_yuv444_kernel<float4v>, grid, dim3(kComposeThreads), 0, s, p);
+        else hipLaunchKernelGGL(compose_yuv444_kernel<half4>, grid, dim3(kComposeThreads), 0, s, p);
+        return hipGetLastError();
+    }
+    const int cw = (p.c.outW + 1) / 2, ch = yuv_chroma_rows(p.c.outH, p.dst.layout);
     const int runs = (cw + kYuvSites - 1) / kYuvSites;
     const dim3 grid((unsigned)((runs + kYuvThreads - 1) / kYuvThreads), (unsigned)(ch < 65535 ? ch : 65535));
-    if (p.c.fp32) hipLaunchKernelGGL(compose_yuv_kernel<float4v>, grid, dim3(kYuvThreads), 0, s, p);
-    else hipLaunchKernelGGL(compose_yuv_kernel<half4>, grid, dim3(kYuvThreads), 0, s, p);
+    switch (p.dst.layout) {
+        case kYuvI420: launch_compose_yuv_as<kYuvI420>(p, grid, s); break;
+        case kYuvI422: launch_compose_yuv_as<kYuvI422>(p, grid, s); break;
+        case kYuvNV12: launch_compose_yuv_as<kYuvNV12>(p, grid, s); break;
+        default: return hipErrorInvalidValue;
+    }
     return hipGetLastError();
 }
 hipError_t launch_se(const SeParams& p, hipStream_t s) {

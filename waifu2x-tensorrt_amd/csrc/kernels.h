@@ -276,10 +276,18 @@ int resample_rows_max(const int* fy, int outH, int inH, int ky);   // host: the 
 hipError_t launch_resample(const ResampleParams& p, hipStream_t s);
 // YUV 4:2:0 frames (Img2Img::renderYuv): three planes - Y of rows x cols, U and V of ceil(rows/2) x ceil(cols/2) - with 8-bit (uint8) or 10-bit
 // (uint16, low 10 bits) samples; steps in bytes.  Chroma siting MPEG-2 "left": chroma (i, j) sits at luma (x = 2j, y = 2i + 1/2).
+// layout (YuvLayout): kYuvI420 the above; kYuvI422 U and V of rows x ceil(cols/2) (chroma row y serves luma row y); kYuvI444 U and V of
+// rows x cols; kYuvNV12 I420 with U and V interleaved in p[1] (ceil(rows/2) rows of 2 * ceil(cols/2) samples, U first; p[2] unused) and, at 10 bits,
+// the code in the high 10 bits of each uint16 of Y and UV (P010: read >> 6, written << 6).
+constexpr int kYuvI420 = 0, kYuvI422 = 1, kYuvI444 = 2, kYuvNV12 = 3;
 struct YuvPlanes {
     uint8_t* p[3] = {nullptr, nullptr, nullptr}; size_t step[3] = {0, 0, 0};
     int rows = 0, cols = 0, bits = 8;
+    int layout = kYuvI420;
 };
+// the chroma plane's rows and samples per row (NV12: both components) of a rows x cols frame
+inline int yuv_chroma_rows(int rows, int layout) { return layout == kYuvI420 || layout == kYuvNV12 ? (rows + 1) / 2 : rows; }
+inline int yuv_chroma_samples(int cols, int layout) { return layout == kYuvI444 ? cols : layout == kYuvNV12 ? 2 * ((cols + 1) / 2) : (cols + 1) / 2; }
 // The code <-> normalised value maps of one (matrix, range, bits) (yuv_coefs): Y' = (Y - y_off) * y_mul, C' = (C - c_off) * c_mul on input,
 // Y = y_off + Y' / y_mul, C = c_off + C' / c_mul on output; kr, kb, kg the matrix
 struct YuvCoefs {
@@ -307,7 +315,8 @@ inline YuvCoefs yuv_coefs(int matrix, int full_range, int bits) {
     return k;
 }
 // k_prepost.hip gather_yuv_kernel: gather_kernel's tiles (same slots, replicate padding, TTA source index) from a YUV frame - Y and the 2 x 2
-// chroma neighbours of the source pixel, chroma upsampled to the luma grid, the matrix inverted in fp32, R, G, B clamped to [0, 1]
+// chroma neighbours of the source pixel, chroma upsampled to the luma grid, the matrix inverted in fp32, R, G, B clamped to [0, 1].  One instantiation
+// per src.layout: I422 interpolates columns only, I444 reads the pixel's own chroma, NV12 is I420 on de-interleaved samples.
 struct GatherYuvParams {
     YuvPlanes src; YuvCoefs k;
     void* out = nullptr; int fp32 = 0;
@@ -322,6 +331,9 @@ struct ComposeYuvParams {
     YuvPlanes dst; YuvCoefs k;
 };
 constexpr int kYuvSites = 4, kYuvThreads = 64;   // chroma sites (8 luma columns, 2 rows) per thread, threads per workgroup (one wave)
+// dst.layout picks the kernel: I420 and NV12 compose_yuv_kernel (NV12: U and V stored interleaved, P010 codes << 6), I422 the same kernel
+// without the vertical pair (a thread owns four sites of ONE luma row), I444 compose_yuv444_kernel (compose_kernel's shape: four pixels of a row per
+// thread, its four-pixel fast path, no chroma filter)
 hipError_t launch_compose_yuv(const ComposeYuvParams& p, hipStream_t s);
 // RGBA frames (renderRgba; k_rgba.hip).
 // alpha_bleed_kernel: the uploaded BGRA frame split into the BGR frame gather reads and the alpha plane, with the colour of every pixel of alpha > 0

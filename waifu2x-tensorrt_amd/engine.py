@@ -52,6 +52,40 @@ def _yuv_bits(planes) -> int:
     return 8 if y.dtype == np.uint8 else 10
 
 
+YUV_LAYOUTS = {"i420": 0, "i422": 1, "i444": 2, "nv12": 3}   # W2X_YUV_I420 .. _NV12 (include/w2x/c_api.h)
+
+
+def _layout_id(name) -> int:
+    if name not in YUV_LAYOUTS:
+        raise ValueError(f"layout must be one of {sorted(YUV_LAYOUTS)}, got {name!r}")
+    return YUV_LAYOUTS[name]
+
+
+def yuv_layout_plane_shapes(rows: int, cols: int, layout: str = "i420"):
+    """[(rows, samples per row)] of the planes of a frame of `layout`: Y, U, V - or Y, UV for "nv12" (U and V interleaved: 2 * ceil(cols/2) samples a row)"""
+    lid = _layout_id(layout)
+    cr = (rows + 1) // 2 if lid in (0, 3) else rows
+    cc = cols if lid == 2 else (cols + 1) // 2
+    return [(rows, cols), (cr, 2 * cc)] if lid == 3 else [(rows, cols), (cr, cc), (cr, cc)]
+
+
+def _yuv_layout_bits(planes, layout) -> int:
+    """_yuv_bits for a frame of `layout`"""
+    y = planes[0]
+    if y.ndim != 2 or y.dtype not in (np.uint8, np.uint16):
+        raise ValueError("YUV planes must be 2-D uint8 (8-bit) or uint16 (10-bit) arrays")
+    shapes = yuv_layout_plane_shapes(*y.shape, layout)
+    if len(planes) != len(shapes) or any(p.dtype != y.dtype or p.shape != shape or p.strides[1] != p.itemsize or p.strides[0] <= 0 for p, shape in zip(planes, shapes)):
+        raise ValueError(f"{layout} planes of one sample type with packed rows expected: {[q.shape for q in planes]} for {y.shape}")
+    return 8 if y.dtype == np.uint8 else 10
+
+
+def _plane_args(planes):
+    """three pointers and three steps of a frame for the C ABI (an NV12 frame leaves the third NULL / 0)"""
+    pad = [None] * (3 - len(planes))
+    return [p.ctypes.data for p in planes] + pad, [p.strides[0] for p in planes] + [0] * len(pad)
+
+
 def _filter_id(name) -> int:
     if name not in RESIZE_FILTERS:
         raise ValueError(f"filter must be one of {sorted(RESIZE_FILTERS)}, got {name!r}")
@@ -156,6 +190,10 @@ def lib():
     L.w2x_alpha_bleed_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int]; L.w2x_alpha_bleed_device.restype = C.c_int
     L.w2x_alpha_bleed.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t]; L.w2x_alpha_bleed.restype = C.c_int
     L.w2x_yuv_plane_sizes.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp]; L.w2x_yuv_plane_sizes.restype = C.c_int
+    L.w2x_render_yuv_layout.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]; L.w2x_render_yuv_layout.restype = C.c_int
+    L.w2x_render_sequence_yuv_layout.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
+    L.w2x_render_sequence_yuv_layout.restype = C.c_int
+    L.w2x_yuv_layout_plane_sizes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]; L.w2x_yuv_layout_plane_sizes.restype = C.c_int
     L.w2x_render_strip.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]; L.w2x_render_strip.restype = C.c_int
     L.w2x_render_sequence.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int]; L.w2x_render_sequence.restype = C.c_int
     L.w2x_alloc_host.argtypes = [vp, C.c_size_t]; L.w2x_alloc_host.restype = vp
@@ -200,6 +238,7 @@ EXPORTED_SYMBOLS = [
     "w2x_render", "w2x_render16", "w2x_infer", "w2x_output_tile_size", "w2x_plan_flops", "w2x_pass_tiles", "w2x_last_render_ms", "w2x_bench_resident", "w2x_resident_output", "w2x_profile_frame", "w2x_op_times",
     "w2x_render_resized", "w2x_render16_resized", "w2x_render_sequence_resized", "w2x_resize_weights",
     "w2x_render_yuv", "w2x_render_sequence_yuv", "w2x_yuv_plane_sizes", "w2x_render_yuv_resized", "w2x_render_sequence_yuv_resized",
+    "w2x_render_yuv_layout", "w2x_render_sequence_yuv_layout", "w2x_yuv_layout_plane_sizes",
     "w2x_render_rgba", "w2x_render_rgba_resized", "w2x_render_sequence_rgba", "w2x_render_sequence_rgba_resized", "w2x_alpha_bleed_device", "w2x_alpha_bleed", "w2x_dead_skip_extents",
     "w2x_render_strip", "w2x_strip_plan", "w2x_render_sharded", "w2x_shard_plan", "w2x_shard_compute", "w2x_shard_slab", "w2x_shard_finish", "w2x_ipc_export", "w2x_ipc_open", "w2x_ipc_close", "w2x_render_sequence", "w2x_alloc_host", "w2x_free_host", "w2x_pin_host", "w2x_unpin_host", "w2x_calculate_tiles", "w2x_tile_weights", "w2x_describe_plan", "w2x_describe_plan_precision", "w2x_write_engine_file", "w2x_validate_engine_file", "w2x_device_pci_bus_id", "w2x_sha256_hex", "w2x_version", "w2x_debug_set"]
 
@@ -506,10 +545,18 @@ class Img2Img:
         dt = np.uint8 if bits == 8 else np.uint16
         return tuple(np.empty(shape, dt) for shape in yuv_plane_shapes(rows * s, cols * s))
 
-    def render_yuv(self, y: np.ndarray, u: np.ndarray, v: np.ndarray, *, matrix: str = "bt709", full_range: bool = False, out_bits: int | None = None,
-                   out=None):
+    def render_yuv(self, y, u: np.ndarray | None = None, v: np.ndarray | None = None, *, matrix: str = "bt709", full_range: bool = False, out_bits: int | None = None,
+                   out=None, layout: str | None = None, out_layout: str | None = None):
         """render() on a YUV 4:2:0 frame (w2x_render_yuv): uint8 planes are 8-bit, uint16 planes 10-bit; out_bits (8 or 10, default the input's)
-        sets the output depth.  Returns (Y, U, V) at the scaled size, or raises.  out: pre-allocated planes (then a bool is returned)."""
+        sets the output depth.  Returns (Y, U, V) at the scaled size, or raises.  out: pre-allocated planes (then a bool is returned).
+        With the frame given as one tuple of planes, or with layout= / out_layout= ("i420", "i422", "i444", "nv12"; out_layout defaults to the input's), the
+        call goes through w2x_render_yuv_layout: an "nv12" frame is (y, uv) with uv of ceil(rows/2) x 2 * ceil(cols/2) samples (10-bit: P010, codes << 6),
+        and the result is the tuple of out_layout's planes (yuv_layout_plane_shapes)."""
+        if isinstance(y, (tuple, list)) or layout is not None or out_layout is not None:
+            if isinstance(y, (tuple, list)) and (u is not None or v is not None):
+                raise ValueError("give the frame as one tuple of planes or as three positional planes, not both")
+            planes = tuple(y) if isinstance(y, (tuple, list)) else tuple(p for p in (y, u, v) if p is not None)
+            return self._render_yuv_layout(planes, layout or "i420", out_layout, matrix, full_range, out_bits, out)
         bits = _yuv_bits((y, u, v))
         ob = bits if out_bits is None else int(out_bits)
         ret_array = out is None
@@ -531,10 +578,34 @@ class Img2Img:
             return dst
         return ok
 
+    def _render_yuv_layout(self, planes, layout, out_layout, matrix, full_range, out_bits, out):
+        """render_yuv() through w2x_render_yuv_layout"""
+        out_layout = layout if out_layout is None else out_layout
+        lid, olid = _layout_id(layout), _layout_id(out_layout)
+        bits = _yuv_layout_bits(planes, layout)
+        ob = bits if out_bits is None else int(out_bits)
+        rows, cols = planes[0].shape
+        s = getattr(self, "_scaling", 0)
+        dt = np.uint16 if ob == 10 else np.uint8
+        shapes = yuv_layout_plane_shapes(rows * s, cols * s, out_layout)
+        ret_array = out is None
+        dst = tuple(np.empty(shape, dt) for shape in shapes) if out is None else tuple(out)
+        if len(dst) != len(shapes) or any(not isinstance(p, np.ndarray) or p.dtype != dt or p.shape != shape or p.strides[1] != p.itemsize for p, shape in zip(dst, shapes)):
+            raise ValueError(f"out must be the 2-D planes of the scaled {out_layout} shapes, uint8 for 8-bit and uint16 for 10-bit output, with packed rows")
+        (sp, ss), (dp, ds) = _plane_args(planes), _plane_args(dst)
+        ok = bool(self._L.w2x_render_yuv_layout(self._h, (C.c_void_p * 3)(*sp), (C.c_size_t * 3)(*ss), rows, cols, bits, lid,
+                                                (C.c_void_p * 3)(*dp), (C.c_size_t * 3)(*ds), rows * s, cols * s, ob, olid, _matrix_id(matrix), 1 if full_range else 0))
+        if ret_array:
+            if not ok:
+                raise W2xError(self.last_error() or "render_yuv failed")
+            return dst
+        return ok
+
     def render_yuv_resized(self, y: np.ndarray, u: np.ndarray, v: np.ndarray, size, *, matrix: str = "bt709", full_range: bool = False,
                            out_bits: int | None = None, filter: str = "bicubic", dst=None):
         """render_yuv() with the canvas resized on the device to size = (rows, cols), each in [input dim, input dim * scaling], before it is encoded
-        (w2x_render_yuv_resized).  Returns (Y, U, V) at the target size, or raises.  dst: pre-allocated planes (then a bool is returned)."""
+        (w2x_render_yuv_resized).  Returns (Y, U, V) at the target size, or raises.  dst: pre-allocated planes (then a bool is returned).
+        4:2:0 planes only, both sides (resample_yuv_kernel encodes 4:2:0): planes of another layout's shapes raise the ValueError that names 4:2:0."""
         bits = _yuv_bits((y, u, v))
         ob = bits if out_bits is None else int(out_bits)
         rows, cols = int(size[0]), int(size[1])
@@ -557,29 +628,43 @@ class Img2Img:
 
     def render_sequence_yuv_resized(self, frames, size, *, matrix: str = "bt709", full_range: bool = False, out_bits: int | None = None, pinned: bool = False,
                                     filter: str = "bicubic"):
-        """render_sequence_yuv() with every frame resized to size = (rows, cols) like render_yuv_resized() (w2x_render_sequence_yuv_resized)"""
+        """render_sequence_yuv() with every frame resized to size = (rows, cols) like render_yuv_resized() (w2x_render_sequence_yuv_resized); 4:2:0 planes only"""
         return self._sequence_yuv(frames, (int(size[0]), int(size[1])), _filter_id(filter), matrix, full_range, out_bits, pinned)
 
-    def render_sequence_yuv(self, frames, *, matrix: str = "bt709", full_range: bool = False, out_bits: int | None = None, pinned: bool = False):
+    def render_sequence_yuv(self, frames, *, matrix: str = "bt709", full_range: bool = False, out_bits: int | None = None, pinned: bool = False,
+                            layout: str | None = None, out_layout: str | None = None):
         """render_yuv() over equally sized frames [(y, u, v), ...] through the pipeline of render_sequence() (w2x_render_sequence_yuv).
-        pinned=True takes the output planes from alloc_host() (a ring of three frames; copies of the results are returned)."""
-        return self._sequence_yuv(frames, None, None, matrix, full_range, out_bits, pinned)
+        pinned=True takes the output planes from alloc_host() (a ring of three frames; copies of the results are returned).
+        layout= / out_layout= as in render_yuv() (w2x_render_sequence_yuv_layout): every frame is a tuple of `layout`'s planes - [(y, uv), ...] for "nv12" -
+        and a frame of another layout's shapes raises ValueError."""
+        return self._sequence_yuv(frames, None, None, matrix, full_range, out_bits, pinned, layout, out_layout)
 
-    def _sequence_yuv(self, frames, size, fid, matrix, full_range, out_bits, pinned):
-        """the two YUV sequence calls: size = None the scaled size (w2x_render_sequence_yuv), else the target of w2x_render_sequence_yuv_resized with filter fid"""
+    def _sequence_yuv(self, frames, size, fid, matrix, full_range, out_bits, pinned, layout=None, out_layout=None):
+        """the YUV sequence calls: size = None the scaled size (w2x_render_sequence_yuv; with a layout given w2x_render_sequence_yuv_layout), else the target of
+        w2x_render_sequence_yuv_resized with filter fid"""
         n = len(frames)
         if n == 0:
             return []
-        bits = _yuv_bits(frames[0])
+        with_layout = layout is not None or out_layout is not None
+        layout = layout or "i420"
+        out_layout = out_layout or layout
+        lid, olid = _layout_id(layout), _layout_id(out_layout)
+        frames = [tuple(f) for f in frames]
+        bits = _yuv_layout_bits(frames[0], layout) if with_layout else _yuv_bits(frames[0])
         ob = bits if out_bits is None else int(out_bits)
         rows, cols = frames[0][0].shape
         steps = [p.strides[0] for p in frames[0]]
-        for f in frames:
-            if _yuv_bits(f) != bits or f[0].shape != (rows, cols) or [p.strides[0] for p in f] != steps:
+        for f in frames[1:]:
+            try:
+                fb = _yuv_layout_bits(f, layout) if with_layout else _yuv_bits(f)
+            except ValueError:
+                fb = None                                                       # (the planes of another layout)
+            if fb != bits or f[0].shape != (rows, cols) or [p.strides[0] for p in f] != steps:
                 raise ValueError("frames must be YUV planes of one size, depth and layout")
         s = getattr(self, "_scaling", 0)
         orows, ocols = (rows * s, cols * s) if size is None else size
-        shapes = yuv_plane_shapes(max(orows, 1), max(ocols, 1))                # (an empty target: refused by the library)
+        shapes = yuv_layout_plane_shapes(max(orows, 1), max(ocols, 1), out_layout)   # (an empty target: refused by the library)
+        steps = steps + [0] * (3 - len(steps))
         dt = np.uint8 if ob != 10 else np.uint16
         own = []
         if pinned:
@@ -591,13 +676,17 @@ class Img2Img:
                     planes.append(buf[o:o + nb].view(dt).reshape(r, c)); o += nb
                 own.append((buf, tuple(planes)))
         outs = [own[k % len(own)][1] for k in range(n)] if own else [tuple(np.empty(shape, dt) for shape in shapes) for _ in range(n)]
-        dsteps = (C.c_size_t * 3)(*[p.strides[0] for p in outs[0]])
+        dsteps = (C.c_size_t * 3)(*_plane_args(outs[0])[1])
 
         def run(fs, os_):
             m = len(fs)
-            sp = (C.c_void_p * (3 * m))(*[p.ctypes.data for f in fs for p in f])
-            dp = (C.c_void_p * (3 * m))(*[p.ctypes.data for o in os_ for p in o])
+            sp = (C.c_void_p * (3 * m))(*[q for f in fs for q in _plane_args(f)[0]])
+            dp = (C.c_void_p * (3 * m))(*[q for o in os_ for q in _plane_args(o)[0]])
             args = (self._h, sp, (C.c_size_t * 3)(*steps), rows, cols, bits, dp, dsteps, orows, ocols, ob, m, _matrix_id(matrix), 1 if full_range else 0)
+            if with_layout and size is None:
+                if not self._L.w2x_render_sequence_yuv_layout(*args[:6], lid, *args[6:11], olid, *args[11:]):
+                    raise W2xError(self.last_error() or "render_sequence_yuv failed")
+                return
             if not (self._L.w2x_render_sequence_yuv(*args) if size is None else self._L.w2x_render_sequence_yuv_resized(*args, fid)):
                 raise W2xError(self.last_error() or ("render_sequence_yuv failed" if size is None else "render_sequence_yuv_resized failed"))
         if own:
@@ -841,6 +930,15 @@ def alpha_bleed(bgr: np.ndarray, alpha: np.ndarray, radius: int) -> np.ndarray:
                                  bgr.shape[0], bgr.shape[1], int(radius), out.ctypes.data if out.size else None, out.strides[0]):
         raise W2xError(f"invalid alpha bleed: a {bgr.shape[1]}x{bgr.shape[0]} frame at radius {radius}")
     return out
+
+
+def yuv_layout_plane_sizes(rows: int, cols: int, bits: int, layout: str = "i420"):
+    """(plane_rows, plane_cols in samples, plane_bytes), one entry per plane of a packed frame of `layout` - two for "nv12" - (w2x_yuv_layout_plane_sizes);
+    raises for invalid arguments"""
+    n, pr, pc, pb = C.c_int(0), (C.c_int * 3)(), (C.c_int * 3)(), (C.c_size_t * 3)()
+    if not lib().w2x_yuv_layout_plane_sizes(int(rows), int(cols), int(bits), _layout_id(layout), C.byref(n), pr, pc, pb):
+        raise W2xError(f"invalid YUV frame {rows}x{cols} at {bits} bits")
+    return list(pr)[:n.value], list(pc)[:n.value], list(pb)[:n.value]
 
 
 def yuv_plane_sizes(rows: int, cols: int, bits: int):
