@@ -196,6 +196,13 @@ Plan lower_for_shape(const std::string& onnxModelPath, int batch, int channels, 
     return plan;
 }
 
+// the filter of a resized call as resize_taps() and resize_problem() number it: 0 bicubic, 1 bilinear; any other value is 2, which resize_problem() refuses
+int filter_id(ResizeFilter filter) { return filter == ResizeFilter::Bilinear ? 1 : filter == ResizeFilter::Bicubic ? 0 : 2; }
+
+// what Impl::entry() logs for a call before a successful load, and in front of the message of an exception
+constexpr const char* kNotLoaded = "Render called before a successful load.";
+constexpr const char* kRenderFailed = "Render failed unexpectedly: ";
+
 }  // namespace
 
 struct Img2Img::Impl {
@@ -312,7 +319,7 @@ struct Img2Img::Impl {
     hipEvent_t ev_up[2] = {nullptr, nullptr}, ev_comp[2] = {nullptr, nullptr}, ev_dn[2] = {nullptr, nullptr};
     // renderResized() / renderSequenceResized(): the fp32 RGB canvas compose_canvas_kernel writes and resample_kernel reads (allocated on the first
     // resized frame, so render() callers pay nothing; not a captured address: growing it keeps the pass graphs) and the device tap tables, uploaded
-    // once per (canvas size, target size, filter).  `rs` is the table of the frame being rendered (null outside a resized call).
+    // once per (canvas size, target size, filter).
     float* d_canvas = nullptr; size_t canvas_cap = 0;
     struct ResizeTables {
         int inW = 0, inH = 0, outW = 0, outH = 0, filter = 0;
@@ -320,24 +327,33 @@ struct Img2Img::Impl {
         int kx = 0, ky = 0, rows_max = 0;
     };
     std::deque<ResizeTables> rs_tables;
-    const ResizeTables* rs = nullptr;
-    // renderYuv() / renderSequenceYuv(): the frame being rendered is YUV (null outside such a call).  d_frame / d_out then hold the planes of in_layout /
-    // out_layout (yuv_layout; kernels.h kYuvI420 ..) and the gather / compose launches are gather_yuv_kernel / compose_yuv_kernel (4:4:4 output:
-    // compose_yuv444_kernel); `key` tells the captured passes of each input format - depth, range, matrix, layout - apart.
-    // With `rs` set as well (renderYuvResized) the frame ends with compose_canvas_kernel and resample_yuv_kernel, and d_out holds planes of the target size.
+    // YUV frames (renderYuv / renderSequenceYuv): d_frame / d_out hold the planes of in_layout / out_layout (yuv_layout; kernels.h kYuvI420 ..) and the gather /
+    // compose launches are gather_yuv_kernel / compose_yuv_kernel (4:4:4 output: compose_yuv444_kernel); `key` tells the captured passes of each input format -
+    // depth, range, matrix, layout - apart.  Resized (renderYuvResized) the frame ends with compose_canvas_kernel and resample_yuv_kernel, and d_out holds planes
+    // of the target size.
     struct YuvJob { YuvCoefs in, out; int in_bits = 8, out_bits = 8, key = 0, in_layout = kYuvI420, out_layout = kYuvI420; };
-    const YuvJob* yuv = nullptr;
-    // renderRgba(): d_frame holds the uploaded BGRA frame, alpha_bleed_kernel writes the BGR frame and the alpha plane the passes gather from (gather_rgba_kernel,
-    // `rgba` set for the duration of the call), d_minmax receives max(A) and max(255 - A), read back into the page-locked h_minmax behind the kernel
+    // RGBA frames (renderRgba, renderRgbaResized, renderSequenceRgba*): d_frame holds the uploaded BGRA frame, alpha_bleed_kernel writes the BGR frame and the alpha
+    // plane the passes gather from (gather_rgba_kernel), d_minmax receives max(A) and max(255 - A), read back into the page-locked h_minmax behind the kernel.  The
+    // frame step is rgba_frame(); resized it ends with compose_canvas_rgba_kernel and resample_rgba_kernel.
     uint8_t* d_bgr = nullptr; size_t bgr_cap = 0;
     uint8_t* d_alpha = nullptr; size_t alpha_cap = 0;
     unsigned* d_minmax = nullptr; unsigned* h_minmax = nullptr;
     hipEvent_t ev_minmax = nullptr;
-    bool rgba = false;
-    // The RGBA entry points (renderRgba, renderRgbaResized, renderSequenceRgba*): the options of the frames being rendered (null outside such a call).  With it set
-    // run_frame() is rgba_frame(); with `rs` set as well the frame ends with compose_canvas_rgba_kernel and resample_rgba_kernel.
     struct RgbaJob { int bleed = 0; bool skip = false; };
-    const RgbaJob* rgba_job = nullptr;
+    // The kind of frame the running entry point renders: what run_frame(), run_rolling_frame(), the gather of run_passes() and the key of the captured
+    // passes branch on.  The default is a plain BGR frame, not resized.  Set once per entry-point family (renderPart / runSequence through job_resize(),
+    // runSequenceYuv, rgba_begin()); entry() puts the default back on every exit, exceptions included.  `rs`: the tap tables of a resized frame's target, else null.
+    // (`deep` is not part of it: it describes the replayable frame in d_frame / d_out and outlives the call.)
+    struct Job {
+        enum Kind { BGR, YUV, RGBA } kind = BGR;
+        const ResizeTables* rs = nullptr;
+        YuvJob yuv;
+        RgbaJob rgba;
+    };
+    Job job;
+    struct JobScope { Impl* im; ~JobScope() { im->job = Job{}; } };
+    // the sample format in the key of a captured pass: 0 / 1 BGR of 8 / 16 bits, 2 .. 49 YuvJob::key, kRgbaKey
+    int sample_format() const { return job.kind == Job::RGBA ? kRgbaKey : job.kind == Job::YUV ? job.yuv.key : deep ? 1 : 0; }
     std::vector<void*> pinned;
     std::vector<void*> host_allocs;     // allocHost(): page-locked buffers handed to the caller
     std::vector<TileSlot> h_slots;
@@ -370,22 +386,39 @@ struct Img2Img::Impl {
     bool one_part_stale = false;          // the last render() ran in parts: d_slots holds the parts' slot tables
     void one_part_slots() {
         if (!one_part_stale) return;
-        const int steps = cfg.tta ? 8 : 1, B = plan.B, S = plan.B / plan.userB;
-        const int batchCount = (int)std::lround(std::ceil((double)(last_strip.tile_count * steps) / plan.userB));
-        const size_t stepCount = (size_t)((batchCount + S - 1) / S) * B;
-        h_slots.resize(stepCount);
-        for (size_t st = 0; st < stepCount; ++st) {
+        const size_t stepCount = pass_slots(last_strip.tile_count);
+        fill_slots(last_grid, last_strip.first_tile, last_strip.tile_count, 1, 0, stepCount);
+        upload_slots(last_grid, stepCount, stepCount);      // (the slab is already that large: renderPart sizes it for both layouts)
+        hipAssert(hipStreamSynchronize(stream));
+        one_part_stale = false;
+    }
+    // The step schedule of a frame's tiles (img2img_render.cpp:246-267): slot = step index, tile = step / stepsPerTile, aug = step % stepsPerTile, zero pad slots at
+    // the end.  batch_count(): the reference batches of `tiles` tiles (:249); pass_slots(): the slots of the whole network passes those batches round up to.
+    int batch_count(int tiles) const {
+        const int steps = cfg.tta ? 8 : 1;
+        return (int)std::lround(std::ceil((double)(tiles * steps) / plan.userB));
+    }
+    size_t pass_slots(int tiles) const {
+        const int S = plan.B / plan.userB;
+        return (size_t)((batch_count(tiles) + S - 1) / S) * plan.B;
+    }
+    // h_slots[at, at + count): the steps of the tiles [first, first + tiles) of the grid, pad slots behind them.  `valid`: 1, or kSlotColour / kSlotAlpha (RGBA)
+    void fill_slots(const TileGrid& grid, int first, int tiles, int valid, size_t at, size_t count) {
+        const int steps = cfg.tta ? 8 : 1;
+        if (h_slots.size() < at + count) h_slots.resize(at + count);
+        for (size_t st = 0; st < count; ++st) {
             const int ti = (int)(st / steps), aug = (int)(st % steps);
             TileSlot sl{0, 0, aug, 0};
-            if (ti < last_strip.tile_count) { sl.x = last_grid.in[last_strip.first_tile + ti].x; sl.y = last_grid.in[last_strip.first_tile + ti].y; sl.valid = 1; }
-            h_slots[st] = sl;
+            if (ti < tiles) { sl.x = grid.in[first + ti].x; sl.y = grid.in[first + ti].y; sl.valid = valid; }
+            h_slots[at + st] = sl;
         }
-        ensure(d_slots, slots_cap, stepCount * sizeof(TileSlot));
-        hipAssert(hipMemcpy(d_slots, h_slots.data(), stepCount * sizeof(TileSlot), hipMemcpyHostToDevice));
-        upload_live(last_grid, stepCount, stream);
-        hipAssert(hipStreamSynchronize(stream));
-        ensure(d_slab, slab_cap, stepCount * plan.Tout * plan.Tout * 4 * plan.elt);      // (already that large: renderPart sizes the slab for both layouts)
-        one_part_stale = false;
+    }
+    // h_slots[0, count) into d_slots and their dead-skip extents into d_live, both on `stream` (not waited for), and a slab that holds `slab_slots` tiles
+    void upload_slots(const TileGrid& grid, size_t count, size_t slab_slots) {
+        ensure(d_slots, slots_cap, count * sizeof(TileSlot));
+        hipAssert(hipMemcpyAsync(d_slots, h_slots.data(), count * sizeof(TileSlot), hipMemcpyHostToDevice, stream));
+        upload_live(grid, count, stream);
+        ensure(d_slab, slab_cap, slab_slots * plan.Tout * plan.Tout * 4 * plan.elt);
     }
     int last_rows = 0, last_cols = 0, last_batches = 0;
     TileGrid last_grid;
@@ -438,11 +471,11 @@ struct Img2Img::Impl {
         if (s_dn) { (void)hipStreamDestroy(s_dn); s_dn = nullptr; }
         frame2_cap = out2_cap = 0;
         for (ResizeTables& t : rs_tables) for (void* q : {(void*)t.fx, (void*)t.fy, (void*)t.wx, (void*)t.wy}) if (q) (void)hipFree(q);
-        rs_tables.clear(); rs = nullptr;
+        rs_tables.clear(); job = Job{};
         if (d_canvas) { (void)hipFree(d_canvas); d_canvas = nullptr; }
         canvas_cap = 0;
         for (void** q : {(void**)&d_bgr, (void**)&d_alpha, (void**)&d_minmax}) if (*q) { (void)hipFree(*q); *q = nullptr; }
-        bgr_cap = alpha_cap = 0; rgba = false; rgba_job = nullptr;
+        bgr_cap = alpha_cap = 0;
         if (h_minmax) { if (hipHostFree(h_minmax) != hipSuccess) (void)hipGetLastError(); h_minmax = nullptr; }
         if (ev_minmax) { (void)hipEventDestroy(ev_minmax); ev_minmax = nullptr; }
         for (void** p : {(void**)&d_frame, (void**)&d_out, (void**)&d_frame2, (void**)&d_out2, &d_slab, &d_slab2, (void**)&d_slots, (void**)&d_live, (void**)&d_rampx, (void**)&d_rampy, (void**)&d_blob_in, (void**)&d_blob_out})
@@ -947,9 +980,10 @@ struct Img2Img::Impl {
 
     // device part of one frame: gather -> network per batch -> compose.  Frame must already be in d_frame.
     void run_frame(int rows, int cols, const TileGrid& grid, bool report, const StripPlan& sp) {
-        if (rgba_job) { rgba_frame(rows, cols, grid, report, nullptr); return; }                               // an RGBA frame of a sequence (renderSequenceRgba)
+        if (job.kind == Job::RGBA) { rgba_frame(rows, cols, grid, report, nullptr); return; }                  // an RGBA frame of a sequence (renderSequenceRgba)
         run_passes(rows, cols, sp.tile_count, 0, report, 0, true);
-        if (rs) { compose_canvas(rows, cols, grid, stream); if (yuv) resample_yuv(stream); else resample(stream); return; }   // a resized frame (renderResized / renderYuvResized)
+        const bool yuv = job.kind == Job::YUV;
+        if (job.rs) { compose_canvas(rows, cols, grid, stream); if (yuv) resample_yuv(stream); else resample(stream); return; }   // a resized frame (renderResized / renderYuvResized)
         if (yuv) { compose_yuv(rows, cols, grid, stream); return; }                       // a YUV frame (renderYuv)
         compose_rect(rows, cols, grid, sp.x0, sp.x1, 0, 0, sp.first_tile);
     }
@@ -980,7 +1014,8 @@ struct Img2Img::Impl {
         hipAssert(hipEventRecord(ev_g0[which], stream));
         hipStream_t s2 = gstream[0];
         hipAssert(hipStreamWaitEvent(s2, ev_g0[which], 0));
-        if (rs) {   // a resized frame: the canvas compose is the slab's last reader, the resample the writer of d_out; in order on s2, they share one canvas
+        const bool yuv = job.kind == Job::YUV;
+        if (job.rs) {   // a resized frame: the canvas compose is the slab's last reader, the resample the writer of d_out; in order on s2, they share one canvas
             compose_canvas(rows, cols, grid, s2);
             hipAssert(hipEventRecord(ev_cmp[which], s2));
             if (out_free) hipAssert(hipStreamWaitEvent(s2, out_free, 0));
@@ -994,11 +1029,25 @@ struct Img2Img::Impl {
     }
     // after the last frame of a rolling sequence: the first stream waits for the second, so that whatever follows on it sees the sequence done
     void end_rolling() { hipAssert(hipEventRecord(ev_join[0], gstream[0])); hipAssert(hipStreamWaitEvent(stream, ev_join[0], 0)); }
-    // The error exits of renderPart() and renderSequence(): every stream that may still touch the caller's buffers, the slabs or d_out drains before the
-    // function returns false (errors here are ignored, the first one is what gets reported); the next call starts outside a rolling sequence.
+    // The error exit of the frame entry points: every stream that may still touch the caller's buffers, the slabs or d_out drains before the function returns
+    // false - a frame in parts and a sequence copy to and from the caller's buffers on the side streams, and a rolling sequence composes on the second group's
+    // stream (end_rolling() has not run when an exception fires).  Errors here are ignored, the first one is what gets reported; the next call starts outside a
+    // rolling sequence.
     void drain_after_error() {
         rolling = false;
         for (hipStream_t st : {s_up, s_dn, gstream[0], stream}) if (st && hipStreamSynchronize(st) != hipSuccess) (void)hipGetLastError();
+    }
+    // What every frame entry point does around its own work `body` (which returns the call's result): refused with `not_ready` before a successful load (shardFinish: or before a shardCompute); the
+    // engine's device current and the job back at its default on every exit; an exception drains the streams and is logged behind `failed`.
+    template <class Body> bool entry(const char* who, const char* not_ready, const char* failed, const Body& body) try {
+        if (!loaded) { log(Severity::error, not_ready, who, __LINE__); return false; }
+        DeviceGuard guard(device);
+        JobScope job_scope{this};
+        return body();
+    } catch (const std::exception& e) {
+        drain_after_error();
+        log(Severity::error, failed + std::string(e.what()) + ".", who, __LINE__);
+        return false;
     }
 
     // the network passes of `tile_count` tiles (slots d_slots[slots_off ..]); their outputs go to slab slots slab_slot0, slab_slot0 + 1, ...
@@ -1008,8 +1057,8 @@ struct Img2Img::Impl {
         const int B = plan.B, T = plan.T, To = plan.Tout;
         const int steps = cfg.tta ? 8 : 1;
         const int userB = plan.userB, S = B / userB;
-        const int batchCount = (int)std::lround(std::ceil((double)(tile_count * steps) / userB));   // img2img_render.cpp:249
-        const int passCount = (batchCount + S - 1) / S;
+        const int batchCount = batch_count(tile_count);
+        const int passCount = (int)(pass_slots(tile_count) / B);
         const size_t slot_bytes = (size_t)To * To * 4 * plan.elt;
         if (poison && fresh) {
             hipAssert(hipMemsetAsync(arena_base, 0x7E, arena_bytes, stream));
@@ -1043,16 +1092,16 @@ struct Img2Img::Impl {
             }
             auto group_stream = [&](int grp) { return grp ? gstream[grp - 1] : stream; };
             auto gather = [&](const GatherParams& gp, hipStream_t gs) {
-                if (rgba) {                                           // an RGBA frame (renderRgba): the same tiles from the bled BGR frame or the alpha plane
+                if (job.kind == Job::RGBA) {                          // an RGBA frame (renderRgba): the same tiles from the bled BGR frame or the alpha plane
                     GatherRgbaParams rp;
                     rp.bgr = d_bgr; rp.bgr_step = (size_t)cols * 3; rp.alpha = d_alpha; rp.alpha_step = (size_t)cols; rp.rows = rows; rp.cols = cols;
                     rp.out = gp.out; rp.fp32 = gp.fp32; rp.slots = gp.slots; rp.B = gp.B; rp.T = gp.T;
                     hipAssert(launch_gather_rgba(rp, gs));
                     return;
                 }
-                if (!yuv) { hipAssert(launch_gather(gp, gs)); return; }
+                if (job.kind != Job::YUV) { hipAssert(launch_gather(gp, gs)); return; }
                 GatherYuvParams yp;                                   // a YUV frame (renderYuv): the same tiles from its planes
-                yp.src = yuv_layout(d_frame, rows, cols, yuv->in_bits, yuv->in_layout); yp.k = yuv->in;
+                yp.src = yuv_layout(d_frame, rows, cols, job.yuv.in_bits, job.yuv.in_layout); yp.k = job.yuv.in;
                 yp.out = gp.out; yp.fp32 = gp.fp32; yp.slots = gp.slots; yp.B = gp.B; yp.T = gp.T;
                 hipAssert(launch_gather_yuv(yp, gs));
             };
@@ -1090,7 +1139,7 @@ struct Img2Img::Impl {
             if (!graphable) run_eager();
             else {
                 // (an RGBA pass reads d_bgr / d_alpha, never d_frame: its graphs do not depend on which frame buffer of a sequence is current)
-                const GraphKey key{rgba ? (const void*)d_bgr : (const void*)d_frame, d_slots + slots_off + (size_t)bi * B, slab_out, arena_base, rows, cols, live, rgba ? kRgbaKey : yuv ? yuv->key : deep ? 1 : 0};
+                const GraphKey key{job.kind == Job::RGBA ? (const void*)d_bgr : (const void*)d_frame, d_slots + slots_off + (size_t)bi * B, slab_out, arena_base, rows, cols, live, sample_format()};
                 auto replay = [&](const PassGraphs& pg) {
                     if (pg.n == 1) { if (rolling && gstream[0]) join(); hipAssert(hipGraphLaunch(pg.g[0], stream)); return; }   // (a whole-arena pass inside a rolling sequence: the other stream's group first)
                     fork();
@@ -1146,45 +1195,36 @@ struct Img2Img::Impl {
     // compose: output columns [x0, x1) (x1 = 0: to the right edge) and rows [y0, y1) (y1 = 0: to the bottom) from the slab, whose slot 0 holds
     // global tile `first_tile`
     void compose_rect(int rows, int cols, const TileGrid& grid, int x0, int x1, int y0, int y1, long first_tile, hipStream_t on = nullptr) {
-        const int To = plan.Tout;
-        ComposeParams cp;
-        cp.tiles = d_slab; cp.fp32 = plan.elt == 4; cp.dst = d_out; cp.dst_step = (size_t)cols * cfg.scaling * 3 * (deep ? 2 : 1); cp.deep = deep ? 1 : 0;
-        cp.outW = cols * cfg.scaling; cp.outH = rows * cfg.scaling; cp.To = To;
-        cp.nx = grid.nx; cp.ny = grid.ny; cp.stride_x = To - grid.outOvX; cp.stride_y = To - grid.outOvY;
-        const bool overlapping = cfg.overlapX != 0 || cfg.overlapY != 0;                      // :244
-        cp.ovx = overlapping ? ovx : 0; cp.ovy = overlapping ? ovy : 0;
-        cp.ramp_x = d_rampx; cp.ramp_y = d_rampy; cp.tta = cfg.tta ? 1 : 0; cp.tta_bug_compat = cfg.ttaBugCompat ? 1 : 0;
+        ComposeParams cp = compose_base(rows, cols, grid);
+        cp.dst = d_out; cp.dst_step = (size_t)cols * cfg.scaling * 3 * (deep ? 2 : 1); cp.deep = deep ? 1 : 0;
         cp.x0 = x0; cp.x1 = x1; cp.y0 = y0; cp.y1 = y1; cp.first_tile = first_tile;
         stamp_begin(4, 0);
         hipAssert(launch_compose(cp, on ? on : stream));
         stamp_end();
     }
-
-    // resized frames (rs set): the whole canvas of the frame's tiles (one part, slot 0 = tile 0) as fp32 planes into d_canvas, then the resize of
-    // d_canvas into d_out (rs->outW x rs->outH, packed)
-    void compose_canvas(int rows, int cols, const TileGrid& grid, hipStream_t on) {
+    // what every compose launch shares: the slab, the canvas size, the tile grid and its strides, the blend ramps, the TTA flags
+    ComposeParams compose_base(int rows, int cols, const TileGrid& grid) const {
         const int To = plan.Tout;
         ComposeParams cp;
         cp.tiles = d_slab; cp.fp32 = plan.elt == 4;
         cp.outW = cols * cfg.scaling; cp.outH = rows * cfg.scaling; cp.To = To;
         cp.nx = grid.nx; cp.ny = grid.ny; cp.stride_x = To - grid.outOvX; cp.stride_y = To - grid.outOvY;
-        const bool overlapping = cfg.overlapX != 0 || cfg.overlapY != 0;
+        const bool overlapping = cfg.overlapX != 0 || cfg.overlapY != 0;                      // :244
         cp.ovx = overlapping ? ovx : 0; cp.ovy = overlapping ? ovy : 0;
         cp.ramp_x = d_rampx; cp.ramp_y = d_rampy; cp.tta = cfg.tta ? 1 : 0; cp.tta_bug_compat = cfg.ttaBugCompat ? 1 : 0;
-        hipAssert(launch_compose_canvas(cp, d_canvas, on));
+        return cp;
     }
-    // YUV frames (yuv set): the whole canvas of the frame's tiles (one part, slot 0 = tile 0) written as the planes of yuv->out_layout into d_out
+
+    // resized frames (job.rs set): the whole canvas of the frame's tiles (one part, slot 0 = tile 0) as fp32 planes into d_canvas, then the resize of
+    // d_canvas into d_out (rs->outW x rs->outH, packed)
+    void compose_canvas(int rows, int cols, const TileGrid& grid, hipStream_t on) {
+        hipAssert(launch_compose_canvas(compose_base(rows, cols, grid), d_canvas, on));
+    }
+    // YUV frames: the whole canvas of the frame's tiles (one part, slot 0 = tile 0) written as the planes of job.yuv.out_layout into d_out
     void compose_yuv(int rows, int cols, const TileGrid& grid, hipStream_t on) {
-        const int To = plan.Tout;
         ComposeYuvParams yp;
-        ComposeParams& cp = yp.c;
-        cp.tiles = d_slab; cp.fp32 = plan.elt == 4;
-        cp.outW = cols * cfg.scaling; cp.outH = rows * cfg.scaling; cp.To = To;
-        cp.nx = grid.nx; cp.ny = grid.ny; cp.stride_x = To - grid.outOvX; cp.stride_y = To - grid.outOvY;
-        const bool overlapping = cfg.overlapX != 0 || cfg.overlapY != 0;
-        cp.ovx = overlapping ? ovx : 0; cp.ovy = overlapping ? ovy : 0;
-        cp.ramp_x = d_rampx; cp.ramp_y = d_rampy; cp.tta = cfg.tta ? 1 : 0; cp.tta_bug_compat = cfg.ttaBugCompat ? 1 : 0;
-        yp.dst = yuv_layout(d_out, cp.outH, cp.outW, yuv->out_bits, yuv->out_layout); yp.k = yuv->out;
+        yp.c = compose_base(rows, cols, grid);
+        yp.dst = yuv_layout(d_out, yp.c.outH, yp.c.outW, job.yuv.out_bits, job.yuv.out_layout); yp.k = job.yuv.out;
         stamp_begin(4, 0);
         hipAssert(launch_compose_yuv(yp, on));
         stamp_end();
@@ -1212,40 +1252,25 @@ struct Img2Img::Impl {
     }
     // the whole canvas of an RGBA frame as BGRA dwords into d_out: colour tiles from slab slot 0, alpha tiles from slot alpha_slot0 (uniform: none, A = value)
     void compose_rgba(int rows, int cols, const TileGrid& grid, size_t alpha_slot0, bool uniform, unsigned value) {
-        const int To = plan.Tout;
         ComposeRgbaParams rp;
-        ComposeParams& cp = rp.c;
-        cp.tiles = d_slab; cp.fp32 = plan.elt == 4; cp.dst = d_out; cp.dst_step = (size_t)cols * cfg.scaling * 4;
-        cp.outW = cols * cfg.scaling; cp.outH = rows * cfg.scaling; cp.To = To;
-        cp.nx = grid.nx; cp.ny = grid.ny; cp.stride_x = To - grid.outOvX; cp.stride_y = To - grid.outOvY;
-        const bool overlapping = cfg.overlapX != 0 || cfg.overlapY != 0;
-        cp.ovx = overlapping ? ovx : 0; cp.ovy = overlapping ? ovy : 0;
-        cp.ramp_x = d_rampx; cp.ramp_y = d_rampy; cp.tta = cfg.tta ? 1 : 0; cp.tta_bug_compat = cfg.ttaBugCompat ? 1 : 0;
-        rp.alpha_tiles = uniform ? nullptr : (const uint8_t*)d_slab + alpha_slot0 * (size_t)To * To * 4 * plan.elt;
+        rp.c = compose_base(rows, cols, grid);
+        rp.c.dst = d_out; rp.c.dst_step = (size_t)cols * cfg.scaling * 4;
+        rp.alpha_tiles = uniform ? nullptr : (const uint8_t*)d_slab + alpha_slot0 * (size_t)plan.Tout * plan.Tout * 4 * plan.elt;
         rp.alpha_value = value;
         hipAssert(launch_compose_rgba(rp, stream));
     }
-    // a resized RGBA frame (rs set): the whole canvas as four fp32 planes R, G, B, A (uniform: three) into d_canvas, then its resize as BGRA dwords into d_out
+    // a resized RGBA frame (job.rs set): the whole canvas as four fp32 planes R, G, B, A (uniform: three) into d_canvas, then its resize as BGRA dwords into d_out
     void compose_canvas_rgba(int rows, int cols, const TileGrid& grid, size_t alpha_slot0, bool uniform) {
-        const int To = plan.Tout;
         ComposeCanvasRgbaParams rp;
-        ComposeParams& cp = rp.c;
-        cp.tiles = d_slab; cp.fp32 = plan.elt == 4;
-        cp.outW = cols * cfg.scaling; cp.outH = rows * cfg.scaling; cp.To = To;
-        cp.nx = grid.nx; cp.ny = grid.ny; cp.stride_x = To - grid.outOvX; cp.stride_y = To - grid.outOvY;
-        const bool overlapping = cfg.overlapX != 0 || cfg.overlapY != 0;
-        cp.ovx = overlapping ? ovx : 0; cp.ovy = overlapping ? ovy : 0;
-        cp.ramp_x = d_rampx; cp.ramp_y = d_rampy; cp.tta = cfg.tta ? 1 : 0; cp.tta_bug_compat = cfg.ttaBugCompat ? 1 : 0;
-        rp.alpha_tiles = uniform ? nullptr : (const uint8_t*)d_slab + alpha_slot0 * (size_t)To * To * 4 * plan.elt;
+        rp.c = compose_base(rows, cols, grid);
+        rp.alpha_tiles = uniform ? nullptr : (const uint8_t*)d_slab + alpha_slot0 * (size_t)plan.Tout * plan.Tout * 4 * plan.elt;
         rp.canvas = d_canvas;
         hipAssert(launch_compose_canvas_rgba(rp, stream));
     }
     void resample_rgba(bool uniform, unsigned value) {
         ResampleRgbaParams rp;
-        rp.canvas = d_canvas; rp.inW = rs->inW; rp.inH = rs->inH;
-        rp.dst = d_out; rp.dst_step = (size_t)rs->outW * 4;
-        rp.outW = rs->outW; rp.outH = rs->outH;
-        rp.fx = rs->fx; rp.wx = rs->wx; rp.kx = rs->kx; rp.fy = rs->fy; rp.wy = rs->wy; rp.ky = rs->ky; rp.rows_max = rs->rows_max;
+        resample_base(rp);
+        rp.dst = d_out; rp.dst_step = (size_t)rp.outW * 4;
         rp.uniform = uniform ? 1 : 0; rp.alpha_value = value;
         hipAssert(launch_resample_rgba(rp, stream));
     }
@@ -1255,10 +1280,11 @@ struct Img2Img::Impl {
     // pointers and steps, then the bleed radius, then the grid - so a null dst with an out-of-range target reports the target.
     struct RgbaCall { int rows = 0, cols = 0, out_rows = 0, out_cols = 0; bool resized = false; TileGrid grid; };
     std::string rgba_check(const Image* srcs, const Image* dsts, int count, const RgbaOptions& opt, int resizeFilter, RgbaCall& c) const {
-        const int rows = srcs[0].rows, cols = srcs[0].cols, s = cfg.scaling;
+        const int rows = srcs[0].rows, cols = srcs[0].cols;
         for (int i = 0; i < count; ++i) if (srcs[i].depth != 8 || dsts[i].depth != 8) return "RGBA input and output images must be 8-bit.";
         if (rows <= 0 || cols <= 0) return "Input image is empty or has an invalid step.";
-        const int out_rows = resizeFilter >= 0 ? dsts[0].rows : rows * s, out_cols = resizeFilter >= 0 ? dsts[0].cols : cols * s;
+        const Target t = target_size(resizeFilter, dsts[0], rows, cols);
+        const int out_rows = t.rows, out_cols = t.cols;
         if (resizeFilter >= 0) {
             const std::string why = resize_problem(rows, cols, out_rows, out_cols, resizeFilter);
             if (!why.empty()) return why;
@@ -1271,68 +1297,77 @@ struct Img2Img::Impl {
         }
         if (opt.bleed < 0 || opt.bleed > kBleedMaxRadius) return "Alpha bleed radius " + std::to_string(opt.bleed) + " is not in [0, " + std::to_string(kBleedMaxRadius) + "].";
         c.rows = rows; c.cols = cols; c.out_rows = out_rows; c.out_cols = out_cols;
-        c.resized = resizeFilter >= 0 && !(out_rows == rows * s && out_cols == cols * s);   // at the scaled size the call is the plain one
-        c.grid = calculate_tiles(cols, rows, cols * s, rows * s, plan.T, plan.T, plan.Tout, plan.Tout, s, cfg.overlapX, cfg.overlapY);
-        if (c.grid.count <= 0) return "Tile grid is empty.";
-        for (const Rect& r : c.grid.out) if (r.w <= 0 || r.h <= 0) return "Tile grid does not fit the output (scaling does not match the model).";
+        c.resized = t.resized;
+        return frame_grid(rows, cols, c.grid);
+    }
+    // The tile grid of a rows x cols frame into `grid`; returns "" or why the engine cannot render it (img2img_render.cpp:232-240)
+    std::string frame_grid(int rows, int cols, TileGrid& grid) const {
+        const int s = cfg.scaling;
+        grid = calculate_tiles(cols, rows, cols * s, rows * s, plan.T, plan.T, plan.Tout, plan.Tout, s, cfg.overlapX, cfg.overlapY);
+        if (grid.count <= 0) return "Tile grid is empty.";
+        for (const Rect& r : grid.out) if (r.w <= 0 || r.h <= 0) return "Tile grid does not fit the output (scaling does not match the model).";
         return "";
     }
-    // resets what rgba_begin() sets, on every exit of an RGBA entry point (also on exceptions)
-    struct RgbaScope { Impl* im; ~RgbaScope() { im->rgba = false; im->rgba_job = nullptr; im->rs = nullptr; } };
-    // after the frame and output buffers are sized: the frame is marked not replayable, the shared tables are made, `rs` and the four-plane canvas of a resized call
-    void rgba_begin(const RgbaCall& c, const RgbaJob& job, int resizeFilter) {
+    // The output size of a call: with a resize filter the size of the first output image, else the scaled size; at the scaled size a resized call is the plain one
+    struct Target { int rows = 0, cols = 0; bool resized = false; };
+    template <class Img> Target target_size(int resizeFilter, const Img& dst0, int rows, int cols) const {
+        const int s = cfg.scaling;
+        Target t;
+        t.rows = resizeFilter >= 0 ? dst0.rows : rows * s; t.cols = resizeFilter >= 0 ? dst0.cols : cols * s;
+        t.resized = resizeFilter >= 0 && !(t.rows == rows * s && t.cols == cols * s);
+        return t;
+    }
+    // the two frame and the two output buffers of a sequence, and the copy streams that fill and empty them
+    void sequence_buffers(size_t in_bytes, size_t out_bytes) {
+        ensure_copy_streams();
+        ensure(d_frame, frame_cap, in_bytes);   ensure(d_frame2, frame2_cap, in_bytes);
+        ensure(d_out, out_cap, out_bytes);      ensure(d_out2, out2_cap, out_bytes);
+    }
+    // a resized frame: the tap tables of its target into the job and a canvas of `planes` fp32 planes of the scaled size
+    void job_resize(int rows, int cols, int out_rows, int out_cols, int resizeFilter, int planes) {
+        const int s = cfg.scaling;
+        job.rs = resize_tables(cols * s, rows * s, out_cols, out_rows, resizeFilter);
+        ensure_canvas((size_t)rows * s * cols * s * planes * sizeof(float));
+    }
+    // after the frame and output buffers are sized: the frame is marked not replayable, the shared tables are made, the job of the call's frames is set
+    void rgba_begin(const RgbaCall& c, const RgbaOptions& opt, int resizeFilter) {
         deep = false;
         last_rows = last_cols = 0;   // (d_frame / d_out hold BGRA from here on: not replayed by benchResident / residentOutput / profileFrame)
-        rgba_setup(c.rows, c.cols, c.grid, job.skip);
-        if (c.resized) {
-            const int s = cfg.scaling;
-            rs = resize_tables(c.cols * s, c.rows * s, c.out_cols, c.out_rows, resizeFilter);
-            ensure_canvas((size_t)c.rows * s * c.cols * s * 4 * sizeof(float));
-        }
-        rgba_job = &job;
+        rgba_setup(c.rows, c.cols, c.grid, opt.skipUniformAlpha);
+        if (c.resized) job_resize(c.rows, c.cols, c.out_rows, c.out_cols, resizeFilter, 4);
+        job.kind = Job::RGBA; job.rgba = RgbaJob{opt.bleed, opt.skipUniformAlpha};
     }
     // What the frames of an RGBA call share, made once per call (the RGBA counterpart of sequence_slots): the planes the bleed writes, the two words' host side,
     // and the slot table, liveness table and slab of the 2N schedule - slot = step index, tile = step / stepsPerTile over the 2N tiles (colour 0 .. N - 1,
     // alpha N .. 2N - 1), zero pad slots at the end.  A frame whose alpha tiles are skipped runs a prefix of the same table.
     void rgba_setup(int rows, int cols, const TileGrid& grid, bool skip) {
-        const int steps = cfg.tta ? 8 : 1, B = plan.B, S = plan.B / plan.userB, N = grid.count;
-        const int batches = (int)std::lround(std::ceil((double)(2 * N * steps) / plan.userB));   // img2img_render.cpp:249
-        const size_t stepTotal = (size_t)((batches + S - 1) / S) * B;
+        const int steps = cfg.tta ? 8 : 1, N = grid.count;
+        const size_t stepTotal = pass_slots(2 * N), colour = (size_t)N * steps;
         ensure_bleed_planes(rows, cols);
         if (skip) {
             if (!h_minmax) hipAssert(hipHostMalloc((void**)&h_minmax, 2 * sizeof(unsigned), hipHostMallocDefault));
             if (!ev_minmax) hipAssert(hipEventCreateWithFlags(&ev_minmax, hipEventDisableTiming));
         }
-        h_slots.resize(stepTotal);
-        for (size_t st = 0; st < stepTotal; ++st) {
-            const int ti = (int)(st / steps), aug = (int)(st % steps);
-            TileSlot sl{0, 0, aug, 0};
-            if (ti < 2 * N) { sl.x = grid.in[ti % N].x; sl.y = grid.in[ti % N].y; sl.valid = ti < N ? kSlotColour : kSlotAlpha; }
-            h_slots[st] = sl;
-        }
-        ensure(d_slots, slots_cap, stepTotal * sizeof(TileSlot));
-        hipAssert(hipMemcpyAsync(d_slots, h_slots.data(), stepTotal * sizeof(TileSlot), hipMemcpyHostToDevice, stream));
-        upload_live(grid, stepTotal, stream);
-        ensure(d_slab, slab_cap, stepTotal * plan.Tout * plan.Tout * 4 * plan.elt);
+        fill_slots(grid, 0, N, kSlotColour, 0, colour);
+        fill_slots(grid, 0, N, kSlotAlpha, colour, stepTotal - colour);
+        upload_slots(grid, stepTotal, stepTotal);
         one_part_stale = false;
     }
     // The device part of one RGBA frame, on `stream`, with the BGRA frame in d_frame and rgba_setup() done: alpha_bleed_kernel, ONE schedule of the frame's N
-    // colour tiles followed by its N alpha tiles, then compose_rgba_kernel - or, with rs set, compose_canvas_rgba_kernel and resample_rgba_kernel - into d_out.
+    // colour tiles followed by its N alpha tiles, then compose_rgba_kernel - or, with job.rs set, compose_canvas_rgba_kernel and resample_rgba_kernel - into d_out.
     // skip (skipUniformAlpha): the two words come back behind the bleed kernel while the passes that hold colour tiles only - the same in the 2N and the N
     // schedule - are issued; the host waits for them, then issues the rest of whichever schedule the frame takes.  `started`: recorded behind the bleed.
     void rgba_frame(int rows, int cols, const TileGrid& grid, bool report, hipEvent_t started) {
-        const RgbaJob job = *rgba_job;
+        const RgbaJob& opt = job.rgba;
         const int steps = cfg.tta ? 8 : 1, B = plan.B, S = plan.B / plan.userB, N = grid.count;
-        auto batches_of = [&](int tiles) { return (int)std::lround(std::ceil((double)(tiles * steps) / plan.userB)); };
-        bleed_frame(rows, cols, job.bleed);
-        if (job.skip) {
+        bleed_frame(rows, cols, opt.bleed);
+        if (opt.skip) {
             hipAssert(hipMemcpyAsync(h_minmax, d_minmax, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, stream));
             hipAssert(hipEventRecord(ev_minmax, stream));
         }
         if (started) hipAssert(hipEventRecord(started, stream));
-        rgba = true;
         bool uniform = false; unsigned value = 255;
-        if (!job.skip) run_passes(rows, cols, 2 * N, 0, report, 0, true);
+        if (!opt.skip) run_passes(rows, cols, 2 * N, 0, report, 0, true);
         else {
             const int F = N * steps / B;                 // passes of colour tiles only: the same launches whether the alpha tiles follow or not
             const auto t0 = std::chrono::steady_clock::now();
@@ -1340,30 +1375,19 @@ struct Img2Img::Impl {
             hipAssert(hipEventSynchronize(ev_minmax));
             uniform = h_minmax[0] + h_minmax[1] == 255u;      // max(A) + max(255 - A) == 255  <=>  min(A) == max(A)
             value = h_minmax[0];
-            const int tiles = uniform ? N : 2 * N, batchCount = batches_of(tiles);
+            const int tiles = uniform ? N : 2 * N, batchCount = batch_count(tiles);
             const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             if (report) for (int k = 0; k < std::min(F * S, batchCount); ++k) log(k + 1, batchCount, 1000.0 * F * S / std::max(ms, 1e-6));
             run_passes(rows, cols, tiles, 0, report, 0, false, 0, 0, F, -1);
         }
-        if (rs) { compose_canvas_rgba(rows, cols, grid, (size_t)N * steps, uniform); resample_rgba(uniform, value); }
+        if (job.rs) { compose_canvas_rgba(rows, cols, grid, (size_t)N * steps, uniform); resample_rgba(uniform, value); }
         else compose_rgba(rows, cols, grid, (size_t)N * steps, uniform, value);
     }
     // the slot table and the slab of a sequence's frames (renderSequence / renderSequenceYuv): every tile of the frame, in one part
     void sequence_slots(const TileGrid& grid, const StripPlan& sp) {
-        const int steps = cfg.tta ? 8 : 1, B = plan.B, S = plan.B / plan.userB;
-        const int batchCount = (int)std::lround(std::ceil((double)(sp.tile_count * steps) / plan.userB));
-        const int stepCount = ((batchCount + S - 1) / S) * B;
-        h_slots.resize(stepCount);
-        for (int st = 0; st < stepCount; ++st) {
-            int ti = st / steps, aug = st % steps;
-            TileSlot sl{0, 0, aug, 0};
-            if (ti < sp.tile_count) { sl.x = grid.in[ti].x; sl.y = grid.in[ti].y; sl.valid = 1; }
-            h_slots[st] = sl;
-        }
-        ensure(d_slots, slots_cap, (size_t)stepCount * sizeof(TileSlot));
-        hipAssert(hipMemcpyAsync(d_slots, h_slots.data(), (size_t)stepCount * sizeof(TileSlot), hipMemcpyHostToDevice, stream));
-        upload_live(grid, (size_t)stepCount, stream);
-        ensure(d_slab, slab_cap, (size_t)stepCount * plan.Tout * plan.Tout * 4 * plan.elt);
+        const size_t stepCount = pass_slots(sp.tile_count);
+        fill_slots(grid, 0, sp.tile_count, 1, 0, stepCount);
+        upload_slots(grid, stepCount, stepCount);
         hipAssert(hipStreamSynchronize(stream));
     }
     // The frame loop of renderSequence() / renderSequenceYuv(): frame i is uploaded by up(i, device buffer, s_up) into one of two frame buffers, rendered
@@ -1378,7 +1402,7 @@ struct Img2Img::Impl {
         // RGBA frames do not roll: d_bgr, d_alpha and d_minmax are single buffers the bleed writes on the compute stream, and in a rolling sequence the second
         // tile group of frame f would still gather from them while frame f + 1 bleeds into them.  Through run_frame() every pass joins its groups before the
         // next launch on `stream`, so stream order alone keeps the single buffers (and the one slab and canvas) safe.
-        const bool roll = count > 1 && !rgba_job && can_roll(sp.tile_count);
+        const bool roll = count > 1 && job.kind != Job::RGBA && can_roll(sp.tile_count);
         if (roll) ensure(d_slab2, slab2_cap, slab_cap);
         hipAssert(hipStreamSynchronize(stream));
         hipAssert(hipEventRecord(ev0, stream));
@@ -1425,24 +1449,27 @@ struct Img2Img::Impl {
         const YuvPlanes f = yuv_layout(nullptr, rows, cols, bits, layout);
         return f.step[0] * rows + (yuv_planes(layout) - 1) * f.step[1] * yuv_chroma_rows(rows, layout);
     }
+    // what the three resample launches share: the canvas, its size and the target's, and the tap tables of job.rs
+    template <class Params> void resample_base(Params& rp) const {
+        const ResizeTables* const rs = job.rs;
+        rp.canvas = d_canvas; rp.inW = rs->inW; rp.inH = rs->inH;
+        rp.outW = rs->outW; rp.outH = rs->outH;
+        rp.fx = rs->fx; rp.wx = rs->wx; rp.kx = rs->kx; rp.fy = rs->fy; rp.wy = rs->wy; rp.ky = rs->ky; rp.rows_max = rs->rows_max;
+    }
     void resample(hipStream_t on) {
         ResampleParams rp;
-        rp.canvas = d_canvas; rp.inW = rs->inW; rp.inH = rs->inH;
-        rp.dst = d_out; rp.dst_step = (size_t)rs->outW * 3 * (deep ? 2 : 1); rp.deep = deep ? 1 : 0;
-        rp.outW = rs->outW; rp.outH = rs->outH;
-        rp.fx = rs->fx; rp.wx = rs->wx; rp.kx = rs->kx; rp.fy = rs->fy; rp.wy = rs->wy; rp.ky = rs->ky; rp.rows_max = rs->rows_max;
+        resample_base(rp);
+        rp.dst = d_out; rp.dst_step = (size_t)rp.outW * 3 * (deep ? 2 : 1); rp.deep = deep ? 1 : 0;
         hipAssert(launch_resample(rp, on));
     }
-    // a resized YUV frame (rs and yuv set, renderYuvResized): the resize of d_canvas written as the planes of d_out (yuv_layout of the target size)
+    // a resized YUV frame (renderYuvResized): the resize of d_canvas written as the planes of d_out (yuv_layout of the target size)
     void resample_yuv(hipStream_t on) {
         ResampleYuvParams rp;
-        rp.canvas = d_canvas; rp.inW = rs->inW; rp.inH = rs->inH;
-        rp.outW = rs->outW; rp.outH = rs->outH;
-        rp.fx = rs->fx; rp.wx = rs->wx; rp.kx = rs->kx; rp.fy = rs->fy; rp.wy = rs->wy; rp.ky = rs->ky; rp.rows_max = rs->rows_max;
-        rp.dst = yuv_layout(d_out, rs->outH, rs->outW, yuv->out_bits, kYuvI420); rp.k = yuv->out;
+        resample_base(rp);
+        rp.dst = yuv_layout(d_out, rp.outH, rp.outW, job.yuv.out_bits, kYuvI420); rp.k = job.yuv.out;
         hipAssert(launch_resample_yuv(rp, on));
     }
-    // the device tap tables of one (canvas, target, filter) and a canvas that holds the frame; the caller sets rs to the result for the frame
+    // the device tap tables of one (canvas, target, filter): what job_resize() puts into the job for the frame
     const ResizeTables* resize_tables(int inW, int inH, int outW, int outH, int filter) {
         for (const ResizeTables& t : rs_tables) if (t.inW == inW && t.inH == inH && t.outW == outW && t.outH == outH && t.filter == filter) return &t;
         if (rs_tables.size() >= 16) {                                        // sizes that keep changing: start over rather than grow without bound
@@ -1692,16 +1719,15 @@ bool Img2Img::render(const Image& src, Image& dst) { return renderPart(src, dst,
 // render() followed by an antialiased resize of the canvas to dst.rows x dst.cols (between the input size and s times it), on the device: the frame's
 // tiles, compose_canvas_kernel (fp32 canvas), resample_kernel (k_resample.hip), the download of the target size.  At the scaled size it is render().
 bool Img2Img::renderResized(const Image& src, Image& dst, ResizeFilter filter) {
-    return renderPart(src, dst, 0, 1, "renderResized", filter == ResizeFilter::Bilinear ? 1 : 0);
+    return renderPart(src, dst, 0, 1, "renderResized", filter_id(filter));
 }
 
 // One GPU's share of a frame when a single image is spread over several devices: renders and writes only the
 // output columns strip_plan() assigns to `part`; the other columns of dst are left untouched.  part 0 of 1 = render().
 bool Img2Img::renderStrip(const Image& src, Image& dst, int part, int parts) { return renderPart(src, dst, part, parts, "renderStrip"); }
 
-bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, const char* who, int resizeFilter) try {
-    if (!impl->loaded) { W2X_LOG_AS(who, error, "Render called before a successful load."); return false; }
-    DeviceGuard guard(impl->device);
+bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, const char* who, int resizeFilter) {
+    return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
     if (parts <= 0 || part < 0 || part >= parts) { W2X_LOG_AS(who, error, "Invalid strip index."); return false; }
     const RenderConfig& cfg = impl->cfg;
     const Plan& plan = impl->plan;
@@ -1710,7 +1736,7 @@ bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, cons
     const size_t bps = src.depth / 8;                          // bytes per sample
     if (!src.data || rows <= 0 || cols <= 0 || src.step < (size_t)cols * 3 * bps) { W2X_LOG_AS(who, error, "Input image is empty or has an invalid step."); return false; }
     // a resized frame (renderResized): dst is the target size; at the scaled size it is a plain render()
-    const bool resized = resizeFilter >= 0 && !(dst.rows == rows * s && dst.cols == cols * s);
+    const bool resized = impl->target_size(resizeFilter, dst, rows, cols).resized;
     if (resized) {
         const std::string why = impl->resize_problem(src, dst, resizeFilter);
         if (!why.empty()) { W2X_LOG_AS(who, error, why); return false; }
@@ -1723,21 +1749,14 @@ bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, cons
     // img2img_render.cpp:226 upload
     impl->ensure(impl->d_frame, impl->frame_cap, (size_t)rows * cols * 3 * bps);
     impl->ensure(impl->d_out, impl->out_cap, (size_t)dst.rows * dst.cols * 3 * bps);
-    struct ResizeScope { Img2Img::Impl* e; ~ResizeScope() { e->rs = nullptr; } } resize_scope{impl.get()};
-    if (resized) {
-        impl->rs = impl->resize_tables(cols * s, rows * s, dst.cols, dst.rows, resizeFilter);
-        impl->ensure_canvas((size_t)rows * s * cols * s * 3 * sizeof(float));
-    }
+    if (resized) impl->job_resize(rows, cols, dst.rows, dst.cols, resizeFilter, 3);
     impl->deep = bps == 2;
     // img2img_render.cpp:226 upload: below, once the parts are known (a frame that runs in parts uploads the first part's columns first)
-    // :232-240
-    TileGrid grid = calculate_tiles(cols, rows, cols * s, rows * s, plan.T, plan.T, plan.Tout, plan.Tout, s, cfg.overlapX, cfg.overlapY);
-    if (grid.count <= 0) { W2X_LOG_AS(who, error, "Tile grid is empty."); return false; }
-    for (const Rect& r : grid.out) if (r.w <= 0 || r.h <= 0) { W2X_LOG_AS(who, error, "Tile grid does not fit the output (scaling does not match the model)."); return false; }
+    TileGrid grid;
+    if (const std::string why = impl->frame_grid(rows, cols, grid); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
     const StripPlan sp = strip_plan(grid, cols * s, plan.Tout, part, parts);
     if (sp.tile_count == 0) return true;                       // more devices than tile columns: this one has no share
-    // :246-267 step schedule: slot = step index, tile = step / stepsPerTile, aug = step % stepsPerTile, zero pad slots at the end
-    const int steps = cfg.tta ? 8 : 1, B = plan.B, S = plan.B / plan.userB;
+    const int steps = cfg.tta ? 8 : 1;
     // A whole frame (render()) runs as a few PARTS one after the other: a part's tiles, its canvas cells composed and handed to the download
     // stream, then the next part's while those cells travel to the host - the synchronous contract of img2img_render.cpp:226-344 with most of
     // the 100 MB download of a 4K frame off the critical path: only the last part's cells travel after the last kernel (config 3: 9.9 ms per
@@ -1765,10 +1784,10 @@ bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, cons
     size_t slots_off[kMaxParts] = {}; size_t stepTotal = 0; int batch_total = 0;
     for (int k = 0; k < npart; ++k) {
         tiles_of[k] = first_of[k + 1] - first_of[k];
-        batches_of[k] = (int)std::lround(std::ceil((double)(tiles_of[k] * steps) / plan.userB));
+        batches_of[k] = impl->batch_count(tiles_of[k]);
         batches_before[k] = batch_total; batch_total += batches_of[k];
         slots_off[k] = stepTotal;
-        stepTotal += (size_t)((batches_of[k] + S - 1) / S) * B;   // reference batches rounded up to whole network passes
+        stepTotal += impl->pass_slots(tiles_of[k]);   // reference batches rounded up to whole network passes
     }
     // :226 upload.  In parts: the frame columns the first part's tiles read go first, on the compute stream; the rest follows on the upload stream while that
     // part computes (tiles are ordered by column, :43-44, so a part reads a column range; the second part waits for the event)
@@ -1779,24 +1798,10 @@ bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, cons
         if (xm > 0 && xm < cols - 64) x_split = xm;
     }
     hipAssert(hipMemcpy2DAsync(impl->d_frame, (size_t)cols * 3 * bps, src.data, src.step, (size_t)x_split * 3 * bps, rows, hipMemcpyHostToDevice, stream));
-    impl->h_slots.resize(stepTotal);
-    for (int k = 0; k < npart; ++k) {
-        const int t0 = first_of[k];
-        const size_t n = (k + 1 < npart ? slots_off[k + 1] : stepTotal) - slots_off[k];
-        for (size_t st = 0; st < n; ++st) {
-            const int ti = (int)(st / steps), aug = (int)(st % steps);
-            TileSlot sl{0, 0, aug, 0};
-            if (ti < tiles_of[k]) { sl.x = grid.in[sp.first_tile + t0 + ti].x; sl.y = grid.in[sp.first_tile + t0 + ti].y; sl.valid = 1; }
-            impl->h_slots[slots_off[k] + st] = sl;
-        }
-    }
-    impl->ensure(impl->d_slots, impl->slots_cap, stepTotal * sizeof(TileSlot));
-    hipAssert(hipMemcpyAsync(impl->d_slots, impl->h_slots.data(), stepTotal * sizeof(TileSlot), hipMemcpyHostToDevice, stream));
-    impl->upload_live(grid, stepTotal, stream);
+    for (int k = 0; k < npart; ++k) impl->fill_slots(grid, sp.first_tile + first_of[k], tiles_of[k], 1, slots_off[k], impl->pass_slots(tiles_of[k]));
     // the slab holds the frame's tiles in tile order: the last part's passes end at most a pass beyond them (and the frame as ONE part - what
     // benchResident / profileFrame replay - ends at most a pass beyond its tiles: sized for both now, an allocation later would drop the captured passes)
-    const size_t one_part_steps = (size_t)(((int)std::lround(std::ceil((double)(sp.tile_count * steps) / plan.userB)) + S - 1) / S) * B;
-    impl->ensure(impl->d_slab, impl->slab_cap, std::max((size_t)first_of[npart - 1] * steps + (stepTotal - slots_off[npart - 1]), one_part_steps) * plan.Tout * plan.Tout * 4 * plan.elt);
+    impl->upload_slots(grid, stepTotal, std::max((size_t)first_of[npart - 1] * steps + (stepTotal - slots_off[npart - 1]), impl->pass_slots(sp.tile_count)));
 
     hipAssert(hipEventRecord(impl->ev0, stream));
     if (npart == 1) {
@@ -1875,12 +1880,7 @@ bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, cons
     // the second slab of a rolling sequence now (an allocation drops the captured passes: better here, on the frame size's first sight, than inside benchResident / renderSequence)
     if (parts == 1 && impl->slab2_cap < impl->slab_cap && impl->can_roll(sp.tile_count)) impl->ensure(impl->d_slab2, impl->slab2_cap, impl->slab_cap);
     return true;
-} catch (const std::exception& e) {
-    // a frame in parts copies to and from the caller's buffers on the side streams and may have left the second group's stream un-joined: let everything
-    // drain before the caller gets its buffers back (errors here are ignored, the first one is what gets reported)
-    impl->drain_after_error();
-    W2X_LOG_AS(who, error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
-    return false;
+    });
 }
 
 // ONE frame over several engines, every tile computed once (img2img.h; SURVEY 8e second option; the reference is single-device,
@@ -1898,26 +1898,14 @@ struct ShardPeer { const void* slab = nullptr; size_t halo_slots = 0; int device
 // preceding parts' bands; records ev0 and ev_shard on the compute stream (no host synchronisation)
 static void shard_phase1(Img2Img::Impl& e, const Image& src, const TileGrid& grid, const ShardPlan& sp, bool report) {
     const int rows = src.rows, cols = src.cols, s = e.cfg.scaling, steps = e.cfg.tta ? 8 : 1;
-    const size_t slot_bytes = (size_t)e.plan.Tout * e.plan.Tout * 4 * e.plan.elt;
     e.deep = false;
     e.ensure(e.d_frame, e.frame_cap, (size_t)rows * cols * 3);
     e.ensure(e.d_out, e.out_cap, (size_t)rows * s * cols * s * 3);
     hipAssert(hipMemcpy2DAsync(e.d_frame, (size_t)cols * 3, src.data, src.step, (size_t)cols * 3, rows, hipMemcpyHostToDevice, e.stream));
-    const int B = e.plan.B, S = e.plan.B / e.plan.userB;
-    const int batchCount = (int)std::lround(std::ceil((double)(sp.tile_count * steps) / e.plan.userB));
-    const int stepCount = ((batchCount + S - 1) / S) * B;
-    e.h_slots.resize(stepCount);
-    for (int st = 0; st < stepCount; ++st) {
-        const int ti = st / steps, aug = st % steps;
-        TileSlot sl{0, 0, aug, 0};
-        if (ti < sp.tile_count) { sl.x = grid.in[sp.first_tile + ti].x; sl.y = grid.in[sp.first_tile + ti].y; sl.valid = 1; }
-        e.h_slots[st] = sl;
-    }
-    e.ensure(e.d_slots, e.slots_cap, (size_t)stepCount * sizeof(TileSlot));
-    hipAssert(hipMemcpyAsync(e.d_slots, e.h_slots.data(), (size_t)stepCount * sizeof(TileSlot), hipMemcpyHostToDevice, e.stream));
-    e.upload_live(grid, (size_t)stepCount, e.stream);
+    const size_t stepCount = e.pass_slots(sp.tile_count);
+    e.fill_slots(grid, sp.first_tile, sp.tile_count, 1, 0, stepCount);
     e.shard_halo_slots = (size_t)(sp.first_tile - sp.halo_first) * steps;
-    e.ensure(e.d_slab, e.slab_cap, (e.shard_halo_slots + (size_t)stepCount) * slot_bytes);
+    e.upload_slots(grid, stepCount, e.shard_halo_slots + stepCount);
     hipAssert(hipEventRecord(e.ev0, e.stream));
     e.run_passes(rows, cols, sp.tile_count, e.shard_halo_slots, report, 0, true);
     if (!e.ev_shard) hipAssert(hipEventCreateWithFlags(&e.ev_shard, hipEventDisableTiming));
@@ -2009,9 +1997,8 @@ bool Img2Img::renderSharded(Img2Img* const* engines, int count, const Image& src
         const Plan& plan = impl->plan;
         const int rows = src.rows, cols = src.cols, s = cfg.scaling;
         if (const std::string why = shard_frame_problem(*impl, src, &dst); !why.empty()) { W2X_LOG(error, why); return false; }
-        const TileGrid grid = calculate_tiles(cols, rows, cols * s, rows * s, plan.T, plan.T, plan.Tout, plan.Tout, s, cfg.overlapX, cfg.overlapY);
-        if (grid.count <= 0) { W2X_LOG(error, "Tile grid is empty."); return false; }
-        for (const Rect& r : grid.out) if (r.w <= 0 || r.h <= 0) { W2X_LOG(error, "Tile grid does not fit the output (scaling does not match the model)."); return false; }
+        TileGrid grid;
+        if (const std::string why = impl->frame_grid(rows, cols, grid); !why.empty()) { W2X_LOG(error, why); return false; }
         std::vector<ShardPlan> sp(count);
         for (int k = 0; k < count; ++k) sp[k] = shard_plan(grid, cols * s, rows * s, plan.Tout, plan.Tout, k, count);
         {   // every tile must have an owner: shard_plan() hands out nothing when the blend bands are as wide as the tile stride
@@ -2057,42 +2044,43 @@ bool Img2Img::renderSharded(Img2Img* const* engines, int count, const Image& src
 // its slab (shardSlab: a device pointer the caller exports with w2x_ipc_export and its peers open with w2x_ipc_open), and after every rank has done so
 // (a host-side barrier - the handle exchange itself) shardFinish(dst, r, N, slabs) with the opened pointers of the parts in front of it.  No collective on
 // the data path: the seam bands are device-to-device copies out of the neighbours' slabs.
-bool Img2Img::shardCompute(const Image& src, int part, int parts) try {
-    if (!impl->loaded) { W2X_LOG(error, "Render called before a successful load."); return false; }
-    if (parts <= 0 || part < 0 || part >= parts) { W2X_LOG(error, "Invalid part index."); return false; }
-    DeviceGuard guard(impl->device);
-    if (const std::string why = shard_frame_problem(*impl, src, nullptr); !why.empty()) { W2X_LOG(error, why); return false; }
+bool Img2Img::shardCompute(const Image& src, int part, int parts) {
+    const char* who = "shardCompute";
+    return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
+    if (parts <= 0 || part < 0 || part >= parts) { W2X_LOG_AS(who, error, "Invalid part index."); return false; }
+    if (const std::string why = shard_frame_problem(*impl, src, nullptr); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
     const Plan& plan = impl->plan;
     const int rows = src.rows, cols = src.cols, s = impl->cfg.scaling;
-    const TileGrid grid = calculate_tiles(cols, rows, cols * s, rows * s, plan.T, plan.T, plan.Tout, plan.Tout, s, impl->cfg.overlapX, impl->cfg.overlapY);
-    if (grid.count <= 0) { W2X_LOG(error, "Tile grid is empty."); return false; }
+    TileGrid grid;
+    if (const std::string why = impl->frame_grid(rows, cols, grid); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
     const ShardPlan sp = shard_plan(grid, cols * s, rows * s, plan.Tout, plan.Tout, part, parts);
     impl->shard_rows = rows; impl->shard_cols = cols;
     {   // every tile must have an owner (shard_plan() hands out nothing when the blend bands are as wide as the tile stride)
         int owned = 0;
         for (int k = 0; k < parts; ++k) owned += shard_plan(grid, cols * s, rows * s, plan.Tout, plan.Tout, k, parts).tile_count;
-        if (owned != grid.count) { W2X_LOG(error, "the blend bands are wider than the tile stride; use render or renderStrip."); return false; }
+        if (owned != grid.count) { W2X_LOG_AS(who, error, "the blend bands are wider than the tile stride; use render or renderStrip."); return false; }
     }
     if (sp.tile_count == 0) return true;                       // more parts than tiles: this one has no share
     shard_phase1(*impl, src, grid, sp, true);
     hipAssert(hipStreamSynchronize(impl->stream));           // the slab is complete when this returns: what the peers copy from after the barrier
     return true;
-} catch (const std::exception& e) {
-    W2X_LOG(error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
-    return false;
+    });
 }
 
 const void* Img2Img::shardSlab(size_t* bytes) const { if (bytes) *bytes = impl->slab_cap; return impl->d_slab; }
 
-bool Img2Img::shardFinish(Image& dst, int part, int parts, const void* const* slabs, const int* devices) try {
-    if (!impl->loaded || impl->shard_rows <= 0) { W2X_LOG(error, "shardFinish without a shardCompute."); return false; }
-    if (parts <= 0 || part < 0 || part >= parts || !slabs) { W2X_LOG(error, "Invalid part index."); return false; }
-    DeviceGuard guard(impl->device);
+bool Img2Img::shardFinish(Image& dst, int part, int parts, const void* const* slabs, const int* devices) {
+    const char* who = "shardFinish";
+    const char* no_compute = "shardFinish without a shardCompute.";
+    return impl->entry(who, no_compute, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
+    if (impl->shard_rows <= 0) { W2X_LOG_AS(who, error, no_compute); return false; }
+    if (parts <= 0 || part < 0 || part >= parts || !slabs) { W2X_LOG_AS(who, error, "Invalid part index."); return false; }
     const Plan& plan = impl->plan;
     const int rows = impl->shard_rows, cols = impl->shard_cols, s = impl->cfg.scaling, steps = impl->cfg.tta ? 8 : 1;
     Image probe; probe.data = (uint8_t*)1; probe.rows = rows; probe.cols = cols; probe.step = (size_t)cols * 3;
-    if (const std::string why = shard_frame_problem(*impl, probe, &dst); !why.empty()) { W2X_LOG(error, why); return false; }
-    const TileGrid grid = calculate_tiles(cols, rows, cols * s, rows * s, plan.T, plan.T, plan.Tout, plan.Tout, s, impl->cfg.overlapX, impl->cfg.overlapY);
+    if (const std::string why = shard_frame_problem(*impl, probe, &dst); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
+    TileGrid grid;                                             // (the grid shardCompute() accepted)
+    if (const std::string why = impl->frame_grid(rows, cols, grid); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
     std::vector<ShardPlan> sp(parts);
     std::vector<ShardPeer> peers(parts);
     for (int k = 0; k < parts; ++k) {
@@ -2105,10 +2093,7 @@ bool Img2Img::shardFinish(Image& dst, int part, int parts, const void* const* sl
     hipAssert(hipStreamSynchronize(impl->stream));
     hipAssert(hipEventElapsedTime(&impl->last_ms, impl->ev0, impl->ev1));
     return true;
-} catch (const std::exception& e) {
-    if (impl->stream) (void)hipStreamSynchronize(impl->stream);
-    W2X_LOG(error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
-    return false;
+    });
 }
 
 // device memory of another process: export / open / close (hipIpc*); the opened pointer is valid in this process on the current device
@@ -2140,20 +2125,20 @@ bool Img2Img::renderSequence(const Image* srcs, Image* dsts, int count) { return
 // renderResized() over a sequence: every frame resized to dsts[i].rows x dsts[i].cols (one target size), the canvas compose and the resample on the
 // compute side of the rolling pipeline (run_rolling_frame), the copy streams overlapped as in renderSequence().  At the scaled size it is renderSequence().
 bool Img2Img::renderSequenceResized(const Image* srcs, Image* dsts, int count, ResizeFilter filter) {
-    return runSequence(srcs, dsts, count, filter == ResizeFilter::Bilinear ? 1 : 0, "renderSequenceResized");
+    return runSequence(srcs, dsts, count, filter_id(filter), "renderSequenceResized");
 }
 
-bool Img2Img::runSequence(const Image* srcs, Image* dsts, int count, int resizeFilter, const char* who) try {
-    if (!impl->loaded) { W2X_LOG_AS(who, error, "Render called before a successful load."); return false; }
+bool Img2Img::runSequence(const Image* srcs, Image* dsts, int count, int resizeFilter, const char* who) {
+    return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
     if (count <= 0) return true;
-    DeviceGuard guard(impl->device);
     const RenderConfig& cfg = impl->cfg;
     const Plan& plan = impl->plan;
     const int rows = srcs[0].rows, cols = srcs[0].cols, s = cfg.scaling;
     for (int i = 0; i < count; ++i) if (srcs[i].depth != 8 || dsts[i].depth != 8) { W2X_LOG_AS(who, error, std::string(who) + " takes 8-bit frames (16-bit images go through render())."); return false; }
     // a resized sequence (renderSequenceResized): every dst is the target size of dsts[0]; at the scaled size it is a plain sequence
-    const int out_rows = resizeFilter >= 0 ? dsts[0].rows : rows * s, out_cols = resizeFilter >= 0 ? dsts[0].cols : cols * s;
-    const bool resized = resizeFilter >= 0 && !(out_rows == rows * s && out_cols == cols * s);
+    const Impl::Target target = impl->target_size(resizeFilter, dsts[0], rows, cols);
+    const int out_rows = target.rows, out_cols = target.cols;
+    const bool resized = target.resized;
     if (resized) {
         const std::string why = impl->resize_problem(srcs[0], dsts[0], resizeFilter);
         if (!why.empty()) { W2X_LOG_AS(who, error, why); return false; }
@@ -2163,22 +2148,12 @@ bool Img2Img::runSequence(const Image* srcs, Image* dsts, int count, int resizeF
         if (!srcs[i].data || srcs[i].rows != rows || srcs[i].cols != cols || srcs[i].step < (size_t)cols * 3 || rows <= 0 || cols <= 0) { W2X_LOG_AS(who, error, "Input images must be non-empty and of one size."); return false; }
         if (!dsts[i].data || dsts[i].rows != out_rows || dsts[i].cols != out_cols || dsts[i].step < (size_t)out_cols * 3) { W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(out_cols) + "x" + std::to_string(out_rows) + "."); return false; }
     }
-    hipStream_t stream = impl->stream;
-    impl->ensure_copy_streams();
-    const size_t in_bytes = (size_t)rows * cols * 3, out_bytes = (size_t)out_rows * out_cols * 3;
-    impl->ensure(impl->d_frame, impl->frame_cap, in_bytes);   impl->ensure(impl->d_frame2, impl->frame2_cap, in_bytes);
-    impl->ensure(impl->d_out, impl->out_cap, out_bytes);      impl->ensure(impl->d_out2, impl->out2_cap, out_bytes);
-    TileGrid grid = calculate_tiles(cols, rows, cols * s, rows * s, plan.T, plan.T, plan.Tout, plan.Tout, s, cfg.overlapX, cfg.overlapY);
-    if (grid.count <= 0) { W2X_LOG_AS(who, error, "Tile grid is empty."); return false; }
-    for (const Rect& r : grid.out) if (r.w <= 0 || r.h <= 0) { W2X_LOG_AS(who, error, "Tile grid does not fit the output (scaling does not match the model)."); return false; }
+    impl->sequence_buffers((size_t)rows * cols * 3, (size_t)out_rows * out_cols * 3);
+    TileGrid grid;
+    if (const std::string why = impl->frame_grid(rows, cols, grid); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
     const StripPlan sp = strip_plan(grid, cols * s, plan.Tout, 0, 1);
     impl->sequence_slots(grid, sp);
-
-    struct ResizeScope { Img2Img::Impl* e; ~ResizeScope() { e->rs = nullptr; } } resize_scope{impl.get()};
-    if (resized) {
-        impl->rs = impl->resize_tables(cols * s, rows * s, out_cols, out_rows, resizeFilter);
-        impl->ensure_canvas((size_t)rows * s * cols * s * 3 * sizeof(float));
-    }
+    if (resized) impl->job_resize(rows, cols, out_rows, out_cols, resizeFilter, 3);
     const float total_ms = impl->run_sequence(count, rows, cols, grid, sp,
         [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dev, (size_t)cols * 3, srcs[i].data, srcs[i].step, (size_t)cols * 3, rows, hipMemcpyHostToDevice, on)); },
         [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dsts[i].data, dsts[i].step, dev, (size_t)out_cols * 3, (size_t)out_cols * 3, out_rows, hipMemcpyDeviceToHost, on)); });
@@ -2186,12 +2161,7 @@ bool Img2Img::runSequence(const Image* srcs, Image* dsts, int count, int resizeF
     impl->last_rows = rows; impl->last_cols = cols; impl->last_grid = grid; impl->last_strip = sp;
     if (resized) impl->last_rows = impl->last_cols = 0;   // (not replayed by benchResident: renderPart)
     return true;
-} catch (const std::exception& e) {
-    // copies on the side streams may still be reading or writing the caller's buffers, and a rolling sequence composes on the second group's stream
-    // (end_rolling() has not run when an exception fires): let all four drain before the caller gets its buffers back
-    impl->drain_after_error();
-    W2X_LOG_AS(who, error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
-    return false;
+    });
 }
 
 // renderYuv(): the sequence of one frame (run_frame: no rolling)
@@ -2205,11 +2175,11 @@ bool Img2Img::renderSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count,
 // compose_canvas_kernel (fp32 canvas, not clamped), resample_yuv_kernel (k_resample.hip: the resize of renderResized, then clamp, Y per pixel, chroma of
 // the filtered RGB), the download of the target's planes.  At the scaled size it is renderYuv().
 bool Img2Img::renderYuvResized(const YuvImage& src, YuvImage& dst, YuvFormat format, ResizeFilter filter) {
-    return runSequenceYuv(&src, &dst, 1, format, filter == ResizeFilter::Bilinear ? 1 : filter == ResizeFilter::Bicubic ? 0 : 2, "renderYuvResized");
+    return runSequenceYuv(&src, &dst, 1, format, filter_id(filter), "renderYuvResized");
 }
 
 bool Img2Img::renderSequenceYuvResized(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, ResizeFilter filter) {
-    return runSequenceYuv(srcs, dsts, count, format, filter == ResizeFilter::Bilinear ? 1 : filter == ResizeFilter::Bicubic ? 0 : 2, "renderSequenceYuvResized");
+    return runSequenceYuv(srcs, dsts, count, format, filter_id(filter), "renderSequenceYuvResized");
 }
 
 // YUV frames through renderSequence()'s pipeline: per frame one copy per plane up on s_up (three, NV12 two), the passes with gather_yuv_kernel, the compose
@@ -2217,11 +2187,10 @@ bool Img2Img::renderSequenceYuvResized(const YuvImage* srcs, YuvImage* dsts, int
 // pair of layouts (srcs[0].layout, dsts[0].layout: DESIGN 9f) for the sequence; nothing is repacked or converted on the host.
 // resizeFilter >= 0 (renderYuvResized / renderSequenceYuvResized): every dst is the target size of dsts[0], the frame step ends with the canvas compose
 // and resample_yuv_kernel; at the scaled size it is the plain sequence.
-bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, int resizeFilter, const char* who) try {
-    if (!impl->loaded) { W2X_LOG_AS(who, error, "Render called before a successful load."); return false; }
+bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, int resizeFilter, const char* who) {
+    return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
     if (count <= 0) return true;
     if (!srcs || !dsts) { W2X_LOG_AS(who, error, "No frames given."); return false; }
-    DeviceGuard guard(impl->device);
     const RenderConfig& cfg = impl->cfg;
     const Plan& plan = impl->plan;
     const int matrix = (int)format.matrix, range = (int)format.range;
@@ -2236,8 +2205,9 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
         return false;
     }
     if (resizeFilter >= 0 && (in_layout != kYuvI420 || out_layout != kYuvI420)) { W2X_LOG_AS(who, error, "Resized YUV frames must be I420 (yuv420p / yuv420p10le) on both sides."); return false; }
-    const int out_rows = resizeFilter >= 0 ? dsts[0].rows : rows * s, out_cols = resizeFilter >= 0 ? dsts[0].cols : cols * s;
-    const bool resized = resizeFilter >= 0 && !(out_rows == rows * s && out_cols == cols * s);
+    const Impl::Target target = impl->target_size(resizeFilter, dsts[0], rows, cols);
+    const int out_rows = target.rows, out_cols = target.cols;
+    const bool resized = target.resized;
     if (resizeFilter >= 0) {
         const std::string why = impl->resize_problem(rows, cols, out_rows, out_cols, resizeFilter);
         if (!why.empty()) { W2X_LOG_AS(who, error, why); return false; }
@@ -2256,29 +2226,19 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
         if (dsts[i].bits != out_bits) { W2X_LOG_AS(who, error, "Output images must be of one depth."); return false; }
         if (!planes_ok(dsts[i])) { W2X_LOG_AS(who, error, "Output image has a missing plane or an invalid step."); return false; }
     }
-    hipStream_t stream = impl->stream;
-    impl->ensure_copy_streams();
-    const size_t in_bytes = Impl::yuv_bytes(rows, cols, in_bits, in_layout), out_bytes = Impl::yuv_bytes(out_rows, out_cols, out_bits, out_layout);
-    impl->ensure(impl->d_frame, impl->frame_cap, in_bytes);   impl->ensure(impl->d_frame2, impl->frame2_cap, in_bytes);
-    impl->ensure(impl->d_out, impl->out_cap, out_bytes);      impl->ensure(impl->d_out2, impl->out2_cap, out_bytes);
-    TileGrid grid = calculate_tiles(cols, rows, cols * s, rows * s, plan.T, plan.T, plan.Tout, plan.Tout, s, cfg.overlapX, cfg.overlapY);
-    if (grid.count <= 0) { W2X_LOG_AS(who, error, "Tile grid is empty."); return false; }
-    for (const Rect& r : grid.out) if (r.w <= 0 || r.h <= 0) { W2X_LOG_AS(who, error, "Tile grid does not fit the output (scaling does not match the model)."); return false; }
+    impl->sequence_buffers(Impl::yuv_bytes(rows, cols, in_bits, in_layout), Impl::yuv_bytes(out_rows, out_cols, out_bits, out_layout));
+    TileGrid grid;
+    if (const std::string why = impl->frame_grid(rows, cols, grid); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
     const StripPlan sp = strip_plan(grid, cols * s, plan.Tout, 0, 1);
     impl->sequence_slots(grid, sp);
 
-    struct YuvScope { Impl* im; ~YuvScope() { im->yuv = nullptr; } } yuv_scope{impl.get()};   // also on exceptions
-    Impl::YuvJob job;
+    Impl::YuvJob& job = impl->job.yuv;
+    impl->job.kind = Impl::Job::YUV;
     job.in = yuv_coefs(matrix, range, in_bits); job.out = yuv_coefs(matrix, range, out_bits);
     job.in_bits = in_bits; job.out_bits = out_bits; job.in_layout = in_layout; job.out_layout = out_layout;
     job.key = 2 + (in_bits == 10 ? 1 : 0) + 2 * range + 4 * matrix + 12 * in_layout;   // 2 .. 13 per layout: 2 .. 49, below kRgbaKey
-    impl->yuv = &job;
     impl->deep = false;
-    struct ResizeScope { Impl* im; ~ResizeScope() { im->rs = nullptr; } } resize_scope{impl.get()};
-    if (resized) {
-        impl->rs = impl->resize_tables(cols * s, rows * s, out_cols, out_rows, resizeFilter);
-        impl->ensure_canvas((size_t)rows * s * cols * s * 3 * sizeof(float));
-    }
+    if (resized) impl->job_resize(rows, cols, out_rows, out_cols, resizeFilter, 3);
     // the planes of a frame (NV12 two, else three) between the caller's layout and the device's (yuv_layout), on copy stream `on`
     auto copy_planes = [&](const YuvImage& host, uint8_t* dev, int r, int c, bool up, hipStream_t on) {
         const int layout = (int)host.layout;
@@ -2296,10 +2256,7 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
     impl->last_ms = total_ms / count;
     impl->last_rows = impl->last_cols = 0;   // (d_frame / d_out hold planes: not replayed by benchResident / residentOutput / profileFrame)
     return true;
-} catch (const std::exception& e) {
-    impl->drain_after_error();
-    W2X_LOG_AS(who, error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
-    return false;
+    });
 }
 
 // RGBA frames.  One upload (4 bytes per pixel), alpha_bleed_kernel (the BGR frame with the visible colours spread under alpha == 0, the alpha plane, the
@@ -2313,20 +2270,17 @@ bool Img2Img::renderRgba(const Image& src, Image& dst, const RgbaOptions& opt) {
 // not quantised) and resample_rgba_kernel (the resize of renderResized over the four planes, BGRA dwords), the download of the target.  Colour and alpha are resized
 // separately and straight.  At the scaled size it is renderRgba().
 bool Img2Img::renderRgbaResized(const Image& src, Image& dst, const RgbaOptions& opt, ResizeFilter filter) {
-    return renderRgbaFrame(src, dst, opt, filter == ResizeFilter::Bilinear ? 1 : filter == ResizeFilter::Bicubic ? 0 : 2, "renderRgbaResized");
+    return renderRgbaFrame(src, dst, opt, filter_id(filter), "renderRgbaResized");
 }
 
-bool Img2Img::renderRgbaFrame(const Image& src, Image& dst, const RgbaOptions& opt, int resizeFilter, const char* who) try {
-    if (!impl->loaded) { W2X_LOG_AS(who, error, "Render called before a successful load."); return false; }
-    DeviceGuard guard(impl->device);
+bool Img2Img::renderRgbaFrame(const Image& src, Image& dst, const RgbaOptions& opt, int resizeFilter, const char* who) {
+    return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
     Impl::RgbaCall c;
     if (const std::string why = impl->rgba_check(&src, &dst, 1, opt, resizeFilter, c); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
     hipStream_t stream = impl->stream;
-    Impl::RgbaScope rgba_scope{impl.get()};
     impl->ensure(impl->d_frame, impl->frame_cap, (size_t)c.rows * c.cols * 4);
     impl->ensure(impl->d_out, impl->out_cap, (size_t)c.out_rows * c.out_cols * 4);
-    const Impl::RgbaJob job{opt.bleed, opt.skipUniformAlpha};
-    impl->rgba_begin(c, job, resizeFilter);
+    impl->rgba_begin(c, opt, resizeFilter);
     hipAssert(hipMemcpy2DAsync(impl->d_frame, (size_t)c.cols * 4, src.data, src.step, (size_t)c.cols * 4, c.rows, hipMemcpyHostToDevice, stream));
     impl->rgba_frame(c.rows, c.cols, c.grid, true, impl->ev0);
     hipAssert(hipEventRecord(impl->ev1, stream));
@@ -2334,10 +2288,7 @@ bool Img2Img::renderRgbaFrame(const Image& src, Image& dst, const RgbaOptions& o
     hipAssert(hipStreamSynchronize(stream));
     hipAssert(hipEventElapsedTime(&impl->last_ms, impl->ev0, impl->ev1));
     return true;
-} catch (const std::exception& e) {
-    impl->drain_after_error();
-    W2X_LOG_AS(who, error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
-    return false;
+    });
 }
 
 // RGBA frames through renderSequence()'s pipeline: frame i is uploaded at 4 bytes per pixel on s_up into one of two frame buffers, its frame step
@@ -2346,40 +2297,31 @@ bool Img2Img::renderRgbaFrame(const Image& src, Image& dst, const RgbaOptions& o
 bool Img2Img::renderSequenceRgba(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt) { return runSequenceRgba(srcs, dsts, count, opt, -1, "renderSequenceRgba"); }
 
 bool Img2Img::renderSequenceRgbaResized(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt, ResizeFilter filter) {
-    return runSequenceRgba(srcs, dsts, count, opt, filter == ResizeFilter::Bilinear ? 1 : filter == ResizeFilter::Bicubic ? 0 : 2, "renderSequenceRgbaResized");
+    return runSequenceRgba(srcs, dsts, count, opt, filter_id(filter), "renderSequenceRgbaResized");
 }
 
-bool Img2Img::runSequenceRgba(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt, int resizeFilter, const char* who) try {
-    if (!impl->loaded) { W2X_LOG_AS(who, error, "Render called before a successful load."); return false; }
+bool Img2Img::runSequenceRgba(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt, int resizeFilter, const char* who) {
+    return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
     if (count <= 0) return true;
     if (!srcs || !dsts) { W2X_LOG_AS(who, error, "No frames given."); return false; }
-    DeviceGuard guard(impl->device);
     Impl::RgbaCall c;
     if (const std::string why = impl->rgba_check(srcs, dsts, count, opt, resizeFilter, c); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
     const int rows = c.rows, cols = c.cols, out_rows = c.out_rows, out_cols = c.out_cols;
     const StripPlan sp = strip_plan(c.grid, cols * impl->cfg.scaling, impl->plan.Tout, 0, 1);
-    Impl::RgbaScope rgba_scope{impl.get()};
-    impl->ensure_copy_streams();
-    const size_t in_bytes = (size_t)rows * cols * 4, out_bytes = (size_t)out_rows * out_cols * 4;
-    impl->ensure(impl->d_frame, impl->frame_cap, in_bytes);   impl->ensure(impl->d_frame2, impl->frame2_cap, in_bytes);
-    impl->ensure(impl->d_out, impl->out_cap, out_bytes);      impl->ensure(impl->d_out2, impl->out2_cap, out_bytes);
-    const Impl::RgbaJob job{opt.bleed, opt.skipUniformAlpha};
-    impl->rgba_begin(c, job, resizeFilter);
+    impl->sequence_buffers((size_t)rows * cols * 4, (size_t)out_rows * out_cols * 4);
+    impl->rgba_begin(c, opt, resizeFilter);
     const float total_ms = impl->run_sequence(count, rows, cols, c.grid, sp,
         [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dev, (size_t)cols * 4, srcs[i].data, srcs[i].step, (size_t)cols * 4, rows, hipMemcpyHostToDevice, on)); },
         [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dsts[i].data, dsts[i].step, dev, (size_t)out_cols * 4, (size_t)out_cols * 4, out_rows, hipMemcpyDeviceToHost, on)); });
     impl->last_ms = total_ms / count;
     return true;
-} catch (const std::exception& e) {
-    impl->drain_after_error();
-    W2X_LOG_AS(who, error, "Render failed unexpectedly: " + std::string(e.what()) + ".");
-    return false;
+    });
 }
 
-bool Img2Img::alphaBleed(const Image& bgra, Image& bgr, int radius) try {
+bool Img2Img::alphaBleed(const Image& bgra, Image& bgr, int radius) {
     const char* who = "alphaBleed";
-    if (!impl->loaded) { W2X_LOG_AS(who, error, "Alpha bleed called before a successful load."); return false; }
-    DeviceGuard guard(impl->device);
+    return impl->entry(who, "Alpha bleed called before a successful load.", "Alpha bleed failed unexpectedly: ",
+                       [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
     const int rows = bgra.rows, cols = bgra.cols;
     if (bgra.depth != 8 || bgr.depth != 8) { W2X_LOG_AS(who, error, "RGBA input and output images must be 8-bit."); return false; }
     if (!bgra.data || rows <= 0 || cols <= 0 || bgra.step < (size_t)cols * 4) { W2X_LOG_AS(who, error, "Input image is empty or has an invalid step."); return false; }
@@ -2390,10 +2332,7 @@ bool Img2Img::alphaBleed(const Image& bgra, Image& bgr, int radius) try {
     hipAssert(hipMemcpy2DAsync(bgr.data, bgr.step, impl->d_bgr, (size_t)cols * 3, (size_t)cols * 3, rows, hipMemcpyDeviceToHost, impl->stream));
     hipAssert(hipStreamSynchronize(impl->stream));
     return true;
-} catch (const std::exception& e) {
-    impl->drain_after_error();
-    W2X_LOG_AS("alphaBleed", error, "Alpha bleed failed unexpectedly: " + std::string(e.what()) + ".");
-    return false;
+    });
 }
 
 // Page-locked frame buffers for renderSequence(): owned by the engine, freed by freeHost() or with the engine.
