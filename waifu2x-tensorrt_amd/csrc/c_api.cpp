@@ -38,10 +38,63 @@ void w2x_set_progress_callback(w2x_engine* e, w2x_progress_fn fn, void* user) {
     else e->engine.setProgressCallback(nullptr);
 }
 
+// ---- the frame arguments of every render entry, built in one place
+// an interleaved BGR / BGRA frame of the ABI (steps in bytes)
+static w2x::Image image(const void* data, int rows, int cols, size_t step, int depth = 8) {
+    w2x::Image m; m.data = static_cast<uint8_t*>(const_cast<void*>(data)); m.rows = rows; m.cols = cols; m.step = step; m.depth = depth;
+    return m;
+}
+// the destination the caller pre-sized to size * scale (main.cpp:234-235); the scale is the engine's
+static w2x::Image scaled_image(w2x::Img2Img& engine, void* data, int rows, int cols, size_t step, int depth = 8) {
+    const int sc = engine.scaling();
+    return image(data, rows * sc, cols * sc, step, depth);
+}
+struct ImageSequence { std::vector<w2x::Image> src, dst; };
+// the frames of an Image sequence entry: srcs[i] / dsts[i] with the size, step and depth of the two model frames
+static ImageSequence image_sequence(const uint8_t* const* srcs, const w2x::Image& src, uint8_t* const* dsts, const w2x::Image& dst, int count) {
+    ImageSequence q; q.src.assign(count, src); q.dst.assign(count, dst);
+    for (int i = 0; i < count; ++i) { q.src[i].data = const_cast<uint8_t*>(srcs[i]); q.dst[i].data = dsts[i]; }
+    return q;
+}
+static bool sequence_ok(const w2x_engine* e, int count, const void* srcs, const void* dsts) { return e && count >= 0 && (count == 0 || (srcs && dsts)); }
+static w2x::RgbaOptions rgba_options(int bleed, int skip_uniform_alpha) { w2x::RgbaOptions o; o.bleed = bleed; o.skipUniformAlpha = skip_uniform_alpha != 0; return o; }
+static w2x::Precision precision_of(int p) { return p == W2X_PRECISION_FP16 ? w2x::Precision::FP16 : p == W2X_PRECISION_FP32 ? w2x::Precision::FP32 : w2x::Precision::TF32; }
+// s into the caller's buffer of cap bytes, cut to fit, always terminated
+static void copy_out(const std::string& s, char* buf, size_t cap) {
+    if (!buf || !cap) return;
+    const size_t n = s.size() < cap - 1 ? s.size() : cap - 1;
+    memcpy(buf, s.data(), n); buf[n] = 0;
+}
+// the resized renders: the target size is explicit; an unknown filter is refused here, through the engine's message callback
+static bool resize_filter(w2x_engine* e, int filter, const char* who, w2x::ResizeFilter& f) {
+    if (filter == W2X_RESIZE_BICUBIC || filter == W2X_RESIZE_BILINEAR) { f = filter == W2X_RESIZE_BILINEAR ? w2x::ResizeFilter::Bilinear : w2x::ResizeFilter::Bicubic; return true; }
+    if (e->msg) e->msg((int)w2x::Severity::error, (std::string("[") + who + "@0] Unknown resize filter " + std::to_string(filter) + ".").c_str(), e->msg_user);
+    return false;
+}
+// the YUV renders: matrix and range go to the engine as given (it refuses unknown values through the message callback)
+static w2x::YuvImage yuv_image(const void* const* planes, const size_t* steps, int rows, int cols, int bits, int layout) {
+    w2x::YuvImage f;
+    for (int k = 0; k < 3; ++k) { f.planes[k] = planes ? (uint8_t*)const_cast<void*>(planes[k]) : nullptr; f.steps[k] = steps ? steps[k] : 0; }
+    f.rows = rows; f.cols = cols; f.bits = bits; f.layout = (w2x::YuvLayout)layout;   // (the engine refuses unknown layouts like unknown matrices)
+    return f;
+}
+static w2x::YuvFormat yuv_format(int matrix, int range) { w2x::YuvFormat f; f.matrix = (w2x::YuvMatrix)matrix; f.range = (w2x::YuvRange)range; return f; }
+struct YuvSequence { std::vector<w2x::YuvImage> src, dst; };
+// the frames of a YUV sequence entry: frame i's planes at [3i .. 3i + 2], one set of steps for the sequence
+static YuvSequence yuv_sequence(const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits, int src_layout,
+                                void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int dst_layout, int count) {
+    YuvSequence q; q.src.reserve(count); q.dst.reserve(count);
+    for (int i = 0; i < count; ++i) {
+        q.src.push_back(yuv_image(src_planes + 3 * i, src_steps, rows, cols, src_bits, src_layout));
+        q.dst.push_back(yuv_image(dst_planes + 3 * i, dst_steps, dst_rows, dst_cols, dst_bits, dst_layout));
+    }
+    return q;
+}
+
 int w2x_build(w2x_engine* e, const char* onnx_path, const w2x_build_config* c) {
     if (!e || !onnx_path || !c) return 0;
     w2x::BuildConfig b;
-    b.deviceId = c->deviceId; b.precision = c->precision == W2X_PRECISION_FP16 ? w2x::Precision::FP16 : c->precision == W2X_PRECISION_FP32 ? w2x::Precision::FP32 : w2x::Precision::TF32;
+    b.deviceId = c->deviceId; b.precision = precision_of(c->precision);
     b.minBatchSize = c->minBatchSize; b.optBatchSize = c->optBatchSize; b.maxBatchSize = c->maxBatchSize;
     b.minChannels = c->minChannels; b.optChannels = c->optChannels; b.maxChannels = c->maxChannels;
     b.minWidth = c->minWidth; b.optWidth = c->optWidth; b.maxWidth = c->maxWidth;
@@ -52,7 +105,7 @@ int w2x_build(w2x_engine* e, const char* onnx_path, const w2x_build_config* c) {
 int w2x_load(w2x_engine* e, const char* onnx_path, const w2x_render_config* c) {
     if (!e || !onnx_path || !c) return 0;
     w2x::RenderConfig r;
-    r.deviceId = c->deviceId; r.precision = c->precision == W2X_PRECISION_FP16 ? w2x::Precision::FP16 : c->precision == W2X_PRECISION_FP32 ? w2x::Precision::FP32 : w2x::Precision::TF32;
+    r.deviceId = c->deviceId; r.precision = precision_of(c->precision);
     r.batchSize = c->batchSize; r.channels = c->channels; r.height = c->height; r.width = c->width; r.scaling = c->scaling;
     r.overlapX = c->overlapX; r.overlapY = c->overlapY; r.tta = c->tta != 0; r.ttaBugCompat = c->ttaBugCompat != 0;
     return e->engine.load(onnx_path, r) ? 1 : 0;
@@ -60,75 +113,51 @@ int w2x_load(w2x_engine* e, const char* onnx_path, const w2x_render_config* c) {
 
 int w2x_render(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, size_t dst_step) {
     if (!e) return 0;
-    w2x::Image s; s.data = const_cast<uint8_t*>(src); s.rows = rows; s.cols = cols; s.step = src_step;
-    // the caller pre-sizes dst to size*scale (main.cpp:234-235); the scale is the engine's
-    w2x::Image d; d.data = dst; d.step = dst_step;
-    const int sc = e->engine.scaling();
-    d.rows = rows * sc; d.cols = cols * sc;
-    return e->engine.render(s, d) ? 1 : 0;
+    w2x::Image d = scaled_image(e->engine, dst, rows, cols, dst_step);
+    return e->engine.render(image(src, rows, cols, src_step), d) ? 1 : 0;
 }
 
 int w2x_render16(w2x_engine* e, const uint16_t* src, int rows, int cols, size_t src_step, uint16_t* dst, size_t dst_step) {
     if (!e) return 0;
-    w2x::Image s; s.data = reinterpret_cast<uint8_t*>(const_cast<uint16_t*>(src)); s.rows = rows; s.cols = cols; s.step = src_step; s.depth = 16;
-    w2x::Image d; d.data = reinterpret_cast<uint8_t*>(dst); d.step = dst_step; d.depth = 16;
-    const int sc = e->engine.scaling();
-    d.rows = rows * sc; d.cols = cols * sc;
-    return e->engine.render(s, d) ? 1 : 0;
-}
-
-// the resized renders: the target size is explicit; an unknown filter is refused here, through the engine's message callback
-static bool resize_filter(w2x_engine* e, int filter, const char* who, w2x::ResizeFilter& f) {
-    if (filter == W2X_RESIZE_BICUBIC || filter == W2X_RESIZE_BILINEAR) { f = filter == W2X_RESIZE_BILINEAR ? w2x::ResizeFilter::Bilinear : w2x::ResizeFilter::Bicubic; return true; }
-    if (e->msg) e->msg((int)w2x::Severity::error, (std::string("[") + who + "@0] Unknown resize filter " + std::to_string(filter) + ".").c_str(), e->msg_user);
-    return false;
+    w2x::Image d = scaled_image(e->engine, dst, rows, cols, dst_step, 16);
+    return e->engine.render(image(src, rows, cols, src_step, 16), d) ? 1 : 0;
 }
 
 int w2x_render_resized(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, int dst_rows, int dst_cols, size_t dst_step, int filter) {
     w2x::ResizeFilter f;
     if (!e || !resize_filter(e, filter, "w2x_render_resized", f)) return 0;
-    w2x::Image s; s.data = const_cast<uint8_t*>(src); s.rows = rows; s.cols = cols; s.step = src_step;
-    w2x::Image d; d.data = dst; d.rows = dst_rows; d.cols = dst_cols; d.step = dst_step;
-    return e->engine.renderResized(s, d, f) ? 1 : 0;
+    w2x::Image d = image(dst, dst_rows, dst_cols, dst_step);
+    return e->engine.renderResized(image(src, rows, cols, src_step), d, f) ? 1 : 0;
 }
 
 int w2x_render16_resized(w2x_engine* e, const uint16_t* src, int rows, int cols, size_t src_step, uint16_t* dst, int dst_rows, int dst_cols, size_t dst_step, int filter) {
     w2x::ResizeFilter f;
     if (!e || !resize_filter(e, filter, "w2x_render16_resized", f)) return 0;
-    w2x::Image s; s.data = reinterpret_cast<uint8_t*>(const_cast<uint16_t*>(src)); s.rows = rows; s.cols = cols; s.step = src_step; s.depth = 16;
-    w2x::Image d; d.data = reinterpret_cast<uint8_t*>(dst); d.rows = dst_rows; d.cols = dst_cols; d.step = dst_step; d.depth = 16;
-    return e->engine.renderResized(s, d, f) ? 1 : 0;
+    w2x::Image d = image(dst, dst_rows, dst_cols, dst_step, 16);
+    return e->engine.renderResized(image(src, rows, cols, src_step, 16), d, f) ? 1 : 0;
 }
 
 int w2x_render_strip(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, size_t dst_step, int part, int parts) {
     if (!e) return 0;
-    w2x::Image s; s.data = const_cast<uint8_t*>(src); s.rows = rows; s.cols = cols; s.step = src_step;
-    w2x::Image d; d.data = dst; d.step = dst_step;
-    const int sc = e->engine.scaling();
-    d.rows = rows * sc; d.cols = cols * sc;
-    return e->engine.renderStrip(s, d, part, parts) ? 1 : 0;
+    w2x::Image d = scaled_image(e->engine, dst, rows, cols, dst_step);
+    return e->engine.renderStrip(image(src, rows, cols, src_step), d, part, parts) ? 1 : 0;
 }
 
 int w2x_render_sharded(w2x_engine* const* engines, int count, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, size_t dst_step) {
     if (!engines || count <= 0) return 0;
     std::vector<w2x::Img2Img*> es(count);
     for (int k = 0; k < count; ++k) { if (!engines[k]) return 0; es[k] = &engines[k]->engine; }
-    w2x::Image s; s.data = const_cast<uint8_t*>(src); s.rows = rows; s.cols = cols; s.step = src_step;
-    w2x::Image d; d.data = dst; d.step = dst_step;
-    const int sc = es[0]->scaling();
-    d.rows = rows * sc; d.cols = cols * sc;
-    return w2x::Img2Img::renderSharded(es.data(), count, s, d) ? 1 : 0;
+    w2x::Image d = scaled_image(*es[0], dst, rows, cols, dst_step);
+    return w2x::Img2Img::renderSharded(es.data(), count, image(src, rows, cols, src_step), d) ? 1 : 0;
 }
 
 int w2x_shard_compute(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, int part, int parts) {
-    if (!e) return 0;
-    w2x::Image s; s.data = const_cast<uint8_t*>(src); s.rows = rows; s.cols = cols; s.step = src_step;
-    return e->engine.shardCompute(s, part, parts) ? 1 : 0;
+    return e && e->engine.shardCompute(image(src, rows, cols, src_step), part, parts) ? 1 : 0;
 }
 const void* w2x_shard_slab(w2x_engine* e, size_t* bytes) { return e ? e->engine.shardSlab(bytes) : nullptr; }
 int w2x_shard_finish(w2x_engine* e, uint8_t* dst, int rows, int cols, size_t dst_step, int part, int parts, const void* const* slabs, const int* devices) {
     if (!e) return 0;
-    w2x::Image d; d.data = dst; d.rows = rows; d.cols = cols; d.step = dst_step;
+    w2x::Image d = image(dst, rows, cols, dst_step);
     return e->engine.shardFinish(d, part, parts, slabs, devices) ? 1 : 0;
 }
 int w2x_ipc_export(const void* device_ptr, uint8_t* out64) { return out64 && w2x::ipc_export(device_ptr, out64) ? 1 : 0; }
@@ -136,135 +165,82 @@ void* w2x_ipc_open(const uint8_t* handle64, int device) { return handle64 ? w2x:
 void w2x_ipc_close(void* p) { w2x::ipc_close(p); }
 
 int w2x_render_sequence(w2x_engine* e, const uint8_t* const* srcs, int rows, int cols, size_t src_step, uint8_t* const* dsts, size_t dst_step, int count) {
-    if (!e || count < 0 || (count > 0 && (!srcs || !dsts))) return 0;
-    const int sc = e->engine.scaling();
-    std::vector<w2x::Image> s(count), d(count);
-    for (int i = 0; i < count; ++i) {
-        s[i].data = const_cast<uint8_t*>(srcs[i]); s[i].rows = rows; s[i].cols = cols; s[i].step = src_step;
-        d[i].data = dsts[i]; d[i].rows = rows * sc; d[i].cols = cols * sc; d[i].step = dst_step;
-    }
-    return e->engine.renderSequence(s.data(), d.data(), count) ? 1 : 0;
+    if (!sequence_ok(e, count, srcs, dsts)) return 0;
+    ImageSequence q = image_sequence(srcs, image(nullptr, rows, cols, src_step), dsts, scaled_image(e->engine, nullptr, rows, cols, dst_step), count);
+    return e->engine.renderSequence(q.src.data(), q.dst.data(), count) ? 1 : 0;
 }
 int w2x_render_sequence_resized(w2x_engine* e, const uint8_t* const* srcs, int rows, int cols, size_t src_step, uint8_t* const* dsts, int dst_rows, int dst_cols, size_t dst_step,
                                 int count, int filter) {
     w2x::ResizeFilter f;
-    if (!e || count < 0 || (count > 0 && (!srcs || !dsts)) || !resize_filter(e, filter, "w2x_render_sequence_resized", f)) return 0;
-    std::vector<w2x::Image> s(count), d(count);
-    for (int i = 0; i < count; ++i) {
-        s[i].data = const_cast<uint8_t*>(srcs[i]); s[i].rows = rows; s[i].cols = cols; s[i].step = src_step;
-        d[i].data = dsts[i]; d[i].rows = dst_rows; d[i].cols = dst_cols; d[i].step = dst_step;
-    }
-    return e->engine.renderSequenceResized(s.data(), d.data(), count, f) ? 1 : 0;
+    if (!sequence_ok(e, count, srcs, dsts) || !resize_filter(e, filter, "w2x_render_sequence_resized", f)) return 0;
+    ImageSequence q = image_sequence(srcs, image(nullptr, rows, cols, src_step), dsts, image(nullptr, dst_rows, dst_cols, dst_step), count);
+    return e->engine.renderSequenceResized(q.src.data(), q.dst.data(), count, f) ? 1 : 0;
 }
-// the YUV renders: matrix and range go to the engine as given (it refuses unknown values through the message callback)
-static w2x::YuvImage yuv_image(const void* const* planes, const size_t* steps, int rows, int cols, int bits, int layout = W2X_YUV_I420) {
-    w2x::YuvImage f;
-    for (int k = 0; k < 3; ++k) { f.planes[k] = planes ? (uint8_t*)const_cast<void*>(planes[k]) : nullptr; f.steps[k] = steps ? steps[k] : 0; }
-    f.rows = rows; f.cols = cols; f.bits = bits; f.layout = (w2x::YuvLayout)layout;   // (the engine refuses unknown layouts like unknown matrices)
-    return f;
-}
-static w2x::YuvFormat yuv_format(int matrix, int range) { w2x::YuvFormat f; f.matrix = (w2x::YuvMatrix)matrix; f.range = (w2x::YuvRange)range; return f; }
 
 int w2x_render_yuv(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
                    void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int matrix, int range) {
-    if (!e) return 0;
-    const w2x::YuvImage s = yuv_image(src_planes, src_steps, rows, cols, src_bits);
-    w2x::YuvImage d = yuv_image(dst_planes, dst_steps, dst_rows, dst_cols, dst_bits);
-    return e->engine.renderYuv(s, d, yuv_format(matrix, range)) ? 1 : 0;
+    return w2x_render_yuv_layout(e, src_planes, src_steps, rows, cols, src_bits, W2X_YUV_I420, dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, W2X_YUV_I420, matrix, range);
 }
 int w2x_render_sequence_yuv(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
                             void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int count, int matrix, int range) {
-    if (!e || count < 0 || (count > 0 && (!src_planes || !dst_planes))) return 0;
-    std::vector<w2x::YuvImage> s(count), d(count);
-    for (int i = 0; i < count; ++i) {
-        s[i] = yuv_image(src_planes + 3 * i, src_steps, rows, cols, src_bits);
-        d[i] = yuv_image(dst_planes + 3 * i, dst_steps, dst_rows, dst_cols, dst_bits);
-    }
-    return e->engine.renderSequenceYuv(s.data(), d.data(), count, yuv_format(matrix, range)) ? 1 : 0;
+    return w2x_render_sequence_yuv_layout(e, src_planes, src_steps, rows, cols, src_bits, W2X_YUV_I420, dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, W2X_YUV_I420, count,
+                                          matrix, range);
 }
 int w2x_render_yuv_layout(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits, int src_layout,
                           void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int dst_layout, int matrix, int range) {
     if (!e) return 0;
-    const w2x::YuvImage s = yuv_image(src_planes, src_steps, rows, cols, src_bits, src_layout);
     w2x::YuvImage d = yuv_image(dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, dst_layout);
-    return e->engine.renderYuv(s, d, yuv_format(matrix, range)) ? 1 : 0;
+    return e->engine.renderYuv(yuv_image(src_planes, src_steps, rows, cols, src_bits, src_layout), d, yuv_format(matrix, range)) ? 1 : 0;
 }
 int w2x_render_sequence_yuv_layout(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits, int src_layout,
                                    void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int dst_layout, int count, int matrix, int range) {
-    if (!e || count < 0 || (count > 0 && (!src_planes || !dst_planes))) return 0;
-    std::vector<w2x::YuvImage> s(count), d(count);
-    for (int i = 0; i < count; ++i) {
-        s[i] = yuv_image(src_planes + 3 * i, src_steps, rows, cols, src_bits, src_layout);
-        d[i] = yuv_image(dst_planes + 3 * i, dst_steps, dst_rows, dst_cols, dst_bits, dst_layout);
-    }
-    return e->engine.renderSequenceYuv(s.data(), d.data(), count, yuv_format(matrix, range)) ? 1 : 0;
+    if (!sequence_ok(e, count, src_planes, dst_planes)) return 0;
+    YuvSequence q = yuv_sequence(src_planes, src_steps, rows, cols, src_bits, src_layout, dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, dst_layout, count);
+    return e->engine.renderSequenceYuv(q.src.data(), q.dst.data(), count, yuv_format(matrix, range)) ? 1 : 0;
 }
 int w2x_render_yuv_resized(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
                            void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int matrix, int range, int filter) {
     w2x::ResizeFilter f;
     if (!e || !resize_filter(e, filter, "w2x_render_yuv_resized", f)) return 0;
-    const w2x::YuvImage s = yuv_image(src_planes, src_steps, rows, cols, src_bits);
-    w2x::YuvImage d = yuv_image(dst_planes, dst_steps, dst_rows, dst_cols, dst_bits);
-    return e->engine.renderYuvResized(s, d, yuv_format(matrix, range), f) ? 1 : 0;
+    w2x::YuvImage d = yuv_image(dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, W2X_YUV_I420);
+    return e->engine.renderYuvResized(yuv_image(src_planes, src_steps, rows, cols, src_bits, W2X_YUV_I420), d, yuv_format(matrix, range), f) ? 1 : 0;
 }
 int w2x_render_sequence_yuv_resized(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
                                     void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int count, int matrix, int range, int filter) {
     w2x::ResizeFilter f;
-    if (!e || count < 0 || (count > 0 && (!src_planes || !dst_planes)) || !resize_filter(e, filter, "w2x_render_sequence_yuv_resized", f)) return 0;
-    std::vector<w2x::YuvImage> s(count), d(count);
-    for (int i = 0; i < count; ++i) {
-        s[i] = yuv_image(src_planes + 3 * i, src_steps, rows, cols, src_bits);
-        d[i] = yuv_image(dst_planes + 3 * i, dst_steps, dst_rows, dst_cols, dst_bits);
-    }
-    return e->engine.renderSequenceYuvResized(s.data(), d.data(), count, yuv_format(matrix, range), f) ? 1 : 0;
+    if (!sequence_ok(e, count, src_planes, dst_planes) || !resize_filter(e, filter, "w2x_render_sequence_yuv_resized", f)) return 0;
+    YuvSequence q = yuv_sequence(src_planes, src_steps, rows, cols, src_bits, W2X_YUV_I420, dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, W2X_YUV_I420, count);
+    return e->engine.renderSequenceYuvResized(q.src.data(), q.dst.data(), count, yuv_format(matrix, range), f) ? 1 : 0;
 }
 int w2x_render_rgba(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, size_t dst_step, int bleed, int skip_uniform_alpha) {
     if (!e) return 0;
-    w2x::Image s; s.data = const_cast<uint8_t*>(src); s.rows = rows; s.cols = cols; s.step = src_step;
-    w2x::Image d; d.data = dst; d.step = dst_step;
-    const int sc = e->engine.scaling();
-    d.rows = rows * sc; d.cols = cols * sc;
-    w2x::RgbaOptions o; o.bleed = bleed; o.skipUniformAlpha = skip_uniform_alpha != 0;
-    return e->engine.renderRgba(s, d, o) ? 1 : 0;
+    w2x::Image d = scaled_image(e->engine, dst, rows, cols, dst_step);
+    return e->engine.renderRgba(image(src, rows, cols, src_step), d, rgba_options(bleed, skip_uniform_alpha)) ? 1 : 0;
 }
 int w2x_render_rgba_resized(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, int dst_rows, int dst_cols, size_t dst_step, int bleed,
                             int skip_uniform_alpha, int filter) {
     w2x::ResizeFilter f;
     if (!e || !resize_filter(e, filter, "w2x_render_rgba_resized", f)) return 0;
-    w2x::Image s; s.data = const_cast<uint8_t*>(src); s.rows = rows; s.cols = cols; s.step = src_step;
-    w2x::Image d; d.data = dst; d.rows = dst_rows; d.cols = dst_cols; d.step = dst_step;
-    w2x::RgbaOptions o; o.bleed = bleed; o.skipUniformAlpha = skip_uniform_alpha != 0;
-    return e->engine.renderRgbaResized(s, d, o, f) ? 1 : 0;
+    w2x::Image d = image(dst, dst_rows, dst_cols, dst_step);
+    return e->engine.renderRgbaResized(image(src, rows, cols, src_step), d, rgba_options(bleed, skip_uniform_alpha), f) ? 1 : 0;
 }
 int w2x_render_sequence_rgba(w2x_engine* e, const uint8_t* const* srcs, int rows, int cols, size_t src_step, uint8_t* const* dsts, size_t dst_step, int count, int bleed,
                              int skip_uniform_alpha) {
-    if (!e || count < 0 || (count > 0 && (!srcs || !dsts))) return 0;
-    const int sc = e->engine.scaling();
-    std::vector<w2x::Image> s(count), d(count);
-    for (int i = 0; i < count; ++i) {
-        s[i].data = const_cast<uint8_t*>(srcs[i]); s[i].rows = rows; s[i].cols = cols; s[i].step = src_step;
-        d[i].data = dsts[i]; d[i].rows = rows * sc; d[i].cols = cols * sc; d[i].step = dst_step;
-    }
-    w2x::RgbaOptions o; o.bleed = bleed; o.skipUniformAlpha = skip_uniform_alpha != 0;
-    return e->engine.renderSequenceRgba(s.data(), d.data(), count, o) ? 1 : 0;
+    if (!sequence_ok(e, count, srcs, dsts)) return 0;
+    ImageSequence q = image_sequence(srcs, image(nullptr, rows, cols, src_step), dsts, scaled_image(e->engine, nullptr, rows, cols, dst_step), count);
+    return e->engine.renderSequenceRgba(q.src.data(), q.dst.data(), count, rgba_options(bleed, skip_uniform_alpha)) ? 1 : 0;
 }
 int w2x_render_sequence_rgba_resized(w2x_engine* e, const uint8_t* const* srcs, int rows, int cols, size_t src_step, uint8_t* const* dsts, int dst_rows, int dst_cols,
                                      size_t dst_step, int count, int bleed, int skip_uniform_alpha, int filter) {
     w2x::ResizeFilter f;
-    if (!e || count < 0 || (count > 0 && (!srcs || !dsts)) || !resize_filter(e, filter, "w2x_render_sequence_rgba_resized", f)) return 0;
-    std::vector<w2x::Image> s(count), d(count);
-    for (int i = 0; i < count; ++i) {
-        s[i].data = const_cast<uint8_t*>(srcs[i]); s[i].rows = rows; s[i].cols = cols; s[i].step = src_step;
-        d[i].data = dsts[i]; d[i].rows = dst_rows; d[i].cols = dst_cols; d[i].step = dst_step;
-    }
-    w2x::RgbaOptions o; o.bleed = bleed; o.skipUniformAlpha = skip_uniform_alpha != 0;
-    return e->engine.renderSequenceRgbaResized(s.data(), d.data(), count, o, f) ? 1 : 0;
+    if (!sequence_ok(e, count, srcs, dsts) || !resize_filter(e, filter, "w2x_render_sequence_rgba_resized", f)) return 0;
+    ImageSequence q = image_sequence(srcs, image(nullptr, rows, cols, src_step), dsts, image(nullptr, dst_rows, dst_cols, dst_step), count);
+    return e->engine.renderSequenceRgbaResized(q.src.data(), q.dst.data(), count, rgba_options(bleed, skip_uniform_alpha), f) ? 1 : 0;
 }
 int w2x_alpha_bleed_device(w2x_engine* e, const uint8_t* bgra, int rows, int cols, size_t bgra_step, uint8_t* bgr, size_t bgr_step, int radius) {
     if (!e) return 0;
-    w2x::Image s; s.data = const_cast<uint8_t*>(bgra); s.rows = rows; s.cols = cols; s.step = bgra_step;
-    w2x::Image d; d.data = bgr; d.rows = rows; d.cols = cols; d.step = bgr_step;
-    return e->engine.alphaBleed(s, d, radius) ? 1 : 0;
+    w2x::Image d = image(bgr, rows, cols, bgr_step);
+    return e->engine.alphaBleed(image(bgra, rows, cols, bgra_step), d, radius) ? 1 : 0;
 }
 void* w2x_alloc_host(w2x_engine* e, size_t bytes) { return e ? e->engine.allocHost(bytes) : nullptr; }
 void w2x_free_host(w2x_engine* e, void* data) { if (e) e->engine.freeHost(data); }
@@ -312,14 +288,7 @@ int w2x_calculate_tiles(int in_w, int in_h, int out_w, int out_h, int tile_in, i
 }
 
 int w2x_yuv_plane_sizes(int rows, int cols, int bits, int* plane_rows, int* plane_cols, size_t* plane_bytes) {
-    if (rows <= 0 || cols <= 0 || (bits != 8 && bits != 10)) return 0;
-    for (int k = 0; k < 3; ++k) {
-        const int r = k ? (rows + 1) / 2 : rows, c = k ? (cols + 1) / 2 : cols;
-        if (plane_rows) plane_rows[k] = r;
-        if (plane_cols) plane_cols[k] = c;
-        if (plane_bytes) plane_bytes[k] = (size_t)r * c * (bits > 8 ? 2 : 1);
-    }
-    return 1;
+    return w2x_yuv_layout_plane_sizes(rows, cols, bits, W2X_YUV_I420, nullptr, plane_rows, plane_cols, plane_bytes);
 }
 
 int w2x_yuv_layout_plane_sizes(int rows, int cols, int bits, int layout, int* nplanes, int* plane_rows, int* plane_cols, size_t* plane_bytes) {
@@ -369,7 +338,7 @@ int w2x_describe_plan_precision(const char* onnx_path, int batch, int tile, int 
         s = w2x::Plan::deserialize(bytes.data(), bytes.size()).describe();
     }
     catch (const std::exception& e) { s = std::string("ERROR: ") + e.what(); ok = 0; }
-    if (buf && cap) { size_t n = s.size() < cap - 1 ? s.size() : cap - 1; memcpy(buf, s.data(), n); buf[n] = 0; }
+    copy_out(s, buf, cap);
     return ok;
 }
 
@@ -382,7 +351,7 @@ int w2x_validate_engine_file(const char* path, char* buf, size_t cap) {
         f.seekg(0); f.read(bytes.data(), (std::streamsize)bytes.size());
         (void)w2x::Plan::deserialize((const uint8_t*)bytes.data(), bytes.size());
     } catch (const std::exception& e) { s = e.what(); ok = 0; }
-    if (buf && cap) { size_t n = s.size() < cap - 1 ? s.size() : cap - 1; memcpy(buf, s.data(), n); buf[n] = 0; }
+    copy_out(s, buf, cap);
     return ok;
 }
 

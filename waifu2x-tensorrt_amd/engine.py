@@ -36,22 +36,6 @@ def _matrix_id(name) -> int:
     return YUV_MATRICES[name]
 
 
-def yuv_plane_shapes(rows: int, cols: int):
-    """[(rows, cols)] of the Y, U and V planes of a 4:2:0 frame"""
-    return [(rows, cols), ((rows + 1) // 2, (cols + 1) // 2), ((rows + 1) // 2, (cols + 1) // 2)]
-
-
-def _yuv_bits(planes) -> int:
-    """8 for uint8 planes, 10 for uint16 ones; checks the 4:2:0 shapes and packed samples"""
-    y = planes[0]
-    if y.ndim != 2 or y.dtype not in (np.uint8, np.uint16):
-        raise ValueError("YUV planes must be 2-D uint8 (8-bit) or uint16 (10-bit) arrays")
-    for p, shape in zip(planes, yuv_plane_shapes(*y.shape)):
-        if p.dtype != y.dtype or p.shape != shape or p.strides[1] != p.itemsize or p.strides[0] <= 0:
-            raise ValueError(f"YUV 4:2:0 planes of one sample type with packed rows expected: {[q.shape for q in planes]} for {y.shape}")
-    return 8 if y.dtype == np.uint8 else 10
-
-
 YUV_LAYOUTS = {"i420": 0, "i422": 1, "i444": 2, "nv12": 3}   # W2X_YUV_I420 .. _NV12 (include/w2x/c_api.h)
 
 
@@ -69,15 +53,26 @@ def yuv_layout_plane_shapes(rows: int, cols: int, layout: str = "i420"):
     return [(rows, cols), (cr, 2 * cc)] if lid == 3 else [(rows, cols), (cr, cc), (cr, cc)]
 
 
-def _yuv_layout_bits(planes, layout) -> int:
-    """_yuv_bits for a frame of `layout`"""
+def yuv_plane_shapes(rows: int, cols: int):
+    """[(rows, cols)] of the Y, U and V planes of a 4:2:0 frame"""
+    return yuv_layout_plane_shapes(rows, cols, "i420")
+
+
+def _yuv_layout_bits(planes, layout, name=None, count_planes=True) -> int:
+    """8 for uint8 planes, 10 for uint16 ones; checks the shapes of `layout` and packed samples.  name: what the error calls the layout (default: its
+    key); count_planes=False: a frame short of a plane passes here and goes to the library, which refuses it - the 4:2:0-only calls never counted them"""
     y = planes[0]
     if y.ndim != 2 or y.dtype not in (np.uint8, np.uint16):
         raise ValueError("YUV planes must be 2-D uint8 (8-bit) or uint16 (10-bit) arrays")
     shapes = yuv_layout_plane_shapes(*y.shape, layout)
-    if len(planes) != len(shapes) or any(p.dtype != y.dtype or p.shape != shape or p.strides[1] != p.itemsize or p.strides[0] <= 0 for p, shape in zip(planes, shapes)):
-        raise ValueError(f"{layout} planes of one sample type with packed rows expected: {[q.shape for q in planes]} for {y.shape}")
+    if (count_planes and len(planes) != len(shapes)) or any(p.dtype != y.dtype or p.shape != shape or p.strides[1] != p.itemsize or p.strides[0] <= 0 for p, shape in zip(planes, shapes)):
+        raise ValueError(f"{name or layout} planes of one sample type with packed rows expected: {[q.shape for q in planes]} for {y.shape}")
     return 8 if y.dtype == np.uint8 else 10
+
+
+def _yuv_bits(planes) -> int:
+    """_yuv_layout_bits of a 4:2:0 frame"""
+    return _yuv_layout_bits(planes, "i420", "YUV 4:2:0", count_planes=False)
 
 
 def _plane_args(planes):
@@ -90,6 +85,28 @@ def _filter_id(name) -> int:
     if name not in RESIZE_FILTERS:
         raise ValueError(f"filter must be one of {sorted(RESIZE_FILTERS)}, got {name!r}")
     return RESIZE_FILTERS[name]
+
+
+def _frame_ok(a, channels, dtypes, error=None, shape=None, rows_packed=False, empty_ok=False) -> bool:
+    """The check of every packed interleaved frame: `a` is a [rows, cols, channels] array of one of `dtypes` whose pixels are packed (rows may be padded
+    unless rows_packed).  shape: the (rows, cols) it must have; empty_ok: the strides of an empty array are not looked at.  A frame that fails raises
+    ValueError(error) - with error=None False is returned, for the callers that refuse through the message callback."""
+    b = a.itemsize
+    ok = a.dtype in dtypes and a.ndim == 3 and a.shape[2] == channels and (shape is None or a.shape[:2] == tuple(shape)) and (
+        (empty_ok and not a.size) or (a.strides[2] == b and a.strides[1] == channels * b and (not rows_packed or a.strides[0] == a.shape[1] * channels * b)))
+    if not ok and error is not None:
+        raise ValueError(error)
+    return ok
+
+
+def _data(a):
+    """the pointer of an array for the C ABI, NULL for an empty one"""
+    return a.ctypes.data if a.size else None
+
+
+def _pointers(arrays, count=None):
+    """the pointer array of a C entry that reads `count` of them (default: all): fewer arrays leave NULLs, which the library refuses; more raise IndexError"""
+    return (C.c_void_p * (len(arrays) if count is None else count))(*[a.ctypes.data for a in arrays])
 
 
 class Severity(enum.IntEnum):       # logger.h:11-18
@@ -152,6 +169,79 @@ class RenderConfig:                 # defaults of config.h:33-43
 
 _MSG_FN = C.CFUNCTYPE(None, C.c_int, C.c_char_p, C.c_void_p)
 _PROG_FN = C.CFUNCTYPE(None, C.c_int, C.c_int, C.c_double, C.c_void_p)
+
+_I, _Z, _D, _F, _P, _S = C.c_int, C.c_size_t, C.c_double, C.c_float, C.c_void_p, C.c_char_p
+_FRAME = [_P, _P, _I, _I, _Z]                # engine, frame (or array of frames), rows, cols, step
+_YUV = [_P, _P, _I, _I, _I]                  # planes, steps, rows, cols, bits
+_YUV2 = [_P] + _YUV + _YUV                   # engine, source frame, destination frame
+_YUV2L = [_P] + _YUV + [_I] + _YUV + [_I]    # the same with a layout after each frame
+_GRID = [_I] * 7 + [_D, _D]                  # in_w, in_h, out_w, out_h, tile_in, tile_out, scaling, overlap_x, overlap_y
+# Every symbol of include/w2x/c_api.h: name -> (restype, argtypes).  A new entry is one row here (tests/test_host_abi.py compares the keys with the header).
+# restype None: void (the three calls that take a pointer back); _I on the other void functions is ctypes' default, as before.  argtypes None: not declared.
+SYMBOLS = {
+    "w2x_create": (_P, None),
+    "w2x_destroy": (_I, [_P]),
+    "w2x_set_message_callback": (_I, [_P, _MSG_FN, _P]),
+    "w2x_set_progress_callback": (_I, [_P, _PROG_FN, _P]),
+    "w2x_build": (_I, [_P, _S, C.POINTER(_BuildConfig)]),
+    "w2x_load": (_I, [_P, _S, C.POINTER(_RenderConfig)]),
+    "w2x_render": (_I, _FRAME + [_P, _Z]),
+    "w2x_render16": (_I, _FRAME + [_P, _Z]),
+    "w2x_render_resized": (_I, _FRAME + [_P, _I, _I, _Z, _I]),
+    "w2x_render16_resized": (_I, _FRAME + [_P, _I, _I, _Z, _I]),
+    "w2x_render_strip": (_I, _FRAME + [_P, _Z, _I, _I]),
+    "w2x_render_sharded": (_I, [_P, _I, _P, _I, _I, _Z, _P, _Z]),
+    "w2x_shard_plan": (_I, _GRID + [_I, _I, _P]),
+    "w2x_shard_compute": (_I, _FRAME + [_I, _I]),
+    "w2x_shard_slab": (_P, [_P, _P]),
+    "w2x_shard_finish": (_I, [_P, _P, _I, _I, _Z, _I, _I, _P, _P]),
+    "w2x_ipc_export": (_I, [_P, _P]),
+    "w2x_ipc_open": (_P, [_P, _I]),
+    "w2x_ipc_close": (None, [_P]),
+    "w2x_render_sequence": (_I, _FRAME + [_P, _Z, _I]),
+    "w2x_render_sequence_resized": (_I, _FRAME + [_P, _I, _I, _Z, _I, _I]),
+    "w2x_render_yuv": (_I, _YUV2 + [_I, _I]),
+    "w2x_render_sequence_yuv": (_I, _YUV2 + [_I, _I, _I]),
+    "w2x_render_yuv_layout": (_I, _YUV2L + [_I, _I]),
+    "w2x_render_sequence_yuv_layout": (_I, _YUV2L + [_I, _I, _I]),
+    "w2x_render_yuv_resized": (_I, _YUV2 + [_I, _I, _I]),
+    "w2x_render_sequence_yuv_resized": (_I, _YUV2 + [_I, _I, _I, _I]),
+    "w2x_render_rgba": (_I, _FRAME + [_P, _Z, _I, _I]),
+    "w2x_render_rgba_resized": (_I, _FRAME + [_P, _I, _I, _Z, _I, _I, _I]),
+    "w2x_render_sequence_rgba": (_I, _FRAME + [_P, _Z, _I, _I, _I]),
+    "w2x_render_sequence_rgba_resized": (_I, _FRAME + [_P, _I, _I, _Z, _I, _I, _I, _I]),
+    "w2x_alpha_bleed_device": (_I, _FRAME + [_P, _Z, _I]),
+    "w2x_alloc_host": (_P, [_P, _Z]),
+    "w2x_free_host": (None, [_P, _P]),
+    "w2x_pin_host": (_I, [_P, _P, _Z]),
+    "w2x_unpin_host": (None, [_P, _P]),
+    "w2x_strip_plan": (_I, _GRID + [_I, _I, _P]),
+    "w2x_infer": (_I, [_P, _P, _P]),
+    "w2x_output_tile_size": (_I, [_P]),
+    "w2x_plan_flops": (_D, [_P]),
+    "w2x_pass_tiles": (_I, [_P]),
+    "w2x_last_render_ms": (_F, [_P]),
+    "w2x_bench_resident": (_F, [_P, _I]),
+    "w2x_resident_output": (_I, [_P, _P, _Z]),
+    "w2x_profile_frame": (_I, [_P, _P, _I]),
+    "w2x_op_times": (_I, [_P, _P, _I]),
+    "w2x_calculate_tiles": (_I, _GRID + [_P, _P, _I]),
+    "w2x_tile_weights": (_I, [_I, _I, _I, _I, _P]),
+    "w2x_resize_weights": (_I, [_I, _I, _I, _P, _P, _I]),
+    "w2x_yuv_plane_sizes": (_I, [_I, _I, _I, _P, _P, _P]),
+    "w2x_yuv_layout_plane_sizes": (_I, [_I, _I, _I, _I, _P, _P, _P, _P]),
+    "w2x_alpha_bleed": (_I, [_P, _Z, _P, _Z, _I, _I, _I, _P, _Z]),
+    "w2x_describe_plan": (_I, [_S, _I, _I, _S, _Z]),
+    "w2x_describe_plan_precision": (_I, [_S, _I, _I, _I, _S, _Z]),
+    "w2x_write_engine_file": (_I, [_S, _I, _I, _S]),
+    "w2x_validate_engine_file": (_I, [_S, _S, _Z]),
+    "w2x_dead_skip_extents": (_I, [_S] + [_I] * 5 + [_D, _D, _I, _I, _P, _I]),
+    "w2x_device_pci_bus_id": (_I, [_I, _S, _Z]),
+    "w2x_sha256_hex": (_I, [_P, _Z, _S]),
+    "w2x_version": (_S, None),
+    "w2x_debug_set": (_I, [_S, _I]),
+}
+EXPORTED_SYMBOLS = list(SYMBOLS)
 _lib = None
 
 
@@ -164,83 +254,11 @@ def lib():
         raise W2xError(f"{lib_path} is missing - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "or `make -C waifu2x-tensorrt_amd` (there is no CPU fallback)")
     L = C.CDLL(lib_path)
-    vp = C.c_void_p
-    L.w2x_create.restype = vp
-    L.w2x_destroy.argtypes = [vp]
-    L.w2x_set_message_callback.argtypes = [vp, _MSG_FN, vp]
-    L.w2x_set_progress_callback.argtypes = [vp, _PROG_FN, vp]
-    L.w2x_build.argtypes = [vp, C.c_char_p, C.POINTER(_BuildConfig)]; L.w2x_build.restype = C.c_int
-    L.w2x_load.argtypes = [vp, C.c_char_p, C.POINTER(_RenderConfig)]; L.w2x_load.restype = C.c_int
-    L.w2x_render.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t]; L.w2x_render.restype = C.c_int
-    L.w2x_render16.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t]; L.w2x_render16.restype = C.c_int
-    L.w2x_render_resized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, C.c_int, C.c_size_t, C.c_int]; L.w2x_render_resized.restype = C.c_int
-    L.w2x_render16_resized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, C.c_int, C.c_size_t, C.c_int]; L.w2x_render16_resized.restype = C.c_int
-    L.w2x_render_sequence_resized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int]; L.w2x_render_sequence_resized.restype = C.c_int
-    L.w2x_resize_weights.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, C.c_int]; L.w2x_resize_weights.restype = C.c_int
-    L.w2x_render_yuv.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]; L.w2x_render_yuv.restype = C.c_int
-    L.w2x_render_sequence_yuv.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.w2x_render_sequence_yuv.restype = C.c_int
-    L.w2x_render_yuv_resized.argtypes = L.w2x_render_yuv.argtypes + [C.c_int]; L.w2x_render_yuv_resized.restype = C.c_int
-    L.w2x_render_sequence_yuv_resized.argtypes = L.w2x_render_sequence_yuv.argtypes + [C.c_int]; L.w2x_render_sequence_yuv_resized.restype = C.c_int
-    L.w2x_render_rgba.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]; L.w2x_render_rgba.restype = C.c_int
-    L.w2x_render_rgba_resized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int]; L.w2x_render_rgba_resized.restype = C.c_int
-    L.w2x_render_sequence_rgba.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, C.c_int]; L.w2x_render_sequence_rgba.restype = C.c_int
-    L.w2x_render_sequence_rgba_resized.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.w2x_render_sequence_rgba_resized.restype = C.c_int
-    L.w2x_alpha_bleed_device.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int]; L.w2x_alpha_bleed_device.restype = C.c_int
-    L.w2x_alpha_bleed.argtypes = [vp, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int, C.c_int, vp, C.c_size_t]; L.w2x_alpha_bleed.restype = C.c_int
-    L.w2x_yuv_plane_sizes.argtypes = [C.c_int, C.c_int, C.c_int, vp, vp, vp]; L.w2x_yuv_plane_sizes.restype = C.c_int
-    L.w2x_render_yuv_layout.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]; L.w2x_render_yuv_layout.restype = C.c_int
-    L.w2x_render_sequence_yuv_layout.argtypes = [vp, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]
-    L.w2x_render_sequence_yuv_layout.restype = C.c_int
-    L.w2x_yuv_layout_plane_sizes.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp, vp, vp, vp]; L.w2x_yuv_layout_plane_sizes.restype = C.c_int
-    L.w2x_render_strip.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int, C.c_int]; L.w2x_render_strip.restype = C.c_int
-    L.w2x_render_sequence.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t, C.c_int]; L.w2x_render_sequence.restype = C.c_int
-    L.w2x_alloc_host.argtypes = [vp, C.c_size_t]; L.w2x_alloc_host.restype = vp
-    L.w2x_free_host.argtypes = [vp, vp]; L.w2x_free_host.restype = None
-    L.w2x_pin_host.argtypes = [vp, vp, C.c_size_t]; L.w2x_pin_host.restype = C.c_int
-    L.w2x_unpin_host.argtypes = [vp, vp]; L.w2x_unpin_host.restype = None
-    L.w2x_strip_plan.argtypes = [C.c_int] * 7 + [C.c_double, C.c_double, C.c_int, C.c_int, vp]; L.w2x_strip_plan.restype = C.c_int
-    L.w2x_render_sharded.argtypes = [vp, C.c_int, vp, C.c_int, C.c_int, C.c_size_t, vp, C.c_size_t]; L.w2x_render_sharded.restype = C.c_int
-    L.w2x_shard_compute.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int]; L.w2x_shard_compute.restype = C.c_int
-    L.w2x_shard_slab.argtypes = [vp, vp]; L.w2x_shard_slab.restype = vp
-    L.w2x_shard_finish.argtypes = [vp, vp, C.c_int, C.c_int, C.c_size_t, C.c_int, C.c_int, vp, vp]; L.w2x_shard_finish.restype = C.c_int
-    L.w2x_ipc_export.argtypes = [vp, vp]; L.w2x_ipc_export.restype = C.c_int
-    L.w2x_ipc_open.argtypes = [vp, C.c_int]; L.w2x_ipc_open.restype = vp
-    L.w2x_ipc_close.argtypes = [vp]; L.w2x_ipc_close.restype = None
-    L.w2x_shard_plan.argtypes = [C.c_int] * 7 + [C.c_double, C.c_double, C.c_int, C.c_int, vp]; L.w2x_shard_plan.restype = C.c_int
-    L.w2x_infer.argtypes = [vp, vp, vp]; L.w2x_infer.restype = C.c_int
-    L.w2x_output_tile_size.argtypes = [vp]; L.w2x_output_tile_size.restype = C.c_int
-    L.w2x_pass_tiles.argtypes = [vp]; L.w2x_pass_tiles.restype = C.c_int
-    L.w2x_plan_flops.argtypes = [vp]; L.w2x_plan_flops.restype = C.c_double
-    L.w2x_last_render_ms.argtypes = [vp]; L.w2x_last_render_ms.restype = C.c_float
-    L.w2x_bench_resident.argtypes = [vp, C.c_int]; L.w2x_bench_resident.restype = C.c_float
-    L.w2x_resident_output.argtypes = [vp, vp, C.c_size_t]; L.w2x_resident_output.restype = C.c_int
-    L.w2x_profile_frame.argtypes = [vp, vp, C.c_int]; L.w2x_profile_frame.restype = C.c_int
-    L.w2x_op_times.argtypes = [vp, vp, C.c_int]; L.w2x_op_times.restype = C.c_int
-    L.w2x_calculate_tiles.argtypes = [C.c_int] * 7 + [C.c_double, C.c_double, vp, vp, C.c_int]; L.w2x_calculate_tiles.restype = C.c_int
-    L.w2x_tile_weights.argtypes = [C.c_int, C.c_int, C.c_int, C.c_int, vp]; L.w2x_tile_weights.restype = C.c_int
-    L.w2x_describe_plan.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_char_p, C.c_size_t]; L.w2x_describe_plan.restype = C.c_int
-    L.w2x_describe_plan_precision.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_int, C.c_char_p, C.c_size_t]; L.w2x_describe_plan_precision.restype = C.c_int
-    L.w2x_write_engine_file.argtypes = [C.c_char_p, C.c_int, C.c_int, C.c_char_p]; L.w2x_write_engine_file.restype = C.c_int
-    L.w2x_validate_engine_file.argtypes = [C.c_char_p, C.c_char_p, C.c_size_t]; L.w2x_validate_engine_file.restype = C.c_int
-    L.w2x_device_pci_bus_id.argtypes = [C.c_int, C.c_char_p, C.c_size_t]; L.w2x_device_pci_bus_id.restype = C.c_int
-    L.w2x_sha256_hex.argtypes = [vp, C.c_size_t, C.c_char_p]
-    L.w2x_version.restype = C.c_char_p
-    L.w2x_debug_set.argtypes = [C.c_char_p, C.c_int]; L.w2x_debug_set.restype = C.c_int
-    L.w2x_dead_skip_extents.argtypes = [C.c_char_p] + [C.c_int] * 5 + [C.c_double, C.c_double, C.c_int, C.c_int, vp, C.c_int]; L.w2x_dead_skip_extents.restype = C.c_int
+    for name, (restype, argtypes) in SYMBOLS.items():
+        fn = getattr(L, name)
+        fn.restype, fn.argtypes = restype, argtypes
     _lib = L
     return L
-
-
-EXPORTED_SYMBOLS = [
-    "w2x_create", "w2x_destroy", "w2x_set_message_callback", "w2x_set_progress_callback", "w2x_build", "w2x_load",
-    "w2x_render", "w2x_render16", "w2x_infer", "w2x_output_tile_size", "w2x_plan_flops", "w2x_pass_tiles", "w2x_last_render_ms", "w2x_bench_resident", "w2x_resident_output", "w2x_profile_frame", "w2x_op_times",
-    "w2x_render_resized", "w2x_render16_resized", "w2x_render_sequence_resized", "w2x_resize_weights",
-    "w2x_render_yuv", "w2x_render_sequence_yuv", "w2x_yuv_plane_sizes", "w2x_render_yuv_resized", "w2x_render_sequence_yuv_resized",
-    "w2x_render_yuv_layout", "w2x_render_sequence_yuv_layout", "w2x_yuv_layout_plane_sizes",
-    "w2x_render_rgba", "w2x_render_rgba_resized", "w2x_render_sequence_rgba", "w2x_render_sequence_rgba_resized", "w2x_alpha_bleed_device", "w2x_alpha_bleed", "w2x_dead_skip_extents",
-    "w2x_render_strip", "w2x_strip_plan", "w2x_render_sharded", "w2x_shard_plan", "w2x_shard_compute", "w2x_shard_slab", "w2x_shard_finish", "w2x_ipc_export", "w2x_ipc_open", "w2x_ipc_close", "w2x_render_sequence", "w2x_alloc_host", "w2x_free_host", "w2x_pin_host", "w2x_unpin_host", "w2x_calculate_tiles", "w2x_tile_weights", "w2x_describe_plan", "w2x_describe_plan_precision", "w2x_write_engine_file", "w2x_validate_engine_file", "w2x_device_pci_bus_id", "w2x_sha256_hex", "w2x_version", "w2x_debug_set"]
 
 
 class Img2Img:
@@ -251,6 +269,8 @@ class Img2Img:
         self._h = self._L.w2x_create()
         if not self._h:
             raise W2xError("w2x_create failed")
+        self._scaling = self._batch = self._tile = 0     # of the loaded configuration; 0 before a successful load
+        self._host_bufs = {}                             # alloc_host() arrays: address -> pointer to free
         self.messages: list[tuple[int, str]] = []
         self._user_msg = None
         self._user_prog = None
@@ -290,6 +310,54 @@ class Img2Img:
         errs = [m for s, m in self.messages if s <= Severity.error]
         return errs[-1] if errs else ""
 
+    def _refuse(self, who, text):
+        """a refusal of the wrapper's own, worded and sent like the engine's (the C ABI sees pointers and steps only, so some cv::Mat-style checks live here)"""
+        self._on_msg(int(Severity.error), f"[{who}@0] {text}".encode(), None)
+
+    def _finish(self, ok, allocated, fallback):
+        """The return convention of the frame calls.  allocated: the array(s) the wrapper made because the caller gave no destination - returned, or W2xError
+        with the library's last message (else `fallback`); None, when the caller gave the destination: the bool, like the reference."""
+        if allocated is None:
+            return bool(ok)
+        if not ok:
+            raise W2xError(self.last_error() or fallback)
+        return allocated
+
+    def _sequence(self, frames, outs, pinned, alloc, copy, run, fallback, check=None):
+        """The driver of the sequence calls: run(frames, outs) -> ok of the C entry, over destinations `outs` (one per frame).  outs=None: alloc(False) makes
+        each - or, pinned, alloc(True) makes a ring of min(n, 3) page-locked (buffer, destination) pairs: the sequence runs in pieces of the ring's length,
+        each result is copied out with copy(destination) and every buffer is freed, also when a later alloc or a piece fails.  check(destination) raises for one that does not fit.  Returns the outputs; W2xError when run fails."""
+        n, ring = len(frames), []
+        try:
+            if outs is None:
+                if pinned:
+                    for _ in range(min(n, 3)):
+                        ring.append(alloc(True))
+                else:
+                    outs = [alloc(False)[1] for _ in range(n)]
+            for o in ([d for _, d in ring] or outs):
+                if check:
+                    check(o)
+            res = [] if ring else outs
+            for k0 in range(0, n, len(ring) or n):
+                piece = frames[k0:k0 + (len(ring) or n)]
+                dsts = [d for _, d in ring[:len(piece)]] if ring else outs
+                self._finish(run(piece, dsts), dsts, fallback)
+                if ring:
+                    res += [copy(d) for d in dsts]
+            return res
+        finally:
+            for buf, _ in ring:
+                self.free_host(buf)
+
+    def _packed_sequence(self, frames, channels, out_shape, outs, pinned, outs_error, run, fallback):
+        """_sequence for interleaved uint8 frames: every destination a packed out_shape array (page-locked: alloc_host)"""
+        def alloc(host):
+            buf = self.alloc_host(out_shape) if host else np.empty(out_shape, np.uint8)
+            return buf, buf
+        return self._sequence(frames, outs, pinned, alloc, np.copy, run, fallback,
+                              lambda o: _frame_ok(o, channels, (np.uint8,), outs_error, shape=out_shape[:2], rows_packed=True))
+
     def build(self, path: str, config: BuildConfig) -> bool:
         c = _BuildConfig(*[int(getattr(config, f[0])) for f in _BuildConfig._fields_])
         return bool(self._L.w2x_build(self._h, os.fsencode(path), C.byref(c)))
@@ -305,223 +373,131 @@ class Img2Img:
 
     def render(self, src: np.ndarray, dst: np.ndarray | None = None):
         """render(src, dst) -> bool like the reference; render(src) -> dst array or raises."""
-        bps = src.dtype.itemsize                  # uint8 frames, or uint16 ones (extension: w2x_render16)
-        if src.dtype not in (np.uint8, np.uint16) or src.ndim != 3 or src.shape[2] != 3 or src.strides[2] != bps or src.strides[1] != 3 * bps:
-            raise ValueError("src must be a uint8 (or uint16) [rows, cols, 3] BGR array with packed pixels")
-        ret_array = dst is None
-        if dst is None:
-            s = getattr(self, "_scaling", 0)
-            dst = np.empty((src.shape[0] * s, src.shape[1] * s, 3), src.dtype)
-        s = getattr(self, "_scaling", 0)
-        if s and (dst.dtype != src.dtype or dst.shape != (src.shape[0] * s, src.shape[1] * s, 3) or dst.strides[2] != bps or dst.strides[1] != 3 * bps):
-            # the C ABI only sees pointers and steps, so the cv::Mat-style size check lives here
-            self._on_msg(int(Severity.error), f"[render@0] Output image has invalid size: expected {src.shape[1] * s}x{src.shape[0] * s}.".encode(), None)
+        _frame_ok(src, 3, (np.uint8, np.uint16), "src must be a uint8 (or uint16) [rows, cols, 3] BGR array with packed pixels")   # uint16: extension, w2x_render16
+        s = self._scaling
+        out = np.empty((src.shape[0] * s, src.shape[1] * s, 3), src.dtype) if dst is None else None
+        dst = out if dst is None else dst
+        # (an engine that was never loaded has s = 0: a dst of any size goes to the library, which refuses the call)
+        if s and not _frame_ok(dst, 3, (src.dtype,), shape=(src.shape[0] * s, src.shape[1] * s)):
+            self._refuse("render", f"Output image has invalid size: expected {src.shape[1] * s}x{src.shape[0] * s}.")
             return False
-        fn = self._L.w2x_render if bps == 1 else self._L.w2x_render16
-        ok = bool(fn(self._h, src.ctypes.data, src.shape[0], src.shape[1], src.strides[0], dst.ctypes.data, dst.strides[0]))
-        if ret_array:
-            if not ok:
-                raise W2xError(self.last_error() or "render failed")
-            return dst
-        return ok
+        fn = self._L.w2x_render if src.itemsize == 1 else self._L.w2x_render16
+        return self._finish(fn(self._h, src.ctypes.data, src.shape[0], src.shape[1], src.strides[0], dst.ctypes.data, dst.strides[0]), out, "render failed")
+
+    def _rgba_frame(self, bgra, who, raises):
+        """the checks of a BGRA frame; False after the refusal of a deeper frame (the C ABI carries no sample depth), sent with the engine's message"""
+        ok = isinstance(bgra, np.ndarray) and bgra.ndim == 3 and bgra.shape[2] == 4
+        if ok and bgra.dtype != np.uint8:
+            self._refuse(who, "RGBA input and output images must be 8-bit.")
+            if raises:
+                raise W2xError(self.last_error())
+            return False
+        if not ok or not _frame_ok(bgra, 4, (np.uint8,)):
+            raise ValueError("bgra must be a uint8 [rows, cols, 4] BGRA array with packed pixels")
+        return True
 
     def render_rgba(self, bgra: np.ndarray, *, bleed: int = 0, skip_uniform_alpha: bool = False, dst: np.ndarray | None = None):
         """render() on a uint8 [rows, cols, 4] BGRA frame in one call (w2x_render_rgba): the colours of the pixels with alpha > 0 are spread `bleed` pixels
         (0..16) under the transparent ones, colour and alpha tiles share one schedule; skip_uniform_alpha: a frame whose alpha plane is one value keeps it
         and runs no alpha tiles.  Rows may be padded (strides[0] >= cols * 4).  With dst=None returns the [rows * s, cols * s, 4] array or raises; with dst
         returns a bool."""
-        ret_array = dst is None
-        s = getattr(self, "_scaling", 0)
-        ok = isinstance(bgra, np.ndarray) and bgra.ndim == 3 and bgra.shape[2] == 4
-        if ok and bgra.dtype != np.uint8:
-            # the C ABI carries no sample depth: deeper frames are refused here, with the engine's message
-            self._on_msg(int(Severity.error), b"[renderRgba@0] RGBA input and output images must be 8-bit.", None)
-            if ret_array:
-                raise W2xError(self.last_error())
+        if not self._rgba_frame(bgra, "renderRgba", dst is None):
             return False
-        if not ok or bgra.strides[2] != 1 or bgra.strides[1] != 4:
-            raise ValueError("bgra must be a uint8 [rows, cols, 4] BGRA array with packed pixels")
-        if dst is None:
-            dst = np.empty((bgra.shape[0] * s, bgra.shape[1] * s, 4), np.uint8)
-        if s and (dst.dtype != np.uint8 or dst.shape != (bgra.shape[0] * s, bgra.shape[1] * s, 4) or dst.strides[2] != 1 or dst.strides[1] != 4):
-            # the C ABI only sees pointers and steps, so the cv::Mat-style size check lives here
-            self._on_msg(int(Severity.error), f"[renderRgba@0] Output image has invalid size: expected {bgra.shape[1] * s}x{bgra.shape[0] * s}.".encode(), None)
+        s = self._scaling
+        out = np.empty((bgra.shape[0] * s, bgra.shape[1] * s, 4), np.uint8) if dst is None else None
+        dst = out if dst is None else dst
+        if s and not _frame_ok(dst, 4, (np.uint8,), shape=(bgra.shape[0] * s, bgra.shape[1] * s)):      # (never loaded: as in render())
+            self._refuse("renderRgba", f"Output image has invalid size: expected {bgra.shape[1] * s}x{bgra.shape[0] * s}.")
             return False
-        ok = bool(self._L.w2x_render_rgba(self._h, bgra.ctypes.data if bgra.size else None, bgra.shape[0], bgra.shape[1], bgra.strides[0],
-                                          dst.ctypes.data if dst.size else None, dst.strides[0], int(bleed), 1 if skip_uniform_alpha else 0))
-        if ret_array:
-            if not ok:
-                raise W2xError(self.last_error() or "render_rgba failed")
-            return dst
-        return ok
+        return self._finish(self._L.w2x_render_rgba(self._h, _data(bgra), bgra.shape[0], bgra.shape[1], bgra.strides[0], _data(dst), dst.strides[0],
+                                                    int(bleed), 1 if skip_uniform_alpha else 0), out, "render_rgba failed")
 
     def render_rgba_resized(self, bgra: np.ndarray, size, *, bleed: int = 0, skip_uniform_alpha: bool = False, filter: str = "bicubic", dst: np.ndarray | None = None):
         """render_rgba() with the output resized on the device to size = (rows, cols), each in [input dim, input dim * scaling] (w2x_render_rgba_resized):
         colour and alpha are resized separately and straight, with the filters of render_resized().  With dst=None returns the [rows, cols, 4] array or
         raises; with dst returns a bool."""
-        ret_array = dst is None
-        ok = isinstance(bgra, np.ndarray) and bgra.ndim == 3 and bgra.shape[2] == 4
-        if ok and bgra.dtype != np.uint8:
-            # the C ABI carries no sample depth: deeper frames are refused here, with the engine's message
-            self._on_msg(int(Severity.error), b"[renderRgbaResized@0] RGBA input and output images must be 8-bit.", None)
-            if ret_array:
-                raise W2xError(self.last_error())
+        if not self._rgba_frame(bgra, "renderRgbaResized", dst is None):
             return False
-        if not ok or bgra.strides[2] != 1 or bgra.strides[1] != 4:
-            raise ValueError("bgra must be a uint8 [rows, cols, 4] BGRA array with packed pixels")
         rows, cols = int(size[0]), int(size[1])
         fid = _filter_id(filter)
-        if dst is None:
-            dst = np.empty((max(rows, 0), max(cols, 0), 4), np.uint8)
-        if dst.dtype != np.uint8 or dst.shape != (rows, cols, 4) or (dst.size and (dst.strides[2] != 1 or dst.strides[1] != 4)):
-            raise ValueError("dst must be a uint8 [rows, cols, 4] array of the target size with packed pixels")   # (an empty target: refused by the library)
-        ok = bool(self._L.w2x_render_rgba_resized(self._h, bgra.ctypes.data if bgra.size else None, bgra.shape[0], bgra.shape[1], bgra.strides[0],
-                                                  dst.ctypes.data if dst.size else None, rows, cols, dst.strides[0], int(bleed), 1 if skip_uniform_alpha else 0, fid))
-        if ret_array:
-            if not ok:
-                raise W2xError(self.last_error() or "render_rgba_resized failed")
-            return dst
-        return ok
+        out = np.empty((max(rows, 0), max(cols, 0), 4), np.uint8) if dst is None else None
+        dst = out if dst is None else dst
+        # (an empty target: refused by the library; a wrong dst raises here, where render_rgba() returns False)
+        _frame_ok(dst, 4, (np.uint8,), "dst must be a uint8 [rows, cols, 4] array of the target size with packed pixels", shape=(rows, cols), empty_ok=True)
+        return self._finish(self._L.w2x_render_rgba_resized(self._h, _data(bgra), bgra.shape[0], bgra.shape[1], bgra.strides[0], _data(dst), rows, cols, dst.strides[0],
+                                                            int(bleed), 1 if skip_uniform_alpha else 0, fid), out, "render_rgba_resized failed")
 
     def render_sequence_rgba(self, frames, *, size=None, bleed: int = 0, skip_uniform_alpha: bool = False, filter: str = "bicubic", outs=None, pinned: bool = False):
         """Equally sized uint8 [rows, cols, 4] BGRA frames with upload / compute / download overlapped (w2x_render_sequence_rgba); with size = (rows, cols) every
         frame is resized like render_rgba_resized() (w2x_render_sequence_rgba_resized).  Output i is the bytes of the single-frame call on frame i.
         outs / pinned as in render_sequence()."""
-        s = getattr(self, "_scaling", 0)
-        n = len(frames)
-        if n == 0:
+        if len(frames) == 0:
             return []
+        s = self._scaling
         r, c = frames[0].shape[:2]
         for f in frames:
-            if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] != 4 or f.strides != (f.shape[1] * 4, 4, 1):
-                raise ValueError("frames must be packed uint8 [rows, cols, 4] arrays")
+            _frame_ok(f, 4, (np.uint8,), "frames must be packed uint8 [rows, cols, 4] arrays", rows_packed=True)
             if f.shape != (r, c, 4):
-                # the C ABI carries one size for the sequence: frames that differ are refused here, with the engine's message
-                self._on_msg(int(Severity.error), b"[renderSequenceRgba@0] Input images must be of one size.", None)
+                # the C ABI carries one size for the sequence: frames that differ are refused here, with the engine's message (the BGR sequences raise ValueError)
+                self._refuse("renderSequenceRgba", "Input images must be of one size.")
                 raise W2xError(self.last_error())
         rows, cols = (r * s, c * s) if size is None else (int(size[0]), int(size[1]))
         fid = _filter_id(filter)
-        own = []
-        if outs is None:
-            if pinned:
-                own = [self.alloc_host((rows, cols, 4)) for _ in range(min(n, 3))]
-            else:
-                outs = [np.empty((rows, cols, 4), np.uint8) for _ in range(n)]
-        for o in (own or outs):
-            if o.dtype != np.uint8 or o.shape != (rows, cols, 4) or o.strides != (cols * 4, 4, 1):
-                raise ValueError("outs must be packed uint8 [rows, cols, 4] arrays of the output size")
         flags = (int(bleed), 1 if skip_uniform_alpha else 0)
 
         def run(fs, os_):
-            m = len(fs)
-            sp = (C.c_void_p * m)(*[f.ctypes.data for f in fs]); dp = (C.c_void_p * m)(*[o.ctypes.data for o in os_])
             if size is None:
-                ok = self._L.w2x_render_sequence_rgba(self._h, sp, r, c, c * 4, dp, cols * 4, m, *flags)
-            else:
-                ok = self._L.w2x_render_sequence_rgba_resized(self._h, sp, r, c, c * 4, dp, rows, cols, cols * 4, m, *flags, fid)
-            if not ok:
-                raise W2xError(self.last_error() or "render_sequence_rgba failed")
-        if own:          # a ring of engine-owned buffers: the sequence in pieces, each result copied out
-            res = []
-            try:
-                for k0 in range(0, n, len(own)):
-                    m = min(len(own), n - k0)
-                    run(frames[k0:k0 + m], own[:m])
-                    res += [o.copy() for o in own[:m]]
-            finally:
-                for o in own:
-                    self.free_host(o)
-            return res
-        run(frames, outs)
-        return outs
+                return self._L.w2x_render_sequence_rgba(self._h, _pointers(fs), r, c, c * 4, _pointers(os_, len(fs)), cols * 4, len(fs), *flags)
+            return self._L.w2x_render_sequence_rgba_resized(self._h, _pointers(fs), r, c, c * 4, _pointers(os_, len(fs)), rows, cols, cols * 4, len(fs), *flags, fid)
+        return self._packed_sequence(frames, 4, (rows, cols, 4), outs, pinned, "outs must be packed uint8 [rows, cols, 4] arrays of the output size", run,
+                                     "render_sequence_rgba failed")
 
     def alpha_bleed_device(self, bgra: np.ndarray, radius: int) -> np.ndarray:
         """Test hook (w2x_alpha_bleed_device): the device bleed alone on a uint8 [rows, cols, 4] BGRA frame -> the [rows, cols, 3] BGR frame the tiles are read from"""
-        if bgra.dtype != np.uint8 or bgra.ndim != 3 or bgra.shape[2] != 4 or bgra.strides[2] != 1 or bgra.strides[1] != 4:
-            raise ValueError("bgra must be a uint8 [rows, cols, 4] BGRA array with packed pixels")
+        _frame_ok(bgra, 4, (np.uint8,), "bgra must be a uint8 [rows, cols, 4] BGRA array with packed pixels")
         out = np.empty((bgra.shape[0], bgra.shape[1], 3), np.uint8)
-        if not self._L.w2x_alpha_bleed_device(self._h, bgra.ctypes.data if bgra.size else None, bgra.shape[0], bgra.shape[1], bgra.strides[0],
-                                              out.ctypes.data if out.size else None, out.strides[0], int(radius)):
-            raise W2xError(self.last_error() or "alpha_bleed_device failed")
-        return out
+        return self._finish(self._L.w2x_alpha_bleed_device(self._h, _data(bgra), bgra.shape[0], bgra.shape[1], bgra.strides[0], _data(out), out.strides[0], int(radius)),
+                            out, "alpha_bleed_device failed")
 
     def render_resized(self, src: np.ndarray, size, filter: str = "bicubic", dst: np.ndarray | None = None):
         """render() followed by an antialiased resize on the device to size = (rows, cols), each in [input dim, input dim * scaling]
         (w2x_render_resized / w2x_render16_resized; uint8 or uint16 frames).  With dst=None returns the array or raises; with dst returns a bool."""
-        bps = src.dtype.itemsize
-        if src.dtype not in (np.uint8, np.uint16) or src.ndim != 3 or src.shape[2] != 3 or src.strides[2] != bps or src.strides[1] != 3 * bps:
-            raise ValueError("src must be a uint8 (or uint16) [rows, cols, 3] BGR array with packed pixels")
+        _frame_ok(src, 3, (np.uint8, np.uint16), "src must be a uint8 (or uint16) [rows, cols, 3] BGR array with packed pixels")
         rows, cols = int(size[0]), int(size[1])
         fid = _filter_id(filter)
-        ret_array = dst is None
-        if dst is None:
-            dst = np.empty((max(rows, 0), max(cols, 0), 3), src.dtype)
-        if dst.dtype != src.dtype or dst.shape != (rows, cols, 3) or (dst.size and (dst.strides[2] != bps or dst.strides[1] != 3 * bps)):
-            raise ValueError("dst must be a packed [rows, cols, 3] array of the target size and the frame's sample type")   # (an empty target: refused by the library)
-        fn = self._L.w2x_render_resized if bps == 1 else self._L.w2x_render16_resized
-        ok = bool(fn(self._h, src.ctypes.data, src.shape[0], src.shape[1], src.strides[0], dst.ctypes.data if dst.size else None, rows, cols,
-                     dst.strides[0], fid))
-        if ret_array:
-            if not ok:
-                raise W2xError(self.last_error() or "render_resized failed")
-            return dst
-        return ok
+        out = np.empty((max(rows, 0), max(cols, 0), 3), src.dtype) if dst is None else None
+        dst = out if dst is None else dst
+        # (an empty target: refused by the library; a wrong dst raises here, where render() returns False)
+        _frame_ok(dst, 3, (src.dtype,), "dst must be a packed [rows, cols, 3] array of the target size and the frame's sample type", shape=(rows, cols), empty_ok=True)
+        fn = self._L.w2x_render_resized if src.itemsize == 1 else self._L.w2x_render16_resized
+        return self._finish(fn(self._h, src.ctypes.data, src.shape[0], src.shape[1], src.strides[0], _data(dst), rows, cols, dst.strides[0], fid), out, "render_resized failed")
 
     def render_sequence_resized(self, frames, size, outs=None, pinned: bool = False, filter: str = "bicubic"):
         """render_sequence() with every frame resized to size = (rows, cols) like render_resized() (w2x_render_sequence_resized; uint8 frames).
         outs / pinned as in render_sequence()."""
-        n = len(frames)
-        if n == 0:
+        if len(frames) == 0:
             return []
         rows, cols = int(size[0]), int(size[1])
         fid = _filter_id(filter)
         r, c = frames[0].shape[:2]
         for f in frames:
-            if f.dtype != np.uint8 or f.shape != (r, c, 3) or f.strides != (c * 3, 3, 1):
-                raise ValueError("frames must be packed uint8 [rows, cols, 3] arrays of one size")
-        own = []
-        if outs is None:
-            if pinned:
-                own = [self.alloc_host((rows, cols, 3)) for _ in range(min(n, 3))]
-            else:
-                outs = [np.empty((rows, cols, 3), np.uint8) for _ in range(n)]
-        for o in (own or outs):
-            if o.dtype != np.uint8 or o.shape != (rows, cols, 3) or o.strides != (cols * 3, 3, 1):
-                raise ValueError("outs must be packed uint8 arrays of the target size")
+            _frame_ok(f, 3, (np.uint8,), "frames must be packed uint8 [rows, cols, 3] arrays of one size", shape=(r, c), rows_packed=True)
 
         def run(fs, os_):
-            m = len(fs)
-            if not self._L.w2x_render_sequence_resized(self._h, (C.c_void_p * m)(*[f.ctypes.data for f in fs]), r, c, c * 3,
-                                                       (C.c_void_p * m)(*[o.ctypes.data for o in os_]), rows, cols, cols * 3, m, fid):
-                raise W2xError(self.last_error() or "render_sequence_resized failed")
-        if own:          # a ring of engine-owned buffers: the sequence in pieces, each result copied out
-            res = []
-            try:
-                for k0 in range(0, n, len(own)):
-                    m = min(len(own), n - k0)
-                    run(frames[k0:k0 + m], own[:m])
-                    res += [o.copy() for o in own[:m]]
-            finally:
-                for o in own:
-                    self.free_host(o)
-            return res
-        run(frames, outs)
-        return outs
+            return self._L.w2x_render_sequence_resized(self._h, _pointers(fs), r, c, c * 3, _pointers(os_, len(fs)), rows, cols, cols * 3, len(fs), fid)
+        return self._packed_sequence(frames, 3, (rows, cols, 3), outs, pinned, "outs must be packed uint8 arrays of the target size", run, "render_sequence_resized failed")
 
     def render_strip(self, src: np.ndarray, dst: np.ndarray, part: int, parts: int) -> bool:
         """One device's share of a frame split into tile-column strips (w2x_render_strip): writes only its columns of dst."""
-        s = getattr(self, "_scaling", 0)
-        if src.dtype != np.uint8 or src.ndim != 3 or src.shape[2] != 3 or src.strides[2] != 1 or src.strides[1] != 3:
-            raise ValueError("src must be a uint8 [rows, cols, 3] BGR array with packed pixels")
-        if dst.dtype != np.uint8 or dst.shape != (src.shape[0] * s, src.shape[1] * s, 3) or dst.strides[2] != 1 or dst.strides[1] != 3:
-            raise ValueError("dst must be a packed uint8 array of the scaled size")
+        s = self._scaling
+        _frame_ok(src, 3, (np.uint8,), "src must be a uint8 [rows, cols, 3] BGR array with packed pixels")
+        _frame_ok(dst, 3, (np.uint8,), "dst must be a packed uint8 array of the scaled size", shape=(src.shape[0] * s, src.shape[1] * s))
         return bool(self._L.w2x_render_strip(self._h, src.ctypes.data, src.shape[0], src.shape[1], src.strides[0],
                                              dst.ctypes.data, dst.strides[0], int(part), int(parts)))
 
     # ---- one frame over several PROCESSES (one engine each): w2x_shard_compute / w2x_shard_slab / w2x_shard_finish + the IPC helpers below
     def shard_compute(self, src: np.ndarray, part: int, parts: int) -> bool:
-        if src.dtype != np.uint8 or src.ndim != 3 or src.shape[2] != 3 or src.strides[2] != 1 or src.strides[1] != 3:
-            raise ValueError("src must be a uint8 [rows, cols, 3] BGR array with packed pixels")
+        _frame_ok(src, 3, (np.uint8,), "src must be a uint8 [rows, cols, 3] BGR array with packed pixels")
         return bool(self._L.w2x_shard_compute(self._h, src.ctypes.data, src.shape[0], src.shape[1], src.strides[0], int(part), int(parts)))
 
     def shard_slab_handle(self):
@@ -534,16 +510,10 @@ class Img2Img:
 
     def shard_finish(self, dst: np.ndarray, part: int, parts: int, slabs, devices=None) -> bool:
         """slabs[q]: device pointer (int) of part q's slab in THIS process (w2x ipc_open of its handle; 0 for parts that are not needed)"""
-        if dst.dtype != np.uint8 or dst.ndim != 3 or dst.shape[2] != 3 or dst.strides[2] != 1 or dst.strides[1] != 3:
-            raise ValueError("dst must be a packed uint8 [rows, cols, 3] array of the scaled size")
+        _frame_ok(dst, 3, (np.uint8,), "dst must be a packed uint8 [rows, cols, 3] array of the scaled size")
         arr = (C.c_void_p * parts)(*[C.c_void_p(int(p) or None) for p in slabs])
         dev = (C.c_int * parts)(*[int(d) for d in devices]) if devices is not None else None
         return bool(self._L.w2x_shard_finish(self._h, dst.ctypes.data, dst.shape[0], dst.shape[1], dst.strides[0], int(part), int(parts), arr, dev))
-
-    def _yuv_out(self, rows, cols, bits):
-        s = getattr(self, "_scaling", 0)
-        dt = np.uint8 if bits == 8 else np.uint16
-        return tuple(np.empty(shape, dt) for shape in yuv_plane_shapes(rows * s, cols * s))
 
     def render_yuv(self, y, u: np.ndarray | None = None, v: np.ndarray | None = None, *, matrix: str = "bt709", full_range: bool = False, out_bits: int | None = None,
                    out=None, layout: str | None = None, out_layout: str | None = None):
@@ -552,54 +522,34 @@ class Img2Img:
         With the frame given as one tuple of planes, or with layout= / out_layout= ("i420", "i422", "i444", "nv12"; out_layout defaults to the input's), the
         call goes through w2x_render_yuv_layout: an "nv12" frame is (y, uv) with uv of ceil(rows/2) x 2 * ceil(cols/2) samples (10-bit: P010, codes << 6),
         and the result is the tuple of out_layout's planes (yuv_layout_plane_shapes)."""
-        if isinstance(y, (tuple, list)) or layout is not None or out_layout is not None:
-            if isinstance(y, (tuple, list)) and (u is not None or v is not None):
-                raise ValueError("give the frame as one tuple of planes or as three positional planes, not both")
+        with_layout = isinstance(y, (tuple, list)) or layout is not None or out_layout is not None
+        if isinstance(y, (tuple, list)) and (u is not None or v is not None):
+            raise ValueError("give the frame as one tuple of planes or as three positional planes, not both")
+        if not with_layout:
+            planes = (y, u, v)
+        else:
             planes = tuple(y) if isinstance(y, (tuple, list)) else tuple(p for p in (y, u, v) if p is not None)
-            return self._render_yuv_layout(planes, layout or "i420", out_layout, matrix, full_range, out_bits, out)
-        bits = _yuv_bits((y, u, v))
-        ob = bits if out_bits is None else int(out_bits)
-        ret_array = out is None
-        dst = self._yuv_out(*y.shape, ob if ob in (8, 10) else 8) if out is None else tuple(out)
-        if out is not None:
-            # the C ABI sees pointers and steps only: the plane shapes and the sample type of out_bits are checked here
-            s = getattr(self, "_scaling", 0)
-            dt = np.uint16 if ob == 10 else np.uint8
-            if len(dst) != 3 or any(not isinstance(p, np.ndarray) or p.dtype != dt or p.ndim != 2 or p.shape != shape or p.strides[1] != p.itemsize
-                                    for p, shape in zip(dst, yuv_plane_shapes(y.shape[0] * s, y.shape[1] * s))):
-                raise ValueError("out must be three 2-D planes of the scaled 4:2:0 shapes, uint8 for 8-bit and uint16 for 10-bit output, with packed rows")
-        dp = (C.c_void_p * 3)(*[p.ctypes.data for p in dst])
-        ok = bool(self._L.w2x_render_yuv(self._h, (C.c_void_p * 3)(*[p.ctypes.data for p in (y, u, v)]), (C.c_size_t * 3)(*[p.strides[0] for p in (y, u, v)]),
-                                         y.shape[0], y.shape[1], bits, dp, (C.c_size_t * 3)(*[p.strides[0] for p in dst]), dst[0].shape[0], dst[0].shape[1], ob,
-                                         _matrix_id(matrix), 1 if full_range else 0))
-        if ret_array:
-            if not ok:
-                raise W2xError(self.last_error() or "render_yuv failed")
-            return dst
-        return ok
-
-    def _render_yuv_layout(self, planes, layout, out_layout, matrix, full_range, out_bits, out):
-        """render_yuv() through w2x_render_yuv_layout"""
+        layout = layout or "i420"
         out_layout = layout if out_layout is None else out_layout
         lid, olid = _layout_id(layout), _layout_id(out_layout)
-        bits = _yuv_layout_bits(planes, layout)
+        bits = _yuv_layout_bits(planes, layout) if with_layout else _yuv_bits(planes)
         ob = bits if out_bits is None else int(out_bits)
         rows, cols = planes[0].shape
-        s = getattr(self, "_scaling", 0)
+        s = self._scaling
         dt = np.uint16 if ob == 10 else np.uint8
         shapes = yuv_layout_plane_shapes(rows * s, cols * s, out_layout)
-        ret_array = out is None
         dst = tuple(np.empty(shape, dt) for shape in shapes) if out is None else tuple(out)
-        if len(dst) != len(shapes) or any(not isinstance(p, np.ndarray) or p.dtype != dt or p.shape != shape or p.strides[1] != p.itemsize for p, shape in zip(dst, shapes)):
-            raise ValueError(f"out must be the 2-D planes of the scaled {out_layout} shapes, uint8 for 8-bit and uint16 for 10-bit output, with packed rows")
+        # the C ABI sees pointers and steps only: the plane shapes and the sample type of out_bits are checked here
+        # (the three-plane call does not look at planes it allocated itself: on an engine that was never loaded it reaches the library, the layout call raises)
+        if (with_layout or out is not None) and (
+                len(dst) != len(shapes) or any(not isinstance(p, np.ndarray) or p.dtype != dt or p.shape != shape or p.strides[1] != p.itemsize for p, shape in zip(dst, shapes))):
+            raise ValueError(f"out must be the 2-D planes of the scaled {out_layout} shapes, uint8 for 8-bit and uint16 for 10-bit output, with packed rows" if with_layout else
+                             "out must be three 2-D planes of the scaled 4:2:0 shapes, uint8 for 8-bit and uint16 for 10-bit output, with packed rows")
         (sp, ss), (dp, ds) = _plane_args(planes), _plane_args(dst)
-        ok = bool(self._L.w2x_render_yuv_layout(self._h, (C.c_void_p * 3)(*sp), (C.c_size_t * 3)(*ss), rows, cols, bits, lid,
-                                                (C.c_void_p * 3)(*dp), (C.c_size_t * 3)(*ds), rows * s, cols * s, ob, olid, _matrix_id(matrix), 1 if full_range else 0))
-        if ret_array:
-            if not ok:
-                raise W2xError(self.last_error() or "render_yuv failed")
-            return dst
-        return ok
+        a = (self._h, (C.c_void_p * 3)(*sp), (C.c_size_t * 3)(*ss), rows, cols, bits, (C.c_void_p * 3)(*dp), (C.c_size_t * 3)(*ds), rows * s, cols * s, ob,
+             _matrix_id(matrix), 1 if full_range else 0)
+        ok = self._L.w2x_render_yuv_layout(*a[:6], lid, *a[6:11], olid, *a[11:]) if with_layout else self._L.w2x_render_yuv(*a)
+        return self._finish(ok, dst if out is None else None, "render_yuv failed")
 
     def render_yuv_resized(self, y: np.ndarray, u: np.ndarray, v: np.ndarray, size, *, matrix: str = "bt709", full_range: bool = False,
                            out_bits: int | None = None, filter: str = "bicubic", dst=None):
@@ -612,19 +562,13 @@ class Img2Img:
         fid = _filter_id(filter)
         dt = np.uint16 if ob == 10 else np.uint8
         shapes = yuv_plane_shapes(max(rows, 0), max(cols, 0))
-        ret_array = dst is None
         out = tuple(np.empty(shape, dt) for shape in shapes) if dst is None else tuple(dst)
         if len(out) != 3 or any(not isinstance(p, np.ndarray) or p.dtype != dt or p.shape != shape or (p.size and p.strides[1] != p.itemsize) for p, shape in zip(out, shapes)):
             raise ValueError("dst must be three 2-D planes of the target's 4:2:0 shapes, uint8 for 8-bit and uint16 for 10-bit output, with packed rows")
-        dp = (C.c_void_p * 3)(*[p.ctypes.data if p.size else None for p in out])   # (an empty target: refused by the library)
-        ok = bool(self._L.w2x_render_yuv_resized(self._h, (C.c_void_p * 3)(*[p.ctypes.data for p in (y, u, v)]), (C.c_size_t * 3)(*[p.strides[0] for p in (y, u, v)]),
-                                                 y.shape[0], y.shape[1], bits, dp, (C.c_size_t * 3)(*[p.strides[0] for p in out]), rows, cols, ob,
-                                                 _matrix_id(matrix), 1 if full_range else 0, fid))
-        if ret_array:
-            if not ok:
-                raise W2xError(self.last_error() or "render_yuv_resized failed")
-            return out
-        return ok
+        dp = (C.c_void_p * 3)(*[_data(p) for p in out])   # (an empty target: refused by the library)
+        ok = self._L.w2x_render_yuv_resized(self._h, _pointers((y, u, v)), (C.c_size_t * 3)(*[p.strides[0] for p in (y, u, v)]), y.shape[0], y.shape[1], bits,
+                                            dp, (C.c_size_t * 3)(*[p.strides[0] for p in out]), rows, cols, ob, _matrix_id(matrix), 1 if full_range else 0, fid)
+        return self._finish(ok, out if dst is None else None, "render_yuv_resized failed")
 
     def render_sequence_yuv_resized(self, frames, size, *, matrix: str = "bt709", full_range: bool = False, out_bits: int | None = None, pinned: bool = False,
                                     filter: str = "bicubic"):
@@ -642,8 +586,7 @@ class Img2Img:
     def _sequence_yuv(self, frames, size, fid, matrix, full_range, out_bits, pinned, layout=None, out_layout=None):
         """the YUV sequence calls: size = None the scaled size (w2x_render_sequence_yuv; with a layout given w2x_render_sequence_yuv_layout), else the target of
         w2x_render_sequence_yuv_resized with filter fid"""
-        n = len(frames)
-        if n == 0:
+        if len(frames) == 0:
             return []
         with_layout = layout is not None or out_layout is not None
         layout = layout or "i420"
@@ -661,47 +604,31 @@ class Img2Img:
                 fb = None                                                       # (the planes of another layout)
             if fb != bits or f[0].shape != (rows, cols) or [p.strides[0] for p in f] != steps:
                 raise ValueError("frames must be YUV planes of one size, depth and layout")
-        s = getattr(self, "_scaling", 0)
+        s = self._scaling
         orows, ocols = (rows * s, cols * s) if size is None else size
         shapes = yuv_layout_plane_shapes(max(orows, 1), max(ocols, 1), out_layout)   # (an empty target: refused by the library)
         steps = steps + [0] * (3 - len(steps))
         dt = np.uint8 if ob != 10 else np.uint16
-        own = []
-        if pinned:
-            for _ in range(min(n, 3)):
-                sizes = [r * c * np.dtype(dt).itemsize for r, c in shapes]
-                buf = self.alloc_host((sum(sizes),))
-                planes, o = [], 0
-                for (r, c), nb in zip(shapes, sizes):
-                    planes.append(buf[o:o + nb].view(dt).reshape(r, c)); o += nb
-                own.append((buf, tuple(planes)))
-        outs = [own[k % len(own)][1] for k in range(n)] if own else [tuple(np.empty(shape, dt) for shape in shapes) for _ in range(n)]
-        dsteps = (C.c_size_t * 3)(*_plane_args(outs[0])[1])
+        sizes = [r * c * np.dtype(dt).itemsize for r, c in shapes]
+
+        def alloc(host):
+            if not host:
+                return None, tuple(np.empty(shape, dt) for shape in shapes)
+            buf = self.alloc_host((sum(sizes),))          # one page-locked block per frame, carved into its planes
+            starts = [sum(sizes[:k]) for k in range(len(sizes))]
+            return buf, tuple(buf[o:o + nb].view(dt).reshape(shape) for o, nb, shape in zip(starts, sizes, shapes))
 
         def run(fs, os_):
             m = len(fs)
             sp = (C.c_void_p * (3 * m))(*[q for f in fs for q in _plane_args(f)[0]])
             dp = (C.c_void_p * (3 * m))(*[q for o in os_ for q in _plane_args(o)[0]])
-            args = (self._h, sp, (C.c_size_t * 3)(*steps), rows, cols, bits, dp, dsteps, orows, ocols, ob, m, _matrix_id(matrix), 1 if full_range else 0)
-            if with_layout and size is None:
-                if not self._L.w2x_render_sequence_yuv_layout(*args[:6], lid, *args[6:11], olid, *args[11:]):
-                    raise W2xError(self.last_error() or "render_sequence_yuv failed")
-                return
-            if not (self._L.w2x_render_sequence_yuv(*args) if size is None else self._L.w2x_render_sequence_yuv_resized(*args, fid)):
-                raise W2xError(self.last_error() or ("render_sequence_yuv failed" if size is None else "render_sequence_yuv_resized failed"))
-        if own:
-            res = []
-            try:
-                for k0 in range(0, n, len(own)):
-                    m = min(len(own), n - k0)
-                    run(frames[k0:k0 + m], outs[k0:k0 + m])
-                    res += [tuple(p.copy() for p in o) for o in outs[k0:k0 + m]]
-            finally:
-                for buf, _ in own:
-                    self.free_host(buf)
-            return res
-        run(frames, outs)
-        return outs
+            # (the matrix is looked at here: a pinned call with an unknown one has taken its ring by now, and gives it back)
+            a = (self._h, sp, (C.c_size_t * 3)(*steps), rows, cols, bits, dp, (C.c_size_t * 3)(*_plane_args(os_[0])[1]), orows, ocols, ob, m,
+                 _matrix_id(matrix), 1 if full_range else 0)
+            if size is not None:
+                return self._L.w2x_render_sequence_yuv_resized(*a, fid)
+            return self._L.w2x_render_sequence_yuv_layout(*a[:6], lid, *a[6:11], olid, *a[11:]) if with_layout else self._L.w2x_render_sequence_yuv(*a)
+        return self._sequence(frames, None, pinned, alloc, lambda d: tuple(p.copy() for p in d), run, "render_sequence_yuv failed" if size is None else "render_sequence_yuv_resized failed")
 
     def alloc_host(self, shape) -> np.ndarray:
         """A uint8 array over page-locked memory owned by the engine (w2x_alloc_host): frame buffers whose PCIe copies
@@ -711,12 +638,11 @@ class Img2Img:
         if not ptr:
             raise W2xError("w2x_alloc_host failed")
         arr = np.frombuffer((C.c_uint8 * n).from_address(ptr), np.uint8).reshape(shape)
-        self._host_bufs = getattr(self, "_host_bufs", {})
         self._host_bufs[arr.ctypes.data] = ptr
         return arr
 
     def free_host(self, arr: np.ndarray) -> None:
-        ptr = getattr(self, "_host_bufs", {}).pop(arr.ctypes.data, None)
+        ptr = self._host_bufs.pop(arr.ctypes.data, None)
         if ptr:
             self._L.w2x_free_host(self._h, ptr)
 
@@ -724,57 +650,28 @@ class Img2Img:
         """Equally sized frames with upload / compute / download overlapped (w2x_render_sequence).  outs: list of pre-allocated
         arrays (may repeat, e.g. a ring of buffers) or None; pinned=True takes the output buffers it allocates from alloc_host()
         (copies of the results are returned) - pass alloc_host() arrays as frames / outs yourself to avoid that copy."""
-        s = getattr(self, "_scaling", 0)
-        n = len(frames)
-        if n == 0:
+        if len(frames) == 0:
             return []
+        s = self._scaling
         r, c = frames[0].shape[:2]
         for f in frames:
-            if f.dtype != np.uint8 or f.shape != (r, c, 3) or f.strides != (c * 3, 3, 1):
-                raise ValueError("frames must be packed uint8 [rows, cols, 3] arrays of one size")
-        own = []
-        if outs is None:
-            if pinned:
-                own = [self.alloc_host((r * s, c * s, 3)) for _ in range(min(n, 3))]
-                outs = [own[k % len(own)] for k in range(n)]
-            else:
-                outs = [np.empty((r * s, c * s, 3), np.uint8) for _ in range(n)]
-        for o in outs:
-            if o.dtype != np.uint8 or o.shape != (r * s, c * s, 3) or o.strides != (c * s * 3, 3, 1):
-                raise ValueError("outs must be packed uint8 arrays of the scaled size")
-        import ctypes as C
-        sp = (C.c_void_p * n)(*[f.ctypes.data for f in frames])
-        dp = (C.c_void_p * n)(*[o.ctypes.data for o in outs])
-        if own:          # a ring of three engine-owned buffers: run the sequence in pieces and copy each result out
-            res = []
-            try:
-                for k0 in range(0, n, len(own)):
-                    m = min(len(own), n - k0)
-                    if not self._L.w2x_render_sequence(self._h, (C.c_void_p * m)(*[f.ctypes.data for f in frames[k0:k0 + m]]), r, c, c * 3,
-                                                       (C.c_void_p * m)(*[o.ctypes.data for o in own[:m]]), c * s * 3, m):
-                        raise W2xError(self.last_error() or "render_sequence failed")
-                    res += [o.copy() for o in own[:m]]
-            finally:
-                for o in own:
-                    self.free_host(o)
-            return res
-        if not self._L.w2x_render_sequence(self._h, sp, r, c, c * 3, dp, c * s * 3, n):
-            raise W2xError(self.last_error() or "render_sequence failed")
-        return outs
+            _frame_ok(f, 3, (np.uint8,), "frames must be packed uint8 [rows, cols, 3] arrays of one size", shape=(r, c), rows_packed=True)
+
+        def run(fs, os_):
+            return self._L.w2x_render_sequence(self._h, _pointers(fs), r, c, c * 3, _pointers(os_, len(fs)), c * s * 3, len(fs))
+        return self._packed_sequence(frames, 3, (r * s, c * s, 3), outs, pinned, "outs must be packed uint8 arrays of the scaled size", run, "render_sequence failed")
 
     def infer(self, x: np.ndarray) -> np.ndarray:
         """Private trt::Img2Img::infer (img2img_infer.cpp:41-93) as a test hook: [B,3,T,T] f32 -> [B,3,T',T'] f32."""
         x = np.ascontiguousarray(x, np.float32)
-        b, t = getattr(self, "_batch", 0), getattr(self, "_tile", 0)
+        b, t = self._batch, self._tile
         if not b:
             raise W2xError("infer called before a successful load")
         if x.shape != (b, 3, t, t):        # img2img_infer.cpp:43-68: batch count and tile shape must be the loaded configuration's
             raise ValueError(f"infer expects a [{b}, 3, {t}, {t}] blob, got {list(x.shape)}")
         to = self.output_tile_size
         y = np.empty((b, 3, to, to), np.float32)
-        if not self._L.w2x_infer(self._h, x.ctypes.data, y.ctypes.data):
-            raise W2xError(self.last_error() or "infer failed")
-        return y
+        return self._finish(self._L.w2x_infer(self._h, x.ctypes.data, y.ctypes.data), y, "infer failed")
 
     @property
     def output_tile_size(self) -> int:
@@ -820,13 +717,11 @@ class Img2Img:
 def render_sharded(engines, src: np.ndarray, dst: np.ndarray = None) -> np.ndarray:
     """ONE frame over several engines of this process, every tile computed once (w2x_render_sharded): engine k takes the k-th contiguous
     range of the tile order, the seam bands travel device to device, each engine composes and downloads its own cells of `dst`."""
-    s = getattr(engines[0], "_scaling", 0)
-    if src.dtype != np.uint8 or src.ndim != 3 or src.shape[2] != 3 or src.strides[2] != 1 or src.strides[1] != 3:
-        raise ValueError("src must be a uint8 [rows, cols, 3] BGR array with packed pixels")
+    s = engines[0]._scaling
+    _frame_ok(src, 3, (np.uint8,), "src must be a uint8 [rows, cols, 3] BGR array with packed pixels")
     if dst is None:
         dst = np.empty((src.shape[0] * s, src.shape[1] * s, 3), np.uint8)
-    if dst.dtype != np.uint8 or dst.shape != (src.shape[0] * s, src.shape[1] * s, 3) or dst.strides[2] != 1 or dst.strides[1] != 3:
-        raise ValueError("dst must be a packed uint8 array of the scaled size")
+    _frame_ok(dst, 3, (np.uint8,), "dst must be a packed uint8 array of the scaled size", shape=(src.shape[0] * s, src.shape[1] * s))
     handles = (C.c_void_p * len(engines))(*[e._h for e in engines])
     if not lib().w2x_render_sharded(handles, len(engines), src.ctypes.data, src.shape[0], src.shape[1], src.strides[0], dst.ctypes.data, dst.strides[0]):
         raise W2xError(engines[0].last_error() or "sharded render failed")
@@ -921,13 +816,11 @@ def resize_weights(in_size: int, out_size: int, filter: str = "bicubic"):
 def alpha_bleed(bgr: np.ndarray, alpha: np.ndarray, radius: int) -> np.ndarray:
     """The colour bleed of the RGBA renders on the host (w2x_alpha_bleed): bgr uint8 [rows, cols, 3], alpha uint8 [rows, cols], radius 0..16 -> the frame with
     the colours of the pixels of alpha > 0 spread `radius` pixels outward under the pixels of alpha == 0; raises for invalid arguments"""
-    if bgr.dtype != np.uint8 or bgr.ndim != 3 or bgr.shape[2] != 3 or (bgr.size and (bgr.strides[2] != 1 or bgr.strides[1] != 3)):
-        raise ValueError("bgr must be a uint8 [rows, cols, 3] array with packed pixels")
+    _frame_ok(bgr, 3, (np.uint8,), "bgr must be a uint8 [rows, cols, 3] array with packed pixels", empty_ok=True)
     if alpha.dtype != np.uint8 or alpha.shape != bgr.shape[:2] or (alpha.size and alpha.strides[1] != 1):
         raise ValueError("alpha must be a uint8 [rows, cols] array of the frame's size with packed rows")
     out = np.empty(bgr.shape, np.uint8)
-    if not lib().w2x_alpha_bleed(bgr.ctypes.data if bgr.size else None, bgr.strides[0], alpha.ctypes.data if alpha.size else None, alpha.strides[0],
-                                 bgr.shape[0], bgr.shape[1], int(radius), out.ctypes.data if out.size else None, out.strides[0]):
+    if not lib().w2x_alpha_bleed(_data(bgr), bgr.strides[0], _data(alpha), alpha.strides[0], bgr.shape[0], bgr.shape[1], int(radius), _data(out), out.strides[0]):
         raise W2xError(f"invalid alpha bleed: a {bgr.shape[1]}x{bgr.shape[0]} frame at radius {radius}")
     return out
 
