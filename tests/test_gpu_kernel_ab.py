@@ -83,3 +83,26 @@ def test_fused_mlp96_tile_shapes_agree_with_each_other_and_with_fp32(tmp_path):
     for a, b in host:
         assert float(b) <= 6e-3 and float(b) <= float(a) + 2e-3, out
     assert re.search(r"32x32 kernel run twice: 0 elements differ", out), out
+
+
+@pytest.mark.gpu
+def test_retired_mlp192_tile32_kernel_agrees_with_the_shipped_one():
+    """tools/ab/k_mlp192q.hip (the C = 192 MLP on 32x32x16 tiles, the engine's kernel of rounds 3 - 5, an alternative source of k_mlp2.o) against
+    the shipped mlp2_kernel<192,2,4> of csrc/k_mlp2.hip in the harness its header names: tools/ab/mlp192_variants.sh with FRAG32_MASK=0b10, variant 0 the
+    shipped file, variant 1 the retired one.  6407 rows = 50 workgroups of 128 rows plus a ragged 7: full tiles, a partial workgroup and a partial wave
+    tile.  The bound: on the commit before the move (both kernels in csrc/k_mlp2.hip, same harness, same rows, same MI355X) the pair differed by
+    max|dy| = 0.00390625 with max|y| = 8.375; neither kernel's ISA changed with the move, so this tree reproduces that value, and the two schedules differ
+    in summation order only, which can move one rounding step of the fp16 result: one fp16 ULP at |y| in [8, 16) is 2^-7 = 0.0078125.
+    Bound = 0.00390625 + 0.0078125 = 0.01171875 (profiles/transformer_helpers/record.txt)."""
+    env = dict(os.environ, FRAG32_MASK="0b10")
+    subprocess.run([os.path.join(ROOT, "tools", "ab", "mlp192_variants.sh"), "", "SRC=" + os.path.join(ROOT, "tools", "ab", "k_mlp192q.hip")],
+                   check=True, env=env, timeout=900)
+    env = dict(os.environ, W2X_AB_REPS="1")          # (the timing rounds behind the comparison: one launch each)
+    out = subprocess.run([os.path.join(ROOT, "tools", "ab", "mlp192_variants"), "6407"], check=True, capture_output=True, text=True, env=env, timeout=120).stdout
+    print(out)
+    m = re.findall(r"v1 vs v0: max\|dy\|=([0-9.]+), (\d+) of (\d+) values differ, nan=(\d+), max\|y\|=([0-9.]+)", out)
+    assert len(m) == 1, out
+    dy, ndiff, total, nan, ymax = m[0]
+    assert int(total) == 6407 * 192 and int(nan) == 0, out
+    assert float(ymax) < 16.0, out                   # the ULP the bound is built from
+    assert float(dy) <= 0.01171875, out

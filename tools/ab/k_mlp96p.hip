@@ -6,72 +6,14 @@
 // with no workgroup barrier and no weight traffic at all (k_mlp2.hip re-stages the 72 KiB for every 128 rows - more bytes than
 // the rows themselves - behind one barrier per 32-hidden-unit chunk; its waves spent 44 % of their time parked).
 // Three waves per SIMD, each in its own phase, cover each other's memory latency.
-#include "kernels.h"
-#ifndef W2X_GELU_DEG
-#define W2X_GELU_DEG 4   // coefficients of q(u): 6 -> 3.1e-7, 5 -> 7.1e-7, 4 -> 8.7e-6 absolute error of GELU (tools/fit_gelu.py).  4: a third of
-                         // the fp16 rounding of the smallest hidden values that matter, network parity unchanged (2.0 ULP16 on every full-width
-                         // graph, same mean error), MLP kernels 5-7 % faster (round 2, profiles/r2_final/gelu_degree_ab.txt; now: tools/ab/lib_variants.sh "k_mlp2.hip:-DW2X_GELU_DEG=6")
-#endif
+#include "transformer_device.h"
 
 #include <algorithm>
 
 namespace w2x {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef unsigned uint4v __attribute__((ext_vector_type(4)));
-
-// GELU(x) = max(x,0) - 0.5 u 2^-q(u), u = min(|x|, 6.5): tools/fit_gelu.py (|err| < 8.7e-6 with the four-coefficient q), two values at a time on v_pk_*_f32
-__device__ __forceinline__ float2v splat2(float c) { return (float2v){c, c}; }
-#ifdef W2X_GELU_SCALAR   // A/B: the same polynomial on single-value instructions
-__device__ __forceinline__ float gelu_fast1(float x) {
-    const float u = fminf(fabsf(x), 6.5f);
-    float q = fmaf(-2.992485764e-05f, u, 7.398797018e-04f);
-    q = fmaf(q, u, -7.977479093e-03f);
-    q = fmaf(q, u, 5.323820859e-02f);
-    q = fmaf(q, u, 4.589156733e-01f);
-    q = fmaf(q, u, 1.151147085e+00f);
-    return fmaf(-0.5f * u, __builtin_amdgcn_exp2f(-(q * u)), fmaxf(x, 0.f));
-}
-__device__ __forceinline__ float2v gelu_fast2(float2v x) { return (float2v){gelu_fast1(x[0]), gelu_fast1(x[1])}; }
-#else
-__device__ __forceinline__ float2v gelu_fast2(float2v x) {
-    const float2v u = {fminf(fabsf(x[0]), 6.5f), fminf(fabsf(x[1]), 6.5f)};
-#if W2X_GELU_DEG == 5
-    float2v q = __builtin_elementwise_fma(splat2(4.881020589e-04f), u, splat2(-7.198718011e-03f));
-    q = __builtin_elementwise_fma(q, u, splat2(5.214663110e-02f));
-    q = __builtin_elementwise_fma(q, u, splat2(4.595958449e-01f));
-    q = __builtin_elementwise_fma(q, u, splat2(1.151000542e+00f));
-#elif W2X_GELU_DEG == 4
-    float2v q = __builtin_elementwise_fma(splat2(-4.161669730e-03f), u, splat2(4.573546095e-02f));
-    q = __builtin_elementwise_fma(q, u, splat2(4.649304537e-01f));
-    q = __builtin_elementwise_fma(q, u, splat2(1.149566979e+00f));
-#else
-    float2v q = __builtin_elementwise_fma(splat2(-2.992485764e-05f), u, splat2(7.398797018e-04f));
-    q = __builtin_elementwise_fma(q, u, splat2(-7.977479093e-03f));
-    q = __builtin_elementwise_fma(q, u, splat2(5.323820859e-02f));
-    q = __builtin_elementwise_fma(q, u, splat2(4.589156733e-01f));
-    q = __builtin_elementwise_fma(q, u, splat2(1.151147085e+00f));
-#endif
-    const float2v t = __builtin_elementwise_fma(q, u, splat2(1.f));              // the factor 1/2 rides in the exponent: 0.5 * 2^-qu = 2^-(qu + 1)
-    const float2v e = {__builtin_amdgcn_exp2f(-t[0]), __builtin_amdgcn_exp2f(-t[1])};
-    const float2v m = {fmaxf(x[0], 0.f), fmaxf(x[1], 0.f)};
-    return __builtin_elementwise_fma(-u, e, m);
-}
-#endif
-__device__ __forceinline__ void sum_sq8(const half8 v, float& s, float& q) {
-    const half2v one = {(_Float16)1.f, (_Float16)1.f};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const half2v h = {v[2 * k], v[2 * k + 1]};
-        s = __builtin_amdgcn_fdot2(h, one, s, false);
-        q = __builtin_amdgcn_fdot2(h, h, q, false);
-    }
-}
+// (the vector types, gelu_fast2, sum_sq8_acc, norm8 and the phase fences: csrc/transformer_device.h)
 // sums over the four 16-lane rows of a wave for two values at once: the two chains fill each other's permlane wait states.
 // The inputs come straight from v_dot2c chains: a dot result needs 3 wait states before a different VALU may read it, and
 // nothing inside an asm statement is padded by the compiler - hence the leading s_nop 2 (without it the sums were wrong on some
@@ -87,23 +29,6 @@ __device__ __forceinline__ void rows_sum2(float& a0, float& a1) {
         "v_add_f32 %0, %0, %2\n\tv_add_f32 %1, %1, %3"
         : "+v"(a0), "+v"(a1), "=&v"(b0), "=&v"(b1));
 }
-// (x * rstd + nm) on 8 halves with fp32 arithmetic: v_fma_mixlo / mixhi read the f16 halves directly and write f16
-__device__ __forceinline__ half8 norm8(const half8 v, float rstd, float nm) {
-    uint4v x = __builtin_bit_cast(uint4v, v), o;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        unsigned r;
-        asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(x[d]), "v"(rstd), "v"(nm));
-        asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(r) : "v"(x[d]), "v"(rstd), "v"(nm));
-        o[d] = r;
-    }
-    return __builtin_bit_cast(half8, o);
-}
-
-// A wave hands data from lane to lane through its own LDS slab; the hardware executes a wave's LDS instructions in order, so a
-// compiler-level fence (no instruction) is all that is needed between the phases.
-#define W2X_PHASE_FENCE() asm volatile("" ::: "memory")
-#define W2X_RING_FENCE() asm volatile("" ::: "memory")   // keeps a ring refill where it is written (the scheduler would sink it to its use)
 
 constexpr int C = 96, TT = 2, RW = 16 * TT, NWV = 12, NTHR = NWV * 64;
 constexpr int LDX = C + 8, PPR = C / 8, KS = C / 32, NT = C / 16, NCH = 2 * C / 32;
@@ -178,7 +103,7 @@ __global__ __launch_bounds__(NTHR, 3) void mlp96p_kernel(const MlpParams p, int 
             half8 raw[KS];
             float s = 0.f, q = 0.f;
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) { raw[ks] = *(const half8*)(Xw + (tt * 16 + fr) * LDX + ks * 32 + g * 8); sum_sq8(raw[ks], s, q); }
+            for (int ks = 0; ks < KS; ++ks) { raw[ks] = *(const half8*)(Xw + (tt * 16 + fr) * LDX + ks * 32 + g * 8); sum_sq8_acc(raw[ks], s, q); }
             rows_sum2(s, q);
             const float mean = s * (1.f / C);
             const float rstd = __builtin_amdgcn_rsqf(fmaxf(q * (1.f / C) - mean * mean, 0.f) + p.eps);
@@ -262,7 +187,7 @@ __global__ __launch_bounds__(NTHR, 3) void mlp96p_kernel(const MlpParams p, int 
         if (p.stats_out && lane < nrows) {   // LayerNorm statistics of the produced rows for an un-fused consumer
             float s = 0.f, q = 0.f;
 #pragma unroll
-            for (int c = 0; c < PPR; ++c) sum_sq8(*(const half8*)(Xw + lane * LDX + c * 8), s, q);
+            for (int c = 0; c < PPR; ++c) sum_sq8_acc(*(const half8*)(Xw + lane * LDX + c * 8), s, q);
             const float mean = s * (1.f / C);
             p.stats_out[2 * (row0 + lane)] = mean;
             p.stats_out[2 * (row0 + lane) + 1] = __builtin_amdgcn_rsqf(fmaxf(q * (1.f / C) - mean * mean, 0.f) + p.eps_out);

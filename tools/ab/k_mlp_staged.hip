@@ -9,15 +9,14 @@
 // chunks of 64 hidden units with register prefetch of the next chunk.  The output tile is staged through LDS so the
 // residual add and the HBM stores are 16-byte row pieces; LayerNorm statistics of the produced rows are emitted for
 // the next op when requested.
-#include "kernels.h"
+#include "transformer_device.h"
 #include <cstdlib>
 
 namespace w2x {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef float float4v __attribute__((ext_vector_type(4)));
+// (half8 / half4 / half2v / float4v and sum_sq8: csrc/transformer_device.h; this round-1 kernel keeps its scalar GELU, its LayerNorm scaling through
+//  conversions and its group sum)
 typedef unsigned int u32x4 __attribute__((ext_vector_type(4)));
 
 // GELU(x) = 0.5 x (1 + erf(x/sqrt2)) = max(x,0) - 0.5 u erfc(u/sqrt2), u = |x|, with erfc(u/sqrt2) = 2^-q(u):
@@ -35,27 +34,15 @@ __device__ __forceinline__ float gelu_fast(float x) {
     return fmaf(-0.5f * u, e, fmaxf(x, 0.f));
 }
 
-// sum over aligned groups of LPR (16 or 32) lanes with DPP (no LDS crossbar): xor1, xor2, half-row mirror, row mirror
-// packed-fp16 row helpers: sum and sum of squares of 8 halves through v_dot2_f32_f16 (fp32 accumulation), and the
-// LayerNorm affine (x - mean) * rstd as one mixed-precision fma per element (fp16 in, fp32 scale/offset, one rounding)
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ void sum_sq8(const half8 v, float& s, float& q) {
-    const half2v one = {(_Float16)1.f, (_Float16)1.f};
-    s = 0.f; q = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const half2v h = {v[2 * k], v[2 * k + 1]};
-        s = __builtin_amdgcn_fdot2(h, one, s, false);
-        q = __builtin_amdgcn_fdot2(h, h, q, false);
-    }
-}
-__device__ __forceinline__ half8 norm8(const half8 v, float rstd, float nm) {
+// the LayerNorm affine (x - mean) * rstd as one mixed-precision fma per element (fp16 in, fp32 scale/offset, one rounding)
+__device__ __forceinline__ half8 norm8_cvt(const half8 v, float rstd, float nm) {
     half8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = (_Float16)fmaf((float)v[e], rstd, nm);
     return o;
 }
 
+// sum over aligned groups of LPR (16 or 32) lanes with DPP (no LDS crossbar): xor1, xor2, half-row mirror, row mirror
 template <int LPR>
 __device__ __forceinline__ float group_sum(float v) {
     v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
@@ -156,7 +143,7 @@ __global__ __launch_bounds__(256, (C == 96 ? 2 : 1)) void mlp_kernel(const MlpPa
             q = group_sum<LPR>(q);
             const float mean = s * (1.f / C);
             const float rstd = rsqrtf(fmaxf(q * (1.f / C) - mean * mean, 0.f) + p.eps);
-            if (li < PPR) *(half8*)(Xs + r * LDX + li * 8) = norm8(xr[ps], rstd, -mean * rstd);
+            if (li < PPR) *(half8*)(Xs + r * LDX + li * 8) = norm8_cvt(xr[ps], rstd, -mean * rstd);
         }
     }
 

@@ -2,7 +2,7 @@
 // tools/ab/attn_ab.hip; the shipped kernel is waifu2x-tensorrt_amd/csrc/k_swinattn96.hip.
 // Fused Swin attention branch, C = 96 / 6 heads of 16 / window 6x6, register-resident variant for gfx950.
 //     y = x + proj( W-MSA( LayerNorm(x) ) )
-// Same math, parameters and bias-table layout as k_swinattn.hip; the schedule is the one of k_swinattn192.hip:
+// Same math, parameters and bias-table layout as csrc/k_swinattn96.hip; the schedule is the one of round 3's C = 192 kernel (git 9576837:tools/ab/k_swinattn192_r3.hip):
 // a workgroup = 4 waves = 2 windows; wave (w, hp) owns window w and the heads 2*it + hp (it = 0..2), reads its weights
 // straight from L2 as MFMA fragments (fragment-major copy, one head ahead) and keeps q, k, v, S and P in registers.
 // With a head dimension of 16 the accumulator layout (lane (col, g) holds rows 4g..4g+3) is exactly the operand layout
@@ -12,53 +12,27 @@
 //     S^T after the softmax       -> B operand of O^T
 // need no LDS round trip and no permutation.  The q/k/v products use v_mfma_f32_16x16x32_f16 over the 96 channels.
 // LDS holds the normalised x slabs (48 rows per window: tokens 0..31, then tokens 32..35 on rows 32, 36, 40, 44 so that
-// key 32+g sits on row 4g of the third key tile - see k_swinattn192.hip) and the head outputs for proj.
+// key 32+g sits on row 4g of the third key tile - slab_row, csrc/transformer_device.h) and the head outputs for proj.
 // Four workgroup barriers in the whole kernel.
 // The kernel is VALU-issue bound (SQ counters: 11 VALU instructions per MFMA before, MFMA pipe < 25 % busy), so the vector
 // work around the products is kept minimal: softmax denominators from a ones-operand MFMA, k bias dropped / v bias after the
 // normalisation, packed fp32 (v_pk_*) where two values share an operation, interleaved permlane / DPP chains without wait
 // states, the row -> pixel map computed once per workgroup, all row loads unconditional from clamped addresses.
-#include "kernels.h"
+#include "transformer_device.h"
 
 namespace w2x {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void sum_sq8(const half8 v, float& s, float& q) {
-    const half2v one = {(_Float16)1.f, (_Float16)1.f};
-    s = 0.f; q = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const half2v h = {v[2 * k], v[2 * k + 1]};
-        s = __builtin_amdgcn_fdot2(h, one, s, false);
-        q = __builtin_amdgcn_fdot2(h, h, q, false);
-    }
-}
-__device__ __forceinline__ half8 norm8(const half8 v, float rstd, float nm) {
+// (the vector types, sum_sq8, group_sum16, rows_max3, slab_row and the W2X_DPP4 / W2X_DPP6 steps: csrc/transformer_device.h.  This schedule predates the
+//  v_fma_mix form of the LayerNorm scaling and the third wait state in front of the DPP chains, and keeps its own of both.)
+__device__ __forceinline__ half8 norm8_cvt(const half8 v, float rstd, float nm) {
     half8 o;
 #pragma unroll
     for (int e = 0; e < 8; ++e) o[e] = (_Float16)fmaf((float)v[e], rstd, nm);
     return o;
 }
-// sum over aligned groups of 16 lanes with DPP
-__device__ __forceinline__ float group_sum16(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-    return v;
-}
-// Row-group sums of several independent values at once: v_add_f32 with a DPP operand (the compiler emits v_mov_dpp +
-// v_add for v += dpp(v)); the chains are interleaved so that each one's two wait states between a VALU write and a
-// DPP read are filled by the others.
-#define W2X_DPP1(R, CTRL) "v_add_f32_dpp " R ", " R ", " R " " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-#define W2X_DPP4(CTRL) W2X_DPP1("%0", CTRL) W2X_DPP1("%1", CTRL) W2X_DPP1("%2", CTRL) W2X_DPP1("%3", CTRL)
-#define W2X_DPP6(CTRL) W2X_DPP4(CTRL) W2X_DPP1("%4", CTRL) W2X_DPP1("%5", CTRL)
+// Row-group sums of several independent values at once: v_add_f32 with a DPP operand; the chains are interleaved so that each one's two wait states
+// between a VALU write and a DPP read are filled by the others.
 #define W2X_DPP_STEPS(N) "s_nop 1\n\t" W2X_DPP##N("quad_perm:[1,0,3,2]") W2X_DPP##N("quad_perm:[2,3,0,1]") W2X_DPP##N("row_half_mirror") W2X_DPP##N("row_mirror")
 __device__ __forceinline__ void group_sum16_x4(float& a, float& b, float& c, float& d) {
     asm volatile(W2X_DPP_STEPS(4) : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
@@ -66,21 +40,6 @@ __device__ __forceinline__ void group_sum16_x4(float& a, float& b, float& c, flo
 __device__ __forceinline__ void group_sum16_x6(float& a, float& b, float& c, float& d, float& e, float& f) {
     asm volatile(W2X_DPP_STEPS(6) : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f));
 }
-// Row maximum of three independent values at once: each chain's permlane wait states (two after the VALU write a swap
-// reads, one before a VALU reads a swap's result) are filled by the other two chains, so the sequence carries no s_nop,
-// and v_max_f32 is used as is (fmaxf() would canonicalise both swap results first).
-__device__ __forceinline__ void rows_max3(float& a0, float& a1, float& a2) {
-    float b0, b1, b2;
-    asm volatile(
-        "v_mov_b32 %3, %0\n\tv_mov_b32 %4, %1\n\tv_mov_b32 %5, %2\n\t"
-        "v_permlane16_swap_b32 %0, %3\n\tv_permlane16_swap_b32 %1, %4\n\tv_permlane16_swap_b32 %2, %5\n\t"
-        "v_max_f32 %0, %0, %3\n\tv_max_f32 %1, %1, %4\n\tv_max_f32 %2, %2, %5\n\t"
-        "v_mov_b32 %3, %0\n\tv_mov_b32 %4, %1\n\tv_mov_b32 %5, %2\n\t"
-        "v_permlane32_swap_b32 %0, %3\n\tv_permlane32_swap_b32 %1, %4\n\tv_permlane32_swap_b32 %2, %5\n\t"
-        "v_max_f32 %0, %0, %3\n\tv_max_f32 %1, %1, %4\n\tv_max_f32 %2, %2, %5"
-        : "+v"(a0), "+v"(a1), "+v"(a2), "=&v"(b0), "=&v"(b1), "=&v"(b2));
-}
-
 constexpr int C = 96, HD = 16, NH = 6, NTOK = 36, G = 2, R = G * NTOK, RT = 5, RP = RT * 16;
 constexpr int SLAB = 48, RPX = G * SLAB;   // slab rows per window / in the tile
 constexpr int LDX = C + 8;                 // 104 halves
@@ -88,8 +47,6 @@ constexpr int XS = RPX * LDX, OS = RP * LDX;
 constexpr int PIXN = 80;                   // row -> pixel table entries (>= the rows the passes touch)
 constexpr int SMEM96 = (XS + OS) * 2 + PIXN * 4;
 constexpr int LPR = 16, PPR = C / 8, RPP = 256 / LPR, NPASS = (R + RPP - 1) / RPP;   // row passes: 16 lanes per row, 16 rows per pass, 5 passes
-
-__device__ __forceinline__ int slab_row(int t) { return t < 32 ? t : 32 + 4 * (t - 32); }
 
 __global__ __launch_bounds__(256, 3) void swin_attn96_g2_kernel(const SwinAttnParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -179,7 +136,7 @@ __global__ __launch_bounds__(256, 3) void swin_attn96_g2_kernel(const SwinAttnPa
             const int w = r >= NTOK ? 1 : 0;
             const float mean = sm[ps] * (1.f / C);
             const float rstd = rsqrtf(fmaxf(sq[ps] * (1.f / C) - mean * mean, 0.f) + p.eps);
-            if (r < R && li < PPR) *(half8*)(Xs + (w * SLAB + slab_row(r - w * NTOK)) * LDX + li * 8) = norm8(xr[ps], rstd, -mean * rstd);
+            if (r < R && li < PPR) *(half8*)(Xs + (w * SLAB + slab_row(r - w * NTOK)) * LDX + li * 8) = norm8_cvt(xr[ps], rstd, -mean * rstd);
         }
         // the 12 rows between tokens 32..35 of each slab are multiplied like the rest (results ignored): keep them finite
         for (int i = tid; i < G * 12 * PPR; i += 256) {

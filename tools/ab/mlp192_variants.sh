@@ -1,7 +1,8 @@
 #!/bin/bash
 # Builds tools/ab/mlp192_variants from variants of csrc/k_mlp2.hip (C = 192 geometry switches):  tools/ab/mlp192_variants.sh "<flags v0>" "<flags v1>" ...
 # e.g.  tools/ab/mlp192_variants.sh "" "-DW2X_MLP192_TT=1 -DW2X_MLP192_WPS=3"        then run tools/ab/mlp192_variants [rows] on the GPU box
-# FRAG32_MASK=0b10 (environment): bit i set = variant i gets its weights in the 32x32x16 fragment order (the mlp2q kernel)
+# FRAG32_MASK=0b10 (environment): bit i set = variant i gets its weights in the 32x32x16 fragment order; csrc/k_mlp2.hip refuses that order at C = 192, the kernel
+# that takes it is the retired tools/ab/k_mlp192q.hip:  FRAG32_MASK=0b10 tools/ab/mlp192_variants.sh "" "SRC=$PWD/tools/ab/k_mlp192q.hip"  (tests/test_gpu_kernel_ab.py)
 # A baseline from an earlier revision: git show 38f61ee:waifu2x-tensorrt_amd/csrc/<kernel>.hip > tools/ab/<kernel>_r2.hip, then "SRC=$PWD/tools/ab/<kernel>_r2.hip".
 set -eu
 ROOT=$(cd "$(dirname "$0")/../.." && pwd)

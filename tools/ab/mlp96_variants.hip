@@ -95,9 +95,9 @@ int main(int argc, char** argv) {
         params_of(v).y = yv[v]; CK(variants[v](params_of(v), 0)); CK(hipDeviceSynchronize());
         CK(hipMemcpy(v ? hv.data() : h0.data(), yv[v], M * C * 2, hipMemcpyDeviceToHost));
         if (v) {
-            double md = 0; long nd = 0, nan = 0;
-            for (long i = 0; i < M * C; ++i) { const float a = f16_to_f32(h0[i]), b = f16_to_f32(hv[i]); if (!(b == b)) { ++nan; continue; } nd += h0[i] != hv[i]; md = std::max(md, (double)std::fabs(a - b)); }
-            printf("v%d vs v0: max|dy|=%.5f, %ld of %ld values differ, nan=%ld\n", v, md, nd, M * C, nan);
+            double md = 0, my = 0; long nd = 0, nan = 0;
+            for (long i = 0; i < M * C; ++i) { const float a = f16_to_f32(h0[i]), b = f16_to_f32(hv[i]); if (!(b == b)) { ++nan; continue; } nd += h0[i] != hv[i]; md = std::max(md, (double)std::fabs(a - b)); my = std::max(my, (double)std::fabs(a)); }
+            printf("v%d vs v0: max|dy|=%.10f, %ld of %ld values differ, nan=%ld, max|y|=%.10f\n", v, md, nd, M * C, nan, my);
         }
     }
     hipEvent_t e0, e1; CK(hipEventCreate(&e0)); CK(hipEventCreate(&e1));

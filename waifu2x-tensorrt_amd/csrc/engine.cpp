@@ -732,7 +732,7 @@ struct Img2Img::Impl {
                 const auto& w1 = plan.blobs[op.m.w1].data; const auto& w2 = plan.blobs[op.m.w2].data;
                 if (w1.size() != (size_t)2 * Cm * Cm * 2 || w2.size() != w1.size()) throw std::runtime_error("plan: MLP weight size");
                 // C = 96: 32x32x16 fragments (k_mlp96q.hip).  C = 192: 16x16x32 fragments (mlp2_kernel<192,2,4> in k_mlp2.hip) since round 6 - the 32x32x16 kernel of
-                // rounds 3-5 (mlp2q_kernel, -DW2X_MLP192_TILE32 here) takes the same time per launch but more energy per product, and the frame runs at the
+                // rounds 3-5 (mlp2q_kernel, now tools/ab/k_mlp192q.hip; -DW2X_MLP192_TILE32 here and that file in place of k_mlp2.hip) takes the same time per launch but more energy per product, and the frame runs at the
                 // board's power cap: 7.272 / 7.274 against 7.306 / 7.312 / 7.307 ms per frame in alternating pairs (profiles/r6_kernels/lib_mlp192_tile16_frame_level.txt)
                 if (!mlp_frag32(Cm)) {
                     if (!frag_blobs[op.m.w1]) upload_frag(op.m.w1, frag_major((const uint16_t*)w1.data(), 2 * Cm, Cm));

@@ -13,12 +13,7 @@
 // with no workgroup barrier and no weight traffic at all (k_mlp2.hip re-stages the 72 KiB for every 128 rows - more bytes than
 // the rows themselves - behind one barrier per 32-hidden-unit chunk; its waves spent 44 % of their time parked).
 // Three waves per SIMD, each in its own phase, cover each other's memory latency.
-#include "kernels.h"
-#ifndef W2X_GELU_DEG
-#define W2X_GELU_DEG 4   // coefficients of q(u): 6 -> 3.1e-7, 5 -> 7.1e-7, 4 -> 8.7e-6 absolute error of GELU (tools/fit_gelu.py).  4: a third of
-                         // the fp16 rounding of the smallest hidden values that matter, network parity unchanged (2.0 ULP16 on every full-width
-                         // graph, same mean error), MLP kernels 5-7 % faster (round 2, profiles/r2_final/gelu_degree_ab.txt; now: tools/ab/lib_variants.sh "k_mlp2.hip:-DW2X_GELU_DEG=6")
-#endif
+#include "transformer_device.h"
 
 #include <algorithm>
 
@@ -55,97 +50,9 @@
 namespace w2x {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef float float16v __attribute__((ext_vector_type(16)));
-typedef unsigned uint4v __attribute__((ext_vector_type(4)));
-
-// Rows move through buffer resources over x / y (32-bit byte offsets, bounds-checked by the hardware): a piece at or beyond the end
-// reads zeros and its store is dropped, so the ragged last tile and the prefetch past the last tile need no predicate.  The launcher
-// cuts passes of more than kMaxBufBytes into runs.
+// Rows move through buffer resources over x / y (transformer_device.h): the ragged last tile and the prefetch past the last tile need no predicate.
+// The launcher cuts passes of more than kMaxBufBytes into runs.
 constexpr size_t kMaxBufBytes = 0xFFF00000u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-
-// GELU(x) = max(x,0) - 0.5 u 2^-q(u), u = min(|x|, 6.5): tools/fit_gelu.py (|err| < 8.7e-6 with the four-coefficient q), two values at a time on v_pk_*_f32
-__device__ __forceinline__ float2v splat2(float c) { return (float2v){c, c}; }
-#ifdef W2X_GELU_SCALAR   // A/B: the same polynomial on single-value instructions
-__device__ __forceinline__ float gelu_fast1(float x) {
-    const float u = fminf(fabsf(x), 6.5f);
-    float q = fmaf(-2.992485764e-05f, u, 7.398797018e-04f);
-    q = fmaf(q, u, -7.977479093e-03f);
-    q = fmaf(q, u, 5.323820859e-02f);
-    q = fmaf(q, u, 4.589156733e-01f);
-    q = fmaf(q, u, 1.151147085e+00f);
-    return fmaf(-0.5f * u, __builtin_amdgcn_exp2f(-(q * u)), fmaxf(x, 0.f));
-}
-__device__ __forceinline__ float2v gelu_fast2(float2v x) { return (float2v){gelu_fast1(x[0]), gelu_fast1(x[1])}; }
-#else
-__device__ __forceinline__ float2v gelu_fast2(float2v x) {
-    const float2v u = {fminf(fabsf(x[0]), 6.5f), fminf(fabsf(x[1]), 6.5f)};
-#if W2X_GELU_DEG == 5
-    float2v q = __builtin_elementwise_fma(splat2(4.881020589e-04f), u, splat2(-7.198718011e-03f));
-    q = __builtin_elementwise_fma(q, u, splat2(5.214663110e-02f));
-    q = __builtin_elementwise_fma(q, u, splat2(4.595958449e-01f));
-    q = __builtin_elementwise_fma(q, u, splat2(1.151000542e+00f));
-#elif W2X_GELU_DEG == 4
-    float2v q = __builtin_elementwise_fma(splat2(-4.161669730e-03f), u, splat2(4.573546095e-02f));
-    q = __builtin_elementwise_fma(q, u, splat2(4.649304537e-01f));
-    q = __builtin_elementwise_fma(q, u, splat2(1.149566979e+00f));
-#else
-    float2v q = __builtin_elementwise_fma(splat2(-2.992485764e-05f), u, splat2(7.398797018e-04f));
-    q = __builtin_elementwise_fma(q, u, splat2(-7.977479093e-03f));
-    q = __builtin_elementwise_fma(q, u, splat2(5.323820859e-02f));
-    q = __builtin_elementwise_fma(q, u, splat2(4.589156733e-01f));
-    q = __builtin_elementwise_fma(q, u, splat2(1.151147085e+00f));
-#endif
-    const float2v t = __builtin_elementwise_fma(q, u, splat2(1.f));              // the factor 1/2 rides in the exponent: 0.5 * 2^-qu = 2^-(qu + 1)
-    const float2v e = {__builtin_amdgcn_exp2f(-t[0]), __builtin_amdgcn_exp2f(-t[1])};
-    const float2v m = {fmaxf(x[0], 0.f), fmaxf(x[1], 0.f)};
-    return __builtin_elementwise_fma(-u, e, m);
-}
-#endif
-__device__ __forceinline__ void sum_sq8(const half8 v, float& s, float& q) {
-    const half2v one = {(_Float16)1.f, (_Float16)1.f};
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const half2v h = {v[2 * k], v[2 * k + 1]};
-        s = __builtin_amdgcn_fdot2(h, one, s, false);
-        q = __builtin_amdgcn_fdot2(h, h, q, false);
-    }
-}
-// sums over the two lanes (l, l ^ 32) that hold one token row, for two values at once: the two chains fill each other's permlane
-// wait states.  The inputs come straight from v_dot2c chains: a dot result needs 3 wait states before a different VALU may read it,
-// and nothing inside an asm statement is padded by the compiler - hence the leading s_nop 2.
-__device__ __forceinline__ void halves_sum2(float& a0, float& a1) {
-    float b0, b1;
-    asm volatile(
-        "s_nop 2\n\tv_mov_b32 %2, %0\n\tv_mov_b32 %3, %1\n\ts_nop 0\n\t"
-        "v_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %1, %3\n\t"
-        "v_add_f32 %0, %0, %2\n\tv_add_f32 %1, %1, %3"
-        : "+v"(a0), "+v"(a1), "=&v"(b0), "=&v"(b1));
-}
-// (x * rstd + nm) on 8 halves with fp32 arithmetic: v_fma_mixlo / mixhi read the f16 halves directly and write f16
-__device__ __forceinline__ half8 norm8(const half8 v, float rstd, float nm) {
-    uint4v x = __builtin_bit_cast(uint4v, v), o;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        unsigned r;
-        asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(x[d]), "v"(rstd), "v"(nm));
-        asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(r) : "v"(x[d]), "v"(rstd), "v"(nm));
-        o[d] = r;
-    }
-    return __builtin_bit_cast(half8, o);
-}
-
-// A wave hands data from lane to lane through its own LDS slab; the hardware executes a wave's LDS instructions in order, so a
-// compiler-level fence (no instruction) is all that is needed between the phases.
-#define W2X_PHASE_FENCE() asm volatile("" ::: "memory")
-#define W2X_RING_FENCE() asm volatile("" ::: "memory")   // keeps a ring refill where it is written (the scheduler would sink it to its use)
 
 constexpr int C = 96, RW = 32, NWV = 12, NTHR = NWV * 64;
 constexpr int LDX = C + 8, PPR = C / 8, KS = C / 16, NT = C / 32, NCH = 2 * C / 32;   // 6 k-steps of 16, 3 output tiles of 32 channels, 6 chunks of 32 hidden units
@@ -274,7 +181,7 @@ __global__ __launch_bounds__(NTHR, 3) void mlp96q_kernel(const MlpParams p, int 
             half8 raw[KS];
             float s = 0.f, q = 0.f;
 #pragma unroll
-            for (int ks = 0; ks < KS; ++ks) { raw[ks] = *(const half8*)(Xw + r32 * LDX + ks * 16 + h * 8); sum_sq8(raw[ks], s, q); }
+            for (int ks = 0; ks < KS; ++ks) { raw[ks] = *(const half8*)(Xw + r32 * LDX + ks * 16 + h * 8); sum_sq8_acc(raw[ks], s, q); }
             halves_sum2(s, q);
             const float mean = s * (1.f / C);
             const float rstd = __builtin_amdgcn_rsqf(fmaxf(q * (1.f / C) - mean * mean, 0.f) + p.eps);
@@ -465,7 +372,7 @@ __global__ __launch_bounds__(NTHR, 3) void mlp96q_kernel(const MlpParams p, int 
         if (!TOIMG && p.stats_out && lane < nrows) {   // LayerNorm statistics of the produced rows for an un-fused consumer
             float s = 0.f, q = 0.f;
 #pragma unroll
-            for (int c = 0; c < PPR; ++c) sum_sq8(*(const half8*)(Xw + lane * LDX + c * 8), s, q);
+            for (int c = 0; c < PPR; ++c) sum_sq8_acc(*(const half8*)(Xw + lane * LDX + c * 8), s, q);
             const float mean = s * (1.f / C);
             p.stats_out[2 * (row0 + lane)] = mean;
             p.stats_out[2 * (row0 + lane) + 1] = __builtin_amdgcn_rsqf(fmaxf(q * (1.f / C) - mean * mean, 0.f) + p.eps_out);
@@ -495,23 +402,14 @@ hipError_t launch_mlp96q(const MlpParams& p, hipStream_t s) {
     // the kernel addresses x / y with 32-bit byte offsets and prefetches one tile stride (NWV tiles per workgroup) past its last tile: longer passes
     // run in pieces that leave room for that stride (a pass of kMaxBufBytes alone would not: tests/test_gpu_transformer_kernels.py split_mlp96_head)
     const long max_tiles = std::min<long>((long)(kMaxBufBytes / (RW * C * 2)), 0xFFFFFFFFl / (RW * C * 2) - (long)ncu * NWV);
-    const long max_rows = max_tiles * RW;
-    for (long r0 = 0; r0 < p.M; r0 += max_rows) {
-        MlpParams q = p;
-        q.M = std::min(max_rows, p.M - r0);
-        q.x = (const char*)p.x + (size_t)r0 * C * 2; q.y = (char*)p.y + (size_t)r0 * C * 2;
-        if (p.stats_out) q.stats_out = p.stats_out + 2 * r0;
-        q.live_row0 = p.live_row0 + r0;
+    return for_mlp_runs(p, max_tiles * RW, [&](const MlpParams& q) {
         const long ntiles = (q.M + RW - 1) / RW;
         const int grid = (int)std::min<long>((ntiles + NWV - 1) / NWV, ncu);
         if ((ntiles + (long)grid * NWV) * (long)(RW * C * 2) > 0xFFFFFFFFl) return hipErrorInvalidValue;   // (cannot happen: max_tiles)
-        if (p.ti_w) {
-            q.ti_row0 = r0;
-            hipLaunchKernelGGL(mlp96q_kernel<true>, dim3(grid), dim3(NTHR), SMEM96Q, s, q, (int)ntiles);
-        } else hipLaunchKernelGGL(mlp96q_kernel<false>, dim3(grid), dim3(NTHR), SMEM96Q, s, q, (int)ntiles);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        if (p.ti_w) hipLaunchKernelGGL(mlp96q_kernel<true>, dim3(grid), dim3(NTHR), SMEM96Q, s, q, (int)ntiles);
+        else hipLaunchKernelGGL(mlp96q_kernel<false>, dim3(grid), dim3(NTHR), SMEM96Q, s, q, (int)ntiles);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace w2x

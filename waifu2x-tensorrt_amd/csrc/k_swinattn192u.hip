@@ -12,56 +12,16 @@
 //   * the projection keeps its 15 output tiles in registers across the barrier that frees the head-output tile, which it then overwrites.
 // That is <= 168 registers and three workgroups per CU (three waves per SIMD), for two more workgroup barriers and a third more weight
 // traffic from L2.  tools/ab/attn192_variants.sh compares it with the shipped kernel bit for bit and times both.
-#include "kernels.h"
-
-#include <algorithm>
+#include "transformer_device.h"
 
 namespace w2x {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-
-__device__ __forceinline__ void sum_sq8(const half8 v, float& s, float& q) {
-    const half2v one = {(_Float16)1.f, (_Float16)1.f};
-    s = 0.f; q = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const half2v h = {v[2 * k], v[2 * k + 1]};
-        s = __builtin_amdgcn_fdot2(h, one, s, false);
-        q = __builtin_amdgcn_fdot2(h, h, q, false);
-    }
-}
-// (x * rstd + nm) on 8 halves with fp32 arithmetic: v_fma_mixlo / mixhi read the f16 halves directly and write f16
-typedef unsigned uint4v __attribute__((ext_vector_type(4)));
-typedef int int2v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ half8 norm8(const half8 v, float rstd, float nm) {
-    uint4v x = __builtin_bit_cast(uint4v, v), o;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        unsigned r;
-        asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(x[d]), "v"(rstd), "v"(nm));
-        asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(r) : "v"(x[d]), "v"(rstd), "v"(nm));
-        o[d] = r;
-    }
-    return __builtin_bit_cast(half8, o);
-}
-// Rows are fetched and stored through buffer resources over x / y (k_swinattn96.hip): an offset at or beyond num_records reads zeros
-// and drops stores, so rows that do not exist and the idle lanes of a row need neither a predicate nor masking of the data.
-constexpr unsigned kNoRow = 0xFFFFFFFFu;     // saturating adds keep it there
+// Rows are fetched and stored through buffer resources over x / y (transformer_device.h): rows that do not exist and the idle lanes of a row need
+// neither a predicate nor masking of the data.  The launcher cuts passes of more than kMaxBufBytes into runs of whole images.
 constexpr size_t kMaxBufBytes = 0xFFFFFF00u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);
-}
-// see k_swinattn.hip for why the swaps are inline asm on two registers
-__device__ __forceinline__ void swap16(float& a, float& b) { asm volatile("s_nop 1\n\tv_permlane16_swap_b32 %0, %1\n\ts_nop 0" : "+v"(a), "+v"(b)); }
-// 32-lane group sums of six independent values at once (k_swinattn96.hip): four v_add_f32 steps with a DPP operand
+// 32-lane group sums of six independent values at once: four v_add_f32 steps with a DPP operand (W2X_DPP6: transformer_device.h)
 // inside the 16-lane rows, then one row swap across; the chains fill each other's wait states.
-#define W2X_DPP1(R, CTRL) "v_add_f32_dpp " R ", " R ", " R " " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-#define W2X_DPP6(CTRL) W2X_DPP1("%0", CTRL) W2X_DPP1("%1", CTRL) W2X_DPP1("%2", CTRL) W2X_DPP1("%3", CTRL) W2X_DPP1("%4", CTRL) W2X_DPP1("%5", CTRL)
 __device__ __forceinline__ void group_sum32_x6(float& a, float& b, float& c, float& d, float& e, float& f) {
     float ta, tb, tc, td, te, tf;
     asm volatile(
@@ -71,28 +31,6 @@ __device__ __forceinline__ void group_sum32_x6(float& a, float& b, float& c, flo
         "v_permlane16_swap_b32 %3, %9\n\tv_permlane16_swap_b32 %4, %10\n\tv_permlane16_swap_b32 %5, %11\n\t"
         "v_add_f32 %0, %0, %6\n\tv_add_f32 %1, %1, %7\n\tv_add_f32 %2, %2, %8\n\tv_add_f32 %3, %3, %9\n\tv_add_f32 %4, %4, %10\n\tv_add_f32 %5, %5, %11"
         : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f), "=&v"(ta), "=&v"(tb), "=&v"(tc), "=&v"(td), "=&v"(te), "=&v"(tf));
-}
-// Row maximum of three independent values at once (k_swinattn96.hip): the chains fill each other's permlane wait states
-// and v_max_f32 is used as is.
-__device__ __forceinline__ void rows_max3(float& a0, float& a1, float& a2) {
-    float b0, b1, b2;
-    asm volatile(
-        "v_mov_b32 %3, %0\n\tv_mov_b32 %4, %1\n\tv_mov_b32 %5, %2\n\t"
-        "v_permlane16_swap_b32 %0, %3\n\tv_permlane16_swap_b32 %1, %4\n\tv_permlane16_swap_b32 %2, %5\n\t"
-        "v_max_f32 %0, %0, %3\n\tv_max_f32 %1, %1, %4\n\tv_max_f32 %2, %2, %5\n\t"
-        "v_mov_b32 %3, %0\n\tv_mov_b32 %4, %1\n\tv_mov_b32 %5, %2\n\t"
-        "v_permlane32_swap_b32 %0, %3\n\tv_permlane32_swap_b32 %1, %4\n\tv_permlane32_swap_b32 %2, %5\n\t"
-        "v_max_f32 %0, %0, %3\n\tv_max_f32 %1, %1, %4\n\tv_max_f32 %2, %2, %5"
-        : "+v"(a0), "+v"(a1), "+v"(a2), "=&v"(b0), "=&v"(b1), "=&v"(b2));
-}
-// sum over aligned groups of 32 lanes: DPP inside the 16-lane rows, one row swap across
-__device__ __forceinline__ float group_sum32(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-    float a = v, b = v; swap16(a, b);
-    return a + b;
 }
 
 // Build switches (tools/ab/attn192_variants.sh):
@@ -123,8 +61,6 @@ constexpr int LPR = 32, PPR = C / 8, RPP = 256 / LPR, NPASS = R / RPP;   // row 
 static_assert(R % RPP == 0, "row passes");
 static_assert(RP * LDX <= XS, "the head-output tile and the output tile fit where the slabs were");
 static_assert(SMEM192U * W2X_A192U_WPC <= 160 * 1024, "LDS per CU");
-
-__device__ __forceinline__ int slab_row(int t) { return t < 32 ? t : 32 + 4 * (t - 32); }
 
 __global__ __launch_bounds__(256, W2X_A192U_WPC) void swin_attn192u_kernel(const SwinAttnParams p) {
     extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
@@ -508,27 +444,17 @@ __global__ __launch_bounds__(256, W2X_A192U_WPC) void swin_attn192u_kernel(const
 
 }  // namespace
 
-// same contract as launch_swin_attn192 (git 9576837:tools/ab/k_swinattn192_r3.hip)
+// same contract as launch_swin_attn96 (k_swinattn96.hip); the grid is one dimension over the window pairs of all images of a run
 hipError_t launch_swin_attn192u(const SwinAttnParams& p, hipStream_t s) {
     auto kern = swin_attn192u_kernel;
     static unsigned lds_ok = 0;   // per-device bit: kernels.h ensure_dynamic_lds
     if (hipError_t e = ensure_dynamic_lds((const void*)kern, SMEM192U, lds_ok); e != hipSuccess) return e;
     // the kernel addresses x / y with 32-bit byte offsets: passes beyond that are cut into runs of whole images (k_swinattn96.hip)
-    const size_t img_bytes = (size_t)p.nwin * NTOK * C * 2;
-    if (img_bytes == 0 || img_bytes > kMaxBufBytes) return hipErrorInvalidValue;
-    const int per_run = (int)std::min<size_t>((size_t)p.B, kMaxBufBytes / img_bytes);
-    for (int b0 = 0; b0 < p.B; b0 += per_run) {
-        SwinAttnParams q = p;
-        q.B = std::min(per_run, p.B - b0);
-        q.x = (const char*)p.x + (size_t)b0 * img_bytes;
-        q.y = (char*)p.y + (size_t)b0 * img_bytes;
-        if (p.stats_out) q.stats_out = p.stats_out + (size_t)b0 * p.nwin * NTOK * 2;
-        if (p.live) q.live = p.live + b0;
+    return for_attn_runs(p, NTOK, C, kMaxBufBytes, [&](const SwinAttnParams& q) {
         const long total_win = (long)q.B * q.nwin;
         hipLaunchKernelGGL(kern, dim3((unsigned)((total_win + G - 1) / G)), dim3(256), SMEM192U, s, q);
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        return hipGetLastError();
+    });
 }
 
 }  // namespace w2x

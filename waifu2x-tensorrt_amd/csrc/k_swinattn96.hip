@@ -24,9 +24,7 @@
 // workgroup, softmax denominators from a ones-operand MFMA, q bias as the initial accumulator, k bias dropped / v bias after
 // the normalisation, proj computed transposed so that a lane ends with 4 consecutive channels of one token (bias as the
 // initial accumulator, 8-byte LDS stores).
-#include "kernels.h"
-
-#include <algorithm>
+#include "transformer_device.h"
 
 // Choices that were build switches while they were being measured (round 3 - 5; the variants are in git history at 9576837, the records under
 // profiles/r5_kernels/a96_*.txt, profiles/r3_kernels/attn96_*.txt):
@@ -50,58 +48,12 @@
 namespace w2x {
 namespace {
 
-typedef _Float16 half8 __attribute__((ext_vector_type(8)));
-typedef _Float16 half4 __attribute__((ext_vector_type(4)));
-typedef _Float16 half2v __attribute__((ext_vector_type(2)));
-typedef float float4v __attribute__((ext_vector_type(4)));
-typedef float float2v __attribute__((ext_vector_type(2)));
-typedef int int2v __attribute__((ext_vector_type(2)));
-typedef unsigned uint4v __attribute__((ext_vector_type(4)));
-
-// Rows are fetched and stored through buffer resources over x / y: an offset at or beyond num_records reads zeros and drops
-// stores, so rows that do not exist (and the four idle lanes of a 16-lane row) need neither a predicate nor masking of the data.
-// Offsets are 32 bits: the launcher cuts passes of more than kMaxBufBytes into runs of whole images.
-constexpr unsigned kNoRow = 0xFFFFFFFFu;     // saturating adds keep it there
+// Rows are fetched and stored through buffer resources over x / y (transformer_device.h): rows that do not exist and the four idle lanes of a 16-lane
+// row need neither a predicate nor masking of the data.  The launcher cuts passes of more than kMaxBufBytes into runs of whole images.
 constexpr size_t kMaxBufBytes = 0xFFFFFF00u;
-__device__ __forceinline__ __amdgpu_buffer_rsrc_t make_rsrc(const void* p, unsigned bytes) {
-    return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(p), 0, bytes, 0x00020000);   // raw buffer, 32-bit offsets, bounds-checked
-}
 
-__device__ __forceinline__ void sum_sq8(const half8 v, float& s, float& q) {
-    const half2v one = {(_Float16)1.f, (_Float16)1.f};
-    s = 0.f; q = 0.f;
-#pragma unroll
-    for (int k = 0; k < 4; ++k) {
-        const half2v h = {v[2 * k], v[2 * k + 1]};
-        s = __builtin_amdgcn_fdot2(h, one, s, false);
-        q = __builtin_amdgcn_fdot2(h, h, q, false);
-    }
-}
-// (x * rstd + nm) on 8 halves with fp32 arithmetic: v_fma_mixlo / mixhi read the f16 halves directly and write f16
-__device__ __forceinline__ half8 norm8(const half8 v, float rstd, float nm) {
-    uint4v x = __builtin_bit_cast(uint4v, v), o;
-#pragma unroll
-    for (int d = 0; d < 4; ++d) {
-        unsigned r;
-        asm("v_fma_mixlo_f16 %0, %1, %2, %3 op_sel_hi:[1,0,0]" : "=v"(r) : "v"(x[d]), "v"(rstd), "v"(nm));
-        asm("v_fma_mixhi_f16 %0, %1, %2, %3 op_sel:[1,0,0] op_sel_hi:[1,0,0]" : "+v"(r) : "v"(x[d]), "v"(rstd), "v"(nm));
-        o[d] = r;
-    }
-    return __builtin_bit_cast(half8, o);
-}
-// sum over aligned groups of 16 lanes with DPP
-__device__ __forceinline__ float group_sum16(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_update_dpp(0, __builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-    return v;
-}
-// Row-group sums of four / six independent values at once: v_add_f32 with a DPP operand; the chains are interleaved so that each
-// one's two wait states between a VALU write and a DPP read are filled by the others.
-#define W2X_DPP1(R, CTRL) "v_add_f32_dpp " R ", " R ", " R " " CTRL " row_mask:0xf bank_mask:0xf bound_ctrl:1\n\t"
-#define W2X_DPP6(CTRL) W2X_DPP1("%0", CTRL) W2X_DPP1("%1", CTRL) W2X_DPP1("%2", CTRL) W2X_DPP1("%3", CTRL) W2X_DPP1("%4", CTRL) W2X_DPP1("%5", CTRL)
-#define W2X_DPP4(CTRL) W2X_DPP1("%0", CTRL) W2X_DPP1("%1", CTRL) W2X_DPP1("%2", CTRL) W2X_DPP1("%3", CTRL)
+// Row-group sums of four / six independent values at once: v_add_f32 with a DPP operand (W2X_DPP4 / W2X_DPP6: transformer_device.h); the chains are
+// interleaved so that each one's two wait states between a VALU write and a DPP read are filled by the others.
 __device__ __forceinline__ void group_sum16_x4(float& a, float& b, float& c, float& d) {
     asm volatile("s_nop 2\n\t" W2X_DPP4("quad_perm:[1,0,3,2]") W2X_DPP4("quad_perm:[2,3,0,1]") W2X_DPP4("row_half_mirror") W2X_DPP4("row_mirror")
                  : "+v"(a), "+v"(b), "+v"(c), "+v"(d));
@@ -110,10 +62,9 @@ __device__ __forceinline__ void group_sum16_x6(float& a, float& b, float& c, flo
     asm volatile("s_nop 2\n\t" W2X_DPP6("quad_perm:[1,0,3,2]") W2X_DPP6("quad_perm:[2,3,0,1]") W2X_DPP6("row_half_mirror") W2X_DPP6("row_mirror")
                  : "+v"(a), "+v"(b), "+v"(c), "+v"(d), "+v"(e), "+v"(f));
 }
-// Maximum over the four lanes that hold one query column (lanes fr, fr+16, fr+32, fr+48) for two / three independent values.
-// Wait states of v_permlane*_swap (two after the VALU write it reads, one before a VALU reads its result) are filled by the
-// other chain(s) or an s_nop; v_max_f32 as is (fmaxf() would canonicalise both swap results first).
-__device__ __forceinline__ void cols_max2(float& a0, float& a1) {
+// Maximum over the four lanes that hold one query column (lanes fr, fr+16, fr+32, fr+48) for two independent values; for three: rows_max3,
+// transformer_device.h, where the wait states are explained.  Two chains leave one of them open: the s_nop.
+__device__ __forceinline__ void rows_max2(float& a0, float& a1) {
     float b0, b1;
     asm volatile(
         "v_mov_b32 %2, %0\n\tv_mov_b32 %3, %1\n\ts_nop 0\n\t"
@@ -123,17 +74,6 @@ __device__ __forceinline__ void cols_max2(float& a0, float& a1) {
         "v_permlane32_swap_b32 %0, %2\n\tv_permlane32_swap_b32 %1, %3\n\t"
         "v_max_f32 %0, %0, %2\n\tv_max_f32 %1, %1, %3"
         : "+v"(a0), "+v"(a1), "=&v"(b0), "=&v"(b1));
-}
-__device__ __forceinline__ void cols_max3(float& a0, float& a1, float& a2) {
-    float b0, b1, b2;
-    asm volatile(
-        "v_mov_b32 %3, %0\n\tv_mov_b32 %4, %1\n\tv_mov_b32 %5, %2\n\t"
-        "v_permlane16_swap_b32 %0, %3\n\tv_permlane16_swap_b32 %1, %4\n\tv_permlane16_swap_b32 %2, %5\n\t"
-        "v_max_f32 %0, %0, %3\n\tv_max_f32 %1, %1, %4\n\tv_max_f32 %2, %2, %5\n\t"
-        "v_mov_b32 %3, %0\n\tv_mov_b32 %4, %1\n\tv_mov_b32 %5, %2\n\t"
-        "v_permlane32_swap_b32 %0, %3\n\tv_permlane32_swap_b32 %1, %4\n\tv_permlane32_swap_b32 %2, %5\n\t"
-        "v_max_f32 %0, %0, %3\n\tv_max_f32 %1, %1, %4\n\tv_max_f32 %2, %2, %5"
-        : "+v"(a0), "+v"(a1), "+v"(a2), "=&v"(b0), "=&v"(b1), "=&v"(b2));
 }
 // max of the nine scores a lane holds for one query (two key tiles of four, one left-over key).  Plain fmaxf on purpose: the
 // inputs are MFMA results, and the wait states between an MFMA and a reader of its result are only inserted for instructions
@@ -154,8 +94,6 @@ constexpr int SMEM96 = BQ_OFF + 3 * C * 4;
 constexpr int DUMMY = XS * 2;              // byte offset of a row nobody reads at that point (first row of Os): target of the stores of lanes / rows without data
 constexpr int LPR = 16, PPR = C / 8, RPP = NTHR / LPR, NPASS = RP / RPP;   // row passes: 16 lanes per row (12 carry data), 16 rows per pass, 5 passes
 static_assert(NPASS == 5, "the row sums are reduced as 3 + 2 passes");
-
-__device__ __forceinline__ int slab_row(int t) { return t < 32 ? t : 32 + 4 * (t - 32); }
 
 // P = exp2(S - max) of one query column as fp16 B-operand fragments (keys on the k axis): p01 = key tiles 0 and 1 (k slot j < 4: key
 // 4g + j, j >= 4: key 16 + 4g + j - 4 - the order concat(v tile 0, v tile 1) has too), p2 = the left-over keys
@@ -426,11 +364,11 @@ __global__ __launch_bounds__(NTHR, 4) void swin_attn96_kernel(const SwinAttnPara
         const float t0 = s[0][2][0] + b2[0], t1 = s[1][2][0] + b2[1];
         float mx0 = max9(s[0][0], s[0][1], t0), mx1 = max9(s[1][0], s[1][1], t1);
         half8 pf01[2]; half4 pf2[2];
-        if (u < NU - 1) cols_max2(mx0, mx1);
+        if (u < NU - 1) rows_max2(mx0, mx1);
         else {
             const float tl = sl[2][0] + b2l;
             float mxl = max9(sl[0], sl[1], tl);
-            cols_max3(mx0, mx1, mxl);
+            rows_max3(mx0, mx1, mxl);
             probs(sl[0], sl[1], tl, mxl, pl01, pl2);
         }
         probs(s[0][0], s[0][1], t0, mx0, pf01[0], pf2[0]);
@@ -522,20 +460,10 @@ hipError_t launch_swin_attn96(const SwinAttnParams& p, hipStream_t s) {
     if (hipError_t e = ensure_dynamic_lds((const void*)swin_attn96_kernel, SMEM96, lds_ok); e != hipSuccess) return e;
     // the kernel addresses x / y with 32-bit byte offsets: passes beyond that are cut into runs of whole images (windows never
     // cross an image, the statistics rows follow the pixels)
-    const size_t img_bytes = (size_t)p.nwin * NTOK * C * 2;
-    if (img_bytes == 0 || img_bytes > kMaxBufBytes) return hipErrorInvalidValue;
-    const int per_run = (int)std::min<size_t>((size_t)p.B, kMaxBufBytes / img_bytes);
-    for (int b0 = 0; b0 < p.B; b0 += per_run) {
-        SwinAttnParams q = p;
-        q.B = std::min(per_run, p.B - b0);
-        q.x = (const char*)p.x + (size_t)b0 * img_bytes;
-        q.y = (char*)p.y + (size_t)b0 * img_bytes;
-        if (p.stats_out) q.stats_out = p.stats_out + (size_t)b0 * p.nwin * NTOK * 2;
-        if (p.live) q.live = p.live + b0;
+    return for_attn_runs(p, NTOK, C, kMaxBufBytes, [&](const SwinAttnParams& q) {
         hipLaunchKernelGGL(swin_attn96_kernel, dim3((unsigned)((q.nwin + G - 1) / G), (unsigned)q.B), dim3(NTHR), SMEM96, s, q);      // x: window pairs of an image, y: images
-        if (hipError_t e = hipGetLastError(); e != hipSuccess) return e;
-    }
-    return hipSuccess;
+        return hipGetLastError();
+    });
 }
 
 }  // namespace w2x

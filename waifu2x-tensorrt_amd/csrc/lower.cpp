@@ -731,7 +731,7 @@ struct Lowerer {
         return true;
     }
 
-    // ---- post-pass: LN+qkv GEMM (window gather), attention core, proj GEMM (window scatter + residual) -> one op (k_swinattn.hip)
+    // ---- post-pass: LN+qkv GEMM (window gather), attention core, proj GEMM (window scatter + residual) -> one op (k_swinattn96.hip / k_swinattn192u.hip)
     void fuse_attn() {
         std::vector<Op> out;
         for (size_t i = 0; i < plan.ops.size(); ++i) {
