@@ -122,6 +122,18 @@ public:
     // allocHost()); output i is the bytes of renderRgba() / renderRgbaResized() on frame i.  skipUniformAlpha is decided per frame.  No progress is reported.
     bool renderSequenceRgba(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt = {});
     bool renderSequenceRgbaResized(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt = {}, ResizeFilter filter = ResizeFilter::Bicubic);
+    // Extension: gray frames.  The Image is read as ONE channel: step >= cols * (depth / 8), depth 8 or 16, dst rows*scaling x cols*scaling of the
+    // same depth.  For rep(g) the BGR frame with B = G = R = g, renderGray(g) is the green channel of render(rep(g)), byte for byte, at 8 and at 16 bits - the rule
+    // renderRgba() states for its alpha plane - with one upload and one download of a sample per pixel and nothing replicated on the host.  Progress counts
+    // ceil(N * steps / batchSize) batches, as render().  Empty images, other or differing depths, short steps, other sizes: false (message callback).
+    bool renderGray(const Image& src, Image& dst);
+    // renderGray() resized on the device to dst.rows x dst.cols, the targets and filters of renderResized(): the green channel of renderResized(rep(g)), byte for
+    // byte.  At the scaled size it is renderGray().
+    bool renderGrayResized(const Image& src, Image& dst, ResizeFilter filter = ResizeFilter::Bicubic);
+    // A sequence of equally sized 8-bit gray frames through renderSequence()'s pipeline (page-locked buffers: allocHost()); output i is the bytes of renderGray() /
+    // renderGrayResized() on frame i.  16-bit frames and frames of differing sizes: false.  No progress is reported.
+    bool renderSequenceGray(const Image* srcs, Image* dsts, int count);
+    bool renderSequenceGrayResized(const Image* srcs, Image* dsts, int count, ResizeFilter filter = ResizeFilter::Bicubic);
     void* allocHost(size_t bytes);
     void freeHost(void* data);
     // Page-locks caller-owned memory in place.  Only whole pages are accepted (data and bytes multiples of 4096): a registration
@@ -158,6 +170,7 @@ private:
     bool runSequence(const Image* srcs, Image* dsts, int count, int resizeFilter, const char* who);
     bool renderRgbaFrame(const Image& src, Image& dst, const RgbaOptions& opt, int resizeFilter, const char* who);   // resizeFilter >= 0: renderRgbaResized
     bool runSequenceRgba(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt, int resizeFilter, const char* who);
+    bool runGray(const Image* srcs, Image* dsts, int count, int resizeFilter, const char* who, bool single);   // single: renderGray / renderGrayResized (8 or 16 bits, progress)
     bool runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, int resizeFilter, const char* who);   // resizeFilter >= 0: renderYuvResized
     std::unique_ptr<Impl> impl;
 };

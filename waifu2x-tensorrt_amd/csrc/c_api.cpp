@@ -1,5 +1,6 @@
 // Flat C ABI over w2x::Img2Img (declared in include/w2x/c_api.h, which cites the reference interfaces).
 #include "../../include/w2x/c_api.h"
+#include "../../include/w2x/c_api_gray.h"
 #include <mutex>
 
 #include <cstring>
@@ -236,6 +237,41 @@ int w2x_render_sequence_rgba_resized(w2x_engine* e, const uint8_t* const* srcs, 
     if (!sequence_ok(e, count, srcs, dsts) || !resize_filter(e, filter, "w2x_render_sequence_rgba_resized", f)) return 0;
     ImageSequence q = image_sequence(srcs, image(nullptr, rows, cols, src_step), dsts, image(nullptr, dst_rows, dst_cols, dst_step), count);
     return e->engine.renderSequenceRgbaResized(q.src.data(), q.dst.data(), count, rgba_options(bleed, skip_uniform_alpha), f) ? 1 : 0;
+}
+// gray frames (include/w2x/c_api_gray.h): the Image of one channel goes through image() like a BGR one - the method says how many channels the buffer holds
+int w2x_render_gray(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, size_t dst_step) {
+    if (!e) return 0;
+    w2x::Image d = scaled_image(e->engine, dst, rows, cols, dst_step);
+    return e->engine.renderGray(image(src, rows, cols, src_step), d) ? 1 : 0;
+}
+int w2x_render_gray16(w2x_engine* e, const uint16_t* src, int rows, int cols, size_t src_step, uint16_t* dst, size_t dst_step) {
+    if (!e) return 0;
+    w2x::Image d = scaled_image(e->engine, dst, rows, cols, dst_step, 16);
+    return e->engine.renderGray(image(src, rows, cols, src_step, 16), d) ? 1 : 0;
+}
+int w2x_render_gray_resized(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, int dst_rows, int dst_cols, size_t dst_step, int filter) {
+    w2x::ResizeFilter f;
+    if (!e || !resize_filter(e, filter, "w2x_render_gray_resized", f)) return 0;
+    w2x::Image d = image(dst, dst_rows, dst_cols, dst_step);
+    return e->engine.renderGrayResized(image(src, rows, cols, src_step), d, f) ? 1 : 0;
+}
+int w2x_render_gray16_resized(w2x_engine* e, const uint16_t* src, int rows, int cols, size_t src_step, uint16_t* dst, int dst_rows, int dst_cols, size_t dst_step, int filter) {
+    w2x::ResizeFilter f;
+    if (!e || !resize_filter(e, filter, "w2x_render_gray16_resized", f)) return 0;
+    w2x::Image d = image(dst, dst_rows, dst_cols, dst_step, 16);
+    return e->engine.renderGrayResized(image(src, rows, cols, src_step, 16), d, f) ? 1 : 0;
+}
+int w2x_render_sequence_gray(w2x_engine* e, const uint8_t* const* srcs, int rows, int cols, size_t src_step, uint8_t* const* dsts, size_t dst_step, int count) {
+    if (!sequence_ok(e, count, srcs, dsts)) return 0;
+    ImageSequence q = image_sequence(srcs, image(nullptr, rows, cols, src_step), dsts, scaled_image(e->engine, nullptr, rows, cols, dst_step), count);
+    return e->engine.renderSequenceGray(q.src.data(), q.dst.data(), count) ? 1 : 0;
+}
+int w2x_render_sequence_gray_resized(w2x_engine* e, const uint8_t* const* srcs, int rows, int cols, size_t src_step, uint8_t* const* dsts, int dst_rows, int dst_cols,
+                                     size_t dst_step, int count, int filter) {
+    w2x::ResizeFilter f;
+    if (!sequence_ok(e, count, srcs, dsts) || !resize_filter(e, filter, "w2x_render_sequence_gray_resized", f)) return 0;
+    ImageSequence q = image_sequence(srcs, image(nullptr, rows, cols, src_step), dsts, image(nullptr, dst_rows, dst_cols, dst_step), count);
+    return e->engine.renderSequenceGrayResized(q.src.data(), q.dst.data(), count, f) ? 1 : 0;
 }
 int w2x_alpha_bleed_device(w2x_engine* e, const uint8_t* bgra, int rows, int cols, size_t bgra_step, uint8_t* bgr, size_t bgr_step, int radius) {
     if (!e) return 0;

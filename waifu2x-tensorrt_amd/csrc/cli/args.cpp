@@ -79,6 +79,9 @@ std::string usage() {
            "      --alpha-bleed INT [0]   (extension) 0..16: stills with an alpha channel: spread the colours of the visible pixels that many pixels under the\n"
            "                              transparent ones before upscaling (no dark fringe on cut-outs); not with --deep\n"
            "      --alpha-skip-uniform    (extension) a still whose alpha channel is one value (an opaque export) keeps it without running it through the network\n"
+           "      --gray                  (extension) gray PNGs (colour type 0, 8- or 16-bit with --deep) stay one channel: one sample per pixel to the GPU and back,\n"
+           "                              a gray PNG out; videos read through ffmpeg travel as raw gray frames.  Colour files, single images in formats\n"
+           "                              only ffmpeg reads (JPEG ...) and gray + alpha PNGs (colour type 4: written as RGBA) are rendered as without it.  Not with --colorspace, not with --devices above 1\n"
            "      --tta-mode TEXT [mean]  (extension) {mean,reference}: with --tta, `mean` averages the 8 augmentations; `reference`\n"
            "                              reproduces the bytes of the reference's accumulation (img2img_render.cpp:313-316); --tta-compat = reference\n"
            "  build                       Build model\n"
@@ -90,7 +93,7 @@ const char* const kYuvFormats[8] = {"yuv420p", "yuv420p10le", "yuv422p", "yuv422
 Options parse(int argc, const char* const* argv) {
     Options o;
     std::vector<std::string> a(argv + 1, argv + argc);
-    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_outsize = false, seen_filter = false, seen_colorspace = false, seen_range = false, seen_bleed = false, seen_skip = false, seen_pixfmt = false;
+    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_outsize = false, seen_filter = false, seen_colorspace = false, seen_range = false, seen_bleed = false, seen_skip = false, seen_pixfmt = false, seen_gray = false;
     auto value = [&](size_t& i) -> std::string {
         const std::string name = a[i];
         auto eq = name.find('=');
@@ -143,6 +146,7 @@ Options parse(int argc, const char* const* argv) {
         }
         else if (k == "--alpha-bleed") { o.alphaBleed = to_int(k, value(i)); seen_bleed = true; }
         else if (k == "--alpha-skip-uniform") { o.alphaSkipUniform = true; seen_skip = true; }
+        else if (k == "--gray") { o.gray = true; seen_gray = true; }
         else if (k == "--resize-filter") { o.resizeFilter = value(i); std::transform(o.resizeFilter.begin(), o.resizeFilter.end(), o.resizeFilter.begin(), ::tolower); seen_filter = true; }
         else if (k == "--colorspace") { o.colorspace = value(i); std::transform(o.colorspace.begin(), o.colorspace.end(), o.colorspace.begin(), ::tolower); seen_colorspace = true; }
         else if (k == "--color_range") { o.colorRange = value(i); std::transform(o.colorRange.begin(), o.colorRange.end(), o.colorRange.begin(), ::tolower); seen_range = true; }
@@ -209,11 +213,16 @@ Options parse(int argc, const char* const* argv) {
             if (seen_outscale) throw std::runtime_error("--colorspace: not together with --outscale (a factor rarely gives the even sizes video wants: use --outsize WxH)");
         } else if (seen_range) throw std::runtime_error("--color_range: needs --colorspace");
         else if (seen_yuv_in || seen_yuv_out) throw std::runtime_error(std::string(seen_yuv_in ? "--yuv-in" : "--yuv-out") + ": needs --colorspace");
+        if (seen_gray) {
+            if (seen_colorspace) throw std::runtime_error("--gray: not together with --colorspace (gray frames carry no chroma)");
+            if (o.devices > 1) throw std::runtime_error("--gray: not with --devices " + std::to_string(o.devices) + " (gray frames are rendered on one device)");
+        }
         if (seen_bleed) {
             if (!(o.alphaBleed >= 0 && o.alphaBleed <= 16)) throw std::runtime_error("--alpha-bleed: " + std::to_string(o.alphaBleed) + " not in [0, 16] (the radius in pixels)");
             if (o.alphaBleed > 0 && o.deep) throw std::runtime_error("--alpha-bleed: not together with --deep (the bleed works on 8-bit colour; 16-bit stills keep the colours as stored)");
         }
-    } else if (seen_outscale || seen_outsize || seen_filter || seen_colorspace || seen_range || seen_bleed || seen_skip || seen_yuv_in || seen_yuv_out)
+    } else if (seen_gray) throw std::runtime_error("--gray: only with render");
+    else if (seen_outscale || seen_outsize || seen_filter || seen_colorspace || seen_range || seen_bleed || seen_skip || seen_yuv_in || seen_yuv_out)
         throw std::runtime_error(std::string(seen_yuv_in ? "--yuv-in" : seen_yuv_out ? "--yuv-out" : seen_outscale ? "--outscale" : seen_outsize ? "--outsize" : seen_filter ? "--resize-filter" : seen_colorspace ? "--colorspace" :
                                              seen_range ? "--color_range" : seen_bleed ? "--alpha-bleed" : "--alpha-skip-uniform") + ": only with render");
     // cross-checks, main.cpp:142-145
@@ -266,7 +275,7 @@ std::string to_json(const Options& o) {
        << ", \"resize_filter\": " << q(o.resizeFilter)
        << ", \"colorspace\": " << (o.colorspace.empty() ? std::string("null") : q(o.colorspace)) << ", \"color_range\": " << q(o.colorRange)
        << ", \"yuv_in\": " << (o.yuvIn.empty() ? std::string("null") : q(o.yuvIn)) << ", \"yuv_out\": " << (o.yuvOut.empty() ? std::string("null") : q(o.yuvOut))
-       << ", \"alpha_bleed\": " << o.alphaBleed << ", \"alpha_skip_uniform\": " << (o.alphaSkipUniform ? "true" : "false")
+       << ", \"alpha_bleed\": " << o.alphaBleed << ", \"alpha_skip_uniform\": " << (o.alphaSkipUniform ? "true" : "false") << ", \"gray\": " << (o.gray ? "true" : "false")
        << ", \"codec\": " << q(o.codec) << ", \"pix_fmt\": " << q(o.pixFmt) << ", \"crf\": " << o.crf << ", \"inputs\": [";
     for (size_t i = 0; i < o.inputs.size(); ++i) os << (i ? ", " : "") << q(o.inputs[i]);
     os << "], \"model_path\": " << q(o.command == "convert" ? "" : model_path(o)) << ", \"suffix\": " << q(o.command == "convert" ? "" : output_suffix(o)) << ", \"outputs\": [";

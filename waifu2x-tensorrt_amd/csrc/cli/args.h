@@ -47,6 +47,7 @@ struct Options {
                                           // transparent ones before the network sees them (Img2Img::renderRgba, with --outscale / --outsize Img2Img::renderRgbaResized; on
                                           // the routes that render colour and alpha in two calls - --devices > 1 - the host alpha_bleed); 0 = the colours as stored
     bool alphaSkipUniform = false;        // --alpha-skip-uniform: a still whose alpha plane is one value keeps it without running the plane through the network
+    bool gray = false;                    // --gray (extension, render only): gray PNGs and ffmpeg videos stay one channel (Img2Img::renderGray*)
     bool printConfig = false;             // --print-config: dump the parsed options and derived names as JSON and exit (tests)
     bool help = false;
 };

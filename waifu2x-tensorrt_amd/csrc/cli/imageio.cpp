@@ -87,7 +87,7 @@ Bitmap read_png(const std::vector<uint8_t>& d, const std::string& path, bool kee
     uLongf rawlen = raw.size();
     if (uncompress(raw.data(), &rawlen, idat.data(), idat.size()) != Z_OK || rawlen != raw.size()) throw std::runtime_error(path + ": PNG data does not inflate");
     const bool deep = keep16 && wide;                              // --deep: the low bytes stay
-    Bitmap b; b.rows = h; b.cols = w;
+    Bitmap b; b.rows = h; b.cols = w; b.gray = ctype == 0;
     if (deep) b.bgr16.resize((size_t)w * h * 3); else b.bgr.resize((size_t)w * h * 3);
     const bool has_alpha = ctype == 4 || ctype == 6;               // kept for the writer (the network sees colour only)
     if (has_alpha) b.alpha.resize((size_t)w * h);
@@ -142,15 +142,19 @@ void chunk(std::vector<uint8_t>& out, const char* type, const std::vector<uint8_
 }
 
 void write_png(const std::string& path, const Bitmap& b) {
-    const bool rgba = !b.alpha.empty(), deep = !b.bgr16.empty();
-    const int ch = rgba ? 4 : 3, bps = deep ? 2 : 1;
+    const bool gray = !b.luma.empty() || !b.luma16.empty();          // a one-plane image: colour type 0
+    const bool rgba = !gray && !b.alpha.empty(), deep = gray ? !b.luma16.empty() : !b.bgr16.empty();
+    const int ch = gray ? 1 : rgba ? 4 : 3, bps = deep ? 2 : 1;
     std::vector<uint8_t> raw(((size_t)b.cols * ch * bps + 1) * b.rows);
     for (int y = 0; y < b.rows; ++y) {
         uint8_t* line = &raw[((size_t)b.cols * ch * bps + 1) * y];
         line[0] = 0;   // filter "none": the payload is deflated at level 1 for speed (a 4K frame is 100 MB)
         for (int x = 0; x < b.cols; ++x) {
             uint8_t* o = line + 1 + (size_t)ch * bps * x;
-            if (!deep) {
+            if (gray) {
+                if (!deep) o[0] = b.luma[(size_t)y * b.cols + x];
+                else { const uint16_t g = b.luma16[(size_t)y * b.cols + x]; o[0] = (uint8_t)(g >> 8); o[1] = (uint8_t)g; }
+            } else if (!deep) {
                 const uint8_t* s = &b.bgr[((size_t)y * b.cols + x) * 3];
                 o[0] = s[2]; o[1] = s[1]; o[2] = s[0];
                 if (rgba) o[3] = b.alpha[(size_t)y * b.cols + x];
@@ -166,7 +170,7 @@ void write_png(const std::string& path, const Bitmap& b) {
     if (compress2(comp.data(), &clen, raw.data(), raw.size(), 1) != Z_OK) throw std::runtime_error("PNG deflate failed");
     comp.resize(clen);
     std::vector<uint8_t> out = {0x89, 'P', 'N', 'G', 0x0d, 0x0a, 0x1a, 0x0a}, ihdr;
-    put32(ihdr, b.cols); put32(ihdr, b.rows); ihdr.insert(ihdr.end(), {(uint8_t)(deep ? 16 : 8), (uint8_t)(rgba ? 6 : 2), 0, 0, 0});
+    put32(ihdr, b.cols); put32(ihdr, b.rows); ihdr.insert(ihdr.end(), {(uint8_t)(deep ? 16 : 8), (uint8_t)(gray ? 0 : rgba ? 6 : 2), 0, 0, 0});
     chunk(out, "IHDR", ihdr); chunk(out, "IDAT", comp); chunk(out, "IEND", {});
     std::ofstream f(path, std::ios::binary);
     if (!f.write((const char*)out.data(), out.size())) throw std::runtime_error("cannot write " + path);
@@ -267,6 +271,12 @@ Bitmap read_image(const std::string& path, bool keep16) {
 
 void write_image(const std::string& path, const Bitmap& b) {
     const size_t n = (size_t)b.rows * b.cols;
+    if (!b.luma.empty() || !b.luma16.empty()) {   // a one-plane image: a gray PNG, nothing else
+        if (!((b.luma.size() == n && b.luma16.empty()) || (b.luma16.size() == n && b.luma.empty()))) throw std::runtime_error("bitmap size mismatch");
+        if (lower_ext(path) != ".png") throw std::runtime_error(path + ": a one-plane image can only be written as PNG");
+        write_png(path, b);
+        return;
+    }
     if (!((b.bgr.size() == n * 3 && b.bgr16.empty()) || (b.bgr16.size() == n * 3 && b.bgr.empty())) || (!b.alpha.empty() && b.alpha.size() != n)) throw std::runtime_error("bitmap size mismatch");
     const std::string e = lower_ext(path);
     if (!b.bgr16.empty() && e != ".png") throw std::runtime_error(path + ": 16-bit samples can only be written as PNG");

@@ -19,6 +19,12 @@ struct Bitmap {
     std::vector<uint8_t> bgr;       // rows * cols * 3, packed (empty when bgr16 is used)
     std::vector<uint8_t> alpha;     // rows * cols, or empty
     std::vector<uint16_t> bgr16;    // 16-bit samples of a 16-bit PNG read with keep16 (--deep); then bgr is empty
+    bool gray = false;              // set by read_image: the file was a gray PNG (colour type 0, any depth; then B = G = R).  Gray + alpha PNGs (colour type 4),
+                                    // PPM and BMP files never set it.  Nothing is written differently because of it.
+    // A one-plane image for write_image (the result of Img2Img::renderGray): rows * cols samples of 8 bits (luma) or 16 bits (luma16).  A bitmap that holds one is
+    // written as a colour-type-0 PNG from it; bgr / bgr16 / alpha are then not looked at.
+    std::vector<uint8_t> luma;
+    std::vector<uint16_t> luma16;
 };
 
 Bitmap read_image(const std::string& path, bool keep16 = false);   // throws std::runtime_error; keep16: 16-bit PNG samples stay 16-bit (Bitmap::bgr16)

@@ -6,6 +6,9 @@
 // A PNG / BMP with an alpha channel keeps it (upstream TODO, README.md:88): an 8-bit still on one device goes through Img2Img::renderRgba, or with --outscale /
 // --outsize through Img2Img::renderRgbaResized (colour and alpha in one call, --alpha-bleed / --alpha-skip-uniform on the GPU); on the other routes
 // (--devices > 1, --deep) the alpha plane goes through the same engine as a gray image.
+// Extension: --gray keeps gray PNGs (colour type 0) and ffmpeg videos one channel wide: Img2Img::renderGray / renderGrayResized for stills, raw `gray` frames
+// through renderSequenceGray[Resized] for videos; colour files, single frames read through ffmpeg, gray + alpha PNGs and the built-in AVI route are rendered
+// as without it.
 // Extension: --devices N drives N engines - a single image is split into tile-column strips (Img2Img::renderStrip), every engine
 // writing its own columns of the shared output buffer; a video is cut into chunks of frames that go round-robin to one persistent
 // worker thread per engine (renderSequence over that engine's page-locked buffers), with one reader and one in-order writer thread.
@@ -255,8 +258,12 @@ int main(int argc, char** argv) {
                 out.rows = cli::out_dim(o, in.rows, false); out.cols = cli::out_dim(o, in.cols, true);
                 if (resize && o.devices > 1) throw std::runtime_error(file + ": --outscale / --outsize render a still on one device (--devices 1)");
                 const bool deep = !in.bgr16.empty();                   // --deep on a 16-bit PNG: CV_16UC3 through the engine (extension)
+                // --gray on a gray PNG: one plane through renderGray / renderGrayResized and a gray PNG out; without the flag the file is the colour image it always was
+                const bool gray_still = o.gray && in.gray && in.alpha.empty();
                 Image src, dst;
-                if (deep) {
+                if (gray_still) {
+                    // (no colour planes: the result is one plane, out.luma / out.luma16)
+                } else if (deep) {
                     out.bgr16.resize((size_t)out.rows * out.cols * 3);
                     src = Image{(uint8_t*)in.bgr16.data(), in.rows, in.cols, (size_t)in.cols * 6, 16}; dst = Image{(uint8_t*)out.bgr16.data(), out.rows, out.cols, (size_t)out.cols * 6, 16};
                 } else {
@@ -283,7 +290,25 @@ int main(int argc, char** argv) {
                 };
                 // an 8-bit still with alpha on one device: colour and alpha in one renderRgba() call, or one renderRgbaResized() call with --outscale / --outsize
                 const bool one_call = !in.alpha.empty() && !deep && o.devices == 1;
-                if (one_call) {
+                // one plane of `bps`-byte samples through the engine as a gray frame
+                auto render_plane = [&](const void* plane, void* result, size_t bps) {
+                    Image s1{(uint8_t*)const_cast<void*>(plane), in.rows, in.cols, (size_t)in.cols * bps, (int)(8 * bps)}, d1{(uint8_t*)result, out.rows, out.cols, (size_t)out.cols * bps, (int)(8 * bps)};
+                    return resize ? engines[0]->renderGrayResized(s1, d1, filter) : engines[0]->renderGray(s1, d1);
+                };
+                if (gray_still) {      // the green samples of the (input-sized) frame as the plane; the result is the one-plane image write_image takes
+                    const size_t n = (size_t)in.rows * in.cols, m = (size_t)out.rows * out.cols;
+                    if (deep) {
+                        std::vector<uint16_t> g(n);
+                        for (size_t i = 0; i < n; ++i) g[i] = in.bgr16[3 * i + 1];
+                        out.luma16.resize(m);
+                        if (!render_plane(g.data(), out.luma16.data(), 2)) return -1;
+                    } else {
+                        std::vector<uint8_t> g(n);
+                        for (size_t i = 0; i < n; ++i) g[i] = in.bgr[3 * i + 1];
+                        out.luma.resize(m);
+                        if (!render_plane(g.data(), out.luma.data(), 1)) return -1;
+                    }
+                } else if (one_call) {
                     std::vector<uint8_t> bgra((size_t)in.rows * in.cols * 4), obgra((size_t)out.rows * out.cols * 4);
                     for (size_t i = 0; i < in.alpha.size(); ++i) { bgra[4 * i] = in.bgr[3 * i]; bgra[4 * i + 1] = in.bgr[3 * i + 1]; bgra[4 * i + 2] = in.bgr[3 * i + 2]; bgra[4 * i + 3] = in.alpha[i]; }
                     Image s4{bgra.data(), in.rows, in.cols, (size_t)in.cols * 4}, d4{obgra.data(), out.rows, out.cols, (size_t)out.cols * 4};
@@ -302,7 +327,10 @@ int main(int argc, char** argv) {
                     }
                     if (!render_still(src, dst)) return -1;
                 }
-                if (!in.alpha.empty() && !one_call) {   // the alpha plane as a gray image through the same engine; its green channel is the new alpha
+                if (!in.alpha.empty() && !one_call && o.devices == 1) {   // the alpha plane as a gray frame (renderGray: the green channel of render() of B = G = R = A)
+                    out.alpha.resize((size_t)out.rows * out.cols);
+                    if (!render_plane(in.alpha.data(), out.alpha.data(), 1)) return -1;
+                } else if (!in.alpha.empty() && !one_call) {   // over several devices: the alpha plane as a gray image through the same engines; its green channel is the new alpha
                     cli::Bitmap ga, go;
                     // sized from the geometry: with --deep the colour planes live in bgr16 and in.bgr / out.bgr are empty
                     ga.rows = in.rows; ga.cols = in.cols; ga.bgr.resize((size_t)in.rows * in.cols * 3);
@@ -326,29 +354,32 @@ int main(int argc, char** argv) {
                 auto avi = std::make_unique<AviSource>();
                 const bool is_avi = fs::path(file).extension() == ".avi" || fs::path(file).extension() == ".AVI";
                 bool yuv = false;                                      // --colorspace on a multi-frame input read through ffmpeg: YUV frames
+                bool gray = false;                                     // --gray on an input read through ffmpeg: raw gray frames, one byte per pixel
                 const std::string& rawIn = o.yuvIn.empty() ? o.pixFmt : o.yuvIn, & rawOut = o.yuvOut.empty() ? o.pixFmt : o.yuvOut;   // --yuv-in / --yuv-out
                 const RawYuv fmtIn = raw_yuv(rawIn), fmtOut = raw_yuv(rawOut);
                 if (is_avi && avi->rd.open(file, &why)) {
                     width = avi->rd.info().width; height = avi->rd.info().height; frames = avi->rd.info().frames; fps = avi->rd.info().fps;
                     source = std::move(avi);
+                    if (o.gray) on_message(Severity::warn, file + ": the built-in AVI route is 24-bit only: --gray is ignored");
                 } else {
                     if (!have_ffmpeg) throw std::runtime_error(file + ": needs ffmpeg and ffprobe on PATH (built in: .png, .ppm, .bmp, uncompressed 24-bit .avi" + (why.empty() ? "" : "; " + why) +
                                                                (o.colorspace.empty() ? "" : "; --colorspace reads and writes YUV frames through ffmpeg only") + ")");
                     const Probe pr = ffprobe(file);
                     width = pr.width; height = pr.height; frames = pr.frames; fps = pr.fps;
                     yuv = !o.colorspace.empty() && frames != 1;
-                    const size_t inBytes = yuv ? yuv_frame_bytes(height, width, fmtIn) : (size_t)width * height * 3;
-                    source.reset(new PipeSource("ffmpeg -v error -i " + shell_quote(file) + " -f rawvideo -pix_fmt " + (yuv ? rawIn : std::string("bgr24")) + " -", inBytes));
+                    gray = o.gray && frames != 1;                      // (a single frame is a still in a format only ffmpeg reads: rendered in colour, as without the flag)
+                    const size_t inBytes = yuv ? yuv_frame_bytes(height, width, fmtIn) : (size_t)width * height * (gray ? 1 : 3);
+                    source.reset(new PipeSource("ffmpeg -v error -i " + shell_quote(file) + " -f rawvideo -pix_fmt " + (yuv ? rawIn : std::string(gray ? "gray" : "bgr24")) + " -", inBytes));
                 }
                 frameIndex = 0; frameCount = frames;
                 const bool single = frames == 1;
                 std::string outFile = cli::output_path(o, file, single);
                 check_outsize(file, width, height);
                 const int outW = cli::out_dim(o, width, true), outH = cli::out_dim(o, height, false);
-                const size_t inBytes = yuv ? yuv_frame_bytes(height, width, fmtIn) : (size_t)width * height * 3;
-                const size_t outBytes = yuv ? yuv_frame_bytes(outH, outW, fmtOut) : (size_t)outW * outH * 3;
+                const size_t inBytes = yuv ? yuv_frame_bytes(height, width, fmtIn) : (size_t)width * height * (gray ? 1 : 3);
+                const size_t outBytes = yuv ? yuv_frame_bytes(outH, outW, fmtOut) : (size_t)outW * outH * (gray ? 1 : 3);
                 if (have_ffmpeg) {
-                    std::string wcmd = "ffmpeg -v error -y -f rawvideo -pix_fmt " + (yuv ? rawOut : std::string("bgr24")) + " -s " + std::to_string(outW) + "x" + std::to_string(outH) +
+                    std::string wcmd = "ffmpeg -v error -y -f rawvideo -pix_fmt " + (yuv ? rawOut : std::string(gray ? "gray" : "bgr24")) + " -s " + std::to_string(outW) + "x" + std::to_string(outH) +
                                        " -r " + std::to_string(single ? 1.0 : fps) + " -i - ";
                     if (!single) wcmd += "-c:v " + o.codec + " -pix_fmt " + o.pixFmt + " -crf " + std::to_string(o.crf) + " ";
                     if (yuv) wcmd += colour_tags(o);
@@ -364,6 +395,11 @@ int main(int argc, char** argv) {
                     std::vector<Image> si(n), di(n);
                     for (int k = 0; k < n; ++k) { si[k] = Image{in[k], height, width, (size_t)width * 3}; di[k] = Image{out[k], outH, outW, (size_t)outW * 3}; }
                     return resize ? e.renderSequenceResized(si.data(), di.data(), n, filter) : e.renderSequence(si.data(), di.data(), n);
+                };
+                if (gray) render = [&](Img2Img& e, uint8_t* const* in, uint8_t* const* out, int n) {
+                    std::vector<Image> si(n), di(n);
+                    for (int k = 0; k < n; ++k) { si[k] = Image{in[k], height, width, (size_t)width}; di[k] = Image{out[k], outH, outW, (size_t)outW}; }
+                    return resize ? e.renderSequenceGrayResized(si.data(), di.data(), n, filter) : e.renderSequenceGray(si.data(), di.data(), n);
                 };
                 if (yuv) {
                     YuvFormat f;

@@ -340,20 +340,27 @@ struct Img2Img::Impl {
     unsigned* d_minmax = nullptr; unsigned* h_minmax = nullptr;
     hipEvent_t ev_minmax = nullptr;
     struct RgbaJob { int bleed = 0; bool skip = false; };
+    // Gray frames (renderGray, renderGrayResized, renderSequenceGray*): d_frame / d_out hold ONE sample per pixel (8 or 16 bits, rows padded to 16 bytes:
+    // gray_step), the gather launch is gather_gray_kernel, the frame ends with compose_gray_kernel - resized with compose_canvas_gray_kernel (one fp32 plane) and
+    // resample_gray_kernel.  The sample depth is the job's, not `deep`: nothing of a gray call is replayable.
+    struct GrayJob { bool deep = false; };
     // The kind of frame the running entry point renders: what run_frame(), run_rolling_frame(), the gather of run_passes() and the key of the captured
     // passes branch on.  The default is a plain BGR frame, not resized.  Set once per entry-point family (renderPart / runSequence through job_resize(),
     // runSequenceYuv, rgba_begin()); entry() puts the default back on every exit, exceptions included.  `rs`: the tap tables of a resized frame's target, else null.
     // (`deep` is not part of it: it describes the replayable frame in d_frame / d_out and outlives the call.)
     struct Job {
-        enum Kind { BGR, YUV, RGBA } kind = BGR;
+        enum Kind { BGR, YUV, RGBA, GRAY } kind = BGR;
         const ResizeTables* rs = nullptr;
         YuvJob yuv;
         RgbaJob rgba;
+        GrayJob gray;
     };
     Job job;
     struct JobScope { Impl* im; ~JobScope() { im->job = Job{}; } };
-    // the sample format in the key of a captured pass: 0 / 1 BGR of 8 / 16 bits, 2 .. 49 YuvJob::key, kRgbaKey
-    int sample_format() const { return job.kind == Job::RGBA ? kRgbaKey : job.kind == Job::YUV ? job.yuv.key : deep ? 1 : 0; }
+    // the sample format in the key of a captured pass: 0 / 1 BGR of 8 / 16 bits, 2 .. 49 YuvJob::key, kRgbaKey, kGrayKey / kGrayKey + 1 gray of 8 / 16 bits
+    int sample_format() const {
+        return job.kind == Job::GRAY ? kGrayKey + (job.gray.deep ? 1 : 0) : job.kind == Job::RGBA ? kRgbaKey : job.kind == Job::YUV ? job.yuv.key : deep ? 1 : 0;
+    }
     std::vector<void*> pinned;
     std::vector<void*> host_allocs;     // allocHost(): page-locked buffers handed to the caller
     std::vector<TileSlot> h_slots;
@@ -430,6 +437,7 @@ struct Img2Img::Impl {
     // A pass is captured the second time it is met (the first run stays eager so that one-time attribute calls are out of the
     // way) and replayed from then on.  The key holds everything the captured launches bake in.
     static constexpr int kRgbaKey = 64;   // (YuvJob::key stays below 50)
+    static constexpr int kGrayKey = 65;   // 65 / 66: gray frames of 8 / 16 bits
     using GraphKey = std::tuple<const void*, const void*, const void*, const void*, int, int, int, int>;   // frame, slots, slab out, arena, rows, cols, live, sample format (1: 16-bit, >= 2: YuvJob::key)
     // A pass that runs as NG tile groups is NG graphs, one per group, each a straight line of launches replayed on that group's OWN stream (fork / join
     // events between the streams are issued around the replays): a single captured graph with NG branches runs its side branches on streams the runtime
@@ -983,6 +991,11 @@ struct Img2Img::Impl {
         if (job.kind == Job::RGBA) { rgba_frame(rows, cols, grid, report, nullptr); return; }                  // an RGBA frame of a sequence (renderSequenceRgba)
         run_passes(rows, cols, sp.tile_count, 0, report, 0, true);
         const bool yuv = job.kind == Job::YUV;
+        if (job.kind == Job::GRAY) {                                                      // a gray frame (renderGray / renderGrayResized)
+            if (job.rs) { compose_canvas_gray(rows, cols, grid, stream); resample_gray(stream); }
+            else compose_gray(rows, cols, grid, stream);
+            return;
+        }
         if (job.rs) { compose_canvas(rows, cols, grid, stream); if (yuv) resample_yuv(stream); else resample(stream); return; }   // a resized frame (renderResized / renderYuvResized)
         if (yuv) { compose_yuv(rows, cols, grid, stream); return; }                       // a YUV frame (renderYuv)
         compose_rect(rows, cols, grid, sp.x0, sp.x1, 0, 0, sp.first_tile);
@@ -1014,16 +1027,17 @@ struct Img2Img::Impl {
         hipAssert(hipEventRecord(ev_g0[which], stream));
         hipStream_t s2 = gstream[0];
         hipAssert(hipStreamWaitEvent(s2, ev_g0[which], 0));
-        const bool yuv = job.kind == Job::YUV;
+        const bool yuv = job.kind == Job::YUV, gray = job.kind == Job::GRAY;
         if (job.rs) {   // a resized frame: the canvas compose is the slab's last reader, the resample the writer of d_out; in order on s2, they share one canvas
-            compose_canvas(rows, cols, grid, s2);
+            if (gray) compose_canvas_gray(rows, cols, grid, s2); else compose_canvas(rows, cols, grid, s2);
             hipAssert(hipEventRecord(ev_cmp[which], s2));
             if (out_free) hipAssert(hipStreamWaitEvent(s2, out_free, 0));
-            if (yuv) resample_yuv(s2); else resample(s2);
+            if (gray) resample_gray(s2); else if (yuv) resample_yuv(s2); else resample(s2);
             return;
         }
         if (out_free) hipAssert(hipStreamWaitEvent(s2, out_free, 0));     // the frame that last left through this output buffer has been downloaded
-        if (yuv) compose_yuv(rows, cols, grid, s2);
+        if (gray) compose_gray(rows, cols, grid, s2);
+        else if (yuv) compose_yuv(rows, cols, grid, s2);
         else compose_rect(rows, cols, grid, sp.x0, sp.x1, 0, 0, sp.first_tile, s2);
         hipAssert(hipEventRecord(ev_cmp[which], s2));
     }
@@ -1097,6 +1111,13 @@ struct Img2Img::Impl {
                     rp.bgr = d_bgr; rp.bgr_step = (size_t)cols * 3; rp.alpha = d_alpha; rp.alpha_step = (size_t)cols; rp.rows = rows; rp.cols = cols;
                     rp.out = gp.out; rp.fp32 = gp.fp32; rp.slots = gp.slots; rp.B = gp.B; rp.T = gp.T;
                     hipAssert(launch_gather_rgba(rp, gs));
+                    return;
+                }
+                if (job.kind == Job::GRAY) {                          // a gray frame (renderGray): the same tiles from its one plane
+                    GatherGrayParams yp;
+                    yp.frame = d_frame; yp.rows = rows; yp.cols = cols; yp.step = gray_step(cols, job.gray.deep); yp.deep = job.gray.deep ? 1 : 0;
+                    yp.out = gp.out; yp.fp32 = gp.fp32; yp.slots = gp.slots; yp.B = gp.B; yp.T = gp.T;
+                    hipAssert(launch_gather_gray(yp, gs));
                     return;
                 }
                 if (job.kind != Job::YUV) { hipAssert(launch_gather(gp, gs)); return; }
@@ -1228,6 +1249,25 @@ struct Img2Img::Impl {
         stamp_begin(4, 0);
         hipAssert(launch_compose_yuv(yp, on));
         stamp_end();
+    }
+    // Gray frames: the device layout of the one plane in d_frame / d_out (rows padded to 16 bytes, like the planes of yuv_layout), and the three launches that end a
+    // gray frame - the whole canvas of the frame's tiles (one part, slot 0 = tile 0) as samples into d_out, or as one fp32 plane into d_canvas and its resize into d_out
+    static size_t gray_step(int cols, bool deep16) { return ((size_t)cols * (deep16 ? 2 : 1) + 15) / 16 * 16; }
+    void compose_gray(int rows, int cols, const TileGrid& grid, hipStream_t on) {
+        ComposeParams cp = compose_base(rows, cols, grid);
+        cp.dst = d_out; cp.dst_step = gray_step(cp.outW, job.gray.deep); cp.deep = job.gray.deep ? 1 : 0;
+        stamp_begin(4, 0);
+        hipAssert(launch_compose_gray(cp, on));
+        stamp_end();
+    }
+    void compose_canvas_gray(int rows, int cols, const TileGrid& grid, hipStream_t on) {
+        hipAssert(launch_compose_canvas_gray(compose_base(rows, cols, grid), d_canvas, on));
+    }
+    void resample_gray(hipStream_t on) {
+        ResampleGrayParams rp;
+        resample_base(rp);
+        rp.dst = d_out; rp.dst_step = gray_step(rp.outW, job.gray.deep); rp.deep = job.gray.deep ? 1 : 0;
+        hipAssert(launch_resample_gray(rp, on));
     }
     // RGBA frames (renderRgba / alphaBleed): the BGRA frame into d_frame, the two words zeroed, alpha_bleed_kernel -> d_bgr, d_alpha, d_minmax; all on `stream`
     void upload_and_bleed(const Image& src, int radius) {
@@ -2314,6 +2354,83 @@ bool Img2Img::runSequenceRgba(const Image* srcs, Image* dsts, int count, const R
         [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dev, (size_t)cols * 4, srcs[i].data, srcs[i].step, (size_t)cols * 4, rows, hipMemcpyHostToDevice, on)); },
         [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dsts[i].data, dsts[i].step, dev, (size_t)out_cols * 4, (size_t)out_cols * 4, out_rows, hipMemcpyDeviceToHost, on)); });
     impl->last_ms = total_ms / count;
+    return true;
+    });
+}
+
+// Gray frames: Image read as ONE channel.  renderGray(g) is the green channel of render() of the frame B = G = R = g, byte for byte, at 8 and 16 bits:
+// one 2-D upload of a sample per pixel, the frame's tiles through gather_gray_kernel, compose_gray_kernel, one 2-D download of a sample per output pixel; nothing is
+// replicated or picked apart on the host.  A single part on the compute stream; progress as render() reports it, ceil(N * steps / batchSize) batches.
+bool Img2Img::renderGray(const Image& src, Image& dst) { return runGray(&src, &dst, 1, -1, "renderGray", true); }
+
+// renderGray() with the canvas resized to dst.rows x dst.cols: compose_canvas_gray_kernel (one fp32 plane) and resample_gray_kernel; the green channel of
+// renderResized() of the replicated frame.  At the scaled size it is renderGray().
+bool Img2Img::renderGrayResized(const Image& src, Image& dst, ResizeFilter filter) { return runGray(&src, &dst, 1, filter_id(filter), "renderGrayResized", true); }
+
+// Gray frames through renderSequence()'s pipeline (rolling when a BGR sequence of the size rolls): 8-bit frames of one size, output i the bytes of the single call
+bool Img2Img::renderSequenceGray(const Image* srcs, Image* dsts, int count) { return runGray(srcs, dsts, count, -1, "renderSequenceGray", false); }
+
+bool Img2Img::renderSequenceGrayResized(const Image* srcs, Image* dsts, int count, ResizeFilter filter) {
+    return runGray(srcs, dsts, count, filter_id(filter), "renderSequenceGrayResized", false);
+}
+
+// single: one frame on the compute stream with progress (8 or 16 bits); else the sequence pipeline (8 bits, no progress).  The refusals come in the order of
+// rgba_check(): depth, the first frame's size, the target, then per frame its size, its pointers and steps, then the grid.
+bool Img2Img::runGray(const Image* srcs, Image* dsts, int count, int resizeFilter, const char* who, bool single) {
+    return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
+    if (count <= 0) return true;
+    if (!srcs || !dsts) { W2X_LOG_AS(who, error, "No frames given."); return false; }
+    const int rows = srcs[0].rows, cols = srcs[0].cols, s = impl->cfg.scaling, depth = srcs[0].depth;
+    if (single) {
+        if ((depth != 8 && depth != 16) || dsts[0].depth != depth) { W2X_LOG_AS(who, error, "Input and output images must both be 8-bit or both 16-bit."); return false; }
+    } else {
+        for (int i = 0; i < count; ++i) if (srcs[i].depth != 8 || dsts[i].depth != 8) { W2X_LOG_AS(who, error, std::string(who) + " takes 8-bit frames (16-bit images go through renderGray())."); return false; }
+    }
+    const bool deep16 = depth == 16;
+    const size_t bps = deep16 ? 2 : 1;
+    if (rows <= 0 || cols <= 0) { W2X_LOG_AS(who, error, "Input image is empty or has an invalid step."); return false; }
+    const Impl::Target target = impl->target_size(resizeFilter, dsts[0], rows, cols);
+    const int out_rows = target.rows, out_cols = target.cols;
+    if (resizeFilter >= 0) {
+        const std::string why = impl->resize_problem(rows, cols, out_rows, out_cols, resizeFilter);
+        if (!why.empty()) { W2X_LOG_AS(who, error, why); return false; }
+    }
+    for (int i = 0; i < count; ++i) {
+        if (srcs[i].rows != rows || srcs[i].cols != cols) { W2X_LOG_AS(who, error, "Input images must be of one size."); return false; }
+        if (!srcs[i].data || srcs[i].step < (size_t)cols * bps) { W2X_LOG_AS(who, error, "Input image is empty or has an invalid step."); return false; }
+        if (!dsts[i].data || dsts[i].rows != out_rows || dsts[i].cols != out_cols || dsts[i].step < (size_t)out_cols * bps) {
+            W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(out_cols) + "x" + std::to_string(out_rows) + ".");
+            return false;
+        }
+    }
+    TileGrid grid;
+    if (const std::string why = impl->frame_grid(rows, cols, grid); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
+    const StripPlan sp = strip_plan(grid, cols * s, impl->plan.Tout, 0, 1);
+    const size_t in_step = Impl::gray_step(cols, deep16), out_step = Impl::gray_step(out_cols, deep16);
+    if (single) {
+        impl->ensure(impl->d_frame, impl->frame_cap, in_step * rows);
+        impl->ensure(impl->d_out, impl->out_cap, out_step * out_rows);
+    } else impl->sequence_buffers(in_step * rows, out_step * out_rows);
+    impl->deep = false;
+    impl->last_rows = impl->last_cols = 0;   // (d_frame / d_out hold one plane: not replayed by benchResident / residentOutput / profileFrame)
+    impl->sequence_slots(grid, sp);
+    impl->one_part_stale = false;
+    impl->job.kind = Impl::Job::GRAY; impl->job.gray.deep = deep16;
+    if (target.resized) impl->job_resize(rows, cols, out_rows, out_cols, resizeFilter, 1);
+    auto up = [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dev, in_step, srcs[i].data, srcs[i].step, (size_t)cols * bps, rows, hipMemcpyHostToDevice, on)); };
+    auto down = [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dsts[i].data, dsts[i].step, dev, out_step, (size_t)out_cols * bps, out_rows, hipMemcpyDeviceToHost, on)); };
+    if (single) {
+        hipStream_t stream = impl->stream;
+        up(0, impl->d_frame, stream);
+        hipAssert(hipEventRecord(impl->ev0, stream));
+        impl->run_frame(rows, cols, grid, true, sp);
+        hipAssert(hipEventRecord(impl->ev1, stream));
+        down(0, impl->d_out, stream);
+        hipAssert(hipStreamSynchronize(stream));
+        hipAssert(hipEventElapsedTime(&impl->last_ms, impl->ev0, impl->ev1));
+        return true;
+    }
+    impl->last_ms = impl->run_sequence(count, rows, cols, grid, sp, up, down) / count;
     return true;
     });
 }

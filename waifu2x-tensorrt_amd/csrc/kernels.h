@@ -392,6 +392,32 @@ struct ResampleRgbaParams {
     int uniform = 0; unsigned alpha_value = 255;
 };
 hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s);
+// Gray frames (renderGray; k_gray.hip): one sample per pixel on both sides, the result the green channel of the BGR path on B = G = R = g.
+// gather_gray_kernel: gather_kernel's tiles (same slots, replicate padding, TTA source index) from a one-sample frame: pixel (a, a, a, 0),
+// a = u8 * fl32(1/255) (deep: u16 * fl32(1/65535)); step in bytes.
+struct GatherGrayParams {
+    const uint8_t* frame = nullptr; int rows = 0, cols = 0; size_t step = 0;
+    int deep = 0;
+    void* out = nullptr; int fp32 = 0;
+    const TileSlot* slots = nullptr;
+    int B = 0, T = 0;
+};
+hipError_t launch_gather_gray(const GatherGrayParams& p, hipStream_t s);
+// compose_gray_kernel: compose_kernel over the whole canvas of p (x0..y1 unused) on the green channel alone: p.dst holds one sample per pixel (deep: u16),
+// p.dst_step bytes per row.  compose_canvas_gray_kernel: the same green sums unquantised as one fp32 plane canvas[Y][X] of outH x outW.
+hipError_t launch_compose_gray(const ComposeParams& p, hipStream_t s);
+hipError_t launch_compose_canvas_gray(const ComposeParams& p, float* canvas, hipStream_t s);
+// resample_gray_kernel: resample_kernel's resize (same tap tables, same rows_max, same accumulation) of that one plane, quantised sat(rint(x * 255))
+// (deep: 65535) and stored one sample per pixel into dst (dst_step bytes per row)
+struct ResampleGrayParams {
+    const float* canvas = nullptr; int inW = 0, inH = 0;
+    uint8_t* dst = nullptr; size_t dst_step = 0; int deep = 0;
+    int outW = 0, outH = 0;
+    const int* fx = nullptr; const float* wx = nullptr; int kx = 0;
+    const int* fy = nullptr; const float* wy = nullptr; int ky = 0;
+    int rows_max = 0;
+};
+hipError_t launch_resample_gray(const ResampleGrayParams& p, hipStream_t s);
 // k_resample.hip resample_yuv_kernel: resample_kernel's resize of the fp32 RGB canvas (same tap tables, same rows_max) with compose_yuv_kernel's
 // encoding behind it instead of the BGR quantisation: the resized R, G, B clamped to [0, 1] and written as YUV 4:2:0 planes of outH x outW
 // (dst.rows x dst.cols), Y per pixel, Cb / Cr of the RGB filtered (1/4, 1/2, 1/4) x (1/2, 1/2) onto each chroma site (renderYuvResized)

@@ -242,6 +242,16 @@ SYMBOLS = {
     "w2x_debug_set": (_I, [_S, _I]),
 }
 EXPORTED_SYMBOLS = list(SYMBOLS)
+# The gray entries of include/w2x/c_api_gray.h, in the row format of SYMBOLS and declared by lib() in the same loop.  A table of their own, not rows of SYMBOLS:
+# the golden call log (tests/golden/binding_calls.json) pins SYMBOLS / EXPORTED_SYMBOLS and the names of c_api.h to each other.
+GRAY_SYMBOLS = {
+    "w2x_render_gray": (_I, _FRAME + [_P, _Z]),
+    "w2x_render_gray16": (_I, _FRAME + [_P, _Z]),
+    "w2x_render_gray_resized": (_I, _FRAME + [_P, _I, _I, _Z, _I]),
+    "w2x_render_gray16_resized": (_I, _FRAME + [_P, _I, _I, _Z, _I]),
+    "w2x_render_sequence_gray": (_I, _FRAME + [_P, _Z, _I]),
+    "w2x_render_sequence_gray_resized": (_I, _FRAME + [_P, _I, _I, _Z, _I, _I]),
+}
 _lib = None
 
 
@@ -254,7 +264,7 @@ def lib():
         raise W2xError(f"{lib_path} is missing - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "or `make -C waifu2x-tensorrt_amd` (there is no CPU fallback)")
     L = C.CDLL(lib_path)
-    for name, (restype, argtypes) in SYMBOLS.items():
+    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -451,6 +461,76 @@ class Img2Img:
             return self._L.w2x_render_sequence_rgba_resized(self._h, _pointers(fs), r, c, c * 4, _pointers(os_, len(fs)), rows, cols, cols * 4, len(fs), *flags, fid)
         return self._packed_sequence(frames, 4, (rows, cols, 4), outs, pinned, "outs must be packed uint8 [rows, cols, 4] arrays of the output size", run,
                                      "render_sequence_rgba failed")
+
+    @staticmethod
+    def _gray_ok(a, error, shape=None, dtypes=(np.uint8, np.uint16), empty_ok=False):
+        """a gray frame: a 2-D array of one of `dtypes` with packed samples (rows may be padded), of `shape` when given; else ValueError(error)"""
+        ok = isinstance(a, np.ndarray) and a.ndim == 2 and a.dtype in dtypes and (shape is None or a.shape == tuple(shape)) and (
+            (empty_ok and not a.size) or (a.strides[1] == a.itemsize and a.strides[0] > 0))
+        if not ok:
+            raise ValueError(error)
+
+    def render_gray(self, gray: np.ndarray, dst: np.ndarray | None = None):
+        """render() on a gray frame, a 2-D uint8 or uint16 array (w2x_render_gray / w2x_render_gray16): the green channel of render() of the frame
+        B = G = R = gray, byte for byte, with one sample per pixel travelling each way.  Rows may be padded, as in render().  With dst=None returns the
+        [rows * s, cols * s] array or raises; with dst returns a bool."""
+        self._gray_ok(gray, "gray must be a 2-D uint8 (or uint16) array with packed samples")
+        s = self._scaling
+        out = np.empty((gray.shape[0] * s, gray.shape[1] * s), gray.dtype) if dst is None else None
+        dst = out if dst is None else dst
+        self._gray_ok(dst, "dst must be a 2-D array of the frame's sample type with packed samples", dtypes=(gray.dtype,), empty_ok=True)
+        if s and dst.shape != (gray.shape[0] * s, gray.shape[1] * s):      # (never loaded: as in render())
+            self._refuse("renderGray", f"Output image has invalid size: expected {gray.shape[1] * s}x{gray.shape[0] * s}.")
+            return False
+        fn = self._L.w2x_render_gray if gray.itemsize == 1 else self._L.w2x_render_gray16
+        return self._finish(fn(self._h, _data(gray), gray.shape[0], gray.shape[1], gray.strides[0], _data(dst), dst.strides[0]), out, "render_gray failed")
+
+    def render_gray_resized(self, gray: np.ndarray, size, filter: str = "bicubic", dst: np.ndarray | None = None):
+        """render_gray() with the output resized on the device to size = (rows, cols), each in [input dim, input dim * scaling] (w2x_render_gray_resized /
+        w2x_render_gray16_resized): the green channel of render_resized() of the replicated frame.  With dst=None returns the array or raises; with dst a bool."""
+        self._gray_ok(gray, "gray must be a 2-D uint8 (or uint16) array with packed samples")
+        rows, cols = int(size[0]), int(size[1])
+        fid = _filter_id(filter)
+        out = np.empty((max(rows, 0), max(cols, 0)), gray.dtype) if dst is None else None
+        dst = out if dst is None else dst
+        # (an empty target: refused by the library)
+        self._gray_ok(dst, "dst must be a 2-D array of the target size and the frame's sample type with packed samples", shape=(max(rows, 0), max(cols, 0)), dtypes=(gray.dtype,), empty_ok=True)
+        fn = self._L.w2x_render_gray_resized if gray.itemsize == 1 else self._L.w2x_render_gray16_resized
+        return self._finish(fn(self._h, _data(gray), gray.shape[0], gray.shape[1], gray.strides[0], _data(dst), rows, cols, dst.strides[0], fid), out, "render_gray_resized failed")
+
+    def render_sequence_gray(self, frames, *, size=None, filter: str = "bicubic", outs=None, pinned: bool = False):
+        """Equally sized 2-D uint8 gray frames with upload / compute / download overlapped (w2x_render_sequence_gray); with size = (rows, cols) every frame is
+        resized like render_gray_resized() (w2x_render_sequence_gray_resized).  Output i is the bytes of the single-frame call on frame i.  The frames share
+        one row stride (rows may be padded); outs / pinned as in render_sequence()."""
+        if len(frames) == 0:
+            return []
+        fid = _filter_id(filter)
+        for f in frames:
+            if isinstance(f, np.ndarray) and f.ndim == 2 and f.dtype == np.uint16:
+                raise ValueError("a gray sequence takes 8-bit frames (16-bit frames go through render_gray())")
+            self._gray_ok(f, "frames must be 2-D uint8 arrays with packed samples", dtypes=(np.uint8,))
+            if f.shape != frames[0].shape or f.strides[0] != frames[0].strides[0]:
+                raise ValueError("frames must be 2-D uint8 arrays of one size and one row stride")
+        s = self._scaling
+        r, c = frames[0].shape
+        step = frames[0].strides[0]
+        rows, cols = (r * s, c * s) if size is None else (int(size[0]), int(size[1]))
+        out_shape = (max(rows, 0), max(cols, 0))
+
+        def alloc(host):
+            buf = self.alloc_host(out_shape) if host else np.empty(out_shape, np.uint8)
+            return buf, buf
+
+        def check(o):
+            self._gray_ok(o, "outs must be packed 2-D uint8 arrays of the output size", shape=out_shape, dtypes=(np.uint8,), empty_ok=True)
+            if o.size and o.strides[0] != cols:
+                raise ValueError("outs must be packed 2-D uint8 arrays of the output size")
+
+        def run(fs, os_):
+            if size is None:
+                return self._L.w2x_render_sequence_gray(self._h, _pointers(fs), r, c, step, _pointers(os_, len(fs)), cols, len(fs))
+            return self._L.w2x_render_sequence_gray_resized(self._h, _pointers(fs), r, c, step, _pointers(os_, len(fs)), rows, cols, cols, len(fs), fid)
+        return self._sequence(frames, outs, pinned, alloc, np.copy, run, "render_sequence_gray failed", check)
 
     def alpha_bleed_device(self, bgra: np.ndarray, radius: int) -> np.ndarray:
         """Test hook (w2x_alpha_bleed_device): the device bleed alone on a uint8 [rows, cols, 4] BGRA frame -> the [rows, cols, 3] BGR frame the tiles are read from"""
