@@ -1,12 +1,16 @@
-"""The refusals of the BGR, YUV and sharded entry points (engine.cpp) that the C entries can reach, pinned word for word, and one interleaving of the frame
+"""The refusals of the BGR, YUV, gray and sharded entry points (engine.cpp) that the C entries can reach, pinned word for word, and one interleaving of the frame
 formats on one engine.
 
 Every entry point checks its arguments in a fixed order and logs one "[who@line] text" error through the message callback; the table below holds, per
 (call, bad argument), the exact text and `who`, and per family cases with two things wrong at once, which pin the order.  The calls go through the C entries
-(the Python binding checks shapes itself and would get there first).  RGBA refusals are asserted in test_gpu_rgba.py and test_gpu_rgba_resize.py.
+(the Python binding checks shapes itself and would get there first).  RGBA refusals are asserted in test_gpu_rgba.py and test_gpu_rgba_resize.py; here
+only the order of the RGBA checks is pinned (two_wrong), next to the order of the gray ones.
 Not reachable through the C ABI, which fills both images of a call from one set of arguments and refuses null frame lists itself, and so not in the table:
 a depth that differs between input and output, "... takes 8-bit frames", "No frames given.", the frames of a sequence differing in size, depth or layout, a
-resized YUV frame of another layout than I420; the two tile-grid refusals need a model whose scaling differs from the load's.
+resized YUV frame of another layout than I420; the two tile-grid refusals need a model whose scaling differs from the load's.  Of the gray calls
+(include/w2x/c_api_gray.h) the same holds: "Input and output images must both be 8-bit or both 16-bit." (one entry per depth fills both images),
+"... takes 8-bit frames (16-bit images go through renderGray()).", "No frames given.", "Input images must be of one size." and the two tile-grid refusals
+are out of the ABI's reach, and so is the engine's "Unknown resize filter.": the C entry refuses an unknown filter under its own name before the engine is asked.
 
 The small Swin graph: batch 2, tile 64, scale 2, 40 x 60 frames (one tile)."""
 import ctypes as C
@@ -50,6 +54,12 @@ class Calls:
         self.yuv = (rng.integers(16, 236, (ROWS, COLS), dtype=np.uint8), rng.integers(16, 241, (ROWS // 2, COLS // 2), dtype=np.uint8),
                     rng.integers(16, 241, (ROWS // 2, COLS // 2), dtype=np.uint8))
         self.yuv_out = (np.empty((ROWS * S, COLS * S), np.uint8), np.empty((ROWS, COLS), np.uint8), np.empty((ROWS, COLS), np.uint8))
+        self.gray8 = np.ascontiguousarray(self.bgr[:, :, 1])
+        self.gray_16 = self.gray8.astype(np.uint16) * 257
+        self.gray_out = np.empty((ROWS * S, COLS * S), np.uint8)
+        self.gray_out16 = np.empty((ROWS * S, COLS * S), np.uint16)
+        self.bgra = rng.integers(0, 256, (ROWS, COLS, 4), dtype=np.uint8)
+        self.bgra_out = np.empty((ROWS * S, COLS * S, 4), np.uint8)
 
     def render(self, fn="w2x_render", **k):
         a = dict(src=self.bgr.ctypes.data, rows=ROWS, cols=COLS, sstep=COLS * 3, dst=self.out.ctypes.data, dstep=COLS * S * 3); a.update(k)
@@ -121,6 +131,59 @@ class Calls:
         a = self._yuv_args(k, 2)
         return bool(self.L.w2x_render_sequence_yuv_resized(self.h, a["sp"], a["ss"], a["rows"], a["cols"], a["sbits"], a["dp"], a["ds"], a["drows"], a["dcols"], a["dbits"], 2,
                                                            a["matrix"], a["range"], a["filter"]))
+
+    # gray frames (c_api_gray.h): the green plane of the BGR frame, 8 and 16 bits
+    def gray(self, fn="w2x_render_gray", **k):
+        a = dict(src=self.gray8.ctypes.data, rows=ROWS, cols=COLS, sstep=COLS, dst=self.gray_out.ctypes.data, dstep=COLS * S); a.update(k)
+        return bool(getattr(self.L, fn)(self.h, a["src"], a["rows"], a["cols"], a["sstep"], a["dst"], a["dstep"]))
+
+    def gray16(self, **k):
+        a = dict(src=self.gray_16.ctypes.data, sstep=COLS * 2, dst=self.gray_out16.ctypes.data, dstep=COLS * S * 2); a.update(k)
+        return self.gray("w2x_render_gray16", **a)
+
+    def gray_resized(self, fn="w2x_render_gray_resized", **k):
+        a = dict(src=self.gray8.ctypes.data, rows=ROWS, cols=COLS, sstep=COLS, dst=self.gray_out.ctypes.data, drows=50, dcols=70, dstep=70, filter=0); a.update(k)
+        return bool(getattr(self.L, fn)(self.h, a["src"], a["rows"], a["cols"], a["sstep"], a["dst"], a["drows"], a["dcols"], a["dstep"], a["filter"]))
+
+    def gray16_resized(self, **k):
+        a = dict(src=self.gray_16.ctypes.data, sstep=COLS * 2, dst=self.gray_out16.ctypes.data, dstep=70 * 2); a.update(k)
+        return self.gray_resized("w2x_render_gray16_resized", **a)
+
+    def gray_sequence(self, srcs=None, dsts=None, **k):
+        a = dict(rows=ROWS, cols=COLS, sstep=COLS, dstep=COLS * S); a.update(k)
+        srcs = [self.gray8.ctypes.data] * 2 if srcs is None else srcs
+        dsts = [self.gray_out.ctypes.data] * 2 if dsts is None else dsts
+        return bool(self.L.w2x_render_sequence_gray(self.h, (C.c_void_p * len(srcs))(*srcs), a["rows"], a["cols"], a["sstep"], (C.c_void_p * len(dsts))(*dsts), a["dstep"], len(srcs)))
+
+    def gray_sequence_resized(self, srcs=None, dsts=None, **k):
+        a = dict(rows=ROWS, cols=COLS, sstep=COLS, drows=50, dcols=70, dstep=70, filter=1); a.update(k)
+        srcs = [self.gray8.ctypes.data] * 2 if srcs is None else srcs
+        dsts = [self.gray_out.ctypes.data] * 2 if dsts is None else dsts
+        return bool(self.L.w2x_render_sequence_gray_resized(self.h, (C.c_void_p * len(srcs))(*srcs), a["rows"], a["cols"], a["sstep"], (C.c_void_p * len(dsts))(*dsts),
+                                                            a["drows"], a["dcols"], a["dstep"], len(srcs), a["filter"]))
+
+    # RGBA frames: only the order of their checks is pinned here (two_wrong)
+    def rgba(self, **k):
+        a = dict(src=self.bgra.ctypes.data, rows=ROWS, cols=COLS, sstep=COLS * 4, dst=self.bgra_out.ctypes.data, dstep=COLS * S * 4, bleed=2, skip=0); a.update(k)
+        return bool(self.L.w2x_render_rgba(self.h, a["src"], a["rows"], a["cols"], a["sstep"], a["dst"], a["dstep"], a["bleed"], a["skip"]))
+
+    def rgba_resized(self, **k):
+        a = dict(src=self.bgra.ctypes.data, rows=ROWS, cols=COLS, sstep=COLS * 4, dst=self.bgra_out.ctypes.data, drows=50, dcols=70, dstep=70 * 4, bleed=2, skip=0, filter=0); a.update(k)
+        return bool(self.L.w2x_render_rgba_resized(self.h, a["src"], a["rows"], a["cols"], a["sstep"], a["dst"], a["drows"], a["dcols"], a["dstep"], a["bleed"], a["skip"], a["filter"]))
+
+    def rgba_sequence(self, srcs=None, dsts=None, **k):
+        a = dict(rows=ROWS, cols=COLS, sstep=COLS * 4, dstep=COLS * S * 4, bleed=2, skip=0); a.update(k)
+        srcs = [self.bgra.ctypes.data] * 2 if srcs is None else srcs
+        dsts = [self.bgra_out.ctypes.data] * 2 if dsts is None else dsts
+        return bool(self.L.w2x_render_sequence_rgba(self.h, (C.c_void_p * len(srcs))(*srcs), a["rows"], a["cols"], a["sstep"], (C.c_void_p * len(dsts))(*dsts), a["dstep"], len(srcs),
+                                                    a["bleed"], a["skip"]))
+
+    def rgba_sequence_resized(self, srcs=None, dsts=None, **k):
+        a = dict(rows=ROWS, cols=COLS, sstep=COLS * 4, drows=50, dcols=70, dstep=70 * 4, bleed=2, skip=0, filter=1); a.update(k)
+        srcs = [self.bgra.ctypes.data] * 2 if srcs is None else srcs
+        dsts = [self.bgra_out.ctypes.data] * 2 if dsts is None else dsts
+        return bool(self.L.w2x_render_sequence_rgba_resized(self.h, (C.c_void_p * len(srcs))(*srcs), a["rows"], a["cols"], a["sstep"], (C.c_void_p * len(dsts))(*dsts),
+                                                            a["drows"], a["dcols"], a["dstep"], len(srcs), a["bleed"], a["skip"], a["filter"]))
 
     def sharded(self, handles=None, **k):
         a = dict(src=self.bgr.ctypes.data, rows=ROWS, cols=COLS, sstep=COLS * 3, dst=self.out.ctypes.data, dstep=COLS * S * 3); a.update(k)
@@ -225,6 +288,42 @@ def table(c):
             (who, lambda f=f: f(drows=50, dcols=121), resize_msg(50, 121)),
             (who, lambda f=f: f(ds=[69, 35, 35]), "Output image has a missing plane or an invalid step."),
         ]
+    # ---- the gray calls: one check list (runGray), every entry under its own name
+    OUT_70x50 = "Output image has invalid size: expected 70x50."
+    g = c.gray8.ctypes.data
+    t += [
+        ("renderGray", lambda: c.gray(rows=0), EMPTY),
+        ("renderGray", lambda: c.gray(cols=-1), EMPTY),
+        ("renderGray", lambda: c.gray(src=None), EMPTY),
+        ("renderGray", lambda: c.gray(sstep=COLS - 1), EMPTY),
+        ("renderGray", lambda: c.gray16(sstep=COLS * 2 - 1), EMPTY),
+        ("renderGray", lambda: c.gray(dst=None), OUT_SIZE),
+        ("renderGray", lambda: c.gray(dstep=COLS * S - 1), OUT_SIZE),
+        ("renderGray", lambda: c.gray16(dstep=COLS * S * 2 - 1), OUT_SIZE),
+        ("renderGrayResized", lambda: c.gray_resized(rows=0), EMPTY),
+        ("renderGrayResized", lambda: c.gray_resized(src=None), EMPTY),
+        ("renderGrayResized", lambda: c.gray_resized(sstep=COLS - 1), EMPTY),
+        ("renderGrayResized", lambda: c.gray16_resized(sstep=COLS * 2 - 1), EMPTY),
+        ("renderGrayResized", lambda: c.gray_resized(drows=39, dcols=60), resize_msg(39, 60)),
+        ("renderGrayResized", lambda: c.gray_resized(drows=80, dcols=121), resize_msg(80, 121)),
+        ("renderGrayResized", lambda: c.gray_resized(drows=0, dcols=0), resize_msg(0, 0)),
+        ("renderGrayResized", lambda: c.gray16_resized(drows=81, dcols=120), resize_msg(81, 120)),
+        ("renderGrayResized", lambda: c.gray_resized(dst=None), OUT_70x50),
+        ("renderGrayResized", lambda: c.gray_resized(dstep=69), OUT_70x50),
+        ("renderGrayResized", lambda: c.gray16_resized(dstep=70 * 2 - 1), OUT_70x50),
+        ("renderGrayResized", lambda: c.gray_resized(drows=ROWS * S, dcols=COLS * S, dstep=COLS * S - 1), OUT_SIZE),      # at the scaled size it is renderGray()
+        ("renderSequenceGray", lambda: c.gray_sequence(rows=0), EMPTY),
+        ("renderSequenceGray", lambda: c.gray_sequence(srcs=[g, None]), EMPTY),
+        ("renderSequenceGray", lambda: c.gray_sequence(sstep=COLS - 1), EMPTY),
+        ("renderSequenceGray", lambda: c.gray_sequence(dsts=[c.gray_out.ctypes.data, None]), OUT_SIZE),
+        ("renderSequenceGray", lambda: c.gray_sequence(dstep=COLS * S - 1), OUT_SIZE),
+        ("renderSequenceGrayResized", lambda: c.gray_sequence_resized(cols=0), EMPTY),
+        ("renderSequenceGrayResized", lambda: c.gray_sequence_resized(drows=39, dcols=70), resize_msg(39, 70)),
+        ("renderSequenceGrayResized", lambda: c.gray_sequence_resized(drows=50, dcols=121), resize_msg(50, 121)),
+        ("renderSequenceGrayResized", lambda: c.gray_sequence_resized(srcs=[None, g]), EMPTY),
+        ("renderSequenceGrayResized", lambda: c.gray_sequence_resized(dsts=[c.gray_out.ctypes.data, None]), OUT_70x50),
+        ("renderSequenceGrayResized", lambda: c.gray_sequence_resized(dstep=69), OUT_70x50),
+    ]
     # ---- the sharded entries' frame checks
     t += [
         ("renderSharded", lambda: c.sharded(src=None), EMPTY),
@@ -242,7 +341,7 @@ def table(c):
 
 
 def two_wrong(c):
-    """(who, call, the refusal that wins): two bad arguments each, two cases per family"""
+    """(who, call, the refusal that wins): two bad arguments each, at least two cases per family"""
     y, u, v = (p.ctypes.data for p in c.yuv)
     return [
         ("render", lambda: c.render(src=None, dst=None), EMPTY),
@@ -263,6 +362,31 @@ def two_wrong(c):
         ("renderYuvResized", lambda: c.yuv_resized(dbits=9, drows=39, dcols=60), "YUV frames must have 8 or 10 bits."),
         ("renderSequenceYuvResized", lambda: c.yuv_sequence_resized(matrix=5, drows=39, dcols=60), "Unknown YUV matrix 5."),
         ("renderSequenceYuvResized", lambda: c.yuv_sequence_resized(drows=81, dcols=60, ss=[1, 1, 1]), resize_msg(81, 60)),
+        # gray and RGBA, one order: depth, the first frame's size, the target, per frame its size, its pointers and steps (input before output), the bleed
+        # radius (RGBA), the grid
+        ("renderGray", lambda: c.gray(rows=0, dst=None), EMPTY),
+        ("renderGray", lambda: c.gray(src=None, dst=None), EMPTY),
+        ("renderGray", lambda: c.gray16(sstep=1, dstep=1), EMPTY),
+        ("renderGrayResized", lambda: c.gray_resized(cols=0, drows=39, dcols=60), EMPTY),                                     # the first frame's size before the target
+        ("renderGrayResized", lambda: c.gray_resized(drows=81, dcols=60, dst=None), resize_msg(81, 60)),                      # a null destination with an out-of-range target: the target
+        ("renderGrayResized", lambda: c.gray_resized(src=None, drows=39, dcols=60), resize_msg(39, 60)),
+        ("renderGrayResized", lambda: c.gray16_resized(src=None, dstep=1), EMPTY),
+        ("renderSequenceGray", lambda: c.gray_sequence(srcs=[None, None], dsts=[None, None]), EMPTY),
+        ("renderSequenceGray", lambda: c.gray_sequence(srcs=[c.gray8.ctypes.data, None], dsts=[None, c.gray_out.ctypes.data]), OUT_SIZE),      # frame 0's output before frame 1's input
+        ("renderSequenceGrayResized", lambda: c.gray_sequence_resized(srcs=[None, None], drows=39, dcols=70), resize_msg(39, 70)),
+        ("renderSequenceGrayResized", lambda: c.gray_sequence_resized(rows=-1, drows=39, dcols=70), EMPTY),
+        ("renderSequenceGrayResized", lambda: c.gray_sequence_resized(sstep=1, dstep=1), EMPTY),
+        ("renderRgba", lambda: c.rgba(rows=0, bleed=17), EMPTY),
+        ("renderRgba", lambda: c.rgba(src=None, dst=None), EMPTY),
+        ("renderRgba", lambda: c.rgba(dst=None, bleed=17), OUT_SIZE),                                                         # pointers and steps before the bleed radius
+        ("renderRgbaResized", lambda: c.rgba_resized(cols=0, drows=39, dcols=60), EMPTY),
+        ("renderRgbaResized", lambda: c.rgba_resized(drows=81, dcols=60, dst=None), resize_msg(81, 60)),
+        ("renderRgbaResized", lambda: c.rgba_resized(drows=39, dcols=60, bleed=-1), resize_msg(39, 60)),
+        ("renderRgbaResized", lambda: c.rgba_resized(dstep=70 * 4 - 1, bleed=17), "Output image has invalid size: expected 70x50."),
+        ("renderSequenceRgba", lambda: c.rgba_sequence(srcs=[c.bgra.ctypes.data, None], dsts=[None, c.bgra_out.ctypes.data]), OUT_SIZE),      # frame 0's output before frame 1's input
+        ("renderSequenceRgba", lambda: c.rgba_sequence(srcs=[c.bgra.ctypes.data, None], bleed=17), EMPTY),
+        ("renderSequenceRgbaResized", lambda: c.rgba_sequence_resized(srcs=[None, None], drows=39, dcols=70), resize_msg(39, 70)),
+        ("renderSequenceRgbaResized", lambda: c.rgba_sequence_resized(sstep=1, bleed=17), EMPTY),
         ("renderSharded", lambda: c.sharded(handles=[c.h, c.h], src=None), "renderSharded: the same engine twice."),
         ("renderSharded", lambda: c.sharded(src=None, dst=None), EMPTY),
         ("shardCompute", lambda: c.shard_compute(0, 0, src=None), "Invalid part index."),
@@ -334,7 +458,8 @@ def test_every_entry_refuses_an_engine_that_is_not_loaded(pkg, eng):
         for who, call in [("render", c.render), ("render", c.render16), ("renderStrip", lambda: c.strip(0, 1)), ("renderResized", c.resized), ("renderSequence", c.sequence),
                           ("renderSequenceResized", c.sequence_resized), ("renderYuv", c.yuv_call), ("renderYuv", c.yuv_layout), ("renderSequenceYuv", c.yuv_sequence),
                           ("renderSequenceYuv", c.yuv_sequence_layout), ("renderYuvResized", c.yuv_resized), ("renderSequenceYuvResized", c.yuv_sequence_resized),
-                          ("shardCompute", c.shard_compute)]:
+                          ("renderGray", c.gray), ("renderGray", c.gray16), ("renderGrayResized", c.gray_resized), ("renderGrayResized", c.gray16_resized),
+                          ("renderSequenceGray", c.gray_sequence), ("renderSequenceGrayResized", c.gray_sequence_resized), ("shardCompute", c.shard_compute)]:
             check(pkg, fresh, who, call, NOT_LOADED)
         check(pkg, fresh, "render", lambda: c.render(src=None), NOT_LOADED)                                         # before any argument check
         check(pkg, fresh, "shardCompute", lambda: c.shard_compute(0, 0), NOT_LOADED)
@@ -347,7 +472,7 @@ def test_every_entry_refuses_an_engine_that_is_not_loaded(pkg, eng):
 
 
 def test_formats_interleaved_on_one_engine(pkg, eng):
-    """the frame format of a call does not outlive it: BGR, YUV, RGBA, resized and sequence calls between two equal render() calls.  The successful calls
+    """the frame format of a call does not outlive it: BGR, YUV, RGBA, gray, resized and sequence calls between two equal render() calls.  The successful calls
     are what tests the reset of the job; the two refused ones are turned away before any job is set and only show that a refusal leaves the engine usable."""
     c = Calls(eng)
     rng = np.random.default_rng(11)
@@ -360,7 +485,11 @@ def test_formats_interleaved_on_one_engine(pkg, eng):
         eng.render_sequence_rgba([bgra, bgra], bleed=17)
     small = eng.render_resized(c.bgr, (50, 70))                                                   # 6
     seq = eng.render_sequence([c.bgr, c.bgr[::-1].copy()])                                        # 7
-    last = eng.render(c.bgr)                                                                      # 8
+    gray_frames = [c.gray8, c.gray8[::-1].copy()]
+    gray = eng.render_gray(c.gray8)                                                               # 8
+    gray_small = eng.render_gray_resized(c.gray8, (50, 70))                                       # 9
+    gray_seq = eng.render_sequence_gray(gray_frames)                                              # 10
+    last = eng.render(c.bgr)                                                                      # 11
     assert np.array_equal(first, last)
     assert np.array_equal(seq[0], first) and not np.array_equal(seq[1], first)
     assert eng.bench_resident(2) > 0
@@ -370,3 +499,8 @@ def test_formats_interleaved_on_one_engine(pkg, eng):
     assert all(np.array_equal(a, b) for a, b in zip(yuv, eng.render_yuv(*c.yuv)))
     assert np.array_equal(rgba, eng.render_rgba_resized(bgra, (50, 70), bleed=2))
     assert np.array_equal(small, eng.render_resized(c.bgr, (50, 70)))
+    assert np.array_equal(gray, eng.render_gray(c.gray8))
+    assert np.array_equal(gray_small, eng.render_gray_resized(c.gray8, (50, 70)))
+    alone = eng.render_sequence_gray(gray_frames)
+    assert len(gray_seq) == 2 and all(np.array_equal(a, b) for a, b in zip(gray_seq, alone))
+    assert np.array_equal(gray_seq[0], gray) and not np.array_equal(gray_seq[1], gray)

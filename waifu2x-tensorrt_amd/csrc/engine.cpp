@@ -339,14 +339,16 @@ struct Img2Img::Impl {
     uint8_t* d_alpha = nullptr; size_t alpha_cap = 0;
     unsigned* d_minmax = nullptr; unsigned* h_minmax = nullptr;
     hipEvent_t ev_minmax = nullptr;
-    struct RgbaJob { int bleed = 0; bool skip = false; };
+    // (alpha_slot0, uniform, value: what rgba_frame() found out about the frame's alpha plane, for the launches that end the frame)
+    struct RgbaJob { int bleed = 0; bool skip = false; size_t alpha_slot0 = 0; bool uniform = false; unsigned value = 255; };
     // Gray frames (renderGray, renderGrayResized, renderSequenceGray*): d_frame / d_out hold ONE sample per pixel (8 or 16 bits, rows padded to 16 bytes:
     // gray_step), the gather launch is gather_gray_kernel, the frame ends with compose_gray_kernel - resized with compose_canvas_gray_kernel (one fp32 plane) and
     // resample_gray_kernel.  The sample depth is the job's, not `deep`: nothing of a gray call is replayable.
     struct GrayJob { bool deep = false; };
-    // The kind of frame the running entry point renders: what run_frame(), run_rolling_frame(), the gather of run_passes() and the key of the captured
-    // passes branch on.  The default is a plain BGR frame, not resized.  Set once per entry-point family (renderPart / runSequence through job_resize(),
-    // runSequenceYuv, rgba_begin()); entry() puts the default back on every exit, exceptions included.  `rs`: the tap tables of a resized frame's target, else null.
+    // The kind of frame the running entry point renders.  Only the block "the frame formats" below branches on it: the key of the captured passes, the
+    // gather (gather_tiles), the end of a frame (finish_frame), the device layout of a frame, the slot tables of a call.  The default is a plain BGR frame, not
+    // resized.  The kind is set in three places - runSequenceYuv, the RGBA calls (rgba_call), runGray - between the call's checks and run_call();
+    // entry() puts the default back on every exit, exceptions included.  `rs`: the tap tables of a resized frame's target (job_resize), else null.
     // (`deep` is not part of it: it describes the replayable frame in d_frame / d_out and outlives the call.)
     struct Job {
         enum Kind { BGR, YUV, RGBA, GRAY } kind = BGR;
@@ -357,10 +359,6 @@ struct Img2Img::Impl {
     };
     Job job;
     struct JobScope { Impl* im; ~JobScope() { im->job = Job{}; } };
-    // the sample format in the key of a captured pass: 0 / 1 BGR of 8 / 16 bits, 2 .. 49 YuvJob::key, kRgbaKey, kGrayKey / kGrayKey + 1 gray of 8 / 16 bits
-    int sample_format() const {
-        return job.kind == Job::GRAY ? kGrayKey + (job.gray.deep ? 1 : 0) : job.kind == Job::RGBA ? kRgbaKey : job.kind == Job::YUV ? job.yuv.key : deep ? 1 : 0;
-    }
     std::vector<void*> pinned;
     std::vector<void*> host_allocs;     // allocHost(): page-locked buffers handed to the caller
     std::vector<TileSlot> h_slots;
@@ -986,19 +984,13 @@ struct Img2Img::Impl {
         cap = bytes;
     }
 
-    // device part of one frame: gather -> network per batch -> compose.  Frame must already be in d_frame.
-    void run_frame(int rows, int cols, const TileGrid& grid, bool report, const StripPlan& sp) {
-        if (job.kind == Job::RGBA) { rgba_frame(rows, cols, grid, report, nullptr); return; }                  // an RGBA frame of a sequence (renderSequenceRgba)
+    // device part of one frame: gather -> network per batch -> the format's end of a frame (finish_frame).  Frame must already be in d_frame.
+    // `started` (a single-frame call's ev0): recorded in front of the passes - of an RGBA frame behind its bleed, whose two-phase schedule is rgba_frame()
+    void run_frame(int rows, int cols, const TileGrid& grid, bool report, const StripPlan& sp, hipEvent_t started = nullptr) {
+        if (job.kind == Job::RGBA) { rgba_frame(rows, cols, grid, sp, report, started); return; }
+        if (started) hipAssert(hipEventRecord(started, stream));
         run_passes(rows, cols, sp.tile_count, 0, report, 0, true);
-        const bool yuv = job.kind == Job::YUV;
-        if (job.kind == Job::GRAY) {                                                      // a gray frame (renderGray / renderGrayResized)
-            if (job.rs) { compose_canvas_gray(rows, cols, grid, stream); resample_gray(stream); }
-            else compose_gray(rows, cols, grid, stream);
-            return;
-        }
-        if (job.rs) { compose_canvas(rows, cols, grid, stream); if (yuv) resample_yuv(stream); else resample(stream); return; }   // a resized frame (renderResized / renderYuvResized)
-        if (yuv) { compose_yuv(rows, cols, grid, stream); return; }                       // a YUV frame (renderYuv)
-        compose_rect(rows, cols, grid, sp.x0, sp.x1, 0, 0, sp.first_tile);
+        finish_frame(rows, cols, grid, sp, stream, nullptr, nullptr);
     }
 
     // One frame of a ROLLING sequence (benchResident, renderSequence): frames of one size, one after the other, whose passes all run as two tile groups.
@@ -1027,19 +1019,7 @@ struct Img2Img::Impl {
         hipAssert(hipEventRecord(ev_g0[which], stream));
         hipStream_t s2 = gstream[0];
         hipAssert(hipStreamWaitEvent(s2, ev_g0[which], 0));
-        const bool yuv = job.kind == Job::YUV, gray = job.kind == Job::GRAY;
-        if (job.rs) {   // a resized frame: the canvas compose is the slab's last reader, the resample the writer of d_out; in order on s2, they share one canvas
-            if (gray) compose_canvas_gray(rows, cols, grid, s2); else compose_canvas(rows, cols, grid, s2);
-            hipAssert(hipEventRecord(ev_cmp[which], s2));
-            if (out_free) hipAssert(hipStreamWaitEvent(s2, out_free, 0));
-            if (gray) resample_gray(s2); else if (yuv) resample_yuv(s2); else resample(s2);
-            return;
-        }
-        if (out_free) hipAssert(hipStreamWaitEvent(s2, out_free, 0));     // the frame that last left through this output buffer has been downloaded
-        if (gray) compose_gray(rows, cols, grid, s2);
-        else if (yuv) compose_yuv(rows, cols, grid, s2);
-        else compose_rect(rows, cols, grid, sp.x0, sp.x1, 0, 0, sp.first_tile, s2);
-        hipAssert(hipEventRecord(ev_cmp[which], s2));
+        finish_frame(rows, cols, grid, sp, s2, ev_cmp[which], out_free);
     }
     // after the last frame of a rolling sequence: the first stream waits for the second, so that whatever follows on it sees the sequence done
     void end_rolling() { hipAssert(hipEventRecord(ev_join[0], gstream[0])); hipAssert(hipStreamWaitEvent(stream, ev_join[0], 0)); }
@@ -1085,7 +1065,7 @@ struct Img2Img::Impl {
             const int live = std::max(0, std::min(B, tile_count * steps - bi * B));
             void* const slab_out = (uint8_t*)d_slab + (slab_slot0 + (size_t)bi * B) * slot_bytes;
             GatherParams gp0;
-            gp0.frame = d_frame; gp0.rows = rows; gp0.cols = cols; gp0.step = (size_t)cols * 3 * (deep ? 2 : 1); gp0.deep = deep ? 1 : 0;
+            gp0.frame = d_frame; gp0.rows = rows; gp0.cols = cols; gp0.step = bgr_step(cols, deep); gp0.deep = deep ? 1 : 0;
             gp0.out = tensors[plan.in_tensor]; gp0.slots = d_slots + slots_off + (size_t)bi * B; gp0.B = B; gp0.T = T; gp0.fp32 = plan.elt == 4;
             const int NG = groups;
             struct NgReset { int& r; ~NgReset() { r = 1; } } ng_reset{ng_now};   // also when a launch throws mid-pass
@@ -1105,31 +1085,10 @@ struct Img2Img::Impl {
                 }
             }
             auto group_stream = [&](int grp) { return grp ? gstream[grp - 1] : stream; };
-            auto gather = [&](const GatherParams& gp, hipStream_t gs) {
-                if (job.kind == Job::RGBA) {                          // an RGBA frame (renderRgba): the same tiles from the bled BGR frame or the alpha plane
-                    GatherRgbaParams rp;
-                    rp.bgr = d_bgr; rp.bgr_step = (size_t)cols * 3; rp.alpha = d_alpha; rp.alpha_step = (size_t)cols; rp.rows = rows; rp.cols = cols;
-                    rp.out = gp.out; rp.fp32 = gp.fp32; rp.slots = gp.slots; rp.B = gp.B; rp.T = gp.T;
-                    hipAssert(launch_gather_rgba(rp, gs));
-                    return;
-                }
-                if (job.kind == Job::GRAY) {                          // a gray frame (renderGray): the same tiles from its one plane
-                    GatherGrayParams yp;
-                    yp.frame = d_frame; yp.rows = rows; yp.cols = cols; yp.step = gray_step(cols, job.gray.deep); yp.deep = job.gray.deep ? 1 : 0;
-                    yp.out = gp.out; yp.fp32 = gp.fp32; yp.slots = gp.slots; yp.B = gp.B; yp.T = gp.T;
-                    hipAssert(launch_gather_gray(yp, gs));
-                    return;
-                }
-                if (job.kind != Job::YUV) { hipAssert(launch_gather(gp, gs)); return; }
-                GatherYuvParams yp;                                   // a YUV frame (renderYuv): the same tiles from its planes
-                yp.src = yuv_layout(d_frame, rows, cols, job.yuv.in_bits, job.yuv.in_layout); yp.k = job.yuv.in;
-                yp.out = gp.out; yp.fp32 = gp.fp32; yp.slots = gp.slots; yp.B = gp.B; yp.T = gp.T;
-                hipAssert(launch_gather_yuv(yp, gs));
-            };
             auto gather_group = [&](int grp, hipStream_t gs) {       // the group's tiles at the start of its part of the arena
                 GatherParams gp = gp0;
                 gp.out = group_ptr(tensors[plan.in_tensor], grp); gp.slots = gp0.slots + (size_t)first[grp]; gp.B = first[grp + 1] - first[grp];
-                gather(gp, gs);
+                gather_tiles(gp, gs);
             };
             const LiveExt* const ext0 = d_live && slots_off + (size_t)(bi + 1) * B <= live_stride ? d_live + slots_off + (size_t)bi * B : nullptr;   // this pass's slots in op 0's table
             auto network_group = [&](int grp, hipStream_t gs) { run_network((uint8_t*)slab_out + (size_t)first[grp] * slot_bytes, first[grp + 1] - first[grp], grp, gs, ext0 ? ext0 + first[grp] : nullptr); };
@@ -1139,7 +1098,7 @@ struct Img2Img::Impl {
             auto run_pass = [&] {
                 if (!split) {
                     stamp_begin(3, 0);
-                    gather(gp0, stream);
+                    gather_tiles(gp0, stream);
                     stamp_end();
                     run_network(slab_out, live, -1, nullptr, ext0);
                     return;
@@ -1159,8 +1118,7 @@ struct Img2Img::Impl {
             auto run_eager = [&] { if (per_group) { fork(); for (int grp = 0; grp < NG; ++grp) run_group(grp); if (!no_join) join(); } else { if (rolling && gstream[0]) { join(); } run_pass(); } };
             if (!graphable) run_eager();
             else {
-                // (an RGBA pass reads d_bgr / d_alpha, never d_frame: its graphs do not depend on which frame buffer of a sequence is current)
-                const GraphKey key{job.kind == Job::RGBA ? (const void*)d_bgr : (const void*)d_frame, d_slots + slots_off + (size_t)bi * B, slab_out, arena_base, rows, cols, live, sample_format()};
+                const GraphKey key{pass_source(), d_slots + slots_off + (size_t)bi * B, slab_out, arena_base, rows, cols, live, sample_format()};
                 auto replay = [&](const PassGraphs& pg) {
                     if (pg.n == 1) { if (rolling && gstream[0]) join(); hipAssert(hipGraphLaunch(pg.g[0], stream)); return; }   // (a whole-arena pass inside a rolling sequence: the other stream's group first)
                     fork();
@@ -1217,7 +1175,7 @@ struct Img2Img::Impl {
     // global tile `first_tile`
     void compose_rect(int rows, int cols, const TileGrid& grid, int x0, int x1, int y0, int y1, long first_tile, hipStream_t on = nullptr) {
         ComposeParams cp = compose_base(rows, cols, grid);
-        cp.dst = d_out; cp.dst_step = (size_t)cols * cfg.scaling * 3 * (deep ? 2 : 1); cp.deep = deep ? 1 : 0;
+        cp.dst = d_out; cp.dst_step = bgr_step(cp.outW, deep); cp.deep = deep ? 1 : 0;
         cp.x0 = x0; cp.x1 = x1; cp.y0 = y0; cp.y1 = y1; cp.first_tile = first_tile;
         stamp_begin(4, 0);
         hipAssert(launch_compose(cp, on ? on : stream));
@@ -1235,40 +1193,185 @@ struct Img2Img::Impl {
         cp.ramp_x = d_rampx; cp.ramp_y = d_rampy; cp.tta = cfg.tta ? 1 : 0; cp.tta_bug_compat = cfg.ttaBugCompat ? 1 : 0;
         return cp;
     }
-
-    // resized frames (job.rs set): the whole canvas of the frame's tiles (one part, slot 0 = tile 0) as fp32 planes into d_canvas, then the resize of
-    // d_canvas into d_out (rs->outW x rs->outH, packed)
-    void compose_canvas(int rows, int cols, const TileGrid& grid, hipStream_t on) {
-        hipAssert(launch_compose_canvas(compose_base(rows, cols, grid), d_canvas, on));
+    // what the four resample launches share: the canvas, its size and the target's, and the tap tables of job.rs
+    template <class Params> void resample_base(Params& rp) const {
+        const ResizeTables* const rs = job.rs;
+        rp.canvas = d_canvas; rp.inW = rs->inW; rp.inH = rs->inH;
+        rp.outW = rs->outW; rp.outH = rs->outH;
+        rp.fx = rs->fx; rp.wx = rs->wx; rp.kx = rs->kx; rp.fy = rs->fy; rp.wy = rs->wy; rp.ky = rs->ky; rp.rows_max = rs->rows_max;
     }
-    // YUV frames: the whole canvas of the frame's tiles (one part, slot 0 = tile 0) written as the planes of job.yuv.out_layout into d_out
-    void compose_yuv(int rows, int cols, const TileGrid& grid, hipStream_t on) {
-        ComposeYuvParams yp;
-        yp.c = compose_base(rows, cols, grid);
-        yp.dst = yuv_layout(d_out, yp.c.outH, yp.c.outW, job.yuv.out_bits, job.yuv.out_layout); yp.k = job.yuv.out;
-        stamp_begin(4, 0);
-        hipAssert(launch_compose_yuv(yp, on));
-        stamp_end();
-    }
-    // Gray frames: the device layout of the one plane in d_frame / d_out (rows padded to 16 bytes, like the planes of yuv_layout), and the three launches that end a
-    // gray frame - the whole canvas of the frame's tiles (one part, slot 0 = tile 0) as samples into d_out, or as one fp32 plane into d_canvas and its resize into d_out
+    // The device layouts the formats are made of.  BGR: packed rows.  Gray: one plane, rows padded to 16 bytes like the planes of yuv_layout.  YUV: Y, U, V
+    // (NV12: Y, UV) one after the other, rows padded to 16 bytes (the stores of the compose kernels).
+    static size_t bgr_step(int cols, bool deep16) { return (size_t)cols * 3 * (deep16 ? 2 : 1); }
     static size_t gray_step(int cols, bool deep16) { return ((size_t)cols * (deep16 ? 2 : 1) + 15) / 16 * 16; }
-    void compose_gray(int rows, int cols, const TileGrid& grid, hipStream_t on) {
-        ComposeParams cp = compose_base(rows, cols, grid);
-        cp.dst = d_out; cp.dst_step = gray_step(cp.outW, job.gray.deep); cp.deep = job.gray.deep ? 1 : 0;
-        stamp_begin(4, 0);
-        hipAssert(launch_compose_gray(cp, on));
-        stamp_end();
+    static YuvPlanes yuv_layout(uint8_t* base, int rows, int cols, int bits, int layout) {
+        const size_t bps = bits > 8 ? 2 : 1;
+        const int cw = yuv_chroma_samples(cols, layout), ch = yuv_chroma_rows(rows, layout);
+        YuvPlanes f;
+        f.rows = rows; f.cols = cols; f.bits = bits; f.layout = layout;
+        f.step[0] = ((size_t)cols * bps + 15) / 16 * 16; f.step[1] = f.step[2] = ((size_t)cw * bps + 15) / 16 * 16;
+        f.p[0] = base; f.p[1] = base + f.step[0] * rows; f.p[2] = layout == kYuvNV12 ? nullptr : f.p[1] + f.step[1] * ch;
+        return f;
     }
-    void compose_canvas_gray(int rows, int cols, const TileGrid& grid, hipStream_t on) {
-        hipAssert(launch_compose_canvas_gray(compose_base(rows, cols, grid), d_canvas, on));
+    static int yuv_planes(int layout) { return layout == kYuvNV12 ? 2 : 3; }
+    static size_t yuv_bytes(int rows, int cols, int bits, int layout) {
+        const YuvPlanes f = yuv_layout(nullptr, rows, cols, bits, layout);
+        return f.step[0] * rows + (yuv_planes(layout) - 1) * f.step[1] * yuv_chroma_rows(rows, layout);
     }
-    void resample_gray(hipStream_t on) {
-        ResampleGrayParams rp;
-        resample_base(rp);
-        rp.dst = d_out; rp.dst_step = gray_step(rp.outW, job.gray.deep); rp.deep = job.gray.deep ? 1 : 0;
-        hipAssert(launch_resample_gray(rp, on));
+
+    // ---- The frame formats: what a Job::Kind does at each device step, each step written once with one switch over job.kind.  Outside this block
+    // only the three places that set a job's kind and run_frame()'s hand-off of an RGBA frame name a kind.  A new format is a case in each function here, a
+    // checker and an entry point that sets its job ("Adding a frame format").
+    //
+    // The key of a captured pass: the sample format - 0 / 1 BGR of 8 / 16 bits, 2 .. 49 YuvJob::key, kRgbaKey, kGrayKey / kGrayKey + 1 gray of 8 / 16 bits - and the
+    // buffer the pass's gather reads (an RGBA pass reads d_bgr / d_alpha, never d_frame: its graphs do not depend on which frame buffer of a sequence is current)
+    int sample_format() const {
+        switch (job.kind) {
+            case Job::YUV: return job.yuv.key;
+            case Job::RGBA: return kRgbaKey;
+            case Job::GRAY: return kGrayKey + (job.gray.deep ? 1 : 0);
+            default: return deep ? 1 : 0;
+        }
     }
+    const void* pass_source() const { return job.kind == Job::RGBA ? (const void*)d_bgr : (const void*)d_frame; }
+    // The device layout of a frame: bytes per row and bytes of a rows x cols frame in d_frame, or (`out`) in d_out.  A YUV frame has a step per plane
+    // (yuv_layout); frame_step() gives its Y plane's.
+    size_t frame_step(int cols, bool out) const {
+        switch (job.kind) {
+            case Job::YUV: return yuv_layout(nullptr, 0, cols, out ? job.yuv.out_bits : job.yuv.in_bits, out ? job.yuv.out_layout : job.yuv.in_layout).step[0];
+            case Job::RGBA: return (size_t)cols * 4;
+            case Job::GRAY: return gray_step(cols, job.gray.deep);
+            default: return bgr_step(cols, deep);
+        }
+    }
+    size_t frame_bytes(int rows, int cols, bool out) const {
+        if (job.kind == Job::YUV) return yuv_bytes(rows, cols, out ? job.yuv.out_bits : job.yuv.in_bits, out ? job.yuv.out_layout : job.yuv.in_layout);
+        return frame_step(cols, out) * rows;
+    }
+    // the fp32 planes of a resized frame's canvas
+    int canvas_planes() const { return job.kind == Job::RGBA ? 4 : job.kind == Job::GRAY ? 1 : 3; }
+    // RGBA frames do not roll: d_bgr, d_alpha and d_minmax are single buffers the bleed writes on the compute stream, and in a rolling sequence the second
+    // tile group of frame f would still gather from them while frame f + 1 bleeds into them.  Through run_frame() every pass joins its groups before the
+    // next launch on `stream`, so stream order alone keeps the single buffers (and the one slab and canvas) safe.
+    bool rolls() const { return job.kind != Job::RGBA; }
+    // only BGR frames are what benchResident / residentOutput / profileFrame replay out of d_frame / d_out
+    bool replayable() const { return job.kind == Job::BGR; }
+    // the slot table, the liveness table and the slab the frames of a call share: every tile of the frame in one part, RGBA the 2N schedule (rgba_setup)
+    void call_slots(int rows, int cols, const TileGrid& grid, const StripPlan& sp) {
+        if (job.kind == Job::RGBA) { rgba_setup(rows, cols, grid, job.rgba.skip); return; }
+        const size_t stepCount = pass_slots(sp.tile_count);
+        fill_slots(grid, 0, sp.tile_count, 1, 0, stepCount);
+        upload_slots(grid, stepCount, stepCount);
+        hipAssert(hipStreamSynchronize(stream));
+    }
+    // The gather of a pass (or of one tile group of it): the tiles of gp.slots out of the frame.  `gp` carries the BGR frame; the other formats take its tile side.
+    template <class P> static P tile_side(const GatherParams& gp) { P p; p.out = gp.out; p.fp32 = gp.fp32; p.slots = gp.slots; p.B = gp.B; p.T = gp.T; return p; }
+    void gather_tiles(const GatherParams& gp, hipStream_t gs) {
+        switch (job.kind) {
+            case Job::BGR: hipAssert(launch_gather(gp, gs)); break;
+            case Job::YUV: {                                          // the same tiles from the frame's planes
+                GatherYuvParams p = tile_side<GatherYuvParams>(gp);
+                p.src = yuv_layout(d_frame, gp.rows, gp.cols, job.yuv.in_bits, job.yuv.in_layout); p.k = job.yuv.in;
+                hipAssert(launch_gather_yuv(p, gs));
+                break;
+            }
+            case Job::RGBA: {                                         // from the bled BGR frame or the alpha plane
+                GatherRgbaParams p = tile_side<GatherRgbaParams>(gp);
+                p.bgr = d_bgr; p.bgr_step = (size_t)gp.cols * 3; p.alpha = d_alpha; p.alpha_step = (size_t)gp.cols; p.rows = gp.rows; p.cols = gp.cols;
+                hipAssert(launch_gather_rgba(p, gs));
+                break;
+            }
+            case Job::GRAY: {                                         // from the frame's one plane
+                GatherGrayParams p = tile_side<GatherGrayParams>(gp);
+                p.frame = d_frame; p.rows = gp.rows; p.cols = gp.cols; p.step = gray_step(gp.cols, job.gray.deep); p.deep = job.gray.deep ? 1 : 0;
+                hipAssert(launch_gather_gray(p, gs));
+                break;
+            }
+        }
+    }
+    // The three launches that can end a frame, all over the whole canvas of the frame's tiles (one part, slot 0 = tile 0; BGR: the strip's columns): the canvas
+    // as fp32 planes into d_canvas (RGBA: R, G, B, A - uniform: three; gray: one), the resize of d_canvas into d_out (rs->outW x rs->outH), or the canvas
+    // quantised straight into d_out.  RGBA: colour tiles from slab slot 0, alpha tiles from slot job.rgba.alpha_slot0 (uniform: none, A = value).
+    const void* alpha_tiles() const { return job.rgba.uniform ? nullptr : (const uint8_t*)d_slab + job.rgba.alpha_slot0 * (size_t)plan.Tout * plan.Tout * 4 * plan.elt; }
+    void compose_canvas(int rows, int cols, const TileGrid& grid, hipStream_t on) {
+        const ComposeParams cp = compose_base(rows, cols, grid);
+        switch (job.kind) {
+            case Job::RGBA: {
+                ComposeCanvasRgbaParams p;
+                p.c = cp; p.alpha_tiles = alpha_tiles(); p.canvas = d_canvas;
+                hipAssert(launch_compose_canvas_rgba(p, on));
+                break;
+            }
+            case Job::GRAY: hipAssert(launch_compose_canvas_gray(cp, d_canvas, on)); break;
+            default: hipAssert(launch_compose_canvas(cp, d_canvas, on));
+        }
+    }
+    template <class P> void resample_into(P& p, hipStream_t on, hipError_t (*launch)(const P&, hipStream_t)) {
+        resample_base(p);
+        p.dst = d_out; p.dst_step = frame_step(p.outW, true);
+        hipAssert(launch(p, on));
+    }
+    void resample(hipStream_t on) {
+        switch (job.kind) {
+            case Job::BGR: { ResampleParams p; p.deep = deep ? 1 : 0; resample_into(p, on, launch_resample); break; }
+            case Job::GRAY: { ResampleGrayParams p; p.deep = job.gray.deep ? 1 : 0; resample_into(p, on, launch_resample_gray); break; }
+            case Job::RGBA: { ResampleRgbaParams p; p.uniform = job.rgba.uniform ? 1 : 0; p.alpha_value = job.rgba.value; resample_into(p, on, launch_resample_rgba); break; }
+            case Job::YUV: {                                          // the planes of the target size (resized YUV frames are I420)
+                ResampleYuvParams p;
+                resample_base(p);
+                p.dst = yuv_layout(d_out, p.outH, p.outW, job.yuv.out_bits, kYuvI420); p.k = job.yuv.out;
+                hipAssert(launch_resample_yuv(p, on));
+                break;
+            }
+        }
+    }
+    void compose(int rows, int cols, const TileGrid& grid, const StripPlan& sp, hipStream_t on) {
+        switch (job.kind) {
+            case Job::BGR: compose_rect(rows, cols, grid, sp.x0, sp.x1, 0, 0, sp.first_tile, on); break;
+            case Job::YUV: {                                          // the planes of job.yuv.out_layout
+                ComposeYuvParams p;
+                p.c = compose_base(rows, cols, grid);
+                p.dst = yuv_layout(d_out, p.c.outH, p.c.outW, job.yuv.out_bits, job.yuv.out_layout); p.k = job.yuv.out;
+                stamp_begin(4, 0);
+                hipAssert(launch_compose_yuv(p, on));
+                stamp_end();
+                break;
+            }
+            case Job::RGBA: {                                         // BGRA dwords
+                ComposeRgbaParams p;
+                p.c = compose_base(rows, cols, grid);
+                p.c.dst = d_out; p.c.dst_step = frame_step(p.c.outW, true);
+                p.alpha_tiles = alpha_tiles(); p.alpha_value = job.rgba.value;
+                hipAssert(launch_compose_rgba(p, on));
+                break;
+            }
+            case Job::GRAY: {                                         // one sample per pixel
+                ComposeParams cp = compose_base(rows, cols, grid);
+                cp.dst = d_out; cp.dst_step = frame_step(cp.outW, true); cp.deep = job.gray.deep ? 1 : 0;
+                stamp_begin(4, 0);
+                hipAssert(launch_compose_gray(cp, on));
+                stamp_end();
+                break;
+            }
+        }
+    }
+    // The end of a frame on stream `on`, behind its passes.  Resized (job.rs): the canvas compose is the slab's last reader, the resample the writer of d_out; in
+    // order on `on`, they share one canvas.  `slab_read`: recorded behind the slab's last reader; `out_free`: the frame that last left through this output buffer
+    // has been downloaded (a rolling sequence gives both, run_frame() and rgba_frame() neither: stream order serves).
+    void finish_frame(int rows, int cols, const TileGrid& grid, const StripPlan& sp, hipStream_t on, hipEvent_t slab_read, hipEvent_t out_free) {
+        if (job.rs) {
+            compose_canvas(rows, cols, grid, on);
+            if (slab_read) hipAssert(hipEventRecord(slab_read, on));
+            if (out_free) hipAssert(hipStreamWaitEvent(on, out_free, 0));
+            resample(on);
+            return;
+        }
+        if (out_free) hipAssert(hipStreamWaitEvent(on, out_free, 0));
+        compose(rows, cols, grid, sp, on);
+        if (slab_read) hipAssert(hipEventRecord(slab_read, on));
+    }
+    // ---- (end of the frame formats)
+
     // RGBA frames (renderRgba / alphaBleed): the BGRA frame into d_frame, the two words zeroed, alpha_bleed_kernel -> d_bgr, d_alpha, d_minmax; all on `stream`
     void upload_and_bleed(const Image& src, int radius) {
         const int rows = src.rows, cols = src.cols;
@@ -1290,55 +1393,96 @@ struct Img2Img::Impl {
         bp.bgr = d_bgr; bp.bgr_step = (size_t)cols * 3; bp.alpha = d_alpha; bp.alpha_step = (size_t)cols; bp.minmax = d_minmax;
         hipAssert(launch_alpha_bleed(bp, stream));
     }
-    // the whole canvas of an RGBA frame as BGRA dwords into d_out: colour tiles from slab slot 0, alpha tiles from slot alpha_slot0 (uniform: none, A = value)
-    void compose_rgba(int rows, int cols, const TileGrid& grid, size_t alpha_slot0, bool uniform, unsigned value) {
-        ComposeRgbaParams rp;
-        rp.c = compose_base(rows, cols, grid);
-        rp.c.dst = d_out; rp.c.dst_step = (size_t)cols * cfg.scaling * 4;
-        rp.alpha_tiles = uniform ? nullptr : (const uint8_t*)d_slab + alpha_slot0 * (size_t)plan.Tout * plan.Tout * 4 * plan.elt;
-        rp.alpha_value = value;
-        hipAssert(launch_compose_rgba(rp, stream));
+
+    // ---- The frame calls other than render() / renderStrip(): one record, one checker per format, one runner.  An entry point checks (X_check fills the record
+    // or returns the first refusal's text), sets the job of its format, and hands the record and its two copy lambdas to run_call().
+    struct FrameCall { int rows = 0, cols = 0, out_rows = 0, out_cols = 0; bool resized = false; TileGrid grid; StripPlan sp; };
+    // The pieces the checkers share, where text and position agree.  call_target(): the sizes of the call into `c` - with a resize filter the target is the size of
+    // the first output image, else the scaled size; at the scaled size a resized call is the plain one - and why a call with a filter (`any_filter` false: only a
+    // resized one) cannot have that target, or "".  out_size_text(): the refusal of an output of another size.  call_grid(): the last check, the tile grid (and its one strip).
+    template <class Img> std::string call_target(int resizeFilter, const Img& dst0, int rows, int cols, bool any_filter, FrameCall& c) const {
+        const int s = cfg.scaling;
+        c.rows = rows; c.cols = cols; c.out_rows = resizeFilter >= 0 ? dst0.rows : rows * s; c.out_cols = resizeFilter >= 0 ? dst0.cols : cols * s;
+        c.resized = resizeFilter >= 0 && !(c.out_rows == rows * s && c.out_cols == cols * s);
+        return (any_filter ? resizeFilter >= 0 : c.resized) ? resize_problem(rows, cols, c.out_rows, c.out_cols, resizeFilter) : "";
     }
-    // a resized RGBA frame (job.rs set): the whole canvas as four fp32 planes R, G, B, A (uniform: three) into d_canvas, then its resize as BGRA dwords into d_out
-    void compose_canvas_rgba(int rows, int cols, const TileGrid& grid, size_t alpha_slot0, bool uniform) {
-        ComposeCanvasRgbaParams rp;
-        rp.c = compose_base(rows, cols, grid);
-        rp.alpha_tiles = uniform ? nullptr : (const uint8_t*)d_slab + alpha_slot0 * (size_t)plan.Tout * plan.Tout * 4 * plan.elt;
-        rp.canvas = d_canvas;
-        hipAssert(launch_compose_canvas_rgba(rp, stream));
+    static std::string out_size_text(const FrameCall& c) { return "Output image has invalid size: expected " + std::to_string(c.out_cols) + "x" + std::to_string(c.out_rows) + "."; }
+    std::string call_grid(FrameCall& c) const {
+        const std::string why = frame_grid(c.rows, c.cols, c.grid);
+        if (why.empty()) c.sp = strip_plan(c.grid, c.cols * cfg.scaling, plan.Tout, 0, 1);
+        return why;
     }
-    void resample_rgba(bool uniform, unsigned value) {
-        ResampleRgbaParams rp;
-        resample_base(rp);
-        rp.dst = d_out; rp.dst_step = (size_t)rp.outW * 4;
-        rp.uniform = uniform ? 1 : 0; rp.alpha_value = value;
-        hipAssert(launch_resample_rgba(rp, stream));
-    }
-    // The refusals and the set-up the RGBA entry points share (renderRgba, renderRgbaResized, renderSequenceRgba*).  rgba_check(): `count` frames of one size,
-    // one target (resizeFilter >= 0: dsts[0]'s size, else the scaled size) and one set of options; returns the message of the first refusal, or "" with `c` filled.
-    // The order is deliberate and the same for one frame and for a sequence: depth, the first frame's size, the target (resize_problem), then per frame its size, its
-    // pointers and steps, then the bleed radius, then the grid - so a null dst with an out-of-range target reports the target.
-    struct RgbaCall { int rows = 0, cols = 0, out_rows = 0, out_cols = 0; bool resized = false; TileGrid grid; };
-    std::string rgba_check(const Image* srcs, const Image* dsts, int count, const RgbaOptions& opt, int resizeFilter, RgbaCall& c) const {
-        const int rows = srcs[0].rows, cols = srcs[0].cols;
-        for (int i = 0; i < count; ++i) if (srcs[i].depth != 8 || dsts[i].depth != 8) return "RGBA input and output images must be 8-bit.";
-        if (rows <= 0 || cols <= 0) return "Input image is empty or has an invalid step.";
-        const Target t = target_size(resizeFilter, dsts[0], rows, cols);
-        const int out_rows = t.rows, out_cols = t.cols;
-        if (resizeFilter >= 0) {
-            const std::string why = resize_problem(rows, cols, out_rows, out_cols, resizeFilter);
-            if (!why.empty()) return why;
+    // renderSequence / renderSequenceResized.  At the scaled size a resized sequence is the plain one: no filter is looked at.  (Not const: `deep` is written
+    // between the target and the per-frame checks, where it always was.)
+    std::string bgr_sequence_check(const Image* srcs, const Image* dsts, int count, int resizeFilter, const char* who, FrameCall& c) {
+        for (int i = 0; i < count; ++i) if (srcs[i].depth != 8 || dsts[i].depth != 8) return std::string(who) + " takes 8-bit frames (16-bit images go through render()).";
+        if (const std::string why = call_target(resizeFilter, dsts[0], srcs[0].rows, srcs[0].cols, false, c); !why.empty()) return why;
+        deep = false;
+        for (int i = 0; i < count; ++i) {
+            if (!srcs[i].data || srcs[i].rows != c.rows || srcs[i].cols != c.cols || srcs[i].step < (size_t)c.cols * 3 || c.rows <= 0 || c.cols <= 0) return "Input images must be non-empty and of one size.";
+            if (!dsts[i].data || dsts[i].rows != c.out_rows || dsts[i].cols != c.out_cols || dsts[i].step < (size_t)c.out_cols * 3) return out_size_text(c);
         }
+        return call_grid(c);
+    }
+    // The YUV calls: one size, one pair of depths and one pair of layouts (srcs[0]'s, dsts[0]'s) for the sequence; resized frames are I420 on both sides.
+    std::string yuv_check(const YuvImage* srcs, const YuvImage* dsts, int count, YuvFormat format, int resizeFilter, FrameCall& c) const {
+        const int matrix = (int)format.matrix, range = (int)format.range;
+        if (matrix < 0 || matrix > 2) return "Unknown YUV matrix " + std::to_string(matrix) + ".";
+        if (range < 0 || range > 1) return "Unknown YUV range " + std::to_string(range) + ".";
+        const int rows = srcs[0].rows, cols = srcs[0].cols, in_bits = srcs[0].bits, out_bits = dsts[0].bits;
+        if ((in_bits != 8 && in_bits != 10) || (out_bits != 8 && out_bits != 10)) return "YUV frames must have 8 or 10 bits.";
+        if (rows <= 0 || cols <= 0) return "Input image is empty.";
+        const int in_layout = (int)srcs[0].layout, out_layout = (int)dsts[0].layout;
+        if (in_layout < kYuvI420 || in_layout > kYuvNV12 || out_layout < kYuvI420 || out_layout > kYuvNV12)
+            return "Unknown YUV layout " + std::to_string(in_layout < kYuvI420 || in_layout > kYuvNV12 ? in_layout : out_layout) + ".";
+        if (resizeFilter >= 0 && (in_layout != kYuvI420 || out_layout != kYuvI420)) return "Resized YUV frames must be I420 (yuv420p / yuv420p10le) on both sides.";
+        if (const std::string why = call_target(resizeFilter, dsts[0], rows, cols, true, c); !why.empty()) return why;
+        // every plane of the layout present (NV12: Y and UV), with a step that holds its row
+        auto planes_ok = [](const YuvImage& f) {
+            const size_t bps = f.bits > 8 ? 2 : 1;
+            for (int k = 0; k < yuv_planes((int)f.layout); ++k) if (!f.planes[k] || f.steps[k] < (size_t)(k ? yuv_chroma_samples(f.cols, (int)f.layout) : f.cols) * bps) return false;
+            return true;
+        };
+        for (int i = 0; i < count; ++i) {
+            if ((int)srcs[i].layout != in_layout || (int)dsts[i].layout != out_layout) return "The frames of a sequence must be of one layout (one for the inputs, one for the outputs).";
+            if (srcs[i].rows != rows || srcs[i].cols != cols || srcs[i].bits != in_bits) return "Input images must be of one size and depth.";
+            if (!planes_ok(srcs[i])) return "Input image has a missing plane or an invalid step.";
+            if (dsts[i].rows != c.out_rows || dsts[i].cols != c.out_cols) return out_size_text(c);
+            if (dsts[i].bits != out_bits) return "Output images must be of one depth.";
+            if (!planes_ok(dsts[i])) return "Output image has a missing plane or an invalid step.";
+        }
+        return call_grid(c);
+    }
+    // The RGBA and the gray calls: `count` frames of one size, one target and (RGBA) one set of options.  The order is deliberate and the same for one frame and
+    // for a sequence: depth, the first frame's size, the target (resize_problem), then per frame its size, its pointers and steps, then (RGBA) the bleed radius,
+    // then the grid - so a null dst with an out-of-range target reports the target.  packed_check(): all of it behind the depth, for `bpp` bytes per pixel.
+    std::string packed_check(const Image* srcs, const Image* dsts, int count, int resizeFilter, size_t bpp, FrameCall& c) const {
+        const int rows = srcs[0].rows, cols = srcs[0].cols;
+        if (rows <= 0 || cols <= 0) return "Input image is empty or has an invalid step.";
+        if (const std::string why = call_target(resizeFilter, dsts[0], rows, cols, true, c); !why.empty()) return why;
         for (int i = 0; i < count; ++i) {
             if (srcs[i].rows != rows || srcs[i].cols != cols) return "Input images must be of one size.";
-            if (!srcs[i].data || srcs[i].step < (size_t)cols * 4) return "Input image is empty or has an invalid step.";
-            if (!dsts[i].data || dsts[i].rows != out_rows || dsts[i].cols != out_cols || dsts[i].step < (size_t)out_cols * 4)
-                return "Output image has invalid size: expected " + std::to_string(out_cols) + "x" + std::to_string(out_rows) + ".";
+            if (!srcs[i].data || srcs[i].step < (size_t)cols * bpp) return "Input image is empty or has an invalid step.";
+            if (!dsts[i].data || dsts[i].rows != c.out_rows || dsts[i].cols != c.out_cols || dsts[i].step < (size_t)c.out_cols * bpp) return out_size_text(c);
         }
+        return "";
+    }
+    std::string rgba_check(const Image* srcs, const Image* dsts, int count, const RgbaOptions& opt, int resizeFilter, FrameCall& c) const {
+        for (int i = 0; i < count; ++i) if (srcs[i].depth != 8 || dsts[i].depth != 8) return "RGBA input and output images must be 8-bit.";
+        if (const std::string why = packed_check(srcs, dsts, count, resizeFilter, 4, c); !why.empty()) return why;
         if (opt.bleed < 0 || opt.bleed > kBleedMaxRadius) return "Alpha bleed radius " + std::to_string(opt.bleed) + " is not in [0, " + std::to_string(kBleedMaxRadius) + "].";
-        c.rows = rows; c.cols = cols; c.out_rows = out_rows; c.out_cols = out_cols;
-        c.resized = t.resized;
-        return frame_grid(rows, cols, c.grid);
+        return call_grid(c);
+    }
+    // single: one frame of 8 or 16 bits (renderGray / renderGrayResized); else a sequence of 8-bit frames
+    std::string gray_check(const Image* srcs, const Image* dsts, int count, int resizeFilter, const char* who, bool single, FrameCall& c) const {
+        const int depth = srcs[0].depth;
+        if (single) {
+            if ((depth != 8 && depth != 16) || dsts[0].depth != depth) return "Input and output images must both be 8-bit or both 16-bit.";
+        } else {
+            for (int i = 0; i < count; ++i) if (srcs[i].depth != 8 || dsts[i].depth != 8) return std::string(who) + " takes 8-bit frames (16-bit images go through renderGray()).";
+        }
+        if (const std::string why = packed_check(srcs, dsts, count, resizeFilter, depth == 16 ? 2 : 1, c); !why.empty()) return why;
+        return call_grid(c);
     }
     // The tile grid of a rows x cols frame into `grid`; returns "" or why the engine cannot render it (img2img_render.cpp:232-240)
     std::string frame_grid(int rows, int cols, TileGrid& grid) const {
@@ -1348,36 +1492,55 @@ struct Img2Img::Impl {
         for (const Rect& r : grid.out) if (r.w <= 0 || r.h <= 0) return "Tile grid does not fit the output (scaling does not match the model).";
         return "";
     }
-    // The output size of a call: with a resize filter the size of the first output image, else the scaled size; at the scaled size a resized call is the plain one
-    struct Target { int rows = 0, cols = 0; bool resized = false; };
-    template <class Img> Target target_size(int resizeFilter, const Img& dst0, int rows, int cols) const {
-        const int s = cfg.scaling;
-        Target t;
-        t.rows = resizeFilter >= 0 ? dst0.rows : rows * s; t.cols = resizeFilter >= 0 ? dst0.cols : cols * s;
-        t.resized = resizeFilter >= 0 && !(t.rows == rows * s && t.cols == cols * s);
-        return t;
-    }
     // the two frame and the two output buffers of a sequence, and the copy streams that fill and empty them
     void sequence_buffers(size_t in_bytes, size_t out_bytes) {
         ensure_copy_streams();
         ensure(d_frame, frame_cap, in_bytes);   ensure(d_frame2, frame2_cap, in_bytes);
         ensure(d_out, out_cap, out_bytes);      ensure(d_out2, out2_cap, out_bytes);
     }
-    // a resized frame: the tap tables of its target into the job and a canvas of `planes` fp32 planes of the scaled size
-    void job_resize(int rows, int cols, int out_rows, int out_cols, int resizeFilter, int planes) {
+    // a resized frame: the tap tables of its target into the job and a canvas of the format's fp32 planes of the scaled size
+    void job_resize(int rows, int cols, int out_rows, int out_cols, int resizeFilter) {
         const int s = cfg.scaling;
         job.rs = resize_tables(cols * s, rows * s, out_cols, out_rows, resizeFilter);
-        ensure_canvas((size_t)rows * s * cols * s * planes * sizeof(float));
+        ensure_canvas((size_t)rows * s * cols * s * canvas_planes() * sizeof(float));
     }
-    // after the frame and output buffers are sized: the frame is marked not replayable, the shared tables are made, the job of the call's frames is set
-    void rgba_begin(const RgbaCall& c, const RgbaOptions& opt, int resizeFilter) {
-        deep = false;
-        last_rows = last_cols = 0;   // (d_frame / d_out hold BGRA from here on: not replayed by benchResident / residentOutput / profileFrame)
-        rgba_setup(c.rows, c.cols, c.grid, opt.skipUniformAlpha);
-        if (c.resized) job_resize(c.rows, c.cols, c.out_rows, c.out_cols, resizeFilter, 4);
+    // What every frame call does behind its checks, with the job of its format set: the buffers (single: one frame on the compute stream, else the two pairs of
+    // a sequence), the slot tables, a resized call's tables and canvas, then the frames - up(i, device buffer, stream) and down(i, device buffer, stream) copy
+    // frame i between the caller's memory and the device layout - and last_ms, the compute stream's milliseconds per frame.  A format that is not replayable
+    // marks the engine so once its buffers are sized (d_frame / d_out hold its samples from here on).
+    template <class Up, class Down>
+    void run_call(const FrameCall& c, int count, bool single, int resizeFilter, const Up& up, const Down& down) {
+        const size_t in_bytes = frame_bytes(c.rows, c.cols, false), out_bytes = frame_bytes(c.out_rows, c.out_cols, true);
+        if (single) { ensure(d_frame, frame_cap, in_bytes); ensure(d_out, out_cap, out_bytes); }
+        else sequence_buffers(in_bytes, out_bytes);
+        if (!replayable()) { deep = false; last_rows = last_cols = 0; }
+        call_slots(c.rows, c.cols, c.grid, c.sp);
+        if (!replayable()) one_part_stale = false;
+        if (c.resized) job_resize(c.rows, c.cols, c.out_rows, c.out_cols, resizeFilter);
+        if (!single) { last_ms = run_sequence(count, c.rows, c.cols, c.grid, c.sp, up, down) / count; return; }
+        up(0, d_frame, stream);
+        run_frame(c.rows, c.cols, c.grid, true, c.sp, ev0);
+        hipAssert(hipEventRecord(ev1, stream));
+        down(0, d_out, stream);
+        hipAssert(hipStreamSynchronize(stream));
+        hipAssert(hipEventElapsedTime(&last_ms, ev0, ev1));
+    }
+    // run_call() for packed frames (every format but YUV): frame i travels as one 2-D copy of `bpp` bytes per pixel between the caller's Image and the device layout
+    void run_packed_call(const FrameCall& c, const Image* srcs, Image* dsts, int count, bool single, int resizeFilter, size_t bpp) {
+        const size_t in_step = frame_step(c.cols, false), out_step = frame_step(c.out_cols, true);
+        run_call(c, count, single, resizeFilter,
+            [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dev, in_step, srcs[i].data, srcs[i].step, (size_t)c.cols * bpp, c.rows, hipMemcpyHostToDevice, on)); },
+            [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dsts[i].data, dsts[i].step, dev, out_step, (size_t)c.out_cols * bpp, c.out_rows, hipMemcpyDeviceToHost, on)); });
+    }
+    // the RGBA calls behind entry(): one frame on the compute stream with progress (renderRgbaFrame), or a sequence (runSequenceRgba)
+    bool rgba_call(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt, int resizeFilter, const char* who, bool single) {
+        FrameCall c;
+        if (const std::string why = rgba_check(srcs, dsts, count, opt, resizeFilter, c); !why.empty()) { log(Severity::error, why, who, __LINE__); return false; }
         job.kind = Job::RGBA; job.rgba = RgbaJob{opt.bleed, opt.skipUniformAlpha};
+        run_packed_call(c, srcs, dsts, count, single, resizeFilter, 4);
+        return true;
     }
-    // What the frames of an RGBA call share, made once per call (the RGBA counterpart of sequence_slots): the planes the bleed writes, the two words' host side,
+    // What the frames of an RGBA call share, made once per call (the RGBA side of call_slots): the planes the bleed writes, the two words' host side,
     // and the slot table, liveness table and slab of the 2N schedule - slot = step index, tile = step / stepsPerTile over the 2N tiles (colour 0 .. N - 1,
     // alpha N .. 2N - 1), zero pad slots at the end.  A frame whose alpha tiles are skipped runs a prefix of the same table.
     void rgba_setup(int rows, int cols, const TileGrid& grid, bool skip) {
@@ -1391,14 +1554,14 @@ struct Img2Img::Impl {
         fill_slots(grid, 0, N, kSlotColour, 0, colour);
         fill_slots(grid, 0, N, kSlotAlpha, colour, stepTotal - colour);
         upload_slots(grid, stepTotal, stepTotal);
-        one_part_stale = false;
     }
     // The device part of one RGBA frame, on `stream`, with the BGRA frame in d_frame and rgba_setup() done: alpha_bleed_kernel, ONE schedule of the frame's N
-    // colour tiles followed by its N alpha tiles, then compose_rgba_kernel - or, with job.rs set, compose_canvas_rgba_kernel and resample_rgba_kernel - into d_out.
+    // colour tiles followed by its N alpha tiles, then the end of an RGBA frame (finish_frame: compose_rgba_kernel - or, with job.rs set, compose_canvas_rgba_kernel
+    // and resample_rgba_kernel - into d_out).
     // skip (skipUniformAlpha): the two words come back behind the bleed kernel while the passes that hold colour tiles only - the same in the 2N and the N
     // schedule - are issued; the host waits for them, then issues the rest of whichever schedule the frame takes.  `started`: recorded behind the bleed.
-    void rgba_frame(int rows, int cols, const TileGrid& grid, bool report, hipEvent_t started) {
-        const RgbaJob& opt = job.rgba;
+    void rgba_frame(int rows, int cols, const TileGrid& grid, const StripPlan& sp, bool report, hipEvent_t started) {
+        RgbaJob& opt = job.rgba;
         const int steps = cfg.tta ? 8 : 1, B = plan.B, S = plan.B / plan.userB, N = grid.count;
         bleed_frame(rows, cols, opt.bleed);
         if (opt.skip) {
@@ -1406,31 +1569,23 @@ struct Img2Img::Impl {
             hipAssert(hipEventRecord(ev_minmax, stream));
         }
         if (started) hipAssert(hipEventRecord(started, stream));
-        bool uniform = false; unsigned value = 255;
+        opt.alpha_slot0 = (size_t)N * steps; opt.uniform = false; opt.value = 255;
         if (!opt.skip) run_passes(rows, cols, 2 * N, 0, report, 0, true);
         else {
             const int F = N * steps / B;                 // passes of colour tiles only: the same launches whether the alpha tiles follow or not
             const auto t0 = std::chrono::steady_clock::now();
             run_passes(rows, cols, 2 * N, 0, false, 0, true, 0, 0, 0, F);
             hipAssert(hipEventSynchronize(ev_minmax));
-            uniform = h_minmax[0] + h_minmax[1] == 255u;      // max(A) + max(255 - A) == 255  <=>  min(A) == max(A)
-            value = h_minmax[0];
-            const int tiles = uniform ? N : 2 * N, batchCount = batch_count(tiles);
+            opt.uniform = h_minmax[0] + h_minmax[1] == 255u;      // max(A) + max(255 - A) == 255  <=>  min(A) == max(A)
+            opt.value = h_minmax[0];
+            const int tiles = opt.uniform ? N : 2 * N, batchCount = batch_count(tiles);
             const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
             if (report) for (int k = 0; k < std::min(F * S, batchCount); ++k) log(k + 1, batchCount, 1000.0 * F * S / std::max(ms, 1e-6));
             run_passes(rows, cols, tiles, 0, report, 0, false, 0, 0, F, -1);
         }
-        if (job.rs) { compose_canvas_rgba(rows, cols, grid, (size_t)N * steps, uniform); resample_rgba(uniform, value); }
-        else compose_rgba(rows, cols, grid, (size_t)N * steps, uniform, value);
+        finish_frame(rows, cols, grid, sp, stream, nullptr, nullptr);
     }
-    // the slot table and the slab of a sequence's frames (renderSequence / renderSequenceYuv): every tile of the frame, in one part
-    void sequence_slots(const TileGrid& grid, const StripPlan& sp) {
-        const size_t stepCount = pass_slots(sp.tile_count);
-        fill_slots(grid, 0, sp.tile_count, 1, 0, stepCount);
-        upload_slots(grid, stepCount, stepCount);
-        hipAssert(hipStreamSynchronize(stream));
-    }
-    // The frame loop of renderSequence() / renderSequenceYuv(): frame i is uploaded by up(i, device buffer, s_up) into one of two frame buffers, rendered
+    // The frame loop of a sequence call (run_call): frame i is uploaded by up(i, device buffer, s_up) into one of two frame buffers, rendered
     // (rolling when every pass of a frame splits: run_rolling_frame) into one of two output buffers, and downloaded by down(i, device buffer, s_dn); events
     // order the three streams where a buffer comes round again.  Returns the compute stream's milliseconds for the whole sequence.
     template <class Up, class Down>
@@ -1439,10 +1594,7 @@ struct Img2Img::Impl {
         uint8_t* const outs[2] = {d_out, d_out2};
         struct Restore { Impl* im; uint8_t* f; uint8_t* o; ~Restore() { im->d_frame = f; im->d_out = o; } } restore{this, frames[0], outs[0]};   // also on exceptions
         // frame f is composed on the second group's stream while frame f + 1's first group already runs (run_rolling_frame) when every pass of a frame splits
-        // RGBA frames do not roll: d_bgr, d_alpha and d_minmax are single buffers the bleed writes on the compute stream, and in a rolling sequence the second
-        // tile group of frame f would still gather from them while frame f + 1 bleeds into them.  Through run_frame() every pass joins its groups before the
-        // next launch on `stream`, so stream order alone keeps the single buffers (and the one slab and canvas) safe.
-        const bool roll = count > 1 && job.kind != Job::RGBA && can_roll(sp.tile_count);
+        const bool roll = count > 1 && rolls() && can_roll(sp.tile_count);
         if (roll) ensure(d_slab2, slab2_cap, slab_cap);
         hipAssert(hipStreamSynchronize(stream));
         hipAssert(hipEventRecord(ev0, stream));
@@ -1474,41 +1626,6 @@ struct Img2Img::Impl {
         hipAssert(hipEventElapsedTime(&total_ms, ev0, ev1));
         return total_ms;
     }
-    // the device layout of a YUV frame in d_frame / d_out: Y, U, V (NV12: Y, UV) one after the other, rows padded to 16 bytes (the stores of the compose kernels)
-    static YuvPlanes yuv_layout(uint8_t* base, int rows, int cols, int bits, int layout) {
-        const size_t bps = bits > 8 ? 2 : 1;
-        const int cw = yuv_chroma_samples(cols, layout), ch = yuv_chroma_rows(rows, layout);
-        YuvPlanes f;
-        f.rows = rows; f.cols = cols; f.bits = bits; f.layout = layout;
-        f.step[0] = ((size_t)cols * bps + 15) / 16 * 16; f.step[1] = f.step[2] = ((size_t)cw * bps + 15) / 16 * 16;
-        f.p[0] = base; f.p[1] = base + f.step[0] * rows; f.p[2] = layout == kYuvNV12 ? nullptr : f.p[1] + f.step[1] * ch;
-        return f;
-    }
-    static int yuv_planes(int layout) { return layout == kYuvNV12 ? 2 : 3; }
-    static size_t yuv_bytes(int rows, int cols, int bits, int layout) {
-        const YuvPlanes f = yuv_layout(nullptr, rows, cols, bits, layout);
-        return f.step[0] * rows + (yuv_planes(layout) - 1) * f.step[1] * yuv_chroma_rows(rows, layout);
-    }
-    // what the three resample launches share: the canvas, its size and the target's, and the tap tables of job.rs
-    template <class Params> void resample_base(Params& rp) const {
-        const ResizeTables* const rs = job.rs;
-        rp.canvas = d_canvas; rp.inW = rs->inW; rp.inH = rs->inH;
-        rp.outW = rs->outW; rp.outH = rs->outH;
-        rp.fx = rs->fx; rp.wx = rs->wx; rp.kx = rs->kx; rp.fy = rs->fy; rp.wy = rs->wy; rp.ky = rs->ky; rp.rows_max = rs->rows_max;
-    }
-    void resample(hipStream_t on) {
-        ResampleParams rp;
-        resample_base(rp);
-        rp.dst = d_out; rp.dst_step = (size_t)rp.outW * 3 * (deep ? 2 : 1); rp.deep = deep ? 1 : 0;
-        hipAssert(launch_resample(rp, on));
-    }
-    // a resized YUV frame (renderYuvResized): the resize of d_canvas written as the planes of d_out (yuv_layout of the target size)
-    void resample_yuv(hipStream_t on) {
-        ResampleYuvParams rp;
-        resample_base(rp);
-        rp.dst = yuv_layout(d_out, rp.outH, rp.outW, job.yuv.out_bits, kYuvI420); rp.k = job.yuv.out;
-        hipAssert(launch_resample_yuv(rp, on));
-    }
     // the device tap tables of one (canvas, target, filter): what job_resize() puts into the job for the frame
     const ResizeTables* resize_tables(int inW, int inH, int outW, int outH, int filter) {
         for (const ResizeTables& t : rs_tables) if (t.inW == inW && t.inH == inH && t.outW == outW && t.outH == outH && t.filter == filter) return &t;
@@ -1538,7 +1655,6 @@ struct Img2Img::Impl {
         canvas_cap = bytes;
     }
     // renderResized() / renderSequenceResized(): the target size of a frame must be a downsample of the network output by a factor of 1 to s per axis
-    std::string resize_problem(const Image& src, const Image& dst, int filter) const { return resize_problem(src.rows, src.cols, dst.rows, dst.cols, filter); }
     std::string resize_problem(int rows, int cols, int out_rows, int out_cols, int filter) const {
         const int s = cfg.scaling;
         if (filter != 0 && filter != 1) return "Unknown resize filter.";
@@ -1776,10 +1892,10 @@ bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, cons
     const size_t bps = src.depth / 8;                          // bytes per sample
     if (!src.data || rows <= 0 || cols <= 0 || src.step < (size_t)cols * 3 * bps) { W2X_LOG_AS(who, error, "Input image is empty or has an invalid step."); return false; }
     // a resized frame (renderResized): dst is the target size; at the scaled size it is a plain render()
-    const bool resized = impl->target_size(resizeFilter, dst, rows, cols).resized;
+    Impl::FrameCall target;
+    if (const std::string why = impl->call_target(resizeFilter, dst, rows, cols, false, target); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
+    const bool resized = target.resized;
     if (resized) {
-        const std::string why = impl->resize_problem(src, dst, resizeFilter);
-        if (!why.empty()) { W2X_LOG_AS(who, error, why); return false; }
         if (!dst.data || dst.step < (size_t)dst.cols * 3 * bps) { W2X_LOG_AS(who, error, "Output image is empty or has an invalid step."); return false; }
     } else if (!dst.data || dst.rows != rows * s || dst.cols != cols * s || dst.step < (size_t)dst.cols * 3 * bps) {
         W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(cols * s) + "x" + std::to_string(rows * s) + ".");
@@ -1787,9 +1903,9 @@ bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, cons
     }
     hipStream_t stream = impl->stream;
     // img2img_render.cpp:226 upload
-    impl->ensure(impl->d_frame, impl->frame_cap, (size_t)rows * cols * 3 * bps);
-    impl->ensure(impl->d_out, impl->out_cap, (size_t)dst.rows * dst.cols * 3 * bps);
-    if (resized) impl->job_resize(rows, cols, dst.rows, dst.cols, resizeFilter, 3);
+    impl->ensure(impl->d_frame, impl->frame_cap, Impl::bgr_step(cols, bps == 2) * rows);
+    impl->ensure(impl->d_out, impl->out_cap, Impl::bgr_step(dst.cols, bps == 2) * dst.rows);
+    if (resized) impl->job_resize(rows, cols, dst.rows, dst.cols, resizeFilter);
     impl->deep = bps == 2;
     // img2img_render.cpp:226 upload: below, once the parts are known (a frame that runs in parts uploads the first part's columns first)
     TileGrid grid;
@@ -2171,35 +2287,11 @@ bool Img2Img::renderSequenceResized(const Image* srcs, Image* dsts, int count, R
 bool Img2Img::runSequence(const Image* srcs, Image* dsts, int count, int resizeFilter, const char* who) {
     return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
     if (count <= 0) return true;
-    const RenderConfig& cfg = impl->cfg;
-    const Plan& plan = impl->plan;
-    const int rows = srcs[0].rows, cols = srcs[0].cols, s = cfg.scaling;
-    for (int i = 0; i < count; ++i) if (srcs[i].depth != 8 || dsts[i].depth != 8) { W2X_LOG_AS(who, error, std::string(who) + " takes 8-bit frames (16-bit images go through render())."); return false; }
-    // a resized sequence (renderSequenceResized): every dst is the target size of dsts[0]; at the scaled size it is a plain sequence
-    const Impl::Target target = impl->target_size(resizeFilter, dsts[0], rows, cols);
-    const int out_rows = target.rows, out_cols = target.cols;
-    const bool resized = target.resized;
-    if (resized) {
-        const std::string why = impl->resize_problem(srcs[0], dsts[0], resizeFilter);
-        if (!why.empty()) { W2X_LOG_AS(who, error, why); return false; }
-    }
-    impl->deep = false;
-    for (int i = 0; i < count; ++i) {
-        if (!srcs[i].data || srcs[i].rows != rows || srcs[i].cols != cols || srcs[i].step < (size_t)cols * 3 || rows <= 0 || cols <= 0) { W2X_LOG_AS(who, error, "Input images must be non-empty and of one size."); return false; }
-        if (!dsts[i].data || dsts[i].rows != out_rows || dsts[i].cols != out_cols || dsts[i].step < (size_t)out_cols * 3) { W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(out_cols) + "x" + std::to_string(out_rows) + "."); return false; }
-    }
-    impl->sequence_buffers((size_t)rows * cols * 3, (size_t)out_rows * out_cols * 3);
-    TileGrid grid;
-    if (const std::string why = impl->frame_grid(rows, cols, grid); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
-    const StripPlan sp = strip_plan(grid, cols * s, plan.Tout, 0, 1);
-    impl->sequence_slots(grid, sp);
-    if (resized) impl->job_resize(rows, cols, out_rows, out_cols, resizeFilter, 3);
-    const float total_ms = impl->run_sequence(count, rows, cols, grid, sp,
-        [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dev, (size_t)cols * 3, srcs[i].data, srcs[i].step, (size_t)cols * 3, rows, hipMemcpyHostToDevice, on)); },
-        [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dsts[i].data, dsts[i].step, dev, (size_t)out_cols * 3, (size_t)out_cols * 3, out_rows, hipMemcpyDeviceToHost, on)); });
-    impl->last_ms = total_ms / count;        // lastRenderMs(): compute-stream time per frame of the sequence
-    impl->last_rows = rows; impl->last_cols = cols; impl->last_grid = grid; impl->last_strip = sp;
-    if (resized) impl->last_rows = impl->last_cols = 0;   // (not replayed by benchResident: renderPart)
+    Impl::FrameCall c;
+    if (const std::string why = impl->bgr_sequence_check(srcs, dsts, count, resizeFilter, who, c); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
+    impl->run_packed_call(c, srcs, dsts, count, false, resizeFilter, 3);      // (lastRenderMs(): compute-stream time per frame of the sequence)
+    impl->last_rows = c.rows; impl->last_cols = c.cols; impl->last_grid = c.grid; impl->last_strip = c.sp;
+    if (c.resized) impl->last_rows = impl->last_cols = 0;   // (not replayed by benchResident: renderPart)
     return true;
     });
 }
@@ -2231,54 +2323,14 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
     return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
     if (count <= 0) return true;
     if (!srcs || !dsts) { W2X_LOG_AS(who, error, "No frames given."); return false; }
-    const RenderConfig& cfg = impl->cfg;
-    const Plan& plan = impl->plan;
-    const int matrix = (int)format.matrix, range = (int)format.range;
-    if (matrix < 0 || matrix > 2) { W2X_LOG_AS(who, error, "Unknown YUV matrix " + std::to_string(matrix) + "."); return false; }
-    if (range < 0 || range > 1) { W2X_LOG_AS(who, error, "Unknown YUV range " + std::to_string(range) + "."); return false; }
-    const int rows = srcs[0].rows, cols = srcs[0].cols, s = cfg.scaling, in_bits = srcs[0].bits, out_bits = dsts[0].bits;
-    if ((in_bits != 8 && in_bits != 10) || (out_bits != 8 && out_bits != 10)) { W2X_LOG_AS(who, error, "YUV frames must have 8 or 10 bits."); return false; }
-    if (rows <= 0 || cols <= 0) { W2X_LOG_AS(who, error, "Input image is empty."); return false; }
-    const int in_layout = (int)srcs[0].layout, out_layout = (int)dsts[0].layout;
-    if (in_layout < kYuvI420 || in_layout > kYuvNV12 || out_layout < kYuvI420 || out_layout > kYuvNV12) {
-        W2X_LOG_AS(who, error, "Unknown YUV layout " + std::to_string(in_layout < kYuvI420 || in_layout > kYuvNV12 ? in_layout : out_layout) + ".");
-        return false;
-    }
-    if (resizeFilter >= 0 && (in_layout != kYuvI420 || out_layout != kYuvI420)) { W2X_LOG_AS(who, error, "Resized YUV frames must be I420 (yuv420p / yuv420p10le) on both sides."); return false; }
-    const Impl::Target target = impl->target_size(resizeFilter, dsts[0], rows, cols);
-    const int out_rows = target.rows, out_cols = target.cols;
-    const bool resized = target.resized;
-    if (resizeFilter >= 0) {
-        const std::string why = impl->resize_problem(rows, cols, out_rows, out_cols, resizeFilter);
-        if (!why.empty()) { W2X_LOG_AS(who, error, why); return false; }
-    }
-    // every plane of the layout present (NV12: Y and UV), with a step that holds its row
-    auto planes_ok = [](const YuvImage& f) {
-        const size_t bps = f.bits > 8 ? 2 : 1;
-        for (int k = 0; k < Impl::yuv_planes((int)f.layout); ++k) if (!f.planes[k] || f.steps[k] < (size_t)(k ? yuv_chroma_samples(f.cols, (int)f.layout) : f.cols) * bps) return false;
-        return true;
-    };
-    for (int i = 0; i < count; ++i) {
-        if ((int)srcs[i].layout != in_layout || (int)dsts[i].layout != out_layout) { W2X_LOG_AS(who, error, "The frames of a sequence must be of one layout (one for the inputs, one for the outputs)."); return false; }
-        if (srcs[i].rows != rows || srcs[i].cols != cols || srcs[i].bits != in_bits) { W2X_LOG_AS(who, error, "Input images must be of one size and depth."); return false; }
-        if (!planes_ok(srcs[i])) { W2X_LOG_AS(who, error, "Input image has a missing plane or an invalid step."); return false; }
-        if (dsts[i].rows != out_rows || dsts[i].cols != out_cols) { W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(out_cols) + "x" + std::to_string(out_rows) + "."); return false; }
-        if (dsts[i].bits != out_bits) { W2X_LOG_AS(who, error, "Output images must be of one depth."); return false; }
-        if (!planes_ok(dsts[i])) { W2X_LOG_AS(who, error, "Output image has a missing plane or an invalid step."); return false; }
-    }
-    impl->sequence_buffers(Impl::yuv_bytes(rows, cols, in_bits, in_layout), Impl::yuv_bytes(out_rows, out_cols, out_bits, out_layout));
-    TileGrid grid;
-    if (const std::string why = impl->frame_grid(rows, cols, grid); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
-    const StripPlan sp = strip_plan(grid, cols * s, plan.Tout, 0, 1);
-    impl->sequence_slots(grid, sp);
-
+    Impl::FrameCall call;
+    if (const std::string why = impl->yuv_check(srcs, dsts, count, format, resizeFilter, call); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
+    const int matrix = (int)format.matrix, range = (int)format.range, in_bits = srcs[0].bits, out_bits = dsts[0].bits, in_layout = (int)srcs[0].layout;
     Impl::YuvJob& job = impl->job.yuv;
     impl->job.kind = Impl::Job::YUV;
     job.in = yuv_coefs(matrix, range, in_bits); job.out = yuv_coefs(matrix, range, out_bits);
-    job.in_bits = in_bits; job.out_bits = out_bits; job.in_layout = in_layout; job.out_layout = out_layout;
+    job.in_bits = in_bits; job.out_bits = out_bits; job.in_layout = in_layout; job.out_layout = (int)dsts[0].layout;
     job.key = 2 + (in_bits == 10 ? 1 : 0) + 2 * range + 4 * matrix + 12 * in_layout;   // 2 .. 13 per layout: 2 .. 49, below kRgbaKey
-    impl->deep = false;
-    if (resized) impl->job_resize(rows, cols, out_rows, out_cols, resizeFilter, 3);
     // the planes of a frame (NV12 two, else three) between the caller's layout and the device's (yuv_layout), on copy stream `on`
     auto copy_planes = [&](const YuvImage& host, uint8_t* dev, int r, int c, bool up, hipStream_t on) {
         const int layout = (int)host.layout;
@@ -2290,11 +2342,9 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
             else hipAssert(hipMemcpy2DAsync(host.planes[k], host.steps[k], d.p[k], d.step[k], width, h, hipMemcpyDeviceToHost, on));
         }
     };
-    const float total_ms = impl->run_sequence(count, rows, cols, grid, sp,
-        [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(srcs[i], dev, rows, cols, true, on); },
-        [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(dsts[i], dev, out_rows, out_cols, false, on); });
-    impl->last_ms = total_ms / count;
-    impl->last_rows = impl->last_cols = 0;   // (d_frame / d_out hold planes: not replayed by benchResident / residentOutput / profileFrame)
+    impl->run_call(call, count, false, resizeFilter,
+        [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(srcs[i], dev, call.rows, call.cols, true, on); },
+        [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(dsts[i], dev, call.out_rows, call.out_cols, false, on); });
     return true;
     });
 }
@@ -2314,21 +2364,7 @@ bool Img2Img::renderRgbaResized(const Image& src, Image& dst, const RgbaOptions&
 }
 
 bool Img2Img::renderRgbaFrame(const Image& src, Image& dst, const RgbaOptions& opt, int resizeFilter, const char* who) {
-    return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
-    Impl::RgbaCall c;
-    if (const std::string why = impl->rgba_check(&src, &dst, 1, opt, resizeFilter, c); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
-    hipStream_t stream = impl->stream;
-    impl->ensure(impl->d_frame, impl->frame_cap, (size_t)c.rows * c.cols * 4);
-    impl->ensure(impl->d_out, impl->out_cap, (size_t)c.out_rows * c.out_cols * 4);
-    impl->rgba_begin(c, opt, resizeFilter);
-    hipAssert(hipMemcpy2DAsync(impl->d_frame, (size_t)c.cols * 4, src.data, src.step, (size_t)c.cols * 4, c.rows, hipMemcpyHostToDevice, stream));
-    impl->rgba_frame(c.rows, c.cols, c.grid, true, impl->ev0);
-    hipAssert(hipEventRecord(impl->ev1, stream));
-    hipAssert(hipMemcpy2DAsync(dst.data, dst.step, impl->d_out, (size_t)c.out_cols * 4, (size_t)c.out_cols * 4, c.out_rows, hipMemcpyDeviceToHost, stream));
-    hipAssert(hipStreamSynchronize(stream));
-    hipAssert(hipEventElapsedTime(&impl->last_ms, impl->ev0, impl->ev1));
-    return true;
-    });
+    return impl->entry(who, kNotLoaded, kRenderFailed, [&] { return impl->rgba_call(&src, &dst, 1, opt, resizeFilter, who, true); });
 }
 
 // RGBA frames through renderSequence()'s pipeline: frame i is uploaded at 4 bytes per pixel on s_up into one of two frame buffers, its frame step
@@ -2344,17 +2380,7 @@ bool Img2Img::runSequenceRgba(const Image* srcs, Image* dsts, int count, const R
     return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
     if (count <= 0) return true;
     if (!srcs || !dsts) { W2X_LOG_AS(who, error, "No frames given."); return false; }
-    Impl::RgbaCall c;
-    if (const std::string why = impl->rgba_check(srcs, dsts, count, opt, resizeFilter, c); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
-    const int rows = c.rows, cols = c.cols, out_rows = c.out_rows, out_cols = c.out_cols;
-    const StripPlan sp = strip_plan(c.grid, cols * impl->cfg.scaling, impl->plan.Tout, 0, 1);
-    impl->sequence_buffers((size_t)rows * cols * 4, (size_t)out_rows * out_cols * 4);
-    impl->rgba_begin(c, opt, resizeFilter);
-    const float total_ms = impl->run_sequence(count, rows, cols, c.grid, sp,
-        [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dev, (size_t)cols * 4, srcs[i].data, srcs[i].step, (size_t)cols * 4, rows, hipMemcpyHostToDevice, on)); },
-        [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dsts[i].data, dsts[i].step, dev, (size_t)out_cols * 4, (size_t)out_cols * 4, out_rows, hipMemcpyDeviceToHost, on)); });
-    impl->last_ms = total_ms / count;
-    return true;
+    return impl->rgba_call(srcs, dsts, count, opt, resizeFilter, who, false);
     });
 }
 
@@ -2374,63 +2400,15 @@ bool Img2Img::renderSequenceGrayResized(const Image* srcs, Image* dsts, int coun
     return runGray(srcs, dsts, count, filter_id(filter), "renderSequenceGrayResized", false);
 }
 
-// single: one frame on the compute stream with progress (8 or 16 bits); else the sequence pipeline (8 bits, no progress).  The refusals come in the order of
-// rgba_check(): depth, the first frame's size, the target, then per frame its size, its pointers and steps, then the grid.
+// single: one frame on the compute stream with progress (8 or 16 bits); else the sequence pipeline (8 bits, no progress)
 bool Img2Img::runGray(const Image* srcs, Image* dsts, int count, int resizeFilter, const char* who, bool single) {
     return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
     if (count <= 0) return true;
     if (!srcs || !dsts) { W2X_LOG_AS(who, error, "No frames given."); return false; }
-    const int rows = srcs[0].rows, cols = srcs[0].cols, s = impl->cfg.scaling, depth = srcs[0].depth;
-    if (single) {
-        if ((depth != 8 && depth != 16) || dsts[0].depth != depth) { W2X_LOG_AS(who, error, "Input and output images must both be 8-bit or both 16-bit."); return false; }
-    } else {
-        for (int i = 0; i < count; ++i) if (srcs[i].depth != 8 || dsts[i].depth != 8) { W2X_LOG_AS(who, error, std::string(who) + " takes 8-bit frames (16-bit images go through renderGray())."); return false; }
-    }
-    const bool deep16 = depth == 16;
-    const size_t bps = deep16 ? 2 : 1;
-    if (rows <= 0 || cols <= 0) { W2X_LOG_AS(who, error, "Input image is empty or has an invalid step."); return false; }
-    const Impl::Target target = impl->target_size(resizeFilter, dsts[0], rows, cols);
-    const int out_rows = target.rows, out_cols = target.cols;
-    if (resizeFilter >= 0) {
-        const std::string why = impl->resize_problem(rows, cols, out_rows, out_cols, resizeFilter);
-        if (!why.empty()) { W2X_LOG_AS(who, error, why); return false; }
-    }
-    for (int i = 0; i < count; ++i) {
-        if (srcs[i].rows != rows || srcs[i].cols != cols) { W2X_LOG_AS(who, error, "Input images must be of one size."); return false; }
-        if (!srcs[i].data || srcs[i].step < (size_t)cols * bps) { W2X_LOG_AS(who, error, "Input image is empty or has an invalid step."); return false; }
-        if (!dsts[i].data || dsts[i].rows != out_rows || dsts[i].cols != out_cols || dsts[i].step < (size_t)out_cols * bps) {
-            W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(out_cols) + "x" + std::to_string(out_rows) + ".");
-            return false;
-        }
-    }
-    TileGrid grid;
-    if (const std::string why = impl->frame_grid(rows, cols, grid); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
-    const StripPlan sp = strip_plan(grid, cols * s, impl->plan.Tout, 0, 1);
-    const size_t in_step = Impl::gray_step(cols, deep16), out_step = Impl::gray_step(out_cols, deep16);
-    if (single) {
-        impl->ensure(impl->d_frame, impl->frame_cap, in_step * rows);
-        impl->ensure(impl->d_out, impl->out_cap, out_step * out_rows);
-    } else impl->sequence_buffers(in_step * rows, out_step * out_rows);
-    impl->deep = false;
-    impl->last_rows = impl->last_cols = 0;   // (d_frame / d_out hold one plane: not replayed by benchResident / residentOutput / profileFrame)
-    impl->sequence_slots(grid, sp);
-    impl->one_part_stale = false;
-    impl->job.kind = Impl::Job::GRAY; impl->job.gray.deep = deep16;
-    if (target.resized) impl->job_resize(rows, cols, out_rows, out_cols, resizeFilter, 1);
-    auto up = [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dev, in_step, srcs[i].data, srcs[i].step, (size_t)cols * bps, rows, hipMemcpyHostToDevice, on)); };
-    auto down = [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dsts[i].data, dsts[i].step, dev, out_step, (size_t)out_cols * bps, out_rows, hipMemcpyDeviceToHost, on)); };
-    if (single) {
-        hipStream_t stream = impl->stream;
-        up(0, impl->d_frame, stream);
-        hipAssert(hipEventRecord(impl->ev0, stream));
-        impl->run_frame(rows, cols, grid, true, sp);
-        hipAssert(hipEventRecord(impl->ev1, stream));
-        down(0, impl->d_out, stream);
-        hipAssert(hipStreamSynchronize(stream));
-        hipAssert(hipEventElapsedTime(&impl->last_ms, impl->ev0, impl->ev1));
-        return true;
-    }
-    impl->last_ms = impl->run_sequence(count, rows, cols, grid, sp, up, down) / count;
+    Impl::FrameCall c;
+    if (const std::string why = impl->gray_check(srcs, dsts, count, resizeFilter, who, single, c); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
+    impl->job.kind = Impl::Job::GRAY; impl->job.gray.deep = srcs[0].depth == 16;
+    impl->run_packed_call(c, srcs, dsts, count, single, resizeFilter, srcs[0].depth / 8);
     return true;
     });
 }
