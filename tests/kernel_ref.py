@@ -139,6 +139,76 @@ def image_head(y, tiw, tib, B, Mrows, aW, clip=None, f16_model=False):
     return h.reshape(B, Hr, aW, 4, 4, 4).transpose(0, 1, 3, 2, 4, 5).reshape(B, 4 * Hr, 4 * aW, 4)
 
 
+# ---- the general implicit GEMM (kernels.h GemmParams; k_gemm.hip and the kernels specialised from it: k_stem.hip, k_conv48.hip, k_pixgemm.hip)
+def activation(v, act, alpha=0.0):
+    """GemmParams::act: 0 none, 1 LeakyReLU(alpha), 2 GELU (exact erf), 3 ReLU, 4 sigmoid."""
+    if act == 1:
+        return np.where(v > 0, v, v * alpha)
+    if act == 2:
+        return gelu(v)
+    if act == 3:
+        return np.maximum(v, 0.0)
+    if act == 4:
+        return 1.0 / (1.0 + np.exp(-v))
+    return v
+
+
+def gemm_ref(params, f16_model=False):
+    """GemmParams restated in float64.  `params` (a dict; absent keys take the struct's defaults):
+      a [B][Hs][Ws][Cs] with origin a_y0 / a_x0; amode 0 rows, 1 rows through win_table, 2 kh x kw taps at `stride` (k = (ky * kw + kx) * Cs + c);
+      Mrows rows per image, row m at pixel (m // aW, m % aW) (amode 1: win_table[m] instead of m); wt [N][>= K] (columns past K ignored), bias [N];
+      ln: rstd * (acc - mean * csum) with (mean, rstd) = stats_in [B][Hs][Ws][2] at the row's input pixel; act / alpha; res, res2 (maps with origins
+      res_y0 / res_x0, res2_y0 / res2_x0, indexed by the OUTPUT pixel); clip (lo, hi) or None; out_shape (Hs, Ws, Cs); omode 0 rows, 1 scatter
+      through win_table (pixel = divmod(table, out Ws)), 2 pixel shuffle by r with column (dy * r + dx) * Cs + c; stats (bool): (mean, rstd) over the
+      Cout stored channels with ln_eps.
+    Returns {"out": [B][Hs][Ws][Cs] (NaN where nothing is stored), "stats": [B][Hs][Ws][2] (likewise) or None}.
+    f16_model=True rounds to fp16 where gemm_kernel stores: the activated value (its LDS tile) and the final one after the skip adds and the clip.  The
+    kernels with a single store (stem_kernel, conv48_kernel, merge_kernel, toimage_kernel, pixgemm_kernel without res) round once, which is the same
+    thing: with no skip add in between, the second rounding (and the clip between fp16 bounds) finds an fp16 value."""
+    g = lambda k, d=None: params.get(k, d)
+    r16 = f16 if f16_model else (lambda v: v)
+    a = np.asarray(params["a"], dtype=np.float64)
+    B, Hs, Ws, Cs = a.shape
+    amode, kh, kw, stride = g("amode", 0), g("kh", 1), g("kw", 1), g("stride", 1)
+    Mrows, aW, K, N = params["Mrows"], params["aW"], params["K"], params["N"]
+    m = np.arange(Mrows)
+    src = np.asarray(params["win_table"], dtype=np.int64)[:Mrows] if amode == 1 else m
+    py, px = (src // aW) * stride + g("a_y0", 0), (src % aW) * stride + g("a_x0", 0)
+    if amode == 2:
+        ky, kx = np.meshgrid(np.arange(kh), np.arange(kw), indexing="ij")
+        A = a[:, py[:, None, None] + ky[None], px[:, None, None] + kx[None], :].reshape(B, Mrows, kh * kw * Cs)[..., :K]
+    else:
+        A = a[:, py, px, :K]
+    v = A @ np.asarray(params["wt"], dtype=np.float64)[:, :K].T                     # [B][Mrows][N]
+    if g("ln", 0):
+        st = np.asarray(params["stats_in"], dtype=np.float64)[:, py, px]             # [B][Mrows][2]
+        v = st[..., 1:2] * (v - st[..., 0:1] * np.asarray(params["csum"], dtype=np.float64))
+    if g("bias") is not None:
+        v = v + np.asarray(params["bias"], dtype=np.float64)
+    v = r16(activation(v, g("act", 0), g("alpha", 0.0)))
+    oHs, oWs, oCs = params["out_shape"]
+    omode, r = g("omode", 0), g("r", 1) if g("omode", 0) == 2 else 1
+    dst = np.asarray(params["win_table"], dtype=np.int64)[:Mrows] if omode == 1 else m
+    oy, ox = (dst // oWs, dst % oWs) if omode == 1 else (m // aW, m % aW)
+    out = np.full((B, oHs, oWs, oCs), np.nan)
+    stats = np.full((B, oHs, oWs, 2), np.nan) if g("stats", False) else None
+    ncol = oCs if omode == 2 else N
+    for sg in range(r * r):
+        dy, dx = sg // r, sg % r
+        Y, X = oy * r + dy, ox * r + dx
+        t = v[..., sg * ncol:(sg + 1) * ncol]
+        for key in ("res", "res2"):
+            if g(key) is not None:
+                t = t + np.asarray(params[key], dtype=np.float64)[:, Y + g(key + "_y0", 0), X + g(key + "_x0", 0), :ncol]
+        if g("clip") is not None:
+            t = np.clip(t, g("clip")[0], g("clip")[1])
+        t = r16(t)
+        out[:, Y, X, :ncol] = t
+        if stats is not None:
+            stats[:, Y, X] = row_stats(t[..., :g("Cout", ncol)], g("ln_eps", 1e-5))
+    return {"out": out, "stats": stats}
+
+
 # ---- the large-input formula (tools/kernel_check/transformer_check.cpp gen_x16)
 _M64 = (1 << 64) - 1
 
@@ -177,12 +247,12 @@ def error_metrics(got, exact):
             "mean_ulp": float(d.mean()), "n": int(d.size)}
 
 
-# ---- the harness (tools/kernel_check/transformer_check.cpp): host code only, built like the w2x command line
-def build_harness(exe):
+# ---- the harnesses (tools/kernel_check/transformer_check.cpp, conv_check.cpp): host code only, built like the w2x command line
+def build_harness(exe, source="transformer_check.cpp"):
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     subprocess.run(["g++", "-std=c++17", "-O2", "-fopenmp", "-Wall", "-D__HIP_PLATFORM_AMD__", "-I/opt/rocm/include",
-                    "-I" + os.path.join(root, "waifu2x-tensorrt_amd", "csrc"), os.path.join(root, "tools", "kernel_check", "transformer_check.cpp"),
+                    "-I" + os.path.join(root, "waifu2x-tensorrt_amd", "csrc"), os.path.join(root, "tools", "kernel_check", source),
                     "-o", str(exe), "-L/opt/rocm/lib", "-lamdhip64", "-ldl", "-Wl,-rpath,/opt/rocm/lib"], check=True, timeout=300)
     return str(exe)

@@ -124,3 +124,85 @@ def test_large_input_formula_matches_the_harness(tmp_path):
         want = kr.gen_rows(rows, C, 77)
         assert got.tobytes() == want.tobytes()
         assert len({r.tobytes() for r in want}) == len(set(rows.tolist()))     # distinct rows stay distinct
+
+
+# ---- gemm_ref (GemmParams in float64) against torch float64
+def test_gemm_ref_convolutions_match_torch_conv2d():
+    rng = np.random.default_rng(6)
+    for (kh, stride, Cin, N, y0, x0, act) in ((3, 1, 48, 96, 1, 2, 1), (3, 1, 4, 32, 0, 0, 0), (2, 2, 96, 192, 0, 0, 0), (2, 2, 8, 16, 2, 4, 3)):
+        B, Ho, Wo = 2, 5, 7
+        Hs, Ws = y0 + (Ho - 1) * stride + kh + 1, x0 + (Wo - 1) * stride + kh + 2
+        a = kr.f16(rng.normal(0, 1, (B, Hs, Ws, Cin)))
+        w = kr.f16(rng.normal(0, 0.1, (N, Cin, kh, kh)))            # torch layout [N][C][ky][kx]
+        bias = rng.normal(0, 0.1, N)
+        K = kh * kh * Cin
+        wt = np.zeros((N, (K + 7) // 8 * 8))
+        wt[:, :K] = w.transpose(0, 2, 3, 1).reshape(N, K)           # k = (ky * kw + kx) * Cin + c
+        got = kr.gemm_ref(dict(a=a, a_y0=y0, a_x0=x0, amode=2, kh=kh, kw=kh, stride=stride, Mrows=Ho * Wo, aW=Wo, K=K, N=N, wt=wt, bias=bias, act=act, alpha=0.1,
+                               out_shape=(Ho + 1, Wo + 2, N)))["out"]
+        t = torch.from_numpy(a).permute(0, 3, 1, 2)[:, :, y0:, x0:]
+        ref = F.conv2d(t, torch.from_numpy(w), torch.from_numpy(bias), stride=stride)[:, :, :Ho, :Wo]
+        ref = {0: ref, 1: F.leaky_relu(ref, 0.1), 3: F.relu(ref)}[act].permute(0, 2, 3, 1).numpy()
+        assert np.abs(got[:, :Ho, :Wo] - ref).max() <= 1e-12
+        assert np.isnan(got[:, Ho:]).all() and np.isnan(got[:, :, Wo:]).all()      # the rest of the view is not stored
+
+
+def test_gemm_ref_pixel_shuffle_matches_torch():
+    """omode 2 puts column (dy * r + dx) * Cs + c at sub-pixel (dy, dx), channel c; torch's pixel_shuffle reads channel c * r * r + dy * r + dx."""
+    rng = np.random.default_rng(7)
+    for r, Cs, K in ((2, 96, 192), (4, 4, 96)):
+        B, H, W, N = 2, 3, 5, r * r * Cs
+        a = kr.f16(rng.normal(0, 1, (B, H, W, K)))
+        wt, bias = _weights(rng, N, K), rng.normal(0, 0.1, N)
+        res = kr.f16(rng.normal(0, 1, (B, r * H + 2, r * W + 3, Cs)))
+        got = kr.gemm_ref(dict(a=a, Mrows=H * W, aW=W, K=K, N=N, wt=wt, bias=bias, omode=2, r=r, out_shape=(r * H, r * W, Cs), res=res, res_y0=1, res_x0=2,
+                               clip=(-1.0, 1.5)))["out"]
+        lin = F.linear(torch.from_numpy(a), torch.from_numpy(wt), torch.from_numpy(bias))                     # [B][H][W][(dy dx c)]
+        chan_major = lin.reshape(B, H, W, r * r, Cs).permute(0, 4, 3, 1, 2).reshape(B, Cs * r * r, H, W)       # [B][(c dy dx)][H][W]
+        ref = F.pixel_shuffle(chan_major, r).permute(0, 2, 3, 1) + torch.from_numpy(res)[:, 1:1 + r * H, 2:2 + r * W]
+        assert np.abs(got - torch.clamp(ref, -1.0, 1.5).numpy()).max() <= 1e-12
+
+
+def test_gemm_ref_folded_layer_norm_matches_torch():
+    """LayerNorm folded as lower.cpp does it: W' = W * gamma, csum = row sums of W', bias' = bias + W beta; the kernel gets the rows' (mean, rstd)."""
+    rng = np.random.default_rng(8)
+    B, H, W, C, N = 2, 4, 6, 96, 192
+    a = kr.f16(rng.normal(3, 2, (B, H, W, C)))
+    w, bias, gamma, beta = rng.normal(0, 0.1, (N, C)), rng.normal(0, 0.1, N), rng.normal(1, 0.1, C), rng.normal(0, 0.1, C)
+    wt = w * gamma
+    for act in (0, 2, 4):
+        got = kr.gemm_ref(dict(a=a, Mrows=H * W, aW=W, K=C, N=N, wt=wt, bias=bias + w @ beta, ln=1, csum=wt.sum(axis=1), stats_in=kr.row_stats(a, 1e-5),
+                               act=act, out_shape=(H, W, N), stats=True, Cout=N, ln_eps=1e-5))
+        t = F.linear(F.layer_norm(torch.from_numpy(a), (C,), torch.from_numpy(gamma), torch.from_numpy(beta), eps=1e-5), torch.from_numpy(w), torch.from_numpy(bias))
+        ref = {0: t, 2: F.gelu(t, approximate="none"), 4: torch.sigmoid(t)}[act]
+        assert np.abs(got["out"] - ref.numpy()).max() <= 1e-12
+        assert np.abs(got["stats"][..., 0] - ref.mean(-1).numpy()).max() <= 1e-12
+        assert np.abs(got["stats"][..., 1] / torch.rsqrt(ref.var(-1, unbiased=False) + 1e-5).numpy() - 1).max() <= 1e-12
+
+
+def test_gemm_ref_window_modes_match_roll_and_partition():
+    rng = np.random.default_rng(9)
+    B, H, W, C = 2, 12, 18, 96
+    a = kr.f16(rng.normal(0, 1, (B, H, W, C)))
+    wt, bias = _weights(rng, C, C), rng.normal(0, 0.1, C)
+    table = kr.window_table(H, W, 3, 3)
+    lin = F.linear(torch.from_numpy(a), torch.from_numpy(wt), torch.from_numpy(bias))
+    # amode 1: rows come out in window order of the rolled map
+    got = kr.gemm_ref(dict(a=a, amode=1, win_table=table, Mrows=H * W, aW=W, K=C, N=C, wt=wt, bias=bias, out_shape=(H, W, C)))["out"]
+    win = lin.roll((-3, -3), dims=(1, 2)).reshape(B, H // 6, 6, W // 6, 6, C).permute(0, 1, 3, 2, 4, 5).reshape(B, H, W, C)
+    assert np.abs(got - win.numpy()).max() <= 1e-12
+    # omode 1: window-order rows go back to their pixels, plus a skip connection read at the OUTPUT pixel
+    res = kr.f16(rng.normal(0, 1, (B, H, W, C)))
+    got = kr.gemm_ref(dict(a=win.numpy(), omode=1, win_table=table, Mrows=H * W, aW=W, K=C, N=C, wt=np.eye(C), out_shape=(H, W, C), res=res))["out"]
+    assert np.abs(got - (lin.numpy() + res)).max() <= 1e-12
+
+
+def test_gemm_ref_fp16_model_rounds_before_and_after_the_skip_adds():
+    a = np.array([[[[1.0, 0, 0, 0, 0, 0, 0, 0]]]])
+    wt = np.zeros((8, 8)); wt[0, 0] = 1.0 + 2.0 ** -11 + 2.0 ** -20            # just above a tie: fp16 rounds it up to 1 + 2^-10, and the skip add makes the next tie
+    res = np.full((1, 1, 1, 8), 2.0 ** -11)
+    p = dict(a=a, Mrows=1, aW=1, K=8, N=8, wt=wt, out_shape=(1, 1, 8), res=res)
+    exact, model = kr.gemm_ref(p)["out"][0, 0, 0, 0], kr.gemm_ref(p, f16_model=True)["out"][0, 0, 0, 0]
+    assert exact == 1.0 + 2.0 ** -10 + 2.0 ** -20
+    assert model == float(np.float16(np.float64(np.float16(wt[0, 0])) + 2.0 ** -11)) == 1.0 + 2.0 ** -9
+    assert float(np.float16(exact)) == 1.0 + 2.0 ** -10                         # a single rounding of the exact sum lands elsewhere

@@ -222,7 +222,7 @@ bool conv48_supported(const GemmParams& p) {
     if (p.a.Cs != CIN || p.N != N || p.K != 9 * CIN || p.out.Cs != N || p.aW <= 0 || p.Mrows % p.aW) return false;
     const int Ho = p.Mrows / p.aW, Wo = p.aW;
     if ((size_t)p.B * p.a.Hs * p.a.Ws * CIN * 2 >= ((size_t)1 << 32) - 65536) return false;   // the halo tile is fetched through a 32-bit buffer resource
-    return p.a.y0 + Ho + 2 <= p.a.Hs && p.a.x0 + Wo + 2 <= p.a.Ws && p.out.Hs >= Ho && p.out.Ws >= Wo;
+    return p.a.y0 >= 0 && p.a.x0 >= 0 && p.a.y0 + Ho + 2 <= p.a.Hs && p.a.x0 + Wo + 2 <= p.a.Ws && p.out.Hs >= Ho && p.out.Ws >= Wo && p.B > 0;
 }
 
 hipError_t launch_conv48(const GemmParams& p, hipStream_t s) {

@@ -321,7 +321,7 @@ hipError_t launch_cfg(const GemmParams& p, hipStream_t s) {
 
 // Tile selection.  BN follows N (all widths in these networks are multiples of 16 after padding); KB = 96 when it
 // divides K (Swin C = 96/192, 3x3 convs over 32/64/128/256 channels), else 64.
-hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
+static hipError_t launch_gemm_run(const GemmParams& p, hipStream_t s) {
     if ((p.a_scale && (p.a.Cs == 4 || p.a.Cs % 8)) || (p.res_scale && (p.out.Cs == 4 || !p.res.p))) return hipErrorInvalidValue;   // gates ride on 8-half pieces
     const bool op4 = p.out.Cs == 4;
     if (p.a.Cs == 4) {                       // first convolution: 4 stored input channels, K = 36
@@ -354,5 +354,34 @@ hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
     }
 }
 
-// widths whose rows fit one workgroup tile of launch_gemm() (bn >= N): only those can carry LayerNorm statistics out of the epilogue
+// gemm_kernel forms the element offsets of its A rows and the pixel indices of res / res2 / out as 32-bit ints: a pass whose maps reach 2^31 of either
+// is cut into runs of whole images (row tiles never straddle images and nothing is reduced across them, so the result is the single launch's bit for bit),
+// every per-image pointer moved to the run's first image.  One image alone past the limit is refused.
+hipError_t launch_gemm(const GemmParams& p, hipStream_t s) {
+    const long lim = 0x7FFFFFFFl;
+    const long a_img = (long)p.a.Hs * p.a.Ws * p.a.Cs, out_img = (long)p.out.Hs * p.out.Ws;
+    const long res_img = p.res.p ? (long)p.res.Hs * p.res.Ws : 0, res2_img = p.res2.p ? (long)p.res2.Hs * p.res2.Ws : 0;
+    long worst = a_img;                  // per image: halves of a, pixels of the other maps
+    for (const long v : {out_img, res_img, res2_img}) worst = v > worst ? v : worst;
+    if (p.B <= 0 || worst <= 0 || (long)p.B * worst <= lim) return launch_gemm_run(p, s);   // (every pass of the shipped plans)
+    const long per_run = lim / worst;
+    if (per_run < 1) return hipErrorInvalidValue;
+    const int tpi = (p.Mrows + kGemmBM - 1) / kGemmBM;
+    for (long b0 = 0; b0 < p.B; b0 += per_run) {
+        GemmParams q = p;
+        q.B = (int)(p.B - b0 < per_run ? p.B - b0 : per_run);
+        q.a.p = (char*)p.a.p + (size_t)b0 * a_img * 2;
+        q.out.p = (char*)p.out.p + (size_t)b0 * out_img * p.out.Cs * 2;
+        if (p.res.p) q.res.p = (char*)p.res.p + (size_t)b0 * res_img * p.res.Cs * 2;
+        if (p.res2.p) q.res2.p = (char*)p.res2.p + (size_t)b0 * res2_img * p.res2.Cs * 2;
+        if (p.stats_in) q.stats_in = p.stats_in + (size_t)b0 * p.a.Hs * p.a.Ws * 2;
+        if (p.stats_out) q.stats_out = p.stats_out + (size_t)b0 * out_img * 2;
+        if (p.pool_out) q.pool_out = p.pool_out + (size_t)b0 * tpi * p.out.Cs;
+        if (p.a_scale) q.a_scale = p.a_scale + (size_t)b0 * p.a.Cs;
+        if (p.res_scale) q.res_scale = p.res_scale + (size_t)b0 * p.res.Cs;
+        if (hipError_t e = launch_gemm_run(q, s); e != hipSuccess) return e;
+    }
+    return hipSuccess;
+}
+
 }  // namespace w2x

@@ -642,6 +642,7 @@ bool pixgemm_supported(const GemmParams& p) {
     if ((p.a_scale || p.res_scale) && p.a.Cs != 64 && p.a.Cs != 128) return false;   // gated operands: compiled into cunet's shapes only (PixCfg / MergeCfg GATES)
     if (!off && p.wt_frag && p.amode == 2 && p.kh == 2 && p.kw == 2 && p.stride == 2 && p.omode == 0 && !p.ln && (p.act == 0 || p.act == 1) && !p.has_clip &&
         !p.stats_out && !p.pool_out && !p.res.p && !p.res2.p && p.out.Cs == p.N && p.Kw == p.K && p.K == 4 * p.a.Cs && (long)p.out.Hs * p.out.Ws == p.Mrows && p.out.Ws == p.aW &&
+        p.a.y0 >= 0 && p.a.x0 >= 0 && p.a.y0 + 2 * p.out.Hs <= p.a.Hs && p.a.x0 + 2 * p.out.Ws <= p.a.Ws &&   // every 2x2 patch inside the input view
         (((p.a.Cs == 96 || p.a.Cs == 192) && p.N == 192 && (size_t)p.B * p.a.Hs * p.a.Ws * p.a.Cs * 2 < 0xFFFF0000u) ||   // (merge_kernel reads its map through 32-bit offsets)
          (p.a.Cs == 64 && p.N == 64) || (p.a.Cs == 128 && p.N == 128))) return true;   // patch merge / cunet down convolution
     // rows = a Linear, or a 1x1 convolution: cunet's 2x2 stride-2 ConvTranspose is lowered to 1x1 + pixel shuffle with LeakyReLU and a
@@ -650,6 +651,9 @@ bool pixgemm_supported(const GemmParams& p) {
     if (off || !p.wt_frag || p.omode != 2 || !rows || p.ln || (p.act != 0 && p.act != 1) || p.stats_out || p.pool_out || p.res2.p) return false;
     if (p.stride != 1 || p.a.y0 || p.a.x0 || p.a.Ws != p.aW || (long)p.a.Hs * p.a.Ws != p.Mrows || p.a.Cs != p.K || p.Kw != p.K) return false;
     if (p.N != p.r * p.r * p.out.Cs) return false;
+    // every sub-pixel inside the output view, every skip pixel inside the skip view (the kernels store / fetch them without a test of their own)
+    if (p.r < 1 || p.out.Hs < p.r * p.a.Hs || p.out.Ws < p.r * p.a.Ws) return false;
+    if (p.res.p && (p.res.y0 < 0 || p.res.x0 < 0 || p.res.y0 + p.r * p.a.Hs > p.res.Hs || p.res.x0 + p.r * p.a.Ws > p.res.Ws)) return false;
     if (p.K == 96 && p.out.Cs == 4 && p.r == 4 && p.N == 64 && !p.res.p && p.act == 0 && p.amode == 0 && !p.a_scale) return true;   // image head
     if (p.has_clip || p.Cout != p.out.Cs || (p.res.p && p.res.Cs != p.out.Cs)) return false;
     {   // pixgemm_kernel addresses its three maps with 32-bit byte offsets and keeps the bias of at most 16 sub-pixels in LDS

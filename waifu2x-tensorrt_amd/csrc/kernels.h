@@ -197,6 +197,7 @@ struct ComposeParams {
     int y0 = 0, y1 = 0;
 };
 
+// (a pass whose maps reach 2^31 halves of a, or pixels of res / res2 / out, is issued as runs of whole images; one image past that is hipErrorInvalidValue)
 hipError_t launch_gemm(const GemmParams& p, hipStream_t s);
 bool pixgemm_supported(const GemmParams& p);                    // k_pixgemm.hip: streaming kernel for pixel-shuffle projections
 hipError_t launch_pixgemm(const GemmParams& p, hipStream_t s);
