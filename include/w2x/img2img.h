@@ -43,6 +43,15 @@ struct YuvImage {
     int bits = 8;
     YuvLayout layout = YuvLayout::I420;
 };
+// Extension: a planar RGB frame - three planes of rows x cols samples, each with its own pointer and step (bytes).  planes[0] = R, planes[1] = G,
+// planes[2] = B (a gbrp AVFrame: data[2], data[0], data[1]); the order carries no meaning of its own, the caller orders the pointers.
+// bits: 8 (uint8), 10 / 12 / 16 (little-endian uint16, the code in the LOW bits), 32 (IEEE float32, nominal [0, 1]); u16 / f32 samples aligned to their size.
+struct PlanarImage {
+    uint8_t* planes[3] = {nullptr, nullptr, nullptr};
+    size_t steps[3] = {0, 0, 0};
+    int rows = 0, cols = 0;
+    int bits = 8;
+};
 enum class YuvMatrix { BT601 = 0, BT709 = 1, BT2020 = 2 };   // (Kr, Kb) = (0.299, 0.114), (0.2126, 0.0722), (0.2627, 0.0593); BT.2020 non-constant luminance
 enum class YuvRange { Limited = 0, Full = 1 };               // "tv": Y 16..235, C 16..240 (times 2^(bits-8)); "pc": 0 .. 2^bits - 1
 struct YuvFormat {
@@ -134,6 +143,22 @@ public:
     // renderGrayResized() on frame i.  16-bit frames and frames of differing sizes: false.  No progress is reported.
     bool renderSequenceGray(const Image* srcs, Image* dsts, int count);
     bool renderSequenceGrayResized(const Image* srcs, Image* dsts, int count, ResizeFilter filter = ResizeFilter::Bicubic);
+    // Extension: planar RGB frames.  src.bits and dst.bits are independent (8 in and 10, 16 or float out is allowed).  The arithmetic is render()'s,
+    // widened to the depths:
+    //   in, integer:  the tile pixel is (r, g, b), each sample min(code, 2^bits - 1) * fl32(1 / (2^bits - 1)) - at 8 and 16 bits render()'s fl32(1/255) / fl32(1/65535);
+    //   in, float:    min(max(x, 0), 1), NaN -> 0;
+    //   out:          render()'s three sums per pixel (resized: renderResized()'s tap tables and tap order on the three canvas planes), then
+    //                 integer sat(rint(x * (2^bits - 1))), float min(max(x, 0), 1) stored as fp32, never rounded to a code.
+    // So at 8 / 8 bits renderPlanar() gives the planes of render() of the interleaved frame, byte for byte, at 16 / 16 bits those of the 16-bit render(); the same
+    // holds for renderPlanarResized() against renderResized(); at the scaled size the resized call is the plain one; a sequence gives the bytes of the single calls.
+    // The single calls report progress as render(): ceil(N * steps / batchSize) batches.  Other depths, empty frames, missing planes, short steps, misaligned
+    // u16 / f32 samples, other sizes: false (message callback).
+    bool renderPlanar(const PlanarImage& src, PlanarImage& dst);
+    bool renderPlanarResized(const PlanarImage& src, PlanarImage& dst, ResizeFilter filter = ResizeFilter::Bicubic);
+    // Planar frames through renderSequence()'s pipeline (page-locked buffers: allocHost()): every depth, one pair of depths and one size per sequence; three 2-D
+    // copies per frame each way.  No progress is reported.
+    bool renderSequencePlanar(const PlanarImage* srcs, PlanarImage* dsts, int count);
+    bool renderSequencePlanarResized(const PlanarImage* srcs, PlanarImage* dsts, int count, ResizeFilter filter = ResizeFilter::Bicubic);
     void* allocHost(size_t bytes);
     void freeHost(void* data);
     // Page-locks caller-owned memory in place.  Only whole pages are accepted (data and bytes multiples of 4096): a registration
@@ -171,6 +196,7 @@ private:
     bool renderRgbaFrame(const Image& src, Image& dst, const RgbaOptions& opt, int resizeFilter, const char* who);   // resizeFilter >= 0: renderRgbaResized
     bool runSequenceRgba(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt, int resizeFilter, const char* who);
     bool runGray(const Image* srcs, Image* dsts, int count, int resizeFilter, const char* who, bool single);   // single: renderGray / renderGrayResized (8 or 16 bits, progress)
+    bool runPlanar(const PlanarImage* srcs, PlanarImage* dsts, int count, int resizeFilter, const char* who, bool single);   // single: renderPlanar / renderPlanarResized (progress)
     bool runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, int resizeFilter, const char* who);   // resizeFilter >= 0: renderYuvResized
     std::unique_ptr<Impl> impl;
 };

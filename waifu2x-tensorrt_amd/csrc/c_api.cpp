@@ -1,6 +1,7 @@
 // Flat C ABI over w2x::Img2Img (declared in include/w2x/c_api.h, which cites the reference interfaces).
 #include "../../include/w2x/c_api.h"
 #include "../../include/w2x/c_api_gray.h"
+#include "../../include/w2x/c_api_planar.h"
 #include <mutex>
 
 #include <cstring>
@@ -80,6 +81,24 @@ static w2x::YuvImage yuv_image(const void* const* planes, const size_t* steps, i
     return f;
 }
 static w2x::YuvFormat yuv_format(int matrix, int range) { w2x::YuvFormat f; f.matrix = (w2x::YuvMatrix)matrix; f.range = (w2x::YuvRange)range; return f; }
+// the planar RGB renders (include/w2x/c_api_planar.h): three planes R, G, B with their steps; the engine refuses unknown depths
+static w2x::PlanarImage planar_image(const void* const* planes, const size_t* steps, int rows, int cols, int bits) {
+    w2x::PlanarImage f;
+    for (int k = 0; k < 3; ++k) { f.planes[k] = planes ? (uint8_t*)const_cast<void*>(planes[k]) : nullptr; f.steps[k] = steps ? steps[k] : 0; }
+    f.rows = rows; f.cols = cols; f.bits = bits;
+    return f;
+}
+struct PlanarSequence { std::vector<w2x::PlanarImage> src, dst; };
+// the frames of a planar sequence entry: frame i's planes at [3i .. 3i + 2], one set of steps for the sequence
+static PlanarSequence planar_sequence(const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                                      void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int count) {
+    PlanarSequence q; q.src.reserve(count); q.dst.reserve(count);
+    for (int i = 0; i < count; ++i) {
+        q.src.push_back(planar_image(src_planes + 3 * i, src_steps, rows, cols, src_bits));
+        q.dst.push_back(planar_image(dst_planes + 3 * i, dst_steps, dst_rows, dst_cols, dst_bits));
+    }
+    return q;
+}
 struct YuvSequence { std::vector<w2x::YuvImage> src, dst; };
 // the frames of a YUV sequence entry: frame i's planes at [3i .. 3i + 2], one set of steps for the sequence
 static YuvSequence yuv_sequence(const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits, int src_layout,
@@ -272,6 +291,37 @@ int w2x_render_sequence_gray_resized(w2x_engine* e, const uint8_t* const* srcs, 
     if (!sequence_ok(e, count, srcs, dsts) || !resize_filter(e, filter, "w2x_render_sequence_gray_resized", f)) return 0;
     ImageSequence q = image_sequence(srcs, image(nullptr, rows, cols, src_step), dsts, image(nullptr, dst_rows, dst_cols, dst_step), count);
     return e->engine.renderSequenceGrayResized(q.src.data(), q.dst.data(), count, f) ? 1 : 0;
+}
+// planar RGB frames (include/w2x/c_api_planar.h): the sizes of both sides are explicit, as in the YUV entries
+int w2x_render_planar(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                      void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits) {
+    if (!e) return 0;
+    w2x::PlanarImage d = planar_image(dst_planes, dst_steps, dst_rows, dst_cols, dst_bits);
+    return e->engine.renderPlanar(planar_image(src_planes, src_steps, rows, cols, src_bits), d) ? 1 : 0;
+}
+int w2x_render_planar_resized(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                              void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int filter) {
+    w2x::ResizeFilter f;
+    if (!e || !resize_filter(e, filter, "w2x_render_planar_resized", f)) return 0;
+    w2x::PlanarImage d = planar_image(dst_planes, dst_steps, dst_rows, dst_cols, dst_bits);
+    return e->engine.renderPlanarResized(planar_image(src_planes, src_steps, rows, cols, src_bits), d, f) ? 1 : 0;
+}
+int w2x_render_sequence_planar(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                               void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int count) {
+    if (!sequence_ok(e, count, src_planes, dst_planes)) return 0;
+    PlanarSequence q = planar_sequence(src_planes, src_steps, rows, cols, src_bits, dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, count);
+    return e->engine.renderSequencePlanar(q.src.data(), q.dst.data(), count) ? 1 : 0;
+}
+int w2x_render_sequence_planar_resized(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                                       void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int count, int filter) {
+    w2x::ResizeFilter f;
+    if (!sequence_ok(e, count, src_planes, dst_planes) || !resize_filter(e, filter, "w2x_render_sequence_planar_resized", f)) return 0;
+    PlanarSequence q = planar_sequence(src_planes, src_steps, rows, cols, src_bits, dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, count);
+    return e->engine.renderSequencePlanarResized(q.src.data(), q.dst.data(), count, f) ? 1 : 0;
+}
+size_t w2x_planar_plane_bytes(int rows, int cols, int bits) {
+    if (rows <= 0 || cols <= 0 || !(bits == 8 || bits == 10 || bits == 12 || bits == 16 || bits == 32)) return 0;
+    return (size_t)rows * cols * (bits == 32 ? 4 : bits > 8 ? 2 : 1);
 }
 int w2x_alpha_bleed_device(w2x_engine* e, const uint8_t* bgra, int rows, int cols, size_t bgra_step, uint8_t* bgr, size_t bgr_step, int radius) {
     if (!e) return 0;

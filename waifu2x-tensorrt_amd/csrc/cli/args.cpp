@@ -82,6 +82,11 @@ std::string usage() {
            "      --gray                  (extension) gray PNGs (colour type 0, 8- or 16-bit with --deep) stay one channel: one sample per pixel to the GPU and back,\n"
            "                              a gray PNG out; videos read through ffmpeg travel as raw gray frames.  Colour files, single images in formats\n"
            "                              only ffmpeg reads (JPEG ...) and gray + alpha PNGs (colour type 4: written as RGBA) are rendered as without it.  Not with --colorspace, not with --devices above 1\n"
+           "      --rgb-in FMT, --rgb-out FMT\n"
+           "                              (extension) {gbrp,gbrp10le,gbrp12le,gbrp16le,gbrpf32le}: videos read through ffmpeg travel as raw planar RGB frames of these\n"
+           "                              formats, 8 to 16 bits or float in, any of them out (one given: the other side is gbrp); --outscale / --outsize apply.\n"
+           "                              With --rgb-out and no --pix_fmt the encoder's format is the --rgb-out one.  Stills, single frames read through ffmpeg and\n"
+           "                              the built-in AVI route are rendered as without them.  Not with --colorspace, not with --gray\n"
            "      --tta-mode TEXT [mean]  (extension) {mean,reference}: with --tta, `mean` averages the 8 augmentations; `reference`\n"
            "                              reproduces the bytes of the reference's accumulation (img2img_render.cpp:313-316); --tta-compat = reference\n"
            "  build                       Build model\n"
@@ -89,6 +94,13 @@ std::string usage() {
 }
 
 const char* const kYuvFormats[8] = {"yuv420p", "yuv420p10le", "yuv422p", "yuv422p10le", "yuv444p", "yuv444p10le", "nv12", "p010le"};
+
+const char* const kRgbFormats[5] = {"gbrp", "gbrp10le", "gbrp12le", "gbrp16le", "gbrpf32le"};
+int rgb_format_bits(const std::string& name) {
+    const int bits[5] = {8, 10, 12, 16, 32};
+    for (int k = 0; k < 5; ++k) if (name == kRgbFormats[k]) return bits[k];
+    return 0;
+}
 
 Options parse(int argc, const char* const* argv) {
     Options o;
@@ -152,6 +164,8 @@ Options parse(int argc, const char* const* argv) {
         else if (k == "--color_range") { o.colorRange = value(i); std::transform(o.colorRange.begin(), o.colorRange.end(), o.colorRange.begin(), ::tolower); seen_range = true; }
         else if (k == "--yuv-in") o.yuvIn = value(i);
         else if (k == "--yuv-out") o.yuvOut = value(i);
+        else if (k == "--rgb-in") o.rgbIn = value(i);
+        else if (k == "--rgb-out") o.rgbOut = value(i);
         else throw std::runtime_error("The following argument was not expected: " + a[i]);
     }
     if (o.command.empty()) throw std::runtime_error("A subcommand is required");
@@ -174,6 +188,7 @@ Options parse(int argc, const char* const* argv) {
     member<std::string>("--split", o.split, {"shards", "strips"});
     member<std::string>("--precision", o.precision, {"fp16", "tf32", "fp32"});   // fp32: an addition (include/w2x/config.h)
     const bool seen_yuv_in = !o.yuvIn.empty(), seen_yuv_out = !o.yuvOut.empty();
+    const bool seen_rgb_in = !o.rgbIn.empty(), seen_rgb_out = !o.rgbOut.empty();
     if (o.command == "render") {
         if (o.inputs.empty()) throw std::runtime_error("--input is required");
         for (const auto& p : o.inputs) if (!std::filesystem::exists(p)) throw std::runtime_error("--input: Path does not exist: " + p);
@@ -217,11 +232,20 @@ Options parse(int argc, const char* const* argv) {
             if (seen_colorspace) throw std::runtime_error("--gray: not together with --colorspace (gray frames carry no chroma)");
             if (o.devices > 1) throw std::runtime_error("--gray: not with --devices " + std::to_string(o.devices) + " (gray frames are rendered on one device)");
         }
+        for (const char* opt : {"--rgb-in", "--rgb-out"}) {
+            const std::string& v = opt[6] == 'i' ? o.rgbIn : o.rgbOut;
+            if (v.empty()) continue;
+            member<std::string>(opt, v, {kRgbFormats[0], kRgbFormats[1], kRgbFormats[2], kRgbFormats[3], kRgbFormats[4]});
+            if (seen_colorspace) throw std::runtime_error(std::string(opt) + ": not together with --colorspace (planar RGB frames are not converted to YUV)");
+            if (seen_gray) throw std::runtime_error(std::string(opt) + ": not together with --gray (one raw frame format per run)");
+        }
+        if (seen_rgb_out && !seen_pixfmt) o.pixFmt = o.rgbOut;   // --pix_fmt is the encoder's format only
         if (seen_bleed) {
             if (!(o.alphaBleed >= 0 && o.alphaBleed <= 16)) throw std::runtime_error("--alpha-bleed: " + std::to_string(o.alphaBleed) + " not in [0, 16] (the radius in pixels)");
             if (o.alphaBleed > 0 && o.deep) throw std::runtime_error("--alpha-bleed: not together with --deep (the bleed works on 8-bit colour; 16-bit stills keep the colours as stored)");
         }
     } else if (seen_gray) throw std::runtime_error("--gray: only with render");
+    else if (seen_rgb_in || seen_rgb_out) throw std::runtime_error(std::string(seen_rgb_in ? "--rgb-in" : "--rgb-out") + ": only with render");
     else if (seen_outscale || seen_outsize || seen_filter || seen_colorspace || seen_range || seen_bleed || seen_skip || seen_yuv_in || seen_yuv_out)
         throw std::runtime_error(std::string(seen_yuv_in ? "--yuv-in" : seen_yuv_out ? "--yuv-out" : seen_outscale ? "--outscale" : seen_outsize ? "--outsize" : seen_filter ? "--resize-filter" : seen_colorspace ? "--colorspace" :
                                              seen_range ? "--color_range" : seen_bleed ? "--alpha-bleed" : "--alpha-skip-uniform") + ": only with render");
@@ -276,6 +300,7 @@ std::string to_json(const Options& o) {
        << ", \"colorspace\": " << (o.colorspace.empty() ? std::string("null") : q(o.colorspace)) << ", \"color_range\": " << q(o.colorRange)
        << ", \"yuv_in\": " << (o.yuvIn.empty() ? std::string("null") : q(o.yuvIn)) << ", \"yuv_out\": " << (o.yuvOut.empty() ? std::string("null") : q(o.yuvOut))
        << ", \"alpha_bleed\": " << o.alphaBleed << ", \"alpha_skip_uniform\": " << (o.alphaSkipUniform ? "true" : "false") << ", \"gray\": " << (o.gray ? "true" : "false")
+       << ", \"rgb_in\": " << (o.rgbIn.empty() ? std::string("null") : q(o.rgbIn)) << ", \"rgb_out\": " << (o.rgbOut.empty() ? std::string("null") : q(o.rgbOut))
        << ", \"codec\": " << q(o.codec) << ", \"pix_fmt\": " << q(o.pixFmt) << ", \"crf\": " << o.crf << ", \"inputs\": [";
     for (size_t i = 0; i < o.inputs.size(); ++i) os << (i ? ", " : "") << q(o.inputs[i]);
     os << "], \"model_path\": " << q(o.command == "convert" ? "" : model_path(o)) << ", \"suffix\": " << q(o.command == "convert" ? "" : output_suffix(o)) << ", \"outputs\": [";

@@ -48,12 +48,17 @@ struct Options {
                                           // the routes that render colour and alpha in two calls - --devices > 1 - the host alpha_bleed); 0 = the colours as stored
     bool alphaSkipUniform = false;        // --alpha-skip-uniform: a still whose alpha plane is one value keeps it without running the plane through the network
     bool gray = false;                    // --gray (extension, render only): gray PNGs and ffmpeg videos stay one channel (Img2Img::renderGray*)
+    std::string rgbIn, rgbOut;            // --rgb-in / --rgb-out FMT (extension, render only; kRgbFormats): videos read through ffmpeg travel as raw planar RGB frames
+                                          // of these formats (Img2Img::renderSequencePlanar*); with --rgb-out and no --pix_fmt the encoder's format is the --rgb-out one
     bool printConfig = false;             // --print-config: dump the parsed options and derived names as JSON and exit (tests)
     bool help = false;
 };
 
 // the raw frame formats of --yuv-in / --yuv-out (ffmpeg's names): planar 4:2:0, 4:2:2, 4:4:4 at 8 / 10 bits, semi-planar 4:2:0 (nv12, 10 bits: p010le)
 extern const char* const kYuvFormats[8];
+// the raw formats of --rgb-in / --rgb-out (ffmpeg's planar RGB: planes G, B, R) and the bits of a sample of each (32: float); 0 for another name
+extern const char* const kRgbFormats[5];
+int rgb_format_bits(const std::string& name);
 // throws std::runtime_error with the message to print (exit code -1 like main.cpp:147-150) on invalid input
 Options parse(int argc, const char* const* argv);
 std::string usage();

@@ -9,6 +9,9 @@
 // Extension: --gray keeps gray PNGs (colour type 0) and ffmpeg videos one channel wide: Img2Img::renderGray / renderGrayResized for stills, raw `gray` frames
 // through renderSequenceGray[Resized] for videos; colour files, single frames read through ffmpeg, gray + alpha PNGs and the built-in AVI route are rendered
 // as without it.
+// Extension: --rgb-in / --rgb-out FMT carry ffmpeg videos as raw planar RGB frames (gbrp, gbrp10le, gbrp12le, gbrp16le, gbrpf32le: planes G, B, R, contiguous)
+// through Img2Img::renderSequencePlanar[Resized], the two depths independent; stills, single frames read through ffmpeg and the built-in AVI route are
+// rendered as without them.  Over --devices N the chunks go to the engines like bgr24 chunks.
 // Extension: --devices N drives N engines - a single image is split into tile-column strips (Img2Img::renderStrip), every engine
 // writing its own columns of the shared output buffer; a video is cut into chunks of frames that go round-robin to one persistent
 // worker thread per engine (renderSequence over that engine's page-locked buffers), with one reader and one in-order writer thread.
@@ -355,12 +358,17 @@ int main(int argc, char** argv) {
                 const bool is_avi = fs::path(file).extension() == ".avi" || fs::path(file).extension() == ".AVI";
                 bool yuv = false;                                      // --colorspace on a multi-frame input read through ffmpeg: YUV frames
                 bool gray = false;                                     // --gray on an input read through ffmpeg: raw gray frames, one byte per pixel
+                bool planar = false;                                   // --rgb-in / --rgb-out on a multi-frame input read through ffmpeg: raw planar RGB frames
+                const std::string rgbIn = o.rgbIn.empty() ? "gbrp" : o.rgbIn, rgbOut = o.rgbOut.empty() ? "gbrp" : o.rgbOut;   // (one given: the other side is gbrp)
+                const int rgbInBits = cli::rgb_format_bits(rgbIn), rgbOutBits = cli::rgb_format_bits(rgbOut);
+                auto plane_bytes = [](int rows, int cols, int bits) { return (size_t)rows * cols * (bits == 32 ? 4 : bits > 8 ? 2 : 1); };
                 const std::string& rawIn = o.yuvIn.empty() ? o.pixFmt : o.yuvIn, & rawOut = o.yuvOut.empty() ? o.pixFmt : o.yuvOut;   // --yuv-in / --yuv-out
                 const RawYuv fmtIn = raw_yuv(rawIn), fmtOut = raw_yuv(rawOut);
                 if (is_avi && avi->rd.open(file, &why)) {
                     width = avi->rd.info().width; height = avi->rd.info().height; frames = avi->rd.info().frames; fps = avi->rd.info().fps;
                     source = std::move(avi);
                     if (o.gray) on_message(Severity::warn, file + ": the built-in AVI route is 24-bit only: --gray is ignored");
+                    if (!o.rgbIn.empty() || !o.rgbOut.empty()) on_message(Severity::warn, file + ": the built-in AVI route is 24-bit only: --rgb-in / --rgb-out are ignored");
                 } else {
                     if (!have_ffmpeg) throw std::runtime_error(file + ": needs ffmpeg and ffprobe on PATH (built in: .png, .ppm, .bmp, uncompressed 24-bit .avi" + (why.empty() ? "" : "; " + why) +
                                                                (o.colorspace.empty() ? "" : "; --colorspace reads and writes YUV frames through ffmpeg only") + ")");
@@ -368,18 +376,19 @@ int main(int argc, char** argv) {
                     width = pr.width; height = pr.height; frames = pr.frames; fps = pr.fps;
                     yuv = !o.colorspace.empty() && frames != 1;
                     gray = o.gray && frames != 1;                      // (a single frame is a still in a format only ffmpeg reads: rendered in colour, as without the flag)
-                    const size_t inBytes = yuv ? yuv_frame_bytes(height, width, fmtIn) : (size_t)width * height * (gray ? 1 : 3);
-                    source.reset(new PipeSource("ffmpeg -v error -i " + shell_quote(file) + " -f rawvideo -pix_fmt " + (yuv ? rawIn : std::string(gray ? "gray" : "bgr24")) + " -", inBytes));
+                    planar = (!o.rgbIn.empty() || !o.rgbOut.empty()) && frames != 1;   // (a single frame: a still, rendered as bgr24 like any other)
+                    const size_t inBytes = yuv ? yuv_frame_bytes(height, width, fmtIn) : planar ? 3 * plane_bytes(height, width, rgbInBits) : (size_t)width * height * (gray ? 1 : 3);
+                    source.reset(new PipeSource("ffmpeg -v error -i " + shell_quote(file) + " -f rawvideo -pix_fmt " + (yuv ? rawIn : planar ? rgbIn : std::string(gray ? "gray" : "bgr24")) + " -", inBytes));
                 }
                 frameIndex = 0; frameCount = frames;
                 const bool single = frames == 1;
                 std::string outFile = cli::output_path(o, file, single);
                 check_outsize(file, width, height);
                 const int outW = cli::out_dim(o, width, true), outH = cli::out_dim(o, height, false);
-                const size_t inBytes = yuv ? yuv_frame_bytes(height, width, fmtIn) : (size_t)width * height * (gray ? 1 : 3);
-                const size_t outBytes = yuv ? yuv_frame_bytes(outH, outW, fmtOut) : (size_t)outW * outH * (gray ? 1 : 3);
+                const size_t inBytes = yuv ? yuv_frame_bytes(height, width, fmtIn) : planar ? 3 * plane_bytes(height, width, rgbInBits) : (size_t)width * height * (gray ? 1 : 3);
+                const size_t outBytes = yuv ? yuv_frame_bytes(outH, outW, fmtOut) : planar ? 3 * plane_bytes(outH, outW, rgbOutBits) : (size_t)outW * outH * (gray ? 1 : 3);
                 if (have_ffmpeg) {
-                    std::string wcmd = "ffmpeg -v error -y -f rawvideo -pix_fmt " + (yuv ? rawOut : std::string(gray ? "gray" : "bgr24")) + " -s " + std::to_string(outW) + "x" + std::to_string(outH) +
+                    std::string wcmd = "ffmpeg -v error -y -f rawvideo -pix_fmt " + (yuv ? rawOut : planar ? rgbOut : std::string(gray ? "gray" : "bgr24")) + " -s " + std::to_string(outW) + "x" + std::to_string(outH) +
                                        " -r " + std::to_string(single ? 1.0 : fps) + " -i - ";
                     if (!single) wcmd += "-c:v " + o.codec + " -pix_fmt " + o.pixFmt + " -crf " + std::to_string(o.crf) + " ";
                     if (yuv) wcmd += colour_tags(o);
@@ -400,6 +409,20 @@ int main(int argc, char** argv) {
                     std::vector<Image> si(n), di(n);
                     for (int k = 0; k < n; ++k) { si[k] = Image{in[k], height, width, (size_t)width}; di[k] = Image{out[k], outH, outW, (size_t)outW}; }
                     return resize ? e.renderSequenceGrayResized(si.data(), di.data(), n, filter) : e.renderSequenceGray(si.data(), di.data(), n);
+                };
+                // a raw gbrp* frame is its planes G, B, R back to back, rows unpadded: PlanarImage wants R, G, B
+                if (planar) render = [&](Img2Img& e, uint8_t* const* in, uint8_t* const* out, int n) {
+                    std::vector<PlanarImage> si(n), di(n);
+                    auto frame = [&](uint8_t* base, int rows, int cols, int bits) {
+                        const size_t plane = plane_bytes(rows, cols, bits), step = plane / rows;
+                        PlanarImage f;
+                        f.rows = rows; f.cols = cols; f.bits = bits;
+                        f.planes[0] = base + 2 * plane; f.planes[1] = base; f.planes[2] = base + plane;
+                        f.steps[0] = f.steps[1] = f.steps[2] = step;
+                        return f;
+                    };
+                    for (int k = 0; k < n; ++k) { si[k] = frame(in[k], height, width, rgbInBits); di[k] = frame(out[k], outH, outW, rgbOutBits); }
+                    return resize ? e.renderSequencePlanarResized(si.data(), di.data(), n, filter) : e.renderSequencePlanar(si.data(), di.data(), n);
                 };
                 if (yuv) {
                     YuvFormat f;

@@ -345,17 +345,22 @@ struct Img2Img::Impl {
     // gray_step), the gather launch is gather_gray_kernel, the frame ends with compose_gray_kernel - resized with compose_canvas_gray_kernel (one fp32 plane) and
     // resample_gray_kernel.  The sample depth is the job's, not `deep`: nothing of a gray call is replayable.
     struct GrayJob { bool deep = false; };
+    // Planar RGB frames (renderPlanar, renderPlanarResized, renderSequencePlanar*): d_frame / d_out hold three planes R, G, B one after the other, each
+    // of in_bits / out_bits samples (8; 10, 12, 16 as uint16; 32 as float) with rows padded to 16 bytes (planar_layout).  The gather launch is gather_planar_kernel,
+    // the frame ends with compose_planar_kernel - resized with compose_canvas_kernel (the BGR path's own canvas) and resample_planar_kernel.
+    struct PlanarJob { int in_bits = 8, out_bits = 8; };
     // The kind of frame the running entry point renders.  Only the block "the frame formats" below branches on it: the key of the captured passes, the
     // gather (gather_tiles), the end of a frame (finish_frame), the device layout of a frame, the slot tables of a call.  The default is a plain BGR frame, not
-    // resized.  The kind is set in three places - runSequenceYuv, the RGBA calls (rgba_call), runGray - between the call's checks and run_call();
+    // resized.  The kind is set in three places - runSequenceYuv, the RGBA calls (rgba_call), runGray, runPlanar - between the call's checks and run_call();
     // entry() puts the default back on every exit, exceptions included.  `rs`: the tap tables of a resized frame's target (job_resize), else null.
     // (`deep` is not part of it: it describes the replayable frame in d_frame / d_out and outlives the call.)
     struct Job {
-        enum Kind { BGR, YUV, RGBA, GRAY } kind = BGR;
+        enum Kind { BGR, YUV, RGBA, GRAY, PLANAR } kind = BGR;
         const ResizeTables* rs = nullptr;
         YuvJob yuv;
         RgbaJob rgba;
         GrayJob gray;
+        PlanarJob planar;
     };
     Job job;
     struct JobScope { Impl* im; ~JobScope() { im->job = Job{}; } };
@@ -436,6 +441,7 @@ struct Img2Img::Impl {
     // way) and replayed from then on.  The key holds everything the captured launches bake in.
     static constexpr int kRgbaKey = 64;   // (YuvJob::key stays below 50)
     static constexpr int kGrayKey = 65;   // 65 / 66: gray frames of 8 / 16 bits
+    static constexpr int kPlanarKey = 67; // 67 .. 71: planar frames whose input samples have 8 / 10 / 12 / 16 / 32 bits
     using GraphKey = std::tuple<const void*, const void*, const void*, const void*, int, int, int, int>;   // frame, slots, slab out, arena, rows, cols, live, sample format (1: 16-bit, >= 2: YuvJob::key)
     // A pass that runs as NG tile groups is NG graphs, one per group, each a straight line of launches replayed on that group's OWN stream (fork / join
     // events between the streams are issued around the replays): a single captured graph with NG branches runs its side branches on streams the runtime
@@ -1213,6 +1219,15 @@ struct Img2Img::Impl {
         f.p[0] = base; f.p[1] = base + f.step[0] * rows; f.p[2] = layout == kYuvNV12 ? nullptr : f.p[1] + f.step[1] * ch;
         return f;
     }
+    // Planar RGB: R, G, B one after the other, every plane's rows padded to 16 bytes (gray_step's rule at 1, 2 or 4 bytes per sample)
+    static size_t planar_step(int cols, int bits) { return ((size_t)cols * planar_sample_bytes(bits) + 15) / 16 * 16; }
+    static PlanarPlanes planar_layout(uint8_t* base, int rows, int cols, int bits) {
+        PlanarPlanes f;
+        f.rows = rows; f.cols = cols; f.bits = bits;
+        for (int k = 0; k < 3; ++k) { f.step[k] = planar_step(cols, bits); f.p[k] = base + (size_t)k * f.step[k] * rows; }
+        return f;
+    }
+    static int planar_key(int bits) { return kPlanarKey + (bits == 8 ? 0 : bits == 10 ? 1 : bits == 12 ? 2 : bits == 16 ? 3 : 4); }
     static int yuv_planes(int layout) { return layout == kYuvNV12 ? 2 : 3; }
     static size_t yuv_bytes(int rows, int cols, int bits, int layout) {
         const YuvPlanes f = yuv_layout(nullptr, rows, cols, bits, layout);
@@ -1223,13 +1238,14 @@ struct Img2Img::Impl {
     // only the three places that set a job's kind and run_frame()'s hand-off of an RGBA frame name a kind.  A new format is a case in each function here, a
     // checker and an entry point that sets its job ("Adding a frame format").
     //
-    // The key of a captured pass: the sample format - 0 / 1 BGR of 8 / 16 bits, 2 .. 49 YuvJob::key, kRgbaKey, kGrayKey / kGrayKey + 1 gray of 8 / 16 bits - and the
-    // buffer the pass's gather reads (an RGBA pass reads d_bgr / d_alpha, never d_frame: its graphs do not depend on which frame buffer of a sequence is current)
+    // The key of a captured pass: the sample format - 0 / 1 BGR of 8 / 16 bits, 2 .. 49 YuvJob::key, kRgbaKey, kGrayKey / kGrayKey + 1 gray of 8 / 16 bits, kPlanarKey .. + 4 planar by
+    // input depth - and the buffer the pass's gather reads (an RGBA pass reads d_bgr / d_alpha, never d_frame: its graphs do not depend on which frame buffer of a sequence is current)
     int sample_format() const {
         switch (job.kind) {
             case Job::YUV: return job.yuv.key;
             case Job::RGBA: return kRgbaKey;
             case Job::GRAY: return kGrayKey + (job.gray.deep ? 1 : 0);
+            case Job::PLANAR: return planar_key(job.planar.in_bits);
             default: return deep ? 1 : 0;
         }
     }
@@ -1241,12 +1257,13 @@ struct Img2Img::Impl {
             case Job::YUV: return yuv_layout(nullptr, 0, cols, out ? job.yuv.out_bits : job.yuv.in_bits, out ? job.yuv.out_layout : job.yuv.in_layout).step[0];
             case Job::RGBA: return (size_t)cols * 4;
             case Job::GRAY: return gray_step(cols, job.gray.deep);
+            case Job::PLANAR: return planar_step(cols, out ? job.planar.out_bits : job.planar.in_bits);
             default: return bgr_step(cols, deep);
         }
     }
     size_t frame_bytes(int rows, int cols, bool out) const {
         if (job.kind == Job::YUV) return yuv_bytes(rows, cols, out ? job.yuv.out_bits : job.yuv.in_bits, out ? job.yuv.out_layout : job.yuv.in_layout);
-        return frame_step(cols, out) * rows;
+        return frame_step(cols, out) * rows * (job.kind == Job::PLANAR ? 3 : 1);
     }
     // the fp32 planes of a resized frame's canvas
     int canvas_planes() const { return job.kind == Job::RGBA ? 4 : job.kind == Job::GRAY ? 1 : 3; }
@@ -1287,6 +1304,12 @@ struct Img2Img::Impl {
                 hipAssert(launch_gather_gray(p, gs));
                 break;
             }
+            case Job::PLANAR: {                                       // from the frame's three planes
+                GatherPlanarParams p = tile_side<GatherPlanarParams>(gp);
+                p.src = planar_layout(d_frame, gp.rows, gp.cols, job.planar.in_bits);
+                hipAssert(launch_gather_planar(p, gs));
+                break;
+            }
         }
     }
     // The three launches that can end a frame, all over the whole canvas of the frame's tiles (one part, slot 0 = tile 0; BGR: the strip's columns): the canvas
@@ -1316,6 +1339,13 @@ struct Img2Img::Impl {
             case Job::BGR: { ResampleParams p; p.deep = deep ? 1 : 0; resample_into(p, on, launch_resample); break; }
             case Job::GRAY: { ResampleGrayParams p; p.deep = job.gray.deep ? 1 : 0; resample_into(p, on, launch_resample_gray); break; }
             case Job::RGBA: { ResampleRgbaParams p; p.uniform = job.rgba.uniform ? 1 : 0; p.alpha_value = job.rgba.value; resample_into(p, on, launch_resample_rgba); break; }
+            case Job::PLANAR: {                                       // the three planes of the target size
+                ResamplePlanarParams p;
+                resample_base(p);
+                p.dst = planar_layout(d_out, p.outH, p.outW, job.planar.out_bits);
+                hipAssert(launch_resample_planar(p, on));
+                break;
+            }
             case Job::YUV: {                                          // the planes of the target size (resized YUV frames are I420)
                 ResampleYuvParams p;
                 resample_base(p);
@@ -1350,6 +1380,15 @@ struct Img2Img::Impl {
                 cp.dst = d_out; cp.dst_step = frame_step(cp.outW, true); cp.deep = job.gray.deep ? 1 : 0;
                 stamp_begin(4, 0);
                 hipAssert(launch_compose_gray(cp, on));
+                stamp_end();
+                break;
+            }
+            case Job::PLANAR: {                                       // three planes of job.planar.out_bits
+                ComposePlanarParams p;
+                p.c = compose_base(rows, cols, grid);
+                p.dst = planar_layout(d_out, p.c.outH, p.c.outW, job.planar.out_bits);
+                stamp_begin(4, 0);
+                hipAssert(launch_compose_planar(p, on));
                 stamp_end();
                 break;
             }
@@ -1482,6 +1521,28 @@ struct Img2Img::Impl {
             for (int i = 0; i < count; ++i) if (srcs[i].depth != 8 || dsts[i].depth != 8) return std::string(who) + " takes 8-bit frames (16-bit images go through renderGray()).";
         }
         if (const std::string why = packed_check(srcs, dsts, count, resizeFilter, depth == 16 ? 2 : 1, c); !why.empty()) return why;
+        return call_grid(c);
+    }
+    // The planar calls: one size and one pair of depths (srcs[0]'s, dsts[0]'s) for the call.  The order: the depths, the first frame's size, the target
+    // (resize_problem: the filter, then the range), then per frame its size and depth, its planes, the output's size, its depth, its planes, then the grid.
+    std::string planar_check(const PlanarImage* srcs, const PlanarImage* dsts, int count, int resizeFilter, FrameCall& c) const {
+        const int rows = srcs[0].rows, cols = srcs[0].cols, in_bits = srcs[0].bits, out_bits = dsts[0].bits;
+        if (!planar_bits_ok(in_bits) || !planar_bits_ok(out_bits)) return "Planar frames must have 8, 10, 12, 16 or 32 (float) bits.";
+        if (rows <= 0 || cols <= 0) return "Input image is empty.";
+        if (const std::string why = call_target(resizeFilter, dsts[0], rows, cols, true, c); !why.empty()) return why;
+        // every plane present, with a step that holds its row, u16 / f32 samples aligned to their size
+        auto planes_ok = [](const PlanarImage& f) {
+            const size_t bps = planar_sample_bytes(f.bits);
+            for (int k = 0; k < 3; ++k) if (!f.planes[k] || f.steps[k] < (size_t)f.cols * bps || ((((size_t)f.planes[k]) | f.steps[k]) & (bps - 1)) != 0) return false;
+            return true;
+        };
+        for (int i = 0; i < count; ++i) {
+            if (srcs[i].rows != rows || srcs[i].cols != cols || srcs[i].bits != in_bits) return "Input images must be of one size and depth.";
+            if (!planes_ok(srcs[i])) return "Input image has a missing plane or an invalid step.";
+            if (dsts[i].rows != c.out_rows || dsts[i].cols != c.out_cols) return out_size_text(c);
+            if (dsts[i].bits != out_bits) return "Output images must be of one depth.";
+            if (!planes_ok(dsts[i])) return "Output image has a missing plane or an invalid step.";
+        }
         return call_grid(c);
     }
     // The tile grid of a rows x cols frame into `grid`; returns "" or why the engine cannot render it (img2img_render.cpp:232-240)
@@ -2409,6 +2470,49 @@ bool Img2Img::runGray(const Image* srcs, Image* dsts, int count, int resizeFilte
     if (const std::string why = impl->gray_check(srcs, dsts, count, resizeFilter, who, single, c); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
     impl->job.kind = Impl::Job::GRAY; impl->job.gray.deep = srcs[0].depth == 16;
     impl->run_packed_call(c, srcs, dsts, count, single, resizeFilter, srcs[0].depth / 8);
+    return true;
+    });
+}
+
+// Planar RGB frames: three planes R, G, B of 8, 10, 12, 16 bits or float32 on either side.  At 8 / 8 and 16 / 16 bits renderPlanar() gives the planes
+// of render() of the interleaved frame, byte for byte; the other depths widen the same expressions (img2img.h).  Per frame three 2-D copies up, the frame's tiles
+// through gather_planar_kernel, compose_planar_kernel, three 2-D copies down; nothing is interleaved or narrowed on the host.  The single calls run as one part on
+// the compute stream and report progress as render() does, ceil(N * steps / batchSize) batches.
+bool Img2Img::renderPlanar(const PlanarImage& src, PlanarImage& dst) { return runPlanar(&src, &dst, 1, -1, "renderPlanar", true); }
+
+// renderPlanar() with the canvas resized to dst.rows x dst.cols: compose_canvas_kernel (the canvas of renderResized()) and resample_planar_kernel.  At the
+// scaled size it is renderPlanar().
+bool Img2Img::renderPlanarResized(const PlanarImage& src, PlanarImage& dst, ResizeFilter filter) {
+    return runPlanar(&src, &dst, 1, filter_id(filter), "renderPlanarResized", true);
+}
+
+// Planar frames through renderSequence()'s pipeline (rolling when a BGR sequence of the size rolls): every depth, one pair of depths and one size per sequence,
+// output i the bytes of the single call on frame i.  No progress is reported.
+bool Img2Img::renderSequencePlanar(const PlanarImage* srcs, PlanarImage* dsts, int count) { return runPlanar(srcs, dsts, count, -1, "renderSequencePlanar", false); }
+
+bool Img2Img::renderSequencePlanarResized(const PlanarImage* srcs, PlanarImage* dsts, int count, ResizeFilter filter) {
+    return runPlanar(srcs, dsts, count, filter_id(filter), "renderSequencePlanarResized", false);
+}
+
+bool Img2Img::runPlanar(const PlanarImage* srcs, PlanarImage* dsts, int count, int resizeFilter, const char* who, bool single) {
+    return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
+    if (count <= 0) return true;
+    if (!srcs || !dsts) { W2X_LOG_AS(who, error, "No frames given."); return false; }
+    Impl::FrameCall call;
+    if (const std::string why = impl->planar_check(srcs, dsts, count, resizeFilter, call); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
+    impl->job.kind = Impl::Job::PLANAR; impl->job.planar.in_bits = srcs[0].bits; impl->job.planar.out_bits = dsts[0].bits;
+    // the three planes of a frame between the caller's pointers and the device layout (planar_layout), on stream `on`
+    auto copy_planes = [&](const PlanarImage& host, uint8_t* dev, int r, int c, bool up, hipStream_t on) {
+        const PlanarPlanes d = Impl::planar_layout(dev, r, c, host.bits);
+        const size_t width = (size_t)c * planar_sample_bytes(host.bits);
+        for (int k = 0; k < 3; ++k) {
+            if (up) hipAssert(hipMemcpy2DAsync(d.p[k], d.step[k], host.planes[k], host.steps[k], width, r, hipMemcpyHostToDevice, on));
+            else hipAssert(hipMemcpy2DAsync(host.planes[k], host.steps[k], d.p[k], d.step[k], width, r, hipMemcpyDeviceToHost, on));
+        }
+    };
+    impl->run_call(call, count, single, resizeFilter,
+        [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(srcs[i], dev, call.rows, call.cols, true, on); },
+        [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(dsts[i], dev, call.out_rows, call.out_cols, false, on); });
     return true;
     });
 }

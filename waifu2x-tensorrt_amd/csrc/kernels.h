@@ -419,6 +419,41 @@ struct ResampleGrayParams {
     int rows_max = 0;
 };
 hipError_t launch_resample_gray(const ResampleGrayParams& p, hipStream_t s);
+// Planar RGB frames (renderPlanar; k_planar.hip): three planes R, G, B of rows x cols samples - uint8 (bits 8), little-endian uint16 with the code
+// in the low bits (10 / 12 / 16) or float32 of nominal [0, 1] (32) - each with its own pointer and step in bytes; u16 / f32 samples aligned to their size.
+struct PlanarPlanes {
+    uint8_t* p[3] = {nullptr, nullptr, nullptr}; size_t step[3] = {0, 0, 0};
+    int rows = 0, cols = 0, bits = 8;
+};
+inline bool planar_bits_ok(int bits) { return bits == 8 || bits == 10 || bits == 12 || bits == 16 || bits == 32; }
+inline size_t planar_sample_bytes(int bits) { return bits == 32 ? 4 : bits > 8 ? 2 : 1; }
+// gather_planar_kernel: gather_kernel's tiles (same slots, replicate padding, TTA source index) from the three planes: the tile pixel is make_px(r, g, b), each
+// sample min(code, 2^bits - 1) * fl32(1 / (2^bits - 1)) - at 8 and 16 bits gather_kernel's own constants - or, float, min(max(x, 0), 1) with NaN -> 0
+struct GatherPlanarParams {
+    PlanarPlanes src;
+    void* out = nullptr; int fp32 = 0;
+    const TileSlot* slots = nullptr;
+    int B = 0, T = 0;
+};
+hipError_t launch_gather_planar(const GatherPlanarParams& p, hipStream_t s);
+// compose_planar_kernel: compose_kernel over the whole canvas of c (c.dst / c.deep / x0..y1 unused): the three sums of compose_pixel_sums into the planes of dst
+// (c.outH x c.outW), integer sat(rint(x * (2^bits - 1))), float min(max(x, 0), 1) stored as fp32
+struct ComposePlanarParams {
+    ComposeParams c;
+    PlanarPlanes dst;
+};
+hipError_t launch_compose_planar(const ComposePlanarParams& p, hipStream_t s);
+// resample_planar_kernel: resample_kernel's resize (same tap tables, same rows_max, same accumulation) of the fp32 RGB canvas compose_canvas_kernel writes, the
+// three accumulators quantised like compose_planar_kernel into the planes of dst (outH x outW)
+struct ResamplePlanarParams {
+    const float* canvas = nullptr; int inW = 0, inH = 0;
+    int outW = 0, outH = 0;
+    const int* fx = nullptr; const float* wx = nullptr; int kx = 0;
+    const int* fy = nullptr; const float* wy = nullptr; int ky = 0;
+    int rows_max = 0;
+    PlanarPlanes dst;
+};
+hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s);
 // k_resample.hip resample_yuv_kernel: resample_kernel's resize of the fp32 RGB canvas (same tap tables, same rows_max) with compose_yuv_kernel's
 // encoding behind it instead of the BGR quantisation: the resized R, G, B clamped to [0, 1] and written as YUV 4:2:0 planes of outH x outW
 // (dst.rows x dst.cols), Y per pixel, Cb / Cr of the RGB filtered (1/4, 1/2, 1/4) x (1/2, 1/2) onto each chroma site (renderYuvResized)

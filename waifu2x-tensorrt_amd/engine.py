@@ -81,6 +81,40 @@ def _plane_args(planes):
     return [p.ctypes.data for p in planes] + pad, [p.strides[0] for p in planes] + [0] * len(pad)
 
 
+PLANAR_DTYPES = {8: np.uint8, 10: np.uint16, 12: np.uint16, 16: np.uint16, 32: np.float32}   # the sample type of each depth of a planar RGB frame
+
+
+def planar_plane_bytes(rows: int, cols: int, bits: int) -> int:
+    """the bytes of one packed plane of a planar RGB frame (w2x_planar_plane_bytes): 0 for an empty plane or a depth the library refuses"""
+    return int(lib().w2x_planar_plane_bytes(int(rows), int(cols), int(bits)))
+
+
+def _planar_order(order):
+    """where R, G and B sit in a frame whose planes come in `order` ("rgb", "gbr" - ffmpeg's gbrp -, any permutation)"""
+    if not isinstance(order, str) or sorted(order) != ["b", "g", "r"]:
+        raise ValueError(f"order must name the planes r, g and b once each (\"rgb\", \"gbr\"), got {order!r}")
+    return [order.index(ch) for ch in "rgb"]
+
+
+def _planar_bits(planes, bits=None, error="planes must be three 2-D arrays of one shape and sample type (uint8, uint16 or float32) with packed samples", shape=None,
+                 empty_ok=False) -> int:
+    """The depth of a planar frame: 8 for uint8, 16 for uint16, 32 for float32 planes; bits= says 10 or 12 for uint16 planes (or restates the default).
+    Checks three 2-D planes of one shape (`shape` when given) and type with packed samples; rows may be padded, every plane its own way."""
+    ok = isinstance(planes, (tuple, list)) and len(planes) == 3 and all(isinstance(p, np.ndarray) and p.ndim == 2 for p in planes)
+    ok = ok and planes[0].dtype in (np.uint8, np.uint16, np.float32) and all(p.dtype == planes[0].dtype and p.shape == planes[0].shape for p in planes)
+    ok = ok and (shape is None or planes[0].shape == tuple(shape))
+    ok = ok and all((empty_ok and not p.size) or (p.strides[1] == p.itemsize and p.strides[0] > 0) for p in planes)
+    if not ok:
+        raise ValueError(error)
+    dt = planes[0].dtype
+    default = 8 if dt == np.uint8 else 16 if dt == np.uint16 else 32
+    if bits is None:
+        return default
+    if int(bits) not in PLANAR_DTYPES or PLANAR_DTYPES[int(bits)] != dt:
+        raise ValueError(f"bits={bits} does not go with {dt} planes (uint8: 8; uint16: 10, 12 or 16; float32: 32)")
+    return int(bits)
+
+
 def _filter_id(name) -> int:
     if name not in RESIZE_FILTERS:
         raise ValueError(f"filter must be one of {sorted(RESIZE_FILTERS)}, got {name!r}")
@@ -252,6 +286,15 @@ GRAY_SYMBOLS = {
     "w2x_render_sequence_gray": (_I, _FRAME + [_P, _Z, _I]),
     "w2x_render_sequence_gray_resized": (_I, _FRAME + [_P, _I, _I, _Z, _I, _I]),
 }
+# The planar RGB entries of include/w2x/c_api_planar.h, in the row format of SYMBOLS and declared by lib() in the same loop; a table of their own for the
+# reason GRAY_SYMBOLS is one.  _YUV is (planes, steps, rows, cols, bits): the planar frames travel the same way.
+PLANAR_SYMBOLS = {
+    "w2x_render_planar": (_I, _YUV2),
+    "w2x_render_planar_resized": (_I, _YUV2 + [_I]),
+    "w2x_render_sequence_planar": (_I, _YUV2 + [_I]),
+    "w2x_render_sequence_planar_resized": (_I, _YUV2 + [_I, _I]),
+    "w2x_planar_plane_bytes": (_Z, [_I, _I, _I]),
+}
 _lib = None
 
 
@@ -264,7 +307,7 @@ def lib():
         raise W2xError(f"{lib_path} is missing - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "or `make -C waifu2x-tensorrt_amd` (there is no CPU fallback)")
     L = C.CDLL(lib_path)
-    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()):
+    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()) + list(PLANAR_SYMBOLS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -531,6 +574,102 @@ class Img2Img:
                 return self._L.w2x_render_sequence_gray(self._h, _pointers(fs), r, c, step, _pointers(os_, len(fs)), cols, len(fs))
             return self._L.w2x_render_sequence_gray_resized(self._h, _pointers(fs), r, c, step, _pointers(os_, len(fs)), rows, cols, cols, len(fs), fid)
         return self._sequence(frames, outs, pinned, alloc, np.copy, run, "render_sequence_gray failed", check)
+
+    def _planar_call(self, planes, size, bits, out_bits, order, dst, who):
+        """what the two single planar calls share: the checks of both sides and the arguments of the C entry up to dst_bits (planes in R, G, B order)"""
+        idx = _planar_order(order)
+        bits = _planar_bits(planes, bits)
+        ob = bits if out_bits is None else int(out_bits)
+        if ob not in PLANAR_DTYPES:
+            raise ValueError(f"out_bits must be one of {sorted(PLANAR_DTYPES)}, got {out_bits!r}")
+        r, c = planes[0].shape
+        s = self._scaling
+        rows, cols = (r * s, c * s) if size is None else (max(int(size[0]), 0), max(int(size[1]), 0))
+        out = tuple(np.empty((rows, cols), PLANAR_DTYPES[ob]) for _ in range(3)) if dst is None else None
+        dst = out if dst is None else tuple(dst)
+        # the C ABI sees pointers and steps only: the shapes and the sample type of out_bits are checked here (an empty target: refused by the library)
+        error = f"dst must be three 2-D {np.dtype(PLANAR_DTYPES[ob]).name} planes of one shape with packed samples"
+        _planar_bits(dst, ob, error, empty_ok=True)
+        if size is not None and dst[0].shape != (rows, cols):
+            raise ValueError(f"dst must be three planes of the target size {(rows, cols)}")
+        if size is None and s and dst[0].shape != (rows, cols):     # (never loaded: as in render())
+            self._refuse(who, f"Output image has invalid size: expected {cols}x{rows}.")
+            return None, out
+        src = [planes[k] for k in idx]
+        d = [dst[k] for k in idx]
+        args = (self._h, (C.c_void_p * 3)(*[_data(p) for p in src]), (C.c_size_t * 3)(*[p.strides[0] for p in src]), r, c, bits,
+                (C.c_void_p * 3)(*[_data(p) for p in d]), (C.c_size_t * 3)(*[p.strides[0] for p in d]),
+                int(size[0]) if size is not None else rows, int(size[1]) if size is not None else cols, ob)
+        return args, out
+
+    def render_planar(self, planes, *, bits: int | None = None, out_bits: int | None = None, order: str = "rgb", dst=None):
+        """render() on a planar RGB frame (w2x_render_planar): three 2-D planes of uint8 (8 bits), uint16 (16; bits=10 / 12 for codes in the low bits) or
+        float32 (nominal [0, 1]) samples; out_bits (8, 10, 12, 16 or 32 for float32; default the input's) sets the output's sample format independently.
+        At 8 / 8 and 16 / 16 bits the planes are those of render() of the interleaved frame, byte for byte.  order: how the planes are ordered, "rgb" or "gbr"
+        (ffmpeg's gbrp); the result comes back in the same order.  Rows may be padded, every plane its own way.  With dst=None returns the three planes or
+        raises; with dst (three planes, views allowed) returns a bool."""
+        args, out = self._planar_call(planes, None, bits, out_bits, order, dst, "renderPlanar")
+        return self._finish(self._L.w2x_render_planar(*args) if args else 0, out, "render_planar failed")
+
+    def render_planar_resized(self, planes, size, *, bits: int | None = None, out_bits: int | None = None, order: str = "rgb", filter: str = "bicubic", dst=None):
+        """render_planar() with the output resized on the device to size = (rows, cols), each in [input dim, input dim * scaling]
+        (w2x_render_planar_resized): at 8 / 8 and 16 / 16 bits the planes of render_resized().  With dst=None returns the planes or raises; with dst a bool."""
+        fid = _filter_id(filter)
+        args, out = self._planar_call(planes, size, bits, out_bits, order, dst, "renderPlanarResized")
+        return self._finish(self._L.w2x_render_planar_resized(*args, fid), out, "render_planar_resized failed")
+
+    def render_sequence_planar(self, frames, size=None, *, bits: int | None = None, out_bits: int | None = None, order: str = "rgb", filter: str = "bicubic",
+                               outs=None, pinned: bool = False):
+        """Equally sized planar RGB frames [(p0, p1, p2), ...] of one depth with upload / compute / download overlapped (w2x_render_sequence_planar); with
+        size = (rows, cols) every frame is resized like render_planar_resized() (w2x_render_sequence_planar_resized).  Output i is the bytes of the single
+        call on frame i.  The frames share one set of row strides (rows may be padded); outs: pre-allocated plane triples of one set of strides;
+        pinned=True takes the output planes from alloc_host() (a ring of three frames; copies of the results are returned)."""
+        if len(frames) == 0:
+            return []
+        fid = _filter_id(filter)
+        idx = _planar_order(order)
+        frames = [tuple(f) if isinstance(f, (tuple, list)) else f for f in frames]
+        bits = _planar_bits(frames[0], bits)
+        ob = bits if out_bits is None else int(out_bits)
+        if ob not in PLANAR_DTYPES:
+            raise ValueError(f"out_bits must be one of {sorted(PLANAR_DTYPES)}, got {out_bits!r}")
+        r, c = frames[0][0].shape
+        steps = [p.strides[0] for p in frames[0]]
+        for f in frames[1:]:
+            try:
+                fb = _planar_bits(f, bits)
+            except ValueError:
+                fb = None                                                       # (planes of another sample type, or no planar frame at all)
+            if fb != bits or f[0].shape != (r, c) or [p.strides[0] for p in f] != steps:
+                raise ValueError("frames must be planar frames of one size, one depth and one set of row strides")
+        s = self._scaling
+        rows, cols = (r * s, c * s) if size is None else (int(size[0]), int(size[1]))
+        shape = (max(rows, 0), max(cols, 0))
+        dt = np.dtype(PLANAR_DTYPES[ob])
+        nb = shape[0] * shape[1] * dt.itemsize
+
+        def alloc(host):
+            if not host:
+                return None, tuple(np.empty(shape, dt) for _ in range(3))
+            buf = self.alloc_host((max(3 * nb, 1),))          # one page-locked block per frame, carved into its planes
+            return buf, tuple(buf[k * nb:(k + 1) * nb].view(dt).reshape(shape) for k in range(3))
+
+        first = []
+
+        def check(o):
+            _planar_bits(o, ob, f"outs must be triples of 2-D {dt.name} planes of the output size with packed samples", shape=shape, empty_ok=True)
+            first.append([p.strides[0] for p in o])
+            if first[-1] != first[0]:
+                raise ValueError("outs must share one set of row strides")
+
+        def run(fs, os_):
+            m = len(fs)
+            sp = (C.c_void_p * (3 * m))(*[_data(f[k]) for f in fs for k in idx])
+            dp = (C.c_void_p * (3 * m))(*[_data(o[k]) for o in list(os_)[:m] for k in idx] + [None] * (3 * (m - len(os_[:m]))))
+            a = (self._h, sp, (C.c_size_t * 3)(*[steps[k] for k in idx]), r, c, bits, dp, (C.c_size_t * 3)(*[os_[0][k].strides[0] for k in idx]), rows, cols, ob, m)
+            return self._L.w2x_render_sequence_planar(*a) if size is None else self._L.w2x_render_sequence_planar_resized(*a, fid)
+        return self._sequence(frames, outs, pinned, alloc, lambda d: tuple(p.copy() for p in d), run,
+                              "render_sequence_planar failed", check)
 
     def alpha_bleed_device(self, bgra: np.ndarray, radius: int) -> np.ndarray:
         """Test hook (w2x_alpha_bleed_device): the device bleed alone on a uint8 [rows, cols, 4] BGRA frame -> the [rows, cols, 3] BGR frame the tiles are read from"""
