@@ -78,7 +78,8 @@ def test_render_gray_is_the_green_channel_of_render(engines, name, rows, cols):
 
 
 # ---- 2. 16-bit frames
-@pytest.mark.parametrize("name,rows,cols", [("swin_x4_b2_blend", 45, 57), ("cunet_x2_b3_noblend_tta", 61, 83)])
+# (cunet_x1_b2_blend at 37 x 541: no TTA, blended, a ragged last group next to fast-path groups - a 16-bit frame on the four-pixel fast path)
+@pytest.mark.parametrize("name,rows,cols", [("swin_x4_b2_blend", 45, 57), ("cunet_x2_b3_noblend_tta", 61, 83), ("cunet_x1_b2_blend", 37, 541)])
 def test_render_gray_at_16_bits(engines, name, rows, cols):
     eng, scale = engines(name)
     g = gray_frame(rows, cols, 3, "noise", np.uint16)
@@ -153,8 +154,8 @@ def test_resized_16_bit_and_fp32(engines):
 # ---- 5. sequences
 @pytest.mark.parametrize("pinned", [False, True])
 def test_rolling_sequence_matches_single_frames(pkg, onnx_model, monkeypatch, pinned):
-    """five 90 x 130 frames on swin x4 with TTA (48 slots of one pass: the sequence rolls, compose_gray_kernel - resized: the canvas compose and
-    resample_gray_kernel - on the second group's stream): the bytes of the per-frame calls, with W2X_NO_ROLLING=1 and without, on a repeated call, pageable and
+    """five 90 x 130 frames on swin x4 with TTA (48 slots of one pass: the sequence rolls, compose_planes_kernel at one plane - resized: the canvas compose and
+    resample_planes_kernel - on the second group's stream): the bytes of the per-frame calls, with W2X_NO_ROLLING=1 and without, on a repeated call, pageable and
     page-locked, and with source rows wider than the frame"""
     path = onnx_model("swin_unet/art", 4, 2, 64, small=True)
     frames = [gray_frame(90, 130, 50 + k, "noise" if k % 2 else "smooth") for k in range(5)]

@@ -166,8 +166,8 @@ def sequence_frames(bits):
 @pytest.mark.parametrize("bits,out_bits", [(8, 8), (8, 10), (16, 32)])
 @pytest.mark.parametrize("pinned", [False, True])
 def test_rolling_sequence_matches_single_frames(pkg, onnx_model, monkeypatch, pinned, bits, out_bits):
-    """five 90 x 130 frames on swin x4 with TTA (48 slots of one pass: the sequence rolls, compose_planar_kernel - resized: the canvas compose and
-    resample_planar_kernel - on the second group's stream): the bytes of the per-frame calls, with W2X_NO_ROLLING=1 and without, on a repeated call, pageable
+    """five 90 x 130 frames on swin x4 with TTA (48 slots of one pass: the sequence rolls, compose_planes_kernel - resized: the canvas compose and
+    resample_planes_kernel - on the second group's stream): the bytes of the per-frame calls, with W2X_NO_ROLLING=1 and without, on a repeated call, pageable
     and page-locked, and with source rows wider than the frame"""
     path = onnx_model("swin_unet/art", 4, 2, 64, small=True)
     frames = sequence_frames(bits)

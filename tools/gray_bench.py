@@ -15,7 +15,7 @@ the other in the process, and the median of each run is reported next to the med
 every difference between two routes.  One JSON line on stdout.
 
 --only MODE runs that mode alone (for `rocprofv3 --kernel-trace --stats -- python tools/gray_bench.py --only gray`, which gives the device time of
-gather_gray_kernel / compose_gray_kernel against gather_kernel / compose_kernel under --only replicated_gpu; with --group resize the canvas and resample
+gather_planes_kernel / compose_planes_kernel at one plane against gather_kernel / compose_kernel under --only replicated_gpu; with --group resize the canvas and resample
 kernels).  --bytes prints the bytes each route moves across PCIe per frame and exits (no GPU).  Not part of bench.py."""
 from __future__ import annotations
 

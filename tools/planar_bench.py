@@ -16,8 +16,8 @@ the other in the process, and the median of each run is reported next to the med
 every difference between two routes.  One JSON line on stdout.
 
 --only MODE runs that mode alone (for `rocprofv3 --kernel-trace --stats -- python tools/planar_bench.py --only planar_8_8`, which gives the device time of
-gather_planar_kernel / compose_planar_kernel against gather_kernel / compose_kernel under --only bgr_sequence).  --resized renders to the x2 target instead
-(the canvas compose and resample_planar_kernel against resample_kernel).  --bytes prints the bytes each mode moves across PCIe per frame and exits (no GPU).
+gather_planes_kernel / compose_planes_kernel against gather_kernel / compose_kernel under --only bgr_sequence).  --resized renders to the x2 target instead
+(the canvas compose and resample_planes_kernel against resample_kernel).  --bytes prints the bytes each mode moves across PCIe per frame and exits (no GPU).
 Not part of bench.py."""
 from __future__ import annotations
 

@@ -342,12 +342,12 @@ struct Img2Img::Impl {
     // (alpha_slot0, uniform, value: what rgba_frame() found out about the frame's alpha plane, for the launches that end the frame)
     struct RgbaJob { int bleed = 0; bool skip = false; size_t alpha_slot0 = 0; bool uniform = false; unsigned value = 255; };
     // Gray frames (renderGray, renderGrayResized, renderSequenceGray*): d_frame / d_out hold ONE sample per pixel (8 or 16 bits, rows padded to 16 bytes:
-    // gray_step), the gather launch is gather_gray_kernel, the frame ends with compose_gray_kernel - resized with compose_canvas_gray_kernel (one fp32 plane) and
-    // resample_gray_kernel.  The sample depth is the job's, not `deep`: nothing of a gray call is replayable.
+    // planar_step) - a planar frame of one plane, through the planar launches below; resized, its canvas is compose_canvas_gray_kernel's one fp32 plane.  The
+    // sample depth is the job's, not `deep`: nothing of a gray call is replayable.
     struct GrayJob { bool deep = false; };
     // Planar RGB frames (renderPlanar, renderPlanarResized, renderSequencePlanar*): d_frame / d_out hold three planes R, G, B one after the other, each
-    // of in_bits / out_bits samples (8; 10, 12, 16 as uint16; 32 as float) with rows padded to 16 bytes (planar_layout).  The gather launch is gather_planar_kernel,
-    // the frame ends with compose_planar_kernel - resized with compose_canvas_kernel (the BGR path's own canvas) and resample_planar_kernel.
+    // of in_bits / out_bits samples (8; 10, 12, 16 as uint16; 32 as float) with rows padded to 16 bytes (planar_layout).  The gather launch is gather_planes_kernel,
+    // the frame ends with compose_planes_kernel - resized with compose_canvas_kernel (the BGR path's own canvas) and resample_planes_kernel.
     struct PlanarJob { int in_bits = 8, out_bits = 8; };
     // The kind of frame the running entry point renders.  Only the block "the frame formats" below branches on it: the key of the captured passes, the
     // gather (gather_tiles), the end of a frame (finish_frame), the device layout of a frame, the slot tables of a call.  The default is a plain BGR frame, not
@@ -1206,10 +1206,9 @@ struct Img2Img::Impl {
         rp.outW = rs->outW; rp.outH = rs->outH;
         rp.fx = rs->fx; rp.wx = rs->wx; rp.kx = rs->kx; rp.fy = rs->fy; rp.wy = rs->wy; rp.ky = rs->ky; rp.rows_max = rs->rows_max;
     }
-    // The device layouts the formats are made of.  BGR: packed rows.  Gray: one plane, rows padded to 16 bytes like the planes of yuv_layout.  YUV: Y, U, V
+    // The device layouts the formats are made of.  BGR: packed rows.  YUV: Y, U, V
     // (NV12: Y, UV) one after the other, rows padded to 16 bytes (the stores of the compose kernels).
     static size_t bgr_step(int cols, bool deep16) { return (size_t)cols * 3 * (deep16 ? 2 : 1); }
-    static size_t gray_step(int cols, bool deep16) { return ((size_t)cols * (deep16 ? 2 : 1) + 15) / 16 * 16; }
     static YuvPlanes yuv_layout(uint8_t* base, int rows, int cols, int bits, int layout) {
         const size_t bps = bits > 8 ? 2 : 1;
         const int cw = yuv_chroma_samples(cols, layout), ch = yuv_chroma_rows(rows, layout);
@@ -1219,12 +1218,13 @@ struct Img2Img::Impl {
         f.p[0] = base; f.p[1] = base + f.step[0] * rows; f.p[2] = layout == kYuvNV12 ? nullptr : f.p[1] + f.step[1] * ch;
         return f;
     }
-    // Planar RGB: R, G, B one after the other, every plane's rows padded to 16 bytes (gray_step's rule at 1, 2 or 4 bytes per sample)
+    // Planar RGB: R, G, B one after the other, every plane's rows padded to 16 bytes like the planes of yuv_layout, at 1, 2 or 4 bytes per sample.  Gray: the
+    // same with one plane.
     static size_t planar_step(int cols, int bits) { return ((size_t)cols * planar_sample_bytes(bits) + 15) / 16 * 16; }
-    static PlanarPlanes planar_layout(uint8_t* base, int rows, int cols, int bits) {
+    static PlanarPlanes planar_layout(uint8_t* base, int rows, int cols, int bits, int n = 3) {
         PlanarPlanes f;
-        f.rows = rows; f.cols = cols; f.bits = bits;
-        for (int k = 0; k < 3; ++k) { f.step[k] = planar_step(cols, bits); f.p[k] = base + (size_t)k * f.step[k] * rows; }
+        f.rows = rows; f.cols = cols; f.bits = bits; f.n = n;
+        for (int k = 0; k < n; ++k) { f.step[k] = planar_step(cols, bits); f.p[k] = base + (size_t)k * f.step[k] * rows; }
         return f;
     }
     static int planar_key(int bits) { return kPlanarKey + (bits == 8 ? 0 : bits == 10 ? 1 : bits == 12 ? 2 : bits == 16 ? 3 : 4); }
@@ -1249,6 +1249,9 @@ struct Img2Img::Impl {
             default: return deep ? 1 : 0;
         }
     }
+    // gray and planar frames: the sample depth of the frame (`out`: of the output) and its planes in d_frame / d_out
+    int plane_bits(bool out) const { return job.kind == Job::GRAY ? (job.gray.deep ? 16 : 8) : out ? job.planar.out_bits : job.planar.in_bits; }
+    PlanarPlanes frame_planes(uint8_t* base, int rows, int cols, bool out) const { return planar_layout(base, rows, cols, plane_bits(out), job.kind == Job::GRAY ? 1 : 3); }
     const void* pass_source() const { return job.kind == Job::RGBA ? (const void*)d_bgr : (const void*)d_frame; }
     // The device layout of a frame: bytes per row and bytes of a rows x cols frame in d_frame, or (`out`) in d_out.  A YUV frame has a step per plane
     // (yuv_layout); frame_step() gives its Y plane's.
@@ -1256,8 +1259,7 @@ struct Img2Img::Impl {
         switch (job.kind) {
             case Job::YUV: return yuv_layout(nullptr, 0, cols, out ? job.yuv.out_bits : job.yuv.in_bits, out ? job.yuv.out_layout : job.yuv.in_layout).step[0];
             case Job::RGBA: return (size_t)cols * 4;
-            case Job::GRAY: return gray_step(cols, job.gray.deep);
-            case Job::PLANAR: return planar_step(cols, out ? job.planar.out_bits : job.planar.in_bits);
+            case Job::GRAY: case Job::PLANAR: return planar_step(cols, plane_bits(out));
             default: return bgr_step(cols, deep);
         }
     }
@@ -1298,15 +1300,9 @@ struct Img2Img::Impl {
                 hipAssert(launch_gather_rgba(p, gs));
                 break;
             }
-            case Job::GRAY: {                                         // from the frame's one plane
-                GatherGrayParams p = tile_side<GatherGrayParams>(gp);
-                p.frame = d_frame; p.rows = gp.rows; p.cols = gp.cols; p.step = gray_step(gp.cols, job.gray.deep); p.deep = job.gray.deep ? 1 : 0;
-                hipAssert(launch_gather_gray(p, gs));
-                break;
-            }
-            case Job::PLANAR: {                                       // from the frame's three planes
+            case Job::GRAY: case Job::PLANAR: {                       // from the frame's one plane or three
                 GatherPlanarParams p = tile_side<GatherPlanarParams>(gp);
-                p.src = planar_layout(d_frame, gp.rows, gp.cols, job.planar.in_bits);
+                p.src = frame_planes(d_frame, gp.rows, gp.cols, false);
                 hipAssert(launch_gather_planar(p, gs));
                 break;
             }
@@ -1337,12 +1333,11 @@ struct Img2Img::Impl {
     void resample(hipStream_t on) {
         switch (job.kind) {
             case Job::BGR: { ResampleParams p; p.deep = deep ? 1 : 0; resample_into(p, on, launch_resample); break; }
-            case Job::GRAY: { ResampleGrayParams p; p.deep = job.gray.deep ? 1 : 0; resample_into(p, on, launch_resample_gray); break; }
             case Job::RGBA: { ResampleRgbaParams p; p.uniform = job.rgba.uniform ? 1 : 0; p.alpha_value = job.rgba.value; resample_into(p, on, launch_resample_rgba); break; }
-            case Job::PLANAR: {                                       // the three planes of the target size
+            case Job::GRAY: case Job::PLANAR: {                       // the one plane or three of the target size
                 ResamplePlanarParams p;
                 resample_base(p);
-                p.dst = planar_layout(d_out, p.outH, p.outW, job.planar.out_bits);
+                p.dst = frame_planes(d_out, p.outH, p.outW, true);
                 hipAssert(launch_resample_planar(p, on));
                 break;
             }
@@ -1375,18 +1370,10 @@ struct Img2Img::Impl {
                 hipAssert(launch_compose_rgba(p, on));
                 break;
             }
-            case Job::GRAY: {                                         // one sample per pixel
-                ComposeParams cp = compose_base(rows, cols, grid);
-                cp.dst = d_out; cp.dst_step = frame_step(cp.outW, true); cp.deep = job.gray.deep ? 1 : 0;
-                stamp_begin(4, 0);
-                hipAssert(launch_compose_gray(cp, on));
-                stamp_end();
-                break;
-            }
-            case Job::PLANAR: {                                       // three planes of job.planar.out_bits
+            case Job::GRAY: case Job::PLANAR: {                       // one sample per pixel, or three planes of job.planar.out_bits
                 ComposePlanarParams p;
                 p.c = compose_base(rows, cols, grid);
-                p.dst = planar_layout(d_out, p.c.outH, p.c.outW, job.planar.out_bits);
+                p.dst = frame_planes(d_out, p.c.outH, p.c.outW, true);
                 stamp_begin(4, 0);
                 hipAssert(launch_compose_planar(p, on));
                 stamp_end();
@@ -2446,11 +2433,11 @@ bool Img2Img::runSequenceRgba(const Image* srcs, Image* dsts, int count, const R
 }
 
 // Gray frames: Image read as ONE channel.  renderGray(g) is the green channel of render() of the frame B = G = R = g, byte for byte, at 8 and 16 bits:
-// one 2-D upload of a sample per pixel, the frame's tiles through gather_gray_kernel, compose_gray_kernel, one 2-D download of a sample per output pixel; nothing is
+// one 2-D upload of a sample per pixel, the frame's tiles through gather_planes_kernel, compose_planes_kernel at one plane, one 2-D download of a sample per output pixel; nothing is
 // replicated or picked apart on the host.  A single part on the compute stream; progress as render() reports it, ceil(N * steps / batchSize) batches.
 bool Img2Img::renderGray(const Image& src, Image& dst) { return runGray(&src, &dst, 1, -1, "renderGray", true); }
 
-// renderGray() with the canvas resized to dst.rows x dst.cols: compose_canvas_gray_kernel (one fp32 plane) and resample_gray_kernel; the green channel of
+// renderGray() with the canvas resized to dst.rows x dst.cols: compose_canvas_gray_kernel (one fp32 plane) and resample_planes_kernel; the green channel of
 // renderResized() of the replicated frame.  At the scaled size it is renderGray().
 bool Img2Img::renderGrayResized(const Image& src, Image& dst, ResizeFilter filter) { return runGray(&src, &dst, 1, filter_id(filter), "renderGrayResized", true); }
 
@@ -2476,11 +2463,11 @@ bool Img2Img::runGray(const Image* srcs, Image* dsts, int count, int resizeFilte
 
 // Planar RGB frames: three planes R, G, B of 8, 10, 12, 16 bits or float32 on either side.  At 8 / 8 and 16 / 16 bits renderPlanar() gives the planes
 // of render() of the interleaved frame, byte for byte; the other depths widen the same expressions (img2img.h).  Per frame three 2-D copies up, the frame's tiles
-// through gather_planar_kernel, compose_planar_kernel, three 2-D copies down; nothing is interleaved or narrowed on the host.  The single calls run as one part on
+// through gather_planes_kernel, compose_planes_kernel, three 2-D copies down; nothing is interleaved or narrowed on the host.  The single calls run as one part on
 // the compute stream and report progress as render() does, ceil(N * steps / batchSize) batches.
 bool Img2Img::renderPlanar(const PlanarImage& src, PlanarImage& dst) { return runPlanar(&src, &dst, 1, -1, "renderPlanar", true); }
 
-// renderPlanar() with the canvas resized to dst.rows x dst.cols: compose_canvas_kernel (the canvas of renderResized()) and resample_planar_kernel.  At the
+// renderPlanar() with the canvas resized to dst.rows x dst.cols: compose_canvas_kernel (the canvas of renderResized()) and resample_planes_kernel.  At the
 // scaled size it is renderPlanar().
 bool Img2Img::renderPlanarResized(const PlanarImage& src, PlanarImage& dst, ResizeFilter filter) {
     return runPlanar(&src, &dst, 1, filter_id(filter), "renderPlanarResized", true);

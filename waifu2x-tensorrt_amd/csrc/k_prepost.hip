@@ -66,13 +66,7 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 // registers) - the flat grid-stride loop it replaces paid a 64-bit division and six 32-bit ones per four pixels, and the kernel ran at
 // 3.1 TB/s with its integer unit busier than its memory pipe.
 // (measured at config 3, profiles/r3_kernels/compose_geometry.txt: rows x threads 8 x 128 0.140 ms, 4 x 128 0.119, 16 x 128 0.177, 4 x 64 0.115-0.118, 2 x 64 0.117, 1 x 64 0.125)
-#ifndef W2X_COMPOSE_ROWS
-#define W2X_COMPOSE_ROWS 4
-#endif
-#ifndef W2X_COMPOSE_THREADS
-#define W2X_COMPOSE_THREADS 64
-#endif
-constexpr int kComposeRows = W2X_COMPOSE_ROWS, kComposeThreads = W2X_COMPOSE_THREADS;
+// (kComposeRows / kComposeThreads: kernels.h, shared with the kernels of k_planar.hip that have this launch shape)
 template <typename P>
 __global__ __launch_bounds__(kComposeThreads) void compose_kernel(const ComposeParams p) {
     constexpr bool kHalf = sizeof(P) == 8;                          // the four-pixel fast path reads fp16 tiles

@@ -1,13 +1,14 @@
 // RGBA frames (renderRgba): the three kernels that stand beside gather / compose of k_prepost.hip, which stay as they are.
 //   alpha_bleed : uploaded u8 BGRA frame -> u8 BGR frame + u8 alpha plane, the colours of the visible pixels (alpha > 0) spread `radius` pixels outward
 //                 under the transparent ones, all iterations in one launch; max(A) and max(255 - A) of the frame reduced into two device words.
-//   gather_rgba : gather_kernel with a slot that says which plane it reads: the BGR frame (the bytes of gather_kernel) or the alpha plane as a gray pixel.
+//   gather_rgba : gather_kernel (gather_loop, pixel_device.h) with a slot that says which plane it reads: the BGR frame (the bytes of gather_kernel) or
+//                 the alpha plane as a gray pixel.
 //   compose_rgba: per output pixel compose_pixel_sums (prepost_device.h, the code compose_kernel inlines) over the colour tiles and over the alpha
 //                 tiles, quantised alike, stored as one BGRA dword.
 // Resized RGBA frames (renderRgbaResized), further down: compose_canvas_rgba (the same sums left unquantised as four fp32 planes) and
-// resample_rgba (k_resample.hip's resize over the four planes, stored as BGRA dwords).
+// resample_rgba (k_resample.hip's resize over the four planes - the shared passes of pixel_device.h -, stored as BGRA dwords).
 #include "kernels.h"
-#include "prepost_device.h"
+#include "pixel_device.h"
 
 namespace w2x {
 namespace {
@@ -114,33 +115,18 @@ __global__ __launch_bounds__(256) void alpha_bleed_kernel(const AlphaBleedParams
     if (tid < 2) atomicMax(p.minmax + tid, wg_max[tid]);
 }
 
-// gather_kernel's indexing (replicate padding, the TTA source map) on the plane the slot names
+// gather_kernel's indexing (gather_loop: replicate padding, the TTA source map) on the plane the slot names
 template <typename P>
-__global__ __launch_bounds__(256) void gather_rgba_kernel(const GatherRgbaParams p) {
-    const int T = p.T;
-    const long total = (long)p.B * T * T;
+__global__ __launch_bounds__(kGatherThreads) void gather_rgba_kernel(const GatherRgbaParams p) {
     const float inv255 = (float)(1.0 / 255.0);
-    for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < total; i += (long)gridDim.x * blockDim.x) {
-        int b = (int)(i / ((long)T * T));
-        int rem = (int)(i - (long)b * T * T);
-        int y = rem / T, x = rem - y * T;
-        TileSlot sl = p.slots[b];
-        P v = make_px<P>(0.f, 0.f, 0.f);
-        if (sl.valid) {
-            int sy, sx;
-            aug_src(sl.aug, T - 1, y, x, sy, sx);
-            int fy = min(max(sl.y + sy, 0), p.rows - 1);
-            int fx = min(max(sl.x + sx, 0), p.cols - 1);
-            if (sl.valid == kSlotAlpha) {
-                const float a = (float)p.alpha[(size_t)fy * p.alpha_step + fx] * inv255;
-                v = make_px<P>(a, a, a);
-            } else {
-                const uint8_t* px = p.bgr + (size_t)fy * p.bgr_step + (size_t)fx * 3;
-                v = make_px<P>((float)px[2] * inv255, (float)px[1] * inv255, (float)px[0] * inv255);
-            }
+    gather_loop<P>(p.slots, p.B, p.T, p.rows, p.cols, p.out, [&](const TileSlot& sl, int fy, int fx) {
+        if (sl.valid == kSlotAlpha) {
+            const float a = (float)p.alpha[(size_t)fy * p.alpha_step + fx] * inv255;
+            return make_px<P>(a, a, a);
         }
-        *((P*)p.out + i) = v;
-    }
+        const uint8_t* px = p.bgr + (size_t)fy * p.bgr_step + (size_t)fx * 3;
+        return make_px<P>((float)px[2] * inv255, (float)px[1] * inv255, (float)px[0] * inv255);
+    });
 }
 
 // A thread per pixel along a row (a wave stores 256 contiguous bytes), a workgroup row per output row.
@@ -184,83 +170,34 @@ __global__ __launch_bounds__(256) void compose_canvas_rgba_kernel(const ComposeC
     }
 }
 
-// resample_kernel (k_resample.hip) over four planes: the same 16 x 64 output tile per workgroup, the same tap tables, pass 1 horizontally from the canvas into
-// LDS, pass 2 vertically out of LDS with a thread per four pixels of a row; every plane is accumulated with resample_kernel's expressions in its tap order
-// (a += wk * s[k]), so a plane's value is the one resample_kernel gives for the same canvas plane, and the quantisation is its q8.
-// LDS: [NP][rows_max][64] fp32, NP = 4 (3 when the alpha plane is uniform and not filtered).  At a factor of 4 with bicubic taps rows_max <= 78:
-// 4 * 78 * 256 B = 78 KiB, two workgroups per CU in its 160 KiB (NP = 3: resample_kernel's 58.5 KiB).  Banks: a row is 64 dwords, one per bank.  Pass 1
-// stores dword c of a row from lane c: a wave covers one whole row, every bank once.  Pass 2 reads 16 bytes per lane (ds_read_b128, served in four groups
-// of 16 lanes that are not contiguous: {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31} and the same in the upper half wave).  Lanes 0-15 of a half wave are the
-// 16 column groups of one output row, lanes 16-31 those of the next, so a group holds column groups 0-3 and 12-15 of one output row - dwords 0-15 and
-// 48-63 of its LDS row - and column groups 4-11 of the other - dwords 16-47 of that row's LDS row (or the complement).  The two LDS rows may differ (each
-// output row's taps start where they start), but a row is exactly 64 dwords, so the bank is the dword's column: the group touches every bank once.
-// The planes lie rows_max * 64 dwords apart, a multiple of the bank count, but each plane is read by an instruction of its own, so the fourth plane
-// adds instructions and no conflicts.
+// resample_kernel (k_resample.hip) over four planes: resample_pass1 / resample_pass2 (pixel_device.h) at NP = 4 - NP = 3 when the alpha plane is uniform and not
+// filtered -, so a plane's value is the one resample_kernel gives for the same canvas plane, and the quantisation is its sat(rint(x * 255)).
+// LDS: [NP][rows_max][64] fp32.  At a factor of 4 with bicubic taps rows_max <= 78: 4 * 78 * 256 B = 78 KiB, two workgroups per CU in its 160 KiB (NP = 3:
+// resample_kernel's 58.5 KiB).  Banks: a row is 64 dwords, one per bank.  Pass 1 stores dword c of a row from lane c: a wave covers one whole row, every bank
+// once.  Pass 2 reads 16 bytes per lane (ds_read_b128, served in four groups of 16 lanes that are not contiguous: {0-3, 12-15, 20-27}, {4-11, 16-19, 28-31}
+// and the same in the upper half wave).  Lanes 0-15 of a half wave are the 16 column groups of one output row, lanes 16-31 those of the next, so a group
+// holds column groups 0-3 and 12-15 of one output row - dwords 0-15 and 48-63 of its LDS row - and column groups 4-11 of the other - dwords 16-47 of that
+// row's LDS row (or the complement).  The two LDS rows may differ (each output row's taps start where they start), but a row is exactly 64 dwords, so the
+// bank is the dword's column: the group touches every bank once.
 // Stores: the thread's four BGRA dwords as one 16-byte store where the address is 16-byte aligned (dst is packed: the pitch outW * 4 is a multiple of 16
 // only when outW % 4 == 0, so this is decided per row from the address), dword by dword otherwise and for the 1 - 3 pixels the right edge leaves.
-// (kRs*, q8: second copies of k_resample.hip's kTR / kTC / kThreads and q8 - a shared device header would have changed that file's translation unit.
-//  They must stay in step with it: byte equality with resample_kernel rests on the same tile, the same tap order and the same quantisation.)
-constexpr int kRsRows = kResampleRows, kRsCols = kResampleCols, kRsThreads = 256;
-static_assert(kRsCols == 64 && kRsRows * (kRsCols / 4) == kRsThreads, "pass 2 maps one thread to four pixels of the tile");
-
-__device__ __forceinline__ unsigned q8(float v) { return (unsigned)min(max(__float2int_rn(v * 255.f), 0), 255); }
-
 template <bool kAlpha>
 __global__ __launch_bounds__(kRsThreads) void resample_rgba_kernel(const ResampleRgbaParams p) {
-    extern __shared__ float rs_lds[];                                     // [kAlpha ? 4 : 3][rows_max][kRsCols]
-    float* const h = rs_lds;
-    const int ox0 = blockIdx.x * kRsCols, oy0 = blockIdx.y * kRsRows;
-    const int tw = min(kRsCols, p.outW - ox0), th = min(kRsRows, p.outH - oy0);
-    const int r0 = p.fy[oy0];
-    const int nr = min(p.inH, p.fy[oy0 + th - 1] + p.ky) - r0;           // <= rows_max (resample_rows_max)
-    const size_t plane = (size_t)p.inW * p.inH;
-    const int rm = p.rows_max;
-    // pass 1: input rows [r0, r0 + nr) filtered horizontally onto the tile's output columns
-    for (int i = threadIdx.x; i < nr * kRsCols; i += kRsThreads) {
-        const int r = i / kRsCols, c = i % kRsCols;
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-        if (c < tw) {
-            const int X = ox0 + c, f = p.fx[X];
-            const int n = min(p.kx, p.inW - f);
-            const float* w = p.wx + (size_t)X * p.kx;
-            const float* s = p.canvas + (size_t)(r0 + r) * p.inW + f;
-            for (int k = 0; k < n; ++k) {
-                const float wk = w[k];
-                a0 += wk * s[k]; a1 += wk * s[plane + k]; a2 += wk * s[2 * plane + k];
-                if (kAlpha) a3 += wk * s[3 * plane + k];
-            }
-        }
-        h[(0 * rm + r) * kRsCols + c] = a0; h[(1 * rm + r) * kRsCols + c] = a1; h[(2 * rm + r) * kRsCols + c] = a2;
-        if (kAlpha) h[(3 * rm + r) * kRsCols + c] = a3;
-    }
+    constexpr int NP = kAlpha ? 4 : 3;
+    extern __shared__ float rs_lds[];
+    const int r0 = resample_pass1<NP>(p, rs_lds);
     __syncthreads();
-    // pass 2: four output pixels of one row per thread
-    const int ty = threadIdx.x / (kRsCols / 4), cg = threadIdx.x % (kRsCols / 4);
-    if (ty >= th) return;
-    const int Y = oy0 + ty, X = ox0 + 4 * cg;
-    const int np = min(4, p.outW - X);
-    if (np <= 0) return;
-    const int f = p.fy[Y];
-    const int n = min(p.ky, p.inH - f);
-    const float* w = p.wy + (size_t)Y * p.ky;
-    float4v a0 = {0.f, 0.f, 0.f, 0.f}, a1 = a0, a2 = a0, a3 = a0;
-    for (int k = 0; k < n; ++k) {
-        const float wk = w[k];
-        const int r = f - r0 + k;
-        a0 += wk * *(const float4v*)&h[(0 * rm + r) * kRsCols + 4 * cg];
-        a1 += wk * *(const float4v*)&h[(1 * rm + r) * kRsCols + 4 * cg];
-        a2 += wk * *(const float4v*)&h[(2 * rm + r) * kRsCols + 4 * cg];
-        if (kAlpha) a3 += wk * *(const float4v*)&h[(3 * rm + r) * kRsCols + 4 * cg];
-    }
+    float4v a[NP];
+    int X, Y, np;
+    if (!resample_pass2<NP>(p, rs_lds, r0, a, X, Y, np)) return;
     unsigned px[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) px[q] = q8(a2[q]) | q8(a1[q]) << 8 | q8(a0[q]) << 16 | (kAlpha ? q8(a3[q]) : p.alpha_value) << 24;   // b | g << 8 | r << 16 | a << 24
+    for (int q = 0; q < 4; ++q)                                           // b | g << 8 | r << 16 | a << 24
+        px[q] = quant(a[2][q], 255.f, 255) | quant(a[1][q], 255.f, 255) << 8 | quant(a[0][q], 255.f, 255) << 16 | (kAlpha ? quant(a[NP - 1][q], 255.f, 255) : p.alpha_value) << 24;
     unsigned* d = (unsigned*)(p.dst + (size_t)Y * p.dst_step) + X;
     if (np == 4 && (((size_t)d) & 15) == 0) *(uint4*)d = make_uint4(px[0], px[1], px[2], px[3]);
     else for (int q = 0; q < np; ++q) d[q] = px[q];
 }
-
-inline unsigned grid_for(long total) { long g = (total + 255) / 256; return (unsigned)(g > 8192 ? 8192 : (g < 1 ? 1 : g)); }
 
 }  // namespace
 
@@ -274,8 +211,8 @@ hipError_t launch_alpha_bleed(const AlphaBleedParams& p, hipStream_t s) {
 }
 hipError_t launch_gather_rgba(const GatherRgbaParams& p, hipStream_t s) {
     const dim3 grid(grid_for((long)p.B * p.T * p.T));
-    if (p.fp32) hipLaunchKernelGGL(gather_rgba_kernel<float4v>, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(gather_rgba_kernel<half4>, grid, dim3(256), 0, s, p);
+    if (p.fp32) hipLaunchKernelGGL(gather_rgba_kernel<float4v>, grid, dim3(kGatherThreads), 0, s, p);
+    else hipLaunchKernelGGL(gather_rgba_kernel<half4>, grid, dim3(kGatherThreads), 0, s, p);
     return hipGetLastError();
 }
 hipError_t launch_compose_rgba(const ComposeRgbaParams& p, hipStream_t s) {
@@ -295,13 +232,12 @@ hipError_t launch_compose_canvas_rgba(const ComposeCanvasRgbaParams& p, hipStrea
 }
 hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
-    constexpr int kMaxRows = 104;                                        // as launch_resample: factor 4, bicubic is 78
-    if (p.rows_max <= 0 || p.rows_max > kMaxRows || (p.dst_step & 3) || p.dst_step < (size_t)p.outW * 4 || (((size_t)p.dst) & 3)) return hipErrorInvalidValue;
+    if (p.rows_max <= 0 || p.rows_max > kRsMaxRows || (p.dst_step & 3) || p.dst_step < (size_t)p.outW * 4 || (((size_t)p.dst) & 3)) return hipErrorInvalidValue;
     const int planes = p.uniform ? 3 : 4;
     const int lds = planes * p.rows_max * kRsCols * (int)sizeof(float);
     static unsigned lds_done[2] = {0, 0};
     const void* fn = p.uniform ? (const void*)resample_rgba_kernel<false> : (const void*)resample_rgba_kernel<true>;
-    hipError_t e = ensure_dynamic_lds(fn, planes * kMaxRows * kRsCols * (int)sizeof(float), lds_done[p.uniform ? 0 : 1]);
+    hipError_t e = ensure_dynamic_lds(fn, planes * kRsMaxRows * kRsCols * (int)sizeof(float), lds_done[p.uniform ? 0 : 1]);
     if (e != hipSuccess) return e;
     const dim3 grid((unsigned)((p.outW + kRsCols - 1) / kRsCols), (unsigned)((p.outH + kRsRows - 1) / kRsRows));
     if (p.uniform) hipLaunchKernelGGL(resample_rgba_kernel<false>, grid, dim3(kRsThreads), lds, s, p);

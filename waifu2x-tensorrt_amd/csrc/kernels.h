@@ -273,6 +273,14 @@ struct ResampleParams {
     int rows_max = 0;
 };
 constexpr int kResampleRows = 16, kResampleCols = 64;
+// compose_kernel's launch shape (k_prepost.hip, where the choice is measured), also compose_planes_kernel's: rows a thread walks, threads per workgroup
+#ifndef W2X_COMPOSE_ROWS
+#define W2X_COMPOSE_ROWS 4
+#endif
+#ifndef W2X_COMPOSE_THREADS
+#define W2X_COMPOSE_THREADS 64
+#endif
+constexpr int kComposeRows = W2X_COMPOSE_ROWS, kComposeThreads = W2X_COMPOSE_THREADS;
 int resample_rows_max(const int* fy, int outH, int inH, int ky);   // host: the largest input row span of an output row tile
 hipError_t launch_resample(const ResampleParams& p, hipStream_t s);
 // YUV 4:2:0 frames (Img2Img::renderYuv): three planes - Y of rows x cols, U and V of ceil(rows/2) x ceil(cols/2) - with 8-bit (uint8) or 10-bit
@@ -393,42 +401,20 @@ struct ResampleRgbaParams {
     int uniform = 0; unsigned alpha_value = 255;
 };
 hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s);
-// Gray frames (renderGray; k_gray.hip): one sample per pixel on both sides, the result the green channel of the BGR path on B = G = R = g.
-// gather_gray_kernel: gather_kernel's tiles (same slots, replicate padding, TTA source index) from a one-sample frame: pixel (a, a, a, 0),
-// a = u8 * fl32(1/255) (deep: u16 * fl32(1/65535)); step in bytes.
-struct GatherGrayParams {
-    const uint8_t* frame = nullptr; int rows = 0, cols = 0; size_t step = 0;
-    int deep = 0;
-    void* out = nullptr; int fp32 = 0;
-    const TileSlot* slots = nullptr;
-    int B = 0, T = 0;
-};
-hipError_t launch_gather_gray(const GatherGrayParams& p, hipStream_t s);
-// compose_gray_kernel: compose_kernel over the whole canvas of p (x0..y1 unused) on the green channel alone: p.dst holds one sample per pixel (deep: u16),
-// p.dst_step bytes per row.  compose_canvas_gray_kernel: the same green sums unquantised as one fp32 plane canvas[Y][X] of outH x outW.
-hipError_t launch_compose_gray(const ComposeParams& p, hipStream_t s);
-hipError_t launch_compose_canvas_gray(const ComposeParams& p, float* canvas, hipStream_t s);
-// resample_gray_kernel: resample_kernel's resize (same tap tables, same rows_max, same accumulation) of that one plane, quantised sat(rint(x * 255))
-// (deep: 65535) and stored one sample per pixel into dst (dst_step bytes per row)
-struct ResampleGrayParams {
-    const float* canvas = nullptr; int inW = 0, inH = 0;
-    uint8_t* dst = nullptr; size_t dst_step = 0; int deep = 0;
-    int outW = 0, outH = 0;
-    const int* fx = nullptr; const float* wx = nullptr; int kx = 0;
-    const int* fy = nullptr; const float* wy = nullptr; int ky = 0;
-    int rows_max = 0;
-};
-hipError_t launch_resample_gray(const ResampleGrayParams& p, hipStream_t s);
-// Planar RGB frames (renderPlanar; k_planar.hip): three planes R, G, B of rows x cols samples - uint8 (bits 8), little-endian uint16 with the code
-// in the low bits (10 / 12 / 16) or float32 of nominal [0, 1] (32) - each with its own pointer and step in bytes; u16 / f32 samples aligned to their size.
+// Frames of planes (k_planar.hip): `n` planes of rows x cols samples - uint8 (bits 8), little-endian uint16 with the code in the low bits (10 / 12 / 16) or
+// float32 of nominal [0, 1] (32) - each with its own pointer and step in bytes; u16 / f32 samples aligned to their size.  n = 3: planar RGB frames (renderPlanar,
+// DESIGN 9h), planes R, G, B.  n = 1: gray frames (renderGray) of 8 or 16 bits: one sample per pixel on both sides, the result the green channel of
+// the BGR path on B = G = R = g - the planar frame whose three planes are the one.
 struct PlanarPlanes {
     uint8_t* p[3] = {nullptr, nullptr, nullptr}; size_t step[3] = {0, 0, 0};
     int rows = 0, cols = 0, bits = 8;
+    int n = 3;
 };
 inline bool planar_bits_ok(int bits) { return bits == 8 || bits == 10 || bits == 12 || bits == 16 || bits == 32; }
 inline size_t planar_sample_bytes(int bits) { return bits == 32 ? 4 : bits > 8 ? 2 : 1; }
-// gather_planar_kernel: gather_kernel's tiles (same slots, replicate padding, TTA source index) from the three planes: the tile pixel is make_px(r, g, b), each
-// sample min(code, 2^bits - 1) * fl32(1 / (2^bits - 1)) - at 8 and 16 bits gather_kernel's own constants - or, float, min(max(x, 0), 1) with NaN -> 0
+// gather_planes_kernel: gather_kernel's tiles (same slots, replicate padding, TTA source index) from the planes: the tile pixel is make_px(r, g, b) - one plane:
+// (a, a, a, 0) -, each sample min(code, 2^bits - 1) * fl32(1 / (2^bits - 1)) - at 8 and 16 bits gather_kernel's own constants - or, float, min(max(x, 0), 1)
+// with NaN -> 0
 struct GatherPlanarParams {
     PlanarPlanes src;
     void* out = nullptr; int fp32 = 0;
@@ -436,15 +422,18 @@ struct GatherPlanarParams {
     int B = 0, T = 0;
 };
 hipError_t launch_gather_planar(const GatherPlanarParams& p, hipStream_t s);
-// compose_planar_kernel: compose_kernel over the whole canvas of c (c.dst / c.deep / x0..y1 unused): the three sums of compose_pixel_sums into the planes of dst
-// (c.outH x c.outW), integer sat(rint(x * (2^bits - 1))), float min(max(x, 0), 1) stored as fp32
+// compose_planes_kernel: compose_kernel over the whole canvas of c (c.dst / c.deep / x0..y1 unused): the three sums of compose_pixel_sums - one plane: the
+// green sum - into the planes of dst (c.outH x c.outW), integer sat(rint(x * (2^bits - 1))), float min(max(x, 0), 1) stored as fp32
 struct ComposePlanarParams {
     ComposeParams c;
     PlanarPlanes dst;
 };
 hipError_t launch_compose_planar(const ComposePlanarParams& p, hipStream_t s);
-// resample_planar_kernel: resample_kernel's resize (same tap tables, same rows_max, same accumulation) of the fp32 RGB canvas compose_canvas_kernel writes, the
-// three accumulators quantised like compose_planar_kernel into the planes of dst (outH x outW)
+// compose_canvas_gray_kernel: the green sums of compose_pixel_sums over the whole canvas of p (x0..y1, dst, deep unused) unquantised as one fp32 plane
+// canvas[Y][X] of outH x outW: the canvas of a resized gray frame (a resized planar frame has compose_canvas_kernel's)
+hipError_t launch_compose_canvas_gray(const ComposeParams& p, float* canvas, hipStream_t s);
+// resample_planes_kernel: resample_kernel's resize (same tap tables, same rows_max, same accumulation) of the fp32 canvas of dst.n planes, the accumulators
+// quantised like compose_planes_kernel into the planes of dst (outH x outW)
 struct ResamplePlanarParams {
     const float* canvas = nullptr; int inW = 0, inH = 0;
     int outW = 0, outH = 0;

@@ -1,0 +1,211 @@
+// Device pieces shared by the frame formats that stand beside the BGR path: planar and gray frames (k_planar.hip) and RGBA frames (k_rgba.hip).  Each piece is
+// the corresponding piece of a BGR kernel (gather_kernel, compose_kernel of k_prepost.hip; resample_kernel of k_resample.hip) with the format-specific load or
+// store left to the caller: a format supplies a loader and a store and reuses the bodies.  The byte-for-byte contracts of DESIGN 9d - 9h rest on the arithmetic
+// and its order here being the BGR kernels': the same slots and clamps, compose_pixel_sums' weights in the order L, T, R, B, resample_kernel's tile, tap tables
+// and tap order (a += wk * s[k]) and one quantisation, sat(rint(x * maxcode)).  k_prepost.hip and k_resample.hip do not include this header: the kernels of the
+// BGR and YUV paths keep their listings.
+#pragma once
+#include "kernels.h"
+#include "prepost_device.h"
+
+namespace w2x {
+namespace {
+
+// ---- launch shapes
+// gather: a flat grid-stride loop of workgroups of kGatherThreads, which the loop takes as a constant: in a device function blockDim.x is not folded to the
+// launch's one workgroup size as it is in a kernel's own body, and costs a dependent load before the first index (0.5 us on a launch of 10 us)
+constexpr int kGatherThreads = 256;
+inline unsigned grid_for(long total) { long g = (total + kGatherThreads - 1) / kGatherThreads; return (unsigned)(g > 8192 ? 8192 : (g < 1 ? 1 : g)); }
+// compose, four pixels per thread: compose_kernel's kComposeRows / kComposeThreads (kernels.h)
+// resample: resample_kernel's output tile (kernels.h) and workgroup.  Byte equality with resample_kernel rests on the same tile, the same tap order and the
+// same quantisation.
+constexpr int kRsRows = kResampleRows, kRsCols = kResampleCols, kRsThreads = 256;
+static_assert(kRsCols == 64 && kRsRows * (kRsCols / 4) == kRsThreads, "pass 2 maps one thread to four pixels of the tile");
+constexpr int kRsMaxRows = 104;                                          // as launch_resample: factor 4, bicubic is 78
+
+// ---- the sample types: what a plane holds per pixel.  `maxcode` is 2^bits - 1 and `inv` fl32(1 / maxcode), both made on the host (launch_*).
+struct U8 { typedef uint8_t T; };
+struct U16 { typedef uint16_t T; };
+struct F32 { typedef float T; };
+
+template <typename S> __device__ __forceinline__ float load_sample(const uint8_t* row, int x, unsigned maxcode, float inv);
+template <> __device__ __forceinline__ float load_sample<U8>(const uint8_t* row, int x, unsigned, float inv) { return (float)row[x] * inv; }
+template <> __device__ __forceinline__ float load_sample<U16>(const uint8_t* row, int x, unsigned maxcode, float inv) {
+    return (float)min((unsigned)((const uint16_t*)row)[x], maxcode) * inv;
+}
+template <> __device__ __forceinline__ float load_sample<F32>(const uint8_t* row, int x, unsigned, float) {
+    const float v = ((const float*)row)[x];
+    return !(v >= 0.f) ? 0.f : fminf(v, 1.f);                      // (NaN fails the comparison: 0)
+}
+
+// sat(rint(x * maxcode)): quantize_bgr's expression per sample (compose) and k_resample.hip's q8 / q16 (resample) with the code range a launch argument - at
+// 255 and 65535 the same product and the same rounding, which byte equality with the BGR kernels rests on.  Float: the sum clamped, never rounded to a code.
+__device__ __forceinline__ unsigned quant(float v, float scale, int maxcode) { return (unsigned)min(max(__float2int_rn(v * scale), 0), maxcode); }
+__device__ __forceinline__ float sat01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
+
+// Four consecutive samples of one plane's row, starting at column X (a multiple of 4): np == 4 and an aligned address leave as ONE store - a dword, 8 or 16
+// bytes -, the 1 - 3 samples of a ragged right end (or a caller's unaligned rows) one by one.  From the engine's buffers (hipMalloc, rows padded to 16 bytes:
+// planar_step) a full group is always aligned.
+template <typename S> __device__ __forceinline__ void store4(uint8_t* row, int X, int np, const float v[4], float scale, int maxcode);
+template <> __device__ __forceinline__ void store4<U8>(uint8_t* row, int X, int np, const float v[4], float scale, int maxcode) {
+    uint8_t* d = row + X;
+    unsigned q[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = quant(v[k], scale, maxcode);
+    if (np == 4 && (((size_t)d) & 3) == 0) *(unsigned*)d = q[0] | q[1] << 8 | q[2] << 16 | q[3] << 24;
+    else for (int k = 0; k < np; ++k) d[k] = (uint8_t)q[k];
+}
+template <> __device__ __forceinline__ void store4<U16>(uint8_t* row, int X, int np, const float v[4], float scale, int maxcode) {
+    uint16_t* d = (uint16_t*)row + X;
+    unsigned q[4];
+#pragma unroll
+    for (int k = 0; k < 4; ++k) q[k] = quant(v[k], scale, maxcode);
+    if (np == 4 && (((size_t)d) & 7) == 0) *(uint2*)d = make_uint2(q[0] | q[1] << 16, q[2] | q[3] << 16);
+    else for (int k = 0; k < np; ++k) d[k] = (uint16_t)q[k];
+}
+template <> __device__ __forceinline__ void store4<F32>(uint8_t* row, int X, int np, const float v[4], float, int) {
+    float* d = (float*)row + X;
+    if (np == 4 && (((size_t)d) & 15) == 0) *(float4v*)d = (float4v){sat01(v[0]), sat01(v[1]), sat01(v[2]), sat01(v[3])};
+    else for (int k = 0; k < np; ++k) d[k] = sat01(v[k]);
+}
+
+// ---- gather_kernel's loop: tile pixel i of B tiles of T x T, the slot lookup, the zero pixel of a pad slot, the TTA source map and the replicate clamp to a
+// frame of rows x cols.  load(slot, fy, fx) makes the tile pixel P of frame pixel (fy, fx).
+template <typename P, typename Load>
+__device__ __forceinline__ void gather_loop(const TileSlot* slots, int B, int T, int rows, int cols, void* out, Load load) {
+    const long total = (long)B * T * T;
+    for (long i = (long)blockIdx.x * kGatherThreads + threadIdx.x; i < total; i += (long)gridDim.x * kGatherThreads) {
+        int b = (int)(i / ((long)T * T));
+        int rem = (int)(i - (long)b * T * T);
+        int y = rem / T, x = rem - y * T;
+        TileSlot sl = slots[b];
+        P v = make_px<P>(0.f, 0.f, 0.f);
+        if (sl.valid) {
+            int sy, sx;
+            aug_src(sl.aug, T - 1, y, x, sy, sx);
+            int fy = min(max(sl.y + sy, 0), rows - 1);
+            int fx = min(max(sl.x + sx, 0), cols - 1);
+            v = load(sl, fy, fx);
+        }
+        *((P*)out + i) = v;
+    }
+}
+
+// ---- compose_kernel's four-pixel fast path: the sums of pixels X .. X + 3 (X a multiple of 4) of row Y where the four share their covering tile columns
+// a0 .. a1, lie inside each of them and no TTA is involved (the caller's test), the tiles [To][To][4] fp16.  A tile contributes its four pixels as two 16-byte
+// loads; the per-pixel arithmetic and its order are compose_pixel_sums', so the sums are the ones the per-pixel path gives.  NC = 3 keeps the three channels
+// (acc[0..2] = r, g, b), NC = 1 the green channel alone (acc[0]).
+template <int NC, typename CP>
+__device__ __forceinline__ void compose_quad_sums(const CP& p, int X, int Y, int a0, int a1, float (&acc)[NC][4]) {
+    static_assert(NC == 1 || NC == 3, "green alone, or r, g, b");
+    const int To = p.To, n = To - 1;
+    float s[NC][4] = {};
+    int j0 = Y - To + 1; j0 = j0 <= 0 ? 0 : (j0 + p.stride_y - 1) / p.stride_y;
+    const int j1 = min(p.ny - 1, Y / p.stride_y);
+    for (int ti = a0; ti <= a1; ++ti) {
+        const int ox = ti * p.stride_x, lx = X - ox;
+        const int rw = ox + To > p.outW ? p.outW - ox : To;
+        for (int tj = j0; tj <= j1; ++tj) {
+            const int oy = tj * p.stride_y, ly = Y - oy;
+            const int rh = oy + To > p.outH ? p.outH - oy : To;
+            const long tile = (long)ti * p.ny + tj - p.first_tile;
+            const half4* tp = (const half4*)p.tiles + tile * (long)To * To + (long)ly * To + lx;
+            half4 h[4];                                            // (NC == 1: only the green halves are converted, or loaded at all)
+            if ((((size_t)tp) & 15) == 0) { const half8 u0 = *(const half8*)tp, u1 = *(const half8*)(tp + 2);
+                h[0] = (half4){u0[0], u0[1], u0[2], u0[3]}; h[1] = (half4){u0[4], u0[5], u0[6], u0[7]}; h[2] = (half4){u1[0], u1[1], u1[2], u1[3]}; h[3] = (half4){u1[4], u1[5], u1[6], u1[7]}; }
+            else if constexpr (NC == 1) { h[0][1] = tp[0][1]; h[1][1] = tp[1][1]; h[2][1] = tp[2][1]; h[3][1] = tp[3][1]; }
+            else { h[0] = tp[0]; h[1] = tp[1]; h[2] = tp[2]; h[3] = tp[3]; }
+            const bool wl = ox > 0, wt = oy > 0 && ly < p.ovy, wr = ox + rw < p.outW, wb = oy + rh < p.outH && n - ly < p.ovy;
+            const float fy_t = wt ? p.ramp_y[ly] : 1.f, fy_b = wb ? p.ramp_y[n - ly] : 1.f;
+#pragma unroll
+            for (int k = 0; k < 4; ++k) {
+                float v[NC];
+#pragma unroll
+                for (int c = 0; c < NC; ++c) v[c] = (float)h[k][NC == 1 ? 1 : c];
+                if (p.ovx || p.ovy) {
+                    const int lk = lx + k;
+                    if (wl && lk < p.ovx) { const float w = p.ramp_x[lk];
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) v[c] *= w; }
+                    if (wt) {
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) v[c] *= fy_t; }
+                    if (wr && n - lk < p.ovx) { const float w = p.ramp_x[n - lk];
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) v[c] *= w; }
+                    if (wb) {
+#pragma unroll
+                        for (int c = 0; c < NC; ++c) v[c] *= fy_b; }
+                }
+#pragma unroll
+                for (int c = 0; c < NC; ++c) s[c][k] += v[c];
+            }
+        }
+    }
+#pragma unroll
+    for (int c = 0; c < NC; ++c)
+#pragma unroll
+        for (int k = 0; k < 4; ++k) acc[c][k] = s[c][k];
+}
+
+// ---- resample_kernel's two passes over NP planes of the fp32 canvas (plane stride inW * inH).  A workgroup of kRsThreads owns an output tile of kRsRows x
+// kRsCols pixels; h is its LDS, [NP][rows_max][kRsCols] fp32.  Banks: a row is 64 dwords, one per bank; pass 1 stores dword c of a row from lane c, pass 2 reads
+// 16 bytes per lane of one row, each plane by an instruction of its own - the planes lie a multiple of the bank count apart and add instructions, no conflicts.
+// Pass 1: the input rows [r0, r0 + nr) the tile needs, filtered horizontally onto its output columns; returns r0.  The caller's barrier follows.
+template <int NP, typename RP>
+__device__ __forceinline__ int resample_pass1(const RP& p, float* h) {
+    const int ox0 = blockIdx.x * kRsCols, oy0 = blockIdx.y * kRsRows;
+    const int tw = min(kRsCols, p.outW - ox0), th = min(kRsRows, p.outH - oy0);
+    const int r0 = p.fy[oy0];
+    const int nr = min(p.inH, p.fy[oy0 + th - 1] + p.ky) - r0;           // <= rows_max (resample_rows_max)
+    const size_t plane = (size_t)p.inW * p.inH;
+    const int rm = p.rows_max;
+    for (int i = threadIdx.x; i < nr * kRsCols; i += kRsThreads) {
+        const int r = i / kRsCols, c = i % kRsCols;
+        float a[NP];
+#pragma unroll
+        for (int q = 0; q < NP; ++q) a[q] = 0.f;
+        if (c < tw) {
+            const int X = ox0 + c, f = p.fx[X];
+            const int n = min(p.kx, p.inW - f);
+            const float* w = p.wx + (size_t)X * p.kx;
+            const float* s = p.canvas + (size_t)(r0 + r) * p.inW + f;
+            for (int k = 0; k < n; ++k) {
+                const float wk = w[k];
+#pragma unroll
+                for (int q = 0; q < NP; ++q) a[q] += wk * s[q * plane + k];
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < NP; ++q) h[(q * rm + r) * kRsCols + c] = a[q];
+    }
+    return r0;
+}
+// Pass 2: the rows of LDS filtered vertically, four output pixels (X .. X + 3 of row Y, np of them inside the frame) per thread: a[q] their sums of plane q.
+// false: the thread has no pixel to store.
+template <int NP, typename RP>
+__device__ __forceinline__ bool resample_pass2(const RP& p, const float* h, int r0, float4v (&a)[NP], int& X, int& Y, int& np) {
+    const int ox0 = blockIdx.x * kRsCols, oy0 = blockIdx.y * kRsRows;
+    const int th = min(kRsRows, p.outH - oy0);
+    const int ty = threadIdx.x / (kRsCols / 4), cg = threadIdx.x % (kRsCols / 4);
+    if (ty >= th) return false;
+    Y = oy0 + ty; X = ox0 + 4 * cg;
+    np = min(4, p.outW - X);
+    if (np <= 0) return false;
+    const int rm = p.rows_max;
+    const int f = p.fy[Y];
+    const int n = min(p.ky, p.inH - f);
+    const float* w = p.wy + (size_t)Y * p.ky;
+#pragma unroll
+    for (int q = 0; q < NP; ++q) a[q] = (float4v){0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < n; ++k) {
+        const float wk = w[k];
+        const int r = f - r0 + k;
+#pragma unroll
+        for (int q = 0; q < NP; ++q) a[q] += wk * *(const float4v*)&h[(q * rm + r) * kRsCols + 4 * cg];
+    }
+    return true;
+}
+
+}  // namespace
+}  // namespace w2x
