@@ -52,6 +52,14 @@ struct PlanarImage {
     int rows = 0, cols = 0;
     int bits = 8;
 };
+// Extension: a planar RGBA frame - PlanarImage with a fourth plane: planes[0..3] = R, G, B, A (a gbrap AVFrame: data[2], data[0], data[1], data[3]),
+// all of one sample type and size; alpha is straight (not premultiplied) and read like a colour sample.
+struct PlanarRgbaImage {
+    uint8_t* planes[4] = {nullptr, nullptr, nullptr, nullptr};
+    size_t steps[4] = {0, 0, 0, 0};
+    int rows = 0, cols = 0;
+    int bits = 8;
+};
 enum class YuvMatrix { BT601 = 0, BT709 = 1, BT2020 = 2 };   // (Kr, Kb) = (0.299, 0.114), (0.2126, 0.0722), (0.2627, 0.0593); BT.2020 non-constant luminance
 enum class YuvRange { Limited = 0, Full = 1 };               // "tv": Y 16..235, C 16..240 (times 2^(bits-8)); "pc": 0 .. 2^bits - 1
 struct YuvFormat {
@@ -159,6 +167,23 @@ public:
     // copies per frame each way.  No progress is reported.
     bool renderSequencePlanar(const PlanarImage* srcs, PlanarImage* dsts, int count);
     bool renderSequencePlanarResized(const PlanarImage* srcs, PlanarImage* dsts, int count, ResizeFilter filter = ResizeFilter::Bicubic);
+    // Extension: planar RGBA frames - renderRgba() on renderPlanar()'s samples: four planes R, G, B, A at 8, 10, 12, 16 bits or float on either side,
+    // src.bits and dst.bits independent, one upload of four planes, the bleed on the device at every integer depth, ONE schedule of the frame's N colour tiles
+    // and N alpha tiles (progress: ceil(2N * steps / batchSize) batches), one download of four planes.  Every sample, alpha included, is read as renderPlanar()
+    // reads it; a pixel is visible iff its alpha sample read that way is > 0.  No tolerance anywhere:
+    //   colour planes: renderPlanar() / renderPlanarResized() of alpha_bleed_planes((R, G, B), A, bleed) at the same depths, byte for byte (float: bit for bit);
+    //   alpha plane:   the G plane of renderPlanar() / renderPlanarResized() of the frame (A, A, A) at the same depths (8 / 8 and 16 / 16 bits: renderGray(A));
+    //   8 / 8 bits:    the four planes interleaved as B, G, R, A are the bytes of renderRgba() / renderRgbaResized() with the same options.
+    // skipUniformAlpha and every alpha sample, read as above, one value v: no alpha tiles, every output alpha is sat(rint(v * (2^dst.bits - 1))) - float: v -, the
+    // progress total is the colour tiles' alone.  At the scaled size a resized call is the plain one.  An integer frame and its float frame give the same
+    // bytes wherever renderPlanar() gives them the same: not where the B or the A plane holds code 2047 or 4094 of 12 bits, 65455 or 65519 of 16.  Other depths, empty frames, missing planes, short steps,
+    // misaligned u16 / f32 samples, other sizes, bleed outside [0, 16], bleed > 0 on float samples (a float bleed is not built): false (message callback).
+    bool renderPlanarRgba(const PlanarRgbaImage& src, PlanarRgbaImage& dst, const RgbaOptions& opt = {});
+    bool renderPlanarRgbaResized(const PlanarRgbaImage& src, PlanarRgbaImage& dst, const RgbaOptions& opt = {}, ResizeFilter filter = ResizeFilter::Bicubic);
+    // Planar RGBA frames through renderSequence()'s pipeline (page-locked buffers: allocHost()): one size, one pair of depths and one set of options per sequence;
+    // output i is the bytes of the single call on frame i, skipUniformAlpha decided per frame.  No progress is reported.
+    bool renderSequencePlanarRgba(const PlanarRgbaImage* srcs, PlanarRgbaImage* dsts, int count, const RgbaOptions& opt = {});
+    bool renderSequencePlanarRgbaResized(const PlanarRgbaImage* srcs, PlanarRgbaImage* dsts, int count, const RgbaOptions& opt = {}, ResizeFilter filter = ResizeFilter::Bicubic);
     void* allocHost(size_t bytes);
     void freeHost(void* data);
     // Page-locks caller-owned memory in place.  Only whole pages are accepted (data and bytes multiples of 4096): a registration
@@ -174,6 +199,9 @@ public:
     bool infer(const float* input, float* output);
     // Test hook: alpha_bleed_kernel alone - the BGRA frame up, the bleed at `radius`, the BGR frame gather would read down (bgr: rows x cols, step >= cols * 3)
     bool alphaBleed(const Image& bgra, Image& bgr, int radius);
+    // Test hook: alpha_bleed_planes_kernel alone - the four planes up, the bleed at `radius`, the three colour planes gather would read down (colour: the size and
+    // depth of src).  words (two, or null): the reduced alpha range, max(key) and max(top - key) (kernels.h AlphaBleedPlanesParams).
+    bool alphaBleedPlanes(const PlanarRgbaImage& src, PlanarImage& colour, int radius, unsigned* words = nullptr);
     int outputTileSize() const;
     int scaling() const;   // RenderConfig::scaling of the loaded configuration (0 before load)
     double planFlops() const;
@@ -197,6 +225,7 @@ private:
     bool runSequenceRgba(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt, int resizeFilter, const char* who);
     bool runGray(const Image* srcs, Image* dsts, int count, int resizeFilter, const char* who, bool single);   // single: renderGray / renderGrayResized (8 or 16 bits, progress)
     bool runPlanar(const PlanarImage* srcs, PlanarImage* dsts, int count, int resizeFilter, const char* who, bool single);   // single: renderPlanar / renderPlanarResized (progress)
+    bool runPlanarRgba(const PlanarRgbaImage* srcs, PlanarRgbaImage* dsts, int count, const RgbaOptions& opt, int resizeFilter, const char* who, bool single);
     bool runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, int resizeFilter, const char* who);   // resizeFilter >= 0: renderYuvResized
     std::unique_ptr<Impl> impl;
 };

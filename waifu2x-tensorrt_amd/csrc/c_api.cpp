@@ -2,6 +2,7 @@
 #include "../../include/w2x/c_api.h"
 #include "../../include/w2x/c_api_gray.h"
 #include "../../include/w2x/c_api_planar.h"
+#include "../../include/w2x/c_api_rgbap.h"
 #include <mutex>
 
 #include <cstring>
@@ -96,6 +97,23 @@ static PlanarSequence planar_sequence(const void* const* src_planes, const size_
     for (int i = 0; i < count; ++i) {
         q.src.push_back(planar_image(src_planes + 3 * i, src_steps, rows, cols, src_bits));
         q.dst.push_back(planar_image(dst_planes + 3 * i, dst_steps, dst_rows, dst_cols, dst_bits));
+    }
+    return q;
+}
+// the planar RGBA renders (include/w2x/c_api_rgbap.h): four planes R, G, B, A; a sequence holds frame i's planes at [4i .. 4i + 3]
+static w2x::PlanarRgbaImage rgbap_image(const void* const* planes, const size_t* steps, int rows, int cols, int bits) {
+    w2x::PlanarRgbaImage f;
+    for (int k = 0; k < 4; ++k) { f.planes[k] = planes ? (uint8_t*)const_cast<void*>(planes[k]) : nullptr; f.steps[k] = steps ? steps[k] : 0; }
+    f.rows = rows; f.cols = cols; f.bits = bits;
+    return f;
+}
+struct RgbapSequence { std::vector<w2x::PlanarRgbaImage> src, dst; };
+static RgbapSequence rgbap_sequence(const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                                    void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int count) {
+    RgbapSequence q; q.src.reserve(count); q.dst.reserve(count);
+    for (int i = 0; i < count; ++i) {
+        q.src.push_back(rgbap_image(src_planes + 4 * i, src_steps, rows, cols, src_bits));
+        q.dst.push_back(rgbap_image(dst_planes + 4 * i, dst_steps, dst_rows, dst_cols, dst_bits));
     }
     return q;
 }
@@ -323,6 +341,40 @@ size_t w2x_planar_plane_bytes(int rows, int cols, int bits) {
     if (rows <= 0 || cols <= 0 || !(bits == 8 || bits == 10 || bits == 12 || bits == 16 || bits == 32)) return 0;
     return (size_t)rows * cols * (bits == 32 ? 4 : bits > 8 ? 2 : 1);
 }
+// planar RGBA frames (include/w2x/c_api_rgbap.h)
+int w2x_render_rgbap(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                     void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int bleed, int skip_uniform_alpha) {
+    if (!e) return 0;
+    w2x::PlanarRgbaImage d = rgbap_image(dst_planes, dst_steps, dst_rows, dst_cols, dst_bits);
+    return e->engine.renderPlanarRgba(rgbap_image(src_planes, src_steps, rows, cols, src_bits), d, rgba_options(bleed, skip_uniform_alpha)) ? 1 : 0;
+}
+int w2x_render_rgbap_resized(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                             void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int bleed, int skip_uniform_alpha, int filter) {
+    w2x::ResizeFilter f;
+    if (!e || !resize_filter(e, filter, "w2x_render_rgbap_resized", f)) return 0;
+    w2x::PlanarRgbaImage d = rgbap_image(dst_planes, dst_steps, dst_rows, dst_cols, dst_bits);
+    return e->engine.renderPlanarRgbaResized(rgbap_image(src_planes, src_steps, rows, cols, src_bits), d, rgba_options(bleed, skip_uniform_alpha), f) ? 1 : 0;
+}
+int w2x_render_sequence_rgbap(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                              void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int count, int bleed, int skip_uniform_alpha) {
+    if (!sequence_ok(e, count, src_planes, dst_planes)) return 0;
+    RgbapSequence q = rgbap_sequence(src_planes, src_steps, rows, cols, src_bits, dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, count);
+    return e->engine.renderSequencePlanarRgba(q.src.data(), q.dst.data(), count, rgba_options(bleed, skip_uniform_alpha)) ? 1 : 0;
+}
+int w2x_render_sequence_rgbap_resized(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                                      void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int count, int bleed,
+                                      int skip_uniform_alpha, int filter) {
+    w2x::ResizeFilter f;
+    if (!sequence_ok(e, count, src_planes, dst_planes) || !resize_filter(e, filter, "w2x_render_sequence_rgbap_resized", f)) return 0;
+    RgbapSequence q = rgbap_sequence(src_planes, src_steps, rows, cols, src_bits, dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, count);
+    return e->engine.renderSequencePlanarRgbaResized(q.src.data(), q.dst.data(), count, rgba_options(bleed, skip_uniform_alpha), f) ? 1 : 0;
+}
+int w2x_alpha_bleed_rgbap_device(w2x_engine* e, const void* const* planes, const size_t* steps, int rows, int cols, int bits, int radius,
+                                 void* const* out_planes, const size_t* out_steps, unsigned* words) {
+    if (!e) return 0;
+    w2x::PlanarImage d = planar_image(out_planes, out_steps, rows, cols, bits);
+    return e->engine.alphaBleedPlanes(rgbap_image(planes, steps, rows, cols, bits), d, radius, words) ? 1 : 0;
+}
 int w2x_alpha_bleed_device(w2x_engine* e, const uint8_t* bgra, int rows, int cols, size_t bgra_step, uint8_t* bgr, size_t bgr_step, int radius) {
     if (!e) return 0;
     w2x::Image d = image(bgr, rows, cols, bgr_step);
@@ -394,6 +446,11 @@ int w2x_yuv_layout_plane_sizes(int rows, int cols, int bits, int layout, int* np
 
 int w2x_alpha_bleed(const uint8_t* bgr, size_t bgr_step, const uint8_t* alpha, size_t alpha_step, int rows, int cols, int radius, uint8_t* out, size_t out_step) {
     try { return w2x::alpha_bleed(bgr, bgr_step, alpha, alpha_step, rows, cols, radius, out, out_step) ? 1 : 0; } catch (...) { return 0; }
+}
+
+int w2x_alpha_bleed_rgbap(const void* const* planes, const size_t* steps, int rows, int cols, int bits, int radius, void* const* out_planes, const size_t* out_steps) {
+    if (!planes || !steps || !out_planes || !out_steps || !(bits == 8 || bits == 10 || bits == 12 || bits == 16)) return 0;
+    try { return w2x::alpha_bleed_planes(planes, steps, planes[3], steps[3], rows, cols, bits > 8 ? 2 : 1, (1u << bits) - 1u, radius, out_planes, out_steps) ? 1 : 0; } catch (...) { return 0; }
 }
 
 int w2x_resize_weights(int in, int out, int filter, int* first, float* weights, int cap) {

@@ -87,6 +87,12 @@ std::string usage() {
            "                              formats, 8 to 16 bits or float in, any of them out (one given: the other side is gbrp); --outscale / --outsize apply.\n"
            "                              With --rgb-out and no --pix_fmt the encoder's format is the --rgb-out one.  Stills, single frames read through ffmpeg and\n"
            "                              the built-in AVI route are rendered as without them.  Not with --colorspace, not with --gray\n"
+           "      --rgba-in FMT, --rgba-out FMT\n"
+           "                              (extension) {gbrap,gbrap10le,gbrap12le,gbrap16le,gbrapf32le}: videos with an alpha channel read through ffmpeg travel as raw\n"
+           "                              planar RGBA frames of these formats (one given: the other side is gbrap), colour and alpha rendered in one call per frame;\n"
+           "                              --alpha-bleed (not on gbrapf32le input) and --alpha-skip-uniform apply to them, as do --outscale / --outsize and --devices.\n"
+           "                              With --rgba-out and no --pix_fmt the encoder's format is the --rgba-out one.  Stills, single frames read through ffmpeg\n"
+           "                              and the built-in AVI route are rendered as without them.  Not with --colorspace, --gray, --rgb-in or --rgb-out\n"
            "      --tta-mode TEXT [mean]  (extension) {mean,reference}: with --tta, `mean` averages the 8 augmentations; `reference`\n"
            "                              reproduces the bytes of the reference's accumulation (img2img_render.cpp:313-316); --tta-compat = reference\n"
            "  build                       Build model\n"
@@ -99,6 +105,13 @@ const char* const kRgbFormats[5] = {"gbrp", "gbrp10le", "gbrp12le", "gbrp16le", 
 int rgb_format_bits(const std::string& name) {
     const int bits[5] = {8, 10, 12, 16, 32};
     for (int k = 0; k < 5; ++k) if (name == kRgbFormats[k]) return bits[k];
+    return 0;
+}
+
+const char* const kRgbaFormats[5] = {"gbrap", "gbrap10le", "gbrap12le", "gbrap16le", "gbrapf32le"};
+int rgba_format_bits(const std::string& name) {
+    const int bits[5] = {8, 10, 12, 16, 32};
+    for (int k = 0; k < 5; ++k) if (name == kRgbaFormats[k]) return bits[k];
     return 0;
 }
 
@@ -166,6 +179,8 @@ Options parse(int argc, const char* const* argv) {
         else if (k == "--yuv-out") o.yuvOut = value(i);
         else if (k == "--rgb-in") o.rgbIn = value(i);
         else if (k == "--rgb-out") o.rgbOut = value(i);
+        else if (k == "--rgba-in") o.rgbaIn = value(i);
+        else if (k == "--rgba-out") o.rgbaOut = value(i);
         else throw std::runtime_error("The following argument was not expected: " + a[i]);
     }
     if (o.command.empty()) throw std::runtime_error("A subcommand is required");
@@ -189,6 +204,7 @@ Options parse(int argc, const char* const* argv) {
     member<std::string>("--precision", o.precision, {"fp16", "tf32", "fp32"});   // fp32: an addition (include/w2x/config.h)
     const bool seen_yuv_in = !o.yuvIn.empty(), seen_yuv_out = !o.yuvOut.empty();
     const bool seen_rgb_in = !o.rgbIn.empty(), seen_rgb_out = !o.rgbOut.empty();
+    const bool seen_rgba_in = !o.rgbaIn.empty(), seen_rgba_out = !o.rgbaOut.empty();
     if (o.command == "render") {
         if (o.inputs.empty()) throw std::runtime_error("--input is required");
         for (const auto& p : o.inputs) if (!std::filesystem::exists(p)) throw std::runtime_error("--input: Path does not exist: " + p);
@@ -240,12 +256,23 @@ Options parse(int argc, const char* const* argv) {
             if (seen_gray) throw std::runtime_error(std::string(opt) + ": not together with --gray (one raw frame format per run)");
         }
         if (seen_rgb_out && !seen_pixfmt) o.pixFmt = o.rgbOut;   // --pix_fmt is the encoder's format only
+        for (const char* opt : {"--rgba-in", "--rgba-out"}) {
+            const std::string& v = opt[7] == 'i' ? o.rgbaIn : o.rgbaOut;
+            if (v.empty()) continue;
+            member<std::string>(opt, v, {kRgbaFormats[0], kRgbaFormats[1], kRgbaFormats[2], kRgbaFormats[3], kRgbaFormats[4]});
+            if (seen_colorspace) throw std::runtime_error(std::string(opt) + ": not together with --colorspace (planar RGBA frames are not converted to YUV)");
+            if (seen_gray) throw std::runtime_error(std::string(opt) + ": not together with --gray (one raw frame format per run)");
+            if (seen_rgb_in || seen_rgb_out) throw std::runtime_error(std::string(opt) + ": not together with " + (seen_rgb_in ? "--rgb-in" : "--rgb-out") + " (one raw frame format per run)");
+        }
+        if (seen_rgba_out && !seen_pixfmt) o.pixFmt = o.rgbaOut;
         if (seen_bleed) {
             if (!(o.alphaBleed >= 0 && o.alphaBleed <= 16)) throw std::runtime_error("--alpha-bleed: " + std::to_string(o.alphaBleed) + " not in [0, 16] (the radius in pixels)");
+            if (o.alphaBleed > 0 && o.rgbaIn == kRgbaFormats[4]) throw std::runtime_error("--alpha-bleed: not together with --rgba-in " + o.rgbaIn + " (the bleed takes integer samples)");
             if (o.alphaBleed > 0 && o.deep) throw std::runtime_error("--alpha-bleed: not together with --deep (the bleed works on 8-bit colour; 16-bit stills keep the colours as stored)");
         }
     } else if (seen_gray) throw std::runtime_error("--gray: only with render");
     else if (seen_rgb_in || seen_rgb_out) throw std::runtime_error(std::string(seen_rgb_in ? "--rgb-in" : "--rgb-out") + ": only with render");
+    else if (seen_rgba_in || seen_rgba_out) throw std::runtime_error(std::string(seen_rgba_in ? "--rgba-in" : "--rgba-out") + ": only with render");
     else if (seen_outscale || seen_outsize || seen_filter || seen_colorspace || seen_range || seen_bleed || seen_skip || seen_yuv_in || seen_yuv_out)
         throw std::runtime_error(std::string(seen_yuv_in ? "--yuv-in" : seen_yuv_out ? "--yuv-out" : seen_outscale ? "--outscale" : seen_outsize ? "--outsize" : seen_filter ? "--resize-filter" : seen_colorspace ? "--colorspace" :
                                              seen_range ? "--color_range" : seen_bleed ? "--alpha-bleed" : "--alpha-skip-uniform") + ": only with render");
@@ -301,6 +328,7 @@ std::string to_json(const Options& o) {
        << ", \"yuv_in\": " << (o.yuvIn.empty() ? std::string("null") : q(o.yuvIn)) << ", \"yuv_out\": " << (o.yuvOut.empty() ? std::string("null") : q(o.yuvOut))
        << ", \"alpha_bleed\": " << o.alphaBleed << ", \"alpha_skip_uniform\": " << (o.alphaSkipUniform ? "true" : "false") << ", \"gray\": " << (o.gray ? "true" : "false")
        << ", \"rgb_in\": " << (o.rgbIn.empty() ? std::string("null") : q(o.rgbIn)) << ", \"rgb_out\": " << (o.rgbOut.empty() ? std::string("null") : q(o.rgbOut))
+       << ", \"rgba_in\": " << (o.rgbaIn.empty() ? std::string("null") : q(o.rgbaIn)) << ", \"rgba_out\": " << (o.rgbaOut.empty() ? std::string("null") : q(o.rgbaOut))
        << ", \"codec\": " << q(o.codec) << ", \"pix_fmt\": " << q(o.pixFmt) << ", \"crf\": " << o.crf << ", \"inputs\": [";
     for (size_t i = 0; i < o.inputs.size(); ++i) os << (i ? ", " : "") << q(o.inputs[i]);
     os << "], \"model_path\": " << q(o.command == "convert" ? "" : model_path(o)) << ", \"suffix\": " << q(o.command == "convert" ? "" : output_suffix(o)) << ", \"outputs\": [";

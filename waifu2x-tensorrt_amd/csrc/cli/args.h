@@ -50,6 +50,8 @@ struct Options {
     bool gray = false;                    // --gray (extension, render only): gray PNGs and ffmpeg videos stay one channel (Img2Img::renderGray*)
     std::string rgbIn, rgbOut;            // --rgb-in / --rgb-out FMT (extension, render only; kRgbFormats): videos read through ffmpeg travel as raw planar RGB frames
                                           // of these formats (Img2Img::renderSequencePlanar*); with --rgb-out and no --pix_fmt the encoder's format is the --rgb-out one
+    std::string rgbaIn, rgbaOut;          // --rgba-in / --rgba-out FMT (extension, render only; kRgbaFormats): videos read through ffmpeg travel as raw planar RGBA frames
+                                          // of these formats (Img2Img::renderSequencePlanarRgba*, with --alpha-bleed / --alpha-skip-uniform); the encoder's format as with --rgb-out
     bool printConfig = false;             // --print-config: dump the parsed options and derived names as JSON and exit (tests)
     bool help = false;
 };
@@ -59,6 +61,9 @@ extern const char* const kYuvFormats[8];
 // the raw formats of --rgb-in / --rgb-out (ffmpeg's planar RGB: planes G, B, R) and the bits of a sample of each (32: float); 0 for another name
 extern const char* const kRgbFormats[5];
 int rgb_format_bits(const std::string& name);
+// the raw formats of --rgba-in / --rgba-out (ffmpeg's planar RGB with alpha: planes G, B, R, A) and the bits of a sample of each (32: float); 0 for another name
+extern const char* const kRgbaFormats[5];
+int rgba_format_bits(const std::string& name);
 // throws std::runtime_error with the message to print (exit code -1 like main.cpp:147-150) on invalid input
 Options parse(int argc, const char* const* argv);
 std::string usage();

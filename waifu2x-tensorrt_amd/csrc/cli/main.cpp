@@ -10,7 +10,8 @@
 // through renderSequenceGray[Resized] for videos; colour files, single frames read through ffmpeg, gray + alpha PNGs and the built-in AVI route are rendered
 // as without it.
 // Extension: --rgb-in / --rgb-out FMT carry ffmpeg videos as raw planar RGB frames (gbrp, gbrp10le, gbrp12le, gbrp16le, gbrpf32le: planes G, B, R, contiguous)
-// through Img2Img::renderSequencePlanar[Resized], the two depths independent; stills, single frames read through ffmpeg and the built-in AVI route are
+// through Img2Img::renderSequencePlanar[Resized], the two depths independent (--rgba-in / --rgba-out: gbrap*, a fourth plane A, through
+// Img2Img::renderSequencePlanarRgba[Resized] with --alpha-bleed / --alpha-skip-uniform); stills, single frames read through ffmpeg and the built-in AVI route are
 // rendered as without them.  Over --devices N the chunks go to the engines like bgr24 chunks.
 // Extension: --devices N drives N engines - a single image is split into tile-column strips (Img2Img::renderStrip), every engine
 // writing its own columns of the shared output buffer; a video is cut into chunks of frames that go round-robin to one persistent
@@ -359,8 +360,11 @@ int main(int argc, char** argv) {
                 bool yuv = false;                                      // --colorspace on a multi-frame input read through ffmpeg: YUV frames
                 bool gray = false;                                     // --gray on an input read through ffmpeg: raw gray frames, one byte per pixel
                 bool planar = false;                                   // --rgb-in / --rgb-out on a multi-frame input read through ffmpeg: raw planar RGB frames
-                const std::string rgbIn = o.rgbIn.empty() ? "gbrp" : o.rgbIn, rgbOut = o.rgbOut.empty() ? "gbrp" : o.rgbOut;   // (one given: the other side is gbrp)
-                const int rgbInBits = cli::rgb_format_bits(rgbIn), rgbOutBits = cli::rgb_format_bits(rgbOut);
+                const bool alphaFrames = !o.rgbaIn.empty() || !o.rgbaOut.empty();   // --rgba-in / --rgba-out: the same with a fourth plane, A (gbrap*; one given: the other side is gbrap)
+                const std::string rgbIn = alphaFrames ? (o.rgbaIn.empty() ? "gbrap" : o.rgbaIn) : o.rgbIn.empty() ? "gbrp" : o.rgbIn;
+                const std::string rgbOut = alphaFrames ? (o.rgbaOut.empty() ? "gbrap" : o.rgbaOut) : o.rgbOut.empty() ? "gbrp" : o.rgbOut;
+                const int rgbInBits = alphaFrames ? cli::rgba_format_bits(rgbIn) : cli::rgb_format_bits(rgbIn), rgbOutBits = alphaFrames ? cli::rgba_format_bits(rgbOut) : cli::rgb_format_bits(rgbOut);
+                const int rgbPlanes = alphaFrames ? 4 : 3;
                 auto plane_bytes = [](int rows, int cols, int bits) { return (size_t)rows * cols * (bits == 32 ? 4 : bits > 8 ? 2 : 1); };
                 const std::string& rawIn = o.yuvIn.empty() ? o.pixFmt : o.yuvIn, & rawOut = o.yuvOut.empty() ? o.pixFmt : o.yuvOut;   // --yuv-in / --yuv-out
                 const RawYuv fmtIn = raw_yuv(rawIn), fmtOut = raw_yuv(rawOut);
@@ -369,6 +373,7 @@ int main(int argc, char** argv) {
                     source = std::move(avi);
                     if (o.gray) on_message(Severity::warn, file + ": the built-in AVI route is 24-bit only: --gray is ignored");
                     if (!o.rgbIn.empty() || !o.rgbOut.empty()) on_message(Severity::warn, file + ": the built-in AVI route is 24-bit only: --rgb-in / --rgb-out are ignored");
+                    if (alphaFrames) on_message(Severity::warn, file + ": the built-in AVI route is 24-bit only: --rgba-in / --rgba-out are ignored");
                 } else {
                     if (!have_ffmpeg) throw std::runtime_error(file + ": needs ffmpeg and ffprobe on PATH (built in: .png, .ppm, .bmp, uncompressed 24-bit .avi" + (why.empty() ? "" : "; " + why) +
                                                                (o.colorspace.empty() ? "" : "; --colorspace reads and writes YUV frames through ffmpeg only") + ")");
@@ -376,8 +381,8 @@ int main(int argc, char** argv) {
                     width = pr.width; height = pr.height; frames = pr.frames; fps = pr.fps;
                     yuv = !o.colorspace.empty() && frames != 1;
                     gray = o.gray && frames != 1;                      // (a single frame is a still in a format only ffmpeg reads: rendered in colour, as without the flag)
-                    planar = (!o.rgbIn.empty() || !o.rgbOut.empty()) && frames != 1;   // (a single frame: a still, rendered as bgr24 like any other)
-                    const size_t inBytes = yuv ? yuv_frame_bytes(height, width, fmtIn) : planar ? 3 * plane_bytes(height, width, rgbInBits) : (size_t)width * height * (gray ? 1 : 3);
+                    planar = (!o.rgbIn.empty() || !o.rgbOut.empty() || alphaFrames) && frames != 1;   // (a single frame: a still, rendered as bgr24 like any other)
+                    const size_t inBytes = yuv ? yuv_frame_bytes(height, width, fmtIn) : planar ? rgbPlanes * plane_bytes(height, width, rgbInBits) : (size_t)width * height * (gray ? 1 : 3);
                     source.reset(new PipeSource("ffmpeg -v error -i " + shell_quote(file) + " -f rawvideo -pix_fmt " + (yuv ? rawIn : planar ? rgbIn : std::string(gray ? "gray" : "bgr24")) + " -", inBytes));
                 }
                 frameIndex = 0; frameCount = frames;
@@ -385,8 +390,8 @@ int main(int argc, char** argv) {
                 std::string outFile = cli::output_path(o, file, single);
                 check_outsize(file, width, height);
                 const int outW = cli::out_dim(o, width, true), outH = cli::out_dim(o, height, false);
-                const size_t inBytes = yuv ? yuv_frame_bytes(height, width, fmtIn) : planar ? 3 * plane_bytes(height, width, rgbInBits) : (size_t)width * height * (gray ? 1 : 3);
-                const size_t outBytes = yuv ? yuv_frame_bytes(outH, outW, fmtOut) : planar ? 3 * plane_bytes(outH, outW, rgbOutBits) : (size_t)outW * outH * (gray ? 1 : 3);
+                const size_t inBytes = yuv ? yuv_frame_bytes(height, width, fmtIn) : planar ? rgbPlanes * plane_bytes(height, width, rgbInBits) : (size_t)width * height * (gray ? 1 : 3);
+                const size_t outBytes = yuv ? yuv_frame_bytes(outH, outW, fmtOut) : planar ? rgbPlanes * plane_bytes(outH, outW, rgbOutBits) : (size_t)outW * outH * (gray ? 1 : 3);
                 if (have_ffmpeg) {
                     std::string wcmd = "ffmpeg -v error -y -f rawvideo -pix_fmt " + (yuv ? rawOut : planar ? rgbOut : std::string(gray ? "gray" : "bgr24")) + " -s " + std::to_string(outW) + "x" + std::to_string(outH) +
                                        " -r " + std::to_string(single ? 1.0 : fps) + " -i - ";
@@ -423,6 +428,21 @@ int main(int argc, char** argv) {
                     };
                     for (int k = 0; k < n; ++k) { si[k] = frame(in[k], height, width, rgbInBits); di[k] = frame(out[k], outH, outW, rgbOutBits); }
                     return resize ? e.renderSequencePlanarResized(si.data(), di.data(), n, filter) : e.renderSequencePlanar(si.data(), di.data(), n);
+                };
+                // a raw gbrap* frame: G, B, R, A; PlanarRgbaImage wants R, G, B, A
+                if (planar && alphaFrames) render = [&](Img2Img& e, uint8_t* const* in, uint8_t* const* out, int n) {
+                    std::vector<PlanarRgbaImage> si(n), di(n);
+                    auto frame = [&](uint8_t* base, int rows, int cols, int bits) {
+                        const size_t plane = plane_bytes(rows, cols, bits), step = plane / rows;
+                        PlanarRgbaImage f;
+                        f.rows = rows; f.cols = cols; f.bits = bits;
+                        f.planes[0] = base + 2 * plane; f.planes[1] = base; f.planes[2] = base + plane; f.planes[3] = base + 3 * plane;
+                        f.steps[0] = f.steps[1] = f.steps[2] = f.steps[3] = step;
+                        return f;
+                    };
+                    for (int k = 0; k < n; ++k) { si[k] = frame(in[k], height, width, rgbInBits); di[k] = frame(out[k], outH, outW, rgbOutBits); }
+                    RgbaOptions ro; ro.bleed = o.alphaBleed; ro.skipUniformAlpha = o.alphaSkipUniform;
+                    return resize ? e.renderSequencePlanarRgbaResized(si.data(), di.data(), n, ro, filter) : e.renderSequencePlanarRgba(si.data(), di.data(), n, ro);
                 };
                 if (yuv) {
                     YuvFormat f;

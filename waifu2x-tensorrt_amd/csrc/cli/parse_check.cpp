@@ -10,9 +10,12 @@
 //   w2x_parse_check args  ARGS...                   cli::parse
 //   w2x_parse_check tiles W H T S TOUT OVX OVY      calculate_tiles
 //   w2x_parse_check bleed FILE RADIUS               read_image, then alpha_bleed of its colour under its alpha plane (an opaque plane without one), padded rows
+//   w2x_parse_check planes BITS ROWS COLS RADIUS SEED OUT   alpha_bleed_planes on a seeded frame of four planes of BITS (8, 10, 12, 16), padded rows; OUT receives
+//                                                           the four planes and the three bled ones, packed, for the test to compare with its own statement
 // Exit code: 0 = accepted, 2 = rejected with a message on stderr (the clean `false` of the product path); anything else is a crash
 // or a sanitizer report.
 #include <algorithm>
+#include <cstdint>
 #include <cstdio>
 #include <cstdlib>
 #include <fstream>
@@ -29,7 +32,7 @@
 using namespace w2x;
 
 static int run(int argc, char** argv) {
-    if (argc < 3) throw std::runtime_error("usage: w2x_parse_check {onnx|plan|image|avi|args|tiles|bleed} ...");
+    if (argc < 3) throw std::runtime_error("usage: w2x_parse_check {onnx|plan|image|avi|args|tiles|bleed|planes} ...");
     const std::string mode = argv[1];
     if (mode == "onnx") {
         if (argc < 5) throw std::runtime_error("onnx FILE BATCH TILE [fp32]");
@@ -87,6 +90,49 @@ static int run(int argc, char** argv) {
             for (size_t x = (size_t)b.cols * 3; x < cs; ++x) if (out[y * cs + x] != 0xEE) throw std::runtime_error("alpha_bleed wrote into the row padding");
         }
         printf("ok: %d x %d at radius %d, %zu bytes changed\n", b.cols, b.rows, radius, changed);
+    } else if (mode == "planes") {
+        if (argc < 8) throw std::runtime_error("planes BITS ROWS COLS RADIUS SEED OUT");
+        const int bits = atoi(argv[2]), rows = atoi(argv[3]), cols = atoi(argv[4]), radius = atoi(argv[5]);
+        if (!(bits == 8 || bits == 10 || bits == 12 || bits == 16) || rows <= 0 || cols <= 0 || rows > 4096 || cols > 4096) throw std::runtime_error("planes: BITS in {8,10,12,16}, a frame of at most 4096 x 4096");
+        const int bps = bits > 8 ? 2 : 1;
+        const unsigned maxcode = (1u << bits) - 1u;
+        // exact-size heap blocks, every plane with a padded step of its own: a read or write past a row or a plane is a sanitizer report.  The samples: a
+        // 64-bit LCG; about half the alpha plane zero; at 10 and 12 bits some codes above the depth
+        uint64_t state = (uint64_t)atoll(argv[6]) * 2862933555777941757ull + 3037000493ull;
+        auto next = [&] { state = state * 6364136223846793005ull + 1442695040888963407ull; return (unsigned)(state >> 33); };
+        std::vector<std::vector<uint8_t>> in(4), out(3);
+        size_t steps[4], osteps[3];
+        auto put = [&](std::vector<uint8_t>& v, size_t step, int y, int x, unsigned code) { if (bps == 1) v[y * step + x] = (uint8_t)code; else { v[y * step + 2 * x] = (uint8_t)code; v[y * step + 2 * x + 1] = (uint8_t)(code >> 8); } };
+        auto get = [&](const std::vector<uint8_t>& v, size_t step, int y, int x) { return bps == 1 ? (unsigned)v[y * step + x] : (unsigned)v[y * step + 2 * x] | (unsigned)v[y * step + 2 * x + 1] << 8; };
+        for (int k = 0; k < 4; ++k) {
+            steps[k] = (size_t)(cols + k + 1) * bps;
+            in[k].assign(steps[k] * rows, 0xEE);
+            for (int y = 0; y < rows; ++y)
+                for (int x = 0; x < cols; ++x) {
+                    unsigned code = next() % ((bps == 1 ? 256u : bits == 16 ? 65536u : maxcode + 1u + maxcode / 8u));
+                    if (k == 3 && (next() & 1u)) code = 0;
+                    put(in[k], steps[k], y, x, code);
+                }
+        }
+        for (int k = 0; k < 3; ++k) { osteps[k] = (size_t)(cols + 2 * k + 2) * bps; out[k].assign(osteps[k] * rows, 0xEE); }
+        const void* cp[3] = {in[0].data(), in[1].data(), in[2].data()};
+        void* op[3] = {out[0].data(), out[1].data(), out[2].data()};
+        if (!alpha_bleed_planes(cp, steps, in[3].data(), steps[3], rows, cols, bps, maxcode, radius, op, osteps)) throw std::runtime_error("alpha_bleed_planes refused the frame");
+        for (int k = 0; k < 3; ++k)
+            for (int y = 0; y < rows; ++y)
+                for (size_t x = (size_t)cols * bps; x < osteps[k]; ++x) if (out[k][y * osteps[k] + x] != 0xEE) throw std::runtime_error("alpha_bleed_planes wrote into the row padding");
+        std::ofstream f(argv[7], std::ios::binary);
+        if (!f.is_open()) throw std::runtime_error("could not open the output file");
+        size_t changed = 0;
+        for (int k = 0; k < 7; ++k)
+            for (int y = 0; y < rows; ++y)
+                for (int x = 0; x < cols; ++x) {
+                    const unsigned code = k < 4 ? get(in[k], steps[k], y, x) : get(out[k - 4], osteps[k - 4], y, x);
+                    if (k >= 4) changed += code != std::min(get(in[k - 4], steps[k - 4], y, x), maxcode);
+                    const char b[2] = {(char)code, (char)(code >> 8)};
+                    f.write(b, bps);
+                }
+        printf("ok: %d x %d of %d bits at radius %d, %zu samples changed\n", cols, rows, bits, radius, changed);
     } else throw std::runtime_error("unknown mode " + mode);
     return 0;
 }

@@ -349,13 +349,17 @@ struct Img2Img::Impl {
     // of in_bits / out_bits samples (8; 10, 12, 16 as uint16; 32 as float) with rows padded to 16 bytes (planar_layout).  The gather launch is gather_planes_kernel,
     // the frame ends with compose_planes_kernel - resized with compose_canvas_kernel (the BGR path's own canvas) and resample_planes_kernel.
     struct PlanarJob { int in_bits = 8, out_bits = 8; };
+    // Planar RGBA frames (renderPlanarRgba, renderPlanarRgbaResized, renderSequencePlanarRgba*): an RGBA frame on planar samples.  Its options are the
+    // two jobs above - job.planar the depths, job.rgba bleed, skip, alpha_slot0, uniform and value (the key of the uniform plane: its clamped code, float: the bits of
+    // its clamped value) - and its frame step is rgba_frame().  d_frame / d_out hold four planes R, G, B, A (planar_layout); alpha_bleed_planes_kernel writes the three
+    // colour planes into d_bgr and the alpha plane into d_alpha (planes of in_bits samples, rows padded as in planar_layout), which gather_planes_rgba_kernel reads.
     // The kind of frame the running entry point renders.  Only the block "the frame formats" below branches on it: the key of the captured passes, the
     // gather (gather_tiles), the end of a frame (finish_frame), the device layout of a frame, the slot tables of a call.  The default is a plain BGR frame, not
-    // resized.  The kind is set in three places - runSequenceYuv, the RGBA calls (rgba_call), runGray, runPlanar - between the call's checks and run_call();
+    // resized.  The kind is set in three places - runSequenceYuv, the RGBA calls (rgba_call), runGray, runPlanar, runPlanarRgba - between the call's checks and run_call();
     // entry() puts the default back on every exit, exceptions included.  `rs`: the tap tables of a resized frame's target (job_resize), else null.
     // (`deep` is not part of it: it describes the replayable frame in d_frame / d_out and outlives the call.)
     struct Job {
-        enum Kind { BGR, YUV, RGBA, GRAY, PLANAR } kind = BGR;
+        enum Kind { BGR, YUV, RGBA, GRAY, PLANAR, PLANAR_RGBA } kind = BGR;
         const ResizeTables* rs = nullptr;
         YuvJob yuv;
         RgbaJob rgba;
@@ -442,6 +446,7 @@ struct Img2Img::Impl {
     static constexpr int kRgbaKey = 64;   // (YuvJob::key stays below 50)
     static constexpr int kGrayKey = 65;   // 65 / 66: gray frames of 8 / 16 bits
     static constexpr int kPlanarKey = 67; // 67 .. 71: planar frames whose input samples have 8 / 10 / 12 / 16 / 32 bits
+    static constexpr int kPlanarRgbaKey = 72; // 72 .. 76: planar RGBA frames, by input depth likewise
     using GraphKey = std::tuple<const void*, const void*, const void*, const void*, int, int, int, int>;   // frame, slots, slab out, arena, rows, cols, live, sample format (1: 16-bit, >= 2: YuvJob::key)
     // A pass that runs as NG tile groups is NG graphs, one per group, each a straight line of launches replayed on that group's OWN stream (fork / join
     // events between the streams are issued around the replays): a single captured graph with NG branches runs its side branches on streams the runtime
@@ -993,7 +998,7 @@ struct Img2Img::Impl {
     // device part of one frame: gather -> network per batch -> the format's end of a frame (finish_frame).  Frame must already be in d_frame.
     // `started` (a single-frame call's ev0): recorded in front of the passes - of an RGBA frame behind its bleed, whose two-phase schedule is rgba_frame()
     void run_frame(int rows, int cols, const TileGrid& grid, bool report, const StripPlan& sp, hipEvent_t started = nullptr) {
-        if (job.kind == Job::RGBA) { rgba_frame(rows, cols, grid, sp, report, started); return; }
+        if (two_tile_sets()) { rgba_frame(rows, cols, grid, sp, report, started); return; }
         if (started) hipAssert(hipEventRecord(started, stream));
         run_passes(rows, cols, sp.tile_count, 0, report, 0, true);
         finish_frame(rows, cols, grid, sp, stream, nullptr, nullptr);
@@ -1235,49 +1240,84 @@ struct Img2Img::Impl {
     }
 
     // ---- The frame formats: what a Job::Kind does at each device step, each step written once with one switch over job.kind.  Outside this block
-    // only the three places that set a job's kind and run_frame()'s hand-off of an RGBA frame name a kind.  A new format is a case in each function here, a
+    // only the places that set a job's kind name one (run_frame() hands a frame of two tile sets to rgba_frame() through two_tile_sets()).  A new format is a case in each function here, a
     // checker and an entry point that sets its job ("Adding a frame format").
     //
     // The key of a captured pass: the sample format - 0 / 1 BGR of 8 / 16 bits, 2 .. 49 YuvJob::key, kRgbaKey, kGrayKey / kGrayKey + 1 gray of 8 / 16 bits, kPlanarKey .. + 4 planar by
-    // input depth - and the buffer the pass's gather reads (an RGBA pass reads d_bgr / d_alpha, never d_frame: its graphs do not depend on which frame buffer of a sequence is current)
+    // input depth, kPlanarRgbaKey .. + 4 planar RGBA likewise - and the buffer the pass's gather reads (an RGBA or planar RGBA pass reads d_bgr / d_alpha, never d_frame: its graphs do not depend on which frame buffer of a sequence is current)
     int sample_format() const {
         switch (job.kind) {
             case Job::YUV: return job.yuv.key;
             case Job::RGBA: return kRgbaKey;
             case Job::GRAY: return kGrayKey + (job.gray.deep ? 1 : 0);
             case Job::PLANAR: return planar_key(job.planar.in_bits);
+            case Job::PLANAR_RGBA: return planar_key(job.planar.in_bits) - kPlanarKey + kPlanarRgbaKey;
             default: return deep ? 1 : 0;
         }
     }
     // gray and planar frames: the sample depth of the frame (`out`: of the output) and its planes in d_frame / d_out
     int plane_bits(bool out) const { return job.kind == Job::GRAY ? (job.gray.deep ? 16 : 8) : out ? job.planar.out_bits : job.planar.in_bits; }
     PlanarPlanes frame_planes(uint8_t* base, int rows, int cols, bool out) const { return planar_layout(base, rows, cols, plane_bits(out), job.kind == Job::GRAY ? 1 : 3); }
-    const void* pass_source() const { return job.kind == Job::RGBA ? (const void*)d_bgr : (const void*)d_frame; }
+    const void* pass_source() const { return two_tile_sets() ? (const void*)d_bgr : (const void*)d_frame; }
+    // RGBA and planar RGBA frames: colour tiles and alpha tiles in one schedule (rgba_setup, rgba_frame), gathered from d_bgr / d_alpha
+    bool two_tile_sets() const { return job.kind == Job::RGBA || job.kind == Job::PLANAR_RGBA; }
+    RgbaPlanes rgba_planes(uint8_t* base, int rows, int cols, bool out) const {
+        const int bits = plane_bits(out);
+        RgbaPlanes f;
+        f.rows = rows; f.cols = cols; f.bits = bits;
+        for (int k = 0; k < 4; ++k) { f.step[k] = planar_step(cols, bits); f.p[k] = base + (size_t)k * f.step[k] * rows; }
+        return f;
+    }
+    // What the bleed of such a frame works with: the bytes of one of the four planes it writes (RGBA: a byte per pixel, three of them per BGR pixel), the top of
+    // the alpha key range its two words are reduced over, and its launch - from d_frame into d_bgr / d_alpha / d_minmax on `stream`
+    size_t bleed_plane_bytes(int rows, int cols) const { return job.kind == Job::PLANAR_RGBA ? planar_step(cols, job.planar.in_bits) * rows : (size_t)rows * cols; }
+    unsigned alpha_top() const { return job.kind == Job::PLANAR_RGBA ? alpha_key_top(job.planar.in_bits) : 255u; }
+    void launch_bleed(int rows, int cols, int radius) {
+        if (job.kind == Job::PLANAR_RGBA) {
+            AlphaBleedPlanesParams bp;
+            bp.src = rgba_planes(d_frame, rows, cols, false); bp.radius = radius;
+            bp.colour_step = bp.alpha_step = planar_step(cols, job.planar.in_bits);
+            for (int k = 0; k < 3; ++k) bp.colour[k] = d_bgr + (size_t)k * bp.colour_step * rows;
+            bp.alpha = d_alpha; bp.minmax = d_minmax;
+            hipAssert(launch_alpha_bleed_planes(bp, stream));
+            return;
+        }
+        AlphaBleedParams bp;
+        bp.bgra = d_frame; bp.step = (size_t)cols * 4; bp.rows = rows; bp.cols = cols; bp.radius = radius;
+        bp.bgr = d_bgr; bp.bgr_step = (size_t)cols * 3; bp.alpha = d_alpha; bp.alpha_step = (size_t)cols; bp.minmax = d_minmax;
+        hipAssert(launch_alpha_bleed(bp, stream));
+    }
+    // the value of a uniform alpha plane as the gather would read it, from its key (job.rgba.value)
+    float uniform_alpha() const {
+        const int bits = job.planar.in_bits;
+        if (bits == 32) { float v; memcpy(&v, &job.rgba.value, sizeof v); return v; }
+        return (float)job.rgba.value * (float)(1.0 / (double)((1 << bits) - 1));
+    }
     // The device layout of a frame: bytes per row and bytes of a rows x cols frame in d_frame, or (`out`) in d_out.  A YUV frame has a step per plane
     // (yuv_layout); frame_step() gives its Y plane's.
     size_t frame_step(int cols, bool out) const {
         switch (job.kind) {
             case Job::YUV: return yuv_layout(nullptr, 0, cols, out ? job.yuv.out_bits : job.yuv.in_bits, out ? job.yuv.out_layout : job.yuv.in_layout).step[0];
             case Job::RGBA: return (size_t)cols * 4;
-            case Job::GRAY: case Job::PLANAR: return planar_step(cols, plane_bits(out));
+            case Job::GRAY: case Job::PLANAR: case Job::PLANAR_RGBA: return planar_step(cols, plane_bits(out));
             default: return bgr_step(cols, deep);
         }
     }
     size_t frame_bytes(int rows, int cols, bool out) const {
         if (job.kind == Job::YUV) return yuv_bytes(rows, cols, out ? job.yuv.out_bits : job.yuv.in_bits, out ? job.yuv.out_layout : job.yuv.in_layout);
-        return frame_step(cols, out) * rows * (job.kind == Job::PLANAR ? 3 : 1);
+        return frame_step(cols, out) * rows * (job.kind == Job::PLANAR ? 3 : job.kind == Job::PLANAR_RGBA ? 4 : 1);
     }
     // the fp32 planes of a resized frame's canvas
-    int canvas_planes() const { return job.kind == Job::RGBA ? 4 : job.kind == Job::GRAY ? 1 : 3; }
-    // RGBA frames do not roll: d_bgr, d_alpha and d_minmax are single buffers the bleed writes on the compute stream, and in a rolling sequence the second
+    int canvas_planes() const { return two_tile_sets() ? 4 : job.kind == Job::GRAY ? 1 : 3; }
+    // RGBA and planar RGBA frames do not roll: d_bgr, d_alpha and d_minmax are single buffers the bleed writes on the compute stream, and in a rolling sequence the second
     // tile group of frame f would still gather from them while frame f + 1 bleeds into them.  Through run_frame() every pass joins its groups before the
     // next launch on `stream`, so stream order alone keeps the single buffers (and the one slab and canvas) safe.
-    bool rolls() const { return job.kind != Job::RGBA; }
+    bool rolls() const { return !two_tile_sets(); }
     // only BGR frames are what benchResident / residentOutput / profileFrame replay out of d_frame / d_out
     bool replayable() const { return job.kind == Job::BGR; }
-    // the slot table, the liveness table and the slab the frames of a call share: every tile of the frame in one part, RGBA the 2N schedule (rgba_setup)
+    // the slot table, the liveness table and the slab the frames of a call share: every tile of the frame in one part, RGBA and planar RGBA the 2N schedule (rgba_setup)
     void call_slots(int rows, int cols, const TileGrid& grid, const StripPlan& sp) {
-        if (job.kind == Job::RGBA) { rgba_setup(rows, cols, grid, job.rgba.skip); return; }
+        if (two_tile_sets()) { rgba_setup(rows, cols, grid, job.rgba.skip); return; }
         const size_t stepCount = pass_slots(sp.tile_count);
         fill_slots(grid, 0, sp.tile_count, 1, 0, stepCount);
         upload_slots(grid, stepCount, stepCount);
@@ -1306,6 +1346,15 @@ struct Img2Img::Impl {
                 hipAssert(launch_gather_planar(p, gs));
                 break;
             }
+            case Job::PLANAR_RGBA: {                                  // from the bled colour planes or the alpha plane
+                GatherPlanarRgbaParams p = tile_side<GatherPlanarRgbaParams>(gp);
+                p.rows = gp.rows; p.cols = gp.cols; p.bits = job.planar.in_bits;
+                p.colour_step = p.alpha_step = planar_step(gp.cols, p.bits);
+                for (int k = 0; k < 3; ++k) p.colour[k] = d_bgr + (size_t)k * p.colour_step * gp.rows;
+                p.alpha = d_alpha;
+                hipAssert(launch_gather_planar_rgba(p, gs));
+                break;
+            }
         }
     }
     // The three launches that can end a frame, all over the whole canvas of the frame's tiles (one part, slot 0 = tile 0; BGR: the strip's columns): the canvas
@@ -1315,7 +1364,7 @@ struct Img2Img::Impl {
     void compose_canvas(int rows, int cols, const TileGrid& grid, hipStream_t on) {
         const ComposeParams cp = compose_base(rows, cols, grid);
         switch (job.kind) {
-            case Job::RGBA: {
+            case Job::RGBA: case Job::PLANAR_RGBA: {                  // (the same four fp32 planes)
                 ComposeCanvasRgbaParams p;
                 p.c = cp; p.alpha_tiles = alpha_tiles(); p.canvas = d_canvas;
                 hipAssert(launch_compose_canvas_rgba(p, on));
@@ -1339,6 +1388,14 @@ struct Img2Img::Impl {
                 resample_base(p);
                 p.dst = frame_planes(d_out, p.outH, p.outW, true);
                 hipAssert(launch_resample_planar(p, on));
+                break;
+            }
+            case Job::PLANAR_RGBA: {                                  // the four planes of the target size
+                ResamplePlanarRgbaParams p;
+                resample_base(p);
+                p.dst = rgba_planes(d_out, p.outH, p.outW, true);
+                p.uniform = job.rgba.uniform ? 1 : 0; p.alpha_value = uniform_alpha();
+                hipAssert(launch_resample_planar_rgba(p, on));
                 break;
             }
             case Job::YUV: {                                          // the planes of the target size (resized YUV frames are I420)
@@ -1368,6 +1425,14 @@ struct Img2Img::Impl {
                 p.c.dst = d_out; p.c.dst_step = frame_step(p.c.outW, true);
                 p.alpha_tiles = alpha_tiles(); p.alpha_value = job.rgba.value;
                 hipAssert(launch_compose_rgba(p, on));
+                break;
+            }
+            case Job::PLANAR_RGBA: {                                  // four planes of job.planar.out_bits
+                ComposePlanarRgbaParams p;
+                p.c = compose_base(rows, cols, grid);
+                p.dst = rgba_planes(d_out, p.c.outH, p.c.outW, true);
+                p.alpha_tiles = alpha_tiles(); p.alpha_value = uniform_alpha();
+                hipAssert(launch_compose_planar_rgba(p, on));
                 break;
             }
             case Job::GRAY: case Job::PLANAR: {                       // one sample per pixel, or three planes of job.planar.out_bits
@@ -1407,17 +1472,15 @@ struct Img2Img::Impl {
         bleed_frame(rows, cols, radius);
     }
     void ensure_bleed_planes(int rows, int cols) {
-        ensure(d_bgr, bgr_cap, (size_t)rows * cols * 3);
-        ensure(d_alpha, alpha_cap, (size_t)rows * cols);
+        const size_t plane = bleed_plane_bytes(rows, cols);
+        ensure(d_bgr, bgr_cap, plane * 3);
+        ensure(d_alpha, alpha_cap, plane);
         if (!d_minmax) hipAssert(hipMalloc((void**)&d_minmax, 2 * sizeof(unsigned)));
     }
-    // the BGRA frame in d_frame (packed) -> d_bgr, d_alpha, d_minmax, on `stream`
+    // the frame in d_frame (BGRA, packed; planar RGBA: its four planes) -> d_bgr, d_alpha, d_minmax, on `stream`
     void bleed_frame(int rows, int cols, int radius) {
         hipAssert(hipMemsetAsync(d_minmax, 0, 2 * sizeof(unsigned), stream));
-        AlphaBleedParams bp;
-        bp.bgra = d_frame; bp.step = (size_t)cols * 4; bp.rows = rows; bp.cols = cols; bp.radius = radius;
-        bp.bgr = d_bgr; bp.bgr_step = (size_t)cols * 3; bp.alpha = d_alpha; bp.alpha_step = (size_t)cols; bp.minmax = d_minmax;
-        hipAssert(launch_alpha_bleed(bp, stream));
+        launch_bleed(rows, cols, radius);
     }
 
     // ---- The frame calls other than render() / renderStrip(): one record, one checker per format, one runner.  An entry point checks (X_check fills the record
@@ -1532,6 +1595,33 @@ struct Img2Img::Impl {
         }
         return call_grid(c);
     }
+    // The planar RGBA calls: planar_check's order over four planes, then the bleed radius (and that a bleed has integer samples to work on), then the grid
+    std::string planar_rgba_check(const PlanarRgbaImage* srcs, const PlanarRgbaImage* dsts, int count, const RgbaOptions& opt, int resizeFilter, FrameCall& c) const {
+        const int rows = srcs[0].rows, cols = srcs[0].cols, in_bits = srcs[0].bits, out_bits = dsts[0].bits;
+        if (!planar_bits_ok(in_bits) || !planar_bits_ok(out_bits)) return "Planar frames must have 8, 10, 12, 16 or 32 (float) bits.";
+        if (rows <= 0 || cols <= 0) return "Input image is empty.";
+        if (const std::string why = call_target(resizeFilter, dsts[0], rows, cols, true, c); !why.empty()) return why;
+        for (int i = 0; i < count; ++i) {
+            if (srcs[i].rows != rows || srcs[i].cols != cols || srcs[i].bits != in_bits) return "Input images must be of one size and depth.";
+            if (!rgba_planes_ok(srcs[i])) return "Input image has a missing plane or an invalid step.";
+            if (dsts[i].rows != c.out_rows || dsts[i].cols != c.out_cols) return out_size_text(c);
+            if (dsts[i].bits != out_bits) return "Output images must be of one depth.";
+            if (!rgba_planes_ok(dsts[i])) return "Output image has a missing plane or an invalid step.";
+        }
+        if (const std::string why = bleed_problem(opt.bleed, in_bits); !why.empty()) return why;
+        return call_grid(c);
+    }
+    // every plane present, with a step that holds its row, u16 / f32 samples aligned to their size
+    static bool rgba_planes_ok(const PlanarRgbaImage& f) {
+        const size_t bps = planar_sample_bytes(f.bits);
+        for (int k = 0; k < 4; ++k) if (!f.planes[k] || f.steps[k] < (size_t)f.cols * bps || ((((size_t)f.planes[k]) | f.steps[k]) & (bps - 1)) != 0) return false;
+        return true;
+    }
+    static std::string bleed_problem(int radius, int bits) {
+        if (radius < 0 || radius > kBleedMaxRadius) return "Alpha bleed radius " + std::to_string(radius) + " is not in [0, " + std::to_string(kBleedMaxRadius) + "].";
+        if (radius > 0 && bits == 32) return "Colour bleed takes integer samples.";
+        return "";
+    }
     // The tile grid of a rows x cols frame into `grid`; returns "" or why the engine cannot render it (img2img_render.cpp:232-240)
     std::string frame_grid(int rows, int cols, TileGrid& grid) const {
         const int s = cfg.scaling;
@@ -1624,7 +1714,7 @@ struct Img2Img::Impl {
             const auto t0 = std::chrono::steady_clock::now();
             run_passes(rows, cols, 2 * N, 0, false, 0, true, 0, 0, 0, F);
             hipAssert(hipEventSynchronize(ev_minmax));
-            opt.uniform = h_minmax[0] + h_minmax[1] == 255u;      // max(A) + max(255 - A) == 255  <=>  min(A) == max(A)
+            opt.uniform = h_minmax[0] + h_minmax[1] == alpha_top();       // max(A) + max(top - A) == top  <=>  min(A) == max(A)
             opt.value = h_minmax[0];
             const int tiles = opt.uniform ? N : 2 * N, batchCount = batch_count(tiles);
             const double ms = std::chrono::duration<double, std::milli>(std::chrono::steady_clock::now() - t0).count();
@@ -2500,6 +2590,77 @@ bool Img2Img::runPlanar(const PlanarImage* srcs, PlanarImage* dsts, int count, i
     impl->run_call(call, count, single, resizeFilter,
         [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(srcs[i], dev, call.rows, call.cols, true, on); },
         [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(dsts[i], dev, call.out_rows, call.out_cols, false, on); });
+    return true;
+    });
+}
+
+// Planar RGBA frames: renderRgba()'s frame on renderPlanar()'s samples.  Four 2-D copies up, alpha_bleed_planes_kernel (three colour planes with the
+// visible colours spread under alpha == 0, the alpha plane, the plane's range), ONE schedule of the frame's N colour tiles followed by its N alpha tiles through
+// gather_planes_rgba_kernel, compose_planes_rgba_kernel - resized: compose_canvas_rgba_kernel and resample_planes_rgba_kernel -, four 2-D copies down.  A single
+// part on the compute stream; progress and skipUniformAlpha as renderRgba() (the frame step is Impl::rgba_frame).
+bool Img2Img::renderPlanarRgba(const PlanarRgbaImage& src, PlanarRgbaImage& dst, const RgbaOptions& opt) { return runPlanarRgba(&src, &dst, 1, opt, -1, "renderPlanarRgba", true); }
+
+bool Img2Img::renderPlanarRgbaResized(const PlanarRgbaImage& src, PlanarRgbaImage& dst, const RgbaOptions& opt, ResizeFilter filter) {
+    return runPlanarRgba(&src, &dst, 1, opt, filter_id(filter), "renderPlanarRgbaResized", true);
+}
+
+// Planar RGBA frames through renderSequence()'s pipeline (never rolling: the bleed's planes are single buffers): output i is the bytes of the single call
+bool Img2Img::renderSequencePlanarRgba(const PlanarRgbaImage* srcs, PlanarRgbaImage* dsts, int count, const RgbaOptions& opt) {
+    return runPlanarRgba(srcs, dsts, count, opt, -1, "renderSequencePlanarRgba", false);
+}
+
+bool Img2Img::renderSequencePlanarRgbaResized(const PlanarRgbaImage* srcs, PlanarRgbaImage* dsts, int count, const RgbaOptions& opt, ResizeFilter filter) {
+    return runPlanarRgba(srcs, dsts, count, opt, filter_id(filter), "renderSequencePlanarRgbaResized", false);
+}
+
+bool Img2Img::runPlanarRgba(const PlanarRgbaImage* srcs, PlanarRgbaImage* dsts, int count, const RgbaOptions& opt, int resizeFilter, const char* who, bool single) {
+    return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
+    if (count <= 0) return true;
+    if (!srcs || !dsts) { W2X_LOG_AS(who, error, "No frames given."); return false; }
+    Impl::FrameCall call;
+    if (const std::string why = impl->planar_rgba_check(srcs, dsts, count, opt, resizeFilter, call); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
+    impl->job.kind = Impl::Job::PLANAR_RGBA; impl->job.planar.in_bits = srcs[0].bits; impl->job.planar.out_bits = dsts[0].bits;
+    impl->job.rgba = Impl::RgbaJob{opt.bleed, opt.skipUniformAlpha};
+    // the four planes of a frame between the caller's pointers and the device layout (rgba_planes), on stream `on`
+    auto copy_planes = [&](const PlanarRgbaImage& host, uint8_t* dev, int r, int c, bool up, hipStream_t on) {
+        const RgbaPlanes d = impl->rgba_planes(dev, r, c, !up);
+        const size_t width = (size_t)c * planar_sample_bytes(host.bits);
+        for (int k = 0; k < 4; ++k) {
+            if (up) hipAssert(hipMemcpy2DAsync(d.p[k], d.step[k], host.planes[k], host.steps[k], width, r, hipMemcpyHostToDevice, on));
+            else hipAssert(hipMemcpy2DAsync(host.planes[k], host.steps[k], d.p[k], d.step[k], width, r, hipMemcpyDeviceToHost, on));
+        }
+    };
+    impl->run_call(call, count, single, resizeFilter,
+        [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(srcs[i], dev, call.rows, call.cols, true, on); },
+        [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(dsts[i], dev, call.out_rows, call.out_cols, false, on); });
+    return true;
+    });
+}
+
+bool Img2Img::alphaBleedPlanes(const PlanarRgbaImage& src, PlanarImage& colour, int radius, unsigned* words) {
+    const char* who = "alphaBleedPlanes";
+    return impl->entry(who, "Alpha bleed called before a successful load.", "Alpha bleed failed unexpectedly: ",
+                       [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
+    const int rows = src.rows, cols = src.cols, bits = src.bits;
+    if (!planar_bits_ok(bits) || colour.bits != bits) { W2X_LOG_AS(who, error, "Planar frames must have 8, 10, 12, 16 or 32 (float) bits, the same on both sides."); return false; }
+    if (rows <= 0 || cols <= 0) { W2X_LOG_AS(who, error, "Input image is empty."); return false; }
+    if (!Impl::rgba_planes_ok(src)) { W2X_LOG_AS(who, error, "Input image has a missing plane or an invalid step."); return false; }
+    if (colour.rows != rows || colour.cols != cols) { W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(cols) + "x" + std::to_string(rows) + "."); return false; }
+    const size_t bps = planar_sample_bytes(bits), width = (size_t)cols * bps;
+    for (int k = 0; k < 3; ++k)
+        if (!colour.planes[k] || colour.steps[k] < width || ((((size_t)colour.planes[k]) | colour.steps[k]) & (bps - 1)) != 0) { W2X_LOG_AS(who, error, "Output image has a missing plane or an invalid step."); return false; }
+    if (const std::string why = Impl::bleed_problem(radius, bits); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
+    impl->last_rows = impl->last_cols = 0;   // (d_frame is overwritten: the last render() frame is no longer there to replay)
+    impl->job.kind = Impl::Job::PLANAR_RGBA; impl->job.planar.in_bits = impl->job.planar.out_bits = bits;
+    impl->ensure(impl->d_frame, impl->frame_cap, impl->frame_bytes(rows, cols, false));
+    impl->ensure_bleed_planes(rows, cols);
+    const RgbaPlanes d = impl->rgba_planes(impl->d_frame, rows, cols, false);
+    for (int k = 0; k < 4; ++k) hipAssert(hipMemcpy2DAsync(d.p[k], d.step[k], src.planes[k], src.steps[k], width, rows, hipMemcpyHostToDevice, impl->stream));
+    impl->bleed_frame(rows, cols, radius);
+    for (int k = 0; k < 3; ++k)
+        hipAssert(hipMemcpy2DAsync(colour.planes[k], colour.steps[k], impl->d_bgr + (size_t)k * d.step[0] * rows, d.step[0], width, rows, hipMemcpyDeviceToHost, impl->stream));
+    if (words) hipAssert(hipMemcpyAsync(words, impl->d_minmax, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, impl->stream));
+    hipAssert(hipStreamSynchronize(impl->stream));
     return true;
     });
 }

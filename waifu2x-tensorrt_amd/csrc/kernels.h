@@ -443,6 +443,57 @@ struct ResamplePlanarParams {
     PlanarPlanes dst;
 };
 hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s);
+// Planar RGBA frames (renderPlanarRgba; k_planar_rgba.hip): four planes R, G, B, A of one sample type, laid out like PlanarPlanes' three.
+struct RgbaPlanes {
+    uint8_t* p[4] = {nullptr, nullptr, nullptr, nullptr}; size_t step[4] = {0, 0, 0, 0};
+    int rows = 0, cols = 0, bits = 8;
+};
+// alpha_bleed_planes_kernel: alpha_bleed_kernel on planes of any integer depth (tiles.h alpha_bleed_planes states the arithmetic): the colour planes of src with
+// every code clamped to 2^bits - 1 and the colours of the visible pixels (clamped alpha > 0) spread `radius` pixels (0 .. kBleedMaxRadius) under the others into
+// colour[0..2], the alpha plane copied into alpha (steps in bytes, planes of src.bits samples).  Float planes: radius 0 only, both copied bit for bit.
+// minmax: two device words (zeroed by the caller) that receive max(key) and max(top - key) over the frame, key the clamped alpha code and top 2^bits - 1 - float:
+// the bits of min(max(a, 0), 1) (NaN, -0.0: 0) and top 0x3F800000, which order as the values do -: the plane is one value iff the two add up to top.
+struct AlphaBleedPlanesParams {
+    RgbaPlanes src;
+    int radius = 0;
+    uint8_t* colour[3] = {nullptr, nullptr, nullptr}; size_t colour_step = 0;
+    uint8_t* alpha = nullptr; size_t alpha_step = 0;
+    unsigned* minmax = nullptr;
+};
+inline unsigned alpha_key_top(int bits) { return bits == 32 ? 0x3F800000u : (1u << bits) - 1u; }
+hipError_t launch_alpha_bleed_planes(const AlphaBleedPlanesParams& p, hipStream_t s);
+// gather_planes_rgba_kernel: gather_rgba_kernel's slots (kSlotColour / kSlotAlpha) over those planes with gather_planes_kernel's samples: a colour slot reads
+// make_px(r, g, b) from colour[0..2], an alpha slot (a, a, a) from the alpha plane
+struct GatherPlanarRgbaParams {
+    const uint8_t* colour[3] = {nullptr, nullptr, nullptr}; size_t colour_step = 0;
+    const uint8_t* alpha = nullptr; size_t alpha_step = 0;
+    int rows = 0, cols = 0, bits = 8;
+    void* out = nullptr; int fp32 = 0;
+    const TileSlot* slots = nullptr;
+    int B = 0, T = 0;
+};
+hipError_t launch_gather_planar_rgba(const GatherPlanarRgbaParams& p, hipStream_t s);
+// compose_planes_rgba_kernel: compose_planes_kernel's three sums over the colour tiles (c.tiles) into dst.p[0..2] and its green sum over the alpha tiles (the same
+// grid, slot 0 = tile 0) into dst.p[3], quantised alike; alpha_tiles == nullptr: the plane is alpha_value (in [0, 1]) quantised like a sum.
+struct ComposePlanarRgbaParams {
+    ComposeParams c;
+    const void* alpha_tiles = nullptr;
+    float alpha_value = 1.f;
+    RgbaPlanes dst;
+};
+hipError_t launch_compose_planar_rgba(const ComposePlanarRgbaParams& p, hipStream_t s);
+// resample_planes_rgba_kernel: resample_planes_kernel over the four planes of compose_canvas_rgba_kernel's canvas; uniform != 0: the canvas has three planes and
+// dst.p[3] is alpha_value quantised like an accumulator
+struct ResamplePlanarRgbaParams {
+    const float* canvas = nullptr; int inW = 0, inH = 0;
+    int outW = 0, outH = 0;
+    const int* fx = nullptr; const float* wx = nullptr; int kx = 0;
+    const int* fy = nullptr; const float* wy = nullptr; int ky = 0;
+    int rows_max = 0;
+    RgbaPlanes dst;
+    int uniform = 0; float alpha_value = 1.f;
+};
+hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStream_t s);
 // k_resample.hip resample_yuv_kernel: resample_kernel's resize of the fp32 RGB canvas (same tap tables, same rows_max) with compose_yuv_kernel's
 // encoding behind it instead of the BGR quantisation: the resized R, G, B clamped to [0, 1] and written as YUV 4:2:0 planes of outH x outW
 // (dst.rows x dst.cols), Y per pixel, Cb / Cr of the RGB filtered (1/4, 1/2, 1/4) x (1/2, 1/2) onto each chroma site (renderYuvResized)

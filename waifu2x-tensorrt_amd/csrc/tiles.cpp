@@ -190,4 +190,66 @@ bool alpha_bleed(const uint8_t* bgr, size_t bgr_step, const uint8_t* alpha, size
     return true;
 }
 
+namespace {
+// alpha_bleed's loop on three planes of samples T (the state: three packed planes of clamped codes and the flags)
+template <typename T>
+void bleed_planes(const void* const colour[3], const size_t colour_steps[3], const void* alpha, size_t alpha_step, int rows, int cols, unsigned maxcode, int radius,
+                  void* const out[3], const size_t out_steps[3]) {
+    const size_t n_px = (size_t)rows * cols;
+    auto at = [](const void* base, size_t step, int y, int x) { return ((const T*)((const uint8_t*)base + (size_t)y * step))[x]; };
+    std::vector<T> col(n_px * 3), col2;
+    std::vector<uint8_t> known(n_px), known2;
+    for (int y = 0; y < rows; ++y)
+        for (int x = 0; x < cols; ++x) {
+            const size_t i = (size_t)y * cols + x;
+            for (int ch = 0; ch < 3; ++ch) col[i * 3 + ch] = (T)std::min<unsigned>(at(colour[ch], colour_steps[ch], y, x), maxcode);
+            known[i] = std::min<unsigned>(at(alpha, alpha_step, y, x), maxcode) > 0;
+        }
+    for (int it = 1; it <= radius; ++it) {
+        col2 = col; known2 = known;
+        bool changed = false;
+        for (int y = 0; y < rows; ++y)
+            for (int x = 0; x < cols; ++x) {
+                const size_t i = (size_t)y * cols + x;
+                if (known[i]) continue;
+                uint32_t n = 0, sum[3] = {0, 0, 0};
+                for (int dy = -1; dy <= 1; ++dy)
+                    for (int dx = -1; dx <= 1; ++dx) {
+                        const int yy = y + dy, xx = x + dx;
+                        if ((dy == 0 && dx == 0) || yy < 0 || yy >= rows || xx < 0 || xx >= cols) continue;
+                        const size_t q = (size_t)yy * cols + xx;
+                        if (!known[q]) continue;
+                        ++n;
+                        for (int ch = 0; ch < 3; ++ch) sum[ch] += col[q * 3 + ch];
+                    }
+                if (!n) continue;
+                for (int ch = 0; ch < 3; ++ch) col2[i * 3 + ch] = (T)((sum[ch] + (n >> 1)) / n);
+                known2[i] = 1; changed = true;
+            }
+        if (!changed) break;
+        col.swap(col2); known.swap(known2);
+    }
+    for (int ch = 0; ch < 3; ++ch)
+        for (int y = 0; y < rows; ++y) {
+            T* d = (T*)((uint8_t*)out[ch] + (size_t)y * out_steps[ch]);
+            for (int x = 0; x < cols; ++x) d[x] = col[((size_t)y * cols + x) * 3 + ch];
+        }
+}
+}  // namespace
+
+bool alpha_bleed_planes(const void* const colour[3], const size_t colour_steps[3], const void* alpha, size_t alpha_step, int rows, int cols, int sample_bytes,
+                        unsigned maxcode, int radius, void* const out[3], const size_t out_steps[3]) {
+    if (!colour || !colour_steps || !alpha || !out || !out_steps || rows <= 0 || cols <= 0 || radius < 0 || radius > 16) return false;
+    if ((sample_bytes != 1 && sample_bytes != 2) || maxcode == 0 || maxcode > (sample_bytes == 1 ? 255u : 65535u)) return false;
+    const size_t row = (size_t)cols * sample_bytes, mis = (size_t)sample_bytes - 1;
+    if (alpha_step < row || ((((size_t)alpha) | alpha_step) & mis)) return false;
+    for (int ch = 0; ch < 3; ++ch) {
+        if (!colour[ch] || !out[ch] || colour_steps[ch] < row || out_steps[ch] < row) return false;
+        if ((((size_t)colour[ch]) | colour_steps[ch] | ((size_t)out[ch]) | out_steps[ch]) & mis) return false;
+    }
+    if (sample_bytes == 1) bleed_planes<uint8_t>(colour, colour_steps, alpha, alpha_step, rows, cols, maxcode, radius, out, out_steps);
+    else bleed_planes<uint16_t>(colour, colour_steps, alpha, alpha_step, rows, cols, maxcode, radius, out, out_steps);
+    return true;
+}
+
 }  // namespace w2x

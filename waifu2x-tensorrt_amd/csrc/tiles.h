@@ -64,4 +64,12 @@ ResizeTaps resize_taps(int in, int out, int filter);
 // plane leave the frame unchanged; a known pixel never changes).  out may not alias bgr.  false (nothing written) for invalid arguments.
 bool alpha_bleed(const uint8_t* bgr, size_t bgr_step, const uint8_t* alpha, size_t alpha_step, int rows, int cols, int radius, uint8_t* out, size_t out_step);
 
+// alpha_bleed restated on planes of codes of any integer depth (planar RGBA frames).  colour[0..2] and alpha: planes of rows x cols samples of
+// sample_bytes (1: uint8, 2: uint16) with steps in bytes; maxcode = 2^bits - 1 (at most 65535, and 255 for one-byte samples).  Every code is first clamped to
+// maxcode, alpha included: known_0(p) = min(alpha(p), maxcode) > 0.  The iterations, the neighbourhood and the mean (sum + (n >> 1)) / n are alpha_bleed's - eight
+// 16-bit codes fit a 32-bit sum.  out[0..2]: the three planes of state R (no plane of out may alias an input).  At one byte and maxcode 255 the planes are those
+// of alpha_bleed.  false (nothing written) for invalid arguments.
+bool alpha_bleed_planes(const void* const colour[3], const size_t colour_steps[3], const void* alpha, size_t alpha_step, int rows, int cols, int sample_bytes,
+                        unsigned maxcode, int radius, void* const out[3], const size_t out_steps[3]);
+
 }  // namespace w2x

@@ -81,6 +81,7 @@ def _plane_args(planes):
     return [p.ctypes.data for p in planes] + pad, [p.strides[0] for p in planes] + [0] * len(pad)
 
 
+_COUNT = {3: "three", 4: "four"}
 PLANAR_DTYPES = {8: np.uint8, 10: np.uint16, 12: np.uint16, 16: np.uint16, 32: np.float32}   # the sample type of each depth of a planar RGB frame
 
 
@@ -89,18 +90,19 @@ def planar_plane_bytes(rows: int, cols: int, bits: int) -> int:
     return int(lib().w2x_planar_plane_bytes(int(rows), int(cols), int(bits)))
 
 
-def _planar_order(order):
-    """where R, G and B sit in a frame whose planes come in `order` ("rgb", "gbr" - ffmpeg's gbrp -, any permutation)"""
-    if not isinstance(order, str) or sorted(order) != ["b", "g", "r"]:
-        raise ValueError(f"order must name the planes r, g and b once each (\"rgb\", \"gbr\"), got {order!r}")
-    return [order.index(ch) for ch in "rgb"]
+def _planar_order(order, names="rgb"):
+    """where R, G and B (names="rgba": and A) sit in a frame whose planes come in `order` ("rgb", "gbr" - ffmpeg's gbrp -, any permutation; "rgba", "gbra" -
+    ffmpeg's gbrap)"""
+    if not isinstance(order, str) or sorted(order) != sorted(names):
+        raise ValueError(f"order must name the planes {', '.join(names)} once each (\"{names}\", \"gbr{names[3:]}\"), got {order!r}")
+    return [order.index(ch) for ch in names]
 
 
-def _planar_bits(planes, bits=None, error="planes must be three 2-D arrays of one shape and sample type (uint8, uint16 or float32) with packed samples", shape=None,
-                 empty_ok=False) -> int:
+def _planar_bits(planes, bits=None, error=None, shape=None, empty_ok=False, n=3) -> int:
     """The depth of a planar frame: 8 for uint8, 16 for uint16, 32 for float32 planes; bits= says 10 or 12 for uint16 planes (or restates the default).
-    Checks three 2-D planes of one shape (`shape` when given) and type with packed samples; rows may be padded, every plane its own way."""
-    ok = isinstance(planes, (tuple, list)) and len(planes) == 3 and all(isinstance(p, np.ndarray) and p.ndim == 2 for p in planes)
+    Checks n (three; planar RGBA: four) 2-D planes of one shape (`shape` when given) and type with packed samples; rows may be padded, every plane its own way."""
+    error = error or f"planes must be {_COUNT[n]} 2-D arrays of one shape and sample type (uint8, uint16 or float32) with packed samples"
+    ok = isinstance(planes, (tuple, list)) and len(planes) == n and all(isinstance(p, np.ndarray) and p.ndim == 2 for p in planes)
     ok = ok and planes[0].dtype in (np.uint8, np.uint16, np.float32) and all(p.dtype == planes[0].dtype and p.shape == planes[0].shape for p in planes)
     ok = ok and (shape is None or planes[0].shape == tuple(shape))
     ok = ok and all((empty_ok and not p.size) or (p.strides[1] == p.itemsize and p.strides[0] > 0) for p in planes)
@@ -295,6 +297,16 @@ PLANAR_SYMBOLS = {
     "w2x_render_sequence_planar_resized": (_I, _YUV2 + [_I, _I]),
     "w2x_planar_plane_bytes": (_Z, [_I, _I, _I]),
 }
+# The planar RGBA entries of include/w2x/c_api_rgbap.h, a table of their own likewise.  Their names say "rgbap": the planar and the gray table own every exported
+# name that holds their word.  _YUV2 + [bleed, skip_uniform_alpha]; the bleed entries: (planes, steps, rows, cols, bits, radius, out planes, out steps[, words]).
+RGBAP_SYMBOLS = {
+    "w2x_render_rgbap": (_I, _YUV2 + [_I, _I]),
+    "w2x_render_rgbap_resized": (_I, _YUV2 + [_I, _I, _I]),
+    "w2x_render_sequence_rgbap": (_I, _YUV2 + [_I, _I, _I]),
+    "w2x_render_sequence_rgbap_resized": (_I, _YUV2 + [_I, _I, _I, _I]),
+    "w2x_alpha_bleed_rgbap": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
+    "w2x_alpha_bleed_rgbap_device": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
+}
 _lib = None
 
 
@@ -307,7 +319,7 @@ def lib():
         raise W2xError(f"{lib_path} is missing - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "or `make -C waifu2x-tensorrt_amd` (there is no CPU fallback)")
     L = C.CDLL(lib_path)
-    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()) + list(PLANAR_SYMBOLS.items()):
+    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()) + list(PLANAR_SYMBOLS.items()) + list(RGBAP_SYMBOLS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -575,30 +587,32 @@ class Img2Img:
             return self._L.w2x_render_sequence_gray_resized(self._h, _pointers(fs), r, c, step, _pointers(os_, len(fs)), rows, cols, cols, len(fs), fid)
         return self._sequence(frames, outs, pinned, alloc, np.copy, run, "render_sequence_gray failed", check)
 
-    def _planar_call(self, planes, size, bits, out_bits, order, dst, who):
-        """what the two single planar calls share: the checks of both sides and the arguments of the C entry up to dst_bits (planes in R, G, B order)"""
-        idx = _planar_order(order)
-        bits = _planar_bits(planes, bits)
+    def _planar_call(self, planes, size, bits, out_bits, order, dst, who, names="rgb"):
+        """what the single planar calls share: the checks of both sides and the arguments of the C entry up to dst_bits (planes in R, G, B order; names="rgba": the
+        four planes of a planar RGBA frame in R, G, B, A order)"""
+        n = len(names)
+        idx = _planar_order(order, names)
+        bits = _planar_bits(planes, bits, n=n)
         ob = bits if out_bits is None else int(out_bits)
         if ob not in PLANAR_DTYPES:
             raise ValueError(f"out_bits must be one of {sorted(PLANAR_DTYPES)}, got {out_bits!r}")
         r, c = planes[0].shape
         s = self._scaling
         rows, cols = (r * s, c * s) if size is None else (max(int(size[0]), 0), max(int(size[1]), 0))
-        out = tuple(np.empty((rows, cols), PLANAR_DTYPES[ob]) for _ in range(3)) if dst is None else None
+        out = tuple(np.empty((rows, cols), PLANAR_DTYPES[ob]) for _ in range(n)) if dst is None else None
         dst = out if dst is None else tuple(dst)
         # the C ABI sees pointers and steps only: the shapes and the sample type of out_bits are checked here (an empty target: refused by the library)
-        error = f"dst must be three 2-D {np.dtype(PLANAR_DTYPES[ob]).name} planes of one shape with packed samples"
-        _planar_bits(dst, ob, error, empty_ok=True)
+        error = f"dst must be {_COUNT[n]} 2-D {np.dtype(PLANAR_DTYPES[ob]).name} planes of one shape with packed samples"
+        _planar_bits(dst, ob, error, empty_ok=True, n=n)
         if size is not None and dst[0].shape != (rows, cols):
-            raise ValueError(f"dst must be three planes of the target size {(rows, cols)}")
+            raise ValueError(f"dst must be {_COUNT[n]} planes of the target size {(rows, cols)}")
         if size is None and s and dst[0].shape != (rows, cols):     # (never loaded: as in render())
             self._refuse(who, f"Output image has invalid size: expected {cols}x{rows}.")
             return None, out
         src = [planes[k] for k in idx]
         d = [dst[k] for k in idx]
-        args = (self._h, (C.c_void_p * 3)(*[_data(p) for p in src]), (C.c_size_t * 3)(*[p.strides[0] for p in src]), r, c, bits,
-                (C.c_void_p * 3)(*[_data(p) for p in d]), (C.c_size_t * 3)(*[p.strides[0] for p in d]),
+        args = (self._h, (C.c_void_p * n)(*[_data(p) for p in src]), (C.c_size_t * n)(*[p.strides[0] for p in src]), r, c, bits,
+                (C.c_void_p * n)(*[_data(p) for p in d]), (C.c_size_t * n)(*[p.strides[0] for p in d]),
                 int(size[0]) if size is not None else rows, int(size[1]) if size is not None else cols, ob)
         return args, out
 
@@ -624,12 +638,19 @@ class Img2Img:
         size = (rows, cols) every frame is resized like render_planar_resized() (w2x_render_sequence_planar_resized).  Output i is the bytes of the single
         call on frame i.  The frames share one set of row strides (rows may be padded); outs: pre-allocated plane triples of one set of strides;
         pinned=True takes the output planes from alloc_host() (a ring of three frames; copies of the results are returned)."""
+        return self._planar_sequence(frames, size, bits, out_bits, order, filter, outs, pinned, "rgb", (),
+                                     self._L.w2x_render_sequence_planar, self._L.w2x_render_sequence_planar_resized, "render_sequence_planar failed")
+
+    def _planar_sequence(self, frames, size, bits, out_bits, order, filter, outs, pinned, names, options, plain, resized, fallback):
+        """what the planar sequence calls share, over len(names) planes per frame: the checks, the outputs and the two C entries, whose arguments end
+        ..., dst_bits, count, *options[, filter]"""
         if len(frames) == 0:
             return []
+        n = len(names)
         fid = _filter_id(filter)
-        idx = _planar_order(order)
+        idx = _planar_order(order, names)
         frames = [tuple(f) if isinstance(f, (tuple, list)) else f for f in frames]
-        bits = _planar_bits(frames[0], bits)
+        bits = _planar_bits(frames[0], bits, n=n)
         ob = bits if out_bits is None else int(out_bits)
         if ob not in PLANAR_DTYPES:
             raise ValueError(f"out_bits must be one of {sorted(PLANAR_DTYPES)}, got {out_bits!r}")
@@ -637,7 +658,7 @@ class Img2Img:
         steps = [p.strides[0] for p in frames[0]]
         for f in frames[1:]:
             try:
-                fb = _planar_bits(f, bits)
+                fb = _planar_bits(f, bits, n=n)
             except ValueError:
                 fb = None                                                       # (planes of another sample type, or no planar frame at all)
             if fb != bits or f[0].shape != (r, c) or [p.strides[0] for p in f] != steps:
@@ -650,26 +671,64 @@ class Img2Img:
 
         def alloc(host):
             if not host:
-                return None, tuple(np.empty(shape, dt) for _ in range(3))
-            buf = self.alloc_host((max(3 * nb, 1),))          # one page-locked block per frame, carved into its planes
-            return buf, tuple(buf[k * nb:(k + 1) * nb].view(dt).reshape(shape) for k in range(3))
+                return None, tuple(np.empty(shape, dt) for _ in range(n))
+            buf = self.alloc_host((max(n * nb, 1),))          # one page-locked block per frame, carved into its planes
+            return buf, tuple(buf[k * nb:(k + 1) * nb].view(dt).reshape(shape) for k in range(n))
 
         first = []
 
         def check(o):
-            _planar_bits(o, ob, f"outs must be triples of 2-D {dt.name} planes of the output size with packed samples", shape=shape, empty_ok=True)
+            _planar_bits(o, ob, f"outs must hold {_COUNT[n]} 2-D {dt.name} planes of the output size with packed samples each", shape=shape, empty_ok=True, n=n)
             first.append([p.strides[0] for p in o])
             if first[-1] != first[0]:
                 raise ValueError("outs must share one set of row strides")
 
         def run(fs, os_):
             m = len(fs)
-            sp = (C.c_void_p * (3 * m))(*[_data(f[k]) for f in fs for k in idx])
-            dp = (C.c_void_p * (3 * m))(*[_data(o[k]) for o in list(os_)[:m] for k in idx] + [None] * (3 * (m - len(os_[:m]))))
-            a = (self._h, sp, (C.c_size_t * 3)(*[steps[k] for k in idx]), r, c, bits, dp, (C.c_size_t * 3)(*[os_[0][k].strides[0] for k in idx]), rows, cols, ob, m)
-            return self._L.w2x_render_sequence_planar(*a) if size is None else self._L.w2x_render_sequence_planar_resized(*a, fid)
-        return self._sequence(frames, outs, pinned, alloc, lambda d: tuple(p.copy() for p in d), run,
-                              "render_sequence_planar failed", check)
+            sp = (C.c_void_p * (n * m))(*[_data(f[k]) for f in fs for k in idx])
+            dp = (C.c_void_p * (n * m))(*[_data(o[k]) for o in list(os_)[:m] for k in idx] + [None] * (n * (m - len(os_[:m]))))
+            a = (self._h, sp, (C.c_size_t * n)(*[steps[k] for k in idx]), r, c, bits, dp, (C.c_size_t * n)(*[os_[0][k].strides[0] for k in idx]), rows, cols, ob, m, *options)
+            return plain(*a) if size is None else resized(*a, fid)
+        return self._sequence(frames, outs, pinned, alloc, lambda d: tuple(p.copy() for p in d), run, fallback, check)
+
+    def render_planar_rgba(self, planes, *, bits: int | None = None, out_bits: int | None = None, order: str = "rgba", bleed: int = 0,
+                           skip_uniform_alpha: bool = False, dst=None):
+        """render_rgba() on a planar RGBA frame (w2x_render_rgbap): four 2-D planes of uint8, uint16 (bits=10 / 12 for codes in the low bits) or float32 samples,
+        out_bits independent, as in render_planar(); alpha is straight.  The colour planes are render_planar() of alpha_bleed_planes(planes, bleed), the alpha
+        plane is the G plane of render_planar((A, A, A)), byte for byte; at 8 / 8 bits the planes are render_rgba()'s bytes.  bleed: 0..16 (float32 planes: 0).
+        skip_uniform_alpha: a frame whose alpha plane is one value runs no alpha tiles.  order: "rgba" or "gbra" (ffmpeg's gbrap); the result comes back in the
+        same order.  With dst=None returns the four planes or raises; with dst (four planes, views allowed) returns a bool."""
+        args, out = self._planar_call(planes, None, bits, out_bits, order, dst, "renderPlanarRgba", "rgba")
+        return self._finish(self._L.w2x_render_rgbap(*args, int(bleed), int(bool(skip_uniform_alpha))) if args else 0, out, "render_planar_rgba failed")
+
+    def render_planar_rgba_resized(self, planes, size, *, bits: int | None = None, out_bits: int | None = None, order: str = "rgba", bleed: int = 0,
+                                   skip_uniform_alpha: bool = False, filter: str = "bicubic", dst=None):
+        """render_planar_rgba() with the output resized on the device to size = (rows, cols), each in [input dim, input dim * scaling]
+        (w2x_render_rgbap_resized); colour and alpha are resized separately and straight.  With dst=None returns the planes or raises; with dst a bool."""
+        fid = _filter_id(filter)
+        args, out = self._planar_call(planes, size, bits, out_bits, order, dst, "renderPlanarRgbaResized", "rgba")
+        return self._finish(self._L.w2x_render_rgbap_resized(*args, int(bleed), int(bool(skip_uniform_alpha)), fid), out, "render_planar_rgba_resized failed")
+
+    def render_sequence_planar_rgba(self, frames, size=None, *, bits: int | None = None, out_bits: int | None = None, order: str = "rgba", bleed: int = 0,
+                                    skip_uniform_alpha: bool = False, filter: str = "bicubic", outs=None, pinned: bool = False):
+        """Equally sized planar RGBA frames [(p0, p1, p2, p3), ...] of one depth and one set of options with upload / compute / download overlapped
+        (w2x_render_sequence_rgbap; with size = (rows, cols): w2x_render_sequence_rgbap_resized).  Output i is the bytes of the single call on frame i;
+        skip_uniform_alpha is decided per frame.  Strides, outs and pinned as in render_sequence_planar()."""
+        return self._planar_sequence(frames, size, bits, out_bits, order, filter, outs, pinned, "rgba", (int(bleed), int(bool(skip_uniform_alpha))),
+                                     self._L.w2x_render_sequence_rgbap, self._L.w2x_render_sequence_rgbap_resized, "render_sequence_planar_rgba failed")
+
+    def alpha_bleed_planes_device(self, planes, radius: int, *, bits: int | None = None, order: str = "rgba", words: bool = False):
+        """Test hook (w2x_alpha_bleed_rgbap_device): the device bleed alone on a planar RGBA frame -> the three colour planes the tiles are read from, in R, G, B
+        order; words=True: (planes, (max(key), max(top - key))) - the alpha range the kernel reduced (c_api_rgbap.h)"""
+        idx = _planar_order(order, "rgba")
+        bits = _planar_bits(planes, bits, n=4)
+        src = [planes[k] for k in idx]
+        r, c = src[0].shape
+        out = tuple(np.empty((r, c), src[0].dtype) for _ in range(3))
+        w = (C.c_uint * 2)(0, 0)
+        ok = self._L.w2x_alpha_bleed_rgbap_device(self._h, (C.c_void_p * 4)(*[_data(p) for p in src]), (C.c_size_t * 4)(*[p.strides[0] for p in src]), r, c, bits,
+                                                  int(radius), (C.c_void_p * 3)(*[_data(p) for p in out]), (C.c_size_t * 3)(*[p.strides[0] for p in out]), w)
+        return self._finish(ok, (out, (int(w[0]), int(w[1]))) if words else out, "alpha_bleed_planes_device failed")
 
     def alpha_bleed_device(self, bgra: np.ndarray, radius: int) -> np.ndarray:
         """Test hook (w2x_alpha_bleed_device): the device bleed alone on a uint8 [rows, cols, 4] BGRA frame -> the [rows, cols, 3] BGR frame the tiles are read from"""
@@ -1030,6 +1089,22 @@ def resize_weights(in_size: int, out_size: int, filter: str = "bicubic"):
     if L.w2x_resize_weights(int(in_size), int(out_size), fid, first.ctypes.data, w.ctypes.data, w.size) != taps:
         raise W2xError("w2x_resize_weights failed")
     return first, w
+
+
+def alpha_bleed_planes(planes, radius: int, *, bits: int | None = None, order: str = "rgba"):
+    """The colour bleed of the planar RGBA renders on the host (w2x_alpha_bleed_rgbap): four 2-D uint8 or uint16 planes (bits=10 / 12 for codes in the low bits),
+    radius 0..16 -> the three colour planes R, G, B with every code clamped to 2^bits - 1 and the colours of the visible pixels (clamped alpha > 0) spread
+    under the others; integer and exact (tiles.h alpha_bleed_planes)."""
+    idx = _planar_order(order, "rgba")
+    bits = _planar_bits(planes, bits, n=4)
+    if bits == 32:
+        raise ValueError("Colour bleed takes integer samples.")
+    src = [planes[k] for k in idx]
+    out = tuple(np.empty(src[0].shape, src[0].dtype) for _ in range(3))
+    if not lib().w2x_alpha_bleed_rgbap((C.c_void_p * 4)(*[_data(p) for p in src]), (C.c_size_t * 4)(*[p.strides[0] for p in src]), src[0].shape[0], src[0].shape[1], bits,
+                                       int(radius), (C.c_void_p * 3)(*[_data(p) for p in out]), (C.c_size_t * 3)(*[p.strides[0] for p in out])):
+        raise ValueError(f"alpha_bleed_planes refused planes of {src[0].shape} at radius {radius}")
+    return out
 
 
 def alpha_bleed(bgr: np.ndarray, alpha: np.ndarray, radius: int) -> np.ndarray:
