@@ -116,7 +116,8 @@ int w2x_render_sequence_yuv(w2x_engine* e, const void* const* src_planes, const 
  * I444: rows x cols; NV12: planes[1] holds (rows + 1) / 2 rows of 2 * ((cols + 1) / 2) samples U, V, U, V, ... and planes[2] / steps[2] are ignored (may be NULL /
  * 0); NV12 at 10 bits is P010: each uint16 of Y and UV carries its code in the HIGH 10 bits (read v >> 6, written code << 6; the planar layouts keep the low 10).
  * With both layouts W2X_YUV_I420 the bytes are w2x_render_yuv's.  Unknown layouts, a missing plane or a step shorter than the layout's row return 0 through
- * the message callback, with whatever w2x_render_yuv refuses.  (The resized calls below take I420 only.) */
+ * the message callback, with whatever w2x_render_yuv refuses.  (The resized calls below take I420 only; resized frames of the other layouts:
+ * c_api_yuv_resized.h.) */
 int w2x_render_yuv_layout(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits, int src_layout,
                           void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int dst_layout, int matrix, int range);
 int w2x_render_sequence_yuv_layout(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits, int src_layout,

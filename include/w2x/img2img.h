@@ -120,9 +120,12 @@ public:
     // the two independent, odd sizes allowed.  The frame is read as renderYuv() reads it, the fp32 canvas is formed and resized as renderResized() does it
     // (not clamped before the resize: the filter's overshoot is part of the result), and the resized RGB is encoded as renderYuv() encodes the canvas, at
     // dst.bits.  At dst = rows*scaling x cols*scaling the bytes are renderYuv()'s.  Other sizes and whatever renderYuv() refuses: false (message callback).
-    // I420 frames only, both sides (resample_yuv_kernel encodes 4:2:0): any other layout: false.
+    // Every layout on either side, source and destination independent like the depths: the resized RGB is encoded as renderYuv() encodes the canvas for
+    // dst.layout - I444 each pixel's own chroma, I422 the chroma filter along the row, NV12 / P010 I420's samples interleaved -, and the Y plane is the same
+    // bytes whatever dst.layout is.
     bool renderYuvResized(const YuvImage& src, YuvImage& dst, YuvFormat format, ResizeFilter filter = ResizeFilter::Bicubic);
-    // renderSequenceYuv() with every frame resized like renderYuvResized() to dsts[i].rows x dsts[i].cols (one size and one pair of depths for the sequence)
+    // renderSequenceYuv() with every frame resized like renderYuvResized() to dsts[i].rows x dsts[i].cols (one size, one pair of depths and one pair of layouts
+    // for the sequence)
     bool renderSequenceYuvResized(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, ResizeFilter filter = ResizeFilter::Bicubic);
     // Extension: render() on 8-bit interleaved BGRA frames (CV_8UC4, what cv::imread(IMREAD_UNCHANGED) hands out; step >= cols * 4; dst rows*scaling x
     // cols*scaling) in one call: one upload of 4 bytes per pixel, the colour bleed on the device, the frame's N colour tiles and N alpha tiles (the alpha plane

@@ -9,7 +9,9 @@ The device time of gather_yuv_kernel / compose_yuv_kernel comes from a separate 
 --bytes prints the bytes each path moves across PCIe per frame.  Not part of bench.py.
 
 --in-layout / --out-layout {i420,i422,i444,nv12} give the YUV modes' frames another layout on either side (renderSequenceYuv through
-w2x_render_sequence_yuv_layout; with both i420, the default, the call is w2x_render_sequence_yuv as before); not with --outsize."""
+w2x_render_sequence_yuv_layout; with both i420, the default, the call is w2x_render_sequence_yuv as before).  With --outsize the call is
+w2x_render_sequence_yuv_layout_resized (with both i420 w2x_render_sequence_yuv_resized as before): `--outsize 3840x2160 --in-layout nv12 --out-layout
+nv12 --modes 8/8` is the nv12 -> nv12 pair of profiles/yuv_resize_layouts/."""
 from __future__ import annotations
 
 import argparse
@@ -53,8 +55,6 @@ def main() -> int:
     resized = (OW, OH) != (W * S, H * S)
     LIN, LOUT = a.in_layout, a.out_layout
     with_layout = (LIN, LOUT) != ("i420", "i420")
-    if with_layout and resized:
-        raise SystemExit("--in-layout / --out-layout: not with --outsize (resized YUV frames are i420)")
     if a.bytes:
         print(json.dumps({m: frame_bytes(m, OW, OH, LIN, LOUT) for m in a.modes.split(",")}))
         return 0
@@ -122,7 +122,8 @@ def main() -> int:
             def region():
                 args = (eng._h, sp, ss, H, W, bits, dp, ds, OH, OW, bits, n, 1, 0)
                 if with_layout:
-                    if not eng._L.w2x_render_sequence_yuv_layout(*args[:6], pkg.YUV_LAYOUTS[LIN], *args[6:11], pkg.YUV_LAYOUTS[LOUT], *args[11:]):
+                    largs = (*args[:6], pkg.YUV_LAYOUTS[LIN], *args[6:11], pkg.YUV_LAYOUTS[LOUT], *args[11:])
+                    if not (eng._L.w2x_render_sequence_yuv_layout_resized(*largs, 0) if resized else eng._L.w2x_render_sequence_yuv_layout(*largs)):
                         raise SystemExit("render_sequence_yuv_layout failed: " + eng.last_error())
                     return
                 if not (eng._L.w2x_render_sequence_yuv_resized(*args, 0) if resized else eng._L.w2x_render_sequence_yuv(*args)):

@@ -3,6 +3,7 @@
 #include "../../include/w2x/c_api_gray.h"
 #include "../../include/w2x/c_api_planar.h"
 #include "../../include/w2x/c_api_rgbap.h"
+#include "../../include/w2x/c_api_yuv_resized.h"
 #include <mutex>
 
 #include <cstring>
@@ -248,6 +249,31 @@ int w2x_render_sequence_yuv_resized(w2x_engine* e, const void* const* src_planes
     w2x::ResizeFilter f;
     if (!sequence_ok(e, count, src_planes, dst_planes) || !resize_filter(e, filter, "w2x_render_sequence_yuv_resized", f)) return 0;
     YuvSequence q = yuv_sequence(src_planes, src_steps, rows, cols, src_bits, W2X_YUV_I420, dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, W2X_YUV_I420, count);
+    return e->engine.renderSequenceYuvResized(q.src.data(), q.dst.data(), count, yuv_format(matrix, range), f) ? 1 : 0;
+}
+// resized YUV frames of any layout (include/w2x/c_api_yuv_resized.h).  An unknown layout is refused here like an unknown filter, in the engine's words: both can
+// be told without a loaded engine
+static bool yuv_layouts(w2x_engine* e, int src_layout, int dst_layout, const char* who) {
+    const bool src_ok = src_layout >= W2X_YUV_I420 && src_layout <= W2X_YUV_NV12;
+    if (src_ok && dst_layout >= W2X_YUV_I420 && dst_layout <= W2X_YUV_NV12) return true;
+    if (e->msg) e->msg((int)w2x::Severity::error, (std::string("[") + who + "@0] Unknown YUV layout " + std::to_string(src_ok ? dst_layout : src_layout) + ".").c_str(), e->msg_user);
+    return false;
+}
+int w2x_render_yuv_layout_resized(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits, int src_layout,
+                                  void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int dst_layout, int matrix, int range,
+                                  int filter) {
+    w2x::ResizeFilter f;
+    if (!e || !resize_filter(e, filter, "w2x_render_yuv_layout_resized", f) || !yuv_layouts(e, src_layout, dst_layout, "w2x_render_yuv_layout_resized")) return 0;
+    w2x::YuvImage d = yuv_image(dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, dst_layout);
+    return e->engine.renderYuvResized(yuv_image(src_planes, src_steps, rows, cols, src_bits, src_layout), d, yuv_format(matrix, range), f) ? 1 : 0;
+}
+int w2x_render_sequence_yuv_layout_resized(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits, int src_layout,
+                                           void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int dst_layout, int count,
+                                           int matrix, int range, int filter) {
+    w2x::ResizeFilter f;
+    if (!sequence_ok(e, count, src_planes, dst_planes) || !resize_filter(e, filter, "w2x_render_sequence_yuv_layout_resized", f) ||
+        !yuv_layouts(e, src_layout, dst_layout, "w2x_render_sequence_yuv_layout_resized")) return 0;
+    YuvSequence q = yuv_sequence(src_planes, src_steps, rows, cols, src_bits, src_layout, dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, dst_layout, count);
     return e->engine.renderSequenceYuvResized(q.src.data(), q.dst.data(), count, yuv_format(matrix, range), f) ? 1 : 0;
 }
 int w2x_render_rgba(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, size_t dst_step, int bleed, int skip_uniform_alpha) {

@@ -329,8 +329,8 @@ struct Img2Img::Impl {
     std::deque<ResizeTables> rs_tables;
     // YUV frames (renderYuv / renderSequenceYuv): d_frame / d_out hold the planes of in_layout / out_layout (yuv_layout; kernels.h kYuvI420 ..) and the gather /
     // compose launches are gather_yuv_kernel / compose_yuv_kernel (4:4:4 output: compose_yuv444_kernel); `key` tells the captured passes of each input format -
-    // depth, range, matrix, layout - apart.  Resized (renderYuvResized) the frame ends with compose_canvas_kernel and resample_yuv_kernel, and d_out holds planes
-    // of the target size.
+    // depth, range, matrix, layout - apart.  Resized (renderYuvResized) the frame ends with compose_canvas_kernel and the resample kernel of out_layout
+    // (launch_resample_yuv: resample_yuv_kernel, k_resample_yuv.hip for I422 / I444 / NV12), and d_out holds out_layout's planes of the target size.
     struct YuvJob { YuvCoefs in, out; int in_bits = 8, out_bits = 8, key = 0, in_layout = kYuvI420, out_layout = kYuvI420; };
     // RGBA frames (renderRgba, renderRgbaResized, renderSequenceRgba*): d_frame holds the uploaded BGRA frame, alpha_bleed_kernel writes the BGR frame and the alpha
     // plane the passes gather from (gather_rgba_kernel), d_minmax receives max(A) and max(255 - A), read back into the page-locked h_minmax behind the kernel.  The
@@ -1398,10 +1398,10 @@ struct Img2Img::Impl {
                 hipAssert(launch_resample_planar_rgba(p, on));
                 break;
             }
-            case Job::YUV: {                                          // the planes of the target size (resized YUV frames are I420)
+            case Job::YUV: {                                          // the planes of job.yuv.out_layout at the target size
                 ResampleYuvParams p;
                 resample_base(p);
-                p.dst = yuv_layout(d_out, p.outH, p.outW, job.yuv.out_bits, kYuvI420); p.k = job.yuv.out;
+                p.dst = yuv_layout(d_out, p.outH, p.outW, job.yuv.out_bits, job.yuv.out_layout); p.k = job.yuv.out;
                 hipAssert(launch_resample_yuv(p, on));
                 break;
             }
@@ -1513,7 +1513,7 @@ struct Img2Img::Impl {
         }
         return call_grid(c);
     }
-    // The YUV calls: one size, one pair of depths and one pair of layouts (srcs[0]'s, dsts[0]'s) for the sequence; resized frames are I420 on both sides.
+    // The YUV calls: one size, one pair of depths and one pair of layouts (srcs[0]'s, dsts[0]'s) for the sequence, resized or not.
     std::string yuv_check(const YuvImage* srcs, const YuvImage* dsts, int count, YuvFormat format, int resizeFilter, FrameCall& c) const {
         const int matrix = (int)format.matrix, range = (int)format.range;
         if (matrix < 0 || matrix > 2) return "Unknown YUV matrix " + std::to_string(matrix) + ".";
@@ -1524,7 +1524,6 @@ struct Img2Img::Impl {
         const int in_layout = (int)srcs[0].layout, out_layout = (int)dsts[0].layout;
         if (in_layout < kYuvI420 || in_layout > kYuvNV12 || out_layout < kYuvI420 || out_layout > kYuvNV12)
             return "Unknown YUV layout " + std::to_string(in_layout < kYuvI420 || in_layout > kYuvNV12 ? in_layout : out_layout) + ".";
-        if (resizeFilter >= 0 && (in_layout != kYuvI420 || out_layout != kYuvI420)) return "Resized YUV frames must be I420 (yuv420p / yuv420p10le) on both sides.";
         if (const std::string why = call_target(resizeFilter, dsts[0], rows, cols, true, c); !why.empty()) return why;
         // every plane of the layout present (NV12: Y and UV), with a step that holds its row
         auto planes_ok = [](const YuvImage& f) {
@@ -2443,7 +2442,8 @@ bool Img2Img::renderSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count,
 
 // renderYuv() with the canvas resized to dst.rows x dst.cols before it is encoded: the frame's tiles from its planes (gather_yuv_kernel),
 // compose_canvas_kernel (fp32 canvas, not clamped), resample_yuv_kernel (k_resample.hip: the resize of renderResized, then clamp, Y per pixel, chroma of
-// the filtered RGB), the download of the target's planes.  At the scaled size it is renderYuv().
+// the filtered RGB; dst.layout I422, I444, NV12: the kernels of k_resample_yuv.hip), the download of the target's planes.  At the scaled size it is
+// renderYuv().
 bool Img2Img::renderYuvResized(const YuvImage& src, YuvImage& dst, YuvFormat format, ResizeFilter filter) {
     return runSequenceYuv(&src, &dst, 1, format, filter_id(filter), "renderYuvResized");
 }

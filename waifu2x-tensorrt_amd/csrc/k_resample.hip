@@ -8,7 +8,7 @@
 // stores the four pixels' 12 bytes as three dwords (compose's fast-path store) where the row allows.  The tap tables come from the host
 // (tiles.h resize_taps): per output column its first input column and kx weights, per output row its first input row and ky weights;
 // weights past the taps an output has are 0, and the loops stop at the canvas edge, so no read leaves the canvas.
-// resample_yuv_kernel, further down, is the same resize with a YUV 4:2:0 output (renderYuvResized).
+// resample_yuv_kernel, further down, is the same resize with a YUV 4:2:0 output (renderYuvResized); the other YUV layouts: k_resample_yuv.hip.
 // LDS: at a factor of 4 with bicubic taps (ky = 17) rows_max <= 15 * 4 + 1 + 17 = 78 rows, 3 * 78 * 256 B = 58.5 KiB: two workgroups per CU.
 #include "kernels.h"
 
@@ -273,6 +273,7 @@ hipError_t launch_resample_yuv(const ResampleYuvParams& p, hipStream_t s) {
     constexpr int kMaxRows = 104;                                        // as launch_resample
     const int lds = 3 * p.rows_max * kYP * (int)sizeof(float);
     if (p.rows_max <= 0 || p.rows_max > kMaxRows || p.dst.rows != p.outH || p.dst.cols != p.outW || (p.dst.bits != 8 && p.dst.bits != 10)) return hipErrorInvalidValue;
+    if (p.dst.layout != kYuvI420) return launch_resample_yuv_layout(p, s);   // I422, I444, NV12: k_resample_yuv.hip
     static unsigned lds_done = 0;
     hipError_t e = ensure_dynamic_lds((const void*)resample_yuv_kernel, 3 * kMaxRows * kYP * (int)sizeof(float), lds_done);
     if (e != hipSuccess) return e;

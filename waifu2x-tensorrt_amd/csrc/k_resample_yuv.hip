@@ -1,0 +1,347 @@
+// Resized YUV output in the layouts beside I420 (renderYuvResized with dst.layout I422, I444 or NV12): resample_kernel's resize of the fp32 RGB
+// canvas - its 16 x 64 tile, its tap tables, its pass 1 and rows_max - with the encoding of compose_yuv_kernel / compose_yuv444_kernel behind it.  The canvas
+// is resized unclamped; R, G, B are clamped to [0, 1] after the resize and coded with the compose kernels' expressions in their order.  resample_yuv_kernel
+// (k_resample.hip) stays the I420 kernel; launch_resample_yuv hands every other layout to launch_resample_yuv_layout below.
+//
+//   resample_yuv444_kernel   resample_kernel's two passes (pixel_device.h resample_pass1 / resample_pass2: a thread per four pixels of a row, float4 LDS reads,
+//                            no halo); each pixel codes Y, Cb and Cr from its own clamped colour.  4 samples per plane and store.
+//   resample_yuv422_kernel   the same shape, two chroma sites per thread: site j filters columns 2j - 1, 2j, 2j + 1 of its own row (1/4, 1/2, 1/4, indices clamped
+//                            to the frame).  Column 2j - 1 of a thread's first site is the last column of the lane on its left; the first thread of a tile row
+//                            takes it from the halo, output column ox0 - 1 (clamped at 0), which pass 1 filters as a 65th column.
+//   resample_yuv_nv12_kernel resample_yuv_kernel's arithmetic in its order, U and V stored interleaved in plane 1, every code << 6 at 10 bits (P010).
+#include "pixel_device.h"
+
+#include <type_traits>
+
+namespace w2x {
+namespace {
+
+// The encoding expressions, each rounding stated (no contraction left to the compiler): the forms resample_yuv_kernel has as compiled for gfx950, which the byte
+// equalities with it rest on - the Y plane of every layout is I420's, NV12 holds I420's samples.  Its listing fuses the last product of Y' = kr R + kg G + kb B on
+// the odd rows of the frame (the second row of a chroma site) and rounds it on its own on the even rows; the chroma expressions are fused throughout.
+__device__ __forceinline__ unsigned yuv_code(float off, float scale, float v, int maxcode) { return (unsigned)min(max(__float2int_rn(__fmaf_rn(scale, v, off)), 0), maxcode); }
+__device__ __forceinline__ float luma_fused(const YuvCoefs& k, float r, float g, float b) { return __fmaf_rn(k.kb, b, __fmaf_rn(k.kr, r, __fmul_rn(k.kg, g))); }
+__device__ __forceinline__ float luma_even_row(const YuvCoefs& k, float r, float g, float b) { return __fadd_rn(__fmul_rn(k.kb, b), __fmaf_rn(k.kr, r, __fmul_rn(k.kg, g))); }
+__device__ __forceinline__ float luma_of_row(const YuvCoefs& k, int Y, float r, float g, float b) { return (Y & 1) ? luma_fused(k, r, g, b) : luma_even_row(k, r, g, b); }
+// a chroma site's colour from the columns 2j - 1, 2j, 2j + 1 (1/4, 1/2, 1/4)
+__device__ __forceinline__ float site_filter(float left, float mid, float right) { return __fmaf_rn(0.25f, right, __fmaf_rn(0.25f, left, __fmul_rn(0.5f, mid))); }
+__device__ __forceinline__ float chroma_of(float c, float y, float div) { return __fmul_rn(__fsub_rn(c, y), div); }
+
+// Four consecutive codes of one plane's row from column X (a multiple of 4): np == 4 and an aligned address leave as one store of 4 (10 bits: 8) bytes, a run
+// cut by the right edge (or a caller's unaligned rows) sample by sample
+__device__ __forceinline__ void store_codes4(uint8_t* row, int X, int np, const unsigned (&q)[4], bool wide) {
+    if (!wide) {
+        uint8_t* d = row + X;
+        if (np == 4 && (((size_t)d) & 3) == 0) *(unsigned*)d = q[0] | q[1] << 8 | q[2] << 16 | q[3] << 24;
+        else for (int k = 0; k < np; ++k) d[k] = (uint8_t)q[k];
+    } else {
+        uint16_t* d = (uint16_t*)row + X;
+        if (np == 4 && (((size_t)d) & 7) == 0) *(uint2*)d = make_uint2(q[0] | q[1] << 16, q[2] | q[3] << 16);
+        else for (int k = 0; k < np; ++k) d[k] = (uint16_t)q[k];
+    }
+}
+
+// ---- 4:4:4.  LDS [3][rows_max][kRsCols] fp32: resample_kernel's, 58.5 KiB at a factor of 4 with bicubic taps, two workgroups per CU
+__global__ __launch_bounds__(kRsThreads) void resample_yuv444_kernel(const ResampleYuvParams p) {
+    extern __shared__ float h[];
+    const int r0 = resample_pass1<3>(p, h);
+    __syncthreads();
+    float4v a[3];
+    int X, Y, np;
+    if (!resample_pass2<3>(p, h, r0, a, X, Y, np)) return;
+    const YuvCoefs& k = p.k;
+    unsigned yc[4], uc[4], vc[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {
+        const float o0 = sat01(a[0][q]), o1 = sat01(a[1][q]), o2 = sat01(a[2][q]);
+        const float Yn = luma_of_row(k, Y, o0, o1, o2);
+        yc[q] = yuv_code(k.y_off, k.y_scale, Yn, k.maxcode);
+        uc[q] = yuv_code(k.c_off, k.c_scale, chroma_of(o2, Yn, k.cb_div), k.maxcode);
+        vc[q] = yuv_code(k.c_off, k.c_scale, chroma_of(o0, Yn, k.cr_div), k.maxcode);
+    }
+    const bool wide = p.dst.bits > 8;
+    store_codes4(p.dst.p[0] + (size_t)Y * p.dst.step[0], X, np, yc, wide);
+    store_codes4(p.dst.p[1] + (size_t)Y * p.dst.step[1], X, np, uc, wide);
+    store_codes4(p.dst.p[2] + (size_t)Y * p.dst.step[2], X, np, vc, wide);
+}
+
+// ---- 4:2:2.  LDS: [3][rows_max][kRsCols] fp32, resample_kernel's image at its pitch of 64 dwords, and behind it the halo column as [3][rows_max].
+// Banks (ds_read_b128: address / 4 mod 64 within groups of 16 lanes that hold eight lanes of one output row and eight of the next): at a pitch of 64 the 16 lanes
+// of a row read the row's 16 slots of 16 bytes whichever input row each output row starts at, so the reads are conflict free as resample_kernel's are.  A pitch
+// of 68, which would keep the halo inside the row, shifts a row's slots by its row number: two output rows whose input rows lie d apart then share 8 - |d mod 16|
+// slots in a group - a two-way conflict at every factor but one.  Hence the halo lies apart.  Pass 1 writes 65 values per input row from consecutive lanes
+// (ds_write_b32: address / 4 mod 32 within 32 lanes): 32 lanes hold at most one row end, so their image addresses are 32 consecutive dwords less one gap and
+// the one halo dword falls on a bank in use - two lanes on one bank at most, which a 4-byte store hides.  The halo is read by the first lane of each tile row
+// (4 lanes of a wave, ds_read_b32), rows a few dwords apart.
+// At a factor of 4 with bicubic taps rows_max <= 78: 3 * 78 * 65 * 4 B = 59.4 KiB, two workgroups per CU.
+__global__ __launch_bounds__(kRsThreads) void resample_yuv422_kernel(const ResampleYuvParams p) {
+    extern __shared__ __attribute__((aligned(16))) float h422[];   // (the alignment stated: pass 2 reads 16 bytes per lane and plane, ds_read_b128)
+    float* const h = h422;
+    const int rm = p.rows_max;
+    float* const halo = h + 3 * rm * kRsCols;
+    const int ox0 = blockIdx.x * kRsCols, oy0 = blockIdx.y * kRsRows;
+    const int tw = min(kRsCols, p.outW - ox0), th = min(kRsRows, p.outH - oy0);
+    const int r0 = p.fy[oy0];
+    const int nr = min(p.inH, p.fy[oy0 + th - 1] + p.ky) - r0;           // <= rows_max (resample_rows_max)
+    const size_t plane = (size_t)p.inW * p.inH;
+    // pass 1: input rows [r0, r0 + nr) filtered horizontally onto the tile's output columns and onto column ox0 - 1
+    for (int i = threadIdx.x; i < nr * (kRsCols + 1); i += kRsThreads) {
+        const int r = i / (kRsCols + 1), c = i % (kRsCols + 1);
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+        if (c < tw || c == kRsCols) {
+            const int X = c == kRsCols ? max(ox0 - 1, 0) : ox0 + c, f = p.fx[X];
+            const int n = min(p.kx, p.inW - f);
+            const float* w = p.wx + (size_t)X * p.kx;
+            const float* s = p.canvas + (size_t)(r0 + r) * p.inW + f;
+            for (int t = 0; t < n; ++t) {
+                const float wk = w[t];
+                a0 += wk * s[t]; a1 += wk * s[plane + t]; a2 += wk * s[2 * plane + t];
+            }
+        }
+        if (c == kRsCols) { halo[r] = a0; halo[rm + r] = a1; halo[2 * rm + r] = a2; }
+        else { h[(0 * rm + r) * kRsCols + c] = a0; h[(1 * rm + r) * kRsCols + c] = a1; h[(2 * rm + r) * kRsCols + c] = a2; }
+    }
+    __syncthreads();
+    // pass 2: four pixels = two chroma sites of one row per thread.  No lane leaves before the cross-lane moves below: lanes outside the frame carry zeros.
+    const YuvCoefs& k = p.k;
+    const int ty = threadIdx.x / (kRsCols / 4), cg = threadIdx.x % (kRsCols / 4);
+    const int Y = oy0 + ty, X = ox0 + 4 * cg;
+    const bool active = Y < p.outH && X < p.outW;
+    const int np = active ? min(4, p.outW - X) : 0;
+    float4v a[3] = {{0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}, {0.f, 0.f, 0.f, 0.f}};
+    float hl[3] = {0.f, 0.f, 0.f};                                        // column ox0 - 1 of the row: the first lane of a tile row
+    if (active) {
+        const int f = p.fy[Y];
+        const int n = min(p.ky, p.inH - f);
+        const float* w = p.wy + (size_t)Y * p.ky;
+        for (int t = 0; t < n; ++t) {
+            const float wk = w[t];
+            const int r = f - r0 + t;
+#pragma unroll
+            for (int e = 0; e < 3; ++e) a[e] += wk * *(const float4v*)&h[(e * rm + r) * kRsCols + 4 * cg];
+        }
+        if (cg == 0)
+            for (int t = 0; t < n; ++t) {
+                const float wk = w[t];
+#pragma unroll
+                for (int e = 0; e < 3; ++e) hl[e] += wk * halo[e * rm + f - r0 + t];
+            }
+    }
+    float o[4][3];
+#pragma unroll
+    for (int q = 0; q < 4; ++q)
+#pragma unroll
+        for (int e = 0; e < 3; ++e) o[q][e] = sat01(a[e][q]);
+    unsigned yc[4];
+#pragma unroll
+    for (int q = 0; q < 4; ++q) yc[q] = yuv_code(k.y_off, k.y_scale, luma_of_row(k, Y, o[q][0], o[q][1], o[q][2]), k.maxcode);
+    unsigned uc[2], vc[2];
+#pragma unroll
+    for (int s = 0; s < 2; ++s) {
+        float f[3];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            float left;
+            if (s == 0) {
+                const float from_left = __shfl_up(o[3][e], 1);            // (the lane on the left is of the same row for every cg > 0)
+                left = cg ? from_left : sat01(hl[e]);
+            } else left = o[1][e];
+            const float right = 2 * s + 1 < np ? o[2 * s + 1][e] : o[2 * s][e];   // column 2j + 1 clamped to the frame (odd widths)
+            f[e] = site_filter(left, o[2 * s][e], right);
+        }
+        const float Yn = luma_fused(k, f[0], f[1], f[2]);
+        uc[s] = yuv_code(k.c_off, k.c_scale, chroma_of(f[2], Yn, k.cb_div), k.maxcode);
+        vc[s] = yuv_code(k.c_off, k.c_scale, chroma_of(f[0], Yn, k.cr_div), k.maxcode);
+    }
+    // chroma stores: the two sites of an odd lane go out through the even lane on its left where the pair's eight pixels are whole and its rows are aligned
+    const unsigned uu = uc[0] | uc[1] << 16, vv = vc[0] | vc[1] << 16;
+    const unsigned nu = __shfl_down(uu, 1), nv = __shfl_down(vv, 1);
+    if (!active) return;
+    const bool wide = p.dst.bits > 8;
+    const int sh = wide ? 1 : 0;                                           // log2 bytes per sample
+    store_codes4(p.dst.p[0] + (size_t)Y * p.dst.step[0], X, np, yc, wide);
+    uint8_t* const rowu = p.dst.p[1] + (size_t)Y * p.dst.step[1];
+    uint8_t* const rowv = p.dst.p[2] + (size_t)Y * p.dst.step[2];
+    const int Xr = ox0 + 4 * (cg & ~1);                                    // the pair's first pixel, a multiple of 8: its first site is Xr / 2
+    const size_t cmask = wide ? 7 : 3;
+    const bool packed = Xr + 8 <= p.outW && ((((size_t)rowu + ((size_t)(Xr >> 1) << sh)) | ((size_t)rowv + ((size_t)(Xr >> 1) << sh))) & cmask) == 0;
+    if (packed) {
+        if (cg & 1) return;
+        if (!wide) {
+            *(unsigned*)(rowu + (Xr >> 1)) = (uu & 0xff) | (uu >> 16) << 8 | (nu & 0xff) << 16 | (nu >> 16) << 24;
+            *(unsigned*)(rowv + (Xr >> 1)) = (vv & 0xff) | (vv >> 16) << 8 | (nv & 0xff) << 16 | (nv >> 16) << 24;
+        } else {
+            *(uint2*)(rowu + Xr) = make_uint2(uu, nu);
+            *(uint2*)(rowv + Xr) = make_uint2(vv, nv);
+        }
+        return;
+    }
+    const int ns = (np + 1) >> 1, j = X >> 1;
+    if (!wide) {
+        for (int s = 0; s < ns; ++s) { rowu[j + s] = (uint8_t)(s ? uc[1] : uc[0]); rowv[j + s] = (uint8_t)(s ? vc[1] : vc[0]); }
+    } else {
+        for (int s = 0; s < ns; ++s) { ((uint16_t*)rowu)[j + s] = (uint16_t)(s ? uc[1] : uc[0]); ((uint16_t*)rowv)[j + s] = (uint16_t)(s ? vc[1] : vc[0]); }
+    }
+}
+
+// ---- NV12 / P010: resample_yuv_kernel (k_resample.hip) restated - pass 1, the vertical filters, the clamps, the Y and the Cb / Cr expressions and their order
+// are its own, so the samples are I420's; only the stores differ: U and V of a site side by side in plane 1 and, at 10 bits, every code in the high bits.
+// LDS as there: [3][rows_max][kYP], kYP = 66 (float2 reads of pass 2 8-byte aligned, the halo at column 64), 60.3 KiB at a factor of 4 with bicubic taps.
+constexpr int kYP = kRsCols + 2;
+typedef float float2v __attribute__((ext_vector_type(2)));
+
+__global__ __launch_bounds__(kRsThreads) void resample_yuv_nv12_kernel(const ResampleYuvParams p) {
+    extern __shared__ float h[];                                          // [3][rows_max][kYP]: columns 0 .. 63 the tile's, 64 the halo
+    const int ox0 = blockIdx.x * kRsCols, oy0 = blockIdx.y * kRsRows;
+    const int tw = min(kRsCols, p.outW - ox0), th = min(kRsRows, p.outH - oy0);
+    const int r0 = p.fy[oy0];
+    const int nr = min(p.inH, p.fy[oy0 + th - 1] + p.ky) - r0;           // <= rows_max (resample_rows_max)
+    const size_t plane = (size_t)p.inW * p.inH;
+    const int rm = p.rows_max;
+    // pass 1: input rows [r0, r0 + nr) filtered horizontally onto the tile's output columns and onto column ox0 - 1
+    for (int i = threadIdx.x; i < nr * (kRsCols + 1); i += kRsThreads) {
+        const int r = i / (kRsCols + 1), c = i % (kRsCols + 1);
+        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
+        if (c < tw || c == kRsCols) {
+            const int X = c == kRsCols ? max(ox0 - 1, 0) : ox0 + c, f = p.fx[X];
+            const int n = min(p.kx, p.inW - f);
+            const float* w = p.wx + (size_t)X * p.kx;
+            const float* s = p.canvas + (size_t)(r0 + r) * p.inW + f;
+            for (int t = 0; t < n; ++t) {
+                const float wk = w[t];
+                a0 += wk * s[t]; a1 += wk * s[plane + t]; a2 += wk * s[2 * plane + t];
+            }
+        }
+        h[(0 * rm + r) * kYP + c] = a0; h[(1 * rm + r) * kYP + c] = a1; h[(2 * rm + r) * kYP + c] = a2;
+    }
+    __syncthreads();
+    // pass 2: a chroma site per thread.  No lane leaves before the cross-lane moves below: lanes outside the frame carry zeros.
+    const YuvCoefs& k = p.k;
+    const int lane = threadIdx.x % 64, ci = threadIdx.x / 32, cj = threadIdx.x % 32;
+    const int Ya = oy0 + 2 * ci, X0 = ox0 + 2 * cj;
+    const bool active = Ya < p.outH && X0 < p.outW;
+    const bool has_b = Ya + 1 < p.outH, has_r = X0 + 1 < p.outW;          // odd sizes: row 2i + 1 / column 2j + 1 clamp to the frame
+    // output row Y filtered vertically at LDS columns col .. col + N - 1, per plane
+    auto vertical = [&](int Y, int col, auto* acc) {
+        const int f = p.fy[Y];
+        const int n = min(p.ky, p.inH - f);
+        const float* w = p.wy + (size_t)Y * p.ky;
+        const float* s = h + (f - r0) * kYP + col;
+        for (int t = 0; t < n; ++t) {
+            const float wk = w[t];
+#pragma unroll
+            for (int e = 0; e < 3; ++e) acc[e] += wk * *(const std::remove_reference_t<decltype(acc[0])>*)&s[(e * rm + t) * kYP];
+        }
+    };
+    float2v a[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}}, b[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};   // rows 2i, 2i + 1: columns 2j, 2j + 1 of R, G, B
+    if (active) {
+        vertical(Ya, 2 * cj, a);
+        if (has_b) vertical(Ya + 1, 2 * cj, b);
+    }
+    float halo[3] = {0.f, 0.f, 0.f};                                      // lanes 0 .. 3: column ox0 - 1 of the wave's four luma rows
+    if (lane < 4 && oy0 + 4 * (int)(threadIdx.x / 64) + lane < p.outH) vertical(oy0 + 4 * (int)(threadIdx.x / 64) + lane, kRsCols, halo);
+    float vl[3], vr[3], left[3];                                          // the site's columns 2j, 2j + 1 and 2j - 1, the two rows averaged
+    unsigned ya[2], yb[2];
+    {
+        float oa[2][3], ob[2][3];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            oa[0][e] = sat01(a[e][0]); oa[1][e] = sat01(a[e][1]);
+            ob[0][e] = has_b ? sat01(b[e][0]) : oa[0][e]; ob[1][e] = has_b ? sat01(b[e][1]) : oa[1][e];
+        }
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            ya[q] = yuv_code(k.y_off, k.y_scale, luma_even_row(k, oa[q][0], oa[q][1], oa[q][2]), k.maxcode);
+            yb[q] = yuv_code(k.y_off, k.y_scale, luma_fused(k, ob[q][0], ob[q][1], ob[q][2]), k.maxcode);
+        }
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            vl[e] = __fmul_rn(0.5f, __fadd_rn(oa[0][e], ob[0][e]));
+            vr[e] = has_r ? __fmul_rn(0.5f, __fadd_rn(oa[1][e], ob[1][e])) : vl[e];
+        }
+    }
+#pragma unroll
+    for (int e = 0; e < 3; ++e) {
+        const float hc = sat01(halo[e]);
+        const float ha = __shfl(hc, 2 * (lane / 32)), hb = __shfl(hc, 2 * (lane / 32) + 1);
+        const float from_left = __shfl_up(vr[e], 1);
+        left[e] = cj ? from_left : __fmul_rn(0.5f, __fadd_rn(ha, has_b ? hb : ha));
+    }
+    const bool wide = p.dst.bits > 8;
+    const int up = wide ? 6 : 0;                                           // P010: the code in the high ten bits
+    unsigned uv;                                                          // U | V << 8 (10 bits: << 16), as the pair lies in plane 1
+    {
+        float f[3];
+#pragma unroll
+        for (int e = 0; e < 3; ++e) f[e] = site_filter(left[e], vl[e], vr[e]);
+        const float Y = luma_fused(k, f[0], f[1], f[2]);
+        uv = (yuv_code(k.c_off, k.c_scale, chroma_of(f[2], Y, k.cb_div), k.maxcode) | yuv_code(k.c_off, k.c_scale, chroma_of(f[0], Y, k.cr_div), k.maxcode) << (wide ? 16 : 8)) << up;
+    }
+    // stores: the run of four sites the lane belongs to goes out through its first lane where the run is whole and its rows are aligned
+    const int sh = wide ? 1 : 0;                                           // log2 bytes per sample
+    const int Xr = ox0 + 2 * (cj & ~3), ic = Ya >> 1;
+    uint8_t* const rowa = p.dst.p[0] + (size_t)Ya * p.dst.step[0];
+    uint8_t* const rowb = rowa + p.dst.step[0];
+    uint8_t* const rowc = p.dst.p[1] + (size_t)ic * p.dst.step[1];        // U, V, U, V, ...: site j at samples 2j, 2j + 1
+    const size_t ymask = wide ? 15 : 7;
+    const bool packed = Xr + 8 <= p.outW &&
+                        ((((size_t)rowa + ((size_t)Xr << sh)) | p.dst.step[0]) & ymask) == 0 &&
+                        (((size_t)rowc + ((size_t)Xr << sh)) & ymask) == 0;
+    const unsigned wa = (ya[0] | ya[1] << (wide ? 16 : 8)) << up, wb = (yb[0] | yb[1] << (wide ? 16 : 8)) << up;
+    unsigned qa[4] = {wa, 0, 0, 0}, qb[4] = {wb, 0, 0, 0}, qc[4] = {uv, 0, 0, 0};
+#pragma unroll
+    for (int q = 1; q < 4; ++q) { qa[q] = __shfl_down(wa, q); qb[q] = __shfl_down(wb, q); qc[q] = __shfl_down(uv, q); }
+    if (!active) return;
+    if (packed) {
+        if (cj & 3) return;
+        if (!wide) {
+            *(uint2*)(rowa + Xr) = make_uint2(qa[0] | qa[1] << 16, qa[2] | qa[3] << 16);
+            if (has_b) *(uint2*)(rowb + Xr) = make_uint2(qb[0] | qb[1] << 16, qb[2] | qb[3] << 16);
+            *(uint2*)(rowc + Xr) = make_uint2(qc[0] | qc[1] << 16, qc[2] | qc[3] << 16);
+        } else {
+            *(uint4*)(rowa + 2 * (size_t)Xr) = make_uint4(qa[0], qa[1], qa[2], qa[3]);
+            if (has_b) *(uint4*)(rowb + 2 * (size_t)Xr) = make_uint4(qb[0], qb[1], qb[2], qb[3]);
+            *(uint4*)(rowc + 2 * (size_t)Xr) = make_uint4(qc[0], qc[1], qc[2], qc[3]);
+        }
+        return;
+    }
+    const int nc = has_r ? 2 : 1;
+    if (!wide) {
+        for (int q = 0; q < nc; ++q) { rowa[X0 + q] = (uint8_t)(wa >> 8 * q); if (has_b) rowb[X0 + q] = (uint8_t)(wb >> 8 * q); }
+        rowc[X0] = (uint8_t)uv; rowc[X0 + 1] = (uint8_t)(uv >> 8);
+    } else {
+        for (int q = 0; q < nc; ++q) { ((uint16_t*)rowa)[X0 + q] = (uint16_t)(wa >> 16 * q); if (has_b) ((uint16_t*)rowb)[X0 + q] = (uint16_t)(wb >> 16 * q); }
+        ((uint16_t*)rowc)[X0] = (uint16_t)uv; ((uint16_t*)rowc)[X0 + 1] = (uint16_t)(uv >> 16);
+    }
+}
+
+template <typename K> hipError_t launch_tile_kernel(K kernel, const ResampleYuvParams& p, int dwords_per_row, unsigned& lds_done, hipStream_t s) {
+    hipError_t e = ensure_dynamic_lds((const void*)kernel, 3 * kRsMaxRows * dwords_per_row * (int)sizeof(float), lds_done);
+    if (e != hipSuccess) return e;
+    const dim3 grid((unsigned)((p.outW + kRsCols - 1) / kRsCols), (unsigned)((p.outH + kRsRows - 1) / kRsRows));
+    hipLaunchKernelGGL(kernel, grid, dim3(kRsThreads), (size_t)(3 * p.rows_max * dwords_per_row) * sizeof(float), s, p);
+    return hipGetLastError();
+}
+
+}  // namespace
+
+// launch_resample_yuv's layouts other than I420 (it has checked the sizes, the depth and rows_max): every plane of the layout present, with a step that holds
+// its row, 10-bit planes at even addresses
+hipError_t launch_resample_yuv_layout(const ResampleYuvParams& p, hipStream_t s) {
+    const int layout = p.dst.layout;
+    if (layout != kYuvI422 && layout != kYuvI444 && layout != kYuvNV12) return hipErrorInvalidValue;
+    if (!p.canvas || p.rows_max <= 0 || p.rows_max > kRsMaxRows || p.dst.rows != p.outH || p.dst.cols != p.outW || (p.dst.bits != 8 && p.dst.bits != 10)) return hipErrorInvalidValue;
+    const size_t bps = p.dst.bits > 8 ? 2 : 1;
+    for (int i = 0; i < (layout == kYuvNV12 ? 2 : 3); ++i) {
+        const size_t samples = (size_t)(i ? yuv_chroma_samples(p.outW, layout) : p.outW);
+        if (!p.dst.p[i] || p.dst.step[i] < samples * bps || ((((size_t)p.dst.p[i]) | p.dst.step[i]) & (bps - 1)) != 0) return hipErrorInvalidValue;
+    }
+    static unsigned done444 = 0, done422 = 0, done_nv12 = 0;
+    switch (layout) {
+        case kYuvI444: return launch_tile_kernel(resample_yuv444_kernel, p, kRsCols, done444, s);
+        case kYuvI422: return launch_tile_kernel(resample_yuv422_kernel, p, kRsCols + 1, done422, s);
+        default: return launch_tile_kernel(resample_yuv_nv12_kernel, p, kYP, done_nv12, s);
+    }
+}
+
+}  // namespace w2x

@@ -505,7 +505,11 @@ struct ResampleYuvParams {
     int rows_max = 0;
     YuvPlanes dst; YuvCoefs k;
 };
+// dst.layout picks the kernel: I420 resample_yuv_kernel; every other layout goes on to launch_resample_yuv_layout (k_resample_yuv.hip): I444
+// resample_kernel's pass 2 with each pixel's own Cb / Cr, I422 the same shape with the chroma filter along the row alone, NV12 / P010 I420's samples with
+// U and V interleaved in plane 1 and, at 10 bits, every code << 6
 hipError_t launch_resample_yuv(const ResampleYuvParams& p, hipStream_t s);
+hipError_t launch_resample_yuv_layout(const ResampleYuvParams& p, hipStream_t s);
 // debug/test helpers used by w2x_infer (mirrors blobFromImages / imagesFromBlob, img2img_infer.cpp:5-39)
 hipError_t launch_blob_to_nhwc(const float* nchw, void* out_nhwc4, int B, int T, bool fp32, hipStream_t s);
 hipError_t launch_nhwc_to_blob(const void* in_nhwc4, float* nchw, int B, int T, bool fp32, hipStream_t s);

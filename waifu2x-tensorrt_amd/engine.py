@@ -307,6 +307,12 @@ RGBAP_SYMBOLS = {
     "w2x_alpha_bleed_rgbap": (_I, [_P, _P, _I, _I, _I, _I, _P, _P]),
     "w2x_alpha_bleed_rgbap_device": (_I, [_P, _P, _P, _I, _I, _I, _I, _P, _P, _P]),
 }
+# The resized YUV entries that carry a layout (include/w2x/c_api_yuv_resized.h), a table of their own likewise: _YUV2L + [matrix, range, filter], the sequence with
+# `count` in front of the matrix.
+YUV_RESIZED_SYMBOLS = {
+    "w2x_render_yuv_layout_resized": (_I, _YUV2L + [_I, _I, _I]),
+    "w2x_render_sequence_yuv_layout_resized": (_I, _YUV2L + [_I, _I, _I, _I]),
+}
 _lib = None
 
 
@@ -319,7 +325,7 @@ def lib():
         raise W2xError(f"{lib_path} is missing - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "or `make -C waifu2x-tensorrt_amd` (there is no CPU fallback)")
     L = C.CDLL(lib_path)
-    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()) + list(PLANAR_SYMBOLS.items()) + list(RGBAP_SYMBOLS.items()):
+    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()) + list(PLANAR_SYMBOLS.items()) + list(RGBAP_SYMBOLS.items()) + list(YUV_RESIZED_SYMBOLS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -833,7 +839,7 @@ class Img2Img:
                            out_bits: int | None = None, filter: str = "bicubic", dst=None):
         """render_yuv() with the canvas resized on the device to size = (rows, cols), each in [input dim, input dim * scaling], before it is encoded
         (w2x_render_yuv_resized).  Returns (Y, U, V) at the target size, or raises.  dst: pre-allocated planes (then a bool is returned).
-        4:2:0 planes only, both sides (resample_yuv_kernel encodes 4:2:0): planes of another layout's shapes raise the ValueError that names 4:2:0."""
+        4:2:0 planes only, both sides: planes of another layout's shapes raise the ValueError that names 4:2:0 (the other layouts: render_yuv_layout_resized)."""
         bits = _yuv_bits((y, u, v))
         ob = bits if out_bits is None else int(out_bits)
         rows, cols = int(size[0]), int(size[1])
@@ -850,8 +856,42 @@ class Img2Img:
 
     def render_sequence_yuv_resized(self, frames, size, *, matrix: str = "bt709", full_range: bool = False, out_bits: int | None = None, pinned: bool = False,
                                     filter: str = "bicubic"):
-        """render_sequence_yuv() with every frame resized to size = (rows, cols) like render_yuv_resized() (w2x_render_sequence_yuv_resized); 4:2:0 planes only"""
+        """render_sequence_yuv() with every frame resized to size = (rows, cols) like render_yuv_resized() (w2x_render_sequence_yuv_resized); 4:2:0 planes only
+        (the other layouts: render_sequence_yuv_layout_resized)"""
         return self._sequence_yuv(frames, (int(size[0]), int(size[1])), _filter_id(filter), matrix, full_range, out_bits, pinned)
+
+    def render_yuv_layout_resized(self, planes, size, *, layout: str = "i420", out_layout: str | None = None, matrix: str = "bt709", full_range: bool = False,
+                                  out_bits: int | None = None, filter: str = "bicubic", dst=None):
+        """render_yuv_resized() on frames of any layout (w2x_render_yuv_layout_resized): planes is the tuple of `layout`'s planes - (y, u, v), or (y, uv) for
+        "nv12" (10-bit: P010, codes << 6) -, out_layout (default: layout) the layout of the result, size = (rows, cols) the target, each in [input dim,
+        input dim * scaling].  Returns the tuple of out_layout's planes at the target size (yuv_layout_plane_shapes), or raises.  dst: pre-allocated planes
+        (then a bool is returned).  Planes that do not have the named layout's shapes and unknown names raise ValueError before any library call."""
+        out_layout = layout if out_layout is None else out_layout
+        lid, olid = _layout_id(layout), _layout_id(out_layout)
+        if not isinstance(planes, (tuple, list)):
+            raise ValueError("give the frame as one tuple of the layout's planes")
+        planes = tuple(planes)
+        bits = _yuv_layout_bits(planes, layout)
+        ob = bits if out_bits is None else int(out_bits)
+        rows, cols = int(size[0]), int(size[1])
+        fid, mid = _filter_id(filter), _matrix_id(matrix)
+        dt = np.uint16 if ob == 10 else np.uint8
+        shapes = yuv_layout_plane_shapes(max(rows, 0), max(cols, 0), out_layout)
+        out = tuple(np.empty(shape, dt) for shape in shapes) if dst is None else tuple(dst)
+        if len(out) != len(shapes) or any(not isinstance(p, np.ndarray) or p.dtype != dt or p.shape != shape or (p.size and p.strides[1] != p.itemsize) for p, shape in zip(out, shapes)):
+            raise ValueError(f"dst must be the 2-D planes of the target's {out_layout} shapes, uint8 for 8-bit and uint16 for 10-bit output, with packed rows")
+        sp, ss = _plane_args(planes)
+        dp = [_data(p) for p in out] + [None] * (3 - len(out))   # (an empty target: refused by the library)
+        ds = [p.strides[0] for p in out] + [0] * (3 - len(out))
+        ok = self._L.w2x_render_yuv_layout_resized(self._h, (C.c_void_p * 3)(*sp), (C.c_size_t * 3)(*ss), planes[0].shape[0], planes[0].shape[1], bits, lid,
+                                                   (C.c_void_p * 3)(*dp), (C.c_size_t * 3)(*ds), rows, cols, ob, olid, mid, 1 if full_range else 0, fid)
+        return self._finish(ok, out if dst is None else None, "render_yuv_layout_resized failed")
+
+    def render_sequence_yuv_layout_resized(self, frames, size, *, layout: str = "i420", out_layout: str | None = None, matrix: str = "bt709", full_range: bool = False,
+                                           out_bits: int | None = None, filter: str = "bicubic", pinned: bool = False):
+        """render_sequence_yuv() over frames of `layout` with every frame resized to size = (rows, cols) like render_yuv_layout_resized()
+        (w2x_render_sequence_yuv_layout_resized): every frame a tuple of `layout`'s planes, every result a tuple of out_layout's"""
+        return self._sequence_yuv(frames, (int(size[0]), int(size[1])), _filter_id(filter), matrix, full_range, out_bits, pinned, layout, out_layout or layout)
 
     def render_sequence_yuv(self, frames, *, matrix: str = "bt709", full_range: bool = False, out_bits: int | None = None, pinned: bool = False,
                             layout: str | None = None, out_layout: str | None = None):
@@ -863,7 +903,7 @@ class Img2Img:
 
     def _sequence_yuv(self, frames, size, fid, matrix, full_range, out_bits, pinned, layout=None, out_layout=None):
         """the YUV sequence calls: size = None the scaled size (w2x_render_sequence_yuv; with a layout given w2x_render_sequence_yuv_layout), else the target of
-        w2x_render_sequence_yuv_resized with filter fid"""
+        w2x_render_sequence_yuv_resized with filter fid (with a layout given w2x_render_sequence_yuv_layout_resized)"""
         if len(frames) == 0:
             return []
         with_layout = layout is not None or out_layout is not None
@@ -903,10 +943,12 @@ class Img2Img:
             # (the matrix is looked at here: a pinned call with an unknown one has taken its ring by now, and gives it back)
             a = (self._h, sp, (C.c_size_t * 3)(*steps), rows, cols, bits, dp, (C.c_size_t * 3)(*_plane_args(os_[0])[1]), orows, ocols, ob, m,
                  _matrix_id(matrix), 1 if full_range else 0)
+            if size is not None and with_layout:
+                return self._L.w2x_render_sequence_yuv_layout_resized(*a[:6], lid, *a[6:11], olid, *a[11:], fid)
             if size is not None:
                 return self._L.w2x_render_sequence_yuv_resized(*a, fid)
             return self._L.w2x_render_sequence_yuv_layout(*a[:6], lid, *a[6:11], olid, *a[11:]) if with_layout else self._L.w2x_render_sequence_yuv(*a)
-        return self._sequence(frames, None, pinned, alloc, lambda d: tuple(p.copy() for p in d), run, "render_sequence_yuv failed" if size is None else "render_sequence_yuv_resized failed")
+        return self._sequence(frames, None, pinned, alloc, lambda d: tuple(p.copy() for p in d), run, "render_sequence_yuv failed" if size is None else "render_sequence_yuv_layout_resized failed" if with_layout else "render_sequence_yuv_resized failed")
 
     def alloc_host(self, shape) -> np.ndarray:
         """A uint8 array over page-locked memory owned by the engine (w2x_alloc_host): frame buffers whose PCIe copies
