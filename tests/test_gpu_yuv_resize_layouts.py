@@ -153,6 +153,24 @@ def test_layouts_that_must_agree_to_the_byte(swin, bits):
                 assert same(got, swin.render_yuv(src, layout="i422", out_layout=lay, out_bits=18 - bits)), (lay, filt)
 
 
+def test_the_even_row_luma_is_one_expression_in_every_layout(swin):
+    """(c) and (d) at the case that told the kernels apart before they shared their expressions (profiles/resample_family/ab_parent.txt): the smooth 50 x 66
+    picture of tools/resample_digest.py to 175 x 250, bicubic, 10 bits out.  Y[36][7] lies on a rounding tie of Y' there - code 500 with kb B rounded on its
+    own, as the I420 kernel forms Y' on even rows, 499 with kb B fused into the sum, which is what the compiler made of the layout kernels' statement of the
+    same form.  No other target of this file or of that tool has such a sample."""
+    import resample_digest as rd
+    planes = rd.yuv_source(rd.picture(50, 66, 7 * 50 + 66), 8)
+    kw = dict(out_bits=10, filter="bicubic")
+    base = swin.render_yuv_resized(*planes, (175, 250), **kw)
+    assert base[0][36, 7] == 500
+    for lay in LAYOUTS:
+        out = swin.render_yuv_layout_resized(planes, (175, 250), out_layout=lay, **kw)
+        if lay == "nv12":
+            assert same(out, ref.pack_nv12(*base))
+        else:
+            assert out[0].dtype == base[0].dtype and np.array_equal(out[0], base[0]), lay
+
+
 @pytest.mark.parametrize("pinned", [False, True])
 def test_rolling_sequence_matches_single_frames(pkg, onnx_model, pinned):
     """(f) renderSequenceYuvResized over five frames that roll (with TTA a 90 x 130 frame on swin x4 fills 48 slots of its one pass: run_rolling_frame, the

@@ -330,7 +330,7 @@ struct Img2Img::Impl {
     // YUV frames (renderYuv / renderSequenceYuv): d_frame / d_out hold the planes of in_layout / out_layout (yuv_layout; kernels.h kYuvI420 ..) and the gather /
     // compose launches are gather_yuv_kernel / compose_yuv_kernel (4:4:4 output: compose_yuv444_kernel); `key` tells the captured passes of each input format -
     // depth, range, matrix, layout - apart.  Resized (renderYuvResized) the frame ends with compose_canvas_kernel and the resample kernel of out_layout
-    // (launch_resample_yuv: resample_yuv_kernel, k_resample_yuv.hip for I422 / I444 / NV12), and d_out holds out_layout's planes of the target size.
+    // (launch_resample_yuv, k_resample_yuv.hip), and d_out holds out_layout's planes of the target size.
     struct YuvJob { YuvCoefs in, out; int in_bits = 8, out_bits = 8, key = 0, in_layout = kYuvI420, out_layout = kYuvI420; };
     // RGBA frames (renderRgba, renderRgbaResized, renderSequenceRgba*): d_frame holds the uploaded BGRA frame, alpha_bleed_kernel writes the BGR frame and the alpha
     // plane the passes gather from (gather_rgba_kernel), d_minmax receives max(A) and max(255 - A), read back into the page-locked h_minmax behind the kernel.  The

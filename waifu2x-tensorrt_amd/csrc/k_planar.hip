@@ -149,19 +149,14 @@ hipError_t launch_compose_canvas_gray(const ComposeParams& p, float* canvas, hip
 }
 hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
-    if (p.rows_max <= 0 || p.rows_max > kRsMaxRows || !p.canvas || !planes_ok(p.dst, p.outH, p.outW)) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((p.outW + kRsCols - 1) / kRsCols), (unsigned)((p.outH + kRsRows - 1) / kRsRows));
+    if (!p.canvas || !planes_ok(p.dst, p.outH, p.outW)) return hipErrorInvalidValue;
     const int maxcode = max_code(p.dst.bits);
     const float scale = (float)maxcode;
     return for_planes(p.dst, [&](auto k) {
         typedef typename decltype(k)::Sample S;
         constexpr int NP = decltype(k)::kPlanes;
-        constexpr int row = NP * kRsCols * (int)sizeof(float);           // LDS bytes per input row
         static unsigned lds_done = 0;                                    // (one per instantiation of this lambda's body)
-        if (kRsMaxRows * row > 64 * 1024)                                // (one plane is 26 KiB at most: no opt-in to large LDS needed)
-            if (hipError_t e = ensure_dynamic_lds((const void*)resample_planes_kernel<S, NP>, kRsMaxRows * row, lds_done); e != hipSuccess) return e;
-        hipLaunchKernelGGL((resample_planes_kernel<S, NP>), grid, dim3(kRsThreads), p.rows_max * row, s, p, scale, maxcode);
-        return hipGetLastError();
+        return launch_resample_tiles(resample_planes_kernel<S, NP>, NP * kRsCols, p.rows_max, lds_done, p.outW, p.outH, s, p, scale, maxcode);
     });
 }
 

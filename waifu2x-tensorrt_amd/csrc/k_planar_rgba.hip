@@ -302,22 +302,14 @@ hipError_t launch_compose_planar_rgba(const ComposePlanarRgbaParams& p, hipStrea
 }
 hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStream_t s) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
-    if (p.rows_max <= 0 || p.rows_max > kRsMaxRows || !p.canvas || !rgba_planes_ok(p.dst, p.outH, p.outW)) return hipErrorInvalidValue;
-    const dim3 grid((unsigned)((p.outW + kRsCols - 1) / kRsCols), (unsigned)((p.outH + kRsRows - 1) / kRsRows));
+    if (!p.canvas || !rgba_planes_ok(p.dst, p.outH, p.outW)) return hipErrorInvalidValue;
     const int maxcode = max_code(p.dst.bits);
     const float scale = (float)maxcode;
-    constexpr int row = kRsCols * (int)sizeof(float);                    // LDS bytes per input row and plane
     return for_sample(p.dst.bits, [&](auto k) {
         typedef decltype(k) S;
         static unsigned lds_done[2] = {0, 0};                            // (a pair per instantiation of this lambda's body)
-        if (p.uniform) {
-            if (hipError_t e = ensure_dynamic_lds((const void*)resample_planes_rgba_kernel<S, 3>, 3 * kRsMaxRows * row, lds_done[0]); e != hipSuccess) return e;
-            hipLaunchKernelGGL((resample_planes_rgba_kernel<S, 3>), grid, dim3(kRsThreads), 3 * p.rows_max * row, s, p, scale, maxcode);
-        } else {
-            if (hipError_t e = ensure_dynamic_lds((const void*)resample_planes_rgba_kernel<S, 4>, 4 * kRsMaxRows * row, lds_done[1]); e != hipSuccess) return e;
-            hipLaunchKernelGGL((resample_planes_rgba_kernel<S, 4>), grid, dim3(kRsThreads), 4 * p.rows_max * row, s, p, scale, maxcode);
-        }
-        return hipGetLastError();
+        if (p.uniform) return launch_resample_tiles(resample_planes_rgba_kernel<S, 3>, 3 * kRsCols, p.rows_max, lds_done[0], p.outW, p.outH, s, p, scale, maxcode);
+        return launch_resample_tiles(resample_planes_rgba_kernel<S, 4>, 4 * kRsCols, p.rows_max, lds_done[1], p.outW, p.outH, s, p, scale, maxcode);
     });
 }
 

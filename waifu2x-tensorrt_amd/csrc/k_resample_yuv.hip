@@ -1,14 +1,15 @@
-// Resized YUV output in the layouts beside I420 (renderYuvResized with dst.layout I422, I444 or NV12): resample_kernel's resize of the fp32 RGB
-// canvas - its 16 x 64 tile, its tap tables, its pass 1 and rows_max - with the encoding of compose_yuv_kernel / compose_yuv444_kernel behind it.  The canvas
-// is resized unclamped; R, G, B are clamped to [0, 1] after the resize and coded with the compose kernels' expressions in their order.  resample_yuv_kernel
-// (k_resample.hip) stays the I420 kernel; launch_resample_yuv hands every other layout to launch_resample_yuv_layout below.
+// Resized YUV output in every layout (renderYuvResized; dst.layout I420, I422, I444 or NV12): the resize of the fp32 RGB canvas that
+// resample_kernel (k_resample.hip) does - the 16 x 64 tile, the tap tables, rows_max and the two passes of pixel_device.h - with the encoding of
+// compose_yuv_kernel / compose_yuv444_kernel behind it.  The canvas is resized unclamped; R, G, B are clamped to [0, 1] after the resize and coded with the
+// expressions below, one statement of each for all four kernels.  launch_resample_yuv, at the end, is the one entry.
 //
-//   resample_yuv444_kernel   resample_kernel's two passes (pixel_device.h resample_pass1 / resample_pass2: a thread per four pixels of a row, float4 LDS reads,
-//                            no halo); each pixel codes Y, Cb and Cr from its own clamped colour.  4 samples per plane and store.
+//   resample_yuv444_kernel   the two shared passes (resample_pass1 / resample_pass2: a thread per four pixels of a row, float4 LDS reads, no halo); each pixel
+//                            codes Y, Cb and Cr from its own clamped colour.  4 samples per plane and store.
 //   resample_yuv422_kernel   the same shape, two chroma sites per thread: site j filters columns 2j - 1, 2j, 2j + 1 of its own row (1/4, 1/2, 1/4, indices clamped
 //                            to the frame).  Column 2j - 1 of a thread's first site is the last column of the lane on its left; the first thread of a tile row
 //                            takes it from the halo, output column ox0 - 1 (clamped at 0), which pass 1 filters as a 65th column.
-//   resample_yuv_nv12_kernel resample_yuv_kernel's arithmetic in its order, U and V stored interleaved in plane 1, every code << 6 at 10 bits (P010).
+//   resample_yuv_kernel      4:2:0, a thread per chroma site = 2 x 2 pixels (resample_yuv420): I420, U and V in planes 1 and 2.
+//   resample_yuv_nv12_kernel the same body: U and V interleaved in plane 1, every code << 6 at 10 bits (P010).
 #include "pixel_device.h"
 
 #include <type_traits>
@@ -16,12 +17,19 @@
 namespace w2x {
 namespace {
 
-// The encoding expressions, each rounding stated (no contraction left to the compiler): the forms resample_yuv_kernel has as compiled for gfx950, which the byte
-// equalities with it rest on - the Y plane of every layout is I420's, NV12 holds I420's samples.  Its listing fuses the last product of Y' = kr R + kg G + kb B on
-// the odd rows of the frame (the second row of a chroma site) and rounds it on its own on the even rows; the chroma expressions are fused throughout.
+// The encoding expressions, each rounding stated (no contraction left to the compiler), so that the byte equalities between the layouts - the Y plane of every
+// layout is I420's, NV12 holds I420's samples - hold by the source and not by what a compiler makes of it.  They are the forms the first I420 kernel had as
+// compiled for gfx950, whose output the later ones had to meet: it fused the last product of Y' = kr R + kg G + kb B on the odd rows of the frame (the second
+// row of a chroma site) and rounded it on its own on the even rows; the chroma expressions were fused throughout.  A fused operation is
+// stated by __fmaf_rn; an operation that must not fuse with its neighbour needs contraction switched off around it, as in luma_even_row - the one place where a
+// product feeds a sum that is not meant to be an fma.  Everywhere else a product feeds an __fmaf_rn or a sum feeds a product, which nothing can contract.
 __device__ __forceinline__ unsigned yuv_code(float off, float scale, float v, int maxcode) { return (unsigned)min(max(__float2int_rn(__fmaf_rn(scale, v, off)), 0), maxcode); }
 __device__ __forceinline__ float luma_fused(const YuvCoefs& k, float r, float g, float b) { return __fmaf_rn(k.kb, b, __fmaf_rn(k.kr, r, __fmul_rn(k.kg, g))); }
-__device__ __forceinline__ float luma_even_row(const YuvCoefs& k, float r, float g, float b) { return __fadd_rn(__fmul_rn(k.kb, b), __fmaf_rn(k.kr, r, __fmul_rn(k.kg, g))); }
+__device__ __forceinline__ float luma_even_row(const YuvCoefs& k, float r, float g, float b) {
+#pragma clang fp contract(off)   // (__fadd_rn / __fmul_rn are `+` and `*` to the compiler, which fuses them where it may: only this keeps kb * b a product of its own)
+    const float pb = k.kb * b;
+    return pb + __fmaf_rn(k.kr, r, k.kg * g);
+}
 __device__ __forceinline__ float luma_of_row(const YuvCoefs& k, int Y, float r, float g, float b) { return (Y & 1) ? luma_fused(k, r, g, b) : luma_even_row(k, r, g, b); }
 // a chroma site's colour from the columns 2j - 1, 2j, 2j + 1 (1/4, 1/2, 1/4)
 __device__ __forceinline__ float site_filter(float left, float mid, float right) { return __fmaf_rn(0.25f, right, __fmaf_rn(0.25f, left, __fmul_rn(0.5f, mid))); }
@@ -80,27 +88,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv422_kernel(const Resam
     const int rm = p.rows_max;
     float* const halo = h + 3 * rm * kRsCols;
     const int ox0 = blockIdx.x * kRsCols, oy0 = blockIdx.y * kRsRows;
-    const int tw = min(kRsCols, p.outW - ox0), th = min(kRsRows, p.outH - oy0);
-    const int r0 = p.fy[oy0];
-    const int nr = min(p.inH, p.fy[oy0 + th - 1] + p.ky) - r0;           // <= rows_max (resample_rows_max)
-    const size_t plane = (size_t)p.inW * p.inH;
-    // pass 1: input rows [r0, r0 + nr) filtered horizontally onto the tile's output columns and onto column ox0 - 1
-    for (int i = threadIdx.x; i < nr * (kRsCols + 1); i += kRsThreads) {
-        const int r = i / (kRsCols + 1), c = i % (kRsCols + 1);
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-        if (c < tw || c == kRsCols) {
-            const int X = c == kRsCols ? max(ox0 - 1, 0) : ox0 + c, f = p.fx[X];
-            const int n = min(p.kx, p.inW - f);
-            const float* w = p.wx + (size_t)X * p.kx;
-            const float* s = p.canvas + (size_t)(r0 + r) * p.inW + f;
-            for (int t = 0; t < n; ++t) {
-                const float wk = w[t];
-                a0 += wk * s[t]; a1 += wk * s[plane + t]; a2 += wk * s[2 * plane + t];
-            }
-        }
-        if (c == kRsCols) { halo[r] = a0; halo[rm + r] = a1; halo[2 * rm + r] = a2; }
-        else { h[(0 * rm + r) * kRsCols + c] = a0; h[(1 * rm + r) * kRsCols + c] = a1; h[(2 * rm + r) * kRsCols + c] = a2; }
-    }
+    const int r0 = resample_pass1_to<3, true>(p, h, [rm](int q, int r, int c) { return c == kRsCols ? 3 * rm * kRsCols + q * rm + r : (q * rm + r) * kRsCols + c; });
     __syncthreads();
     // pass 2: four pixels = two chroma sites of one row per thread.  No lane leaves before the cross-lane moves below: lanes outside the frame carry zeros.
     const YuvCoefs& k = p.k;
@@ -184,36 +172,27 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv422_kernel(const Resam
     }
 }
 
-// ---- NV12 / P010: resample_yuv_kernel (k_resample.hip) restated - pass 1, the vertical filters, the clamps, the Y and the Cb / Cr expressions and their order
-// are its own, so the samples are I420's; only the stores differ: U and V of a site side by side in plane 1 and, at 10 bits, every code in the high bits.
-// LDS as there: [3][rows_max][kYP], kYP = 66 (float2 reads of pass 2 8-byte aligned, the halo at column 64), 60.3 KiB at a factor of 4 with bicubic taps.
+// ---- 4:2:0: I420 and, with kNV12, NV12 / P010 - the samples are the same, only the stores differ: U and V of a site in planes 1 and 2, or side by side in
+// plane 1 with, at 10 bits, every code in the high bits.
+// The tile and pass 1 are resample_kernel's, over one more column: chroma site j filters the luma columns 2j - 1, 2j, 2j + 1, and tile origins are multiples of
+// 16 rows and 64 columns, so every site and both of its rows lie in one tile and the only value from outside is output column ox0 - 1 (clamped at 0), the halo,
+// kept at column kRsCols of the LDS rows.  Pass 2: a thread per chroma site = 2 x 2 luma pixels, 32 sites of one chroma row per half wave.  It filters columns
+// 2j, 2j + 1 of its two rows vertically out of LDS (a float2 per plane and tap), clamps them to [0, 1], codes Y, averages the two rows, takes column 2j - 1 from
+// the lane on its left (lanes 0 and 32, the row's first sites, from the halo, which lanes 0 .. 3 of the wave filter for its four luma rows) and codes Cb / Cr.
+// Four neighbouring lanes then pass their codes to the first of them, which stores 8 luma samples per row and 4 + 4 chroma samples in one store each (8 or 16
+// bytes of Y; 4 or 8 of U and of V, or 8 or 16 of UV); a run cut by the right edge (or a caller's unaligned rows) stores sample by sample.
+// LDS: [3][rows_max][kYP] fp32.  kYP = 66: even, so the float2 reads of pass 2 are 8-byte aligned; a half wave reads 64 consecutive dwords of one row
+// (ds_read_b64 banks: address / 4 mod 64 within 32 lanes), conflict free whatever the pitch, and the halo reads of lanes 0 .. 3 hit rows 66 dwords apart
+// (banks 2 apart).  Pass 1 writes 65 consecutive dwords per row, rows 66 apart: at most two lanes of 32 on one bank, which a 4-byte store hides.
+// At a factor of 4 with bicubic taps rows_max <= 78: 3 * 78 * 66 * 4 B = 60.3 KiB, two workgroups per CU.
 constexpr int kYP = kRsCols + 2;
 typedef float float2v __attribute__((ext_vector_type(2)));
 
-__global__ __launch_bounds__(kRsThreads) void resample_yuv_nv12_kernel(const ResampleYuvParams p) {
-    extern __shared__ float h[];                                          // [3][rows_max][kYP]: columns 0 .. 63 the tile's, 64 the halo
+template <bool kNV12>
+__device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, float* h) {   // h: [3][rows_max][kYP], columns 0 .. 63 the tile's, 64 the halo
     const int ox0 = blockIdx.x * kRsCols, oy0 = blockIdx.y * kRsRows;
-    const int tw = min(kRsCols, p.outW - ox0), th = min(kRsRows, p.outH - oy0);
-    const int r0 = p.fy[oy0];
-    const int nr = min(p.inH, p.fy[oy0 + th - 1] + p.ky) - r0;           // <= rows_max (resample_rows_max)
-    const size_t plane = (size_t)p.inW * p.inH;
     const int rm = p.rows_max;
-    // pass 1: input rows [r0, r0 + nr) filtered horizontally onto the tile's output columns and onto column ox0 - 1
-    for (int i = threadIdx.x; i < nr * (kRsCols + 1); i += kRsThreads) {
-        const int r = i / (kRsCols + 1), c = i % (kRsCols + 1);
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f;
-        if (c < tw || c == kRsCols) {
-            const int X = c == kRsCols ? max(ox0 - 1, 0) : ox0 + c, f = p.fx[X];
-            const int n = min(p.kx, p.inW - f);
-            const float* w = p.wx + (size_t)X * p.kx;
-            const float* s = p.canvas + (size_t)(r0 + r) * p.inW + f;
-            for (int t = 0; t < n; ++t) {
-                const float wk = w[t];
-                a0 += wk * s[t]; a1 += wk * s[plane + t]; a2 += wk * s[2 * plane + t];
-            }
-        }
-        h[(0 * rm + r) * kYP + c] = a0; h[(1 * rm + r) * kYP + c] = a1; h[(2 * rm + r) * kYP + c] = a2;
-    }
+    const int r0 = resample_pass1_to<3, true>(p, h, [rm](int q, int r, int c) { return (q * rm + r) * kYP + c; });
     __syncthreads();
     // pass 2: a chroma site per thread.  No lane leaves before the cross-lane moves below: lanes outside the frame carry zeros.
     const YuvCoefs& k = p.k;
@@ -268,26 +247,29 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv_nv12_kernel(const Res
         left[e] = cj ? from_left : __fmul_rn(0.5f, __fadd_rn(ha, has_b ? hb : ha));
     }
     const bool wide = p.dst.bits > 8;
-    const int up = wide ? 6 : 0;                                           // P010: the code in the high ten bits
-    unsigned uv;                                                          // U | V << 8 (10 bits: << 16), as the pair lies in plane 1
+    const int sbits = wide ? 16 : 8, up = kNV12 && wide ? 6 : 0;          // bits per stored sample; P010: the code in the high ten bits
+    unsigned uc, vc;
     {
         float f[3];
 #pragma unroll
         for (int e = 0; e < 3; ++e) f[e] = site_filter(left[e], vl[e], vr[e]);
         const float Y = luma_fused(k, f[0], f[1], f[2]);
-        uv = (yuv_code(k.c_off, k.c_scale, chroma_of(f[2], Y, k.cb_div), k.maxcode) | yuv_code(k.c_off, k.c_scale, chroma_of(f[0], Y, k.cr_div), k.maxcode) << (wide ? 16 : 8)) << up;
+        uc = yuv_code(k.c_off, k.c_scale, chroma_of(f[2], Y, k.cb_div), k.maxcode) << up;
+        vc = yuv_code(k.c_off, k.c_scale, chroma_of(f[0], Y, k.cr_div), k.maxcode) << up;
     }
     // stores: the run of four sites the lane belongs to goes out through its first lane where the run is whole and its rows are aligned
     const int sh = wide ? 1 : 0;                                           // log2 bytes per sample
-    const int Xr = ox0 + 2 * (cj & ~3), ic = Ya >> 1;
+    const int Xr = ox0 + 2 * (cj & ~3), ic = Ya >> 1, j = X0 >> 1;
     uint8_t* const rowa = p.dst.p[0] + (size_t)Ya * p.dst.step[0];
     uint8_t* const rowb = rowa + p.dst.step[0];
-    uint8_t* const rowc = p.dst.p[1] + (size_t)ic * p.dst.step[1];        // U, V, U, V, ...: site j at samples 2j, 2j + 1
-    const size_t ymask = wide ? 15 : 7;
-    const bool packed = Xr + 8 <= p.outW &&
-                        ((((size_t)rowa + ((size_t)Xr << sh)) | p.dst.step[0]) & ymask) == 0 &&
-                        (((size_t)rowc + ((size_t)Xr << sh)) & ymask) == 0;
-    const unsigned wa = (ya[0] | ya[1] << (wide ? 16 : 8)) << up, wb = (yb[0] | yb[1] << (wide ? 16 : 8)) << up;
+    uint8_t* const rowu = p.dst.p[1] + (size_t)ic * p.dst.step[1];        // NV12: U, V, U, V, ...: site j at samples 2j, 2j + 1
+    uint8_t* const rowv = kNV12 ? rowu : p.dst.p[2] + (size_t)ic * p.dst.step[2];
+    const size_t ymask = wide ? 15 : 7, cmask = wide ? 7 : 3;
+    const bool chroma_aligned = kNV12 ? (((size_t)rowu + ((size_t)Xr << sh)) & ymask) == 0
+                                      : ((((size_t)rowu + ((size_t)(Xr >> 1) << sh)) | ((size_t)rowv + ((size_t)(Xr >> 1) << sh))) & cmask) == 0;
+    const bool packed = Xr + 8 <= p.outW && ((((size_t)rowa + ((size_t)Xr << sh)) | p.dst.step[0]) & ymask) == 0 && chroma_aligned;
+    const unsigned wa = (ya[0] | ya[1] << sbits) << up, wb = (yb[0] | yb[1] << sbits) << up;
+    const unsigned uv = uc | vc << (kNV12 ? sbits : 16);                   // NV12: as the pair lies in plane 1
     unsigned qa[4] = {wa, 0, 0, 0}, qb[4] = {wb, 0, 0, 0}, qc[4] = {uv, 0, 0, 0};
 #pragma unroll
     for (int q = 1; q < 4; ++q) { qa[q] = __shfl_down(wa, q); qb[q] = __shfl_down(wb, q); qc[q] = __shfl_down(uv, q); }
@@ -297,50 +279,64 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv_nv12_kernel(const Res
         if (!wide) {
             *(uint2*)(rowa + Xr) = make_uint2(qa[0] | qa[1] << 16, qa[2] | qa[3] << 16);
             if (has_b) *(uint2*)(rowb + Xr) = make_uint2(qb[0] | qb[1] << 16, qb[2] | qb[3] << 16);
-            *(uint2*)(rowc + Xr) = make_uint2(qc[0] | qc[1] << 16, qc[2] | qc[3] << 16);
+            if constexpr (kNV12) *(uint2*)(rowu + Xr) = make_uint2(qc[0] | qc[1] << 16, qc[2] | qc[3] << 16);
+            else {
+                *(unsigned*)(rowu + (Xr >> 1)) = (qc[0] & 0xff) | (qc[1] & 0xff) << 8 | (qc[2] & 0xff) << 16 | (qc[3] & 0xff) << 24;
+                *(unsigned*)(rowv + (Xr >> 1)) = (qc[0] >> 16) | (qc[1] >> 16) << 8 | (qc[2] >> 16) << 16 | (qc[3] >> 16) << 24;
+            }
         } else {
             *(uint4*)(rowa + 2 * (size_t)Xr) = make_uint4(qa[0], qa[1], qa[2], qa[3]);
             if (has_b) *(uint4*)(rowb + 2 * (size_t)Xr) = make_uint4(qb[0], qb[1], qb[2], qb[3]);
-            *(uint4*)(rowc + 2 * (size_t)Xr) = make_uint4(qc[0], qc[1], qc[2], qc[3]);
+            if constexpr (kNV12) *(uint4*)(rowu + 2 * (size_t)Xr) = make_uint4(qc[0], qc[1], qc[2], qc[3]);
+            else {
+                *(uint2*)(rowu + Xr) = make_uint2((qc[0] & 0xffff) | qc[1] << 16, (qc[2] & 0xffff) | qc[3] << 16);
+                *(uint2*)(rowv + Xr) = make_uint2(qc[0] >> 16 | (qc[1] & 0xffff0000u), qc[2] >> 16 | (qc[3] & 0xffff0000u));
+            }
         }
         return;
     }
-    const int nc = has_r ? 2 : 1;
+    const int nc = has_r ? 2 : 1, ju = kNV12 ? X0 : j, jv = kNV12 ? X0 + 1 : j;   // the samples of U and V in their rows
     if (!wide) {
         for (int q = 0; q < nc; ++q) { rowa[X0 + q] = (uint8_t)(wa >> 8 * q); if (has_b) rowb[X0 + q] = (uint8_t)(wb >> 8 * q); }
-        rowc[X0] = (uint8_t)uv; rowc[X0 + 1] = (uint8_t)(uv >> 8);
+        rowu[ju] = (uint8_t)uc; rowv[jv] = (uint8_t)vc;
     } else {
         for (int q = 0; q < nc; ++q) { ((uint16_t*)rowa)[X0 + q] = (uint16_t)(wa >> 16 * q); if (has_b) ((uint16_t*)rowb)[X0 + q] = (uint16_t)(wb >> 16 * q); }
-        ((uint16_t*)rowc)[X0] = (uint16_t)uv; ((uint16_t*)rowc)[X0 + 1] = (uint16_t)(uv >> 16);
+        ((uint16_t*)rowu)[ju] = (uint16_t)uc; ((uint16_t*)rowv)[jv] = (uint16_t)vc;
     }
 }
 
-template <typename K> hipError_t launch_tile_kernel(K kernel, const ResampleYuvParams& p, int dwords_per_row, unsigned& lds_done, hipStream_t s) {
-    hipError_t e = ensure_dynamic_lds((const void*)kernel, 3 * kRsMaxRows * dwords_per_row * (int)sizeof(float), lds_done);
-    if (e != hipSuccess) return e;
-    const dim3 grid((unsigned)((p.outW + kRsCols - 1) / kRsCols), (unsigned)((p.outH + kRsRows - 1) / kRsRows));
-    hipLaunchKernelGGL(kernel, grid, dim3(kRsThreads), (size_t)(3 * p.rows_max * dwords_per_row) * sizeof(float), s, p);
-    return hipGetLastError();
+__global__ __launch_bounds__(kRsThreads) void resample_yuv_kernel(const ResampleYuvParams p) {
+    extern __shared__ float h[];
+    resample_yuv420<false>(p, h);
+}
+__global__ __launch_bounds__(kRsThreads) void resample_yuv_nv12_kernel(const ResampleYuvParams p) {
+    extern __shared__ float h[];
+    resample_yuv420<true>(p, h);
 }
 
 }  // namespace
 
-// launch_resample_yuv's layouts other than I420 (it has checked the sizes, the depth and rows_max): every plane of the layout present, with a step that holds
-// its row, 10-bit planes at even addresses
-hipError_t launch_resample_yuv_layout(const ResampleYuvParams& p, hipStream_t s) {
+// dst.layout picks the kernel.  The layouts beside I420 also ask for a canvas and for every plane of the layout, with a step that holds its row and 10-bit
+// planes at even addresses.
+hipError_t launch_resample_yuv(const ResampleYuvParams& p, hipStream_t s) {
+    if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
+    if (p.dst.rows != p.outH || p.dst.cols != p.outW || (p.dst.bits != 8 && p.dst.bits != 10)) return hipErrorInvalidValue;
     const int layout = p.dst.layout;
-    if (layout != kYuvI422 && layout != kYuvI444 && layout != kYuvNV12) return hipErrorInvalidValue;
-    if (!p.canvas || p.rows_max <= 0 || p.rows_max > kRsMaxRows || p.dst.rows != p.outH || p.dst.cols != p.outW || (p.dst.bits != 8 && p.dst.bits != 10)) return hipErrorInvalidValue;
-    const size_t bps = p.dst.bits > 8 ? 2 : 1;
-    for (int i = 0; i < (layout == kYuvNV12 ? 2 : 3); ++i) {
-        const size_t samples = (size_t)(i ? yuv_chroma_samples(p.outW, layout) : p.outW);
-        if (!p.dst.p[i] || p.dst.step[i] < samples * bps || ((((size_t)p.dst.p[i]) | p.dst.step[i]) & (bps - 1)) != 0) return hipErrorInvalidValue;
+    if (layout != kYuvI420) {
+        if (layout != kYuvI422 && layout != kYuvI444 && layout != kYuvNV12) return hipErrorInvalidValue;
+        if (!p.canvas) return hipErrorInvalidValue;
+        const size_t bps = p.dst.bits > 8 ? 2 : 1;
+        for (int i = 0; i < (layout == kYuvNV12 ? 2 : 3); ++i) {
+            const size_t samples = (size_t)(i ? yuv_chroma_samples(p.outW, layout) : p.outW);
+            if (!p.dst.p[i] || p.dst.step[i] < samples * bps || ((((size_t)p.dst.p[i]) | p.dst.step[i]) & (bps - 1)) != 0) return hipErrorInvalidValue;
+        }
     }
-    static unsigned done444 = 0, done422 = 0, done_nv12 = 0;
-    switch (layout) {
-        case kYuvI444: return launch_tile_kernel(resample_yuv444_kernel, p, kRsCols, done444, s);
-        case kYuvI422: return launch_tile_kernel(resample_yuv422_kernel, p, kRsCols + 1, done422, s);
-        default: return launch_tile_kernel(resample_yuv_nv12_kernel, p, kYP, done_nv12, s);
+    static unsigned done420 = 0, done422 = 0, done444 = 0, done_nv12 = 0;
+    switch (layout) {                                                      // LDS dwords per input row: three planes of the kernel's pitch
+        case kYuvI420: return launch_resample_tiles(resample_yuv_kernel, 3 * kYP, p.rows_max, done420, p.outW, p.outH, s, p);
+        case kYuvI422: return launch_resample_tiles(resample_yuv422_kernel, 3 * (kRsCols + 1), p.rows_max, done422, p.outW, p.outH, s, p);
+        case kYuvI444: return launch_resample_tiles(resample_yuv444_kernel, 3 * kRsCols, p.rows_max, done444, p.outW, p.outH, s, p);
+        default: return launch_resample_tiles(resample_yuv_nv12_kernel, 3 * kYP, p.rows_max, done_nv12, p.outW, p.outH, s, p);
     }
 }
 

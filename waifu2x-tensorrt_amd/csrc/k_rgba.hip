@@ -232,17 +232,10 @@ hipError_t launch_compose_canvas_rgba(const ComposeCanvasRgbaParams& p, hipStrea
 }
 hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
-    if (p.rows_max <= 0 || p.rows_max > kRsMaxRows || (p.dst_step & 3) || p.dst_step < (size_t)p.outW * 4 || (((size_t)p.dst) & 3)) return hipErrorInvalidValue;
-    const int planes = p.uniform ? 3 : 4;
-    const int lds = planes * p.rows_max * kRsCols * (int)sizeof(float);
+    if ((p.dst_step & 3) || p.dst_step < (size_t)p.outW * 4 || (((size_t)p.dst) & 3)) return hipErrorInvalidValue;
     static unsigned lds_done[2] = {0, 0};
-    const void* fn = p.uniform ? (const void*)resample_rgba_kernel<false> : (const void*)resample_rgba_kernel<true>;
-    hipError_t e = ensure_dynamic_lds(fn, planes * kRsMaxRows * kRsCols * (int)sizeof(float), lds_done[p.uniform ? 0 : 1]);
-    if (e != hipSuccess) return e;
-    const dim3 grid((unsigned)((p.outW + kRsCols - 1) / kRsCols), (unsigned)((p.outH + kRsRows - 1) / kRsRows));
-    if (p.uniform) hipLaunchKernelGGL(resample_rgba_kernel<false>, grid, dim3(kRsThreads), lds, s, p);
-    else hipLaunchKernelGGL(resample_rgba_kernel<true>, grid, dim3(kRsThreads), lds, s, p);
-    return hipGetLastError();
+    if (p.uniform) return launch_resample_tiles(resample_rgba_kernel<false>, 3 * kRsCols, p.rows_max, lds_done[0], p.outW, p.outH, s, p);
+    return launch_resample_tiles(resample_rgba_kernel<true>, 4 * kRsCols, p.rows_max, lds_done[1], p.outW, p.outH, s, p);
 }
 
 }  // namespace w2x

@@ -263,7 +263,8 @@ hipError_t launch_compose(const ComposeParams& p, hipStream_t s);
 hipError_t launch_compose_canvas(const ComposeParams& p, float* canvas, hipStream_t s);
 // k_resample.hip resample_kernel: an antialiased separable resize of the fp32 RGB canvas (three planes of inH x inW) to outH x outW, quantised like
 // compose (sat(rint(x * 255)), 16-bit: 65535) and stored as BGR.  The tap tables (tiles.h resize_taps) live on the device: fx / wx per output column,
-// fy / wy per output row; rows_max = the input rows an output tile of kResampleRows rows reads at most (resample_rows_max)
+// fy / wy per output row; rows_max = the input rows an output tile of kResampleRows rows reads at most (resample_rows_max).  Every resize kernel
+// below (RGBA, planes, YUV) is this one with another store: the two passes and the launch sequence are shared (pixel_device.h)
 struct ResampleParams {
     const float* canvas = nullptr; int inW = 0, inH = 0;
     uint8_t* dst = nullptr; size_t dst_step = 0; int deep = 0;
@@ -494,9 +495,9 @@ struct ResamplePlanarRgbaParams {
     int uniform = 0; float alpha_value = 1.f;
 };
 hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStream_t s);
-// k_resample.hip resample_yuv_kernel: resample_kernel's resize of the fp32 RGB canvas (same tap tables, same rows_max) with compose_yuv_kernel's
-// encoding behind it instead of the BGR quantisation: the resized R, G, B clamped to [0, 1] and written as YUV 4:2:0 planes of outH x outW
-// (dst.rows x dst.cols), Y per pixel, Cb / Cr of the RGB filtered (1/4, 1/2, 1/4) x (1/2, 1/2) onto each chroma site (renderYuvResized)
+// k_resample_yuv.hip: resample_kernel's resize of the fp32 RGB canvas (same tap tables, same rows_max, the same two passes) with compose_yuv_kernel's
+// encoding behind it instead of the BGR quantisation: the resized R, G, B clamped to [0, 1] and written as the YUV planes of dst (outH x outW =
+// dst.rows x dst.cols), Y per pixel; 4:2:0: Cb / Cr of the RGB filtered (1/4, 1/2, 1/4) x (1/2, 1/2) onto each chroma site (renderYuvResized)
 struct ResampleYuvParams {
     const float* canvas = nullptr; int inW = 0, inH = 0;
     int outW = 0, outH = 0;
@@ -505,11 +506,10 @@ struct ResampleYuvParams {
     int rows_max = 0;
     YuvPlanes dst; YuvCoefs k;
 };
-// dst.layout picks the kernel: I420 resample_yuv_kernel; every other layout goes on to launch_resample_yuv_layout (k_resample_yuv.hip): I444
-// resample_kernel's pass 2 with each pixel's own Cb / Cr, I422 the same shape with the chroma filter along the row alone, NV12 / P010 I420's samples with
-// U and V interleaved in plane 1 and, at 10 bits, every code << 6
+// dst.layout picks the kernel: I420 resample_yuv_kernel, a thread per chroma site; NV12 / P010 resample_yuv_nv12_kernel, the same body and so
+// I420's samples, with U and V interleaved in plane 1 and, at 10 bits, every code << 6; I444 resample_kernel's pass 2 with each pixel's own Cb / Cr; I422 the
+// same shape with the chroma filter along the row alone
 hipError_t launch_resample_yuv(const ResampleYuvParams& p, hipStream_t s);
-hipError_t launch_resample_yuv_layout(const ResampleYuvParams& p, hipStream_t s);
 // debug/test helpers used by w2x_infer (mirrors blobFromImages / imagesFromBlob, img2img_infer.cpp:5-39)
 hipError_t launch_blob_to_nhwc(const float* nchw, void* out_nhwc4, int B, int T, bool fp32, hipStream_t s);
 hipError_t launch_nhwc_to_blob(const void* in_nhwc4, float* nchw, int B, int T, bool fp32, hipStream_t s);

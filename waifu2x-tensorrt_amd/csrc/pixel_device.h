@@ -1,9 +1,10 @@
-// Device pieces shared by the frame formats that stand beside the BGR path: planar and gray frames (k_planar.hip) and RGBA frames (k_rgba.hip).  Each piece is
-// the corresponding piece of a BGR kernel (gather_kernel, compose_kernel of k_prepost.hip; resample_kernel of k_resample.hip) with the format-specific load or
-// store left to the caller: a format supplies a loader and a store and reuses the bodies.  The byte-for-byte contracts of DESIGN 9d - 9h rest on the arithmetic
-// and its order here being the BGR kernels': the same slots and clamps, compose_pixel_sums' weights in the order L, T, R, B, resample_kernel's tile, tap tables
-// and tap order (a += wk * s[k]) and one quantisation, sat(rint(x * maxcode)).  k_prepost.hip and k_resample.hip do not include this header: the kernels of the
-// BGR and YUV paths keep their listings.
+// Device pieces shared by the frame formats: planar and gray frames (k_planar.hip), RGBA frames (k_rgba.hip, k_planar_rgba.hip) and every resize kernel, the BGR
+// and YUV ones included (k_resample.hip, k_resample_yuv.hip).  The gather and compose pieces are the corresponding pieces of a BGR kernel (gather_kernel,
+// compose_kernel of k_prepost.hip) with the format-specific load or store left to the caller: a format supplies a loader and a store and reuses the bodies.  The
+// resize has no BGR original any more: its two passes and its launch sequence are stated here once, and a kernel adds its store.  The byte-for-byte
+// contracts of DESIGN 9d - 9j rest on the arithmetic and its order: the same slots and clamps, compose_pixel_sums' weights in the order L, T, R, B, one resize
+// tile, tap tables and tap order (a += wk * s[k]) and one quantisation, sat(rint(x * maxcode)).  k_prepost.hip does not include this header: the gather and
+// compose kernels of the BGR and YUV paths keep their listings.
 #pragma once
 #include "kernels.h"
 #include "prepost_device.h"
@@ -17,11 +18,25 @@ namespace {
 constexpr int kGatherThreads = 256;
 inline unsigned grid_for(long total) { long g = (total + kGatherThreads - 1) / kGatherThreads; return (unsigned)(g > 8192 ? 8192 : (g < 1 ? 1 : g)); }
 // compose, four pixels per thread: compose_kernel's kComposeRows / kComposeThreads (kernels.h)
-// resample: resample_kernel's output tile (kernels.h) and workgroup.  Byte equality with resample_kernel rests on the same tile, the same tap order and the
-// same quantisation.
+// resample: the output tile of every resize kernel (kernels.h) and its workgroup.  Byte equality between the formats rests on the same tile, the same tap order
+// and the same quantisation.
 constexpr int kRsRows = kResampleRows, kRsCols = kResampleCols, kRsThreads = 256;
 static_assert(kRsCols == 64 && kRsRows * (kRsCols / 4) == kRsThreads, "pass 2 maps one thread to four pixels of the tile");
-constexpr int kRsMaxRows = 104;                                          // as launch_resample: factor 4, bicubic is 78
+constexpr int kRsMaxRows = 104;                                          // factor 4, bicubic: 78 (a factor of 4 is the largest the engine asks for)
+
+// The launch of a resize kernel over the tiles of an outW x outH frame: `row_dwords` of LDS per input row (all planes, a halo included), rows_max of them in this
+// launch and kRsMaxRows at most, which is what the kernel is opted in to where that passes 64 KiB (one plane never does: 26 KiB, no call).  `done` is the
+// kernel's own per-device mask (ensure_dynamic_lds).
+template <typename... KA, typename... A>
+hipError_t launch_resample_tiles(void (*kernel)(KA...), int row_dwords, int rows_max, unsigned& done, int outW, int outH, hipStream_t s, const A&... args) {
+    if (rows_max <= 0 || rows_max > kRsMaxRows) return hipErrorInvalidValue;
+    const int row = row_dwords * (int)sizeof(float);
+    if (kRsMaxRows * row > 64 * 1024)
+        if (hipError_t e = ensure_dynamic_lds((const void*)kernel, kRsMaxRows * row, done); e != hipSuccess) return e;
+    const dim3 grid((unsigned)((outW + kRsCols - 1) / kRsCols), (unsigned)((outH + kRsRows - 1) / kRsRows));
+    hipLaunchKernelGGL(kernel, grid, dim3(kRsThreads), (size_t)rows_max * row, s, args...);
+    return hipGetLastError();
+}
 
 // ---- the sample types: what a plane holds per pixel.  `maxcode` is 2^bits - 1 and `inv` fl32(1 / maxcode), both made on the host (launch_*).
 struct U8 { typedef uint8_t T; };
@@ -38,8 +53,8 @@ template <> __device__ __forceinline__ float load_sample<F32>(const uint8_t* row
     return !(v >= 0.f) ? 0.f : fminf(v, 1.f);                      // (NaN fails the comparison: 0)
 }
 
-// sat(rint(x * maxcode)): quantize_bgr's expression per sample (compose) and k_resample.hip's q8 / q16 (resample) with the code range a launch argument - at
-// 255 and 65535 the same product and the same rounding, which byte equality with the BGR kernels rests on.  Float: the sum clamped, never rounded to a code.
+// sat(rint(x * maxcode)): quantize_bgr's expression per sample (compose) and the one quantisation of every resize kernel, with the code range a launch
+// argument - at 255 and 65535 the same product and the same rounding, which byte equality with the BGR kernels rests on.  Float: the sum clamped, never rounded.
 __device__ __forceinline__ unsigned quant(float v, float scale, int maxcode) { return (unsigned)min(max(__float2int_rn(v * scale), 0), maxcode); }
 __device__ __forceinline__ float sat01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
 
@@ -148,25 +163,28 @@ __device__ __forceinline__ void compose_quad_sums(const CP& p, int X, int Y, int
         for (int k = 0; k < 4; ++k) acc[c][k] = s[c][k];
 }
 
-// ---- resample_kernel's two passes over NP planes of the fp32 canvas (plane stride inW * inH).  A workgroup of kRsThreads owns an output tile of kRsRows x
-// kRsCols pixels; h is its LDS, [NP][rows_max][kRsCols] fp32.  Banks: a row is 64 dwords, one per bank; pass 1 stores dword c of a row from lane c, pass 2 reads
-// 16 bytes per lane of one row, each plane by an instruction of its own - the planes lie a multiple of the bank count apart and add instructions, no conflicts.
-// Pass 1: the input rows [r0, r0 + nr) the tile needs, filtered horizontally onto its output columns; returns r0.  The caller's barrier follows.
-template <int NP, typename RP>
-__device__ __forceinline__ int resample_pass1(const RP& p, float* h) {
+// ---- the two passes of every resize kernel over NP planes of the fp32 canvas (plane stride inW * inH).  A workgroup of kRsThreads owns an output tile of
+// kRsRows x kRsCols pixels; h is its LDS.  The plain layout is [NP][rows_max][kRsCols] fp32.  Banks: a row is 64 dwords, one per bank; pass 1 stores dword c of
+// a row from lane c, pass 2 reads 16 bytes per lane of one row, each plane by an instruction of its own - the planes lie a multiple of the bank count apart and
+// add instructions, no conflicts.
+// Pass 1: the input rows [r0, r0 + nr) the tile needs, filtered horizontally onto its output columns; returns r0.  The caller's barrier follows.  The value of
+// plane q, input row r, tile column c goes to h[slot(q, r, c)].  kHalo: a 65th column, c == kRsCols, holds output column ox0 - 1 (clamped at 0), which the
+// 4:2:0 and 4:2:2 kernels' chroma sites reach; where it lies is the slot's business (k_resample_yuv.hip).  The loop runs nr * 65 items then, nr * 64 without.
+template <int NP, bool kHalo, typename RP, typename Slot>
+__device__ __forceinline__ int resample_pass1_to(const RP& p, float* h, Slot slot) {
+    constexpr int kCols = kRsCols + (kHalo ? 1 : 0);
     const int ox0 = blockIdx.x * kRsCols, oy0 = blockIdx.y * kRsRows;
     const int tw = min(kRsCols, p.outW - ox0), th = min(kRsRows, p.outH - oy0);
     const int r0 = p.fy[oy0];
     const int nr = min(p.inH, p.fy[oy0 + th - 1] + p.ky) - r0;           // <= rows_max (resample_rows_max)
     const size_t plane = (size_t)p.inW * p.inH;
-    const int rm = p.rows_max;
-    for (int i = threadIdx.x; i < nr * kRsCols; i += kRsThreads) {
-        const int r = i / kRsCols, c = i % kRsCols;
+    for (int i = threadIdx.x; i < nr * kCols; i += kRsThreads) {
+        const int r = i / kCols, c = i % kCols;
         float a[NP];
 #pragma unroll
         for (int q = 0; q < NP; ++q) a[q] = 0.f;
-        if (c < tw) {
-            const int X = ox0 + c, f = p.fx[X];
+        if (c < tw || (kHalo && c == kRsCols)) {
+            const int X = kHalo && c == kRsCols ? max(ox0 - 1, 0) : ox0 + c, f = p.fx[X];
             const int n = min(p.kx, p.inW - f);
             const float* w = p.wx + (size_t)X * p.kx;
             const float* s = p.canvas + (size_t)(r0 + r) * p.inW + f;
@@ -177,9 +195,15 @@ __device__ __forceinline__ int resample_pass1(const RP& p, float* h) {
             }
         }
 #pragma unroll
-        for (int q = 0; q < NP; ++q) h[(q * rm + r) * kRsCols + c] = a[q];
+        for (int q = 0; q < NP; ++q) h[slot(q, r, c)] = a[q];
     }
     return r0;
+}
+// the plain layout, no halo
+template <int NP, typename RP>
+__device__ __forceinline__ int resample_pass1(const RP& p, float* h) {
+    const int rm = p.rows_max;
+    return resample_pass1_to<NP, false>(p, h, [rm](int q, int r, int c) { return (q * rm + r) * kRsCols + c; });
 }
 // Pass 2: the rows of LDS filtered vertically, four output pixels (X .. X + 3 of row Y, np of them inside the frame) per thread: a[q] their sums of plane q.
 // false: the thread has no pixel to store.
