@@ -30,18 +30,24 @@ struct Image {          // stand-in for cv::Mat of type CV_8UC3
 
 // Extension: planar YUV 4:2:0 frames as ffmpeg's yuv420p / yuv420p10le lay them out (an AVFrame's data[0..2] / linesize[0..2]): a Y plane of
 // rows x cols samples, U (Cb) and V (Cr) planes of ceil(rows/2) x ceil(cols/2); bits 8 (uint8 samples) or 10 (little-endian uint16 holding the low
-// 10 bits); each plane has its own pointer and step in bytes.  Chroma siting MPEG-2 "left" (chroma (i, j) at luma x = 2j, y = 2i + 1/2).
+// 10 bits); each plane has its own pointer and step in bytes.
+// `siting` says where the chroma samples sit, per frame like layout and depth and independent for source and destination: Left (the default;
+// MPEG-2, H.264: chroma (i, j) at luma x = 2j, y = 2i + 1/2), Center (JPEG, MJPEG, MPEG-1: x = 2j + 1/2, y = 2i + 1/2; AVCHROMA_LOC_CENTER) or TopLeft
+// (BT.2020 / UHD: x = 2j, y = 2i; AVCHROMA_LOC_TOPLEFT).  Chroma is upsampled from and filtered onto that grid.  I422 has a column rule only (TopLeft is Left
+// there), I444 none: both are accepted and give Left's bytes.
 // `layout` picks one of four arrangements of the same samples: I420 is the above; I422 (yuv422p / yuv422p10le) has U and V of
 // rows x ceil(cols/2), chroma row y co-sited with luma row y; I444 (yuv444p / yuv444p10le) has U and V of rows x cols; NV12 (nv12 / p010le) is I420
 // with the chroma in ONE plane, planes[1], of ceil(rows/2) rows of 2 * ceil(cols/2) samples U, V, U, V, ... (planes[2] is ignored and may be null) - and
 // at 10 bits it is P010: the code sits in the HIGH 10 bits of each uint16 (read v >> 6, written code << 6), in Y and in UV.
 enum class YuvLayout { I420 = 0, I422 = 1, I444 = 2, NV12 = 3 };
+enum class YuvSiting { Left = 0, Center = 1, TopLeft = 2 };
 struct YuvImage {
     uint8_t* planes[3] = {nullptr, nullptr, nullptr};
     size_t steps[3] = {0, 0, 0};
     int rows = 0, cols = 0;
     int bits = 8;
     YuvLayout layout = YuvLayout::I420;
+    YuvSiting siting = YuvSiting::Left;
 };
 // Extension: a planar RGB frame - three planes of rows x cols samples, each with its own pointer and step (bytes).  planes[0] = R, planes[1] = G,
 // planes[2] = B (a gbrp AVFrame: data[2], data[0], data[1]); the order carries no meaning of its own, the caller orders the pointers.

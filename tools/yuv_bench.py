@@ -11,7 +11,10 @@ The device time of gather_yuv_kernel / compose_yuv_kernel comes from a separate 
 --in-layout / --out-layout {i420,i422,i444,nv12} give the YUV modes' frames another layout on either side (renderSequenceYuv through
 w2x_render_sequence_yuv_layout; with both i420, the default, the call is w2x_render_sequence_yuv as before).  With --outsize the call is
 w2x_render_sequence_yuv_layout_resized (with both i420 w2x_render_sequence_yuv_resized as before): `--outsize 3840x2160 --in-layout nv12 --out-layout
-nv12 --modes 8/8` is the nv12 -> nv12 pair of profiles/yuv_resize_layouts/."""
+nv12 --modes 8/8` is the nv12 -> nv12 pair of profiles/yuv_resize_layouts/.
+
+--siting {left,center,topleft} gives the YUV modes' frames that chroma siting on both sides.  "left", the default, changes nothing about the calls
+above; the others go through w2x_render_sequence_yuv_sited (at the x4 raster as well: there it is the plain sequence)."""
 from __future__ import annotations
 
 import argparse
@@ -49,6 +52,7 @@ def main() -> int:
     ap.add_argument("--outsize", default="", help="WxH: render to this raster (between 1920x1080 and 7680x4320) instead of the x4 one")
     ap.add_argument("--in-layout", default="i420", choices=["i420", "i422", "i444", "nv12"], help="the layout of the YUV modes' input frames")
     ap.add_argument("--out-layout", default="i420", choices=["i420", "i422", "i444", "nv12"], help="the layout of the YUV modes' output frames")
+    ap.add_argument("--siting", default="left", choices=["left", "center", "topleft"], help="the chroma siting of the YUV modes' frames, both sides")
     ap.add_argument("--bytes", action="store_true", help="print the bytes per frame of each mode and exit (no GPU)")
     a = ap.parse_args()
     OW, OH = (int(v) for v in a.outsize.split("x")) if a.outsize else (W * S, H * S)
@@ -121,6 +125,12 @@ def main() -> int:
 
             def region():
                 args = (eng._h, sp, ss, H, W, bits, dp, ds, OH, OW, bits, n, 1, 0)
+                if a.siting != "left":
+                    sid = pkg.YUV_SITINGS[a.siting]
+                    sargs = (*args[:6], pkg.YUV_LAYOUTS[LIN], sid, *args[6:11], pkg.YUV_LAYOUTS[LOUT], sid, *args[11:])
+                    if not eng._L.w2x_render_sequence_yuv_sited(*sargs, 0):
+                        raise SystemExit("render_sequence_yuv_sited failed: " + eng.last_error())
+                    return
                 if with_layout:
                     largs = (*args[:6], pkg.YUV_LAYOUTS[LIN], *args[6:11], pkg.YUV_LAYOUTS[LOUT], *args[11:])
                     if not (eng._L.w2x_render_sequence_yuv_layout_resized(*largs, 0) if resized else eng._L.w2x_render_sequence_yuv_layout(*largs)):
@@ -139,7 +149,7 @@ def main() -> int:
         for b in bufs:
             eng.free_host(b)
     eng.close()
-    layouts = f", {LIN} in -> {LOUT} out" if with_layout else ""
+    layouts = (f", {LIN} in -> {LOUT} out" if with_layout else "") + (f", chroma sited {a.siting}" if a.siting != "left" else "")
     print(json.dumps({"tool": "yuv_bench", "workload": f"{MODEL} x{S} noise{NOISE} batch{BATCH} tile{TILE} fp16, {W}x{H} -> {OW}x{OH} frames, blend 1/16, "
                       f"{'renderSequenceResized (bgr24) / renderSequenceYuvResized' if resized else 'renderSequence (bgr24) / renderSequenceYuv'} (BT.709 limited, in/out bits{layouts}) host to host, page-locked buffers, "
                       f"{a.regions} regions x {n} frames after {a.warmup} warm-up regions", "results": res}))

@@ -4,6 +4,7 @@
 #include "../../include/w2x/c_api_planar.h"
 #include "../../include/w2x/c_api_rgbap.h"
 #include "../../include/w2x/c_api_yuv_resized.h"
+#include "../../include/w2x/c_api_yuv_siting.h"
 #include <mutex>
 
 #include <cstring>
@@ -76,10 +77,11 @@ static bool resize_filter(w2x_engine* e, int filter, const char* who, w2x::Resiz
     return false;
 }
 // the YUV renders: matrix and range go to the engine as given (it refuses unknown values through the message callback)
-static w2x::YuvImage yuv_image(const void* const* planes, const size_t* steps, int rows, int cols, int bits, int layout) {
+static w2x::YuvImage yuv_image(const void* const* planes, const size_t* steps, int rows, int cols, int bits, int layout, int siting = W2X_YUV_SITING_LEFT) {
     w2x::YuvImage f;
     for (int k = 0; k < 3; ++k) { f.planes[k] = planes ? (uint8_t*)const_cast<void*>(planes[k]) : nullptr; f.steps[k] = steps ? steps[k] : 0; }
     f.rows = rows; f.cols = cols; f.bits = bits; f.layout = (w2x::YuvLayout)layout;   // (the engine refuses unknown layouts like unknown matrices)
+    f.siting = (w2x::YuvSiting)siting;
     return f;
 }
 static w2x::YuvFormat yuv_format(int matrix, int range) { w2x::YuvFormat f; f.matrix = (w2x::YuvMatrix)matrix; f.range = (w2x::YuvRange)range; return f; }
@@ -121,11 +123,12 @@ static RgbapSequence rgbap_sequence(const void* const* src_planes, const size_t*
 struct YuvSequence { std::vector<w2x::YuvImage> src, dst; };
 // the frames of a YUV sequence entry: frame i's planes at [3i .. 3i + 2], one set of steps for the sequence
 static YuvSequence yuv_sequence(const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits, int src_layout,
-                                void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int dst_layout, int count) {
+                                void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int dst_layout, int count,
+                                int src_siting = W2X_YUV_SITING_LEFT, int dst_siting = W2X_YUV_SITING_LEFT) {
     YuvSequence q; q.src.reserve(count); q.dst.reserve(count);
     for (int i = 0; i < count; ++i) {
-        q.src.push_back(yuv_image(src_planes + 3 * i, src_steps, rows, cols, src_bits, src_layout));
-        q.dst.push_back(yuv_image(dst_planes + 3 * i, dst_steps, dst_rows, dst_cols, dst_bits, dst_layout));
+        q.src.push_back(yuv_image(src_planes + 3 * i, src_steps, rows, cols, src_bits, src_layout, src_siting));
+        q.dst.push_back(yuv_image(dst_planes + 3 * i, dst_steps, dst_rows, dst_cols, dst_bits, dst_layout, dst_siting));
     }
     return q;
 }
@@ -274,6 +277,25 @@ int w2x_render_sequence_yuv_layout_resized(w2x_engine* e, const void* const* src
     if (!sequence_ok(e, count, src_planes, dst_planes) || !resize_filter(e, filter, "w2x_render_sequence_yuv_layout_resized", f) ||
         !yuv_layouts(e, src_layout, dst_layout, "w2x_render_sequence_yuv_layout_resized")) return 0;
     YuvSequence q = yuv_sequence(src_planes, src_steps, rows, cols, src_bits, src_layout, dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, dst_layout, count);
+    return e->engine.renderSequenceYuvResized(q.src.data(), q.dst.data(), count, yuv_format(matrix, range), f) ? 1 : 0;
+}
+// YUV frames with a chroma siting per side (include/w2x/c_api_yuv_siting.h): the two entries above with the sitings, which go to the engine as given (it refuses
+// unknown values through the message callback, like unknown matrices)
+int w2x_render_yuv_sited(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits, int src_layout, int src_siting,
+                         void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int dst_layout, int dst_siting, int matrix, int range,
+                         int filter) {
+    w2x::ResizeFilter f;
+    if (!e || !resize_filter(e, filter, "w2x_render_yuv_sited", f) || !yuv_layouts(e, src_layout, dst_layout, "w2x_render_yuv_sited")) return 0;
+    w2x::YuvImage d = yuv_image(dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, dst_layout, dst_siting);
+    return e->engine.renderYuvResized(yuv_image(src_planes, src_steps, rows, cols, src_bits, src_layout, src_siting), d, yuv_format(matrix, range), f) ? 1 : 0;
+}
+int w2x_render_sequence_yuv_sited(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits, int src_layout, int src_siting,
+                                  void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int dst_layout, int dst_siting, int count,
+                                  int matrix, int range, int filter) {
+    w2x::ResizeFilter f;
+    if (!sequence_ok(e, count, src_planes, dst_planes) || !resize_filter(e, filter, "w2x_render_sequence_yuv_sited", f) ||
+        !yuv_layouts(e, src_layout, dst_layout, "w2x_render_sequence_yuv_sited")) return 0;
+    YuvSequence q = yuv_sequence(src_planes, src_steps, rows, cols, src_bits, src_layout, dst_planes, dst_steps, dst_rows, dst_cols, dst_bits, dst_layout, count, src_siting, dst_siting);
     return e->engine.renderSequenceYuvResized(q.src.data(), q.dst.data(), count, yuv_format(matrix, range), f) ? 1 : 0;
 }
 int w2x_render_rgba(w2x_engine* e, const uint8_t* src, int rows, int cols, size_t src_step, uint8_t* dst, size_t dst_step, int bleed, int skip_uniform_alpha) {

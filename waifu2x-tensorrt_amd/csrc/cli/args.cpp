@@ -72,6 +72,9 @@ std::string usage() {
            "      --colorspace TEXT       (extension) {bt601,bt709,bt2020}: videos read through ffmpeg stay YUV 4:2:0 at --pix_fmt\n"
            "                              (yuv420p or yuv420p10le) and are converted on the GPU; the output carries the colour tags\n"
            "      --color_range TEXT [tv] (extension) {tv,pc}: the range of the --colorspace frames\n"
+           "      --chroma-loc TEXT [left] (extension) with --colorspace: {left,center,topleft}, where the chroma samples of the frames sit (left: MPEG-2 / H.264,\n"
+           "                              center: JPEG / MJPEG / MPEG-1, topleft: BT.2020 / UHD); chroma is resampled on that grid both ways and the writer is\n"
+           "                              handed -chroma_sample_location\n"
            "      --yuv-in FMT            (extension) with --colorspace: the raw format asked of the ffmpeg reader [--pix_fmt], one of\n"
            "                              {yuv420p,yuv420p10le,yuv422p,yuv422p10le,yuv444p,yuv444p10le,nv12,p010le}; converted on the GPU\n"
            "      --yuv-out FMT           (extension) with --colorspace: the raw format handed to the writer [--pix_fmt], same choices; --pix_fmt is then\n"
@@ -175,6 +178,7 @@ Options parse(int argc, const char* const* argv) {
         else if (k == "--resize-filter") { o.resizeFilter = value(i); std::transform(o.resizeFilter.begin(), o.resizeFilter.end(), o.resizeFilter.begin(), ::tolower); seen_filter = true; }
         else if (k == "--colorspace") { o.colorspace = value(i); std::transform(o.colorspace.begin(), o.colorspace.end(), o.colorspace.begin(), ::tolower); seen_colorspace = true; }
         else if (k == "--color_range") { o.colorRange = value(i); std::transform(o.colorRange.begin(), o.colorRange.end(), o.colorRange.begin(), ::tolower); seen_range = true; }
+        else if (k == "--chroma-loc") { o.chromaLoc = value(i); std::transform(o.chromaLoc.begin(), o.chromaLoc.end(), o.chromaLoc.begin(), ::tolower); }
         else if (k == "--yuv-in") o.yuvIn = value(i);
         else if (k == "--yuv-out") o.yuvOut = value(i);
         else if (k == "--rgb-in") o.rgbIn = value(i);
@@ -202,7 +206,7 @@ Options parse(int argc, const char* const* argv) {
     if (o.devices < 1) throw std::runtime_error("--devices: number must be positive");
     member<std::string>("--split", o.split, {"shards", "strips"});
     member<std::string>("--precision", o.precision, {"fp16", "tf32", "fp32"});   // fp32: an addition (include/w2x/config.h)
-    const bool seen_yuv_in = !o.yuvIn.empty(), seen_yuv_out = !o.yuvOut.empty();
+    const bool seen_yuv_in = !o.yuvIn.empty(), seen_yuv_out = !o.yuvOut.empty(), seen_loc = !o.chromaLoc.empty();
     const bool seen_rgb_in = !o.rgbIn.empty(), seen_rgb_out = !o.rgbOut.empty();
     const bool seen_rgba_in = !o.rgbaIn.empty(), seen_rgba_out = !o.rgbaOut.empty();
     if (o.command == "render") {
@@ -233,6 +237,7 @@ Options parse(int argc, const char* const* argv) {
         if (seen_colorspace) {
             member<std::string>("--colorspace", o.colorspace, {"bt601", "bt709", "bt2020"});
             member<std::string>("--color_range", o.colorRange, {"tv", "pc"});
+            if (seen_loc) member<std::string>("--chroma-loc", o.chromaLoc, {"left", "center", "topleft"});
             for (const char* opt : {"--yuv-in", "--yuv-out"}) {
                 const std::string& v = opt[6] == 'i' ? o.yuvIn : o.yuvOut;
                 if (v.empty()) continue;
@@ -244,6 +249,7 @@ Options parse(int argc, const char* const* argv) {
             if (seen_outscale) throw std::runtime_error("--colorspace: not together with --outscale (a factor rarely gives the even sizes video wants: use --outsize WxH)");
         } else if (seen_range) throw std::runtime_error("--color_range: needs --colorspace");
         else if (seen_yuv_in || seen_yuv_out) throw std::runtime_error(std::string(seen_yuv_in ? "--yuv-in" : "--yuv-out") + ": needs --colorspace");
+        else if (seen_loc) throw std::runtime_error("--chroma-loc: needs --colorspace");
         if (seen_gray) {
             if (seen_colorspace) throw std::runtime_error("--gray: not together with --colorspace (gray frames carry no chroma)");
             if (o.devices > 1) throw std::runtime_error("--gray: not with --devices " + std::to_string(o.devices) + " (gray frames are rendered on one device)");
@@ -273,8 +279,8 @@ Options parse(int argc, const char* const* argv) {
     } else if (seen_gray) throw std::runtime_error("--gray: only with render");
     else if (seen_rgb_in || seen_rgb_out) throw std::runtime_error(std::string(seen_rgb_in ? "--rgb-in" : "--rgb-out") + ": only with render");
     else if (seen_rgba_in || seen_rgba_out) throw std::runtime_error(std::string(seen_rgba_in ? "--rgba-in" : "--rgba-out") + ": only with render");
-    else if (seen_outscale || seen_outsize || seen_filter || seen_colorspace || seen_range || seen_bleed || seen_skip || seen_yuv_in || seen_yuv_out)
-        throw std::runtime_error(std::string(seen_yuv_in ? "--yuv-in" : seen_yuv_out ? "--yuv-out" : seen_outscale ? "--outscale" : seen_outsize ? "--outsize" : seen_filter ? "--resize-filter" : seen_colorspace ? "--colorspace" :
+    else if (seen_outscale || seen_outsize || seen_filter || seen_colorspace || seen_range || seen_bleed || seen_skip || seen_yuv_in || seen_yuv_out || seen_loc)
+        throw std::runtime_error(std::string(seen_loc ? "--chroma-loc" : seen_yuv_in ? "--yuv-in" : seen_yuv_out ? "--yuv-out" : seen_outscale ? "--outscale" : seen_outsize ? "--outsize" : seen_filter ? "--resize-filter" : seen_colorspace ? "--colorspace" :
                                              seen_range ? "--color_range" : seen_bleed ? "--alpha-bleed" : "--alpha-skip-uniform") + ": only with render");
     // cross-checks, main.cpp:142-145
     if (o.model == "cunet/art" && o.scale == 4) throw std::runtime_error("cunet/art does not support scale factor 4.");
@@ -325,6 +331,7 @@ std::string to_json(const Options& o) {
        << ", \"outscale\": " << (o.outscale > 0 ? std::to_string(o.outscale) : std::string("null")) << ", \"outsize\": " << (o.outsizeW > 0 ? "[" + std::to_string(o.outsizeW) + ", " + std::to_string(o.outsizeH) + "]" : std::string("null"))
        << ", \"resize_filter\": " << q(o.resizeFilter)
        << ", \"colorspace\": " << (o.colorspace.empty() ? std::string("null") : q(o.colorspace)) << ", \"color_range\": " << q(o.colorRange)
+       << ", \"chroma_loc\": " << (o.chromaLoc.empty() ? std::string("null") : q(o.chromaLoc))
        << ", \"yuv_in\": " << (o.yuvIn.empty() ? std::string("null") : q(o.yuvIn)) << ", \"yuv_out\": " << (o.yuvOut.empty() ? std::string("null") : q(o.yuvOut))
        << ", \"alpha_bleed\": " << o.alphaBleed << ", \"alpha_skip_uniform\": " << (o.alphaSkipUniform ? "true" : "false") << ", \"gray\": " << (o.gray ? "true" : "false")
        << ", \"rgb_in\": " << (o.rgbIn.empty() ? std::string("null") : q(o.rgbIn)) << ", \"rgb_out\": " << (o.rgbOut.empty() ? std::string("null") : q(o.rgbOut))

@@ -39,6 +39,8 @@ struct Options {
     std::string resizeFilter = "bicubic"; // --resize-filter {bicubic,bilinear}: the antialiasing filter of --outscale / --outsize
     std::string colorspace;               // --colorspace {bt601,bt709,bt2020}: videos read through ffmpeg travel as raw --pix_fmt (yuv420p / yuv420p10le)
                                           // frames, converted on the GPU (Img2Img::renderSequenceYuv); "" = bgr24 frames, the reference's path
+    std::string chromaLoc;                // --chroma-loc {left,center,topleft} (with --colorspace only): where the chroma samples of those frames sit, both for the frames read and
+                                          // the frames written (YuvImage::siting); empty = not given (left)
     std::string colorRange = "tv";        // --color_range {tv,pc}: the range of those frames (with --colorspace only)
     std::string yuvIn, yuvOut;            // --yuv-in / --yuv-out FMT (with --colorspace only; kYuvFormats): the raw format asked of the ffmpeg reader / handed to the
                                           // writer, converted on the GPU in either direction (YuvImage::layout); "" = --pix_fmt, which with --yuv-out given is the

@@ -99,7 +99,8 @@ std::string colour_tags(const cli::Options& o) {
     const char* m = o.colorspace == "bt601" ? "smpte170m" : o.colorspace == "bt2020" ? "bt2020nc" : "bt709";
     const char* pr = o.colorspace == "bt601" ? "smpte170m" : o.colorspace == "bt2020" ? "bt2020" : "bt709";
     const char* trc = o.colorspace == "bt601" ? "smpte170m" : o.colorspace == "bt2020" ? "bt2020-10" : "bt709";
-    return std::string("-colorspace ") + m + " -color_primaries " + pr + " -color_trc " + trc + " -color_range " + o.colorRange + " ";
+    const std::string loc = o.chromaLoc.empty() ? "" : "-chroma_sample_location " + o.chromaLoc + " ";   // --chroma-loc
+    return std::string("-colorspace ") + m + " -color_primaries " + pr + " -color_trc " + trc + " -color_range " + o.colorRange + " " + loc;
 }
 
 // ---- frame streams: raw bgr24 (or --colorspace: YUV 4:2:0) frames from / to an ffmpeg pipe or a built-in uncompressed AVI
@@ -448,9 +449,10 @@ int main(int argc, char** argv) {
                     YuvFormat f;
                     f.matrix = o.colorspace == "bt601" ? YuvMatrix::BT601 : o.colorspace == "bt2020" ? YuvMatrix::BT2020 : YuvMatrix::BT709;
                     f.range = o.colorRange == "pc" ? YuvRange::Full : YuvRange::Limited;
+                    const YuvSiting siting = o.chromaLoc == "center" ? YuvSiting::Center : o.chromaLoc == "topleft" ? YuvSiting::TopLeft : YuvSiting::Left;   // --chroma-loc: both sides
                     render = [=](Img2Img& e, uint8_t* const* in, uint8_t* const* out, int n) {
                         std::vector<YuvImage> si(n), di(n);
-                        for (int k = 0; k < n; ++k) { si[k] = packed_yuv(in[k], height, width, fmtIn); di[k] = packed_yuv(out[k], outH, outW, fmtOut); }
+                        for (int k = 0; k < n; ++k) { si[k] = packed_yuv(in[k], height, width, fmtIn); di[k] = packed_yuv(out[k], outH, outW, fmtOut); si[k].siting = di[k].siting = siting; }
                         return resize ? e.renderSequenceYuvResized(si.data(), di.data(), n, f, filter) : e.renderSequenceYuv(si.data(), di.data(), n, f);
                     };
                 }

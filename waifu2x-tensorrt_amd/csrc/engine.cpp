@@ -325,13 +325,16 @@ struct Img2Img::Impl {
         int inW = 0, inH = 0, outW = 0, outH = 0, filter = 0;
         int *fx = nullptr, *fy = nullptr; float *wx = nullptr, *wy = nullptr;
         int kx = 0, ky = 0, rows_max = 0;
+        int rows_max_above = 0;                                              // rows_max of a tile and the output row above it (top-left sited 4:2:0 output)
     };
     std::deque<ResizeTables> rs_tables;
     // YUV frames (renderYuv / renderSequenceYuv): d_frame / d_out hold the planes of in_layout / out_layout (yuv_layout; kernels.h kYuvI420 ..) and the gather /
     // compose launches are gather_yuv_kernel / compose_yuv_kernel (4:4:4 output: compose_yuv444_kernel); `key` tells the captured passes of each input format -
     // depth, range, matrix, layout - apart.  Resized (renderYuvResized) the frame ends with compose_canvas_kernel and the resample kernel of out_layout
     // (launch_resample_yuv, k_resample_yuv.hip), and d_out holds out_layout's planes of the target size.
-    struct YuvJob { YuvCoefs in, out; int in_bits = 8, out_bits = 8, key = 0, in_layout = kYuvI420, out_layout = kYuvI420; };
+    // in_siting / out_siting: where the chroma samples of each side sit (kYuvLeft ..); the kernels are instantiated per siting, and the source's is
+    // part of `key` (a captured pass bakes its gather kernel in).
+    struct YuvJob { YuvCoefs in, out; int in_bits = 8, out_bits = 8, key = 0, in_layout = kYuvI420, out_layout = kYuvI420, in_siting = kYuvLeft, out_siting = kYuvLeft; };
     // RGBA frames (renderRgba, renderRgbaResized, renderSequenceRgba*): d_frame holds the uploaded BGRA frame, alpha_bleed_kernel writes the BGR frame and the alpha
     // plane the passes gather from (gather_rgba_kernel), d_minmax receives max(A) and max(255 - A), read back into the page-locked h_minmax behind the kernel.  The
     // frame step is rgba_frame(); resized it ends with compose_canvas_rgba_kernel and resample_rgba_kernel.
@@ -443,7 +446,7 @@ struct Img2Img::Impl {
     // enqueueV3 (img2img_infer.cpp:80); here a pass is ~40 launches, which the host cannot issue fast enough for small tiles.
     // A pass is captured the second time it is met (the first run stays eager so that one-time attribute calls are out of the
     // way) and replayed from then on.  The key holds everything the captured launches bake in.
-    static constexpr int kRgbaKey = 64;   // (YuvJob::key stays below 50)
+    static constexpr int kRgbaKey = 64;   // (YuvJob::key stays below 50 for left-sited sources and is 100 .. 149 / 200 .. 249 for centre / top-left sited ones)
     static constexpr int kGrayKey = 65;   // 65 / 66: gray frames of 8 / 16 bits
     static constexpr int kPlanarKey = 67; // 67 .. 71: planar frames whose input samples have 8 / 10 / 12 / 16 / 32 bits
     static constexpr int kPlanarRgbaKey = 72; // 72 .. 76: planar RGBA frames, by input depth likewise
@@ -1330,7 +1333,7 @@ struct Img2Img::Impl {
             case Job::BGR: hipAssert(launch_gather(gp, gs)); break;
             case Job::YUV: {                                          // the same tiles from the frame's planes
                 GatherYuvParams p = tile_side<GatherYuvParams>(gp);
-                p.src = yuv_layout(d_frame, gp.rows, gp.cols, job.yuv.in_bits, job.yuv.in_layout); p.k = job.yuv.in;
+                p.src = yuv_layout(d_frame, gp.rows, gp.cols, job.yuv.in_bits, job.yuv.in_layout); p.src.siting = job.yuv.in_siting; p.k = job.yuv.in;
                 hipAssert(launch_gather_yuv(p, gs));
                 break;
             }
@@ -1401,8 +1404,8 @@ struct Img2Img::Impl {
             case Job::YUV: {                                          // the planes of job.yuv.out_layout at the target size
                 ResampleYuvParams p;
                 resample_base(p);
-                p.dst = yuv_layout(d_out, p.outH, p.outW, job.yuv.out_bits, job.yuv.out_layout); p.k = job.yuv.out;
-                hipAssert(launch_resample_yuv(p, on));
+                p.dst = yuv_layout(d_out, p.outH, p.outW, job.yuv.out_bits, job.yuv.out_layout); p.dst.siting = job.yuv.out_siting; p.k = job.yuv.out;
+                hipAssert(launch_resample_yuv(p, job.rs->rows_max_above, on));
                 break;
             }
         }
@@ -1413,7 +1416,7 @@ struct Img2Img::Impl {
             case Job::YUV: {                                          // the planes of job.yuv.out_layout
                 ComposeYuvParams p;
                 p.c = compose_base(rows, cols, grid);
-                p.dst = yuv_layout(d_out, p.c.outH, p.c.outW, job.yuv.out_bits, job.yuv.out_layout); p.k = job.yuv.out;
+                p.dst = yuv_layout(d_out, p.c.outH, p.c.outW, job.yuv.out_bits, job.yuv.out_layout); p.dst.siting = job.yuv.out_siting; p.k = job.yuv.out;
                 stamp_begin(4, 0);
                 hipAssert(launch_compose_yuv(p, on));
                 stamp_end();
@@ -1524,6 +1527,9 @@ struct Img2Img::Impl {
         const int in_layout = (int)srcs[0].layout, out_layout = (int)dsts[0].layout;
         if (in_layout < kYuvI420 || in_layout > kYuvNV12 || out_layout < kYuvI420 || out_layout > kYuvNV12)
             return "Unknown YUV layout " + std::to_string(in_layout < kYuvI420 || in_layout > kYuvNV12 ? in_layout : out_layout) + ".";
+        const int in_siting = (int)srcs[0].siting, out_siting = (int)dsts[0].siting;
+        if (in_siting < kYuvLeft || in_siting > kYuvTopLeft || out_siting < kYuvLeft || out_siting > kYuvTopLeft)
+            return "Unknown YUV chroma siting " + std::to_string(in_siting < kYuvLeft || in_siting > kYuvTopLeft ? in_siting : out_siting) + ".";
         if (const std::string why = call_target(resizeFilter, dsts[0], rows, cols, true, c); !why.empty()) return why;
         // every plane of the layout present (NV12: Y and UV), with a step that holds its row
         auto planes_ok = [](const YuvImage& f) {
@@ -1533,6 +1539,7 @@ struct Img2Img::Impl {
         };
         for (int i = 0; i < count; ++i) {
             if ((int)srcs[i].layout != in_layout || (int)dsts[i].layout != out_layout) return "The frames of a sequence must be of one layout (one for the inputs, one for the outputs).";
+            if ((int)srcs[i].siting != in_siting || (int)dsts[i].siting != out_siting) return "The frames of a sequence must be of one chroma siting (one for the inputs, one for the outputs).";
             if (srcs[i].rows != rows || srcs[i].cols != cols || srcs[i].bits != in_bits) return "Input images must be of one size and depth.";
             if (!planes_ok(srcs[i])) return "Input image has a missing plane or an invalid step.";
             if (dsts[i].rows != c.out_rows || dsts[i].cols != c.out_cols) return out_size_text(c);
@@ -1775,6 +1782,7 @@ struct Img2Img::Impl {
         ResizeTables t;
         t.inW = inW; t.inH = inH; t.outW = outW; t.outH = outH; t.filter = filter; t.kx = tx.taps; t.ky = ty.taps;
         t.rows_max = resample_rows_max(ty.first.data(), outH, inH, ty.taps);
+        t.rows_max_above = resample_rows_max(ty.first.data(), outH, inH, ty.taps, 1);
         auto upload = [&](auto*& d, const auto& v) {
             hipAssert(hipMalloc((void**)&d, v.size() * sizeof(v[0])));
             hipAssert(hipMemcpy(d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
@@ -2468,7 +2476,10 @@ bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, Yu
     impl->job.kind = Impl::Job::YUV;
     job.in = yuv_coefs(matrix, range, in_bits); job.out = yuv_coefs(matrix, range, out_bits);
     job.in_bits = in_bits; job.out_bits = out_bits; job.in_layout = in_layout; job.out_layout = (int)dsts[0].layout;
+    job.in_siting = (int)srcs[0].siting; job.out_siting = (int)dsts[0].siting;
     job.key = 2 + (in_bits == 10 ? 1 : 0) + 2 * range + 4 * matrix + 12 * in_layout;   // 2 .. 13 per layout: 2 .. 49, below kRgbaKey
+    // the siting the gather launch dispatches on (launch_gather_yuv: I444 none, I422 the column rule alone): centre 102 .. 149, top-left 202 .. 249, above every other format's key
+    job.key += 100 * (in_layout == kYuvI444 || (in_layout == kYuvI422 && job.in_siting == kYuvTopLeft) ? kYuvLeft : job.in_siting);
     // the planes of a frame (NV12 two, else three) between the caller's layout and the device's (yuv_layout), on copy stream `on`
     auto copy_planes = [&](const YuvImage& host, uint8_t* dev, int r, int c, bool up, hipStream_t on) {
         const int layout = (int)host.layout;

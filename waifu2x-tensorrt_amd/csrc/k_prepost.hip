@@ -189,8 +189,27 @@ __device__ __forceinline__ float yuv_chroma(const YuvPlanes& f, int pl, int y, i
 // 2k takes 1/4 C[k-1] + 3/4 C[k], 2k+1 takes 3/4 C[k] + 1/4 C[k+1]; indices clamped), the matrix inverted in fp32, R, G, B clamped to [0, 1].
 // (The upsampled codes are exact in fp32: integers below 2^10 times quarters.)  That is I420, and NV12 through yuv_luma / yuv_chroma; I422 keeps the
 // column rule and takes chroma row fy itself; I444 takes the chroma of the pixel.
-template <typename P, int L>
+// S: the siting of the frame's chroma.  kYuvLeft is the above, its statements untouched.  The others take the same 2 x 2 neighbourhood by
+// yuv_axis_taps, one 1-D rule per axis: kYuvCenter centred columns (1/4, 3/4 like the rows), kYuvTopLeft co-sited rows (the column rule's shape); the codes
+// stay exact (integers below 2^10 times sixteenths).  I422 has the column rule only, so its kYuvTopLeft is kYuvLeft, as every siting of I444 is
+// (launch_gather_yuv).
+// The two chroma samples and weights of luma index n along one axis of cn samples: co-sited - even n C[n/2] alone, odd n the mean of C[(n-1)/2] and
+// C[(n+1)/2]; centred - n = 2k 1/4 C[k-1] + 3/4 C[k], n = 2k+1 3/4 C[k] + 1/4 C[k+1]; indices clamped to the plane.
+template <bool kCentred>
+__device__ __forceinline__ void yuv_axis_taps(int n, int cn, int& i0, int& i1, float& w0, float& w1) {
+    const int k = n >> 1;
+    const bool odd = n & 1;
+    if constexpr (kCentred) {
+        i0 = odd ? k : max(k - 1, 0); i1 = odd ? min(k + 1, cn - 1) : k;
+        w0 = odd ? 0.75f : 0.25f; w1 = odd ? 0.25f : 0.75f;
+    } else {
+        i0 = k; i1 = odd ? min(k + 1, cn - 1) : k;
+        w0 = 0.5f; w1 = 0.5f;
+    }
+}
+template <typename P, int L, int S = kYuvLeft>
 __global__ __launch_bounds__(256) void gather_yuv_kernel(const GatherYuvParams p) {
+    static_assert(S == kYuvLeft || L == kYuvI420 || L == kYuvNV12 || (L == kYuvI422 && S == kYuvCenter), "a siting the layout does not tell from kYuvLeft");
     const int T = p.T;
     const long total = (long)p.B * T * T;
     const int rows = p.src.rows, cols = p.src.cols, ch = (rows + 1) >> 1, cw = (cols + 1) >> 1;
@@ -206,7 +225,14 @@ __global__ __launch_bounds__(256) void gather_yuv_kernel(const GatherYuvParams p
             aug_src(sl.aug, T - 1, y, x, sy, sx);
             const int fy = min(max(sl.y + sy, 0), rows - 1), fx = min(max(sl.x + sx, 0), cols - 1);
             float u, w;
-            if constexpr (L == kYuvI444) {
+            if constexpr (S != kYuvLeft) {
+                int c0, c1, r0 = fy, r1 = fy;
+                float wc0, wc1, w0 = 0.5f, w1 = 0.5f;
+                yuv_axis_taps<yuv_cols_centred(S)>(fx, cw, c0, c1, wc0, wc1);
+                if constexpr (L != kYuvI422) yuv_axis_taps<yuv_rows_centred(S)>(fy, ch, r0, r1, w0, w1);
+                u = w0 * (wc0 * yuv_chroma<L>(p.src, 1, r0, c0) + wc1 * yuv_chroma<L>(p.src, 1, r0, c1)) + w1 * (wc0 * yuv_chroma<L>(p.src, 1, r1, c0) + wc1 * yuv_chroma<L>(p.src, 1, r1, c1));
+                w = w0 * (wc0 * yuv_chroma<L>(p.src, 2, r0, c0) + wc1 * yuv_chroma<L>(p.src, 2, r0, c1)) + w1 * (wc0 * yuv_chroma<L>(p.src, 2, r1, c0) + wc1 * yuv_chroma<L>(p.src, 2, r1, c1));
+            } else if constexpr (L == kYuvI444) {
                 u = yuv_chroma<L>(p.src, 1, fy, fx); w = yuv_chroma<L>(p.src, 2, fy, fx);
             } else if constexpr (L == kYuvI422) {
                 const int cj = fx >> 1, c1 = (fx & 1) ? min(cj + 1, cw - 1) : cj;
@@ -240,12 +266,20 @@ __device__ __forceinline__ unsigned yuv_code(float off, float scale, float v, in
 // L: kYuvI420 is the above.  kYuvNV12 is the same arithmetic with U and V stored interleaved in plane 1 (8 bytes per full run, 10-bit: 16)
 // and, at 10 bits, every code shifted into the high bits (P010).  kYuvI422 has one luma row per chroma row: no vertical pair, a thread owns four
 // sites (8 luma columns) of row i and filters the columns of that row alone.
-template <typename P, int L>
+// S: the siting of the chroma sites.  kYuvLeft is the above.  kYuvCenter: site j is the mean of columns 2j and 2j + 1 (of the two rows averaged, as
+// above) - nothing from the lane on the left, no cross-lane move, no column recomputed by lane 0.  kYuvTopLeft (I420 / NV12; I422 has no row rule and takes
+// kYuvLeft): site (i, j) filters rows 2i - 1, 2i, 2i + 1 (1/4, 1/2, 1/4) and then the columns as kYuvLeft does.  Row 2i - 1 is the second row of the chroma row
+// above, so a workgroup walks a BAND of kYuvBand consecutive chroma rows (blockIdx.y picks the band) and carries that row's clamped R, G, B - 8 columns x 3
+// floats per lane and lane 0's left column - in registers from one chroma row into the next; only the luma row above a band's first chroma row is computed a
+// second time (row -1 clamps to row 0: nothing to compute).  Pixel sums: (2 kYuvBand + 1) / (2 kYuvBand) of kYuvLeft's.
+template <typename P, int L, int S = kYuvLeft>
 __global__ __launch_bounds__(kYuvThreads) void compose_yuv_kernel(const ComposeYuvParams p) {
     static_assert(kYuvSites == 4, "the packed stores below are written for four sites per thread");
     static_assert(L == kYuvI420 || L == kYuvI422 || L == kYuvNV12, "4:4:4 output is compose_yuv444_kernel");
+    static_assert(S == kYuvLeft || S == kYuvCenter || (S == kYuvTopLeft && L != kYuvI422), "I422 has no row rule: its kYuvTopLeft is kYuvLeft");
     constexpr int kCols = 2 * kYuvSites;
     constexpr bool kPair = L != kYuvI422, kSemi = L == kYuvNV12;
+    constexpr bool kBand = S == kYuvTopLeft, kLeftCol = S != kYuvCenter;   // rows 2i - 1 carried down a band; column 2j - 1 taken from the left
     const ComposeParams& c = p.c;
     const P* tiles = (const P*)c.tiles;
     const YuvCoefs& k = p.k;
@@ -262,10 +296,25 @@ __global__ __launch_bounds__(kYuvThreads) void compose_yuv_kernel(const ComposeY
         compose_pixel_sums<P>(c, tiles, X, Y, r, g, b);
         o[0] = fminf(fmaxf(r, 0.f), 1.f); o[1] = fminf(fmaxf(g, 0.f), 1.f); o[2] = fminf(fmaxf(b, 0.f), 1.f);
     };
-    for (int ci = blockIdx.y; ci < ch; ci += gridDim.y) {
+    // the chroma rows of this workgroup: every gridDim.y-th, or (kBand) the kYuvBand consecutive rows of band blockIdx.y
+    const int ci0 = kBand ? blockIdx.y * kYuvBand : blockIdx.y;
+    float above[kBand ? kCols : 1][3] = {}, above_left[3] = {0.f, 0.f, 0.f};   // kBand: luma row 2 ci - 1 (clamped R, G, B), and its column X0 - 1 in lane 0
+    for (int ci = ci0; ci < (kBand ? min(ch, ci0 + kYuvBand) : ch); ci += kBand ? 1 : gridDim.y) {
         const int Ya = kPair ? 2 * ci : ci, Yb = kPair ? min(2 * ci + 1, H - 1) : ci;
-        float v[kCols][3];                                      // the run's columns, the two rows averaged
+        float v[kCols][3];                                      // the run's columns, the two rows averaged (kBand: rows 2i - 1, 2i, 2i + 1 by 1/4, 1/2, 1/4)
         float left[3] = {0.f, 0.f, 0.f};
+        if constexpr (kBand) {
+            if (ci == ci0 && ci > 0) {                              // the band's first chroma row: the luma row above it comes from the tiles once more
+#pragma unroll
+                for (int q = 0; q < kCols; ++q) {
+                    float o[3] = {0.f, 0.f, 0.f};
+                    if (q < ncols) pixel(X0 + q, Ya - 1, o);
+#pragma unroll
+                    for (int e = 0; e < 3; ++e) above[q][e] = o[e];
+                }
+                if (threadIdx.x == 0 && active && X0 > 0) pixel(X0 - 1, Ya - 1, above_left);
+            }
+        }
         for (int r = 0; r < (kPair ? 2 : 1); ++r) {
             const int Y = r ? Yb : Ya;
             const bool store_y = r == 0 || Yb != Ya;
@@ -275,14 +324,30 @@ __global__ __launch_bounds__(kYuvThreads) void compose_yuv_kernel(const ComposeY
                 float o[3] = {0.f, 0.f, 0.f};
                 if (q < ncols) pixel(X0 + q, Y, o);
                 yc[q] = yuv_code(k.y_off, k.y_scale, k.kr * o[0] + k.kg * o[1] + k.kb * o[2], k.maxcode) << sh;
+                if constexpr (kBand) {
 #pragma unroll
-                for (int e = 0; e < 3; ++e) v[q][e] = r ? 0.5f * (v[q][e] + o[e]) : o[e];
+                    for (int e = 0; e < 3; ++e) {                   // row 2i: 1/4 of the row above (row -1 clamps to row 0) + 1/2; row 2i + 1: + 1/4, and carried down
+                        if (r == 0) v[q][e] = 0.25f * (ci ? above[q][e] : o[e]) + 0.5f * o[e];
+                        else { v[q][e] += 0.25f * o[e]; above[q][e] = o[e]; }
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 3; ++e) v[q][e] = r ? 0.5f * (v[q][e] + o[e]) : o[e];
+                }
             }
-            if (threadIdx.x == 0 && active && X0 > 0) {              // the wave's first lane: column X0 - 1 from the tiles
+            if (kLeftCol && threadIdx.x == 0 && active && X0 > 0) {  // the wave's first lane: column X0 - 1 from the tiles
                 float o[3];
                 pixel(X0 - 1, Y, o);
+                if constexpr (kBand) {
 #pragma unroll
-                for (int e = 0; e < 3; ++e) left[e] = r ? 0.5f * (left[e] + o[e]) : o[e];
+                    for (int e = 0; e < 3; ++e) {
+                        if (r == 0) left[e] = 0.25f * (ci ? above_left[e] : o[e]) + 0.5f * o[e];
+                        else { left[e] += 0.25f * o[e]; above_left[e] = o[e]; }
+                    }
+                } else {
+#pragma unroll
+                    for (int e = 0; e < 3; ++e) left[e] = r ? 0.5f * (left[e] + o[e]) : o[e];
+                }
             }
             if (!active || !store_y) continue;
             uint8_t* row = p.dst.p[0] + (size_t)Y * p.dst.step[0];
@@ -299,11 +364,13 @@ __global__ __launch_bounds__(kYuvThreads) void compose_yuv_kernel(const ComposeY
             }
         }
         // column X0 - 1: the left lane's last column (every lane takes part in the move; lane 0 keeps its own)
+        if constexpr (kLeftCol) {
 #pragma unroll
-        for (int e = 0; e < 3; ++e) {
-            const float from_left = __shfl_up(v[kCols - 1][e], 1);
-            if (threadIdx.x != 0) left[e] = from_left;
-            if (X0 == 0) left[e] = v[0][e];                          // column -1 clamps to column 0
+            for (int e = 0; e < 3; ++e) {
+                const float from_left = __shfl_up(v[kCols - 1][e], 1);
+                if (threadIdx.x != 0) left[e] = from_left;
+                if (X0 == 0) left[e] = v[0][e];                      // column -1 clamps to column 0
+            }
         }
         if (!active) continue;
         const int nsites = min(kYuvSites, cw - j0);
@@ -313,7 +380,7 @@ __global__ __launch_bounds__(kYuvThreads) void compose_yuv_kernel(const ComposeY
             const int qc = 2 * s, qr = min(2 * s + 1, ncols - 1);   // column 2j + 1 clamped to the frame (odd W)
             float f[3];
 #pragma unroll
-            for (int e = 0; e < 3; ++e) f[e] = 0.25f * (s ? v[qc - 1][e] : left[e]) + 0.5f * v[qc][e] + 0.25f * v[qr][e];
+            for (int e = 0; e < 3; ++e) f[e] = kLeftCol ? 0.25f * (s ? v[qc - 1][e] : left[e]) + 0.5f * v[qc][e] + 0.25f * v[qr][e] : 0.5f * v[qc][e] + 0.5f * v[qr][e];
             const float Y = k.kr * f[0] + k.kg * f[1] + k.kb * f[2];
             uc[s] = yuv_code(k.c_off, k.c_scale, (f[2] - Y) * k.cb_div, k.maxcode);
             vc[s] = yuv_code(k.c_off, k.c_scale, (f[0] - Y) * k.cr_div, k.maxcode);
@@ -556,29 +623,57 @@ hipError_t launch_compose_canvas(const ComposeParams& p, float* canvas, hipStrea
     else hipLaunchKernelGGL(compose_canvas_kernel<half4>, grid, dim3(256), 0, s, p, canvas);
     return hipGetLastError();
 }
-template <int L>
+template <int L, int S = kYuvLeft>
 static void launch_gather_yuv_as(const GatherYuvParams& p, dim3 grid, hipStream_t s) {
-    if (p.fp32) hipLaunchKernelGGL((gather_yuv_kernel<float4v, L>), grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL((gather_yuv_kernel<half4, L>), grid, dim3(256), 0, s, p);
+    if (p.fp32) hipLaunchKernelGGL((gather_yuv_kernel<float4v, L, S>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((gather_yuv_kernel<half4, L, S>), grid, dim3(256), 0, s, p);
+}
+// The siting a layout tells apart: I444 none, I422 the column rule alone (kYuvTopLeft is kYuvLeft); -1: no such siting
+static int yuv_effective_siting(int layout, int siting) {
+    if (siting < kYuvLeft || siting > kYuvTopLeft) return -1;
+    if (layout == kYuvI444 || (layout == kYuvI422 && siting == kYuvTopLeft)) return kYuvLeft;
+    return siting;
 }
 hipError_t launch_gather_yuv(const GatherYuvParams& p, hipStream_t s) {
     const dim3 grid(grid_for((long)p.B * p.T * p.T));
-    switch (p.src.layout) {
-        case kYuvI420: launch_gather_yuv_as<kYuvI420>(p, grid, s); break;
-        case kYuvI422: launch_gather_yuv_as<kYuvI422>(p, grid, s); break;
-        case kYuvI444: launch_gather_yuv_as<kYuvI444>(p, grid, s); break;
-        case kYuvNV12: launch_gather_yuv_as<kYuvNV12>(p, grid, s); break;
-        default: return hipErrorInvalidValue;                       // no kernel for it: an error, never another layout's kernel
+    switch (yuv_effective_siting(p.src.layout, p.src.siting)) {
+        case kYuvLeft:
+            switch (p.src.layout) {
+                case kYuvI420: launch_gather_yuv_as<kYuvI420>(p, grid, s); break;
+                case kYuvI422: launch_gather_yuv_as<kYuvI422>(p, grid, s); break;
+                case kYuvI444: launch_gather_yuv_as<kYuvI444>(p, grid, s); break;
+                case kYuvNV12: launch_gather_yuv_as<kYuvNV12>(p, grid, s); break;
+                default: return hipErrorInvalidValue;               // no kernel for it: an error, never another layout's kernel
+            }
+            break;
+        case kYuvCenter:
+            switch (p.src.layout) {
+                case kYuvI420: launch_gather_yuv_as<kYuvI420, kYuvCenter>(p, grid, s); break;
+                case kYuvI422: launch_gather_yuv_as<kYuvI422, kYuvCenter>(p, grid, s); break;
+                case kYuvNV12: launch_gather_yuv_as<kYuvNV12, kYuvCenter>(p, grid, s); break;
+                default: return hipErrorInvalidValue;
+            }
+            break;
+        case kYuvTopLeft:
+            switch (p.src.layout) {
+                case kYuvI420: launch_gather_yuv_as<kYuvI420, kYuvTopLeft>(p, grid, s); break;
+                case kYuvNV12: launch_gather_yuv_as<kYuvNV12, kYuvTopLeft>(p, grid, s); break;
+                default: return hipErrorInvalidValue;
+            }
+            break;
+        default: return hipErrorInvalidValue;                       // no kernel for it: an error, never another siting's kernel
     }
     return hipGetLastError();
 }
-template <int L>
+template <int L, int S = kYuvLeft>
 static void launch_compose_yuv_as(const ComposeYuvParams& p, dim3 grid, hipStream_t s) {
-    if (p.c.fp32) hipLaunchKernelGGL((compose_yuv_kernel<float4v, L>), grid, dim3(kYuvThreads), 0, s, p);
-    else hipLaunchKernelGGL((compose_yuv_kernel<half4, L>), grid, dim3(kYuvThreads), 0, s, p);
+    if (p.c.fp32) hipLaunchKernelGGL((compose_yuv_kernel<float4v, L, S>), grid, dim3(kYuvThreads), 0, s, p);
+    else hipLaunchKernelGGL((compose_yuv_kernel<half4, L, S>), grid, dim3(kYuvThreads), 0, s, p);
 }
 hipError_t launch_compose_yuv(const ComposeYuvParams& p, hipStream_t s) {
     if (p.c.outW <= 0 || p.c.outH <= 0) return hipSuccess;
+    const int siting = yuv_effective_siting(p.dst.layout, p.dst.siting);
+    if (siting < 0) return hipErrorInvalidValue;
     if (p.dst.layout == kYuvI444) {
         const int gw = (p.c.outW + 3) / 4;
         const dim3 grid((unsigned)((gw + kComposeThreads - 1) / kComposeThreads), (unsigned)((p.c.outH + kComposeRows - 1) / kComposeRows));
@@ -589,6 +684,26 @@ hipError_t launch_compose_yuv(const ComposeYuvParams& p, hipStream_t s) {
     const int cw = (p.c.outW + 1) / 2, ch = yuv_chroma_rows(p.c.outH, p.dst.layout);
     const int runs = (cw + kYuvSites - 1) / kYuvSites;
     const dim3 grid((unsigned)((runs + kYuvThreads - 1) / kYuvThreads), (unsigned)(ch < 65535 ? ch : 65535));
+    if (siting == kYuvTopLeft) {                                    // a workgroup per band of kYuvBand chroma rows (at most 65535 bands: 1.5 million luma rows)
+        const int bands = (ch + kYuvBand - 1) / kYuvBand;
+        if (bands > 65535) return hipErrorInvalidValue;
+        const dim3 bgrid(grid.x, (unsigned)bands);
+        switch (p.dst.layout) {
+            case kYuvI420: launch_compose_yuv_as<kYuvI420, kYuvTopLeft>(p, bgrid, s); break;
+            case kYuvNV12: launch_compose_yuv_as<kYuvNV12, kYuvTopLeft>(p, bgrid, s); break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
+    if (siting == kYuvCenter) {
+        switch (p.dst.layout) {
+            case kYuvI420: launch_compose_yuv_as<kYuvI420, kYuvCenter>(p, grid, s); break;
+            case kYuvI422: launch_compose_yuv_as<kYuvI422, kYuvCenter>(p, grid, s); break;
+            case kYuvNV12: launch_compose_yuv_as<kYuvNV12, kYuvCenter>(p, grid, s); break;
+            default: return hipErrorInvalidValue;
+        }
+        return hipGetLastError();
+    }
     switch (p.dst.layout) {
         case kYuvI420: launch_compose_yuv_as<kYuvI420>(p, grid, s); break;
         case kYuvI422: launch_compose_yuv_as<kYuvI422>(p, grid, s); break;

@@ -54,12 +54,13 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const ResamplePara
 
 }  // namespace
 
-int resample_rows_max(const int* fy, int outH, int inH, int ky) {
+int resample_rows_max(const int* fy, int outH, int inH, int ky, int rows_above) {
     int m = 0;
     for (int y0 = 0; y0 < outH; y0 += kRsRows) {
         const int y1 = (y0 + kRsRows < outH ? y0 + kRsRows : outH) - 1;
         const int e = fy[y1] + ky < inH ? fy[y1] + ky : inH;
-        if (e - fy[y0] > m) m = e - fy[y0];
+        const int first = fy[y0 - rows_above > 0 ? y0 - rows_above : 0];
+        if (e - first > m) m = e - first;
     }
     return m;
 }

@@ -33,6 +33,10 @@ __device__ __forceinline__ float luma_even_row(const YuvCoefs& k, float r, float
 __device__ __forceinline__ float luma_of_row(const YuvCoefs& k, int Y, float r, float g, float b) { return (Y & 1) ? luma_fused(k, r, g, b) : luma_even_row(k, r, g, b); }
 // a chroma site's colour from the columns 2j - 1, 2j, 2j + 1 (1/4, 1/2, 1/4)
 __device__ __forceinline__ float site_filter(float left, float mid, float right) { return __fmaf_rn(0.25f, right, __fmaf_rn(0.25f, left, __fmul_rn(0.5f, mid))); }
+// centred columns: the mean of columns 2j and 2j + 1
+__device__ __forceinline__ float site_mean(float mid, float right) { return __fmul_rn(0.5f, __fadd_rn(mid, right)); }
+// co-sited rows: rows 2i - 1, 2i, 2i + 1 by (1/4, 1/2, 1/4)
+__device__ __forceinline__ float rows_cosited(float above, float mid, float below) { return __fmaf_rn(0.25f, below, __fmaf_rn(0.25f, above, __fmul_rn(0.5f, mid))); }
 __device__ __forceinline__ float chroma_of(float c, float y, float div) { return __fmul_rn(__fsub_rn(c, y), div); }
 
 // Four consecutive codes of one plane's row from column X (a multiple of 4): np == 4 and an aligned address leave as one store of 4 (10 bits: 8) bytes, a run
@@ -82,13 +86,17 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv444_kernel(const Resam
 // the one halo dword falls on a bank in use - two lanes on one bank at most, which a 4-byte store hides.  The halo is read by the first lane of each tile row
 // (4 lanes of a wave, ds_read_b32), rows a few dwords apart.
 // At a factor of 4 with bicubic taps rows_max <= 78: 3 * 78 * 65 * 4 B = 59.4 KiB, two workgroups per CU.
+// S: kYuvLeft is the above (resample_yuv422_kernel).  kYuvCenter: site j is the mean of columns 2j and 2j + 1 - pass 1 filters no halo column and
+// nothing crosses lanes before the stores.  (I422 has no row rule: kYuvTopLeft is kYuvLeft.)
+template <int S>
 __global__ __launch_bounds__(kRsThreads) void resample_yuv422_kernel(const ResampleYuvParams p) {
+    constexpr bool kLeftCol = S != kYuvCenter;
     extern __shared__ __attribute__((aligned(16))) float h422[];   // (the alignment stated: pass 2 reads 16 bytes per lane and plane, ds_read_b128)
     float* const h = h422;
     const int rm = p.rows_max;
     float* const halo = h + 3 * rm * kRsCols;
     const int ox0 = blockIdx.x * kRsCols, oy0 = blockIdx.y * kRsRows;
-    const int r0 = resample_pass1_to<3, true>(p, h, [rm](int q, int r, int c) { return c == kRsCols ? 3 * rm * kRsCols + q * rm + r : (q * rm + r) * kRsCols + c; });
+    const int r0 = resample_pass1_to<3, kLeftCol>(p, h, [rm](int q, int r, int c) { return c == kRsCols ? 3 * rm * kRsCols + q * rm + r : (q * rm + r) * kRsCols + c; });
     __syncthreads();
     // pass 2: four pixels = two chroma sites of one row per thread.  No lane leaves before the cross-lane moves below: lanes outside the frame carry zeros.
     const YuvCoefs& k = p.k;
@@ -108,7 +116,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv422_kernel(const Resam
 #pragma unroll
             for (int e = 0; e < 3; ++e) a[e] += wk * *(const float4v*)&h[(e * rm + r) * kRsCols + 4 * cg];
         }
-        if (cg == 0)
+        if (kLeftCol && cg == 0)
             for (int t = 0; t < n; ++t) {
                 const float wk = w[t];
 #pragma unroll
@@ -129,13 +137,15 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv422_kernel(const Resam
         float f[3];
 #pragma unroll
         for (int e = 0; e < 3; ++e) {
-            float left;
-            if (s == 0) {
-                const float from_left = __shfl_up(o[3][e], 1);            // (the lane on the left is of the same row for every cg > 0)
-                left = cg ? from_left : sat01(hl[e]);
-            } else left = o[1][e];
+            float left = 0.f;
+            if constexpr (kLeftCol) {
+                if (s == 0) {
+                    const float from_left = __shfl_up(o[3][e], 1);        // (the lane on the left is of the same row for every cg > 0)
+                    left = cg ? from_left : sat01(hl[e]);
+                } else left = o[1][e];
+            }
             const float right = 2 * s + 1 < np ? o[2 * s + 1][e] : o[2 * s][e];   // column 2j + 1 clamped to the frame (odd widths)
-            f[e] = site_filter(left, o[2 * s][e], right);
+            f[e] = kLeftCol ? site_filter(left, o[2 * s][e], right) : site_mean(o[2 * s][e], right);
         }
         const float Yn = luma_fused(k, f[0], f[1], f[2]);
         uc[s] = yuv_code(k.c_off, k.c_scale, chroma_of(f[2], Yn, k.cb_div), k.maxcode);
@@ -188,11 +198,19 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv422_kernel(const Resam
 constexpr int kYP = kRsCols + 2;
 typedef float float2v __attribute__((ext_vector_type(2)));
 
-template <bool kNV12>
+// S: kYuvLeft is the above.  kYuvCenter: site j is the mean of columns 2j and 2j + 1 of the two rows averaged - no halo column in pass 1, no move
+// from the lane on the left.  kYuvTopLeft: a site filters rows 2i - 1, 2i, 2i + 1 (1/4, 1/2, 1/4), then the columns as kYuvLeft.  Row 2i - 1 of a tile's
+// first chroma row is output row oy0 - 1 of the tile above: a ROW halo, handled as the column halo is - pass 1 starts at the input rows that row reaches
+// (resample_pass1_to's kAbove; rows_max is resample_rows_max(.., 1), one output row's stride of input rows more) and every thread filters row 2i - 1 at its two
+// columns itself (row -1 clamps to row 0), lanes 0 .. 4 of a wave the halo column of its five luma rows.  That is 3 vertical filters per thread where kYuvLeft
+// has 2; the horizontal pass, the kernel's larger part at 17 taps, grows by one output row's reach in 16.
+// LDS at a factor of 4 with bicubic taps: rows_max <= 82 (16 * 4 + 1 + 17), 3 * 82 * 66 * 4 B = 63.4 KiB - two workgroups per CU still fit the CU's 160 KiB.
+template <bool kNV12, int S = kYuvLeft>
 __device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, float* h) {   // h: [3][rows_max][kYP], columns 0 .. 63 the tile's, 64 the halo
+    constexpr bool kLeftCol = S != kYuvCenter, kAbove = S == kYuvTopLeft;
     const int ox0 = blockIdx.x * kRsCols, oy0 = blockIdx.y * kRsRows;
     const int rm = p.rows_max;
-    const int r0 = resample_pass1_to<3, true>(p, h, [rm](int q, int r, int c) { return (q * rm + r) * kYP + c; });
+    const int r0 = resample_pass1_to<3, kLeftCol, kAbove>(p, h, [rm](int q, int r, int c) { return (q * rm + r) * kYP + c; });
     __syncthreads();
     // pass 2: a chroma site per thread.  No lane leaves before the cross-lane moves below: lanes outside the frame carry zeros.
     const YuvCoefs& k = p.k;
@@ -213,12 +231,19 @@ __device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, floa
         }
     };
     float2v a[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}}, b[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};   // rows 2i, 2i + 1: columns 2j, 2j + 1 of R, G, B
+    float2v z[3] = {{0.f, 0.f}, {0.f, 0.f}, {0.f, 0.f}};                  // kAbove: row 2i - 1
     if (active) {
         vertical(Ya, 2 * cj, a);
         if (has_b) vertical(Ya + 1, 2 * cj, b);
+        if constexpr (kAbove) vertical(max(Ya - 1, 0), 2 * cj, z);
     }
     float halo[3] = {0.f, 0.f, 0.f};                                      // lanes 0 .. 3: column ox0 - 1 of the wave's four luma rows
-    if (lane < 4 && oy0 + 4 * (int)(threadIdx.x / 64) + lane < p.outH) vertical(oy0 + 4 * (int)(threadIdx.x / 64) + lane, kRsCols, halo);
+    if constexpr (kAbove) {                                               // lanes 0 .. 4: of the row above them and the four
+        const int Yh = oy0 + 4 * (int)(threadIdx.x / 64) - 1 + lane;
+        if (lane < 5 && Yh < p.outH) vertical(max(Yh, 0), kRsCols, halo);
+    } else if constexpr (kLeftCol) {
+        if (lane < 4 && oy0 + 4 * (int)(threadIdx.x / 64) + lane < p.outH) vertical(oy0 + 4 * (int)(threadIdx.x / 64) + lane, kRsCols, halo);
+    }
     float vl[3], vr[3], left[3];                                          // the site's columns 2j, 2j + 1 and 2j - 1, the two rows averaged
     unsigned ya[2], yb[2];
     {
@@ -235,16 +260,31 @@ __device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, floa
         }
 #pragma unroll
         for (int e = 0; e < 3; ++e) {
-            vl[e] = __fmul_rn(0.5f, __fadd_rn(oa[0][e], ob[0][e]));
-            vr[e] = has_r ? __fmul_rn(0.5f, __fadd_rn(oa[1][e], ob[1][e])) : vl[e];
+            if constexpr (kAbove) {
+                vl[e] = rows_cosited(sat01(z[e][0]), oa[0][e], ob[0][e]);
+                vr[e] = has_r ? rows_cosited(sat01(z[e][1]), oa[1][e], ob[1][e]) : vl[e];
+            } else {
+                vl[e] = __fmul_rn(0.5f, __fadd_rn(oa[0][e], ob[0][e]));
+                vr[e] = has_r ? __fmul_rn(0.5f, __fadd_rn(oa[1][e], ob[1][e])) : vl[e];
+            }
         }
     }
+    if constexpr (kAbove) {
 #pragma unroll
-    for (int e = 0; e < 3; ++e) {
-        const float hc = sat01(halo[e]);
-        const float ha = __shfl(hc, 2 * (lane / 32)), hb = __shfl(hc, 2 * (lane / 32) + 1);
-        const float from_left = __shfl_up(vr[e], 1);
-        left[e] = cj ? from_left : __fmul_rn(0.5f, __fadd_rn(ha, has_b ? hb : ha));
+        for (int e = 0; e < 3; ++e) {                                     // the halo column of rows 2i - 1, 2i, 2i + 1: lanes 2 hw, 2 hw + 1, 2 hw + 2 of the wave
+            const float hc = sat01(halo[e]);
+            const float hz = __shfl(hc, 2 * (lane / 32)), ha = __shfl(hc, 2 * (lane / 32) + 1), hb = __shfl(hc, 2 * (lane / 32) + 2);
+            const float from_left = __shfl_up(vr[e], 1);
+            left[e] = cj ? from_left : rows_cosited(hz, ha, has_b ? hb : ha);
+        }
+    } else if constexpr (kLeftCol) {
+#pragma unroll
+        for (int e = 0; e < 3; ++e) {
+            const float hc = sat01(halo[e]);
+            const float ha = __shfl(hc, 2 * (lane / 32)), hb = __shfl(hc, 2 * (lane / 32) + 1);
+            const float from_left = __shfl_up(vr[e], 1);
+            left[e] = cj ? from_left : __fmul_rn(0.5f, __fadd_rn(ha, has_b ? hb : ha));
+        }
     }
     const bool wide = p.dst.bits > 8;
     const int sbits = wide ? 16 : 8, up = kNV12 && wide ? 6 : 0;          // bits per stored sample; P010: the code in the high ten bits
@@ -252,7 +292,7 @@ __device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, floa
     {
         float f[3];
 #pragma unroll
-        for (int e = 0; e < 3; ++e) f[e] = site_filter(left[e], vl[e], vr[e]);
+        for (int e = 0; e < 3; ++e) f[e] = kLeftCol ? site_filter(left[e], vl[e], vr[e]) : site_mean(vl[e], vr[e]);
         const float Y = luma_fused(k, f[0], f[1], f[2]);
         uc = yuv_code(k.c_off, k.c_scale, chroma_of(f[2], Y, k.cb_div), k.maxcode) << up;
         vc = yuv_code(k.c_off, k.c_scale, chroma_of(f[0], Y, k.cr_div), k.maxcode) << up;
@@ -313,12 +353,19 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv_nv12_kernel(const Res
     extern __shared__ float h[];
     resample_yuv420<true>(p, h);
 }
+// the other sitings of the pair
+template <bool kNV12, int S>
+__global__ __launch_bounds__(kRsThreads) void resample_yuv_sited_kernel(const ResampleYuvParams p) {
+    extern __shared__ float h[];
+    resample_yuv420<kNV12, S>(p, h);
+}
 
 }  // namespace
 
 // dst.layout picks the kernel.  The layouts beside I420 also ask for a canvas and for every plane of the layout, with a step that holds its row and 10-bit
 // planes at even addresses.
-hipError_t launch_resample_yuv(const ResampleYuvParams& p, hipStream_t s) {
+hipError_t launch_resample_yuv(const ResampleYuvParams& params, int rows_max_above, hipStream_t s) {
+    ResampleYuvParams p = params;
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
     if (p.dst.rows != p.outH || p.dst.cols != p.outW || (p.dst.bits != 8 && p.dst.bits != 10)) return hipErrorInvalidValue;
     const int layout = p.dst.layout;
@@ -331,10 +378,29 @@ hipError_t launch_resample_yuv(const ResampleYuvParams& p, hipStream_t s) {
             if (!p.dst.p[i] || p.dst.step[i] < samples * bps || ((((size_t)p.dst.p[i]) | p.dst.step[i]) & (bps - 1)) != 0) return hipErrorInvalidValue;
         }
     }
+    // the siting the layout tells apart: I444 none, I422 the column rule alone
+    if (p.dst.siting < kYuvLeft || p.dst.siting > kYuvTopLeft) return hipErrorInvalidValue;
+    const int siting = layout == kYuvI444 || (layout == kYuvI422 && p.dst.siting == kYuvTopLeft) ? kYuvLeft : p.dst.siting;
+    if (siting != kYuvLeft) {
+        static unsigned done_c = 0, done_cn = 0, done_c422 = 0, done_t = 0, done_tn = 0;
+        const bool tl = siting == kYuvTopLeft;
+        if (tl) {                                                          // pass 1 starts at the output row above the tile: the LDS holds those input rows too
+            if (rows_max_above < p.rows_max) return hipErrorInvalidValue;
+            p.rows_max = rows_max_above;
+        }
+        switch (layout) {
+            case kYuvI420: return tl ? launch_resample_tiles(resample_yuv_sited_kernel<false, kYuvTopLeft>, 3 * kYP, p.rows_max, done_t, p.outW, p.outH, s, p)
+                                     : launch_resample_tiles(resample_yuv_sited_kernel<false, kYuvCenter>, 3 * kYP, p.rows_max, done_c, p.outW, p.outH, s, p);
+            case kYuvNV12: return tl ? launch_resample_tiles(resample_yuv_sited_kernel<true, kYuvTopLeft>, 3 * kYP, p.rows_max, done_tn, p.outW, p.outH, s, p)
+                                     : launch_resample_tiles(resample_yuv_sited_kernel<true, kYuvCenter>, 3 * kYP, p.rows_max, done_cn, p.outW, p.outH, s, p);
+            case kYuvI422: return launch_resample_tiles(resample_yuv422_kernel<kYuvCenter>, 3 * (kRsCols + 1), p.rows_max, done_c422, p.outW, p.outH, s, p);
+            default: return hipErrorInvalidValue;
+        }
+    }
     static unsigned done420 = 0, done422 = 0, done444 = 0, done_nv12 = 0;
     switch (layout) {                                                      // LDS dwords per input row: three planes of the kernel's pitch
         case kYuvI420: return launch_resample_tiles(resample_yuv_kernel, 3 * kYP, p.rows_max, done420, p.outW, p.outH, s, p);
-        case kYuvI422: return launch_resample_tiles(resample_yuv422_kernel, 3 * (kRsCols + 1), p.rows_max, done422, p.outW, p.outH, s, p);
+        case kYuvI422: return launch_resample_tiles(resample_yuv422_kernel<kYuvLeft>, 3 * (kRsCols + 1), p.rows_max, done422, p.outW, p.outH, s, p);
         case kYuvI444: return launch_resample_tiles(resample_yuv444_kernel, 3 * kRsCols, p.rows_max, done444, p.outW, p.outH, s, p);
         default: return launch_resample_tiles(resample_yuv_nv12_kernel, 3 * kYP, p.rows_max, done_nv12, p.outW, p.outH, s, p);
     }

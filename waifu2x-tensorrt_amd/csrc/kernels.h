@@ -282,10 +282,13 @@ constexpr int kResampleRows = 16, kResampleCols = 64;
 #define W2X_COMPOSE_THREADS 64
 #endif
 constexpr int kComposeRows = W2X_COMPOSE_ROWS, kComposeThreads = W2X_COMPOSE_THREADS;
-int resample_rows_max(const int* fy, int outH, int inH, int ky);   // host: the largest input row span of an output row tile
+// host: the largest input row span of an output row tile; rows_above = 1: of the tile and the output row above it (top-left sited 4:2:0 chroma)
+int resample_rows_max(const int* fy, int outH, int inH, int ky, int rows_above = 0);
 hipError_t launch_resample(const ResampleParams& p, hipStream_t s);
 // YUV 4:2:0 frames (Img2Img::renderYuv): three planes - Y of rows x cols, U and V of ceil(rows/2) x ceil(cols/2) - with 8-bit (uint8) or 10-bit
-// (uint16, low 10 bits) samples; steps in bytes.  Chroma siting MPEG-2 "left": chroma (i, j) sits at luma (x = 2j, y = 2i + 1/2).
+// (uint16, low 10 bits) samples; steps in bytes.  Chroma siting (siting): kYuvLeft, MPEG-2 "left", chroma (i, j) at luma (x = 2j, y = 2i + 1/2);
+// kYuvCenter (JPEG, MPEG-1) at (2j + 1/2, 2i + 1/2); kYuvTopLeft (BT.2020) at (2j, 2i).  Per subsampled axis a siting is one of two rules, co-sited or centred:
+// Left = co-sited columns, centred rows; Center = both centred; TopLeft = both co-sited.  I422 has the column rule only, I444 none.
 // layout (YuvLayout): kYuvI420 the above; kYuvI422 U and V of rows x ceil(cols/2) (chroma row y serves luma row y); kYuvI444 U and V of
 // rows x cols; kYuvNV12 I420 with U and V interleaved in p[1] (ceil(rows/2) rows of 2 * ceil(cols/2) samples, U first; p[2] unused) and, at 10 bits,
 // the code in the high 10 bits of each uint16 of Y and UV (P010: read >> 6, written << 6).
@@ -294,7 +297,12 @@ struct YuvPlanes {
     uint8_t* p[3] = {nullptr, nullptr, nullptr}; size_t step[3] = {0, 0, 0};
     int rows = 0, cols = 0, bits = 8;
     int layout = kYuvI420;
+    int siting = 0;                                             // kYuvLeft
 };
+constexpr int kYuvLeft = 0, kYuvCenter = 1, kYuvTopLeft = 2;
+// the 1-D rule of a siting along the columns / the rows: true = centred, false = co-sited
+constexpr bool yuv_cols_centred(int siting) { return siting == kYuvCenter; }
+constexpr bool yuv_rows_centred(int siting) { return siting != kYuvTopLeft; }
 // the chroma plane's rows and samples per row (NV12: both components) of a rows x cols frame
 inline int yuv_chroma_rows(int rows, int layout) { return layout == kYuvI420 || layout == kYuvNV12 ? (rows + 1) / 2 : rows; }
 inline int yuv_chroma_samples(int cols, int layout) { return layout == kYuvI444 ? cols : layout == kYuvNV12 ? 2 * ((cols + 1) / 2) : (cols + 1) / 2; }
@@ -341,6 +349,12 @@ struct ComposeYuvParams {
     YuvPlanes dst; YuvCoefs k;
 };
 constexpr int kYuvSites = 4, kYuvThreads = 64;   // chroma sites (8 luma columns, 2 rows) per thread, threads per workgroup (one wave)
+// dst.siting kYuvTopLeft, I420 / NV12: the chroma rows a workgroup walks with the luma row above carried in registers.  One luma row is computed
+// twice per band: (2 * 12 + 1) / (2 * 12) = 1.042 of kYuvLeft's pixel sums
+#ifndef W2X_YUV_BAND
+#define W2X_YUV_BAND 12
+#endif
+constexpr int kYuvBand = W2X_YUV_BAND;   // (a build switch like W2X_COMPOSE_ROWS, for A/B runs of k_prepost.hip: profiles/yuv_siting/compose_band.txt)
 // dst.layout picks the kernel: I420 and NV12 compose_yuv_kernel (NV12: U and V stored interleaved, P010 codes << 6), I422 the same kernel
 // without the vertical pair (a thread owns four sites of ONE luma row), I444 compose_yuv444_kernel (compose_kernel's shape: four pixels of a row per
 // thread, its four-pixel fast path, no chroma filter)
@@ -509,7 +523,10 @@ struct ResampleYuvParams {
 // dst.layout picks the kernel: I420 resample_yuv_kernel, a thread per chroma site; NV12 / P010 resample_yuv_nv12_kernel, the same body and so
 // I420's samples, with U and V interleaved in plane 1 and, at 10 bits, every code << 6; I444 resample_kernel's pass 2 with each pixel's own Cb / Cr; I422 the
 // same shape with the chroma filter along the row alone
-hipError_t launch_resample_yuv(const ResampleYuvParams& p, hipStream_t s);
+// rows_max_above: resample_rows_max(.., 1) of the same tables.  The launcher, which knows what the destination's siting dispatches, sizes the LDS and the kernel's
+// row pitch by it where the kernel reads the row above its tile (top-left sited I420 / NV12) and by p.rows_max everywhere else; a top-left launch
+// without it is an error, not a launch with too little LDS.
+hipError_t launch_resample_yuv(const ResampleYuvParams& p, int rows_max_above, hipStream_t s);
 // debug/test helpers used by w2x_infer (mirrors blobFromImages / imagesFromBlob, img2img_infer.cpp:5-39)
 hipError_t launch_blob_to_nhwc(const float* nchw, void* out_nhwc4, int B, int T, bool fp32, hipStream_t s);
 hipError_t launch_nhwc_to_blob(const void* in_nhwc4, float* nchw, int B, int T, bool fp32, hipStream_t s);

@@ -170,12 +170,13 @@ __device__ __forceinline__ void compose_quad_sums(const CP& p, int X, int Y, int
 // Pass 1: the input rows [r0, r0 + nr) the tile needs, filtered horizontally onto its output columns; returns r0.  The caller's barrier follows.  The value of
 // plane q, input row r, tile column c goes to h[slot(q, r, c)].  kHalo: a 65th column, c == kRsCols, holds output column ox0 - 1 (clamped at 0), which the
 // 4:2:0 and 4:2:2 kernels' chroma sites reach; where it lies is the slot's business (k_resample_yuv.hip).  The loop runs nr * 65 items then, nr * 64 without.
-template <int NP, bool kHalo, typename RP, typename Slot>
+// kAbove: the rows start with those of output row oy0 - 1 (clamped at 0), the row halo of top-left sited chroma (resample_rows_max(.., 1) rows).
+template <int NP, bool kHalo, bool kAbove = false, typename RP, typename Slot>
 __device__ __forceinline__ int resample_pass1_to(const RP& p, float* h, Slot slot) {
     constexpr int kCols = kRsCols + (kHalo ? 1 : 0);
     const int ox0 = blockIdx.x * kRsCols, oy0 = blockIdx.y * kRsRows;
     const int tw = min(kRsCols, p.outW - ox0), th = min(kRsRows, p.outH - oy0);
-    const int r0 = p.fy[oy0];
+    const int r0 = p.fy[kAbove ? max(oy0 - 1, 0) : oy0];
     const int nr = min(p.inH, p.fy[oy0 + th - 1] + p.ky) - r0;           // <= rows_max (resample_rows_max)
     const size_t plane = (size_t)p.inW * p.inH;
     for (int i = threadIdx.x; i < nr * kCols; i += kRsThreads) {

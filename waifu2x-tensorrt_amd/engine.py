@@ -39,6 +39,18 @@ def _matrix_id(name) -> int:
 YUV_LAYOUTS = {"i420": 0, "i422": 1, "i444": 2, "nv12": 3}   # W2X_YUV_I420 .. _NV12 (include/w2x/c_api.h)
 
 
+YUV_SITINGS = {"left": 0, "center": 1, "topleft": 2}        # W2X_YUV_SITING_LEFT .. _TOPLEFT (include/w2x/c_api_yuv_siting.h)
+
+
+def _siting_ids(siting, out_siting):
+    """the ids of a call's two chroma sitings (out_siting None: the input's); unknown names raise before any library call"""
+    out_siting = siting if out_siting is None else out_siting
+    for name in (siting, out_siting):
+        if name not in YUV_SITINGS:
+            raise ValueError(f"siting must be one of {sorted(YUV_SITINGS)}, got {name!r}")
+    return YUV_SITINGS[siting], YUV_SITINGS[out_siting]
+
+
 def _layout_id(name) -> int:
     if name not in YUV_LAYOUTS:
         raise ValueError(f"layout must be one of {sorted(YUV_LAYOUTS)}, got {name!r}")
@@ -211,6 +223,7 @@ _FRAME = [_P, _P, _I, _I, _Z]                # engine, frame (or array of frames
 _YUV = [_P, _P, _I, _I, _I]                  # planes, steps, rows, cols, bits
 _YUV2 = [_P] + _YUV + _YUV                   # engine, source frame, destination frame
 _YUV2L = [_P] + _YUV + [_I] + _YUV + [_I]    # the same with a layout after each frame
+_YUV2S = [_P] + _YUV + [_I, _I] + _YUV + [_I, _I]   # the same with a layout and a chroma siting after each frame
 _GRID = [_I] * 7 + [_D, _D]                  # in_w, in_h, out_w, out_h, tile_in, tile_out, scaling, overlap_x, overlap_y
 # Every symbol of include/w2x/c_api.h: name -> (restype, argtypes).  A new entry is one row here (tests/test_host_abi.py compares the keys with the header).
 # restype None: void (the three calls that take a pointer back); _I on the other void functions is ctypes' default, as before.  argtypes None: not declared.
@@ -313,6 +326,12 @@ YUV_RESIZED_SYMBOLS = {
     "w2x_render_yuv_layout_resized": (_I, _YUV2L + [_I, _I, _I]),
     "w2x_render_sequence_yuv_layout_resized": (_I, _YUV2L + [_I, _I, _I, _I]),
 }
+# The YUV entries that carry a chroma siting per side (include/w2x/c_api_yuv_siting.h), a table of their own likewise: _YUV2S + [matrix, range, filter], the
+# sequence with `count` in front of the matrix.
+YUV_SITED_SYMBOLS = {
+    "w2x_render_yuv_sited": (_I, _YUV2S + [_I, _I, _I]),
+    "w2x_render_sequence_yuv_sited": (_I, _YUV2S + [_I, _I, _I, _I]),
+}
 _lib = None
 
 
@@ -325,7 +344,7 @@ def lib():
         raise W2xError(f"{lib_path} is missing - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "or `make -C waifu2x-tensorrt_amd` (there is no CPU fallback)")
     L = C.CDLL(lib_path)
-    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()) + list(PLANAR_SYMBOLS.items()) + list(RGBAP_SYMBOLS.items()) + list(YUV_RESIZED_SYMBOLS.items()):
+    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()) + list(PLANAR_SYMBOLS.items()) + list(RGBAP_SYMBOLS.items()) + list(YUV_RESIZED_SYMBOLS.items()) + list(YUV_SITED_SYMBOLS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -800,12 +819,15 @@ class Img2Img:
         return bool(self._L.w2x_shard_finish(self._h, dst.ctypes.data, dst.shape[0], dst.shape[1], dst.strides[0], int(part), int(parts), arr, dev))
 
     def render_yuv(self, y, u: np.ndarray | None = None, v: np.ndarray | None = None, *, matrix: str = "bt709", full_range: bool = False, out_bits: int | None = None,
-                   out=None, layout: str | None = None, out_layout: str | None = None):
+                   out=None, layout: str | None = None, out_layout: str | None = None, siting: str = "left", out_siting: str | None = None):
         """render() on a YUV 4:2:0 frame (w2x_render_yuv): uint8 planes are 8-bit, uint16 planes 10-bit; out_bits (8 or 10, default the input's)
         sets the output depth.  Returns (Y, U, V) at the scaled size, or raises.  out: pre-allocated planes (then a bool is returned).
         With the frame given as one tuple of planes, or with layout= / out_layout= ("i420", "i422", "i444", "nv12"; out_layout defaults to the input's), the
         call goes through w2x_render_yuv_layout: an "nv12" frame is (y, uv) with uv of ceil(rows/2) x 2 * ceil(cols/2) samples (10-bit: P010, codes << 6),
-        and the result is the tuple of out_layout's planes (yuv_layout_plane_shapes)."""
+        and the result is the tuple of out_layout's planes (yuv_layout_plane_shapes).
+        siting= / out_siting= ("left", "center", "topleft"; out_siting defaults to the input's): where the chroma samples of the frame / of the result sit
+        (DESIGN 9l).  With both "left" the call is the one above; any other pair goes through w2x_render_yuv_sited at the scaled size."""
+        sid, osid = _siting_ids(siting, out_siting)
         with_layout = isinstance(y, (tuple, list)) or layout is not None or out_layout is not None
         if isinstance(y, (tuple, list)) and (u is not None or v is not None):
             raise ValueError("give the frame as one tuple of planes or as three positional planes, not both")
@@ -832,7 +854,10 @@ class Img2Img:
         (sp, ss), (dp, ds) = _plane_args(planes), _plane_args(dst)
         a = (self._h, (C.c_void_p * 3)(*sp), (C.c_size_t * 3)(*ss), rows, cols, bits, (C.c_void_p * 3)(*dp), (C.c_size_t * 3)(*ds), rows * s, cols * s, ob,
              _matrix_id(matrix), 1 if full_range else 0)
-        ok = self._L.w2x_render_yuv_layout(*a[:6], lid, *a[6:11], olid, *a[11:]) if with_layout else self._L.w2x_render_yuv(*a)
+        if sid or osid:
+            ok = self._L.w2x_render_yuv_sited(*a[:6], lid, sid, *a[6:11], olid, osid, *a[11:], RESIZE_FILTERS["bicubic"])
+        else:
+            ok = self._L.w2x_render_yuv_layout(*a[:6], lid, *a[6:11], olid, *a[11:]) if with_layout else self._L.w2x_render_yuv(*a)
         return self._finish(ok, dst if out is None else None, "render_yuv failed")
 
     def render_yuv_resized(self, y: np.ndarray, u: np.ndarray, v: np.ndarray, size, *, matrix: str = "bt709", full_range: bool = False,
@@ -861,11 +886,13 @@ class Img2Img:
         return self._sequence_yuv(frames, (int(size[0]), int(size[1])), _filter_id(filter), matrix, full_range, out_bits, pinned)
 
     def render_yuv_layout_resized(self, planes, size, *, layout: str = "i420", out_layout: str | None = None, matrix: str = "bt709", full_range: bool = False,
-                                  out_bits: int | None = None, filter: str = "bicubic", dst=None):
+                                  out_bits: int | None = None, filter: str = "bicubic", dst=None, siting: str = "left", out_siting: str | None = None):
         """render_yuv_resized() on frames of any layout (w2x_render_yuv_layout_resized): planes is the tuple of `layout`'s planes - (y, u, v), or (y, uv) for
         "nv12" (10-bit: P010, codes << 6) -, out_layout (default: layout) the layout of the result, size = (rows, cols) the target, each in [input dim,
         input dim * scaling].  Returns the tuple of out_layout's planes at the target size (yuv_layout_plane_shapes), or raises.  dst: pre-allocated planes
-        (then a bool is returned).  Planes that do not have the named layout's shapes and unknown names raise ValueError before any library call."""
+        (then a bool is returned).  Planes that do not have the named layout's shapes and unknown names raise ValueError before any library call.
+        siting= / out_siting= as in render_yuv(): any pair but "left" / "left" goes through w2x_render_yuv_sited."""
+        sid, osid = _siting_ids(siting, out_siting)
         out_layout = layout if out_layout is None else out_layout
         lid, olid = _layout_id(layout), _layout_id(out_layout)
         if not isinstance(planes, (tuple, list)):
@@ -883,27 +910,36 @@ class Img2Img:
         sp, ss = _plane_args(planes)
         dp = [_data(p) for p in out] + [None] * (3 - len(out))   # (an empty target: refused by the library)
         ds = [p.strides[0] for p in out] + [0] * (3 - len(out))
-        ok = self._L.w2x_render_yuv_layout_resized(self._h, (C.c_void_p * 3)(*sp), (C.c_size_t * 3)(*ss), planes[0].shape[0], planes[0].shape[1], bits, lid,
-                                                   (C.c_void_p * 3)(*dp), (C.c_size_t * 3)(*ds), rows, cols, ob, olid, mid, 1 if full_range else 0, fid)
+        if sid or osid:
+            ok = self._L.w2x_render_yuv_sited(self._h, (C.c_void_p * 3)(*sp), (C.c_size_t * 3)(*ss), planes[0].shape[0], planes[0].shape[1], bits, lid, sid,
+                                              (C.c_void_p * 3)(*dp), (C.c_size_t * 3)(*ds), rows, cols, ob, olid, osid, mid, 1 if full_range else 0, fid)
+        else:
+            ok = self._L.w2x_render_yuv_layout_resized(self._h, (C.c_void_p * 3)(*sp), (C.c_size_t * 3)(*ss), planes[0].shape[0], planes[0].shape[1], bits, lid,
+                                                       (C.c_void_p * 3)(*dp), (C.c_size_t * 3)(*ds), rows, cols, ob, olid, mid, 1 if full_range else 0, fid)
         return self._finish(ok, out if dst is None else None, "render_yuv_layout_resized failed")
 
     def render_sequence_yuv_layout_resized(self, frames, size, *, layout: str = "i420", out_layout: str | None = None, matrix: str = "bt709", full_range: bool = False,
-                                           out_bits: int | None = None, filter: str = "bicubic", pinned: bool = False):
+                                           out_bits: int | None = None, filter: str = "bicubic", pinned: bool = False, siting: str = "left",
+                                           out_siting: str | None = None):
         """render_sequence_yuv() over frames of `layout` with every frame resized to size = (rows, cols) like render_yuv_layout_resized()
-        (w2x_render_sequence_yuv_layout_resized): every frame a tuple of `layout`'s planes, every result a tuple of out_layout's"""
-        return self._sequence_yuv(frames, (int(size[0]), int(size[1])), _filter_id(filter), matrix, full_range, out_bits, pinned, layout, out_layout or layout)
+        (w2x_render_sequence_yuv_layout_resized): every frame a tuple of `layout`'s planes, every result a tuple of out_layout's.  siting= / out_siting= as in
+        render_yuv(), one pair for the sequence (any but "left" / "left": w2x_render_sequence_yuv_sited)"""
+        return self._sequence_yuv(frames, (int(size[0]), int(size[1])), _filter_id(filter), matrix, full_range, out_bits, pinned, layout, out_layout or layout,
+                                  _siting_ids(siting, out_siting))
 
     def render_sequence_yuv(self, frames, *, matrix: str = "bt709", full_range: bool = False, out_bits: int | None = None, pinned: bool = False,
-                            layout: str | None = None, out_layout: str | None = None):
+                            layout: str | None = None, out_layout: str | None = None, siting: str = "left", out_siting: str | None = None):
         """render_yuv() over equally sized frames [(y, u, v), ...] through the pipeline of render_sequence() (w2x_render_sequence_yuv).
         pinned=True takes the output planes from alloc_host() (a ring of three frames; copies of the results are returned).
         layout= / out_layout= as in render_yuv() (w2x_render_sequence_yuv_layout): every frame is a tuple of `layout`'s planes - [(y, uv), ...] for "nv12" -
-        and a frame of another layout's shapes raises ValueError."""
-        return self._sequence_yuv(frames, None, None, matrix, full_range, out_bits, pinned, layout, out_layout)
+        and a frame of another layout's shapes raises ValueError.  siting= / out_siting= as in render_yuv(), one pair for the sequence (any but "left" / "left":
+        w2x_render_sequence_yuv_sited at the scaled size)."""
+        return self._sequence_yuv(frames, None, None, matrix, full_range, out_bits, pinned, layout, out_layout, _siting_ids(siting, out_siting))
 
-    def _sequence_yuv(self, frames, size, fid, matrix, full_range, out_bits, pinned, layout=None, out_layout=None):
+    def _sequence_yuv(self, frames, size, fid, matrix, full_range, out_bits, pinned, layout=None, out_layout=None, sitings=(0, 0)):
         """the YUV sequence calls: size = None the scaled size (w2x_render_sequence_yuv; with a layout given w2x_render_sequence_yuv_layout), else the target of
-        w2x_render_sequence_yuv_resized with filter fid (with a layout given w2x_render_sequence_yuv_layout_resized)"""
+        w2x_render_sequence_yuv_resized with filter fid (with a layout given w2x_render_sequence_yuv_layout_resized); sitings other than (left, left):
+        w2x_render_sequence_yuv_sited, at the scaled size with the bicubic filter's id, which no resize uses there"""
         if len(frames) == 0:
             return []
         with_layout = layout is not None or out_layout is not None
@@ -943,6 +979,8 @@ class Img2Img:
             # (the matrix is looked at here: a pinned call with an unknown one has taken its ring by now, and gives it back)
             a = (self._h, sp, (C.c_size_t * 3)(*steps), rows, cols, bits, dp, (C.c_size_t * 3)(*_plane_args(os_[0])[1]), orows, ocols, ob, m,
                  _matrix_id(matrix), 1 if full_range else 0)
+            if sitings[0] or sitings[1]:
+                return self._L.w2x_render_sequence_yuv_sited(*a[:6], lid, sitings[0], *a[6:11], olid, sitings[1], *a[11:], RESIZE_FILTERS["bicubic"] if fid is None else fid)
             if size is not None and with_layout:
                 return self._L.w2x_render_sequence_yuv_layout_resized(*a[:6], lid, *a[6:11], olid, *a[11:], fid)
             if size is not None:
