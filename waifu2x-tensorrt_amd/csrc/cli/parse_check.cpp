@@ -1,6 +1,6 @@
 // Sanitizer driver for everything in this tree that parses files or command lines: the hand-written ONNX protobuf reader
 // (onnx_pb.cpp), constant folding and lowering (fold.cpp, lower.cpp), the engine-file reader (plan.cpp), the tile grid (tiles.cpp),
-// the built-in image / video codecs (cli/imageio.cpp) and the option parser (cli/args.cpp).  `make asan` builds it with
+// the built-in image / video codecs (cli/imageio.cpp) and the option parser (cli/args.cpp) - and for the pass schedule of a lowered plan (schedule.cpp).  `make asan` builds it with
 // g++ -fsanitize=address,undefined -fno-sanitize-recover=all - host code only, no HIP - and tests/test_malformed_inputs.py feeds it
 // truncated and bit-flipped files.  The reference has no such target (CMakeLists.txt:49-68).
 //   w2x_parse_check onnx  FILE BATCH TILE [fp32]    load_onnx -> fold_graph -> lower_graph -> serialize -> deserialize
@@ -12,6 +12,8 @@
 //   w2x_parse_check bleed FILE RADIUS               read_image, then alpha_bleed of its colour under its alpha plane (an opaque plane without one), padded rows
 //   w2x_parse_check planes BITS ROWS COLS RADIUS SEED OUT   alpha_bleed_planes on a seeded frame of four planes of BITS (8, 10, 12, 16), padded rows; OUT receives
 //                                                           the four planes and the three bled ones, packed, for the test to compare with its own statement
+//   w2x_parse_check schedule FILE BATCH TILE {fp16|tf32|fp32} [switch=value ...]   lower_for_shape -> candidate_launches -> layout_arena (schedule.h), printed: one line
+//                                                           per plan, op, launch and tensor and one for the arena; tests/test_schedule_host.py judges them
 // Exit code: 0 = accepted, 2 = rejected with a message on stderr (the clean `false` of the product path); anything else is a crash
 // or a sanitizer report.
 #include <algorithm>
@@ -25,6 +27,8 @@
 #include <vector>
 
 #include "../lower.h"
+#include "../schedule.h"
+#include "../switches.h"
 #include "../tiles.h"
 #include "args.h"
 #include "imageio.h"
@@ -32,7 +36,7 @@
 using namespace w2x;
 
 static int run(int argc, char** argv) {
-    if (argc < 3) throw std::runtime_error("usage: w2x_parse_check {onnx|plan|image|avi|args|tiles|bleed|planes} ...");
+    if (argc < 3) throw std::runtime_error("usage: w2x_parse_check {onnx|plan|image|avi|args|tiles|bleed|planes|schedule} ...");
     const std::string mode = argv[1];
     if (mode == "onnx") {
         if (argc < 5) throw std::runtime_error("onnx FILE BATCH TILE [fp32]");
@@ -133,6 +137,34 @@ static int run(int argc, char** argv) {
                     f.write(b, bps);
                 }
         printf("ok: %d x %d of %d bits at radius %d, %zu samples changed\n", cols, rows, bits, radius, changed);
+    } else if (mode == "schedule") {
+        if (argc < 6) throw std::runtime_error("schedule FILE BATCH TILE {fp16|tf32|fp32} [switch=value ...]");
+        const int batch = atoi(argv[3]), tile = atoi(argv[4]);
+        const std::string word = argv[5];
+        if (word != "fp16" && word != "tf32" && word != "fp32") throw std::runtime_error("schedule: precision " + word + " is none of fp16, tf32, fp32");
+        const Precision prec = word == "fp16" ? Precision::FP16 : word == "tf32" ? Precision::TF32 : Precision::FP32;
+        for (int k = 6; k < argc; ++k) {
+            const std::string a = argv[k];
+            const size_t eq = a.find('=');
+            if (eq == std::string::npos || !set_switch(a.substr(0, eq).c_str(), atol(a.c_str() + eq + 1))) throw std::runtime_error("schedule: no switch " + a.substr(0, eq));
+        }
+        const Plan plan = lower_for_shape(argv[2], batch, 3, tile, tile, prec != Precision::FP16);
+        const std::vector<Launch> ls = candidate_launches(plan, prec, switches().check_general);
+        const Lifetimes lt = lifetimes(plan, ls);
+        const ArenaLayout lay = layout_arena(plan, ls);
+        static const char* const kOp[] = {"gemm", "attn", "se", "scale_add", "mlp", "swinattn"};
+        static const char* const kLaunch[] = {"op", "head", "stem", "up", "mlp32", "attn32"};
+        auto ids = [](const auto& v) { std::string s; for (int t : v) if (t >= 0) s += (s.empty() ? "" : ",") + std::to_string(t); return s.empty() ? std::string("-") : s; };
+        printf("plan ops=%zu tensors=%zu B=%d userB=%d in=%d out=%d\n", plan.ops.size(), plan.tensors.size(), plan.B, plan.userB, plan.in_tensor, plan.out_tensor);
+        for (size_t i = 0; i < plan.ops.size(); ++i) {
+            const Op& op = plan.ops[i];
+            const TensorUse u = tensor_use(op);
+            printf("op %zu kind=%s rd=%s wr=%s name=%s\n", i, op.kind >= 0 && op.kind < 6 ? kOp[op.kind] : "?", ids(u.rd).c_str(), ids(u.wr).c_str(), op.name.c_str());
+        }
+        for (const Launch& L : ls) printf("launch kind=%s first=%d last=%d timed=%d family=%d label=%s\n", kLaunch[L.kind], L.first, L.last, L.timed, L.family, launch_label(plan, L).c_str());
+        for (size_t t = 0; t < plan.tensors.size(); ++t)
+            printf("tensor %zu bytes=%lld first=%d last=%d placed=%d off=%zu\n", t, (long long)plan.tensors[t].bytes(), lt.first[t], lt.last[t], lay.placed[t] ? 1 : 0, lay.off[t]);
+        printf("arena bytes=%zu part2=%zu part3=%zu part4=%zu\n", lay.bytes, arena_part_bytes(lay.bytes, 2), arena_part_bytes(lay.bytes, 3), arena_part_bytes(lay.bytes, 4));
     } else throw std::runtime_error("unknown mode " + mode);
     return 0;
 }

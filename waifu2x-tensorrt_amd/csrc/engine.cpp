@@ -25,6 +25,7 @@
 #include "liveness.h"
 #include "lower.h"
 #include "plan.h"
+#include "schedule.h"
 #include "sha256.h"
 #include "switches.h"
 #include "tiles.h"
@@ -170,32 +171,6 @@ bool isOptimized(const RenderConfig& r, const BuildConfig& b) {
 
 constexpr const char* kEngineExt = ".w2x";
 
-// Lowering of a model for one input shape, shared by build() (which writes the result to disk) and by load() when the render
-// configuration lies inside an engine's [min, max] range but is not the shape that engine was specialised for.
-// Super-batching: tiles are independent, so one network pass may carry several reference batches (S x batchSize tiles); results
-// are bit-identical, launches per frame drop S-fold and the low-resolution stages fill all 256 CUs.  W2X_SUPERBATCH (switches.h) overrides;
-// the default targets the pixel count of 48 tiles of 256x256 per pass (one 1080p frame at config 3), capped at 64 tiles.  Small
-// tiles gain the most: at tile 64 / batch 1 a pass of one tile is ~40 launches of a few microseconds of work each (a 1080p frame:
-// 1100 passes, 650 ms, hipGraph replay or not); 64 tiles per pass make it 18 passes.
-Plan lower_for_shape(const std::string& onnxModelPath, int batch, int channels, int height, int width, bool fp32) {
-    int S = 1;
-    if (switches().superbatch > 0) S = switches().superbatch;
-    else {
-        const double want = 48.0 * 256 * 256 / ((double)batch * height * width);
-        S = std::max(1, (int)std::lround(want));
-        while (S > 1 && S * batch > 64) --S;
-    }
-    Plan plan;
-    try {
-        plan = build_plan(onnxModelPath, batch * S, channels, height, width, fp32);
-    } catch (const std::exception&) {
-        if (S == 1) throw;
-        plan = build_plan(onnxModelPath, batch, channels, height, width, fp32);   // e.g. a graph with a static batch dimension
-    }
-    plan.userB = batch;
-    return plan;
-}
-
 // the filter of a resized call as resize_taps() and resize_problem() number it: 0 bicubic, 1 bilinear; any other value is 2, which resize_problem() refuses
 int filter_id(ResizeFilter filter) { return filter == ResizeFilter::Bilinear ? 1 : filter == ResizeFilter::Bicubic ? 0 : 2; }
 
@@ -242,23 +217,10 @@ struct Img2Img::Impl {
     void* arena_base = nullptr; size_t arena_bytes = 0;
     std::vector<GemmParams> gemm;      // per op (kind == OP_GEMM)
     int final_op = -1;
-    // The launches of one network pass, decided once per load() (upload_plan) and walked by run_network().  A fold computes several neighbouring plan ops
-    // in one launch; the map between them is neither stored nor read:
-    //  head   - a C = 96 MLP and the image head behind it (k_mlp96q.hip)
-    //  stem   - a stem convolution and the 3x3 convolution behind it, which computes the 48- / 32-channel map in its halo stage (k_conv48.hip; k_conv3.hip for cunet)
-    //  up     - cunet's pixel-shuffle projection (ConvTranspose) and the 64 -> 64 3x3 convolution behind it, which computes it in its halo stage (k_conv3.hip UP)
-    //  mlp32  - fp32 plans at Precision::TF32: LayerNorm + fc1 + GELU and fc2 + residual (k_f32.hip mlp32_kernel)
-    //  attn32 - the same: LayerNorm + window gather + qkv, attention core, proj + window scatter + residual (k_f32.hip swinattn32_kernel)
-    enum LaunchKind { L_OP, L_HEAD, L_STEM, L_UP, L_MLP32, L_ATTN32 };
-    struct Launch {
-        LaunchKind kind = L_OP;
-        int first = 0, last = 0;      // the plan ops it computes
-        int timed = 0;                // the op whose op_ms slot receives its time (profileFrame / opTimes)
-        double flops = 0;
-        int family = 0;               // profileFrame's kernel family (stamp_begin)
-        std::array<void*, 4> planes{{nullptr, nullptr, nullptr, nullptr}};   // mlp32 / attn32: bf16 hi / lo planes of both matrices, fragment-major (freed by release())
-    };
+    // The launches of one network pass (schedule.h), decided once per load() (upload_plan) and walked by run_network(); launch_planes[k]: launch k's device side -
+    // mlp32 / attn32: bf16 hi / lo planes of both matrices, fragment-major (freed by release())
     std::vector<Launch> launches;
+    std::vector<std::array<void*, 4>> launch_planes;
 
     // frame-level buffers (grown on demand, reused across frames like the reference's input/output GpuMats, img2img.h:37-38)
     bool deep = false;                   // the frame in d_frame / d_out has 16-bit samples (Image::depth == 16)
@@ -480,8 +442,8 @@ struct Img2Img::Impl {
         frag_blobs.clear();
         for (void* p : perm_blobs) if (p) (void)hipFree(p);
         perm_blobs.clear();
-        for (const Launch& L : launches) for (void* p : L.planes) if (p) (void)hipFree(p);
-        launches.clear();
+        for (const auto& planes : launch_planes) for (void* p : planes) if (p) (void)hipFree(p);
+        launch_planes.clear(); launches.clear();
         tensors.clear(); blobs.clear(); gemm.clear();
         for (void* h : pinned) if (hipHostUnregister(h) != hipSuccess) (void)hipGetLastError();
         pinned.clear();
@@ -525,118 +487,6 @@ struct Img2Img::Impl {
         return t;
     }
 
-    // The tensors an op reads and writes: the one table behind the arena's lifetimes and the fold tests
-    struct TensorUse { std::array<int, 6> rd; std::array<int, 3> wr; };
-    static TensorUse tensor_use(const Op& op) {
-        TensorUse u; u.rd.fill(-1); u.wr.fill(-1);
-        switch (op.kind) {
-            case OP_GEMM: u.rd = {{op.g.a.t, op.g.res.t, op.g.res2.t, op.g.stats_in, op.g.se_scale, op.g.res_scale}}; u.wr = {{op.g.out.t, op.g.stats_out, op.g.pool_out}}; break;
-            case OP_ATTN: u.rd[0] = op.at.qkv; u.wr[0] = op.at.out; break;
-            case OP_SE: u.rd[0] = op.se.pool; u.wr[0] = op.se.scale; break;
-            case OP_SCALE_ADD: u.rd = {{op.se.pool, op.se.scale, -1, -1, -1, -1}}; u.wr[0] = op.se.pool; break;      // (in place)
-            case OP_MLP: u.rd[0] = op.m.x; u.wr = {{op.m.y, op.m.stats_out, -1}}; break;
-            case OP_SWINATTN: u.rd[0] = op.sa.x; u.wr = {{op.sa.y, op.sa.stats_out, -1}}; break;
-            default: break;
-        }
-        return u;
-    }
-    // Every tensor's lifetime [first op, last op] when the pass runs as the launches `ls`: everything a launch touches is live across the whole launch (a fold
-    // writes its last op's outputs while other workgroups still read its first op's inputs).  The input is written before op 0 (gather), the output read after the last op.
-    struct Lifetimes { std::vector<int> first, last; };
-    Lifetimes lifetimes(const std::vector<Launch>& ls) const {
-        const int nops = (int)plan.ops.size();
-        Lifetimes lt{std::vector<int>(plan.tensors.size(), nops), std::vector<int>(plan.tensors.size(), -1)};
-        for (const Launch& L : ls)
-            for (int i = L.first; i <= L.last; ++i) {
-                const TensorUse u = tensor_use(plan.ops[i]);
-                auto touch = [&](int t) { if (t >= 0) { lt.first[t] = std::min(lt.first[t], L.first); lt.last[t] = std::max(lt.last[t], L.last); } };
-                for (int t : u.rd) touch(t);
-                for (int t : u.wr) touch(t);
-            }
-        lt.first[plan.in_tensor] = -1;
-        lt.last[plan.out_tensor] = nops;
-        return lt;
-    }
-    // t is op i's output and only op i + 1 reads it (over the plan's own lifetimes: no other op touches it, and it is not the pass's output)
-    static bool passes_on(const Lifetimes& lt, int t, int i) { return t >= 0 && lt.first[t] == i && lt.last[t] == i + 1; }
-    Launch launch(LaunchKind kind, int first, int last) const {
-        static constexpr int kFamily[] = {0, 1, 2, 2, 5, 1};   // per OpKind: gemm, attention, se / scale, fused mlp (profileFrame's out[5 * k])
-        Launch L; L.kind = kind; L.first = first; L.last = last;
-        L.timed = kind == L_STEM || kind == L_UP ? first + 1 : first;     // (the convolution's launch computes the op in front of it)
-        const int k = plan.ops[first].kind;
-        L.family = kind == L_ATTN32 ? 1 : k >= 0 && k < 6 ? kFamily[k] : 0;
-        if (L.family != 2) for (int i = first; i <= last; ++i) L.flops += plan.ops[i].flops;   // (squeeze-excite launches are not priced)
-        return L;
-    }
-
-    // fp32 plans, Precision::TF32: which runs of un-fused ops one fused launch of k_f32.hip serves.  Facts of the plan alone (lower.cpp's fuse_mlp() / fuse_attn() state
-    // the same patterns for the fp16 plan); the plan itself stays un-fused - one lowering serves TF32 and FP32, and Precision::FP32 runs every launch.
-    bool whole_view(const View& v) const { if (v.t < 0) return false; const TensorDesc& t = plan.tensors[v.t]; return v.y0 == 0 && v.x0 == 0 && v.H == t.H && v.W == t.W; }
-    bool mlp32_pair(size_t i, const Lifetimes& lt) const {
-        if (plan.elt != 4 || switches().no_fuse || i + 1 >= plan.ops.size() || plan.ops[i].kind != OP_GEMM || plan.ops[i + 1].kind != OP_GEMM) return false;
-        const GemmOp& g1 = plan.ops[i].g; const GemmOp& g2 = plan.ops[i + 1].g;
-        const int Cm = g1.K;
-        return mlp32_supported(Cm) && g1.amode == A_ROWS && g1.ln && g1.stats_in >= 0 && g1.act == ACT_GELU && g1.omode == O_ROWS && g1.res.t < 0 && g1.res2.t < 0 && !g1.has_clip &&
-               g1.N == 2 * Cm && g1.stats_out < 0 && g1.pool_out < 0 && g1.se_scale < 0 && whole_view(g1.a) && whole_view(g1.out) && plan.tensors[g1.a.t].C == Cm && plan.tensors[g1.out.t].C == 2 * Cm &&
-               g1.Mrows == plan.tensors[g1.a.t].H * plan.tensors[g1.a.t].W &&
-               g2.amode == A_ROWS && !g2.ln && g2.act == ACT_NONE && g2.omode == O_ROWS && g2.a.t == g1.out.t && g2.K == 2 * Cm && g2.N == Cm && g2.res.t == g1.a.t && g2.res2.t < 0 &&
-               !g2.has_clip && g2.pool_out < 0 && g2.se_scale < 0 && g2.res_scale < 0 && whole_view(g2.a) && whole_view(g2.res) && whole_view(g2.out) && plan.tensors[g2.out.t].C == Cm && g2.Mrows == g1.Mrows &&
-               passes_on(lt, g1.out.t, (int)i) &&
-               plan.blobs[g1.w].data.size() == (size_t)2 * Cm * Cm * 4 && plan.blobs[g2.w].data.size() == (size_t)2 * Cm * Cm * 4;      // fp32 [2C][C] and [C][2C], rows unpadded
-    }
-    bool attn32_triple(size_t i, const Lifetimes& lt) const {
-        if (plan.elt != 4 || switches().no_fuse || switches().no_fuse_attn || i + 2 >= plan.ops.size() || plan.ops[i].kind != OP_GEMM || plan.ops[i + 1].kind != OP_ATTN || plan.ops[i + 2].kind != OP_GEMM) return false;
-        const GemmOp& g1 = plan.ops[i].g; const AttnOp& a = plan.ops[i + 1].at; const GemmOp& g2 = plan.ops[i + 2].g;
-        const int Cm = g1.K;
-        return swinattn32_supported(Cm, a.heads, a.hd, a.ws * a.ws) && a.heads * a.hd == Cm &&
-               g1.amode == A_WIN && g1.win_table >= 0 && g1.ln && g1.stats_in >= 0 && g1.act == ACT_NONE && g1.omode == O_ROWS && g1.res.t < 0 && g1.res2.t < 0 && !g1.has_clip && g1.N == 3 * Cm &&
-               g1.stats_out < 0 && g1.pool_out < 0 && g1.se_scale < 0 && whole_view(g1.a) && whole_view(g1.out) && plan.tensors[g1.a.t].C == Cm && plan.tensors[g1.out.t].C == 3 * Cm &&
-               g1.Mrows == a.nwin * a.ws * a.ws && g1.Mrows == plan.tensors[g1.a.t].H * plan.tensors[g1.a.t].W &&
-               a.qkv == g1.out.t && a.bias >= 0 && a.maskid >= 0 &&
-               g2.amode == A_ROWS && g2.a.t == a.out && !g2.ln && g2.act == ACT_NONE && g2.omode == O_WIN && g2.win_table >= 0 && g2.K == Cm && g2.N == Cm && g2.res.t == g1.a.t && g2.res2.t < 0 &&
-               !g2.has_clip && g2.pool_out < 0 && g2.se_scale < 0 && g2.res_scale < 0 && whole_view(g2.a) && whole_view(g2.res) && whole_view(g2.out) && plan.tensors[g2.out.t].C == Cm &&
-               plan.tensors[g2.out.t].H * plan.tensors[g2.out.t].W == g1.Mrows && g2.Mrows == g1.Mrows &&
-               passes_on(lt, g1.out.t, (int)i) && passes_on(lt, a.out, (int)i + 1) &&
-               plan.blobs[g1.w].data.size() == (size_t)3 * Cm * Cm * 4 && plan.blobs[g2.w].data.size() == (size_t)Cm * Cm * 4;
-    }
-    // The candidate launches of a pass: the folds that plan facts, the load's switches and its precision allow.  upload_plan() lays the arena out for them and then
-    // confirms or splits each with the prepared launch parameters.  No op but a launch's last may write the pass's output (out_override replaces the last op's).
-    std::vector<Launch> candidate_launches(Precision prec) const {
-        const int nops = (int)plan.ops.size();
-        std::vector<Launch> ls;
-        for (int i = 0; i < nops; ++i) ls.push_back(launch(L_OP, i, i));
-        const Lifetimes lt = lifetimes(ls);
-        ls.clear();
-        const bool fp16 = plan.elt == 2 && !check_general, tf32 = plan.elt == 4 && prec == Precision::TF32;   // (W2X_CHECK_GENERAL compares every shape-specialised launch alone)
-        // the image head (Linear 96 -> 4x4 sub-pixels x 4 channels) behind a C = 96 MLP: it rides on k_mlp96q.hip's launch only
-        auto head = [&](const Op& a, const Op& b, int i) {
-            return !switches().no_fuse_head && mlp_frag32(96) && a.kind == OP_MLP && b.kind == OP_GEMM && a.m.C == 96 && a.m.stats_out < 0 && b.g.a.t == a.m.y && passes_on(lt, a.m.y, i) &&
-                   b.g.amode == A_ROWS && b.g.K == 96 && b.g.N == 64 && b.g.r == 4 && b.g.omode == O_PIXSHUF && b.g.res.t < 0 && b.g.res2.t < 0 && b.g.act == ACT_NONE && !b.g.ln &&
-                   b.g.se_scale < 0 && b.g.res_scale < 0 && b.g.stats_out < 0 && b.g.pool_out < 0;
-        };
-        // the stem (3x3, 4 -> 48 / 32 channels) in front of the 3x3 convolution that alone reads it
-        auto stem = [&](const Op& a, const Op& b, int i) {
-            return a.kind == OP_GEMM && b.kind == OP_GEMM && a.g.a.t >= 0 && plan.tensors[a.g.a.t].C == 4 && ((a.g.N == 48 && b.g.K == 9 * 48) || (a.g.N == 32 && b.g.K == 9 * 32 && b.g.N == 64 && b.g.pool_out < 0)) &&
-                   b.g.a.t == a.g.out.t && passes_on(lt, a.g.out.t, i) && a.g.stats_out < 0 && a.g.pool_out < 0;
-        };
-        // cunet's ConvTranspose 2x2 stride 2 (a pixel-shuffle projection with a skip add) in front of the 64 -> 64 3x3 convolution that alone reads it
-        auto up = [&](const Op& a, const Op& b, int i) {
-            return a.kind == OP_GEMM && b.kind == OP_GEMM && a.g.omode == O_PIXSHUF && a.g.r == 2 && a.g.K == 64 && a.g.N == 256 && a.g.res.t >= 0 && a.g.res2.t < 0 && a.g.res_scale < 0 && !a.g.ln &&
-                   a.g.stats_out < 0 && a.g.pool_out < 0 && b.g.amode == A_CONV && b.g.kh == 3 && b.g.kw == 3 && b.g.stride == 1 && b.g.K == 9 * 64 && b.g.N == 64 && b.g.pool_out < 0 &&
-                   b.g.a.t == a.g.out.t && passes_on(lt, a.g.out.t, i);
-        };
-        auto writes_output = [&](int j) { const auto wr = tensor_use(plan.ops[j]).wr; return std::find(wr.begin(), wr.end(), plan.out_tensor) != wr.end(); };
-        for (int i = 0; i < nops;) {
-            const Op& a = plan.ops[i]; const Op& b = plan.ops[std::min(i + 1, nops - 1)];
-            LaunchKind k = tf32 && attn32_triple(i, lt) ? L_ATTN32 : tf32 && mlp32_pair(i, lt) ? L_MLP32 : i + 1 == nops || !fp16 ? L_OP :
-                           head(a, b, i) ? L_HEAD : stem(a, b, i) ? L_STEM : up(a, b, i) ? L_UP : L_OP;
-            int last = i + (k == L_OP ? 0 : k == L_ATTN32 ? 2 : 1);
-            for (int j = i; j < last; ++j) if (writes_output(j)) { k = L_OP; last = i; }
-            ls.push_back(launch(k, i, last));
-            i = last + 1;
-        }
-        return ls;
-    }
     // the bf16 hi / lo planes of an fp32 matrix [N][K] in fragment-major order (split4 of k_f32.hip on the host: hi = bf16(x), lo = bf16(x - hi), round to nearest even)
     void upload_planes(const std::vector<uint8_t>& w, int N, int K, void*& dh, void*& dl) {
         std::vector<uint16_t> hi((size_t)N * K), lo((size_t)N * K);
@@ -655,52 +505,28 @@ struct Img2Img::Impl {
         }
     }
 
+    // load(): the plan on the device, in four steps.  The order of the allocations and copies is part of it (load() says why).
     void upload_plan(Precision prec) {
-        // Activation arena: tensors whose lifetimes (first writer .. last reader, in op order) do not overlap share
-        // memory.  An op's outputs are placed before its inputs are released, so no op reads and writes one address.
-        // The lifetimes are those of the candidate launches: a candidate split back into its ops below keeps a layout that covers what they need.
-        const std::vector<Launch> candidates = candidate_launches(prec);
-        {
-            const int nt = (int)plan.tensors.size(), nops = (int)plan.ops.size();
-            const Lifetimes lt = lifetimes(candidates);
-            const std::vector<int>& first = lt.first; const std::vector<int>& last = lt.last;
-            struct Block { size_t off, size; };
-            std::vector<Block> free_list;
-            std::vector<size_t> off(nt, 0);
-            size_t arena = 0;
-            // 256 bytes x 12: offsets stay 256-byte aligned when the arena is cut into 2, 3 or 4 group parts (run_network).
-            constexpr size_t unit = 3072;
-            auto align = [](size_t v) { return (v + unit - 1) / unit * unit; };
-            auto alloc = [&](size_t bytes) -> size_t {
-                bytes = align(bytes);
-                int best = -1;
-                for (int k = 0; k < (int)free_list.size(); ++k) if (free_list[k].size >= bytes && (best < 0 || free_list[k].size < free_list[best].size)) best = k;
-                if (best >= 0) { size_t o = free_list[best].off; free_list[best].off += bytes; free_list[best].size -= bytes; if (!free_list[best].size) free_list.erase(free_list.begin() + best); return o; }
-                if (!free_list.empty()) {   // grow the last free block if it touches the end of the arena
-                    for (int k = 0; k < (int)free_list.size(); ++k) if (free_list[k].off + free_list[k].size == arena) { size_t o = free_list[k].off; arena = o + bytes; free_list.erase(free_list.begin() + k); return o; }
-                }
-                size_t o = arena; arena += bytes; return o;
-            };
-            auto release = [&](size_t o, size_t bytes) {
-                bytes = align(bytes);
-                free_list.push_back({o, bytes});
-                std::sort(free_list.begin(), free_list.end(), [](const Block& a, const Block& b) { return a.off < b.off; });
-                for (size_t k = 0; k + 1 < free_list.size();) { if (free_list[k].off + free_list[k].size == free_list[k + 1].off) { free_list[k].size += free_list[k + 1].size; free_list.erase(free_list.begin() + k + 1); } else ++k; }
-            };
-            std::vector<char> placed(nt, 0);
-            for (int step = -1; step <= nops; ++step) {
-                for (int t = 0; t < nt; ++t) if (!placed[t] && first[t] == step && last[t] >= 0) { off[t] = alloc((size_t)plan.tensors[t].bytes()); placed[t] = 1; }
-                for (int t = 0; t < nt; ++t) if (placed[t] == 1 && last[t] == step) { release(off[t], (size_t)plan.tensors[t].bytes()); placed[t] = 2; }
-            }
-            // (tensors no op touches - the q / k / v, score and hidden maps inside the fused attention and MLP ops - get no memory: at config 3 they
-            //  were 19 of the arena's 20.7 GiB until round 3)
-            hipAssert(hipMalloc(&arena_base, arena + 1024));   // slack: vector reads past a table's last row; the group parts rounded up to 256 bytes
-            hipAssert(hipMemsetAsync(arena_base, 0, arena + 1024, stream));
-            arena_bytes = arena;
-            pool_blocks.assign(nt, 0);
-            tensors.assign(nt, nullptr);
-            for (int t = 0; t < nt; ++t) tensors[t] = placed[t] ? (uint8_t*)arena_base + off[t] : nullptr;
-        }
+        const std::vector<Launch> candidates = candidate_launches(plan, prec, check_general);
+        place_tensors(layout_arena(plan, candidates));
+        upload_weights();
+        prepare_gemm_params();
+        confirm_launches(candidates);
+        hipAssert(hipStreamSynchronize(stream));
+    }
+    // step 1: the activation arena for the layout of the candidate launches (schedule.h): one allocation, tensors[] from the offsets
+    void place_tensors(const ArenaLayout& lay) {
+        const int nt = (int)plan.tensors.size();
+        const size_t arena = lay.bytes;
+        hipAssert(hipMalloc(&arena_base, arena + 1024));   // slack: vector reads past a table's last row; the group parts rounded up to 256 bytes
+        hipAssert(hipMemsetAsync(arena_base, 0, arena + 1024, stream));
+        arena_bytes = arena;
+        pool_blocks.assign(nt, 0);
+        tensors.assign(nt, nullptr);
+        for (int t = 0; t < nt; ++t) tensors[t] = lay.placed[t] ? (uint8_t*)arena_base + lay.off[t] : nullptr;
+    }
+    // step 2: the weights and tables, and the fragment-major / permuted copies of the matrices that kernels read in that order
+    void upload_weights() {
         blobs.assign(plan.blobs.size(), nullptr);
         for (size_t i = 0; i < plan.blobs.size(); ++i) {
             const auto& d = plan.blobs[i].data;
@@ -764,6 +590,9 @@ struct Img2Img::Impl {
             }
         for (const Op& op : plan.ops)
             if (plan.elt == 2 && op.kind == OP_SWINATTN) { frag_major_blob(op.sa.wqkv, 3 * op.sa.C, op.sa.C); frag_major_blob(op.sa.wproj, op.sa.C, op.sa.C); }
+    }
+    // step 3: every GEMM op's launch parameters for a whole pass (run_network() adjusts a copy per pass and group)
+    void prepare_gemm_params() {
         gemm.assign(plan.ops.size(), GemmParams{}); final_op = -1;
         for (size_t i = 0; i < plan.ops.size(); ++i) {
             const Op& op = plan.ops[i];
@@ -796,6 +625,9 @@ struct Img2Img::Impl {
             if (p.a.Cs != 4 && (p.a.Cs % 8)) throw std::runtime_error("plan: unaligned input channels");
         }
         if (final_op < 0) throw std::runtime_error("plan: the output tensor is not produced by a fused op");
+    }
+    // step 4: the launch list.  The candidates are what plan facts allow (schedule.h); what the kernels take of the prepared parameters - which compare device pointers - is decided here.
+    void confirm_launches(const std::vector<Launch>& candidates) {
         // Each fold confirmed with the prepared launch parameters, or split back into its ops.  The image head: k_mlp96q.hip takes a 32-row tile inside one image, at most
         // two token rows, and clip bounds that fp16 holds exactly.  The stem and the transposed convolution: k_conv48.hip conv48_kernel<true> / k_conv3.hip conv3_kernel
         // (switches.h no_fuse_head / no_fuse_stem / no_fuse_up keep the launches apart).
@@ -808,16 +640,18 @@ struct Img2Img::Impl {
             const GemmParams& p = gemm[L.last]; const GemmParams& q = gemm[L.first];
             const bool ok = L.kind == L_HEAD ? head_supported(p) : L.kind == L_STEM ? conv48_stem_supported(p, q) || conv3_stem_supported(p, q) : L.kind == L_UP ? conv3_up_supported(p, q) : true;
             if (ok) launches.push_back(L);
-            else for (int i = L.first; i <= L.last; ++i) launches.push_back(launch(L_OP, i, i));
+            else for (int i = L.first; i <= L.last; ++i) launches.push_back(make_launch(plan, L_OP, i, i));
         }
         // fp32 plans at Precision::TF32: the weights of the fused launches as bf16 hi / lo planes
-        for (Launch& L : launches)
+        launch_planes.assign(launches.size(), {{nullptr, nullptr, nullptr, nullptr}});
+        for (size_t k = 0; k < launches.size(); ++k) {
+            const Launch& L = launches[k]; std::array<void*, 4>& planes = launch_planes[k];
             if (L.kind == L_MLP32 || L.kind == L_ATTN32) {
                 const GemmOp& g1 = plan.ops[L.first].g; const GemmOp& g2 = plan.ops[L.last].g;
-                upload_planes(plan.blobs[g1.w].data, g1.N, g1.K, L.planes[0], L.planes[1]);
-                upload_planes(plan.blobs[g2.w].data, g2.N, g2.K, L.planes[2], L.planes[3]);
+                upload_planes(plan.blobs[g1.w].data, g1.N, g1.K, planes[0], planes[1]);
+                upload_planes(plan.blobs[g2.w].data, g2.N, g2.K, planes[2], planes[3]);
             }
-        hipAssert(hipStreamSynchronize(stream));
+        }
     }
 
     // one pass of the network over the tiles currently in plan.in_tensor; the last op writes to `out_override`
@@ -825,13 +659,12 @@ struct Img2Img::Impl {
     // (img2img_render.cpp:281) are never read back (:298-299), so they are not computed at all.
     // `grp` / `s`: the pass may be cut into NG tile groups that run side by side on NG streams (run_frame).  Tensors with disjoint
     // lifetimes share arena memory, which only holds while the ops run one after the other - so each group gets its own PART of the
-    // arena, laid out like the whole one at 1/NG of the size (a tensor of B tiles at offset o becomes B/NG tiles at o/NG; offsets are
-    // multiples of 3072 bytes): group grp of up to B/NG tiles runs the plan on arena_base + grp * arena_part.  out_override is the
-    // slab address of the group's first tile.
+    // arena, laid out like the whole one at 1/NG of the size (schedule.h arena_part_bytes / arena_group_offset): group grp of up to B/NG tiles
+    // runs the plan on arena_base + grp * arena_part.  out_override is the slab address of the group's first tile.
     int ng_now = 1;                      // NG of the pass being issued
-    size_t arena_part() const { return ((arena_bytes / ng_now) + 255) / 256 * 256; }
+    size_t arena_part() const { return arena_part_bytes(arena_bytes, ng_now); }
     uint8_t* group_ptr(const void* full, int grp) const {
-        return full ? (uint8_t*)arena_base + (size_t)grp * arena_part() + (size_t)((const uint8_t*)full - (const uint8_t*)arena_base) / ng_now : nullptr;
+        return full ? (uint8_t*)arena_base + arena_group_offset(arena_bytes, ng_now, grp, (size_t)((const uint8_t*)full - (const uint8_t*)arena_base)) : nullptr;
     }
     void run_network(void* out_override, int live = -1, int grp = -1, hipStream_t s = nullptr, const LiveExt* ext = nullptr) {
         if (!s) s = stream;
@@ -852,9 +685,10 @@ struct Img2Img::Impl {
             return p;
         };
         for (const Launch& L : launches) try {
+            const std::array<void*, 4>& planes = launch_planes[&L - launches.data()];
             const Op& op = plan.ops[L.first];
             struct Range { Impl* e; bool on; ~Range() { if (on) e->roctx_pop(); } } range{this, roctx_push != nullptr};   // W2X_ROCTX=1: a roctx range per launch (rocprofv3 --marker-trace)
-            if (range.on) roctx_push(launch_label(L).c_str());
+            if (range.on) roctx_push(launch_label(plan, L).c_str());
             auto issue = [&](auto&& f) { stamp_begin(L.family, L.flops, L.timed); hipAssert(f()); stamp_end(); };   // (profileFrame: events around the launch alone)
             switch (L.kind) {
                 case L_HEAD: {      // the image head rides on the MLP launch
@@ -875,7 +709,7 @@ struct Img2Img::Impl {
                     const GemmParams p = gp(L.first), q = gp(L.last);
                     Mlp32Params m;
                     m.x = (const float*)p.a.p; m.y = (float*)q.out.p; m.M = (long)live * p.Mrows; m.C = p.K; m.stats_in = p.stats_in;
-                    m.w1h = L.planes[0]; m.w1l = L.planes[1]; m.w2h = L.planes[2]; m.w2l = L.planes[3];
+                    m.w1h = planes[0]; m.w1l = planes[1]; m.w2h = planes[2]; m.w2l = planes[3];
                     m.b1 = p.bias; m.b2 = q.bias; m.stats_out = q.stats_out; m.eps_out = q.ln_eps;
                     issue([&] { return launch_mlp32(m, s); });
                     break;
@@ -886,7 +720,7 @@ struct Img2Img::Impl {
                     SwinAttn32Params m;
                     m.x = (const float*)p.a.p; m.y = (float*)q.out.p; m.res = (const float*)q.res.p; m.B = live; m.nwin = a.nwin; m.C = p.K; m.pix_per_item = p.Mrows;
                     m.table_in = p.win_table; m.table_out = q.win_table; m.stats_in = p.stats_in;
-                    m.wqkv_h = L.planes[0]; m.wqkv_l = L.planes[1]; m.wproj_h = L.planes[2]; m.wproj_l = L.planes[3];
+                    m.wqkv_h = planes[0]; m.wqkv_l = planes[1]; m.wproj_h = planes[2]; m.wproj_l = planes[3];
                     m.bqkv = p.bias; m.bproj = q.bias; m.scale = a.scale; m.bias = (const float*)blobs[a.bias]; m.maskid = (const int*)blobs[a.maskid];
                     m.stats_out = q.stats_out; m.eps_out = q.ln_eps;
                     issue([&] { return launch_swinattn32(m, s); });
@@ -946,14 +780,8 @@ struct Img2Img::Impl {
                 }
             }
         } catch (const std::exception& e) {     // name the op: "invalid argument" alone says nothing about a 60-op plan
-            throw std::runtime_error("op " + launch_label(L) + ": " + e.what());
+            throw std::runtime_error("op " + launch_label(plan, L) + ": " + e.what());
         }
-    }
-    // "12 [name]", or "12-13 [name + name]" for a fold: the roctx range and the error messages of a launch
-    std::string launch_label(const Launch& L) const {
-        std::string m = std::to_string(L.first) + (L.last > L.first ? "-" + std::to_string(L.last) : "") + " [";
-        for (int i = L.first; i <= L.last; ++i) m += (i > L.first ? " + " : "") + plan.ops[i].name;
-        return m + "]";
     }
     template <class TP> MlpParams mlp_params(const Op& op, int live, const TP& tp) const {
         const MlpOp& m = op.m;
@@ -1989,14 +1817,14 @@ bool Img2Img::load(const std::string& modelPath, const RenderConfig& config) try
         return false;
     }
     impl->cfg = config;
-    int folds[Impl::L_ATTN32 + 1] = {};
-    for (const Impl::Launch& L : impl->launches) ++folds[L.kind];
+    int folds[L_ATTN32 + 1] = {};
+    for (const Launch& L : impl->launches) ++folds[L.kind];
     W2X_LOG(info, "Loaded \"" + enginePath + "\": " + std::to_string(plan.ops.size()) + " ops, " + std::to_string(plan.B) + " tiles per pass, activation arena " +
                       std::to_string(impl->arena_bytes >> 20) + " MiB" +
-                      (folds[Impl::L_STEM] ? ", " + std::to_string(folds[Impl::L_STEM]) + " stem folded into the launch of the convolution behind it" : "") +
-                      (folds[Impl::L_UP] ? ", " + std::to_string(folds[Impl::L_UP]) + " transposed convolution folded into the launch of the convolution behind it" : "") +
-                      (folds[Impl::L_HEAD] ? ", image head folded into the last MLP launch" : "") +
-                      (folds[Impl::L_ATTN32] + folds[Impl::L_MLP32] ? ", " + std::to_string(folds[Impl::L_ATTN32]) + " attention and " + std::to_string(folds[Impl::L_MLP32]) + " MLP branches as fused fp32-row launches." : "."));
+                      (folds[L_STEM] ? ", " + std::to_string(folds[L_STEM]) + " stem folded into the launch of the convolution behind it" : "") +
+                      (folds[L_UP] ? ", " + std::to_string(folds[L_UP]) + " transposed convolution folded into the launch of the convolution behind it" : "") +
+                      (folds[L_HEAD] ? ", image head folded into the last MLP launch" : "") +
+                      (folds[L_ATTN32] + folds[L_MLP32] ? ", " + std::to_string(folds[L_ATTN32]) + " attention and " + std::to_string(folds[L_MLP32]) + " MLP branches as fused fp32-row launches." : "."));
     // :262-269 blend ramps
     impl->ovx = (int)std::lround(plan.T * config.scaling * config.overlapX);
     impl->ovy = (int)std::lround(plan.T * config.scaling * config.overlapY);

@@ -980,7 +980,6 @@ hipError_t launch_swinattn32_c(const SwinAttn32Params& p, hipStream_t s) {
 
 }  // namespace
 
-bool mlp32_supported(int C) { return C == 96 || C == 192; }
 hipError_t launch_mlp32(const Mlp32Params& p, hipStream_t s) {
     if (p.M <= 0 || !p.x || !p.y || !p.stats_in || !p.w1h || !p.w1l || !p.w2h || !p.w2l || !p.b1 || !p.b2) return hipErrorInvalidValue;
     if (p.C == 96) return launch_mlp32_c<96>(p, s);
@@ -988,7 +987,6 @@ hipError_t launch_mlp32(const Mlp32Params& p, hipStream_t s) {
     return hipErrorInvalidValue;
 }
 
-bool swinattn32_supported(int C, int heads, int hd, int ntok) { return heads == 6 && ntok == 36 && ((C == 96 && hd == 16) || (C == 192 && hd == 32)); }
 hipError_t launch_swinattn32(const SwinAttn32Params& p, hipStream_t s) {
     if (p.B <= 0 || p.nwin <= 0 || !p.x || !p.y || !p.res || !p.stats_in || !p.table_in || !p.table_out || !p.wqkv_h || !p.wqkv_l || !p.wproj_h || !p.wproj_l ||
         !p.bqkv || !p.bproj || !p.bias || !p.maskid) return hipErrorInvalidValue;

@@ -232,7 +232,6 @@ struct Mlp32Params {
     const float *b1 = nullptr, *b2 = nullptr;
     float* stats_out = nullptr; float eps_out = 1e-5f;
 };
-bool mlp32_supported(int C);
 hipError_t launch_mlp32(const Mlp32Params& p, hipStream_t s);
 // Fused Swin attention branch on fp32 rows with split-bf16 products (Precision::TF32; k_f32.hip swinattn32_kernel): y = res + proj(W-MSA((x - mean) rstd)), in place of the
 // un-fused plan's qkv gemm -> attention core -> proj gemm.  Rows are pixels of plain [pixels][C] maps; table_in / table_out: window-order row -> pixel inside a batch item
@@ -249,11 +248,10 @@ struct SwinAttn32Params {
     const float* bias = nullptr; const int* maskid = nullptr;      // fp32 [nmask][6][36][36], [nwin]
     float* stats_out = nullptr; float eps_out = 1e-5f;
 };
-bool swinattn32_supported(int C, int heads, int hd, int ntok);
 hipError_t launch_swinattn32(const SwinAttn32Params& p, hipStream_t s);
 hipError_t launch_mlp(const MlpParams& p, hipStream_t s);
 hipError_t launch_swin_attn(const SwinAttnParams& p, hipStream_t s);
-// swin_attn_supported / mlp_supported / gemm_row_stats_supported / attn_supported: support.h
+// swin_attn_supported / mlp_supported / mlp32_supported / swinattn32_supported / gemm_row_stats_supported / attn_supported: support.h
 hipError_t launch_se(const SeParams& p, hipStream_t s);
 hipError_t launch_scale(void* x, const float* scale, int B, int HW, int Cs, bool fp32, hipStream_t s);
 hipError_t launch_gather(const GatherParams& p, hipStream_t s);
