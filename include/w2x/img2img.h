@@ -77,6 +77,16 @@ struct YuvFormat {
 // the transparent ones before the network sees the frame; skipUniformAlpha: a frame whose alpha plane is one value keeps it and runs no alpha tiles.
 struct RgbaOptions { int bleed = 0; bool skipUniformAlpha = false; };
 
+// Extension: dithered output (setDither).  Without it every integer sample the engine writes is sat(rint(V)) of an fp32 value V; with it the sample
+// (x, y) of plane c is min(max(floor(fl32(V + t)), 0), maxcode) with the threshold t = (rank + 0.5) / N of its position:
+//   Ordered:   N = 64, rank from the recursive 8 x 8 Bayer matrix at ((x + dx) & 7, (y + dy) & 7);
+//   BlueNoise: N = 4096, rank from a 64 x 64 void-and-cluster table at ((x + dx) & 63, (y + dy) & 63);
+//   dx = 17 c + 23 phase, dy = 29 c + 41 phase; c: R, G, B = 0, 1, 2 whatever the memory order, a gray frame is plane 1, Y, U, V = 0, 1, 2; (x, y) absolute in the destination.
+// Alpha is never dithered, float destinations are not touched, and a V that is an integer gives that integer.  Frame i of a sequence call is dithered as a
+// single call at phase + i * advance would be: advance 0 keeps the pattern still (what encoders prefer), 1 is temporal dither.
+enum class Dither { None = 0, Ordered = 1, BlueNoise = 2 };
+struct DitherOptions { Dither mode = Dither::None; unsigned phase = 0; unsigned advance = 0; };
+
 class Img2Img {
 public:
     Img2Img();
@@ -200,6 +210,13 @@ public:
     // registrations behind on this runtime - a later copy from recycled addresses then aborted the process.
     bool pinHost(void* data, size_t bytes);
     void unpinHost(void* data);
+    // Extension: the dither of every integer sample the following frame calls write (DitherOptions above).  A setting of the engine like the callbacks: allowed
+    // before load(), kept across calls and loads, read by the very next frame.  An unknown mode: false (message callback), the previous setting stays.  The
+    // default, Dither::None, is the undithered engine: the same kernels, the same bytes.  renderStrip / renderSharded / shardFinish keep their bytes equal to
+    // render()'s (the threshold depends on absolute coordinates only; renderSharded refuses engines whose settings differ).  YUV frames: Y, U, V are
+    // the plane indices 0, 1, 2, a chroma sample takes the coordinates of its own plane, NV12 / P010 those of the I420 samples they are.
+    bool setDither(const DitherOptions& options);
+    DitherOptions dither() const;
     void setMessageCallback(MessageCallback callback);   // img2img.h:21
     void setProgressCallback(ProgressCallback callback); // img2img.h:22
 
@@ -211,6 +228,10 @@ public:
     // Test hook: alpha_bleed_planes_kernel alone - the four planes up, the bleed at `radius`, the three colour planes gather would read down (colour: the size and
     // depth of src).  words (two, or null): the reduced alpha range, max(key) and max(top - key) (kernels.h AlphaBleedPlanesParams).
     bool alphaBleedPlanes(const PlanarRgbaImage& src, PlanarImage& colour, int radius, unsigned* words = nullptr);
+    // Test hook: the dithered store alone - the planes of src (bits 32: fp32 values v, any number) up, every sample quantised from V = v * (2^bits - 1)
+    // by the device function the compose and resample kernels store through, with the current setDither() options (None: sat(rint(V))), the planes of dst (8, 10,
+    // 12 or 16 bits, the size of src) down.  Plane k has plane index k.  No network, no tiles.
+    bool ditherPlanes(const PlanarImage& src, PlanarImage& dst);
     int outputTileSize() const;
     int scaling() const;   // RenderConfig::scaling of the loaded configuration (0 before load)
     double planFlops() const;

@@ -1,5 +1,6 @@
 // Flat C ABI over w2x::Img2Img (declared in include/w2x/c_api.h, which cites the reference interfaces).
 #include "../../include/w2x/c_api.h"
+#include "../../include/w2x/c_api_dither.h"
 #include "../../include/w2x/c_api_gray.h"
 #include "../../include/w2x/c_api_planar.h"
 #include "../../include/w2x/c_api_rgbap.h"
@@ -427,6 +428,33 @@ int w2x_alpha_bleed_device(w2x_engine* e, const uint8_t* bgra, int rows, int col
     if (!e) return 0;
     w2x::Image d = image(bgr, rows, cols, bgr_step);
     return e->engine.alphaBleed(image(bgra, rows, cols, bgra_step), d, radius) ? 1 : 0;
+}
+// dithered output (include/w2x/c_api_dither.h)
+int w2x_set_dither(w2x_engine* e, int mode, unsigned phase, unsigned advance) {
+    if (!e) return 0;
+    w2x::DitherOptions o; o.mode = (w2x::Dither)mode; o.phase = phase; o.advance = advance;   // (the engine refuses unknown modes through the message callback)
+    return e->engine.setDither(o) ? 1 : 0;
+}
+int w2x_get_dither(const w2x_engine* e, int* mode, unsigned* phase, unsigned* advance) {
+    if (!e) return 0;
+    const w2x::DitherOptions o = e->engine.dither();
+    if (mode) *mode = (int)o.mode;
+    if (phase) *phase = o.phase;
+    if (advance) *advance = o.advance;
+    return 1;
+}
+int w2x_dither_table(int mode, uint16_t* out, int* side) {
+    if (mode != W2X_DITHER_ORDERED && mode != W2X_DITHER_BLUENOISE) return 0;
+    const int n = mode == W2X_DITHER_ORDERED ? 8 : w2x::kDitherSide;
+    if (side) *side = n;
+    if (out) for (int y = 0; y < n; ++y) for (int x = 0; x < n; ++x) out[y * n + x] = (uint16_t)w2x::dither_rank(mode, 0, 0, x, y);
+    return 1;
+}
+int w2x_dither_rank(int mode, unsigned phase, int c, int x, int y) { return w2x::dither_rank(mode, phase, c, x, y); }
+int w2x_dither_planes(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, void* const* dst_planes, const size_t* dst_steps, int bits) {
+    if (!e) return 0;
+    w2x::PlanarImage d = planar_image(dst_planes, dst_steps, rows, cols, bits);
+    return e->engine.ditherPlanes(planar_image(src_planes, src_steps, rows, cols, 32), d) ? 1 : 0;
 }
 void* w2x_alloc_host(w2x_engine* e, size_t bytes) { return e ? e->engine.allocHost(bytes) : nullptr; }
 void w2x_free_host(w2x_engine* e, void* data) { if (e) e->engine.freeHost(data); }

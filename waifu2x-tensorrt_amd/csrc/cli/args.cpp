@@ -96,6 +96,11 @@ std::string usage() {
            "                              --alpha-bleed (not on gbrapf32le input) and --alpha-skip-uniform apply to them, as do --outscale / --outsize and --devices.\n"
            "                              With --rgba-out and no --pix_fmt the encoder's format is the --rgba-out one.  Stills, single frames read through ffmpeg\n"
            "                              and the built-in AVI route are rendered as without them.  Not with --colorspace, --gray, --rgb-in or --rgb-out\n"
+           "      --dither TEXT [none]    (extension) {none,ordered,bluenoise}: dither every 8- to 16-bit sample written instead of rounding it - an 8 x 8 Bayer\n"
+           "                              matrix or a 64 x 64 blue-noise table, on the GPU where the unrounded value is; smooth gradients leave without bands.\n"
+           "                              Alpha and float output are never dithered.  Every route honours it\n"
+           "      --dither-temporal       (extension) with --dither: videos move the pattern from frame to frame (default: the same pattern on every frame,\n"
+           "                              which encoders prefer)\n"
            "      --tta-mode TEXT [mean]  (extension) {mean,reference}: with --tta, `mean` averages the 8 augmentations; `reference`\n"
            "                              reproduces the bytes of the reference's accumulation (img2img_render.cpp:313-316); --tta-compat = reference\n"
            "  build                       Build model\n"
@@ -121,7 +126,7 @@ int rgba_format_bits(const std::string& name) {
 Options parse(int argc, const char* const* argv) {
     Options o;
     std::vector<std::string> a(argv + 1, argv + argc);
-    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_outsize = false, seen_filter = false, seen_colorspace = false, seen_range = false, seen_bleed = false, seen_skip = false, seen_pixfmt = false, seen_gray = false;
+    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_outsize = false, seen_filter = false, seen_colorspace = false, seen_range = false, seen_bleed = false, seen_skip = false, seen_pixfmt = false, seen_gray = false, seen_dither = false;
     auto value = [&](size_t& i) -> std::string {
         const std::string name = a[i];
         auto eq = name.find('=');
@@ -175,6 +180,8 @@ Options parse(int argc, const char* const* argv) {
         else if (k == "--alpha-bleed") { o.alphaBleed = to_int(k, value(i)); seen_bleed = true; }
         else if (k == "--alpha-skip-uniform") { o.alphaSkipUniform = true; seen_skip = true; }
         else if (k == "--gray") { o.gray = true; seen_gray = true; }
+        else if (k == "--dither") { o.dither = value(i); std::transform(o.dither.begin(), o.dither.end(), o.dither.begin(), ::tolower); seen_dither = true; }
+        else if (k == "--dither-temporal") { o.ditherTemporal = true; seen_dither = true; }
         else if (k == "--resize-filter") { o.resizeFilter = value(i); std::transform(o.resizeFilter.begin(), o.resizeFilter.end(), o.resizeFilter.begin(), ::tolower); seen_filter = true; }
         else if (k == "--colorspace") { o.colorspace = value(i); std::transform(o.colorspace.begin(), o.colorspace.end(), o.colorspace.begin(), ::tolower); seen_colorspace = true; }
         else if (k == "--color_range") { o.colorRange = value(i); std::transform(o.colorRange.begin(), o.colorRange.end(), o.colorRange.begin(), ::tolower); seen_range = true; }
@@ -271,12 +278,17 @@ Options parse(int argc, const char* const* argv) {
             if (seen_rgb_in || seen_rgb_out) throw std::runtime_error(std::string(opt) + ": not together with " + (seen_rgb_in ? "--rgb-in" : "--rgb-out") + " (one raw frame format per run)");
         }
         if (seen_rgba_out && !seen_pixfmt) o.pixFmt = o.rgbaOut;
+        if (seen_dither) {
+            member<std::string>("--dither", o.dither, {"none", "ordered", "bluenoise"});
+            if (o.ditherTemporal && o.dither == "none") throw std::runtime_error("--dither-temporal: needs --dither ordered or --dither bluenoise");
+        }
         if (seen_bleed) {
             if (!(o.alphaBleed >= 0 && o.alphaBleed <= 16)) throw std::runtime_error("--alpha-bleed: " + std::to_string(o.alphaBleed) + " not in [0, 16] (the radius in pixels)");
             if (o.alphaBleed > 0 && o.rgbaIn == kRgbaFormats[4]) throw std::runtime_error("--alpha-bleed: not together with --rgba-in " + o.rgbaIn + " (the bleed takes integer samples)");
             if (o.alphaBleed > 0 && o.deep) throw std::runtime_error("--alpha-bleed: not together with --deep (the bleed works on 8-bit colour; 16-bit stills keep the colours as stored)");
         }
-    } else if (seen_gray) throw std::runtime_error("--gray: only with render");
+    } else if (seen_dither) throw std::runtime_error(std::string(o.ditherTemporal ? "--dither-temporal" : "--dither") + ": only with render");
+    else if (seen_gray) throw std::runtime_error("--gray: only with render");
     else if (seen_rgb_in || seen_rgb_out) throw std::runtime_error(std::string(seen_rgb_in ? "--rgb-in" : "--rgb-out") + ": only with render");
     else if (seen_rgba_in || seen_rgba_out) throw std::runtime_error(std::string(seen_rgba_in ? "--rgba-in" : "--rgba-out") + ": only with render");
     else if (seen_outscale || seen_outsize || seen_filter || seen_colorspace || seen_range || seen_bleed || seen_skip || seen_yuv_in || seen_yuv_out || seen_loc)
@@ -336,6 +348,7 @@ std::string to_json(const Options& o) {
        << ", \"alpha_bleed\": " << o.alphaBleed << ", \"alpha_skip_uniform\": " << (o.alphaSkipUniform ? "true" : "false") << ", \"gray\": " << (o.gray ? "true" : "false")
        << ", \"rgb_in\": " << (o.rgbIn.empty() ? std::string("null") : q(o.rgbIn)) << ", \"rgb_out\": " << (o.rgbOut.empty() ? std::string("null") : q(o.rgbOut))
        << ", \"rgba_in\": " << (o.rgbaIn.empty() ? std::string("null") : q(o.rgbaIn)) << ", \"rgba_out\": " << (o.rgbaOut.empty() ? std::string("null") : q(o.rgbaOut))
+       << ", \"dither\": " << q(o.dither) << ", \"dither_temporal\": " << (o.ditherTemporal ? "true" : "false")
        << ", \"codec\": " << q(o.codec) << ", \"pix_fmt\": " << q(o.pixFmt) << ", \"crf\": " << o.crf << ", \"inputs\": [";
     for (size_t i = 0; i < o.inputs.size(); ++i) os << (i ? ", " : "") << q(o.inputs[i]);
     os << "], \"model_path\": " << q(o.command == "convert" ? "" : model_path(o)) << ", \"suffix\": " << q(o.command == "convert" ? "" : output_suffix(o)) << ", \"outputs\": [";

@@ -52,6 +52,9 @@ struct Options {
     bool gray = false;                    // --gray (extension, render only): gray PNGs and ffmpeg videos stay one channel (Img2Img::renderGray*)
     std::string rgbIn, rgbOut;            // --rgb-in / --rgb-out FMT (extension, render only; kRgbFormats): videos read through ffmpeg travel as raw planar RGB frames
                                           // of these formats (Img2Img::renderSequencePlanar*); with --rgb-out and no --pix_fmt the encoder's format is the --rgb-out one
+    std::string dither = "none";          // --dither {none,ordered,bluenoise} (extension, render only): every integer sample the engine writes is dithered
+                                          // (Img2Img::setDither) - stills, --deep, --gray, colour of alpha PNGs, every raw video format; alpha never
+    bool ditherTemporal = false;          // --dither-temporal: videos move the pattern from frame to frame (DitherOptions::advance = 1); default: a still pattern
     std::string rgbaIn, rgbaOut;          // --rgba-in / --rgba-out FMT (extension, render only; kRgbaFormats): videos read through ffmpeg travel as raw planar RGBA frames
                                           // of these formats (Img2Img::renderSequencePlanarRgba*, with --alpha-bleed / --alpha-skip-uniform); the encoder's format as with --rgb-out
     bool printConfig = false;             // --print-config: dump the parsed options and derived names as JSON and exit (tests)

@@ -243,6 +243,17 @@ int main(int argc, char** argv) {
             c.overlapX = c.overlapY = o.blend; c.tta = o.tta; c.ttaBugCompat = o.ttaMode == "reference";
             if (!engines.back()->load(modelPath, c)) return -1;
         }
+        // --dither: a setting of the engines, so every route below - stills, --deep, --gray, the colour of alpha PNGs, every raw video format, --outscale /
+        // --outsize - writes dithered samples without knowing about it; a video moves the pattern per frame with --dither-temporal.  dither_on(false) switches it
+        // off around the one thing that must not be dithered and is rendered as a frame of its own: the alpha plane of the two-call routes.
+        DitherOptions ditherOptions;
+        ditherOptions.mode = o.dither == "ordered" ? Dither::Ordered : o.dither == "bluenoise" ? Dither::BlueNoise : Dither::None;
+        ditherOptions.advance = o.ditherTemporal ? 1u : 0u;
+        auto dither_on = [&](bool on) {
+            for (auto& e : engines) if (!e->setDither(on ? ditherOptions : DitherOptions())) return false;
+            return true;
+        };
+        if (!dither_on(true)) return -1;
         // --outscale (extension): every output lround(W * F) x lround(H * F), the network's output resized on the device; --outsize: every output W x H
         const ResizeFilter filter = o.resizeFilter == "bilinear" ? ResizeFilter::Bilinear : ResizeFilter::Bicubic;
         const bool resize = o.outscale > 0 || o.outsizeW > 0;
@@ -332,6 +343,7 @@ int main(int argc, char** argv) {
                     }
                     if (!render_still(src, dst)) return -1;
                 }
+                if (!in.alpha.empty() && !one_call && !dither_on(false)) return -1;   // alpha is never dithered: an opaque cut-out stays opaque
                 if (!in.alpha.empty() && !one_call && o.devices == 1) {   // the alpha plane as a gray frame (renderGray: the green channel of render() of B = G = R = A)
                     out.alpha.resize((size_t)out.rows * out.cols);
                     if (!render_plane(in.alpha.data(), out.alpha.data(), 1)) return -1;
@@ -346,6 +358,7 @@ int main(int argc, char** argv) {
                     out.alpha.resize((size_t)out.rows * out.cols);
                     for (size_t i = 0; i < out.alpha.size(); ++i) out.alpha[i] = go.bgr[3 * i + 1];
                 }
+                if (!in.alpha.empty() && !one_call && !dither_on(true)) return -1;
                 std::string outFile = cli::output_path(o, file, true);
                 if (fs::path(file).extension() == ".bmp" || fs::path(file).extension() == ".BMP") outFile = fs::path(outFile).replace_extension(".bmp").string();   // built-in formats stay what they were, except ...
                 if (fs::path(outFile).extension() == ".ppm") outFile = fs::path(outFile).replace_extension(".png").string();

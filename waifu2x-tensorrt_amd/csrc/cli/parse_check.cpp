@@ -14,6 +14,9 @@
 //                                                           the four planes and the three bled ones, packed, for the test to compare with its own statement
 //   w2x_parse_check schedule FILE BATCH TILE {fp16|tf32|fp32} [switch=value ...]   lower_for_shape -> candidate_launches -> layout_arena (schedule.h), printed: one line
 //                                                           per plan, op, launch and tensor and one for the arena; tests/test_schedule_host.py judges them
+//   w2x_parse_check dither {ordered|bluenoise} PHASE PLANE X0 Y0 W H   dither_rank / dither_threshold (dither.h) over a W x H window of plane PLANE at PHASE:
+//                                                           one line of ranks per row and, behind a line "thresholds", one of thresholds; "table" in place of the
+//                                                           mode prints the 64 x 64 table.  tests/test_dither_host.py compares them with its own statement
 // Exit code: 0 = accepted, 2 = rejected with a message on stderr (the clean `false` of the product path); anything else is a crash
 // or a sanitizer report.
 #include <algorithm>
@@ -26,6 +29,7 @@
 #include <string>
 #include <vector>
 
+#include "../dither.h"
 #include "../lower.h"
 #include "../schedule.h"
 #include "../switches.h"
@@ -36,7 +40,7 @@
 using namespace w2x;
 
 static int run(int argc, char** argv) {
-    if (argc < 3) throw std::runtime_error("usage: w2x_parse_check {onnx|plan|image|avi|args|tiles|bleed|planes|schedule} ...");
+    if (argc < 3) throw std::runtime_error("usage: w2x_parse_check {onnx|plan|image|avi|args|tiles|bleed|planes|schedule|dither} ...");
     const std::string mode = argv[1];
     if (mode == "onnx") {
         if (argc < 5) throw std::runtime_error("onnx FILE BATCH TILE [fp32]");
@@ -165,6 +169,24 @@ static int run(int argc, char** argv) {
         for (size_t t = 0; t < plan.tensors.size(); ++t)
             printf("tensor %zu bytes=%lld first=%d last=%d placed=%d off=%zu\n", t, (long long)plan.tensors[t].bytes(), lt.first[t], lt.last[t], lay.placed[t] ? 1 : 0, lay.off[t]);
         printf("arena bytes=%zu part2=%zu part3=%zu part4=%zu\n", lay.bytes, arena_part_bytes(lay.bytes, 2), arena_part_bytes(lay.bytes, 3), arena_part_bytes(lay.bytes, 4));
+    } else if (mode == "dither") {
+        const std::string what = argv[2];
+        if (what == "table") {
+            const uint16_t* t = dither_table();
+            for (int y = 0; y < kDitherSide; ++y) { for (int x = 0; x < kDitherSide; ++x) printf(x ? " %d" : "%d", (int)t[y * kDitherSide + x]); printf("\n"); }
+            return 0;
+        }
+        if (argc < 9) throw std::runtime_error("dither {ordered|bluenoise} PHASE PLANE X0 Y0 W H  |  dither table");
+        int m = kDitherNone;
+        if (!dither_parse_mode(what.c_str(), m) || m == kDitherNone) throw std::runtime_error("dither: mode " + what + " is none of ordered, bluenoise");
+        const unsigned phase = (unsigned)strtoul(argv[3], nullptr, 10);
+        const int c = atoi(argv[4]), x0 = atoi(argv[5]), y0 = atoi(argv[6]), w = atoi(argv[7]), h = atoi(argv[8]);
+        if (argc > 9 || c < 0 || c > 2 || x0 < 0 || y0 < 0 || w <= 0 || h <= 0 || w > 4096 || h > 4096) throw std::runtime_error("dither: PLANE in 0..2, a window of at most 4096 x 4096 at a non-negative origin");
+        std::vector<int> ranks((size_t)w * h);                           // (an exact-size heap block: an index past the window is a sanitizer report)
+        for (int y = 0; y < h; ++y) for (int x = 0; x < w; ++x) ranks[(size_t)y * w + x] = dither_rank(m, phase, c, x0 + x, y0 + y);
+        for (int y = 0; y < h; ++y) { for (int x = 0; x < w; ++x) printf(x ? " %d" : "%d", ranks[(size_t)y * w + x]); printf("\n"); }
+        printf("thresholds\n");
+        for (int y = 0; y < h; ++y) { for (int x = 0; x < w; ++x) printf(x ? " %.17g" : "%.17g", (double)dither_threshold(m, phase, c, x0 + x, y0 + y)); printf("\n"); }
     } else throw std::runtime_error("unknown mode " + mode);
     return 0;
 }

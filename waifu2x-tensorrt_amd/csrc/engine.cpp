@@ -331,6 +331,23 @@ struct Img2Img::Impl {
         GrayJob gray;
         PlanarJob planar;
     };
+    // Dithered output (setDither): a setting of the engine like the callbacks, NOT part of the job - it outlives the call that follows it and every
+    // load().  The launches that end a frame (finish_frame, outside the captured passes) read it through dither_now(), so a changed setting acts on the very
+    // next frame, replayed passes or not.  seq_frame: the index of the frame a sequence call is issuing (run_sequence), 0 everywhere else - frame i of a
+    // sequence is dithered like a single call at phase + i * advance.
+    DitherOptions dither;
+    unsigned seq_frame = 0;
+    const uint16_t* d_noise = nullptr;                                   // the blue-noise table on this engine's device, looked up once per load (release() forgets it)
+    DitherArgs dither_now() {
+        const int mode = (int)dither.mode;
+        if (mode == kDitherNone) return DitherArgs();
+        if (mode == kDitherBlueNoise && !d_noise) {                      // (the caller holds the engine's DeviceGuard)
+            hipError_t e = hipSuccess;
+            d_noise = dither_table_device(&e);
+            hipAssert(e);
+        }
+        return dither_args(mode, dither.phase + seq_frame * dither.advance, mode == kDitherBlueNoise ? d_noise : nullptr);
+    }
     Job job;
     struct JobScope { Impl* im; ~JobScope() { im->job = Job{}; } };
     std::vector<void*> pinned;
@@ -453,7 +470,7 @@ struct Img2Img::Impl {
         if (s_dn) { (void)hipStreamDestroy(s_dn); s_dn = nullptr; }
         frame2_cap = out2_cap = 0;
         for (ResizeTables& t : rs_tables) for (void* q : {(void*)t.fx, (void*)t.fy, (void*)t.wx, (void*)t.wy}) if (q) (void)hipFree(q);
-        rs_tables.clear(); job = Job{};
+        rs_tables.clear(); job = Job{}; d_noise = nullptr;
         if (d_canvas) { (void)hipFree(d_canvas); d_canvas = nullptr; }
         canvas_cap = 0;
         for (void** q : {(void**)&d_bgr, (void**)&d_alpha, (void**)&d_minmax}) if (*q) { (void)hipFree(*q); *q = nullptr; }
@@ -1020,7 +1037,7 @@ struct Img2Img::Impl {
         cp.dst = d_out; cp.dst_step = bgr_step(cp.outW, deep); cp.deep = deep ? 1 : 0;
         cp.x0 = x0; cp.x1 = x1; cp.y0 = y0; cp.y1 = y1; cp.first_tile = first_tile;
         stamp_begin(4, 0);
-        hipAssert(launch_compose(cp, on ? on : stream));
+        hipAssert(launch_compose(cp, on ? on : stream, dither_now()));
         stamp_end();
     }
     // what every compose launch shares: the slab, the canvas size, the tile grid and its strides, the blend ramps, the TTA flags
@@ -1205,10 +1222,10 @@ struct Img2Img::Impl {
             default: hipAssert(launch_compose_canvas(cp, d_canvas, on));
         }
     }
-    template <class P> void resample_into(P& p, hipStream_t on, hipError_t (*launch)(const P&, hipStream_t)) {
+    template <class P> void resample_into(P& p, hipStream_t on, hipError_t (*launch)(const P&, hipStream_t, const DitherArgs&)) {
         resample_base(p);
         p.dst = d_out; p.dst_step = frame_step(p.outW, true);
-        hipAssert(launch(p, on));
+        hipAssert(launch(p, on, dither_now()));
     }
     void resample(hipStream_t on) {
         switch (job.kind) {
@@ -1218,7 +1235,7 @@ struct Img2Img::Impl {
                 ResamplePlanarParams p;
                 resample_base(p);
                 p.dst = frame_planes(d_out, p.outH, p.outW, true);
-                hipAssert(launch_resample_planar(p, on));
+                hipAssert(launch_resample_planar(p, on, dither_now()));
                 break;
             }
             case Job::PLANAR_RGBA: {                                  // the four planes of the target size
@@ -1226,14 +1243,14 @@ struct Img2Img::Impl {
                 resample_base(p);
                 p.dst = rgba_planes(d_out, p.outH, p.outW, true);
                 p.uniform = job.rgba.uniform ? 1 : 0; p.alpha_value = uniform_alpha();
-                hipAssert(launch_resample_planar_rgba(p, on));
+                hipAssert(launch_resample_planar_rgba(p, on, dither_now()));
                 break;
             }
             case Job::YUV: {                                          // the planes of job.yuv.out_layout at the target size
                 ResampleYuvParams p;
                 resample_base(p);
                 p.dst = yuv_layout(d_out, p.outH, p.outW, job.yuv.out_bits, job.yuv.out_layout); p.dst.siting = job.yuv.out_siting; p.k = job.yuv.out;
-                hipAssert(launch_resample_yuv(p, job.rs->rows_max_above, on));
+                hipAssert(launch_resample_yuv(p, job.rs->rows_max_above, on, dither_now()));
                 break;
             }
         }
@@ -1246,7 +1263,7 @@ struct Img2Img::Impl {
                 p.c = compose_base(rows, cols, grid);
                 p.dst = yuv_layout(d_out, p.c.outH, p.c.outW, job.yuv.out_bits, job.yuv.out_layout); p.dst.siting = job.yuv.out_siting; p.k = job.yuv.out;
                 stamp_begin(4, 0);
-                hipAssert(launch_compose_yuv(p, on));
+                hipAssert(launch_compose_yuv(p, on, dither_now()));
                 stamp_end();
                 break;
             }
@@ -1255,7 +1272,7 @@ struct Img2Img::Impl {
                 p.c = compose_base(rows, cols, grid);
                 p.c.dst = d_out; p.c.dst_step = frame_step(p.c.outW, true);
                 p.alpha_tiles = alpha_tiles(); p.alpha_value = job.rgba.value;
-                hipAssert(launch_compose_rgba(p, on));
+                hipAssert(launch_compose_rgba(p, on, dither_now()));
                 break;
             }
             case Job::PLANAR_RGBA: {                                  // four planes of job.planar.out_bits
@@ -1263,7 +1280,7 @@ struct Img2Img::Impl {
                 p.c = compose_base(rows, cols, grid);
                 p.dst = rgba_planes(d_out, p.c.outH, p.c.outW, true);
                 p.alpha_tiles = alpha_tiles(); p.alpha_value = uniform_alpha();
-                hipAssert(launch_compose_planar_rgba(p, on));
+                hipAssert(launch_compose_planar_rgba(p, on, dither_now()));
                 break;
             }
             case Job::GRAY: case Job::PLANAR: {                       // one sample per pixel, or three planes of job.planar.out_bits
@@ -1271,7 +1288,7 @@ struct Img2Img::Impl {
                 p.c = compose_base(rows, cols, grid);
                 p.dst = frame_planes(d_out, p.c.outH, p.c.outW, true);
                 stamp_begin(4, 0);
-                hipAssert(launch_compose_planar(p, on));
+                hipAssert(launch_compose_planar(p, on, dither_now()));
                 stamp_end();
                 break;
             }
@@ -1564,7 +1581,7 @@ struct Img2Img::Impl {
     float run_sequence(int count, int rows, int cols, const TileGrid& grid, const StripPlan& sp, const Up& up, const Down& down) {
         uint8_t* const frames[2] = {d_frame, d_frame2};
         uint8_t* const outs[2] = {d_out, d_out2};
-        struct Restore { Impl* im; uint8_t* f; uint8_t* o; ~Restore() { im->d_frame = f; im->d_out = o; } } restore{this, frames[0], outs[0]};   // also on exceptions
+        struct Restore { Impl* im; uint8_t* f; uint8_t* o; ~Restore() { im->d_frame = f; im->d_out = o; im->seq_frame = 0; } } restore{this, frames[0], outs[0]};   // also on exceptions
         // frame f is composed on the second group's stream while frame f + 1's first group already runs (run_rolling_frame) when every pass of a frame splits
         const bool roll = count > 1 && rolls() && can_roll(sp.tile_count);
         if (roll) ensure(d_slab2, slab2_cap, slab_cap);
@@ -1577,6 +1594,7 @@ struct Img2Img::Impl {
             hipAssert(hipEventRecord(ev_up[b], s_up));
             hipAssert(hipStreamWaitEvent(stream, ev_up[b], 0));
             d_frame = frames[b]; d_out = outs[b];
+            seq_frame = (unsigned)i;                                     // (the frame's dither phase: dither_now())
             if (roll) {
                 run_rolling_frame(rows, cols, grid, sp, b, i >= 2 ? ev_dn[b] : nullptr);
                 hipAssert(hipEventRecord(ev_comp[b], gstream[0]));              // (behind the compose launch: both groups have gathered, the output is whole)
@@ -2120,6 +2138,9 @@ bool Img2Img::renderSharded(Img2Img* const* engines, int count, const Image& src
                 c.overlapY != c0.overlapY || c.tta != c0.tta || c.ttaBugCompat != c0.ttaBugCompat || c.batchSize != c0.batchSize) {
                 W2X_LOG(error, "renderSharded: engine " + std::to_string(k) + " was loaded with another model or configuration."); return false;
             }
+            if (a.dither.mode != impl->dither.mode || a.dither.phase != impl->dither.phase || a.dither.advance != impl->dither.advance) {
+                W2X_LOG(error, "renderSharded: engine " + std::to_string(k) + " has another dither setting."); return false;
+            }
             for (int j = 0; j < k; ++j) if (engines[j] == engines[k]) { W2X_LOG(error, "renderSharded: the same engine twice."); return false; }
         }
         const RenderConfig& cfg = impl->cfg;
@@ -2499,6 +2520,44 @@ bool Img2Img::alphaBleedPlanes(const PlanarRgbaImage& src, PlanarImage& colour, 
     for (int k = 0; k < 3; ++k)
         hipAssert(hipMemcpy2DAsync(colour.planes[k], colour.steps[k], impl->d_bgr + (size_t)k * d.step[0] * rows, d.step[0], width, rows, hipMemcpyDeviceToHost, impl->stream));
     if (words) hipAssert(hipMemcpyAsync(words, impl->d_minmax, 2 * sizeof(unsigned), hipMemcpyDeviceToHost, impl->stream));
+    hipAssert(hipStreamSynchronize(impl->stream));
+    return true;
+    });
+}
+
+bool Img2Img::setDither(const DitherOptions& options) {
+    if (!dither_mode_ok((int)options.mode)) { W2X_LOG(error, "Unknown dither mode " + std::to_string((int)options.mode) + ": expected none, ordered or bluenoise."); return false; }
+    impl->dither = options;
+    return true;
+}
+DitherOptions Img2Img::dither() const { return impl->dither; }
+
+bool Img2Img::ditherPlanes(const PlanarImage& src, PlanarImage& dst) {
+    const char* who = "ditherPlanes";
+    return impl->entry(who, "Dither planes called before a successful load.", "Dither planes failed unexpectedly: ",
+                       [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
+    const int rows = src.rows, cols = src.cols, bits = dst.bits;
+    if (src.bits != 32 || (bits != 8 && bits != 10 && bits != 12 && bits != 16)) { W2X_LOG_AS(who, error, "Dither planes take float (32-bit) planes and give planes of 8, 10, 12 or 16 bits."); return false; }
+    if (rows <= 0 || cols <= 0) { W2X_LOG_AS(who, error, "Input image is empty."); return false; }
+    if (dst.rows != rows || dst.cols != cols) { W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(cols) + "x" + std::to_string(rows) + "."); return false; }
+    const size_t bps = planar_sample_bytes(bits), in_width = (size_t)cols * 4, out_width = (size_t)cols * bps;
+    for (int k = 0; k < 3; ++k) {
+        if (!src.planes[k] || src.steps[k] < in_width || ((((size_t)src.planes[k]) | src.steps[k]) & 3) != 0) { W2X_LOG_AS(who, error, "Input image has a missing plane or an invalid step."); return false; }
+        if (!dst.planes[k] || dst.steps[k] < out_width || ((((size_t)dst.planes[k]) | dst.steps[k]) & (bps - 1)) != 0) { W2X_LOG_AS(who, error, "Output image has a missing plane or an invalid step."); return false; }
+    }
+    impl->last_rows = impl->last_cols = 0;   // (d_frame and d_out are overwritten: the last render() frame is no longer there to replay)
+    const size_t in_step = Impl::planar_step(cols, 32), out_step = Impl::planar_step(cols, bits);
+    impl->ensure(impl->d_frame, impl->frame_cap, 3 * in_step * rows);
+    impl->ensure(impl->d_out, impl->out_cap, 3 * out_step * rows);
+    PlanarPlanes a, b;
+    a.rows = b.rows = rows; a.cols = b.cols = cols; a.n = b.n = 3; a.bits = 32; b.bits = bits;
+    for (int k = 0; k < 3; ++k) {
+        a.p[k] = impl->d_frame + (size_t)k * in_step * rows; a.step[k] = in_step;
+        b.p[k] = impl->d_out + (size_t)k * out_step * rows; b.step[k] = out_step;
+        hipAssert(hipMemcpy2DAsync(a.p[k], in_step, src.planes[k], src.steps[k], in_width, rows, hipMemcpyHostToDevice, impl->stream));
+    }
+    hipAssert(launch_dither_planes(a, b, impl->dither_now(), impl->stream));
+    for (int k = 0; k < 3; ++k) hipAssert(hipMemcpy2DAsync(dst.planes[k], dst.steps[k], b.p[k], out_step, out_width, rows, hipMemcpyDeviceToHost, impl->stream));
     hipAssert(hipStreamSynchronize(impl->stream));
     return true;
     });

@@ -30,8 +30,12 @@ __global__ __launch_bounds__(kGatherThreads) void gather_planes_kernel(const Gat
 // compose_kernel with NP planes behind it.  A thread owns four consecutive pixels of a row and walks kComposeRows rows; what depends on the column only is computed
 // once per thread.  Where the four share their covering tiles, lie inside each of them and no TTA is involved, the sums come from compose_quad_sums - at every
 // output depth, since the fast path is about how the sums are fetched and not about what is stored.  The whole canvas: these frames take no strips or shards.
-template <typename P, typename S, int NP>
-__global__ __launch_bounds__(kComposeThreads) void compose_planes_kernel(const ComposePlanarParams q, float scale, int maxcode) {
+// M: kDitherNone - no further argument - is the kernel above; a dithered mode takes its DitherArgs behind maxcode (dither_of).  A gray frame's one
+// plane has plane index 1.
+template <typename P, typename S, int NP, int M = kDitherNone, typename... D>
+__global__ __launch_bounds__(kComposeThreads) void compose_planes_kernel(const ComposePlanarParams q, float scale, int maxcode, const D... dzs) {
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    const DitherArgs& dz = dither_of(dzs...);
     constexpr bool kHalf = sizeof(P) == 8;
     const ComposeParams& p = q.c;
     const int gw = (p.outW + 3) >> 2;
@@ -58,7 +62,7 @@ __global__ __launch_bounds__(kComposeThreads) void compose_planes_kernel(const C
             }
         }
 #pragma unroll
-        for (int c = 0; c < NP; ++c) store4<S>(q.dst.p[c] + (size_t)Y * q.dst.step[c], X, np, acc[c], scale, maxcode);
+        for (int c = 0; c < NP; ++c) store4<S, M>(q.dst.p[c] + (size_t)Y * q.dst.step[c], X, np, acc[c], scale, maxcode, dz, NP == 1 ? 1 : c, Y);
     }
 }
 
@@ -77,8 +81,10 @@ __global__ __launch_bounds__(256) void compose_canvas_gray_kernel(const ComposeP
 
 // resample_kernel (k_resample.hip) with NP planes behind it.  LDS: [NP][rows_max][64] fp32 - NP = 3: resample_kernel's (58.5 KiB at a factor of 4 with bicubic
 // taps), NP = 1: 19.5 KiB.
-template <typename S, int NP>
-__global__ __launch_bounds__(kRsThreads) void resample_planes_kernel(const ResamplePlanarParams p, float scale, int maxcode) {
+template <typename S, int NP, int M = kDitherNone, typename... D>
+__global__ __launch_bounds__(kRsThreads) void resample_planes_kernel(const ResamplePlanarParams p, float scale, int maxcode, const D... dzs) {
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    const DitherArgs& dz = dither_of(dzs...);
     extern __shared__ float h[];
     const int r0 = resample_pass1<NP>(p, h);
     __syncthreads();
@@ -88,7 +94,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_planes_kernel(const Resam
 #pragma unroll
     for (int c = 0; c < NP; ++c) {
         const float v[4] = {a[c][0], a[c][1], a[c][2], a[c][3]};
-        store4<S>(p.dst.p[c] + (size_t)Y * p.dst.step[c], X, np, v, scale, maxcode);
+        store4<S, M>(p.dst.p[c] + (size_t)Y * p.dst.step[c], X, np, v, scale, maxcode, dz, NP == 1 ? 1 : c, Y);
     }
 }
 
@@ -124,9 +130,9 @@ hipError_t launch_gather_planar(const GatherPlanarParams& p, hipStream_t s) {
         return hipGetLastError();
     });
 }
-hipError_t launch_compose_planar(const ComposePlanarParams& p, hipStream_t s) {
+hipError_t launch_compose_planar(const ComposePlanarParams& p, hipStream_t s, const DitherArgs& d) {
     if (p.c.outW <= 0 || p.c.outH <= 0) return hipSuccess;
-    if (!planes_ok(p.dst, p.c.outH, p.c.outW)) return hipErrorInvalidValue;
+    if (!planes_ok(p.dst, p.c.outH, p.c.outW) || !dither_args_ok(d)) return hipErrorInvalidValue;
     const int gw = (p.c.outW + 3) / 4;
     const dim3 grid((unsigned)((gw + kComposeThreads - 1) / kComposeThreads), (unsigned)((p.c.outH + kComposeRows - 1) / kComposeRows));
     const int maxcode = max_code(p.dst.bits);
@@ -134,6 +140,14 @@ hipError_t launch_compose_planar(const ComposePlanarParams& p, hipStream_t s) {
     return for_planes(p.dst, [&](auto k) {
         typedef typename decltype(k)::Sample S;
         constexpr int NP = decltype(k)::kPlanes;
+        if constexpr (!std::is_same<S, F32>::value) {                 // (float samples are never dithered: their one kernel below)
+            if (d.mode != kDitherNone) return for_dither(d, [&](auto m) {
+                constexpr int M = decltype(m)::value;
+                if (p.c.fp32) hipLaunchKernelGGL((compose_planes_kernel<float4v, S, NP, M, DitherArgs>), grid, dim3(kComposeThreads), 0, s, p, scale, maxcode, d);
+                else hipLaunchKernelGGL((compose_planes_kernel<half4, S, NP, M, DitherArgs>), grid, dim3(kComposeThreads), 0, s, p, scale, maxcode, d);
+                return hipGetLastError();
+            });
+        }
         if (p.c.fp32) hipLaunchKernelGGL((compose_planes_kernel<float4v, S, NP>), grid, dim3(kComposeThreads), 0, s, p, scale, maxcode);
         else hipLaunchKernelGGL((compose_planes_kernel<half4, S, NP>), grid, dim3(kComposeThreads), 0, s, p, scale, maxcode);
         return hipGetLastError();
@@ -147,14 +161,21 @@ hipError_t launch_compose_canvas_gray(const ComposeParams& p, float* canvas, hip
     else hipLaunchKernelGGL(compose_canvas_gray_kernel<half4>, grid, dim3(256), 0, s, p, canvas);
     return hipGetLastError();
 }
-hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s) {
+hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s, const DitherArgs& d) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
-    if (!p.canvas || !planes_ok(p.dst, p.outH, p.outW)) return hipErrorInvalidValue;
+    if (!p.canvas || !planes_ok(p.dst, p.outH, p.outW) || !dither_args_ok(d)) return hipErrorInvalidValue;
     const int maxcode = max_code(p.dst.bits);
     const float scale = (float)maxcode;
     return for_planes(p.dst, [&](auto k) {
         typedef typename decltype(k)::Sample S;
         constexpr int NP = decltype(k)::kPlanes;
+        if constexpr (!std::is_same<S, F32>::value) {
+            if (d.mode != kDitherNone) return for_dither(d, [&](auto m) {
+                constexpr int M = decltype(m)::value;
+                static unsigned lds_dither = 0;
+                return launch_resample_tiles(resample_planes_kernel<S, NP, M, DitherArgs>, NP * kRsCols, p.rows_max, lds_dither, p.outW, p.outH, s, p, scale, maxcode, d);
+            });
+        }
         static unsigned lds_done = 0;                                    // (one per instantiation of this lambda's body)
         return launch_resample_tiles(resample_planes_kernel<S, NP>, NP * kRsCols, p.rows_max, lds_done, p.outW, p.outH, s, p, scale, maxcode);
     });

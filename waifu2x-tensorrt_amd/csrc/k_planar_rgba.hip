@@ -191,8 +191,12 @@ __device__ __forceinline__ void quad_sums(const ComposeParams& p, int X, int Y, 
 }
 // compose_planes_kernel (k_planar.hip) over both tile sets: per thread four consecutive pixels of a row and kComposeRows rows; the colour planes are its NP = 3
 // sums over c.tiles, the alpha plane its NP = 1 sum over alpha_tiles.
-template <typename P, typename S>
-__global__ __launch_bounds__(kComposeThreads) void compose_planes_rgba_kernel(const ComposePlanarRgbaParams q, float scale, int maxcode) {
+// M: kDitherNone - no further argument - is the kernel above; a dithered mode takes its DitherArgs behind maxcode (dither_of).  The colour planes
+// are dithered; the alpha plane, the uniform one included, keeps sat(rint(.)).
+template <typename P, typename S, int M = kDitherNone, typename... D>
+__global__ __launch_bounds__(kComposeThreads) void compose_planes_rgba_kernel(const ComposePlanarRgbaParams q, float scale, int maxcode, const D... dzs) {
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    const DitherArgs& dz = dither_of(dzs...);
     constexpr bool kHalf = sizeof(P) == 8;
     const ComposeParams& p = q.c;
     const int gw = (p.outW + 3) >> 2;
@@ -212,7 +216,7 @@ __global__ __launch_bounds__(kComposeThreads) void compose_planes_rgba_kernel(co
         float acc[3][4] = {};                                      // [plane][pixel]
         quad_sums<P, 3>(p, X, Y, np, fast, a0, a1, acc);
 #pragma unroll
-        for (int c = 0; c < 3; ++c) store4<S>(q.dst.p[c] + (size_t)Y * q.dst.step[c], X, np, acc[c], scale, maxcode);
+        for (int c = 0; c < 3; ++c) store4<S, M>(q.dst.p[c] + (size_t)Y * q.dst.step[c], X, np, acc[c], scale, maxcode, dz, c, Y);
         float al[1][4] = {{q.alpha_value, q.alpha_value, q.alpha_value, q.alpha_value}};
         if (q.alpha_tiles) quad_sums<P, 1>(pa, X, Y, np, fast, a0, a1, al);
         store4<S>(q.dst.p[3] + (size_t)Y * q.dst.step[3], X, np, al[0], scale, maxcode);
@@ -221,8 +225,10 @@ __global__ __launch_bounds__(kComposeThreads) void compose_planes_rgba_kernel(co
 
 // resample_planes_kernel (k_planar.hip) over the canvas of an RGBA frame: NP = 4, or NP = 3 and the alpha plane its one value.  LDS: [NP][rows_max][64] fp32, at
 // a factor of 4 with bicubic taps 78 KiB (NP = 3: 58.5 KiB), resample_rgba_kernel's.
-template <typename S, int NP>
-__global__ __launch_bounds__(kRsThreads) void resample_planes_rgba_kernel(const ResamplePlanarRgbaParams p, float scale, int maxcode) {
+template <typename S, int NP, int M = kDitherNone, typename... D>
+__global__ __launch_bounds__(kRsThreads) void resample_planes_rgba_kernel(const ResamplePlanarRgbaParams p, float scale, int maxcode, const D... dzs) {
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    const DitherArgs& dz = dither_of(dzs...);
     extern __shared__ float rsp_lds[];
     const int r0 = resample_pass1<NP>(p, rsp_lds);
     __syncthreads();
@@ -232,7 +238,8 @@ __global__ __launch_bounds__(kRsThreads) void resample_planes_rgba_kernel(const 
 #pragma unroll
     for (int c = 0; c < NP; ++c) {
         const float v[4] = {a[c][0], a[c][1], a[c][2], a[c][3]};
-        store4<S>(p.dst.p[c] + (size_t)Y * p.dst.step[c], X, np, v, scale, maxcode);
+        if (M != kDitherNone && c < 3) store4<S, M>(p.dst.p[c] + (size_t)Y * p.dst.step[c], X, np, v, scale, maxcode, dz, c, Y);   // (plane 3 is alpha)
+        else store4<S>(p.dst.p[c] + (size_t)Y * p.dst.step[c], X, np, v, scale, maxcode);
     }
     if constexpr (NP == 3) {
         const float v[4] = {p.alpha_value, p.alpha_value, p.alpha_value, p.alpha_value};
@@ -286,27 +293,43 @@ hipError_t launch_gather_planar_rgba(const GatherPlanarRgbaParams& p, hipStream_
         return hipGetLastError();
     });
 }
-hipError_t launch_compose_planar_rgba(const ComposePlanarRgbaParams& p, hipStream_t s) {
+hipError_t launch_compose_planar_rgba(const ComposePlanarRgbaParams& p, hipStream_t s, const DitherArgs& d) {
     if (p.c.outW <= 0 || p.c.outH <= 0) return hipSuccess;
-    if (!rgba_planes_ok(p.dst, p.c.outH, p.c.outW)) return hipErrorInvalidValue;
+    if (!rgba_planes_ok(p.dst, p.c.outH, p.c.outW) || !dither_args_ok(d)) return hipErrorInvalidValue;
     const int gw = (p.c.outW + 3) / 4;
     const dim3 grid((unsigned)((gw + kComposeThreads - 1) / kComposeThreads), (unsigned)((p.c.outH + kComposeRows - 1) / kComposeRows));
     const int maxcode = max_code(p.dst.bits);
     const float scale = (float)maxcode;
     return for_sample(p.dst.bits, [&](auto k) {
         typedef decltype(k) S;
+        if constexpr (!std::is_same<S, F32>::value) {                 // (float samples are never dithered)
+            if (d.mode != kDitherNone) return for_dither(d, [&](auto m) {
+                constexpr int M = decltype(m)::value;
+                if (p.c.fp32) hipLaunchKernelGGL((compose_planes_rgba_kernel<float4v, S, M, DitherArgs>), grid, dim3(kComposeThreads), 0, s, p, scale, maxcode, d);
+                else hipLaunchKernelGGL((compose_planes_rgba_kernel<half4, S, M, DitherArgs>), grid, dim3(kComposeThreads), 0, s, p, scale, maxcode, d);
+                return hipGetLastError();
+            });
+        }
         if (p.c.fp32) hipLaunchKernelGGL((compose_planes_rgba_kernel<float4v, S>), grid, dim3(kComposeThreads), 0, s, p, scale, maxcode);
         else hipLaunchKernelGGL((compose_planes_rgba_kernel<half4, S>), grid, dim3(kComposeThreads), 0, s, p, scale, maxcode);
         return hipGetLastError();
     });
 }
-hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStream_t s) {
+hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStream_t s, const DitherArgs& d) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
-    if (!p.canvas || !rgba_planes_ok(p.dst, p.outH, p.outW)) return hipErrorInvalidValue;
+    if (!p.canvas || !rgba_planes_ok(p.dst, p.outH, p.outW) || !dither_args_ok(d)) return hipErrorInvalidValue;
     const int maxcode = max_code(p.dst.bits);
     const float scale = (float)maxcode;
     return for_sample(p.dst.bits, [&](auto k) {
         typedef decltype(k) S;
+        if constexpr (!std::is_same<S, F32>::value) {
+            if (d.mode != kDitherNone) return for_dither(d, [&](auto m) {
+                constexpr int M = decltype(m)::value;
+                static unsigned lds_dither[2] = {0, 0};
+                if (p.uniform) return launch_resample_tiles(resample_planes_rgba_kernel<S, 3, M, DitherArgs>, 3 * kRsCols, p.rows_max, lds_dither[0], p.outW, p.outH, s, p, scale, maxcode, d);
+                return launch_resample_tiles(resample_planes_rgba_kernel<S, 4, M, DitherArgs>, 4 * kRsCols, p.rows_max, lds_dither[1], p.outW, p.outH, s, p, scale, maxcode, d);
+            });
+        }
         static unsigned lds_done[2] = {0, 0};                            // (a pair per instantiation of this lambda's body)
         if (p.uniform) return launch_resample_tiles(resample_planes_rgba_kernel<S, 3>, 3 * kRsCols, p.rows_max, lds_done[0], p.outW, p.outH, s, p, scale, maxcode);
         return launch_resample_tiles(resample_planes_rgba_kernel<S, 4>, 4 * kRsCols, p.rows_max, lds_done[1], p.outW, p.outH, s, p, scale, maxcode);

@@ -14,6 +14,7 @@
 //   se/scale: cunet squeeze-excite gate and channel scaling.
 #include "kernels.h"
 #include "prepost_device.h"
+#include <type_traits>
 
 namespace w2x {
 namespace {
@@ -46,11 +47,17 @@ __global__ __launch_bounds__(256) void gather_kernel(const GatherParams p) {
     }
 }
 
-template <typename P>
-__device__ __forceinline__ unsigned compose_pixel(const ComposeParams& p, const P* tiles, int X, int Y) {
+template <typename P, int M>
+__device__ __forceinline__ unsigned compose_pixel(const ComposeParams& p, const P* tiles, int X, int Y, const DitherArgs& dz) {
     float a0, a1, a2;
     compose_pixel_sums<P>(p, tiles, X, Y, a0, a1, a2);
-    return quantize_bgr(a0, a1, a2);
+    return quantize_bgr_at<M>(a0, a1, a2, dz, X, Y);
+}
+// launch(std::integral_constant<int, M>()) for the dithered mode of d: the switch from the run-time mode to the kernel instantiation
+template <typename Launch> hipError_t for_dither(const DitherArgs& d, Launch launch) {
+    if (d.mode == kDitherOrdered) return launch(std::integral_constant<int, kDitherOrdered>());
+    if (d.mode == kDitherBlueNoise && d.table) return launch(std::integral_constant<int, kDitherBlueNoise>());
+    return hipErrorInvalidValue;                                    // no kernel for it: an error, never the undithered kernel
 }
 
 typedef _Float16 half8 __attribute__((ext_vector_type(8)));
@@ -67,8 +74,12 @@ typedef _Float16 half8 __attribute__((ext_vector_type(8)));
 // 3.1 TB/s with its integer unit busier than its memory pipe.
 // (measured at config 3, profiles/r3_kernels/compose_geometry.txt: rows x threads 8 x 128 0.140 ms, 4 x 128 0.119, 16 x 128 0.177, 4 x 64 0.115-0.118, 2 x 64 0.117, 1 x 64 0.125)
 // (kComposeRows / kComposeThreads: kernels.h, shared with the kernels of k_planar.hip that have this launch shape)
-template <typename P>
-__global__ __launch_bounds__(kComposeThreads) void compose_kernel(const ComposeParams p) {
+// M: kDitherNone - no further argument - is the kernel above; a dithered mode takes its DitherArgs behind p (dither_of).  (X, Y) are canvas
+// coordinates, so a strip's or a shard's rect gets the thresholds the whole frame would.
+template <typename P, int M = kDitherNone, typename... D>
+__global__ __launch_bounds__(kComposeThreads) void compose_kernel(const ComposeParams p, const D... dzs) {
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    const DitherArgs& dz = dither_of(dzs...);
     constexpr bool kHalf = sizeof(P) == 8;                          // the four-pixel fast path reads fp16 tiles
     const int x1 = p.x1 > 0 ? p.x1 : p.outW, sw = x1 - p.x0;
     const int gw = (sw + 3) >> 2;                                   // pixel groups per row
@@ -92,9 +103,15 @@ __global__ __launch_bounds__(kComposeThreads) void compose_kernel(const ComposeP
             for (int k = 0; k < np; ++k) {
                 float r, g, b;
                 compose_pixel_sums<P>(p, tiles, X + k, Y, r, g, b);
-                d16[3 * k] = (uint16_t)min(max(__float2int_rn(b * 65535.f), 0), 65535);
-                d16[3 * k + 1] = (uint16_t)min(max(__float2int_rn(g * 65535.f), 0), 65535);
-                d16[3 * k + 2] = (uint16_t)min(max(__float2int_rn(r * 65535.f), 0), 65535);
+                if constexpr (M == kDitherNone) {
+                    d16[3 * k] = (uint16_t)min(max(__float2int_rn(b * 65535.f), 0), 65535);
+                    d16[3 * k + 1] = (uint16_t)min(max(__float2int_rn(g * 65535.f), 0), 65535);
+                    d16[3 * k + 2] = (uint16_t)min(max(__float2int_rn(r * 65535.f), 0), 65535);
+                } else {
+                    d16[3 * k] = (uint16_t)quant_code<M>(b * 65535.f, 65535, dz, 2, X + k, Y);
+                    d16[3 * k + 1] = (uint16_t)quant_code<M>(g * 65535.f, 65535, dz, 1, X + k, Y);
+                    d16[3 * k + 2] = (uint16_t)quant_code<M>(r * 65535.f, 65535, dz, 0, X + k, Y);
+                }
             }
             continue;
         }
@@ -132,14 +149,14 @@ __global__ __launch_bounds__(kComposeThreads) void compose_kernel(const ComposeP
                 }
             }
 #pragma unroll
-            for (int k = 0; k < 4; ++k) px[k] = quantize_bgr(acc[k][0], acc[k][1], acc[k][2]);
+            for (int k = 0; k < 4; ++k) px[k] = quantize_bgr_at<M>(acc[k][0], acc[k][1], acc[k][2], dz, X + k, Y);
             unsigned* dw = (unsigned*)d;
             dw[0] = px[0] | px[1] << 24;
             dw[1] = px[1] >> 8 | px[2] << 16;
             dw[2] = px[2] >> 16 | px[3] << 8;
         } else {
             for (int k = 0; k < np; ++k) {
-                const unsigned v = compose_pixel<P>(p, tiles, X + k, Y);
+                const unsigned v = compose_pixel<P, M>(p, tiles, X + k, Y, dz);
                 d[3 * k] = (uint8_t)v; d[3 * k + 1] = (uint8_t)(v >> 8); d[3 * k + 2] = (uint8_t)(v >> 16);
             }
         }
@@ -257,6 +274,14 @@ __global__ __launch_bounds__(256) void gather_yuv_kernel(const GatherYuvParams p
 
 __device__ __forceinline__ unsigned yuv_code(float off, float scale, float v, int maxcode) { return (unsigned)min(max(__float2int_rn(off + scale * v), 0), maxcode); }
 
+// M: the code of sample (x, y) of plane c (Y, U, V = 0, 1, 2; chroma samples in their own plane's coordinates, NV12's as the I420 samples they are).
+// kDitherNone is yuv_code; a dithered mode adds the sample's threshold to the same value - the expression as yuv_code writes it - and rounds down.
+template <int M>
+__device__ __forceinline__ unsigned yuv_code_at(float off, float scale, float v, int maxcode, const DitherArgs& dz, int c, int x, int y) {
+    if constexpr (M == kDitherNone) return yuv_code(off, scale, v, maxcode);
+    else return dither_code<M>(off + scale * v, dither_t<M>(dz, c, x, y), maxcode);
+}
+
 // compose_kernel for a YUV 4:2:0 output.  A thread owns kYuvSites consecutive chroma sites of one chroma row: the 2 x 8 luma pixels under them
 // (rows 2i, 2i + 1, columns 8t .. 8t + 7).  Each pixel's sums come from compose_pixel_sums (the blend and TTA order of the u8 path), clamped to [0, 1];
 // Y is coded per pixel.  Chroma site j filters the two rows (1/2, 1/2) and columns 2j - 1, 2j, 2j + 1 (1/4, 1/2, 1/4), coordinates clamped to the
@@ -272,8 +297,12 @@ __device__ __forceinline__ unsigned yuv_code(float off, float scale, float v, in
 // above, so a workgroup walks a BAND of kYuvBand consecutive chroma rows (blockIdx.y picks the band) and carries that row's clamped R, G, B - 8 columns x 3
 // floats per lane and lane 0's left column - in registers from one chroma row into the next; only the luma row above a band's first chroma row is computed a
 // second time (row -1 clamps to row 0: nothing to compute).  Pixel sums: (2 kYuvBand + 1) / (2 kYuvBand) of kYuvLeft's.
-template <typename P, int L, int S = kYuvLeft>
-__global__ __launch_bounds__(kYuvThreads) void compose_yuv_kernel(const ComposeYuvParams p) {
+// M: kDitherNone - no further argument - is the above; a dithered mode takes its DitherArgs behind p (dither_of): Y at (X0 + q, Y), the codes of
+// chroma site (ci, j0 + s) at that position of planes 1 and 2.
+template <typename P, int L, int S = kYuvLeft, int M = kDitherNone, typename... D>
+__global__ __launch_bounds__(kYuvThreads) void compose_yuv_kernel(const ComposeYuvParams p, const D... dzs) {
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    const DitherArgs& dz = dither_of(dzs...);
     static_assert(kYuvSites == 4, "the packed stores below are written for four sites per thread");
     static_assert(L == kYuvI420 || L == kYuvI422 || L == kYuvNV12, "4:4:4 output is compose_yuv444_kernel");
     static_assert(S == kYuvLeft || S == kYuvCenter || (S == kYuvTopLeft && L != kYuvI422), "I422 has no row rule: its kYuvTopLeft is kYuvLeft");
@@ -323,7 +352,7 @@ __global__ __launch_bounds__(kYuvThreads) void compose_yuv_kernel(const ComposeY
             for (int q = 0; q < kCols; ++q) {
                 float o[3] = {0.f, 0.f, 0.f};
                 if (q < ncols) pixel(X0 + q, Y, o);
-                yc[q] = yuv_code(k.y_off, k.y_scale, k.kr * o[0] + k.kg * o[1] + k.kb * o[2], k.maxcode) << sh;
+                yc[q] = yuv_code_at<M>(k.y_off, k.y_scale, k.kr * o[0] + k.kg * o[1] + k.kb * o[2], k.maxcode, dz, 0, X0 + q, Y) << sh;
                 if constexpr (kBand) {
 #pragma unroll
                     for (int e = 0; e < 3; ++e) {                   // row 2i: 1/4 of the row above (row -1 clamps to row 0) + 1/2; row 2i + 1: + 1/4, and carried down
@@ -382,8 +411,8 @@ __global__ __launch_bounds__(kYuvThreads) void compose_yuv_kernel(const ComposeY
 #pragma unroll
             for (int e = 0; e < 3; ++e) f[e] = kLeftCol ? 0.25f * (s ? v[qc - 1][e] : left[e]) + 0.5f * v[qc][e] + 0.25f * v[qr][e] : 0.5f * v[qc][e] + 0.5f * v[qr][e];
             const float Y = k.kr * f[0] + k.kg * f[1] + k.kb * f[2];
-            uc[s] = yuv_code(k.c_off, k.c_scale, (f[2] - Y) * k.cb_div, k.maxcode);
-            vc[s] = yuv_code(k.c_off, k.c_scale, (f[0] - Y) * k.cr_div, k.maxcode);
+            uc[s] = yuv_code_at<M>(k.c_off, k.c_scale, (f[2] - Y) * k.cb_div, k.maxcode, dz, 1, j0 + s, ci);
+            vc[s] = yuv_code_at<M>(k.c_off, k.c_scale, (f[0] - Y) * k.cr_div, k.maxcode, dz, 2, j0 + s, ci);
         }
         if constexpr (kSemi) {                                      // NV12 / P010: U, V, U, V, ... in plane 1
             uint8_t* row = p.dst.p[1] + (size_t)ci * p.dst.step[1];
@@ -421,8 +450,10 @@ __global__ __launch_bounds__(kYuvThreads) void compose_yuv_kernel(const ComposeY
 // 16-byte loads, elsewhere each pixel goes through compose_pixel_sums; the sums and their order are compose_pixel_sums' either way.  Each pixel's R, G, B
 // are clamped to [0, 1] and coded on the spot: Y by compose_yuv_kernel's expression (the same bytes on the same canvas), Cb and Cr from the pixel's own
 // colour - no filter, no neighbour.  A full group stores 4 bytes per plane (10-bit: 8); the ragged right end stores sample by sample.
-template <typename P>
-__global__ __launch_bounds__(kComposeThreads) void compose_yuv444_kernel(const ComposeYuvParams p) {
+template <typename P, int M = kDitherNone, typename... D>
+__global__ __launch_bounds__(kComposeThreads) void compose_yuv444_kernel(const ComposeYuvParams p, const D... dzs) {
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    const DitherArgs& dz = dither_of(dzs...);
     constexpr bool kHalf = sizeof(P) == 8;
     const ComposeParams& c = p.c;
     const YuvCoefs& k = p.k;
@@ -483,9 +514,9 @@ __global__ __launch_bounds__(kComposeThreads) void compose_yuv444_kernel(const C
 #pragma unroll
             for (int e = 0; e < 3; ++e) o[e] = fminf(fmaxf(acc[q][e], 0.f), 1.f);
             const float Yn = k.kr * o[0] + k.kg * o[1] + k.kb * o[2];
-            yc[q] = yuv_code(k.y_off, k.y_scale, Yn, k.maxcode);
-            uc[q] = yuv_code(k.c_off, k.c_scale, (o[2] - Yn) * k.cb_div, k.maxcode);
-            vc[q] = yuv_code(k.c_off, k.c_scale, (o[0] - Yn) * k.cr_div, k.maxcode);
+            yc[q] = yuv_code_at<M>(k.y_off, k.y_scale, Yn, k.maxcode, dz, 0, X + q, Y);
+            uc[q] = yuv_code_at<M>(k.c_off, k.c_scale, (o[2] - Yn) * k.cb_div, k.maxcode, dz, 1, X + q, Y);
+            vc[q] = yuv_code_at<M>(k.c_off, k.c_scale, (o[0] - Yn) * k.cr_div, k.maxcode, dz, 2, X + q, Y);
         }
         for (int pl = 0; pl < 3; ++pl) {
             const unsigned* cc = pl == 0 ? yc : pl == 1 ? uc : vc;
@@ -605,12 +636,19 @@ hipError_t launch_gather(const GatherParams& p, hipStream_t s) {
     else hipLaunchKernelGGL(gather_kernel<half4>, grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }
-hipError_t launch_compose(const ComposeParams& p, hipStream_t s) {
+hipError_t launch_compose(const ComposeParams& p, hipStream_t s, const DitherArgs& d) {
+    if (!dither_args_ok(d)) return hipErrorInvalidValue;
     const int gw = (((p.x1 > 0 ? p.x1 : p.outW) - p.x0) + 3) / 4;
     if (gw <= 0 || p.outH <= 0) return hipSuccess;
     const int nrows = (p.y1 > 0 ? p.y1 : p.outH) - p.y0;
     if (nrows <= 0) return hipSuccess;
     const dim3 grid((unsigned)((gw + kComposeThreads - 1) / kComposeThreads), (unsigned)((nrows + kComposeRows - 1) / kComposeRows));
+    if (d.mode != kDitherNone) return for_dither(d, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        if (p.fp32) hipLaunchKernelGGL((compose_kernel<float4v, M, DitherArgs>), grid, dim3(kComposeThreads), 0, s, p, d);
+        else hipLaunchKernelGGL((compose_kernel<half4, M, DitherArgs>), grid, dim3(kComposeThreads), 0, s, p, d);
+        return hipGetLastError();
+    });
     if (p.fp32) hipLaunchKernelGGL(compose_kernel<float4v>, grid, dim3(kComposeThreads), 0, s, p);
     else hipLaunchKernelGGL(compose_kernel<half4>, grid, dim3(kComposeThreads), 0, s, p);
     return hipGetLastError();
@@ -665,20 +703,22 @@ hipError_t launch_gather_yuv(const GatherYuvParams& p, hipStream_t s) {
     }
     return hipGetLastError();
 }
-template <int L, int S = kYuvLeft>
-static void launch_compose_yuv_as(const ComposeYuvParams& p, dim3 grid, hipStream_t s) {
-    if (p.c.fp32) hipLaunchKernelGGL((compose_yuv_kernel<float4v, L, S>), grid, dim3(kYuvThreads), 0, s, p);
-    else hipLaunchKernelGGL((compose_yuv_kernel<half4, L, S>), grid, dim3(kYuvThreads), 0, s, p);
+// the kernels of mode M with their extra arguments dz: none, or the DitherArgs
+template <int L, int S, int M, typename... D>
+static void launch_compose_yuv_as(const ComposeYuvParams& p, dim3 grid, hipStream_t s, const D&... dz) {
+    if (p.c.fp32) hipLaunchKernelGGL((compose_yuv_kernel<float4v, L, S, M, D...>), grid, dim3(kYuvThreads), 0, s, p, dz...);
+    else hipLaunchKernelGGL((compose_yuv_kernel<half4, L, S, M, D...>), grid, dim3(kYuvThreads), 0, s, p, dz...);
 }
-hipError_t launch_compose_yuv(const ComposeYuvParams& p, hipStream_t s) {
+template <int M, typename... D>
+static hipError_t launch_compose_yuv_mode(const ComposeYuvParams& p, hipStream_t s, const D&... dz) {
     if (p.c.outW <= 0 || p.c.outH <= 0) return hipSuccess;
     const int siting = yuv_effective_siting(p.dst.layout, p.dst.siting);
     if (siting < 0) return hipErrorInvalidValue;
     if (p.dst.layout == kYuvI444) {
         const int gw = (p.c.outW + 3) / 4;
         const dim3 grid((unsigned)((gw + kComposeThreads - 1) / kComposeThreads), (unsigned)((p.c.outH + kComposeRows - 1) / kComposeRows));
-        if (p.c.fp32) hipLaunchKernelGGL(compose_yuv444_kernel<float4v>, grid, dim3(kComposeThreads), 0, s, p);
-        else hipLaunchKernelGGL(compose_yuv444_kernel<half4>, grid, dim3(kComposeThreads), 0, s, p);
+        if (p.c.fp32) hipLaunchKernelGGL((compose_yuv444_kernel<float4v, M, D...>), grid, dim3(kComposeThreads), 0, s, p, dz...);
+        else hipLaunchKernelGGL((compose_yuv444_kernel<half4, M, D...>), grid, dim3(kComposeThreads), 0, s, p, dz...);
         return hipGetLastError();
     }
     const int cw = (p.c.outW + 1) / 2, ch = yuv_chroma_rows(p.c.outH, p.dst.layout);
@@ -689,28 +729,33 @@ hipError_t launch_compose_yuv(const ComposeYuvParams& p, hipStream_t s) {
         if (bands > 65535) return hipErrorInvalidValue;
         const dim3 bgrid(grid.x, (unsigned)bands);
         switch (p.dst.layout) {
-            case kYuvI420: launch_compose_yuv_as<kYuvI420, kYuvTopLeft>(p, bgrid, s); break;
-            case kYuvNV12: launch_compose_yuv_as<kYuvNV12, kYuvTopLeft>(p, bgrid, s); break;
+            case kYuvI420: launch_compose_yuv_as<kYuvI420, kYuvTopLeft, M>(p, bgrid, s, dz...); break;
+            case kYuvNV12: launch_compose_yuv_as<kYuvNV12, kYuvTopLeft, M>(p, bgrid, s, dz...); break;
             default: return hipErrorInvalidValue;
         }
         return hipGetLastError();
     }
     if (siting == kYuvCenter) {
         switch (p.dst.layout) {
-            case kYuvI420: launch_compose_yuv_as<kYuvI420, kYuvCenter>(p, grid, s); break;
-            case kYuvI422: launch_compose_yuv_as<kYuvI422, kYuvCenter>(p, grid, s); break;
-            case kYuvNV12: launch_compose_yuv_as<kYuvNV12, kYuvCenter>(p, grid, s); break;
+            case kYuvI420: launch_compose_yuv_as<kYuvI420, kYuvCenter, M>(p, grid, s, dz...); break;
+            case kYuvI422: launch_compose_yuv_as<kYuvI422, kYuvCenter, M>(p, grid, s, dz...); break;
+            case kYuvNV12: launch_compose_yuv_as<kYuvNV12, kYuvCenter, M>(p, grid, s, dz...); break;
             default: return hipErrorInvalidValue;
         }
         return hipGetLastError();
     }
     switch (p.dst.layout) {
-        case kYuvI420: launch_compose_yuv_as<kYuvI420>(p, grid, s); break;
-        case kYuvI422: launch_compose_yuv_as<kYuvI422>(p, grid, s); break;
-        case kYuvNV12: launch_compose_yuv_as<kYuvNV12>(p, grid, s); break;
+        case kYuvI420: launch_compose_yuv_as<kYuvI420, kYuvLeft, M>(p, grid, s, dz...); break;
+        case kYuvI422: launch_compose_yuv_as<kYuvI422, kYuvLeft, M>(p, grid, s, dz...); break;
+        case kYuvNV12: launch_compose_yuv_as<kYuvNV12, kYuvLeft, M>(p, grid, s, dz...); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();
+}
+hipError_t launch_compose_yuv(const ComposeYuvParams& p, hipStream_t s, const DitherArgs& d) {
+    if (!dither_args_ok(d)) return hipErrorInvalidValue;
+    if (d.mode == kDitherNone) return launch_compose_yuv_mode<kDitherNone>(p, s);
+    return for_dither(d, [&](auto m) { return launch_compose_yuv_mode<decltype(m)::value>(p, s, d); });
 }
 hipError_t launch_se(const SeParams& p, hipStream_t s) {
     const int threads = 1024, slices = threads / p.C > 0 ? threads / p.C : 1;

@@ -16,7 +16,12 @@
 namespace w2x {
 namespace {
 
-__global__ __launch_bounds__(kRsThreads) void resample_kernel(const ResampleParams p) {
+// M: kDitherNone - no further argument - is the kernel above; a dithered mode takes its DitherArgs behind p (dither_of).  Pixel X + q of row Y:
+// the channels r, g, b are the plane indices 0, 1, 2.
+template <int M = kDitherNone, typename... D>
+__global__ __launch_bounds__(kRsThreads) void resample_kernel(const ResampleParams p, const D... dzs) {
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    const DitherArgs& dz = dither_of(dzs...);
     extern __shared__ float h[];                                          // [3][rows_max][kRsCols]
     const int r0 = resample_pass1<3>(p, h);
     __syncthreads();
@@ -28,7 +33,10 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const ResamplePara
         d += (size_t)X * 3;
         unsigned px[4];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) px[q] = quant(a[2][q], 255.f, 255) | quant(a[1][q], 255.f, 255) << 8 | quant(a[0][q], 255.f, 255) << 16;   // b | g << 8 | r << 16
+        for (int q = 0; q < 4; ++q) {
+            if constexpr (M == kDitherNone) px[q] = quant(a[2][q], 255.f, 255) | quant(a[1][q], 255.f, 255) << 8 | quant(a[0][q], 255.f, 255) << 16;   // b | g << 8 | r << 16
+            else px[q] = quantize_bgr_at<M>(a[0][q], a[1][q], a[2][q], dz, X + q, Y);
+        }
         if (np == 4 && (((size_t)d) & 3) == 0) {
             unsigned* dw = (unsigned*)d;
             dw[0] = px[0] | px[1] << 24;
@@ -41,7 +49,13 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const ResamplePara
         uint16_t* d16 = (uint16_t*)d + (size_t)X * 3;
         unsigned v[12];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) { v[3 * q] = quant(a[2][q], 65535.f, 65535); v[3 * q + 1] = quant(a[1][q], 65535.f, 65535); v[3 * q + 2] = quant(a[0][q], 65535.f, 65535); }
+        for (int q = 0; q < 4; ++q) {
+            if constexpr (M == kDitherNone) { v[3 * q] = quant(a[2][q], 65535.f, 65535); v[3 * q + 1] = quant(a[1][q], 65535.f, 65535); v[3 * q + 2] = quant(a[0][q], 65535.f, 65535); }
+            else {
+#pragma unroll
+                for (int e = 0; e < 3; ++e) v[3 * q + e] = quant_code<M>(a[2 - e][q] * 65535.f, 65535, dz, 2 - e, X + q, Y);
+            }
+        }
         if (np == 4 && (((size_t)d16) & 3) == 0) {
             unsigned* dw = (unsigned*)d16;
 #pragma unroll
@@ -65,10 +79,15 @@ int resample_rows_max(const int* fy, int outH, int inH, int ky, int rows_above) 
     return m;
 }
 
-hipError_t launch_resample(const ResampleParams& p, hipStream_t s) {
+hipError_t launch_resample(const ResampleParams& p, hipStream_t s, const DitherArgs& d) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
+    if (!dither_args_ok(d)) return hipErrorInvalidValue;
+    if (d.mode != kDitherNone) return for_dither(d, [&](auto m) {
+        static unsigned lds_dither = 0;
+        return launch_resample_tiles(resample_kernel<decltype(m)::value, DitherArgs>, 3 * kRsCols, p.rows_max, lds_dither, p.outW, p.outH, s, p, d);
+    });
     static unsigned lds_done = 0;
-    return launch_resample_tiles(resample_kernel, 3 * kRsCols, p.rows_max, lds_done, p.outW, p.outH, s, p);
+    return launch_resample_tiles(resample_kernel<>, 3 * kRsCols, p.rows_max, lds_done, p.outW, p.outH, s, p);
 }
 
 }  // namespace w2x

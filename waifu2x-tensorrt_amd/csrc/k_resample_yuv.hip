@@ -24,6 +24,13 @@ namespace {
 // stated by __fmaf_rn; an operation that must not fuse with its neighbour needs contraction switched off around it, as in luma_even_row - the one place where a
 // product feeds a sum that is not meant to be an fma.  Everywhere else a product feeds an __fmaf_rn or a sum feeds a product, which nothing can contract.
 __device__ __forceinline__ unsigned yuv_code(float off, float scale, float v, int maxcode) { return (unsigned)min(max(__float2int_rn(__fmaf_rn(scale, v, off)), 0), maxcode); }
+// M: the code of sample (x, y) of plane c (Y, U, V = 0, 1, 2; chroma samples in their own plane's coordinates, NV12's as the I420 samples they are).
+// kDitherNone is yuv_code; a dithered mode adds the sample's threshold to the same fused value and rounds down (dither_code, prepost_device.h).
+template <int M>
+__device__ __forceinline__ unsigned yuv_code_at(float off, float scale, float v, int maxcode, const DitherArgs& dz, int c, int x, int y) {
+    if constexpr (M == kDitherNone) return yuv_code(off, scale, v, maxcode);
+    else return dither_code<M>(__fmaf_rn(scale, v, off), dither_t<M>(dz, c, x, y), maxcode);
+}
 __device__ __forceinline__ float luma_fused(const YuvCoefs& k, float r, float g, float b) { return __fmaf_rn(k.kb, b, __fmaf_rn(k.kr, r, __fmul_rn(k.kg, g))); }
 __device__ __forceinline__ float luma_even_row(const YuvCoefs& k, float r, float g, float b) {
 #pragma clang fp contract(off)   // (__fadd_rn / __fmul_rn are `+` and `*` to the compiler, which fuses them where it may: only this keeps kb * b a product of its own)
@@ -54,7 +61,10 @@ __device__ __forceinline__ void store_codes4(uint8_t* row, int X, int np, const 
 }
 
 // ---- 4:4:4.  LDS [3][rows_max][kRsCols] fp32: resample_kernel's, 58.5 KiB at a factor of 4 with bicubic taps, two workgroups per CU
-__global__ __launch_bounds__(kRsThreads) void resample_yuv444_kernel(const ResampleYuvParams p) {
+template <int M = kDitherNone, typename... D>
+__global__ __launch_bounds__(kRsThreads) void resample_yuv444_kernel(const ResampleYuvParams p, const D... dzs) {
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    const DitherArgs& dz = dither_of(dzs...);
     extern __shared__ float h[];
     const int r0 = resample_pass1<3>(p, h);
     __syncthreads();
@@ -67,9 +77,9 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv444_kernel(const Resam
     for (int q = 0; q < 4; ++q) {
         const float o0 = sat01(a[0][q]), o1 = sat01(a[1][q]), o2 = sat01(a[2][q]);
         const float Yn = luma_of_row(k, Y, o0, o1, o2);
-        yc[q] = yuv_code(k.y_off, k.y_scale, Yn, k.maxcode);
-        uc[q] = yuv_code(k.c_off, k.c_scale, chroma_of(o2, Yn, k.cb_div), k.maxcode);
-        vc[q] = yuv_code(k.c_off, k.c_scale, chroma_of(o0, Yn, k.cr_div), k.maxcode);
+        yc[q] = yuv_code_at<M>(k.y_off, k.y_scale, Yn, k.maxcode, dz, 0, X + q, Y);
+        uc[q] = yuv_code_at<M>(k.c_off, k.c_scale, chroma_of(o2, Yn, k.cb_div), k.maxcode, dz, 1, X + q, Y);
+        vc[q] = yuv_code_at<M>(k.c_off, k.c_scale, chroma_of(o0, Yn, k.cr_div), k.maxcode, dz, 2, X + q, Y);
     }
     const bool wide = p.dst.bits > 8;
     store_codes4(p.dst.p[0] + (size_t)Y * p.dst.step[0], X, np, yc, wide);
@@ -88,8 +98,10 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv444_kernel(const Resam
 // At a factor of 4 with bicubic taps rows_max <= 78: 3 * 78 * 65 * 4 B = 59.4 KiB, two workgroups per CU.
 // S: kYuvLeft is the above (resample_yuv422_kernel).  kYuvCenter: site j is the mean of columns 2j and 2j + 1 - pass 1 filters no halo column and
 // nothing crosses lanes before the stores.  (I422 has no row rule: kYuvTopLeft is kYuvLeft.)
-template <int S>
-__global__ __launch_bounds__(kRsThreads) void resample_yuv422_kernel(const ResampleYuvParams p) {
+template <int S, int M = kDitherNone, typename... D>
+__global__ __launch_bounds__(kRsThreads) void resample_yuv422_kernel(const ResampleYuvParams p, const D... dzs) {
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    const DitherArgs& dz = dither_of(dzs...);
     constexpr bool kLeftCol = S != kYuvCenter;
     extern __shared__ __attribute__((aligned(16))) float h422[];   // (the alignment stated: pass 2 reads 16 bytes per lane and plane, ds_read_b128)
     float* const h = h422;
@@ -130,7 +142,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv422_kernel(const Resam
         for (int e = 0; e < 3; ++e) o[q][e] = sat01(a[e][q]);
     unsigned yc[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) yc[q] = yuv_code(k.y_off, k.y_scale, luma_of_row(k, Y, o[q][0], o[q][1], o[q][2]), k.maxcode);
+    for (int q = 0; q < 4; ++q) yc[q] = yuv_code_at<M>(k.y_off, k.y_scale, luma_of_row(k, Y, o[q][0], o[q][1], o[q][2]), k.maxcode, dz, 0, X + q, Y);
     unsigned uc[2], vc[2];
 #pragma unroll
     for (int s = 0; s < 2; ++s) {
@@ -148,8 +160,8 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv422_kernel(const Resam
             f[e] = kLeftCol ? site_filter(left, o[2 * s][e], right) : site_mean(o[2 * s][e], right);
         }
         const float Yn = luma_fused(k, f[0], f[1], f[2]);
-        uc[s] = yuv_code(k.c_off, k.c_scale, chroma_of(f[2], Yn, k.cb_div), k.maxcode);
-        vc[s] = yuv_code(k.c_off, k.c_scale, chroma_of(f[0], Yn, k.cr_div), k.maxcode);
+        uc[s] = yuv_code_at<M>(k.c_off, k.c_scale, chroma_of(f[2], Yn, k.cb_div), k.maxcode, dz, 1, (X >> 1) + s, Y);   // (site (X / 2 + s, Y) of the chroma plane)
+        vc[s] = yuv_code_at<M>(k.c_off, k.c_scale, chroma_of(f[0], Yn, k.cr_div), k.maxcode, dz, 2, (X >> 1) + s, Y);
     }
     // chroma stores: the two sites of an odd lane go out through the even lane on its left where the pair's eight pixels are whole and its rows are aligned
     const unsigned uu = uc[0] | uc[1] << 16, vv = vc[0] | vc[1] << 16;
@@ -205,8 +217,8 @@ typedef float float2v __attribute__((ext_vector_type(2)));
 // columns itself (row -1 clamps to row 0), lanes 0 .. 4 of a wave the halo column of its five luma rows.  That is 3 vertical filters per thread where kYuvLeft
 // has 2; the horizontal pass, the kernel's larger part at 17 taps, grows by one output row's reach in 16.
 // LDS at a factor of 4 with bicubic taps: rows_max <= 82 (16 * 4 + 1 + 17), 3 * 82 * 66 * 4 B = 63.4 KiB - two workgroups per CU still fit the CU's 160 KiB.
-template <bool kNV12, int S = kYuvLeft>
-__device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, float* h) {   // h: [3][rows_max][kYP], columns 0 .. 63 the tile's, 64 the halo
+template <bool kNV12, int S = kYuvLeft, int M = kDitherNone>
+__device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, float* h, const DitherArgs& dz) {   // h: [3][rows_max][kYP], columns 0 .. 63 the tile's, 64 the halo
     constexpr bool kLeftCol = S != kYuvCenter, kAbove = S == kYuvTopLeft;
     const int ox0 = blockIdx.x * kRsCols, oy0 = blockIdx.y * kRsRows;
     const int rm = p.rows_max;
@@ -255,8 +267,8 @@ __device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, floa
         }
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
-            ya[q] = yuv_code(k.y_off, k.y_scale, luma_even_row(k, oa[q][0], oa[q][1], oa[q][2]), k.maxcode);
-            yb[q] = yuv_code(k.y_off, k.y_scale, luma_fused(k, ob[q][0], ob[q][1], ob[q][2]), k.maxcode);
+            ya[q] = yuv_code_at<M>(k.y_off, k.y_scale, luma_even_row(k, oa[q][0], oa[q][1], oa[q][2]), k.maxcode, dz, 0, X0 + q, Ya);
+            yb[q] = yuv_code_at<M>(k.y_off, k.y_scale, luma_fused(k, ob[q][0], ob[q][1], ob[q][2]), k.maxcode, dz, 0, X0 + q, Ya + 1);
         }
 #pragma unroll
         for (int e = 0; e < 3; ++e) {
@@ -294,8 +306,13 @@ __device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, floa
 #pragma unroll
         for (int e = 0; e < 3; ++e) f[e] = kLeftCol ? site_filter(left[e], vl[e], vr[e]) : site_mean(vl[e], vr[e]);
         const float Y = luma_fused(k, f[0], f[1], f[2]);
-        uc = yuv_code(k.c_off, k.c_scale, chroma_of(f[2], Y, k.cb_div), k.maxcode) << up;
-        vc = yuv_code(k.c_off, k.c_scale, chroma_of(f[0], Y, k.cr_div), k.maxcode) << up;
+        if constexpr (M == kDitherNone) {
+            uc = yuv_code(k.c_off, k.c_scale, chroma_of(f[2], Y, k.cb_div), k.maxcode) << up;
+            vc = yuv_code(k.c_off, k.c_scale, chroma_of(f[0], Y, k.cr_div), k.maxcode) << up;
+        } else {                                                           // site (j, i) of the chroma plane, NV12 too
+            uc = yuv_code_at<M>(k.c_off, k.c_scale, chroma_of(f[2], Y, k.cb_div), k.maxcode, dz, 1, X0 >> 1, Ya >> 1) << up;
+            vc = yuv_code_at<M>(k.c_off, k.c_scale, chroma_of(f[0], Y, k.cr_div), k.maxcode, dz, 2, X0 >> 1, Ya >> 1) << up;
+        }
     }
     // stores: the run of four sites the lane belongs to goes out through its first lane where the run is whole and its rows are aligned
     const int sh = wide ? 1 : 0;                                           // log2 bytes per sample
@@ -345,26 +362,33 @@ __device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, floa
     }
 }
 
-__global__ __launch_bounds__(kRsThreads) void resample_yuv_kernel(const ResampleYuvParams p) {
+// M: kDitherNone - no further argument - is the kernel the undithered engine launches; a dithered mode takes its DitherArgs behind p (dither_of)
+template <int M = kDitherNone, typename... D>
+__global__ __launch_bounds__(kRsThreads) void resample_yuv_kernel(const ResampleYuvParams p, const D... dzs) {
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
     extern __shared__ float h[];
-    resample_yuv420<false>(p, h);
+    resample_yuv420<false, kYuvLeft, M>(p, h, dither_of(dzs...));
 }
-__global__ __launch_bounds__(kRsThreads) void resample_yuv_nv12_kernel(const ResampleYuvParams p) {
+template <int M = kDitherNone, typename... D>
+__global__ __launch_bounds__(kRsThreads) void resample_yuv_nv12_kernel(const ResampleYuvParams p, const D... dzs) {
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
     extern __shared__ float h[];
-    resample_yuv420<true>(p, h);
+    resample_yuv420<true, kYuvLeft, M>(p, h, dither_of(dzs...));
 }
 // the other sitings of the pair
-template <bool kNV12, int S>
-__global__ __launch_bounds__(kRsThreads) void resample_yuv_sited_kernel(const ResampleYuvParams p) {
+template <bool kNV12, int S, int M = kDitherNone, typename... D>
+__global__ __launch_bounds__(kRsThreads) void resample_yuv_sited_kernel(const ResampleYuvParams p, const D... dzs) {
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
     extern __shared__ float h[];
-    resample_yuv420<kNV12, S>(p, h);
+    resample_yuv420<kNV12, S, M>(p, h, dither_of(dzs...));
 }
 
 }  // namespace
 
 // dst.layout picks the kernel.  The layouts beside I420 also ask for a canvas and for every plane of the layout, with a step that holds its row and 10-bit
 // planes at even addresses.
-hipError_t launch_resample_yuv(const ResampleYuvParams& params, int rows_max_above, hipStream_t s) {
+hipError_t launch_resample_yuv(const ResampleYuvParams& params, int rows_max_above, hipStream_t s, const DitherArgs& d) {
+    if (!dither_args_ok(d)) return hipErrorInvalidValue;
     ResampleYuvParams p = params;
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
     if (p.dst.rows != p.outH || p.dst.cols != p.outW || (p.dst.bits != 8 && p.dst.bits != 10)) return hipErrorInvalidValue;
@@ -381,29 +405,35 @@ hipError_t launch_resample_yuv(const ResampleYuvParams& params, int rows_max_abo
     // the siting the layout tells apart: I444 none, I422 the column rule alone
     if (p.dst.siting < kYuvLeft || p.dst.siting > kYuvTopLeft) return hipErrorInvalidValue;
     const int siting = layout == kYuvI444 || (layout == kYuvI422 && p.dst.siting == kYuvTopLeft) ? kYuvLeft : p.dst.siting;
-    if (siting != kYuvLeft) {
-        static unsigned done_c = 0, done_cn = 0, done_c422 = 0, done_t = 0, done_tn = 0;
-        const bool tl = siting == kYuvTopLeft;
-        if (tl) {                                                          // pass 1 starts at the output row above the tile: the LDS holds those input rows too
-            if (rows_max_above < p.rows_max) return hipErrorInvalidValue;
-            p.rows_max = rows_max_above;
+    // the kernels of mode M with their extra arguments dz (none, or the DitherArgs); the LDS opt-in masks are per instantiation of this body
+    auto go = [&](auto m, const auto&... dz) -> hipError_t {
+        constexpr int M = decltype(m)::value;
+        if (siting != kYuvLeft) {
+            static unsigned done_c = 0, done_cn = 0, done_c422 = 0, done_t = 0, done_tn = 0;
+            const bool tl = siting == kYuvTopLeft;
+            switch (layout) {
+                case kYuvI420: return tl ? launch_resample_tiles(resample_yuv_sited_kernel<false, kYuvTopLeft, M, std::decay_t<decltype(dz)>...>, 3 * kYP, p.rows_max, done_t, p.outW, p.outH, s, p, dz...)
+                                         : launch_resample_tiles(resample_yuv_sited_kernel<false, kYuvCenter, M, std::decay_t<decltype(dz)>...>, 3 * kYP, p.rows_max, done_c, p.outW, p.outH, s, p, dz...);
+                case kYuvNV12: return tl ? launch_resample_tiles(resample_yuv_sited_kernel<true, kYuvTopLeft, M, std::decay_t<decltype(dz)>...>, 3 * kYP, p.rows_max, done_tn, p.outW, p.outH, s, p, dz...)
+                                         : launch_resample_tiles(resample_yuv_sited_kernel<true, kYuvCenter, M, std::decay_t<decltype(dz)>...>, 3 * kYP, p.rows_max, done_cn, p.outW, p.outH, s, p, dz...);
+                case kYuvI422: return launch_resample_tiles(resample_yuv422_kernel<kYuvCenter, M, std::decay_t<decltype(dz)>...>, 3 * (kRsCols + 1), p.rows_max, done_c422, p.outW, p.outH, s, p, dz...);
+                default: return hipErrorInvalidValue;
+            }
         }
-        switch (layout) {
-            case kYuvI420: return tl ? launch_resample_tiles(resample_yuv_sited_kernel<false, kYuvTopLeft>, 3 * kYP, p.rows_max, done_t, p.outW, p.outH, s, p)
-                                     : launch_resample_tiles(resample_yuv_sited_kernel<false, kYuvCenter>, 3 * kYP, p.rows_max, done_c, p.outW, p.outH, s, p);
-            case kYuvNV12: return tl ? launch_resample_tiles(resample_yuv_sited_kernel<true, kYuvTopLeft>, 3 * kYP, p.rows_max, done_tn, p.outW, p.outH, s, p)
-                                     : launch_resample_tiles(resample_yuv_sited_kernel<true, kYuvCenter>, 3 * kYP, p.rows_max, done_cn, p.outW, p.outH, s, p);
-            case kYuvI422: return launch_resample_tiles(resample_yuv422_kernel<kYuvCenter>, 3 * (kRsCols + 1), p.rows_max, done_c422, p.outW, p.outH, s, p);
-            default: return hipErrorInvalidValue;
+        static unsigned done420 = 0, done422 = 0, done444 = 0, done_nv12 = 0;
+        switch (layout) {                                                  // LDS dwords per input row: three planes of the kernel's pitch
+            case kYuvI420: return launch_resample_tiles(resample_yuv_kernel<M, std::decay_t<decltype(dz)>...>, 3 * kYP, p.rows_max, done420, p.outW, p.outH, s, p, dz...);
+            case kYuvI422: return launch_resample_tiles(resample_yuv422_kernel<kYuvLeft, M, std::decay_t<decltype(dz)>...>, 3 * (kRsCols + 1), p.rows_max, done422, p.outW, p.outH, s, p, dz...);
+            case kYuvI444: return launch_resample_tiles(resample_yuv444_kernel<M, std::decay_t<decltype(dz)>...>, 3 * kRsCols, p.rows_max, done444, p.outW, p.outH, s, p, dz...);
+            default: return launch_resample_tiles(resample_yuv_nv12_kernel<M, std::decay_t<decltype(dz)>...>, 3 * kYP, p.rows_max, done_nv12, p.outW, p.outH, s, p, dz...);
         }
+    };
+    if (siting == kYuvTopLeft) {                                           // pass 1 starts at the output row above the tile: the LDS holds those input rows too
+        if (rows_max_above < p.rows_max) return hipErrorInvalidValue;
+        p.rows_max = rows_max_above;
     }
-    static unsigned done420 = 0, done422 = 0, done444 = 0, done_nv12 = 0;
-    switch (layout) {                                                      // LDS dwords per input row: three planes of the kernel's pitch
-        case kYuvI420: return launch_resample_tiles(resample_yuv_kernel, 3 * kYP, p.rows_max, done420, p.outW, p.outH, s, p);
-        case kYuvI422: return launch_resample_tiles(resample_yuv422_kernel<kYuvLeft>, 3 * (kRsCols + 1), p.rows_max, done422, p.outW, p.outH, s, p);
-        case kYuvI444: return launch_resample_tiles(resample_yuv444_kernel, 3 * kRsCols, p.rows_max, done444, p.outW, p.outH, s, p);
-        default: return launch_resample_tiles(resample_yuv_nv12_kernel, 3 * kYP, p.rows_max, done_nv12, p.outW, p.outH, s, p);
-    }
+    if (d.mode == kDitherNone) return go(std::integral_constant<int, kDitherNone>());
+    return for_dither(d, [&](auto m) { return go(m, d); });
 }
 
 }  // namespace w2x

@@ -130,15 +130,19 @@ __global__ __launch_bounds__(kGatherThreads) void gather_rgba_kernel(const Gathe
 }
 
 // A thread per pixel along a row (a wave stores 256 contiguous bytes), a workgroup row per output row.
-template <typename P>
-__global__ __launch_bounds__(256) void compose_rgba_kernel(const ComposeRgbaParams p) {
+// M: kDitherNone - no further argument - is the kernel above; a dithered mode takes its DitherArgs behind p (dither_of).  The colour channels alone
+// are dithered; alpha keeps sat(rint(x * 255)) - an opaque cut-out stays 255 everywhere.
+template <typename P, int M = kDitherNone, typename... D>
+__global__ __launch_bounds__(256) void compose_rgba_kernel(const ComposeRgbaParams p, const D... dzs) {
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    const DitherArgs& dz = dither_of(dzs...);
     const ComposeParams& c = p.c;
     const int X = blockIdx.x * 256 + threadIdx.x;
     if (X >= c.outW) return;
     for (int Y = blockIdx.y; Y < c.outH; Y += gridDim.y) {
         float r, g, b;
         compose_pixel_sums<P>(c, (const P*)c.tiles, X, Y, r, g, b);
-        const unsigned bgr = quantize_bgr(r, g, b);
+        const unsigned bgr = quantize_bgr_at<M>(r, g, b, dz, X, Y);
         unsigned A = p.alpha_value;
         if (p.alpha_tiles) {
             compose_pixel_sums<P>(c, (const P*)p.alpha_tiles, X, Y, r, g, b);
@@ -181,8 +185,11 @@ __global__ __launch_bounds__(256) void compose_canvas_rgba_kernel(const ComposeC
 // bank is the dword's column: the group touches every bank once.
 // Stores: the thread's four BGRA dwords as one 16-byte store where the address is 16-byte aligned (dst is packed: the pitch outW * 4 is a multiple of 16
 // only when outW % 4 == 0, so this is decided per row from the address), dword by dword otherwise and for the 1 - 3 pixels the right edge leaves.
-template <bool kAlpha>
-__global__ __launch_bounds__(kRsThreads) void resample_rgba_kernel(const ResampleRgbaParams p) {
+// M: as above - colour dithered at (X + q, Y), alpha rounded to nearest.
+template <bool kAlpha, int M = kDitherNone, typename... D>
+__global__ __launch_bounds__(kRsThreads) void resample_rgba_kernel(const ResampleRgbaParams p, const D... dzs) {
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    const DitherArgs& dz = dither_of(dzs...);
     constexpr int NP = kAlpha ? 4 : 3;
     extern __shared__ float rs_lds[];
     const int r0 = resample_pass1<NP>(p, rs_lds);
@@ -192,8 +199,12 @@ __global__ __launch_bounds__(kRsThreads) void resample_rgba_kernel(const Resampl
     if (!resample_pass2<NP>(p, rs_lds, r0, a, X, Y, np)) return;
     unsigned px[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q)                                           // b | g << 8 | r << 16 | a << 24
-        px[q] = quant(a[2][q], 255.f, 255) | quant(a[1][q], 255.f, 255) << 8 | quant(a[0][q], 255.f, 255) << 16 | (kAlpha ? quant(a[NP - 1][q], 255.f, 255) : p.alpha_value) << 24;
+    for (int q = 0; q < 4; ++q) {                                         // b | g << 8 | r << 16 | a << 24
+        if constexpr (M == kDitherNone)
+            px[q] = quant(a[2][q], 255.f, 255) | quant(a[1][q], 255.f, 255) << 8 | quant(a[0][q], 255.f, 255) << 16 | (kAlpha ? quant(a[NP - 1][q], 255.f, 255) : p.alpha_value) << 24;
+        else
+            px[q] = quantize_bgr_at<M>(a[0][q], a[1][q], a[2][q], dz, X + q, Y) | (kAlpha ? quant(a[NP - 1][q], 255.f, 255) : p.alpha_value) << 24;
+    }
     unsigned* d = (unsigned*)(p.dst + (size_t)Y * p.dst_step) + X;
     if (np == 4 && (((size_t)d) & 15) == 0) *(uint4*)d = make_uint4(px[0], px[1], px[2], px[3]);
     else for (int q = 0; q < np; ++q) d[q] = px[q];
@@ -215,9 +226,16 @@ hipError_t launch_gather_rgba(const GatherRgbaParams& p, hipStream_t s) {
     else hipLaunchKernelGGL(gather_rgba_kernel<half4>, grid, dim3(kGatherThreads), 0, s, p);
     return hipGetLastError();
 }
-hipError_t launch_compose_rgba(const ComposeRgbaParams& p, hipStream_t s) {
+hipError_t launch_compose_rgba(const ComposeRgbaParams& p, hipStream_t s, const DitherArgs& d) {
     if (p.c.outW <= 0 || p.c.outH <= 0) return hipSuccess;
+    if (!dither_args_ok(d)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((p.c.outW + 255) / 256), (unsigned)(p.c.outH < 65535 ? p.c.outH : 65535));
+    if (d.mode != kDitherNone) return for_dither(d, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        if (p.c.fp32) hipLaunchKernelGGL((compose_rgba_kernel<float4v, M, DitherArgs>), grid, dim3(256), 0, s, p, d);
+        else hipLaunchKernelGGL((compose_rgba_kernel<half4, M, DitherArgs>), grid, dim3(256), 0, s, p, d);
+        return hipGetLastError();
+    });
     if (p.c.fp32) hipLaunchKernelGGL(compose_rgba_kernel<float4v>, grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL(compose_rgba_kernel<half4>, grid, dim3(256), 0, s, p);
     return hipGetLastError();
@@ -230,9 +248,15 @@ hipError_t launch_compose_canvas_rgba(const ComposeCanvasRgbaParams& p, hipStrea
     else hipLaunchKernelGGL(compose_canvas_rgba_kernel<half4>, grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }
-hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s) {
+hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s, const DitherArgs& d) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
-    if ((p.dst_step & 3) || p.dst_step < (size_t)p.outW * 4 || (((size_t)p.dst) & 3)) return hipErrorInvalidValue;
+    if ((p.dst_step & 3) || p.dst_step < (size_t)p.outW * 4 || (((size_t)p.dst) & 3) || !dither_args_ok(d)) return hipErrorInvalidValue;
+    if (d.mode != kDitherNone) return for_dither(d, [&](auto m) {
+        constexpr int M = decltype(m)::value;
+        static unsigned lds_dither[2] = {0, 0};
+        if (p.uniform) return launch_resample_tiles(resample_rgba_kernel<false, M, DitherArgs>, 3 * kRsCols, p.rows_max, lds_dither[0], p.outW, p.outH, s, p, d);
+        return launch_resample_tiles(resample_rgba_kernel<true, M, DitherArgs>, 4 * kRsCols, p.rows_max, lds_dither[1], p.outW, p.outH, s, p, d);
+    });
     static unsigned lds_done[2] = {0, 0};
     if (p.uniform) return launch_resample_tiles(resample_rgba_kernel<false>, 3 * kRsCols, p.rows_max, lds_done[0], p.outW, p.outH, s, p);
     return launch_resample_tiles(resample_rgba_kernel<true>, 4 * kRsCols, p.rows_max, lds_done[1], p.outW, p.outH, s, p);

@@ -4,6 +4,7 @@
 
 #include "support.h"
 #include "switches.h"
+#include "dither.h"
 #include <cstdint>
 
 namespace w2x {
@@ -252,10 +253,32 @@ hipError_t launch_swinattn32(const SwinAttn32Params& p, hipStream_t s);
 hipError_t launch_mlp(const MlpParams& p, hipStream_t s);
 hipError_t launch_swin_attn(const SwinAttnParams& p, hipStream_t s);
 // swin_attn_supported / mlp_supported / mlp32_supported / swinattn32_supported / gemm_row_stats_supported / attn_supported: support.h
+// Dithered output (dither.h states the rule): what a dithered launch gets beside its parameters.  dx / dy: the pattern's offset per plane index c
+// (R, G, B / Y, U, V = 0, 1, 2; gray = 1), already reduced mod 64; table: the device's copy of the 64 x 64 blue-noise ranks (dither_table_device(), BlueNoise
+// only).  Every launcher below takes one as its last argument; mode None - the default - launches the kernel of the undithered engine, whose argument list and
+// instructions do not know about any of this; a mode it has no kernel for is hipErrorInvalidValue.
+struct DitherArgs {
+    int mode = kDitherNone;
+    int dx[3] = {0, 0, 0}, dy[3] = {0, 0, 0};
+    const uint16_t* table = nullptr;
+};
+inline DitherArgs dither_args(int mode, unsigned phase, const uint16_t* table) {
+    DitherArgs d;
+    d.mode = mode; d.table = table;
+    for (int c = 0; c < 3; ++c) { d.dx[c] = (int)dither_dx(phase, c); d.dy[c] = (int)dither_dy(phase, c); }
+    return d;
+}
+inline bool dither_args_ok(const DitherArgs& d) { return dither_mode_ok(d.mode) && (d.mode != kDitherBlueNoise || d.table); }
+// k_dither.hip: the blue-noise table in the current device's memory (part of the code object: nothing is uploaded); nullptr and *err on failure
+const uint16_t* dither_table_device(hipError_t* err = nullptr);
+// k_dither.hip dither_planes_kernel (test hook, Img2Img::ditherPlanes): n planes of rows x cols fp32 values (src, steps in bytes) quantised into the planes of
+// dst (8 .. 16 bits) by the store of the compose / resample kernels (store4): V = v * (2^bits - 1), plane k with plane index k (one plane: 1)
+struct PlanarPlanes;
+hipError_t launch_dither_planes(const PlanarPlanes& src, const PlanarPlanes& dst, const DitherArgs& d, hipStream_t s);
 hipError_t launch_se(const SeParams& p, hipStream_t s);
 hipError_t launch_scale(void* x, const float* scale, int B, int HW, int Cs, bool fp32, hipStream_t s);
 hipError_t launch_gather(const GatherParams& p, hipStream_t s);
-hipError_t launch_compose(const ComposeParams& p, hipStream_t s);
+hipError_t launch_compose(const ComposeParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
 // k_prepost.hip compose_canvas_kernel: compose_kernel's per-pixel sums for the same rect of p (x0..x1, y0..y1; p.dst / p.deep unused) left
 // unquantised as fp32 RGB planes: canvas[c][Y][X], plane stride outW * outH (the input of the resize, renderResized)
 hipError_t launch_compose_canvas(const ComposeParams& p, float* canvas, hipStream_t s);
@@ -282,7 +305,7 @@ constexpr int kResampleRows = 16, kResampleCols = 64;
 constexpr int kComposeRows = W2X_COMPOSE_ROWS, kComposeThreads = W2X_COMPOSE_THREADS;
 // host: the largest input row span of an output row tile; rows_above = 1: of the tile and the output row above it (top-left sited 4:2:0 chroma)
 int resample_rows_max(const int* fy, int outH, int inH, int ky, int rows_above = 0);
-hipError_t launch_resample(const ResampleParams& p, hipStream_t s);
+hipError_t launch_resample(const ResampleParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
 // YUV 4:2:0 frames (Img2Img::renderYuv): three planes - Y of rows x cols, U and V of ceil(rows/2) x ceil(cols/2) - with 8-bit (uint8) or 10-bit
 // (uint16, low 10 bits) samples; steps in bytes.  Chroma siting (siting): kYuvLeft, MPEG-2 "left", chroma (i, j) at luma (x = 2j, y = 2i + 1/2);
 // kYuvCenter (JPEG, MPEG-1) at (2j + 1/2, 2i + 1/2); kYuvTopLeft (BT.2020) at (2j, 2i).  Per subsampled axis a siting is one of two rules, co-sited or centred:
@@ -356,7 +379,7 @@ constexpr int kYuvBand = W2X_YUV_BAND;   // (a build switch like W2X_COMPOSE_ROW
 // dst.layout picks the kernel: I420 and NV12 compose_yuv_kernel (NV12: U and V stored interleaved, P010 codes << 6), I422 the same kernel
 // without the vertical pair (a thread owns four sites of ONE luma row), I444 compose_yuv444_kernel (compose_kernel's shape: four pixels of a row per
 // thread, its four-pixel fast path, no chroma filter)
-hipError_t launch_compose_yuv(const ComposeYuvParams& p, hipStream_t s);
+hipError_t launch_compose_yuv(const ComposeYuvParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
 // RGBA frames (renderRgba; k_rgba.hip).
 // alpha_bleed_kernel: the uploaded BGRA frame split into the BGR frame gather reads and the alpha plane, with the colour of every pixel of alpha > 0
 // spread `radius` pixels (0..16) outward under the pixels of alpha == 0 (tiles.h alpha_bleed states the arithmetic), all iterations in one launch.
@@ -390,7 +413,7 @@ struct ComposeRgbaParams {
     const void* alpha_tiles = nullptr;
     unsigned alpha_value = 255;
 };
-hipError_t launch_compose_rgba(const ComposeRgbaParams& p, hipStream_t s);
+hipError_t launch_compose_rgba(const ComposeRgbaParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
 // Resized RGBA frames (renderRgbaResized; k_rgba.hip).
 // compose_canvas_rgba_kernel: compose_canvas_kernel over both tile sets of an RGBA frame - the colour tiles' sums as the fp32 planes R, G, B (what
 // compose_canvas_kernel writes for the colour frame) and the green sum of the alpha tiles as a fourth plane A (what it writes into plane 1 for the gray
@@ -413,7 +436,7 @@ struct ResampleRgbaParams {
     int rows_max = 0;
     int uniform = 0; unsigned alpha_value = 255;
 };
-hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s);
+hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
 // Frames of planes (k_planar.hip): `n` planes of rows x cols samples - uint8 (bits 8), little-endian uint16 with the code in the low bits (10 / 12 / 16) or
 // float32 of nominal [0, 1] (32) - each with its own pointer and step in bytes; u16 / f32 samples aligned to their size.  n = 3: planar RGB frames (renderPlanar,
 // DESIGN 9h), planes R, G, B.  n = 1: gray frames (renderGray) of 8 or 16 bits: one sample per pixel on both sides, the result the green channel of
@@ -441,7 +464,7 @@ struct ComposePlanarParams {
     ComposeParams c;
     PlanarPlanes dst;
 };
-hipError_t launch_compose_planar(const ComposePlanarParams& p, hipStream_t s);
+hipError_t launch_compose_planar(const ComposePlanarParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
 // compose_canvas_gray_kernel: the green sums of compose_pixel_sums over the whole canvas of p (x0..y1, dst, deep unused) unquantised as one fp32 plane
 // canvas[Y][X] of outH x outW: the canvas of a resized gray frame (a resized planar frame has compose_canvas_kernel's)
 hipError_t launch_compose_canvas_gray(const ComposeParams& p, float* canvas, hipStream_t s);
@@ -455,7 +478,7 @@ struct ResamplePlanarParams {
     int rows_max = 0;
     PlanarPlanes dst;
 };
-hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s);
+hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
 // Planar RGBA frames (renderPlanarRgba; k_planar_rgba.hip): four planes R, G, B, A of one sample type, laid out like PlanarPlanes' three.
 struct RgbaPlanes {
     uint8_t* p[4] = {nullptr, nullptr, nullptr, nullptr}; size_t step[4] = {0, 0, 0, 0};
@@ -494,7 +517,7 @@ struct ComposePlanarRgbaParams {
     float alpha_value = 1.f;
     RgbaPlanes dst;
 };
-hipError_t launch_compose_planar_rgba(const ComposePlanarRgbaParams& p, hipStream_t s);
+hipError_t launch_compose_planar_rgba(const ComposePlanarRgbaParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
 // resample_planes_rgba_kernel: resample_planes_kernel over the four planes of compose_canvas_rgba_kernel's canvas; uniform != 0: the canvas has three planes and
 // dst.p[3] is alpha_value quantised like an accumulator
 struct ResamplePlanarRgbaParams {
@@ -506,7 +529,7 @@ struct ResamplePlanarRgbaParams {
     RgbaPlanes dst;
     int uniform = 0; float alpha_value = 1.f;
 };
-hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStream_t s);
+hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
 // k_resample_yuv.hip: resample_kernel's resize of the fp32 RGB canvas (same tap tables, same rows_max, the same two passes) with compose_yuv_kernel's
 // encoding behind it instead of the BGR quantisation: the resized R, G, B clamped to [0, 1] and written as the YUV planes of dst (outH x outW =
 // dst.rows x dst.cols), Y per pixel; 4:2:0: Cb / Cr of the RGB filtered (1/4, 1/2, 1/4) x (1/2, 1/2) onto each chroma site (renderYuvResized)
@@ -524,7 +547,7 @@ struct ResampleYuvParams {
 // rows_max_above: resample_rows_max(.., 1) of the same tables.  The launcher, which knows what the destination's siting dispatches, sizes the LDS and the kernel's
 // row pitch by it where the kernel reads the row above its tile (top-left sited I420 / NV12) and by p.rows_max everywhere else; a top-left launch
 // without it is an error, not a launch with too little LDS.
-hipError_t launch_resample_yuv(const ResampleYuvParams& p, int rows_max_above, hipStream_t s);
+hipError_t launch_resample_yuv(const ResampleYuvParams& p, int rows_max_above, hipStream_t s, const DitherArgs& d = DitherArgs());
 // debug/test helpers used by w2x_infer (mirrors blobFromImages / imagesFromBlob, img2img_infer.cpp:5-39)
 hipError_t launch_blob_to_nhwc(const float* nchw, void* out_nhwc4, int B, int T, bool fp32, hipStream_t s);
 hipError_t launch_nhwc_to_blob(const void* in_nhwc4, float* nchw, int B, int T, bool fp32, hipStream_t s);

@@ -8,6 +8,7 @@
 #pragma once
 #include "kernels.h"
 #include "prepost_device.h"
+#include <type_traits>
 
 namespace w2x {
 namespace {
@@ -36,6 +37,14 @@ hipError_t launch_resample_tiles(void (*kernel)(KA...), int row_dwords, int rows
     const dim3 grid((unsigned)((outW + kRsCols - 1) / kRsCols), (unsigned)((outH + kRsRows - 1) / kRsRows));
     hipLaunchKernelGGL(kernel, grid, dim3(kRsThreads), (size_t)rows_max * row, s, args...);
     return hipGetLastError();
+}
+
+// launch(std::integral_constant<int, M>()) for the dithered mode of d (Ordered or BlueNoise; dither_args_ok(d)): the launchers' switch from the run-time mode
+// to the kernel instantiation.  The table's bytes are not staged in LDS, so no resize launch counts them in its dynamic LDS.
+template <typename Launch> hipError_t for_dither(const DitherArgs& d, Launch launch) {
+    if (d.mode == kDitherOrdered) return launch(std::integral_constant<int, kDitherOrdered>());
+    if (d.mode == kDitherBlueNoise && d.table) return launch(std::integral_constant<int, kDitherBlueNoise>());
+    return hipErrorInvalidValue;                                         // no kernel for it: an error, never the undithered kernel
 }
 
 // ---- the sample types: what a plane holds per pixel.  `maxcode` is 2^bits - 1 and `inv` fl32(1 / maxcode), both made on the host (launch_*).
@@ -82,6 +91,25 @@ template <> __device__ __forceinline__ void store4<F32>(uint8_t* row, int X, int
     float* d = (float*)row + X;
     if (np == 4 && (((size_t)d) & 15) == 0) *(float4v*)d = (float4v){sat01(v[0]), sat01(v[1]), sat01(v[2]), sat01(v[3])};
     else for (int k = 0; k < np; ++k) d[k] = sat01(v[k]);
+}
+// M: store4<S, M> is the store of plane index c, row Y of a kernel templated on the dither mode.  kDitherNone and float samples: the store above,
+// untouched.  A dithered mode quantises sample k with the threshold of (X + k, Y) of plane c (quant_code, prepost_device.h) and packs the same stores.
+template <typename S, int M>
+__device__ __forceinline__ void store4(uint8_t* row, int X, int np, const float v[4], float scale, int maxcode, const DitherArgs& dz, int c, int Y) {
+    if constexpr (M == kDitherNone || std::is_same<S, F32>::value) store4<S>(row, X, np, v, scale, maxcode);
+    else {
+        typename S::T* d = (typename S::T*)row + X;
+        unsigned q[4];
+#pragma unroll
+        for (int k = 0; k < 4; ++k) q[k] = quant_code<M>(v[k] * scale, maxcode, dz, c, X + k, Y);
+        if constexpr (std::is_same<S, U8>::value) {
+            if (np == 4 && (((size_t)d) & 3) == 0) *(unsigned*)d = q[0] | q[1] << 8 | q[2] << 16 | q[3] << 24;
+            else for (int k = 0; k < np; ++k) d[k] = (uint8_t)q[k];
+        } else {
+            if (np == 4 && (((size_t)d) & 7) == 0) *(uint2*)d = make_uint2(q[0] | q[1] << 16, q[2] | q[3] << 16);
+            else for (int k = 0; k < np; ++k) d[k] = (uint16_t)q[k];
+        }
+    }
 }
 
 // ---- gather_kernel's loop: tile pixel i of B tiles of T x T, the slot lookup, the zero pixel of a pad slot, the TTA source map and the replicate clamp to a

@@ -3,6 +3,7 @@
 // lives here once and both files inline it.
 #pragma once
 #include "kernels.h"
+#include <type_traits>
 
 namespace w2x {
 namespace {
@@ -49,6 +50,51 @@ __device__ __forceinline__ unsigned quantize_bgr(float r, float g, float b) {
                    R = (unsigned)min(max(__float2int_rn(r * 255.f), 0), 255);
     return B | G << 8 | R << 16;
 }
+// ---- dithered quantisation (dither.h states the rule).  M is a template parameter of every kernel that stores integer samples; its kDitherNone
+// instantiation contains none of the code below and is the undithered kernel, instruction for instruction.
+// The threshold t = (rank + 0.5) / N of the sample (x, y) of plane index c.  Ordered: the Bayer rank from the bits of u = x + dx, v = y + dy, no table -
+// q_b = ((u_b ^ v_b) << 1) | v_b, rank = q_0 << 4 | q_1 << 2 | q_2.  BlueNoise: one 2-byte load from the 8 KiB table, which every workgroup of the launch reads
+// and the vector L1 keeps (a thread's four samples start at any (x + dx) & 63 and wrap, so they are four loads, not one).  c is a compile-time constant or a
+// loop counter of an unrolled loop wherever this is called: d.dx[c] / d.dy[c] are scalar registers.
+// A kernel templated on M ends its parameter list with a pack: empty for kDitherNone - the argument list, and so the kernarg offsets, of the undithered kernel -
+// and one DitherArgs for a dithered mode.  dither_of(dzs...) is that argument, or a default nobody reads.
+__device__ __forceinline__ DitherArgs dither_of() { return DitherArgs(); }
+__device__ __forceinline__ const DitherArgs& dither_of(const DitherArgs& d) { return d; }
+template <int M, typename... D> constexpr bool dither_pack_ok = M == kDitherNone ? sizeof...(D) == 0 : (sizeof...(D) == 1 && (std::is_same<D, DitherArgs>::value && ...));
+template <int M>
+__device__ __forceinline__ float dither_t(const DitherArgs& d, int c, int x, int y) {
+    static_assert(M == kDitherOrdered || M == kDitherBlueNoise, "None adds nothing");
+    const unsigned u = (unsigned)(x + d.dx[c]), v = (unsigned)(y + d.dy[c]);
+    if constexpr (M == kDitherOrdered) {
+        const unsigned w = u ^ v;
+        const unsigned rank = (w & 1u) << 5 | (v & 1u) << 4 | (w & 2u) << 2 | (v & 2u) << 1 | (w & 4u) >> 1 | (v & 4u) >> 2;
+        return ((float)rank + 0.5f) * (1.f / 64.f);
+    } else {
+        const unsigned rank = d.table[(v & (kDitherSide - 1)) * kDitherSide + (u & (kDitherSide - 1))];
+        return ((float)rank + 0.5f) * (1.f / 4096.f);
+    }
+}
+// min(max(floor(fl32(V + t)), 0), maxcode): V the value the undithered kernel rounds to nearest, made by the caller with the contraction it has there.  The
+// addition is one rounded fp32 add: contraction is off in this block, so the product or fma that made V is never fused with it.
+template <int M>
+__device__ __forceinline__ unsigned dither_code(float V, float t, int maxcode) {
+#pragma clang fp contract(off)
+    const float s = __fadd_rn(V, t);
+    return (unsigned)min(max(__float2int_rd(s), 0), maxcode);
+}
+// sat(rint(V)) or the dithered code of sample (x, y) of plane c: the one quantisation of a kernel templated on M
+template <int M>
+__device__ __forceinline__ unsigned quant_code(float V, int maxcode, const DitherArgs& d, int c, int x, int y) {
+    if constexpr (M == kDitherNone) return (unsigned)min(max(__float2int_rn(V), 0), maxcode);
+    else return dither_code<M>(V, dither_t<M>(d, c, x, y), maxcode);
+}
+// quantize_bgr of pixel (x, y) of a BGR frame: b | g << 8 | r << 16, R, G, B = planes 0, 1, 2
+template <int M>
+__device__ __forceinline__ unsigned quantize_bgr_at(float r, float g, float b, const DitherArgs& d, int x, int y) {
+    if constexpr (M == kDitherNone) return quantize_bgr(r, g, b);
+    else return quant_code<M>(b * 255.f, 255, d, 2, x, y) | quant_code<M>(g * 255.f, 255, d, 1, x, y) << 8 | quant_code<M>(r * 255.f, 255, d, 0, x, y) << 16;
+}
+
 template <typename P>
 __device__ __forceinline__ void compose_pixel_sums(const ComposeParams& p, const P* tiles, int X, int Y, float& r0, float& r1, float& r2) {
     const int To = p.To, n = To - 1;

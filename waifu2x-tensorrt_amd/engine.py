@@ -332,6 +332,16 @@ YUV_SITED_SYMBOLS = {
     "w2x_render_yuv_sited": (_I, _YUV2S + [_I, _I, _I]),
     "w2x_render_sequence_yuv_sited": (_I, _YUV2S + [_I, _I, _I, _I]),
 }
+# The dither entries of include/w2x/c_api_dither.h, a table of their own likewise: (engine, mode, phase, advance), its getter, the rank table and one rank
+# without an engine, and the test hook (engine, src planes, src steps, rows, cols, dst planes, dst steps, bits).
+DITHER_SYMBOLS = {
+    "w2x_set_dither": (_I, [_P, _I, C.c_uint, C.c_uint]),
+    "w2x_get_dither": (_I, [_P, _P, _P, _P]),
+    "w2x_dither_table": (_I, [_I, _P, _P]),
+    "w2x_dither_rank": (_I, [_I, C.c_uint, _I, _I, _I]),
+    "w2x_dither_planes": (_I, [_P, _P, _P, _I, _I, _P, _P, _I]),
+}
+DITHER_MODES = {"none": 0, "ordered": 1, "bluenoise": 2}    # W2X_DITHER_NONE .. _BLUENOISE (include/w2x/c_api_dither.h)
 _lib = None
 
 
@@ -344,7 +354,7 @@ def lib():
         raise W2xError(f"{lib_path} is missing - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "or `make -C waifu2x-tensorrt_amd` (there is no CPU fallback)")
     L = C.CDLL(lib_path)
-    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()) + list(PLANAR_SYMBOLS.items()) + list(RGBAP_SYMBOLS.items()) + list(YUV_RESIZED_SYMBOLS.items()) + list(YUV_SITED_SYMBOLS.items()):
+    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()) + list(PLANAR_SYMBOLS.items()) + list(RGBAP_SYMBOLS.items()) + list(YUV_RESIZED_SYMBOLS.items()) + list(YUV_SITED_SYMBOLS.items()) + list(DITHER_SYMBOLS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -741,6 +751,44 @@ class Img2Img:
         skip_uniform_alpha is decided per frame.  Strides, outs and pinned as in render_sequence_planar()."""
         return self._planar_sequence(frames, size, bits, out_bits, order, filter, outs, pinned, "rgba", (int(bleed), int(bool(skip_uniform_alpha))),
                                      self._L.w2x_render_sequence_rgbap, self._L.w2x_render_sequence_rgbap_resized, "render_sequence_planar_rgba failed")
+
+    def set_dither(self, mode="none", phase: int = 0, advance: int = 0) -> bool:
+        """The dither of every integer sample the following frame calls write (w2x_set_dither, c_api_dither.h states the rule): mode "none", "ordered" (8 x 8
+        Bayer) or "bluenoise" (64 x 64 void-and-cluster table) - or its number, which the engine checks.  phase moves the pattern; frame i of a sequence call is
+        dithered as the single call at phase + i * advance (advance 0: a still pattern, 1: temporal dither).  Alpha and float outputs are never dithered.  The
+        setting stays until it is changed and may be made before load().  An unknown name raises ValueError; an unknown number returns False (message
+        callback) and leaves the previous setting."""
+        if isinstance(mode, str):
+            if mode not in DITHER_MODES:
+                raise ValueError(f"dither mode must be one of {sorted(DITHER_MODES)}, got {mode!r}")
+            mode = DITHER_MODES[mode]
+        return bool(self._L.w2x_set_dither(self._h, int(mode), int(phase) & 0xFFFFFFFF, int(advance) & 0xFFFFFFFF))
+
+    def dither(self):
+        """the current setting as (mode name, phase, advance) (w2x_get_dither)"""
+        m, p, a = C.c_int(0), C.c_uint(0), C.c_uint(0)
+        if not self._L.w2x_get_dither(self._h, C.byref(m), C.byref(p), C.byref(a)):
+            raise W2xError("w2x_get_dither failed")
+        return {v: k for k, v in DITHER_MODES.items()}[m.value], int(p.value), int(a.value)
+
+    def dither_planes(self, planes, bits: int, dst=None):
+        """Test hook (w2x_dither_planes): three 2-D float32 planes of one shape (views with padded rows allowed) -> three planes of `bits` (8: uint8; 10, 12, 16:
+        uint16), every sample quantised on the device from V = v * (2^bits - 1) by the store of the compose and resample kernels with the current set_dither()
+        setting (none: sat(rint(V))); plane k has plane index k.  dst: three pre-allocated planes of that depth's dtype (views allowed), which are returned."""
+        src = [np.asarray(p) for p in planes]
+        if len(src) != 3 or any(p.ndim != 2 or p.dtype != np.float32 or p.shape != src[0].shape or p.strides[1] != 4 for p in src):
+            raise ValueError("planes must be three 2-D float32 planes of one shape with packed samples")
+        bits = int(bits)
+        if bits not in (8, 10, 12, 16):
+            raise ValueError(f"bits must be 8, 10, 12 or 16, got {bits!r}")
+        r, c = src[0].shape
+        dt = np.dtype(PLANAR_DTYPES[bits])
+        out = tuple(np.empty((r, c), dt) for _ in range(3)) if dst is None else tuple(dst)
+        if len(out) != 3 or any(p.ndim != 2 or p.dtype != dt or p.shape != (r, c) or p.strides[1] != dt.itemsize for p in out):
+            raise ValueError(f"dst must be three 2-D {dt.name} planes of the input's shape with packed samples")
+        ok = self._L.w2x_dither_planes(self._h, (C.c_void_p * 3)(*[_data(p) for p in src]), (C.c_size_t * 3)(*[p.strides[0] for p in src]), r, c,
+                                       (C.c_void_p * 3)(*[_data(p) for p in out]), (C.c_size_t * 3)(*[p.strides[0] for p in out]), bits)
+        return self._finish(ok, out, "dither_planes failed")
 
     def alpha_bleed_planes_device(self, planes, radius: int, *, bits: int | None = None, order: str = "rgba", words: bool = False):
         """Test hook (w2x_alpha_bleed_rgbap_device): the device bleed alone on a planar RGBA frame -> the three colour planes the tiles are read from, in R, G, B
@@ -1185,6 +1233,24 @@ def alpha_bleed_planes(planes, radius: int, *, bits: int | None = None, order: s
                                        int(radius), (C.c_void_p * 3)(*[_data(p) for p in out]), (C.c_size_t * 3)(*[p.strides[0] for p in out])):
         raise ValueError(f"alpha_bleed_planes refused planes of {src[0].shape} at radius {radius}")
     return out
+
+
+def dither_table(mode) -> np.ndarray:
+    """The rank table of a dither mode (w2x_dither_table): "ordered" the 8 x 8 Bayer matrix, "bluenoise" the 64 x 64 void-and-cluster table; uint16 [side, side],
+    every rank 0 .. side^2 - 1 once.  The threshold of a sample is (rank + 0.5) / side^2."""
+    m = DITHER_MODES.get(mode, mode) if isinstance(mode, str) else int(mode)
+    side = C.c_int(0)
+    if not isinstance(m, int) or not lib().w2x_dither_table(m, None, C.byref(side)):
+        raise ValueError(f"dither_table: no table for mode {mode!r}")
+    out = np.empty((side.value, side.value), np.uint16)
+    lib().w2x_dither_table(m, _data(out), C.byref(side))
+    return out
+
+
+def dither_rank(mode, phase: int, c: int, x: int, y: int) -> int:
+    """The rank of sample (x, y) of plane index c at `phase` (w2x_dither_rank); -1 for mode none, an unknown mode, c outside 0 .. 2 or a negative position."""
+    m = DITHER_MODES.get(mode, -1) if isinstance(mode, str) else int(mode)
+    return int(lib().w2x_dither_rank(m, int(phase) & 0xFFFFFFFF, int(c), int(x), int(y)))
 
 
 def alpha_bleed(bgr: np.ndarray, alpha: np.ndarray, radius: int) -> np.ndarray:
