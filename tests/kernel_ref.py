@@ -139,7 +139,8 @@ def image_head(y, tiw, tib, B, Mrows, aW, clip=None, f16_model=False):
     return h.reshape(B, Hr, aW, 4, 4, 4).transpose(0, 1, 3, 2, 4, 5).reshape(B, 4 * Hr, 4 * aW, 4)
 
 
-# ---- the general implicit GEMM (kernels.h GemmParams; k_gemm.hip and the kernels specialised from it: k_stem.hip, k_conv48.hip, k_pixgemm.hip)
+# ---- the general implicit GEMM (kernels.h GemmParams; k_gemm.hip and the kernels specialised from it: k_stem.hip, k_conv48.hip, k_pixgemm.hip; cunet's k_conv3.hip,
+# k_conv3h.hip and gated operands, for tests/test_gpu_cunet_kernels.py)
 def activation(v, act, alpha=0.0):
     """GemmParams::act: 0 none, 1 LeakyReLU(alpha), 2 GELU (exact erf), 3 ReLU, 4 sigmoid."""
     if act == 1:
@@ -164,11 +165,22 @@ def gemm_ref(params, f16_model=False):
     Returns {"out": [B][Hs][Ws][Cs] (NaN where nothing is stored), "stats": [B][Hs][Ws][2] (likewise) or None}.
     f16_model=True rounds to fp16 where gemm_kernel stores: the activated value (its LDS tile) and the final one after the skip adds and the clip.  The
     kernels with a single store (stem_kernel, conv48_kernel, merge_kernel, toimage_kernel, pixgemm_kernel without res) round once, which is the same
-    thing: with no skip add in between, the second rounding (and the clip between fp16 bounds) finds an fp16 value."""
+    thing: with no skip add in between, the second rounding (and the clip between fp16 bounds) finds an fp16 value.
+    cunet's additions:
+      a_scale [B][a Cs], res_scale [B][res Cs]: squeeze-excite gates of the input map / the first skip map.  Exact: x * s unrounded; f16_model: fp16(x * s), the one
+        rounding of kernels.h gate8 (and of the in-place pass scale_kernel);
+      round_once=True: the activated value is NOT rounded, the skip add and the clip run on it and the result is rounded once (conv3h_kernel; f16_model only);
+      N smaller than the stored channels (rows mode onto 4 stored channels, N = 3): the missing rows count as zero weights with zero bias, so a missing channel holds
+        clip(act(0) + res) = clip(res);
+      pool = ("rows", R) or ("tiles", TH, TW): also returns "pool" [B][tiles][N], the column sums of the stored values per workgroup (pool_sums below)."""
     g = lambda k, d=None: params.get(k, d)
     r16 = f16 if f16_model else (lambda v: v)
     a = np.asarray(params["a"], dtype=np.float64)
     B, Hs, Ws, Cs = a.shape
+    once = bool(g("round_once", False))
+    if g("a_scale") is not None:
+        with np.errstate(invalid="ignore"):
+            a = r16(a * np.asarray(params["a_scale"], dtype=np.float64).reshape(B, 1, 1, Cs))
     amode, kh, kw, stride = g("amode", 0), g("kh", 1), g("kw", 1), g("stride", 1)
     Mrows, aW, K, N = params["Mrows"], params["aW"], params["K"], params["N"]
     m = np.arange(Mrows)
@@ -179,13 +191,20 @@ def gemm_ref(params, f16_model=False):
         A = a[:, py[:, None, None] + ky[None], px[:, None, None] + kx[None], :].reshape(B, Mrows, kh * kw * Cs)[..., :K]
     else:
         A = a[:, py, px, :K]
-    v = A @ np.asarray(params["wt"], dtype=np.float64)[:, :K].T                     # [B][Mrows][N]
+    wt, bias = np.asarray(params["wt"], dtype=np.float64)[:, :K], g("bias")
+    if g("omode", 0) != 2 and params["out_shape"][2] == 4 and N < 4:                  # a head of fewer than 4 channels stores 4: zero weights, zero bias
+        wt = np.concatenate([wt[:N], np.zeros((4 - N, K))])
+        bias = None if bias is None else np.concatenate([np.asarray(bias, dtype=np.float64)[:N], np.zeros(4 - N)])
+        N = 4
+    v = A @ wt.T                                                                     # [B][Mrows][N]
     if g("ln", 0):
         st = np.asarray(params["stats_in"], dtype=np.float64)[:, py, px]             # [B][Mrows][2]
         v = st[..., 1:2] * (v - st[..., 0:1] * np.asarray(params["csum"], dtype=np.float64))
-    if g("bias") is not None:
-        v = v + np.asarray(params["bias"], dtype=np.float64)
-    v = r16(activation(v, g("act", 0), g("alpha", 0.0)))
+    if bias is not None:
+        v = v + np.asarray(bias, dtype=np.float64)
+    v = activation(v, g("act", 0), g("alpha", 0.0))
+    if not once:
+        v = r16(v)
     oHs, oWs, oCs = params["out_shape"]
     omode, r = g("omode", 0), g("r", 1) if g("omode", 0) == 2 else 1
     dst = np.asarray(params["win_table"], dtype=np.int64)[:Mrows] if omode == 1 else m
@@ -199,14 +218,102 @@ def gemm_ref(params, f16_model=False):
         t = v[..., sg * ncol:(sg + 1) * ncol]
         for key in ("res", "res2"):
             if g(key) is not None:
-                t = t + np.asarray(params[key], dtype=np.float64)[:, Y + g(key + "_y0", 0), X + g(key + "_x0", 0), :ncol]
+                rm = np.asarray(params[key], dtype=np.float64)[:, Y + g(key + "_y0", 0), X + g(key + "_x0", 0), :ncol]
+                if key == "res" and g("res_scale") is not None:
+                    rm = r16(rm * np.asarray(params["res_scale"], dtype=np.float64)[:, None, :ncol])
+                t = t + rm
         if g("clip") is not None:
             t = np.clip(t, g("clip")[0], g("clip")[1])
         t = r16(t)
         out[:, Y, X, :ncol] = t
         if stats is not None:
             stats[:, Y, X] = row_stats(t[..., :g("Cout", ncol)], g("ln_eps", 1e-5))
-    return {"out": out, "stats": stats}
+    pool = pool_sums(out, Mrows, aW, g("pool"))[..., :N] if g("pool") is not None else None
+    return {"out": out, "stats": stats, "pool": pool}
+
+
+def pool_sums(out, Mrows, aW, tiling):
+    """Squeeze-excite pooling partials of a rows-mode output map [B][Hs][Ws][C] whose rows m < Mrows sit at (m // aW, m % aW): float64 column sums per workgroup in
+    tile order.  ("rows", R): gemm_kernel, R consecutive rows of an image; ("tiles", TH, TW): conv3_kernel, TH x TW pixel tiles in row-major tile order - the
+    pixels of a ragged tile past Ho x Wo are left out."""
+    out = np.asarray(out, dtype=np.float64)
+    B, C = out.shape[0], out.shape[3]
+    Ho, Wo = Mrows // aW, aW
+    v = out[:, :Ho, :Wo]
+    if tiling[0] == "rows":
+        R = tiling[1]
+        flat = v.reshape(B, Ho * Wo, C)
+        return np.stack([flat[:, t:t + R].sum(axis=1) for t in range(0, Mrows, R)], axis=1)
+    TH, TW = tiling[1], tiling[2]
+    return np.stack([v[:, y:y + TH, x:x + TW].sum(axis=(1, 2)) for y in range(0, Ho, TH) for x in range(0, Wo, TW)], axis=1)
+
+
+def pool_abs_counts(out, Mrows, aW, tiling):
+    """For pool_sums' derived bound (n - 1) 2^-24 sum |v|: (sum |v|, n) per partial."""
+    o = np.asarray(out, dtype=np.float64)
+    return pool_sums(np.abs(o), Mrows, aW, tiling), pool_sums(np.ones_like(o), Mrows, aW, tiling)
+
+
+def cells_read(params):
+    """The reference's own index arithmetic: bool [Hs][Ws] of the input map's pixels that a stored output depends on (the same for every image), and for each skip map
+    present {"res": mask, ...}.  Everything else may hold NaN."""
+    g = lambda k, d=None: params.get(k, d)
+    Hs, Ws = np.asarray(params["a"]).shape[1:3]
+    amode, kh, kw, stride = g("amode", 0), g("kh", 1), g("kw", 1), g("stride", 1)
+    Mrows, aW = params["Mrows"], params["aW"]
+    m = np.arange(Mrows)
+    src = np.asarray(params["win_table"], dtype=np.int64)[:Mrows] if amode == 1 else m
+    py, px = (src // aW) * stride + g("a_y0", 0), (src % aW) * stride + g("a_x0", 0)
+    mask = np.zeros((Hs, Ws), dtype=bool)
+    for ky in range(kh if amode == 2 else 1):
+        for kx in range(kw if amode == 2 else 1):
+            mask[py + ky, px + kx] = True
+    r = g("r", 1) if g("omode", 0) == 2 else 1
+    oy, ox = m // aW, m % aW
+    skips = {}
+    for key in ("res", "res2"):
+        if g(key) is not None:
+            rm = np.zeros(np.asarray(params[key]).shape[1:3], dtype=bool)
+            for dy in range(r):
+                for dx in range(r):
+                    rm[oy * r + dy + g(key + "_y0", 0), ox * r + dx + g(key + "_x0", 0)] = True
+            skips[key] = rm
+    return mask, skips
+
+
+def two_launches(P1, P2, f16_model=False):
+    """A fused launch as its two launches: P2 reads P1's output map (P2["a"] is ignored).  Exact: no rounding in between; f16_model: fp16 where each launch stores.
+    STEM: stem -> fp16 -> conv.  UP: fp16(leaky(proj(fp16(x s)))) -> fp16(+ skip) -> conv (gemm_ref's two roundings of a launch with a skip add)."""
+    mid = gemm_ref(P1, f16_model)["out"]
+    return mid, gemm_ref(dict(P2, a=np.nan_to_num(mid)), f16_model)["out"]
+
+
+# ---- squeeze-excite gates (k_prepost.hip se_kernel)
+def se_ref(pool_partials, inv_count, w1, b1, w2, b2, dtype=np.float64):
+    """gate[b][c] = sigmoid(W2 relu(W1 mean + b1) + b2), mean = inv_count * (sum of the image's partials); pool_partials [B][nblocks][>= C] (columns past C ignored),
+    w1 [Cmid][C], w2 [C][Cmid].  dtype=np.float32 restates the same formula in float32 - the "ideal fp32 kernel" se_kernel is measured beside."""
+    w1, b1, w2, b2 = (np.asarray(v, dtype=dtype) for v in (w1, b1, w2, b2))
+    C = w1.shape[1]
+    mean = np.asarray(pool_partials, dtype=dtype)[:, :, :C].sum(axis=1, dtype=dtype) * dtype(inv_count)
+    mid = np.maximum(mean @ w1.T + b1, dtype(0))
+    return (dtype(1) / (dtype(1) + np.exp(-(mid @ w2.T + b2)))).astype(dtype)
+
+
+def se_bound(pool_partials, inv_count, w1, b1, w2, b2):
+    """Derived fp32 bound Delta a on the sigmoid's argument: the partial-sum tree (n - 1 additions), the product with inv_count and the two dot products, each of L
+    terms at (L + 1) 2^-24 of its sum of magnitudes, the first layer's error carried through |W2|.  [B][C]."""
+    u = 2.0 ** -24
+    w1, b1, w2, b2 = (np.asarray(v, dtype=np.float64) for v in (w1, b1, w2, b2))
+    C, Cmid = w1.shape[1], w1.shape[0]
+    pp = np.asarray(pool_partials, dtype=np.float64)[:, :, :C]
+    n = pp.shape[1]
+    amean = np.abs(pp).sum(axis=1) * inv_count
+    dmean = (n + 1) * u * amean
+    mag1 = amean @ np.abs(w1).T + np.abs(b1)
+    dmid = dmean @ np.abs(w1).T + (C + 1) * u * mag1
+    mid = np.maximum((pp.sum(axis=1) * inv_count) @ w1.T + b1, 0)
+    mag2 = np.abs(mid) @ np.abs(w2).T + np.abs(b2)
+    return dmid @ np.abs(w2).T + (Cmid + 1) * u * mag2
 
 
 # ---- the large-input formula (tools/kernel_check/transformer_check.cpp gen_x16)
@@ -248,7 +355,7 @@ def error_metrics(got, exact):
 
 
 # ---- the harnesses (tools/kernel_check/transformer_check.cpp, conv_check.cpp): host code only, built like the w2x command line
-def build_harness(exe, source="transformer_check.cpp"):
+def build_harness(exe, source="transformer_check.cpp"):   # (cunet_check.cpp too)
     import os
     import subprocess
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))

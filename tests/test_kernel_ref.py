@@ -206,3 +206,144 @@ def test_gemm_ref_fp16_model_rounds_before_and_after_the_skip_adds():
     assert exact == 1.0 + 2.0 ** -10 + 2.0 ** -20
     assert model == float(np.float16(np.float64(np.float16(wt[0, 0])) + 2.0 ** -11)) == 1.0 + 2.0 ** -9
     assert float(np.float16(exact)) == 1.0 + 2.0 ** -10                         # a single rounding of the exact sum lands elsewhere
+
+
+# ---- cunet's additions to gemm_ref, the squeeze-excite reference
+def test_gemm_ref_round_once_rounds_the_skip_sum_alone():
+    """conv3h_kernel adds the skip and clips in fp32 and rounds once: the same tie as above lands on the exact sum's rounding, not on gemm_kernel's."""
+    a = np.array([[[[1.0, 0, 0, 0, 0, 0, 0, 0]]]])
+    wt = np.zeros((8, 8)); wt[0, 0] = 1.0 + 2.0 ** -11 + 2.0 ** -20
+    res = np.full((1, 1, 1, 8), 2.0 ** -11)
+    p = dict(a=a, Mrows=1, aW=1, K=8, N=8, wt=wt, out_shape=(1, 1, 8), res=res)
+    twice, once = kr.gemm_ref(p, f16_model=True)["out"][0, 0, 0, 0], kr.gemm_ref(dict(p, round_once=True), f16_model=True)["out"][0, 0, 0, 0]
+    assert twice == 1.0 + 2.0 ** -9 and once == 1.0 + 2.0 ** -10 == float(np.float16(kr.gemm_ref(p)["out"][0, 0, 0, 0]))
+    assert kr.gemm_ref(dict(p, round_once=True))["out"][0, 0, 0, 0] == kr.gemm_ref(p)["out"][0, 0, 0, 0]      # the exact form has no rounding to move
+    # the clip runs on the unrounded sum
+    c = kr.gemm_ref(dict(p, round_once=True, clip=(0.0, 1.0)), f16_model=True)["out"][0, 0, 0, 0]
+    assert c == 1.0
+
+
+def test_gemm_ref_gates_against_an_explicit_loop():
+    """a_scale / res_scale [B][C]: exact x * s unrounded; the fp16 model rounds fp16(x * s) once per element (gate8) - held against a per-element loop, for the
+    rows mode, the 3x3 taps (channel = k mod Cs) and the 2x2 stride-2 taps."""
+    rng = np.random.default_rng(11)
+    for amode, kh, stride, Cs in ((0, 1, 1, 16), (2, 3, 1, 8), (2, 2, 2, 8)):
+        B, Ho, Wo, N = 2, 2, 3, 8
+        K = kh * kh * Cs
+        Hs, Ws = (Ho - 1) * stride + kh + 1, (Wo - 1) * stride + kh
+        a = kr.f16(rng.normal(0, 1, (B, Hs, Ws, Cs)))
+        wt, bias = _weights(rng, N, K), rng.normal(0, 0.1, N)
+        s, rs = rng.uniform(0.1, 0.9, (B, Cs)).astype(np.float32), rng.uniform(0.1, 0.9, (B, N)).astype(np.float32)
+        res = kr.f16(rng.normal(0, 1, (B, Ho + 1, Wo + 1, N)))
+        p = dict(a=a, a_y0=1, amode=amode, kh=kh, kw=kh, stride=stride, Mrows=Ho * Wo, aW=Wo, K=K, N=N, wt=wt, bias=bias, out_shape=(Ho, Wo, N), a_scale=s, res=res, res_y0=1,
+                 res_x0=1, res_scale=rs)
+        for model in (False, True):
+            got = kr.gemm_ref(p, model)["out"]
+            r = kr.f16 if model else (lambda v: v)
+            for b in range(B):
+                for oy in range(Ho):
+                    for ox in range(Wo):
+                        for n in range(N):
+                            acc = 0.0
+                            for ky in range(kh):
+                                for kx in range(kh):
+                                    for c in range(Cs):
+                                        x = float(r(a[b, oy * stride + 1 + ky, ox * stride + kx, c] * np.float64(s[b, c])))
+                                        acc += x * wt[n, (ky * kh + kx) * Cs + c]
+                            v = float(r(acc + bias[n]))
+                            v = float(r(v + float(r(res[b, oy + 1, ox + 1, n] * np.float64(rs[b, n])))))
+                            assert abs(got[b, oy, ox, n] - v) <= 1e-12, (amode, model)
+        # the gate's rounding is visible: the model differs from the exact form by more than the two output roundings alone would allow somewhere
+        assert np.abs(kr.gemm_ref(p, True)["out"] - kr.gemm_ref(p)["out"]).max() > 0
+
+
+def test_gemm_ref_short_head_counts_missing_rows_as_zero():
+    rng = np.random.default_rng(12)
+    B, Ho, Wo, Cin = 2, 3, 4, 8
+    a = kr.f16(rng.normal(0, 1, (B, Ho + 2, Wo + 2, Cin)))
+    wt, bias = _weights(rng, 3, 9 * Cin), rng.normal(0.5, 0.1, 3)
+    res = kr.f16(rng.normal(0.5, 1.0, (B, Ho, Wo, 4)))
+    p = dict(a=a, amode=2, kh=3, kw=3, Mrows=Ho * Wo, aW=Wo, K=9 * Cin, N=3, wt=wt, bias=bias, out_shape=(Ho, Wo, 4), res=res, clip=(0.0, 1.0), round_once=True)
+    full = dict(p, N=4, wt=np.concatenate([wt, np.zeros((1, wt.shape[1]))]), bias=np.concatenate([bias, [0.0]]))
+    for model in (False, True):
+        got = kr.gemm_ref(p, model)["out"]
+        assert np.array_equal(got, kr.gemm_ref(full, model)["out"])
+        assert np.array_equal(got[..., 3], np.clip(res[..., 3], 0.0, 1.0))
+    assert np.array_equal(kr.gemm_ref(dict(p, res=None, clip=None))["out"][..., 3], np.zeros((B, Ho, Wo)))
+
+
+def test_pool_sums_tile_orders():
+    rng = np.random.default_rng(13)
+    B, Ho, Wo, C = 2, 9, 65, 8
+    out = np.full((B, Ho + 1, Wo + 2, C), np.nan)
+    out[:, :Ho, :Wo] = rng.normal(0, 1, (B, Ho, Wo, C))
+    rows = kr.pool_sums(out, Ho * Wo, Wo, ("rows", 128))
+    assert rows.shape == (B, 5, C)
+    flat = out[:, :Ho, :Wo].reshape(B, -1, C)
+    for t in range(5):
+        assert np.allclose(rows[:, t], flat[:, 128 * t:128 * (t + 1)].sum(axis=1), rtol=0, atol=1e-12)
+    tiles = kr.pool_sums(out, Ho * Wo, Wo, ("tiles", 8, 64))
+    assert tiles.shape == (B, 4, C)
+    want = [out[:, :8, :64], out[:, :8, 64:65], out[:, 8:9, :64], out[:, 8:9, 64:65]]          # row-major tile order, the ragged tiles hold 8, 64 and 1 pixels
+    for t in range(4):
+        assert np.allclose(tiles[:, t], want[t].sum(axis=(1, 2)), rtol=0, atol=1e-12)
+    assert np.allclose(rows.sum(axis=1), tiles.sum(axis=1), rtol=0, atol=1e-10)
+    mag, n = kr.pool_abs_counts(out, Ho * Wo, Wo, ("tiles", 8, 64))
+    assert np.array_equal(n[0, :, 0], [512, 8, 64, 1]) and (mag >= np.abs(tiles)).all()
+    got = kr.gemm_ref(dict(a=np.ones((1, 1, 130, 8)), Mrows=130, aW=130, K=8, N=8, wt=np.eye(8), out_shape=(1, 130, 8), pool=("rows", 128)))["pool"]
+    assert np.array_equal(got[0, :, 0], [128.0, 2.0])
+
+
+def test_cells_read_is_the_reference_gather():
+    """Whatever cells_read leaves out may hold NaN without touching gemm_ref's stored outputs; and every cell it keeps reaches one."""
+    rng = np.random.default_rng(14)
+    a = kr.f16(rng.normal(0, 1, (2, 9, 11, 8)))
+    wt = _weights(rng, 8, 72)
+    res = kr.f16(rng.normal(0, 1, (2, 6, 8, 8)))
+    p = dict(a=a, a_y0=1, a_x0=2, amode=2, kh=3, kw=3, Mrows=4 * 5, aW=5, K=72, N=8, wt=wt, out_shape=(5, 6, 8), res=res, res_y0=1, res_x0=2)
+    mask, skips = kr.cells_read(p)
+    assert mask.sum() == 6 * 7 and mask[1:7, 2:9].all() and skips["res"].sum() == 20 and skips["res"][1:5, 2:7].all()
+    q = dict(p, a=a.copy(), res=res.copy())
+    q["a"][:, ~mask] = np.nan
+    q["res"][:, ~skips["res"]] = np.nan
+    want, got = kr.gemm_ref(p)["out"], kr.gemm_ref(q)["out"]
+    assert np.array_equal(np.isnan(got), np.isnan(want)) and np.array_equal(got[~np.isnan(want)], want[~np.isnan(want)])
+    q["a"][0, 1, 2, 0] = np.nan                                   # a cell it keeps
+    assert np.isnan(kr.gemm_ref(q)["out"][0, 0, 0]).all()
+    m2, _ = kr.cells_read(dict(a=a, amode=2, kh=2, kw=2, stride=2, Mrows=6, aW=3, K=32, N=8, wt=wt, out_shape=(2, 3, 8)))
+    assert m2.sum() == 24 and m2[:4, :6].all()
+
+
+def test_two_launches_is_conv_of_conv():
+    rng = np.random.default_rng(15)
+    a = kr.f16(rng.normal(0, 1, (1, 9, 9, 4)))
+    w1, w2 = kr.f16(rng.normal(0, 0.3, (8, 4, 3, 3))), kr.f16(rng.normal(0, 0.2, (8, 8, 3, 3)))
+    flat = lambda w: w.transpose(0, 2, 3, 1).reshape(w.shape[0], -1)
+    wt1 = np.zeros((8, 40)); wt1[:, :36] = flat(w1)
+    P1 = dict(a=a, amode=2, kh=3, kw=3, Mrows=49, aW=7, K=36, N=8, wt=wt1, act=1, alpha=0.1, out_shape=(7, 7, 8))
+    P2 = dict(a=None, a_y0=1, a_x0=1, amode=2, kh=3, kw=3, Mrows=16, aW=4, K=72, N=8, wt=flat(w2), out_shape=(4, 4, 8))
+    mid, out = kr.two_launches(P1, P2)
+    t = F.leaky_relu(F.conv2d(torch.from_numpy(a).permute(0, 3, 1, 2), torch.from_numpy(w1)), 0.1)
+    ref = F.conv2d(t[:, :, 1:, 1:], torch.from_numpy(w2))[:, :, :4, :4].permute(0, 2, 3, 1).numpy()
+    assert np.abs(mid - t.permute(0, 2, 3, 1).numpy()).max() <= 1e-12 and np.abs(out - ref).max() <= 1e-12
+    mid16, out16 = kr.two_launches(P1, P2, True)
+    assert np.array_equal(mid16, kr.f16(mid16)) and np.array_equal(out16, kr.f16(out16)) and np.abs(mid16 - mid).max() > 0
+
+
+def test_se_ref_matches_torch_float64():
+    rng = np.random.default_rng(16)
+    B, nb, C, Cm = 3, 5, 64, 8
+    pp = rng.normal(0, 30, (B, nb, C + 8))                       # (columns past C are ignored)
+    w1, b1, w2, b2 = rng.normal(0, 0.2, (Cm, C)), rng.normal(0, 0.2, Cm), rng.normal(0, 0.5, (C, Cm)), rng.normal(0, 0.5, C)
+    inv = 1.0 / 585
+    got = kr.se_ref(pp, inv, w1, b1, w2, b2)
+    mean = torch.from_numpy(pp[:, :, :C]).sum(dim=1) * inv
+    ref = torch.sigmoid(F.linear(F.relu(F.linear(mean, torch.from_numpy(w1), torch.from_numpy(b1))), torch.from_numpy(w2), torch.from_numpy(b2)))
+    assert got.dtype == np.float64 and np.abs(got - ref.numpy()).max() <= 1e-14
+    f32 = kr.se_ref(pp, inv, w1, b1, w2, b2, dtype=np.float32)
+    assert f32.dtype == np.float32
+    d = np.abs(f32.astype(np.float64) - got)
+    assert 0 < d.max() <= (0.25 * kr.se_bound(pp, inv, w1, b1, w2, b2) + 4 * 2.0 ** -24 * got).max()       # an fp32 evaluation sits inside the derived bound
+    # the bound sees a partial that is off by one part in 100 (these partials cancel: the worst-case bound is a few 1e-5)
+    pp2 = pp.copy(); pp2[:, 0, :C] *= 1.01
+    assert (np.abs(kr.se_ref(pp2, inv, w1, b1, w2, b2) - got) > 0.25 * kr.se_bound(pp, inv, w1, b1, w2, b2) + 16 * 2.0 ** -24 * got).any()

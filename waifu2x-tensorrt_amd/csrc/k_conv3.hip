@@ -435,6 +435,10 @@ int conv3_tiles(const GemmParams& p) {   // workgroups (pooling partials) per im
     return ((Wo + Conv3Cfg::TW - 1) / Conv3Cfg::TW) * ((Ho + Conv3Cfg::TH - 1) / Conv3Cfg::TH);
 }
 
+// Limits: what it accepts, conv3_kernel can address.  B >= 1; the Ho + 2 x Wo + 2 input pixels behind a NON-NEGATIVE origin lie inside the input view (the kernel
+// forms a tile's base pointer from the origin and reads forward from it through a bounds-checked resource, so a negative origin would read the previous image's
+// rows); the output view holds Ho x Wo pixels and has NO origin of its own (the epilogue stores at (oy, ox) of the view and never looks at out.y0 / out.x0 - every
+// plan has them zero); an output image and HR + 1 input rows stay below 2^31 bytes (32-bit offsets inside an image; the image bases are size_t).
 bool conv3_supported(const GemmParams& p) {
     if (switches().no_conv3 || p.a_scale || p.res_scale || !p.wt_perm || p.amode != 2 || p.kh != 3 || p.kw != 3 || p.stride != 1 || p.omode != 0 || p.ln || (p.act != 0 && p.act != 1) ||
         p.has_clip || p.stats_out || p.res.p || p.res2.p) return false;
@@ -442,6 +446,7 @@ bool conv3_supported(const GemmParams& p) {
     const int Cin = p.a.Cs;
     if (p.K != 9 * Cin || p.Kw != p.K || Cin % 32 || p.out.Cs != p.N || p.aW <= 0 || p.Mrows % p.aW) return false;
     const int Ho = p.Mrows / p.aW, Wo = p.aW;
+    if (p.B <= 0 || Ho <= 0 || p.a.y0 < 0 || p.a.x0 < 0 || p.out.y0 || p.out.x0) return false;
     if (p.a.y0 + Ho + 2 > p.a.Hs || p.a.x0 + Wo + 2 > p.a.Ws || p.out.Hs < Ho || p.out.Ws < Wo) return false;
     if ((size_t)p.out.Hs * p.out.Ws * p.out.Cs * 2 > 0x7FFFFFFFull || (size_t)(Conv3Cfg::HR + 1) * p.a.Ws * Cin * 2 > 0x7FFFFFFFull) return false;   // 32-bit offsets
     // pooling partials: one per workgroup; the plan sized the buffer for ceil(Mrows / kGemmBM) row tiles per image
@@ -478,6 +483,7 @@ hipError_t launch_conv3(const GemmParams& p, hipStream_t s) { return launch_conv
 bool conv3_stem_supported(const GemmParams& p, const GemmParams& ps) {
     if (switches().no_fuse_stem || !conv3_supported(p) || !stem_supported(ps) || p.pool_out || p.a.Cs != 32 || p.N != 64 || ps.N != 32 || ps.out.Cs != 32 || p.a.p != ps.out.p || ps.out.y0 || ps.out.x0) return false;
     const int Hs_o = ps.Mrows / ps.aW, Ws_o = ps.aW, Ho = p.Mrows / p.aW, Wo = p.aW;
+    if ((size_t)ps.a.Hs * ps.a.Ws * 8 > 0x7FFFFFFFull) return false;     // the halo stage addresses an image of the network's input with 32-bit byte offsets
     return p.a.Hs == ps.out.Hs && p.a.Ws == ps.out.Ws && p.a.y0 >= 0 && p.a.x0 >= 0 && p.a.y0 + Ho + 2 <= Hs_o && p.a.x0 + Wo + 2 <= Ws_o && p.B == ps.B;
 }
 

@@ -320,6 +320,9 @@ hipError_t launch_c3h_walk(const GemmParams& p, int Ho, int Wo, hipStream_t s) {
 
 }  // namespace
 
+// Rows mode stores all 4 halves of a pixel whatever N is (N <= 4; the heads have N = 3): a channel past N has zero weights and zero bias - the weight rows >= N and the
+// bias entries >= N are never read -, so it holds clip(act(0) + res[..., c]) = clip(res[..., c]), and exactly 0 without a skip map (gemm_kernel stores the same;
+// tests/test_gpu_cunet_kernels.py asserts it).
 bool conv3h_supported(const GemmParams& p) {
     if (switches().no_conv3h || p.a_scale || p.res_scale || p.amode != 2 || p.kh != 3 || p.kw != 3 || p.stride != 1 || p.ln || (p.act != 0 && p.act != 1) || p.stats_out || p.pool_out || p.res2.p) return false;
     const int Cin = p.a.Cs;

@@ -637,14 +637,21 @@ hipError_t launch_merge(const GemmParams& p, hipStream_t s) {
 }  // namespace
 
 // true if this launch can take the streaming kernel (everything else stays on gemm_kernel)
+// Limits: what it accepts, every kernel here can address.  The 2 x 2 stride-2 branch - merge_kernel (96 | 192 -> 192) and merge_slab_kernel (cunet's 64 -> 64,
+// 128 -> 128) alike - takes an input pass of less than 0xFFFF0000 bytes (all B images together), so merge_kernel's 32-bit byte offsets and merge_slab_kernel's
+// int row offset counted in halves (< 2^31) cannot wrap, and every 2 x 2 patch lies inside the input view behind a non-negative origin.  The pixel-shuffle branch
+// holds each of its three maps (rows, output, skip) under the same byte limit, every sub-pixel inside the output view and every skip pixel inside the skip view.
+// A pass past a limit is refused here and runs on launch_gemm, which cuts it into runs of whole images.  B >= 1.  LeakyReLU takes any slope: every kernel here selects
+// v > 0 ? v : v * alpha (unlike k_conv3.hip's max(v, v * alpha), which needs 0 <= alpha <= 1).
 bool pixgemm_supported(const GemmParams& p) {
     const bool off = switches().no_pixgemm;   // reference path (switches.h)
+    if (p.B <= 0) return false;               // (an empty pass would be a launch of zero workgroups: an error, not a no-op)
     if ((p.a_scale || p.res_scale) && p.a.Cs != 64 && p.a.Cs != 128) return false;   // gated operands: compiled into cunet's shapes only (PixCfg / MergeCfg GATES)
     if (!off && p.wt_frag && p.amode == 2 && p.kh == 2 && p.kw == 2 && p.stride == 2 && p.omode == 0 && !p.ln && (p.act == 0 || p.act == 1) && !p.has_clip &&
         !p.stats_out && !p.pool_out && !p.res.p && !p.res2.p && p.out.Cs == p.N && p.Kw == p.K && p.K == 4 * p.a.Cs && (long)p.out.Hs * p.out.Ws == p.Mrows && p.out.Ws == p.aW &&
         p.a.y0 >= 0 && p.a.x0 >= 0 && p.a.y0 + 2 * p.out.Hs <= p.a.Hs && p.a.x0 + 2 * p.out.Ws <= p.a.Ws &&   // every 2x2 patch inside the input view
-        (((p.a.Cs == 96 || p.a.Cs == 192) && p.N == 192 && (size_t)p.B * p.a.Hs * p.a.Ws * p.a.Cs * 2 < 0xFFFF0000u) ||   // (merge_kernel reads its map through 32-bit offsets)
-         (p.a.Cs == 64 && p.N == 64) || (p.a.Cs == 128 && p.N == 128))) return true;   // patch merge / cunet down convolution
+        (size_t)p.B * p.a.Hs * p.a.Ws * p.a.Cs * 2 < 0xFFFF0000u &&   // (merge_kernel reads its map through 32-bit byte offsets; merge_slab_kernel keeps a row's offset as an int counted in halves)
+        (((p.a.Cs == 96 || p.a.Cs == 192) && p.N == 192) || (p.a.Cs == 64 && p.N == 64) || (p.a.Cs == 128 && p.N == 128))) return true;   // patch merge / cunet down convolution
     // rows = a Linear, or a 1x1 convolution: cunet's 2x2 stride-2 ConvTranspose is lowered to 1x1 + pixel shuffle with LeakyReLU and a
     // cropped skip add (K = 64 / 128)
     const bool rows = p.amode == 0 || (p.amode == 2 && p.kh == 1 && p.kw == 1);
@@ -663,6 +670,17 @@ bool pixgemm_supported(const GemmParams& p) {
     }
     if ((p.K == 64 && p.out.Cs == 64) || (p.K == 128 && p.out.Cs == 128)) return true;
     return (p.K == 192 && (p.out.Cs == 96 || p.out.Cs == 192));
+}
+
+// rows of a pass that one workgroup of the kernel launch_pixgemm picks for `p` owns (output pixels for the 2 x 2 branch); 0: no kernel.  For tests that straddle it.
+int pixgemm_rows_per_workgroup(const GemmParams& p) {
+    if (p.amode == 2 && p.kh == 2) return p.a.Cs == 64 || p.a.Cs == 128 ? 128 : p.a.Cs == 96 ? 4 * MergeCfg<96, 192, 192>::RW : 4 * MergeCfg<192, 192, 192>::RW;
+    if (p.out.Cs == 4) return 256;
+    if (p.K == 192 && p.out.Cs == 96) return PixCfg<192, 96, 2>::BM;
+    if (p.K == 192 && p.out.Cs == 192) return PixCfg<192, 192, 2, W2X_PIX192_TT>::BM;
+    if (p.K == 64 && p.out.Cs == 64) return PixCfg<64, 64, 2>::BM;
+    if (p.K == 128 && p.out.Cs == 128) return PixCfg<128, 128, 2, 1>::BM;
+    return 0;
 }
 
 hipError_t launch_pixgemm(const GemmParams& p, hipStream_t s) {

@@ -757,7 +757,10 @@ hipError_t launch_compose_yuv(const ComposeYuvParams& p, hipStream_t s, const Di
     if (d.mode == kDitherNone) return launch_compose_yuv_mode<kDitherNone>(p, s);
     return for_dither(d, [&](auto m) { return launch_compose_yuv_mode<decltype(m)::value>(p, s, d); });
 }
+// (nblocks must be the partials per image the producer wrote: conv3_tiles(p) behind launch_conv3, ceil(Mrows / kGemmBM) behind launch_gemm - se_kernel reads
+// pool[b * nblocks + t], the producers write by global tile index)
 hipError_t launch_se(const SeParams& p, hipStream_t s) {
+    if (p.B <= 0 || p.C <= 0 || p.C > 256 || p.Cs < p.C || p.Cmid <= 0 || p.nblocks <= 0) return hipErrorInvalidValue;
     const int threads = 1024, slices = threads / p.C > 0 ? threads / p.C : 1;
     hipLaunchKernelGGL(se_kernel, dim3(p.B), dim3(threads), (p.C + p.Cmid + slices * p.C) * sizeof(float), s, p);
     return hipGetLastError();

@@ -202,6 +202,7 @@ struct ComposeParams {
 hipError_t launch_gemm(const GemmParams& p, hipStream_t s);
 bool pixgemm_supported(const GemmParams& p);                    // k_pixgemm.hip: streaming kernel for pixel-shuffle projections
 hipError_t launch_pixgemm(const GemmParams& p, hipStream_t s);
+int pixgemm_rows_per_workgroup(const GemmParams& p);            // rows (2 x 2 branch: output pixels) per workgroup of the kernel launch_pixgemm picks; 0: none
 bool conv3_supported(const GemmParams& p);                      // k_conv3.hip: LDS-tiled direct 3x3 convolution
 // k_stem.hip: first 3x3 convolution on the 4-halves-per-pixel input tile (no LDS, weights in registers)
 bool stem_supported(const GemmParams& p);
