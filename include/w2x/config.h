@@ -22,6 +22,10 @@ enum class Precision { TF32, FP16, FP32 };
 // the plan from the same ONNX file for a shape inside the range that is not the opt shape.
 // Extension: the filter of Img2Img::renderResized (an antialiased downsample of the network's output): bicubic (a = -0.5) or bilinear (triangle)
 enum class ResizeFilter { Bicubic, Bilinear };
+// Extension: the light the resize of renderResized and its siblings averages in (Img2Img::setResizeLight).  Gamma: the encoded values as they are
+// (the default, and the engine's behaviour before the setting existed).  LinearSrgb / LinearBt709: the canvas is decoded by the sRGB (IEC 61966-2-1) or the
+// BT.709 / BT.2020 transfer curve, resized in linear light and encoded again ahead of everything else the output path does.
+enum class ResizeLight { Gamma = 0, LinearSrgb = 1, LinearBt709 = 2 };
 
 struct BuildConfig {
     int deviceId = 0;                                             // HIP device ordinal

@@ -217,6 +217,14 @@ public:
     // the plane indices 0, 1, 2, a chroma sample takes the coordinates of its own plane, NV12 / P010 those of the I420 samples they are.
     bool setDither(const DitherOptions& options);
     DitherOptions dither() const;
+    // Extension: resize in linear light (config.h ResizeLight).  With LinearSrgb / LinearBt709 every following resized frame - render*Resized, the
+    // resized sequences, every frame format - is L = decode(sat01(canvas)) per colour sample, the same resize of L, and V = encode(sat01(L')) where the kernels
+    // otherwise clamp; quantisation, dither, packing, the Y'CbCr matrix and the chroma-site filters follow on V.  Alpha is coverage: never decoded, never encoded,
+    // its bytes do not depend on the setting.  Float destinations hold V.  A resized call at the scaled size stays the plain call (no round trip).  A setting
+    // of the engine like setDither: allowed before load(), kept across calls and loads, read by the very next frame; an unknown mode: false (message
+    // callback), the previous setting stays.  Gamma, the default, is the engine that never heard of the setting: the same kernels, the same bytes.
+    bool setResizeLight(ResizeLight mode);
+    ResizeLight resizeLight() const;
     void setMessageCallback(MessageCallback callback);   // img2img.h:21
     void setProgressCallback(ProgressCallback callback); // img2img.h:22
 
@@ -232,6 +240,11 @@ public:
     // by the device function the compose and resample kernels store through, with the current setDither() options (None: sat(rint(V))), the planes of dst (8, 10,
     // 12 or 16 bits, the size of src) down.  Plane k has plane index k.  No network, no tiles.
     bool ditherPlanes(const PlanarImage& src, PlanarImage& dst);
+    // Test hook: the resize of a resized frame alone - the three fp32 planes of src are taken as the canvas and go the production way: the decode of
+    // the canvas kernels (their device function in a kernel of its own; Gamma: nothing), resample_planes_kernel, the store, under the current setResizeLight()
+    // and setDither() settings, into the planes of dst (8 .. 16 bits or float; its size the target: between a quarter of src's and src's per axis).  No network,
+    // no tiles.
+    bool resizePlanes(const PlanarImage& src, PlanarImage& dst, ResizeFilter filter = ResizeFilter::Bicubic);
     int outputTileSize() const;
     int scaling() const;   // RenderConfig::scaling of the loaded configuration (0 before load)
     double planFlops() const;

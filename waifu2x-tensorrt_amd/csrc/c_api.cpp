@@ -3,6 +3,7 @@
 #include "../../include/w2x/c_api_dither.h"
 #include "../../include/w2x/c_api_gray.h"
 #include "../../include/w2x/c_api_planar.h"
+#include "../../include/w2x/c_api_resize_light.h"
 #include "../../include/w2x/c_api_rgbap.h"
 #include "../../include/w2x/c_api_yuv_resized.h"
 #include "../../include/w2x/c_api_yuv_siting.h"
@@ -455,6 +456,20 @@ int w2x_dither_planes(w2x_engine* e, const void* const* src_planes, const size_t
     if (!e) return 0;
     w2x::PlanarImage d = planar_image(dst_planes, dst_steps, rows, cols, bits);
     return e->engine.ditherPlanes(planar_image(src_planes, src_steps, rows, cols, 32), d) ? 1 : 0;
+}
+// resize in linear light (include/w2x/c_api_resize_light.h)
+int w2x_set_resize_light(w2x_engine* e, int mode) { return e && e->engine.setResizeLight((w2x::ResizeLight)mode) ? 1 : 0; }   // (the engine refuses unknown modes)
+int w2x_get_resize_light(const w2x_engine* e) { return e ? (int)e->engine.resizeLight() : -1; }
+static float light_clamped(float v) { return !(v >= 0.f) ? 0.f : (v > 1.f ? 1.f : v); }
+float w2x_light_decode(int mode, float v) { return w2x::light_mode_ok(mode) ? w2x::light_decode(w2x::light_args(mode), light_clamped(v)) : NAN; }
+float w2x_light_encode(int mode, float v) { return w2x::light_mode_ok(mode) ? w2x::light_encode(w2x::light_args(mode), light_clamped(v)) : NAN; }
+int w2x_resize_planes(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols,
+                      void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int bits, int filter) {
+    if (!e) return 0;
+    w2x::ResizeFilter f;
+    if (!resize_filter(e, filter, "resizePlanes", f)) return 0;
+    w2x::PlanarImage d = planar_image(dst_planes, dst_steps, dst_rows, dst_cols, bits);
+    return e->engine.resizePlanes(planar_image(src_planes, src_steps, rows, cols, 32), d, f) ? 1 : 0;
 }
 void* w2x_alloc_host(w2x_engine* e, size_t bytes) { return e ? e->engine.allocHost(bytes) : nullptr; }
 void w2x_free_host(w2x_engine* e, void* data) { if (e) e->engine.freeHost(data); }

@@ -1,5 +1,6 @@
 #include "args.h"
 #include "imageio.h"
+#include "../light.h"
 
 #include <algorithm>
 #include <cmath>
@@ -69,6 +70,9 @@ std::string usage() {
            "      --outsize WxH           (extension) every output exactly W x H; each input w x h needs w <= W <= w x --scale, h <= H <= h x --scale\n"
            "                              (the two factors independent); works with --colorspace: YUV frames are resized on the GPU before they are encoded\n"
            "      --resize-filter TEXT [bicubic]  (extension) {bicubic,bilinear}: the antialiasing filter of --outscale / --outsize\n"
+           "      --resize-light TEXT [gamma]  (extension) {gamma,srgb,bt709}: the light --outscale / --outsize average in - gamma: the encoded values as they are;\n"
+           "                              srgb, bt709: the frame is decoded by that transfer curve, resized in linear light and encoded again (thin lines and fine\n"
+           "                              texture keep their brightness).  Alpha is never touched.  Every route that takes --outscale / --outsize honours it\n"
            "      --colorspace TEXT       (extension) {bt601,bt709,bt2020}: videos read through ffmpeg stay YUV 4:2:0 at --pix_fmt\n"
            "                              (yuv420p or yuv420p10le) and are converted on the GPU; the output carries the colour tags\n"
            "      --color_range TEXT [tv] (extension) {tv,pc}: the range of the --colorspace frames\n"
@@ -126,7 +130,7 @@ int rgba_format_bits(const std::string& name) {
 Options parse(int argc, const char* const* argv) {
     Options o;
     std::vector<std::string> a(argv + 1, argv + argc);
-    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_outsize = false, seen_filter = false, seen_colorspace = false, seen_range = false, seen_bleed = false, seen_skip = false, seen_pixfmt = false, seen_gray = false, seen_dither = false;
+    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_outsize = false, seen_filter = false, seen_colorspace = false, seen_range = false, seen_bleed = false, seen_skip = false, seen_pixfmt = false, seen_gray = false, seen_dither = false, seen_light = false;
     auto value = [&](size_t& i) -> std::string {
         const std::string name = a[i];
         auto eq = name.find('=');
@@ -182,6 +186,7 @@ Options parse(int argc, const char* const* argv) {
         else if (k == "--gray") { o.gray = true; seen_gray = true; }
         else if (k == "--dither") { o.dither = value(i); std::transform(o.dither.begin(), o.dither.end(), o.dither.begin(), ::tolower); seen_dither = true; }
         else if (k == "--dither-temporal") { o.ditherTemporal = true; seen_dither = true; }
+        else if (k == "--resize-light") { o.resizeLight = value(i); std::transform(o.resizeLight.begin(), o.resizeLight.end(), o.resizeLight.begin(), ::tolower); seen_light = true; }
         else if (k == "--resize-filter") { o.resizeFilter = value(i); std::transform(o.resizeFilter.begin(), o.resizeFilter.end(), o.resizeFilter.begin(), ::tolower); seen_filter = true; }
         else if (k == "--colorspace") { o.colorspace = value(i); std::transform(o.colorspace.begin(), o.colorspace.end(), o.colorspace.begin(), ::tolower); seen_colorspace = true; }
         else if (k == "--color_range") { o.colorRange = value(i); std::transform(o.colorRange.begin(), o.colorRange.end(), o.colorRange.begin(), ::tolower); seen_range = true; }
@@ -240,6 +245,11 @@ Options parse(int argc, const char* const* argv) {
                 for (const auto& p : o.inputs)
                     if (!std::filesystem::is_directory(p) && is_builtin_still(p)) throw std::runtime_error("--outsize: a still over --devices " + std::to_string(o.devices) + " is not supported: " + p);
         } else if (seen_filter) throw std::runtime_error("--resize-filter: needs --outscale or --outsize");
+        if (seen_light) {                                                 // (a setting of the resize like the filter: every route that resizes honours it)
+            if (!seen_outscale && !seen_outsize) throw std::runtime_error("--resize-light: needs --outscale or --outsize");
+            int light_mode = 0;
+            if (!light_parse_mode(o.resizeLight.c_str(), light_mode)) member<std::string>("--resize-light", o.resizeLight, {"gamma", "srgb", "bt709"});
+        }
         if (seen_outscale && seen_outsize) throw std::runtime_error("--outsize: not together with --outscale (one of a factor and a size)");
         if (seen_colorspace) {
             member<std::string>("--colorspace", o.colorspace, {"bt601", "bt709", "bt2020"});
@@ -288,6 +298,7 @@ Options parse(int argc, const char* const* argv) {
             if (o.alphaBleed > 0 && o.deep) throw std::runtime_error("--alpha-bleed: not together with --deep (the bleed works on 8-bit colour; 16-bit stills keep the colours as stored)");
         }
     } else if (seen_dither) throw std::runtime_error(std::string(o.ditherTemporal ? "--dither-temporal" : "--dither") + ": only with render");
+    else if (seen_light) throw std::runtime_error("--resize-light: only with render");
     else if (seen_gray) throw std::runtime_error("--gray: only with render");
     else if (seen_rgb_in || seen_rgb_out) throw std::runtime_error(std::string(seen_rgb_in ? "--rgb-in" : "--rgb-out") + ": only with render");
     else if (seen_rgba_in || seen_rgba_out) throw std::runtime_error(std::string(seen_rgba_in ? "--rgba-in" : "--rgba-out") + ": only with render");
@@ -341,7 +352,7 @@ std::string to_json(const Options& o) {
        << ", \"precision\": " << q(o.precision) << ", \"recursive\": " << (o.recursive ? "true" : "false") << ", \"output\": " << q(o.output)
        << ", \"nosuffix\": " << (o.nosuffix ? "true" : "false") << ", \"blend\": " << o.blend << ", \"tta\": " << (o.tta ? "true" : "false") << ", \"tta_mode\": " << q(o.ttaMode)
        << ", \"outscale\": " << (o.outscale > 0 ? std::to_string(o.outscale) : std::string("null")) << ", \"outsize\": " << (o.outsizeW > 0 ? "[" + std::to_string(o.outsizeW) + ", " + std::to_string(o.outsizeH) + "]" : std::string("null"))
-       << ", \"resize_filter\": " << q(o.resizeFilter)
+       << ", \"resize_filter\": " << q(o.resizeFilter) << ", \"resize_light\": " << q(o.resizeLight)
        << ", \"colorspace\": " << (o.colorspace.empty() ? std::string("null") : q(o.colorspace)) << ", \"color_range\": " << q(o.colorRange)
        << ", \"chroma_loc\": " << (o.chromaLoc.empty() ? std::string("null") : q(o.chromaLoc))
        << ", \"yuv_in\": " << (o.yuvIn.empty() ? std::string("null") : q(o.yuvIn)) << ", \"yuv_out\": " << (o.yuvOut.empty() ? std::string("null") : q(o.yuvOut))

@@ -249,8 +249,11 @@ int main(int argc, char** argv) {
         DitherOptions ditherOptions;
         ditherOptions.mode = o.dither == "ordered" ? Dither::Ordered : o.dither == "bluenoise" ? Dither::BlueNoise : Dither::None;
         ditherOptions.advance = o.ditherTemporal ? 1u : 0u;
+        // --resize-light: a setting of the engines likewise - every route below that resizes (--outscale / --outsize) averages in that light.  Alpha is coverage
+        // and is neither dithered nor decoded: dither_on(false) puts both settings back to their defaults around the alpha plane's own frame.
+        const ResizeLight light = o.resizeLight == "srgb" ? ResizeLight::LinearSrgb : o.resizeLight == "bt709" ? ResizeLight::LinearBt709 : ResizeLight::Gamma;
         auto dither_on = [&](bool on) {
-            for (auto& e : engines) if (!e->setDither(on ? ditherOptions : DitherOptions())) return false;
+            for (auto& e : engines) if (!e->setDither(on ? ditherOptions : DitherOptions()) || !e->setResizeLight(on ? light : ResizeLight::Gamma)) return false;
             return true;
         };
         if (!dither_on(true)) return -1;

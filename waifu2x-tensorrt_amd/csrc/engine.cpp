@@ -348,6 +348,11 @@ struct Img2Img::Impl {
         }
         return dither_args(mode, dither.phase + seq_frame * dither.advance, mode == kDitherBlueNoise ? d_noise : nullptr);
     }
+    // Resize in linear light (setResizeLight): an engine-wide setting like the dither, read by the two launches that end a resized frame - the canvas
+    // compose decodes, the resample encodes - through light_now().  Nothing else reads it: a frame that is not resized (job.rs null, the scaled size included)
+    // never passes through the curves.
+    ResizeLight light = ResizeLight::Gamma;
+    LightArgs light_now() const { return light_args((int)light); }
     Job job;
     struct JobScope { Impl* im; ~JobScope() { im->job = Job{}; } };
     std::vector<void*> pinned;
@@ -1215,17 +1220,17 @@ struct Img2Img::Impl {
             case Job::RGBA: case Job::PLANAR_RGBA: {                  // (the same four fp32 planes)
                 ComposeCanvasRgbaParams p;
                 p.c = cp; p.alpha_tiles = alpha_tiles(); p.canvas = d_canvas;
-                hipAssert(launch_compose_canvas_rgba(p, on));
+                hipAssert(launch_compose_canvas_rgba(p, on, light_now()));
                 break;
             }
-            case Job::GRAY: hipAssert(launch_compose_canvas_gray(cp, d_canvas, on)); break;
-            default: hipAssert(launch_compose_canvas(cp, d_canvas, on));
+            case Job::GRAY: hipAssert(launch_compose_canvas_gray(cp, d_canvas, on, light_now())); break;
+            default: hipAssert(launch_compose_canvas(cp, d_canvas, on, light_now()));
         }
     }
-    template <class P> void resample_into(P& p, hipStream_t on, hipError_t (*launch)(const P&, hipStream_t, const DitherArgs&)) {
+    template <class P> void resample_into(P& p, hipStream_t on, hipError_t (*launch)(const P&, hipStream_t, const DitherArgs&, const LightArgs&)) {
         resample_base(p);
         p.dst = d_out; p.dst_step = frame_step(p.outW, true);
-        hipAssert(launch(p, on, dither_now()));
+        hipAssert(launch(p, on, dither_now(), light_now()));
     }
     void resample(hipStream_t on) {
         switch (job.kind) {
@@ -1235,7 +1240,7 @@ struct Img2Img::Impl {
                 ResamplePlanarParams p;
                 resample_base(p);
                 p.dst = frame_planes(d_out, p.outH, p.outW, true);
-                hipAssert(launch_resample_planar(p, on, dither_now()));
+                hipAssert(launch_resample_planar(p, on, dither_now(), light_now()));
                 break;
             }
             case Job::PLANAR_RGBA: {                                  // the four planes of the target size
@@ -1243,14 +1248,14 @@ struct Img2Img::Impl {
                 resample_base(p);
                 p.dst = rgba_planes(d_out, p.outH, p.outW, true);
                 p.uniform = job.rgba.uniform ? 1 : 0; p.alpha_value = uniform_alpha();
-                hipAssert(launch_resample_planar_rgba(p, on, dither_now()));
+                hipAssert(launch_resample_planar_rgba(p, on, dither_now(), light_now()));
                 break;
             }
             case Job::YUV: {                                          // the planes of job.yuv.out_layout at the target size
                 ResampleYuvParams p;
                 resample_base(p);
                 p.dst = yuv_layout(d_out, p.outH, p.outW, job.yuv.out_bits, job.yuv.out_layout); p.dst.siting = job.yuv.out_siting; p.k = job.yuv.out;
-                hipAssert(launch_resample_yuv(p, job.rs->rows_max_above, on, dither_now()));
+                hipAssert(launch_resample_yuv(p, job.rs->rows_max_above, on, dither_now(), light_now()));
                 break;
             }
         }
@@ -2138,6 +2143,7 @@ bool Img2Img::renderSharded(Img2Img* const* engines, int count, const Image& src
                 c.overlapY != c0.overlapY || c.tta != c0.tta || c.ttaBugCompat != c0.ttaBugCompat || c.batchSize != c0.batchSize) {
                 W2X_LOG(error, "renderSharded: engine " + std::to_string(k) + " was loaded with another model or configuration."); return false;
             }
+            if (a.light != impl->light) { W2X_LOG(error, "renderSharded: engine " + std::to_string(k) + " has another resize-light setting."); return false; }
             if (a.dither.mode != impl->dither.mode || a.dither.phase != impl->dither.phase || a.dither.advance != impl->dither.advance) {
                 W2X_LOG(error, "renderSharded: engine " + std::to_string(k) + " has another dither setting."); return false;
             }
@@ -2558,6 +2564,52 @@ bool Img2Img::ditherPlanes(const PlanarImage& src, PlanarImage& dst) {
     }
     hipAssert(launch_dither_planes(a, b, impl->dither_now(), impl->stream));
     for (int k = 0; k < 3; ++k) hipAssert(hipMemcpy2DAsync(dst.planes[k], dst.steps[k], b.p[k], out_step, out_width, rows, hipMemcpyDeviceToHost, impl->stream));
+    hipAssert(hipStreamSynchronize(impl->stream));
+    return true;
+    });
+}
+
+bool Img2Img::setResizeLight(ResizeLight mode) {
+    if (!light_mode_ok((int)mode)) { W2X_LOG(error, "Unknown resize light " + std::to_string((int)mode) + ": expected gamma, srgb or bt709."); return false; }
+    impl->light = mode;
+    return true;
+}
+ResizeLight Img2Img::resizeLight() const { return impl->light; }
+
+bool Img2Img::resizePlanes(const PlanarImage& src, PlanarImage& dst, ResizeFilter filter) {
+    const char* who = "resizePlanes";
+    return impl->entry(who, "Resize planes called before a successful load.", "Resize planes failed unexpectedly: ",
+                       [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
+    const int rows = src.rows, cols = src.cols, out_rows = dst.rows, out_cols = dst.cols, bits = dst.bits;
+    if (src.bits != 32 || !planar_bits_ok(bits)) { W2X_LOG_AS(who, error, "Resize planes take float (32-bit) planes and give planes of 8, 10, 12, 16 or 32 bits."); return false; }
+    if (rows <= 0 || cols <= 0) { W2X_LOG_AS(who, error, "Input image is empty."); return false; }
+    if (filter != ResizeFilter::Bicubic && filter != ResizeFilter::Bilinear) { W2X_LOG_AS(who, error, "Unknown resize filter."); return false; }
+    // a downscale by 1 to 4 per axis, the range the resize kernels' LDS is sized for (kResampleRows rows of a tile reach at most 4 x as many input rows plus the taps)
+    if (out_rows <= 0 || out_cols <= 0 || out_rows > rows || out_cols > cols || (long)out_rows * 4 < rows || (long)out_cols * 4 < cols) {
+        W2X_LOG_AS(who, error, "Output image has invalid size for a resize: " + std::to_string(out_cols) + "x" + std::to_string(out_rows) + " is not between a quarter of " +
+                   std::to_string(cols) + "x" + std::to_string(rows) + " and it."); return false;
+    }
+    const size_t bps = planar_sample_bytes(bits), in_width = (size_t)cols * 4, out_width = (size_t)out_cols * bps;
+    for (int k = 0; k < 3; ++k) {
+        if (!src.planes[k] || src.steps[k] < in_width || ((((size_t)src.planes[k]) | src.steps[k]) & 3) != 0) { W2X_LOG_AS(who, error, "Input image has a missing plane or an invalid step."); return false; }
+        if (!dst.planes[k] || dst.steps[k] < out_width || ((((size_t)dst.planes[k]) | dst.steps[k]) & (bps - 1)) != 0) { W2X_LOG_AS(who, error, "Output image has a missing plane or an invalid step."); return false; }
+    }
+    impl->last_rows = impl->last_cols = 0;   // (d_out is overwritten: the last render() frame is no longer there to replay)
+    const Impl::ResizeTables* const rs = impl->resize_tables(cols, rows, out_cols, out_rows, (int)filter);
+    const size_t plane = (size_t)rows * cols, out_step = Impl::planar_step(out_cols, bits);
+    impl->ensure_canvas(3 * plane * sizeof(float));
+    impl->ensure(impl->d_out, impl->out_cap, 3 * out_step * out_rows);
+    for (int k = 0; k < 3; ++k)
+        hipAssert(hipMemcpy2DAsync(impl->d_canvas + (size_t)k * plane, in_width, src.planes[k], src.steps[k], in_width, rows, hipMemcpyHostToDevice, impl->stream));
+    const LightArgs light = impl->light_now();
+    hipAssert(launch_light_decode_planes(impl->d_canvas, 3 * plane, light, impl->stream));
+    ResamplePlanarParams p;
+    p.canvas = impl->d_canvas; p.inW = cols; p.inH = rows; p.outW = out_cols; p.outH = out_rows;
+    p.fx = rs->fx; p.wx = rs->wx; p.kx = rs->kx; p.fy = rs->fy; p.wy = rs->wy; p.ky = rs->ky; p.rows_max = rs->rows_max;
+    p.dst.rows = out_rows; p.dst.cols = out_cols; p.dst.n = 3; p.dst.bits = bits;
+    for (int k = 0; k < 3; ++k) { p.dst.p[k] = impl->d_out + (size_t)k * out_step * out_rows; p.dst.step[k] = out_step; }
+    hipAssert(launch_resample_planar(p, impl->stream, impl->dither_now(), light));
+    for (int k = 0; k < 3; ++k) hipAssert(hipMemcpy2DAsync(dst.planes[k], dst.steps[k], p.dst.p[k], out_step, out_width, out_rows, hipMemcpyDeviceToHost, impl->stream));
     hipAssert(hipStreamSynchronize(impl->stream));
     return true;
     });

@@ -68,14 +68,16 @@ __global__ __launch_bounds__(kComposeThreads) void compose_planes_kernel(const C
 
 // compose_canvas_kernel's mapping (a thread per pixel along a row, a workgroup row per canvas row) writing the green sums alone: the plane compose_canvas_kernel
 // puts at canvas[1] for the frame B = G = R
-template <typename P>
-__global__ __launch_bounds__(256) void compose_canvas_gray_kernel(const ComposeParams p, float* canvas) {
+// L: empty - the kernel above -, or one LightArgs: the plane holds decode(sat01(g))
+template <typename P, typename... L>
+__global__ __launch_bounds__(256) void compose_canvas_gray_kernel(const ComposeParams p, float* canvas, const L... ls) {
+    static_assert(dither_pack_ok<kDitherNone, L...>, "no argument, or one LightArgs");
     const int X = blockIdx.x * 256 + threadIdx.x;
     if (X >= p.outW) return;
     for (int Y = blockIdx.y; Y < p.outH; Y += gridDim.y) {
         float r, g, b;
         compose_pixel_sums<P>(p, (const P*)p.tiles, X, Y, r, g, b);
-        canvas[(size_t)Y * p.outW + X] = g;
+        canvas[(size_t)Y * p.outW + X] = light_canvas<light_on<L...>>(light_of(ls...), g);
     }
 }
 
@@ -83,8 +85,10 @@ __global__ __launch_bounds__(256) void compose_canvas_gray_kernel(const ComposeP
 // taps), NP = 1: 19.5 KiB.
 template <typename S, int NP, int M = kDitherNone, typename... D>
 __global__ __launch_bounds__(kRsThreads) void resample_planes_kernel(const ResamplePlanarParams p, float scale, int maxcode, const D... dzs) {
-    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no DitherArgs, else one; then one LightArgs or none");
     const DitherArgs& dz = dither_of(dzs...);
+    constexpr bool kLin = light_on<D...>;                                 // 
+    const LightArgs& lz = light_of(dzs...);
     extern __shared__ float h[];
     const int r0 = resample_pass1<NP>(p, h);
     __syncthreads();
@@ -93,7 +97,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_planes_kernel(const Resam
     if (!resample_pass2<NP>(p, h, r0, a, X, Y, np)) return;
 #pragma unroll
     for (int c = 0; c < NP; ++c) {
-        const float v[4] = {a[c][0], a[c][1], a[c][2], a[c][3]};
+        const float v[4] = {light_out<kLin>(lz, a[c][0]), light_out<kLin>(lz, a[c][1]), light_out<kLin>(lz, a[c][2]), light_out<kLin>(lz, a[c][3])};
         store4<S, M>(p.dst.p[c] + (size_t)Y * p.dst.step[c], X, np, v, scale, maxcode, dz, NP == 1 ? 1 : c, Y);
     }
 }
@@ -153,15 +157,20 @@ hipError_t launch_compose_planar(const ComposePlanarParams& p, hipStream_t s, co
         return hipGetLastError();
     });
 }
-hipError_t launch_compose_canvas_gray(const ComposeParams& p, float* canvas, hipStream_t s) {
+hipError_t launch_compose_canvas_gray(const ComposeParams& p, float* canvas, hipStream_t s, const LightArgs& l) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
-    if (!canvas) return hipErrorInvalidValue;
+    if (!canvas || !light_args_ok(l)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((p.outW + 255) / 256), (unsigned)(p.outH < 65535 ? p.outH : 65535));
+    if (l.mode != kLightGamma) {
+        if (p.fp32) hipLaunchKernelGGL((compose_canvas_gray_kernel<float4v, LightArgs>), grid, dim3(256), 0, s, p, canvas, l);
+        else hipLaunchKernelGGL((compose_canvas_gray_kernel<half4, LightArgs>), grid, dim3(256), 0, s, p, canvas, l);
+        return hipGetLastError();
+    }
     if (p.fp32) hipLaunchKernelGGL(compose_canvas_gray_kernel<float4v>, grid, dim3(256), 0, s, p, canvas);
     else hipLaunchKernelGGL(compose_canvas_gray_kernel<half4>, grid, dim3(256), 0, s, p, canvas);
     return hipGetLastError();
 }
-hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s, const DitherArgs& d) {
+hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s, const DitherArgs& d, const LightArgs& l) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
     if (!p.canvas || !planes_ok(p.dst, p.outH, p.outW) || !dither_args_ok(d)) return hipErrorInvalidValue;
     const int maxcode = max_code(p.dst.bits);
@@ -169,15 +178,12 @@ hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s, 
     return for_planes(p.dst, [&](auto k) {
         typedef typename decltype(k)::Sample S;
         constexpr int NP = decltype(k)::kPlanes;
-        if constexpr (!std::is_same<S, F32>::value) {
-            if (d.mode != kDitherNone) return for_dither(d, [&](auto m) {
-                constexpr int M = decltype(m)::value;
-                static unsigned lds_dither = 0;
-                return launch_resample_tiles(resample_planes_kernel<S, NP, M, DitherArgs>, NP * kRsCols, p.rows_max, lds_dither, p.outW, p.outH, s, p, scale, maxcode, d);
-            });
-        }
-        static unsigned lds_done = 0;                                    // (one per instantiation of this lambda's body)
-        return launch_resample_tiles(resample_planes_kernel<S, NP>, NP * kRsCols, p.rows_max, lds_done, p.outW, p.outH, s, p, scale, maxcode);
+        auto go = [&](auto m, const auto&... extra) {
+            static unsigned lds_done = 0;                                // (one per instantiation of this lambda's body)
+            return launch_resample_tiles(resample_planes_kernel<S, NP, decltype(m)::value, std::decay_t<decltype(extra)>...>, NP * kRsCols, p.rows_max, lds_done, p.outW, p.outH, s, p, scale, maxcode, extra...);
+        };
+        if constexpr (std::is_same<S, F32>::value) return for_light(l, go);   // (float samples are never dithered: no such kernels)
+        else return for_modes(d, l, go);
     });
 }
 

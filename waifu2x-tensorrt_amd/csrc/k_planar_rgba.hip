@@ -227,7 +227,7 @@ __global__ __launch_bounds__(kComposeThreads) void compose_planes_rgba_kernel(co
 // a factor of 4 with bicubic taps 78 KiB (NP = 3: 58.5 KiB), resample_rgba_kernel's.
 template <typename S, int NP, int M = kDitherNone, typename... D>
 __global__ __launch_bounds__(kRsThreads) void resample_planes_rgba_kernel(const ResamplePlanarRgbaParams p, float scale, int maxcode, const D... dzs) {
-    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no DitherArgs, else one; then one LightArgs or none");
     const DitherArgs& dz = dither_of(dzs...);
     extern __shared__ float rsp_lds[];
     const int r0 = resample_pass1<NP>(p, rsp_lds);
@@ -235,6 +235,13 @@ __global__ __launch_bounds__(kRsThreads) void resample_planes_rgba_kernel(const 
     float4v a[NP];
     int X, Y, np;
     if (!resample_pass2<NP>(p, rsp_lds, r0, a, X, Y, np)) return;
+    if constexpr (light_on<D...>) {                                       // (the colour planes are encoded, plane 3 - alpha - is not)
+        const LightArgs& lz = light_of(dzs...);
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) a[c][q] = light_out<true>(lz, a[c][q]);
+    }
 #pragma unroll
     for (int c = 0; c < NP; ++c) {
         const float v[4] = {a[c][0], a[c][1], a[c][2], a[c][3]};
@@ -315,24 +322,21 @@ hipError_t launch_compose_planar_rgba(const ComposePlanarRgbaParams& p, hipStrea
         return hipGetLastError();
     });
 }
-hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStream_t s, const DitherArgs& d) {
+hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStream_t s, const DitherArgs& d, const LightArgs& l) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
     if (!p.canvas || !rgba_planes_ok(p.dst, p.outH, p.outW) || !dither_args_ok(d)) return hipErrorInvalidValue;
     const int maxcode = max_code(p.dst.bits);
     const float scale = (float)maxcode;
     return for_sample(p.dst.bits, [&](auto k) {
         typedef decltype(k) S;
-        if constexpr (!std::is_same<S, F32>::value) {
-            if (d.mode != kDitherNone) return for_dither(d, [&](auto m) {
-                constexpr int M = decltype(m)::value;
-                static unsigned lds_dither[2] = {0, 0};
-                if (p.uniform) return launch_resample_tiles(resample_planes_rgba_kernel<S, 3, M, DitherArgs>, 3 * kRsCols, p.rows_max, lds_dither[0], p.outW, p.outH, s, p, scale, maxcode, d);
-                return launch_resample_tiles(resample_planes_rgba_kernel<S, 4, M, DitherArgs>, 4 * kRsCols, p.rows_max, lds_dither[1], p.outW, p.outH, s, p, scale, maxcode, d);
-            });
-        }
-        static unsigned lds_done[2] = {0, 0};                            // (a pair per instantiation of this lambda's body)
-        if (p.uniform) return launch_resample_tiles(resample_planes_rgba_kernel<S, 3>, 3 * kRsCols, p.rows_max, lds_done[0], p.outW, p.outH, s, p, scale, maxcode);
-        return launch_resample_tiles(resample_planes_rgba_kernel<S, 4>, 4 * kRsCols, p.rows_max, lds_done[1], p.outW, p.outH, s, p, scale, maxcode);
+        auto go = [&](auto m, const auto&... extra) {
+            constexpr int M = decltype(m)::value;
+            static unsigned lds_done[2] = {0, 0};                        // (a pair per instantiation of this lambda's body)
+            if (p.uniform) return launch_resample_tiles(resample_planes_rgba_kernel<S, 3, M, std::decay_t<decltype(extra)>...>, 3 * kRsCols, p.rows_max, lds_done[0], p.outW, p.outH, s, p, scale, maxcode, extra...);
+            return launch_resample_tiles(resample_planes_rgba_kernel<S, 4, M, std::decay_t<decltype(extra)>...>, 4 * kRsCols, p.rows_max, lds_done[1], p.outW, p.outH, s, p, scale, maxcode, extra...);
+        };
+        if constexpr (std::is_same<S, F32>::value) return for_light(l, go);   // (float samples are never dithered: no such kernels)
+        else return for_modes(d, l, go);
     });
 }
 

@@ -165,8 +165,13 @@ __global__ __launch_bounds__(kComposeThreads) void compose_kernel(const ComposeP
 
 // The canvas of a resized frame (renderResized): compose_pixel_sums for every pixel of the rect, unquantised, as three fp32 planes.  A thread
 // per pixel along a row (the plane stores of a wave are 256 contiguous bytes each), a workgroup row per canvas row.
-template <typename P>
-__global__ __launch_bounds__(256) void compose_canvas_kernel(const ComposeParams p, float* canvas) {
+// L: empty - the kernel above -, or one LightArgs: the planes hold decode(sat01(sum)), linear light, for the resize to average.  This is where a
+// decode costs one evaluation per canvas pixel and not one per tap.
+template <typename P, typename... L>
+__global__ __launch_bounds__(256) void compose_canvas_kernel(const ComposeParams p, float* canvas, const L... ls) {
+    static_assert(dither_pack_ok<kDitherNone, L...>, "no argument, or one LightArgs");
+    constexpr bool kLin = light_on<L...>;
+    const LightArgs& lz = light_of(ls...);
     const int x1 = p.x1 > 0 ? p.x1 : p.outW, y1 = p.y1 > 0 ? p.y1 : p.outH;
     const int X = p.x0 + blockIdx.x * 256 + threadIdx.x;
     if (X >= x1) return;
@@ -175,7 +180,7 @@ __global__ __launch_bounds__(256) void compose_canvas_kernel(const ComposeParams
         float r, g, b;
         compose_pixel_sums<P>(p, (const P*)p.tiles, X, Y, r, g, b);
         const size_t i = (size_t)Y * p.outW + X;
-        canvas[i] = r; canvas[plane + i] = g; canvas[2 * plane + i] = b;
+        canvas[i] = light_canvas<kLin>(lz, r); canvas[plane + i] = light_canvas<kLin>(lz, g); canvas[2 * plane + i] = light_canvas<kLin>(lz, b);
     }
 }
 
@@ -653,10 +658,16 @@ hipError_t launch_compose(const ComposeParams& p, hipStream_t s, const DitherArg
     else hipLaunchKernelGGL(compose_kernel<half4>, grid, dim3(kComposeThreads), 0, s, p);
     return hipGetLastError();
 }
-hipError_t launch_compose_canvas(const ComposeParams& p, float* canvas, hipStream_t s) {
+hipError_t launch_compose_canvas(const ComposeParams& p, float* canvas, hipStream_t s, const LightArgs& l) {
     const int w = (p.x1 > 0 ? p.x1 : p.outW) - p.x0, h = (p.y1 > 0 ? p.y1 : p.outH) - p.y0;
     if (w <= 0 || h <= 0) return hipSuccess;
+    if (!light_args_ok(l)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((w + 255) / 256), (unsigned)(h < 65535 ? h : 65535));
+    if (l.mode != kLightGamma) {
+        if (p.fp32) hipLaunchKernelGGL((compose_canvas_kernel<float4v, LightArgs>), grid, dim3(256), 0, s, p, canvas, l);
+        else hipLaunchKernelGGL((compose_canvas_kernel<half4, LightArgs>), grid, dim3(256), 0, s, p, canvas, l);
+        return hipGetLastError();
+    }
     if (p.fp32) hipLaunchKernelGGL(compose_canvas_kernel<float4v>, grid, dim3(256), 0, s, p, canvas);
     else hipLaunchKernelGGL(compose_canvas_kernel<half4>, grid, dim3(256), 0, s, p, canvas);
     return hipGetLastError();

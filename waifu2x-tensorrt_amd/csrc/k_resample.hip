@@ -20,14 +20,22 @@ namespace {
 // the channels r, g, b are the plane indices 0, 1, 2.
 template <int M = kDitherNone, typename... D>
 __global__ __launch_bounds__(kRsThreads) void resample_kernel(const ResampleParams p, const D... dzs) {
-    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no DitherArgs, else one; then one LightArgs or none");
     const DitherArgs& dz = dither_of(dzs...);
+    constexpr bool kLin = light_on<D...>;                                 // (the resized values are linear light and are encoded before they are quantised)
+    const LightArgs& lz = light_of(dzs...);
     extern __shared__ float h[];                                          // [3][rows_max][kRsCols]
     const int r0 = resample_pass1<3>(p, h);
     __syncthreads();
     float4v a[3];                                                         // R, G, B of four pixels
     int X, Y, np;
     if (!resample_pass2<3>(p, h, r0, a, X, Y, np)) return;
+    if constexpr (kLin) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) a[c][q] = light_out<true>(lz, a[c][q]);
+    }
     uint8_t* d = p.dst + (size_t)Y * p.dst_step;
     if (!p.deep) {
         d += (size_t)X * 3;
@@ -79,15 +87,12 @@ int resample_rows_max(const int* fy, int outH, int inH, int ky, int rows_above) 
     return m;
 }
 
-hipError_t launch_resample(const ResampleParams& p, hipStream_t s, const DitherArgs& d) {
+hipError_t launch_resample(const ResampleParams& p, hipStream_t s, const DitherArgs& d, const LightArgs& l) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
-    if (!dither_args_ok(d)) return hipErrorInvalidValue;
-    if (d.mode != kDitherNone) return for_dither(d, [&](auto m) {
-        static unsigned lds_dither = 0;
-        return launch_resample_tiles(resample_kernel<decltype(m)::value, DitherArgs>, 3 * kRsCols, p.rows_max, lds_dither, p.outW, p.outH, s, p, d);
+    return for_modes(d, l, [&](auto m, const auto&... extra) {
+        static unsigned lds_done = 0;                                    // (one per instantiation of this lambda's body)
+        return launch_resample_tiles(resample_kernel<decltype(m)::value, std::decay_t<decltype(extra)>...>, 3 * kRsCols, p.rows_max, lds_done, p.outW, p.outH, s, p, extra...);
     });
-    static unsigned lds_done = 0;
-    return launch_resample_tiles(resample_kernel<>, 3 * kRsCols, p.rows_max, lds_done, p.outW, p.outH, s, p);
 }
 
 }  // namespace w2x

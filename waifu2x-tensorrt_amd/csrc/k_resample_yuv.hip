@@ -63,8 +63,10 @@ __device__ __forceinline__ void store_codes4(uint8_t* row, int X, int np, const 
 // ---- 4:4:4.  LDS [3][rows_max][kRsCols] fp32: resample_kernel's, 58.5 KiB at a factor of 4 with bicubic taps, two workgroups per CU
 template <int M = kDitherNone, typename... D>
 __global__ __launch_bounds__(kRsThreads) void resample_yuv444_kernel(const ResampleYuvParams p, const D... dzs) {
-    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no DitherArgs, else one; then one LightArgs or none");
     const DitherArgs& dz = dither_of(dzs...);
+    constexpr bool kLin = light_on<D...>;                                 // (R, G, B are encoded where they are clamped, ahead of the matrix)
+    const LightArgs& lz = light_of(dzs...);
     extern __shared__ float h[];
     const int r0 = resample_pass1<3>(p, h);
     __syncthreads();
@@ -75,7 +77,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv444_kernel(const Resam
     unsigned yc[4], uc[4], vc[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
-        const float o0 = sat01(a[0][q]), o1 = sat01(a[1][q]), o2 = sat01(a[2][q]);
+        const float o0 = sat01_out<kLin>(lz, a[0][q]), o1 = sat01_out<kLin>(lz, a[1][q]), o2 = sat01_out<kLin>(lz, a[2][q]);
         const float Yn = luma_of_row(k, Y, o0, o1, o2);
         yc[q] = yuv_code_at<M>(k.y_off, k.y_scale, Yn, k.maxcode, dz, 0, X + q, Y);
         uc[q] = yuv_code_at<M>(k.c_off, k.c_scale, chroma_of(o2, Yn, k.cb_div), k.maxcode, dz, 1, X + q, Y);
@@ -100,8 +102,10 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv444_kernel(const Resam
 // nothing crosses lanes before the stores.  (I422 has no row rule: kYuvTopLeft is kYuvLeft.)
 template <int S, int M = kDitherNone, typename... D>
 __global__ __launch_bounds__(kRsThreads) void resample_yuv422_kernel(const ResampleYuvParams p, const D... dzs) {
-    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no DitherArgs, else one; then one LightArgs or none");
     const DitherArgs& dz = dither_of(dzs...);
+    constexpr bool kLin = light_on<D...>;                                 // (every pixel, the halo column's included, is encoded before the site filter reads it)
+    const LightArgs& lz = light_of(dzs...);
     constexpr bool kLeftCol = S != kYuvCenter;
     extern __shared__ __attribute__((aligned(16))) float h422[];   // (the alignment stated: pass 2 reads 16 bytes per lane and plane, ds_read_b128)
     float* const h = h422;
@@ -139,7 +143,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv422_kernel(const Resam
 #pragma unroll
     for (int q = 0; q < 4; ++q)
 #pragma unroll
-        for (int e = 0; e < 3; ++e) o[q][e] = sat01(a[e][q]);
+        for (int e = 0; e < 3; ++e) o[q][e] = sat01_out<kLin>(lz, a[e][q]);
     unsigned yc[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) yc[q] = yuv_code_at<M>(k.y_off, k.y_scale, luma_of_row(k, Y, o[q][0], o[q][1], o[q][2]), k.maxcode, dz, 0, X + q, Y);
@@ -153,7 +157,7 @@ __global__ __launch_bounds__(kRsThreads) void resample_yuv422_kernel(const Resam
             if constexpr (kLeftCol) {
                 if (s == 0) {
                     const float from_left = __shfl_up(o[3][e], 1);        // (the lane on the left is of the same row for every cg > 0)
-                    left = cg ? from_left : sat01(hl[e]);
+                    left = cg ? from_left : sat01_out<kLin>(lz, hl[e]);
                 } else left = o[1][e];
             }
             const float right = 2 * s + 1 < np ? o[2 * s + 1][e] : o[2 * s][e];   // column 2j + 1 clamped to the frame (odd widths)
@@ -217,8 +221,10 @@ typedef float float2v __attribute__((ext_vector_type(2)));
 // columns itself (row -1 clamps to row 0), lanes 0 .. 4 of a wave the halo column of its five luma rows.  That is 3 vertical filters per thread where kYuvLeft
 // has 2; the horizontal pass, the kernel's larger part at 17 taps, grows by one output row's reach in 16.
 // LDS at a factor of 4 with bicubic taps: rows_max <= 82 (16 * 4 + 1 + 17), 3 * 82 * 66 * 4 B = 63.4 KiB - two workgroups per CU still fit the CU's 160 KiB.
-template <bool kNV12, int S = kYuvLeft, int M = kDitherNone>
-__device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, float* h, const DitherArgs& dz) {   // h: [3][rows_max][kYP], columns 0 .. 63 the tile's, 64 the halo
+// kLin: every resized pixel - the two or three rows of a site, the halo column's and the row halo's included - is encoded where it is clamped, so the
+// site filters, which are defined on encoded values, read V.
+template <bool kNV12, int S = kYuvLeft, int M = kDitherNone, bool kLin = false>
+__device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, float* h, const DitherArgs& dz, const LightArgs& lz) {   // h: [3][rows_max][kYP], columns 0 .. 63 the tile's, 64 the halo
     constexpr bool kLeftCol = S != kYuvCenter, kAbove = S == kYuvTopLeft;
     const int ox0 = blockIdx.x * kRsCols, oy0 = blockIdx.y * kRsRows;
     const int rm = p.rows_max;
@@ -262,8 +268,8 @@ __device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, floa
         float oa[2][3], ob[2][3];
 #pragma unroll
         for (int e = 0; e < 3; ++e) {
-            oa[0][e] = sat01(a[e][0]); oa[1][e] = sat01(a[e][1]);
-            ob[0][e] = has_b ? sat01(b[e][0]) : oa[0][e]; ob[1][e] = has_b ? sat01(b[e][1]) : oa[1][e];
+            oa[0][e] = sat01_out<kLin>(lz, a[e][0]); oa[1][e] = sat01_out<kLin>(lz, a[e][1]);
+            ob[0][e] = has_b ? sat01_out<kLin>(lz, b[e][0]) : oa[0][e]; ob[1][e] = has_b ? sat01_out<kLin>(lz, b[e][1]) : oa[1][e];
         }
 #pragma unroll
         for (int q = 0; q < 2; ++q) {
@@ -273,8 +279,8 @@ __device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, floa
 #pragma unroll
         for (int e = 0; e < 3; ++e) {
             if constexpr (kAbove) {
-                vl[e] = rows_cosited(sat01(z[e][0]), oa[0][e], ob[0][e]);
-                vr[e] = has_r ? rows_cosited(sat01(z[e][1]), oa[1][e], ob[1][e]) : vl[e];
+                vl[e] = rows_cosited(sat01_out<kLin>(lz, z[e][0]), oa[0][e], ob[0][e]);
+                vr[e] = has_r ? rows_cosited(sat01_out<kLin>(lz, z[e][1]), oa[1][e], ob[1][e]) : vl[e];
             } else {
                 vl[e] = __fmul_rn(0.5f, __fadd_rn(oa[0][e], ob[0][e]));
                 vr[e] = has_r ? __fmul_rn(0.5f, __fadd_rn(oa[1][e], ob[1][e])) : vl[e];
@@ -284,7 +290,7 @@ __device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, floa
     if constexpr (kAbove) {
 #pragma unroll
         for (int e = 0; e < 3; ++e) {                                     // the halo column of rows 2i - 1, 2i, 2i + 1: lanes 2 hw, 2 hw + 1, 2 hw + 2 of the wave
-            const float hc = sat01(halo[e]);
+            const float hc = sat01_out<kLin>(lz, halo[e]);
             const float hz = __shfl(hc, 2 * (lane / 32)), ha = __shfl(hc, 2 * (lane / 32) + 1), hb = __shfl(hc, 2 * (lane / 32) + 2);
             const float from_left = __shfl_up(vr[e], 1);
             left[e] = cj ? from_left : rows_cosited(hz, ha, has_b ? hb : ha);
@@ -292,7 +298,7 @@ __device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, floa
     } else if constexpr (kLeftCol) {
 #pragma unroll
         for (int e = 0; e < 3; ++e) {
-            const float hc = sat01(halo[e]);
+            const float hc = sat01_out<kLin>(lz, halo[e]);
             const float ha = __shfl(hc, 2 * (lane / 32)), hb = __shfl(hc, 2 * (lane / 32) + 1);
             const float from_left = __shfl_up(vr[e], 1);
             left[e] = cj ? from_left : __fmul_rn(0.5f, __fadd_rn(ha, has_b ? hb : ha));
@@ -365,30 +371,30 @@ __device__ __forceinline__ void resample_yuv420(const ResampleYuvParams& p, floa
 // M: kDitherNone - no further argument - is the kernel the undithered engine launches; a dithered mode takes its DitherArgs behind p (dither_of)
 template <int M = kDitherNone, typename... D>
 __global__ __launch_bounds__(kRsThreads) void resample_yuv_kernel(const ResampleYuvParams p, const D... dzs) {
-    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no DitherArgs, else one; then one LightArgs or none");
     extern __shared__ float h[];
-    resample_yuv420<false, kYuvLeft, M>(p, h, dither_of(dzs...));
+    resample_yuv420<false, kYuvLeft, M, light_on<D...>>(p, h, dither_of(dzs...), light_of(dzs...));
 }
 template <int M = kDitherNone, typename... D>
 __global__ __launch_bounds__(kRsThreads) void resample_yuv_nv12_kernel(const ResampleYuvParams p, const D... dzs) {
-    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no DitherArgs, else one; then one LightArgs or none");
     extern __shared__ float h[];
-    resample_yuv420<true, kYuvLeft, M>(p, h, dither_of(dzs...));
+    resample_yuv420<true, kYuvLeft, M, light_on<D...>>(p, h, dither_of(dzs...), light_of(dzs...));
 }
 // the other sitings of the pair
 template <bool kNV12, int S, int M = kDitherNone, typename... D>
 __global__ __launch_bounds__(kRsThreads) void resample_yuv_sited_kernel(const ResampleYuvParams p, const D... dzs) {
-    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no DitherArgs, else one; then one LightArgs or none");
     extern __shared__ float h[];
-    resample_yuv420<kNV12, S, M>(p, h, dither_of(dzs...));
+    resample_yuv420<kNV12, S, M, light_on<D...>>(p, h, dither_of(dzs...), light_of(dzs...));
 }
 
 }  // namespace
 
 // dst.layout picks the kernel.  The layouts beside I420 also ask for a canvas and for every plane of the layout, with a step that holds its row and 10-bit
 // planes at even addresses.
-hipError_t launch_resample_yuv(const ResampleYuvParams& params, int rows_max_above, hipStream_t s, const DitherArgs& d) {
-    if (!dither_args_ok(d)) return hipErrorInvalidValue;
+hipError_t launch_resample_yuv(const ResampleYuvParams& params, int rows_max_above, hipStream_t s, const DitherArgs& d, const LightArgs& l) {
+    if (!dither_args_ok(d) || !light_args_ok(l)) return hipErrorInvalidValue;
     ResampleYuvParams p = params;
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
     if (p.dst.rows != p.outH || p.dst.cols != p.outW || (p.dst.bits != 8 && p.dst.bits != 10)) return hipErrorInvalidValue;
@@ -405,7 +411,7 @@ hipError_t launch_resample_yuv(const ResampleYuvParams& params, int rows_max_abo
     // the siting the layout tells apart: I444 none, I422 the column rule alone
     if (p.dst.siting < kYuvLeft || p.dst.siting > kYuvTopLeft) return hipErrorInvalidValue;
     const int siting = layout == kYuvI444 || (layout == kYuvI422 && p.dst.siting == kYuvTopLeft) ? kYuvLeft : p.dst.siting;
-    // the kernels of mode M with their extra arguments dz (none, or the DitherArgs); the LDS opt-in masks are per instantiation of this body
+    // the kernels of mode M with their extra arguments dz (none, the DitherArgs, the LightArgs or both: for_modes); the LDS opt-in masks are per instantiation of this body
     auto go = [&](auto m, const auto&... dz) -> hipError_t {
         constexpr int M = decltype(m)::value;
         if (siting != kYuvLeft) {
@@ -432,8 +438,7 @@ hipError_t launch_resample_yuv(const ResampleYuvParams& params, int rows_max_abo
         if (rows_max_above < p.rows_max) return hipErrorInvalidValue;
         p.rows_max = rows_max_above;
     }
-    if (d.mode == kDitherNone) return go(std::integral_constant<int, kDitherNone>());
-    return for_dither(d, [&](auto m) { return go(m, d); });
+    return for_modes(d, l, go);
 }
 
 }  // namespace w2x

@@ -156,8 +156,12 @@ __global__ __launch_bounds__(256) void compose_rgba_kernel(const ComposeRgbaPara
 //
 // compose_canvas_kernel's thread and grid mapping (a thread per pixel along a row, a workgroup row per canvas row) over both tile sets: the unquantised sums
 // of the colour tiles as planes R, G, B and the green sum of the alpha tiles as plane A.
-template <typename P>
-__global__ __launch_bounds__(256) void compose_canvas_rgba_kernel(const ComposeCanvasRgbaParams p) {
+// L: empty - the kernel above -, or one LightArgs: the colour planes hold decode(sat01(sum)); plane A, coverage, is never decoded
+template <typename P, typename... L>
+__global__ __launch_bounds__(256) void compose_canvas_rgba_kernel(const ComposeCanvasRgbaParams p, const L... ls) {
+    static_assert(dither_pack_ok<kDitherNone, L...>, "no argument, or one LightArgs");
+    constexpr bool kLin = light_on<L...>;
+    const LightArgs& lz = light_of(ls...);
     const ComposeParams& c = p.c;
     const int X = blockIdx.x * 256 + threadIdx.x;
     if (X >= c.outW) return;
@@ -166,7 +170,7 @@ __global__ __launch_bounds__(256) void compose_canvas_rgba_kernel(const ComposeC
         float r, g, b;
         compose_pixel_sums<P>(c, (const P*)c.tiles, X, Y, r, g, b);
         const size_t i = (size_t)Y * c.outW + X;
-        p.canvas[i] = r; p.canvas[plane + i] = g; p.canvas[2 * plane + i] = b;
+        p.canvas[i] = light_canvas<kLin>(lz, r); p.canvas[plane + i] = light_canvas<kLin>(lz, g); p.canvas[2 * plane + i] = light_canvas<kLin>(lz, b);
         if (p.alpha_tiles) {
             compose_pixel_sums<P>(c, (const P*)p.alpha_tiles, X, Y, r, g, b);
             p.canvas[3 * plane + i] = g;
@@ -188,7 +192,7 @@ __global__ __launch_bounds__(256) void compose_canvas_rgba_kernel(const ComposeC
 // M: as above - colour dithered at (X + q, Y), alpha rounded to nearest.
 template <bool kAlpha, int M = kDitherNone, typename... D>
 __global__ __launch_bounds__(kRsThreads) void resample_rgba_kernel(const ResampleRgbaParams p, const D... dzs) {
-    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no argument; else one DitherArgs");
+    static_assert(dither_pack_ok<M, D...>, "kDitherNone: no DitherArgs, else one; then one LightArgs or none");
     const DitherArgs& dz = dither_of(dzs...);
     constexpr int NP = kAlpha ? 4 : 3;
     extern __shared__ float rs_lds[];
@@ -197,6 +201,13 @@ __global__ __launch_bounds__(kRsThreads) void resample_rgba_kernel(const Resampl
     float4v a[NP];
     int X, Y, np;
     if (!resample_pass2<NP>(p, rs_lds, r0, a, X, Y, np)) return;
+    if constexpr (light_on<D...>) {                                       // (the colour is encoded, alpha - a[3] - is not)
+        const LightArgs& lz = light_of(dzs...);
+#pragma unroll
+        for (int c = 0; c < 3; ++c)
+#pragma unroll
+            for (int q = 0; q < 4; ++q) a[c][q] = light_out<true>(lz, a[c][q]);
+    }
     unsigned px[4];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {                                         // b | g << 8 | r << 16 | a << 24
@@ -240,26 +251,28 @@ hipError_t launch_compose_rgba(const ComposeRgbaParams& p, hipStream_t s, const 
     else hipLaunchKernelGGL(compose_rgba_kernel<half4>, grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }
-hipError_t launch_compose_canvas_rgba(const ComposeCanvasRgbaParams& p, hipStream_t s) {
+hipError_t launch_compose_canvas_rgba(const ComposeCanvasRgbaParams& p, hipStream_t s, const LightArgs& l) {
     if (p.c.outW <= 0 || p.c.outH <= 0) return hipSuccess;
-    if (!p.canvas) return hipErrorInvalidValue;
+    if (!p.canvas || !light_args_ok(l)) return hipErrorInvalidValue;
     const dim3 grid((unsigned)((p.c.outW + 255) / 256), (unsigned)(p.c.outH < 65535 ? p.c.outH : 65535));
+    if (l.mode != kLightGamma) {
+        if (p.c.fp32) hipLaunchKernelGGL((compose_canvas_rgba_kernel<float4v, LightArgs>), grid, dim3(256), 0, s, p, l);
+        else hipLaunchKernelGGL((compose_canvas_rgba_kernel<half4, LightArgs>), grid, dim3(256), 0, s, p, l);
+        return hipGetLastError();
+    }
     if (p.c.fp32) hipLaunchKernelGGL(compose_canvas_rgba_kernel<float4v>, grid, dim3(256), 0, s, p);
     else hipLaunchKernelGGL(compose_canvas_rgba_kernel<half4>, grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }
-hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s, const DitherArgs& d) {
+hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s, const DitherArgs& d, const LightArgs& l) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
-    if ((p.dst_step & 3) || p.dst_step < (size_t)p.outW * 4 || (((size_t)p.dst) & 3) || !dither_args_ok(d)) return hipErrorInvalidValue;
-    if (d.mode != kDitherNone) return for_dither(d, [&](auto m) {
+    if ((p.dst_step & 3) || p.dst_step < (size_t)p.outW * 4 || (((size_t)p.dst) & 3)) return hipErrorInvalidValue;
+    return for_modes(d, l, [&](auto m, const auto&... extra) {
         constexpr int M = decltype(m)::value;
-        static unsigned lds_dither[2] = {0, 0};
-        if (p.uniform) return launch_resample_tiles(resample_rgba_kernel<false, M, DitherArgs>, 3 * kRsCols, p.rows_max, lds_dither[0], p.outW, p.outH, s, p, d);
-        return launch_resample_tiles(resample_rgba_kernel<true, M, DitherArgs>, 4 * kRsCols, p.rows_max, lds_dither[1], p.outW, p.outH, s, p, d);
+        static unsigned lds_done[2] = {0, 0};                            // (a pair per instantiation of this lambda's body)
+        if (p.uniform) return launch_resample_tiles(resample_rgba_kernel<false, M, std::decay_t<decltype(extra)>...>, 3 * kRsCols, p.rows_max, lds_done[0], p.outW, p.outH, s, p, extra...);
+        return launch_resample_tiles(resample_rgba_kernel<true, M, std::decay_t<decltype(extra)>...>, 4 * kRsCols, p.rows_max, lds_done[1], p.outW, p.outH, s, p, extra...);
     });
-    static unsigned lds_done[2] = {0, 0};
-    if (p.uniform) return launch_resample_tiles(resample_rgba_kernel<false>, 3 * kRsCols, p.rows_max, lds_done[0], p.outW, p.outH, s, p);
-    return launch_resample_tiles(resample_rgba_kernel<true>, 4 * kRsCols, p.rows_max, lds_done[1], p.outW, p.outH, s, p);
 }
 
 }  // namespace w2x

@@ -5,6 +5,7 @@
 #include "support.h"
 #include "switches.h"
 #include "dither.h"
+#include "light.h"
 #include <cstdint>
 
 namespace w2x {
@@ -276,13 +277,19 @@ const uint16_t* dither_table_device(hipError_t* err = nullptr);
 // dst (8 .. 16 bits) by the store of the compose / resample kernels (store4): V = v * (2^bits - 1), plane k with plane index k (one plane: 1)
 struct PlanarPlanes;
 hipError_t launch_dither_planes(const PlanarPlanes& src, const PlanarPlanes& dst, const DitherArgs& d, hipStream_t s);
+// Resize in linear light (light.h states the rule): LightArgs, the curve as data.  The canvas launchers (launch_compose_canvas*) and the resample
+// launchers take one as their last argument; mode Gamma - the default - launches the kernel of the engine that never heard of it, whose argument list and
+// instructions do not know about any of this.  A canvas launch decodes the colour planes (never the alpha plane), a resample launch encodes them.
+// k_light.hip light_decode_planes_kernel (test hook, Img2Img::resizePlanes): n fp32 values in place, v = decode(sat01(v)) by the device function the canvas
+// kernels call; mode Gamma: no launch
+hipError_t launch_light_decode_planes(float* v, size_t n, const LightArgs& l, hipStream_t s);
 hipError_t launch_se(const SeParams& p, hipStream_t s);
 hipError_t launch_scale(void* x, const float* scale, int B, int HW, int Cs, bool fp32, hipStream_t s);
 hipError_t launch_gather(const GatherParams& p, hipStream_t s);
 hipError_t launch_compose(const ComposeParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
 // k_prepost.hip compose_canvas_kernel: compose_kernel's per-pixel sums for the same rect of p (x0..x1, y0..y1; p.dst / p.deep unused) left
 // unquantised as fp32 RGB planes: canvas[c][Y][X], plane stride outW * outH (the input of the resize, renderResized)
-hipError_t launch_compose_canvas(const ComposeParams& p, float* canvas, hipStream_t s);
+hipError_t launch_compose_canvas(const ComposeParams& p, float* canvas, hipStream_t s, const LightArgs& l = LightArgs());
 // k_resample.hip resample_kernel: an antialiased separable resize of the fp32 RGB canvas (three planes of inH x inW) to outH x outW, quantised like
 // compose (sat(rint(x * 255)), 16-bit: 65535) and stored as BGR.  The tap tables (tiles.h resize_taps) live on the device: fx / wx per output column,
 // fy / wy per output row; rows_max = the input rows an output tile of kResampleRows rows reads at most (resample_rows_max).  Every resize kernel
@@ -306,7 +313,7 @@ constexpr int kResampleRows = 16, kResampleCols = 64;
 constexpr int kComposeRows = W2X_COMPOSE_ROWS, kComposeThreads = W2X_COMPOSE_THREADS;
 // host: the largest input row span of an output row tile; rows_above = 1: of the tile and the output row above it (top-left sited 4:2:0 chroma)
 int resample_rows_max(const int* fy, int outH, int inH, int ky, int rows_above = 0);
-hipError_t launch_resample(const ResampleParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
+hipError_t launch_resample(const ResampleParams& p, hipStream_t s, const DitherArgs& d = DitherArgs(), const LightArgs& l = LightArgs());
 // YUV 4:2:0 frames (Img2Img::renderYuv): three planes - Y of rows x cols, U and V of ceil(rows/2) x ceil(cols/2) - with 8-bit (uint8) or 10-bit
 // (uint16, low 10 bits) samples; steps in bytes.  Chroma siting (siting): kYuvLeft, MPEG-2 "left", chroma (i, j) at luma (x = 2j, y = 2i + 1/2);
 // kYuvCenter (JPEG, MPEG-1) at (2j + 1/2, 2i + 1/2); kYuvTopLeft (BT.2020) at (2j, 2i).  Per subsampled axis a siting is one of two rules, co-sited or centred:
@@ -424,7 +431,7 @@ struct ComposeCanvasRgbaParams {
     const void* alpha_tiles = nullptr;
     float* canvas = nullptr;
 };
-hipError_t launch_compose_canvas_rgba(const ComposeCanvasRgbaParams& p, hipStream_t s);
+hipError_t launch_compose_canvas_rgba(const ComposeCanvasRgbaParams& p, hipStream_t s, const LightArgs& l = LightArgs());
 // resample_rgba_kernel: resample_kernel's resize (same tap tables, same rows_max, same accumulation per plane) over the four planes of that canvas, each
 // quantised sat(rint(x * 255)) and stored as one dword B | G << 8 | R << 16 | A << 24 per pixel into dst (dst_step bytes per row, a multiple of 4).
 // uniform != 0: the canvas has three planes, none is filtered for alpha and A = alpha_value everywhere.
@@ -437,7 +444,7 @@ struct ResampleRgbaParams {
     int rows_max = 0;
     int uniform = 0; unsigned alpha_value = 255;
 };
-hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
+hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s, const DitherArgs& d = DitherArgs(), const LightArgs& l = LightArgs());
 // Frames of planes (k_planar.hip): `n` planes of rows x cols samples - uint8 (bits 8), little-endian uint16 with the code in the low bits (10 / 12 / 16) or
 // float32 of nominal [0, 1] (32) - each with its own pointer and step in bytes; u16 / f32 samples aligned to their size.  n = 3: planar RGB frames (renderPlanar,
 // DESIGN 9h), planes R, G, B.  n = 1: gray frames (renderGray) of 8 or 16 bits: one sample per pixel on both sides, the result the green channel of
@@ -468,7 +475,7 @@ struct ComposePlanarParams {
 hipError_t launch_compose_planar(const ComposePlanarParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
 // compose_canvas_gray_kernel: the green sums of compose_pixel_sums over the whole canvas of p (x0..y1, dst, deep unused) unquantised as one fp32 plane
 // canvas[Y][X] of outH x outW: the canvas of a resized gray frame (a resized planar frame has compose_canvas_kernel's)
-hipError_t launch_compose_canvas_gray(const ComposeParams& p, float* canvas, hipStream_t s);
+hipError_t launch_compose_canvas_gray(const ComposeParams& p, float* canvas, hipStream_t s, const LightArgs& l = LightArgs());
 // resample_planes_kernel: resample_kernel's resize (same tap tables, same rows_max, same accumulation) of the fp32 canvas of dst.n planes, the accumulators
 // quantised like compose_planes_kernel into the planes of dst (outH x outW)
 struct ResamplePlanarParams {
@@ -479,7 +486,7 @@ struct ResamplePlanarParams {
     int rows_max = 0;
     PlanarPlanes dst;
 };
-hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
+hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s, const DitherArgs& d = DitherArgs(), const LightArgs& l = LightArgs());
 // Planar RGBA frames (renderPlanarRgba; k_planar_rgba.hip): four planes R, G, B, A of one sample type, laid out like PlanarPlanes' three.
 struct RgbaPlanes {
     uint8_t* p[4] = {nullptr, nullptr, nullptr, nullptr}; size_t step[4] = {0, 0, 0, 0};
@@ -530,7 +537,7 @@ struct ResamplePlanarRgbaParams {
     RgbaPlanes dst;
     int uniform = 0; float alpha_value = 1.f;
 };
-hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
+hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStream_t s, const DitherArgs& d = DitherArgs(), const LightArgs& l = LightArgs());
 // k_resample_yuv.hip: resample_kernel's resize of the fp32 RGB canvas (same tap tables, same rows_max, the same two passes) with compose_yuv_kernel's
 // encoding behind it instead of the BGR quantisation: the resized R, G, B clamped to [0, 1] and written as the YUV planes of dst (outH x outW =
 // dst.rows x dst.cols), Y per pixel; 4:2:0: Cb / Cr of the RGB filtered (1/4, 1/2, 1/4) x (1/2, 1/2) onto each chroma site (renderYuvResized)
@@ -548,7 +555,7 @@ struct ResampleYuvParams {
 // rows_max_above: resample_rows_max(.., 1) of the same tables.  The launcher, which knows what the destination's siting dispatches, sizes the LDS and the kernel's
 // row pitch by it where the kernel reads the row above its tile (top-left sited I420 / NV12) and by p.rows_max everywhere else; a top-left launch
 // without it is an error, not a launch with too little LDS.
-hipError_t launch_resample_yuv(const ResampleYuvParams& p, int rows_max_above, hipStream_t s, const DitherArgs& d = DitherArgs());
+hipError_t launch_resample_yuv(const ResampleYuvParams& p, int rows_max_above, hipStream_t s, const DitherArgs& d = DitherArgs(), const LightArgs& l = LightArgs());
 // debug/test helpers used by w2x_infer (mirrors blobFromImages / imagesFromBlob, img2img_infer.cpp:5-39)
 hipError_t launch_blob_to_nhwc(const float* nchw, void* out_nhwc4, int B, int T, bool fp32, hipStream_t s);
 hipError_t launch_nhwc_to_blob(const void* in_nhwc4, float* nchw, int B, int T, bool fp32, hipStream_t s);

@@ -47,6 +47,21 @@ template <typename Launch> hipError_t for_dither(const DitherArgs& d, Launch lau
     return hipErrorInvalidValue;                                         // no kernel for it: an error, never the undithered kernel
 }
 
+// launch(std::integral_constant<int, M>(), extra...) for the dither mode of d and the light mode of l: extra... is what the kernel takes behind its
+// parameters - nothing, d, l, or d and l - and names the instantiation (kernel<.., M, std::decay_t<decltype(extra)>...>).  This is the one place where the two
+// engine-wide settings pick a resize kernel, for every frame format.  Invalid arguments: an error, never another kernel.
+// for_light: the same for a kernel that is never dithered (float samples).
+template <typename Launch> hipError_t for_light(const LightArgs& l, Launch launch) {
+    if (!light_args_ok(l)) return hipErrorInvalidValue;
+    return l.mode != kLightGamma ? launch(std::integral_constant<int, kDitherNone>(), l) : launch(std::integral_constant<int, kDitherNone>());
+}
+template <typename Launch> hipError_t for_modes(const DitherArgs& d, const LightArgs& l, Launch launch) {
+    if (!dither_args_ok(d) || !light_args_ok(l)) return hipErrorInvalidValue;
+    if (d.mode == kDitherNone) return for_light(l, launch);
+    const bool lin = l.mode != kLightGamma;
+    return for_dither(d, [&](auto m) { return lin ? launch(m, d, l) : launch(m, d); });
+}
+
 // ---- the sample types: what a plane holds per pixel.  `maxcode` is 2^bits - 1 and `inv` fl32(1 / maxcode), both made on the host (launch_*).
 struct U8 { typedef uint8_t T; };
 struct U16 { typedef uint16_t T; };
@@ -66,6 +81,11 @@ template <> __device__ __forceinline__ float load_sample<F32>(const uint8_t* row
 // argument - at 255 and 65535 the same product and the same rounding, which byte equality with the BGR kernels rests on.  Float: the sum clamped, never rounded.
 __device__ __forceinline__ unsigned quant(float v, float scale, int maxcode) { return (unsigned)min(max(__float2int_rn(v * scale), 0), maxcode); }
 __device__ __forceinline__ float sat01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
+// the clamp of the YUV resize kernels: sat01(v), or V = encode(sat01(v)) in a kernel whose launch carries a curve
+template <bool kLin> __device__ __forceinline__ float sat01_out(const LightArgs& c, float v) {
+    if constexpr (kLin) return light_encode(c, sat01(v));
+    else return sat01(v);
+}
 
 // Four consecutive samples of one plane's row, starting at column X (a multiple of 4): np == 4 and an aligned address leave as ONE store - a dword, 8 or 16
 // bytes -, the 1 - 3 samples of a ragged right end (or a caller's unaligned rows) one by one.  From the engine's buffers (hipMalloc, rows padded to 16 bytes:

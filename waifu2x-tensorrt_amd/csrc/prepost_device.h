@@ -3,6 +3,7 @@
 // lives here once and both files inline it.
 #pragma once
 #include "kernels.h"
+#include <tuple>
 #include <type_traits>
 
 namespace w2x {
@@ -58,9 +59,52 @@ __device__ __forceinline__ unsigned quantize_bgr(float r, float g, float b) {
 // loop counter of an unrolled loop wherever this is called: d.dx[c] / d.dy[c] are scalar registers.
 // A kernel templated on M ends its parameter list with a pack: empty for kDitherNone - the argument list, and so the kernarg offsets, of the undithered kernel -
 // and one DitherArgs for a dithered mode.  dither_of(dzs...) is that argument, or a default nobody reads.
+// Resize in linear light: the pack of a kernel that encodes may end in one LightArgs behind that - (), (DitherArgs), (LightArgs) or (DitherArgs,
+// LightArgs); light_on<D...> is the kernel's compile-time switch and light_of(dzs...) the curve, or a default nobody reads.
 __device__ __forceinline__ DitherArgs dither_of() { return DitherArgs(); }
 __device__ __forceinline__ const DitherArgs& dither_of(const DitherArgs& d) { return d; }
-template <int M, typename... D> constexpr bool dither_pack_ok = M == kDitherNone ? sizeof...(D) == 0 : (sizeof...(D) == 1 && (std::is_same<D, DitherArgs>::value && ...));
+__device__ __forceinline__ DitherArgs dither_of(const LightArgs&) { return DitherArgs(); }
+__device__ __forceinline__ const DitherArgs& dither_of(const DitherArgs& d, const LightArgs&) { return d; }
+__device__ __forceinline__ LightArgs light_of() { return LightArgs(); }
+__device__ __forceinline__ LightArgs light_of(const DitherArgs&) { return LightArgs(); }
+__device__ __forceinline__ const LightArgs& light_of(const LightArgs& l) { return l; }
+__device__ __forceinline__ const LightArgs& light_of(const DitherArgs&, const LightArgs& l) { return l; }
+template <typename... D> constexpr bool light_on = (std::is_same<D, LightArgs>::value || ...);
+template <int M, typename... D> constexpr bool dither_pack_ok =
+    sizeof...(D) == (M == kDitherNone ? 0 : 1) + (light_on<D...> ? 1 : 0) &&
+    (M == kDitherNone || std::is_same<std::tuple_element_t<0, std::tuple<D..., void>>, DitherArgs>::value) &&
+    (!light_on<D...> || std::is_same<std::tuple_element_t<sizeof...(D) == 0 ? 0 : sizeof...(D) - 1, std::tuple<D..., void>>, LightArgs>::value);
+// The two curve functions on the device (light.h states them and their roundings; the power goes through the hardware's log2 / exp2, v_log_f32 / v_exp_f32,
+// whose arguments here are never subnormal: the base of decode is at least 1 / (1 + a) > 0.9 a, the argument of encode's power at least t / k).  The curve is
+// data: both branches are computed and one is selected.  e and l are in [0, 1] - the callers clamp.  Contraction is off: every product and sum below is the
+// stated one.
+__device__ __forceinline__ float light_decode(const LightArgs& c, float e) {
+#pragma clang fp contract(off)
+    const float lin = __fmul_rn(e, c.inv_k);
+    const float base = __fmaf_rn(__fsub_rn(e, 1.f), c.inv_1a, 1.f);
+    const float pw = __builtin_amdgcn_exp2f(__fmul_rn(c.g, __builtin_amdgcn_logf(base)));
+    return e < c.t ? lin : pw;
+}
+__device__ __forceinline__ float light_encode(const LightArgs& c, float l) {
+#pragma clang fp contract(off)
+    const float lin = __fmul_rn(c.k, l);
+    const float p = __builtin_amdgcn_exp2f(__fmul_rn(c.inv_g, __builtin_amdgcn_logf(l)));
+    const float pw = __fmaf_rn(c.a, __fsub_rn(p, 1.f), p);
+    return l < c.tl ? lin : pw;
+}
+__device__ __forceinline__ float light_sat01(float v) { return fminf(fmaxf(v, 0.f), 1.f); }
+// the canvas value of a colour sum s: s itself, or decode(sat01(s)) where the launch carries a curve (kOn)
+template <bool kOn>
+__device__ __forceinline__ float light_canvas(const LightArgs& c, float s) {
+    if constexpr (kOn) return light_decode(c, light_sat01(s));
+    else return s;
+}
+// the resized value the store of an encoding kernel takes: encode(sat01(v)) (kOn; the stores clamp and quantise it as they do any value), else v untouched
+template <bool kOn>
+__device__ __forceinline__ float light_out(const LightArgs& c, float v) {
+    if constexpr (kOn) return light_encode(c, light_sat01(v));
+    else return v;
+}
 template <int M>
 __device__ __forceinline__ float dither_t(const DitherArgs& d, int c, int x, int y) {
     static_assert(M == kDitherOrdered || M == kDitherBlueNoise, "None adds nothing");

@@ -342,6 +342,16 @@ DITHER_SYMBOLS = {
     "w2x_dither_planes": (_I, [_P, _P, _P, _I, _I, _P, _P, _I]),
 }
 DITHER_MODES = {"none": 0, "ordered": 1, "bluenoise": 2}    # W2X_DITHER_NONE .. _BLUENOISE (include/w2x/c_api_dither.h)
+# The entries of include/w2x/c_api_resize_light.h, a table of their own likewise: (engine, mode), its getter, the two curve functions without an engine, and
+# the test hook (engine, src planes, src steps, rows, cols, dst planes, dst steps, dst rows, dst cols, bits, filter).
+RESIZE_LIGHT_SYMBOLS = {
+    "w2x_set_resize_light": (_I, [_P, _I]),
+    "w2x_get_resize_light": (_I, [_P]),
+    "w2x_light_decode": (C.c_float, [_I, C.c_float]),
+    "w2x_light_encode": (C.c_float, [_I, C.c_float]),
+    "w2x_resize_planes": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I]),
+}
+RESIZE_LIGHTS = {"gamma": 0, "srgb": 1, "bt709": 2}    # W2X_LIGHT_GAMMA .. _BT709 (include/w2x/c_api_resize_light.h)
 _lib = None
 
 
@@ -354,7 +364,7 @@ def lib():
         raise W2xError(f"{lib_path} is missing - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "or `make -C waifu2x-tensorrt_amd` (there is no CPU fallback)")
     L = C.CDLL(lib_path)
-    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()) + list(PLANAR_SYMBOLS.items()) + list(RGBAP_SYMBOLS.items()) + list(YUV_RESIZED_SYMBOLS.items()) + list(YUV_SITED_SYMBOLS.items()) + list(DITHER_SYMBOLS.items()):
+    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()) + list(PLANAR_SYMBOLS.items()) + list(RGBAP_SYMBOLS.items()) + list(YUV_RESIZED_SYMBOLS.items()) + list(YUV_SITED_SYMBOLS.items()) + list(DITHER_SYMBOLS.items()) + list(RESIZE_LIGHT_SYMBOLS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -789,6 +799,46 @@ class Img2Img:
         ok = self._L.w2x_dither_planes(self._h, (C.c_void_p * 3)(*[_data(p) for p in src]), (C.c_size_t * 3)(*[p.strides[0] for p in src]), r, c,
                                        (C.c_void_p * 3)(*[_data(p) for p in out]), (C.c_size_t * 3)(*[p.strides[0] for p in out]), bits)
         return self._finish(ok, out, "dither_planes failed")
+
+    def set_resize_light(self, mode="gamma") -> bool:
+        """The light every following resized frame is averaged in (w2x_set_resize_light, c_api_resize_light.h states the rule): "gamma" - the encoded values as
+        they are, the default -, "srgb" or "bt709" - the canvas decoded by that curve, resized in linear light and encoded again ahead of quantisation, dither
+        and the Y'CbCr matrix - or the mode's number, which the engine checks.  Alpha is never touched; a call at the scaled size stays the plain call.  The
+        setting stays until it is changed and may be made before load().  An unknown name raises ValueError; an unknown number returns False (message
+        callback) and leaves the previous setting."""
+        if isinstance(mode, str):
+            if mode not in RESIZE_LIGHTS:
+                raise ValueError(f"resize light must be one of {sorted(RESIZE_LIGHTS)}, got {mode!r}")
+            mode = RESIZE_LIGHTS[mode]
+        return bool(self._L.w2x_set_resize_light(self._h, int(mode)))
+
+    def resize_light(self) -> str:
+        """the current setting's name (w2x_get_resize_light)"""
+        return {v: k for k, v in RESIZE_LIGHTS.items()}[int(self._L.w2x_get_resize_light(self._h))]
+
+    def resize_planes(self, planes, size, bits: int, filter: str = "bicubic", dst=None):
+        """Test hook (w2x_resize_planes): three 2-D float32 planes of one shape (views with padded rows allowed) are taken as the canvas of a resized frame and
+        go the production way - the canvas kernels' decode, the planar resize kernel, its store - under the current set_resize_light() and set_dither()
+        settings -> three planes of size = (rows, cols) and `bits` (8: uint8; 10, 12, 16: uint16; 32: float32).  The target lies between a quarter of the
+        source size and the source size per axis.  dst: three pre-allocated planes of that shape and dtype (views allowed), which are returned."""
+        src = [np.asarray(p) for p in planes]
+        if len(src) != 3 or any(p.ndim != 2 or p.dtype != np.float32 or p.shape != src[0].shape or p.strides[1] != 4 for p in src):
+            raise ValueError("planes must be three 2-D float32 planes of one shape with packed samples")
+        bits = int(bits)
+        if bits not in PLANAR_DTYPES:
+            raise ValueError(f"bits must be one of {sorted(PLANAR_DTYPES)}, got {bits!r}")
+        if filter not in RESIZE_FILTERS:
+            raise ValueError(f"filter must be one of {sorted(RESIZE_FILTERS)}, got {filter!r}")
+        r, c = src[0].shape
+        orows, ocols = int(size[0]), int(size[1])
+        dt = np.dtype(PLANAR_DTYPES[bits])
+        out = tuple(np.empty((orows, ocols), dt) for _ in range(3)) if dst is None else tuple(dst)
+        if len(out) != 3 or any(p.ndim != 2 or p.dtype != dt or p.shape != (orows, ocols) or p.strides[1] != dt.itemsize for p in out):
+            raise ValueError(f"dst must be three 2-D {dt.name} planes of the target's shape with packed samples")
+        ok = self._L.w2x_resize_planes(self._h, (C.c_void_p * 3)(*[_data(p) for p in src]), (C.c_size_t * 3)(*[p.strides[0] for p in src]), r, c,
+                                       (C.c_void_p * 3)(*[_data(p) for p in out]), (C.c_size_t * 3)(*[p.strides[0] for p in out]), orows, ocols, bits,
+                                       RESIZE_FILTERS[filter])
+        return self._finish(ok, out, "resize_planes failed")
 
     def alpha_bleed_planes_device(self, planes, radius: int, *, bits: int | None = None, order: str = "rgba", words: bool = False):
         """Test hook (w2x_alpha_bleed_rgbap_device): the device bleed alone on a planar RGBA frame -> the three colour planes the tiles are read from, in R, G, B
@@ -1233,6 +1283,19 @@ def alpha_bleed_planes(planes, radius: int, *, bits: int | None = None, order: s
                                        int(radius), (C.c_void_p * 3)(*[_data(p) for p in out]), (C.c_size_t * 3)(*[p.strides[0] for p in out])):
         raise ValueError(f"alpha_bleed_planes refused planes of {src[0].shape} at radius {radius}")
     return out
+
+
+def light_decode(mode, v: float) -> float:
+    """The host statement of a curve's decode (w2x_light_decode): v clamped to [0, 1] -> linear light in the engine's fp32 arithmetic; mode a name of
+    RESIZE_LIGHTS or its number ("gamma": the clamped value); NaN for an unknown number."""
+    m = RESIZE_LIGHTS.get(mode, -1) if isinstance(mode, str) else int(mode)
+    return float(lib().w2x_light_decode(m, float(v)))
+
+
+def light_encode(mode, v: float) -> float:
+    """The host statement of a curve's encode (w2x_light_encode), likewise."""
+    m = RESIZE_LIGHTS.get(mode, -1) if isinstance(mode, str) else int(mode)
+    return float(lib().w2x_light_encode(m, float(v)))
 
 
 def dither_table(mode) -> np.ndarray:
