@@ -70,7 +70,7 @@ def test_other_graph_families_and_scales_byte_exact(pkg, onnx_model, model, scal
 
 @pytest.mark.parametrize("tta,batch", [(False, 3), (True, 4)])
 def test_render_call_in_pipelined_parts_returns_the_one_part_bytes(pkg, onnx_model, monkeypatch, tta, batch):
-    """render() runs a frame of >= 16 tiles as up to four PARTS (engine.cpp renderPart: contiguous tile ranges cut at whole reference batches, each
+    """render() runs a frame of >= 16 tiles as up to four PARTS (tiles.cpp render_parts, engine.cpp run_frame_in_parts: contiguous tile ranges cut at whole reference batches, each
     part's canvas cells composed and sent to the host while the next part computes; W2X_RENDER_PARTS, read at load).  Every part count must return
     the bytes of the one-part frame - which is the oracle's - for 8- and 16-bit frames, with TTA (a tile = 8 slots: the cut is a whole batch for
     any tile) and with a batch that does not divide the tile count."""
@@ -96,7 +96,7 @@ def test_render_pipelines_agree_on_random_frame_sizes(pkg, onnx_model, monkeypat
     """The machinery around a render() call - parts with a small last one, the upload split at the first part's columns, parts rolling into each other,
     one graph per tile group - against the plain path (one part, joins, W2X_RENDER_PARTS=1 W2X_NO_ROLLING=1) on seeded random frame sizes from one tile
     row to 130 tiles, 8- and 16-bit, each rendered twice (eager, then replayed) and followed by a resident replay: same bytes every time.  With TTA a
-    tile is eight slots, so a part boundary may fall on any tile."""
+    tile is eight slots, so a part boundary may fall on any tile.  (The cut of these sizes itself: tests/test_render_parts_host.py.)"""
     path = onnx_model("swin_unet/art", 4, batch, 64)
     rng = np.random.default_rng(2024 + batch)
     shapes = [(int(rng.integers(40, 520)), int(rng.integers(40, 640))) for _ in range(5 if tta else 10)] + [(48, 600), (600, 48), (199, 263)]

@@ -8,7 +8,10 @@
 //   w2x_parse_check image FILE [deep]               read_image, then write_image to /dev/null-like temp names in every format it allows
 //   w2x_parse_check avi   FILE                      AviReader::open + every frame
 //   w2x_parse_check args  ARGS...                   cli::parse
-//   w2x_parse_check tiles W H T S TOUT OVX OVY      calculate_tiles
+//   w2x_parse_check tiles W H T S TOUT OVX OVY      calculate_tiles, then strip_plan, shard_plans, tile_range_cells and render_parts over the grid
+//   w2x_parse_check parts W H T S TOUT OVX OVY [STEPS USERB B WANT]...   the grid, its tiles and its shard plans for 1-8 parts beside tile_range_cells of the same
+//                                                           ranges, then render_parts (tiles.h) of the whole frame per schedule: one line per case and per part;
+//                                                           tests/test_render_parts_host.py judges them
 //   w2x_parse_check bleed FILE RADIUS               read_image, then alpha_bleed of its colour under its alpha plane (an opaque plane without one), padded rows
 //   w2x_parse_check planes BITS ROWS COLS RADIUS SEED OUT   alpha_bleed_planes on a seeded frame of four planes of BITS (8, 10, 12, 16), padded rows; OUT receives
 //                                                           the four planes and the three bled ones, packed, for the test to compare with its own statement
@@ -40,7 +43,7 @@
 using namespace w2x;
 
 static int run(int argc, char** argv) {
-    if (argc < 3) throw std::runtime_error("usage: w2x_parse_check {onnx|plan|image|avi|args|tiles|bleed|planes|schedule|dither} ...");
+    if (argc < 3) throw std::runtime_error("usage: w2x_parse_check {onnx|plan|image|avi|args|tiles|parts|bleed|planes|schedule|dither} ...");
     const std::string mode = argv[1];
     if (mode == "onnx") {
         if (argc < 5) throw std::runtime_error("onnx FILE BATCH TILE [fp32]");
@@ -78,7 +81,47 @@ static int run(int argc, char** argv) {
         const int W = atoi(argv[2]), H = atoi(argv[3]), T = atoi(argv[4]), S = atoi(argv[5]), TO = atoi(argv[6]);
         const TileGrid g = calculate_tiles(W, H, W * S, H * S, T, T, TO, TO, S, atof(argv[7]), atof(argv[8]));
         for (int parts = 1; parts <= 8 && parts <= g.nx; ++parts) for (int p = 0; p < parts; ++p) (void)strip_plan(g, W * S, TO, p, parts);
+        // the shards, the cells of every tile range that begins at tile 0 or ends at the last, and the pipelined parts of the frame under a few schedules
+        std::vector<ShardPlan> plans;
+        for (int parts = 1; parts <= 8; ++parts) (void)shard_plans(g, W * S, H * S, TO, parts, plans);
+        Rect cells[3];
+        for (int t = 0; t <= g.count; ++t) { (void)tile_range_cells(g, W * S, H * S, TO, TO, 0, t, cells); (void)tile_range_cells(g, W * S, H * S, TO, TO, t, g.count, cells); }
+        if (g.count > 0)
+            for (int steps : {1, 8}) for (int userB = 1; userB <= 4; ++userB) for (int want = 1; want <= kMaxRenderParts + 1; ++want) {
+                const RenderParts rp = render_parts(g, strip_plan(g, W * S, TO, 0, 1), W, W * S, H * S, T, TO, steps, userB, 4 * userB, want);
+                (void)last_pass_live(rp.part[rp.n - 1].tiles, steps, 4 * userB);
+            }
         printf("ok: %d tiles (%d x %d)\n", g.count, g.nx, g.ny);
+    } else if (mode == "parts") {
+        if (argc < 9 || (argc - 9) % 4) throw std::runtime_error("parts W H T S TOUT OVX OVY [STEPS USERB B WANT]...");
+        const int W = atoi(argv[2]), H = atoi(argv[3]), T = atoi(argv[4]), S = atoi(argv[5]), TO = atoi(argv[6]);
+        const TileGrid g = calculate_tiles(W, H, W * S, H * S, T, T, TO, TO, S, atof(argv[7]), atof(argv[8]));
+        if (g.count <= 0) throw std::runtime_error("parts: the tile grid is empty");
+        auto rects = [](const Rect* r, int n) { std::string s; for (int k = 0; k < n; ++k) s += (k ? ";" : "") + std::to_string(r[k].x) + "," + std::to_string(r[k].y) + "," + std::to_string(r[k].w) + "," + std::to_string(r[k].h); return s.empty() ? std::string("-") : s; };
+        printf("grid nx=%d ny=%d count=%d ovx=%d ovy=%d\n", g.nx, g.ny, g.count, g.outOvX, g.outOvY);
+        for (int t = 0; t < g.count; ++t) printf("tile %d x=%d y=%d\n", t, g.in[t].x, g.in[t].y);
+        for (int parts = 1; parts <= 8; ++parts) {
+            std::vector<ShardPlan> plans;
+            const bool all = shard_plans(g, W * S, H * S, TO, parts, plans);
+            for (int p = 0; p < parts; ++p) {
+                Rect cells[3];
+                const int n = tile_range_cells(g, W * S, H * S, TO, TO, plans[p].first_tile, plans[p].first_tile + plans[p].tile_count, cells);
+                printf("shard parts=%d part=%d owned=%d first=%d tiles=%d halo=%zu plan=%s cells=%s\n", parts, p, all ? 1 : 0, plans[p].first_tile, plans[p].tile_count, halo_slots(plans[p], 1),
+                       rects(plans[p].rect, plans[p].nrect).c_str(), rects(cells, n).c_str());
+            }
+        }
+        const StripPlan whole = strip_plan(g, W * S, TO, 0, 1);
+        for (int a = 9; a + 3 < argc; a += 4) {
+            const int steps = atoi(argv[a]), userB = atoi(argv[a + 1]), B = atoi(argv[a + 2]), want = atoi(argv[a + 3]);
+            if ((steps != 1 && steps != 8) || userB <= 0 || B < userB || B > 4096) throw std::runtime_error("parts: STEPS is 1 or 8, 0 < USERB <= B <= 4096");
+            const RenderParts rp = render_parts(g, whole, W, W * S, H * S, T, TO, steps, userB, B, want);
+            printf("case steps=%d userB=%d B=%d want=%d parts=%d batches=%d slots=%zu x_split=%d slab=%zu\n", steps, userB, B, want, rp.n, rp.batch_total, rp.slot_total, rp.x_split, rp.slab_slots);
+            for (int k = 0; k < rp.n; ++k) {
+                const RenderParts::Part& p = rp.part[k];
+                printf("part %d first=%d tiles=%d batches=%d before=%d slots_off=%zu slots=%zu live=%d rects=%s\n", k, p.first, p.tiles, p.batches, p.batches_before, p.slots_off, p.slots,
+                       last_pass_live(p.tiles, steps, B), rects(p.rect, p.nrect).c_str());
+            }
+        }
     } else if (mode == "bleed") {
         if (argc < 4) throw std::runtime_error("bleed FILE RADIUS");
         const cli::Bitmap b = cli::read_image(argv[2]);

@@ -202,7 +202,6 @@ struct Img2Img::Impl {
     // W2X_ROCTX=1 (read at load): roctxRangePushA / roctxRangePop around the launches of every plan op, resolved from libroctx64.so at run time (no link dependency)
     int (*roctx_push)(const char*) = nullptr; int (*roctx_pop)() = nullptr;
     hipEvent_t ev_shard = nullptr;       // renderSharded(): this engine's tiles are in its slab
-    static constexpr int kMaxRenderParts = 4;
     hipEvent_t ev_part[kMaxRenderParts] = {nullptr, nullptr, nullptr, nullptr};
     int pipeline_parts = 3;              // W2X_RENDER_PARTS (read at load): parts a render() call runs a frame in (1 = one part; at most kMaxRenderParts)
     size_t shard_halo_slots = 0;         // renderSharded(): slab slots in front of this engine's own tiles (the bands copied from the preceding parts)
@@ -393,16 +392,9 @@ struct Img2Img::Impl {
         hipAssert(hipStreamSynchronize(stream));
         one_part_stale = false;
     }
-    // The step schedule of a frame's tiles (img2img_render.cpp:246-267): slot = step index, tile = step / stepsPerTile, aug = step % stepsPerTile, zero pad slots at
-    // the end.  batch_count(): the reference batches of `tiles` tiles (:249); pass_slots(): the slots of the whole network passes those batches round up to.
-    int batch_count(int tiles) const {
-        const int steps = cfg.tta ? 8 : 1;
-        return (int)std::lround(std::ceil((double)(tiles * steps) / plan.userB));
-    }
-    size_t pass_slots(int tiles) const {
-        const int S = plan.B / plan.userB;
-        return (size_t)((batch_count(tiles) + S - 1) / S) * plan.B;
-    }
+    // the step schedule of a frame's tiles (tiles.h) under this engine's plan and configuration
+    int batch_count(int tiles) const { return w2x::batch_count(tiles, cfg.tta ? 8 : 1, plan.userB); }
+    size_t pass_slots(int tiles) const { return w2x::pass_slots(tiles, cfg.tta ? 8 : 1, plan.userB, plan.B); }
     // h_slots[at, at + count): the steps of the tiles [first, first + tiles) of the grid, pad slots behind them.  `valid`: 1, or kSlotColour / kSlotAlpha (RGBA)
     void fill_slots(const TileGrid& grid, int first, int tiles, int valid, size_t at, size_t count) {
         const int steps = cfg.tta ? 8 : 1;
@@ -866,9 +858,7 @@ struct Img2Img::Impl {
     // events instead of stream order where a buffer comes round again (ev_cmp).  Same launches on the same data: the frames are the bytes of render().
     // Returns false when the frame cannot roll (a pass that does not split, profiling, one group): the caller then runs run_frame().
     bool can_roll(int tile_count) const {
-        const int steps = cfg.tta ? 8 : 1, B = plan.B;
-        const int last_live = tile_count * steps - (tile_count * steps - 1) / B * B;                    // live slots of the frame's last pass
-        return rolling_ok && groups == 2 && use_graphs && !profiling && !check_general && !poison && gstream[0] && last_live >= 8 && B % 2 == 0;
+        return rolling_ok && groups == 2 && use_graphs && !profiling && !check_general && !poison && gstream[0] && last_pass_live(tile_count, cfg.tta ? 8 : 1, plan.B) >= 8 && plan.B % 2 == 0;
     }
     void run_rolling_frame(int rows, int cols, const TileGrid& grid, const StripPlan& sp, int which, hipEvent_t out_free) {
         for (int k = 0; k < 2; ++k) {
@@ -906,6 +896,27 @@ struct Img2Img::Impl {
         drain_after_error();
         log(Severity::error, failed + std::string(e.what()) + ".", who, __LINE__);
         return false;
+    }
+
+    // The graphs of one pass into `pg`: run_pass() captured on the compute stream, or (per_group) run_group(c) on the stream of each of the `ngroups` tile groups,
+    // each instantiated.  Returns "" or the step that failed and the runtime's text; then `pg` holds the graphs made before it, for the caller to destroy.
+    template <class RunGroup, class RunPass>
+    std::string capture_pass(bool per_group, int ngroups, const RunGroup& run_group, const RunPass& run_pass, PassGraphs& pg) {
+        std::string why;
+        const int ncap = per_group ? ngroups : 1;
+        for (int c = 0; c < ncap && why.empty(); ++c) {
+            hipStream_t cs = per_group && c ? gstream[c - 1] : stream;
+            hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
+            hipError_t ge = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
+            if (ge != hipSuccess) { why = std::string("begin capture: ") + hipGetErrorString(ge); break; }
+            try { if (per_group) run_group(c); else run_pass(); } catch (const std::exception& e) { why = std::string("capture: ") + e.what(); }
+            ge = hipStreamEndCapture(cs, &graph);
+            if (why.empty() && ge != hipSuccess) why = std::string("end capture: ") + hipGetErrorString(ge);
+            if (why.empty()) { ge = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0); if (ge != hipSuccess) why = std::string("instantiation: ") + hipGetErrorString(ge); }
+            if (graph) (void)hipGraphDestroy(graph);
+            if (why.empty()) pg.g[pg.n++] = exec;
+        }
+        return why;
     }
 
     // the network passes of `tile_count` tiles (slots d_slots[slots_off ..]); their outputs go to slab slots slab_slot0, slab_slot0 + 1, ...
@@ -999,21 +1010,7 @@ struct Img2Img::Impl {
                     // a capture invalidated by a runtime call inside a launcher, end, instantiate) the pass is still to be done:
                     // graphs are switched off for good (otherwise every later frame would retry and fail again) and it runs on plain launches.
                     PassGraphs pg;
-                    std::string why;
-                    const int ncap = per_group ? NG : 1;
-                    for (int c = 0; c < ncap && why.empty(); ++c) {
-                        hipStream_t cs = per_group ? group_stream(c) : stream;
-                        hipGraph_t graph = nullptr; hipGraphExec_t exec = nullptr;
-                        hipError_t ge = hipStreamBeginCapture(cs, hipStreamCaptureModeThreadLocal);
-                        if (ge != hipSuccess) { why = std::string("begin capture: ") + hipGetErrorString(ge); break; }
-                        try { if (per_group) run_group(c); else run_pass(); } catch (const std::exception& e) { why = std::string("capture: ") + e.what(); }
-                        ge = hipStreamEndCapture(cs, &graph);
-                        if (why.empty() && ge != hipSuccess) why = std::string("end capture: ") + hipGetErrorString(ge);
-                        if (why.empty()) { ge = hipGraphInstantiate(&exec, graph, nullptr, nullptr, 0); if (ge != hipSuccess) why = std::string("instantiation: ") + hipGetErrorString(ge); }
-                        if (graph) (void)hipGraphDestroy(graph);
-                        if (why.empty()) pg.g[pg.n++] = exec;
-                    }
-                    if (!why.empty()) {
+                    if (const std::string why = capture_pass(per_group, NG, run_group, run_pass, pg); !why.empty()) {
                         (void)hipGetLastError();
                         for (int c = 0; c < pg.n; ++c) (void)hipGraphExecDestroy(pg.g[c]);
                         use_graphs = false;
@@ -1336,8 +1333,9 @@ struct Img2Img::Impl {
         launch_bleed(rows, cols, radius);
     }
 
-    // ---- The frame calls other than render() / renderStrip(): one record, one checker per format, one runner.  An entry point checks (X_check fills the record
-    // or returns the first refusal's text), sets the job of its format, and hands the record and its two copy lambdas to run_call().
+    // ---- The frame calls: one record, one checker per format, one runner.  An entry point checks (X_check fills the record or returns the first refusal's
+    // text), sets the job of its format, and hands the record and its two copy lambdas to run_call() - render() / renderStrip() (renderPart) hand theirs to
+    // run_frame() or, for a frame in pipelined parts, run_frame_in_parts().
     struct FrameCall { int rows = 0, cols = 0, out_rows = 0, out_cols = 0; bool resized = false; TileGrid grid; StripPlan sp; };
     // The pieces the checkers share, where text and position agree.  call_target(): the sizes of the call into `c` - with a resize filter the target is the size of
     // the first output image, else the scaled size; at the scaled size a resized call is the plain one - and why a call with a filter (`any_filter` false: only a
@@ -1365,6 +1363,19 @@ struct Img2Img::Impl {
             if (!dsts[i].data || dsts[i].rows != c.out_rows || dsts[i].cols != c.out_cols || dsts[i].step < (size_t)c.out_cols * 3) return out_size_text(c);
         }
         return call_grid(c);
+    }
+    // render / renderResized / renderStrip: one frame of 8 or 16 bits, or strip `part` of `parts` of it (c.sp is that strip; it has no tiles when there are more
+    // strips than tile columns).  At the scaled size a resized frame is the plain one.
+    std::string bgr_frame_check(const Image& src, const Image& dst, int part, int parts, int resizeFilter, FrameCall& c) const {
+        if (parts <= 0 || part < 0 || part >= parts) return "Invalid strip index.";
+        if ((src.depth != 8 && src.depth != 16) || dst.depth != src.depth) return "Input and output images must both be 8-bit or both 16-bit.";
+        const size_t px = (size_t)3 * (src.depth / 8);                 // bytes per pixel
+        if (!src.data || src.rows <= 0 || src.cols <= 0 || src.step < src.cols * px) return "Input image is empty or has an invalid step.";
+        if (const std::string why = call_target(resizeFilter, dst, src.rows, src.cols, false, c); !why.empty()) return why;
+        if (!dst.data || dst.rows != c.out_rows || dst.cols != c.out_cols || dst.step < dst.cols * px) return c.resized ? "Output image is empty or has an invalid step." : out_size_text(c);
+        if (const std::string why = call_grid(c); !why.empty()) return why;
+        if (parts > 1) c.sp = strip_plan(c.grid, c.cols * cfg.scaling, plan.Tout, part, parts);
+        return "";
     }
     // The YUV calls: one size, one pair of depths and one pair of layouts (srcs[0]'s, dsts[0]'s) for the sequence, resized or not.
     std::string yuv_check(const YuvImage* srcs, const YuvImage* dsts, int count, YuvFormat format, int resizeFilter, FrameCall& c) const {
@@ -1525,6 +1536,55 @@ struct Img2Img::Impl {
         run_call(c, count, single, resizeFilter,
             [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dev, in_step, srcs[i].data, srcs[i].step, (size_t)c.cols * bpp, c.rows, hipMemcpyHostToDevice, on)); },
             [&](int i, uint8_t* dev, hipStream_t on) { hipAssert(hipMemcpy2DAsync(dsts[i].data, dsts[i].step, dev, out_step, (size_t)c.out_cols * bpp, c.out_rows, hipMemcpyDeviceToHost, on)); });
+    }
+    // A render() frame in the pipelined parts of render_parts() (tiles.h), behind the upload of the columns [0, rp.x_split) and the slot tables: per part its
+    // passes, its cells composed and an event; the rest of the upload behind the first part's launches; the downloads of the parts' cells, in order, on a copy
+    // stream; ev1 behind the last part.  Returns with dst complete.
+    void run_frame_in_parts(const FrameCall& c, const RenderParts& rp, const Image& src, Image& dst) {
+        const int rows = c.rows, cols = c.cols, steps = cfg.tta ? 8 : 1;
+        const size_t px = deep ? 6 : 3;                                   // bytes per pixel
+        ensure_copy_streams();
+        for (int k = 0; k < rp.n; ++k) if (!ev_part[k]) hipAssert(hipEventCreateWithFlags(&ev_part[k], hipEventDisableTiming));
+        // the parts ROLL like the frames of a sequence (run_rolling_frame) when all their passes split: no join at the end of a part - the second group's stream
+        // composes the part's cells behind its own tiles while the first stream starts the next part's (one slab: the parts' tiles lie side by side in it)
+        bool roll = true;
+        for (int k = 0; k < rp.n; ++k) roll = roll && can_roll(rp.part[k].tiles);
+        struct Unroll { Impl* e; ~Unroll() { e->rolling = false; } } unroll{this};
+        if (roll) for (int k = 0; k < 2; ++k) if (!ev_g0[k]) hipAssert(hipEventCreateWithFlags(&ev_g0[k], hipEventDisableTiming));
+        for (int k = 0; k < rp.n; ++k) {
+            const RenderParts::Part& p = rp.part[k];
+            if (k == 1 && rp.x_split < cols) hipAssert(hipStreamWaitEvent(stream, ev_up[0], 0));      // the rest of the frame has arrived
+            rolling = roll;
+            run_passes(rows, cols, p.tiles, (size_t)p.first * steps, true, p.slots_off, k == 0, p.batches_before, rp.batch_total);
+            rolling = false;
+            if (k == 0 && rp.x_split < cols) {      // issued behind the first part's launches: from pageable memory the call returns when the copy is done
+                hipAssert(hipMemcpy2DAsync(d_frame + (size_t)rp.x_split * px, (size_t)cols * px, src.data + (size_t)rp.x_split * px, src.step, (size_t)(cols - rp.x_split) * px, rows,
+                                           hipMemcpyHostToDevice, s_dn));
+                hipAssert(hipEventRecord(ev_up[0], s_dn));
+            }
+            hipStream_t cs = stream;
+            if (roll) {
+                cs = gstream[0];
+                hipAssert(hipEventRecord(ev_g0[k & 1], stream));
+                hipAssert(hipStreamWaitEvent(cs, ev_g0[k & 1], 0));
+            }
+            for (int r = 0; r < p.nrect; ++r) compose_rect(rows, cols, c.grid, p.rect[r].x, p.rect[r].x + p.rect[r].w, p.rect[r].y, p.rect[r].y + p.rect[r].h, 0, cs);
+            hipAssert(hipEventRecord(ev_part[k], cs));
+            if (k + 1 == rp.n) { if (roll) end_rolling(); hipAssert(hipEventRecord(ev1, stream)); }
+        }
+        // the downloads, in order, on a copy stream: a part's cells travel while the next part computes.  Which of the two copy streams: the one created
+        // FIRST (renderSequence()'s upload stream, idle here) - the runtime spreads streams over its hardware queues in creation order, and from
+        // pageable memory the download only ran beside the kernels on that one (9.1 against 9.9 ms per call, profiles/r4_kernels/render_parts_ab*.txt)
+        for (int k = 0; k < rp.n; ++k) {
+            hipAssert(hipStreamWaitEvent(s_up, ev_part[k], 0));
+            for (int r = 0; r < rp.part[k].nrect; ++r) {
+                const Rect& rc = rp.part[k].rect[r];
+                hipAssert(hipMemcpy2DAsync(dst.data + (size_t)rc.y * dst.step + (size_t)rc.x * px, dst.step, d_out + ((size_t)rc.y * dst.cols + rc.x) * px, (size_t)dst.cols * px,
+                                           (size_t)rc.w * px, rc.h, hipMemcpyDeviceToHost, s_up));
+            }
+        }
+        hipAssert(hipStreamSynchronize(s_up));
+        hipAssert(hipStreamSynchronize(stream));
     }
     // the RGBA calls behind entry(): one frame on the compute stream with progress (renderRgbaFrame), or a sequence (runSequenceRgba)
     bool rgba_call(const Image* srcs, Image* dsts, int count, const RgbaOptions& opt, int resizeFilter, const char* who, bool single) {
@@ -1782,7 +1842,7 @@ bool Img2Img::load(const std::string& modelPath, const RenderConfig& config) try
     impl->check_general = sw.check_general;
     impl->use_graphs = !sw.no_graph;
     impl->rolling_ok = !sw.no_rolling;
-    impl->pipeline_parts = std::min(Impl::kMaxRenderParts, std::max(1, sw.render_parts));
+    impl->pipeline_parts = std::min(kMaxRenderParts, std::max(1, sw.render_parts));
     if (const std::string nd = switches_nondefault(); !nd.empty()) W2X_LOG(warn, "Switches off their defaults: " + nd + ".");
     if (sw.roctx && !impl->roctx_push) {
         if (void* h = dlopen("libroctx64.so", RTLD_NOW | RTLD_GLOBAL)) {
@@ -1880,155 +1940,40 @@ bool Img2Img::renderStrip(const Image& src, Image& dst, int part, int parts) { r
 
 bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, const char* who, int resizeFilter) {
     return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
-    if (parts <= 0 || part < 0 || part >= parts) { W2X_LOG_AS(who, error, "Invalid strip index."); return false; }
-    const RenderConfig& cfg = impl->cfg;
+    Impl::FrameCall c;
+    if (const std::string why = impl->bgr_frame_check(src, dst, part, parts, resizeFilter, c); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
     const Plan& plan = impl->plan;
-    const int rows = src.rows, cols = src.cols, s = cfg.scaling;
-    if ((src.depth != 8 && src.depth != 16) || dst.depth != src.depth) { W2X_LOG_AS(who, error, "Input and output images must both be 8-bit or both 16-bit."); return false; }
+    const int rows = c.rows, cols = c.cols, s = impl->cfg.scaling;
     const size_t bps = src.depth / 8;                          // bytes per sample
-    if (!src.data || rows <= 0 || cols <= 0 || src.step < (size_t)cols * 3 * bps) { W2X_LOG_AS(who, error, "Input image is empty or has an invalid step."); return false; }
-    // a resized frame (renderResized): dst is the target size; at the scaled size it is a plain render()
-    Impl::FrameCall target;
-    if (const std::string why = impl->call_target(resizeFilter, dst, rows, cols, false, target); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
-    const bool resized = target.resized;
-    if (resized) {
-        if (!dst.data || dst.step < (size_t)dst.cols * 3 * bps) { W2X_LOG_AS(who, error, "Output image is empty or has an invalid step."); return false; }
-    } else if (!dst.data || dst.rows != rows * s || dst.cols != cols * s || dst.step < (size_t)dst.cols * 3 * bps) {
-        W2X_LOG_AS(who, error, "Output image has invalid size: expected " + std::to_string(cols * s) + "x" + std::to_string(rows * s) + ".");
-        return false;
-    }
     hipStream_t stream = impl->stream;
-    // img2img_render.cpp:226 upload
     impl->ensure(impl->d_frame, impl->frame_cap, Impl::bgr_step(cols, bps == 2) * rows);
     impl->ensure(impl->d_out, impl->out_cap, Impl::bgr_step(dst.cols, bps == 2) * dst.rows);
-    if (resized) impl->job_resize(rows, cols, dst.rows, dst.cols, resizeFilter);
+    if (c.resized) impl->job_resize(rows, cols, dst.rows, dst.cols, resizeFilter);
     impl->deep = bps == 2;
-    // img2img_render.cpp:226 upload: below, once the parts are known (a frame that runs in parts uploads the first part's columns first)
-    TileGrid grid;
-    if (const std::string why = impl->frame_grid(rows, cols, grid); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
-    const StripPlan sp = strip_plan(grid, cols * s, plan.Tout, part, parts);
+    const StripPlan& sp = c.sp;
     if (sp.tile_count == 0) return true;                       // more devices than tile columns: this one has no share
-    const int steps = cfg.tta ? 8 : 1;
-    // A whole frame (render()) runs as a few PARTS one after the other: a part's tiles, its canvas cells composed and handed to the download
-    // stream, then the next part's while those cells travel to the host - the synchronous contract of img2img_render.cpp:226-344 with most of
-    // the 100 MB download of a 4K frame off the critical path: only the last part's cells travel after the last kernel (config 3: 9.9 ms per
-    // call as one part, 8.4 as three, profiles/r4_kernels/render_parts_*.txt).  The parts are those of shard_plan() (contiguous tile ranges, canvas cells of their
-    // tiles; a part reads the tiles in front of its range from the same slab), cut at multiples of the batch size so that batches, their order
-    // and the progress schedule (:246-250, 336-338) are the reference's.
-    constexpr int kMaxParts = Impl::kMaxRenderParts;
-    int npart = 1;
-    int first_of[kMaxParts + 1] = {0, sp.tile_count, 0, 0, 0};   // part k = tiles [first_of[k], first_of[k + 1]) of the strip
-    if (parts == 1 && !resized && impl->pipeline_parts > 1 && sp.tile_count >= 16 && grid.outOvX < plan.Tout - grid.outOvX && grid.outOvY < plan.Tout - grid.outOvY) {
-        int q = 1; while ((q * steps) % plan.userB) ++q;        // part boundaries: whole reference batches
-        const int want = std::min({impl->pipeline_parts, kMaxParts, sp.tile_count / 8});
-        // the LAST part is the small one - its cells are the only ones that travel after the last kernel (a fifth of the tiles, at least 8: smaller passes no longer
-        // fill the device) - and the tiles in front of it split evenly: config 3's 45 tiles run as 16 + 20 + 9 (8.4 ms per call; as 15 + 15 + 15: 8.8, 12 + 12 + 12 + 9: 8.45)
-        int n = 0;
-        const int body = want >= 2 ? (sp.tile_count - std::max(8, sp.tile_count / 5)) / q * q : 0;
-        for (int k = 1; k < want; ++k) {
-            const int t = k + 1 == want ? body : (int)((long)k * body / (want - 1)) / q * q;
-            if (t > first_of[n] && t < sp.tile_count) first_of[++n] = t;
-        }
-        first_of[++n] = sp.tile_count;
-        npart = n;
-    }
-    int tiles_of[kMaxParts] = {}, batches_of[kMaxParts] = {}, batches_before[kMaxParts] = {};
-    size_t slots_off[kMaxParts] = {}; size_t stepTotal = 0; int batch_total = 0;
-    for (int k = 0; k < npart; ++k) {
-        tiles_of[k] = first_of[k + 1] - first_of[k];
-        batches_of[k] = impl->batch_count(tiles_of[k]);
-        batches_before[k] = batch_total; batch_total += batches_of[k];
-        slots_off[k] = stepTotal;
-        stepTotal += impl->pass_slots(tiles_of[k]);   // reference batches rounded up to whole network passes
-    }
-    // :226 upload.  In parts: the frame columns the first part's tiles read go first, on the compute stream; the rest follows on the upload stream while that
-    // part computes (tiles are ordered by column, :43-44, so a part reads a column range; the second part waits for the event)
-    int x_split = cols;
-    if (npart > 1) {
-        int xm = 0;
-        for (int t = 0; t < first_of[1]; ++t) xm = std::max(xm, grid.in[sp.first_tile + t].x + plan.T);
-        if (xm > 0 && xm < cols - 64) x_split = xm;
-    }
-    hipAssert(hipMemcpy2DAsync(impl->d_frame, (size_t)cols * 3 * bps, src.data, src.step, (size_t)x_split * 3 * bps, rows, hipMemcpyHostToDevice, stream));
-    for (int k = 0; k < npart; ++k) impl->fill_slots(grid, sp.first_tile + first_of[k], tiles_of[k], 1, slots_off[k], impl->pass_slots(tiles_of[k]));
-    // the slab holds the frame's tiles in tile order: the last part's passes end at most a pass beyond them (and the frame as ONE part - what
-    // benchResident / profileFrame replay - ends at most a pass beyond its tiles: sized for both now, an allocation later would drop the captured passes)
-    impl->upload_slots(grid, stepTotal, std::max((size_t)first_of[npart - 1] * steps + (stepTotal - slots_off[npart - 1]), impl->pass_slots(sp.tile_count)));
+    // the frame's parts (tiles.h): several for a whole frame at the scaled size when the pipeline is switched on and the frame is large enough
+    const RenderParts rp = render_parts(c.grid, sp, cols, cols * s, rows * s, plan.T, plan.Tout, impl->cfg.tta ? 8 : 1, plan.userB, plan.B,
+                                        parts == 1 && !c.resized ? impl->pipeline_parts : 1);
+    // img2img_render.cpp:226 upload.  In parts: the frame columns the first part's tiles read go first, on the compute stream; the rest follows on the upload
+    // stream while that part computes (run_frame_in_parts)
+    hipAssert(hipMemcpy2DAsync(impl->d_frame, (size_t)cols * 3 * bps, src.data, src.step, (size_t)rp.x_split * 3 * bps, rows, hipMemcpyHostToDevice, stream));
+    for (int k = 0; k < rp.n; ++k) impl->fill_slots(c.grid, sp.first_tile + rp.part[k].first, rp.part[k].tiles, 1, rp.part[k].slots_off, rp.part[k].slots);
+    impl->upload_slots(c.grid, rp.slot_total, rp.slab_slots);   // (the slab sized for the parts and for the frame as one part now: an allocation later would drop the captured passes)
 
     hipAssert(hipEventRecord(impl->ev0, stream));
-    if (npart == 1) {
-        impl->run_frame(rows, cols, grid, true, sp);
+    if (rp.n == 1) {
+        impl->run_frame(rows, cols, c.grid, true, sp);
         hipAssert(hipEventRecord(impl->ev1, stream));
         // :344 download ; the reference leaves the sync commented out (:345, quirk Q10) - we wait before handing dst back
-        const int dx0 = resized ? 0 : sp.x0, dx1 = resized ? dst.cols : sp.x1;
+        const int dx0 = c.resized ? 0 : sp.x0, dx1 = c.resized ? dst.cols : sp.x1;
         hipAssert(hipMemcpy2DAsync(dst.data + (size_t)dx0 * 3 * bps, dst.step, impl->d_out + (size_t)dx0 * 3 * bps, (size_t)dst.cols * 3 * bps, (size_t)(dx1 - dx0) * 3 * bps, dst.rows, hipMemcpyDeviceToHost, stream));
         hipAssert(hipStreamSynchronize(stream));
-    } else {
-        impl->ensure_copy_streams();
-        for (int k = 0; k < npart; ++k) if (!impl->ev_part[k]) hipAssert(hipEventCreateWithFlags(&impl->ev_part[k], hipEventDisableTiming));
-        ShardPlan part_plan[kMaxParts];
-        for (int k = 0; k < npart; ++k) {
-            // the cells of the part's tiles: shard_plan()'s rectangles for these (batch-aligned) boundaries
-            ShardPlan q; q.first_tile = first_of[k]; q.tile_count = tiles_of[k];
-            const int sx = plan.Tout - grid.outOvX, sy = plan.Tout - grid.outOvY;
-            auto x_of = [&](int i) { return i >= grid.nx ? cols * s : i * sx; };
-            auto y_of = [&](int j) { return j >= grid.ny ? rows * s : j * sy; };
-            auto add = [&](int i0, int i1, int j0, int j1) { if (i0 < i1 && j0 < j1) q.rect[q.nrect++] = Rect{x_of(i0), y_of(j0), x_of(i1) - x_of(i0), y_of(j1) - y_of(j0)}; };
-            const int t0 = q.first_tile, t1 = t0 + q.tile_count;
-            const int c0 = t0 / grid.ny, r0 = t0 % grid.ny, c1 = t1 / grid.ny, r1 = t1 % grid.ny;
-            if (c0 == c1) add(c0, c0 + 1, r0, r1);
-            else { int full0 = c0; if (r0) { add(c0, c0 + 1, r0, grid.ny); full0 = c0 + 1; } add(full0, c1, 0, grid.ny); if (r1) add(c1, c1 + 1, 0, r1); }
-            part_plan[k] = q;
-        }
-        hipStream_t dn = impl->s_up;      // (which of the two copy streams: below)
-        auto download_part = [&](int k) {
-            hipAssert(hipStreamWaitEvent(dn, impl->ev_part[k], 0));
-            for (int r = 0; r < part_plan[k].nrect; ++r) {
-                const Rect& rc = part_plan[k].rect[r];
-                hipAssert(hipMemcpy2DAsync(dst.data + (size_t)rc.y * dst.step + (size_t)rc.x * 3 * bps, dst.step, impl->d_out + ((size_t)rc.y * dst.cols + rc.x) * 3 * bps, (size_t)dst.cols * 3 * bps,
-                                           (size_t)rc.w * 3 * bps, rc.h, hipMemcpyDeviceToHost, dn));
-            }
-        };
-        // the parts ROLL like the frames of a sequence (run_rolling_frame) when all their passes split: no join at the end of a part - the second group's stream
-        // composes the part's cells behind its own tiles while the first stream starts the next part's (one slab: the parts' tiles lie side by side in it)
-        bool roll = true;
-        for (int k = 0; k < npart; ++k) roll = roll && impl->can_roll(tiles_of[k]);
-        struct Unroll { Impl* e; ~Unroll() { e->rolling = false; } } unroll{impl.get()};
-        if (roll) for (int k = 0; k < 2; ++k) if (!impl->ev_g0[k]) hipAssert(hipEventCreateWithFlags(&impl->ev_g0[k], hipEventDisableTiming));
-        for (int k = 0; k < npart; ++k) {
-            if (k == 1 && x_split < cols) hipAssert(hipStreamWaitEvent(stream, impl->ev_up[0], 0));      // the rest of the frame has arrived
-            impl->rolling = roll;
-            impl->run_passes(rows, cols, tiles_of[k], (size_t)first_of[k] * steps, true, slots_off[k], k == 0, batches_before[k], batch_total);
-            impl->rolling = false;
-            if (k == 0 && x_split < cols) {      // issued behind the first part's launches: from pageable memory the call returns when the copy is done
-                hipAssert(hipMemcpy2DAsync(impl->d_frame + (size_t)x_split * 3 * bps, (size_t)cols * 3 * bps, src.data + (size_t)x_split * 3 * bps, src.step, (size_t)(cols - x_split) * 3 * bps, rows,
-                                           hipMemcpyHostToDevice, impl->s_dn));
-                hipAssert(hipEventRecord(impl->ev_up[0], impl->s_dn));
-            }
-            hipStream_t cs = stream;
-            if (roll) {
-                cs = impl->gstream[0];
-                hipAssert(hipEventRecord(impl->ev_g0[k & 1], stream));
-                hipAssert(hipStreamWaitEvent(cs, impl->ev_g0[k & 1], 0));
-            }
-            for (int r = 0; r < part_plan[k].nrect; ++r) {
-                const Rect& rc = part_plan[k].rect[r];
-                impl->compose_rect(rows, cols, grid, rc.x, rc.x + rc.w, rc.y, rc.y + rc.h, 0, cs);
-            }
-            hipAssert(hipEventRecord(impl->ev_part[k], cs));
-            if (k + 1 == npart) { if (roll) impl->end_rolling(); hipAssert(hipEventRecord(impl->ev1, stream)); }
-        }
-        // the downloads, in order, on a copy stream: a part's cells travel while the next part computes.  Which of the two copy streams: the one created
-        // FIRST (renderSequence()'s upload stream, idle here) - the runtime spreads streams over its hardware queues in creation order, and from
-        // pageable memory the download only ran beside the kernels on that one (9.1 against 9.9 ms per call, profiles/r4_kernels/render_parts_ab*.txt)
-        for (int k = 0; k < npart; ++k) download_part(k);
-        hipAssert(hipStreamSynchronize(dn));
-        hipAssert(hipStreamSynchronize(stream));
-    }
+    } else impl->run_frame_in_parts(c, rp, src, dst);
     hipAssert(hipEventElapsedTime(&impl->last_ms, impl->ev0, impl->ev1));
-    impl->last_rows = rows; impl->last_cols = cols; impl->last_grid = grid; impl->last_strip = sp;
-    impl->one_part_stale = npart > 1;     // (benchResident / profileFrame replay the frame as ONE part and rebuild the slot table when they are called: one_part_slots)
-    if (resized) impl->last_rows = impl->last_cols = 0;   // (a resized frame is not replayed: benchResident / residentOutput / profileFrame serve render() frames)
+    impl->last_rows = rows; impl->last_cols = cols; impl->last_grid = c.grid; impl->last_strip = sp;
+    impl->one_part_stale = rp.n > 1;      // (benchResident / profileFrame replay the frame as ONE part and rebuild the slot table when they are called: one_part_slots)
+    if (c.resized) impl->last_rows = impl->last_cols = 0;   // (a resized frame is not replayed: benchResident / residentOutput / profileFrame serve render() frames)
     // the second slab of a rolling sequence now (an allocation drops the captured passes: better here, on the frame size's first sight, than inside benchResident / renderSequence)
     if (parts == 1 && impl->slab2_cap < impl->slab_cap && impl->can_roll(sp.tile_count)) impl->ensure(impl->d_slab2, impl->slab2_cap, impl->slab_cap);
     return true;
@@ -2056,7 +2001,7 @@ static void shard_phase1(Img2Img::Impl& e, const Image& src, const TileGrid& gri
     hipAssert(hipMemcpy2DAsync(e.d_frame, (size_t)cols * 3, src.data, src.step, (size_t)cols * 3, rows, hipMemcpyHostToDevice, e.stream));
     const size_t stepCount = e.pass_slots(sp.tile_count);
     e.fill_slots(grid, sp.first_tile, sp.tile_count, 1, 0, stepCount);
-    e.shard_halo_slots = (size_t)(sp.first_tile - sp.halo_first) * steps;
+    e.shard_halo_slots = halo_slots(sp, steps);
     e.upload_slots(grid, stepCount, e.shard_halo_slots + stepCount);
     hipAssert(hipEventRecord(e.ev0, e.stream));
     e.run_passes(rows, cols, sp.tile_count, e.shard_halo_slots, report, 0, true);
@@ -2155,13 +2100,8 @@ bool Img2Img::renderSharded(Img2Img* const* engines, int count, const Image& src
         if (const std::string why = shard_frame_problem(*impl, src, &dst); !why.empty()) { W2X_LOG(error, why); return false; }
         TileGrid grid;
         if (const std::string why = impl->frame_grid(rows, cols, grid); !why.empty()) { W2X_LOG(error, why); return false; }
-        std::vector<ShardPlan> sp(count);
-        for (int k = 0; k < count; ++k) sp[k] = shard_plan(grid, cols * s, rows * s, plan.Tout, plan.Tout, k, count);
-        {   // every tile must have an owner: shard_plan() hands out nothing when the blend bands are as wide as the tile stride
-            int owned = 0;
-            for (int k = 0; k < count; ++k) owned += sp[k].tile_count;
-            if (owned != grid.count) { W2X_LOG(error, "renderSharded: the blend bands are wider than the tile stride; use render or renderStrip."); return false; }
-        }
+        std::vector<ShardPlan> sp;
+        if (!shard_plans(grid, cols * s, rows * s, plan.Tout, count, sp)) { W2X_LOG(error, "renderSharded: the blend bands are wider than the tile stride; use render or renderStrip."); return false; }
         // ---- phase 1: every engine computes its own tiles
         for (int k = 0; k < count; ++k) {
             Impl& e = *engines[k]->impl;
@@ -2209,15 +2149,11 @@ bool Img2Img::shardCompute(const Image& src, int part, int parts) {
     const int rows = src.rows, cols = src.cols, s = impl->cfg.scaling;
     TileGrid grid;
     if (const std::string why = impl->frame_grid(rows, cols, grid); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
-    const ShardPlan sp = shard_plan(grid, cols * s, rows * s, plan.Tout, plan.Tout, part, parts);
     impl->shard_rows = rows; impl->shard_cols = cols;
-    {   // every tile must have an owner (shard_plan() hands out nothing when the blend bands are as wide as the tile stride)
-        int owned = 0;
-        for (int k = 0; k < parts; ++k) owned += shard_plan(grid, cols * s, rows * s, plan.Tout, plan.Tout, k, parts).tile_count;
-        if (owned != grid.count) { W2X_LOG_AS(who, error, "the blend bands are wider than the tile stride; use render or renderStrip."); return false; }
-    }
-    if (sp.tile_count == 0) return true;                       // more parts than tiles: this one has no share
-    shard_phase1(*impl, src, grid, sp, true);
+    std::vector<ShardPlan> sp;
+    if (!shard_plans(grid, cols * s, rows * s, plan.Tout, parts, sp)) { W2X_LOG_AS(who, error, "the blend bands are wider than the tile stride; use render or renderStrip."); return false; }
+    if (sp[part].tile_count == 0) return true;                 // more parts than tiles: this one has no share
+    shard_phase1(*impl, src, grid, sp[part], true);
     hipAssert(hipStreamSynchronize(impl->stream));           // the slab is complete when this returns: what the peers copy from after the barrier
     return true;
     });
@@ -2237,13 +2173,12 @@ bool Img2Img::shardFinish(Image& dst, int part, int parts, const void* const* sl
     if (const std::string why = shard_frame_problem(*impl, probe, &dst); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
     TileGrid grid;                                             // (the grid shardCompute() accepted)
     if (const std::string why = impl->frame_grid(rows, cols, grid); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
-    std::vector<ShardPlan> sp(parts);
+    std::vector<ShardPlan> sp;
     std::vector<ShardPeer> peers(parts);
-    for (int k = 0; k < parts; ++k) {
-        sp[k] = shard_plan(grid, cols * s, rows * s, plan.Tout, plan.Tout, k, parts);
-        if (sp[k].tile_count) peers[k] = ShardPeer{k == part ? impl->d_slab : slabs[k], (size_t)(sp[k].first_tile - sp[k].halo_first) * steps, k == part ? impl->device : devices ? physical_device(devices[k]) : -1,
+    shard_plans(grid, cols * s, rows * s, plan.Tout, parts, sp);   // (shardCompute() has checked that every tile has an owner)
+    for (int k = 0; k < parts; ++k)
+        if (sp[k].tile_count) peers[k] = ShardPeer{k == part ? impl->d_slab : slabs[k], halo_slots(sp[k], steps), k == part ? impl->device : devices ? physical_device(devices[k]) : -1,
                                                    nullptr, sp[k].first_tile, sp[k].tile_count};
-    }
     if (sp[part].tile_count == 0) return true;
     shard_phase2(*impl, part, sp, peers, grid, rows, cols, dst);
     hipAssert(hipStreamSynchronize(impl->stream));

@@ -106,13 +106,21 @@ ShardPlan shard_plan(const TileGrid& g, int outW, int outH, int tileOutW, int ti
     if (t0 >= t1) return sp;                                           // more parts than tiles
     sp.first_tile = (int)t0; sp.tile_count = (int)(t1 - t0);
     sp.halo_first = (int)std::max<long>(0, t0 - g.ny - 1);
+    sp.nrect = tile_range_cells(g, outW, outH, tileOutW, tileOutH, sp.first_tile, sp.first_tile + sp.tile_count, sp.rect);
+    return sp;
+}
+
+int tile_range_cells(const TileGrid& g, int outW, int outH, int tileOutW, int tileOutH, int t0, int t1, Rect out[3]) {
+    if (g.ny <= 0 || t0 < 0 || t0 >= t1 || t1 > g.count) return 0;
+    const int sx = tileOutW - g.outOvX, sy = tileOutH - g.outOvY;
+    int n = 0;
     auto x_of = [&](int i) { return i >= g.nx ? outW : i * sx; };
     auto y_of = [&](int j) { return j >= g.ny ? outH : j * sy; };
     auto add = [&](int i0, int i1, int j0, int j1) {                   // cells of columns [i0, i1) x rows [j0, j1)
         if (i0 >= i1 || j0 >= j1) return;
-        sp.rect[sp.nrect++] = Rect{x_of(i0), y_of(j0), x_of(i1) - x_of(i0), y_of(j1) - y_of(j0)};
+        out[n++] = Rect{x_of(i0), y_of(j0), x_of(i1) - x_of(i0), y_of(j1) - y_of(j0)};
     };
-    const int c0 = (int)(t0 / g.ny), r0 = (int)(t0 % g.ny), c1 = (int)(t1 / g.ny), r1 = (int)(t1 % g.ny);
+    const int c0 = t0 / g.ny, r0 = t0 % g.ny, c1 = t1 / g.ny, r1 = t1 % g.ny;
     if (c0 == c1) add(c0, c0 + 1, r0, r1);                             // inside one column
     else {
         int full0 = c0;
@@ -120,7 +128,62 @@ ShardPlan shard_plan(const TileGrid& g, int outW, int outH, int tileOutW, int ti
         add(full0, c1, 0, g.ny);                                       // whole columns
         if (r1 != 0) add(c1, c1 + 1, 0, r1);                           // the head of the last column
     }
-    return sp;
+    return n;
+}
+
+bool shard_plans(const TileGrid& g, int outW, int outH, int tileOut, int parts, std::vector<ShardPlan>& plans) {
+    plans.assign(std::max(parts, 0), ShardPlan{});
+    int owned = 0;
+    for (int k = 0; k < parts; ++k) { plans[k] = shard_plan(g, outW, outH, tileOut, tileOut, k, parts); owned += plans[k].tile_count; }
+    return owned == g.count;
+}
+
+int batch_count(int tiles, int steps, int userB) { return (int)std::lround(std::ceil((double)(tiles * steps) / userB)); }
+
+size_t pass_slots(int tiles, int steps, int userB, int B) {
+    const int S = B / userB;
+    return (size_t)((batch_count(tiles, steps, userB) + S - 1) / S) * B;
+}
+
+int last_pass_live(int tiles, int steps, int B) { return tiles * steps - (tiles * steps - 1) / B * B; }
+
+RenderParts render_parts(const TileGrid& grid, const StripPlan& strip, int cols, int outW, int outH, int T, int Tout, int steps, int userB, int B, int want) {
+    RenderParts rp;
+    const int tiles = strip.tile_count;
+    int first_of[kMaxRenderParts + 1] = {0, tiles, 0, 0, 0};            // part k = tiles [first_of[k], first_of[k + 1]) of the strip
+    if (want > 1 && tiles >= 16 && grid.outOvX < Tout - grid.outOvX && grid.outOvY < Tout - grid.outOvY) {
+        int q = 1; while ((q * steps) % userB) ++q;                     // part boundaries: whole reference batches
+        want = std::min({want, kMaxRenderParts, tiles / 8});
+        // the LAST part is the small one - its cells are the only ones that travel after the last kernel (a fifth of the tiles, at least 8: smaller passes no longer
+        // fill the device) - and the tiles in front of it split evenly: config 3's 45 tiles run as 16 + 20 + 9 (8.4 ms per call; as 15 + 15 + 15: 8.8, 12 + 12 + 12 + 9: 8.45)
+        int n = 0;
+        const int body = want >= 2 ? (tiles - std::max(8, tiles / 5)) / q * q : 0;
+        for (int k = 1; k < want; ++k) {
+            const int t = k + 1 == want ? body : (int)((long)k * body / (want - 1)) / q * q;
+            if (t > first_of[n] && t < tiles) first_of[++n] = t;
+        }
+        first_of[++n] = tiles;
+        rp.n = n;
+    }
+    for (int k = 0; k < rp.n; ++k) {
+        RenderParts::Part& p = rp.part[k];
+        p.first = first_of[k]; p.tiles = first_of[k + 1] - first_of[k];
+        p.batches = batch_count(p.tiles, steps, userB);
+        p.batches_before = rp.batch_total; rp.batch_total += p.batches;
+        p.slots_off = rp.slot_total;
+        p.slots = pass_slots(p.tiles, steps, userB, B);                 // reference batches rounded up to whole network passes
+        rp.slot_total += p.slots;
+        p.nrect = tile_range_cells(grid, outW, outH, Tout, Tout, strip.first_tile + p.first, strip.first_tile + p.first + p.tiles, p.rect);
+    }
+    rp.x_split = cols;
+    if (rp.n > 1) {
+        int xm = 0;
+        for (int t = 0; t < first_of[1]; ++t) xm = std::max(xm, grid.in[strip.first_tile + t].x + T);
+        if (xm > 0 && xm < cols - 64) rp.x_split = xm;
+    }
+    const RenderParts::Part& last = rp.part[rp.n - 1];
+    rp.slab_slots = std::max((size_t)last.first * steps + last.slots, pass_slots(tiles, steps, userB, B));
+    return rp;
 }
 
 ResizeTaps resize_taps(int in, int out, int filter) {

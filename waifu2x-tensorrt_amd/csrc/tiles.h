@@ -1,5 +1,7 @@
 // Host-side tile geometry: bit-exact restatement of calculateTiles / createTileWeights
-// (/root/reference/src/tensorrt/img2img_render.cpp:7-66, img2img_load.cpp:29-52, 262-265).
+// (/root/reference/src/tensorrt/img2img_render.cpp:7-66, img2img_load.cpp:29-52, 262-265), and everything the engine derives from the grid by integer
+// arithmetic alone: the strips and shards of a frame spread over devices, the step schedule (batches, passes, slots) and the pipelined parts of a render()
+// call.  Host-only: the CPU suite runs it under the sanitizers (w2x_parse_check tiles / parts, tests/test_render_parts_host.py).
 #pragma once
 #include <cstddef>
 #include <cstdint>
@@ -42,6 +44,51 @@ struct ShardPlan {
     Rect rect[3];                         // output rectangles this part composes (x, y, w, h in canvas pixels)
 };
 ShardPlan shard_plan(const TileGrid& g, int outW, int outH, int tileOutW, int tileOutH, int part, int parts);
+// The canvas cells of the contiguous tile range [t0, t1) into out[0..2]; returns how many rectangles (0 for an empty range or a grid without cells).
+int tile_range_cells(const TileGrid& g, int outW, int outH, int tileOutW, int tileOutH, int t0, int t1, Rect out[3]);
+// shard_plan() of every part into `plans`; false when the plans do not own every tile (shard_plan() hands out nothing when the blend bands are as wide as
+// the tile stride).
+bool shard_plans(const TileGrid& g, int outW, int outH, int tileOut, int parts, std::vector<ShardPlan>& plans);
+// the slab slots a part keeps in front of its own tiles for the blend bands of the preceding parts' tiles [halo_first, first_tile)
+inline size_t halo_slots(const ShardPlan& sp, int steps) { return (size_t)(sp.first_tile - sp.halo_first) * steps; }
+
+// The step schedule of a frame's tiles (img2img_render.cpp:246-267): slot = step index, tile = step / steps, augmentation = step % steps (steps = 8 under TTA,
+// else 1), zero pad slots at the end.  batch_count(): the reference batches (of userB steps) of `tiles` tiles (:249); pass_slots(): the slots of the whole
+// network passes (of B slots, B / userB batches) those batches round up to; last_pass_live(): the live slots of the last of those passes.
+int batch_count(int tiles, int steps, int userB);
+size_t pass_slots(int tiles, int steps, int userB, int B);
+int last_pass_live(int tiles, int steps, int B);
+
+// A whole frame (render()) runs as a few PARTS one after the other: a part's tiles, its canvas cells composed and handed to the download
+// stream, then the next part's while those cells travel to the host - the synchronous contract of img2img_render.cpp:226-344 with most of
+// the 100 MB download of a 4K frame off the critical path: only the last part's cells travel after the last kernel (config 3: 9.9 ms per
+// call as one part, 8.4 as three, profiles/r4_kernels/render_parts_*.txt).  The parts are those of shard_plan() (contiguous tile ranges, canvas cells of their
+// tiles; a part reads the tiles in front of its range from the same slab), cut at multiples of the batch size so that batches, their order
+// and the progress schedule (:246-250, 336-338) are the reference's.
+constexpr int kMaxRenderParts = 4;
+struct RenderParts {
+    struct Part {
+        int first = 0, tiles = 0;             // tiles [first, first + tiles) of the strip
+        int batches = 0, batches_before = 0;  // reference batches of the part, and of the parts in front of it
+        size_t slots_off = 0, slots = 0;      // where the part's steps begin in the slot table, and its pass_slots()
+        int nrect = 0;
+        Rect rect[3];                         // the cells of the part's tiles (tile_range_cells)
+    };
+    int n = 1;
+    Part part[kMaxRenderParts];
+    int batch_total = 0;
+    size_t slot_total = 0;
+    // the frame columns [0, x_split) are what the first part's tiles read: they are uploaded first, the rest while that part computes (tiles are ordered by
+    // column, :43-44, so a part reads a column range).  == cols: the frame travels in one piece
+    int x_split = 0;
+    // the slab holds the frame's tiles in tile order: the last part's passes end at most a pass beyond them, and the frame as ONE part (what a resident replay
+    // runs) ends at most a pass beyond its tiles - slots for both
+    size_t slab_slots = 0;
+};
+// The parts of `strip` (tiles of `grid`, T x T in, Tout x Tout out) of a frame of `cols` columns and an outW x outH canvas.  `want`: how many parts the call
+// may use (1 for a strip of several, a resized frame or a switched-off pipeline); a frame of fewer than 16 tiles or with an overlap that reaches the stride
+// is one part, every other at most min(want, kMaxRenderParts, tiles / 8).
+RenderParts render_parts(const TileGrid& grid, const StripPlan& strip, int cols, int outW, int outH, int T, int Tout, int steps, int userB, int B, int want);
 
 // left/top ramp: w[i] = float(double(i+1)/(ov+1)), i < ov  (img2img_load.cpp:34-45)
 std::vector<float> blend_ramp(int ov);
