@@ -87,6 +87,10 @@ struct RgbaOptions { int bleed = 0; bool skipUniformAlpha = false; };
 enum class Dither { None = 0, Ordered = 1, BlueNoise = 2 };
 struct DitherOptions { Dither mode = Dither::None; unsigned phase = 0; unsigned advance = 0; };
 
+// Extension: chained renders (renderChained*).  quantize: the frame between two stages is rounded to the samples of the source's depth, which is what
+// running the single calls one after the other gives; the default keeps it unrounded.
+struct ChainOptions { bool quantize = false; };
+
 class Img2Img {
 public:
     Img2Img();
@@ -203,6 +207,32 @@ public:
     // output i is the bytes of the single call on frame i, skipUniformAlpha decided per frame.  No progress is reported.
     bool renderSequencePlanarRgba(const PlanarRgbaImage* srcs, PlanarRgbaImage* dsts, int count, const RgbaOptions& opt = {});
     bool renderSequencePlanarRgbaResized(const PlanarRgbaImage* srcs, PlanarRgbaImage* dsts, int count, const RgbaOptions& opt = {}, ResizeFilter filter = ResizeFilter::Bicubic);
+    // Extension: ONE frame through `count` engines one after the other - x4 from two x2 models, x8, x16 - with the frame staying on the device between
+    // them.  count is 2, 3 or 4; the total factor is S, the product of the engines' scaling(); all engines are loaded, live in this process and share one device;
+    // model, noise level, tile size, batch size, TTA, blend and precision may differ from stage to stage, and the same engine may appear more than once.  The
+    // calling convention is renderSharded()'s: driven from the calling thread, engines[0] owns the message and progress callbacks and the chain's device buffers.
+    // Stage 0 reads src as render() / renderPlanar() read it, stage k reads stage k - 1's output, the last stage writes dst as render() / renderResized() / the
+    // planar calls write it: the LAST engine's setDither() and setResizeLight() apply, to the last stage only.  The frame between two stages:
+    //   quantize = false: stage k's canvas clamped to [0, 1], unrounded, in the element type of the CONSUMING engine's tiles (fp16; TF32 / FP32 engines: fp32), the
+    //                     consuming stage's tiles taken from it with gather's replicate padding and TTA maps.  This is the value chain of renderPlanar(dst.bits = 32)
+    //                     followed by renderPlanar(src.bits = 32) - clamp, fp32, clamp, rounded to the tile type - so the bytes are that route's, bit for bit.
+    //   quantize = true:  render()'s bytes at src.depth (planar: renderPlanar()'s at src.bits, an integer depth), read as render() reads a frame: the bytes of
+    //                     calling the single calls one after the other.
+    // renderChained: dst is rows * S x cols * S.  The resized calls: each dimension of dst in [src dim, src dim * S], the two independent, and at least a quarter
+    // of the last stage's canvas (w2x_chain_plan holds the rules); the last stage's canvas is resized as renderResized() does it - so its own ratio may be below 1
+    // (480 rows to 1080 through x2 x2 shrinks a canvas of 1920) -, and at the full size a resized call is the plain one.  No host synchronisation between the
+    // stages: stage k's stream records an event stage k + 1's waits on.  A single call reports progress to engines[0]'s callback: total = the sum over the stages
+    // of ceil(N * steps / batchSize), current = 1 .. total in stage order; the last stage of renderChained() runs in render()'s pipelined parts.  Sequences
+    // (8-bit interleaved frames of one size, page-locked buffers: allocHost()) overlap upload, stages and download like renderSequence(), report nothing, and
+    // output i is the bytes of the single call on frame i.  Refused (false through engines[0]'s message callback, nothing written): a count outside 2 .. 4, a null
+    // or unloaded engine, engines on differing devices, a dst of another size, quantize on float planes, whatever the single calls refuse of src and dst.
+    // Not built: YUV, RGBA and gray chains; strips, shards and several devices for a chained frame; planar sequences.
+    static bool renderChained(Img2Img* const* engines, int count, const Image& src, Image& dst, const ChainOptions& opt = {});
+    static bool renderChainedResized(Img2Img* const* engines, int count, const Image& src, Image& dst, const ChainOptions& opt = {}, ResizeFilter filter = ResizeFilter::Bicubic);
+    static bool renderSequenceChained(Img2Img* const* engines, int count, const Image* srcs, Image* dsts, int n, const ChainOptions& opt = {});
+    static bool renderSequenceChainedResized(Img2Img* const* engines, int count, const Image* srcs, Image* dsts, int n, const ChainOptions& opt = {}, ResizeFilter filter = ResizeFilter::Bicubic);
+    static bool renderChainedPlanar(Img2Img* const* engines, int count, const PlanarImage& src, PlanarImage& dst, const ChainOptions& opt = {});
+    static bool renderChainedPlanarResized(Img2Img* const* engines, int count, const PlanarImage& src, PlanarImage& dst, const ChainOptions& opt = {}, ResizeFilter filter = ResizeFilter::Bicubic);
     void* allocHost(size_t bytes);
     void freeHost(void* data);
     // Page-locks caller-owned memory in place.  Only whole pages are accepted (data and bytes multiples of 4096): a registration
@@ -270,6 +300,9 @@ private:
     bool runPlanar(const PlanarImage* srcs, PlanarImage* dsts, int count, int resizeFilter, const char* who, bool single);   // single: renderPlanar / renderPlanarResized (progress)
     bool runPlanarRgba(const PlanarRgbaImage* srcs, PlanarRgbaImage* dsts, int count, const RgbaOptions& opt, int resizeFilter, const char* who, bool single);
     bool runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, int resizeFilter, const char* who);   // resizeFilter >= 0: renderYuvResized
+    // the six chained calls: n frames, interleaved (srcs / dsts) or planar (psrcs / pdsts; the other pair null); single: one frame with progress
+    static bool runChained(Img2Img* const* engines, int count, const Image* srcs, Image* dsts, const PlanarImage* psrcs, PlanarImage* pdsts, int n, const ChainOptions& opt,
+                           int resizeFilter, const char* who, bool single);
     std::unique_ptr<Impl> impl;
 };
 

@@ -1,5 +1,6 @@
 // Flat C ABI over w2x::Img2Img (declared in include/w2x/c_api.h, which cites the reference interfaces).
 #include "../../include/w2x/c_api.h"
+#include "../../include/w2x/c_api_chain.h"
 #include "../../include/w2x/c_api_dither.h"
 #include "../../include/w2x/c_api_gray.h"
 #include "../../include/w2x/c_api_planar.h"
@@ -391,6 +392,70 @@ size_t w2x_planar_plane_bytes(int rows, int cols, int bits) {
     if (rows <= 0 || cols <= 0 || !(bits == 8 || bits == 10 || bits == 12 || bits == 16 || bits == 32)) return 0;
     return (size_t)rows * cols * (bits == 32 ? 4 : bits > 8 ? 2 : 1);
 }
+// chained renders (include/w2x/c_api_chain.h): the engines of the handles, or nothing where one is missing
+static std::vector<w2x::Img2Img*> chain_engines(w2x_engine* const* engines, int count) {
+    std::vector<w2x::Img2Img*> es;
+    if (!engines || count <= 0 || count > 64) return es;
+    for (int k = 0; k < count; ++k) { if (!engines[k]) return {}; es.push_back(&engines[k]->engine); }
+    return es;
+}
+static w2x::ChainOptions chain_options(int quantize) { w2x::ChainOptions o; o.quantize = quantize != 0; return o; }
+static int chain_total(const std::vector<w2x::Img2Img*>& es) { int S = 1; for (w2x::Img2Img* e : es) S *= e->scaling() > 0 && e->scaling() <= 4 ? e->scaling() : 1; return S; }
+int w2x_chain_plan(int rows, int cols, const int* scalings, int count, int dst_rows, int dst_cols, int* out) {
+    w2x::ChainPlan cp;
+    const w2x::ChainRefusal why = w2x::chain_plan(rows, cols, scalings, count, dst_rows, dst_cols, cp);
+    if (why != w2x::kChainOk || !out) return why != w2x::kChainOk ? (int)why : W2X_CHAIN_COUNT;
+    for (int k = 0; k <= count; ++k) { out[2 * k] = cp.rows[k]; out[2 * k + 1] = cp.cols[k]; }
+    out[2 * count + 2] = cp.out_rows; out[2 * count + 3] = cp.out_cols; out[2 * count + 4] = cp.S;
+    return W2X_CHAIN_OK;
+}
+int w2x_render_chained(w2x_engine* const* engines, int count, const void* src, int rows, int cols, size_t src_step, void* dst, size_t dst_step, int depth, int quantize) {
+    const std::vector<w2x::Img2Img*> es = chain_engines(engines, count);
+    if (es.empty()) return 0;
+    const int S = chain_total(es);
+    w2x::Image d = image(dst, rows * S, cols * S, dst_step, depth);
+    return w2x::Img2Img::renderChained(es.data(), count, image(src, rows, cols, src_step, depth), d, chain_options(quantize)) ? 1 : 0;
+}
+int w2x_render_chained_resized(w2x_engine* const* engines, int count, const void* src, int rows, int cols, size_t src_step, void* dst, int dst_rows, int dst_cols,
+                               size_t dst_step, int depth, int quantize, int filter) {
+    const std::vector<w2x::Img2Img*> es = chain_engines(engines, count);
+    w2x::ResizeFilter f;
+    if (es.empty() || !resize_filter(engines[0], filter, "w2x_render_chained_resized", f)) return 0;
+    w2x::Image d = image(dst, dst_rows, dst_cols, dst_step, depth);
+    return w2x::Img2Img::renderChainedResized(es.data(), count, image(src, rows, cols, src_step, depth), d, chain_options(quantize), f) ? 1 : 0;
+}
+int w2x_render_sequence_chained(w2x_engine* const* engines, int count, const void* const* srcs, int rows, int cols, size_t src_step, void* const* dsts, size_t dst_step,
+                                int frames, int quantize) {
+    const std::vector<w2x::Img2Img*> es = chain_engines(engines, count);
+    if (es.empty() || !sequence_ok(engines[0], frames, srcs, dsts)) return 0;
+    const int S = chain_total(es);
+    ImageSequence q = image_sequence((const uint8_t* const*)srcs, image(nullptr, rows, cols, src_step), (uint8_t* const*)dsts, image(nullptr, rows * S, cols * S, dst_step), frames);
+    return w2x::Img2Img::renderSequenceChained(es.data(), count, q.src.data(), q.dst.data(), frames, chain_options(quantize)) ? 1 : 0;
+}
+int w2x_render_sequence_chained_resized(w2x_engine* const* engines, int count, const void* const* srcs, int rows, int cols, size_t src_step, void* const* dsts,
+                                        int dst_rows, int dst_cols, size_t dst_step, int frames, int quantize, int filter) {
+    const std::vector<w2x::Img2Img*> es = chain_engines(engines, count);
+    w2x::ResizeFilter f;
+    if (es.empty() || !sequence_ok(engines[0], frames, srcs, dsts) || !resize_filter(engines[0], filter, "w2x_render_sequence_chained_resized", f)) return 0;
+    ImageSequence q = image_sequence((const uint8_t* const*)srcs, image(nullptr, rows, cols, src_step), (uint8_t* const*)dsts, image(nullptr, dst_rows, dst_cols, dst_step), frames);
+    return w2x::Img2Img::renderSequenceChainedResized(es.data(), count, q.src.data(), q.dst.data(), frames, chain_options(quantize), f) ? 1 : 0;
+}
+int w2x_render_chained_planes(w2x_engine* const* engines, int count, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                              void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int quantize) {
+    const std::vector<w2x::Img2Img*> es = chain_engines(engines, count);
+    if (es.empty()) return 0;
+    w2x::PlanarImage d = planar_image(dst_planes, dst_steps, dst_rows, dst_cols, dst_bits);
+    return w2x::Img2Img::renderChainedPlanar(es.data(), count, planar_image(src_planes, src_steps, rows, cols, src_bits), d, chain_options(quantize)) ? 1 : 0;
+}
+int w2x_render_chained_planes_resized(w2x_engine* const* engines, int count, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
+                                      void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int quantize, int filter) {
+    const std::vector<w2x::Img2Img*> es = chain_engines(engines, count);
+    w2x::ResizeFilter f;
+    if (es.empty() || !resize_filter(engines[0], filter, "w2x_render_chained_planes_resized", f)) return 0;
+    w2x::PlanarImage d = planar_image(dst_planes, dst_steps, dst_rows, dst_cols, dst_bits);
+    return w2x::Img2Img::renderChainedPlanarResized(es.data(), count, planar_image(src_planes, src_steps, rows, cols, src_bits), d, chain_options(quantize), f) ? 1 : 0;
+}
+
 // planar RGBA frames (include/w2x/c_api_rgbap.h)
 int w2x_render_rgbap(w2x_engine* e, const void* const* src_planes, const size_t* src_steps, int rows, int cols, int src_bits,
                      void* const* dst_planes, const size_t* dst_steps, int dst_rows, int dst_cols, int dst_bits, int bleed, int skip_uniform_alpha) {

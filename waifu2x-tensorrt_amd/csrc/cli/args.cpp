@@ -100,6 +100,12 @@ std::string usage() {
            "                              --alpha-bleed (not on gbrapf32le input) and --alpha-skip-uniform apply to them, as do --outscale / --outsize and --devices.\n"
            "                              With --rgba-out and no --pix_fmt the encoder's format is the --rgba-out one.  Stills, single frames read through ffmpeg\n"
            "                              and the built-in AVI route are rendered as without them.  Not with --colorspace, --gray, --rgb-in or --rgb-out\n"
+           "      --chain INT             (extension) {2,3,4}: the frame goes through INT engines one after the other on the GPU - x4 from a x2 model, x8, x16 - the\n"
+           "                              first --model at --scale and --noise, the others --model at --scale and --chain-noise; --outscale / --outsize then range\n"
+           "                              up to scale^INT (and down to a quarter of it).  Stills without alpha and videos as bgr24 or --rgb-in / --rgb-out frames, on one\n"
+           "                              device.  Not with --colorspace, --gray, --rgba-in / --rgba-out, --alpha-bleed or --devices.  build: builds every stage's engine\n"
+           "      --chain-noise INT [-1]  (extension) {-1,0,1,2,3}: the noise level of the stages behind the first; -1: they only scale\n"
+           "      --chain-quantize        (extension) round the frame between two stages to the input's depth: the bytes of running the tool INT times\n"
            "      --dither TEXT [none]    (extension) {none,ordered,bluenoise}: dither every 8- to 16-bit sample written instead of rounding it - an 8 x 8 Bayer\n"
            "                              matrix or a 64 x 64 blue-noise table, on the GPU where the unrounded value is; smooth gradients leave without bands.\n"
            "                              Alpha and float output are never dithered.  Every route honours it\n"
@@ -130,7 +136,7 @@ int rgba_format_bits(const std::string& name) {
 Options parse(int argc, const char* const* argv) {
     Options o;
     std::vector<std::string> a(argv + 1, argv + argc);
-    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_outsize = false, seen_filter = false, seen_colorspace = false, seen_range = false, seen_bleed = false, seen_skip = false, seen_pixfmt = false, seen_gray = false, seen_dither = false, seen_light = false;
+    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_outsize = false, seen_filter = false, seen_colorspace = false, seen_range = false, seen_bleed = false, seen_skip = false, seen_pixfmt = false, seen_gray = false, seen_dither = false, seen_light = false, seen_chain = false, seen_chain_noise = false;
     auto value = [&](size_t& i) -> std::string {
         const std::string name = a[i];
         auto eq = name.find('=');
@@ -184,6 +190,9 @@ Options parse(int argc, const char* const* argv) {
         else if (k == "--alpha-bleed") { o.alphaBleed = to_int(k, value(i)); seen_bleed = true; }
         else if (k == "--alpha-skip-uniform") { o.alphaSkipUniform = true; seen_skip = true; }
         else if (k == "--gray") { o.gray = true; seen_gray = true; }
+        else if (k == "--chain") { o.chain = to_int(k, value(i)); seen_chain = true; }
+        else if (k == "--chain-noise") { o.chainNoise = to_int(k, value(i)); seen_chain_noise = true; }
+        else if (k == "--chain-quantize") o.chainQuantize = true;
         else if (k == "--dither") { o.dither = value(i); std::transform(o.dither.begin(), o.dither.end(), o.dither.begin(), ::tolower); seen_dither = true; }
         else if (k == "--dither-temporal") { o.ditherTemporal = true; seen_dither = true; }
         else if (k == "--resize-light") { o.resizeLight = value(i); std::transform(o.resizeLight.begin(), o.resizeLight.end(), o.resizeLight.begin(), ::tolower); seen_light = true; }
@@ -218,6 +227,15 @@ Options parse(int argc, const char* const* argv) {
     if (o.devices < 1) throw std::runtime_error("--devices: number must be positive");
     member<std::string>("--split", o.split, {"shards", "strips"});
     member<std::string>("--precision", o.precision, {"fp16", "tf32", "fp32"});   // fp32: an addition (include/w2x/config.h)
+    // --chain (extension): N stages of --model at --scale; the stages behind the first take --chain-noise
+    if (seen_chain) {
+        member("--chain", o.chain, {2, 3, 4});
+        member("--chain-noise", o.chainNoise, {-1, 0, 1, 2, 3});
+        if (o.command == "render" || o.command == "build") {
+            if (o.scale == 1) throw std::runtime_error("--chain: needs --scale 2 or 4 (a chain of scale 1 stages leaves the size as it is)");
+        }
+        if (o.devices > 1) throw std::runtime_error("--chain: not with --devices " + std::to_string(o.devices) + " (a chained frame is rendered on one device)");
+    } else if (seen_chain_noise || o.chainQuantize) throw std::runtime_error(std::string(seen_chain_noise ? "--chain-noise" : "--chain-quantize") + ": needs --chain");
     const bool seen_yuv_in = !o.yuvIn.empty(), seen_yuv_out = !o.yuvOut.empty(), seen_loc = !o.chromaLoc.empty();
     const bool seen_rgb_in = !o.rgbIn.empty(), seen_rgb_out = !o.rgbOut.empty();
     const bool seen_rgba_in = !o.rgbaIn.empty(), seen_rgba_out = !o.rgbaOut.empty();
@@ -231,8 +249,12 @@ Options parse(int argc, const char* const* argv) {
         member<std::string>("--tta-mode", o.ttaMode, {"mean", "reference"});
         if (o.ttaMode == "reference" && !o.tta) throw std::runtime_error("--tta-mode reference: needs --tta");
         if (seen_outscale) {
-            if (!(o.outscale >= 1.0 && o.outscale <= o.scale)) {
-                std::ostringstream os; os << "--outscale: " << o.outscale << " not in [1, " << o.scale << "] (the output is a downsample of the --scale network's)";
+            if (!(o.outscale >= 1.0 && o.outscale <= total_scale(o))) {
+                std::ostringstream os; os << "--outscale: " << o.outscale << " not in [1, " << total_scale(o) << "] (the output is a downsample of the --scale network's)";
+                throw std::runtime_error(os.str());
+            }
+            if (seen_chain && o.outscale * 4 < total_scale(o)) {
+                std::ostringstream os; os << "--outscale: " << o.outscale << " is below a quarter of the chain's factor " << total_scale(o) << " (the last stage's output shrinks by 4 at most)";
                 throw std::runtime_error(os.str());
             }
             member<std::string>("--resize-filter", o.resizeFilter, {"bicubic", "bilinear"});
@@ -288,6 +310,12 @@ Options parse(int argc, const char* const* argv) {
             if (seen_rgb_in || seen_rgb_out) throw std::runtime_error(std::string(opt) + ": not together with " + (seen_rgb_in ? "--rgb-in" : "--rgb-out") + " (one raw frame format per run)");
         }
         if (seen_rgba_out && !seen_pixfmt) o.pixFmt = o.rgbaOut;
+        if (seen_chain) {      // chained frames are interleaved or planar RGB on one device
+            if (seen_colorspace) throw std::runtime_error("--chain: not together with --colorspace (a YUV chain is not built)");
+            if (seen_gray) throw std::runtime_error("--chain: not together with --gray (a gray chain is not built)");
+            if (seen_rgba_in || seen_rgba_out) throw std::runtime_error(std::string("--chain: not together with ") + (seen_rgba_in ? "--rgba-in" : "--rgba-out") + " (an RGBA chain is not built)");
+            if (seen_bleed || seen_skip) throw std::runtime_error(std::string("--chain: not together with ") + (seen_bleed ? "--alpha-bleed" : "--alpha-skip-uniform") + " (an RGBA chain is not built)");
+        }
         if (seen_dither) {
             member<std::string>("--dither", o.dither, {"none", "ordered", "bluenoise"});
             if (o.ditherTemporal && o.dither == "none") throw std::runtime_error("--dither-temporal: needs --dither ordered or --dither bluenoise");
@@ -311,9 +339,16 @@ Options parse(int argc, const char* const* argv) {
     return o;
 }
 
-std::string model_path(const Options& o) {
-    return o.models + "/" + o.model + "/" + (o.noise == -1 ? "" : "noise" + std::to_string(o.noise) + "_") +
+static std::string model_file(const Options& o, int noise) {
+    return o.models + "/" + o.model + "/" + (noise == -1 ? "" : "noise" + std::to_string(noise) + "_") +
            (o.scale == 1 ? "" : "scale" + std::to_string(o.scale) + "x") + ".onnx";
+}
+std::string model_path(const Options& o) { return model_file(o, o.noise); }
+std::string chain_model_path(const Options& o) { return model_file(o, o.chainNoise); }
+int total_scale(const Options& o) {
+    int s = o.scale;
+    for (int k = 1; k < o.chain; ++k) s *= o.scale;
+    return s;
 }
 
 static std::string outscale_tag(const Options& o) {
@@ -327,12 +362,12 @@ std::string output_suffix(const Options& o) {
     std::string m = o.model;
     std::replace(m.begin(), m.end(), '/', '_');
     return "(" + m + ")" + (o.noise == -1 ? "" : "(noise" + std::to_string(o.noise) + ")") +
-           (o.scale == 1 ? "" : "(scale" + std::to_string(o.scale) + ")") + outscale_tag(o) + (o.tta ? "(tta)" : "");
+           (o.scale == 1 ? "" : "(scale" + std::to_string(o.scale) + ")") + (o.chain > 1 ? "(chain" + std::to_string(o.chain) + ")" : "") + outscale_tag(o) + (o.tta ? "(tta)" : "");
 }
 
 int out_dim(const Options& o, int dim, bool width) {
     if (o.outsizeW > 0) return width ? o.outsizeW : o.outsizeH;
-    return o.outscale > 0 ? (int)std::lround(dim * o.outscale) : dim * o.scale;
+    return o.outscale > 0 ? (int)std::lround(dim * o.outscale) : dim * total_scale(o);
 }
 
 std::string output_path(const Options& o, const std::string& input, bool single_frame) {
@@ -359,6 +394,8 @@ std::string to_json(const Options& o) {
        << ", \"alpha_bleed\": " << o.alphaBleed << ", \"alpha_skip_uniform\": " << (o.alphaSkipUniform ? "true" : "false") << ", \"gray\": " << (o.gray ? "true" : "false")
        << ", \"rgb_in\": " << (o.rgbIn.empty() ? std::string("null") : q(o.rgbIn)) << ", \"rgb_out\": " << (o.rgbOut.empty() ? std::string("null") : q(o.rgbOut))
        << ", \"rgba_in\": " << (o.rgbaIn.empty() ? std::string("null") : q(o.rgbaIn)) << ", \"rgba_out\": " << (o.rgbaOut.empty() ? std::string("null") : q(o.rgbaOut))
+       << ", \"chain\": " << o.chain << ", \"chain_noise\": " << o.chainNoise << ", \"chain_quantize\": " << (o.chainQuantize ? "true" : "false")
+       << ", \"chain_model_path\": " << (o.chain > 1 ? q(chain_model_path(o)) : std::string("null"))
        << ", \"dither\": " << q(o.dither) << ", \"dither_temporal\": " << (o.ditherTemporal ? "true" : "false")
        << ", \"codec\": " << q(o.codec) << ", \"pix_fmt\": " << q(o.pixFmt) << ", \"crf\": " << o.crf << ", \"inputs\": [";
     for (size_t i = 0; i < o.inputs.size(); ++i) os << (i ? ", " : "") << q(o.inputs[i]);

@@ -58,6 +58,10 @@ struct Options {
     bool ditherTemporal = false;          // --dither-temporal: videos move the pattern from frame to frame (DitherOptions::advance = 1); default: a still pattern
     std::string rgbaIn, rgbaOut;          // --rgba-in / --rgba-out FMT (extension, render only; kRgbaFormats): videos read through ffmpeg travel as raw planar RGBA frames
                                           // of these formats (Img2Img::renderSequencePlanarRgba*, with --alpha-bleed / --alpha-skip-uniform); the encoder's format as with --rgb-out
+    int chain = 1;                        // --chain N (extension; 2..4): the frame goes through N engines one after the other on the GPU (Img2Img::renderChained*):
+                                          // stage 1 is --model at --scale and --noise, the stages behind it --model at --scale and --chain-noise; 1 = not given
+    int chainNoise = -1;                  // --chain-noise L [-1]: the noise level of the stages behind the first (-1: they only scale - the rule of waifu2x-caffe)
+    bool chainQuantize = false;           // --chain-quantize: the frame between two stages is rounded to the samples of the input's depth (ChainOptions::quantize)
     bool printConfig = false;             // --print-config: dump the parsed options and derived names as JSON and exit (tests)
     bool help = false;
 };
@@ -76,6 +80,10 @@ std::string usage();
 
 // models/<model>/[noiseN_][scaleSx].onnx  (main.cpp:201-204)
 std::string model_path(const Options& o);
+// the model of the stages of a --chain behind the first: --model at --scale and --chain-noise
+std::string chain_model_path(const Options& o);
+// the factor between input and network output: --scale, with --chain N its N-th power
+int total_scale(const Options& o);
 // "(model_with_underscores)(noiseN)(scaleS)(tta)"  (main.cpp:205-209); with --outscale F "(outscale<F as %g>)", with --outsize WxH "(WxH)" after (scaleS)
 std::string output_suffix(const Options& o);
 // output file name for one input (main.cpp:240-257): directory override, suffix, .png for stills / .mp4 for videos

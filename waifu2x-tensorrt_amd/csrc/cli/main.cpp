@@ -225,7 +225,10 @@ int main(int argc, char** argv) {
             c.minBatchSize = c.optBatchSize = c.maxBatchSize = o.batchSize;
             c.minChannels = c.optChannels = c.maxChannels = 3;                       // main.cpp:280-282
             c.minWidth = c.optWidth = c.maxWidth = c.minHeight = c.optHeight = c.maxHeight = o.tileSize;
-            return engine.build(modelPath, c) ? 0 : -1;
+            if (!engine.build(modelPath, c)) return -1;
+            // --chain: the engine file of the stages behind the first, where they take another model file
+            if (o.chain > 1 && cli::chain_model_path(o) != modelPath && !engine.build(cli::chain_model_path(o), c)) return -1;
+            return 0;
         }
 
         // render: one engine per device
@@ -243,6 +246,26 @@ int main(int argc, char** argv) {
             c.overlapX = c.overlapY = o.blend; c.tta = o.tta; c.ttaBugCompat = o.ttaMode == "reference";
             if (!engines.back()->load(modelPath, c)) return -1;
         }
+        // --chain: the stages of a chained frame - engines[0], then the engine of the stages behind it (one engine, run chain - 1 times; engines[0] again
+        // where --chain-noise is --noise).  Img2Img::renderChained* drive them; the frame stays on the device in between.
+        std::unique_ptr<Img2Img> chainEngine;
+        std::vector<Img2Img*> stages;
+        if (o.chain > 1) {
+            Img2Img* later = engines[0].get();
+            if (cli::chain_model_path(o) != modelPath) {
+                chainEngine.reset(new Img2Img);
+                chainEngine->setMessageCallback(on_message);
+                RenderConfig c;
+                c.deviceId = o.device; c.precision = prec; c.batchSize = o.batchSize; c.channels = 3; c.height = c.width = o.tileSize; c.scaling = o.scale;
+                c.overlapX = c.overlapY = o.blend; c.tta = o.tta; c.ttaBugCompat = o.ttaMode == "reference";
+                if (!chainEngine->load(cli::chain_model_path(o), c)) return -1;
+                later = chainEngine.get();
+            }
+            stages.push_back(engines[0].get());
+            for (int k = 1; k < o.chain; ++k) stages.push_back(later);
+        }
+        ChainOptions chainOptions;
+        chainOptions.quantize = o.chainQuantize;
         // --dither: a setting of the engines, so every route below - stills, --deep, --gray, the colour of alpha PNGs, every raw video format, --outscale /
         // --outsize - writes dithered samples without knowing about it; a video moves the pattern per frame with --dither-temporal.  dither_on(false) switches it
         // off around the one thing that must not be dithered and is rendered as a frame of its own: the alpha plane of the two-call routes.
@@ -254,6 +277,7 @@ int main(int argc, char** argv) {
         const ResizeLight light = o.resizeLight == "srgb" ? ResizeLight::LinearSrgb : o.resizeLight == "bt709" ? ResizeLight::LinearBt709 : ResizeLight::Gamma;
         auto dither_on = [&](bool on) {
             for (auto& e : engines) if (!e->setDither(on ? ditherOptions : DitherOptions()) || !e->setResizeLight(on ? light : ResizeLight::Gamma)) return false;
+            if (chainEngine && (!chainEngine->setDither(on ? ditherOptions : DitherOptions()) || !chainEngine->setResizeLight(on ? light : ResizeLight::Gamma))) return false;   // (the last stage's settings count)
             return true;
         };
         if (!dither_on(true)) return -1;
@@ -262,10 +286,12 @@ int main(int argc, char** argv) {
         const bool resize = o.outscale > 0 || o.outsizeW > 0;
         // --outsize: an input the size cannot be reached from stops the run
         auto check_outsize = [&](const std::string& file, int w, int h) {
-            if (o.outsizeW <= 0 || (o.outsizeW >= w && o.outsizeW <= w * o.scale && o.outsizeH >= h && o.outsizeH <= h * o.scale)) return;
+            const int total = cli::total_scale(o);
+            const bool shrink_ok = o.chain <= 1 || ((long)o.outsizeW * 4 >= (long)w * total && (long)o.outsizeH * 4 >= (long)h * total);   // (the last stage of a chain shrinks by 4 at most)
+            if (o.outsizeW <= 0 || (o.outsizeW >= w && o.outsizeW <= w * total && o.outsizeH >= h && o.outsizeH <= h * total && shrink_ok)) return;
             throw std::runtime_error(file + ": --outsize " + std::to_string(o.outsizeW) + "x" + std::to_string(o.outsizeH) + " cannot be reached from this " + std::to_string(w) + "x" +
-                                     std::to_string(h) + " input: the output must lie between " + std::to_string(w) + "x" + std::to_string(h) + " and " + std::to_string(w * o.scale) + "x" +
-                                     std::to_string(h * o.scale) + " (--scale " + std::to_string(o.scale) + ")");
+                                     std::to_string(h) + " input: the output must lie between " + std::to_string(w) + "x" + std::to_string(h) + " and " + std::to_string(w * total) + "x" +
+                                     std::to_string(h * total) + " (--scale " + std::to_string(o.scale) + (o.chain > 1 ? ", --chain " + std::to_string(o.chain) + ": and no less than a quarter of the latter" : "") + ")");
         };
         const std::vector<std::string> files = find_inputs(o);
         fileCount = files.size();
@@ -289,7 +315,9 @@ int main(int argc, char** argv) {
                     out.bgr.resize((size_t)out.rows * out.cols * 3);
                     src = Image{in.bgr.data(), in.rows, in.cols, (size_t)in.cols * 3}; dst = Image{out.bgr.data(), out.rows, out.cols, (size_t)out.cols * 3};
                 }
+                if (o.chain > 1 && !in.alpha.empty()) throw std::runtime_error(file + ": --chain renders no alpha channel (an RGBA chain is not built)");
                 auto render_still = [&](const Image& s0, Image& d0) {
+                    if (o.chain > 1) return resize ? Img2Img::renderChainedResized(stages.data(), o.chain, s0, d0, chainOptions, filter) : Img2Img::renderChained(stages.data(), o.chain, s0, d0, chainOptions);
                     if (resize) return engines[0]->renderResized(s0, d0, filter);
                     if (o.devices == 1) return engines[0]->render(s0, d0);
                     // every tile once: engine k takes the k-th contiguous range of the tile order, the seam bands travel device to device, each
@@ -425,6 +453,8 @@ int main(int argc, char** argv) {
                 RenderFrames render = [&](Img2Img& e, uint8_t* const* in, uint8_t* const* out, int n) {
                     std::vector<Image> si(n), di(n);
                     for (int k = 0; k < n; ++k) { si[k] = Image{in[k], height, width, (size_t)width * 3}; di[k] = Image{out[k], outH, outW, (size_t)outW * 3}; }
+                    if (o.chain > 1) return resize ? Img2Img::renderSequenceChainedResized(stages.data(), o.chain, si.data(), di.data(), n, chainOptions, filter)
+                                                   : Img2Img::renderSequenceChained(stages.data(), o.chain, si.data(), di.data(), n, chainOptions);
                     return resize ? e.renderSequenceResized(si.data(), di.data(), n, filter) : e.renderSequence(si.data(), di.data(), n);
                 };
                 if (gray) render = [&](Img2Img& e, uint8_t* const* in, uint8_t* const* out, int n) {
@@ -444,6 +474,11 @@ int main(int argc, char** argv) {
                         return f;
                     };
                     for (int k = 0; k < n; ++k) { si[k] = frame(in[k], height, width, rgbInBits); di[k] = frame(out[k], outH, outW, rgbOutBits); }
+                    if (o.chain > 1) {      // (a chained planar sequence is not built: frame by frame)
+                        for (int k = 0; k < n; ++k)
+                            if (!(resize ? Img2Img::renderChainedPlanarResized(stages.data(), o.chain, si[k], di[k], chainOptions, filter) : Img2Img::renderChainedPlanar(stages.data(), o.chain, si[k], di[k], chainOptions))) return false;
+                        return true;
+                    }
                     return resize ? e.renderSequencePlanarResized(si.data(), di.data(), n, filter) : e.renderSequencePlanar(si.data(), di.data(), n);
                 };
                 // a raw gbrap* frame: G, B, R, A; PlanarRgbaImage wants R, G, B, A

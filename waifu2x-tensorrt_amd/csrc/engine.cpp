@@ -187,7 +187,8 @@ struct Img2Img::Impl {
     // logger.cpp:14-22
     void log(Severity s, const std::string& m) { if (messageCallback) messageCallback(s, m); }
     void log(Severity s, const std::string& m, const std::string& fn, int line) { if (messageCallback) messageCallback(s, "[" + fn + "@" + std::to_string(line) + "] " + m); }
-    void log(int current, int total, double speed) { if (progressCallback) progressCallback(current, total, speed); }
+    void log(int current, int total, double speed) { Impl* const to = report_to ? report_to : this; if (to->progressCallback) to->progressCallback(current, total, speed); }
+    Impl* report_to = nullptr;           // a stage of a chained render: the engine whose progress callback hears of its batches (engines[0]); else null
 
     bool loaded = false;
     int device = -1;                   // physical HIP ordinal this engine lives on (set by load)
@@ -317,6 +318,11 @@ struct Img2Img::Impl {
     // two jobs above - job.planar the depths, job.rgba bleed, skip, alpha_slot0, uniform and value (the key of the uniform plane: its clamped code, float: the bits of
     // its clamped value) - and its frame step is rgba_frame().  d_frame / d_out hold four planes R, G, B, A (planar_layout); alpha_bleed_planes_kernel writes the three
     // colour planes into d_bgr and the alpha plane into d_alpha (planes of in_bits samples, rows padded as in planar_layout), which gather_planes_rgba_kernel reads.
+    // A stage of a chained render (runChained) keeps the kind of the chain's frames and replaces one side or both: src set - the stage's tiles are
+    // gathered from a device frame of tile pixels (gather_px_kernel; [rows][cols][4] of THIS engine's tile type) instead of d_frame; dst set - the frame ends with
+    // compose_px_kernel into that frame (of the NEXT engine's tile type, dst_fp32) instead of the format's compose into d_out.  A quantised chain sets neither: its
+    // stages run the format's own kernels with d_frame / d_out pointed at the chain's buffers.
+    struct ChainJob { const void* src = nullptr; void* dst = nullptr; bool dst_fp32 = false; };
     // The kind of frame the running entry point renders.  Only the block "the frame formats" below branches on it: the key of the captured passes, the
     // gather (gather_tiles), the end of a frame (finish_frame), the device layout of a frame, the slot tables of a call.  The default is a plain BGR frame, not
     // resized.  The kind is set in three places - runSequenceYuv, the RGBA calls (rgba_call), runGray, runPlanar, runPlanarRgba - between the call's checks and run_call();
@@ -329,6 +335,7 @@ struct Img2Img::Impl {
         RgbaJob rgba;
         GrayJob gray;
         PlanarJob planar;
+        ChainJob chain;
     };
     // Dithered output (setDither): a setting of the engine like the callbacks, NOT part of the job - it outlives the call that follows it and every
     // load().  The launches that end a frame (finish_frame, outside the captured passes) read it through dither_now(), so a changed setting acts on the very
@@ -354,6 +361,28 @@ struct Img2Img::Impl {
     LightArgs light_now() const { return light_args((int)light); }
     Job job;
     struct JobScope { Impl* im; ~JobScope() { im->job = Job{}; } };
+    // Chained renders (runChained).  On engines[0]: the frames between the stages (d_chain[k]: stage k's output) and the events that order the
+    // stages' streams - ev_chain_done[k]: stage k's frame is whole; ev_chain_read[k]: stage k + 1 has gathered its tiles out of d_chain[k] (a sequence's next
+    // frame may overwrite it).  Plain allocations: no captured pass of THIS engine is tied to them beyond its key, which holds the address.
+    // On every engine, per stage index it runs: slot and liveness tables of that stage's own grid (an engine that appears twice runs two grids in one call, and
+    // the host side of an upload must stay untouched until the stream has taken it), swapped into d_slots / d_live / h_slots / h_live for the stage's duration.
+    static constexpr int kChainStages = 4;
+    void* d_chain[kChainStages - 1] = {nullptr, nullptr, nullptr}; size_t chain_cap[kChainStages - 1] = {0, 0, 0};
+    hipEvent_t ev_chain_done[kChainStages] = {nullptr, nullptr, nullptr, nullptr}, ev_chain_read[kChainStages - 1] = {nullptr, nullptr, nullptr};
+    struct StageTables { TileSlot* d_slots = nullptr; size_t slots_cap = 0; LiveExt* d_live = nullptr; size_t live_cap = 0, live_stride = 0; std::vector<LiveExt> h_live; std::vector<TileSlot> h_slots; };
+    StageTables chain_tables[kChainStages];
+    void swap_tables(int k) {
+        StageTables& t = chain_tables[k];
+        std::swap(d_slots, t.d_slots); std::swap(slots_cap, t.slots_cap); std::swap(d_live, t.d_live); std::swap(live_cap, t.live_cap); std::swap(live_stride, t.live_stride);
+        h_live.swap(t.h_live); h_slots.swap(t.h_slots);
+    }
+    void ensure_chain(int k, size_t bytes) {
+        if (bytes <= chain_cap[k]) return;
+        if (d_chain[k]) hipAssert(hipFree(d_chain[k]));
+        d_chain[k] = nullptr; chain_cap[k] = 0;
+        hipAssert(hipMalloc(&d_chain[k], bytes));
+        chain_cap[k] = bytes;
+    }
     std::vector<void*> pinned;
     std::vector<void*> host_allocs;     // allocHost(): page-locked buffers handed to the caller
     std::vector<TileSlot> h_slots;
@@ -426,6 +455,7 @@ struct Img2Img::Impl {
     static constexpr int kGrayKey = 65;   // 65 / 66: gray frames of 8 / 16 bits
     static constexpr int kPlanarKey = 67; // 67 .. 71: planar frames whose input samples have 8 / 10 / 12 / 16 / 32 bits
     static constexpr int kPlanarRgbaKey = 72; // 72 .. 76: planar RGBA frames, by input depth likewise
+    static constexpr int kChainKey = 80;      // a stage of a chained render that gathers from a frame of tile pixels (whatever the chain's frame format)
     using GraphKey = std::tuple<const void*, const void*, const void*, const void*, int, int, int, int>;   // frame, slots, slab out, arena, rows, cols, live, sample format (1: 16-bit, >= 2: YuvJob::key)
     // A pass that runs as NG tile groups is NG graphs, one per group, each a straight line of launches replayed on that group's OWN stream (fork / join
     // events between the streams are issued around the replays): a single captured graph with NG branches runs its side branches on streams the runtime
@@ -470,6 +500,10 @@ struct Img2Img::Impl {
         rs_tables.clear(); job = Job{}; d_noise = nullptr;
         if (d_canvas) { (void)hipFree(d_canvas); d_canvas = nullptr; }
         canvas_cap = 0;
+        for (int k = 0; k + 1 < kChainStages; ++k) { if (d_chain[k]) (void)hipFree(d_chain[k]); d_chain[k] = nullptr; chain_cap[k] = 0; if (ev_chain_read[k]) { (void)hipEventDestroy(ev_chain_read[k]); ev_chain_read[k] = nullptr; } }
+        for (hipEvent_t& e : ev_chain_done) if (e) { (void)hipEventDestroy(e); e = nullptr; }
+        for (StageTables& t : chain_tables) { if (t.d_slots) (void)hipFree(t.d_slots); if (t.d_live) (void)hipFree(t.d_live); t = StageTables{}; }
+        report_to = nullptr;
         for (void** q : {(void**)&d_bgr, (void**)&d_alpha, (void**)&d_minmax}) if (*q) { (void)hipFree(*q); *q = nullptr; }
         bgr_cap = alpha_cap = 0;
         if (h_minmax) { if (hipHostFree(h_minmax) != hipSuccess) (void)hipGetLastError(); h_minmax = nullptr; }
@@ -1096,6 +1130,7 @@ struct Img2Img::Impl {
     // The key of a captured pass: the sample format - 0 / 1 BGR of 8 / 16 bits, 2 .. 49 YuvJob::key, kRgbaKey, kGrayKey / kGrayKey + 1 gray of 8 / 16 bits, kPlanarKey .. + 4 planar by
     // input depth, kPlanarRgbaKey .. + 4 planar RGBA likewise - and the buffer the pass's gather reads (an RGBA or planar RGBA pass reads d_bgr / d_alpha, never d_frame: its graphs do not depend on which frame buffer of a sequence is current)
     int sample_format() const {
+        if (job.chain.src) return kChainKey;
         switch (job.kind) {
             case Job::YUV: return job.yuv.key;
             case Job::RGBA: return kRgbaKey;
@@ -1108,7 +1143,7 @@ struct Img2Img::Impl {
     // gray and planar frames: the sample depth of the frame (`out`: of the output) and its planes in d_frame / d_out
     int plane_bits(bool out) const { return job.kind == Job::GRAY ? (job.gray.deep ? 16 : 8) : out ? job.planar.out_bits : job.planar.in_bits; }
     PlanarPlanes frame_planes(uint8_t* base, int rows, int cols, bool out) const { return planar_layout(base, rows, cols, plane_bits(out), job.kind == Job::GRAY ? 1 : 3); }
-    const void* pass_source() const { return two_tile_sets() ? (const void*)d_bgr : (const void*)d_frame; }
+    const void* pass_source() const { return job.chain.src ? job.chain.src : two_tile_sets() ? (const void*)d_bgr : (const void*)d_frame; }
     // RGBA and planar RGBA frames: colour tiles and alpha tiles in one schedule (rgba_setup, rgba_frame), gathered from d_bgr / d_alpha
     bool two_tile_sets() const { return job.kind == Job::RGBA || job.kind == Job::PLANAR_RGBA; }
     RgbaPlanes rgba_planes(uint8_t* base, int rows, int cols, bool out) const {
@@ -1176,6 +1211,12 @@ struct Img2Img::Impl {
     // The gather of a pass (or of one tile group of it): the tiles of gp.slots out of the frame.  `gp` carries the BGR frame; the other formats take its tile side.
     template <class P> static P tile_side(const GatherParams& gp) { P p; p.out = gp.out; p.fp32 = gp.fp32; p.slots = gp.slots; p.B = gp.B; p.T = gp.T; return p; }
     void gather_tiles(const GatherParams& gp, hipStream_t gs) {
+        if (job.chain.src) {                                          // a later stage of a chained render: the tiles copied out of the frame of tile pixels
+            GatherPxParams p = tile_side<GatherPxParams>(gp);
+            p.frame = job.chain.src; p.rows = gp.rows; p.cols = gp.cols;
+            hipAssert(launch_gather_px(p, gs));
+            return;
+        }
         switch (job.kind) {
             case Job::BGR: hipAssert(launch_gather(gp, gs)); break;
             case Job::YUV: {                                          // the same tiles from the frame's planes
@@ -1300,6 +1341,13 @@ struct Img2Img::Impl {
     // order on `on`, they share one canvas.  `slab_read`: recorded behind the slab's last reader; `out_free`: the frame that last left through this output buffer
     // has been downloaded (a rolling sequence gives both, run_frame() and rgba_frame() neither: stream order serves).
     void finish_frame(int rows, int cols, const TileGrid& grid, const StripPlan& sp, hipStream_t on, hipEvent_t slab_read, hipEvent_t out_free) {
+        if (job.chain.dst) {                                          // an earlier stage of a chained render: the canvas as the next stage's frame of tile pixels
+            ComposePxParams p;
+            p.c = compose_base(rows, cols, grid); p.frame = job.chain.dst; p.frame_fp32 = job.chain.dst_fp32 ? 1 : 0;
+            hipAssert(launch_compose_px(p, on));
+            if (slab_read) hipAssert(hipEventRecord(slab_read, on));
+            return;
+        }
         if (job.rs) {
             compose_canvas(rows, cols, grid, on);
             if (slab_read) hipAssert(hipEventRecord(slab_read, on));
@@ -2065,6 +2113,9 @@ static void shard_phase2(Img2Img::Impl& e, int k, const std::vector<ShardPlan>& 
     }
 }
 
+// the total factor of a chain
+static int cp_total(const int* scalings, int count) { int S = 1; for (int k = 0; k < count; ++k) S *= scalings[k]; return S; }
+
 // frame / output checks shared by the sharded entries; "" when fine
 static std::string shard_frame_problem(const Img2Img::Impl& e, const Image& src, const Image* dst) {
     const int s = e.cfg.scaling;
@@ -2393,6 +2444,252 @@ bool Img2Img::runPlanar(const PlanarImage* srcs, PlanarImage* dsts, int count, i
         [&](int i, uint8_t* dev, hipStream_t on) { copy_planes(dsts[i], dev, call.out_rows, call.out_cols, false, on); });
     return true;
     });
+}
+
+// Chained renders: ONE frame through `count` engines, the frame staying in HBM between them.  The six entries are runChained() over n frames,
+// interleaved or planar.  Per stage k on engine e_k, all on e_k's compute stream: wait for stage k - 1's event, the stage's passes (gather_px_kernel out of
+// engines[0]'s d_chain[k - 1] - stage 0: the format's gather out of d_frame), then compose_px_kernel into d_chain[k] - the last stage: the format's end of a frame
+// into d_out -, an event.  Quantised, the stages run the format's own gather and compose with d_frame / d_out pointed at the chain's buffers.  Every stage has slot
+// and liveness tables of its own (Impl::chain_tables), uploaded before the first frame without waiting for them.  The host synchronises once, behind the download.
+bool Img2Img::renderChained(Img2Img* const* engines, int count, const Image& src, Image& dst, const ChainOptions& opt) {
+    return runChained(engines, count, &src, &dst, nullptr, nullptr, 1, opt, -1, "renderChained", true);
+}
+bool Img2Img::renderChainedResized(Img2Img* const* engines, int count, const Image& src, Image& dst, const ChainOptions& opt, ResizeFilter filter) {
+    return runChained(engines, count, &src, &dst, nullptr, nullptr, 1, opt, filter_id(filter), "renderChainedResized", true);
+}
+bool Img2Img::renderSequenceChained(Img2Img* const* engines, int count, const Image* srcs, Image* dsts, int n, const ChainOptions& opt) {
+    return runChained(engines, count, srcs, dsts, nullptr, nullptr, n, opt, -1, "renderSequenceChained", false);
+}
+bool Img2Img::renderSequenceChainedResized(Img2Img* const* engines, int count, const Image* srcs, Image* dsts, int n, const ChainOptions& opt, ResizeFilter filter) {
+    return runChained(engines, count, srcs, dsts, nullptr, nullptr, n, opt, filter_id(filter), "renderSequenceChainedResized", false);
+}
+bool Img2Img::renderChainedPlanar(Img2Img* const* engines, int count, const PlanarImage& src, PlanarImage& dst, const ChainOptions& opt) {
+    return runChained(engines, count, nullptr, nullptr, &src, &dst, 1, opt, -1, "renderChainedPlanar", true);
+}
+bool Img2Img::renderChainedPlanarResized(Img2Img* const* engines, int count, const PlanarImage& src, PlanarImage& dst, const ChainOptions& opt, ResizeFilter filter) {
+    return runChained(engines, count, nullptr, nullptr, &src, &dst, 1, opt, filter_id(filter), "renderChainedPlanarResized", true);
+}
+
+bool Img2Img::runChained(Img2Img* const* engines, int count, const Image* srcs, Image* dsts, const PlanarImage* psrcs, PlanarImage* pdsts, int n, const ChainOptions& opt,
+                         int resizeFilter, const char* who, bool single) {
+    if (!engines || !engines[0]) return false;                 // (nobody to tell)
+    Impl* const impl = engines[0]->impl.get();                 // (the log macros name `impl`)
+    auto refuse = [&](const std::string& why) { W2X_LOG_AS(who, error, why); return false; };
+    // ---- the checks: the chain, the source as the single calls check it, the target (chain_plan), the destination, every stage's tile grid
+    if (count < kChainMinStages || count > kChainMaxStages) return refuse(chain_refusal_text(kChainCount));
+    for (int k = 0; k < count; ++k) if (!engines[k] || !engines[k]->impl->loaded) return refuse("Render called before a successful load (engine " + std::to_string(k) + ").");
+    for (int k = 1; k < count; ++k) if (engines[k]->impl->device != impl->device) return refuse("The engines of a chain must live on one device (engine " + std::to_string(k) + " is on another).");
+    if (n <= 0) return n == 0 ? true : refuse("No frames given.");
+    const bool planar = psrcs != nullptr || pdsts != nullptr;
+    if (planar ? !psrcs || !pdsts : !srcs || !dsts) return refuse("No frames given.");
+    const bool quantize = opt.quantize;
+    const int last = count - 1;
+    const int rows = planar ? psrcs[0].rows : srcs[0].rows, cols = planar ? psrcs[0].cols : srcs[0].cols;
+    const int in_bits = planar ? psrcs[0].bits : srcs[0].depth, out_bits = planar ? pdsts[0].bits : dsts[0].depth;
+    auto planes_ok = [](const PlanarImage& f) {
+        const size_t bps = planar_sample_bytes(f.bits);
+        for (int k = 0; k < 3; ++k) if (!f.planes[k] || f.steps[k] < (size_t)f.cols * bps || ((((size_t)f.planes[k]) | f.steps[k]) & (bps - 1)) != 0) return false;
+        return true;
+    };
+    if (planar) {
+        if (!planar_bits_ok(in_bits) || !planar_bits_ok(out_bits)) return refuse("Planar frames must have 8, 10, 12, 16 or 32 (float) bits.");
+        if (quantize && in_bits == 32) return refuse("A quantised chain takes integer samples: the frame between two stages has the source's depth.");
+        if (rows <= 0 || cols <= 0) return refuse("Input image is empty.");
+    } else {
+        if (single) { if ((in_bits != 8 && in_bits != 16) || out_bits != in_bits) return refuse("Input and output images must both be 8-bit or both 16-bit."); }
+        else for (int i = 0; i < n; ++i) if (srcs[i].depth != 8 || dsts[i].depth != 8) return refuse(std::string(who) + " takes 8-bit frames (16-bit images go through renderChained()).");
+        if (!srcs[0].data || rows <= 0 || cols <= 0 || srcs[0].step < (size_t)cols * 3 * (in_bits / 8)) return refuse("Input image is empty or has an invalid step.");
+    }
+    if (resizeFilter >= 0 && resizeFilter != 0 && resizeFilter != 1) return refuse("Unknown resize filter.");
+    int scalings[kChainMaxStages];
+    for (int k = 0; k < count; ++k) scalings[k] = engines[k]->impl->cfg.scaling;
+    ChainPlan cp;
+    const int want_rows = planar ? pdsts[0].rows : dsts[0].rows, want_cols = planar ? pdsts[0].cols : dsts[0].cols;
+    if (const ChainRefusal why = chain_plan(rows, cols, scalings, count, resizeFilter >= 0 ? want_rows : 0, resizeFilter >= 0 ? want_cols : 0, cp); why != kChainOk) {
+        if (why == kChainTarget) return refuse("Output image has invalid size for a resize: " + std::to_string(want_cols) + "x" + std::to_string(want_rows) + " is not between " + std::to_string(cols) + "x" +
+                                               std::to_string(rows) + " and " + std::to_string(cols * cp_total(scalings, count)) + "x" + std::to_string(rows * cp_total(scalings, count)) + ".");
+        return refuse(chain_refusal_text(why));
+    }
+    const std::string out_size = "Output image has invalid size: expected " + std::to_string(cp.out_cols) + "x" + std::to_string(cp.out_rows) + ".";
+    for (int i = 0; i < n; ++i) {
+        if (planar) {
+            if (psrcs[i].rows != rows || psrcs[i].cols != cols || psrcs[i].bits != in_bits) return refuse("Input images must be of one size and depth.");
+            if (!planes_ok(psrcs[i])) return refuse("Input image has a missing plane or an invalid step.");
+            if (pdsts[i].rows != cp.out_rows || pdsts[i].cols != cp.out_cols) return refuse(out_size);
+            if (pdsts[i].bits != out_bits) return refuse("Output images must be of one depth.");
+            if (!planes_ok(pdsts[i])) return refuse("Output image has a missing plane or an invalid step.");
+        } else {
+            const size_t px = (size_t)3 * (in_bits / 8);
+            if (!srcs[i].data || srcs[i].rows != rows || srcs[i].cols != cols || srcs[i].step < cols * px) return refuse("Input images must be non-empty and of one size.");
+            if (!dsts[i].data || dsts[i].rows != cp.out_rows || dsts[i].cols != cp.out_cols || dsts[i].step < cp.out_cols * px) return refuse(out_size);
+        }
+    }
+    struct Stage { Impl* e = nullptr; Impl::FrameCall c; Impl::Job job; };
+    Stage st[kChainMaxStages];
+    for (int k = 0; k < count; ++k) {
+        Stage& g = st[k];
+        g.e = engines[k]->impl.get();
+        g.c.rows = cp.rows[k]; g.c.cols = cp.cols[k];
+        g.c.out_rows = k == last ? cp.out_rows : cp.rows[k + 1]; g.c.out_cols = k == last ? cp.out_cols : cp.cols[k + 1];
+        g.c.resized = k == last && cp.resized;
+        if (const std::string why = g.e->call_grid(g.c); !why.empty()) return refuse(why + " (stage " + std::to_string(k) + ")");
+    }
+    const bool deep = !planar && in_bits == 16;
+    // the bytes of the frame behind stage k: tile pixels of the consuming engine, or (quantised) the format's device frame at the source's depth
+    auto between_bytes = [&](int k) {
+        const size_t r = (size_t)cp.rows[k + 1], c = (size_t)cp.cols[k + 1];
+        if (!quantize) return r * c * 4 * (size_t)st[k + 1].e->plan.elt;
+        return planar ? Impl::planar_step((int)c, in_bits) * r * 3 : Impl::bgr_step((int)c, deep) * r;
+    };
+    // Everything a stage changes on its engine for its own duration, put back on every exit: the job, the slot tables, the frame buffers, the sample depth, the
+    // sequence's frame index, where progress goes, and the dither - the frame between two stages is never dithered, whatever the setting of the engine that
+    // writes it; the last stage keeps its engine's.  (An engine may run several stages: each one enters and leaves.)
+    struct StageScope {
+        Impl& e; int k; Impl::Job job; uint8_t* frame; uint8_t* out; bool deep; unsigned seq; Impl* report; DitherOptions dither;
+        StageScope(Impl& e_, int k_, bool is_last) : e(e_), k(k_), job(e_.job), frame(e_.d_frame), out(e_.d_out), deep(e_.deep), seq(e_.seq_frame), report(e_.report_to), dither(e_.dither) {
+            e.swap_tables(k);
+            if (!is_last) e.dither = DitherOptions{};
+        }
+        ~StageScope() { e.swap_tables(k); e.job = job; e.d_frame = frame; e.d_out = out; e.deep = deep; e.seq_frame = seq; e.report_to = report; e.dither = dither; }
+    };
+    try {
+        DeviceGuard guard(impl->device);
+        Impl& e0 = *st[0].e; Impl& eL = *st[last].e;
+        // ---- set-up, once per call: the frames between the stages, the events, every stage's job, tables and slab, the two ends' frame buffers
+        for (int k = 0; k < last; ++k) impl->ensure_chain(k, between_bytes(k));
+        for (int k = 0; k < count; ++k) if (!impl->ev_chain_done[k]) hipAssert(hipEventCreateWithFlags(&impl->ev_chain_done[k], hipEventDisableTiming));
+        for (int k = 0; k < last; ++k) if (!impl->ev_chain_read[k]) hipAssert(hipEventCreateWithFlags(&impl->ev_chain_read[k], hipEventDisableTiming));
+        int batch0[kChainMaxStages + 1] = {0};
+        for (int k = 0; k < count; ++k) batch0[k + 1] = batch0[k] + st[k].e->batch_count(st[k].c.sp.tile_count);
+        for (int k = 0; k < count; ++k) {
+            Stage& g = st[k];
+            g.job.kind = planar ? Impl::Job::PLANAR : Impl::Job::BGR;
+            g.job.planar.in_bits = k == 0 || quantize ? in_bits : 32; g.job.planar.out_bits = k == last ? out_bits : in_bits;
+            if (!quantize) {
+                if (k > 0) g.job.chain.src = impl->d_chain[k - 1];
+                if (k < last) { g.job.chain.dst = impl->d_chain[k]; g.job.chain.dst_fp32 = st[k + 1].e->plan.elt == 4; }
+            }
+        }
+        const size_t in_bytes = planar ? Impl::planar_step(cols, in_bits) * rows * 3 : Impl::bgr_step(cols, deep) * rows;
+        const size_t out_bytes = planar ? Impl::planar_step(cp.out_cols, out_bits) * cp.out_rows * 3 : Impl::bgr_step(cp.out_cols, deep) * cp.out_rows;
+        e0.ensure(e0.d_frame, e0.frame_cap, in_bytes);
+        eL.ensure(eL.d_out, eL.out_cap, out_bytes);
+        if (!single) {
+            e0.ensure_copy_streams(); eL.ensure_copy_streams();
+            e0.ensure(e0.d_frame2, e0.frame2_cap, in_bytes);
+            eL.ensure(eL.d_out2, eL.out2_cap, out_bytes);
+        }
+        // render()'s pipelined parts for the last stage of a plain interleaved single call (tiles.h render_parts; one part for a small frame)
+        RenderParts rp;
+        {
+            const Stage& g = st[last];
+            const Plan& pl = g.e->plan;
+            rp = render_parts(g.c.grid, g.c.sp, g.c.cols, g.c.cols * g.e->cfg.scaling, g.c.rows * g.e->cfg.scaling, pl.T, pl.Tout, g.e->cfg.tta ? 8 : 1, pl.userB, pl.B,
+                              single && !planar && !cp.resized ? g.e->pipeline_parts : 1);
+            rp.x_split = g.c.cols;                                 // (nothing of the stage's frame is uploaded: run_frame_in_parts copies no columns)
+            rp.batch_total = batch0[count];
+            for (int q = 0; q < rp.n; ++q) rp.part[q].batches_before += batch0[last];
+        }
+        for (int k = 0; k < count; ++k) {
+            Stage& g = st[k];
+            Impl& e = *g.e;
+            StageScope scope(e, k, k == last);
+            e.job = g.job;
+            if (k == last && rp.n > 1) {
+                for (int q = 0; q < rp.n; ++q) e.fill_slots(g.c.grid, g.c.sp.first_tile + rp.part[q].first, rp.part[q].tiles, 1, rp.part[q].slots_off, rp.part[q].slots);
+                e.upload_slots(g.c.grid, rp.slot_total, rp.slab_slots);
+            } else {
+                const size_t stepCount = e.pass_slots(g.c.sp.tile_count);
+                e.fill_slots(g.c.grid, 0, g.c.sp.tile_count, 1, 0, stepCount);
+                e.upload_slots(g.c.grid, stepCount, stepCount);
+            }
+            if (g.c.resized) { e.job_resize(g.c.rows, g.c.cols, g.c.out_rows, g.c.out_cols, resizeFilter); g.job.rs = e.job.rs; }
+        }
+        for (int k = 0; k < count; ++k) { Impl& e = *st[k].e; e.last_rows = e.last_cols = 0; e.one_part_stale = false; e.deep = false; }   // (nothing of a chained call is replayable)
+        // ---- one frame through the stages: its source in `frame` (stage 0's device buffer), its output in `out` (the last stage's); i: its index in the sequence
+        auto run_stages = [&](uint8_t* frame, uint8_t* out, int i, hipEvent_t in_read, hipEvent_t out_free) {
+            for (int k = 0; k < count; ++k) {
+                Stage& g = st[k];
+                Impl& e = *g.e;
+                StageScope scope(e, k, k == last);
+                e.job = g.job; e.deep = deep; e.report_to = impl;
+                if (k == 0) e.d_frame = frame; else if (quantize) e.d_frame = (uint8_t*)impl->d_chain[k - 1];
+                if (k == last) { e.d_out = out; e.seq_frame = (unsigned)i; } else if (quantize) e.d_out = (uint8_t*)impl->d_chain[k];
+                if (k > 0) hipAssert(hipStreamWaitEvent(e.stream, impl->ev_chain_done[k - 1], 0));
+                if (k == last && rp.n > 1) {                           // (a single call: nothing else is in flight)
+                    e.run_frame_in_parts(g.c, rp, srcs[0], dsts[0]);
+                    continue;
+                }
+                e.run_passes(g.c.rows, g.c.cols, g.c.sp.tile_count, 0, single, 0, true, batch0[k], batch0[count]);
+                if (k > 0) hipAssert(hipEventRecord(impl->ev_chain_read[k - 1], e.stream));      // (every pass has joined its tile groups: the gathers are done)
+                if (k == 0 && in_read) hipAssert(hipEventRecord(in_read, e.stream));
+                if (k < last) hipAssert(hipStreamWaitEvent(e.stream, impl->ev_chain_read[k], 0));   // (a never-recorded event does not wait)
+                if (k == last && out_free) hipAssert(hipStreamWaitEvent(e.stream, out_free, 0));
+                e.finish_frame(g.c.rows, g.c.cols, g.c.grid, g.c.sp, e.stream, nullptr, nullptr);
+                hipAssert(hipEventRecord(impl->ev_chain_done[k], e.stream));
+            }
+        };
+        // frame i between the caller's memory and the device layout of the format, on stream `on`
+        auto copy_planes = [&](const PlanarImage& host, uint8_t* dev, int r, int c, bool up, hipStream_t on) {
+            const PlanarPlanes d = Impl::planar_layout(dev, r, c, host.bits);
+            const size_t width = (size_t)c * planar_sample_bytes(host.bits);
+            for (int k = 0; k < 3; ++k) {
+                if (up) hipAssert(hipMemcpy2DAsync(d.p[k], d.step[k], host.planes[k], host.steps[k], width, r, hipMemcpyHostToDevice, on));
+                else hipAssert(hipMemcpy2DAsync(host.planes[k], host.steps[k], d.p[k], d.step[k], width, r, hipMemcpyDeviceToHost, on));
+            }
+        };
+        const size_t px = (size_t)3 * (deep ? 2 : 1);
+        auto up = [&](int i, uint8_t* dev, hipStream_t on) {
+            if (planar) copy_planes(psrcs[i], dev, rows, cols, true, on);
+            else hipAssert(hipMemcpy2DAsync(dev, (size_t)cols * px, srcs[i].data, srcs[i].step, (size_t)cols * px, rows, hipMemcpyHostToDevice, on));
+        };
+        auto down = [&](int i, uint8_t* dev, hipStream_t on) {
+            if (planar) copy_planes(pdsts[i], dev, cp.out_rows, cp.out_cols, false, on);
+            else hipAssert(hipMemcpy2DAsync(dsts[i].data, dsts[i].step, dev, (size_t)cp.out_cols * px, (size_t)cp.out_cols * px, cp.out_rows, hipMemcpyDeviceToHost, on));
+        };
+        auto sync_all = [&] { for (int k = 0; k < count; ++k) hipAssert(hipStreamSynchronize(st[k].e->stream)); };
+        if (single) {
+            up(0, e0.d_frame, e0.stream);
+            hipAssert(hipEventRecord(e0.ev0, e0.stream));
+            run_stages(e0.d_frame, eL.d_out, 0, nullptr, nullptr);
+            if (rp.n == 1) {
+                hipAssert(hipEventRecord(eL.ev1, eL.stream));
+                down(0, eL.d_out, eL.stream);
+            }
+            sync_all();
+            hipAssert(hipEventElapsedTime(&impl->last_ms, e0.ev0, eL.ev1));
+            return true;
+        }
+        // a sequence: run_sequence()'s three streams - frame i + 1 travels up on e0's upload stream and frame i - 1 down on the last engine's download stream while
+        // frame i runs through the stages; two frame buffers on e0, two output buffers on the last engine, one frame between each pair of stages
+        uint8_t* const frames[2] = {e0.d_frame, e0.d_frame2};
+        uint8_t* const outs[2] = {eL.d_out, eL.d_out2};
+        sync_all();
+        hipAssert(hipEventRecord(e0.ev0, e0.stream));
+        for (int i = 0; i < n; ++i) {
+            const int b = i & 1;
+            if (i >= 2) hipAssert(hipStreamWaitEvent(e0.s_up, e0.ev_comp[b], 0));                 // frame i - 2 has been gathered out of this buffer
+            up(i, frames[b], e0.s_up);
+            hipAssert(hipEventRecord(e0.ev_up[b], e0.s_up));
+            hipAssert(hipStreamWaitEvent(e0.stream, e0.ev_up[b], 0));
+            run_stages(frames[b], outs[b], i, e0.ev_comp[b], i >= 2 ? eL.ev_dn[b] : nullptr);
+            hipAssert(hipStreamWaitEvent(eL.s_dn, impl->ev_chain_done[last], 0));
+            down(i, outs[b], eL.s_dn);
+            hipAssert(hipEventRecord(eL.ev_dn[b], eL.s_dn));
+        }
+        hipAssert(hipEventRecord(eL.ev1, eL.stream));
+        hipAssert(hipStreamSynchronize(eL.s_dn));
+        sync_all();
+        hipAssert(hipStreamSynchronize(e0.s_up));
+        float total_ms = 0.f;
+        hipAssert(hipEventElapsedTime(&total_ms, e0.ev0, eL.ev1));
+        impl->last_ms = total_ms / n;
+        return true;
+    } catch (const std::exception& ex) {
+        for (int k = 0; k < count; ++k) { try { DeviceGuard guard(st[k].e->device); st[k].e->drain_after_error(); } catch (...) {} }
+        W2X_LOG_AS(who, error, kRenderFailed + std::string(ex.what()) + ".");
+        return false;
+    }
 }
 
 // Planar RGBA frames: renderRgba()'s frame on renderPlanar()'s samples.  Four 2-D copies up, alpha_bleed_planes_kernel (three colour planes with the

@@ -473,6 +473,24 @@ struct ComposePlanarParams {
     PlanarPlanes dst;
 };
 hipError_t launch_compose_planar(const ComposePlanarParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
+// The hand-off of a chained render (k_chain.hip): the frame between two stages is [rows][cols][4] tile pixels of the CONSUMING engine's type - half4
+// (frame_fp32 / fp32 = 0) or float4v -, values in [0, 1], lane 3 zero, 8- / 16-byte aligned.
+// compose_px_kernel: compose_kernel over the whole canvas of c (c.dst / c.deep / x0..y1 unused): the three sums of compose_pixel_sums, each min(max(x, 0), 1), rounded
+// once to the frame's type, one vector store per pixel into frame[c.outH][c.outW]
+struct ComposePxParams {
+    ComposeParams c;
+    void* frame = nullptr; int frame_fp32 = 0;
+};
+hipError_t launch_compose_px(const ComposePxParams& p, hipStream_t s);
+// gather_px_kernel: gather_kernel's tiles (same slots, replicate padding, TTA source index) copied out of such a frame: one vector load and one vector store per
+// tile pixel, no conversion (fp32: the type of frame and tiles alike)
+struct GatherPxParams {
+    const void* frame = nullptr; int rows = 0, cols = 0;
+    void* out = nullptr; int fp32 = 0;
+    const TileSlot* slots = nullptr;
+    int B = 0, T = 0;
+};
+hipError_t launch_gather_px(const GatherPxParams& p, hipStream_t s);
 // compose_canvas_gray_kernel: the green sums of compose_pixel_sums over the whole canvas of p (x0..y1, dst, deep unused) unquantised as one fp32 plane
 // canvas[Y][X] of outH x outW: the canvas of a resized gray frame (a resized planar frame has compose_canvas_kernel's)
 hipError_t launch_compose_canvas_gray(const ComposeParams& p, float* canvas, hipStream_t s, const LightArgs& l = LightArgs());

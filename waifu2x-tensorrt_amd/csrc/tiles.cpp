@@ -315,4 +315,39 @@ bool alpha_bleed_planes(const void* const colour[3], const size_t colour_steps[3
     return true;
 }
 
+ChainRefusal chain_plan(int rows, int cols, const int* scalings, int count, int dst_rows, int dst_cols, ChainPlan& plan) {
+    plan = ChainPlan{};
+    if (count < kChainMinStages || count > kChainMaxStages || !scalings) return kChainCount;
+    for (int k = 0; k < count; ++k) if (scalings[k] < 1 || scalings[k] > kChainMaxScaling) return kChainScaling;
+    if (rows <= 0 || cols <= 0) return kChainSource;
+    plan.count = count; plan.S = 1;
+    long r = rows, c = cols;
+    plan.rows[0] = rows; plan.cols[0] = cols;
+    for (int k = 0; k < count; ++k) {
+        r *= scalings[k]; c *= scalings[k]; plan.S *= scalings[k];
+        if (r > kChainMaxDim || c > kChainMaxDim) { plan = ChainPlan{}; return kChainTooLarge; }
+        plan.rows[k + 1] = (int)r; plan.cols[k + 1] = (int)c;
+    }
+    const bool full = dst_rows == 0 && dst_cols == 0;
+    plan.out_rows = full ? (int)r : dst_rows; plan.out_cols = full ? (int)c : dst_cols;
+    ChainRefusal why = kChainOk;
+    if (plan.out_rows < rows || plan.out_rows > r || plan.out_cols < cols || plan.out_cols > c) why = kChainTarget;
+    else if ((long)plan.out_rows * kChainMaxShrink < r || (long)plan.out_cols * kChainMaxShrink < c) why = kChainShrink;
+    if (why != kChainOk) { plan = ChainPlan{}; return why; }
+    plan.resized = plan.out_rows != r || plan.out_cols != c;
+    return kChainOk;
+}
+const char* chain_refusal_text(ChainRefusal why) {
+    switch (why) {
+        case kChainOk: return "";
+        case kChainCount: return "A chain takes 2 to 4 stages.";
+        case kChainScaling: return "A stage of the chain has a scale factor outside 1..4.";
+        case kChainSource: return "Input image is empty.";
+        case kChainTooLarge: return "A frame of the chain is larger than 65536 samples per side.";
+        case kChainTarget: return "Output image has invalid size for the chain: each dimension must lie between the input's and the input's times the product of the stages' scale factors.";
+        case kChainShrink: return "Output image has invalid size for the chain: the last stage's canvas can shrink by a factor of 4 at most.";
+    }
+    return "Unknown chain refusal.";
+}
+
 }  // namespace w2x

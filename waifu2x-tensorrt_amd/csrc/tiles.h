@@ -90,6 +90,22 @@ struct RenderParts {
 // is one part, every other at most min(want, kMaxRenderParts, tiles / 8).
 RenderParts render_parts(const TileGrid& grid, const StripPlan& strip, int cols, int outW, int outH, int T, int Tout, int steps, int userB, int B, int want);
 
+// The frames of a chained render (Img2Img::renderChained*): `count` stages (kChainMinStages .. kChainMaxStages) with the scale factors scalings[k]
+// take a rows x cols frame to rows * S x cols * S, S their product; stage k reads a frame of rows[k] x cols[k] (rows[0] = the source's) and the last stage's
+// canvas, rows[count] x cols[count], is resized to the target dst_rows x dst_cols (0 x 0: the canvas itself).  This is the one place the size rules live:
+// every scaling in 1 .. kChainMaxScaling, no frame beyond kChainMaxDim samples per side, the target per axis in [source dim, source dim * S] - the two axes
+// independent - and no smaller than the last canvas over kChainMaxShrink (the resize kernels' tile holds the input rows of a shrink by 4 at most).
+constexpr int kChainMinStages = 2, kChainMaxStages = 4, kChainMaxScaling = 4, kChainMaxDim = 1 << 16, kChainMaxShrink = 4;
+enum ChainRefusal { kChainOk = 0, kChainCount = 1, kChainScaling = 2, kChainSource = 3, kChainTooLarge = 4, kChainTarget = 5, kChainShrink = 6 };
+struct ChainPlan {
+    int count = 0, S = 0;
+    int rows[kChainMaxStages + 1] = {}, cols[kChainMaxStages + 1] = {};
+    int out_rows = 0, out_cols = 0;                                      // the target
+    bool resized = false;                                                // the target is not the last canvas
+};
+ChainRefusal chain_plan(int rows, int cols, const int* scalings, int count, int dst_rows, int dst_cols, ChainPlan& plan);
+const char* chain_refusal_text(ChainRefusal why);
+
 // left/top ramp: w[i] = float(double(i+1)/(ov+1)), i < ov  (img2img_load.cpp:34-45)
 std::vector<float> blend_ramp(int ov);
 

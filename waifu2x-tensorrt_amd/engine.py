@@ -352,6 +352,19 @@ RESIZE_LIGHT_SYMBOLS = {
     "w2x_resize_planes": (_I, [_P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _I]),
 }
 RESIZE_LIGHTS = {"gamma": 0, "srgb": 1, "bt709": 2}    # W2X_LIGHT_GAMMA .. _BT709 (include/w2x/c_api_resize_light.h)
+# The chained renders of include/w2x/c_api_chain.h, a table of their own likewise: (engines, count) in front of the frame arguments of the single entries, then
+# depth (interleaved frames), quantize and, resized, the filter; the planar entries say "planes" (PLANAR_SYMBOLS owns every name that holds "planar").
+_CHAIN = [_P, _I]
+CHAIN_SYMBOLS = {
+    "w2x_chain_plan": (_I, [_I, _I, _P, _I, _I, _I, _P]),
+    "w2x_render_chained": (_I, _CHAIN + [_P, _I, _I, _Z, _P, _Z, _I, _I]),
+    "w2x_render_chained_resized": (_I, _CHAIN + [_P, _I, _I, _Z, _P, _I, _I, _Z, _I, _I, _I]),
+    "w2x_render_sequence_chained": (_I, _CHAIN + [_P, _I, _I, _Z, _P, _Z, _I, _I]),
+    "w2x_render_sequence_chained_resized": (_I, _CHAIN + [_P, _I, _I, _Z, _P, _I, _I, _Z, _I, _I, _I]),
+    "w2x_render_chained_planes": (_I, _CHAIN + _YUV + _YUV + [_I]),
+    "w2x_render_chained_planes_resized": (_I, _CHAIN + _YUV + _YUV + [_I, _I]),
+}
+CHAIN_REFUSALS = {1: "count", 2: "scaling", 3: "source", 4: "too_large", 5: "target", 6: "shrink"}    # W2X_CHAIN_COUNT .. _SHRINK
 _lib = None
 
 
@@ -364,7 +377,7 @@ def lib():
         raise W2xError(f"{lib_path} is missing - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "or `make -C waifu2x-tensorrt_amd` (there is no CPU fallback)")
     L = C.CDLL(lib_path)
-    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()) + list(PLANAR_SYMBOLS.items()) + list(RGBAP_SYMBOLS.items()) + list(YUV_RESIZED_SYMBOLS.items()) + list(YUV_SITED_SYMBOLS.items()) + list(DITHER_SYMBOLS.items()) + list(RESIZE_LIGHT_SYMBOLS.items()):
+    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()) + list(PLANAR_SYMBOLS.items()) + list(RGBAP_SYMBOLS.items()) + list(YUV_RESIZED_SYMBOLS.items()) + list(YUV_SITED_SYMBOLS.items()) + list(DITHER_SYMBOLS.items()) + list(RESIZE_LIGHT_SYMBOLS.items()) + list(CHAIN_SYMBOLS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -1182,6 +1195,107 @@ def render_sharded(engines, src: np.ndarray, dst: np.ndarray = None) -> np.ndarr
     if not lib().w2x_render_sharded(handles, len(engines), src.ctypes.data, src.shape[0], src.shape[1], src.strides[0], dst.ctypes.data, dst.strides[0]):
         raise W2xError(engines[0].last_error() or "sharded render failed")
     return dst
+
+
+def chain_plan(rows: int, cols: int, scalings, size=None) -> dict:
+    """The frames of a chained render (w2x_chain_plan, host only): a rows x cols frame through stages of the scale factors `scalings` (2 to 4 of them), the last
+    stage's canvas resized to size = (rows, cols) or, size=None, left as it is.  Returns {"stages": [(rows, cols) of the frame each stage reads], "canvas": the
+    last stage's, "target": (rows, cols), "scale": S}; ValueError naming the rule (CHAIN_REFUSALS) for a chain the library refuses."""
+    sc = [int(v) for v in scalings]
+    n = len(sc)
+    out = (C.c_int * (2 * max(n, 0) + 5))()
+    dr, dc = (0, 0) if size is None else (int(size[0]), int(size[1]))
+    if size is not None and (dr <= 0 or dc <= 0):
+        raise ValueError("chain refused: target")
+    why = lib().w2x_chain_plan(int(rows), int(cols), (C.c_int * max(n, 1))(*sc), n, dr, dc, out)
+    if why:
+        raise ValueError(f"chain refused: {CHAIN_REFUSALS.get(why, why)}")
+    v = list(out)
+    return {"stages": [(v[2 * k], v[2 * k + 1]) for k in range(n)], "canvas": (v[2 * n], v[2 * n + 1]), "target": (v[2 * n + 2], v[2 * n + 3]), "scale": v[2 * n + 4]}
+
+
+def _chain(engines):
+    """the handle array and the total scale factor of the engines of a chained call (0 while one of them is not loaded: the library refuses the call)"""
+    if not isinstance(engines, (list, tuple)) or not 2 <= len(engines) <= 4 or not all(isinstance(e, Img2Img) and e._h for e in engines):
+        raise ValueError("engines must be a list of 2 to 4 open Img2Img engines (the same engine may appear more than once)")
+    total = 1
+    for e in engines:
+        total *= e._scaling
+    return (C.c_void_p * len(engines))(*[e._h for e in engines]), len(engines), total
+
+
+def render_chained(engines, src: np.ndarray, quantize: bool = False, dst: np.ndarray | None = None):
+    """ONE frame through 2 to 4 engines one after the other (w2x_render_chained): x4 from two x2 models, x8, x16, the frame staying on the device between the
+    stages.  src: a uint8 or uint16 [rows, cols, 3] BGR frame; the result has rows * S x cols * S, S the product of the engines' scale factors.  quantize=False:
+    the frame between two stages is unrounded - the bytes of render_planar(out_bits=32) followed by render_planar() of that -; quantize=True: it is rounded to
+    the frame's depth - the bytes of b.render(a.render(src)).  engines[0] reports messages and progress.  With dst=None returns the array or raises; with dst a bool."""
+    h, n, S = _chain(engines)
+    _frame_ok(src, 3, (np.uint8, np.uint16), "src must be a uint8 (or uint16) [rows, cols, 3] BGR array with packed pixels")
+    out = np.empty((src.shape[0] * S, src.shape[1] * S, 3), src.dtype) if dst is None else None
+    dst = out if dst is None else dst
+    if S and not _frame_ok(dst, 3, (src.dtype,), shape=(src.shape[0] * S, src.shape[1] * S)):
+        engines[0]._refuse("renderChained", f"Output image has invalid size: expected {src.shape[1] * S}x{src.shape[0] * S}.")
+        return False
+    ok = lib().w2x_render_chained(h, n, _data(src), src.shape[0], src.shape[1], src.strides[0], _data(dst), dst.strides[0], src.itemsize * 8, int(bool(quantize)))
+    return engines[0]._finish(ok, out, "render_chained failed")
+
+
+def render_chained_resized(engines, src: np.ndarray, size, quantize: bool = False, filter: str = "bicubic", dst: np.ndarray | None = None):
+    """render_chained() with the last stage's canvas resized on the device to size = (rows, cols), each in [input dim, input dim * S] and at least a quarter of
+    that canvas (w2x_render_chained_resized; chain_plan() holds the rules).  At the full size it is render_chained()."""
+    h, n, S = _chain(engines)
+    _frame_ok(src, 3, (np.uint8, np.uint16), "src must be a uint8 (or uint16) [rows, cols, 3] BGR array with packed pixels")
+    rows, cols = int(size[0]), int(size[1])
+    fid = _filter_id(filter)
+    out = np.empty((max(rows, 0), max(cols, 0), 3), src.dtype) if dst is None else None
+    dst = out if dst is None else dst
+    _frame_ok(dst, 3, (src.dtype,), "dst must be a packed [rows, cols, 3] array of the target size and the frame's sample type", shape=(rows, cols), empty_ok=True)
+    ok = lib().w2x_render_chained_resized(h, n, _data(src), src.shape[0], src.shape[1], src.strides[0], _data(dst), rows, cols, dst.strides[0], src.itemsize * 8,
+                                          int(bool(quantize)), fid)
+    return engines[0]._finish(ok, out, "render_chained_resized failed")
+
+
+def render_sequence_chained(engines, frames, size=None, quantize: bool = False, filter: str = "bicubic", outs=None, pinned: bool = False):
+    """Equally sized uint8 frames through the chain with upload, stages and download overlapped (w2x_render_sequence_chained; size = (rows, cols):
+    w2x_render_sequence_chained_resized).  Output i is the bytes of the single call on frame i.  outs / pinned as in render_sequence() (page-locked buffers
+    come from engines[0])."""
+    h, n, S = _chain(engines)
+    if len(frames) == 0:
+        return []
+    fid = _filter_id(filter)
+    r, c = frames[0].shape[:2]
+    rows, cols = (r * S, c * S) if size is None else (int(size[0]), int(size[1]))
+    for f in frames:
+        _frame_ok(f, 3, (np.uint8,), "frames must be packed uint8 [rows, cols, 3] arrays of one size", shape=(r, c), rows_packed=True)
+    q = int(bool(quantize))
+
+    def run(fs, os_):
+        if size is None:
+            return lib().w2x_render_sequence_chained(h, n, _pointers(fs), r, c, c * 3, _pointers(os_, len(fs)), cols * 3, len(fs), q)
+        return lib().w2x_render_sequence_chained_resized(h, n, _pointers(fs), r, c, c * 3, _pointers(os_, len(fs)), rows, cols, cols * 3, len(fs), q, fid)
+    return engines[0]._packed_sequence(frames, 3, (max(rows, 0), max(cols, 0), 3), outs, pinned, "outs must be packed uint8 arrays of the output size", run,
+                                       "render_sequence_chained failed")
+
+
+def render_chained_planar(engines, planes, size=None, *, bits: int | None = None, out_bits: int | None = None, order: str = "rgb", quantize: bool = False,
+                          filter: str = "bicubic", dst=None):
+    """render_chained() on a planar RGB frame (w2x_render_chained_planes; size = (rows, cols): w2x_render_chained_planes_resized): planes, bits, out_bits, order
+    and dst as in render_planar().  quantize=False gives the bytes of b.render_planar(a.render_planar(planes, out_bits=32), out_bits=out_bits); quantize=True
+    (integer samples) those of b.render_planar(a.render_planar(planes), out_bits=out_bits)."""
+    h, n, S = _chain(engines)
+    fid = _filter_id(filter)
+    first = engines[0]
+    keep = first._scaling
+    first._scaling = S                                      # (the planar frame-argument path sizes the output by the caller's scale factor: here the chain's)
+    try:
+        args, out = first._planar_call(planes, size, bits, out_bits, order, dst, "renderChainedPlanar")
+    finally:
+        first._scaling = keep
+    if args is None:
+        return first._finish(0, out, "render_chained_planar failed")
+    a = (h, n) + tuple(args[1:]) + (int(bool(quantize)),)
+    ok = lib().w2x_render_chained_planes(*a) if size is None else lib().w2x_render_chained_planes_resized(*a, fid)
+    return first._finish(ok, out, "render_chained_planar failed")
 
 
 class debug_switches:
