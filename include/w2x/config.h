@@ -26,6 +26,10 @@ enum class ResizeFilter { Bicubic, Bilinear };
 // (the default, and the engine's behaviour before the setting existed).  LinearSrgb / LinearBt709: the canvas is decoded by the sRGB (IEC 61966-2-1) or the
 // BT.709 / BT.2020 transfer curve, resized in linear light and encoded again ahead of everything else the output path does.
 enum class ResizeLight { Gamma = 0, LinearSrgb = 1, LinearBt709 = 2 };
+// Extension: what lies beyond the frame edge (Img2Img::setEdge) - the source index of coordinate i in a dimension of n samples, for any integer i.
+// Replicate: min(max(i, 0), n - 1), the reference's BORDER_REPLICATE, the default and the engine's behaviour before the setting existed.  Wrap: ((i % n) + n) % n,
+// for textures made to tile.  Mirror: reflection that does not repeat the edge sample (-1 -> 1, n -> n - 2; period 2 (n - 1); n == 1: 0).
+enum class EdgeMode { Replicate = 0, Wrap = 1, Mirror = 2 };
 
 struct BuildConfig {
     int deviceId = 0;                                             // HIP device ordinal

@@ -255,6 +255,19 @@ public:
     // callback), the previous setting stays.  Gamma, the default, is the engine that never heard of the setting: the same kernels, the same bytes.
     bool setResizeLight(ResizeLight mode);
     ResizeLight resizeLight() const;
+    // Extension: edge modes (config.h EdgeMode).  With Wrap / Mirror every following frame call of the RGB family - render, gray, planar, RGBA, planar
+    // RGBA, their resized calls and sequences, chains - takes what a tile, the colour bleed and the resize read beyond the frame edge through the mode's rule:
+    //   tiles:   the gather's source index (the tile border may fold round a small frame more than once);
+    //   bleed:   under Wrap a pixel's eight neighbours are taken through the rule - all eight exist, colour spreads across the joint; Mirror keeps Replicate's
+    //            rule (a neighbour outside the frame does not exist: its reflection carries no new information);
+    //   resize:  the taps are not cut off and renormalised at the border; every output sample has its full support, read through the rule.
+    // Dither and linear light are per sample and do not know about it.  A chained render's stage gathers under its own engine's mode; the resize at its end is
+    // the last engine's.  A setting of the engine like setDither: allowed before load(), kept across calls and loads, read by the very next frame (it is part
+    // of the key of the captured passes); an unknown mode: false (message callback), the previous setting stays.  Replicate, the default, is the engine that never
+    // heard of the setting: the same kernels, the same bytes.  Not built under Wrap / Mirror and refused by name (false, message callback, nothing written):
+    // every YUV call, renderStrip, renderSharded, shardCompute and shardFinish.
+    bool setEdge(EdgeMode mode);
+    EdgeMode edge() const;
     void setMessageCallback(MessageCallback callback);   // img2img.h:21
     void setProgressCallback(ProgressCallback callback); // img2img.h:22
 

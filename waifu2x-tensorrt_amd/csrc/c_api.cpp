@@ -2,6 +2,7 @@
 #include "../../include/w2x/c_api.h"
 #include "../../include/w2x/c_api_chain.h"
 #include "../../include/w2x/c_api_dither.h"
+#include "../../include/w2x/c_api_edge.h"
 #include "../../include/w2x/c_api_gray.h"
 #include "../../include/w2x/c_api_planar.h"
 #include "../../include/w2x/c_api_resize_light.h"
@@ -617,6 +618,27 @@ int w2x_resize_weights(int in, int out, int filter, int* first, float* weights, 
     memcpy(first, t.first.data(), t.first.size() * sizeof(int));
     memcpy(weights, t.w.data(), t.w.size() * sizeof(float));
     return t.taps;
+}
+
+// edge modes (include/w2x/c_api_edge.h)
+int w2x_set_edge(w2x_engine* e, int mode) { return e && e->engine.setEdge((w2x::EdgeMode)mode) ? 1 : 0; }   // (the engine refuses unknown modes)
+int w2x_get_edge(const w2x_engine* e) { return e ? (int)e->engine.edge() : -1; }
+int w2x_edge_index(int mode, long long i, int n) { return w2x::edge_mode_ok(mode) && n > 0 ? w2x::edge_index(mode, i, n) : -1; }
+int w2x_resize_weights_edge(int in, int out, int filter, int mode, int* first, float* weights, int cap) {
+    if (in <= 0 || out <= 0 || (filter != W2X_RESIZE_BICUBIC && filter != W2X_RESIZE_BILINEAR) || !w2x::edge_mode_ok(mode)) return 0;
+    const w2x::ResizeTaps t = w2x::resize_taps_edge(in, out, filter, mode);
+    if (!first || !weights) return t.taps;
+    if ((long)cap < (long)out * t.taps) return -t.taps;
+    memcpy(first, t.first.data(), t.first.size() * sizeof(int));
+    memcpy(weights, t.w.data(), t.w.size() * sizeof(float));
+    return t.taps;
+}
+int w2x_alpha_bleed_edge(const uint8_t* bgr, size_t bgr_step, const uint8_t* alpha, size_t alpha_step, int rows, int cols, int radius, uint8_t* out, size_t out_step, int mode) {
+    try { return w2x::alpha_bleed(bgr, bgr_step, alpha, alpha_step, rows, cols, radius, out, out_step, mode) ? 1 : 0; } catch (...) { return 0; }
+}
+int w2x_alpha_bleed_planes_edge(const void* const* planes, const size_t* steps, int rows, int cols, int bits, int radius, void* const* out_planes, const size_t* out_steps, int mode) {
+    if (!planes || !steps || !out_planes || !out_steps || !(bits == 8 || bits == 10 || bits == 12 || bits == 16)) return 0;
+    try { return w2x::alpha_bleed_planes(planes, steps, planes[3], steps[3], rows, cols, bits > 8 ? 2 : 1, (1u << bits) - 1u, radius, out_planes, out_steps, mode) ? 1 : 0; } catch (...) { return 0; }
 }
 
 int w2x_tile_weights(int which, int overlap_x, int overlap_y, int size, float* out) {

@@ -1,6 +1,7 @@
 #include "args.h"
 #include "imageio.h"
 #include "../light.h"
+#include "../edge.h"
 
 #include <algorithm>
 #include <cmath>
@@ -73,6 +74,9 @@ std::string usage() {
            "      --resize-light TEXT [gamma]  (extension) {gamma,srgb,bt709}: the light --outscale / --outsize average in - gamma: the encoded values as they are;\n"
            "                              srgb, bt709: the frame is decoded by that transfer curve, resized in linear light and encoded again (thin lines and fine\n"
            "                              texture keep their brightness).  Alpha is never touched.  Every route that takes --outscale / --outsize honours it\n"
+           "      --edge TEXT [replicate] (extension) {replicate,wrap,mirror}: what lies beyond the frame edge - replicate: the edge pixel repeated; wrap: the frame\n"
+           "                              is one period of a texture that tiles (seamless textures); mirror: reflection.  Stills with and without alpha, --gray,\n"
+           "                              --rgb-in/out, --rgba-in/out, bgr24 video, --outscale / --outsize and --chain honour it; not with --colorspace\n"
            "      --colorspace TEXT       (extension) {bt601,bt709,bt2020}: videos read through ffmpeg stay YUV 4:2:0 at --pix_fmt\n"
            "                              (yuv420p or yuv420p10le) and are converted on the GPU; the output carries the colour tags\n"
            "      --color_range TEXT [tv] (extension) {tv,pc}: the range of the --colorspace frames\n"
@@ -136,7 +140,7 @@ int rgba_format_bits(const std::string& name) {
 Options parse(int argc, const char* const* argv) {
     Options o;
     std::vector<std::string> a(argv + 1, argv + argc);
-    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_outsize = false, seen_filter = false, seen_colorspace = false, seen_range = false, seen_bleed = false, seen_skip = false, seen_pixfmt = false, seen_gray = false, seen_dither = false, seen_light = false, seen_chain = false, seen_chain_noise = false;
+    bool seen_model = false, seen_scale = false, seen_noise = false, seen_batch = false, seen_tile = false, seen_outscale = false, seen_outsize = false, seen_filter = false, seen_colorspace = false, seen_range = false, seen_bleed = false, seen_skip = false, seen_pixfmt = false, seen_gray = false, seen_dither = false, seen_light = false, seen_edge = false, seen_chain = false, seen_chain_noise = false;
     auto value = [&](size_t& i) -> std::string {
         const std::string name = a[i];
         auto eq = name.find('=');
@@ -195,6 +199,7 @@ Options parse(int argc, const char* const* argv) {
         else if (k == "--chain-quantize") o.chainQuantize = true;
         else if (k == "--dither") { o.dither = value(i); std::transform(o.dither.begin(), o.dither.end(), o.dither.begin(), ::tolower); seen_dither = true; }
         else if (k == "--dither-temporal") { o.ditherTemporal = true; seen_dither = true; }
+        else if (k == "--edge") { o.edge = value(i); std::transform(o.edge.begin(), o.edge.end(), o.edge.begin(), ::tolower); seen_edge = true; }
         else if (k == "--resize-light") { o.resizeLight = value(i); std::transform(o.resizeLight.begin(), o.resizeLight.end(), o.resizeLight.begin(), ::tolower); seen_light = true; }
         else if (k == "--resize-filter") { o.resizeFilter = value(i); std::transform(o.resizeFilter.begin(), o.resizeFilter.end(), o.resizeFilter.begin(), ::tolower); seen_filter = true; }
         else if (k == "--colorspace") { o.colorspace = value(i); std::transform(o.colorspace.begin(), o.colorspace.end(), o.colorspace.begin(), ::tolower); seen_colorspace = true; }
@@ -272,6 +277,14 @@ Options parse(int argc, const char* const* argv) {
             int light_mode = 0;
             if (!light_parse_mode(o.resizeLight.c_str(), light_mode)) member<std::string>("--resize-light", o.resizeLight, {"gamma", "srgb", "bt709"});
         }
+        if (seen_edge) {                                                  // (a setting of the engines: every route of the RGB family honours it)
+            int edge_mode = 0;
+            if (!edge_parse_mode(o.edge.c_str(), edge_mode)) member<std::string>("--edge", o.edge, {"replicate", "wrap", "mirror"});
+            if (seen_colorspace) throw std::runtime_error("--edge: not together with --colorspace (YUV frames under an edge mode are not built)");
+            if (edge_mode != kEdgeReplicate && o.devices > 1)
+                for (const auto& p : o.inputs)
+                    if (!std::filesystem::is_directory(p) && is_builtin_still(p)) throw std::runtime_error("--edge " + o.edge + ": a still over --devices " + std::to_string(o.devices) + " is not supported (strips and shards under an edge mode are not built): " + p);
+        }
         if (seen_outscale && seen_outsize) throw std::runtime_error("--outsize: not together with --outscale (one of a factor and a size)");
         if (seen_colorspace) {
             member<std::string>("--colorspace", o.colorspace, {"bt601", "bt709", "bt2020"});
@@ -327,6 +340,7 @@ Options parse(int argc, const char* const* argv) {
         }
     } else if (seen_dither) throw std::runtime_error(std::string(o.ditherTemporal ? "--dither-temporal" : "--dither") + ": only with render");
     else if (seen_light) throw std::runtime_error("--resize-light: only with render");
+    else if (seen_edge) throw std::runtime_error("--edge: only with render");
     else if (seen_gray) throw std::runtime_error("--gray: only with render");
     else if (seen_rgb_in || seen_rgb_out) throw std::runtime_error(std::string(seen_rgb_in ? "--rgb-in" : "--rgb-out") + ": only with render");
     else if (seen_rgba_in || seen_rgba_out) throw std::runtime_error(std::string(seen_rgba_in ? "--rgba-in" : "--rgba-out") + ": only with render");
@@ -387,7 +401,7 @@ std::string to_json(const Options& o) {
        << ", \"precision\": " << q(o.precision) << ", \"recursive\": " << (o.recursive ? "true" : "false") << ", \"output\": " << q(o.output)
        << ", \"nosuffix\": " << (o.nosuffix ? "true" : "false") << ", \"blend\": " << o.blend << ", \"tta\": " << (o.tta ? "true" : "false") << ", \"tta_mode\": " << q(o.ttaMode)
        << ", \"outscale\": " << (o.outscale > 0 ? std::to_string(o.outscale) : std::string("null")) << ", \"outsize\": " << (o.outsizeW > 0 ? "[" + std::to_string(o.outsizeW) + ", " + std::to_string(o.outsizeH) + "]" : std::string("null"))
-       << ", \"resize_filter\": " << q(o.resizeFilter) << ", \"resize_light\": " << q(o.resizeLight)
+       << ", \"resize_filter\": " << q(o.resizeFilter) << ", \"resize_light\": " << q(o.resizeLight) << ", \"edge\": " << q(o.edge)
        << ", \"colorspace\": " << (o.colorspace.empty() ? std::string("null") : q(o.colorspace)) << ", \"color_range\": " << q(o.colorRange)
        << ", \"chroma_loc\": " << (o.chromaLoc.empty() ? std::string("null") : q(o.chromaLoc))
        << ", \"yuv_in\": " << (o.yuvIn.empty() ? std::string("null") : q(o.yuvIn)) << ", \"yuv_out\": " << (o.yuvOut.empty() ? std::string("null") : q(o.yuvOut))

@@ -37,6 +37,7 @@ struct Options {
     int outsizeW = 0, outsizeH = 0;       // --outsize WxH: every output exactly W x H, each input w x h with w <= W <= w * scale, h <= H <= h * scale (the two factors
                                           // independent): resized on the device like --outscale; with --colorspace through Img2Img::renderSequenceYuvResized; 0 = not given
     std::string resizeFilter = "bicubic"; // --resize-filter {bicubic,bilinear}: the antialiasing filter of --outscale / --outsize
+    std::string edge = "replicate";       // --edge {replicate,wrap,mirror}: what tiles, the colour bleed and the resize read beyond the frame edge (Img2Img::setEdge)
     std::string resizeLight = "gamma";    // --resize-light {gamma,srgb,bt709}: the light --outscale / --outsize average in (Img2Img::setResizeLight)
     std::string colorspace;               // --colorspace {bt601,bt709,bt2020}: videos read through ffmpeg travel as raw --pix_fmt (yuv420p / yuv420p10le)
                                           // frames, converted on the GPU (Img2Img::renderSequenceYuv); "" = bgr24 frames, the reference's path

@@ -281,6 +281,10 @@ int main(int argc, char** argv) {
             return true;
         };
         if (!dither_on(true)) return -1;
+        // --edge: a setting of the engines likewise, and one that stays on for the alpha plane's own frame - every route below reads beyond the frame edge by it
+        const EdgeMode edge = o.edge == "wrap" ? EdgeMode::Wrap : o.edge == "mirror" ? EdgeMode::Mirror : EdgeMode::Replicate;
+        for (auto& e : engines) if (!e->setEdge(edge)) return -1;
+        if (chainEngine && !chainEngine->setEdge(edge)) return -1;
         // --outscale (extension): every output lround(W * F) x lround(H * F), the network's output resized on the device; --outsize: every output W x H
         const ResizeFilter filter = o.resizeFilter == "bilinear" ? ResizeFilter::Bilinear : ResizeFilter::Bicubic;
         const bool resize = o.outscale > 0 || o.outsizeW > 0;

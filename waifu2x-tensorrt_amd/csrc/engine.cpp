@@ -284,7 +284,7 @@ struct Img2Img::Impl {
     // once per (canvas size, target size, filter).
     float* d_canvas = nullptr; size_t canvas_cap = 0;
     struct ResizeTables {
-        int inW = 0, inH = 0, outW = 0, outH = 0, filter = 0;
+        int inW = 0, inH = 0, outW = 0, outH = 0, filter = 0, edge = kEdgeReplicate;
         int *fx = nullptr, *fy = nullptr; float *wx = nullptr, *wy = nullptr;
         int kx = 0, ky = 0, rows_max = 0;
         int rows_max_above = 0;                                              // rows_max of a tile and the output row above it (top-left sited 4:2:0 output)
@@ -359,6 +359,17 @@ struct Img2Img::Impl {
     // never passes through the curves.
     ResizeLight light = ResizeLight::Gamma;
     LightArgs light_now() const { return light_args((int)light); }
+    // Edge modes (setEdge): an engine-wide setting like the two above.  Unlike them it is read INSIDE the captured passes - the gather launch is part
+    // of a pass's graph - so it is part of the pass key (sample_format()); the bleed and the resize of a frame read it outside them.  A chained render's stage
+    // gathers under its own engine's mode, and the resize at its end is the last engine's.
+    int edge = kEdgeReplicate;
+    // What is not built under Wrap and Mirror - YUV frames, strips and shards - is refused by name before anything else is looked at: true, and
+    // the message names setEdge.  Replicate: false, the call goes on as it always did.
+    bool edge_refuses(const char* who, const char* what) {
+        if (edge == kEdgeReplicate) return false;
+        log(Severity::error, std::string(what) + " not built under setEdge(" + edge_mode_name(edge) + "): only setEdge(replicate) serves this call.", who, __LINE__);
+        return true;
+    }
     Job job;
     struct JobScope { Impl* im; ~JobScope() { im->job = Job{}; } };
     // Chained renders (runChained).  On engines[0]: the frames between the stages (d_chain[k]: stage k's output) and the events that order the
@@ -1129,7 +1140,11 @@ struct Img2Img::Impl {
     //
     // The key of a captured pass: the sample format - 0 / 1 BGR of 8 / 16 bits, 2 .. 49 YuvJob::key, kRgbaKey, kGrayKey / kGrayKey + 1 gray of 8 / 16 bits, kPlanarKey .. + 4 planar by
     // input depth, kPlanarRgbaKey .. + 4 planar RGBA likewise - and the buffer the pass's gather reads (an RGBA or planar RGBA pass reads d_bgr / d_alpha, never d_frame: its graphs do not depend on which frame buffer of a sequence is current)
-    int sample_format() const {
+    // The edge mode is part of it too (kEdgeKey per mode, above every format's key): the gather kernel a captured pass bakes in is an instantiation per mode, and
+    // a call after setEdge() must not replay the old one.
+    static constexpr int kEdgeKey = 1024;
+    int sample_format() const { return frame_format() + kEdgeKey * edge; }
+    int frame_format() const {
         if (job.chain.src) return kChainKey;
         switch (job.kind) {
             case Job::YUV: return job.yuv.key;
@@ -1164,13 +1179,13 @@ struct Img2Img::Impl {
             bp.colour_step = bp.alpha_step = planar_step(cols, job.planar.in_bits);
             for (int k = 0; k < 3; ++k) bp.colour[k] = d_bgr + (size_t)k * bp.colour_step * rows;
             bp.alpha = d_alpha; bp.minmax = d_minmax;
-            hipAssert(launch_alpha_bleed_planes(bp, stream));
+            hipAssert(launch_alpha_bleed_planes(bp, stream, edge == kEdgeWrap));
             return;
         }
         AlphaBleedParams bp;
         bp.bgra = d_frame; bp.step = (size_t)cols * 4; bp.rows = rows; bp.cols = cols; bp.radius = radius;
         bp.bgr = d_bgr; bp.bgr_step = (size_t)cols * 3; bp.alpha = d_alpha; bp.alpha_step = (size_t)cols; bp.minmax = d_minmax;
-        hipAssert(launch_alpha_bleed(bp, stream));
+        hipAssert(launch_alpha_bleed(bp, stream, edge == kEdgeWrap));
     }
     // the value of a uniform alpha plane as the gather would read it, from its key (job.rgba.value)
     float uniform_alpha() const {
@@ -1214,11 +1229,11 @@ struct Img2Img::Impl {
         if (job.chain.src) {                                          // a later stage of a chained render: the tiles copied out of the frame of tile pixels
             GatherPxParams p = tile_side<GatherPxParams>(gp);
             p.frame = job.chain.src; p.rows = gp.rows; p.cols = gp.cols;
-            hipAssert(launch_gather_px(p, gs));
+            hipAssert(launch_gather_px(p, gs, edge));
             return;
         }
         switch (job.kind) {
-            case Job::BGR: hipAssert(launch_gather(gp, gs)); break;
+            case Job::BGR: hipAssert(launch_gather(gp, gs, edge)); break;
             case Job::YUV: {                                          // the same tiles from the frame's planes
                 GatherYuvParams p = tile_side<GatherYuvParams>(gp);
                 p.src = yuv_layout(d_frame, gp.rows, gp.cols, job.yuv.in_bits, job.yuv.in_layout); p.src.siting = job.yuv.in_siting; p.k = job.yuv.in;
@@ -1228,13 +1243,13 @@ struct Img2Img::Impl {
             case Job::RGBA: {                                         // from the bled BGR frame or the alpha plane
                 GatherRgbaParams p = tile_side<GatherRgbaParams>(gp);
                 p.bgr = d_bgr; p.bgr_step = (size_t)gp.cols * 3; p.alpha = d_alpha; p.alpha_step = (size_t)gp.cols; p.rows = gp.rows; p.cols = gp.cols;
-                hipAssert(launch_gather_rgba(p, gs));
+                hipAssert(launch_gather_rgba(p, gs, edge));
                 break;
             }
             case Job::GRAY: case Job::PLANAR: {                       // from the frame's one plane or three
                 GatherPlanarParams p = tile_side<GatherPlanarParams>(gp);
                 p.src = frame_planes(d_frame, gp.rows, gp.cols, false);
-                hipAssert(launch_gather_planar(p, gs));
+                hipAssert(launch_gather_planar(p, gs, edge));
                 break;
             }
             case Job::PLANAR_RGBA: {                                  // from the bled colour planes or the alpha plane
@@ -1243,7 +1258,7 @@ struct Img2Img::Impl {
                 p.colour_step = p.alpha_step = planar_step(gp.cols, p.bits);
                 for (int k = 0; k < 3; ++k) p.colour[k] = d_bgr + (size_t)k * p.colour_step * gp.rows;
                 p.alpha = d_alpha;
-                hipAssert(launch_gather_planar_rgba(p, gs));
+                hipAssert(launch_gather_planar_rgba(p, gs, edge));
                 break;
             }
         }
@@ -1265,10 +1280,12 @@ struct Img2Img::Impl {
             default: hipAssert(launch_compose_canvas(cp, d_canvas, on, light_now()));
         }
     }
-    template <class P> void resample_into(P& p, hipStream_t on, hipError_t (*launch)(const P&, hipStream_t, const DitherArgs&, const LightArgs&)) {
+    // (the edge mode of a resize launch is the one its tables were made under: job.rs->edge)
+    EdgeArgs resize_edge() const { EdgeArgs e; e.mode = job.rs->edge; return e; }
+    template <class P> void resample_into(P& p, hipStream_t on, hipError_t (*launch)(const P&, hipStream_t, const DitherArgs&, const LightArgs&, const EdgeArgs&)) {
         resample_base(p);
         p.dst = d_out; p.dst_step = frame_step(p.outW, true);
-        hipAssert(launch(p, on, dither_now(), light_now()));
+        hipAssert(launch(p, on, dither_now(), light_now(), resize_edge()));
     }
     void resample(hipStream_t on) {
         switch (job.kind) {
@@ -1278,7 +1295,7 @@ struct Img2Img::Impl {
                 ResamplePlanarParams p;
                 resample_base(p);
                 p.dst = frame_planes(d_out, p.outH, p.outW, true);
-                hipAssert(launch_resample_planar(p, on, dither_now(), light_now()));
+                hipAssert(launch_resample_planar(p, on, dither_now(), light_now(), resize_edge()));
                 break;
             }
             case Job::PLANAR_RGBA: {                                  // the four planes of the target size
@@ -1286,7 +1303,7 @@ struct Img2Img::Impl {
                 resample_base(p);
                 p.dst = rgba_planes(d_out, p.outH, p.outW, true);
                 p.uniform = job.rgba.uniform ? 1 : 0; p.alpha_value = uniform_alpha();
-                hipAssert(launch_resample_planar_rgba(p, on, dither_now(), light_now()));
+                hipAssert(launch_resample_planar_rgba(p, on, dither_now(), light_now(), resize_edge()));
                 break;
             }
             case Job::YUV: {                                          // the planes of job.yuv.out_layout at the target size
@@ -1731,17 +1748,21 @@ struct Img2Img::Impl {
     }
     // the device tap tables of one (canvas, target, filter): what job_resize() puts into the job for the frame
     const ResizeTables* resize_tables(int inW, int inH, int outW, int outH, int filter) {
-        for (const ResizeTables& t : rs_tables) if (t.inW == inW && t.inH == inH && t.outW == outW && t.outH == outH && t.filter == filter) return &t;
+        for (const ResizeTables& t : rs_tables) if (t.inW == inW && t.inH == inH && t.outW == outW && t.outH == outH && t.filter == filter && t.edge == edge) return &t;
         if (rs_tables.size() >= 16) {                                        // sizes that keep changing: start over rather than grow without bound
             for (ResizeTables& t : rs_tables) for (void* q : {(void*)t.fx, (void*)t.fy, (void*)t.wx, (void*)t.wy}) if (q) hipAssert(hipFree(q));
             rs_tables.clear();
         }
-        const ResizeTaps tx = resize_taps(inW, outW, filter), ty = resize_taps(inH, outH, filter);
+        // (under Wrap and Mirror the tables keep every tap - resize_taps_edge - and a tile's rows are not cut at the canvas: rows_max from those tables; no YUV
+        // frame is resized under such a mode, so rows_max_above stays 0 there)
+        const ResizeTaps tx = resize_taps_edge(inW, outW, filter, edge), ty = resize_taps_edge(inH, outH, filter, edge);
         if (tx.taps <= 0 || ty.taps <= 0) throw std::runtime_error("invalid resize");
         ResizeTables t;
-        t.inW = inW; t.inH = inH; t.outW = outW; t.outH = outH; t.filter = filter; t.kx = tx.taps; t.ky = ty.taps;
-        t.rows_max = resample_rows_max(ty.first.data(), outH, inH, ty.taps);
-        t.rows_max_above = resample_rows_max(ty.first.data(), outH, inH, ty.taps, 1);
+        t.inW = inW; t.inH = inH; t.outW = outW; t.outH = outH; t.filter = filter; t.edge = edge; t.kx = tx.taps; t.ky = ty.taps;
+        if (edge == kEdgeReplicate) {
+            t.rows_max = resample_rows_max(ty.first.data(), outH, inH, ty.taps);
+            t.rows_max_above = resample_rows_max(ty.first.data(), outH, inH, ty.taps, 1);
+        } else t.rows_max = resample_rows_max_edge(ty.first.data(), outH, ty.taps);
         auto upload = [&](auto*& d, const auto& v) {
             hipAssert(hipMalloc((void**)&d, v.size() * sizeof(v[0])));
             hipAssert(hipMemcpy(d, v.data(), v.size() * sizeof(v[0]), hipMemcpyHostToDevice));
@@ -1984,7 +2005,10 @@ bool Img2Img::renderResized(const Image& src, Image& dst, ResizeFilter filter) {
 
 // One GPU's share of a frame when a single image is spread over several devices: renders and writes only the
 // output columns strip_plan() assigns to `part`; the other columns of dst are left untouched.  part 0 of 1 = render().
-bool Img2Img::renderStrip(const Image& src, Image& dst, int part, int parts) { return renderPart(src, dst, part, parts, "renderStrip"); }
+bool Img2Img::renderStrip(const Image& src, Image& dst, int part, int parts) {
+    if (impl->edge_refuses("renderStrip", "Strips of a frame are")) return false;
+    return renderPart(src, dst, part, parts, "renderStrip");
+}
 
 bool Img2Img::renderPart(const Image& src, Image& dst, int part, int parts, const char* who, int resizeFilter) {
     return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
@@ -2130,6 +2154,11 @@ bool Img2Img::renderSharded(Img2Img* const* engines, int count, const Image& src
     if (!engines || count <= 0 || !engines[0]) return false;
     Img2Img* const first = engines[0];
     Impl* const impl = first->impl.get();                      // (the log macros name `impl`)
+    for (int k = 0; k < count; ++k)                            // (any engine under Wrap or Mirror: refused through engines[0]'s callback)
+        if (engines[k] && engines[k]->impl->edge != kEdgeReplicate) {
+            W2X_LOG(error, "Shards of a frame are not built under setEdge(" + std::string(edge_mode_name(engines[k]->impl->edge)) + ") (engine " + std::to_string(k) + "): only setEdge(replicate) serves this call.");
+            return false;
+        }
     try {
         for (int k = 0; k < count; ++k) {
             if (!engines[k] || !engines[k]->impl->loaded) { W2X_LOG(error, "Render called before a successful load (engine " + std::to_string(k) + ")."); return false; }
@@ -2193,6 +2222,7 @@ bool Img2Img::renderSharded(Img2Img* const* engines, int count, const Image& src
 // the data path: the seam bands are device-to-device copies out of the neighbours' slabs.
 bool Img2Img::shardCompute(const Image& src, int part, int parts) {
     const char* who = "shardCompute";
+    if (impl->edge_refuses(who, "Shards of a frame are")) return false;
     return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
     if (parts <= 0 || part < 0 || part >= parts) { W2X_LOG_AS(who, error, "Invalid part index."); return false; }
     if (const std::string why = shard_frame_problem(*impl, src, nullptr); !why.empty()) { W2X_LOG_AS(who, error, why); return false; }
@@ -2215,6 +2245,7 @@ const void* Img2Img::shardSlab(size_t* bytes) const { if (bytes) *bytes = impl->
 bool Img2Img::shardFinish(Image& dst, int part, int parts, const void* const* slabs, const int* devices) {
     const char* who = "shardFinish";
     const char* no_compute = "shardFinish without a shardCompute.";
+    if (impl->edge_refuses(who, "Shards of a frame are")) return false;
     return impl->entry(who, no_compute, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
     if (impl->shard_rows <= 0) { W2X_LOG_AS(who, error, no_compute); return false; }
     if (parts <= 0 || part < 0 || part >= parts || !slabs) { W2X_LOG_AS(who, error, "Invalid part index."); return false; }
@@ -2307,6 +2338,7 @@ bool Img2Img::renderSequenceYuvResized(const YuvImage* srcs, YuvImage* dsts, int
 // resizeFilter >= 0 (renderYuvResized / renderSequenceYuvResized): every dst is the target size of dsts[0], the frame step ends with the canvas compose
 // and resample_yuv_kernel; at the scaled size it is the plain sequence.
 bool Img2Img::runSequenceYuv(const YuvImage* srcs, YuvImage* dsts, int count, YuvFormat format, int resizeFilter, const char* who) {
+    if (impl->edge_refuses(who, "YUV frames are")) return false;
     return impl->entry(who, kNotLoaded, kRenderFailed, [&] {   // (the call's own work, to the closing `});` - deliberately left at function indentation)
     if (count <= 0) return true;
     if (!srcs || !dsts) { W2X_LOG_AS(who, error, "No frames given."); return false; }
@@ -2801,6 +2833,13 @@ bool Img2Img::ditherPlanes(const PlanarImage& src, PlanarImage& dst) {
     });
 }
 
+bool Img2Img::setEdge(EdgeMode mode) {
+    if (!edge_mode_ok((int)mode)) { W2X_LOG(error, "Unknown edge mode " + std::to_string((int)mode) + ": expected replicate, wrap or mirror."); return false; }
+    impl->edge = (int)mode;
+    return true;
+}
+EdgeMode Img2Img::edge() const { return (EdgeMode)impl->edge; }
+
 bool Img2Img::setResizeLight(ResizeLight mode) {
     if (!light_mode_ok((int)mode)) { W2X_LOG(error, "Unknown resize light " + std::to_string((int)mode) + ": expected gamma, srgb or bt709."); return false; }
     impl->light = mode;
@@ -2840,7 +2879,8 @@ bool Img2Img::resizePlanes(const PlanarImage& src, PlanarImage& dst, ResizeFilte
     p.fx = rs->fx; p.wx = rs->wx; p.kx = rs->kx; p.fy = rs->fy; p.wy = rs->wy; p.ky = rs->ky; p.rows_max = rs->rows_max;
     p.dst.rows = out_rows; p.dst.cols = out_cols; p.dst.n = 3; p.dst.bits = bits;
     for (int k = 0; k < 3; ++k) { p.dst.p[k] = impl->d_out + (size_t)k * out_step * out_rows; p.dst.step[k] = out_step; }
-    hipAssert(launch_resample_planar(p, impl->stream, impl->dither_now(), light));
+    EdgeArgs edge; edge.mode = rs->edge;
+    hipAssert(launch_resample_planar(p, impl->stream, impl->dither_now(), light, edge));
     for (int k = 0; k < 3; ++k) hipAssert(hipMemcpy2DAsync(dst.planes[k], dst.steps[k], p.dst.p[k], out_step, out_width, out_rows, hipMemcpyDeviceToHost, impl->stream));
     hipAssert(hipStreamSynchronize(impl->stream));
     return true;

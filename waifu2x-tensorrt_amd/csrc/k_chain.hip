@@ -42,11 +42,11 @@ __global__ __launch_bounds__(kComposeThreads) void compose_px_kernel(const Compo
     }
 }
 
-template <typename P>
+template <typename P, int E = kEdgeReplicate>
 __global__ __launch_bounds__(kGatherThreads) void gather_px_kernel(const GatherPxParams p) {
     const P* const frame = (const P*)p.frame;
     const int cols = p.cols;
-    gather_loop<P>(p.slots, p.B, p.T, p.rows, p.cols, p.out, [&](const TileSlot&, int fy, int fx) { return frame[(size_t)fy * cols + fx]; });
+    gather_loop<P, E>(p.slots, p.B, p.T, p.rows, p.cols, p.out, [&](const TileSlot&, int fy, int fx) { return frame[(size_t)fy * cols + fx]; });
 }
 
 }  // namespace
@@ -67,14 +67,17 @@ hipError_t launch_compose_px(const ComposePxParams& p, hipStream_t s) {
     return hipGetLastError();
 }
 
-hipError_t launch_gather_px(const GatherPxParams& p, hipStream_t s) {
+hipError_t launch_gather_px(const GatherPxParams& p, hipStream_t s, int edge) {
     if (p.B <= 0) return hipSuccess;
     const size_t px = p.fp32 ? 16 : 8;
     if (!p.frame || !p.out || !p.slots || p.rows <= 0 || p.cols <= 0 || p.T <= 0 || (((size_t)p.frame) & (px - 1)) != 0) return hipErrorInvalidValue;
     const dim3 grid(grid_for((long)p.B * p.T * p.T));
-    if (p.fp32) hipLaunchKernelGGL(gather_px_kernel<float4v>, grid, dim3(kGatherThreads), 0, s, p);
-    else hipLaunchKernelGGL(gather_px_kernel<half4>, grid, dim3(kGatherThreads), 0, s, p);
-    return hipGetLastError();
+    return for_edge(edge, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        if (p.fp32) hipLaunchKernelGGL((gather_px_kernel<float4v, E>), grid, dim3(kGatherThreads), 0, s, p);
+        else hipLaunchKernelGGL((gather_px_kernel<half4, E>), grid, dim3(kGatherThreads), 0, s, p);
+        return hipGetLastError();
+    });
 }
 
 }  // namespace w2x

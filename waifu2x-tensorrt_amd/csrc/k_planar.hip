@@ -17,9 +17,9 @@
 namespace w2x {
 namespace {
 
-template <typename P, typename S, int NP>
+template <typename P, typename S, int NP, int E = kEdgeReplicate>
 __global__ __launch_bounds__(kGatherThreads) void gather_planes_kernel(const GatherPlanarParams p, unsigned maxcode, float inv) {
-    gather_loop<P>(p.slots, p.B, p.T, p.src.rows, p.src.cols, p.out, [&](const TileSlot&, int fy, int fx) {
+    gather_loop<P, E>(p.slots, p.B, p.T, p.src.rows, p.src.cols, p.out, [&](const TileSlot&, int fy, int fx) {
         float a[NP];
 #pragma unroll
         for (int c = 0; c < NP; ++c) a[c] = load_sample<S>(p.src.p[c] + (size_t)fy * p.src.step[c], fx, maxcode, inv);
@@ -89,12 +89,13 @@ __global__ __launch_bounds__(kRsThreads) void resample_planes_kernel(const Resam
     const DitherArgs& dz = dither_of(dzs...);
     constexpr bool kLin = light_on<D...>;                                 // 
     const LightArgs& lz = light_of(dzs...);
+    constexpr bool kEdge = edge_on<D...>;                                 // 
     extern __shared__ float h[];
-    const int r0 = resample_pass1<NP>(p, h);
+    const int r0 = resample_pass1<NP, kEdge>(p, h, edge_of(dzs...).mode);
     __syncthreads();
     float4v a[NP];
     int X, Y, np;
-    if (!resample_pass2<NP>(p, h, r0, a, X, Y, np)) return;
+    if (!resample_pass2<NP, kEdge>(p, h, r0, a, X, Y, np)) return;
 #pragma unroll
     for (int c = 0; c < NP; ++c) {
         const float v[4] = {light_out<kLin>(lz, a[c][0]), light_out<kLin>(lz, a[c][1]), light_out<kLin>(lz, a[c][2]), light_out<kLin>(lz, a[c][3])};
@@ -121,7 +122,7 @@ template <typename Launch> hipError_t for_planes(const PlanarPlanes& f, Launch l
 
 }  // namespace
 
-hipError_t launch_gather_planar(const GatherPlanarParams& p, hipStream_t s) {
+hipError_t launch_gather_planar(const GatherPlanarParams& p, hipStream_t s, int edge) {
     if (!planes_ok(p.src, p.src.rows, p.src.cols)) return hipErrorInvalidValue;
     const dim3 grid(grid_for((long)p.B * p.T * p.T));
     const unsigned maxcode = (unsigned)max_code(p.src.bits);
@@ -129,9 +130,12 @@ hipError_t launch_gather_planar(const GatherPlanarParams& p, hipStream_t s) {
     return for_planes(p.src, [&](auto k) {
         typedef typename decltype(k)::Sample S;
         constexpr int NP = decltype(k)::kPlanes;
-        if (p.fp32) hipLaunchKernelGGL((gather_planes_kernel<float4v, S, NP>), grid, dim3(kGatherThreads), 0, s, p, maxcode, inv);
-        else hipLaunchKernelGGL((gather_planes_kernel<half4, S, NP>), grid, dim3(kGatherThreads), 0, s, p, maxcode, inv);
-        return hipGetLastError();
+        return for_edge(edge, [&](auto e) {
+            constexpr int E = decltype(e)::value;
+            if (p.fp32) hipLaunchKernelGGL((gather_planes_kernel<float4v, S, NP, E>), grid, dim3(kGatherThreads), 0, s, p, maxcode, inv);
+            else hipLaunchKernelGGL((gather_planes_kernel<half4, S, NP, E>), grid, dim3(kGatherThreads), 0, s, p, maxcode, inv);
+            return hipGetLastError();
+        });
     });
 }
 hipError_t launch_compose_planar(const ComposePlanarParams& p, hipStream_t s, const DitherArgs& d) {
@@ -170,7 +174,7 @@ hipError_t launch_compose_canvas_gray(const ComposeParams& p, float* canvas, hip
     else hipLaunchKernelGGL(compose_canvas_gray_kernel<half4>, grid, dim3(256), 0, s, p, canvas);
     return hipGetLastError();
 }
-hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s, const DitherArgs& d, const LightArgs& l) {
+hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s, const DitherArgs& d, const LightArgs& l, const EdgeArgs& e) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
     if (!p.canvas || !planes_ok(p.dst, p.outH, p.outW) || !dither_args_ok(d)) return hipErrorInvalidValue;
     const int maxcode = max_code(p.dst.bits);
@@ -182,8 +186,8 @@ hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s, 
             static unsigned lds_done = 0;                                // (one per instantiation of this lambda's body)
             return launch_resample_tiles(resample_planes_kernel<S, NP, decltype(m)::value, std::decay_t<decltype(extra)>...>, NP * kRsCols, p.rows_max, lds_done, p.outW, p.outH, s, p, scale, maxcode, extra...);
         };
-        if constexpr (std::is_same<S, F32>::value) return for_light(l, go);   // (float samples are never dithered: no such kernels)
-        else return for_modes(d, l, go);
+        if constexpr (std::is_same<S, F32>::value) return for_light(l, e, go);   // (float samples are never dithered: no such kernels)
+        else return for_modes(d, l, e, go);
     });
 }
 

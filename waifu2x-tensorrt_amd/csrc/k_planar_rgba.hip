@@ -49,7 +49,9 @@ template <typename T> __device__ __forceinline__ void put4(uint8_t* row, int X, 
 template <typename S> __device__ __forceinline__ unsigned alpha_key(typename S::T a, unsigned maxcode) { return min((unsigned)a, maxcode); }
 template <> __device__ __forceinline__ unsigned alpha_key<F32>(float a, unsigned) { return a > 0.f ? __float_as_uint(fminf(a, 1.f)) : 0u; }   // (NaN, -0.0, < 0: 0)
 
-template <typename S>
+// kWrap (EdgeMode::Wrap): the halo outside the frame holds the frame's periodic continuation (edge_src<kEdgeWrap>) instead of the outside flag, so a
+// pixel's eight neighbours always exist and colour spreads across the joint; the iterations are the same.  false: the kernel it always was.
+template <typename S, bool kWrap = false>
 __global__ __launch_bounds__(256) void alpha_bleed_planes_kernel(const AlphaBleedPlanesParams p, unsigned maxcode) {
     typedef typename S::T T;
     constexpr bool kInt = !std::is_same<S, F32>::value;
@@ -66,9 +68,10 @@ __global__ __launch_bounds__(256) void alpha_bleed_planes_kernel(const AlphaBlee
             const int LH = kBleedTileH + 2 * R;
             for (int i = tid; i < LW * LH; i += 256) {
                 const int ly = i / LW, lx = i - ly * LW;
-                const int fy = y0 - R + ly, fx = x0 - R + lx;
+                int fy = y0 - R + ly, fx = x0 - R + lx;
+                if constexpr (kWrap) { fy = edge_src<kEdgeWrap>(fy, rows); fx = edge_src<kEdgeWrap>(fx, cols); }
                 uint2 v = make_uint2(0u, kOutsideFlag << 16);
-                if (fy >= 0 && fy < rows && fx >= 0 && fx < cols) {
+                if (kWrap || (fy >= 0 && fy < rows && fx >= 0 && fx < cols)) {
                     unsigned c[4];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) c[k] = min((unsigned)((const T*)(p.src.p[k] + (size_t)fy * p.src.step[k]))[fx], maxcode);
@@ -166,9 +169,9 @@ template <typename S> struct TilePx<half4, S> {
 };
 
 // gather_kernel's indexing (gather_loop) on the planes the slot names: the three colour planes, or the alpha plane three times - the frame (A, A, A)
-template <typename P, typename S>
+template <typename P, typename S, int E = kEdgeReplicate>
 __global__ __launch_bounds__(kGatherThreads) void gather_planes_rgba_kernel(const GatherPlanarRgbaParams p, unsigned maxcode, float inv) {
-    gather_loop<P>(p.slots, p.B, p.T, p.rows, p.cols, p.out, [&](const TileSlot& sl, int fy, int fx) {
+    gather_loop<P, E>(p.slots, p.B, p.T, p.rows, p.cols, p.out, [&](const TileSlot& sl, int fy, int fx) {
         if (sl.valid == kSlotAlpha) {
             const uint8_t* a = p.alpha + (size_t)fy * p.alpha_step;
             return TilePx<P, S>::make(a, a, a, fx, maxcode, inv);
@@ -229,12 +232,13 @@ template <typename S, int NP, int M = kDitherNone, typename... D>
 __global__ __launch_bounds__(kRsThreads) void resample_planes_rgba_kernel(const ResamplePlanarRgbaParams p, float scale, int maxcode, const D... dzs) {
     static_assert(dither_pack_ok<M, D...>, "kDitherNone: no DitherArgs, else one; then one LightArgs or none");
     const DitherArgs& dz = dither_of(dzs...);
+    constexpr bool kEdge = edge_on<D...>;                                 // 
     extern __shared__ float rsp_lds[];
-    const int r0 = resample_pass1<NP>(p, rsp_lds);
+    const int r0 = resample_pass1<NP, kEdge>(p, rsp_lds, edge_of(dzs...).mode);
     __syncthreads();
     float4v a[NP];
     int X, Y, np;
-    if (!resample_pass2<NP>(p, rsp_lds, r0, a, X, Y, np)) return;
+    if (!resample_pass2<NP, kEdge>(p, rsp_lds, r0, a, X, Y, np)) return;
     if constexpr (light_on<D...>) {                                       // (the colour planes are encoded, plane 3 - alpha - is not)
         const LightArgs& lz = light_of(dzs...);
 #pragma unroll
@@ -273,7 +277,7 @@ template <typename Launch> hipError_t for_sample(int bits, Launch launch) { retu
 
 }  // namespace
 
-hipError_t launch_alpha_bleed_planes(const AlphaBleedPlanesParams& p, hipStream_t s) {
+hipError_t launch_alpha_bleed_planes(const AlphaBleedPlanesParams& p, hipStream_t s, bool wrap) {
     const int rows = p.src.rows, cols = p.src.cols, bits = p.src.bits, R = p.radius;
     if (!rgba_planes_ok(p.src, rows, cols) || R < 0 || R > kBleedMaxRadius || (bits == 32 && R > 0) || !p.minmax) return hipErrorInvalidValue;
     for (int k = 0; k < 3; ++k) if (!plane_ok(p.colour[k], p.colour_step, cols, bits)) return hipErrorInvalidValue;
@@ -283,11 +287,12 @@ hipError_t launch_alpha_bleed_planes(const AlphaBleedPlanesParams& p, hipStream_
     const unsigned maxcode = (unsigned)max_code(bits);
     return for_sample(bits, [&](auto k) {
         typedef decltype(k) S;
-        hipLaunchKernelGGL(alpha_bleed_planes_kernel<S>, grid, dim3(256), lds, s, p, maxcode);
+        if (wrap) hipLaunchKernelGGL((alpha_bleed_planes_kernel<S, true>), grid, dim3(256), lds, s, p, maxcode);
+        else hipLaunchKernelGGL(alpha_bleed_planes_kernel<S>, grid, dim3(256), lds, s, p, maxcode);
         return hipGetLastError();
     });
 }
-hipError_t launch_gather_planar_rgba(const GatherPlanarRgbaParams& p, hipStream_t s) {
+hipError_t launch_gather_planar_rgba(const GatherPlanarRgbaParams& p, hipStream_t s, int edge) {
     if (!planar_bits_ok(p.bits) || p.rows <= 0 || p.cols <= 0 || !plane_ok(p.alpha, p.alpha_step, p.cols, p.bits)) return hipErrorInvalidValue;
     for (int k = 0; k < 3; ++k) if (!plane_ok(p.colour[k], p.colour_step, p.cols, p.bits)) return hipErrorInvalidValue;
     const dim3 grid(grid_for((long)p.B * p.T * p.T));
@@ -295,9 +300,12 @@ hipError_t launch_gather_planar_rgba(const GatherPlanarRgbaParams& p, hipStream_
     const float inv = inv_code(p.bits);
     return for_sample(p.bits, [&](auto k) {
         typedef decltype(k) S;
-        if (p.fp32) hipLaunchKernelGGL((gather_planes_rgba_kernel<float4v, S>), grid, dim3(kGatherThreads), 0, s, p, maxcode, inv);
-        else hipLaunchKernelGGL((gather_planes_rgba_kernel<half4, S>), grid, dim3(kGatherThreads), 0, s, p, maxcode, inv);
-        return hipGetLastError();
+        return for_edge(edge, [&](auto e) {
+            constexpr int E = decltype(e)::value;
+            if (p.fp32) hipLaunchKernelGGL((gather_planes_rgba_kernel<float4v, S, E>), grid, dim3(kGatherThreads), 0, s, p, maxcode, inv);
+            else hipLaunchKernelGGL((gather_planes_rgba_kernel<half4, S, E>), grid, dim3(kGatherThreads), 0, s, p, maxcode, inv);
+            return hipGetLastError();
+        });
     });
 }
 hipError_t launch_compose_planar_rgba(const ComposePlanarRgbaParams& p, hipStream_t s, const DitherArgs& d) {
@@ -322,7 +330,7 @@ hipError_t launch_compose_planar_rgba(const ComposePlanarRgbaParams& p, hipStrea
         return hipGetLastError();
     });
 }
-hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStream_t s, const DitherArgs& d, const LightArgs& l) {
+hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStream_t s, const DitherArgs& d, const LightArgs& l, const EdgeArgs& e) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
     if (!p.canvas || !rgba_planes_ok(p.dst, p.outH, p.outW) || !dither_args_ok(d)) return hipErrorInvalidValue;
     const int maxcode = max_code(p.dst.bits);
@@ -335,8 +343,8 @@ hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStr
             if (p.uniform) return launch_resample_tiles(resample_planes_rgba_kernel<S, 3, M, std::decay_t<decltype(extra)>...>, 3 * kRsCols, p.rows_max, lds_done[0], p.outW, p.outH, s, p, scale, maxcode, extra...);
             return launch_resample_tiles(resample_planes_rgba_kernel<S, 4, M, std::decay_t<decltype(extra)>...>, 4 * kRsCols, p.rows_max, lds_done[1], p.outW, p.outH, s, p, scale, maxcode, extra...);
         };
-        if constexpr (std::is_same<S, F32>::value) return for_light(l, go);   // (float samples are never dithered: no such kernels)
-        else return for_modes(d, l, go);
+        if constexpr (std::is_same<S, F32>::value) return for_light(l, e, go);   // (float samples are never dithered: no such kernels)
+        else return for_modes(d, l, e, go);
     });
 }
 

@@ -19,7 +19,8 @@
 namespace w2x {
 namespace {
 
-template <typename P>
+// E: the edge rule of the two source-index lines (edge_src); kEdgeReplicate is the clamp
+template <typename P, int E = kEdgeReplicate>
 __global__ __launch_bounds__(256) void gather_kernel(const GatherParams p) {
     const int T = p.T;
     const long total = (long)p.B * T * T;
@@ -33,8 +34,8 @@ __global__ __launch_bounds__(256) void gather_kernel(const GatherParams p) {
         if (sl.valid) {
             int sy, sx;
             aug_src(sl.aug, T - 1, y, x, sy, sx);
-            int fy = min(max(sl.y + sy, 0), p.rows - 1);
-            int fx = min(max(sl.x + sx, 0), p.cols - 1);
+            int fy = edge_src<E>(sl.y + sy, p.rows);
+            int fx = edge_src<E>(sl.x + sx, p.cols);
             if (!p.deep) {
                 const uint8_t* px = p.frame + (size_t)fy * p.step + (size_t)fx * 3;
                 v = make_px<P>((float)px[2] * inv255, (float)px[1] * inv255, (float)px[0] * inv255);
@@ -635,11 +636,20 @@ inline unsigned grid_for(long total) { long g = (total + 255) / 256; return (uns
 
 }  // namespace
 
-hipError_t launch_gather(const GatherParams& p, hipStream_t s) {
-    const dim3 grid(grid_for((long)p.B * p.T * p.T));
-    if (p.fp32) hipLaunchKernelGGL(gather_kernel<float4v>, grid, dim3(256), 0, s, p);
-    else hipLaunchKernelGGL(gather_kernel<half4>, grid, dim3(256), 0, s, p);
+template <int E>
+static hipError_t launch_gather_as(const GatherParams& p, dim3 grid, hipStream_t s) {
+    if (p.fp32) hipLaunchKernelGGL((gather_kernel<float4v, E>), grid, dim3(256), 0, s, p);
+    else hipLaunchKernelGGL((gather_kernel<half4, E>), grid, dim3(256), 0, s, p);
     return hipGetLastError();
+}
+hipError_t launch_gather(const GatherParams& p, hipStream_t s, int edge) {
+    const dim3 grid(grid_for((long)p.B * p.T * p.T));
+    switch (edge) {
+        case kEdgeReplicate: return launch_gather_as<kEdgeReplicate>(p, grid, s);
+        case kEdgeWrap: return launch_gather_as<kEdgeWrap>(p, grid, s);
+        case kEdgeMirror: return launch_gather_as<kEdgeMirror>(p, grid, s);
+    }
+    return hipErrorInvalidValue;                                    // no kernel for it: an error, never the replicating kernel
 }
 hipError_t launch_compose(const ComposeParams& p, hipStream_t s, const DitherArgs& d) {
     if (!dither_args_ok(d)) return hipErrorInvalidValue;

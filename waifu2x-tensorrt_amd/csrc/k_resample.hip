@@ -24,12 +24,13 @@ __global__ __launch_bounds__(kRsThreads) void resample_kernel(const ResamplePara
     const DitherArgs& dz = dither_of(dzs...);
     constexpr bool kLin = light_on<D...>;                                 // (the resized values are linear light and are encoded before they are quantised)
     const LightArgs& lz = light_of(dzs...);
+    constexpr bool kEdge = edge_on<D...>;                                 // (the input indices of the passes go through the edge rule)
     extern __shared__ float h[];                                          // [3][rows_max][kRsCols]
-    const int r0 = resample_pass1<3>(p, h);
+    const int r0 = resample_pass1<3, kEdge>(p, h, edge_of(dzs...).mode);
     __syncthreads();
     float4v a[3];                                                         // R, G, B of four pixels
     int X, Y, np;
-    if (!resample_pass2<3>(p, h, r0, a, X, Y, np)) return;
+    if (!resample_pass2<3, kEdge>(p, h, r0, a, X, Y, np)) return;
     if constexpr (kLin) {
 #pragma unroll
         for (int c = 0; c < 3; ++c)
@@ -87,9 +88,18 @@ int resample_rows_max(const int* fy, int outH, int inH, int ky, int rows_above) 
     return m;
 }
 
-hipError_t launch_resample(const ResampleParams& p, hipStream_t s, const DitherArgs& d, const LightArgs& l) {
+int resample_rows_max_edge(const int* fy, int outH, int ky) {
+    int m = 0;
+    for (int y0 = 0; y0 < outH; y0 += kRsRows) {
+        const int y1 = (y0 + kRsRows < outH ? y0 + kRsRows : outH) - 1;
+        if (fy[y1] + ky - fy[y0] > m) m = fy[y1] + ky - fy[y0];
+    }
+    return m;
+}
+
+hipError_t launch_resample(const ResampleParams& p, hipStream_t s, const DitherArgs& d, const LightArgs& l, const EdgeArgs& e) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
-    return for_modes(d, l, [&](auto m, const auto&... extra) {
+    return for_modes(d, l, e, [&](auto m, const auto&... extra) {
         static unsigned lds_done = 0;                                    // (one per instantiation of this lambda's body)
         return launch_resample_tiles(resample_kernel<decltype(m)::value, std::decay_t<decltype(extra)>...>, 3 * kRsCols, p.rows_max, lds_done, p.outW, p.outH, s, p, extra...);
     });

@@ -28,6 +28,9 @@ namespace {
 // radius 0: no LDS, the planes are split straight from the frame.
 constexpr unsigned kKnown = 1u << 24, kOutside = 2u << 24;
 
+// kWrap (EdgeMode::Wrap): the halo outside the frame holds the frame's periodic continuation (edge_src<kEdgeWrap>) instead of the outside flag, so a
+// pixel's eight neighbours always exist and colour spreads across the joint; the iterations are the same.  false: the kernel it always was.
+template <bool kWrap = false>
 __global__ __launch_bounds__(256) void alpha_bleed_kernel(const AlphaBleedParams p) {
     extern __shared__ unsigned bleed_lds[];
     __shared__ unsigned wg_max[2];
@@ -40,9 +43,10 @@ __global__ __launch_bounds__(256) void alpha_bleed_kernel(const AlphaBleedParams
     if (R > 0) {
         for (int i = tid; i < LW * LH; i += 256) {
             const int ly = i / LW, lx = i - ly * LW;
-            const int fy = y0 - R + ly, fx = x0 - R + lx;
+            int fy = y0 - R + ly, fx = x0 - R + lx;
+            if constexpr (kWrap) { fy = edge_src<kEdgeWrap>(fy, p.rows); fx = edge_src<kEdgeWrap>(fx, p.cols); }
             unsigned v = kOutside;
-            if (fy >= 0 && fy < p.rows && fx >= 0 && fx < p.cols) {
+            if (kWrap || (fy >= 0 && fy < p.rows && fx >= 0 && fx < p.cols)) {
                 const unsigned px = ((const unsigned*)(p.bgra + (size_t)fy * p.step))[fx];
                 v = (px & 0xFFFFFFu) | ((px >> 24) ? kKnown : 0u);
             }
@@ -116,10 +120,10 @@ __global__ __launch_bounds__(256) void alpha_bleed_kernel(const AlphaBleedParams
 }
 
 // gather_kernel's indexing (gather_loop: replicate padding, the TTA source map) on the plane the slot names
-template <typename P>
+template <typename P, int E = kEdgeReplicate>
 __global__ __launch_bounds__(kGatherThreads) void gather_rgba_kernel(const GatherRgbaParams p) {
     const float inv255 = (float)(1.0 / 255.0);
-    gather_loop<P>(p.slots, p.B, p.T, p.rows, p.cols, p.out, [&](const TileSlot& sl, int fy, int fx) {
+    gather_loop<P, E>(p.slots, p.B, p.T, p.rows, p.cols, p.out, [&](const TileSlot& sl, int fy, int fx) {
         if (sl.valid == kSlotAlpha) {
             const float a = (float)p.alpha[(size_t)fy * p.alpha_step + fx] * inv255;
             return make_px<P>(a, a, a);
@@ -195,12 +199,13 @@ __global__ __launch_bounds__(kRsThreads) void resample_rgba_kernel(const Resampl
     static_assert(dither_pack_ok<M, D...>, "kDitherNone: no DitherArgs, else one; then one LightArgs or none");
     const DitherArgs& dz = dither_of(dzs...);
     constexpr int NP = kAlpha ? 4 : 3;
+    constexpr bool kEdge = edge_on<D...>;                                 // 
     extern __shared__ float rs_lds[];
-    const int r0 = resample_pass1<NP>(p, rs_lds);
+    const int r0 = resample_pass1<NP, kEdge>(p, rs_lds, edge_of(dzs...).mode);
     __syncthreads();
     float4v a[NP];
     int X, Y, np;
-    if (!resample_pass2<NP>(p, rs_lds, r0, a, X, Y, np)) return;
+    if (!resample_pass2<NP, kEdge>(p, rs_lds, r0, a, X, Y, np)) return;
     if constexpr (light_on<D...>) {                                       // (the colour is encoded, alpha - a[3] - is not)
         const LightArgs& lz = light_of(dzs...);
 #pragma unroll
@@ -223,19 +228,23 @@ __global__ __launch_bounds__(kRsThreads) void resample_rgba_kernel(const Resampl
 
 }  // namespace
 
-hipError_t launch_alpha_bleed(const AlphaBleedParams& p, hipStream_t s) {
+hipError_t launch_alpha_bleed(const AlphaBleedParams& p, hipStream_t s, bool wrap) {
     if (p.rows <= 0 || p.cols <= 0 || p.radius < 0 || p.radius > kBleedMaxRadius) return hipErrorInvalidValue;
     const int R = p.radius;
     const size_t lds = R > 0 ? (size_t)2 * (kBleedTileW + 2 * R) * (kBleedTileH + 2 * R) * sizeof(unsigned) : 0;
     const dim3 grid((unsigned)((p.cols + kBleedTileW - 1) / kBleedTileW), (unsigned)((p.rows + kBleedTileH - 1) / kBleedTileH));
-    hipLaunchKernelGGL(alpha_bleed_kernel, grid, dim3(256), lds, s, p);
+    if (wrap) hipLaunchKernelGGL(alpha_bleed_kernel<true>, grid, dim3(256), lds, s, p);
+    else hipLaunchKernelGGL(alpha_bleed_kernel<false>, grid, dim3(256), lds, s, p);
     return hipGetLastError();
 }
-hipError_t launch_gather_rgba(const GatherRgbaParams& p, hipStream_t s) {
+hipError_t launch_gather_rgba(const GatherRgbaParams& p, hipStream_t s, int edge) {
     const dim3 grid(grid_for((long)p.B * p.T * p.T));
-    if (p.fp32) hipLaunchKernelGGL(gather_rgba_kernel<float4v>, grid, dim3(kGatherThreads), 0, s, p);
-    else hipLaunchKernelGGL(gather_rgba_kernel<half4>, grid, dim3(kGatherThreads), 0, s, p);
-    return hipGetLastError();
+    return for_edge(edge, [&](auto e) {
+        constexpr int E = decltype(e)::value;
+        if (p.fp32) hipLaunchKernelGGL((gather_rgba_kernel<float4v, E>), grid, dim3(kGatherThreads), 0, s, p);
+        else hipLaunchKernelGGL((gather_rgba_kernel<half4, E>), grid, dim3(kGatherThreads), 0, s, p);
+        return hipGetLastError();
+    });
 }
 hipError_t launch_compose_rgba(const ComposeRgbaParams& p, hipStream_t s, const DitherArgs& d) {
     if (p.c.outW <= 0 || p.c.outH <= 0) return hipSuccess;
@@ -264,10 +273,10 @@ hipError_t launch_compose_canvas_rgba(const ComposeCanvasRgbaParams& p, hipStrea
     else hipLaunchKernelGGL(compose_canvas_rgba_kernel<half4>, grid, dim3(256), 0, s, p);
     return hipGetLastError();
 }
-hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s, const DitherArgs& d, const LightArgs& l) {
+hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s, const DitherArgs& d, const LightArgs& l, const EdgeArgs& e) {
     if (p.outW <= 0 || p.outH <= 0) return hipSuccess;
     if ((p.dst_step & 3) || p.dst_step < (size_t)p.outW * 4 || (((size_t)p.dst) & 3)) return hipErrorInvalidValue;
-    return for_modes(d, l, [&](auto m, const auto&... extra) {
+    return for_modes(d, l, e, [&](auto m, const auto&... extra) {
         constexpr int M = decltype(m)::value;
         static unsigned lds_done[2] = {0, 0};                            // (a pair per instantiation of this lambda's body)
         if (p.uniform) return launch_resample_tiles(resample_rgba_kernel<false, M, std::decay_t<decltype(extra)>...>, 3 * kRsCols, p.rows_max, lds_done[0], p.outW, p.outH, s, p, extra...);

@@ -6,6 +6,7 @@
 #include "switches.h"
 #include "dither.h"
 #include "light.h"
+#include "edge.h"
 #include <cstdint>
 
 namespace w2x {
@@ -285,7 +286,9 @@ hipError_t launch_dither_planes(const PlanarPlanes& src, const PlanarPlanes& dst
 hipError_t launch_light_decode_planes(float* v, size_t n, const LightArgs& l, hipStream_t s);
 hipError_t launch_se(const SeParams& p, hipStream_t s);
 hipError_t launch_scale(void* x, const float* scale, int B, int HW, int Cs, bool fp32, hipStream_t s);
-hipError_t launch_gather(const GatherParams& p, hipStream_t s);
+// edge (every gather launcher of the RGB family): the rule that replaces the two clamp lines, a template parameter of the kernel; kEdgeReplicate - the
+// default - launches the kernel that never heard of it; an unknown mode is hipErrorInvalidValue
+hipError_t launch_gather(const GatherParams& p, hipStream_t s, int edge = kEdgeReplicate);
 hipError_t launch_compose(const ComposeParams& p, hipStream_t s, const DitherArgs& d = DitherArgs());
 // k_prepost.hip compose_canvas_kernel: compose_kernel's per-pixel sums for the same rect of p (x0..x1, y0..y1; p.dst / p.deep unused) left
 // unquantised as fp32 RGB planes: canvas[c][Y][X], plane stride outW * outH (the input of the resize, renderResized)
@@ -313,7 +316,11 @@ constexpr int kResampleRows = 16, kResampleCols = 64;
 constexpr int kComposeRows = W2X_COMPOSE_ROWS, kComposeThreads = W2X_COMPOSE_THREADS;
 // host: the largest input row span of an output row tile; rows_above = 1: of the tile and the output row above it (top-left sited 4:2:0 chroma)
 int resample_rows_max(const int* fy, int outH, int inH, int ky, int rows_above = 0);
-hipError_t launch_resample(const ResampleParams& p, hipStream_t s, const DitherArgs& d = DitherArgs(), const LightArgs& l = LightArgs());
+// the same for the tables of an edged resize (resize_taps_edge: full support, rows below 0 and past inH): nothing is cut at inH
+int resample_rows_max_edge(const int* fy, int outH, int ky);
+// e (launch_resample, _rgba, _planar, _planar_rgba): mode Wrap or Mirror - the tables are resize_taps_edge's, rows_max resample_rows_max_edge's, and
+// every input index of pass 1 goes through the rule; Replicate - the default - launches the kernel that never heard of it
+hipError_t launch_resample(const ResampleParams& p, hipStream_t s, const DitherArgs& d = DitherArgs(), const LightArgs& l = LightArgs(), const EdgeArgs& e = EdgeArgs());
 // YUV 4:2:0 frames (Img2Img::renderYuv): three planes - Y of rows x cols, U and V of ceil(rows/2) x ceil(cols/2) - with 8-bit (uint8) or 10-bit
 // (uint16, low 10 bits) samples; steps in bytes.  Chroma siting (siting): kYuvLeft, MPEG-2 "left", chroma (i, j) at luma (x = 2j, y = 2i + 1/2);
 // kYuvCenter (JPEG, MPEG-1) at (2j + 1/2, 2i + 1/2); kYuvTopLeft (BT.2020) at (2j, 2i).  Per subsampled axis a siting is one of two rules, co-sited or centred:
@@ -400,7 +407,8 @@ struct AlphaBleedParams {
     unsigned* minmax = nullptr;
 };
 constexpr int kBleedTileW = 64, kBleedTileH = 32, kBleedMaxRadius = 16;
-hipError_t launch_alpha_bleed(const AlphaBleedParams& p, hipStream_t s);
+// wrap (kEdgeWrap): the eight neighbours are taken through the rule, so all eight always exist; false: a neighbour outside the frame does not exist
+hipError_t launch_alpha_bleed(const AlphaBleedParams& p, hipStream_t s, bool wrap = false);
 // gather_rgba_kernel: gather_kernel on the two planes of an RGBA frame.  A slot of this table says which plane it reads in `valid`: 1 the BGR frame
 // (exactly gather_kernel), 2 the alpha plane as the gray pixel (a, a, a, 0), a = u8 * fl32(1/255); 0 stays the zero-pad slot.
 struct GatherRgbaParams {
@@ -412,7 +420,7 @@ struct GatherRgbaParams {
     int B = 0, T = 0;
 };
 constexpr int kSlotColour = 1, kSlotAlpha = 2;
-hipError_t launch_gather_rgba(const GatherRgbaParams& p, hipStream_t s);
+hipError_t launch_gather_rgba(const GatherRgbaParams& p, hipStream_t s, int edge = kEdgeReplicate);
 // compose_rgba_kernel: compose_pixel_sums over the colour tiles (c.tiles) quantised to B, G, R, and over the alpha tiles (alpha_tiles, the same grid, slot 0 =
 // tile 0) whose green sum quantised the same way is A; one dword B | G << 8 | R << 16 | A << 24 per pixel into c.dst (c.dst_step bytes per row, 4-byte
 // aligned).  alpha_tiles == nullptr: A = alpha_value everywhere (a uniform plane whose tiles were not run).
@@ -444,7 +452,7 @@ struct ResampleRgbaParams {
     int rows_max = 0;
     int uniform = 0; unsigned alpha_value = 255;
 };
-hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s, const DitherArgs& d = DitherArgs(), const LightArgs& l = LightArgs());
+hipError_t launch_resample_rgba(const ResampleRgbaParams& p, hipStream_t s, const DitherArgs& d = DitherArgs(), const LightArgs& l = LightArgs(), const EdgeArgs& e = EdgeArgs());
 // Frames of planes (k_planar.hip): `n` planes of rows x cols samples - uint8 (bits 8), little-endian uint16 with the code in the low bits (10 / 12 / 16) or
 // float32 of nominal [0, 1] (32) - each with its own pointer and step in bytes; u16 / f32 samples aligned to their size.  n = 3: planar RGB frames (renderPlanar,
 // DESIGN 9h), planes R, G, B.  n = 1: gray frames (renderGray) of 8 or 16 bits: one sample per pixel on both sides, the result the green channel of
@@ -465,7 +473,7 @@ struct GatherPlanarParams {
     const TileSlot* slots = nullptr;
     int B = 0, T = 0;
 };
-hipError_t launch_gather_planar(const GatherPlanarParams& p, hipStream_t s);
+hipError_t launch_gather_planar(const GatherPlanarParams& p, hipStream_t s, int edge = kEdgeReplicate);
 // compose_planes_kernel: compose_kernel over the whole canvas of c (c.dst / c.deep / x0..y1 unused): the three sums of compose_pixel_sums - one plane: the
 // green sum - into the planes of dst (c.outH x c.outW), integer sat(rint(x * (2^bits - 1))), float min(max(x, 0), 1) stored as fp32
 struct ComposePlanarParams {
@@ -490,7 +498,7 @@ struct GatherPxParams {
     const TileSlot* slots = nullptr;
     int B = 0, T = 0;
 };
-hipError_t launch_gather_px(const GatherPxParams& p, hipStream_t s);
+hipError_t launch_gather_px(const GatherPxParams& p, hipStream_t s, int edge = kEdgeReplicate);
 // compose_canvas_gray_kernel: the green sums of compose_pixel_sums over the whole canvas of p (x0..y1, dst, deep unused) unquantised as one fp32 plane
 // canvas[Y][X] of outH x outW: the canvas of a resized gray frame (a resized planar frame has compose_canvas_kernel's)
 hipError_t launch_compose_canvas_gray(const ComposeParams& p, float* canvas, hipStream_t s, const LightArgs& l = LightArgs());
@@ -504,7 +512,7 @@ struct ResamplePlanarParams {
     int rows_max = 0;
     PlanarPlanes dst;
 };
-hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s, const DitherArgs& d = DitherArgs(), const LightArgs& l = LightArgs());
+hipError_t launch_resample_planar(const ResamplePlanarParams& p, hipStream_t s, const DitherArgs& d = DitherArgs(), const LightArgs& l = LightArgs(), const EdgeArgs& e = EdgeArgs());
 // Planar RGBA frames (renderPlanarRgba; k_planar_rgba.hip): four planes R, G, B, A of one sample type, laid out like PlanarPlanes' three.
 struct RgbaPlanes {
     uint8_t* p[4] = {nullptr, nullptr, nullptr, nullptr}; size_t step[4] = {0, 0, 0, 0};
@@ -523,7 +531,7 @@ struct AlphaBleedPlanesParams {
     unsigned* minmax = nullptr;
 };
 inline unsigned alpha_key_top(int bits) { return bits == 32 ? 0x3F800000u : (1u << bits) - 1u; }
-hipError_t launch_alpha_bleed_planes(const AlphaBleedPlanesParams& p, hipStream_t s);
+hipError_t launch_alpha_bleed_planes(const AlphaBleedPlanesParams& p, hipStream_t s, bool wrap = false);
 // gather_planes_rgba_kernel: gather_rgba_kernel's slots (kSlotColour / kSlotAlpha) over those planes with gather_planes_kernel's samples: a colour slot reads
 // make_px(r, g, b) from colour[0..2], an alpha slot (a, a, a) from the alpha plane
 struct GatherPlanarRgbaParams {
@@ -534,7 +542,7 @@ struct GatherPlanarRgbaParams {
     const TileSlot* slots = nullptr;
     int B = 0, T = 0;
 };
-hipError_t launch_gather_planar_rgba(const GatherPlanarRgbaParams& p, hipStream_t s);
+hipError_t launch_gather_planar_rgba(const GatherPlanarRgbaParams& p, hipStream_t s, int edge = kEdgeReplicate);
 // compose_planes_rgba_kernel: compose_planes_kernel's three sums over the colour tiles (c.tiles) into dst.p[0..2] and its green sum over the alpha tiles (the same
 // grid, slot 0 = tile 0) into dst.p[3], quantised alike; alpha_tiles == nullptr: the plane is alpha_value (in [0, 1]) quantised like a sum.
 struct ComposePlanarRgbaParams {
@@ -555,7 +563,7 @@ struct ResamplePlanarRgbaParams {
     RgbaPlanes dst;
     int uniform = 0; float alpha_value = 1.f;
 };
-hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStream_t s, const DitherArgs& d = DitherArgs(), const LightArgs& l = LightArgs());
+hipError_t launch_resample_planar_rgba(const ResamplePlanarRgbaParams& p, hipStream_t s, const DitherArgs& d = DitherArgs(), const LightArgs& l = LightArgs(), const EdgeArgs& e = EdgeArgs());
 // k_resample_yuv.hip: resample_kernel's resize of the fp32 RGB canvas (same tap tables, same rows_max, the same two passes) with compose_yuv_kernel's
 // encoding behind it instead of the BGR quantisation: the resized R, G, B clamped to [0, 1] and written as the YUV planes of dst (outH x outW =
 // dst.rows x dst.cols), Y per pixel; 4:2:0: Cb / Cr of the RGB filtered (1/4, 1/2, 1/4) x (1/2, 1/2) onto each chroma site (renderYuvResized)

@@ -62,6 +62,25 @@ template <typename Launch> hipError_t for_modes(const DitherArgs& d, const Light
     return for_dither(d, [&](auto m) { return lin ? launch(m, d, l) : launch(m, d); });
 }
 
+// launch(std::integral_constant<int, E>()) for the edge mode of a gather launch: the switch from the run-time mode to the kernel instantiation
+template <typename Launch> hipError_t for_edge(int edge, Launch launch) {
+    if (edge == kEdgeReplicate) return launch(std::integral_constant<int, kEdgeReplicate>());
+    if (edge == kEdgeWrap) return launch(std::integral_constant<int, kEdgeWrap>());
+    if (edge == kEdgeMirror) return launch(std::integral_constant<int, kEdgeMirror>());
+    return hipErrorInvalidValue;                                         // no kernel for it: an error, never the replicating kernel
+}
+// for_modes with the edge mode of a resize launch: Wrap and Mirror end the pack with one EdgeArgs, which names the edged instantiation; Replicate adds nothing
+template <typename Launch> hipError_t for_light(const LightArgs& l, const EdgeArgs& e, Launch launch) {
+    if (!edge_mode_ok(e.mode)) return hipErrorInvalidValue;
+    if (e.mode == kEdgeReplicate) return for_light(l, launch);
+    return for_light(l, [&](auto m, const auto&... extra) { return launch(m, extra..., e); });
+}
+template <typename Launch> hipError_t for_modes(const DitherArgs& d, const LightArgs& l, const EdgeArgs& e, Launch launch) {
+    if (!edge_mode_ok(e.mode)) return hipErrorInvalidValue;
+    if (e.mode == kEdgeReplicate) return for_modes(d, l, launch);
+    return for_modes(d, l, [&](auto m, const auto&... extra) { return launch(m, extra..., e); });
+}
+
 // ---- the sample types: what a plane holds per pixel.  `maxcode` is 2^bits - 1 and `inv` fl32(1 / maxcode), both made on the host (launch_*).
 struct U8 { typedef uint8_t T; };
 struct U16 { typedef uint16_t T; };
@@ -132,9 +151,9 @@ __device__ __forceinline__ void store4(uint8_t* row, int X, int np, const float 
     }
 }
 
-// ---- gather_kernel's loop: tile pixel i of B tiles of T x T, the slot lookup, the zero pixel of a pad slot, the TTA source map and the replicate clamp to a
-// frame of rows x cols.  load(slot, fy, fx) makes the tile pixel P of frame pixel (fy, fx).
-template <typename P, typename Load>
+// ---- gather_kernel's loop: tile pixel i of B tiles of T x T, the slot lookup, the zero pixel of a pad slot, the TTA source map and the edge rule E (edge_src;
+// kEdgeReplicate: the replicate clamp) onto a frame of rows x cols.  load(slot, fy, fx) makes the tile pixel P of frame pixel (fy, fx).
+template <typename P, int E = kEdgeReplicate, typename Load>
 __device__ __forceinline__ void gather_loop(const TileSlot* slots, int B, int T, int rows, int cols, void* out, Load load) {
     const long total = (long)B * T * T;
     for (long i = (long)blockIdx.x * kGatherThreads + threadIdx.x; i < total; i += (long)gridDim.x * kGatherThreads) {
@@ -146,8 +165,8 @@ __device__ __forceinline__ void gather_loop(const TileSlot* slots, int B, int T,
         if (sl.valid) {
             int sy, sx;
             aug_src(sl.aug, T - 1, y, x, sy, sx);
-            int fy = min(max(sl.y + sy, 0), rows - 1);
-            int fx = min(max(sl.x + sx, 0), cols - 1);
+            int fy = edge_src<E>(sl.y + sy, rows);
+            int fx = edge_src<E>(sl.x + sx, cols);
             v = load(sl, fy, fx);
         }
         *((P*)out + i) = v;
@@ -219,13 +238,16 @@ __device__ __forceinline__ void compose_quad_sums(const CP& p, int X, int Y, int
 // plane q, input row r, tile column c goes to h[slot(q, r, c)].  kHalo: a 65th column, c == kRsCols, holds output column ox0 - 1 (clamped at 0), which the
 // 4:2:0 and 4:2:2 kernels' chroma sites reach; where it lies is the slot's business (k_resample_yuv.hip).  The loop runs nr * 65 items then, nr * 64 without.
 // kAbove: the rows start with those of output row oy0 - 1 (clamped at 0), the row halo of top-left sited chroma (resample_rows_max(.., 1) rows).
-template <int NP, bool kHalo, bool kAbove = false, typename RP, typename Slot>
-__device__ __forceinline__ int resample_pass1_to(const RP& p, float* h, Slot slot) {
+// kEdge: the tables are resize_taps_edge's - every output has its full support, fx / fy may be negative and f + k may pass the canvas - and every
+// input index goes through the rule of mode `edge`: column index(f + k, inW), LDS row r holds canvas row index(r0 + r, inH), nr is not cut at inH (on a tiny
+// canvas the same input row may fill several LDS rows).  false: the code below is the code it always was.
+template <int NP, bool kHalo, bool kAbove = false, bool kEdge = false, typename RP, typename Slot>
+__device__ __forceinline__ int resample_pass1_to(const RP& p, float* h, Slot slot, int edge = kEdgeReplicate) {
     constexpr int kCols = kRsCols + (kHalo ? 1 : 0);
     const int ox0 = blockIdx.x * kRsCols, oy0 = blockIdx.y * kRsRows;
     const int tw = min(kRsCols, p.outW - ox0), th = min(kRsRows, p.outH - oy0);
     const int r0 = p.fy[kAbove ? max(oy0 - 1, 0) : oy0];
-    const int nr = min(p.inH, p.fy[oy0 + th - 1] + p.ky) - r0;           // <= rows_max (resample_rows_max)
+    const int nr = (kEdge ? p.fy[oy0 + th - 1] + p.ky : min(p.inH, p.fy[oy0 + th - 1] + p.ky)) - r0;   // <= rows_max (resample_rows_max / _edge)
     const size_t plane = (size_t)p.inW * p.inH;
     for (int i = threadIdx.x; i < nr * kCols; i += kRsThreads) {
         const int r = i / kCols, c = i % kCols;
@@ -234,13 +256,23 @@ __device__ __forceinline__ int resample_pass1_to(const RP& p, float* h, Slot slo
         for (int q = 0; q < NP; ++q) a[q] = 0.f;
         if (c < tw || (kHalo && c == kRsCols)) {
             const int X = kHalo && c == kRsCols ? max(ox0 - 1, 0) : ox0 + c, f = p.fx[X];
-            const int n = min(p.kx, p.inW - f);
             const float* w = p.wx + (size_t)X * p.kx;
-            const float* s = p.canvas + (size_t)(r0 + r) * p.inW + f;
-            for (int k = 0; k < n; ++k) {
-                const float wk = w[k];
+            if constexpr (kEdge) {
+                const float* s = p.canvas + (size_t)edge_index_dev(edge, r0 + r, p.inH) * p.inW;
+                for (int k = 0; k < p.kx; ++k) {
+                    const float wk = w[k];
+                    const int x = edge_index_dev(edge, f + k, p.inW);
 #pragma unroll
-                for (int q = 0; q < NP; ++q) a[q] += wk * s[q * plane + k];
+                    for (int q = 0; q < NP; ++q) a[q] += wk * s[q * plane + x];
+                }
+            } else {
+                const int n = min(p.kx, p.inW - f);
+                const float* s = p.canvas + (size_t)(r0 + r) * p.inW + f;
+                for (int k = 0; k < n; ++k) {
+                    const float wk = w[k];
+#pragma unroll
+                    for (int q = 0; q < NP; ++q) a[q] += wk * s[q * plane + k];
+                }
             }
         }
 #pragma unroll
@@ -249,14 +281,15 @@ __device__ __forceinline__ int resample_pass1_to(const RP& p, float* h, Slot slo
     return r0;
 }
 // the plain layout, no halo
-template <int NP, typename RP>
-__device__ __forceinline__ int resample_pass1(const RP& p, float* h) {
+template <int NP, bool kEdge = false, typename RP>
+__device__ __forceinline__ int resample_pass1(const RP& p, float* h, int edge = kEdgeReplicate) {
     const int rm = p.rows_max;
-    return resample_pass1_to<NP, false>(p, h, [rm](int q, int r, int c) { return (q * rm + r) * kRsCols + c; });
+    return resample_pass1_to<NP, false, false, kEdge>(p, h, [rm](int q, int r, int c) { return (q * rm + r) * kRsCols + c; }, edge);
 }
 // Pass 2: the rows of LDS filtered vertically, four output pixels (X .. X + 3 of row Y, np of them inside the frame) per thread: a[q] their sums of plane q.
-// false: the thread has no pixel to store.
-template <int NP, typename RP>
+// false: the thread has no pixel to store.  kEdge: every output row has its ky taps in LDS (pass 1 loaded the rows past the canvas through the rule), so none
+// is cut at inH; the arithmetic and its order are the same.
+template <int NP, bool kEdge = false, typename RP>
 __device__ __forceinline__ bool resample_pass2(const RP& p, const float* h, int r0, float4v (&a)[NP], int& X, int& Y, int& np) {
     const int ox0 = blockIdx.x * kRsCols, oy0 = blockIdx.y * kRsRows;
     const int th = min(kRsRows, p.outH - oy0);
@@ -267,7 +300,7 @@ __device__ __forceinline__ bool resample_pass2(const RP& p, const float* h, int 
     if (np <= 0) return false;
     const int rm = p.rows_max;
     const int f = p.fy[Y];
-    const int n = min(p.ky, p.inH - f);
+    const int n = kEdge ? p.ky : min(p.ky, p.inH - f);
     const float* w = p.wy + (size_t)Y * p.ky;
 #pragma unroll
     for (int q = 0; q < NP; ++q) a[q] = (float4v){0.f, 0.f, 0.f, 0.f};

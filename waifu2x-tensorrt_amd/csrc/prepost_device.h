@@ -30,6 +30,24 @@ __device__ __forceinline__ void aug_src(int k, int n, int y, int x, int& sy, int
         case 7: sy = x; sx = y; break;              // flip1 then rot90
     }
 }
+// The edge rule (edge.h states it): the source index of frame coordinate i in a dimension of n >= 1 samples, for any i.  E is a template parameter of
+// every gather of the RGB family; its kEdgeReplicate instantiation is the clamp the kernels always had, instruction for instruction.  Wrap and Mirror fold as
+// often as needed (one signed remainder): a tile border may be several times a small frame.
+template <int E>
+__device__ __forceinline__ int edge_src(int i, int n) {
+    if constexpr (E != kEdgeReplicate) { if ((unsigned)i < (unsigned)n) return i; }   // (inside the frame, which is nearly every call: no division)
+    if constexpr (E == kEdgeWrap) { const int r = i % n; return r < 0 ? r + n : r; }
+    else if constexpr (E == kEdgeMirror) {
+        if (n == 1) return 0;
+        const int p = 2 * (n - 1);
+        int r = i % p;
+        if (r < 0) r += p;
+        return r < n ? r : p - r;
+    }
+    else return min(max(i, 0), n - 1);
+}
+// the same with the mode as data (the edged resize kernels and the wrapped bleed: one instantiation for Wrap and Mirror)
+__device__ __forceinline__ int edge_index_dev(int mode, int i, int n) { return mode == kEdgeWrap ? edge_src<kEdgeWrap>(i, n) : mode == kEdgeMirror ? edge_src<kEdgeMirror>(i, n) : edge_src<kEdgeReplicate>(i, n); }
 // source coordinate inside the network output for pixel (y,x) of the de-augmented tile (reverseAugmentation)
 __device__ __forceinline__ void deaug_src(int k, int n, int y, int x, int& sy, int& sx) {
     switch (k) {
@@ -69,11 +87,29 @@ __device__ __forceinline__ LightArgs light_of() { return LightArgs(); }
 __device__ __forceinline__ LightArgs light_of(const DitherArgs&) { return LightArgs(); }
 __device__ __forceinline__ const LightArgs& light_of(const LightArgs& l) { return l; }
 __device__ __forceinline__ const LightArgs& light_of(const DitherArgs&, const LightArgs& l) { return l; }
+// Edge modes: the pack of a resize kernel may end in one EdgeArgs behind all that - the kernel whose pass 1 takes every input index through the
+// rule; edge_on<D...> is the compile-time switch and edge_of(dzs...) the mode, or a default nobody reads.  A pack without it names the kernel it always named.
+__device__ __forceinline__ DitherArgs dither_of(const EdgeArgs&) { return DitherArgs(); }
+__device__ __forceinline__ const DitherArgs& dither_of(const DitherArgs& d, const EdgeArgs&) { return d; }
+__device__ __forceinline__ DitherArgs dither_of(const LightArgs&, const EdgeArgs&) { return DitherArgs(); }
+__device__ __forceinline__ const DitherArgs& dither_of(const DitherArgs& d, const LightArgs&, const EdgeArgs&) { return d; }
+__device__ __forceinline__ LightArgs light_of(const EdgeArgs&) { return LightArgs(); }
+__device__ __forceinline__ LightArgs light_of(const DitherArgs&, const EdgeArgs&) { return LightArgs(); }
+__device__ __forceinline__ const LightArgs& light_of(const LightArgs& l, const EdgeArgs&) { return l; }
+__device__ __forceinline__ const LightArgs& light_of(const DitherArgs&, const LightArgs& l, const EdgeArgs&) { return l; }
+__device__ __forceinline__ EdgeArgs edge_of() { return EdgeArgs(); }
+template <typename A, typename... R> __device__ __forceinline__ EdgeArgs edge_of(const A& a, const R&... r) {
+    if constexpr (std::is_same<A, EdgeArgs>::value) return a;
+    else return edge_of(r...);
+}
 template <typename... D> constexpr bool light_on = (std::is_same<D, LightArgs>::value || ...);
+template <typename... D> constexpr bool edge_on = (std::is_same<D, EdgeArgs>::value || ...);
+template <int M> constexpr int kLightAt = (M == kDitherNone ? 0 : 1);                  // where the LightArgs of a pack stands
 template <int M, typename... D> constexpr bool dither_pack_ok =
-    sizeof...(D) == (M == kDitherNone ? 0 : 1) + (light_on<D...> ? 1 : 0) &&
+    sizeof...(D) == (M == kDitherNone ? 0 : 1) + (light_on<D...> ? 1 : 0) + (edge_on<D...> ? 1 : 0) &&
     (M == kDitherNone || std::is_same<std::tuple_element_t<0, std::tuple<D..., void>>, DitherArgs>::value) &&
-    (!light_on<D...> || std::is_same<std::tuple_element_t<sizeof...(D) == 0 ? 0 : sizeof...(D) - 1, std::tuple<D..., void>>, LightArgs>::value);
+    (!light_on<D...> || std::is_same<std::tuple_element_t<kLightAt<M>, std::tuple<D..., void, void>>, LightArgs>::value) &&
+    (!edge_on<D...> || std::is_same<std::tuple_element_t<sizeof...(D) == 0 ? 0 : sizeof...(D) - 1, std::tuple<D..., void>>, EdgeArgs>::value);
 // The two curve functions on the device (light.h states them and their roundings; the power goes through the hardware's log2 / exp2, v_log_f32 / v_exp_f32,
 // whose arguments here are never subnormal: the base of decode is at least 1 / (1 + a) > 0.9 a, the argument of encode's power at least t / k).  The curve is
 // data: both branches are computed and one is selected.  e and l are in [0, 1] - the callers clamp.  Contraction is off: every product and sum below is the

@@ -216,8 +216,41 @@ ResizeTaps resize_taps(int in, int out, int filter) {
     return t;
 }
 
-bool alpha_bleed(const uint8_t* bgr, size_t bgr_step, const uint8_t* alpha, size_t alpha_step, int rows, int cols, int radius, uint8_t* out, size_t out_step) {
-    if (!bgr || !alpha || !out || rows <= 0 || cols <= 0 || radius < 0 || radius > 16) return false;
+ResizeTaps resize_taps_edge(int in, int out, int filter, int mode) {
+    if (!edge_mode_ok(mode)) return ResizeTaps();
+    if (mode == kEdgeReplicate) return resize_taps(in, out, filter);
+    ResizeTaps t;
+    if (in <= 0 || out <= 0 || (filter != 0 && filter != 1)) return t;
+    const double scale = (double)in / out;
+    const double half = filter == 0 ? 2.0 : 1.0;
+    const double support = scale >= 1.0 ? half * scale : half;
+    const double inv = scale >= 1.0 ? 1.0 / scale : 1.0;
+    t.taps = (int)std::ceil(support) * 2 + 1;
+    t.first.assign(out, 0); t.w.assign((size_t)out * t.taps, 0.f);
+    auto f = [&](double x) {                                          // (resize_taps' two filters)
+        x = std::fabs(x);
+        if (filter == 1) return x < 1.0 ? 1.0 - x : 0.0;
+        const double a = -0.5;
+        if (x < 1.0) return ((a + 2.0) * x - (a + 3.0)) * x * x + 1.0;
+        if (x < 2.0) return ((a * x - 5.0 * a) * x + 8.0 * a) * x - 4.0 * a;
+        return 0.0;
+    };
+    std::vector<double> w(t.taps);
+    for (int i = 0; i < out; ++i) {
+        const double center = scale * (i + 0.5);
+        const long x0 = (long)std::floor(center - support + 0.5);      // (resize_taps truncates, which is floor where it does not clip)
+        const long n = std::min<long>((long)std::floor(center + support + 0.5) - x0, t.taps);
+        double total = 0.0;
+        for (long k = 0; k < n; ++k) { w[k] = f((k + x0 - center + 0.5) * inv); total += w[k]; }
+        t.first[i] = (int)x0;
+        for (long k = 0; k < n; ++k) t.w[(size_t)i * t.taps + k] = (float)(total != 0.0 ? w[k] / total : w[k]);
+    }
+    return t;
+}
+
+bool alpha_bleed(const uint8_t* bgr, size_t bgr_step, const uint8_t* alpha, size_t alpha_step, int rows, int cols, int radius, uint8_t* out, size_t out_step, int edge) {
+    if (!bgr || !alpha || !out || rows <= 0 || cols <= 0 || radius < 0 || radius > 16 || !edge_mode_ok(edge)) return false;
+    const bool wrap = edge == kEdgeWrap;
     if (bgr_step < (size_t)cols * 3 || out_step < (size_t)cols * 3 || alpha_step < (size_t)cols) return false;
     const size_t n_px = (size_t)rows * cols;
     std::vector<uint8_t> col(n_px * 3), col2, known(n_px), known2;
@@ -235,8 +268,10 @@ bool alpha_bleed(const uint8_t* bgr, size_t bgr_step, const uint8_t* alpha, size
                 unsigned n = 0, sum[3] = {0, 0, 0};
                 for (int dy = -1; dy <= 1; ++dy)
                     for (int dx = -1; dx <= 1; ++dx) {
-                        const int yy = y + dy, xx = x + dx;
-                        if ((dy == 0 && dx == 0) || yy < 0 || yy >= rows || xx < 0 || xx >= cols) continue;
+                        int yy = y + dy, xx = x + dx;
+                        if (dy == 0 && dx == 0) continue;
+                        if (wrap) { yy = edge_index(kEdgeWrap, yy, rows); xx = edge_index(kEdgeWrap, xx, cols); }
+                        else if (yy < 0 || yy >= rows || xx < 0 || xx >= cols) continue;
                         const size_t q = (size_t)yy * cols + xx;
                         if (!known[q]) continue;
                         ++n;
@@ -257,7 +292,7 @@ namespace {
 // alpha_bleed's loop on three planes of samples T (the state: three packed planes of clamped codes and the flags)
 template <typename T>
 void bleed_planes(const void* const colour[3], const size_t colour_steps[3], const void* alpha, size_t alpha_step, int rows, int cols, unsigned maxcode, int radius,
-                  void* const out[3], const size_t out_steps[3]) {
+                  void* const out[3], const size_t out_steps[3], bool wrap) {
     const size_t n_px = (size_t)rows * cols;
     auto at = [](const void* base, size_t step, int y, int x) { return ((const T*)((const uint8_t*)base + (size_t)y * step))[x]; };
     std::vector<T> col(n_px * 3), col2;
@@ -278,8 +313,10 @@ void bleed_planes(const void* const colour[3], const size_t colour_steps[3], con
                 uint32_t n = 0, sum[3] = {0, 0, 0};
                 for (int dy = -1; dy <= 1; ++dy)
                     for (int dx = -1; dx <= 1; ++dx) {
-                        const int yy = y + dy, xx = x + dx;
-                        if ((dy == 0 && dx == 0) || yy < 0 || yy >= rows || xx < 0 || xx >= cols) continue;
+                        int yy = y + dy, xx = x + dx;
+                        if (dy == 0 && dx == 0) continue;
+                        if (wrap) { yy = edge_index(kEdgeWrap, yy, rows); xx = edge_index(kEdgeWrap, xx, cols); }
+                        else if (yy < 0 || yy >= rows || xx < 0 || xx >= cols) continue;
                         const size_t q = (size_t)yy * cols + xx;
                         if (!known[q]) continue;
                         ++n;
@@ -301,8 +338,9 @@ void bleed_planes(const void* const colour[3], const size_t colour_steps[3], con
 }  // namespace
 
 bool alpha_bleed_planes(const void* const colour[3], const size_t colour_steps[3], const void* alpha, size_t alpha_step, int rows, int cols, int sample_bytes,
-                        unsigned maxcode, int radius, void* const out[3], const size_t out_steps[3]) {
-    if (!colour || !colour_steps || !alpha || !out || !out_steps || rows <= 0 || cols <= 0 || radius < 0 || radius > 16) return false;
+                        unsigned maxcode, int radius, void* const out[3], const size_t out_steps[3], int edge) {
+    if (!colour || !colour_steps || !alpha || !out || !out_steps || rows <= 0 || cols <= 0 || radius < 0 || radius > 16 || !edge_mode_ok(edge)) return false;
+    const bool wrap = edge == kEdgeWrap;
     if ((sample_bytes != 1 && sample_bytes != 2) || maxcode == 0 || maxcode > (sample_bytes == 1 ? 255u : 65535u)) return false;
     const size_t row = (size_t)cols * sample_bytes, mis = (size_t)sample_bytes - 1;
     if (alpha_step < row || ((((size_t)alpha) | alpha_step) & mis)) return false;
@@ -310,8 +348,8 @@ bool alpha_bleed_planes(const void* const colour[3], const size_t colour_steps[3
         if (!colour[ch] || !out[ch] || colour_steps[ch] < row || out_steps[ch] < row) return false;
         if ((((size_t)colour[ch]) | colour_steps[ch] | ((size_t)out[ch]) | out_steps[ch]) & mis) return false;
     }
-    if (sample_bytes == 1) bleed_planes<uint8_t>(colour, colour_steps, alpha, alpha_step, rows, cols, maxcode, radius, out, out_steps);
-    else bleed_planes<uint16_t>(colour, colour_steps, alpha, alpha_step, rows, cols, maxcode, radius, out, out_steps);
+    if (sample_bytes == 1) bleed_planes<uint8_t>(colour, colour_steps, alpha, alpha_step, rows, cols, maxcode, radius, out, out_steps, wrap);
+    else bleed_planes<uint16_t>(colour, colour_steps, alpha, alpha_step, rows, cols, maxcode, radius, out, out_steps, wrap);
     return true;
 }
 

@@ -7,6 +7,8 @@
 #include <cstdint>
 #include <vector>
 
+#include "edge.h"
+
 namespace w2x {
 
 struct Rect { int x, y, w, h; };
@@ -119,13 +121,22 @@ std::vector<float> tile_weight_mask(int which, int ovx, int ovy, int size);
 // its k-th weight (zero past the taps output i has).  filter: 0 bicubic, 1 bilinear.  taps = 0 for invalid arguments.
 struct ResizeTaps { int taps = 0; std::vector<int> first; std::vector<float> w; };
 ResizeTaps resize_taps(int in, int out, int filter);
+// The same under an edge mode (edge.h).  kEdgeReplicate: resize_taps, to the bit.  kEdgeWrap / kEdgeMirror: the taps are NOT clipped at the border -
+// every output has its full support, first[i] = floor(centre - support + 0.5) may be negative and first[i] + k may pass `in`; tap k reads the sample
+// edge_index(mode, first[i] + k, in); the weights are normalised over all taps.  This is the table torch's resampler has in the interior of a frame padded with
+// np.pad(mode = "wrap" / "reflect").  taps = 0 for invalid arguments, an unknown mode included.
+ResizeTaps resize_taps_edge(int in, int out, int filter, int mode);
 
 // Colour bleed under transparent pixels (RGBA frames), integer and exact.  bgr: rows x cols interleaved 8-bit BGR, alpha: rows x cols
 // bytes, radius R in [0, 16].  known_0(p) = alpha(p) > 0, col_0 = bgr.  Iteration it = 1..R reads state it - 1 and writes state it (Jacobi): a pixel unknown in
 // state it - 1 with n > 0 neighbours among its eight that lie inside the frame and are known in state it - 1 takes, per channel, (their sum + (n >> 1)) / n
 // and becomes known; every other pixel keeps colour and flag.  out = col_R (a pixel still unknown keeps its colour; R = 0, an all-zero and an all-non-zero
 // plane leave the frame unchanged; a known pixel never changes).  out may not alias bgr.  false (nothing written) for invalid arguments.
-bool alpha_bleed(const uint8_t* bgr, size_t bgr_step, const uint8_t* alpha, size_t alpha_step, int rows, int cols, int radius, uint8_t* out, size_t out_step);
+// edge: kEdgeWrap - the eight neighbours are taken through edge_index (all eight always exist; colour spreads across the joint of a texture that
+// tiles); kEdgeReplicate and kEdgeMirror - the rule above, a neighbour outside the frame does not exist (a reflected neighbour carries no new information).  An
+// unknown mode is an invalid argument.  The same for alpha_bleed_planes.
+bool alpha_bleed(const uint8_t* bgr, size_t bgr_step, const uint8_t* alpha, size_t alpha_step, int rows, int cols, int radius, uint8_t* out, size_t out_step,
+                 int edge = kEdgeReplicate);
 
 // alpha_bleed restated on planes of codes of any integer depth (planar RGBA frames).  colour[0..2] and alpha: planes of rows x cols samples of
 // sample_bytes (1: uint8, 2: uint16) with steps in bytes; maxcode = 2^bits - 1 (at most 65535, and 255 for one-byte samples).  Every code is first clamped to
@@ -133,6 +144,6 @@ bool alpha_bleed(const uint8_t* bgr, size_t bgr_step, const uint8_t* alpha, size
 // 16-bit codes fit a 32-bit sum.  out[0..2]: the three planes of state R (no plane of out may alias an input).  At one byte and maxcode 255 the planes are those
 // of alpha_bleed.  false (nothing written) for invalid arguments.
 bool alpha_bleed_planes(const void* const colour[3], const size_t colour_steps[3], const void* alpha, size_t alpha_step, int rows, int cols, int sample_bytes,
-                        unsigned maxcode, int radius, void* const out[3], const size_t out_steps[3]);
+                        unsigned maxcode, int radius, void* const out[3], const size_t out_steps[3], int edge = kEdgeReplicate);
 
 }  // namespace w2x

@@ -364,6 +364,17 @@ CHAIN_SYMBOLS = {
     "w2x_render_chained_planes": (_I, _CHAIN + _YUV + _YUV + [_I]),
     "w2x_render_chained_planes_resized": (_I, _CHAIN + _YUV + _YUV + [_I, _I]),
 }
+# The entries of include/w2x/c_api_edge.h, a table of their own likewise: (engine, mode), its getter, the rule without an engine (mode, i, n), the tap table
+# under a mode (w2x_resize_weights' arguments with the mode behind the filter) and the two host bleeds with the mode as their last argument.
+EDGE_SYMBOLS = {
+    "w2x_set_edge": (_I, [_P, _I]),
+    "w2x_get_edge": (_I, [_P]),
+    "w2x_edge_index": (_I, [_I, C.c_longlong, _I]),
+    "w2x_resize_weights_edge": (_I, [_I, _I, _I, _I, _P, _P, _I]),
+    "w2x_alpha_bleed_edge": (_I, [_P, _Z, _P, _Z, _I, _I, _I, _P, _Z, _I]),
+    "w2x_alpha_bleed_planes_edge": (_I, [_P, _P, _I, _I, _I, _I, _P, _P, _I]),
+}
+EDGE_MODES = {"replicate": 0, "wrap": 1, "mirror": 2}    # W2X_EDGE_REPLICATE .. _MIRROR (include/w2x/c_api_edge.h)
 CHAIN_REFUSALS = {1: "count", 2: "scaling", 3: "source", 4: "too_large", 5: "target", 6: "shrink"}    # W2X_CHAIN_COUNT .. _SHRINK
 _lib = None
 
@@ -377,7 +388,7 @@ def lib():
         raise W2xError(f"{lib_path} is missing - build it with `python -c 'import __graft_entry__ as g; g.build()'` "
                        "or `make -C waifu2x-tensorrt_amd` (there is no CPU fallback)")
     L = C.CDLL(lib_path)
-    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()) + list(PLANAR_SYMBOLS.items()) + list(RGBAP_SYMBOLS.items()) + list(YUV_RESIZED_SYMBOLS.items()) + list(YUV_SITED_SYMBOLS.items()) + list(DITHER_SYMBOLS.items()) + list(RESIZE_LIGHT_SYMBOLS.items()) + list(CHAIN_SYMBOLS.items()):
+    for name, (restype, argtypes) in list(SYMBOLS.items()) + list(GRAY_SYMBOLS.items()) + list(PLANAR_SYMBOLS.items()) + list(RGBAP_SYMBOLS.items()) + list(YUV_RESIZED_SYMBOLS.items()) + list(YUV_SITED_SYMBOLS.items()) + list(DITHER_SYMBOLS.items()) + list(RESIZE_LIGHT_SYMBOLS.items()) + list(CHAIN_SYMBOLS.items()) + list(EDGE_SYMBOLS.items()):
         fn = getattr(L, name)
         fn.restype, fn.argtypes = restype, argtypes
     _lib = L
@@ -828,6 +839,22 @@ class Img2Img:
     def resize_light(self) -> str:
         """the current setting's name (w2x_get_resize_light)"""
         return {v: k for k, v in RESIZE_LIGHTS.items()}[int(self._L.w2x_get_resize_light(self._h))]
+
+    def set_edge(self, mode="replicate") -> bool:
+        """What every following frame call of the RGB family reads beyond the frame edge (w2x_set_edge, c_api_edge.h states the rule): "replicate" - the edge
+        pixel repeated, the default -, "wrap" - the frame is one period of a texture that tiles - or "mirror" - reflection without repeating the edge sample -, or
+        the mode's number, which the engine checks.  It acts on the tiles' borders, on the colour bleed (wrap) and on the taps of the resized calls.  The setting
+        stays until it is changed and may be made before load().  YUV calls, strips and shards are refused under wrap and mirror.  An unknown name raises
+        ValueError; an unknown number returns False (message callback) and leaves the previous setting."""
+        if isinstance(mode, str):
+            if mode not in EDGE_MODES:
+                raise ValueError(f"edge mode must be one of {sorted(EDGE_MODES)}, got {mode!r}")
+            mode = EDGE_MODES[mode]
+        return bool(self._L.w2x_set_edge(self._h, int(mode)))
+
+    def edge(self) -> str:
+        """the current setting's name (w2x_get_edge)"""
+        return {v: k for k, v in EDGE_MODES.items()}[int(self._L.w2x_get_edge(self._h))]
 
     def resize_planes(self, planes, size, bits: int, filter: str = "bicubic", dst=None):
         """Test hook (w2x_resize_planes): three 2-D float32 planes of one shape (views with padded rows allowed) are taken as the canvas of a resized frame and
@@ -1369,21 +1396,42 @@ def tile_weights(which, ovx, ovy, size):
     return out
 
 
-def resize_weights(in_size: int, out_size: int, filter: str = "bicubic"):
-    """Tap tables of the resized renders along one axis (w2x_resize_weights) -> (first[out] int32, weights[out, taps] float32)."""
+def _edge_id(mode) -> int:
+    if isinstance(mode, str):
+        if mode not in EDGE_MODES:
+            raise ValueError(f"edge mode must be one of {sorted(EDGE_MODES)}, got {mode!r}")
+        return EDGE_MODES[mode]
+    return int(mode)
+
+
+def edge_index(mode, i: int, n: int) -> int:
+    """The edge rule (w2x_edge_index): the source index of coordinate i in a dimension of n samples under `mode`, a name of EDGE_MODES or its number; -1 for an
+    unknown number or n <= 0."""
+    return int(lib().w2x_edge_index(_edge_id(mode), int(i), int(n)))
+
+
+def resize_weights(in_size: int, out_size: int, filter: str = "bicubic", edge=None):
+    """Tap tables of the resized renders along one axis (w2x_resize_weights) -> (first[out] int32, weights[out, taps] float32).  edge (a name of EDGE_MODES or
+    its number): the table under that mode (w2x_resize_weights_edge) - under "wrap" and "mirror" every output has its full support, first may be negative and
+    first + k may pass in_size; tap k reads the sample edge_index(edge, first + k, in_size)."""
     L = lib()
     fid = _filter_id(filter)
-    taps = L.w2x_resize_weights(int(in_size), int(out_size), fid, None, None, 0)
+    if edge is None:
+        call = lambda *a: L.w2x_resize_weights(int(in_size), int(out_size), fid, *a)
+    else:
+        mode = _edge_id(edge)
+        call = lambda *a: L.w2x_resize_weights_edge(int(in_size), int(out_size), fid, mode, *a)
+    taps = call(None, None, 0)
     if taps <= 0:
         raise W2xError(f"invalid resize {in_size} -> {out_size}")
     first = np.zeros(out_size, np.int32)
     w = np.zeros((out_size, taps), np.float32)
-    if L.w2x_resize_weights(int(in_size), int(out_size), fid, first.ctypes.data, w.ctypes.data, w.size) != taps:
+    if call(first.ctypes.data, w.ctypes.data, w.size) != taps:
         raise W2xError("w2x_resize_weights failed")
     return first, w
 
 
-def alpha_bleed_planes(planes, radius: int, *, bits: int | None = None, order: str = "rgba"):
+def alpha_bleed_planes(planes, radius: int, *, bits: int | None = None, order: str = "rgba", edge=None):
     """The colour bleed of the planar RGBA renders on the host (w2x_alpha_bleed_rgbap): four 2-D uint8 or uint16 planes (bits=10 / 12 for codes in the low bits),
     radius 0..16 -> the three colour planes R, G, B with every code clamped to 2^bits - 1 and the colours of the visible pixels (clamped alpha > 0) spread
     under the others; integer and exact (tiles.h alpha_bleed_planes)."""
@@ -1393,8 +1441,9 @@ def alpha_bleed_planes(planes, radius: int, *, bits: int | None = None, order: s
         raise ValueError("Colour bleed takes integer samples.")
     src = [planes[k] for k in idx]
     out = tuple(np.empty(src[0].shape, src[0].dtype) for _ in range(3))
-    if not lib().w2x_alpha_bleed_rgbap((C.c_void_p * 4)(*[_data(p) for p in src]), (C.c_size_t * 4)(*[p.strides[0] for p in src]), src[0].shape[0], src[0].shape[1], bits,
-                                       int(radius), (C.c_void_p * 3)(*[_data(p) for p in out]), (C.c_size_t * 3)(*[p.strides[0] for p in out])):
+    args = ((C.c_void_p * 4)(*[_data(p) for p in src]), (C.c_size_t * 4)(*[p.strides[0] for p in src]), src[0].shape[0], src[0].shape[1], bits,
+            int(radius), (C.c_void_p * 3)(*[_data(p) for p in out]), (C.c_size_t * 3)(*[p.strides[0] for p in out]))
+    if not (lib().w2x_alpha_bleed_rgbap(*args) if edge is None else lib().w2x_alpha_bleed_planes_edge(*args, _edge_id(edge))):   # (edge: the bleed under that mode, c_api_edge.h)
         raise ValueError(f"alpha_bleed_planes refused planes of {src[0].shape} at radius {radius}")
     return out
 
@@ -1430,14 +1479,15 @@ def dither_rank(mode, phase: int, c: int, x: int, y: int) -> int:
     return int(lib().w2x_dither_rank(m, int(phase) & 0xFFFFFFFF, int(c), int(x), int(y)))
 
 
-def alpha_bleed(bgr: np.ndarray, alpha: np.ndarray, radius: int) -> np.ndarray:
+def alpha_bleed(bgr: np.ndarray, alpha: np.ndarray, radius: int, edge=None) -> np.ndarray:
     """The colour bleed of the RGBA renders on the host (w2x_alpha_bleed): bgr uint8 [rows, cols, 3], alpha uint8 [rows, cols], radius 0..16 -> the frame with
     the colours of the pixels of alpha > 0 spread `radius` pixels outward under the pixels of alpha == 0; raises for invalid arguments"""
     _frame_ok(bgr, 3, (np.uint8,), "bgr must be a uint8 [rows, cols, 3] array with packed pixels", empty_ok=True)
     if alpha.dtype != np.uint8 or alpha.shape != bgr.shape[:2] or (alpha.size and alpha.strides[1] != 1):
         raise ValueError("alpha must be a uint8 [rows, cols] array of the frame's size with packed rows")
     out = np.empty(bgr.shape, np.uint8)
-    if not lib().w2x_alpha_bleed(_data(bgr), bgr.strides[0], _data(alpha), alpha.strides[0], bgr.shape[0], bgr.shape[1], int(radius), _data(out), out.strides[0]):
+    args = (_data(bgr), bgr.strides[0], _data(alpha), alpha.strides[0], bgr.shape[0], bgr.shape[1], int(radius), _data(out), out.strides[0])
+    if not (lib().w2x_alpha_bleed(*args) if edge is None else lib().w2x_alpha_bleed_edge(*args, _edge_id(edge))):   # (edge: the bleed under that mode - "wrap" takes the neighbours round the frame)
         raise W2xError(f"invalid alpha bleed: a {bgr.shape[1]}x{bgr.shape[0]} frame at radius {radius}")
     return out
 
